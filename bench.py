@@ -3,16 +3,22 @@
 AdiSolver3D::TimeStep (+ UpdateBoundaries, + EvalDivError every 10th step, exactly the
 reference's time loop, FluidSolver3D.cpp:226-262) on the synthetic 256^3 fp32 box.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N = 1: one context on cuda:0.  N > 1 (launched by torch.distributed.run, one rank per
 GPU): the 256^3 box is cut into N x-slabs (strong scaling); halo planes, the cross-slab
 X solve and the 2-scalar error reduction go over RCCL inside libfs3d_hip.so; torch.distributed
 only carries the ncclUniqueId and the barrier / max-over-ranks timing.
 
-Prints ONE JSON line (rank 0).  `roofline` is measured live with HIP events on the
-library's stream over the timed region; `cpu_baseline` times the CPU oracle (a port of
-the reference's CPU path) on a bounded sample of the same workload on this host.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times K steps and prints
+the headline (`value` in Mcells/s, `ms_per_step`).  --dump-outputs DIR writes the fields
+u, v, w, T of the current layer after the last timed step as DIR/<name>.npy (float32 or
+float64 as --dtype): every cell of a grid up to DUMP_SAMPLE cells, else the same seeded
+sample of DUMP_SAMPLE cells per field in every run.  --full adds the secondary figures:
+`roofline` (HIP events on the library's stream over an instrumented pass of K more steps
+after the timed ones, the device copy rate, PMC traffic), the final divergence error,
+`cpu_baseline` (the CPU oracle, a port of the reference's CPU path, on a bounded sample of
+the same workload on this host) and `parity_check`.
 """
 import argparse
 import json
@@ -29,6 +35,32 @@ HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.29 
 RE, PR, LAMBDA = 200.0, 0.72, 1.4
 NUM_GLOBAL, NUM_LOCAL = 4, 2   # data/3D/**/*config.txt: num_global 4, num_local 2
 MGPU_TOL = 1e-6                # slab fields vs single-GPU fields (rel-L2): the bound of every one-card slab test
+DUMP_SAMPLE = 1 << 20          # --dump-outputs: cells per field (4 fields: 16 MB in fp32, 32 MB in fp64)
+DUMP_SEED = 20261016
+DUMP_FIELDS = ("u", "v", "w", "T")
+
+
+def dump_indices(cells):
+    """Flat cell indices (x slowest, z fastest) that --dump-outputs writes: every cell of a grid of up to DUMP_SAMPLE cells,
+    else a fixed seeded sample of DUMP_SAMPLE cells, sorted -- the same for every run of the same --size."""
+    if cells <= DUMP_SAMPLE:
+        return np.arange(cells)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(cells, DUMP_SAMPLE, replace=False))
+
+
+def slab_sample(fields, x0, plane, idx):
+    """The values at the global flat indices `idx` that fall into this rank's x-slab (fields: [x1 - x0, ny, nz] each, starting
+    at plane x0; plane = ny * nz cells), in the order of idx."""
+    lo = x0 * plane
+    hi = lo + fields[0].size
+    sel = idx[(idx >= lo) & (idx < hi)] - lo
+    return [np.ascontiguousarray(f).ravel()[sel] for f in fields]
+
+
+def write_outputs(path, arrays):
+    os.makedirs(path, exist_ok=True)
+    for name, a in zip(DUMP_FIELDS, arrays):
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def cpu_baseline(n, dt, steps, dtype=np.float32):
@@ -88,6 +120,29 @@ def parity_check(n, dt, steps, dtype, cpu_fields, kernel, device):
     return out
 
 
+def headline(args, world, n, sec, g, dt, kernels_ran, mgpu_check):
+    """The result line of a plain run: throughput of the timed steps and what was run."""
+    from cmc_fluid_solver_amd import grids
+    out = {
+        "metric": "Mcells/sec (FluidSolver3D step)", "value": round(n ** 3 * args.steps / sec / 1e6, 2),
+        "unit": "Mcells/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(sec / args.steps * 1e3, 4), "higher_is_better": True,
+        "scaling": "strong", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
+        "config": {"workload": "FluidSolver3D %d^3 %s empty box (shell NODE_BOUND, x=0 inflow valve U=1, x=max free "
+                               "outflow valve), Re 200 Pr 0.72 lambda 1.4, num_global 4, num_local 2, dt %.5g, "
+                               "UpdateBoundaries+TimeStep per step, EvalDivError every 10th step" % (n, args.dtype, dt),
+                   "grid": [n, n, n], "parallelism": "x-slab x%d" % world, "sweep_kernel_requested": args.kernel,
+                   "sweep_kernels_ran": kernels_ran,
+                   "node_in_fraction": round(float((g.type == grids.NODE_IN).mean()), 4)},
+    }
+    if args.dump_outputs:
+        out["outputs"] = {"dir": args.dump_outputs, "files": [f + ".npy" for f in DUMP_FIELDS],
+                          "cells_per_field": min(n ** 3, DUMP_SAMPLE), "seed": DUMP_SEED if n ** 3 > DUMP_SAMPLE else None}
+    if mgpu_check is not None:
+        out["multi_gpu_check"] = mgpu_check
+    return out
+
+
 def self_launch(n):
     """`python bench.py --gpus N` started plainly: run the N ranks under torch.distributed.run as a CHILD process (never exec: this
     pool forbids replacing a process image once anything touched the GPU, and nothing has yet), relay rank 0's JSON line, return
@@ -118,9 +173,15 @@ def main():
     ap.add_argument("--size", type=int, default=256, help="box edge (default 256: BASELINE configs[2])")
     ap.add_argument("--dtype", default="f32", choices=["f32", "f64"])
     ap.add_argument("--kernel", type=int, default=0, help="0 auto (partition kernels in fp32), 1 line, 2 pipe, 3 partition, 4 fastest bit-exact")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write u, v, w, T after the last timed step as DIR/<name>.npy (all cells, or a fixed seeded sample of a large grid)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the secondary figures: roofline, final divergence error, CPU baseline and parity check")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out cpu_baseline and parity_check")
     ap.add_argument("--cpu-steps", type=int, default=2)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args.gpus))         # before torch or the GPU is touched: the ranks are child processes
@@ -265,22 +326,45 @@ def main():
     for i in range(args.warmup):
         step(i)
     fence()
-    # HIP events around the kernel launches of the timed region -- of every 7th step (steps 0, 7, 14 of the default 20: 24 launches per sweep class): two events per launch cost a few microseconds
-    # each (52 per step: measured 4-5 % of the step), the per-class averages need a sample, not every launch
-    s.enable_timing(int(os.environ.get("FS3D_BENCH_EVENT_PERIOD", "7")))
     t0 = time.perf_counter()
     for i in range(args.steps):
         step(i)
     fence()
     sec = time.perf_counter() - t0
-    ms_cls, n_cls = s.last_step_timing()
-    s.enable_timing(False)
-    err, _ = s.eval_div_error(capi.LAYER_CUR)
     kernels_ran = s.last_sweep_kernels()
     if world > 1:
         t = torch.tensor([sec], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         sec = float(t.item())
+
+    if args.dump_outputs:
+        # the current layer after the last timed step; each rank contributes the sampled cells of its slab, in rank (= x) order
+        part = slab_sample(s.download_layer(capi.LAYER_CUR), x0, n * n, dump_indices(n ** 3))
+        if world > 1:
+            parts = [None] * world
+            dist.all_gather_object(parts, part)
+            part = [np.concatenate([p[j] for p in parts]) for j in range(len(DUMP_FIELDS))]
+        if rank == 0:
+            write_outputs(args.dump_outputs, part)
+
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline(args, world, n, sec, g, dt, kernels_ran, mgpu_check)))
+        s.close()
+        if world > 1:
+            dist.destroy_process_group()
+        return
+
+    err, _ = s.eval_div_error(capi.LAYER_CUR)
+    # roofline: HIP events around the kernel launches of an instrumented pass of --steps more steps after the timed ones -- of
+    # every 7th step (steps 0, 7, 14 of the default 20: 24 launches per sweep class): two events per launch cost a few
+    # microseconds each (52 per step: measured 4-5 % of the step), the per-class averages need a sample, not every launch
+    s.enable_timing(int(os.environ.get("FS3D_BENCH_EVENT_PERIOD", "7")))
+    for i in range(args.steps):
+        step(i)
+    fence()
+    ms_cls, n_cls = s.last_step_timing()
+    s.enable_timing(False)
 
     # what a plain device-to-device copy reaches on this card (read + write bytes per second): context for `peak`
     copy_gbps = None
@@ -329,19 +413,9 @@ def main():
                 traffic = pt.get(names[k])
         except Exception:
             traffic = None
-        out = {
-            "metric": "Mcells/sec (FluidSolver3D step)", "value": round(cells * args.steps / sec / 1e6, 2),
-            "unit": "Mcells/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(sec / args.steps * 1e3, 4), "higher_is_better": True,
-            "scaling": "strong", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
-            "config": {"workload": "FluidSolver3D %d^3 %s empty box (shell NODE_BOUND, x=0 inflow valve U=1, x=max free "
-                                   "outflow valve), Re 200 Pr 0.72 lambda 1.4, num_global 4, num_local 2, dt %.5g, "
-                                   "UpdateBoundaries+TimeStep per step, EvalDivError every 10th step" % (n, args.dtype, dt),
-                       "grid": [n, n, n], "parallelism": "x-slab x%d" % world, "sweep_kernel_requested": args.kernel,
-                       "sweep_kernels_ran": kernels_ran,
-                       "node_in_fraction": round(float((g.type == grids.NODE_IN).mean()), 4),
-                       "final_div_error": err},
-            "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+        out = headline(args, world, n, sec, g, dt, kernels_ran, mgpu_check)
+        out["config"]["final_div_error"] = err
+        out["roofline"] = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
                          "kernel": names[k], "avg_launch_ms": round(per_launch_ms, 4),
                          "device_copy_GBps": copy_gbps,
@@ -351,15 +425,12 @@ def main():
                          "per_class_ms_per_launch": {nm: round(ms_cls[j] / max(1, n_cls[j]), 4)
                                                      for j, nm in enumerate(names + ["other"])},
                          "launches": dict(zip(names + ["other"], n_cls)),
-                         "launches_timed": "HIP events around the launches of every %s-th step of the timed region" % os.environ.get("FS3D_BENCH_EVENT_PERIOD", "7"),
+                         "launches_timed": "HIP events around the launches of every %s-th step of an instrumented pass after the timed region" % os.environ.get("FS3D_BENCH_EVENT_PERIOD", "7"),
                          "step_frac_of_hbm_roofline_1760B": round(
                              (cells * 1760.0 * (esize / 4) * args.steps / sec / 1e9) / (HBM_PEAK_GBS * world), 4),
                          "step_frac_of_hbm_roofline_moved": round(
                              (cells * (1760.0 - 32.0 - 48.0 * NUM_GLOBAL - 16.0 * NUM_GLOBAL * (3 * NUM_LOCAL * skip + (skip_x - skip) * NUM_LOCAL)) * (esize / 4) * args.steps / sec / 1e9)
-                             / (HBM_PEAK_GBS * world), 4)},
-        }
-        if mgpu_check is not None:
-            out["multi_gpu_check"] = mgpu_check
+                             / (HBM_PEAK_GBS * world), 4)}
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"], cpu_fields = cpu_baseline(n, dt, args.cpu_steps, dtype)
             out["parity_check"] = parity_check(n, dt, args.cpu_steps, dtype, cpu_fields, args.kernel, local_rank)

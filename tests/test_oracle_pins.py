@@ -1,7 +1,8 @@
 """CPU tests of the oracle (no GPU).
 
 PINNED TO THE REFERENCE ITSELF (oracle/_ref = the reference's own Common/Algorithms.h and
-Common/Geometry.h compiled as they lie, see oracle/Makefile):
+Common/Geometry.h compiled as they lie, see oracle/Makefile; its results on the inputs below are stored in
+tests/golden/ref_pins.npz by tests/golden/make_ref_pins.py, and checked against the live library when oracle/_ref is built):
   - SolveTridiagonal (fp32 and fp64), bit for bit;
   - FluidParams (both constructors) and AlignBy32.
 PINNED TO REFERENCE OUTPUTS RECORDED IN SURVEY.md (the reference binary run by the survey):
@@ -11,7 +12,9 @@ by the reference's own translation units (oracle/Makefile target ref_full).  The
 self-generated golden vectors of BuildMatrix/DissFunc/merge/EvalDivError below remain as unit-level checks of the restatement.
 """
 import ctypes as C
+import json
 import os
+import sys
 
 import numpy as np
 import pytest
@@ -20,39 +23,52 @@ from cmc_fluid_solver_amd import capi, grids
 from oracle import oracle as O
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-needs_ref = pytest.mark.skipif(O.ref_lib() is None, reason="oracle/_ref not built (reference tree absent)")
+sys.path.insert(0, GOLD)
+import make_ref_pins as RP  # noqa: E402  (the inputs of the pinned cases)
+
+PINS = np.load(os.path.join(GOLD, "ref_pins.npz"))
 
 
-@needs_ref
+def _live():
+    """The reference's own pieces when oracle/_ref is built (reference tree present), else None: the stored results suffice."""
+    return O.ref_lib()
+
+
 @pytest.mark.parametrize("dtype,ct,name", [(np.float32, C.c_float, "f32"), (np.float64, C.c_double, "f64")])
 def test_thomas_is_the_reference_thomas(dtype, ct, name):
-    rl = O.ref_lib()
-    rng = np.random.default_rng(1)
-    for n in (2, 3, 5, 64, 257):
-        for rep in range(5):
-            a = rng.uniform(-1, 1, n).astype(dtype); c = rng.uniform(-1, 1, n).astype(dtype)
-            b = rng.uniform(2.1, 4, n).astype(dtype); d = rng.uniform(-5, 5, n).astype(dtype)
-            x = O.tridiag(a, b, c, d)
+    rl = _live()
+    for n, rep, a, b, c, d in RP.thomas_inputs(dtype):
+        x = O.tridiag(a, b, c, d)
+        xr = PINS["thomas_%s_%d_%d" % (name, n, rep)]
+        assert xr.dtype == dtype and np.array_equal(x, xr)
+        if rl is not None:
             aa, bb, cc, dd = [v.copy() for v in (a, b, c, d)]
-            xr = np.zeros_like(a)
-            getattr(rl, "ref_tridiag_" + name)(*[v.ctypes.data_as(C.POINTER(ct)) for v in (aa, bb, cc, dd, xr)], n)
-            assert np.array_equal(x, xr)
+            xl = np.zeros_like(a)
+            getattr(rl, "ref_tridiag_" + name)(*[v.ctypes.data_as(C.POINTER(ct)) for v in (aa, bb, cc, dd, xl)], n)
+            assert np.array_equal(xl, xr)
 
 
-@needs_ref
 def test_fluid_params_and_align_are_the_reference_ones():
-    rl = O.ref_lib()
+    rl = _live()
     pf = C.POINTER(C.c_float)
-    for Re, Pr, lam in ((200.0, 0.72, 1.4), (1000.0, 0.7, 1.3), (50.0, 6.9, 1.01)):
-        ref = np.zeros(4, np.float32)
-        rl.ref_fluid_params_normalized_f32(Re, Pr, lam, ref.ctypes.data_as(pf))
+    for (Re, Pr, lam), ref in zip(RP.FP_TRIPLES, PINS["fluid_params_normalized_f32"]):
         assert np.array_equal(O.fluid_params(np.float32, Re, Pr, lam), ref)
         assert np.array_equal(np.array(capi.fluid_params(np.float32, Re, Pr, lam), np.float32), ref)
-    ref = np.zeros(4, np.float32)
-    rl.ref_fluid_params_physical_f32(0.001, 998.0, 287.0, 0.6, 4180.0, ref.ctypes.data_as(pf))
-    assert np.array_equal(np.array(capi.fluid_params_physical(np.float32, 0.001, 998.0, 287.0, 0.6, 4180.0), np.float32), ref)
-    for n in list(range(0, 200)) + [255, 256, 257, 1023]:
-        assert O.lib().fs3d_oracle_align_by_32(n) == rl.ref_align_by_32(n)
+        if rl is not None:
+            live = np.zeros(4, np.float32)
+            rl.ref_fluid_params_normalized_f32(Re, Pr, lam, live.ctypes.data_as(pf))
+            assert np.array_equal(live, ref)
+    ref = PINS["fluid_params_physical_f32"]
+    assert np.array_equal(np.array(capi.fluid_params_physical(np.float32, *RP.FP_PHYSICAL), np.float32), ref)
+    if rl is not None:
+        live = np.zeros(4, np.float32)
+        rl.ref_fluid_params_physical_f32(*RP.FP_PHYSICAL, live.ctypes.data_as(pf))
+        assert np.array_equal(live, ref)
+    assert list(RP.ALIGN_NS) == list(range(0, 200)) + [255, 256, 257, 1023]
+    for n, ref in zip(RP.ALIGN_NS, PINS["align_by_32"]):
+        assert O.lib().fs3d_oracle_align_by_32(n) == ref
+        if rl is not None:
+            assert rl.ref_align_by_32(n) == ref
 
 
 def test_thomas_solves_the_system():
@@ -193,19 +209,22 @@ def test_time_step_reports_divergence():
     assert rc == 1 and e > 0.01
 
 
-# ---- the host-side loaders against the reference's own code (oracle/_ref: Common/Config.h + LinuxIO.cpp, Geometry.h) -------------
+# ---- the host-side loaders against the reference's own code (oracle/_ref: Common/Config.h + LinuxIO.cpp, Geometry.h; stored in
+# tests/golden/ref_pins.npz, checked against the live library when it is built) ---------------------------------------------------
 INPUTS = os.path.join(GOLD, "inputs")
+REF_CONFIGS = json.loads(str(PINS["config_json"]))
 
 
-@needs_ref
 @pytest.mark.parametrize("name", ["box_pipe_2D_config.txt", "non_uniform_pipe_2D_config.txt", "white_sea_config.txt", "heart_us_2D_config.txt"])
 def test_config_parser_is_the_reference_parser(name):
     """Every value the reference's Config::LoadFromFile leaves behind for a config, against the Python parser (shape2d.Config; the
     C++ one, host/Config.h, is held to the Python one in tests/test_grid_loader.py / test_host_driver.py)."""
     from cmc_fluid_solver_amd import shape2d
     path = os.path.join(INPUTS, name)
-    ref = O.ref_config(path)
-    assert ref is not None and "rejected" not in ref, ref
+    ref = REF_CONFIGS[name]
+    assert "rejected" not in ref, ref
+    if _live() is not None:
+        assert O.ref_config(path) == ref
     c = shape2d.Config(path)
     for k in ("R_specific", "k", "cv", "baseT", "bc_strength", "bc_inT", "viscosity", "density", "Re", "Pr", "lam", "depth_var", "frame_time", "dx", "dy", "dz", "depth"):
         assert getattr(c, k) == ref[k], (k, getattr(c, k), ref[k])
@@ -218,63 +237,68 @@ def test_config_parser_is_the_reference_parser(name):
     assert ["NetCDF", "MultiVox"][ref["out_fmt"]] == c.out_fmt and ["Explicit", "ADI", "Stable"][ref["solver"]] == c.solver
 
 
-@needs_ref
 def test_reference_parser_rejects_what_ours_rejects(tmp_path):
     """The shipped heart_us configs (old keys, no out_vars) and configs with a missing key: the reference prints its message and
     exits; the Python / C++ parsers raise with the same message."""
     from cmc_fluid_solver_amd import shape2d
-    good = open(os.path.join(INPUTS, "box_pipe_2D_config.txt")).read().replace("\r", "")
-    cases = {"no_vars": "\n".join(ln for ln in good.split("\n") if not ln.startswith("out_vars")),
-             "no_dz": "\n".join(ln for ln in good.split("\n") if not ln.startswith("grid_dz")),
-             "no_solver": "\n".join(ln for ln in good.split("\n") if not ln.startswith("solver"))}
-    for tag, text in cases.items():
+    assert RP.REJECT_DROP == {"no_vars": "out_vars", "no_dz": "grid_dz", "no_solver": "solver"}
+    for tag in RP.REJECT_DROP:
         p = str(tmp_path / (tag + ".txt"))
-        open(p, "w").write(text)
-        ref = O.ref_config(p)
+        open(p, "w").write(RP.reject_case(tag))
+        ref = REF_CONFIGS[tag]
+        if _live() is not None:
+            assert O.ref_config(p) == ref, tag
         assert "rejected" in ref, tag
         with pytest.raises(ValueError) as ei:
             shape2d.Config(p)
         assert str(ei.value) in ref["rejected"], (tag, str(ei.value), ref["rejected"])
 
 
-@needs_ref
 def test_bounding_boxes_are_the_reference_ones(tmp_path):
     """BBox2D::Build / BBox3D::Build (Geometry.h:464-480, 510-529) on the points of the fixture inputs, all frames."""
     from cmc_fluid_solver_amd import shape2d, shape3d
-    rl = O.ref_lib()
+    rl = _live()
     pf, pi = C.POINTER(C.c_float), C.POINTER(C.c_int)
-    for name in ("box_pipe_2D_data.txt", "non_uniform_pipe_2D_data.txt", "heart_us_2D_data.txt"):
+    assert RP.BBOX2D == ("box_pipe_2D_data.txt", "non_uniform_pipe_2D_data.txt", "heart_us_2D_data.txt")
+    for name in RP.BBOX2D:
         frames = shape2d.parse_shape2d(open(os.path.join(INPUTS, name)).read())
-        pts = [np.array([p for sh in fr["shapes"] for p in sh["points"]], np.float32) for fr in frames]
-        npts = np.array([len(p) for p in pts], np.int32)
-        xy = np.ascontiguousarray(np.concatenate(pts), np.float32)
-        out = np.zeros(4, np.float32)
-        rl.ref_bbox2d_build(len(frames), npts.ctypes.data_as(pi), xy.ctypes.data_as(pf), out.ctypes.data_as(pf))
+        out = PINS["bbox2d_" + name]
+        if rl is not None:
+            nf, npts, xy = RP.bbox2d_points(name)
+            live = np.zeros(4, np.float32)
+            rl.ref_bbox2d_build(nf, npts.ctypes.data_as(pi), xy.ctypes.data_as(pf), live.ctypes.data_as(pf))
+            assert np.array_equal(live, out), name
         g2 = shape2d.Grid2D(frames, 0.01, 0.01, 1.0, False)
         assert tuple(np.float32(v) for v in g2.bbox) == tuple(out), name
-    rng = np.random.default_rng(5)
-    vs = [rng.uniform(-30, 50, (40, 3)), rng.uniform(-35, 45, (40, 3))]
     tri = np.array([[0, 1, 2]])
     path = str(tmp_path / "m.txt")
-    shape3d.write_mesh(path, [(v, tri) for v in vs])
+    shape3d.write_mesh(path, [(v, tri) for v in RP.bbox3d_vertices()])
     frames = shape3d.parse_shape3d(open(path).read())
     sh = shape3d.Shape3D(frames, 0.001, 0.001, 0.001, False)
     nv = np.array([40, 40], np.int32)
     xyz = np.ascontiguousarray(np.concatenate([fr["v"] for fr in frames]), np.float32)
-    out = np.zeros(6, np.float32)
-    rl.ref_bbox3d_build(2, nv.ctypes.data_as(pi), xyz.ctypes.data_as(pf), out.ctypes.data_as(pf))
+    assert np.array_equal(xyz, PINS["bbox3d_vertices"])                 # the input the stored result was computed on
+    out = PINS["bbox3d"]
+    if rl is not None:
+        live = np.zeros(6, np.float32)
+        rl.ref_bbox3d_build(2, nv.ctypes.data_as(pi), xyz.ctypes.data_as(pf), live.ctypes.data_as(pf))
+        assert np.array_equal(live, out)
     assert tuple(np.float32(v) for v in sh.bbox) == tuple(out)
 
 
-@needs_ref
 def test_depth_resampling_is_the_reference_one():
     """DepthInfo3D(nx, ny, info) (Geometry.h:429-441): the `d` variable of a SeaNetCDF run and the depth lookup of the loader."""
     from cmc_fluid_solver_amd import seanetcdf
-    rl = O.ref_lib()
+    rl = _live()
     pf = C.POINTER(C.c_float)
-    rng = np.random.default_rng(6)
-    src = rng.uniform(-200, 100, (301, 722)).astype(np.float32)
-    for nx, ny in ((150, 100), (160, 96), (301, 722), (7, 1000)):
-        out = np.zeros((nx, ny), np.float32)
-        rl.ref_depth_resample(nx, ny, 301, 722, src.ctypes.data_as(pf), out.ctypes.data_as(pf))
-        assert np.array_equal(out, seanetcdf.resample_depths(src, nx, ny))
+    src = RP.depth_source()
+    assert RP.sha(src) == str(PINS["depth_source_sha256"])                # the input the stored results were computed on
+    assert RP.DEPTH_SIZES == ((150, 100), (160, 96), (301, 722), (7, 1000))
+    for nx, ny in RP.DEPTH_SIZES:
+        got = seanetcdf.resample_depths(src, nx, ny)
+        assert got.dtype == np.float32 and got.shape == (nx, ny)
+        assert RP.sha(got) == str(PINS["depth_%dx%d_sha256" % (nx, ny)]), (nx, ny)
+        if rl is not None:
+            out = np.zeros((nx, ny), np.float32)
+            rl.ref_depth_resample(nx, ny, 301, 722, src.ctypes.data_as(pf), out.ctypes.data_as(pf))
+            assert np.array_equal(out, got)
