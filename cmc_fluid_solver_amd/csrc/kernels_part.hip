@@ -48,21 +48,7 @@ typedef unsigned pu32x4 __attribute__((ext_vector_type(4)));
 // second read of the store phase are served from them (nt there: X +6 %, Y +3 % slower).  Z kernel: nt on every stream.
 // Measured (profiles/r3_ab_nt.txt, one box, interleaved, per launch with all stores): X 0.300 -> 0.279, Y 0.272 -> 0.248,
 // Z 0.242 -> 0.219 ms; tools/ubench/stream2.hip: nt loads read at 7.0 instead of 6.0-6.2 TB/s.
-#ifndef FS3D_PART_AUX_CUR
-#define FS3D_PART_AUX_CUR 2
-#endif
-#ifndef FS3D_PART_AUX_TMP
-#define FS3D_PART_AUX_TMP 0
-#endif
-#ifndef FS3D_PART_AUX_ST
-#define FS3D_PART_AUX_ST 2
-#endif
-#ifndef FS3D_PARTZ_AUX_TMP
-#define FS3D_PARTZ_AUX_TMP 2
-#endif
-#ifndef FS3D_PARTZ_AUX_W
-#define FS3D_PARTZ_AUX_W 0        // W of the line itself: the rows j+-1 and planes i+-1 read it again as their neighbour
-#endif
+constexpr int PART_AUX_NT = 2;
 template <typename R> struct PBuf;
 template <> struct PBuf<float> {
     template <int AUX = 0> static __device__ __forceinline__ float ld(prsrc_t r, unsigned vo, unsigned so) { return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, vo, so, AUX)); }
@@ -122,14 +108,12 @@ __device__ __forceinline__ void part_coefs(R q, int code4, R vis_v, R b_v, R vis
 // Measured on the shipped 64^3 example against the fp64 oracle: with the correction the partition kernels deviate
 // from the fp64 solution as much as the sequential fp32 recurrence does (8.5e-7 vs 7.9e-7 after 10 steps, 1.2e-6 vs
 // 1.0e-6 after 30); without it twice as much.  No measurable cost: the phases that divide are not the ones that bind.
-#ifndef FS3D_PART_QCORR
-#define FS3D_PART_QCORR 1         // 1: every quotient of the elimination gets a correction step (correctly rounded x/den)
-#endif
+// Every quotient of the elimination gets that correction step (correctly rounded x/den).
 template <typename R>
 __device__ __forceinline__ R pquot(R num, R den, R r)
 {
     const R q = num * r;
-    return FS3D_PART_QCORR ? pfma(pfma(-den, q, num), r, q) : q;
+    return pfma(pfma(-den, q, num), r, q);
 }
 template <typename R, int NR>
 __device__ __forceinline__ void part_step(R lead, R diag, R trail, R &cp, R &sp, R (&dp)[NR], const R (&d)[NR])
@@ -155,21 +139,12 @@ __device__ __forceinline__ void part_step(R lead, R diag, R trail, R &cp, R &sp,
 // Measured (profiles/r3_ab_packed.txt, interleaved, bit-identical fields): Z kernel (226 of 256 VGPRs, no spills) 0.2111 -> 0.2022 ms;
 // X/Y kernels 0.254 -> 0.275 / 0.245 -> 0.271 -- they sit at their 128-VGPR budget and the even-aligned register pairs cost 16-21
 // spilled registers.  Packed in the Z kernel only.
-#ifndef FS3D_PART_UCOL
-#define FS3D_PART_UCOL 1              // shared code columns (SweepParams::ucol)
-#endif
-#ifndef FS3D_PART_PACKED_XY
-#define FS3D_PART_PACKED_XY 0
-#endif
-#ifndef FS3D_PART_PACKED_Z
-#define FS3D_PART_PACKED_Z 1
-#endif
 typedef float pf2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ pf2 pk_fma(pf2 a, pf2 b, pf2 c) { return __builtin_elementwise_fma(a, b, c); }
 __device__ __forceinline__ pf2 pk_quot(pf2 num, pf2 den, pf2 r)
 {
     const pf2 q = num * r;
-    return FS3D_PART_QCORR ? pk_fma(pk_fma(-den, q, num), r, q) : q;
+    return pk_fma(pk_fma(-den, q, num), r, q);
 }
 // lead/diag/trail: (a, b, c) going down, (c, b, a) going up, of the velocity (_v) and temperature (_t) matrix
 template <typename R, bool PK>
@@ -200,18 +175,15 @@ __device__ __forceinline__ void part_step_vt(R lead_v, R diag_v, R trail_v, R le
 // ------------------------------------------------------------------------------------------------------------
 // X / Y sweeps
 // ------------------------------------------------------------------------------------------------------------
-#ifndef FS3D_PART_PF
-#define FS3D_PART_PF 2            // cells whose loads are in flight ahead of the cell being computed (P phase)
-#endif
-#ifndef FS3D_PART_OPF
-#define FS3D_PART_OPF 2           // cells whose temp values are in flight ahead of the cell being stored (O phase)
-#endif
 #define PART_EXW 18               // interface words per (line, chunk): 5 per matrix, 2 per right-hand side
 
-template <typename R, int DIR, int M, int NCH, int WPS, int LT, int PF = FS3D_PART_PF, int XB = 0, int OPF = FS3D_PART_OPF, bool KT = false>
-__global__ void __launch_bounds__(LT * NCH, WPS) k_sweep_part(SweepParams<R> p, int n_o, int n_tiles, int order)
+// order: bit 0 = tile order (below); 0x40 = late start, delay in bits 8+ (part_launch_xy)
+template <typename R, int DIR, int M, int NCH, int LT, int XB = 0>
+__global__ void __launch_bounds__(LT * NCH, 4) k_sweep_part(SweepParams<R> p, int n_o, int n_tiles, int order)
 {
     static_assert(DIR == 0 || DIR == 1, "lanes along k: X and Y sweeps");
+    constexpr int PF = 2;                                // cells whose loads are in flight ahead of the cell being computed (P phase)
+    constexpr int OPF = 2;                               // cells whose temp values are in flight ahead of the cell being stored (O phase)
     extern __shared__ __attribute__((aligned(16))) unsigned char part_smem[];
     static_assert(LT == 16 || LT == 32 || LT == 64, "lines per workgroup");
     R *const ldsD = (R *)part_smem;                      // [NCH*M][LT]  dT of every cell (P -> E)
@@ -221,12 +193,8 @@ __global__ void __launch_bounds__(LT * NCH, WPS) k_sweep_part(SweepParams<R> p, 
     // s_memrealtime (100 MHz) instead -- s_memtime counters are not aligned between CUs
     unsigned long long *const stamp = p.stamps ? p.stamps + ((size_t)blockIdx.x * 8 + (t >> 6) % 8) * 8 : nullptr;
 #define PSTAMP(k) do { if (stamp && (t & 63) == 0 && (t >> 6) < 8) stamp[k] = (t >> 6) == 7 ? __builtin_amdgcn_s_memrealtime() : __builtin_amdgcn_s_memtime(); } while (0)
-    // Start stagger: the first workgroup of every CU starts with the launch, so all CUs load, then solve, then store at the
-    // same time and HBM idles while they solve (tools/part_phases.py timeline).  Part of the first generation starts late.
-    if ((order & 0x30) && blockIdx.x < 256) {
-        const int grp = (order & 0x20) ? (int)((blockIdx.x >> 3) % 3) : (int)((blockIdx.x >> 3) & 1);
-        for (int w = grp * (order >> 8); w > 0; w--) __builtin_amdgcn_s_sleep(127);
-    }
+    // Late start: the first workgroup of every CU starts with the launch, so all CUs load, then solve, then store at the
+    // same time and HBM idles while they solve (tools/part_phases.py timeline).
     if (order & 0x40) {                                   // several workgroups per CU: the k-th one of every CU starts k delays late
         constexpr int WPC = 1024 / (LT * NCH) < 2 ? 2 : 1024 / (LT * NCH);
         const int slot = (int)(blockIdx.x >> 8);
@@ -244,15 +212,6 @@ __global__ void __launch_bounds__(LT * NCH, WPS) k_sweep_part(SweepParams<R> p, 
     }
     // order 0: consecutive ids = consecutive rows/planes `o` of one lane tile; 1: = the lane tiles of one row/plane
     // (concurrently running workgroups then stream whole rows: DRAM page locality)
-#ifdef FS3D_EXPERIMENTS              // timing experiments only (WRONG NUMBERS): never compiled into libfs3d_hip.so (build.build_variant only)
-    const bool x_nonb = order & 2, x_nore = order & 4;
-#else
-    constexpr bool x_nonb = false, x_nore = false;
-#endif
-    if (order & 8) {                                      // experiment: the later waves of the workgroup first during P
-        const int wq = (t >> 6) * 4 / (LT * NCH / 64);
-        if (wq == 1) __builtin_amdgcn_s_setprio(1); else if (wq == 2) __builtin_amdgcn_s_setprio(2); else if (wq == 3) __builtin_amdgcn_s_setprio(3);
-    }      // timing experiments only (wrong numbers): FS3D_PART_ORDER bits 1, 2
     const int tile_id = (order & 1) ? lb % n_tiles : lb / n_o;
     const int o = ((order & 1) ? lb / n_tiles : lb - tile_id * n_o) + (DIR == 1 ? p.o_begin : 0);
 
@@ -297,7 +256,7 @@ __global__ void __launch_bounds__(LT * NCH, WPS) k_sweep_part(SweepParams<R> p, 
         // addresses on all lanes of a chunk: cache hits) instead of M 2-byte loads per lane, 2 bytes per cell from HBM
         bool tile_uni = false;
         unsigned ucol_id = 0;
-        if (p.uflag && XB == 0 && FS3D_PART_UCOL != 0) {
+        if (p.uflag && XB == 0) {
             const unsigned f = p.uflag[(long long)o * p.ung + tile_id * LT / 32];
             tile_uni = LT == 64 ? (f & 2u) != 0 : (f & 1u) != 0;
             ucol_id = f >> 2;
@@ -328,17 +287,14 @@ __global__ void __launch_bounds__(LT * NCH, WPS) k_sweep_part(SweepParams<R> p, 
         const unsigned sc = s_is;
         s_is = opq_s(s_is + ssb);
 #pragma unroll
-        for (int f = 0; f < 4; f++) L.tp[f] = PBuf<R>::template ld<FS3D_PART_AUX_TMP>(Ltmp, vo, sc + ssb + (unsigned)f * fsb);
+        for (int f = 0; f < 4; f++) L.tp[f] = PBuf<R>::ld(Ltmp, vo, sc + ssb + (unsigned)f * fsb);
 #pragma unroll
-        for (int f = 0; f < 4; f++) L.c[f] = PBuf<R>::template ld<FS3D_PART_AUX_CUR>(Lcur, vo, sc + (unsigned)f * fsb);
+        for (int f = 0; f < 4; f++) L.c[f] = PBuf<R>::template ld<PART_AUX_NT>(Lcur, vo, sc + (unsigned)f * fsb);
         const unsigned sv = sc + (unsigned)DIR * fsb;
-        if (x_nonb) { L.om = L.op = L.le = L.c[0]; }
-        else {
-            L.om = PBuf<R>::ld(Ltmp, vo, sv - osb); L.op = PBuf<R>::ld(Ltmp, vo, sv + osb);
-            // lane-axis neighbours: the lanes next door hold them (DPP shifts below); only the tile's first and last lane
-            // fetch theirs from outside the tile -- every other lane of this load is out of range (no memory access)
-            L.le = PBuf<R>::ld(Ltmp, vo_edge, sv);
-        }
+        L.om = PBuf<R>::ld(Ltmp, vo, sv - osb); L.op = PBuf<R>::ld(Ltmp, vo, sv + osb);
+        // lane-axis neighbours: the lanes next door hold them (DPP shifts below); only the tile's first and last lane
+        // fetch theirs from outside the tile -- every other lane of this load is out of range (no memory access)
+        L.le = PBuf<R>::ld(Ltmp, vo_edge, sv);
     };
     R Tm[4], Tc[4];
 #pragma unroll
@@ -395,7 +351,6 @@ __global__ void __launch_bounds__(LT * NCH, WPS) k_sweep_part(SweepParams<R> p, 
     PSTAMP(1);
     // ---- P: rows -------------------------------------------------------------------------------------------
     R q[M], dU[M], dV[M], dW[M];
-    R tkeep[KT ? 4 : 1][KT ? M : 1];                     // KT: the temp values of the own cells stay in registers for the merge (no second read)
     {
         pstatic_for<M>([&](auto ic) __attribute__((always_inline)) {
             constexpr int i = decltype(ic)::value;
@@ -441,10 +396,6 @@ __global__ void __launch_bounds__(LT * NCH, WPS) k_sweep_part(SweepParams<R> p, 
                 }
             }
             q[i] = qq; dU[i] = dd[0]; dV[i] = dd[1]; dW[i] = dd[2];
-            if constexpr (KT) {
-#pragma unroll
-                for (int f = 0; f < 4; f++) tkeep[f][i] = Tc[f];
-            }
             ldsD[(s0 + i) * LT + kk] = dd[3];
 #pragma unroll
             for (int f = 0; f < 4; f++) { Tm[f] = Tc[f]; Tc[f] = c.tp[f]; }
@@ -453,7 +404,6 @@ __global__ void __launch_bounds__(LT * NCH, WPS) k_sweep_part(SweepParams<R> p, 
         });
     }
 
-    if (order & 8) __builtin_amdgcn_s_setprio(0);
     PSTAMP(2);
     // ---- E: chunk elimination -> interface coefficients ------------------------------------------------------
     // every use recomputes the coefficients from an opaque copy of q (4 operations) instead of keeping 6 x M values alive
@@ -475,8 +425,8 @@ __global__ void __launch_bounds__(LT * NCH, WPS) k_sweep_part(SweepParams<R> p, 
             PMat<R> mv, mt, nv, nt;
             coefs(i, mv, mt);
             coefs(j, nv, nt);
-            { const R d3[3] = {dU[i], dV[i], dW[i]}, d1[1] = {tdi}; part_step_vt<R, FS3D_PART_PACKED_XY != 0>(mv.a, mv.b, mv.c, mt.a, mt.b, mt.c, cpv, cpt, lpv, lpt, dp3, dp1, d3, d1); }
-            { const R d3[3] = {dU[j], dV[j], dW[j]}, d1[1] = {tdj}; part_step_vt<R, FS3D_PART_PACKED_XY != 0>(nv.c, nv.b, nv.a, nt.c, nt.b, nt.a, apv, apt, upv, upt, ep3, ep1, d3, d1); }
+            { const R d3[3] = {dU[i], dV[i], dW[i]}, d1[1] = {tdi}; part_step_vt<R, false>(mv.a, mv.b, mv.c, mt.a, mt.b, mt.c, cpv, cpt, lpv, lpt, dp3, dp1, d3, d1); }
+            { const R d3[3] = {dU[j], dV[j], dW[j]}, d1[1] = {tdj}; part_step_vt<R, false>(nv.c, nv.b, nv.a, nt.c, nt.b, nt.a, apv, apt, upv, upt, ep3, ep1, d3, d1); }
         });
         // the interface cell's own row with x[M-2] eliminated:  A X_{p-1} + Bp X_p + cl x_first(p+1) = Dp
         PMat<R> lv, lt;
@@ -613,7 +563,7 @@ __global__ void __launch_bounds__(LT * NCH, WPS) k_sweep_part(SweepParams<R> p, 
             if (i + 1 < M - 1) tdn = myD[(i + 1) * LT];
             PMat<R> mv, mt;
             coefs(i, mv, mt);
-            { const R d3[3] = {dU[i], dV[i], dW[i]}, d1[1] = {tdi}; R spt = sp; part_step_vt<R, FS3D_PART_PACKED_XY != 0>(mv.a, mv.b, mv.c, mt.a, mt.b, mt.c, cpv, cpt, sp, spt, dp3, dp1, d3, d1); }
+            { const R d3[3] = {dU[i], dV[i], dW[i]}, d1[1] = {tdi}; R spt = sp; part_step_vt<R, false>(mv.a, mv.b, mv.c, mt.a, mt.b, mt.c, cpv, cpt, sp, spt, dp3, dp1, d3, d1); }
             q[i] = cpv; cT[i] = cpt; dU[i] = dp3[0]; dV[i] = dp3[1]; dW[i] = dp3[2]; dT[i] = dp1[0];
         });
         dU[M - 1] = xo[0]; dV[M - 1] = xo[1]; dW[M - 1] = xo[2]; dT[M - 1] = xo[3];
@@ -636,10 +586,10 @@ __global__ void __launch_bounds__(LT * NCH, WPS) k_sweep_part(SweepParams<R> p, 
         const int nloc = opq_v(n - s0);                 // cells of this chunk inside the line
         auto issue = [&](R (&v)[4]) __attribute__((always_inline)) {
 #pragma unroll
-            for (int f = 0; f < 4; f++) v[f] = x_nore ? R(f) : PBuf<R>::ld(Ltmp, vo, s_is + (unsigned)f * fsb);
+            for (int f = 0; f < 4; f++) v[f] = PBuf<R>::ld(Ltmp, vo, s_is + (unsigned)f * fsb);
             s_is = opq_s(s_is + ssb);
         };
-        if (p.merge && !KT) {
+        if (p.merge) {
 #pragma unroll
             for (int i = 0; i < OPF && i < M; i++) issue(tv[i]);
         }
@@ -647,7 +597,7 @@ __global__ void __launch_bounds__(LT * NCH, WPS) k_sweep_part(SweepParams<R> p, 
             constexpr int i = decltype(ic)::value;
             const unsigned sc = s_o;
             s_o = opq_s(s_o + ssb);
-            if (p.merge && !KT && i + OPF < M) issue(tv[(i + OPF) % (OPF + 1)]);
+            if (p.merge && i + OPF < M) issue(tv[(i + OPF) % (OPF + 1)]);
             __builtin_amdgcn_sched_barrier(0);
             R xv[4] = {dU[i], dV[i], dW[i], dT[i]};
             const bool uni = (opq_s(umask) >> i) & 1u;
@@ -656,12 +606,10 @@ __global__ void __launch_bounds__(LT * NCH, WPS) k_sweep_part(SweepParams<R> p, 
             if (p.store_next) {
                 const unsigned v_ = seg ? vo_st : PART_OOB;            // UpdateSegment: every cell of a segment, nothing else
 #pragma unroll
-                for (int f = 0; f < 4; f++) PBuf<R>::template st<FS3D_PART_AUX_ST>(Lnext, v_, sc + (unsigned)f * fsb, xv[f]);
+                for (int f = 0; f < 4; f++) PBuf<R>::template st<PART_AUX_NT>(Lnext, v_, sc + (unsigned)f * fsb, xv[f]);
             }
             if (p.merge) {
-                R tq[4];
-#pragma unroll
-                for (int f = 0; f < 4; f++) tq[f] = KT ? tkeep[f][KT ? i : 0] : tv[i % (OPF + 1)][f];
+                const R (&tq)[4] = tv[i % (OPF + 1)];
                 if (!uni && __any(isin && !seg)) {
                     // NODE_IN cell outside every segment (run without a closing cell, Grid3D.cpp:87-117): the reference
                     // merges the stale `next` value
@@ -673,7 +621,7 @@ __global__ void __launch_bounds__(LT * NCH, WPS) k_sweep_part(SweepParams<R> p, 
                 for (int f = 0; f < 4; f++) {
                     R mv = (tq[f] + xv[f]) * R(0.5);                                   // MergeFieldTo (TimeLayer3D.h:415-436)
                     if (p.merge == 2) mv = (mv + xv[f]) * R(0.5);
-                    PBuf<R>::template st<FS3D_PART_AUX_ST>(Ltout, v_, sc + (unsigned)f * fsb, isin ? mv : tq[f]);
+                    PBuf<R>::template st<PART_AUX_NT>(Ltout, v_, sc + (unsigned)f * fsb, isin ? mv : tq[f]);
                 }
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -683,26 +631,16 @@ __global__ void __launch_bounds__(LT * NCH, WPS) k_sweep_part(SweepParams<R> p, 
 #undef PSTAMP
 }
 
-// Kernel-experiment knobs (tile order, start delays, LDS padding, ...; FS3D_PART_ORDER bits 1/2 skip loads and give WRONG numbers):
-// read from the environment only in -DFS3D_EXPERIMENTS builds (build.build_variant); libfs3d_hip.so compiles the defaults in.
-#ifdef FS3D_EXPERIMENTS
-static int part_exp_env(const char *name, int dflt) { const char *e = getenv(name); return e ? atoi(e) : dflt; }
-#else
-static constexpr int part_exp_env(const char *, int dflt) { return dflt; }
-#endif
-
-template <typename R, int DIR, int M, int NCH, int WPS, int LT, int PF = FS3D_PART_PF, int XB = 0, int OPF = FS3D_PART_OPF, bool KT = false>
+template <typename R, int DIR, int M, int NCH, int LT, int XB = 0>
 static bool part_launch_xy(fs3d_ctx *c, const SweepParams<R> &p)
 {
     const int n_o = DIR == 0 ? p.dimy : (p.o_count ? p.o_count : p.dimx);
     const int n_tiles = (p.dimz + LT - 1) / LT;
-    // FS3D_PART_LDSPAD (kernel experiments): more dynamic LDS than needed, to hold the workgroups per CU down
-    static const size_t lds_pad = (size_t)part_exp_env("FS3D_PART_LDSPAD", 0);
-    const size_t lds = ((size_t)NCH * M * LT + (size_t)(PART_EXW + (NCH > 16 ? 4 : 0)) * NCH * LT) * sizeof(R) + lds_pad;
+    const size_t lds = ((size_t)NCH * M * LT + (size_t)(PART_EXW + (NCH > 16 ? 4 : 0)) * NCH * LT) * sizeof(R);
     static std::atomic<unsigned long long> attr_set{0};
     const unsigned long long dev_bit = 1ull << (c->device & 63);
     if (!(attr_set.load() & dev_bit)) {
-        if (hipFuncSetAttribute((const void *)k_sweep_part<R, DIR, M, NCH, WPS, LT, PF, XB, OPF, KT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+        if (hipFuncSetAttribute((const void *)k_sweep_part<R, DIR, M, NCH, LT, XB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
             c->err = std::string("partition kernel: hipFuncSetAttribute: ") + hipGetErrorString(hipGetLastError());
             return false;
         }
@@ -710,16 +648,13 @@ static bool part_launch_xy(fs3d_ctx *c, const SweepParams<R> &p)
     }
     // workgroup order: 32-line tiles run the lane tiles of one row/plane on consecutive workgroups (the 128-byte pieces of a
     // row are then fetched together: 512^3 X 2.93 -> 2.71 ms, Y 2.18 -> 2.10), 64-line tiles the rows/planes of one lane tile
-    static const int order_env = part_exp_env("FS3D_PART_ORDER", -1);
     // 32-line tiles, two workgroups per CU: the second workgroup of every CU starts ~16 us late, so that the two do not load,
-    // solve and store at the same time (tools/ab_tiles.py, interleaved on one box: 64 lines 6.12 ms per step, 32 lines 5.81,
-    // 32 lines with the late start 5.63-5.66).  Few workgroups (thin slabs) and 512-cell lines: lane tiles fastest.
+    // solve and store at the same time (profiles/r2_variants.txt, r2_timeline.txt; interleaved on one box: 64 lines 6.12 ms per
+    // step, 32 lines 5.81, 32 lines with the late start 5.63-5.66).  Few workgroups (thin slabs) and 512-cell lines: lane tiles fastest.
     // (the late start only where it was measured: 512-thread workgroups, two per CU, at least two generations of them)
     const bool late = LT <= 32 && NCH == 16 && M == 16 && (long long)n_o * n_tiles >= 1024;
-    static const int late_slab = part_exp_env("FS3D_PART_LATE_SLAB", 0);   // experiment: slab kernels (XB != 0), delay units
-    int order = order_env >= 0 ? order_env : (LT <= 32 ? (((long long)n_o * n_tiles < 1024 || NCH == 32) ? 1 : 0) | (late ? 0x40 | (4 << 8) : 0) : 0);
-    if (XB != 0 && late_slab > 0 && LT * NCH <= 512 && (long long)n_o * n_tiles >= 512) order |= 0x40 | (late_slab << 8);
-    hipLaunchKernelGGL((k_sweep_part<R, DIR, M, NCH, WPS, LT, PF, XB, OPF, KT>), dim3((unsigned)(n_o * n_tiles)), dim3(LT * NCH), lds, c->stream, p, n_o, n_tiles, order);
+    const int order = LT <= 32 ? (((long long)n_o * n_tiles < 1024 || NCH == 32) ? 1 : 0) | (late ? 0x40 | (4 << 8) : 0) : 0;
+    hipLaunchKernelGGL((k_sweep_part<R, DIR, M, NCH, LT, XB>), dim3((unsigned)(n_o * n_tiles)), dim3(LT * NCH), lds, c->stream, p, n_o, n_tiles, order);
     return true;
 }
 
@@ -734,47 +669,39 @@ static bool part_dispatch_xy(fs3d_ctx *c, const SweepParams<R> &p)
             // first pass of the cross-slab sweep: the slab's interface words (whole chunks only)
             constexpr int D0 = 0;
             if (!p.carry_out) return false;
-            if (n <= 32 && n % 8 == 0) return part_launch_xy<R, D0, 8, 4, 4, 64, FS3D_PART_PF, 2>(c, p);   // thin slabs: 8-cell chunks, every thread has cells
+            if (n <= 32 && n % 8 == 0) return part_launch_xy<R, D0, 8, 4, 64, 2>(c, p);   // thin slabs: 8-cell chunks, every thread has cells
             if (n % 16 != 0) return false;
             const bool wide = (long long)p.dimy * ((p.dimz + 63) / 64) >= 512;      // enough 64-line tiles to fill the chip: 256-byte row pieces
-            if (n <= 64) return wide ? part_launch_xy<R, D0, 16, 4, 4, 64, FS3D_PART_PF, 2>(c, p) : part_launch_xy<R, D0, 16, 4, 4, 32, FS3D_PART_PF, 2>(c, p);
-            if (n <= 128) return wide ? part_launch_xy<R, D0, 16, 8, 4, 64, FS3D_PART_PF, 2>(c, p) : part_launch_xy<R, D0, 16, 8, 4, 32, FS3D_PART_PF, 2>(c, p);
-            if (n <= 256) return part_launch_xy<R, D0, 16, 16, 4, 64, FS3D_PART_PF, 2>(c, p);
+            if (n <= 64) return wide ? part_launch_xy<R, D0, 16, 4, 64, 2>(c, p) : part_launch_xy<R, D0, 16, 4, 32, 2>(c, p);
+            if (n <= 128) return wide ? part_launch_xy<R, D0, 16, 8, 64, 2>(c, p) : part_launch_xy<R, D0, 16, 8, 32, 2>(c, p);
+            if (n <= 256) return part_launch_xy<R, D0, 16, 16, 64, 2>(c, p);
             return false;
         }
         if (DIR == 0 && p.carry_in && p.xcarry_in) {
             // x-slab with the values below / above it given (reduced-interface form of the cross-slab sweep)
             constexpr int D0 = 0;
-            if (n <= 32) return part_launch_xy<R, D0, 8, 4, 4, 64, FS3D_PART_PF, 1>(c, p);      // thin slabs (a 32-plane slab of the 256^3 box)
+            if (n <= 32) return part_launch_xy<R, D0, 8, 4, 64, 1>(c, p);      // thin slabs (a 32-plane slab of the 256^3 box)
             const bool wide = (long long)p.dimy * ((p.dimz + 63) / 64) >= 512;      // enough 64-line tiles to fill the chip: 256-byte row pieces
-            if (n <= 64) return wide ? part_launch_xy<R, D0, 16, 4, 4, 64, FS3D_PART_PF, 1>(c, p) : part_launch_xy<R, D0, 16, 4, 4, 32, FS3D_PART_PF, 1>(c, p);
-            if (n <= 128) return wide ? part_launch_xy<R, D0, 16, 8, 4, 64, FS3D_PART_PF, 1>(c, p) : part_launch_xy<R, D0, 16, 8, 4, 32, FS3D_PART_PF, 1>(c, p);
-            if (n <= 256) return part_launch_xy<R, D0, 16, 16, 4, 64, FS3D_PART_PF, 1>(c, p);
+            if (n <= 64) return wide ? part_launch_xy<R, D0, 16, 4, 64, 1>(c, p) : part_launch_xy<R, D0, 16, 4, 32, 1>(c, p);
+            if (n <= 128) return wide ? part_launch_xy<R, D0, 16, 8, 64, 1>(c, p) : part_launch_xy<R, D0, 16, 8, 32, 1>(c, p);
+            if (n <= 256) return part_launch_xy<R, D0, 16, 16, 64, 1>(c, p);
             return false;
         }
-        if (n <= 64) return part_launch_xy<R, DIR, 16, 4, 4, 32>(c, p);
-        if (n <= 128) return part_launch_xy<R, DIR, 16, 8, 4, 32>(c, p);
+        if (n <= 64) return part_launch_xy<R, DIR, 16, 4, 32>(c, p);
+        if (n <= 128) return part_launch_xy<R, DIR, 16, 8, 32>(c, p);
         if (n <= 256) {
-#ifdef FS3D_EXPERIMENTS
-            // measured alternatives (profiles/r2_variants.txt): other chunk sizes = another rounding of the same algebra, so they
-            // exist in experiment builds only
-            if (variant == 1) return part_launch_xy<R, DIR, 32, 8, 2, 32>(c, p);     // 256 threads x 32 cells, <= 256 VGPRs: 1.15x slower
-            if (variant == 10) return part_launch_xy<R, DIR, 8, 32, 4, 32, 2, false, 2, true>(c, p);   // 8 cells per thread, 32 lines, the temp values
-                                                                                                    // stay in registers for the merge: 1.1x slower
-                                                                                                    // (without keeping them: 1.25x)
-#endif
             // 64 lines x 16 chunks (one workgroup of 1024 threads per CU, 256-byte row pieces) was the default until the layer fields
             // were padded; since then two 32-line workgroups per CU are faster (their phases overlap inside the CU)
-            if (variant == 64) return part_launch_xy<R, DIR, 16, 16, 4, 64>(c, p);
-            if (variant == 32) return part_launch_xy<R, DIR, 16, 16, 4, 32>(c, p);
+            if (variant == 64) return part_launch_xy<R, DIR, 16, 16, 64>(c, p);
+            if (variant == 32) return part_launch_xy<R, DIR, 16, 16, 32>(c, p);
             // (r3) with the nontemporal streams the X sweep -- rows a plane apart -- is faster again with 256-byte row pieces
             // (64-line tiles: 0.2685 -> 0.2514 ms), the Y sweep stays with two 32-line workgroups per CU (0.2427 vs 0.2482):
             // profiles/r3_ab_env.txt.  Few workgroups (small planes): 32-line tiles, twice as many.
-            if (DIR == 0 && variant == 0 && (long long)p.dimy * ((p.dimz + 63) / 64) >= 512) return part_launch_xy<R, DIR, 16, 16, 4, 64>(c, p);
-            if (variant == 16) return part_launch_xy<R, DIR, 16, 16, 4, 16>(c, p);      // 16-line tiles: 256 threads, four workgroups per CU, 64-byte row pieces
-            return part_launch_xy<R, DIR, 16, 16, 4, 32>(c, p);
+            if (DIR == 0 && variant == 0 && (long long)p.dimy * ((p.dimz + 63) / 64) >= 512) return part_launch_xy<R, DIR, 16, 16, 64>(c, p);
+            if (variant == 16) return part_launch_xy<R, DIR, 16, 16, 16>(c, p);      // 16-line tiles: 256 threads, four workgroups per CU, 64-byte row pieces
+            return part_launch_xy<R, DIR, 16, 16, 32>(c, p);
         }
-        if (n <= 512) return part_launch_xy<R, DIR, 16, 32, 4, 32>(c, p);
+        if (n <= 512) return part_launch_xy<R, DIR, 16, 32, 32>(c, p);
     }
     return false;
 }
@@ -878,10 +805,11 @@ __global__ void __launch_bounds__(256, WPS) k_sweep_part_z(SweepParams<float> p,
         // jrow: first line of the row (wave-uniform); this lane's line is jrow + sub, clamped into the plane for the loads
         const int jr = jrow < p.dimy ? jrow : p.dimy - 1;   // a row past the plane (tail of the last group): valid addresses, nothing stored
         const unsigned so = opq_s(line_so(jr));
-        L.tc[2] = pld4<FS3D_PARTZ_AUX_W>(Ltmp, vo_l, so + 2u * fsb);       // W first: the row before needs it as its j+1 neighbour... and the stencils
-        L.tc[0] = pld4<FS3D_PARTZ_AUX_TMP>(Ltmp, vo_l, so); L.tc[1] = pld4<FS3D_PARTZ_AUX_TMP>(Ltmp, vo_l, so + fsb); L.tc[3] = pld4<FS3D_PARTZ_AUX_TMP>(Ltmp, vo_l, so + 3u * fsb);
+        L.tc[2] = pld4(Ltmp, vo_l, so + 2u * fsb);       // W first: the row before needs it as its j+1 neighbour... and the stencils
+        // (cached: the rows j+-1 and planes i+-1 read the W of this line again as their neighbour; the other temp fields nt)
+        L.tc[0] = pld4<PART_AUX_NT>(Ltmp, vo_l, so); L.tc[1] = pld4<PART_AUX_NT>(Ltmp, vo_l, so + fsb); L.tc[3] = pld4<PART_AUX_NT>(Ltmp, vo_l, so + 3u * fsb);
 #pragma unroll
-        for (int f = 0; f < 4; f++) L.cu[f] = pld4<FS3D_PART_AUX_CUR>(Lcur, vo_l, so + (unsigned)f * fsb);
+        for (int f = 0; f < 4; f++) L.cu[f] = pld4<PART_AUX_NT>(Lcur, vo_l, so + (unsigned)f * fsb);
         L.wim = pld4(Ltmp, vo_l, so + 2u * fsb - planeb); L.wip = pld4(Ltmp, vo_l, so + 2u * fsb + planeb);
         if (LI > 1) { L.wjm = pld4(Ltmp, vo_l, so + 2u * fsb - rowb); L.wjp = pld4(Ltmp, vo_l, so + 2u * fsb + rowb); }
         const unsigned son = opq_s(line_son(jr));
@@ -972,7 +900,7 @@ __global__ void __launch_bounds__(256, WPS) k_sweep_part_z(SweepParams<float> p,
             R cv = R(0), lv = R(-1), ct = R(0), lt = R(-1), d3[3] = {R(0), R(0), R(0)}, d1[1] = {R(0)};
 #pragma unroll
             for (int c = 0; c < 3; c++) {
-                { const R dd3[3] = {d[0][c], d[1][c], d[2][c]}, dd1[1] = {d[3][c]}; part_step_vt<R, FS3D_PART_PACKED_Z != 0>(mv[c].a, mv[c].b, mv[c].c, mt[c].a, mt[c].b, mt[c].c, cv, ct, lv, lt, d3, d1, dd3, dd1); }
+                { const R dd3[3] = {d[0][c], d[1][c], d[2][c]}, dd1[1] = {d[3][c]}; part_step_vt<R, true>(mv[c].a, mv[c].b, mv[c].c, mt[c].a, mt[c].b, mt[c].c, cv, ct, lv, lt, d3, d1, dd3, dd1); }
                 cpv[c] = cv; lpv[c] = lv; cpt[c] = ct; lpt[c] = lt;
                 dpd[c][0] = d3[0]; dpd[c][1] = d3[1]; dpd[c][2] = d3[2]; dpd[c][3] = d1[0];
             }
@@ -980,7 +908,7 @@ __global__ void __launch_bounds__(256, WPS) k_sweep_part_z(SweepParams<float> p,
         R apv = R(0), upv = R(-1), apt = R(0), upt = R(-1), ep3[3] = {R(0), R(0), R(0)}, ep1[1] = {R(0)};
 #pragma unroll
         for (int c = 2; c >= 0; c--) {
-            { const R dd3[3] = {d[0][c], d[1][c], d[2][c]}, dd1[1] = {d[3][c]}; part_step_vt<R, FS3D_PART_PACKED_Z != 0>(mv[c].c, mv[c].b, mv[c].a, mt[c].c, mt[c].b, mt[c].a, apv, apt, upv, upt, ep3, ep1, dd3, dd1); }
+            { const R dd3[3] = {d[0][c], d[1][c], d[2][c]}, dd1[1] = {d[3][c]}; part_step_vt<R, true>(mv[c].c, mv[c].b, mv[c].a, mt[c].c, mt[c].b, mt[c].a, apv, apt, upv, upt, ep3, ep1, dd3, dd1); }
         }
         // ---- interface row (cell 3) with x[2] eliminated and x_first of the next lane substituted; normalised
         R av, cv_, at, ct_, dd[4];
@@ -1014,8 +942,8 @@ __global__ void __launch_bounds__(256, WPS) k_sweep_part_z(SweepParams<float> p,
         }
         // ---- parallel cyclic reduction over the LPL lanes of the line.  (r3) on 2-vectors: (velocity, temperature) matrix words,
         // right-hand sides U/V against the velocity matrix and W/T against (velocity, temperature): the same operations, component for
-        // component, as the scalar form (FS3D_PART_PACKED_Z 0), half the VALU issue slots
-        if constexpr (FS3D_PART_PACKED_Z != 0) {
+        // component, as one scalar reduction per matrix, half the VALU issue slots
+        {
             pf2 A = {av, at}, C = {cv_, ct_}, D01 = {dd[0], dd[1]}, D23 = {dd[2], dd[3]}, E = {ev, et};
             auto sh_up = [&](pf2 v, int s) __attribute__((always_inline)) { return pf2{__shfl_up(v.x, s, LPL), __shfl_up(v.y, s, LPL)}; };
             auto sh_dn = [&](pf2 v, int s) __attribute__((always_inline)) { return pf2{__shfl_down(v.x, s, LPL), __shfl_down(v.y, s, LPL)}; };
@@ -1023,6 +951,7 @@ __global__ void __launch_bounds__(256, WPS) k_sweep_part_z(SweepParams<float> p,
             for (int s = 1; s < LPL; s <<= 1) {
                 const pf2 Am = sh_up(A, s), Cm = sh_up(C, s), Ap = sh_dn(A, s), Cp = sh_dn(C, s);
                 const pf2 Dm01 = sh_up(D01, s), Dm23 = sh_up(D23, s), Dq01 = sh_dn(D01, s), Dq23 = sh_dn(D23, s);
+                // lanes without a partner at this distance: their a (c) is zero by now, the partner values must only be finite
                 const bool has_m = l >= s, has_p = l + s < LPL;
                 const pf2 zero = {0.0f, 0.0f}, one = {1.0f, 1.0f};
                 const pf2 a = has_m ? A : zero, c = has_p ? C : zero;
@@ -1039,30 +968,6 @@ __global__ void __launch_bounds__(256, WPS) k_sweep_part_z(SweepParams<float> p,
                 A = pk_quot(-a * Am, dn, r); C = pk_quot(-c * Cp, dn, r);
             }
             av = A.x; at = A.y; cv_ = C.x; ct_ = C.y; dd[0] = D01.x; dd[1] = D01.y; dd[2] = D23.x; dd[3] = D23.y; ev = E.x; et = E.y;
-        } else {
-#pragma unroll
-        for (int s = 1; s < LPL; s <<= 1) {
-            const R amv = __shfl_up(av, s, LPL), cmv = __shfl_up(cv_, s, LPL), apv_ = __shfl_down(av, s, LPL), cpv_ = __shfl_down(cv_, s, LPL);
-            const R amt = __shfl_up(at, s, LPL), cmt = __shfl_up(ct_, s, LPL), apt_ = __shfl_down(at, s, LPL), cpt_ = __shfl_down(ct_, s, LPL);
-            R dm[4], dq[4];
-#pragma unroll
-            for (int k = 0; k < 4; k++) { dm[k] = __shfl_up(dd[k], s, LPL); dq[k] = __shfl_down(dd[k], s, LPL); }
-            // lanes without a partner at this distance: their a (c) is zero by now, the partner values must only be finite
-            const bool has_m = l >= s, has_p = l + s < LPL;
-            const R a_v = has_m ? av : R(0), c_v = has_p ? cv_ : R(0), a_t = has_m ? at : R(0), c_t = has_p ? ct_ : R(0);
-            const R dnv = pfma(-a_v, cmv, pfma(-c_v, apv_, R(1))), dnt = pfma(-a_t, cmt, pfma(-c_t, apt_, R(1)));
-            const R rv = prcp(dnv), rt = prcp(dnt);
-#pragma unroll
-            for (int k = 0; k < 3; k++) dd[k] = pquot(pfma(-a_v, dm[k], pfma(-c_v, dq[k], dd[k])), dnv, rv);
-            dd[3] = pquot(pfma(-a_t, dm[3], pfma(-c_t, dq[3], dd[3])), dnt, rt);
-            if (NW == 2) {
-                const R emv = __shfl_up(ev, s, LPL), eqv = __shfl_down(ev, s, LPL), emt = __shfl_up(et, s, LPL), eqt = __shfl_down(et, s, LPL);
-                ev = pquot(pfma(-a_v, emv, pfma(-c_v, eqv, ev)), dnv, rv);
-                et = pquot(pfma(-a_t, emt, pfma(-c_t, eqt, et)), dnt, rt);
-            }
-            av = pquot(-a_v * amv, dnv, rv); cv_ = pquot(-c_v * cpv_, dnv, rv);
-            at = pquot(-a_t * amt, dnt, rt); ct_ = pquot(-c_t * cpt_, dnt, rt);
-        }
         }
         // ---- back-substitution: x[3] = X, x[c] = d'[c] - l[c] X_left - c'[c] x[c+1]
         R x[4][4];                                        // x[f][c]
@@ -1100,7 +1005,7 @@ __global__ void __launch_bounds__(256, WPS) k_sweep_part_z(SweepParams<float> p,
         if (p.store_next) {
             if (__all(all_seg || !st_ok)) {
 #pragma unroll
-                for (int f = 0; f < 4; f++) pst4<FS3D_PART_AUX_ST>(Lnext, vo_st, so + (unsigned)f * fsb, x[f]);
+                for (int f = 0; f < 4; f++) pst4<PART_AUX_NT>(Lnext, vo_st, so + (unsigned)f * fsb, x[f]);
             } else {
 #pragma unroll
                 for (int f = 0; f < 4; f++)
@@ -1131,7 +1036,7 @@ __global__ void __launch_bounds__(256, WPS) k_sweep_part_z(SweepParams<float> p,
                     if (p.merge == 2) mvv = (mvv + x[f][c]) * R(0.5);
                     o4[c] = isin[c] ? mvv : L.tc[f].v[c];
                 }
-                pst4<FS3D_PART_AUX_ST>(Ltout, vo_st, so + (unsigned)f * fsb, o4);
+                pst4<PART_AUX_NT>(Ltout, vo_st, so + (unsigned)f * fsb, o4);
             }
         }
     };
@@ -1190,12 +1095,11 @@ template <int LPL, int NW = 1>
 static bool part_launch_z(fs3d_ctx *c, const SweepParams<float> &p)
 {
     constexpr int LI = 64 / LPL;
-    static const int lg_env = part_exp_env("FS3D_PART_ZLG", 0);
     const int rows = (p.dimy + LI - 1) / LI;              // rows of LI lines per plane
     const int npl = p.o_count ? p.o_count : p.dimx;
     // 8 rows per wave where the grid is large enough to give every CU several workgroups that way; fewer on small grids /
     // thin slabs (a 64^3 grid would otherwise launch 32 workgroups for 256 CUs)
-    int LG = lg_env > 0 ? lg_env : 16;                   // (r3) 16 rows per wave: 0.219 -> 0.207 ms at 256^3 (profiles/r3_ab_env.txt)
+    int LG = 16;                                         // (r3) 16 rows per wave: 0.219 -> 0.207 ms at 256^3 (profiles/r3_ab_env.txt)
     while (LG > 1 && (long long)((rows + LG - 1) / LG) * npl < 4096) LG >>= 1;
     if (LG > rows) LG = rows;
     const int n_grp = (rows + LG - 1) / LG;

@@ -31,9 +31,6 @@
 #include "fs3d_rows.h"
 
 #define PIPE_NW 8             // waves per workgroup of a whole sweep; the halves of short slab pieces use fewer (NW)
-#ifndef FS3D_Z_TILE_STORE
-#define FS3D_Z_TILE_STORE 1   // Z sweep: scatter through the LDS tile in whole 64-byte row pieces
-#endif
 
 
 // Compile-time loop: f(integral_constant<int, 0>) ... f(integral_constant<int, N-1>).  The sub-pass loops of the
@@ -150,12 +147,7 @@ typedef __amdgpu_buffer_rsrc_t rsrc_t;
 // VALU address arithmetic, and a store is masked by an out-of-range voffset instead of a branch.
 // Cache policy (aux operand: 2 = nt): `cur` is read once per sweep, `next` / `temp_out` are written once and read by the next launch
 // only (see kernels_part.hip); the temp loads stay cached (neighbour rows, second read of the O phase).  Hints only: same bits.
-#ifndef PIPE_AUX_CUR
-#define PIPE_AUX_CUR 2
-#endif
-#ifndef PIPE_AUX_ST
-#define PIPE_AUX_ST 2
-#endif
+constexpr int PIPE_AUX_NT = 2;
 template <typename R> struct Buf;
 template <> struct Buf<float> {
     template <int AUX = 0> static __device__ __forceinline__ float ld(rsrc_t r, unsigned vo, unsigned so) { return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, vo, so, AUX)); }
@@ -172,10 +164,7 @@ template <> struct Buf<double> {
 template <typename R, int DIR, int CH, int NW = PIPE_NW>
 struct Chunk {
     static constexpr int VW = 16 / sizeof(R);          // elements per 16-byte vector
-#ifndef FS3D_PC_BYTES_XY
-#define FS3D_PC_BYTES_XY 64
-#endif
-    static constexpr int PCB = DIR == 2 ? 64 : FS3D_PC_BYTES_XY;       // bytes of a line per sub-pass (Z: 64-byte row pieces)
+    static constexpr int PCB = 64;                     // bytes of a line per sub-pass (Z: 64-byte row pieces)
     static constexpr int PC = PCB / sizeof(R) < CH ? PCB / sizeof(R) : CH;   // cells per sub-pass
     static constexpr int NPASS = CH / PC;
     static constexpr int PR = PC / VW;                 // 16-byte pieces per tile row
@@ -236,7 +225,7 @@ struct Chunk {
     // Cells past the end of the line and lanes past the lane axis receive clamped (valid, meaningless) data.
     // EDGES (Z only): also fetch the lines just below/above the tile (-> tile rows 64 and 65 in land()).
     // HALO: also the two cells just outside [c0, c0+PC) on the own line (clamped into the line).
-    // AUX: cache policy of the loads (PIPE_AUX_CUR for the read-once `cur` fields)
+    // AUX: cache policy of the loads (PIPE_AUX_NT for the read-once `cur` fields)
     template <bool EDGES, bool HALO, int AUX = 0>
     __device__ __forceinline__ void issue(rsrc_t f, int dub, int c0, Raw &r) const
     {
@@ -310,7 +299,7 @@ struct Chunk {
     // covering 64/PC whole tile rows of PC contiguous cells (full 64-byte segments).
     __device__ __forceinline__ void store(rsrc_t f, unsigned fo, int c0, const R (&in)[PC], unsigned wmask, bool all) const
     {
-        if (DIR == 2 && FS3D_Z_TILE_STORE) {
+        if (DIR == 2) {
             constexpr int RPS = 64 / PC;                        // tile rows per store instruction
             const int col = lane % PC, rsub = lane / PC;
             R *const tcol = tile + lane * TSTRIDE;
@@ -337,13 +326,13 @@ struct Chunk {
                 const int row = r * RPS + rsub;
                 const R val = trow[r * RPS * TSTRIDE];
                 const bool ok = col_ok && row < rows_valid && ((tmask >> r) & 1u);
-                Buf<R>::template st<PIPE_AUX_ST>(f, ok ? (unsigned)(row * dimz + base(c0) + col) * (unsigned)sizeof(R) : BUF_OOB, row0 + fo, val);
+                Buf<R>::template st<PIPE_AUX_NT>(f, ok ? (unsigned)(row * dimz + base(c0) + col) * (unsigned)sizeof(R) : BUF_OOB, row0 + fo, val);
             }
         } else {
 #pragma unroll
             for (int t = 0; t < PC; t++) {
                 const bool ok = lane_valid && cell_ok(c0 + t) && ((wmask >> t) & 1u);
-                Buf<R>::template st<PIPE_AUX_ST>(f, ok ? vob : BUF_OOB, soff(c0 + t) + fo, in[t]);
+                Buf<R>::template st<PIPE_AUX_NT>(f, ok ? vob : BUF_OOB, soff(c0 + t) + fo, in[t]);
             }
         }
     }
@@ -351,11 +340,11 @@ struct Chunk {
     // live_only: solved values -- nothing is written on dead lines
     __device__ __forceinline__ void store_plain(rsrc_t f, unsigned fo, int c0, const R (&in)[PC], bool live_only = false) const
     {
-        if (DIR == 2 && FS3D_Z_TILE_STORE) store(f, fo, c0, in, dead ? 0u : 0xFFFFFFFFu, !(live_only && any_dead));
+        if (DIR == 2) store(f, fo, c0, in, dead ? 0u : 0xFFFFFFFFu, !(live_only && any_dead));
         else {
             const unsigned vo = live_only ? vob_live : vob_st;
 #pragma unroll
-            for (int t = 0; t < PC; t++) Buf<R>::template st<PIPE_AUX_ST>(f, vo, soff(c0 + t) + fo, in[t]);
+            for (int t = 0; t < PC; t++) Buf<R>::template st<PIPE_AUX_NT>(f, vo, soff(c0 + t) + fo, in[t]);
         }
     }
     // central difference along the sweep, in place: a[t] <- (a[t+1] - a[t-1]) / two_ds   (TimeLayer3D.h:338-340)
@@ -659,7 +648,7 @@ __global__ void __launch_bounds__(NW * 64, 2) k_sweep_pipe(SweepParams<R> p, int
             SB;
             // I6: temperature (cur layer)
             Raw rCT;
-            ck.template issue<false, false, PIPE_AUX_CUR>(Lcur, (int)(3 * fsb), c0, rCT);
+            ck.template issue<false, false, PIPE_AUX_NT>(Lcur, (int)(3 * fsb), c0, rCT);
             SB;
             // C5: temperature gradient along s (momentum RHS, AdiSolver3D.cpp:766/781/796)
             R gT[PC];
@@ -670,7 +659,7 @@ __global__ void __launch_bounds__(NW * 64, 2) k_sweep_pipe(SweepParams<R> p, int
             SB;
             // I7..I9 / C6..C9: the four `cur` fields -> right-hand sides
             Raw rC0, rC1, rC2;
-            ck.template issue<false, false, PIPE_AUX_CUR>(Lcur, 0, c0, rC0);
+            ck.template issue<false, false, PIPE_AUX_NT>(Lcur, 0, c0, rC0);
             SB;
             {
                 R cT[PC];
@@ -679,7 +668,7 @@ __global__ void __launch_bounds__(NW * 64, 2) k_sweep_pipe(SweepParams<R> p, int
                 for (int t = 0; t < PC; t++) { myD[(c0 + t) * 64] = divc<FM>(cT[t] * R(3), dDt, ok) + acc[t]; if (FM && (t & 3) == 3) SB; }   // T right-hand side -> LDS
             }
             SB;
-            ck.template issue<false, false, PIPE_AUX_CUR>(Lcur, (int)fsb, c0, rC1);
+            ck.template issue<false, false, PIPE_AUX_NT>(Lcur, (int)fsb, c0, rC1);
             SB;
             {
                 R cV[PC];
@@ -688,7 +677,7 @@ __global__ void __launch_bounds__(NW * 64, 2) k_sweep_pipe(SweepParams<R> p, int
                 for (int t = 0; t < PC; t++) { R d = divc<FM>(cV[t] * R(3), dDt, ok); if (DIR == 0) d = d - gT[t]; st1[c0 + t] = d; if (FM && (t & 3) == 3) SB; }
             }
             SB;
-            ck.template issue<false, false, PIPE_AUX_CUR>(Lcur, (int)(2 * fsb), c0, rC2);
+            ck.template issue<false, false, PIPE_AUX_NT>(Lcur, (int)(2 * fsb), c0, rC2);
             SB;
             {
                 R cV[PC];

@@ -532,9 +532,9 @@ def test_halo_planes_beside_the_interior_sweep(built, nranks):
 def test_results_do_not_depend_on_layout_padding_or_workgroup_schedule(built, tmp_path):
     """Every FS3D_* environment variable the production library reads is a speed knob: field padding / layer skew (fs3d_create) and
     the tiling of the X/Y kernels (FS3D_PART_VARIANT) -- the fields after two steps are bit-identical whatever they are set to (each
-    setting in a process of its own: the knobs are read once).  The kernel-experiment knobs (FS3D_PART_ORDER -- whose bits 1/2 skip
-    loads and give WRONG numbers --, _LDSPAD, _LATE_SLAB, _ZLG) exist only in -DFS3D_EXPERIMENTS builds (build.build_variant):
-    libfs3d_hip.so must not read them at all."""
+    setting in a process of its own: the knobs are read once).  The former kernel-experiment knobs (FS3D_PART_ORDER, _LDSPAD,
+    _LATE_SLAB, _ZLG) and the experiment-only chunk size (FS3D_PART_VARIANT=10) were removed from the library: setting them must
+    change nothing."""
     import subprocess
     import sys
     code = ("import sys, hashlib, numpy as np\n"
