@@ -118,6 +118,7 @@ struct fs3d_ctx {
     hipEvent_t ev_src = nullptr, ev_halo = nullptr;
     int opt_overlap = 1;                   // FS3D_OPT_OVERLAP
     int opt_keep_temp = 0;                 // FS3D_OPT_KEEP_TEMP
+    int opt_f64_part = 0;                  // FS3D_OPT_F64_PART
     // options
     int opt_kernel = FS3D_SWEEP_AUTO;
     int ran_kernel[3] = {0, 0, 0};   // per direction: the kernel the last sweep really ran (fs3d_last_sweep_kernel)
@@ -161,6 +162,7 @@ struct fs3d_ctx {
 template <typename R> void launch_sweep_line(fs3d_ctx *c, int dir, const SweepParams<R> &p);
 template <typename R> bool launch_sweep_pipe(fs3d_ctx *c, int dir, const SweepParams<R> &p); // false: dims unsupported
 // kernels_part.hip: partition (reduced-interface) solve, results to a stated tolerance; false: dims / precision unsupported
+// (double: only with c->opt_f64_part, and never for a slab)
 template <typename R> bool launch_sweep_part(fs3d_ctx *c, int dir, const SweepParams<R> &p);
 // X sweep halves of an x-slab for the bundles [b0, b1) (64 lines each, line = j*dimz + k); false: dims unsupported
 template <typename R> bool xslab_pipe_supported(const SweepParams<R> &p);

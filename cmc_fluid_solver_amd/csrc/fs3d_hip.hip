@@ -277,6 +277,7 @@ extern "C" fs3d_status fs3d_create(fs3d_ctx **out, int device, fs3d_precision pr
         const int v = atoi(e);
         if (v >= FS3D_SWEEP_AUTO && v <= FS3D_SWEEP_EXACT) c->opt_kernel = v;
     }
+    if (const char *e = getenv("FS3D_DEFAULT_F64_PART")) c->opt_f64_part = atoi(e) ? 1 : 0;   // initial FS3D_OPT_F64_PART of new contexts
 #define CK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { char b_[256]; snprintf(b_, sizeof b_, "GPU %d: %s failed: %s", device, #call, hipGetErrorString(e_)); g_create_err = b_; fs3d_destroy(c); return FS3D_ERR_HIP; } } while (0)
     CK(hipSetDevice(device));
     CK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
@@ -364,6 +365,7 @@ extern "C" fs3d_status fs3d_set_option(fs3d_ctx *c, int option, int value)
     case FS3D_OPT_DIV_CORE: c->opt_div_core = value ? 1 : 0; return FS3D_OK;
     case FS3D_OPT_OVERLAP: c->opt_overlap = value ? 1 : 0; return FS3D_OK;
     case FS3D_OPT_KEEP_TEMP: c->opt_keep_temp = value ? 1 : 0; return FS3D_OK;
+    case FS3D_OPT_F64_PART: c->opt_f64_part = value ? 1 : 0; return FS3D_OK;
     case FS3D_OPT_XSOLVE:
         if (value < 0 || value > 3) return fail(c, FS3D_ERR_INVALID, "bad cross-slab X solve id");
         c->opt_xsolve = value; return FS3D_OK;

@@ -1,4 +1,5 @@
-// Partition (reduced-interface) sweep kernels (FS3D_SWEEP_PART) for CDNA4 -- the production path for fp32.
+// Partition (reduced-interface) sweep kernels (FS3D_SWEEP_PART) for CDNA4 -- the production path for fp32, and for fp64
+// contexts that switch FS3D_OPT_F64_PART on (single-context form only; the end of this comment).
 //
 // What the reference does: one sequential Thomas recurrence per grid line (Common/Algorithms.h:21-38), rows from
 // BuildMatrix / ApplyBC0/1 (FluidSolver3D/AdiSolver3D.cpp:732-852), scatter + merge (UpdateSegment :707-730,
@@ -25,6 +26,15 @@
 //   piece; a wave-wide access is the whole contiguous line), neighbouring lines are further registers of the same
 //   lane.  Chunks of a line = lanes of a wave: the interface system is solved by parallel cyclic reduction across
 //   the lanes (shuffles), no LDS, no barrier, nothing resident but the lines in flight.
+// fp64 (FS3D_OPT_F64_PART = 1, a context that is not a slab; otherwise launch_sweep_part<double> says false and the exact
+//   kernels run): the same algebra on doubles, ~1e-15 from the sequential recurrence.  Reciprocals are
+//   v_rcp_f64 + two Newton steps, every quotient takes the same correction step as in fp32.
+//   X / Y: the same kernel, 256 VGPRs (two waves per SIMD instead of four: no scratch), lines of 4..256 cells; 32 lines x 4 / 8
+//   chunks up to 64 / 128 cells, 16 lines x 16 chunks (68 KiB of LDS, two workgroups per CU) up to 256.  Lines of 257..512
+//   cells are not taken (152 KiB of LDS at 16 lines, unmeasured): false.  No late start: measured slower in fp64 (X +5 %,
+//   Y +4 % per launch at 256^3, profiles/f64_part_tiles.txt).
+//   Z (k_sweep_part_z64): a 16-byte piece is TWO cells, a lane owns cells [2l, 2l+2): 128 cells per wave, 130..256 per pair of
+//   waves.  dimz even, 8 <= dimz <= 256, dimy >= 4; otherwise false.
 #include <algorithm>
 #include <atomic>
 #include <cstdlib>
@@ -65,7 +75,14 @@ __device__ __forceinline__ float prcp(float y)
     const float r = __builtin_amdgcn_rcpf(y);
     return __builtin_fmaf(__builtin_fmaf(-y, r, 1.0f), r, r);
 }
-__device__ __forceinline__ double prcp(double y) { return 1.0 / y; }
+// v_rcp_f64 + two Newton steps.  No scaling of the operand: the divisors of the elimination are diagonal entries
+// (3/dt + 2 vis, 1, 2 and what the recurrence makes of them) and 1 - (products below 1) of the cyclic reduction
+__device__ __forceinline__ double prcp(double y)
+{
+    double r = __builtin_amdgcn_rcp(y);
+    r = __builtin_fma(__builtin_fma(-y, r, 1.0), r, r);
+    return __builtin_fma(__builtin_fma(-y, r, 1.0), r, r);
+}
 __device__ __forceinline__ float pfma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
 __device__ __forceinline__ double pfma(double a, double b, double c) { return __builtin_fma(a, b, c); }
 
@@ -74,7 +91,7 @@ __device__ __forceinline__ double pfma(double a, double b, double c) { return __
 // perturbation of the advection coefficients and right-hand sides (like a slightly different h or dt) that does not
 // average out over the steps; with the correction the quotient is the correctly rounded one in all but rare cases.
 __device__ __forceinline__ float pdivc(float x, float y, float r) { const float q = x * r; return __builtin_fmaf(__builtin_fmaf(-y, q, x), r, q); }
-__device__ __forceinline__ double pdivc(double x, double y, double) { return x / y; }
+__device__ __forceinline__ double pdivc(double x, double y, double r) { const double q = x * r; return __builtin_fma(__builtin_fma(-y, q, x), r, q); }
 
 // Opaque copies: the compiler must not merge the (cheap) address / coefficient computations of different phases
 // into one computation whose results stay live -- in scratch memory -- from the first phase to the last.
@@ -178,8 +195,9 @@ __device__ __forceinline__ void part_step_vt(R lead_v, R diag_v, R trail_v, R le
 #define PART_EXW 18               // interface words per (line, chunk): 5 per matrix, 2 per right-hand side
 
 // order: bit 0 = tile order (below); 0x40 = late start, delay in bits 8+ (part_launch_xy)
+// launch bound: fp32 four waves per SIMD (128 VGPRs), fp64 two (256 VGPRs: at 128 the double instances spill ~550 bytes per lane)
 template <typename R, int DIR, int M, int NCH, int LT, int XB = 0>
-__global__ void __launch_bounds__(LT * NCH, 4) k_sweep_part(SweepParams<R> p, int n_o, int n_tiles, int order)
+__global__ void __launch_bounds__(LT * NCH, sizeof(R) == 8 ? 2 : 4) k_sweep_part(SweepParams<R> p, int n_o, int n_tiles, int order)
 {
     static_assert(DIR == 0 || DIR == 1, "lanes along k: X and Y sweeps");
     constexpr int PF = 2;                                // cells whose loads are in flight ahead of the cell being computed (P phase)
@@ -652,7 +670,8 @@ static bool part_launch_xy(fs3d_ctx *c, const SweepParams<R> &p)
     // solve and store at the same time (profiles/r2_variants.txt, r2_timeline.txt; interleaved on one box: 64 lines 6.12 ms per
     // step, 32 lines 5.81, 32 lines with the late start 5.63-5.66).  Few workgroups (thin slabs) and 512-cell lines: lane tiles fastest.
     // (the late start only where it was measured: 512-thread workgroups, two per CU, at least two generations of them)
-    const bool late = LT <= 32 && NCH == 16 && M == 16 && (long long)n_o * n_tiles >= 1024;
+    // fp64 (256-thread workgroups): the late start costs 4-9 % per launch, 32-line tiles win at 256^3 (X) and lose at 192^3: off, 16 lines
+    const bool late = sizeof(R) == 4 && LT <= 32 && NCH == 16 && M == 16 && (long long)n_o * n_tiles >= 1024;
     const int order = LT <= 32 ? (((long long)n_o * n_tiles < 1024 || NCH == 32) ? 1 : 0) | (late ? 0x40 | (4 << 8) : 0) : 0;
     hipLaunchKernelGGL((k_sweep_part<R, DIR, M, NCH, LT, XB>), dim3((unsigned)(n_o * n_tiles)), dim3(LT * NCH), lds, c->stream, p, n_o, n_tiles, order);
     return true;
@@ -663,7 +682,15 @@ static bool part_dispatch_xy(fs3d_ctx *c, const SweepParams<R> &p)
 {
     const int n = DIR == 0 ? p.dimx : p.dimy;
     if (n < 4) return false;
-    if constexpr (std::is_same<R, float>::value) {       // fp64 contexts run the exact kernels
+    if constexpr (std::is_same<R, double>::value) {
+        // fp64 (FS3D_OPT_F64_PART; launch_sweep_part lets only the single-context form through): 68 KiB of LDS per workgroup at
+        // 32 lines x 8 chunks and at 16 lines x 16 chunks, 256 threads, two workgroups per CU
+        if (n <= 64) return part_launch_xy<R, DIR, 16, 4, 32>(c, p);
+        if (n <= 128) return part_launch_xy<R, DIR, 16, 8, 32>(c, p);
+        if (n <= 256) return part_launch_xy<R, DIR, 16, 16, 16>(c, p);
+        return false;
+    }
+    if constexpr (std::is_same<R, float>::value) {
         static const int variant = getenv("FS3D_PART_VARIANT") ? atoi(getenv("FS3D_PART_VARIANT")) : 0;   // 16 / 32 / 64 lines per workgroup: same chunks, same arithmetic, same bits (tested)
         if (DIR == 0 && p.xiface_pass) {
             // first pass of the cross-slab sweep: the slab's interface words (whole chunks only)
@@ -1121,13 +1148,384 @@ static bool part_dispatch_z(fs3d_ctx *c, const SweepParams<float> &p)
     if (n <= 512) return part_launch_z<64, 2>(c, p);       // a pair of waves per line
     return false;
 }
-static bool part_dispatch_z(fs3d_ctx *, const SweepParams<double> &) { return false; }
+// ------------------------------------------------------------------------------------------------------------
+// Z sweep, fp64: lanes along the line, TWO cells per lane
+// ------------------------------------------------------------------------------------------------------------
+// The scheme of k_sweep_part_z with a 16-byte piece of two doubles: lane l owns cells [2l, 2l+2) (four fp64 cells per lane
+// with two rows in flight: ~210 VGPRs of loaded values alone).  A wave holds 128 cells; LPL = 16 / 32 / 64 lanes per line for dimz <= 32 /
+// 64 / 128, a pair of waves (NW == 2, the join of k_sweep_part_z) for 130..256.  A chunk of two cells has ONE cell before its
+// interface cell: the down-sweep and the up-sweep over it are the same single step (x[0] = d/b - (a/b) X_left - (c/b) X), so
+// one step serves both.  Cross-lane moves carry 32 bits: every shuffle of a value is two moves; no packed arithmetic.
+struct PV2 { double v[2]; };
+template <int AUX = 0>
+__device__ __forceinline__ PV2 pld2(prsrc_t r, unsigned vo, unsigned so)
+{
+    const pu32x4 q = __builtin_amdgcn_raw_buffer_load_b128(r, vo, so, AUX);
+    PV2 o;
+    __builtin_memcpy(o.v, &q, 16);
+    return o;
+}
+template <int AUX = 0>
+__device__ __forceinline__ void pst2(prsrc_t r, unsigned vo, unsigned so, const double (&v)[2])
+{
+    pu32x4 q;
+    __builtin_memcpy(&q, v, 16);
+    __builtin_amdgcn_raw_buffer_store_b128(q, r, vo, so, AUX);
+    // the wait states of pst4: the hazard is the 16-byte store with a scalar offset, whatever the element type
+    asm volatile("s_nop 1" : : "v"(q.x), "v"(q.y), "v"(q.z), "v"(q.w));
+}
+
+struct ZLine64 { PV2 tc[4], cu[4], wim, wip, wjm, wjp; unsigned code; double nve[4], nb[4]; };   // wjm/wjp: LI > 1; nb: NW == 2
+
+template <int LPL, int NW = 1>
+__global__ void __launch_bounds__(256, 2) k_sweep_part_z64(SweepParams<double> p, int n_grp, int LG)
+{
+    typedef double R;
+    static_assert(NW == 1 || (NW == 2 && LPL == 64), "a pair of waves per line: 64 lanes each");
+    constexpr int LI = 64 / LPL;                        // lines per wave-wide access
+    const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int l = lane % LPL, sub = lane / LPL;
+    const int hi = NW == 2 ? (w & 1) : 0;               // upper half of the line
+    const int gl = l + 64 * hi;                         // position of this lane's piece along the line
+    __shared__ double zx1[2][8], zx2[2][2][8];          // NW == 2: [pair][..] exchange buffers
+    int lb = blockIdx.x;
+    {
+        const int nb = gridDim.x, q = nb >> 3, r = nb & 7, x = lb & 7, slot = lb >> 3;
+        lb = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + slot;
+    }
+    // task = (group of LG*LI lines, plane): consecutive tasks = consecutive planes of one line group
+    const int task = NW == 2 ? lb * 2 + (w >> 1) : lb * 4 + w;
+    const int npl = p.dimx;                             // single-context form: every plane
+    int grp = task / npl;
+    const int i = task - grp * npl;
+    bool task_ok = true;
+    if (NW == 1) { if (grp >= n_grp) return; }          // whole wave (wave-uniform)
+    else { task_ok = grp < n_grp; grp = task_ok ? grp : n_grp - 1; }   // the pairs of a workgroup meet at barriers: a pair past the end runs along, stores nothing
+    const int n = p.dimz;                               // even
+    const int j0 = grp * LG * LI;
+    const bool l_ok = 2 * gl < n;
+    const int lc = l_ok ? gl : (n / 2 - 1);
+    const unsigned fsb = (unsigned)(p.fstride * 8ll), nsb = (unsigned)(p.nstride * 8ll);
+    const unsigned rowb = (unsigned)p.dimz * 8u, planeb = (unsigned)(p.plane * 8ll);
+    const unsigned lbytes = 4u * fsb;
+    const prsrc_t Lcur = __builtin_amdgcn_make_buffer_rsrc((void *)(p.cur_ - p.plane), 0, (int)lbytes, 0x00020000);
+    const prsrc_t Ltmp = __builtin_amdgcn_make_buffer_rsrc((void *)(p.temp_ - p.plane), 0, (int)lbytes, 0x00020000);
+    const prsrc_t Lnext = __builtin_amdgcn_make_buffer_rsrc((void *)(p.next_ - p.plane), 0, (int)lbytes, 0x00020000);
+    const prsrc_t Ltout = __builtin_amdgcn_make_buffer_rsrc((void *)(p.temp_out_ - p.plane), 0, (int)lbytes, 0x00020000);
+    const prsrc_t rNode = __builtin_amdgcn_make_buffer_rsrc((void *)p.node_, 0, (int)(4u * nsb), 0x00020000);
+    const prsrc_t rCode = __builtin_amdgcn_make_buffer_rsrc((void *)p.code, 0, (int)(nsb / 4u), 0x00020000);
+
+    const R h2s = p.two_ds[2], h2o = p.two_ds[0], h2l = p.two_ds[1], dtv = p.dt;
+    const R ir2s = R(1) / h2s, ir2o = R(1) / h2o, ir2l = R(1) / h2l, irdt = R(1) / dtv;
+    const R vis_v = p.vis_v, vis_t = p.vis_t, b_v = p.b_v, b_t = p.b_t;
+
+    // byte offset of (plane i, line j, cell 0) inside a layer field (one halo plane first) / inside the node arrays
+    auto line_so = [&](int j) __attribute__((always_inline)) { return (unsigned)(((long long)(i + 1) * p.plane + (long long)j * p.dimz) * 8ll); };
+    auto line_son = [&](int j) __attribute__((always_inline)) { return (unsigned)(((long long)i * p.plane + (long long)j * p.dimz) * 8ll); };
+    const unsigned vo_l = (unsigned)(sub * p.dimz + 2 * lc) * 8u;          // per-lane bytes: own line of the row, own piece
+    // the two lanes that hold the ends of the line (cell 0: START or SKIP; cell n-1: END or SKIP) fetch that cell's node
+    // values with the line's other loads (n >= 8: never the same lane)
+    const bool is_end = l_ok && (gl == 0 || gl == n / 2 - 1);
+    const int ec = gl == 0 ? 0 : 1;
+    const unsigned vo_e = is_end ? vo_l + 8u * (unsigned)ec : PART_OOB;
+    // NW == 2: the cell across the cut between the two waves (cell 127 for the upper wave's first lane, 128 for the lower
+    // wave's last lane; n >= 130: both exist) comes with the line's other loads
+    const bool at_cut = NW == 2 && (hi ? l == 0 : l == 63);
+    const unsigned vo_nb = at_cut ? (hi ? 127u * 8u : 128u * 8u) : PART_OOB;
+
+    auto issue = [&](int jrow, ZLine64 &L) __attribute__((always_inline)) {
+        // jrow: first line of the row (wave-uniform); this lane's line is jrow + sub.  A row that starts past the plane (tail of
+        // the last group) is clamped; the lines jrow + sub past the plane read the next plane / the halo plane behind the last
+        // one: valid addresses (out-of-range ones return 0), nothing stored
+        const int jr = jrow < p.dimy ? jrow : p.dimy - 1;
+        const unsigned so = opq_s(line_so(jr));
+        L.tc[2] = pld2(Ltmp, vo_l, so + 2u * fsb);       // W first (cached: the rows j+-1 and planes i+-1 read it again as their neighbour)
+        L.tc[0] = pld2<PART_AUX_NT>(Ltmp, vo_l, so); L.tc[1] = pld2<PART_AUX_NT>(Ltmp, vo_l, so + fsb); L.tc[3] = pld2<PART_AUX_NT>(Ltmp, vo_l, so + 3u * fsb);
+#pragma unroll
+        for (int f = 0; f < 4; f++) L.cu[f] = pld2<PART_AUX_NT>(Lcur, vo_l, so + (unsigned)f * fsb);
+        L.wim = pld2(Ltmp, vo_l, so + 2u * fsb - planeb); L.wip = pld2(Ltmp, vo_l, so + 2u * fsb + planeb);
+        if (LI > 1) { L.wjm = pld2(Ltmp, vo_l, so + 2u * fsb - rowb); L.wjp = pld2(Ltmp, vo_l, so + 2u * fsb + rowb); }
+        const unsigned son = opq_s(line_son(jr));
+        L.code = __builtin_amdgcn_raw_buffer_load_b32(rCode, vo_l / 4u, son / 4u, 0);
+#pragma unroll
+        for (int f = 0; f < 4; f++) L.nve[f] = PBuf<R>::ld(rNode, vo_e, son + (unsigned)f * nsb);     // other lanes: out of range, no memory access
+        if (NW == 2) {
+#pragma unroll
+            for (int f = 0; f < 4; f++) L.nb[f] = PBuf<R>::ld(Ltmp, vo_nb, so + (unsigned)f * fsb);
+        }
+    };
+
+    // wjm / wjp: W of the lines j-1 / j+1 (LI == 1: the neighbouring rows' registers; else loaded with the line)
+    auto process = [&](int jrow, const ZLine64 &L, const PV2 &wjm, const PV2 &wjp) __attribute__((always_inline)) {
+        const int j = jrow + sub;
+        const bool st_ok = l_ok && j < p.dimy && task_ok; // lines past the plane compute on whatever was loaded, nothing is stored
+        const unsigned so = opq_s(line_so(jrow)), son = opq_s(line_son(jrow));
+        // ---- codes
+        int code4[2]; bool isin[2], seg[2], inter[2];
+#pragma unroll
+        for (int c = 0; c < 2; c++) {
+            int cw = (int)(L.code >> (16 * c)) & 0xFFFF;
+            cw = l_ok ? cw : 0;
+            code4[c] = (cw >> 8) & 0xF;
+            isin[c] = ((cw >> CODE_TYPE_SHIFT) & 3) == FS3D_NODE_IN && l_ok;
+            inter[c] = (code4[c] & 3) == ROW_INTERIOR;
+            seg[c] = (code4[c] & 3) != ROW_SKIP;
+        }
+        // ---- rows: neighbours along the line from the lanes next door
+        R q[2], d[4][2];                                  // d[f][c]
+        {
+            R tm1[4], tp2[4];                             // cell 2l-1 and cell 2l+2 of U, V, W, T
+#pragma unroll
+            for (int f = 0; f < 4; f++) {
+                tm1[f] = __shfl_up(L.tc[f].v[1], 1, LPL); tp2[f] = __shfl_down(L.tc[f].v[0], 1, LPL);
+                if (NW == 2) { tm1[f] = (at_cut && hi) ? L.nb[f] : tm1[f]; tp2[f] = (at_cut && !hi) ? L.nb[f] : tp2[f]; }
+            }
+#pragma unroll
+            for (int c = 0; c < 2; c++) {
+                R g[4];
+#pragma unroll
+                for (int f = 0; f < 4; f++) {
+                    const R lo = c == 0 ? tm1[f] : L.tc[f].v[0], up = c == 1 ? tp2[f] : L.tc[f].v[1];
+                    g[f] = pdivc(up - lo, h2s, ir2s);     // d/dz of U, V, W, T
+                }
+                const R x1 = pdivc(L.wip.v[c] - L.wim.v[c], h2o, ir2o), x2 = pdivc(wjp.v[c] - wjm.v[c], h2l, ir2l);   // dW/dx, dW/dy
+                const R diss = (((g[0] * g[0] + g[1] * g[1]) + R(2) * g[2] * g[2]) + g[0] * x1) + g[1] * x2;   // DissFuncZ (TimeLayer3D.h:578-588)
+                q[c] = pdivc(L.tc[2].v[c], h2s, ir2s);
+                d[0][c] = pdivc(L.cu[0].v[c] * R(3), dtv, irdt); d[1][c] = pdivc(L.cu[1].v[c] * R(3), dtv, irdt);
+                d[2][c] = pfma(-p.v_T, g[3], pdivc(L.cu[2].v[c] * R(3), dtv, irdt));
+                d[3][c] = pfma(p.t_phi, diss, pdivc(L.cu[3].v[c] * R(3), dtv, irdt));
+            }
+        }
+        PMat<R> mv[2], mt[2];
+#pragma unroll
+        for (int c = 0; c < 2; c++) part_coefs<R, false>(q[c], 0, vis_v, b_v, vis_t, b_t, mv[c], mt[c]);
+        {
+            // Rows that are not INTERIOR: the ends of every line (node values came with the line) and, rarely, obstacles /
+            // lanes past the line (their node values are fetched here).  Per cell slot c a wave-uniform test.
+            bool slow = false;
+#pragma unroll
+            for (int c = 0; c < 2; c++) {
+                const int kind = code4[c] & 3;
+                slow = slow || ((kind == ROW_START || kind == ROW_END) && !(is_end && c == ec));
+            }
+            PV2 nv[4];
+            if (__any(slow)) {
+#pragma unroll
+                for (int f = 0; f < 4; f++) nv[f] = pld2(rNode, vo_l, son + (unsigned)f * nsb);
+            }
+#pragma unroll
+            for (int c = 0; c < 2; c++) {
+                if (__any(!inter[c])) {
+                    const int kind = code4[c] & 3;
+                    const bool ns_v = kind != ROW_SKIP && !(code4[c] & ROW_VELFREE), ns_t = kind != ROW_SKIP && !(code4[c] & ROW_TEMPFREE);
+                    const bool pre = is_end && c == ec;
+                    part_coefs<R, true>(q[c], code4[c], vis_v, b_v, vis_t, b_t, mv[c], mt[c]);
+#pragma unroll
+                    for (int f = 0; f < 3; f++) d[f][c] = inter[c] ? d[f][c] : (ns_v ? (pre ? L.nve[f] : nv[f].v[c]) : R(0));
+                    d[3][c] = inter[c] ? d[3][c] : (ns_t ? (pre ? L.nve[3] : nv[3].v[c]) : R(0));
+                }
+            }
+        }
+        // ---- chunk elimination: the one step over cell 0 -- x[0] = dp - lp X_left - cp X (down-sweep) = ep - ap X_left - up X (up-sweep)
+        R cpv = R(0), lpv = R(-1), cpt = R(0), lpt = R(-1), dp3[3] = {R(0), R(0), R(0)}, dp1[1] = {R(0)};
+        { const R dd3[3] = {d[0][0], d[1][0], d[2][0]}, dd1[1] = {d[3][0]}; part_step_vt<R, false>(mv[0].a, mv[0].b, mv[0].c, mt[0].a, mt[0].b, mt[0].c, cpv, cpt, lpv, lpt, dp3, dp1, dd3, dd1); }
+        // ---- interface row (cell 1) with x[0] eliminated and x_first of the next lane substituted; normalised
+        R av, cv_, at, ct_, dd[4];
+        {
+            R nvf = __shfl_down(lpv, 1, LPL), nwf = __shfl_down(cpv, 1, LPL), ntf = __shfl_down(lpt, 1, LPL), nuf = __shfl_down(cpt, 1, LPL);
+            R ng0 = __shfl_down(dp3[0], 1, LPL), ng1 = __shfl_down(dp3[1], 1, LPL), ng2 = __shfl_down(dp3[2], 1, LPL), ng3 = __shfl_down(dp1[0], 1, LPL);
+            if (NW == 2) {
+                // the lower wave's last lane takes the first-cell coefficients of the upper wave's first lane
+                double *const b = zx1[w >> 1];
+                if (hi && l == 0) { b[0] = lpv; b[1] = cpv; b[2] = lpt; b[3] = cpt; b[4] = dp3[0]; b[5] = dp3[1]; b[6] = dp3[2]; b[7] = dp1[0]; }
+                __syncthreads();
+                if (at_cut && !hi) { nvf = b[0]; nwf = b[1]; ntf = b[2]; nuf = b[3]; ng0 = b[4]; ng1 = b[5]; ng2 = b[6]; ng3 = b[7]; }
+            }
+            const bool last = NW == 2 ? (hi && l == 63) : l == LPL - 1;   // no lane behind: its first cell does not exist (the row has c = 0 anyway)
+            const R clv = last ? R(0) : mv[1].c, clt = last ? R(0) : mt[1].c;
+            const R lov = -mv[1].a * lpv, div = pfma(-clv, nvf, pfma(-mv[1].a, cpv, mv[1].b)), upv_ = -clv * nwf;
+            const R lot = -mt[1].a * lpt, dit = pfma(-clt, ntf, pfma(-mt[1].a, cpt, mt[1].b)), upt_ = -clt * nuf;
+            const R rv = prcp(div), rt = prcp(dit);
+            av = pquot(lov, div, rv); cv_ = pquot(upv_, div, rv); at = pquot(lot, dit, rt); ct_ = pquot(upt_, dit, rt);
+            dd[0] = pquot(pfma(-clv, ng0, pfma(-mv[1].a, dp3[0], d[0][1])), div, rv);
+            dd[1] = pquot(pfma(-clv, ng1, pfma(-mv[1].a, dp3[1], d[1][1])), div, rv);
+            dd[2] = pquot(pfma(-clv, ng2, pfma(-mv[1].a, dp3[2], d[2][1])), div, rv);
+            dd[3] = pquot(pfma(-clt, ng3, pfma(-mt[1].a, dp1[0], d[3][1])), dit, rt);
+        }
+        // NW == 2: the coupling across the cut leaves the wave's system and becomes a right-hand side of its own
+        // (x_l = X_l - Z * E_l with Z the unknown on the other side of the cut)
+        R ev = R(0), et = R(0);
+        if (NW == 2) {
+            if (at_cut && !hi) { ev = cv_; et = ct_; cv_ = R(0); ct_ = R(0); }
+            if (at_cut && hi) { ev = av; et = at; av = R(0); at = R(0); }
+        }
+        // ---- parallel cyclic reduction over the LPL lanes of the line, one scalar reduction per matrix
+#pragma unroll
+        for (int s = 1; s < LPL; s <<= 1) {
+            // lanes without a partner at this distance: their a (c) is zero by now, the partner values must only be finite
+            const bool has_m = l >= s, has_p = l + s < LPL;
+            const R a_v = has_m ? av : R(0), c_v = has_p ? cv_ : R(0), a_t = has_m ? at : R(0), c_t = has_p ? ct_ : R(0);
+            const R dnv = pfma(-a_v, __shfl_up(cv_, s, LPL), pfma(-c_v, __shfl_down(av, s, LPL), R(1)));
+            const R dnt = pfma(-a_t, __shfl_up(ct_, s, LPL), pfma(-c_t, __shfl_down(at, s, LPL), R(1)));
+            const R rv = prcp(dnv), rt = prcp(dnt);
+            R nd[4];
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const R a = k < 3 ? a_v : a_t, c = k < 3 ? c_v : c_t;
+                nd[k] = pquot(pfma(-a, __shfl_up(dd[k], s, LPL), pfma(-c, __shfl_down(dd[k], s, LPL), dd[k])), k < 3 ? dnv : dnt, k < 3 ? rv : rt);
+            }
+            if (NW == 2) {
+                const R nev = pquot(pfma(-a_v, __shfl_up(ev, s, LPL), pfma(-c_v, __shfl_down(ev, s, LPL), ev)), dnv, rv);
+                const R net = pquot(pfma(-a_t, __shfl_up(et, s, LPL), pfma(-c_t, __shfl_down(et, s, LPL), et)), dnt, rt);
+                ev = nev; et = net;
+            }
+            const R nav = pquot(-a_v * __shfl_up(av, s, LPL), dnv, rv), ncv = pquot(-c_v * __shfl_down(cv_, s, LPL), dnv, rv);
+            const R nat = pquot(-a_t * __shfl_up(at, s, LPL), dnt, rt), nct = pquot(-c_t * __shfl_down(ct_, s, LPL), dnt, rt);
+            av = nav; cv_ = ncv; at = nat; ct_ = nct;
+#pragma unroll
+            for (int k = 0; k < 4; k++) dd[k] = nd[k];
+        }
+        // ---- back-substitution: x[1] = X, x[0] = d'[0] - l[0] X_left - c'[0] X
+        R x[4][2];                                        // x[f][c]
+        {
+            R xcut[4] = {R(0), R(0), R(0), R(0)};         // NW == 2, upper wave: the lower wave's last unknown
+            if (NW == 2) {
+                // join the halves: X = Xd - Y0 E_lo, Y = Yd - X63 E_hi  ->  per right-hand side a 2x2 system in (X63, Y0)
+                double *const bl = zx2[w >> 1][0], *const bh = zx2[w >> 1][1];
+                if (at_cut) { double *const b = hi ? bh : bl; b[0] = dd[0]; b[1] = dd[1]; b[2] = dd[2]; b[3] = dd[3]; b[4] = ev; b[5] = et; }
+                __syncthreads();
+                const R elv = bl[4], elt = bl[5], ehv = bh[4], eht = bh[5];
+                const R rdv = prcp(pfma(-elv, ehv, R(1))), rdt = prcp(pfma(-elt, eht, R(1)));
+#pragma unroll
+                for (int k = 0; k < 4; k++) {
+                    const R el = k < 3 ? elv : elt, eh = k < 3 ? ehv : eht, den = pfma(-el, eh, R(1));
+                    const R x63 = pquot(pfma(-el, bh[k], bl[k]), den, k < 3 ? rdv : rdt);
+                    const R y0 = pfma(-x63, eh, bh[k]);
+                    dd[k] = pfma(-(hi ? x63 : y0), k < 3 ? ev : et, dd[k]);
+                    xcut[k] = x63;
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                R xl = __shfl_up(dd[k], 1, LPL);
+                xl = l == 0 ? (NW == 2 && hi ? xcut[k] : R(0)) : xl;
+                x[k][1] = dd[k];
+                x[k][0] = pfma(-(k < 3 ? cpv : cpt), dd[k], pfma(-(k < 3 ? lpv : lpt), xl, k < 3 ? dp3[k] : dp1[0]));
+            }
+        }
+        // ---- scatter + merge
+        const unsigned vo_st = st_ok ? vo_l : PART_OOB;
+        const bool all_seg = seg[0] && seg[1];
+        if (p.store_next) {
+            if (__all(all_seg || !st_ok)) {
+#pragma unroll
+                for (int f = 0; f < 4; f++) pst2<PART_AUX_NT>(Lnext, vo_st, so + (unsigned)f * fsb, x[f]);
+            } else {
+#pragma unroll
+                for (int f = 0; f < 4; f++)
+#pragma unroll
+                    for (int c = 0; c < 2; c++)
+                        PBuf<R>::st(Lnext, seg[c] ? vo_st : PART_OOB, so + (unsigned)f * fsb + 8u * (unsigned)c, x[f][c]);
+            }
+        }
+        if (p.merge) {
+            const bool stale = (isin[0] && !seg[0]) || (isin[1] && !seg[1]);
+            if (__any(stale)) {
+                // NODE_IN cell outside every segment: the reference merges the stale `next` value (Grid3D.cpp:87-117)
+#pragma unroll
+                for (int f = 0; f < 4; f++) {
+                    const PV2 sv = pld2(Lnext, vo_l, so + (unsigned)f * fsb);
+#pragma unroll
+                    for (int c = 0; c < 2; c++) x[f][c] = (isin[c] && !seg[c]) ? sv.v[c] : x[f][c];
+                }
+            }
+#pragma unroll
+            for (int f = 0; f < 4; f++) {
+                R o2[2];
+#pragma unroll
+                for (int c = 0; c < 2; c++) {
+                    R mvv = (L.tc[f].v[c] + x[f][c]) * R(0.5);       // MergeFieldTo (TimeLayer3D.h:415-436)
+                    if (p.merge == 2) mvv = (mvv + x[f][c]) * R(0.5);
+                    o2[c] = isin[c] ? mvv : L.tc[f].v[c];
+                }
+                pst2<PART_AUX_NT>(Ltout, vo_st, so + (unsigned)f * fsb, o2);
+            }
+        }
+    };
+
+    // ---- the rows of this wave's group, two per trip, the next row's loads in flight (the loop of k_sweep_part_z)
+    ZLine64 La, Lb;
+    PV2 wprev, wedge;
+    if (LI == 1) {
+        wprev = pld2(Ltmp, vo_l, opq_s(line_so(j0)) + 2u * fsb - rowb);
+        const int jl = j0 + LG < p.dimy ? j0 + LG : p.dimy - 1;
+        wedge = pld2(Ltmp, vo_l, opq_s(line_so(jl)) + 2u * fsb);
+    }
+    issue(j0, La);
+    for (int r = 0; r < LG; r += 2) {
+        const int ja = j0 + r * LI, jb = ja + LI, jc = jb + LI;
+        if (r + 1 < LG) issue(jb, Lb);
+        __builtin_amdgcn_sched_barrier(0);
+        if (LI == 1) {
+            PV2 wn = wedge;
+            if (r + 1 < LG) wn = Lb.tc[2];
+            process(ja, La, wprev, wn);
+            wprev = La.tc[2];
+        }
+        else process(ja, La, La.wjm, La.wjp);
+        __builtin_amdgcn_sched_barrier(0);
+        if (r + 1 < LG) {
+            if (r + 2 < LG) issue(jc, La);
+            __builtin_amdgcn_sched_barrier(0);
+            if (LI == 1) {
+                PV2 wn = wedge;
+                if (r + 2 < LG) wn = La.tc[2];
+                process(jb, Lb, wprev, wn);
+                wprev = Lb.tc[2];
+            }
+            else process(jb, Lb, Lb.wjm, Lb.wjp);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+}
+
+template <int LPL, int NW = 1>
+static bool part_launch_z64(fs3d_ctx *c, const SweepParams<double> &p)
+{
+    constexpr int LI = 64 / LPL;
+    const int rows = (p.dimy + LI - 1) / LI;              // rows of LI lines per plane
+    // rows per wave as in part_launch_z: 16 where that still gives every CU several workgroups
+    int LG = 16;
+    while (LG > 1 && (long long)((rows + LG - 1) / LG) * p.dimx < 4096) LG >>= 1;
+    if (LG > rows) LG = rows;
+    const int n_grp = (rows + LG - 1) / LG;
+    const long long tasks = (long long)n_grp * p.dimx;
+    const int tpw = NW == 2 ? 2 : 4;                      // tasks per workgroup of four waves
+    hipLaunchKernelGGL((k_sweep_part_z64<LPL, NW>), dim3((unsigned)((tasks + tpw - 1) / tpw)), dim3(256), 0, c->stream, p, n_grp, LG);
+    return true;
+}
+
+static bool part_dispatch_z(fs3d_ctx *c, const SweepParams<double> &p)
+{
+    const int n = p.dimz;
+    if (n % 2 != 0 || n < 8) return false;                // whole 16-byte pieces of two cells
+    if (p.dimy < 4) return false;
+    if (n <= 32) return part_launch_z64<16>(c, p);
+    if (n <= 64) return part_launch_z64<32>(c, p);
+    if (n <= 128) return part_launch_z64<64>(c, p);
+    if (n <= 256) return part_launch_z64<64, 2>(c, p);     // a pair of waves per line
+    return false;
+}
 
 // false: dims / precision / slab configuration not covered -> the caller falls back to the exact kernels
 template <typename R>
 bool launch_sweep_part(fs3d_ctx *c, int dir, const SweepParams<R> &p)
 {
     if ((unsigned long long)p.fstride * 4ull * sizeof(R) >= (1ull << 32)) return false;   // 32-bit buffer offsets span a layer
+    // fp64: only where the context asks for it (FS3D_OPT_F64_PART), and only the single-context form -- no sweep of a slab
+    // (a group's rank, ghost planes, a range of planes beside the halo exchange, either pass of the cross-slab X sweep)
+    if (std::is_same<R, double>::value &&
+        (!c->opt_f64_part || c->nranks > 1 || p.ghost_lo || p.ghost_hi || p.o_begin || p.o_count || p.xiface_pass || p.carry_in || p.xcarry_in)) return false;
     if (dir == 0 && (p.ghost_lo || p.ghost_hi) && !(p.carry_in && p.xcarry_in) && !p.xiface_pass) return false;   // X sweep of an x-slab: only with the values below / above the slab given
     if (dir == 0) return part_dispatch_xy<R, 0>(c, p);
     if (dir == 1) return part_dispatch_xy<R, 1>(c, p);

@@ -51,12 +51,14 @@ enum { FS3D_VAR_U = 0, FS3D_VAR_V = 1, FS3D_VAR_W = 2, FS3D_VAR_T = 3 };
 
 /* kernel selection for the line sweeps (fs3d_set_option(FS3D_OPT_SWEEP_KERNEL)) */
 enum {
-    FS3D_SWEEP_AUTO = 0,      /* fastest kernel that supports the dims: PART where it applies (fp32), else as EXACT */
+    FS3D_SWEEP_AUTO = 0,      /* fastest kernel that supports the dims: PART where it applies (fp32; fp64 only with
+                                 FS3D_OPT_F64_PART, direction by direction), else as EXACT */
     FS3D_SWEEP_LINE = 1,      /* thread-per-line Thomas, c'/d' scratch in HBM (any dims); bit-equal to the CPU path */
     FS3D_SWEEP_PIPE = 2,      /* wave-pipelined Thomas, c'/d' in registers+LDS; bit-equal to the CPU path */
     FS3D_SWEEP_PART = 3,      /* partition (reduced-interface) solve: every chunk of a line eliminated at once; same
                                  equations, different rounding -- equal to the CPU path to a stated tolerance
-                                 (DESIGN.md section 5), not bit for bit; errors where it does not apply */
+                                 (DESIGN.md section 5), not bit for bit; errors where it does not apply (an fp64 context
+                                 without FS3D_OPT_F64_PART; dims outside the kernels) */
     FS3D_SWEEP_EXACT = 4      /* fastest of the bit-exact kernels (PIPE, its segmented form, LINE) */
 };  /* environment FS3D_DEFAULT_KERNEL=<id> sets the initial value of FS3D_OPT_SWEEP_KERNEL for new contexts */
 enum {
@@ -74,8 +76,17 @@ enum {
                                  reads it: the next step starts from temp := cur (AdiSolver3D.cpp:320), GetLayer and EvalDivError read
                                  `next`; FS3D_LAYER_TEMP then holds the iterate before that last merge.  1: store it, as the
                                  reference's private `temp` member holds it after TimeStep (the parity tests that download it) */
-    FS3D_OPT_DIV_CORE = 2     /* 1 (default): fp32 pipe kernel divides with the scaling-free core of the IEEE expansion and
+    FS3D_OPT_DIV_CORE = 2,    /* 1 (default): fp32 pipe kernel divides with the scaling-free core of the IEEE expansion and
                                  falls back to the full division where an operand needs scaling (same results); 0: always full */
+    FS3D_OPT_F64_PART = 6     /* fp64 contexts only (accepted and without effect in fp32).  0 (default): fp64 runs the bit-exact kernels,
+                                 FS3D_SWEEP_PART fails with FS3D_ERR_UNSUPPORTED.  1: the fp64 partition kernels are open -- FS3D_SWEEP_AUTO
+                                 runs them in every direction where they apply and falls back to the bit-exact kernels direction by
+                                 direction where they do not; FS3D_SWEEP_PART runs them or fails, never falls back.  They apply to
+                                 X / Y lines of 4..256 cells and to Z lines of 8..256 cells with dimz even and dimy >= 4 (longer
+                                 lines: bit-exact kernels).  Results equal the CPU path to ~1e-15, not bit for bit.
+                                 No effect on slab contexts (a multi-GPU group, or a context with a neighbouring slab's ghost planes):
+                                 fp64 slabs keep the bit-exact Y / Z kernels and their cross-slab X solve.
+                                 Environment FS3D_DEFAULT_F64_PART=1 sets the initial value for new contexts */
 };
 
 /* ---- lifetime ---------------------------------------------------------------
