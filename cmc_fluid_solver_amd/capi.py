@@ -21,6 +21,7 @@ SWEEP_AUTO, SWEEP_LINE, SWEEP_PIPE, SWEEP_PART, SWEEP_EXACT = 0, 1, 2, 3, 4
 KERNEL_NAMES = {0: "none", 1: "line", 2: "pipe", 3: "part"}
 OPT_SWEEP_KERNEL, OPT_FUSE_MERGE, OPT_DIV_CORE, OPT_XSOLVE, OPT_OVERLAP, OPT_KEEP_TEMP = 0, 1, 2, 3, 4, 5
 OPT_F64_PART = 6          # fp64 contexts: 1 opens the fp64 partition kernels to SWEEP_AUTO / SWEEP_PART (default 0: bit-exact kernels)
+OPT_ERR_ORDER = 7         # 1: EvalDivError sums its terms serially in cell order, as the CPU path (bit-equal reported error on the exact kernels)
 XSOLVE_AUTO, XSOLVE_PIPELINED, XSOLVE_REDUCED, XSOLVE_REDUCED_A2A = 0, 1, 2, 3
 
 # every symbol include/fs3d.h declares: name -> (restype, argtypes)
@@ -32,6 +33,11 @@ SYMBOLS = {
     "fs3d_set_params": (_i, [_vp, _d, _d, _d, _d]),
     "fs3d_set_option": (_i, [_vp, _i, _i]),
     "fs3d_upload_nodes": (_i, [_vp] + [_vp] * 7 + [C.POINTER(_i)]),
+    "fs3d_update_nodes": (_i, [_vp] + [_vp] * 7 + [C.POINTER(_i)]),
+    "fs3d_update_nodes_dev": (_i, [_vp] + [_vp] * 7 + [C.POINTER(_i)]),
+    "fs3d_clear_outer_cells": (_i, [_vp, _i, _d]),
+    "fs3d_geometry_info": (_i, [_vp, C.POINTER(C.c_longlong)]),
+    "fs3d_last_update_device_ms": (_i, [_vp, C.POINTER(C.c_float)]),
     "fs3d_init_layers_from_nodes": (_i, [_vp]),
     "fs3d_upload_layer": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
     "fs3d_download_layer": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
@@ -151,6 +157,55 @@ class Solver:
     def comm_init_local(self, group, rank):
         self._chk(self.lib.fs3d_comm_init_local(self.h, group.h, rank))
         self._group = group        # keep the group alive as long as the context
+
+    # -- moving geometry ------------------------------------------------------------
+    def update_nodes(self, nodes):
+        """AdiSolver3D::CreateSegments between time steps: the tables of a new geometry (same dims), rebuilt on the device.
+        Layers are kept.  After a refusal the context has no geometry until an update succeeds."""
+        assert tuple(nodes.shape) == tuple(self.gdims)
+        arrs = [np.ascontiguousarray(nodes.type, np.uint8), np.ascontiguousarray(nodes.bc_vel, np.uint8),
+                np.ascontiguousarray(nodes.bc_temp, np.uint8)] + [
+            np.ascontiguousarray(v, self.dtype) for v in (nodes.vx, nodes.vy, nodes.vz, nodes.T)]
+        nseg = (C.c_int * 3)()
+        self._chk(self.lib.fs3d_update_nodes(self.h, *[_p(a) for a in arrs], nseg))
+        self.num_segments = list(nseg)
+        return self.num_segments
+
+    def update_nodes_dev(self, type, bc_vel, bc_temp, vx, vy, vz, T):
+        """The same from arrays on the context's device: torch tensors (contiguous; uint8 x 3, the context's precision x 4)
+        or raw device pointers (int)."""
+        def ptr(a, want):
+            if isinstance(a, int):
+                return C.c_void_p(a)
+            if not a.is_cuda or not a.is_contiguous() or a.element_size() != want or a.numel() != int(np.prod(self.gdims)):
+                raise ValueError("update_nodes_dev: contiguous device tensors of the grid's size and the context's precision")
+            return C.c_void_p(a.data_ptr())
+        es = self.dtype.itemsize
+        ptrs = [ptr(a, 1) for a in (type, bc_vel, bc_temp)] + [ptr(a, es) for a in (vx, vy, vz, T)]
+        nseg = (C.c_int * 3)()
+        self._chk(self.lib.fs3d_update_nodes_dev(self.h, *ptrs, nseg))
+        self.num_segments = list(nseg)
+        return self.num_segments
+
+    def clear_outer_cells(self, layer, baseT):
+        """Solver3D::ClearOutterCells on one layer: U, V, W := 0 and T := baseT on the NODE_OUT cells."""
+        self._chk(self.lib.fs3d_clear_outer_cells(self.h, layer, float(baseT)))
+
+    def last_update_device_ms(self):
+        """Device time of the last update_nodes* call (measured while enable_timing is on, else 0)."""
+        ms = C.c_float(0)
+        self._chk(self.lib.fs3d_last_update_device_ms(self.h, C.byref(ms)))
+        return ms.value
+
+    GEOMETRY_INFO = ("segments_x", "segments_y", "segments_z", "bound_cells", "stale_in_cells", "dead_lines_x", "dead_lines_y",
+                     "dead_lines_z", "uniform_groups_x", "uniform_groups_y", "shared_columns_x", "shared_columns_y", "code_digest",
+                     "device_allocs_and_frees")
+
+    def geometry_info(self):
+        """fs3d_geometry_info as a dict (keys: Solver.GEOMETRY_INFO); measurement and test aid."""
+        info = (C.c_longlong * len(self.GEOMETRY_INFO))()
+        self._chk(self.lib.fs3d_geometry_info(self.h, info))
+        return dict(zip(self.GEOMETRY_INFO, list(info)))
 
     # -- reference-shaped interface -----------------------------------------------
     def UpdateBoundaries(self):

@@ -77,6 +77,23 @@ struct SweepParams {
 #define UCOL_PITCH 512                 // codes per shared column (the partition kernels take lines of <= 512 cells)
 #define FS3D_XREDUCE_MAX_RANKS 64      // k_xreduce (kernels_line.hip) holds the R x R slab system of a line in per-thread arrays of this size
 
+// moving geometry (kernels_geom.hip): what fs3d_update_nodes* keeps between calls, allocated by the first one
+struct fs3d_geom {
+    uint8_t *stage = nullptr;               // 3 x ncell: type, bc_vel, bc_temp of the host entry point
+    int *lst[3] = {};                       // per line of X / Y / Z: last index whose type is not NODE_IN (-1: none)
+    uint16_t *col[2] = {};                  // [o][group][UCOL_PITCH]: every group's candidate shared column (X, Y)
+    uint8_t *cflag[2] = {};                 // [o][group]: bit 0 uniform, bit 1 the pair is
+    unsigned long long *hash[2] = {};       // [o][group]: hash of the column, for the identity decision on the host
+    int *rep[2] = {};                       // [column id]: the group whose column it is
+    unsigned long long *cnt = nullptr;      // counter words of one update
+    void *host = nullptr;                   // pinned: counters, hashes, flags on their way to / from the host
+    // device time of one update (fs3d_last_update_device_ms): event pairs around every batch of launches between two synchronisations
+    hipEvent_t ev[16] = {};
+    int ev_n = 0;
+    bool ev_open = false;
+    float last_dev_ms = 0;
+};
+
 struct fs3d_ctx {
     int device = 0;
     fs3d_precision prec = FS3D_F32;
@@ -104,6 +121,13 @@ struct fs3d_ctx {
     int *bnd_idx = nullptr;
     void *bnd_val[4] = {};
     int n_bnd = 0;
+    int bnd_cap = 0;            // entries the list buffers hold (fs3d_update_nodes grows them, never shrinks)
+    long long ucol_cap[2] = {0, 0};   // columns ucol[d] holds when fs3d_update_nodes allocated it (0: the upload's exact-size table)
+    int n_ucol[2] = {0, 0};     // distinct shared columns
+    bool uploaded_once = false; // fs3d_upload_nodes has succeeded: the fixed-size tables exist
+    long long geom_allocs = 0;  // device allocations + frees made by fs3d_upload_nodes / fs3d_update_nodes* (fs3d_geometry_info)
+    int n_create_segments = 0;  // successful uploads + updates
+    fs3d_geom geom;
     int nseg[3] = {0, 0, 0};
     long long stale_in_cells = 0;  // NODE_IN cells on no segment of some direction (they merge stale `next` values): 0 for closed geometries
     // div error partials
@@ -119,6 +143,9 @@ struct fs3d_ctx {
     int opt_overlap = 1;                   // FS3D_OPT_OVERLAP
     int opt_keep_temp = 0;                 // FS3D_OPT_KEEP_TEMP
     int opt_f64_part = 0;                  // FS3D_OPT_F64_PART
+    int opt_err_order = 0;                 // FS3D_OPT_ERR_ORDER: 1 = EvalDivError sums its per-cell terms serially in cell order (host), as the CPU path
+    double *err_terms = nullptr;           // ... one term per cell (device, allocated on first use)
+    std::vector<double> err_terms_host;
     // options
     int opt_kernel = FS3D_SWEEP_AUTO;
     int ran_kernel[3] = {0, 0, 0};   // per direction: the kernel the last sweep really ran (fs3d_last_sweep_kernel)
@@ -157,6 +184,9 @@ struct fs3d_ctx {
     int xblocks = 4;               // line blocks of the cross-slab X sweep pipeline (env FS3D_XBLOCKS)
     std::string err;
 };
+
+// kernels_geom.hip
+void fs3d_geom_destroy(fs3d_ctx *c);
 
 // kernels_*.hip
 template <typename R> void launch_sweep_line(fs3d_ctx *c, int dir, const SweepParams<R> &p);

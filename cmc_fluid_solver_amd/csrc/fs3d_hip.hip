@@ -176,6 +176,28 @@ __global__ void __launch_bounds__(256) k_div_error(const uint16_t *__restrict__ 
     }
 }
 
+// FS3D_OPT_ERR_ORDER = 1: the same per-cell terms, one per cell (0 where the reference's loop adds nothing), for the host to sum
+// serially in cell order as TimeLayer3D::EvalDivError does.  Single context (no ghost planes).  Thread per cell, lanes along k.
+template <typename R>
+__global__ void __launch_bounds__(256) k_div_terms(const uint16_t *__restrict__ code, const R *__restrict__ U, const R *__restrict__ V,
+                                                    const R *__restrict__ W, int dimx, int dimy, int dimz, R dx, R dy, R dz,
+                                                    double *__restrict__ terms)
+{
+    const long long plane = (long long)dimy * dimz, n = plane * dimx;
+    for (long long l = (long long)blockIdx.x * 256 + threadIdx.x; l < n; l += (long long)gridDim.x * 256) {
+        const int i = (int)(l / plane), rem = (int)(l - (long long)i * plane), j = rem / dimz, k = rem - j * dimz;
+        double t = 0.0;
+        if (i >= 1 && i < dimx - 1 && j >= 1 && j < dimy - 1 && k >= 1 && k < dimz - 1 && ((code[l] >> CODE_TYPE_SHIFT) & 3) == FS3D_NODE_IN) {
+            const long long a = l, b = l - dimz, cc = l - dimz - 1, d = l - 1;           // (j,k), (j-1,k), (j-1,k-1), (j,k-1); "- plane" = i-1
+            const double ex = (double)((U[a] + U[b] + U[cc] + U[d] - U[a - plane] - U[b - plane] - U[cc - plane] - U[d - plane]) * dz * dy) / 4.0;
+            const double ey = (double)((V[a] + V[a - plane] + V[d - plane] + V[d] - V[b] - V[b - plane] - V[cc - plane] - V[cc]) * dx * dz) / 4.0;
+            const double ez = (double)((W[a] + W[b] + W[b - plane] + W[a - plane] - W[d] - W[cc] - W[cc - plane] - W[d - plane]) * dx * dy) / 4.0;
+            t = fabs(ex + ey + ez);
+        }
+        terms[l] = t;
+    }
+}
+
 __global__ void __launch_bounds__(256) k_div_final(const double *partial, int nblocks, double *out)
 {
     __shared__ double se[256], sc[256];
@@ -335,6 +357,8 @@ extern "C" void fs3d_destroy(fs3d_ctx *c)
     if (c->xif_all) hipFree(c->xif_all);
     for (int v = 0; v < 4; v++) if (c->bnd_val[v]) hipFree(c->bnd_val[v]);
     if (c->bnd_idx) hipFree(c->bnd_idx);
+    fs3d_geom_destroy(c);
+    if (c->err_terms) hipFree(c->err_terms);
     if (c->red_buf) hipFree(c->red_buf);
     if (c->stamps) hipFree(c->stamps);
     if (c->red_host) hipHostFree(c->red_host);
@@ -366,6 +390,7 @@ extern "C" fs3d_status fs3d_set_option(fs3d_ctx *c, int option, int value)
     case FS3D_OPT_OVERLAP: c->opt_overlap = value ? 1 : 0; return FS3D_OK;
     case FS3D_OPT_KEEP_TEMP: c->opt_keep_temp = value ? 1 : 0; return FS3D_OK;
     case FS3D_OPT_F64_PART: c->opt_f64_part = value ? 1 : 0; return FS3D_OK;
+    case FS3D_OPT_ERR_ORDER: c->opt_err_order = value ? 1 : 0; return FS3D_OK;
     case FS3D_OPT_XSOLVE:
         if (value < 0 || value > 3) return fail(c, FS3D_ERR_INVALID, "bad cross-slab X solve id");
         c->opt_xsolve = value; return FS3D_OK;
@@ -401,7 +426,7 @@ extern "C" fs3d_status fs3d_profiler_events(fs3d_ctx *c, const char *names[FS3D_
     for (int k = 0; k < 8; k++) { if (names) names[k] = k_event_names[k]; if (ms) ms[k] = c->t_ms[k]; if (n) n[k] = c->t_n[k]; }
     if (names) names[8] = k_event_names[8];
     if (ms) ms[8] = (float)c->t_create_segments_ms;
-    if (n) n[8] = c->have_nodes ? 1 : 0;
+    if (n) n[8] = c->n_create_segments;
     return FS3D_OK;
 }
 
@@ -518,14 +543,15 @@ static fs3d_status upload_nodes_impl(fs3d_ctx *c, const uint8_t *type, const uin
                 const bool live = ((code[(size_t)l] >> (4 * d)) & 3) != ROW_SKIP || ((code[(size_t)l] >> CODE_TYPE_SHIFT) & 3) == FS3D_NODE_IN;
                 if (live) dead[(size_t)(d == 0 ? (long long)j * dz + k : (d == 1 ? (long long)i * dz + k : (long long)i * dy + j))] = 0;
             }
-            if (c->dead[d]) { hipFree(c->dead[d]); c->dead[d] = nullptr; }
-            HIPCHK(c, hipMalloc((void **)&c->dead[d], (size_t)nl[d]));
+            if (c->dead[d]) { hipFree(c->dead[d]); c->dead[d] = nullptr; c->geom_allocs++; }
+            HIPCHK(c, hipMalloc((void **)&c->dead[d], (size_t)nl[d])); c->geom_allocs++;
             HIPCHK(c, hipMemcpy(c->dead[d], dead.data(), (size_t)nl[d], hipMemcpyHostToDevice));
             if (d < 2) {
                 // shared code columns (X: o = j, line cells along i; Y: o = i, cells along j; lanes k in groups of 32): a group is
                 // uniform when all its live lines carry the same (row code of this direction, node type) on every cell
-                if (c->ucol[d]) { hipFree(c->ucol[d]); c->ucol[d] = nullptr; }
-                if (c->uflag[d]) { hipFree(c->uflag[d]); c->uflag[d] = nullptr; }
+                if (c->ucol[d]) { hipFree(c->ucol[d]); c->ucol[d] = nullptr; c->geom_allocs++; }
+                c->ucol_cap[d] = 0; c->n_ucol[d] = 0;
+                if (c->uflag[d]) { hipFree(c->uflag[d]); c->uflag[d] = nullptr; c->geom_allocs++; }
                 const int n_o = d == 0 ? dy : nx, n = d == 0 ? nx : dy, ng = (dz + 31) / 32;
                 if (n <= UCOL_PITCH) {
                     const uint16_t keep = (uint16_t)((0xF << (4 * d)) | (3 << CODE_TYPE_SHIFT));
@@ -572,10 +598,11 @@ static fs3d_status upload_nodes_impl(fs3d_ctx *c, const uint8_t *type, const uin
                         if (it == ids.end()) { it = ids.emplace(key, (unsigned)(uniq.size() / UCOL_PITCH)).first; uniq.insert(uniq.end(), cc, cc + UCOL_PITCH); }
                         fl[q] = (unsigned)flag[q] | (it->second << 2);
                     }
+                    c->n_ucol[d] = (int)ids.size();
                     if (uniq.empty()) uniq.resize(UCOL_PITCH, 0);
-                    HIPCHK(c, hipMalloc((void **)&c->ucol[d], uniq.size() * sizeof(uint16_t)));
+                    HIPCHK(c, hipMalloc((void **)&c->ucol[d], uniq.size() * sizeof(uint16_t))); c->geom_allocs++;
                     HIPCHK(c, hipMemcpy(c->ucol[d], uniq.data(), uniq.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-                    HIPCHK(c, hipMalloc((void **)&c->uflag[d], fl.size() * sizeof(unsigned)));
+                    HIPCHK(c, hipMalloc((void **)&c->uflag[d], fl.size() * sizeof(unsigned))); c->geom_allocs++;
                     HIPCHK(c, hipMemcpy(c->uflag[d], fl.data(), fl.size() * sizeof(unsigned), hipMemcpyHostToDevice));
                 }
             }
@@ -583,19 +610,19 @@ static fs3d_status upload_nodes_impl(fs3d_ctx *c, const uint8_t *type, const uin
     }
     for (int v = 0; v < 4; v++)
         HIPCHK(c, hipMemcpy((R *)c->node + (size_t)v * c->nstride, nv[v].data(), (size_t)c->ncell * sizeof(R), hipMemcpyHostToDevice));
-    if (c->bnd_idx) { hipFree(c->bnd_idx); c->bnd_idx = nullptr; }
-    for (int v = 0; v < 4; v++) if (c->bnd_val[v]) { hipFree(c->bnd_val[v]); c->bnd_val[v] = nullptr; }
-    c->n_bnd = (int)bidx.size();
+    if (c->bnd_idx) { hipFree(c->bnd_idx); c->bnd_idx = nullptr; c->geom_allocs++; }
+    for (int v = 0; v < 4; v++) if (c->bnd_val[v]) { hipFree(c->bnd_val[v]); c->bnd_val[v] = nullptr; c->geom_allocs++; }
+    c->n_bnd = (int)bidx.size(); c->bnd_cap = c->n_bnd;
     if (c->n_bnd) {
-        HIPCHK(c, hipMalloc((void **)&c->bnd_idx, sizeof(int) * bidx.size()));
+        HIPCHK(c, hipMalloc((void **)&c->bnd_idx, sizeof(int) * bidx.size())); c->geom_allocs++;
         HIPCHK(c, hipMemcpy(c->bnd_idx, bidx.data(), sizeof(int) * bidx.size(), hipMemcpyHostToDevice));
         for (int v = 0; v < 4; v++) {
-            HIPCHK(c, hipMalloc(&c->bnd_val[v], sizeof(R) * bidx.size()));
+            HIPCHK(c, hipMalloc(&c->bnd_val[v], sizeof(R) * bidx.size())); c->geom_allocs++;
             HIPCHK(c, hipMemcpy(c->bnd_val[v], bval[v].data(), sizeof(R) * bidx.size(), hipMemcpyHostToDevice));
         }
     }
     for (int d = 0; d < 3; d++) { c->nseg[d] = (int)nseg[d]; if (n_seg_out) n_seg_out[d] = (int)nseg[d]; }
-    c->have_nodes = true;
+    c->have_nodes = true; c->uploaded_once = true; c->n_create_segments++;
     return FS3D_OK;
 }
 
@@ -608,7 +635,7 @@ extern "C" fs3d_status fs3d_upload_nodes(fs3d_ctx *c, const uint8_t *type, const
     const fs3d_status st = c->prec == FS3D_F32
         ? upload_nodes_impl<float>(c, type, bc_vel, bc_temp, (const float *)vx, (const float *)vy, (const float *)vz, (const float *)T, n_seg_out)
         : upload_nodes_impl<double>(c, type, bc_vel, bc_temp, (const double *)vx, (const double *)vy, (const double *)vz, (const double *)T, n_seg_out);
-    c->t_create_segments_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    c->t_create_segments_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return st;
 }
 
@@ -1049,12 +1076,22 @@ static fs3d_status div_error_enqueue(fs3d_ctx *c, int layer)
     const int b = c->slot[layer];
     // the last slab skips its final plane (TimeLayer3D.h:606); inner slabs need the i-1 ghost (halo exchanged by caller)
     const int i_end = (c->x_offset + c->dimx == c->dimx_global) ? c->dimx - 1 : c->dimx;
+    if (c->opt_err_order) {
+        if (c->dimx != c->dimx_global || c->comm || c->local || c->nranks > 1)
+            return fail(c, FS3D_ERR_UNSUPPORTED, "FS3D_OPT_ERR_ORDER = 1 (the CPU path's summation order) is implemented for a single context only");
+        if (!c->err_terms) HIPCHK(c, hipMalloc((void **)&c->err_terms, (size_t)c->ncell * sizeof(double)));
+    }
     rec_begin(c, 5);
     hipLaunchKernelGGL((k_div_error<R>), dim3(c->red_blocks), dim3(256), 0, c->stream, c->code,
                        (const R *)fld<R>(c, b, 0), (const R *)fld<R>(c, b, 1), (const R *)fld<R>(c, b, 2),
                        c->dimx, c->dimy, c->dimz, i_end, c->x_offset == 0 ? 1 : 0, (R)c->gdx, (R)c->gdy, (R)c->gdz, c->red_buf + 2,
                        (c->dimy + DIVE_JS - 1) / DIVE_JS);
     hipLaunchKernelGGL(k_div_final, dim3(1), dim3(256), 0, c->stream, c->red_buf + 2, c->red_blocks, c->red_buf);
+    if (c->opt_err_order) {
+        hipLaunchKernelGGL((k_div_terms<R>), dim3(grid_for(c->ncell, 256)), dim3(256), 0, c->stream, c->code,
+                           (const R *)fld<R>(c, b, 0), (const R *)fld<R>(c, b, 1), (const R *)fld<R>(c, b, 2),
+                           c->dimx, c->dimy, c->dimz, (R)c->gdx, (R)c->gdy, (R)c->gdz, c->err_terms);
+    }
     rec_end(c);
     HIPCHK(c, hipGetLastError());
     return FS3D_OK;
@@ -1065,6 +1102,15 @@ static fs3d_status div_error_finish(fs3d_ctx *c, double *err, long long *count)
     fs3d_status st = fs3d_comm_allreduce_sum2(c, c->red_buf);   // no-op for a single rank
     if (st) return st;
     HIPCHK(c, hipMemcpyAsync(c->red_host, c->red_buf, 2 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (c->opt_err_order) {
+        // TimeLayer3D.h:604-628: err += fabs(...) cell after cell; adding the 0.0 of a cell the loop skips changes nothing
+        c->err_terms_host.resize((size_t)c->ncell);
+        HIPCHK(c, hipMemcpyAsync(c->err_terms_host.data(), c->err_terms, (size_t)c->ncell * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        double sum = 0.0;
+        for (double t : c->err_terms_host) sum += t;
+        c->red_host[0] = sum;
+    }
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (count) *count = (long long)c->red_host[1];
     if (err) *err = c->red_host[0] / c->red_host[1];   // err / count (0/0 = NaN as in the reference)

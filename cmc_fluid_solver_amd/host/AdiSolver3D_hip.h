@@ -89,6 +89,21 @@ public:
     static void DestroyLocalGroup(void *g) { fs3d_local_group_destroy(g); }
     void JoinLocalGroup(void *group, int rank) { chk(fs3d_comm_init_local(ctx_, group, rank)); }
 
+    // AdiSolver3D::CreateSegments again, for a grid whose walls have moved (same dims; single GPU): the device tables are rebuilt
+    // by kernels, the layers are kept
+    void UpdateGrid(const Grid3D<FTYPE> &grid)
+    {
+        grid_ = &grid;
+        chk(fs3d_update_nodes(ctx_, grid.type.data(), grid.bc_vel.data(), grid.bc_temp.data(), grid.vx.data(), grid.vy.data(),
+                              grid.vz.data(), grid.T.data(), numSegs));
+    }
+    // Solver3D::ClearOutterCells (Solver3D.cpp:41-44), on `next` as there and on `cur`: a cell that turns NODE_IN with the next
+    // geometry starts from (0, 0, 0, baseT) in both
+    void ClearOutterCells()
+    {
+        chk(fs3d_clear_outer_cells(ctx_, FS3D_LAYER_NEXT, grid_->baseT));
+        chk(fs3d_clear_outer_cells(ctx_, FS3D_LAYER_CUR, grid_->baseT));
+    }
     void UpdateBoundaries() { chk(fs3d_update_boundaries(ctx_)); }                        // AdiSolver3D.cpp:286-304
     // AdiSolver3D::TimeStep (AdiSolver3D.cpp:306-391); throws where the reference throws
     void TimeStep(FTYPE dt, int num_global, int num_local, bool computeError)

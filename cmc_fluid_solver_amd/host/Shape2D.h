@@ -221,20 +221,20 @@ public:
     float Temp(int x, int y) const { return T[id(x, y)]; }
 };
 
-// Grid3D(dx,dy,dz,depth,depth_var,baseT) + LoadFromFile + Prepare2D(0) (Grid3D.cpp:488-513, 608-668)
+// Grid3D::Prepare2D(time) after grid2D->Prepare(time) (Grid3D.cpp:608-668): the extrusion of the 2D grid as it stands into the
+// 3D node array.  g keeps its dims (set by LoadShape2D); every node is rewritten, so a grid can be extruded again after
+// g2.Prepare(t) without reading the file or resizing.
 template <typename FTYPE>
-void LoadShape2D(Grid3D<FTYPE> &g, Grid2D &g2, const std::string &path, double dx, double dy, double dz, double depth, double depth_var, double baseT, bool align)
+void ExtrudeShape2D(Grid3D<FTYPE> &g, const Grid2D &g2, double dz, double depth, double depth_var, double baseT)
 {
-    g2.Load(path, dx, dy, baseT, align);
-    const int dimx = g2.dimx, dimy = g2.dimy;
-    if (!(dz > 0) || !(depth >= 0) || depth / dz > 65536.0) throw std::runtime_error("Shape2D: depth / grid_dz gives more than 65536 cells");
+    const int dimx = g.dimx, dimy = g.dimy, dimz = g.dimz;
+    if (dimx != g2.dimx || dimy != g2.dimy) throw std::runtime_error("Shape2D: the 3D grid does not have the 2D grid's dims");
     const int active_dimz = (int)std::ceil(depth / dz) + 1;                 // Grid3D.cpp:503-505
-    const int dimz = align ? AlignBy32(active_dimz) : active_dimz;
-    if ((double)dimx * dimy * dimz >= 2147483648.0) throw std::runtime_error("Shape2D: grid of more than 2^31 cells");
-    g.Resize(dimx, dimy, dimz);
-    g.dx = dx; g.dy = dy; g.dz = dz; g.baseT = baseT;
     // memset(nodes, 0): type NODE_IN, bc NOSLIP, v = 0, T = 0   (Grid3D.cpp:612)
     std::fill(g.type.begin(), g.type.end(), (uint8_t)NODE_IN);
+    std::fill(g.bc_vel.begin(), g.bc_vel.end(), (uint8_t)BC_NOSLIP); std::fill(g.bc_temp.begin(), g.bc_temp.end(), (uint8_t)BC_NOSLIP);
+    std::fill(g.vx.begin(), g.vx.end(), (FTYPE)0); std::fill(g.vy.begin(), g.vy.end(), (FTYPE)0);
+    std::fill(g.vz.begin(), g.vz.end(), (FTYPE)0); std::fill(g.T.begin(), g.T.end(), (FTYPE)0);
     const int height = std::max(active_dimz - 2 - 2, 0);
     for (int i = 0; i < dimx; i++)
         for (int j = 0; j < dimy; j++) {
@@ -259,6 +259,21 @@ void LoadShape2D(Grid3D<FTYPE> &g, Grid2D &g2, const std::string &path, double d
                 }
             }
         }
+}
+
+// Grid3D(dx,dy,dz,depth,depth_var,baseT) + LoadFromFile + Prepare2D(0) (Grid3D.cpp:488-513, 608-668)
+template <typename FTYPE>
+void LoadShape2D(Grid3D<FTYPE> &g, Grid2D &g2, const std::string &path, double dx, double dy, double dz, double depth, double depth_var, double baseT, bool align)
+{
+    g2.Load(path, dx, dy, baseT, align);
+    const int dimx = g2.dimx, dimy = g2.dimy;
+    if (!(dz > 0) || !(depth >= 0) || depth / dz > 65536.0) throw std::runtime_error("Shape2D: depth / grid_dz gives more than 65536 cells");
+    const int active_dimz = (int)std::ceil(depth / dz) + 1;                 // Grid3D.cpp:503-505
+    const int dimz = align ? AlignBy32(active_dimz) : active_dimz;
+    if ((double)dimx * dimy * dimz >= 2147483648.0) throw std::runtime_error("Shape2D: grid of more than 2^31 cells");
+    g.Resize(dimx, dimy, dimz);
+    g.dx = dx; g.dy = dy; g.dz = dz; g.baseT = baseT;
+    ExtrudeShape2D(g, g2, dz, depth, depth_var, baseT);
 }
 
 }  // namespace fs3d

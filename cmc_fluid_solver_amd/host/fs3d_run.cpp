@@ -1,5 +1,5 @@
 // Command-line driver: the reference's FluidSolver3D main (FluidSolver3D/FluidSolver3D.cpp:60-330) on top of
-// libfs3d_hip.so.   fs3d_run <input data> <output prefix> <config> [align] [GPU [n]] [double] [--steps N] [--same-device] [--grid-only FILE]
+// libfs3d_hip.so.   fs3d_run <input data> <output prefix> <config> [align] [GPU [n]] [double] [moving] [--steps N] [--same-device] [--grid-only FILE [--grid-time T]]
 //   * reads the config (host/Config.h) and a Shape2D, Shape3D or SeaNetCDF geometry (host/Shape2D.h, Shape3D.h, SeaNetCDF.h), prints the grid summary lines
 //     the reference prints ("Grid = X x Y x Z", "NODE_IN points = ..."),
 //   * runs the same loop: dt = cycle length / (frames * time_steps), UpdateBoundaries + TimeStep per step with the
@@ -7,9 +7,13 @@
 //   * writes <output prefix>_res.nc through host/NetCDF3.h every out_time_steps steps (GetLayer).
 // `transpose`, `decompose`, `blocking n` of the reference are accepted and ignored (backend tuning switches); `CSV`
 // switches the closing timing table to the reference's comma-separated form.
+// `moving` (single GPU, in_fmt Shape2D): the walls follow the frames of the input -- per step grid2D->Prepare(t), the extrusion,
+//   CreateSegments on the device (UpdateGrid), UpdateBoundaries, TimeStep, the output, ClearOutterCells: the loop of the reference's
+//   2D driver (FluidSolver2D.cpp:130-133) with the 3D classes' mechanism (AdiSolver3D.cpp:382-385, Solver3D.cpp:41-44).
 // There is no CPU backend here: without a GPU the run stops with the library's error.
 // --grid-only FILE: build the grid, dump it (dims, type, bc_vel, bc_temp, vx, vy, vz, T as raw arrays) and exit
 //   without touching the GPU -- used by the CPU tests to compare the C++ loader with its Python twin.
+//   --grid-time T: the grid the moving loop uses at time T (load, Prepare(T), extrude again) instead of the one of time 0.
 #include <algorithm>
 #include <chrono>
 #include <condition_variable>
@@ -46,8 +50,11 @@ static int run_slabs(const fs3d::Grid3D<FTYPE> &grid, const RunGeom &geo, const 
 
 template <typename FTYPE>
 static int run(const std::string &data, const std::string &prefix, const fs3d::Config &cfg, bool align, int device, long max_steps, const std::string &grid_only, bool csv,
-               int nslabs, bool same_device, bool grid_images)
+               int nslabs, bool same_device, bool grid_images, bool moving, double grid_time)
 {
+    if (moving && cfg.in_fmt != "Shape2D") throw std::runtime_error("moving: only in_fmt Shape2D inputs move (this one is " + cfg.in_fmt + ")");
+    if (moving && nslabs > 1) throw std::runtime_error("moving: single GPU only (moving geometry on x-slabs is not implemented)");
+    if (grid_time >= 0 && cfg.in_fmt != "Shape2D") throw std::runtime_error("--grid-time: only in_fmt Shape2D inputs move");
     using namespace fs3d;
     Grid3D<FTYPE> grid;
     Grid2D g2;
@@ -78,6 +85,7 @@ static int run(const std::string &data, const std::string &prefix, const fs3d::C
                 inside * grid.dx * grid.dy * grid.dz);                                          // :170
     if (grid_images) OutputGridImages(grid, prefix + "_grid_3d");                             // FluidSolver3D.cpp:152-153 (there: always)
     if (!grid_only.empty()) {
+        if (grid_time >= 0) { g2.Prepare(grid_time); ExtrudeShape2D(grid, g2, cfg.dz, cfg.depth, cfg.depth_var, cfg.baseT); }
         FILE *f = std::fopen(grid_only.c_str(), "wb");
         if (!f) throw std::runtime_error("cannot create " + grid_only);
         const int hdr[4] = {grid.dimx, grid.dimy, grid.dimz, (int)sizeof(FTYPE)};
@@ -119,6 +127,11 @@ static int run(const std::string &data, const std::string &prefix, const fs3d::C
     for (int i = 0; t < finaltime && (max_steps < 0 || steps < max_steps); t += dt, i++, steps++) {
         const int currentframe = geo.GetFrame(t);                                                        // :229-236
         if (currentframe != lastframe) { lastframe = currentframe; i = 0; }
+        if (moving) {                                                                                    // grid->Prepare(t), :237
+            g2.Prepare(t);
+            ExtrudeShape2D(grid, g2, cfg.dz, cfg.depth, cfg.depth_var, cfg.baseT);
+            solver.UpdateGrid(grid);
+        }
         solver.UpdateBoundaries();                                                                       // :244
         solver.TimeStep((FTYPE)dt, cfg.num_global, cfg.num_local, (i % 10 == 0) || (t + dt >= finaltime)); // :245
         std::printf("\rerr = %.8f,", solver.diffError);                                                  // AdiSolver3D.cpp:376
@@ -134,6 +147,7 @@ static int run(const std::string &data, const std::string &prefix, const fs3d::C
             solver.GetLayer(resVel.data(), resT.data(), cfg.outdimx, cfg.outdimy, cfg.outdimz);
             nc.AppendLayer(resVel.data(), resT.data());
         }
+        if (moving) solver.ClearOutterCells();                                                           // AdiSolver3D.cpp:382-385
     }
     const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     // the reference's Profiler table (Common/Profiler.h:90-131: sorted by total time, events that never ran are absent; event
@@ -269,7 +283,7 @@ static int run_slabs(const fs3d::Grid3D<FTYPE> &grid, const RunGeom &geo, const 
 int main(int argc, char **argv)
 {
     if (argc < 4) {
-        std::printf("Usage: %s <input data> <output prefix> <config file> [align] [GPU [n]] [double] [--steps N] [--grid-only FILE] [--grid-images]\n", argv[0]);
+        std::printf("Usage: %s <input data> <output prefix> <config file> [align] [GPU [n]] [double] [--steps N] [moving] [--grid-only FILE [--grid-time T]] [--grid-images]\n", argv[0]);
         return 0;
     }
     try {
@@ -279,7 +293,8 @@ int main(int argc, char **argv)
         if (cfg.in_fmt != "Shape2D" && cfg.in_fmt != "Shape3D" && cfg.in_fmt != "SeaNetCDF") throw std::runtime_error("in_fmt " + cfg.in_fmt + ": unknown input format");
         if (cfg.in_fmt != "Shape2D" && !(cfg.frame_time > 0)) throw std::runtime_error("must specify frame time!");   // the cycle length of a Shape3D run (Grid3D.cpp:303-309)
         if (cfg.solver != "ADI") throw std::runtime_error("solver " + cfg.solver + " is not implemented (the reference implements ADI only)");
-        bool align = false, dbl = false, csv = false, same_device = false, grid_images = false;
+        bool align = false, dbl = false, csv = false, same_device = false, grid_images = false, moving = false;
+        double grid_time = -1;
         int nslabs = 1;
         int device = 0;
         long max_steps = -1;
@@ -293,13 +308,15 @@ int main(int argc, char **argv)
             else if (s == "--device" && a + 1 < argc) device = std::atoi(argv[++a]);
             else if (s == "--steps" && a + 1 < argc) max_steps = std::atol(argv[++a]);
             else if (s == "--grid-only" && a + 1 < argc) grid_only = argv[++a];
+            else if (s == "--grid-time" && a + 1 < argc) grid_time = std::atof(argv[++a]);
+            else if (s == "moving") moving = true;
             else if (s == "blocking") { if (a + 1 < argc) a++; }
             else if (s == "CSV") csv = true;
             else if (s == "--grid-images") grid_images = true;       // <prefix>_grid_3d/<k>.bmp: the node types, one image per z-slice
             // transpose, decompose: accepted, no effect
         }
-        return dbl ? run<double>(argv[1], argv[2], cfg, align, device, max_steps, grid_only, csv, nslabs, same_device, grid_images)
-                   : run<float>(argv[1], argv[2], cfg, align, device, max_steps, grid_only, csv, nslabs, same_device, grid_images);
+        return dbl ? run<double>(argv[1], argv[2], cfg, align, device, max_steps, grid_only, csv, nslabs, same_device, grid_images, moving, grid_time)
+                   : run<float>(argv[1], argv[2], cfg, align, device, max_steps, grid_only, csv, nslabs, same_device, grid_images, moving, grid_time);
     } catch (std::exception &e) {
         std::fprintf(stderr, "\n\nCaught exception:\n%s\n\nTerminating...\n", e.what());     // FluidSolver3D.cpp:313-318
         return -1;

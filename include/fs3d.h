@@ -78,7 +78,7 @@ enum {
                                  reference's private `temp` member holds it after TimeStep (the parity tests that download it) */
     FS3D_OPT_DIV_CORE = 2,    /* 1 (default): fp32 pipe kernel divides with the scaling-free core of the IEEE expansion and
                                  falls back to the full division where an operand needs scaling (same results); 0: always full */
-    FS3D_OPT_F64_PART = 6     /* fp64 contexts only (accepted and without effect in fp32).  0 (default): fp64 runs the bit-exact kernels,
+    FS3D_OPT_F64_PART = 6,    /* fp64 contexts only (accepted and without effect in fp32).  0 (default): fp64 runs the bit-exact kernels,
                                  FS3D_SWEEP_PART fails with FS3D_ERR_UNSUPPORTED.  1: the fp64 partition kernels are open -- FS3D_SWEEP_AUTO
                                  runs them in every direction where they apply and falls back to the bit-exact kernels direction by
                                  direction where they do not; FS3D_SWEEP_PART runs them or fails, never falls back.  They apply to
@@ -87,6 +87,13 @@ enum {
                                  No effect on slab contexts (a multi-GPU group, or a context with a neighbouring slab's ghost planes):
                                  fp64 slabs keep the bit-exact Y / Z kernels and their cross-slab X solve.
                                  Environment FS3D_DEFAULT_F64_PART=1 sets the initial value for new contexts */
+    FS3D_OPT_ERR_ORDER = 7    /* summation order of EvalDivError (fs3d_eval_div_error, fs3d_time_step with compute_error).  0 (default): the
+                                 per-cell terms are summed in parallel (per workgroup, then over the workgroups; deterministic, equal to the
+                                 CPU path to ~1e-12 relative).  1: they are summed one after the other in cell order, as the loop of
+                                 TimeLayer3D::EvalDivError (TimeLayer3D.h:604-628) does -- on the bit-exact kernels the reported error then
+                                 equals the CPU path's bit for bit, as the fields do.  Costs 8 bytes per cell of device memory, a copy of
+                                 them to the host and a serial pass per evaluation; single context only (an x-slab: FS3D_ERR_UNSUPPORTED
+                                 from the evaluation) */
 };
 
 /* ---- lifetime ---------------------------------------------------------------
@@ -124,6 +131,48 @@ fs3d_status fs3d_set_option(fs3d_ctx *ctx, int option, int value);
 fs3d_status fs3d_upload_nodes(fs3d_ctx *ctx, const uint8_t *type, const uint8_t *bc_vel,
                               const uint8_t *bc_temp, const void *vx, const void *vy,
                               const void *vz, const void *T, int n_seg_out[3]);
+
+/* ---- moving geometry ----------------------------------------------------------
+ * AdiSolver3D::CreateSegments called again between time steps, after Grid3D::Prepare(t) has moved the walls (the reference's
+ * 2D driver runs this loop, FluidSolver2D.cpp:130-133; the 3D classes carry it, AdiSolver3D.cpp:382-385).  Arguments and
+ * meaning as fs3d_upload_nodes (global grid, SoA Node array, Grid3D::GenerateListSegments semantics), but every table the
+ * sweeps read -- cell codes, dead-line bytes, shared code columns and their flags, node values, the BOUND / VALVE list, the
+ * segment counts -- is rebuilt by kernels on the context's stream, and ends equal to what fs3d_upload_nodes would have built.
+ * fs3d_update_nodes takes host arrays (seven copies into buffers the context keeps, then the device path),
+ * fs3d_update_nodes_dev takes device arrays (same device as the context; read on the context's stream).
+ *  - layers, options, params and timing are not touched.
+ *  - only after a successful fs3d_upload_nodes (else FS3D_ERR_INVALID): the first geometry comes through the static path.
+ *  - after the first call nothing is allocated or freed in steady state; the BOUND / VALVE list grows when a geometry
+ *    exceeds its capacity and never shrinks.  Counts and flags (tens of bytes, and a few KB of column hashes) are read back.
+ *  - one context = the whole grid: an x-slab (dimx != dimx_global, or a member of a group) gets FS3D_ERR_UNSUPPORTED.
+ *  - a geometry that fs3d_upload_nodes refuses is refused with the same status.  The tables are rebuilt IN PLACE: after a
+ *    refusal, or any failure half way, the context has NO geometry -- every call that needs nodes returns FS3D_ERR_INVALID
+ *    ("upload nodes first") until an fs3d_upload_nodes or fs3d_update_nodes* succeeds.
+ *  - host time of the call is added to the CreateSegments profiler event; its count is the number of uploads + updates. */
+fs3d_status fs3d_update_nodes(fs3d_ctx *ctx, const uint8_t *type, const uint8_t *bc_vel,
+                              const uint8_t *bc_temp, const void *vx, const void *vy,
+                              const void *vz, const void *T, int n_seg_out[3]);
+fs3d_status fs3d_update_nodes_dev(fs3d_ctx *ctx, const uint8_t *type, const uint8_t *bc_vel,
+                                  const uint8_t *bc_temp, const void *vx, const void *vy,
+                                  const void *vz, const void *T, int n_seg_out[3]);
+/* Solver3D::ClearOutterCells (Solver3D.cpp:41-44) = TimeLayer3D::Clear(grid, NODE_OUT, 0, 0, 0, (FTYPE)baseT) on one layer:
+ * U, V, W := 0 and T := baseT on the NODE_OUT cells of the current geometry, every other cell untouched.  Needed once cells
+ * change type: fs3d_get_layer stamps 99999 into the NODE_OUT cells of `next`, and a cell that becomes NODE_IN starts from
+ * what its layer holds. */
+fs3d_status fs3d_clear_outer_cells(fs3d_ctx *ctx, int layer, double baseT);
+/* Summary of the geometry tables, the same after an upload and after an update of the same geometry.  info[0..2] segment
+ * counts X, Y, Z; [3] BOUND / VALVE cells; [4] NODE_IN cells on no segment of some direction; [5..7] dead lines X, Y, Z;
+ * [8..9] shared-column groups flagged uniform in X, Y; [10..11] distinct shared columns in X, Y; [12] an order-independent
+ * 64-bit digest of the cell-code table (sum over cells of a mix of cell index and code), computed on the device from the
+ * table the sweeps read; [13] the number of device allocations and frees fs3d_upload_nodes / fs3d_update_nodes* have made
+ * since the context was created (the one entry that describes the path taken, not the tables).
+ * Measurement and test aid; no reference counterpart. */
+/* Device time of the last fs3d_update_nodes* call: its kernels and copies on the context's stream, summed over HIP event pairs
+ * around every batch of launches (the host's decisions between the batches are not in it).  Measured while fs3d_enable_timing is
+ * on, else 0.  Measurement aid (tools/geometry_update_cost.py). */
+fs3d_status fs3d_last_update_device_ms(fs3d_ctx *ctx, float *ms_out);
+#define FS3D_N_GEOM_INFO 14
+fs3d_status fs3d_geometry_info(fs3d_ctx *ctx, long long info[FS3D_N_GEOM_INFO]);
 
 /* ---- layers -----------------------------------------------------------------
  * TimeLayer3D(backend, grid) constructor: cur <- every node's v and T
@@ -217,7 +266,7 @@ fs3d_status fs3d_comm_selftest(fs3d_ctx *ctx, size_t elems);
 fs3d_status fs3d_last_step_timing(fs3d_ctx *ctx, float ms[4], int n[4]);
 /* The same device times under the event names of the reference's Profiler (Common/Profiler.h:44-134; StartEvent/StopEvent
  * sites AdiSolver3D.cpp:297-367, 555-680): SolveSegments_Z/_Y/_X, CopyLayer, MergeLayer (zero launches while the merge is fused
- * into the sweeps), EvalDivError, UpdateBoundaries, syncHalos, CreateSegments (host time of fs3d_upload_nodes).  names[] receives
+ * into the sweeps), EvalDivError, UpdateBoundaries, syncHalos, CreateSegments (host time of fs3d_upload_nodes and fs3d_update_nodes*, one launch per call that succeeded).  names[] receives
  * static strings.  The driver prints them as the reference's PrintTimings table. */
 #define FS3D_N_EVENTS 9
 fs3d_status fs3d_profiler_events(fs3d_ctx *ctx, const char *names[FS3D_N_EVENTS], float ms[FS3D_N_EVENTS], int n[FS3D_N_EVENTS]);
