@@ -35,6 +35,9 @@ SYMBOLS = {
     "fs3d_upload_nodes": (_i, [_vp] + [_vp] * 7 + [C.POINTER(_i)]),
     "fs3d_update_nodes": (_i, [_vp] + [_vp] * 7 + [C.POINTER(_i)]),
     "fs3d_update_nodes_dev": (_i, [_vp] + [_vp] * 7 + [C.POINTER(_i)]),
+    "fs3d_extrude_shape2d_dev": (_i, [_vp] + [_vp] * 4 + [_d] * 4 + [_vp] * 7),
+    "fs3d_update_nodes_shape2d": (_i, [_vp] + [_vp] * 4 + [_d] * 4 + [C.POINTER(_i)]),
+    "fs3d_shape2d_bottom": (_i, [_i, _i, _d, _d, _d, C.POINTER(_i)]),
     "fs3d_clear_outer_cells": (_i, [_vp, _i, _d]),
     "fs3d_geometry_info": (_i, [_vp, C.POINTER(C.c_longlong)]),
     "fs3d_last_update_device_ms": (_i, [_vp, C.POINTER(C.c_float)]),
@@ -184,6 +187,37 @@ class Solver:
         ptrs = [ptr(a, 1) for a in (type, bc_vel, bc_temp)] + [ptr(a, es) for a in (vx, vy, vz, T)]
         nseg = (C.c_int * 3)()
         self._chk(self.lib.fs3d_update_nodes_dev(self.h, *ptrs, nseg))
+        self.num_segments = list(nseg)
+        return self.num_segments
+
+    def _grid2d_arrays(self, g2):
+        """cell, velx, vely, T of a shape2d.Grid2D (or any object with these four [dimx, dimy] arrays) as the C ABI takes them."""
+        arrs = [np.ascontiguousarray(g2.cell, np.uint8)] + [np.ascontiguousarray(a, np.float32) for a in (g2.velx, g2.vely, g2.T)]
+        for a in arrs:
+            if a.shape != tuple(self.gdims[:2]):
+                raise ValueError("the 2D grid is %s, the context's plane %s" % (a.shape, tuple(self.gdims[:2])))
+        return arrs
+
+    def extrude_shape2d_dev(self, g2, dz, depth, depth_var, baseT, type, bc_vel, bc_temp, vx, vy, vz, T):
+        """Grid3D::Prepare2D on the device: the 2D grid g2 as it stands (after g2.prepare(t)) extruded into seven arrays on the
+        context's device -- torch tensors or raw pointers, as update_nodes_dev takes them.  The context's geometry is not touched."""
+        def ptr(a, want):
+            if isinstance(a, int):
+                return C.c_void_p(a)
+            if not a.is_cuda or not a.is_contiguous() or a.element_size() != want or a.numel() != int(np.prod(self.gdims)):
+                raise ValueError("extrude_shape2d_dev: contiguous device tensors of the grid's size and the context's precision")
+            return C.c_void_p(a.data_ptr())
+        es = self.dtype.itemsize
+        ptrs = [ptr(a, 1) for a in (type, bc_vel, bc_temp)] + [ptr(a, es) for a in (vx, vy, vz, T)]
+        arrs = self._grid2d_arrays(g2)
+        self._chk(self.lib.fs3d_extrude_shape2d_dev(self.h, *[_p(a) for a in arrs], float(dz), float(depth), float(depth_var), float(baseT), *ptrs))
+
+    def update_nodes_shape2d(self, g2, dz, depth, depth_var, baseT):
+        """update_nodes with the extrusion of the 2D grid g2 as the source: 13 bytes per column travel, the node arrays are written
+        by a kernel.  Same contract as update_nodes."""
+        arrs = self._grid2d_arrays(g2)
+        nseg = (C.c_int * 3)()
+        self._chk(self.lib.fs3d_update_nodes_shape2d(self.h, *[_p(a) for a in arrs], float(dz), float(depth), float(depth_var), float(baseT), nseg))
         self.num_segments = list(nseg)
         return self.num_segments
 
@@ -341,6 +375,15 @@ class LocalGroup:
             self.close()
         except Exception:
             pass
+
+
+def shape2d_bottom(dimx, dimy, dz, depth, depth_var):
+    """The per-column `bottom` table of the extrusion as the library computes it (host only, no GPU): int32 [dimx, dimy]."""
+    out = np.empty((dimx, dimy), np.int32)
+    st = load().fs3d_shape2d_bottom(dimx, dimy, float(dz), float(depth), float(depth_var), out.ctypes.data_as(C.POINTER(C.c_int)))
+    if st != OK:
+        raise Fs3dError(st, "fs3d_shape2d_bottom: bad dims, or depth / dz gives no active_dimz")
+    return out
 
 
 def fluid_params(dtype, Re, Pr, lam):

@@ -87,6 +87,12 @@ struct fs3d_geom {
     int *rep[2] = {};                       // [column id]: the group whose column it is
     unsigned long long *cnt = nullptr;      // counter words of one update
     void *host = nullptr;                   // pinned: counters, hashes, flags on their way to / from the host
+    // extrusion of a Shape2D grid (k_geom_extrude): the per-column records, allocated by the first call.  One pinned block and its
+    // device copy, dimx*dimy columns each: velx, vely, T (float), cell (uint8) -- the 13 bytes per column that change with time --
+    // then bottom (int), which changes with (dz, depth, depth_var) only
+    void *ex_host = nullptr, *ex_dev = nullptr;
+    bool ex_bottom_valid = false;           // the bottom table on the device is the one of (ex_dz, ex_depth, ex_depth_var)
+    double ex_dz = 0, ex_depth = 0, ex_depth_var = 0;
     // device time of one update (fs3d_last_update_device_ms): event pairs around every batch of launches between two synchronisations
     hipEvent_t ev[16] = {};
     int ev_n = 0;

@@ -2,6 +2,8 @@
 // (fs3d_update_nodes / fs3d_update_nodes_dev), Solver3D::ClearOutterCells (fs3d_clear_outer_cells) and the
 // table summary fs3d_geometry_info.  The host routine upload_nodes_impl (fs3d_hip.hip) stays the first upload and the
 // definition of every table; the kernels here end with the same tables.
+// Also the extrusion of a Shape2D grid into the node arrays on the device (k_geom_extrude; fs3d_extrude_shape2d_dev,
+// fs3d_update_nodes_shape2d): a moving Shape2D geometry then ships its 2D grid per step, not the 3D node arrays.
 //
 // Row kinds without the serial walk of line_kinds (fs3d_hip.hip): that walk opens a run at `pos` when cell pos + 1 is
 // NODE_IN and closes it at the first cell after the run that is not NODE_IN; a run that reaches the end of the line is
@@ -13,6 +15,8 @@
 // refusal), and the number of segments is the number of START cells.
 #include <algorithm>
 #include <chrono>
+#include <climits>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -289,6 +293,97 @@ __global__ void __launch_bounds__(256) k_clear_outer(const uint16_t *__restrict_
         if (((code[i] >> CODE_TYPE_SHIFT) & 3) == FS3D_NODE_OUT) { d0[i] = R(0); d1[i] = R(0); d2[i] = R(0); d3[i] = baseT; }
 }
 
+// Grid3D::Prepare2D (Grid3D.cpp:608-668) as host/Shape2D.h ExtrudeShape2D states it: the node of cell (i, j, k) from the record of
+// column (i, j) -- the 2D cell type c2, its velocity and temperature, and `bottom` -- and the scalars A = active_dimz and baseT.
+// The host function writes some cells several times and the last write wins; as a priority list, first match decides:
+//   1. c2 == NODE_OUT                       OUT,   NOSLIP / NOSLIP, v = 0, T = 0     (the whole column; nothing else is written)
+//   2. bottom < k < A - 2  (the middle)     c2 == IN:    IN,    NOSLIP / NOSLIP, v = 0,                T = baseT
+//                                           c2 == BOUND: BOUND, NOSLIP / FREE,   v = (velx, vely, 0),  T = T2
+//                                           c2 == VALVE: VALVE, FREE / FREE when velx == 0 and vely == 0, else NOSLIP / NOSLIP; v, T as BOUND
+//   3. 1 <= k <= bottom    (the floor)      BOUND, NOSLIP / FREE, v = 0, T = baseT   (passes A - 2 and the lid where bottom does)
+//   4. k == 0                               OUT by type only: what the bound of A - 2 wrote stays when A == 2 (NOSLIP / FREE, T = baseT),
+//                                           else NOSLIP / NOSLIP, v = 0, T = 0
+//   5. k == A - 2          (the bound)      BOUND, NOSLIP / FREE, v = 0, T = baseT
+//   6. k >= A - 1          (the lid)        OUT,   NOSLIP / NOSLIP, v = 0, T = 0
+// (host order: memset, 1, 6, 5, 4, 3, 2.)  vz is 0 everywhere.  No arithmetic: 2D floats widen to R exactly.
+struct ExNode { int type, bv, bt; float vx, vy, T; };
+
+__device__ __forceinline__ ExNode extrude_node(int k, int c2, float velx, float vely, float T2, int bottom, int A, float baseT)
+{
+    ExNode n = {FS3D_NODE_OUT, FS3D_BC_NOSLIP, FS3D_BC_NOSLIP, 0.0f, 0.0f, 0.0f};
+    if (c2 == FS3D_NODE_OUT) return n;
+    if (k > bottom && k < A - 2) {
+        n.type = c2;
+        if (c2 == FS3D_NODE_IN) { n.T = baseT; return n; }
+        const bool rest = c2 == FS3D_NODE_VALVE && velx == 0.0f && vely == 0.0f;
+        n.bv = rest ? FS3D_BC_FREE : FS3D_BC_NOSLIP;
+        n.bt = (rest || c2 == FS3D_NODE_BOUND) ? FS3D_BC_FREE : FS3D_BC_NOSLIP;
+        n.vx = velx; n.vy = vely; n.T = T2;
+        return n;
+    }
+    const bool floor_ = k >= 1 && k <= bottom;
+    if (floor_ || k == A - 2) {                         // k == 0 == A - 2: the bound's values under the type of rule 4
+        n.type = (floor_ || k != 0) ? FS3D_NODE_BOUND : FS3D_NODE_OUT;
+        n.bt = FS3D_BC_FREE; n.T = baseT;
+    }
+    return n;
+}
+
+// Pure store kernel, 19 bytes per cell in fp32 and 35 in fp64.  One thread writes V consecutive k of one column: V == 4 (dimz % 4 == 0,
+// the byte arrays aligned to 4 bytes and the value arrays to 16) one dword per byte array and 16-byte stores for the value arrays
+// (one per array in fp32, two in fp64), V == 1 cell by cell.
+// Lanes run along k, so a wave writes 64 * V consecutive cells; the column record is read once per thread.  Stores are nontemporal:
+// the geometry kernels read these arrays next, but only after the whole grid has been written.
+template <typename R, int V>
+__global__ void __launch_bounds__(256) k_geom_extrude(const float *__restrict__ velx, const float *__restrict__ vely, const float *__restrict__ T2,
+                                                       const int *__restrict__ bottom, const uint8_t *__restrict__ cell, long long ncol, int dimz,
+                                                       int A, float baseT, uint8_t *__restrict__ type, uint8_t *__restrict__ bc_vel,
+                                                       uint8_t *__restrict__ bc_temp, R *__restrict__ vx, R *__restrict__ vy, R *__restrict__ vz,
+                                                       R *__restrict__ T)
+{
+    constexpr int P = 16 / sizeof(R);                  // values per 16-byte store
+    typedef R RP __attribute__((ext_vector_type(P)));
+    const int nq = dimz / V;                           // V == 4: dimz % 4 == 0
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= ncol * nq) return;
+    const long long col = t / nq;
+    const int k0 = (int)(t - col * nq) * V;
+    const int c2 = cell[col], bot = bottom[col];
+    const float ux = velx[col], uy = vely[col], t2 = T2[col];
+    const long long l = col * dimz + k0;               // < ncol * dimz: the arrays' size
+    unsigned wt = 0, wv = 0, wb = 0;
+    R ax[V], ay[V], aT[V];
+#pragma unroll
+    for (int q = 0; q < V; q++) {
+        const ExNode n = extrude_node(k0 + q, c2, ux, uy, t2, bot, A, baseT);
+        wt |= (unsigned)n.type << (8 * q); wv |= (unsigned)n.bv << (8 * q); wb |= (unsigned)n.bt << (8 * q);
+        ax[q] = (R)n.vx; ay[q] = (R)n.vy; aT[q] = (R)n.T;
+    }
+    if constexpr (V == 4) {
+        __builtin_nontemporal_store(wt, (unsigned *)(type + l));
+        __builtin_nontemporal_store(wv, (unsigned *)(bc_vel + l));
+        __builtin_nontemporal_store(wb, (unsigned *)(bc_temp + l));
+#pragma unroll
+        for (int h = 0; h < V; h += P) {
+            RP x, y, z, w;
+#pragma unroll
+            for (int q = 0; q < P; q++) { x[q] = ax[h + q]; y[q] = ay[h + q]; z[q] = R(0); w[q] = aT[h + q]; }
+            __builtin_nontemporal_store(x, (RP *)(vx + l + h));
+            __builtin_nontemporal_store(y, (RP *)(vy + l + h));
+            __builtin_nontemporal_store(z, (RP *)(vz + l + h));
+            __builtin_nontemporal_store(w, (RP *)(T + l + h));
+        }
+    } else {
+        __builtin_nontemporal_store((uint8_t)wt, type + l);
+        __builtin_nontemporal_store((uint8_t)wv, bc_vel + l);
+        __builtin_nontemporal_store((uint8_t)wb, bc_temp + l);
+        __builtin_nontemporal_store(ax[0], vx + l);
+        __builtin_nontemporal_store(ay[0], vy + l);
+        __builtin_nontemporal_store(R(0), vz + l);
+        __builtin_nontemporal_store(aT[0], T + l);
+    }
+}
+
 // ---------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------
@@ -347,6 +442,8 @@ void fs3d_geom_destroy(fs3d_ctx *c)
     }
     if (g.cnt) hipFree(g.cnt);
     if (g.host) hipHostFree(g.host);
+    if (g.ex_host) hipHostFree(g.ex_host);
+    if (g.ex_dev) hipFree(g.ex_dev);
 }
 
 // the buffers an update keeps: allocated by the first one
@@ -482,27 +579,140 @@ static fs3d_status update_nodes_impl(fs3d_ctx *c, const uint8_t *type, const uin
     return FS3D_OK;
 }
 
-static fs3d_status update_nodes_common(fs3d_ctx *c, bool host_arrays, const uint8_t *type, const uint8_t *bc_vel, const uint8_t *bc_temp,
-                                       const void *vx, const void *vy, const void *vz, const void *T, int n_seg_out[3])
+// ---- extrusion of a Shape2D grid ----------------------------------------------------------------------------------------------
+struct ExtrudeIn { const uint8_t *cell; const float *velx, *vely, *T; double dz, depth, depth_var, baseT; int A; };
+
+#define EX_BOTTOM_BAD INT_MIN
+
+// active_dimz of Grid3D::LoadFromFile (Grid3D.cpp:503-505), for values that give an int
+static bool extrude_active_dimz(double dz, double depth, int *A)
 {
-    const char *name = host_arrays ? "fs3d_update_nodes" : "fs3d_update_nodes_dev";
+    if (!(dz > 0) || !(depth >= 0) || !(depth / dz <= 65536.0)) return false;
+    *A = (int)std::ceil(depth / dz) + 1;
+    return true;
+}
+
+// `bottom` of every column with the expression of ExtrudeShape2D (Grid3D.cpp:632-636), on the host and without contraction: a
+// last-bit difference in front of (int) moves a wall by a cell.  A product outside int marks the column EX_BOTTOM_BAD.
+static void extrude_bottom_table(int dimx, int dimy, int A, double depth_var, int *out)
+{
+#pragma clang fp contract(off)
+    const int height = std::max(A - 2 - 2, 0);
+    for (int i = 0; i < dimx; i++)
+        for (int j = 0; j < dimy; j++) {
+            const double x = -1 + 2 * (double)i / dimx, y = -1 + 2 * (double)j / dimy;
+            const double z = 1.0 - (x * x + y * y) * 0.5;
+            const double v = depth_var * z * height;
+            out[(size_t)i * dimy + j] = (v > -1e9 && v < 1e9) ? 1 + (int)v : EX_BOTTOM_BAD;
+        }
+}
+
+extern "C" fs3d_status fs3d_shape2d_bottom(int dimx, int dimy, double dz, double depth, double depth_var, int *bottom_out)
+{
+    int A = 0;
+    if (dimx < 1 || dimy < 1 || !bottom_out || !extrude_active_dimz(dz, depth, &A)) return FS3D_ERR_INVALID;
+    extrude_bottom_table(dimx, dimy, A, depth_var, bottom_out);
+    return FS3D_OK;
+}
+
+static inline size_t ex_off_cell(size_t ncol) { return 12 * ncol; }
+static inline size_t ex_off_bottom(size_t ncol) { return 12 * ncol + ((ncol + 3) & ~(size_t)3); }
+static inline size_t ex_bytes(size_t ncol) { return ex_off_bottom(ncol) + 4 * ncol; }
+
+// Everything that refuses an extrusion, before anything is launched; leaves the column records in the pinned block.
+static fs3d_status extrude_check(fs3d_ctx *c, ExtrudeIn &in, const char *name)
+{
+    fs3d_geom &g = c->geom;
+    if (!extrude_active_dimz(in.dz, in.depth, &in.A) || in.A < 2 || in.A > c->dimz)
+        return gfail(c, FS3D_ERR_INVALID, std::string(name) + ": active_dimz = ceil(depth / dz) + 1 must lie in 2 .. dimz");
+    const size_t ncol = (size_t)c->dimx * c->dimy;
+    GHIP(c, hipSetDevice(c->device));
+    if (!g.ex_host) GHIP(c, hipHostMalloc(&g.ex_host, ex_bytes(ncol), hipHostMallocDefault));
+    if (!g.ex_dev) {                                      // (a failure leaves the pointer null: the next call allocates again)
+        GMALLOC(c, &g.ex_dev, ex_bytes(ncol));
+        g.ex_bottom_valid = false; g.ex_dz = -1;
+    }
+    char *h = (char *)g.ex_host;
+    int *bottom = (int *)(h + ex_off_bottom(ncol));
+    if (g.ex_dz != in.dz || g.ex_depth != in.depth || g.ex_depth_var != in.depth_var) {      // (a NaN depth_var: recomputed every call)
+        extrude_bottom_table(c->dimx, c->dimy, in.A, in.depth_var, bottom);
+        g.ex_dz = in.dz; g.ex_depth = in.depth; g.ex_depth_var = in.depth_var; g.ex_bottom_valid = false;
+    }
+    for (size_t q = 0; q < ncol; q++) {
+        const uint8_t t = in.cell[q];
+        if (t > FS3D_NODE_VALVE) return gfail(c, FS3D_ERR_INVALID, std::string(name) + ": a cell2d value is not a node type");
+        // where ExtrudeShape2D would write outside the column's dimz cells (it reads `bottom` of the columns that are not NODE_OUT)
+        if (t != FS3D_NODE_OUT && (bottom[q] < -1 || bottom[q] >= c->dimz))
+            return gfail(c, FS3D_ERR_INVALID, std::string(name) + ": depth_var puts the bottom of a column outside the grid");
+    }
+    memcpy(h, in.velx, 4 * ncol); memcpy(h + 4 * ncol, in.vely, 4 * ncol); memcpy(h + 8 * ncol, in.T, 4 * ncol);
+    memcpy(h + ex_off_cell(ncol), in.cell, ncol);
+    return FS3D_OK;
+}
+
+// the column records to the device and the kernel, on the context's stream; not synchronised
+template <typename R>
+static fs3d_status extrude_launch(fs3d_ctx *c, const ExtrudeIn &in, uint8_t *type, uint8_t *bc_vel, uint8_t *bc_temp, void *vx, void *vy, void *vz, void *T)
+{
+    fs3d_geom &g = c->geom;
+    const size_t ncol = (size_t)c->dimx * c->dimy;
+    const char *d = (const char *)g.ex_dev;
+    GHIP(c, hipMemcpyAsync(g.ex_dev, g.ex_host, g.ex_bottom_valid ? ex_off_cell(ncol) + ncol : ex_bytes(ncol), hipMemcpyHostToDevice, c->stream));
+    g.ex_bottom_valid = true;
+    uintptr_t mis = ((uintptr_t)type | (uintptr_t)bc_vel | (uintptr_t)bc_temp) & 3;
+    mis |= ((uintptr_t)vx | (uintptr_t)vy | (uintptr_t)vz | (uintptr_t)T) & 15;
+    const bool vec = c->dimz % 4 == 0 && !mis;
+    const long long nthr = (long long)ncol * (vec ? c->dimz / 4 : c->dimz);
+    auto kern = vec ? k_geom_extrude<R, 4> : k_geom_extrude<R, 1>;
+    hipLaunchKernelGGL(kern, dim3(geom_grid(nthr, 1 << 30)), dim3(256), 0, c->stream, (const float *)d, (const float *)(d + 4 * ncol),
+                       (const float *)(d + 8 * ncol), (const int *)(d + ex_off_bottom(ncol)), (const uint8_t *)(d + ex_off_cell(ncol)),
+                       (long long)ncol, c->dimz, in.A, (float)in.baseT, type, bc_vel, bc_temp, (R *)vx, (R *)vy, (R *)vz, (R *)T);
+    GHIP(c, hipGetLastError());
+    return FS3D_OK;
+}
+
+static bool geom_is_slab(const fs3d_ctx *c) { return c->dimx != c->dimx_global || c->x_offset != 0 || c->comm || c->local || c->nranks > 1; }
+
+// ex != nullptr: the seven arrays come from the extrusion kernel (fs3d_update_nodes_shape2d)
+static fs3d_status update_nodes_common(fs3d_ctx *c, bool host_arrays, const uint8_t *type, const uint8_t *bc_vel, const uint8_t *bc_temp,
+                                       const void *vx, const void *vy, const void *vz, const void *T, int n_seg_out[3],
+                                       const ExtrudeIn *ex = nullptr)
+{
+    const char *name = ex ? "fs3d_update_nodes_shape2d" : host_arrays ? "fs3d_update_nodes" : "fs3d_update_nodes_dev";
     if (!c) return FS3D_ERR_INVALID;
-    if (!type || !bc_vel || !bc_temp || !vx || !vy || !vz || !T) return gfail(c, FS3D_ERR_INVALID, std::string(name) + ": NULL array");
-    if (c->dimx != c->dimx_global || c->x_offset != 0 || c->comm || c->local || c->nranks > 1)
+    if (ex ? (!ex->cell || !ex->velx || !ex->vely || !ex->T) : (!type || !bc_vel || !bc_temp || !vx || !vy || !vz || !T))
+        return gfail(c, FS3D_ERR_INVALID, std::string(name) + ": NULL array");
+    if (geom_is_slab(c))
         return gfail(c, FS3D_ERR_UNSUPPORTED, std::string(name) + ": moving geometry is implemented for a single context only, "
                      "not for an x-slab of a larger grid or a member of a multi-GPU group");
     if (!c->uploaded_once)
         return gfail(c, FS3D_ERR_INVALID, std::string(name) + ": the first geometry comes through fs3d_upload_nodes; upload nodes first");
     const auto t0 = std::chrono::steady_clock::now();
     GHIP(c, hipSetDevice(c->device));
+    fs3d_status st;
+    ExtrudeIn exin;
+    if (ex) {                                             // refused here, the context keeps the geometry it has
+        exin = *ex;
+        st = extrude_check(c, exin, name);
+        if (st) return st;
+    }
     // rebuilt in place: from here until the end the context has no geometry
     c->have_nodes = false;
-    fs3d_status st = geom_prepare(c, host_arrays);
+    st = geom_prepare(c, host_arrays || ex);
     if (st) return st;
     const void *val[4] = {vx, vy, vz, T};
     c->geom.ev_n = 0; c->geom.ev_open = false;
     gev_begin(c);
-    if (host_arrays) {
+    if (ex) {
+        // the three byte arrays into the staging buffer, the four value fields straight into the node-value table
+        uint8_t *sg = c->geom.stage;
+        char *nv[4];
+        for (int v = 0; v < 4; v++) { nv[v] = (char *)c->node + (size_t)v * c->nstride * c->esize; val[v] = nv[v]; }
+        st = c->prec == FS3D_F32 ? extrude_launch<float>(c, exin, sg, sg + c->ncell, sg + 2 * c->ncell, nv[0], nv[1], nv[2], nv[3])
+                                 : extrude_launch<double>(c, exin, sg, sg + c->ncell, sg + 2 * c->ncell, nv[0], nv[1], nv[2], nv[3]);
+        if (st) return st;
+        type = sg; bc_vel = sg + c->ncell; bc_temp = sg + 2 * c->ncell;
+    } else if (host_arrays) {
         const uint8_t *src[3] = {type, bc_vel, bc_temp};
         for (int a = 0; a < 3; a++)
             GHIP(c, hipMemcpyAsync(c->geom.stage + (size_t)a * c->ncell, src[a], (size_t)c->ncell, hipMemcpyHostToDevice, c->stream));
@@ -533,6 +743,34 @@ extern "C" fs3d_status fs3d_update_nodes_dev(fs3d_ctx *c, const uint8_t *type, c
                                              const void *vx, const void *vy, const void *vz, const void *T, int n_seg_out[3])
 {
     return update_nodes_common(c, false, type, bc_vel, bc_temp, vx, vy, vz, T, n_seg_out);
+}
+
+extern "C" fs3d_status fs3d_update_nodes_shape2d(fs3d_ctx *c, const uint8_t *cell2d, const float *velx2d, const float *vely2d, const float *T2d,
+                                                 double dz, double depth, double depth_var, double baseT, int n_seg_out[3])
+{
+    const ExtrudeIn in = {cell2d, velx2d, vely2d, T2d, dz, depth, depth_var, baseT, 0};
+    return update_nodes_common(c, false, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, n_seg_out, &in);
+}
+
+extern "C" fs3d_status fs3d_extrude_shape2d_dev(fs3d_ctx *c, const uint8_t *cell2d, const float *velx2d, const float *vely2d, const float *T2d,
+                                                double dz, double depth, double depth_var, double baseT, uint8_t *type_out,
+                                                uint8_t *bc_vel_out, uint8_t *bc_temp_out, void *vx_out, void *vy_out, void *vz_out, void *T_out)
+{
+    const char *name = "fs3d_extrude_shape2d_dev";
+    if (!c) return FS3D_ERR_INVALID;
+    if (!cell2d || !velx2d || !vely2d || !T2d || !type_out || !bc_vel_out || !bc_temp_out || !vx_out || !vy_out || !vz_out || !T_out)
+        return gfail(c, FS3D_ERR_INVALID, std::string(name) + ": NULL array");
+    if (geom_is_slab(c))
+        return gfail(c, FS3D_ERR_UNSUPPORTED, std::string(name) + ": the extrusion is implemented for a single context only, "
+                     "not for an x-slab of a larger grid or a member of a multi-GPU group");
+    ExtrudeIn in = {cell2d, velx2d, vely2d, T2d, dz, depth, depth_var, baseT, 0};
+    fs3d_status st = extrude_check(c, in, name);
+    if (st) return st;
+    st = c->prec == FS3D_F32 ? extrude_launch<float>(c, in, type_out, bc_vel_out, bc_temp_out, vx_out, vy_out, vz_out, T_out)
+                             : extrude_launch<double>(c, in, type_out, bc_vel_out, bc_temp_out, vx_out, vy_out, vz_out, T_out);
+    if (st) return st;
+    GHIP(c, hipStreamSynchronize(c->stream));
+    return FS3D_OK;
 }
 
 extern "C" fs3d_status fs3d_last_update_device_ms(fs3d_ctx *c, float *ms_out)

@@ -97,6 +97,16 @@ public:
         chk(fs3d_update_nodes(ctx_, grid.type.data(), grid.bc_vel.data(), grid.bc_temp.data(), grid.vx.data(), grid.vy.data(),
                               grid.vz.data(), grid.T.data(), numSegs));
     }
+    // The same for a grid that is the extrusion of a 2D grid (Grid3D::Prepare2D, Grid3D.cpp:608-668): g2 as it stands after
+    // g2.Prepare(t) is extruded on the device -- its cell types and three floats per column travel, no 3D node array is built or
+    // copied on the host.  G2 = fs3d::Grid2D (host/Shape2D.h); dz, depth, depth_var as ExtrudeShape2D takes them, baseT the grid's
+    // of Init.  The host Grid3D given to Init is NOT kept current by this call: only its dims and baseT are read afterwards.
+    template <typename G2>
+    void UpdateGridExtruded(const G2 &g2, double dz, double depth, double depth_var)
+    {
+        if (g2.dimx != grid_->dimx || g2.dimy != grid_->dimy) throw std::runtime_error("UpdateGridExtruded: the 2D grid does not have the 3D grid's dims");
+        chk(fs3d_update_nodes_shape2d(ctx_, g2.cell.data(), g2.velx.data(), g2.vely.data(), g2.T.data(), dz, depth, depth_var, grid_->baseT, numSegs));
+    }
     // Solver3D::ClearOutterCells (Solver3D.cpp:41-44), on `next` as there and on `cur`: a cell that turns NODE_IN with the next
     // geometry starts from (0, 0, 0, baseT) in both
     void ClearOutterCells()

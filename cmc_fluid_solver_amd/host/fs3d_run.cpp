@@ -1,5 +1,5 @@
 // Command-line driver: the reference's FluidSolver3D main (FluidSolver3D/FluidSolver3D.cpp:60-330) on top of
-// libfs3d_hip.so.   fs3d_run <input data> <output prefix> <config> [align] [GPU [n]] [double] [moving] [--steps N] [--same-device] [--grid-only FILE [--grid-time T]]
+// libfs3d_hip.so.   fs3d_run <input data> <output prefix> <config> [align] [GPU [n]] [double] [moving [--host-extrusion] [--time-geometry]] [--steps N] [--same-device] [--grid-only FILE [--grid-time T]]
 //   * reads the config (host/Config.h) and a Shape2D, Shape3D or SeaNetCDF geometry (host/Shape2D.h, Shape3D.h, SeaNetCDF.h), prints the grid summary lines
 //     the reference prints ("Grid = X x Y x Z", "NODE_IN points = ..."),
 //   * runs the same loop: dt = cycle length / (frames * time_steps), UpdateBoundaries + TimeStep per step with the
@@ -7,9 +7,13 @@
 //   * writes <output prefix>_res.nc through host/NetCDF3.h every out_time_steps steps (GetLayer).
 // `transpose`, `decompose`, `blocking n` of the reference are accepted and ignored (backend tuning switches); `CSV`
 // switches the closing timing table to the reference's comma-separated form.
-// `moving` (single GPU, in_fmt Shape2D): the walls follow the frames of the input -- per step grid2D->Prepare(t), the extrusion,
-//   CreateSegments on the device (UpdateGrid), UpdateBoundaries, TimeStep, the output, ClearOutterCells: the loop of the reference's
-//   2D driver (FluidSolver2D.cpp:130-133) with the 3D classes' mechanism (AdiSolver3D.cpp:382-385, Solver3D.cpp:41-44).
+// `moving` (single GPU, in_fmt Shape2D): the walls follow the frames of the input -- per step grid2D->Prepare(t), the extrusion and
+//   CreateSegments on the device (UpdateGridExtruded: the 2D grid travels, the node arrays are written by a kernel), UpdateBoundaries,
+//   TimeStep, the output, ClearOutterCells: the loop of the reference's 2D driver (FluidSolver2D.cpp:130-133) with the 3D classes'
+//   mechanism (AdiSolver3D.cpp:382-385, Solver3D.cpp:41-44).
+//   --host-extrusion: the extrusion on the host (ExtrudeShape2D into the Grid3D, then UpdateGrid with its seven arrays) -- the same
+//   results bit for bit; kept for A/B timing and as the checker of the device extrusion.
+//   --time-geometry: one more line after the timing table, the host clock per step around Prepare, the host extrusion and the update call.
 // There is no CPU backend here: without a GPU the run stops with the library's error.
 // --grid-only FILE: build the grid, dump it (dims, type, bc_vel, bc_temp, vx, vy, vz, T as raw arrays) and exit
 //   without touching the GPU -- used by the CPU tests to compare the C++ loader with its Python twin.
@@ -50,10 +54,12 @@ static int run_slabs(const fs3d::Grid3D<FTYPE> &grid, const RunGeom &geo, const 
 
 template <typename FTYPE>
 static int run(const std::string &data, const std::string &prefix, const fs3d::Config &cfg, bool align, int device, long max_steps, const std::string &grid_only, bool csv,
-               int nslabs, bool same_device, bool grid_images, bool moving, double grid_time)
+               int nslabs, bool same_device, bool grid_images, bool moving, double grid_time, bool host_extrusion, bool time_geometry)
 {
     if (moving && cfg.in_fmt != "Shape2D") throw std::runtime_error("moving: only in_fmt Shape2D inputs move (this one is " + cfg.in_fmt + ")");
     if (moving && nslabs > 1) throw std::runtime_error("moving: single GPU only (moving geometry on x-slabs is not implemented)");
+    if (host_extrusion && !moving) throw std::runtime_error("--host-extrusion: only with moving (it selects where a moving geometry is extruded)");
+    if (time_geometry && !moving) throw std::runtime_error("--time-geometry: only with moving (it times the per-step geometry work)");
     if (grid_time >= 0 && cfg.in_fmt != "Shape2D") throw std::runtime_error("--grid-time: only in_fmt Shape2D inputs move");
     using namespace fs3d;
     Grid3D<FTYPE> grid;
@@ -122,15 +128,24 @@ static int run(const std::string &data, const std::string &prefix, const fs3d::C
     double t = dt;
     long steps = 0;
     int lastframe = -1;
+    double geom_ms[3] = {0, 0, 0};                     // moving: host clock around Prepare, the host extrusion, the update call
     // the geometry is frame 0's for the whole run: the reference prepares the grid once, before the loop (grid->Prepare(0), :226;
     // the per-step grid->Prepare(t) is commented out, :237) -- the frame only restarts the substep counter
     for (int i = 0; t < finaltime && (max_steps < 0 || steps < max_steps); t += dt, i++, steps++) {
         const int currentframe = geo.GetFrame(t);                                                        // :229-236
         if (currentframe != lastframe) { lastframe = currentframe; i = 0; }
         if (moving) {                                                                                    // grid->Prepare(t), :237
+            const auto g0 = std::chrono::steady_clock::now();
             g2.Prepare(t);
-            ExtrudeShape2D(grid, g2, cfg.dz, cfg.depth, cfg.depth_var, cfg.baseT);
-            solver.UpdateGrid(grid);
+            const auto g1 = std::chrono::steady_clock::now();
+            if (host_extrusion) ExtrudeShape2D(grid, g2, cfg.dz, cfg.depth, cfg.depth_var, cfg.baseT);
+            const auto g3 = std::chrono::steady_clock::now();
+            if (host_extrusion) solver.UpdateGrid(grid);
+            else solver.UpdateGridExtruded(g2, cfg.dz, cfg.depth, cfg.depth_var);   // `grid` keeps the nodes of time 0: only its dims and baseT are read from here on
+            const auto g4 = std::chrono::steady_clock::now();
+            geom_ms[0] += std::chrono::duration<double, std::milli>(g1 - g0).count();
+            geom_ms[1] += std::chrono::duration<double, std::milli>(g3 - g1).count();
+            geom_ms[2] += std::chrono::duration<double, std::milli>(g4 - g3).count();
         }
         solver.UpdateBoundaries();                                                                       // :244
         solver.TimeStep((FTYPE)dt, cfg.num_global, cfg.num_local, (i % 10 == 0) || (t + dt >= finaltime)); // :245
@@ -174,6 +189,9 @@ static int run(const std::string &data, const std::string &prefix, const fs3d::C
         fs3d_last_sweep_kernel(solver.ctx(), 0, &kx, &sg); fs3d_last_sweep_kernel(solver.ctx(), 1, &ky, &sg); fs3d_last_sweep_kernel(solver.ctx(), 2, &kz, &sg);
         std::printf("Sweep kernels: X %s, Y %s, Z %s\n", kn[kx & 3], kn[ky & 3], kn[kz & 3]);
     }
+    if (moving && time_geometry && steps > 0)
+        std::printf("Moving geometry per step (host clock, ms): Prepare %.3f, extrusion on the host %.3f, update call %.3f; step %.3f\n",
+                    geom_ms[0] / steps, geom_ms[1] / steps, geom_ms[2] / steps, sec * 1e3 / steps);
     std::printf("%ld steps in %.3f s: %.1f Mcells/s; %u layers in %s\n", steps, sec,
                 (double)grid.dimx * grid.dimy * grid.dimz * steps / sec / 1e6, nc.NumRecords(), out.c_str());
     return 0;
@@ -283,7 +301,7 @@ static int run_slabs(const fs3d::Grid3D<FTYPE> &grid, const RunGeom &geo, const 
 int main(int argc, char **argv)
 {
     if (argc < 4) {
-        std::printf("Usage: %s <input data> <output prefix> <config file> [align] [GPU [n]] [double] [--steps N] [moving] [--grid-only FILE [--grid-time T]] [--grid-images]\n", argv[0]);
+        std::printf("Usage: %s <input data> <output prefix> <config file> [align] [GPU [n]] [double] [--steps N] [moving [--host-extrusion] [--time-geometry]] [--grid-only FILE [--grid-time T]] [--grid-images]\n", argv[0]);
         return 0;
     }
     try {
@@ -293,7 +311,7 @@ int main(int argc, char **argv)
         if (cfg.in_fmt != "Shape2D" && cfg.in_fmt != "Shape3D" && cfg.in_fmt != "SeaNetCDF") throw std::runtime_error("in_fmt " + cfg.in_fmt + ": unknown input format");
         if (cfg.in_fmt != "Shape2D" && !(cfg.frame_time > 0)) throw std::runtime_error("must specify frame time!");   // the cycle length of a Shape3D run (Grid3D.cpp:303-309)
         if (cfg.solver != "ADI") throw std::runtime_error("solver " + cfg.solver + " is not implemented (the reference implements ADI only)");
-        bool align = false, dbl = false, csv = false, same_device = false, grid_images = false, moving = false;
+        bool align = false, dbl = false, csv = false, same_device = false, grid_images = false, moving = false, host_extrusion = false, time_geometry = false;
         double grid_time = -1;
         int nslabs = 1;
         int device = 0;
@@ -310,13 +328,15 @@ int main(int argc, char **argv)
             else if (s == "--grid-only" && a + 1 < argc) grid_only = argv[++a];
             else if (s == "--grid-time" && a + 1 < argc) grid_time = std::atof(argv[++a]);
             else if (s == "moving") moving = true;
+            else if (s == "--host-extrusion") host_extrusion = true;
+            else if (s == "--time-geometry") time_geometry = true;
             else if (s == "blocking") { if (a + 1 < argc) a++; }
             else if (s == "CSV") csv = true;
             else if (s == "--grid-images") grid_images = true;       // <prefix>_grid_3d/<k>.bmp: the node types, one image per z-slice
             // transpose, decompose: accepted, no effect
         }
-        return dbl ? run<double>(argv[1], argv[2], cfg, align, device, max_steps, grid_only, csv, nslabs, same_device, grid_images, moving, grid_time)
-                   : run<float>(argv[1], argv[2], cfg, align, device, max_steps, grid_only, csv, nslabs, same_device, grid_images, moving, grid_time);
+        return dbl ? run<double>(argv[1], argv[2], cfg, align, device, max_steps, grid_only, csv, nslabs, same_device, grid_images, moving, grid_time, host_extrusion, time_geometry)
+                   : run<float>(argv[1], argv[2], cfg, align, device, max_steps, grid_only, csv, nslabs, same_device, grid_images, moving, grid_time, host_extrusion, time_geometry);
     } catch (std::exception &e) {
         std::fprintf(stderr, "\n\nCaught exception:\n%s\n\nTerminating...\n", e.what());     // FluidSolver3D.cpp:313-318
         return -1;

@@ -225,6 +225,74 @@ def load_shape2d(path_or_text, dx, dy, dz, depth, depth_var=0.0, baseT=1.0, alig
     return nodes, g2
 
 
+def active_dimz_of(dz, depth):
+    return int(math.ceil(depth / dz)) + 1                            # Grid3D.cpp:503-505
+
+
+def bottom_table(dimx, dimy, active_dimz, depth_var):
+    """`bottom` of every column (Grid3D.cpp:632-636): 1 + (int)(depth_var * z * height), z = 1 - (x^2 + y^2) / 2 in double, every
+    operation rounded on its own (numpy does not contract), (int) truncating towards zero.  int64 [dimx, dimy]."""
+    height = max(active_dimz - 2 - 2, 0)
+    x = -1 + 2 * np.arange(dimx, dtype=np.float64)[:, None] / dimx
+    y = -1 + 2 * np.arange(dimy, dtype=np.float64)[None, :] / dimy
+    z = 1.0 - (x * x + y * y) * 0.5
+    return 1 + np.trunc(depth_var * z * height).astype(np.int64)
+
+
+def extrude_shape2d(cell, velx, vely, T2, dx, dy, dz, depth, depth_var=0.0, baseT=1.0, align=True, dimz=None):
+    """Grid3D::Prepare2D as a per-cell rule: what load_shape2d's loop leaves in every cell, stated without the loop -- the rule the
+    device kernel k_geom_extrude implements (csrc/kernels_geom.hip).  cell / velx / vely / T2: the [dimx, dimy] arrays of a Grid2D.
+    The loop writes some cells several times and the last write wins; as a priority list, first match decides, for cell (i, j, k)
+    with c2 = cell[i, j], A = active_dimz and bottom = bottom_table(...)[i, j]:
+      1. c2 == NODE_OUT                  OUT,   NOSLIP / NOSLIP, v = 0, T = 0
+      2. bottom < k < A - 2 (middle)     c2 == IN: IN, NOSLIP / NOSLIP, v = 0, T = baseT;  c2 == BOUND: BOUND, NOSLIP / FREE, v = (velx, vely, 0),
+                                         T = T2;  c2 == VALVE: VALVE, FREE / FREE at rest (velx == vely == 0) else NOSLIP / NOSLIP, v and T as BOUND
+      3. 1 <= k <= bottom   (floor)      BOUND, NOSLIP / FREE, v = 0, T = baseT
+      4. k == 0                          OUT by type only; NOSLIP / FREE and T = baseT where A == 2 (the bound of rule 5 wrote them), else zeros
+      5. k == A - 2         (bound)      BOUND, NOSLIP / FREE, v = 0, T = baseT
+      6. k >= A - 1         (lid)        OUT,   NOSLIP / NOSLIP, v = 0, T = 0
+    Returns Nodes (values float64 holding float32 numbers, as load_shape2d gives them)."""
+    cell = np.asarray(cell, np.uint8)
+    dimx, dimy = cell.shape
+    A = active_dimz_of(dz, depth)
+    if dimz is None:
+        dimz = align_by_32(A) if align else A
+    if A < 2 or A > dimz:
+        raise ValueError("active_dimz %d outside 2 .. dimz = %d" % (A, dimz))
+    bottom = bottom_table(dimx, dimy, A, depth_var)
+    live = cell != NODE_OUT
+    if live.any() and (bottom[live].min() < -1 or bottom[live].max() >= dimz):
+        raise ValueError("depth_var puts the bottom of a column outside the grid")
+    sh = (dimx, dimy, dimz)
+    k = np.arange(dimz)[None, None, :]
+    c2, bot = cell[:, :, None], bottom[:, :, None]
+    ux, uy, t2 = (np.asarray(a, np.float32)[:, :, None] for a in (velx, vely, T2))
+    bT = F(baseT)
+    out2 = np.broadcast_to(c2 == NODE_OUT, sh)
+    middle = ~out2 & (k > bot) & (k < A - 2)
+    floor = ~out2 & ~middle & (k >= 1) & (k <= bot)
+    bound = ~out2 & ~middle & ~floor & (k == A - 2)              # k == 0 here when A == 2: the values stay, rule 4 takes the type
+    wall = floor | (bound & (k != 0))
+    rest = (c2 == NODE_VALVE) & (ux == 0) & (uy == 0)
+    m_in, m_bv = middle & (c2 == NODE_IN), middle & (c2 != NODE_IN)
+    typ = np.full(sh, NODE_OUT, np.uint8)
+    typ[wall] = NODE_BOUND
+    typ[middle] = np.broadcast_to(c2, sh)[middle]
+    bcv = np.where(m_bv & rest, BC_FREE, BC_NOSLIP).astype(np.uint8)
+    bct = np.where(floor | bound | (m_bv & (rest | (c2 == NODE_BOUND))), BC_FREE, BC_NOSLIP).astype(np.uint8)
+    zero = np.zeros(sh, np.float32)
+    vx = np.where(m_bv, ux, zero)
+    vy = np.where(m_bv, uy, zero)
+    T = np.where(m_bv, t2, np.where(m_in | floor | bound, bT, zero)).astype(np.float32)
+    return Nodes(dimx, dimy, dimz, dx, dy, dz, typ, bcv, bct,
+                 vx.astype(np.float64), vy.astype(np.float64), np.zeros(sh), T.astype(np.float64))
+
+
+def extrude_grid2d(g2, dz, depth, depth_var=0.0, baseT=1.0, align=True, dimz=None):
+    """extrude_shape2d of a Grid2D as it stands (after g2.prepare(t))."""
+    return extrude_shape2d(g2.cell, g2.velx, g2.vely, g2.T, g2.dx, g2.dy, dz, depth, depth_var, baseT, align, dimz)
+
+
 def read_config(path):
     """The whitespace `key value` pairs of a reference config file (Config.h:195-245), as a dict of strings."""
     toks = open(path).read().replace("\r", "").split()

@@ -155,6 +155,41 @@ fs3d_status fs3d_update_nodes(fs3d_ctx *ctx, const uint8_t *type, const uint8_t 
 fs3d_status fs3d_update_nodes_dev(fs3d_ctx *ctx, const uint8_t *type, const uint8_t *bc_vel,
                                   const uint8_t *bc_temp, const void *vx, const void *vy,
                                   const void *vz, const void *T, int n_seg_out[3]);
+/* ---- moving geometry from a Shape2D grid: the extrusion on the device -------------
+ * Grid3D::Prepare2D (Grid3D.cpp:608-668) after grid2D->Prepare(t): the 2D grid as it stands, extruded into the Node array by a
+ * kernel.  What changes with time is the 2D grid -- per column (i, j) of the dimx x dimy plane, index i*dimy + j, the cell type
+ * (uint8, one of FS3D_NODE_*) and velx, vely, T (float: Grid2D is float whatever the context's precision) -- 13 bytes per column
+ * where fs3d_update_nodes ships 19 (fp32) or 35 (fp64) bytes per cell.  dz, depth, depth_var, baseT are Grid3D's constructor
+ * arguments: active_dimz = ceil(depth / dz) + 1 cells of the context's dimz are inside the extrusion, the per-column `bottom`
+ * (1 + (int)(depth_var * z * height), Grid3D.cpp:632-636) is computed on the host with the reference's expression, kept in the
+ * context and uploaded again only when (dz, depth, depth_var) change.  The nodes equal those of the reference's loop cell for
+ * cell, byte for byte, including the cells it writes several times (kernels_geom.hip states the rule as a priority list;
+ * cmc_fluid_solver_amd/shape2d.py extrude_shape2d is its numpy twin).
+ * Both entries return FS3D_ERR_INVALID before anything is launched, the context unchanged, for a NULL array, a cell2d value that is
+ * not a node type, active_dimz below 2 or above dimz, and a depth_var that puts the `bottom` of a column that is not NODE_OUT
+ * outside 0 .. dimz - 1 (where the reference's loop writes outside its array); FS3D_ERR_UNSUPPORTED for an x-slab or group member.
+ *
+ * fs3d_extrude_shape2d_dev: the seven SoA node arrays (ncell elements each, on the context's device; real = the context's
+ * precision) are written on the context's stream; returns synchronised.  The context's geometry is not touched (it needs none).
+ * Fast path (4 cells per thread, 16-byte stores): dimz % 4 == 0, the three byte arrays aligned to 4 bytes and the four value
+ * arrays to 16 bytes (fp32 and fp64 alike); any other dimz or alignment runs one cell per thread, same results.
+ *
+ * fs3d_update_nodes_shape2d: fs3d_update_nodes* with the extrusion as the source -- the 2D arrays go through a pinned buffer the
+ * context keeps, the kernel writes type / bc_vel / bc_temp into the staging buffer of fs3d_update_nodes and the four value
+ * fields into the node-value table, and the device path of fs3d_update_nodes_dev rebuilds every table.  Its contract is that of
+ * fs3d_update_nodes* above in every line: after a first fs3d_upload_nodes only, single context only, a refused geometry gets
+ * the upload's status and leaves NO geometry, nothing allocated after the first call, counted in CreateSegments, device time in
+ * fs3d_last_update_device_ms. */
+fs3d_status fs3d_extrude_shape2d_dev(fs3d_ctx *ctx, const uint8_t *cell2d, const float *velx2d, const float *vely2d,
+                                     const float *T2d, double dz, double depth, double depth_var, double baseT,
+                                     uint8_t *type_out, uint8_t *bc_vel_out, uint8_t *bc_temp_out, void *vx_out,
+                                     void *vy_out, void *vz_out, void *T_out);
+fs3d_status fs3d_update_nodes_shape2d(fs3d_ctx *ctx, const uint8_t *cell2d, const float *velx2d, const float *vely2d,
+                                      const float *T2d, double dz, double depth, double depth_var, double baseT,
+                                      int n_seg_out[3]);
+/* The `bottom` table the two entries use, dimx*dimy ints (index i*dimy + j); host only, no context, no GPU.  Test aid: the
+ * table must equal the host loader's, whose (int) truncates a double product. */
+fs3d_status fs3d_shape2d_bottom(int dimx, int dimy, double dz, double depth, double depth_var, int *bottom_out);
 /* Solver3D::ClearOutterCells (Solver3D.cpp:41-44) = TimeLayer3D::Clear(grid, NODE_OUT, 0, 0, 0, (FTYPE)baseT) on one layer:
  * U, V, W := 0 and T := baseT on the NODE_OUT cells of the current geometry, every other cell untouched.  Needed once cells
  * change type: fs3d_get_layer stamps 99999 into the NODE_OUT cells of `next`, and a cell that becomes NODE_IN starts from

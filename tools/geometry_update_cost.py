@@ -9,6 +9,24 @@ the same with a solid block added).  Per case, alternating the two geometries af
   (c) fs3d_update_nodes_dev per call   -- device arrays; host clock, and the device time alone (HIP events inside the library)
   (d) time per step (G 4, L 2, AUTO, fp32) after an upload and after an update of the same geometry, interleaved, with the spread
 Needs the GPU: there is no fallback.  One process, one context per case.
+
+    python tools/geometry_update_cost.py --extrude [--repeats 20] [--out profiles/extrude_update_cost.json] [--kernel-trace CSV]
+
+The extrusion of a Shape2D grid on the device (fs3d_update_nodes_shape2d) against today's path, on heart_us at the shipped resolution
+(96 x 160 x 128) and at grid_dx 0.00027, grid_dz 0.004 (256 x 384 x 256).  Per grid, two geometries of the cycle alternating, interleaved
+in one process, after a warm-up:
+  (e) fs3d_update_nodes per call          -- the host-extruded node arrays, copies included; host clock
+  (f) fs3d_update_nodes_shape2d per call  -- the 2D grid; host clock, and the device time alone
+  (g) the driver, `moving` and `moving --host-extrusion`, alternating: per step the host clock around Grid2D::Prepare, the host
+      ExtrudeShape2D and the update call, and the whole step (fs3d_run --time-geometry)
+  (h) k_geom_extrude alone, against its bytes (19 per cell) and the box's write-only rate (5.4 TB/s, profiles/r3_stream_ubench2.txt),
+      from a second run of the library calls under the profiler.  Three steps:
+        1. python tools/geometry_update_cost.py --extrude                                   -> profiles/extrude_update_cost.json, rows (e)-(g)
+        2. rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o ext -- \
+               python tools/geometry_update_cost.py --extrude --skip-driver                 -> DIR/ext_kernel_trace.csv, DIR/ext_kernel_stats.csv
+           (--skip-driver: no child processes under the profiler; its own rows are printed, and written only where --out names a file)
+        3. python tools/geometry_update_cost.py --extrude --kernel-trace DIR/ext_kernel_trace.csv
+           adds the kernel rows to the file of step 1, which must exist; DIR/ext_kernel_stats.csv is kept as profiles/extrude_kernel_stats.csv
 """
 import argparse
 import ctypes as C
@@ -121,23 +139,182 @@ def measure(name, ga, gb, params, repeats, steps_per_sample=10):
     return out
 
 
+WRITE_ONLY_TBS = 5.4          # profiles/r3_stream_ubench2.txt
+
+
+def heart_config(dx=None, dz=None):
+    """The shipped heart_us config, optionally at another resolution; returns the path of a temporary copy."""
+    import tempfile
+    text = open(os.path.join(ROOT, "tests", "golden", "inputs", "heart_us_2D_config.txt")).read()
+    out = []
+    for ln in text.splitlines():
+        w = ln.split()
+        if dx is not None and w and w[0] in ("grid_dx", "grid_dy"):
+            ln = "%s %r" % (w[0], dx)
+        if dz is not None and w and w[0] == "grid_dz":
+            ln = "%s %r" % (w[0], dz)
+        out.append(ln)
+    f = tempfile.NamedTemporaryFile("w", suffix="_config.txt", delete=False)
+    f.write("\n".join(out) + "\n")
+    f.close()
+    return f.name
+
+
+def measure_extrude(name, cfgf, repeats, driver_steps=12, driver_runs=5, skip_driver=False):
+    import re
+    from cmc_fluid_solver_amd import build as B
+    from cmc_fluid_solver_amd import shape2d
+    dtype = np.float32
+    data = os.path.join(ROOT, "tests", "golden", "inputs", "heart_us_2D_data.txt")
+    cfg = shape2d.Config(cfgf)
+    ex = (cfg.dz, cfg.depth, cfg.depth_var, cfg.baseT)
+    g2s, nodes = [], []
+    cyc = None
+    for frac in (0.0, 0.37):
+        g2 = shape2d.Grid2D(shape2d.parse_shape2d(open(data).read()), cfg.dx, cfg.dy, cfg.baseT, True, 0.0)
+        cyc = g2.cycle_length()
+        g2.prepare(frac * cyc)
+        g2s.append(g2)
+        nodes.append(shape2d.extrude_grid2d(g2, *ex, align=True))
+    s = capi.Solver(nodes[0], capi.fluid_params(dtype, cfg.Re, cfg.Pr, cfg.lam), dtype)
+    s.set_option(capi.OPT_SWEEP_KERNEL, capi.SWEEP_AUTO)
+    host = [arrays(n, dtype) for n in nodes]
+    nseg = (C.c_int * 3)()
+
+    def update(k):
+        s._chk(s.lib.fs3d_update_nodes(s.h, *[capi._p(a) for a in host[k]], nseg))
+
+    def update_2d(k):
+        s.update_nodes_shape2d(g2s[k], *ex)
+
+    def clock(fn, k):
+        t0 = time.perf_counter(); fn(k); s.synchronize()
+        return (time.perf_counter() - t0) * 1e3
+
+    out = {"dims": list(nodes[0].shape), "cells": nodes[0].ncells, "columns": g2s[0].dimx * g2s[0].dimy,
+           "bytes_per_call_update_nodes": 19 * nodes[0].ncells, "bytes_per_call_update_nodes_shape2d": 13 * g2s[0].dimx * g2s[0].dimy}
+    info = {}
+    for fn in (update, update_2d):
+        for k in (1, 0, 1):
+            fn(k)
+        info[fn.__name__] = s.geometry_info()
+    out["tables_equal"] = all(info["update"][k] == info["update_2d"][k] for k in capi.Solver.GEOMETRY_INFO[:13])
+    s.enable_timing(True)
+    t_up, t_2d, d_up, d_2d = [], [], [], []
+    for r in range(repeats):                                 # interleaved: both paths see the same box in the same minute
+        k = r % 2
+        t_up.append(clock(update, k)); d_up.append(s.last_update_device_ms())
+        t_2d.append(clock(update_2d, k)); d_2d.append(s.last_update_device_ms())
+    s.enable_timing(False)
+    out["update_nodes"], out["update_nodes_device_time"] = stats(t_up), stats(d_up)
+    out["update_nodes_shape2d"], out["update_nodes_shape2d_device_time"] = stats(t_2d), stats(d_2d)
+    out["shape2d_over_update_nodes"] = out["update_nodes_shape2d"]["median_ms"] / out["update_nodes"]["median_ms"]
+    out["condition_1_shape2d_call_faster"] = out["update_nodes_shape2d"]["median_ms"] < out["update_nodes"]["median_ms"]
+    s.close()
+    if skip_driver:
+        print(name, json.dumps(out), flush=True)
+        return out
+    # the driver, both words alternating
+    driver = B.build_driver()
+    keys = ("prepare_ms", "host_extrusion_ms", "update_call_ms", "step_ms")
+    runs = {"moving": {k: [] for k in keys}, "moving --host-extrusion": {k: [] for k in keys}}
+    for r in range(driver_runs + 1):
+        for word in runs:
+            o = subprocess.run([driver, data, "/tmp/extrude_cost_%d" % os.getpid(), cfgf, "align", "GPU"] + word.split() + ["--time-geometry", "--steps", str(driver_steps)],
+                               check=True, capture_output=True, text=True, timeout=900).stdout
+            m = re.search(r"Prepare ([0-9.]+), extrusion on the host ([0-9.]+), update call ([0-9.]+); step ([0-9.]+)", o)
+            if r:                                            # the first pair is the warm-up
+                for k, v in zip(keys, m.groups()):
+                    runs[word][k].append(float(v))
+    out["driver"] = {w: {k: stats(v) for k, v in d.items()} for w, d in runs.items()}
+    out["driver"]["steps_per_run"] = driver_steps
+    dm, dh = out["driver"]["moving"]["step_ms"], out["driver"]["moving --host-extrusion"]["step_ms"]
+    out["condition_2_driver_step_faster"] = dm["median_ms"] < dh["median_ms"]
+    out["driver_step_host_over_device"] = dh["median_ms"] / dm["median_ms"]
+    for f in ("/tmp/extrude_cost_%d_res.nc" % os.getpid(),):
+        if os.path.exists(f):
+            os.unlink(f)
+    print(name, json.dumps(out), flush=True)
+    return out
+
+
+def kernel_rows(csv_path, cells_by_grid):
+    """k_geom_extrude dispatches of a rocprofv3 kernel trace, by grid: median duration against 19 bytes per cell."""
+    import csv
+    by = {}
+    for row in csv.DictReader(open(csv_path)):
+        if "k_geom_extrude" not in row.get("Kernel_Name", ""):
+            continue
+        threads = int(row.get("Grid_Size_X") or row.get("Grid_Size") or 0)
+        by.setdefault(threads, []).append((int(row["End_Timestamp"]) - int(row["Start_Timestamp"])) / 1e3)
+    out = {}
+    for threads, us in sorted(by.items()):
+        cells = min(cells_by_grid, key=lambda c: abs(c / 4 - threads))       # one thread per 4 cells, rounded up to workgroups of 256
+        st = {"n": len(us), "median_us": statistics.median(us), "min_us": min(us), "max_us": max(us), "cells": cells, "bytes": 19 * cells}
+        st["TB_per_s"] = st["bytes"] / (st["median_us"] * 1e-6) / 1e12
+        st["fraction_of_write_only_rate"] = st["TB_per_s"] / WRITE_ONLY_TBS
+        out["%s (%d threads)" % (cells_by_grid[cells], threads)] = st
+    return out
+
+
+def main_extrude(a):
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("geometry_update_cost: no GPU (there is no CPU fallback)")
+    out_path = a.out if a.out != DEFAULT_OUT else os.path.join(ROOT, "profiles", "extrude_update_cost.json")
+    if a.skip_driver and a.out == DEFAULT_OUT:
+        out_path = None                                      # the run under the profiler never replaces the complete file
+    if a.kernel_trace and not (os.path.exists(out_path) and "driver" in json.load(open(out_path)).get("heart_us", {})):
+        raise SystemExit("--kernel-trace: %s does not hold the rows of a complete --extrude run (step 1)" % out_path)
+    res = {"device": torch.cuda.get_device_name(0), "commit": a.commit or tree_commit(), "repeats": a.repeats, "precision": "fp32",
+           "note": "host clock around calls that end synchronised, the two paths interleaved; device time from HIP events inside the library; "
+                   "driver: fs3d_run --time-geometry, 12 steps per run, the two words alternating"}
+    if a.kernel_trace:                                       # the kernel rows come from a second run, under the profiler
+        res = json.load(open(out_path))
+    else:
+        shipped, fine = heart_config(), heart_config(dx=0.00027, dz=0.004)
+        res["heart_us"] = measure_extrude("heart_us", shipped, a.repeats, skip_driver=a.skip_driver)
+        res["heart_us_256x384x256"] = measure_extrude("heart_us_256x384x256", fine, a.repeats, driver_runs=3, skip_driver=a.skip_driver)
+        os.unlink(shipped); os.unlink(fine)
+    if a.kernel_trace:
+        res["k_geom_extrude"] = kernel_rows(a.kernel_trace, {res[k]["cells"]: k for k in ("heart_us", "heart_us_256x384x256")})
+        res["k_geom_extrude"]["write_only_rate_TB_per_s"] = WRITE_ONLY_TBS
+    if out_path is None:
+        return
+    os.makedirs(os.path.dirname(out_path), exist_ok=True)
+    with open(out_path, "w") as f:
+        json.dump(res, f, indent=1)
+    print("wrote", out_path)
+
+
+def tree_commit():
+    try:
+        return subprocess.run(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], capture_output=True, text=True).stdout.strip() or None
+    except OSError:
+        return None
+
+
+DEFAULT_OUT = os.path.join(ROOT, "profiles", "geometry_update_cost.json")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=20)
+    ap.add_argument("--extrude", action="store_true", help="the rows of the device extrusion (profiles/extrude_update_cost.json)")
+    ap.add_argument("--skip-driver", action="store_true", help="--extrude: the library calls only (the run under the profiler)")
+    ap.add_argument("--kernel-trace", default=None, help="--extrude: ..._kernel_trace.csv of a rocprofv3 run of this command; adds the kernel rows")
     ap.add_argument("--commit", default=None, help="what to record as the commit (default: git rev-parse of the tree)")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "geometry_update_cost.json"))
+    ap.add_argument("--out", default=DEFAULT_OUT)
     a = ap.parse_args()
+    if a.extrude:
+        return main_extrude(a)
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("geometry_update_cost: no GPU (there is no CPU fallback)")
     torch.cuda.init()                       # torch opens the device before the library does (its tensors are handed to the library)
     import refgolden as RG
     from cmc_fluid_solver_amd import shape2d
-    commit = a.commit
-    try:
-        commit = commit or subprocess.run(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], capture_output=True, text=True).stdout.strip() or None
-    except OSError:
-        commit = None
+    commit = a.commit or tree_commit()
     res = {"device": torch.cuda.get_device_name(0), "commit": commit, "repeats": a.repeats, "precision": "fp32",
            "note": "host clock around calls that end synchronised; device time from HIP events inside the library; step = G 4, L 2, AUTO"}
     fx = RG.Fixture("heart_us", "f32")
