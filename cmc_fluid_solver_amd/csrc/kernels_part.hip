@@ -22,8 +22,8 @@
 //   6 words per cell stay on chip between P and O: 4 in registers, dT/d'_T and c'_T in registers after P (LDS
 //   during P), nothing goes through HBM.  Two workgroups per CU (<= 128 VGPRs, 68 KiB LDS): one streams while the
 //   other solves.
-// Z sweep  (k_sweep_part_z): lanes run along the line itself: lane l owns cells [4l, 4l+4) of ONE line (a 16-byte
-//   piece; a wave-wide access is the whole contiguous line), neighbouring lines are further registers of the same
+// Z sweep  (k_sweep_part_z): lanes run along the line itself: lane l owns the C = 16 / sizeof(R) cells [C l, C l + C) of ONE
+//   line (a 16-byte piece; a wave-wide access is the whole contiguous line), neighbouring lines are further registers of the same
 //   lane.  Chunks of a line = lanes of a wave: the interface system is solved by parallel cyclic reduction across
 //   the lanes (shuffles), no LDS, no barrier, nothing resident but the lines in flight.
 // fp64 (FS3D_OPT_F64_PART = 1, a context that is not a slab; otherwise launch_sweep_part<double> says false and the exact
@@ -33,7 +33,7 @@
 //   chunks up to 64 / 128 cells, 16 lines x 16 chunks (68 KiB of LDS, two workgroups per CU) up to 256.  Lines of 257..512
 //   cells are not taken (152 KiB of LDS at 16 lines, unmeasured): false.  No late start: measured slower in fp64 (X +5 %,
 //   Y +4 % per launch at 256^3, profiles/f64_part_tiles.txt).
-//   Z (k_sweep_part_z64): a 16-byte piece is TWO cells, a lane owns cells [2l, 2l+2): 128 cells per wave, 130..256 per pair of
+//   Z: the same kernel; a 16-byte piece is TWO cells, a lane owns cells [2l, 2l+2): 128 cells per wave, 130..256 per pair of
 //   waves.  dimz even, 8 <= dimz <= 256, dimy >= 4; otherwise false.
 #include <algorithm>
 #include <atomic>
@@ -737,52 +737,58 @@ static bool part_dispatch_xy(fs3d_ctx *c, const SweepParams<R> &p)
 // ------------------------------------------------------------------------------------------------------------
 // Z sweep: lanes along the line
 // ------------------------------------------------------------------------------------------------------------
-// Lane l of a line owns the 4 cells [4l, 4l+4): one 16-byte piece, so a wave-wide access is LI = 64/LPL whole
-// contiguous lines (LPL lanes per line: 64 for 128 < dimz <= 256).  A wave works through LG such rows of lines, one
-// after the other, with the next row's loads in flight; nothing is shared between waves (no LDS, no barrier).
-// Per line:  rows of the 4 cells -> down-/up-sweep over cells 0..2 -> the interface row of cell 3 -> the LPL x LPL
-// interface system by parallel cyclic reduction across the lanes (log2(LPL) steps of shuffles) -> back-substitution
-// -> x to `next`, merged temp to `temp_out`; the temp values needed by the merge are still in registers.
-typedef float pf4 __attribute__((ext_vector_type(4)));
-struct PV4 { float v[4]; };
-template <int AUX = 0>
-__device__ __forceinline__ PV4 pld4(prsrc_t r, unsigned vo, unsigned so)
+// Lane l of a line owns the C = 16 / sizeof(R) cells [C l, C l + C): one 16-byte piece (4 cells in fp32, 2 in fp64), so a
+// wave-wide access is LI = 64/LPL whole contiguous lines (LPL lanes per line: 64 for 32 C < dimz <= 64 C).  A wave works
+// through LG such rows of lines, one after the other, with the next row's loads in flight (in fp64 two rows in flight are
+// four cells per lane: more cells per lane do not fit the registers); nothing is shared between waves (no LDS, no barrier).
+// Per line:  rows of the C cells -> down-/up-sweep over cells 0..C-2 -> the interface row of cell C-1 -> the LPL x LPL
+// interface system by parallel cyclic reduction across the lanes (log2(LPL) steps of shuffles; a cross-lane move carries
+// 32 bits: two moves per double) -> back-substitution -> x to `next`, merged temp to `temp_out`; the temp values needed by
+// the merge are still in registers.
+template <typename R> struct PV { R v[16 / sizeof(R)]; };
+template <typename R, int AUX = 0>
+__device__ __forceinline__ PV<R> pld(prsrc_t r, unsigned vo, unsigned so)
 {
     const pu32x4 q = __builtin_amdgcn_raw_buffer_load_b128(r, vo, so, AUX);
-    PV4 o;
+    PV<R> o;
     __builtin_memcpy(o.v, &q, 16);
     return o;
 }
-template <int AUX = 0>
-__device__ __forceinline__ void pst4(prsrc_t r, unsigned vo, unsigned so, const float (&v)[4])
+template <int AUX = 0, typename R, int C>
+__device__ __forceinline__ void pst(prsrc_t r, unsigned vo, unsigned so, const R (&v)[C])
 {
+    static_assert(sizeof(R) * C == 16, "one 16-byte piece");
     pu32x4 q;
     __builtin_memcpy(&q, v, 16);
     __builtin_amdgcn_raw_buffer_store_b128(q, r, vo, so, AUX);
     // A 16-byte store reads its data registers a few cycles after it issues.  hipcc pads a following VALU write of
     // those registers only for stores without a scalar offset; here (SGPR soffset) it reused them two instructions
     // later and the first dword of the NEXT field's data reached memory (seen on gfx950: sporadic, last lanes of a
-    // line).  The four values stay live until this statement, which supplies the wait states.
+    // line).  The four dwords stay live until this statement, which supplies the wait states -- whatever the element type.
     asm volatile("s_nop 1" : : "v"(q.x), "v"(q.y), "v"(q.z), "v"(q.w));
 }
 
-struct ZLine { PV4 tc[4], cu[4], wim, wip, wjm, wjp; pu32x2 code; float nve[4], nb[4]; };   // wjm/wjp: only where a wave-wide access holds several lines; nb: NW == 2
+// code: the piece's 16-bit code words; wjm/wjp: only where a wave-wide access holds several lines; nb: NW == 2
+template <typename R> struct ZLine { PV<R> tc[4], cu[4], wim, wip, wjm, wjp; unsigned code[8 / sizeof(R)]; R nve[4], nb[4]; };
 
-// NW == 2 (lines of 260..512 cells): a line is held by a PAIR of waves (waves 2q, 2q+1 of the workgroup: cells [0,256) and
-// [256,512)).  Each wave reduces its 64 interface unknowns by itself; the single coupling between the halves (the row of the
-// lower wave's last lane <-> the upper wave's first unknown) is carried through the cyclic reduction as one more right-hand
-// side per matrix, and a 2x2 system per right-hand side joins the halves (two small LDS exchanges + barriers per line).
-template <int LPL, int WPS, int NW = 1>
-__global__ void __launch_bounds__(256, WPS) k_sweep_part_z(SweepParams<float> p, int n_grp, int LG)
+// NW == 2 (lines of 64 C + 2 .. 128 C cells): a line is held by a PAIR of waves (waves 2q, 2q+1 of the workgroup: cells
+// [0, 64 C) and [64 C, 128 C)).  Each wave reduces its 64 interface unknowns by itself; the single coupling between the halves
+// (the row of the lower wave's last lane <-> the upper wave's first unknown) is carried through the cyclic reduction as one
+// more right-hand side per matrix, and a 2x2 system per right-hand side joins the halves (two small LDS exchanges + barriers
+// per line).
+// 2 waves per SIMD: the kernel needs ~200 VGPRs (fp32 at 168: it spills 70 of them and runs 1.5x slower)
+template <typename R, int LPL, int NW = 1>
+__global__ void __launch_bounds__(256, 2) k_sweep_part_z(SweepParams<R> p, int n_grp, int LG)
 {
-    typedef float R;
     static_assert(NW == 1 || (NW == 2 && LPL == 64), "a pair of waves per line: 64 lanes each");
+    constexpr int C = 16 / sizeof(R);                   // cells per lane
+    constexpr unsigned SZ = sizeof(R);
     constexpr int LI = 64 / LPL;                        // lines per wave-wide access
     const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int l = lane % LPL, sub = lane / LPL;
     const int hi = NW == 2 ? (w & 1) : 0;               // upper half of the line
     const int gl = l + 64 * hi;                         // position of this lane's piece along the line
-    __shared__ float zx1[2][8], zx2[2][2][8];           // NW == 2: [pair][..] exchange buffers
+    __shared__ R zx1[2][8], zx2[2][2][8];               // NW == 2: [pair][..] exchange buffers
     int lb = blockIdx.x;
     {
         const int nb = gridDim.x, q = nb >> 3, r = nb & 7, x = lb & 7, slot = lb >> 3;
@@ -796,51 +802,56 @@ __global__ void __launch_bounds__(256, WPS) k_sweep_part_z(SweepParams<float> p,
     bool task_ok = true;
     if (NW == 1) { if (grp >= n_grp) return; }          // whole wave (wave-uniform)
     else { task_ok = grp < n_grp; grp = task_ok ? grp : n_grp - 1; }   // the pairs of a workgroup meet at barriers: a pair past the end runs along, stores nothing
-    const int n = p.dimz;
+    const int n = p.dimz;                               // a multiple of C
     const int j0 = grp * LG * LI;
-    const bool l_ok = 4 * gl < n;
-    const int lc = l_ok ? gl : (n / 4 - 1);
-    const unsigned fsb = (unsigned)(p.fstride * 4ll), nsb = (unsigned)(p.nstride * 4ll);
-    const unsigned rowb = (unsigned)p.dimz * 4u, planeb = (unsigned)(p.plane * 4ll);
+    const bool l_ok = C * gl < n;
+    const int lc = l_ok ? gl : (n / C - 1);
+    const unsigned fsb = (unsigned)(p.fstride * (long long)SZ), nsb = (unsigned)(p.nstride * (long long)SZ);
+    const unsigned rowb = (unsigned)p.dimz * SZ, planeb = (unsigned)(p.plane * (long long)SZ);
     const unsigned lbytes = 4u * fsb;
     const prsrc_t Lcur = __builtin_amdgcn_make_buffer_rsrc((void *)(p.cur_ - p.plane), 0, (int)lbytes, 0x00020000);
     const prsrc_t Ltmp = __builtin_amdgcn_make_buffer_rsrc((void *)(p.temp_ - p.plane), 0, (int)lbytes, 0x00020000);
     const prsrc_t Lnext = __builtin_amdgcn_make_buffer_rsrc((void *)(p.next_ - p.plane), 0, (int)lbytes, 0x00020000);
     const prsrc_t Ltout = __builtin_amdgcn_make_buffer_rsrc((void *)(p.temp_out_ - p.plane), 0, (int)lbytes, 0x00020000);
     const prsrc_t rNode = __builtin_amdgcn_make_buffer_rsrc((void *)p.node_, 0, (int)(4u * nsb), 0x00020000);
-    const prsrc_t rCode = __builtin_amdgcn_make_buffer_rsrc((void *)p.code, 0, (int)(nsb / 2u), 0x00020000);
+    const prsrc_t rCode = __builtin_amdgcn_make_buffer_rsrc((void *)p.code, 0, (int)(nsb / (SZ / 2u)), 0x00020000);   // 2 bytes per cell
 
     const R h2s = p.two_ds[2], h2o = p.two_ds[0], h2l = p.two_ds[1], dtv = p.dt;
     const R ir2s = R(1) / h2s, ir2o = R(1) / h2o, ir2l = R(1) / h2l, irdt = R(1) / dtv;
     const R vis_v = p.vis_v, vis_t = p.vis_t, b_v = p.b_v, b_t = p.b_t;
 
     // byte offset of (plane i, line j, cell 0) inside a layer field (one halo plane first) / inside the node arrays
-    auto line_so = [&](int j) __attribute__((always_inline)) { return (unsigned)(((long long)(i + 1) * p.plane + (long long)j * p.dimz) * 4ll); };
-    auto line_son = [&](int j) __attribute__((always_inline)) { return (unsigned)(((long long)i * p.plane + (long long)j * p.dimz) * 4ll); };
-    const unsigned vo_l = (unsigned)(sub * p.dimz + 4 * lc) * 4u;          // per-lane bytes: own line of the row, own piece
-    // the two lanes that hold the ends of the line (cell 0: START or SKIP; cell n-1: END or SKIP) fetch that cell's node
-    // values with the line's other loads: every line has them, they must not cost a memory round trip of their own
-    const bool is_end = l_ok && (gl == 0 || gl == n / 4 - 1);
-    const int ec = gl == 0 ? 0 : 3;
-    const unsigned vo_e = is_end ? vo_l + 4u * (unsigned)ec : PART_OOB;
-    // NW == 2: the cell across the cut between the two waves (cell 255 for the upper wave's first lane, 256 for the lower
-    // wave's last lane) comes with the line's other loads
+    auto line_so = [&](int j) __attribute__((always_inline)) { return (unsigned)(((long long)(i + 1) * p.plane + (long long)j * p.dimz) * (long long)SZ); };
+    auto line_son = [&](int j) __attribute__((always_inline)) { return (unsigned)(((long long)i * p.plane + (long long)j * p.dimz) * (long long)SZ); };
+    const unsigned vo_l = (unsigned)(sub * p.dimz + C * lc) * SZ;          // per-lane bytes: own line of the row, own piece
+    // the two lanes that hold the ends of the line (cell 0: START or SKIP; cell n-1: END or SKIP; n >= 8: never the same
+    // lane) fetch that cell's node values with the line's other loads: every line has them, they must not cost a memory
+    // round trip of their own
+    const bool is_end = l_ok && (gl == 0 || gl == n / C - 1);
+    const int ec = gl == 0 ? 0 : C - 1;
+    const unsigned vo_e = is_end ? vo_l + SZ * (unsigned)ec : PART_OOB;
+    // NW == 2: the cell across the cut between the two waves (cell 64 C - 1 for the upper wave's first lane, 64 C for the
+    // lower wave's last lane; n >= 64 C + 2: both exist) comes with the line's other loads
     const bool at_cut = NW == 2 && (hi ? l == 0 : l == 63);
-    const unsigned vo_nb = at_cut ? (hi ? 255u * 4u : 256u * 4u) : PART_OOB;
+    const unsigned vo_nb = at_cut ? (hi ? (64u * C - 1u) * SZ : 64u * C * SZ) : PART_OOB;
 
-    auto issue = [&](int jrow, ZLine &L) __attribute__((always_inline)) {
-        // jrow: first line of the row (wave-uniform); this lane's line is jrow + sub, clamped into the plane for the loads
-        const int jr = jrow < p.dimy ? jrow : p.dimy - 1;   // a row past the plane (tail of the last group): valid addresses, nothing stored
+    auto issue = [&](int jrow, ZLine<R> &L) __attribute__((always_inline)) {
+        // jrow: first line of the row (wave-uniform); this lane's line is jrow + sub.  A row that starts past the plane (tail of
+        // the last group) is clamped; the lines jrow + sub past the plane read the next plane / the halo plane behind the last
+        // one: valid addresses (out-of-range ones return 0), nothing stored
+        const int jr = jrow < p.dimy ? jrow : p.dimy - 1;
         const unsigned so = opq_s(line_so(jr));
-        L.tc[2] = pld4(Ltmp, vo_l, so + 2u * fsb);       // W first: the row before needs it as its j+1 neighbour... and the stencils
+        L.tc[2] = pld<R>(Ltmp, vo_l, so + 2u * fsb);     // W first: the row before needs it as its j+1 neighbour... and the stencils
         // (cached: the rows j+-1 and planes i+-1 read the W of this line again as their neighbour; the other temp fields nt)
-        L.tc[0] = pld4<PART_AUX_NT>(Ltmp, vo_l, so); L.tc[1] = pld4<PART_AUX_NT>(Ltmp, vo_l, so + fsb); L.tc[3] = pld4<PART_AUX_NT>(Ltmp, vo_l, so + 3u * fsb);
+        L.tc[0] = pld<R, PART_AUX_NT>(Ltmp, vo_l, so); L.tc[1] = pld<R, PART_AUX_NT>(Ltmp, vo_l, so + fsb); L.tc[3] = pld<R, PART_AUX_NT>(Ltmp, vo_l, so + 3u * fsb);
 #pragma unroll
-        for (int f = 0; f < 4; f++) L.cu[f] = pld4<PART_AUX_NT>(Lcur, vo_l, so + (unsigned)f * fsb);
-        L.wim = pld4(Ltmp, vo_l, so + 2u * fsb - planeb); L.wip = pld4(Ltmp, vo_l, so + 2u * fsb + planeb);
-        if (LI > 1) { L.wjm = pld4(Ltmp, vo_l, so + 2u * fsb - rowb); L.wjp = pld4(Ltmp, vo_l, so + 2u * fsb + rowb); }
+        for (int f = 0; f < 4; f++) L.cu[f] = pld<R, PART_AUX_NT>(Lcur, vo_l, so + (unsigned)f * fsb);
+        L.wim = pld<R>(Ltmp, vo_l, so + 2u * fsb - planeb); L.wip = pld<R>(Ltmp, vo_l, so + 2u * fsb + planeb);
+        if (LI > 1) { L.wjm = pld<R>(Ltmp, vo_l, so + 2u * fsb - rowb); L.wjp = pld<R>(Ltmp, vo_l, so + 2u * fsb + rowb); }
         const unsigned son = opq_s(line_son(jr));
-        L.code = __builtin_amdgcn_raw_buffer_load_b64(rCode, vo_l / 2u, son / 2u, 0);
+        // the piece's C code words: 2 C bytes
+        if constexpr (C == 4) { const pu32x2 cw = __builtin_amdgcn_raw_buffer_load_b64(rCode, vo_l / 2u, son / 2u, 0); L.code[0] = cw.x; L.code[1] = cw.y; }
+        else L.code[0] = __builtin_amdgcn_raw_buffer_load_b32(rCode, vo_l / 4u, son / 4u, 0);
 #pragma unroll
         for (int f = 0; f < 4; f++) L.nve[f] = PBuf<R>::ld(rNode, vo_e, son + (unsigned)f * nsb);     // other lanes: out of range, no memory access
         if (NW == 2) {
@@ -850,38 +861,36 @@ __global__ void __launch_bounds__(256, WPS) k_sweep_part_z(SweepParams<float> p,
     };
 
     // wjm / wjp: W of the lines j-1 / j+1 (LI == 1: the neighbouring rows' registers; else loaded with the line)
-    auto process = [&](int jrow, const ZLine &L, const PV4 &wjm, const PV4 &wjp) __attribute__((always_inline)) {
+    auto process = [&](int jrow, const ZLine<R> &L, const PV<R> &wjm, const PV<R> &wjp) __attribute__((always_inline)) {
         const int j = jrow + sub;
         const bool st_ok = l_ok && j < p.dimy && task_ok; // lines past the plane compute on whatever was loaded, nothing is stored
         const unsigned so = opq_s(line_so(jrow)), son = opq_s(line_son(jrow));
         // ---- codes
-        int code4[4]; bool isin[4], seg[4], inter[4];
-        bool all_int = true;
+        int code4[C]; bool isin[C], seg[C], inter[C];
 #pragma unroll
-        for (int c = 0; c < 4; c++) {
-            int cw = (int)((c < 2 ? L.code.x : L.code.y) >> (16 * (c & 1))) & 0xFFFF;
+        for (int c = 0; c < C; c++) {
+            int cw = (int)(L.code[c / 2] >> (16 * (c & 1))) & 0xFFFF;
             cw = l_ok ? cw : 0;
             code4[c] = (cw >> 8) & 0xF;
             isin[c] = ((cw >> CODE_TYPE_SHIFT) & 3) == FS3D_NODE_IN && l_ok;
             inter[c] = (code4[c] & 3) == ROW_INTERIOR;
             seg[c] = (code4[c] & 3) != ROW_SKIP;
-            all_int = all_int && inter[c];
         }
         // ---- rows: neighbours along the line from the lanes next door
-        R tm1[4], tp4[4];                                 // cell 4l-1 and cell 4l+4 of U, V, W, T
+        R tm1[4], tpC[4];                                 // cell C l - 1 and cell C l + C of U, V, W, T
 #pragma unroll
         for (int f = 0; f < 4; f++) {
-            tm1[f] = __shfl_up(L.tc[f].v[3], 1, LPL); tp4[f] = __shfl_down(L.tc[f].v[0], 1, LPL);
-            if (NW == 2) { tm1[f] = (at_cut && hi) ? L.nb[f] : tm1[f]; tp4[f] = (at_cut && !hi) ? L.nb[f] : tp4[f]; }
+            tm1[f] = __shfl_up(L.tc[f].v[C - 1], 1, LPL); tpC[f] = __shfl_down(L.tc[f].v[0], 1, LPL);
+            if (NW == 2) { tm1[f] = (at_cut && hi) ? L.nb[f] : tm1[f]; tpC[f] = (at_cut && !hi) ? L.nb[f] : tpC[f]; }
         }
-        R q[4], d[4][4];                                  // d[f][c]
+        R q[C], d[4][C];                                  // d[f][c]
 #pragma unroll
-        for (int c = 0; c < 4; c++) {
+        for (int c = 0; c < C; c++) {
             R g[4];
 #pragma unroll
             for (int f = 0; f < 4; f++) {
-                const R lo = c == 0 ? tm1[f] : L.tc[f].v[c == 0 ? 0 : c - 1], hi = c == 3 ? tp4[f] : L.tc[f].v[c == 3 ? 3 : c + 1];
-                g[f] = pdivc(hi - lo, h2s, ir2s);         // d/dz of U, V, W, T
+                const R lo = c == 0 ? tm1[f] : L.tc[f].v[c == 0 ? 0 : c - 1], up = c == C - 1 ? tpC[f] : L.tc[f].v[c == C - 1 ? C - 1 : c + 1];
+                g[f] = pdivc(up - lo, h2s, ir2s);         // d/dz of U, V, W, T
             }
             const R x1 = pdivc(L.wip.v[c] - L.wim.v[c], h2o, ir2o), x2 = pdivc(wjp.v[c] - wjm.v[c], h2l, ir2l);   // dW/dx, dW/dy
             const R diss = (((g[0] * g[0] + g[1] * g[1]) + R(2) * g[2] * g[2]) + g[0] * x1) + g[1] * x2;   // DissFuncZ (TimeLayer3D.h:578-588)
@@ -890,26 +899,26 @@ __global__ void __launch_bounds__(256, WPS) k_sweep_part_z(SweepParams<float> p,
             d[2][c] = pfma(-p.v_T, g[3], pdivc(L.cu[2].v[c] * R(3), dtv, irdt));
             d[3][c] = pfma(p.t_phi, diss, pdivc(L.cu[3].v[c] * R(3), dtv, irdt));
         }
-        PMat<R> mv[4], mt[4];
+        PMat<R> mv[C], mt[C];
 #pragma unroll
-        for (int c = 0; c < 4; c++) part_coefs<R, false>(q[c], 0, vis_v, b_v, vis_t, b_t, mv[c], mt[c]);
+        for (int c = 0; c < C; c++) part_coefs<R, false>(q[c], 0, vis_v, b_v, vis_t, b_t, mv[c], mt[c]);
         {
             // Rows that are not INTERIOR: the ends of every line (node values came with the line) and, rarely, obstacles /
             // lanes past the line (their node values are fetched here).  Per cell slot c a wave-uniform test: in a box only
-            // c = 0 (first lane) and c = 3 (last lane) take the selects.
+            // c = 0 (first lane) and c = C - 1 (last lane) take the selects.
             bool slow = false;
 #pragma unroll
-            for (int c = 0; c < 4; c++) {
+            for (int c = 0; c < C; c++) {
                 const int kind = code4[c] & 3;
                 slow = slow || ((kind == ROW_START || kind == ROW_END) && !(is_end && c == ec));
             }
-            PV4 nv[4];
+            PV<R> nv[4];
             if (__any(slow)) {
 #pragma unroll
-                for (int f = 0; f < 4; f++) nv[f] = pld4(rNode, vo_l, son + (unsigned)f * nsb);
+                for (int f = 0; f < 4; f++) nv[f] = pld<R>(rNode, vo_l, son + (unsigned)f * nsb);
             }
 #pragma unroll
-            for (int c = 0; c < 4; c++) {
+            for (int c = 0; c < C; c++) {
                 if (__any(!inter[c])) {
                     const int kind = code4[c] & 3;
                     const bool ns_v = kind != ROW_SKIP && !(code4[c] & ROW_VELFREE), ns_t = kind != ROW_SKIP && !(code4[c] & ROW_TEMPFREE);
@@ -921,44 +930,52 @@ __global__ void __launch_bounds__(256, WPS) k_sweep_part_z(SweepParams<float> p,
                 }
             }
         }
-        // ---- chunk elimination: down-sweep over cells 0..2 (kept for the back-substitution), up-sweep 2..0
-        R cpv[3], lpv[3], cpt[3], lpt[3], dpd[3][4];
+        // ---- chunk elimination: down-sweep over cells 0..C-2 (kept for the back-substitution):  x[c] = dpd[c] - lp[c] X_left - cp[c] x[c+1]
+        R cpv[C - 1], lpv[C - 1], cpt[C - 1], lpt[C - 1], dpd[C - 1][4];
         {
             R cv = R(0), lv = R(-1), ct = R(0), lt = R(-1), d3[3] = {R(0), R(0), R(0)}, d1[1] = {R(0)};
 #pragma unroll
-            for (int c = 0; c < 3; c++) {
+            for (int c = 0; c < C - 1; c++) {
                 { const R dd3[3] = {d[0][c], d[1][c], d[2][c]}, dd1[1] = {d[3][c]}; part_step_vt<R, true>(mv[c].a, mv[c].b, mv[c].c, mt[c].a, mt[c].b, mt[c].c, cv, ct, lv, lt, d3, d1, dd3, dd1); }
                 cpv[c] = cv; lpv[c] = lv; cpt[c] = ct; lpt[c] = lt;
                 dpd[c][0] = d3[0]; dpd[c][1] = d3[1]; dpd[c][2] = d3[2]; dpd[c][3] = d1[0];
             }
         }
+        // up-sweep C-2..0:  x[0] = ep - ap X_left - up X
         R apv = R(0), upv = R(-1), apt = R(0), upt = R(-1), ep3[3] = {R(0), R(0), R(0)}, ep1[1] = {R(0)};
+        if constexpr (C == 2) {
+            // one cell before the interface cell: the down-sweep's single step is the up-sweep too (x[0] = d/b - (a/b) X_left - (c/b) X)
+            apv = lpv[0]; upv = cpv[0]; apt = lpt[0]; upt = cpt[0];
+            ep3[0] = dpd[0][0]; ep3[1] = dpd[0][1]; ep3[2] = dpd[0][2]; ep1[0] = dpd[0][3];
+        } else {
 #pragma unroll
-        for (int c = 2; c >= 0; c--) {
-            { const R dd3[3] = {d[0][c], d[1][c], d[2][c]}, dd1[1] = {d[3][c]}; part_step_vt<R, true>(mv[c].c, mv[c].b, mv[c].a, mt[c].c, mt[c].b, mt[c].a, apv, apt, upv, upt, ep3, ep1, dd3, dd1); }
+            for (int c = C - 2; c >= 0; c--) {
+                { const R dd3[3] = {d[0][c], d[1][c], d[2][c]}, dd1[1] = {d[3][c]}; part_step_vt<R, true>(mv[c].c, mv[c].b, mv[c].a, mt[c].c, mt[c].b, mt[c].a, apv, apt, upv, upt, ep3, ep1, dd3, dd1); }
+            }
         }
-        // ---- interface row (cell 3) with x[2] eliminated and x_first of the next lane substituted; normalised
+        // ---- interface row (cell C-1) with x[C-2] eliminated and x_first of the next lane substituted; normalised
         R av, cv_, at, ct_, dd[4];
         {
+            constexpr int ci = C - 1, cb = C - 2;
             R nvf = __shfl_down(apv, 1, LPL), nwf = __shfl_down(upv, 1, LPL), ntf = __shfl_down(apt, 1, LPL), nuf = __shfl_down(upt, 1, LPL);
             R ng0 = __shfl_down(ep3[0], 1, LPL), ng1 = __shfl_down(ep3[1], 1, LPL), ng2 = __shfl_down(ep3[2], 1, LPL), ng3 = __shfl_down(ep1[0], 1, LPL);
             if (NW == 2) {
                 // the lower wave's last lane takes the up-sweep of the upper wave's first lane
-                float *const b = zx1[w >> 1];
+                R *const b = zx1[w >> 1];
                 if (hi && l == 0) { b[0] = apv; b[1] = upv; b[2] = apt; b[3] = upt; b[4] = ep3[0]; b[5] = ep3[1]; b[6] = ep3[2]; b[7] = ep1[0]; }
                 __syncthreads();
                 if (at_cut && !hi) { nvf = b[0]; nwf = b[1]; ntf = b[2]; nuf = b[3]; ng0 = b[4]; ng1 = b[5]; ng2 = b[6]; ng3 = b[7]; }
             }
             const bool last = NW == 2 ? (hi && l == 63) : l == LPL - 1;   // no lane behind: its first cell does not exist (the row has c = 0 anyway)
-            const R clv = last ? R(0) : mv[3].c, clt = last ? R(0) : mt[3].c;
-            const R lov = -mv[3].a * lpv[2], div = pfma(-clv, nvf, pfma(-mv[3].a, cpv[2], mv[3].b)), upv_ = -clv * nwf;
-            const R lot = -mt[3].a * lpt[2], dit = pfma(-clt, ntf, pfma(-mt[3].a, cpt[2], mt[3].b)), upt_ = -clt * nuf;
+            const R clv = last ? R(0) : mv[ci].c, clt = last ? R(0) : mt[ci].c;
+            const R lov = -mv[ci].a * lpv[cb], div = pfma(-clv, nvf, pfma(-mv[ci].a, cpv[cb], mv[ci].b)), upv_ = -clv * nwf;
+            const R lot = -mt[ci].a * lpt[cb], dit = pfma(-clt, ntf, pfma(-mt[ci].a, cpt[cb], mt[ci].b)), upt_ = -clt * nuf;
             const R rv = prcp(div), rt = prcp(dit);
             av = pquot(lov, div, rv); cv_ = pquot(upv_, div, rv); at = pquot(lot, dit, rt); ct_ = pquot(upt_, dit, rt);
-            dd[0] = pquot(pfma(-clv, ng0, pfma(-mv[3].a, dpd[2][0], d[0][3])), div, rv);
-            dd[1] = pquot(pfma(-clv, ng1, pfma(-mv[3].a, dpd[2][1], d[1][3])), div, rv);
-            dd[2] = pquot(pfma(-clv, ng2, pfma(-mv[3].a, dpd[2][2], d[2][3])), div, rv);
-            dd[3] = pquot(pfma(-clt, ng3, pfma(-mt[3].a, dpd[2][3], d[3][3])), dit, rt);
+            dd[0] = pquot(pfma(-clv, ng0, pfma(-mv[ci].a, dpd[cb][0], d[0][ci])), div, rv);
+            dd[1] = pquot(pfma(-clv, ng1, pfma(-mv[ci].a, dpd[cb][1], d[1][ci])), div, rv);
+            dd[2] = pquot(pfma(-clv, ng2, pfma(-mv[ci].a, dpd[cb][2], d[2][ci])), div, rv);
+            dd[3] = pquot(pfma(-clt, ng3, pfma(-mt[ci].a, dpd[cb][3], d[3][ci])), dit, rt);
         }
         // NW == 2: the coupling across the cut leaves the wave's system and becomes a right-hand side of its own
         // (x_l = X_l - Z * E_l with Z the unknown on the other side of the cut)
@@ -967,21 +984,22 @@ __global__ void __launch_bounds__(256, WPS) k_sweep_part_z(SweepParams<float> p,
             if (at_cut && !hi) { ev = cv_; et = ct_; cv_ = R(0); ct_ = R(0); }
             if (at_cut && hi) { ev = av; et = at; av = R(0); at = R(0); }
         }
-        // ---- parallel cyclic reduction over the LPL lanes of the line.  (r3) on 2-vectors: (velocity, temperature) matrix words,
-        // right-hand sides U/V against the velocity matrix and W/T against (velocity, temperature): the same operations, component for
-        // component, as one scalar reduction per matrix, half the VALU issue slots
-        {
-            pf2 A = {av, at}, C = {cv_, ct_}, D01 = {dd[0], dd[1]}, D23 = {dd[2], dd[3]}, E = {ev, et};
+        // ---- parallel cyclic reduction over the LPL lanes of the line.  Per precision: fp32 has packed arithmetic, fp64 has not
+        if constexpr (sizeof(R) == 4) {
+            // (r3) on 2-vectors: (velocity, temperature) matrix words, right-hand sides U/V against the velocity matrix and W/T against
+            // (velocity, temperature): the same operations, component for component, as one scalar reduction per matrix, half the
+            // VALU issue slots
+            pf2 A2 = {av, at}, C2 = {cv_, ct_}, D01 = {dd[0], dd[1]}, D23 = {dd[2], dd[3]}, E = {ev, et};
             auto sh_up = [&](pf2 v, int s) __attribute__((always_inline)) { return pf2{__shfl_up(v.x, s, LPL), __shfl_up(v.y, s, LPL)}; };
             auto sh_dn = [&](pf2 v, int s) __attribute__((always_inline)) { return pf2{__shfl_down(v.x, s, LPL), __shfl_down(v.y, s, LPL)}; };
 #pragma unroll
             for (int s = 1; s < LPL; s <<= 1) {
-                const pf2 Am = sh_up(A, s), Cm = sh_up(C, s), Ap = sh_dn(A, s), Cp = sh_dn(C, s);
+                const pf2 Am = sh_up(A2, s), Cm = sh_up(C2, s), Ap = sh_dn(A2, s), Cp = sh_dn(C2, s);
                 const pf2 Dm01 = sh_up(D01, s), Dm23 = sh_up(D23, s), Dq01 = sh_dn(D01, s), Dq23 = sh_dn(D23, s);
                 // lanes without a partner at this distance: their a (c) is zero by now, the partner values must only be finite
                 const bool has_m = l >= s, has_p = l + s < LPL;
                 const pf2 zero = {0.0f, 0.0f}, one = {1.0f, 1.0f};
-                const pf2 a = has_m ? A : zero, c = has_p ? C : zero;
+                const pf2 a = has_m ? A2 : zero, c = has_p ? C2 : zero;
                 const pf2 dn = pk_fma(-a, Cm, pk_fma(-c, Ap, one));
                 pf2 r = {__builtin_amdgcn_rcpf(dn.x), __builtin_amdgcn_rcpf(dn.y)};
                 r = pk_fma(pk_fma(-dn, r, one), r, r);
@@ -992,18 +1010,45 @@ __global__ void __launch_bounds__(256, WPS) k_sweep_part_z(SweepParams<float> p,
                     const pf2 Em = sh_up(E, s), Eq = sh_dn(E, s);
                     E = pk_quot(pk_fma(-a, Em, pk_fma(-c, Eq, E)), dn, r);
                 }
-                A = pk_quot(-a * Am, dn, r); C = pk_quot(-c * Cp, dn, r);
+                A2 = pk_quot(-a * Am, dn, r); C2 = pk_quot(-c * Cp, dn, r);
             }
-            av = A.x; at = A.y; cv_ = C.x; ct_ = C.y; dd[0] = D01.x; dd[1] = D01.y; dd[2] = D23.x; dd[3] = D23.y; ev = E.x; et = E.y;
+            av = A2.x; at = A2.y; cv_ = C2.x; ct_ = C2.y; dd[0] = D01.x; dd[1] = D01.y; dd[2] = D23.x; dd[3] = D23.y; ev = E.x; et = E.y;
+        } else {
+            // one scalar reduction per matrix
+#pragma unroll
+            for (int s = 1; s < LPL; s <<= 1) {
+                // lanes without a partner at this distance: their a (c) is zero by now, the partner values must only be finite
+                const bool has_m = l >= s, has_p = l + s < LPL;
+                const R a_v = has_m ? av : R(0), c_v = has_p ? cv_ : R(0), a_t = has_m ? at : R(0), c_t = has_p ? ct_ : R(0);
+                const R dnv = pfma(-a_v, __shfl_up(cv_, s, LPL), pfma(-c_v, __shfl_down(av, s, LPL), R(1)));
+                const R dnt = pfma(-a_t, __shfl_up(ct_, s, LPL), pfma(-c_t, __shfl_down(at, s, LPL), R(1)));
+                const R rv = prcp(dnv), rt = prcp(dnt);
+                R nd[4];
+#pragma unroll
+                for (int k = 0; k < 4; k++) {
+                    const R a = k < 3 ? a_v : a_t, c = k < 3 ? c_v : c_t;
+                    nd[k] = pquot(pfma(-a, __shfl_up(dd[k], s, LPL), pfma(-c, __shfl_down(dd[k], s, LPL), dd[k])), k < 3 ? dnv : dnt, k < 3 ? rv : rt);
+                }
+                if (NW == 2) {
+                    const R nev = pquot(pfma(-a_v, __shfl_up(ev, s, LPL), pfma(-c_v, __shfl_down(ev, s, LPL), ev)), dnv, rv);
+                    const R net = pquot(pfma(-a_t, __shfl_up(et, s, LPL), pfma(-c_t, __shfl_down(et, s, LPL), et)), dnt, rt);
+                    ev = nev; et = net;
+                }
+                const R nav = pquot(-a_v * __shfl_up(av, s, LPL), dnv, rv), ncv = pquot(-c_v * __shfl_down(cv_, s, LPL), dnv, rv);
+                const R nat = pquot(-a_t * __shfl_up(at, s, LPL), dnt, rt), nct = pquot(-c_t * __shfl_down(ct_, s, LPL), dnt, rt);
+                av = nav; cv_ = ncv; at = nat; ct_ = nct;
+#pragma unroll
+                for (int k = 0; k < 4; k++) dd[k] = nd[k];
         }
-        // ---- back-substitution: x[3] = X, x[c] = d'[c] - l[c] X_left - c'[c] x[c+1]
-        R x[4][4];                                        // x[f][c]
+        }
+        // ---- back-substitution: x[C-1] = X, x[c] = d'[c] - l[c] X_left - c'[c] x[c+1]
+        R x[4][C];                                        // x[f][c]
         {
             R xcut[4] = {R(0), R(0), R(0), R(0)};         // NW == 2, upper wave: the lower wave's last unknown
             if (NW == 2) {
                 // join the halves: X = Xd - Y0 E_lo, Y = Yd - X63 E_hi  ->  per right-hand side a 2x2 system in (X63, Y0)
-                float *const bl = zx2[w >> 1][0], *const bh = zx2[w >> 1][1];
-                if (at_cut) { float *const b = hi ? bh : bl; b[0] = dd[0]; b[1] = dd[1]; b[2] = dd[2]; b[3] = dd[3]; b[4] = ev; b[5] = et; }
+                R *const bl = zx2[w >> 1][0], *const bh = zx2[w >> 1][1];
+                if (at_cut) { R *const b = hi ? bh : bl; b[0] = dd[0]; b[1] = dd[1]; b[2] = dd[2]; b[3] = dd[3]; b[4] = ev; b[5] = et; }
                 __syncthreads();
                 const R elv = bl[4], elt = bl[5], ehv = bh[4], eht = bh[5];
                 const R rdv = prcp(pfma(-elv, ehv, R(1))), rdt = prcp(pfma(-elt, eht, R(1)));
@@ -1018,9 +1063,9 @@ __global__ void __launch_bounds__(256, WPS) k_sweep_part_z(SweepParams<float> p,
             }
             R xl[4];
 #pragma unroll
-            for (int k = 0; k < 4; k++) { xl[k] = __shfl_up(dd[k], 1, LPL); xl[k] = l == 0 ? (NW == 2 && hi ? xcut[k] : R(0)) : xl[k]; x[k][3] = dd[k]; }
+            for (int k = 0; k < 4; k++) { xl[k] = __shfl_up(dd[k], 1, LPL); xl[k] = l == 0 ? (NW == 2 && hi ? xcut[k] : R(0)) : xl[k]; x[k][C - 1] = dd[k]; }
 #pragma unroll
-            for (int c = 2; c >= 0; c--) {
+            for (int c = C - 2; c >= 0; c--) {
 #pragma unroll
                 for (int k = 0; k < 3; k++) x[k][c] = pfma(-cpv[c], x[k][c + 1], pfma(-lpv[c], xl[k], dpd[c][k]));
                 x[3][c] = pfma(-cpt[c], x[3][c + 1], pfma(-lpt[c], xl[3], dpd[c][3]));
@@ -1028,42 +1073,41 @@ __global__ void __launch_bounds__(256, WPS) k_sweep_part_z(SweepParams<float> p,
         }
         // ---- scatter + merge
         const unsigned vo_st = st_ok ? vo_l : PART_OOB;
-        const bool all_seg = seg[0] && seg[1] && seg[2] && seg[3];
+        bool all_seg = true, stale = false;
+#pragma unroll
+        for (int c = 0; c < C; c++) { all_seg = all_seg && seg[c]; stale = stale || (isin[c] && !seg[c]); }
         if (p.store_next) {
             if (__all(all_seg || !st_ok)) {
 #pragma unroll
-                for (int f = 0; f < 4; f++) pst4<PART_AUX_NT>(Lnext, vo_st, so + (unsigned)f * fsb, x[f]);
+                for (int f = 0; f < 4; f++) pst<PART_AUX_NT>(Lnext, vo_st, so + (unsigned)f * fsb, x[f]);
             } else {
 #pragma unroll
                 for (int f = 0; f < 4; f++)
 #pragma unroll
-                    for (int c = 0; c < 4; c++)
-                        PBuf<R>::st(Lnext, seg[c] ? vo_st : PART_OOB, so + (unsigned)f * fsb + 4u * (unsigned)c, x[f][c]);
+                    for (int c = 0; c < C; c++)
+                        PBuf<R>::st(Lnext, seg[c] ? vo_st : PART_OOB, so + (unsigned)f * fsb + SZ * (unsigned)c, x[f][c]);
             }
         }
         if (p.merge) {
-            bool stale = false;
-#pragma unroll
-            for (int c = 0; c < 4; c++) stale = stale || (isin[c] && !seg[c]);
             if (__any(stale)) {
                 // NODE_IN cell outside every segment: the reference merges the stale `next` value (Grid3D.cpp:87-117)
 #pragma unroll
                 for (int f = 0; f < 4; f++) {
-                    const PV4 sv = pld4(Lnext, vo_l, so + (unsigned)f * fsb);
+                    const PV<R> sv = pld<R>(Lnext, vo_l, so + (unsigned)f * fsb);
 #pragma unroll
-                    for (int c = 0; c < 4; c++) x[f][c] = (isin[c] && !seg[c]) ? sv.v[c] : x[f][c];
+                    for (int c = 0; c < C; c++) x[f][c] = (isin[c] && !seg[c]) ? sv.v[c] : x[f][c];
                 }
             }
 #pragma unroll
             for (int f = 0; f < 4; f++) {
-                R o4[4];
+                R o[C];
 #pragma unroll
-                for (int c = 0; c < 4; c++) {
+                for (int c = 0; c < C; c++) {
                     R mvv = (L.tc[f].v[c] + x[f][c]) * R(0.5);       // MergeFieldTo (TimeLayer3D.h:415-436)
                     if (p.merge == 2) mvv = (mvv + x[f][c]) * R(0.5);
-                    o4[c] = isin[c] ? mvv : L.tc[f].v[c];
+                    o[c] = isin[c] ? mvv : L.tc[f].v[c];
                 }
-                pst4<PART_AUX_NT>(Ltout, vo_st, so + (unsigned)f * fsb, o4);
+                pst<PART_AUX_NT>(Ltout, vo_st, so + (unsigned)f * fsb, o);
             }
         }
     };
@@ -1071,12 +1115,12 @@ __global__ void __launch_bounds__(256, WPS) k_sweep_part_z(SweepParams<float> p,
     // ---- the rows of this wave's group, two per trip, the next row's loads in flight
     // LI == 1: W of the lines j-1 / j+1 are the previous / next row's registers; the lines just outside the group come
     // from two extra loads.  (The next row's W is its first load: it has arrived long before the rest.)
-    ZLine La, Lb;
-    PV4 wprev, wedge;
+    ZLine<R> La, Lb;
+    PV<R> wprev, wedge;
     if (LI == 1) {
-        wprev = pld4(Ltmp, vo_l, opq_s(line_so(j0)) + 2u * fsb - rowb);
+        wprev = pld<R>(Ltmp, vo_l, opq_s(line_so(j0)) + 2u * fsb - rowb);
         const int jl = j0 + LG < p.dimy ? j0 + LG : p.dimy - 1;
-        wedge = pld4(Ltmp, vo_l, opq_s(line_so(jl)) + 2u * fsb);
+        wedge = pld<R>(Ltmp, vo_l, opq_s(line_so(jl)) + 2u * fsb);
     }
     issue(j0, La);
     for (int r = 0; r < LG; r += 2) {
@@ -1084,16 +1128,16 @@ __global__ void __launch_bounds__(256, WPS) k_sweep_part_z(SweepParams<float> p,
         if (r + 1 < LG) issue(jb, Lb);
         __builtin_amdgcn_sched_barrier(0);
         if (LI == 1) {
-            PV4 wn;
+            PV<R> wn;
 #pragma unroll
-            for (int c = 0; c < 4; c++) wn.v[c] = wedge.v[c];
+            for (int c = 0; c < C; c++) wn.v[c] = wedge.v[c];
             if (r + 1 < LG) {
 #pragma unroll
-                for (int c = 0; c < 4; c++) wn.v[c] = Lb.tc[2].v[c];
+                for (int c = 0; c < C; c++) wn.v[c] = Lb.tc[2].v[c];
             }
             process(ja, La, wprev, wn);
 #pragma unroll
-            for (int c = 0; c < 4; c++) wprev.v[c] = La.tc[2].v[c];
+            for (int c = 0; c < C; c++) wprev.v[c] = La.tc[2].v[c];
         }
         else process(ja, La, La.wjm, La.wjp);
         __builtin_amdgcn_sched_barrier(0);
@@ -1101,16 +1145,16 @@ __global__ void __launch_bounds__(256, WPS) k_sweep_part_z(SweepParams<float> p,
             if (r + 2 < LG) issue(jc, La);
             __builtin_amdgcn_sched_barrier(0);
             if (LI == 1) {
-                PV4 wn;
+                PV<R> wn;
 #pragma unroll
-                for (int c = 0; c < 4; c++) wn.v[c] = wedge.v[c];
+                for (int c = 0; c < C; c++) wn.v[c] = wedge.v[c];
                 if (r + 2 < LG) {
 #pragma unroll
-                    for (int c = 0; c < 4; c++) wn.v[c] = La.tc[2].v[c];
+                    for (int c = 0; c < C; c++) wn.v[c] = La.tc[2].v[c];
                 }
                 process(jb, Lb, wprev, wn);
 #pragma unroll
-                for (int c = 0; c < 4; c++) wprev.v[c] = Lb.tc[2].v[c];
+                for (int c = 0; c < C; c++) wprev.v[c] = Lb.tc[2].v[c];
             }
             else process(jb, Lb, Lb.wjm, Lb.wjp);
             __builtin_amdgcn_sched_barrier(0);
@@ -1118,8 +1162,8 @@ __global__ void __launch_bounds__(256, WPS) k_sweep_part_z(SweepParams<float> p,
     }
 }
 
-template <int LPL, int NW = 1>
-static bool part_launch_z(fs3d_ctx *c, const SweepParams<float> &p)
+template <typename R, int LPL, int NW = 1>
+static bool part_launch_z(fs3d_ctx *c, const SweepParams<R> &p)
 {
     constexpr int LI = 64 / LPL;
     const int rows = (p.dimy + LI - 1) / LI;              // rows of LI lines per plane
@@ -1130,390 +1174,23 @@ static bool part_launch_z(fs3d_ctx *c, const SweepParams<float> &p)
     while (LG > 1 && (long long)((rows + LG - 1) / LG) * npl < 4096) LG >>= 1;
     if (LG > rows) LG = rows;
     const int n_grp = (rows + LG - 1) / LG;
-    const long long tasks = (long long)n_grp * (p.o_count ? p.o_count : p.dimx);
-    // 2 waves per SIMD: the kernel needs ~200 VGPRs (at 168 it spills 70 of them and runs 1.5x slower)
-    if (NW == 2) hipLaunchKernelGGL((k_sweep_part_z<LPL, 2, NW>), dim3((unsigned)((tasks + 1) / 2)), dim3(256), 0, c->stream, p, n_grp, LG);
-    else hipLaunchKernelGGL((k_sweep_part_z<LPL, 2, NW>), dim3((unsigned)((tasks + 3) / 4)), dim3(256), 0, c->stream, p, n_grp, LG);
-    return true;
-}
-
-static bool part_dispatch_z(fs3d_ctx *c, const SweepParams<float> &p)
-{
-    const int n = p.dimz;
-    if (n % 4 != 0 || n < 8) return false;                // whole 16-byte pieces
-    if (p.dimy < 4) return false;
-    if (n <= 64) return part_launch_z<16>(c, p);
-    if (n <= 128) return part_launch_z<32>(c, p);
-    if (n <= 256) return part_launch_z<64>(c, p);
-    if (n <= 512) return part_launch_z<64, 2>(c, p);       // a pair of waves per line
-    return false;
-}
-// ------------------------------------------------------------------------------------------------------------
-// Z sweep, fp64: lanes along the line, TWO cells per lane
-// ------------------------------------------------------------------------------------------------------------
-// The scheme of k_sweep_part_z with a 16-byte piece of two doubles: lane l owns cells [2l, 2l+2) (four fp64 cells per lane
-// with two rows in flight: ~210 VGPRs of loaded values alone).  A wave holds 128 cells; LPL = 16 / 32 / 64 lanes per line for dimz <= 32 /
-// 64 / 128, a pair of waves (NW == 2, the join of k_sweep_part_z) for 130..256.  A chunk of two cells has ONE cell before its
-// interface cell: the down-sweep and the up-sweep over it are the same single step (x[0] = d/b - (a/b) X_left - (c/b) X), so
-// one step serves both.  Cross-lane moves carry 32 bits: every shuffle of a value is two moves; no packed arithmetic.
-struct PV2 { double v[2]; };
-template <int AUX = 0>
-__device__ __forceinline__ PV2 pld2(prsrc_t r, unsigned vo, unsigned so)
-{
-    const pu32x4 q = __builtin_amdgcn_raw_buffer_load_b128(r, vo, so, AUX);
-    PV2 o;
-    __builtin_memcpy(o.v, &q, 16);
-    return o;
-}
-template <int AUX = 0>
-__device__ __forceinline__ void pst2(prsrc_t r, unsigned vo, unsigned so, const double (&v)[2])
-{
-    pu32x4 q;
-    __builtin_memcpy(&q, v, 16);
-    __builtin_amdgcn_raw_buffer_store_b128(q, r, vo, so, AUX);
-    // the wait states of pst4: the hazard is the 16-byte store with a scalar offset, whatever the element type
-    asm volatile("s_nop 1" : : "v"(q.x), "v"(q.y), "v"(q.z), "v"(q.w));
-}
-
-struct ZLine64 { PV2 tc[4], cu[4], wim, wip, wjm, wjp; unsigned code; double nve[4], nb[4]; };   // wjm/wjp: LI > 1; nb: NW == 2
-
-template <int LPL, int NW = 1>
-__global__ void __launch_bounds__(256, 2) k_sweep_part_z64(SweepParams<double> p, int n_grp, int LG)
-{
-    typedef double R;
-    static_assert(NW == 1 || (NW == 2 && LPL == 64), "a pair of waves per line: 64 lanes each");
-    constexpr int LI = 64 / LPL;                        // lines per wave-wide access
-    const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int l = lane % LPL, sub = lane / LPL;
-    const int hi = NW == 2 ? (w & 1) : 0;               // upper half of the line
-    const int gl = l + 64 * hi;                         // position of this lane's piece along the line
-    __shared__ double zx1[2][8], zx2[2][2][8];          // NW == 2: [pair][..] exchange buffers
-    int lb = blockIdx.x;
-    {
-        const int nb = gridDim.x, q = nb >> 3, r = nb & 7, x = lb & 7, slot = lb >> 3;
-        lb = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + slot;
-    }
-    // task = (group of LG*LI lines, plane): consecutive tasks = consecutive planes of one line group
-    const int task = NW == 2 ? lb * 2 + (w >> 1) : lb * 4 + w;
-    const int npl = p.dimx;                             // single-context form: every plane
-    int grp = task / npl;
-    const int i = task - grp * npl;
-    bool task_ok = true;
-    if (NW == 1) { if (grp >= n_grp) return; }          // whole wave (wave-uniform)
-    else { task_ok = grp < n_grp; grp = task_ok ? grp : n_grp - 1; }   // the pairs of a workgroup meet at barriers: a pair past the end runs along, stores nothing
-    const int n = p.dimz;                               // even
-    const int j0 = grp * LG * LI;
-    const bool l_ok = 2 * gl < n;
-    const int lc = l_ok ? gl : (n / 2 - 1);
-    const unsigned fsb = (unsigned)(p.fstride * 8ll), nsb = (unsigned)(p.nstride * 8ll);
-    const unsigned rowb = (unsigned)p.dimz * 8u, planeb = (unsigned)(p.plane * 8ll);
-    const unsigned lbytes = 4u * fsb;
-    const prsrc_t Lcur = __builtin_amdgcn_make_buffer_rsrc((void *)(p.cur_ - p.plane), 0, (int)lbytes, 0x00020000);
-    const prsrc_t Ltmp = __builtin_amdgcn_make_buffer_rsrc((void *)(p.temp_ - p.plane), 0, (int)lbytes, 0x00020000);
-    const prsrc_t Lnext = __builtin_amdgcn_make_buffer_rsrc((void *)(p.next_ - p.plane), 0, (int)lbytes, 0x00020000);
-    const prsrc_t Ltout = __builtin_amdgcn_make_buffer_rsrc((void *)(p.temp_out_ - p.plane), 0, (int)lbytes, 0x00020000);
-    const prsrc_t rNode = __builtin_amdgcn_make_buffer_rsrc((void *)p.node_, 0, (int)(4u * nsb), 0x00020000);
-    const prsrc_t rCode = __builtin_amdgcn_make_buffer_rsrc((void *)p.code, 0, (int)(nsb / 4u), 0x00020000);
-
-    const R h2s = p.two_ds[2], h2o = p.two_ds[0], h2l = p.two_ds[1], dtv = p.dt;
-    const R ir2s = R(1) / h2s, ir2o = R(1) / h2o, ir2l = R(1) / h2l, irdt = R(1) / dtv;
-    const R vis_v = p.vis_v, vis_t = p.vis_t, b_v = p.b_v, b_t = p.b_t;
-
-    // byte offset of (plane i, line j, cell 0) inside a layer field (one halo plane first) / inside the node arrays
-    auto line_so = [&](int j) __attribute__((always_inline)) { return (unsigned)(((long long)(i + 1) * p.plane + (long long)j * p.dimz) * 8ll); };
-    auto line_son = [&](int j) __attribute__((always_inline)) { return (unsigned)(((long long)i * p.plane + (long long)j * p.dimz) * 8ll); };
-    const unsigned vo_l = (unsigned)(sub * p.dimz + 2 * lc) * 8u;          // per-lane bytes: own line of the row, own piece
-    // the two lanes that hold the ends of the line (cell 0: START or SKIP; cell n-1: END or SKIP) fetch that cell's node
-    // values with the line's other loads (n >= 8: never the same lane)
-    const bool is_end = l_ok && (gl == 0 || gl == n / 2 - 1);
-    const int ec = gl == 0 ? 0 : 1;
-    const unsigned vo_e = is_end ? vo_l + 8u * (unsigned)ec : PART_OOB;
-    // NW == 2: the cell across the cut between the two waves (cell 127 for the upper wave's first lane, 128 for the lower
-    // wave's last lane; n >= 130: both exist) comes with the line's other loads
-    const bool at_cut = NW == 2 && (hi ? l == 0 : l == 63);
-    const unsigned vo_nb = at_cut ? (hi ? 127u * 8u : 128u * 8u) : PART_OOB;
-
-    auto issue = [&](int jrow, ZLine64 &L) __attribute__((always_inline)) {
-        // jrow: first line of the row (wave-uniform); this lane's line is jrow + sub.  A row that starts past the plane (tail of
-        // the last group) is clamped; the lines jrow + sub past the plane read the next plane / the halo plane behind the last
-        // one: valid addresses (out-of-range ones return 0), nothing stored
-        const int jr = jrow < p.dimy ? jrow : p.dimy - 1;
-        const unsigned so = opq_s(line_so(jr));
-        L.tc[2] = pld2(Ltmp, vo_l, so + 2u * fsb);       // W first (cached: the rows j+-1 and planes i+-1 read it again as their neighbour)
-        L.tc[0] = pld2<PART_AUX_NT>(Ltmp, vo_l, so); L.tc[1] = pld2<PART_AUX_NT>(Ltmp, vo_l, so + fsb); L.tc[3] = pld2<PART_AUX_NT>(Ltmp, vo_l, so + 3u * fsb);
-#pragma unroll
-        for (int f = 0; f < 4; f++) L.cu[f] = pld2<PART_AUX_NT>(Lcur, vo_l, so + (unsigned)f * fsb);
-        L.wim = pld2(Ltmp, vo_l, so + 2u * fsb - planeb); L.wip = pld2(Ltmp, vo_l, so + 2u * fsb + planeb);
-        if (LI > 1) { L.wjm = pld2(Ltmp, vo_l, so + 2u * fsb - rowb); L.wjp = pld2(Ltmp, vo_l, so + 2u * fsb + rowb); }
-        const unsigned son = opq_s(line_son(jr));
-        L.code = __builtin_amdgcn_raw_buffer_load_b32(rCode, vo_l / 4u, son / 4u, 0);
-#pragma unroll
-        for (int f = 0; f < 4; f++) L.nve[f] = PBuf<R>::ld(rNode, vo_e, son + (unsigned)f * nsb);     // other lanes: out of range, no memory access
-        if (NW == 2) {
-#pragma unroll
-            for (int f = 0; f < 4; f++) L.nb[f] = PBuf<R>::ld(Ltmp, vo_nb, so + (unsigned)f * fsb);
-        }
-    };
-
-    // wjm / wjp: W of the lines j-1 / j+1 (LI == 1: the neighbouring rows' registers; else loaded with the line)
-    auto process = [&](int jrow, const ZLine64 &L, const PV2 &wjm, const PV2 &wjp) __attribute__((always_inline)) {
-        const int j = jrow + sub;
-        const bool st_ok = l_ok && j < p.dimy && task_ok; // lines past the plane compute on whatever was loaded, nothing is stored
-        const unsigned so = opq_s(line_so(jrow)), son = opq_s(line_son(jrow));
-        // ---- codes
-        int code4[2]; bool isin[2], seg[2], inter[2];
-#pragma unroll
-        for (int c = 0; c < 2; c++) {
-            int cw = (int)(L.code >> (16 * c)) & 0xFFFF;
-            cw = l_ok ? cw : 0;
-            code4[c] = (cw >> 8) & 0xF;
-            isin[c] = ((cw >> CODE_TYPE_SHIFT) & 3) == FS3D_NODE_IN && l_ok;
-            inter[c] = (code4[c] & 3) == ROW_INTERIOR;
-            seg[c] = (code4[c] & 3) != ROW_SKIP;
-        }
-        // ---- rows: neighbours along the line from the lanes next door
-        R q[2], d[4][2];                                  // d[f][c]
-        {
-            R tm1[4], tp2[4];                             // cell 2l-1 and cell 2l+2 of U, V, W, T
-#pragma unroll
-            for (int f = 0; f < 4; f++) {
-                tm1[f] = __shfl_up(L.tc[f].v[1], 1, LPL); tp2[f] = __shfl_down(L.tc[f].v[0], 1, LPL);
-                if (NW == 2) { tm1[f] = (at_cut && hi) ? L.nb[f] : tm1[f]; tp2[f] = (at_cut && !hi) ? L.nb[f] : tp2[f]; }
-            }
-#pragma unroll
-            for (int c = 0; c < 2; c++) {
-                R g[4];
-#pragma unroll
-                for (int f = 0; f < 4; f++) {
-                    const R lo = c == 0 ? tm1[f] : L.tc[f].v[0], up = c == 1 ? tp2[f] : L.tc[f].v[1];
-                    g[f] = pdivc(up - lo, h2s, ir2s);     // d/dz of U, V, W, T
-                }
-                const R x1 = pdivc(L.wip.v[c] - L.wim.v[c], h2o, ir2o), x2 = pdivc(wjp.v[c] - wjm.v[c], h2l, ir2l);   // dW/dx, dW/dy
-                const R diss = (((g[0] * g[0] + g[1] * g[1]) + R(2) * g[2] * g[2]) + g[0] * x1) + g[1] * x2;   // DissFuncZ (TimeLayer3D.h:578-588)
-                q[c] = pdivc(L.tc[2].v[c], h2s, ir2s);
-                d[0][c] = pdivc(L.cu[0].v[c] * R(3), dtv, irdt); d[1][c] = pdivc(L.cu[1].v[c] * R(3), dtv, irdt);
-                d[2][c] = pfma(-p.v_T, g[3], pdivc(L.cu[2].v[c] * R(3), dtv, irdt));
-                d[3][c] = pfma(p.t_phi, diss, pdivc(L.cu[3].v[c] * R(3), dtv, irdt));
-            }
-        }
-        PMat<R> mv[2], mt[2];
-#pragma unroll
-        for (int c = 0; c < 2; c++) part_coefs<R, false>(q[c], 0, vis_v, b_v, vis_t, b_t, mv[c], mt[c]);
-        {
-            // Rows that are not INTERIOR: the ends of every line (node values came with the line) and, rarely, obstacles /
-            // lanes past the line (their node values are fetched here).  Per cell slot c a wave-uniform test.
-            bool slow = false;
-#pragma unroll
-            for (int c = 0; c < 2; c++) {
-                const int kind = code4[c] & 3;
-                slow = slow || ((kind == ROW_START || kind == ROW_END) && !(is_end && c == ec));
-            }
-            PV2 nv[4];
-            if (__any(slow)) {
-#pragma unroll
-                for (int f = 0; f < 4; f++) nv[f] = pld2(rNode, vo_l, son + (unsigned)f * nsb);
-            }
-#pragma unroll
-            for (int c = 0; c < 2; c++) {
-                if (__any(!inter[c])) {
-                    const int kind = code4[c] & 3;
-                    const bool ns_v = kind != ROW_SKIP && !(code4[c] & ROW_VELFREE), ns_t = kind != ROW_SKIP && !(code4[c] & ROW_TEMPFREE);
-                    const bool pre = is_end && c == ec;
-                    part_coefs<R, true>(q[c], code4[c], vis_v, b_v, vis_t, b_t, mv[c], mt[c]);
-#pragma unroll
-                    for (int f = 0; f < 3; f++) d[f][c] = inter[c] ? d[f][c] : (ns_v ? (pre ? L.nve[f] : nv[f].v[c]) : R(0));
-                    d[3][c] = inter[c] ? d[3][c] : (ns_t ? (pre ? L.nve[3] : nv[3].v[c]) : R(0));
-                }
-            }
-        }
-        // ---- chunk elimination: the one step over cell 0 -- x[0] = dp - lp X_left - cp X (down-sweep) = ep - ap X_left - up X (up-sweep)
-        R cpv = R(0), lpv = R(-1), cpt = R(0), lpt = R(-1), dp3[3] = {R(0), R(0), R(0)}, dp1[1] = {R(0)};
-        { const R dd3[3] = {d[0][0], d[1][0], d[2][0]}, dd1[1] = {d[3][0]}; part_step_vt<R, false>(mv[0].a, mv[0].b, mv[0].c, mt[0].a, mt[0].b, mt[0].c, cpv, cpt, lpv, lpt, dp3, dp1, dd3, dd1); }
-        // ---- interface row (cell 1) with x[0] eliminated and x_first of the next lane substituted; normalised
-        R av, cv_, at, ct_, dd[4];
-        {
-            R nvf = __shfl_down(lpv, 1, LPL), nwf = __shfl_down(cpv, 1, LPL), ntf = __shfl_down(lpt, 1, LPL), nuf = __shfl_down(cpt, 1, LPL);
-            R ng0 = __shfl_down(dp3[0], 1, LPL), ng1 = __shfl_down(dp3[1], 1, LPL), ng2 = __shfl_down(dp3[2], 1, LPL), ng3 = __shfl_down(dp1[0], 1, LPL);
-            if (NW == 2) {
-                // the lower wave's last lane takes the first-cell coefficients of the upper wave's first lane
-                double *const b = zx1[w >> 1];
-                if (hi && l == 0) { b[0] = lpv; b[1] = cpv; b[2] = lpt; b[3] = cpt; b[4] = dp3[0]; b[5] = dp3[1]; b[6] = dp3[2]; b[7] = dp1[0]; }
-                __syncthreads();
-                if (at_cut && !hi) { nvf = b[0]; nwf = b[1]; ntf = b[2]; nuf = b[3]; ng0 = b[4]; ng1 = b[5]; ng2 = b[6]; ng3 = b[7]; }
-            }
-            const bool last = NW == 2 ? (hi && l == 63) : l == LPL - 1;   // no lane behind: its first cell does not exist (the row has c = 0 anyway)
-            const R clv = last ? R(0) : mv[1].c, clt = last ? R(0) : mt[1].c;
-            const R lov = -mv[1].a * lpv, div = pfma(-clv, nvf, pfma(-mv[1].a, cpv, mv[1].b)), upv_ = -clv * nwf;
-            const R lot = -mt[1].a * lpt, dit = pfma(-clt, ntf, pfma(-mt[1].a, cpt, mt[1].b)), upt_ = -clt * nuf;
-            const R rv = prcp(div), rt = prcp(dit);
-            av = pquot(lov, div, rv); cv_ = pquot(upv_, div, rv); at = pquot(lot, dit, rt); ct_ = pquot(upt_, dit, rt);
-            dd[0] = pquot(pfma(-clv, ng0, pfma(-mv[1].a, dp3[0], d[0][1])), div, rv);
-            dd[1] = pquot(pfma(-clv, ng1, pfma(-mv[1].a, dp3[1], d[1][1])), div, rv);
-            dd[2] = pquot(pfma(-clv, ng2, pfma(-mv[1].a, dp3[2], d[2][1])), div, rv);
-            dd[3] = pquot(pfma(-clt, ng3, pfma(-mt[1].a, dp1[0], d[3][1])), dit, rt);
-        }
-        // NW == 2: the coupling across the cut leaves the wave's system and becomes a right-hand side of its own
-        // (x_l = X_l - Z * E_l with Z the unknown on the other side of the cut)
-        R ev = R(0), et = R(0);
-        if (NW == 2) {
-            if (at_cut && !hi) { ev = cv_; et = ct_; cv_ = R(0); ct_ = R(0); }
-            if (at_cut && hi) { ev = av; et = at; av = R(0); at = R(0); }
-        }
-        // ---- parallel cyclic reduction over the LPL lanes of the line, one scalar reduction per matrix
-#pragma unroll
-        for (int s = 1; s < LPL; s <<= 1) {
-            // lanes without a partner at this distance: their a (c) is zero by now, the partner values must only be finite
-            const bool has_m = l >= s, has_p = l + s < LPL;
-            const R a_v = has_m ? av : R(0), c_v = has_p ? cv_ : R(0), a_t = has_m ? at : R(0), c_t = has_p ? ct_ : R(0);
-            const R dnv = pfma(-a_v, __shfl_up(cv_, s, LPL), pfma(-c_v, __shfl_down(av, s, LPL), R(1)));
-            const R dnt = pfma(-a_t, __shfl_up(ct_, s, LPL), pfma(-c_t, __shfl_down(at, s, LPL), R(1)));
-            const R rv = prcp(dnv), rt = prcp(dnt);
-            R nd[4];
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                const R a = k < 3 ? a_v : a_t, c = k < 3 ? c_v : c_t;
-                nd[k] = pquot(pfma(-a, __shfl_up(dd[k], s, LPL), pfma(-c, __shfl_down(dd[k], s, LPL), dd[k])), k < 3 ? dnv : dnt, k < 3 ? rv : rt);
-            }
-            if (NW == 2) {
-                const R nev = pquot(pfma(-a_v, __shfl_up(ev, s, LPL), pfma(-c_v, __shfl_down(ev, s, LPL), ev)), dnv, rv);
-                const R net = pquot(pfma(-a_t, __shfl_up(et, s, LPL), pfma(-c_t, __shfl_down(et, s, LPL), et)), dnt, rt);
-                ev = nev; et = net;
-            }
-            const R nav = pquot(-a_v * __shfl_up(av, s, LPL), dnv, rv), ncv = pquot(-c_v * __shfl_down(cv_, s, LPL), dnv, rv);
-            const R nat = pquot(-a_t * __shfl_up(at, s, LPL), dnt, rt), nct = pquot(-c_t * __shfl_down(ct_, s, LPL), dnt, rt);
-            av = nav; cv_ = ncv; at = nat; ct_ = nct;
-#pragma unroll
-            for (int k = 0; k < 4; k++) dd[k] = nd[k];
-        }
-        // ---- back-substitution: x[1] = X, x[0] = d'[0] - l[0] X_left - c'[0] X
-        R x[4][2];                                        // x[f][c]
-        {
-            R xcut[4] = {R(0), R(0), R(0), R(0)};         // NW == 2, upper wave: the lower wave's last unknown
-            if (NW == 2) {
-                // join the halves: X = Xd - Y0 E_lo, Y = Yd - X63 E_hi  ->  per right-hand side a 2x2 system in (X63, Y0)
-                double *const bl = zx2[w >> 1][0], *const bh = zx2[w >> 1][1];
-                if (at_cut) { double *const b = hi ? bh : bl; b[0] = dd[0]; b[1] = dd[1]; b[2] = dd[2]; b[3] = dd[3]; b[4] = ev; b[5] = et; }
-                __syncthreads();
-                const R elv = bl[4], elt = bl[5], ehv = bh[4], eht = bh[5];
-                const R rdv = prcp(pfma(-elv, ehv, R(1))), rdt = prcp(pfma(-elt, eht, R(1)));
-#pragma unroll
-                for (int k = 0; k < 4; k++) {
-                    const R el = k < 3 ? elv : elt, eh = k < 3 ? ehv : eht, den = pfma(-el, eh, R(1));
-                    const R x63 = pquot(pfma(-el, bh[k], bl[k]), den, k < 3 ? rdv : rdt);
-                    const R y0 = pfma(-x63, eh, bh[k]);
-                    dd[k] = pfma(-(hi ? x63 : y0), k < 3 ? ev : et, dd[k]);
-                    xcut[k] = x63;
-                }
-            }
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                R xl = __shfl_up(dd[k], 1, LPL);
-                xl = l == 0 ? (NW == 2 && hi ? xcut[k] : R(0)) : xl;
-                x[k][1] = dd[k];
-                x[k][0] = pfma(-(k < 3 ? cpv : cpt), dd[k], pfma(-(k < 3 ? lpv : lpt), xl, k < 3 ? dp3[k] : dp1[0]));
-            }
-        }
-        // ---- scatter + merge
-        const unsigned vo_st = st_ok ? vo_l : PART_OOB;
-        const bool all_seg = seg[0] && seg[1];
-        if (p.store_next) {
-            if (__all(all_seg || !st_ok)) {
-#pragma unroll
-                for (int f = 0; f < 4; f++) pst2<PART_AUX_NT>(Lnext, vo_st, so + (unsigned)f * fsb, x[f]);
-            } else {
-#pragma unroll
-                for (int f = 0; f < 4; f++)
-#pragma unroll
-                    for (int c = 0; c < 2; c++)
-                        PBuf<R>::st(Lnext, seg[c] ? vo_st : PART_OOB, so + (unsigned)f * fsb + 8u * (unsigned)c, x[f][c]);
-            }
-        }
-        if (p.merge) {
-            const bool stale = (isin[0] && !seg[0]) || (isin[1] && !seg[1]);
-            if (__any(stale)) {
-                // NODE_IN cell outside every segment: the reference merges the stale `next` value (Grid3D.cpp:87-117)
-#pragma unroll
-                for (int f = 0; f < 4; f++) {
-                    const PV2 sv = pld2(Lnext, vo_l, so + (unsigned)f * fsb);
-#pragma unroll
-                    for (int c = 0; c < 2; c++) x[f][c] = (isin[c] && !seg[c]) ? sv.v[c] : x[f][c];
-                }
-            }
-#pragma unroll
-            for (int f = 0; f < 4; f++) {
-                R o2[2];
-#pragma unroll
-                for (int c = 0; c < 2; c++) {
-                    R mvv = (L.tc[f].v[c] + x[f][c]) * R(0.5);       // MergeFieldTo (TimeLayer3D.h:415-436)
-                    if (p.merge == 2) mvv = (mvv + x[f][c]) * R(0.5);
-                    o2[c] = isin[c] ? mvv : L.tc[f].v[c];
-                }
-                pst2<PART_AUX_NT>(Ltout, vo_st, so + (unsigned)f * fsb, o2);
-            }
-        }
-    };
-
-    // ---- the rows of this wave's group, two per trip, the next row's loads in flight (the loop of k_sweep_part_z)
-    ZLine64 La, Lb;
-    PV2 wprev, wedge;
-    if (LI == 1) {
-        wprev = pld2(Ltmp, vo_l, opq_s(line_so(j0)) + 2u * fsb - rowb);
-        const int jl = j0 + LG < p.dimy ? j0 + LG : p.dimy - 1;
-        wedge = pld2(Ltmp, vo_l, opq_s(line_so(jl)) + 2u * fsb);
-    }
-    issue(j0, La);
-    for (int r = 0; r < LG; r += 2) {
-        const int ja = j0 + r * LI, jb = ja + LI, jc = jb + LI;
-        if (r + 1 < LG) issue(jb, Lb);
-        __builtin_amdgcn_sched_barrier(0);
-        if (LI == 1) {
-            PV2 wn = wedge;
-            if (r + 1 < LG) wn = Lb.tc[2];
-            process(ja, La, wprev, wn);
-            wprev = La.tc[2];
-        }
-        else process(ja, La, La.wjm, La.wjp);
-        __builtin_amdgcn_sched_barrier(0);
-        if (r + 1 < LG) {
-            if (r + 2 < LG) issue(jc, La);
-            __builtin_amdgcn_sched_barrier(0);
-            if (LI == 1) {
-                PV2 wn = wedge;
-                if (r + 2 < LG) wn = La.tc[2];
-                process(jb, Lb, wprev, wn);
-                wprev = Lb.tc[2];
-            }
-            else process(jb, Lb, Lb.wjm, Lb.wjp);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    }
-}
-
-template <int LPL, int NW = 1>
-static bool part_launch_z64(fs3d_ctx *c, const SweepParams<double> &p)
-{
-    constexpr int LI = 64 / LPL;
-    const int rows = (p.dimy + LI - 1) / LI;              // rows of LI lines per plane
-    // rows per wave as in part_launch_z: 16 where that still gives every CU several workgroups
-    int LG = 16;
-    while (LG > 1 && (long long)((rows + LG - 1) / LG) * p.dimx < 4096) LG >>= 1;
-    if (LG > rows) LG = rows;
-    const int n_grp = (rows + LG - 1) / LG;
-    const long long tasks = (long long)n_grp * p.dimx;
+    const long long tasks = (long long)n_grp * npl;
     const int tpw = NW == 2 ? 2 : 4;                      // tasks per workgroup of four waves
-    hipLaunchKernelGGL((k_sweep_part_z64<LPL, NW>), dim3((unsigned)((tasks + tpw - 1) / tpw)), dim3(256), 0, c->stream, p, n_grp, LG);
+    hipLaunchKernelGGL((k_sweep_part_z<R, LPL, NW>), dim3((unsigned)((tasks + tpw - 1) / tpw)), dim3(256), 0, c->stream, p, n_grp, LG);
     return true;
 }
 
-static bool part_dispatch_z(fs3d_ctx *c, const SweepParams<double> &p)
+template <typename R>
+static bool part_dispatch_z(fs3d_ctx *c, const SweepParams<R> &p)
 {
+    constexpr int C = 16 / sizeof(R);
     const int n = p.dimz;
-    if (n % 2 != 0 || n < 8) return false;                // whole 16-byte pieces of two cells
+    if (n % C != 0 || n < 8) return false;                // whole 16-byte pieces
     if (p.dimy < 4) return false;
-    if (n <= 32) return part_launch_z64<16>(c, p);
-    if (n <= 64) return part_launch_z64<32>(c, p);
-    if (n <= 128) return part_launch_z64<64>(c, p);
-    if (n <= 256) return part_launch_z64<64, 2>(c, p);     // a pair of waves per line
+    if (n <= 16 * C) return part_launch_z<R, 16>(c, p);
+    if (n <= 32 * C) return part_launch_z<R, 32>(c, p);
+    if (n <= 64 * C) return part_launch_z<R, 64>(c, p);
+    if (n <= 128 * C) return part_launch_z<R, 64, 2>(c, p);   // a pair of waves per line
     return false;
 }
 

@@ -1,6 +1,6 @@
 """CPU: the public face of FS3D_OPT_F64_PART (fp64 partition kernels, off by default) and the algebra of the chunking only
 the fp64 Z kernel uses -- two cells per lane, the interface system by parallel cyclic reduction across up to 128 chunks
-(csrc/kernels_part.hip: k_sweep_part_z64) -- stated by the numpy twin (cmc_fluid_solver_amd/partition.py) against the
+(csrc/kernels_part.hip: k_sweep_part_z<double, ...>) -- stated by the numpy twin (cmc_fluid_solver_amd/partition.py) against the
 sequential Thomas solve of the oracle."""
 import os
 import re

@@ -102,8 +102,12 @@ GRIDS = {
     "obstacle_12x256x40": lambda: grids.box_with_obstacle(12, 256, 40, h=0.004),     # full-length Y lines
     "obstacle_10x20x256": lambda: grids.box_with_obstacle(10, 20, 256, h=0.004),     # full-length Z lines: a pair of waves per line
     "obstacle_9x7x128": lambda: grids.box_with_obstacle(9, 7, 128, h=0.01),          # Z: one wave per line, all 64 lanes; odd line count
+    # the fp32 grids obstacle_8x10x388 and box_7x6x260 at half the line length: the edge cases of a pair of waves per line
+    "obstacle_8x10x194": lambda: grids.box_with_obstacle(8, 10, 194, h=0.003),       # Z: the upper wave partly past the line
+    "box_7x6x130": lambda: grids.box(7, 6, 130, h=0.004),                            # Z: one piece in the upper wave
 }
-SWEEP_GRIDS = ["box_20x24x28", "obstacle_70x40x36", "box_130x100x64", "obstacle_256x16x48", "obstacle_12x256x40", "obstacle_10x20x256", "obstacle_9x7x128"]
+SWEEP_GRIDS = ["box_20x24x28", "obstacle_70x40x36", "box_130x100x64", "obstacle_256x16x48", "obstacle_12x256x40", "obstacle_10x20x256", "obstacle_9x7x128",
+               "obstacle_8x10x194", "box_7x6x130"]
 
 
 @pytest.mark.parametrize("gname", SWEEP_GRIDS)
