@@ -195,16 +195,19 @@ struct fs3d_ctx {
 void fs3d_geom_destroy(fs3d_ctx *c);
 
 // kernels_*.hip
+// What a sweep launcher did.  NA: it does not cover these dims / this precision / this slab form -- the caller may try the
+// next kernel.  FAILED: a HIP call failed and c->err says which -- the caller returns FS3D_ERR_HIP, nothing falls back.
+enum class Launch { RAN, NA, FAILED };
 template <typename R> void launch_sweep_line(fs3d_ctx *c, int dir, const SweepParams<R> &p);
-template <typename R> bool launch_sweep_pipe(fs3d_ctx *c, int dir, const SweepParams<R> &p); // false: dims unsupported
-// kernels_part.hip: partition (reduced-interface) solve, results to a stated tolerance; false: dims / precision unsupported
-// (double: only with c->opt_f64_part, and never for a slab)
-template <typename R> bool launch_sweep_part(fs3d_ctx *c, int dir, const SweepParams<R> &p);
-// X sweep halves of an x-slab for the bundles [b0, b1) (64 lines each, line = j*dimz + k); false: dims unsupported
+template <typename R> Launch launch_sweep_pipe(fs3d_ctx *c, int dir, const SweepParams<R> &p);
+// kernels_part.hip: partition (reduced-interface) solve, results to a stated tolerance (double: only with c->opt_f64_part,
+// and never for a slab)
+template <typename R> Launch launch_sweep_part(fs3d_ctx *c, int dir, const SweepParams<R> &p);
+// X sweep halves of an x-slab for the bundles [b0, b1) (64 lines each, line = j*dimz + k)
 template <typename R> bool xslab_pipe_supported(const SweepParams<R> &p);
-template <typename R> bool launch_xslab_pipe(fs3d_ctx *c, SweepParams<R> p, int half, int b0, int b1);
-// lines longer than the pipe kernel holds: the sweep as a sequence of segment halves on one GPU; false: unsupported
-template <typename R> bool launch_sweep_pipe_segmented(fs3d_ctx *c, int dir, SweepParams<R> p);
+template <typename R> Launch launch_xslab_pipe(fs3d_ctx *c, SweepParams<R> p, int half, int b0, int b1);
+// lines longer than the pipe kernel holds: the sweep as a sequence of segment halves on one GPU
+template <typename R> Launch launch_sweep_pipe_segmented(fs3d_ctx *c, int dir, SweepParams<R> p);
 template <typename R> void launch_xsweep_fwd(fs3d_ctx *c, const SweepParams<R> &p, const void *carry_in, void *carry_out, long long l0, long long l1);
 // reduced-interface cross-slab X sweep: interface coefficients of this slab (18 words per line), the R x R interface solve
 template <typename R> void launch_xiface(fs3d_ctx *c, const SweepParams<R> &p, void *out);

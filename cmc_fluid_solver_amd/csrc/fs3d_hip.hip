@@ -226,24 +226,29 @@ static inline unsigned grid_for(long long n, int bs, int cap = 4096)
     return (unsigned)std::max(1LL, std::min<long long>(g, cap));
 }
 
-// per-launch HIP-event timing on the context's stream (events are pooled and reused)
-static void rec_begin(fs3d_ctx *c, int cls)
-{
-    if (!c->timing) return;
-    if (c->ev_used + 2 > c->ev.size()) {
-        hipEvent_t e0, e1;
-        hipEventCreate(&e0); hipEventCreate(&e1);
-        c->ev.push_back(e0); c->ev.push_back(e1);
+// per-launch HIP-event timing on the context's stream (events are pooled and reused): one event pair around what a scope
+// enqueues.  The end event is recorded on every way out of the scope, so rec_collect never meets a pair without one.
+struct RecScope {
+    fs3d_ctx *c;
+    size_t end = 0;             // index of the end event; 0: no pair (timing off, or cancelled)
+    RecScope(fs3d_ctx *c_, int cls) : c(c_)
+    {
+        if (!c->timing) return;
+        if (c->ev_used + 2 > c->ev.size()) {
+            hipEvent_t e0, e1;
+            hipEventCreate(&e0); hipEventCreate(&e1);
+            c->ev.push_back(e0); c->ev.push_back(e1);
+        }
+        hipEventRecord(c->ev[c->ev_used], c->stream);
+        c->ev_used += 2;
+        c->ev_class.push_back(cls);
+        end = c->ev_used - 1;
     }
-    hipEventRecord(c->ev[c->ev_used], c->stream);
-    c->ev_used += 2;
-    c->ev_class.push_back(cls);
-}
-static void rec_end(fs3d_ctx *c)
-{
-    if (!c->timing) return;
-    hipEventRecord(c->ev[c->ev_used - 1], c->stream);
-}
+    RecScope(const RecScope &) = delete;
+    ~RecScope() { if (end) hipEventRecord(c->ev[end], c->stream); }
+    // nothing was launched: drop the pair (the last one begun)
+    void cancel() { if (end) { c->ev_used -= 2; c->ev_class.pop_back(); end = 0; } }
+};
 // accumulates into t_ms/t_n (reset with fs3d_enable_timing)
 static void rec_collect(fs3d_ctx *c)
 {
@@ -265,6 +270,19 @@ static fs3d_status check_device_errors(fs3d_ctx *c)
     *c->errw_host = 0;
     return fail(c, FS3D_ERR_HIP, "GPU " + std::to_string(c->device) + ": sweep kernel: a relay hand-over between waves timed out; the fields of this step are invalid");
 }
+
+// the partition kernels may be tried (results to a stated tolerance; the other kernel ids ask for one kernel or for exact bits)
+static bool part_allowed(const fs3d_ctx *c) { return c->opt_kernel == FS3D_SWEEP_AUTO || c->opt_kernel == FS3D_SWEEP_PART; }
+
+// Launch::FAILED of a sweep launcher -> FS3D_ERR_HIP with the launcher's message (c->err)
+static fs3d_status launch_failed(fs3d_ctx *c, const char *what)
+{
+    return fail(c, FS3D_ERR_HIP, "GPU " + std::to_string(c->device) + ": " + what + ": " + c->err);
+}
+
+// A rank that fails anywhere in a cross-slab sweep -- allocations included -- must not leave its neighbours blocked in their
+// receives: it aborts the group (fs3d_comm_abort), the peers' pending and later exchanges return FS3D_ERR_COMM
+struct AbortOnError { fs3d_ctx *c; fs3d_status *st; ~AbortOnError() { if (*st != FS3D_OK) fs3d_comm_abort(c); } };
 
 // ---------------------------------------------------------------------------------
 // lifetime
@@ -773,10 +791,8 @@ static fs3d_status ensure_carries(fs3d_ctx *c)
 template <typename R>
 static fs3d_status xsweep_multi(fs3d_ctx *c, SweepParams<R> &p)
 {
-    // a rank that fails anywhere in here -- allocations included -- must not leave its neighbours blocked in their receives: it
-    // aborts the group (fs3d_comm_abort), the peers' pending and later exchanges return FS3D_ERR_COMM
     fs3d_status st = FS3D_OK;
-    struct AbortOnError { fs3d_ctx *c; fs3d_status *st; ~AbortOnError() { if (*st != FS3D_OK) fs3d_comm_abort(c); } } guard{c, &st};
+    AbortOnError guard{c, &st};
     if ((st = ensure_scratch(c))) return st;
     p.scr_ = (R *)c->scr;
     const size_t pl = (size_t)c->plane;
@@ -797,7 +813,7 @@ static fs3d_status xsweep_multi(fs3d_ctx *c, SweepParams<R> &p)
         long long l0, l1; range(b, l0, l1);
         if (l1 <= l0) continue;
         if (!first && (st = fs3d_comm_xfer_rows(c, c->carry[0], 6, pl, l0, l1, c->rank - 1, false))) return st;
-        if (pipe) { if (!launch_xslab_pipe<R>(c, p, 1, (int)(l0 / 64), (int)(l1 / 64))) return st = fail(c, FS3D_ERR_HIP, "pipe kernel launch (forward half)"); }
+        if (pipe) { if (launch_xslab_pipe<R>(c, p, 1, (int)(l0 / 64), (int)(l1 / 64)) != Launch::RAN) return st = launch_failed(c, "cross-slab X sweep, forward half"); }
         else launch_xsweep_fwd<R>(c, p, first ? nullptr : c->carry[0], c->carry[1], l0, l1);
         if (!last && (st = fs3d_comm_xfer_rows(c, c->carry[1], 6, pl, l0, l1, c->rank + 1, true))) return st;
     }
@@ -805,7 +821,7 @@ static fs3d_status xsweep_multi(fs3d_ctx *c, SweepParams<R> &p)
         long long l0, l1; range(b, l0, l1);
         if (l1 <= l0) continue;
         if (!last && (st = fs3d_comm_xfer_rows(c, c->carry[2], 4, pl, l0, l1, c->rank + 1, false))) return st;
-        if (pipe) { if (!launch_xslab_pipe<R>(c, p, 2, (int)(l0 / 64), (int)(l1 / 64))) return st = fail(c, FS3D_ERR_HIP, "pipe kernel launch (backward half)"); }
+        if (pipe) { if (launch_xslab_pipe<R>(c, p, 2, (int)(l0 / 64), (int)(l1 / 64)) != Launch::RAN) return st = launch_failed(c, "cross-slab X sweep, backward half"); }
         else launch_xsweep_bwd<R>(c, p, last ? nullptr : c->carry[2], c->carry[3], l0, l1);
         if (!first && (st = fs3d_comm_xfer_rows(c, c->carry[3], 4, pl, l0, l1, c->rank - 1, true))) return st;
     }
@@ -819,7 +835,7 @@ template <typename R>
 static fs3d_status xsweep_reduced(fs3d_ctx *c, SweepParams<R> &p)
 {
     fs3d_status st = FS3D_OK;
-    struct AbortOnError { fs3d_ctx *c; fs3d_status *st; ~AbortOnError() { if (*st != FS3D_OK) fs3d_comm_abort(c); } } guard{c, &st};   // peers never block on a rank that failed
+    AbortOnError guard{c, &st};
     if (c->nranks > FS3D_XREDUCE_MAX_RANKS) return st = fail(c, FS3D_ERR_UNSUPPORTED, "reduced-interface X solve: more than 64 slabs (k_xreduce holds the slab system in registers); use FS3D_XSOLVE_PIPELINED");
     if ((st = ensure_scratch(c))) return st;
     p.scr_ = (R *)c->scr;
@@ -834,10 +850,12 @@ static fs3d_status xsweep_reduced(fs3d_ctx *c, SweepParams<R> &p)
     // the slab's interface words: a first pass of the X partition kernel (rows and chunk elimination on chip, 8 words per cell
     // read, 18 words per line written) where it applies, else the thread-per-line walk over the planes
     bool iface_done = false;
-    if (c->opt_kernel == FS3D_SWEEP_AUTO || c->opt_kernel == FS3D_SWEEP_PART) {
+    if (part_allowed(c)) {
         SweepParams<R> pa = p;
         pa.xiface_pass = 1; pa.carry_in = nullptr; pa.xcarry_in = nullptr; pa.carry_out = (R *)c->xif_send; pa.merge = 0; pa.store_next = 0;
-        iface_done = launch_sweep_part<R>(c, 0, pa);
+        const Launch r = launch_sweep_part<R>(c, 0, pa);
+        if (r == Launch::FAILED) return st = launch_failed(c, "reduced-interface X solve, interface pass");
+        iface_done = r == Launch::RAN;
     }
     if (!iface_done) launch_xiface<R>(c, p, c->xif_send);
     // the R x R interface systems: every rank solves every line's (one all-gather), or -- three ranks and more -- every rank solves
@@ -869,16 +887,20 @@ static fs3d_status xsweep_reduced(fs3d_ctx *c, SweepParams<R> &p)
     p.xcarry_in = (const R *)c->carry[2]; p.xcarry_out = (R *)c->carry[3];
     c->ran_xsolve = iface_done ? 3 : 2;
     // the slab with both boundary values given: the X partition kernel (rows on chip, 16 words per cell) where it applies ...
-    if ((c->opt_kernel == FS3D_SWEEP_AUTO || c->opt_kernel == FS3D_SWEEP_PART) && launch_sweep_part<R>(c, 0, p)) {
-        c->ran_kernel[0] = FS3D_SWEEP_PART; c->ran_segmented[0] = 0;
-        return FS3D_OK;
+    if (part_allowed(c)) {
+        const Launch r = launch_sweep_part<R>(c, 0, p);
+        if (r == Launch::FAILED) return st = launch_failed(c, "reduced-interface X solve, slab sweep");
+        if (r == Launch::RAN) {
+            c->ran_kernel[0] = FS3D_SWEEP_PART; c->ran_segmented[0] = 0;
+            return FS3D_OK;
+        }
     }
     // ... else the exact halves (rows through the HBM scratch)
     const bool pipe = c->opt_kernel != FS3D_SWEEP_LINE && xslab_pipe_supported<R>(p);
     c->ran_kernel[0] = pipe ? FS3D_SWEEP_PIPE : FS3D_SWEEP_LINE; c->ran_segmented[0] = 1;
     if (pipe) {
-        if (!launch_xslab_pipe<R>(c, p, 1, 0, (int)(pl / 64))) return st = fail(c, FS3D_ERR_HIP, "pipe kernel launch (forward half)");
-        if (!launch_xslab_pipe<R>(c, p, 2, 0, (int)(pl / 64))) return st = fail(c, FS3D_ERR_HIP, "pipe kernel launch (backward half)");
+        if (launch_xslab_pipe<R>(c, p, 1, 0, (int)(pl / 64)) != Launch::RAN) return st = launch_failed(c, "reduced-interface X solve, forward half");
+        if (launch_xslab_pipe<R>(c, p, 2, 0, (int)(pl / 64)) != Launch::RAN) return st = launch_failed(c, "reduced-interface X solve, backward half");
     } else {
         launch_xsweep_fwd<R>(c, p, c->carry[0], c->carry[1], 0, (long long)pl);
         launch_xsweep_bwd<R>(c, p, c->carry[2], c->carry[3], 0, (long long)pl);
@@ -899,8 +921,7 @@ static bool sweep_overlapped(fs3d_ctx *c, int dir, SweepParams<R> &p, int b_temp
 {
     st = FS3D_OK;
     if (!c->opt_overlap || c->nranks < 2 || dir == 0 || c->dimx < 3) return false;
-    if (c->opt_kernel != FS3D_SWEEP_AUTO && c->opt_kernel != FS3D_SWEEP_PART) return false;
-    if (std::is_same<R, double>::value) return false;
+    if (!part_allowed(c) || std::is_same<R, double>::value) return false;
     if (!c->comm_stream) {
         if (hipStreamCreateWithFlags(&c->comm_stream, hipStreamNonBlocking) != hipSuccess ||
             hipEventCreateWithFlags(&c->ev_src, hipEventDisableTiming) != hipSuccess ||
@@ -908,7 +929,9 @@ static bool sweep_overlapped(fs3d_ctx *c, int dir, SweepParams<R> &p, int b_temp
     }
     if (hipEventRecord(c->ev_src, c->stream) != hipSuccess) { st = fail(c, FS3D_ERR_HIP, "halo overlap: event"); return true; }
     p.o_begin = 1; p.o_count = c->dimx - 2;
-    if (!launch_sweep_part<R>(c, dir, p)) { p.o_begin = 0; p.o_count = 0; return false; }      // dims outside the partition kernels
+    const Launch r = launch_sweep_part<R>(c, dir, p);
+    if (r == Launch::FAILED) { st = launch_failed(c, "halo overlap, interior planes"); return true; }
+    if (r == Launch::NA) { p.o_begin = 0; p.o_count = 0; return false; }      // dims outside the partition kernels
     c->ran_kernel[dir] = FS3D_SWEEP_PART; c->ran_segmented[dir] = 0;
     // the interior planes are running; now the exchange, on its own stream, behind everything that was enqueued before them
     if (hipStreamWaitEvent(c->comm_stream, c->ev_src, 0) != hipSuccess) { st = fail(c, FS3D_ERR_HIP, "halo overlap: event"); return true; }
@@ -933,60 +956,57 @@ static fs3d_status sweep_buffers(fs3d_ctx *c, int dir, double dt, int b_cur, int
     SweepParams<R> p;
     fill_params<R>(c, p, dir, dt, b_cur, b_temp, b_next, b_tout, merge);
     const int cls = dir == 2 ? 0 : (dir == 1 ? 1 : 2);
+    fs3d_status st;
     if (halo && c->nranks > 1) {
-        fs3d_status so;
-        rec_begin(c, cls);
-        if (sweep_overlapped<R>(c, dir, p, b_temp, so)) {      // the exchange runs beside the interior planes: inside the sweep's time
-            rec_end(c);
-            if (so) return so;
-            HIPCHK(c, hipGetLastError());
-            return FS3D_OK;
+        {
+            RecScope rec(c, cls);
+            if (sweep_overlapped<R>(c, dir, p, b_temp, st)) {      // the exchange runs beside the interior planes: inside the sweep's time
+                if (st) return st;
+                HIPCHK(c, hipGetLastError());
+                return FS3D_OK;
+            }
+            rec.cancel();
         }
-        if (c->timing) { c->ev_used -= 2; c->ev_class.pop_back(); }      // nothing was launched: drop the event pair
-        rec_begin(c, 7);                                       // syncHalos_{X,Y,Z} (AdiSolver3D.cpp:608)
-        so = fs3d_comm_halo_exchange(c, b_temp, 4);
-        rec_end(c);
-        if (so) return so;
+        RecScope rec(c, 7);                                    // syncHalos_{X,Y,Z} (AdiSolver3D.cpp:608)
+        if ((st = fs3d_comm_halo_exchange(c, b_temp, 4))) return st;
     }
-    rec_begin(c, cls);
+    RecScope rec(c, cls);
     // (a slab context without peers that asks for the reduced form runs its kernels on the slab alone: tools/slab_cost.py times
     // what one rank computes)
     if (dir == 0 && (c->nranks > 1 || ((c->opt_xsolve == 2 || c->opt_xsolve == 3) && (p.ghost_lo || p.ghost_hi)))) {
         // reduced-interface form (all ranks at once) unless bit-equality with the sequential recurrence was asked for
-        const bool reduced = c->opt_xsolve == 2 || c->opt_xsolve == 3 || (c->opt_xsolve == 0 && c->nranks <= FS3D_XREDUCE_MAX_RANKS && (c->opt_kernel == FS3D_SWEEP_AUTO || c->opt_kernel == FS3D_SWEEP_PART));
-        fs3d_status st = reduced ? xsweep_reduced<R>(c, p) : xsweep_multi<R>(c, p);
-        rec_end(c);
-        if (st) return st;
+        const bool reduced = c->opt_xsolve == 2 || c->opt_xsolve == 3 || (c->opt_xsolve == 0 && c->nranks <= FS3D_XREDUCE_MAX_RANKS && part_allowed(c));
+        if ((st = reduced ? xsweep_reduced<R>(c, p) : xsweep_multi<R>(c, p))) return st;
         HIPCHK(c, hipGetLastError());
         return FS3D_OK;
     }
-    bool done = false;
+    // the first kernel that covers these dims, in the order the option allows; a launcher that failed ends the sweep
     const int ok = c->opt_kernel;
-    c->ran_segmented[dir] = 0;
-    if (ok == FS3D_SWEEP_AUTO || ok == FS3D_SWEEP_PART) {
-        done = launch_sweep_part<R>(c, dir, p);
-        if (done) c->ran_kernel[dir] = FS3D_SWEEP_PART;
-        else if (ok == FS3D_SWEEP_PART) { rec_end(c); return fail(c, FS3D_ERR_UNSUPPORTED, "partition sweep kernel does not support these dims / this precision"); }
-    }
     const bool exact_fast = ok == FS3D_SWEEP_AUTO || ok == FS3D_SWEEP_EXACT || ok == FS3D_SWEEP_PIPE;
-    if (!done && exact_fast) { done = launch_sweep_pipe<R>(c, dir, p); if (done) c->ran_kernel[dir] = FS3D_SWEEP_PIPE; }
-    if (!done && exact_fast) {
-        // lines longer than one launch holds on chip: segment by segment, rows through the HBM scratch
-        fs3d_status st = ensure_scratch(c);
-        if (st) return st;
-        p.scr_ = (R *)c->scr;
-        done = launch_sweep_pipe_segmented<R>(c, dir, p);
-        if (done) { c->ran_kernel[dir] = FS3D_SWEEP_PIPE; c->ran_segmented[dir] = 1; }
+    Launch r = Launch::NA;
+    int ran = FS3D_SWEEP_LINE;
+    c->ran_segmented[dir] = 0;
+    if (part_allowed(c)) {
+        r = launch_sweep_part<R>(c, dir, p); ran = FS3D_SWEEP_PART;
+        if (r == Launch::NA && ok == FS3D_SWEEP_PART) return fail(c, FS3D_ERR_UNSUPPORTED, "partition sweep kernel does not support these dims / this precision");
     }
-    if (!done) {
-        if (ok == FS3D_SWEEP_PIPE) { rec_end(c); return fail(c, FS3D_ERR_UNSUPPORTED, "pipelined sweep kernel does not support these dims (" + c->err + ")"); }
-        fs3d_status st = ensure_scratch(c);
-        if (st) return st;
+    if (r == Launch::NA && exact_fast) { r = launch_sweep_pipe<R>(c, dir, p); ran = FS3D_SWEEP_PIPE; }
+    if (r == Launch::NA && exact_fast) {
+        // lines longer than one launch holds on chip: segment by segment, rows through the HBM scratch
+        if ((st = ensure_scratch(c))) return st;
+        p.scr_ = (R *)c->scr;
+        r = launch_sweep_pipe_segmented<R>(c, dir, p);
+        if (r == Launch::RAN) c->ran_segmented[dir] = 1;
+    }
+    if (r == Launch::NA) {
+        if (ok == FS3D_SWEEP_PIPE) return fail(c, FS3D_ERR_UNSUPPORTED, "pipelined sweep kernel does not support these dims (" + c->err + ")");
+        if ((st = ensure_scratch(c))) return st;
         fill_params<R>(c, p, dir, dt, b_cur, b_temp, b_next, b_tout, merge);
         launch_sweep_line<R>(c, dir, p);
-        c->ran_kernel[dir] = FS3D_SWEEP_LINE;
+        r = Launch::RAN; ran = FS3D_SWEEP_LINE;
     }
-    rec_end(c);
+    if (r == Launch::FAILED) return launch_failed(c, "sweep");
+    c->ran_kernel[dir] = ran;
     HIPCHK(c, hipGetLastError());
     return FS3D_OK;
 }
@@ -1008,17 +1028,18 @@ extern "C" fs3d_status fs3d_profile_sweep(fs3d_ctx *c, int dir, double dt, int l
         c->stamps_cap = nb;
     }
     HIPCHK(c, hipMemsetAsync(c->stamps, 0, sizeof(unsigned long long) * 64 * (size_t)nb, c->stream));
-    bool ok;
+    Launch r = Launch::NA;
     if (c->prec == FS3D_F32) {
         SweepParams<float> p; fill_params<float>(c, p, dir, dt, c->slot[l_cur], c->slot[l_temp], c->slot[l_next], c->spare, 1);
         p.stamps = c->stamps;
-        ok = (c->opt_kernel == FS3D_SWEEP_AUTO || c->opt_kernel == FS3D_SWEEP_PART) && launch_sweep_part<float>(c, dir, p);
-        if (!ok) ok = launch_sweep_pipe<float>(c, dir, p);
+        if (part_allowed(c)) r = launch_sweep_part<float>(c, dir, p);
+        if (r == Launch::NA) r = launch_sweep_pipe<float>(c, dir, p);
     } else {
         SweepParams<double> p; fill_params<double>(c, p, dir, dt, c->slot[l_cur], c->slot[l_temp], c->slot[l_next], c->spare, 1);
-        p.stamps = c->stamps; ok = launch_sweep_pipe<double>(c, dir, p);
+        p.stamps = c->stamps; r = launch_sweep_pipe<double>(c, dir, p);
     }
-    if (!ok) return fail(c, FS3D_ERR_UNSUPPORTED, "fs3d_profile_sweep: pipelined kernel does not support these dims");
+    if (r == Launch::FAILED) return launch_failed(c, "fs3d_profile_sweep");
+    if (r == Launch::NA) return fail(c, FS3D_ERR_UNSUPPORTED, "fs3d_profile_sweep: pipelined kernel does not support these dims");
     HIPCHK(c, hipGetLastError());
     const int nout = nb < max_blocks ? nb : max_blocks;
     HIPCHK(c, hipMemcpyAsync(stamps_out, c->stamps, sizeof(unsigned long long) * 64 * (size_t)nout, hipMemcpyDeviceToHost, c->stream));
@@ -1030,11 +1051,10 @@ extern "C" fs3d_status fs3d_profile_sweep(fs3d_ctx *c, int dir, double dt, int l
 template <typename R>
 static fs3d_status merge_buffers(fs3d_ctx *c, int b_src, int b_dest)
 {
-    rec_begin(c, 4);
+    RecScope rec(c, 4);
     hipLaunchKernelGGL((k_merge<R>), dim3(grid_for(c->ncell, 256)), dim3(256), 0, c->stream, c->code, c->ncell,
                        fld<R>(c, b_src, 0), fld<R>(c, b_src, 1), fld<R>(c, b_src, 2), fld<R>(c, b_src, 3),
                        fld<R>(c, b_dest, 0), fld<R>(c, b_dest, 1), fld<R>(c, b_dest, 2), fld<R>(c, b_dest, 3));
-    rec_end(c);
     HIPCHK(c, hipGetLastError());
     return FS3D_OK;
 }
@@ -1044,7 +1064,7 @@ static fs3d_status update_boundaries_impl(fs3d_ctx *c, bool also_next = false)
 {
     if (!c->n_bnd) return FS3D_OK;
     const int b = c->slot[FS3D_LAYER_CUR];
-    rec_begin(c, 6);
+    RecScope rec(c, 6);
     if (also_next) {
         const int bn = c->slot[FS3D_LAYER_NEXT];
         hipLaunchKernelGGL((k_impose_list2<R>), dim3((c->n_bnd + 255) / 256), dim3(256), 0, c->stream, c->bnd_idx, c->n_bnd,
@@ -1054,7 +1074,6 @@ static fs3d_status update_boundaries_impl(fs3d_ctx *c, bool also_next = false)
     hipLaunchKernelGGL((k_impose_list<R>), dim3((c->n_bnd + 255) / 256), dim3(256), 0, c->stream, c->bnd_idx, c->n_bnd,
                        (const R *)c->bnd_val[0], (const R *)c->bnd_val[1], (const R *)c->bnd_val[2], (const R *)c->bnd_val[3],
                        fld<R>(c, b, 0), fld<R>(c, b, 1), fld<R>(c, b, 2), fld<R>(c, b, 3));
-    rec_end(c);
     HIPCHK(c, hipGetLastError());
     return FS3D_OK;
 }
@@ -1081,7 +1100,7 @@ static fs3d_status div_error_enqueue(fs3d_ctx *c, int layer)
             return fail(c, FS3D_ERR_UNSUPPORTED, "FS3D_OPT_ERR_ORDER = 1 (the CPU path's summation order) is implemented for a single context only");
         if (!c->err_terms) HIPCHK(c, hipMalloc((void **)&c->err_terms, (size_t)c->ncell * sizeof(double)));
     }
-    rec_begin(c, 5);
+    RecScope rec(c, 5);
     hipLaunchKernelGGL((k_div_error<R>), dim3(c->red_blocks), dim3(256), 0, c->stream, c->code,
                        (const R *)fld<R>(c, b, 0), (const R *)fld<R>(c, b, 1), (const R *)fld<R>(c, b, 2),
                        c->dimx, c->dimy, c->dimz, i_end, c->x_offset == 0 ? 1 : 0, (R)c->gdx, (R)c->gdy, (R)c->gdz, c->red_buf + 2,
@@ -1092,7 +1111,6 @@ static fs3d_status div_error_enqueue(fs3d_ctx *c, int layer)
                            (const R *)fld<R>(c, b, 0), (const R *)fld<R>(c, b, 1), (const R *)fld<R>(c, b, 2),
                            c->dimx, c->dimy, c->dimz, (R)c->gdx, (R)c->gdy, (R)c->gdz, c->err_terms);
     }
-    rec_end(c);
     HIPCHK(c, hipGetLastError());
     return FS3D_OK;
 }
@@ -1183,20 +1201,20 @@ static fs3d_status time_step_enqueue(fs3d_ctx *c, double dt, int G, int L, bool 
     fs3d_status st;
     // :310-311  cur -> next on NODE_BOUND and NODE_VALVE
     if (c->n_bnd && !bnd_copied) {
-        rec_begin(c, 3);
+        RecScope rec(c, 3);
         hipLaunchKernelGGL((k_copy_list<R>), dim3((c->n_bnd + 255) / 256), dim3(256), 0, c->stream, c->bnd_idx, c->n_bnd,
                            (const R *)fld<R>(c, bCur, 0), (const R *)fld<R>(c, bCur, 1), (const R *)fld<R>(c, bCur, 2), (const R *)fld<R>(c, bCur, 3),
                            fld<R>(c, bNext, 0), fld<R>(c, bNext, 1), fld<R>(c, bNext, 2), fld<R>(c, bNext, 3));
-        rec_end(c);
     }
     const bool fuse = c->opt_fuse && L >= 1 && G >= 1;
     if (!fuse) {
         // :320 cur->CopyLayerTo(temp)
-        rec_begin(c, 3);
-        for (int v = 0; v < 4; v++)
-            HIPCHK(c, hipMemcpyAsync(fld<R>(c, c->slot[FS3D_LAYER_TEMP], v), fld<R>(c, bCur, v), (size_t)c->ncell * sizeof(R),
-                                     hipMemcpyDeviceToDevice, c->stream));
-        rec_end(c);
+        {
+            RecScope rec(c, 3);
+            for (int v = 0; v < 4; v++)
+                HIPCHK(c, hipMemcpyAsync(fld<R>(c, c->slot[FS3D_LAYER_TEMP], v), fld<R>(c, bCur, v), (size_t)c->ncell * sizeof(R),
+                                         hipMemcpyDeviceToDevice, c->stream));
+        }
         for (int it = 0; it < G; it++) {
             const int bT = c->slot[FS3D_LAYER_TEMP];
             const int plan[3][3] = {{2, bCur, bNext}, {1, bNext, bHalf}, {0, bHalf, bNext}};   // :338, :342, :343

@@ -11,20 +11,11 @@
 // + 4 (temp again) + 8 (out) = 32 words/cell against the 16-word algorithmic figure.
 #include "fs3d_rows.h"
 
+// Forward elimination over the n cells base, base + stride, ... of a line: c'(2) and d'(4) of every cell to the scratch.
+// cp_v, cp_t, dp: the recurrence's state before the first cell (zeros, or the carries of the slab below) and after the last.
 template <typename R, int DIR>
-__global__ void __launch_bounds__(256) k_sweep_line(SweepParams<R> p)
+__device__ __forceinline__ void line_forward(const SweepParams<R> &p, long long base, long long stride, int n, R &cp_v, R &cp_t, R (&dp)[4])
 {
-    const long long tid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    long long nlines, base, stride;
-    int n;
-    if (DIR == 0) { nlines = p.plane; base = tid; stride = p.plane; n = p.dimx; }
-    else if (DIR == 1) {
-        nlines = (long long)p.dimx * p.dimz;
-        base = (tid / p.dimz) * p.plane + (tid % p.dimz); stride = p.dimz; n = p.dimy;
-    } else { nlines = (long long)p.dimx * p.dimy; base = tid * p.dimz; stride = 1; n = p.dimz; }
-    if (tid >= nlines) return;
-
-    R cp_v = R(0), cp_t = R(0), dp[4] = {R(0), R(0), R(0), R(0)};
     for (int s = 0; s < n; s++) {
         const long long idx = base + s * stride;
         const int code = (p.code[idx] >> (4 * DIR)) & 0xF;
@@ -36,8 +27,13 @@ __global__ void __launch_bounds__(256) k_sweep_line(SweepParams<R> p)
         p.scr(0)[idx] = cp_v; p.scr(1)[idx] = cp_t;
         p.scr(2)[idx] = dp[0]; p.scr(3)[idx] = dp[1]; p.scr(4)[idx] = dp[2]; p.scr(5)[idx] = dp[3];
     }
-    // back-substitution: x[n-1] = d'[n-1]; x[i] = d'[i] - c'[i]*x[i+1]
-    R x[4] = {R(0), R(0), R(0), R(0)};
+}
+
+// Back-substitution over the same cells in reverse: x[n-1] = d'[n-1]; x[i] = d'[i] - c'[i]*x[i+1], scattered into `next` and
+// merged into temp.  x: the values of the cell behind the last one (zeros, or those of the slab above) and, after, of the first.
+template <typename R, int DIR>
+__device__ __forceinline__ void line_backward(const SweepParams<R> &p, long long base, long long stride, int n, R (&x)[4])
+{
     for (int s = n - 1; s >= 0; s--) {
         const long long idx = base + s * stride;
         const int cw = p.code[idx];
@@ -68,6 +64,25 @@ __global__ void __launch_bounds__(256) k_sweep_line(SweepParams<R> p)
             }
         }
     }
+}
+
+template <typename R, int DIR>
+__global__ void __launch_bounds__(256) k_sweep_line(SweepParams<R> p)
+{
+    const long long tid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    long long nlines, base, stride;
+    int n;
+    if (DIR == 0) { nlines = p.plane; base = tid; stride = p.plane; n = p.dimx; }
+    else if (DIR == 1) {
+        nlines = (long long)p.dimx * p.dimz;
+        base = (tid / p.dimz) * p.plane + (tid % p.dimz); stride = p.dimz; n = p.dimy;
+    } else { nlines = (long long)p.dimx * p.dimy; base = tid * p.dimz; stride = 1; n = p.dimz; }
+    if (tid >= nlines) return;
+
+    R cp_v = R(0), cp_t = R(0), dp[4] = {R(0), R(0), R(0), R(0)};
+    line_forward<R, DIR>(p, base, stride, n, cp_v, cp_t, dp);
+    R x[4] = {R(0), R(0), R(0), R(0)};
+    line_backward<R, DIR>(p, base, stride, n, x);
 }
 
 template <typename R>
@@ -107,17 +122,7 @@ __global__ void __launch_bounds__(256) k_xsweep_fwd(SweepParams<R> p, const R *c
         dp[0] = carry_in[2 * nlines + tid]; dp[1] = carry_in[3 * nlines + tid];
         dp[2] = carry_in[4 * nlines + tid]; dp[3] = carry_in[5 * nlines + tid];
     }
-    for (int s = 0; s < p.dimx; s++) {
-        const long long idx = tid + s * p.plane;
-        const int code = p.code[idx] & 0xF;
-        const int kind = code & 3;
-        RowUVWT<R> r;
-        if (kind == ROW_INTERIOR) build_interior_row<R, 0>(p, idx, r);
-        else if (kind != ROW_SKIP) build_bc_row<R>(p, idx, code, r);
-        thomas_forward<R>(kind, r, cp_v, cp_t, dp);
-        p.scr(0)[idx] = cp_v; p.scr(1)[idx] = cp_t;
-        p.scr(2)[idx] = dp[0]; p.scr(3)[idx] = dp[1]; p.scr(4)[idx] = dp[2]; p.scr(5)[idx] = dp[3];
-    }
+    line_forward<R, 0>(p, tid, p.plane, p.dimx, cp_v, cp_t, dp);
     carry_out[0 * nlines + tid] = cp_v; carry_out[1 * nlines + tid] = cp_t;
     carry_out[2 * nlines + tid] = dp[0]; carry_out[3 * nlines + tid] = dp[1];
     carry_out[4 * nlines + tid] = dp[2]; carry_out[5 * nlines + tid] = dp[3];
@@ -131,34 +136,7 @@ __global__ void __launch_bounds__(256) k_xsweep_bwd(SweepParams<R> p, const R *x
     if (tid >= l1) return;
     R x[4] = {R(0), R(0), R(0), R(0)};
     if (xcarry_in) { x[0] = xcarry_in[tid]; x[1] = xcarry_in[nlines + tid]; x[2] = xcarry_in[2 * nlines + tid]; x[3] = xcarry_in[3 * nlines + tid]; }
-    for (int s = p.dimx - 1; s >= 0; s--) {
-        const long long idx = tid + s * p.plane;
-        const int cw = p.code[idx];
-        const int kind = cw & 3;
-        const R c_v = p.scr(0)[idx], c_t = p.scr(1)[idx];
-        const R d0 = p.scr(2)[idx], d1 = p.scr(3)[idx], d2 = p.scr(4)[idx], d3 = p.scr(5)[idx];
-        if (kind == ROW_END || kind == ROW_SKIP) { x[0] = d0; x[1] = d1; x[2] = d2; x[3] = d3; }
-        else {
-            x[0] = d0 - c_v * x[0]; x[1] = d1 - c_v * x[1];
-            x[2] = d2 - c_v * x[2]; x[3] = d3 - c_t * x[3];
-        }
-        if (kind != ROW_SKIP) {
-            p.next(0)[idx] = x[0]; p.next(1)[idx] = x[1]; p.next(2)[idx] = x[2]; p.next(3)[idx] = x[3];
-        }
-        if (p.merge) {
-            const bool is_in = ((cw >> CODE_TYPE_SHIFT) & 3) == FS3D_NODE_IN;
-#pragma unroll
-            for (int v = 0; v < 4; v++) {
-                R t = p.temp(v)[idx];
-                if (is_in) {
-                    const R xv = kind != ROW_SKIP ? x[v] : p.next(v)[idx];
-                    t = (t + xv) / R(2);
-                    if (p.merge == 2) t = (t + xv) / R(2);
-                }
-                p.temp_out(v)[idx] = t;
-            }
-        }
-    }
+    line_backward<R, 0>(p, tid, p.plane, p.dimx, x);
     xcarry_out[tid] = x[0]; xcarry_out[nlines + tid] = x[1]; xcarry_out[2 * nlines + tid] = x[2]; xcarry_out[3 * nlines + tid] = x[3];
 }
 
@@ -257,6 +235,30 @@ __global__ void __launch_bounds__(256) k_xiface(SweepParams<R> p, R *out)
 }
 
 #define XREDUCE_MAXR FS3D_XREDUCE_MAX_RANKS      // larger groups: refused (explicit) / pipelined form (auto), fs3d_hip.hip
+// The R x R interface system of one line for unknown `sys` (U, V, W, T): elimination over the ranks, back-substitution from the
+// last rank down; got(r, X_r) receives every X_r as it is produced.  W(r, w): word w of rank r's 18.  The one copy of this
+// arithmetic: k_xreduce and k_xreduce_a2a give the same bits because both run it.
+template <typename R, typename WordFn, typename GotFn>
+__device__ __forceinline__ void xiface_solve(const WordFn &W, int nranks, int sys, const GotFn &got)
+{
+    const int m = sys == 3 ? 5 : 0;
+    R cp[XREDUCE_MAXR], dq[XREDUCE_MAXR];
+    R c_ = R(0), d_ = R(0);
+    for (int r = 0; r < nranks; r++) {
+        const R lo = W(r, m + 0), cl = W(r, m + 2);
+        R di = W(r, m + 1), up = R(0), rhs = W(r, 10 + sys);
+        if (r + 1 < nranks) { di = di - cl * W(r + 1, m + 3); up = -cl * W(r + 1, m + 4); rhs = rhs - cl * W(r + 1, 14 + sys); }
+        const R den = di - lo * c_;
+        c_ = up / den; d_ = (rhs - lo * d_) / den;
+        cp[r] = c_; dq[r] = d_;
+    }
+    R x = dq[nranks - 1];
+    for (int r = nranks - 1; r >= 0; r--) {
+        if (r < nranks - 1) x = dq[r] - cp[r] * x;
+        got(r, x);
+    }
+}
+
 template <typename R>
 __global__ void __launch_bounds__(256) k_xreduce(const R *all, long long nl, int nranks, int me, R *carry_in, R *xcarry_in)
 {
@@ -267,23 +269,12 @@ __global__ void __launch_bounds__(256) k_xreduce(const R *all, long long nl, int
     R xl[4], xr[4];
     for (int sys = 0; sys < 4; sys++) {
         const int m = sys == 3 ? 5 : 0;
-        R cp[XREDUCE_MAXR], dq[XREDUCE_MAXR];
-        R c_ = R(0), d_ = R(0);
-        for (int r = 0; r < nranks; r++) {
-            const R lo = W(r, m + 0), cl = W(r, m + 2);
-            R di = W(r, m + 1), up = R(0), rhs = W(r, 10 + sys);
-            if (r + 1 < nranks) { di = di - cl * W(r + 1, m + 3); up = -cl * W(r + 1, m + 4); rhs = rhs - cl * W(r + 1, 14 + sys); }
-            const R den = di - lo * c_;
-            c_ = up / den; d_ = (rhs - lo * d_) / den;
-            cp[r] = c_; dq[r] = d_;
-        }
-        R x = dq[nranks - 1], xme = R(0), xabove = R(0), xbelow = R(0);
-        for (int r = nranks - 1; r >= 0; r--) {
-            if (r < nranks - 1) x = dq[r] - cp[r] * x;
+        R xme = R(0), xabove = R(0), xbelow = R(0);
+        xiface_solve<R>(W, nranks, sys, [&](int r, R x) {
             if (r == me + 1) xabove = x;
             if (r == me) xme = x;
             if (r == me - 1) xbelow = x;
-        }
+        });
         xl[sys] = me > 0 ? xbelow : R(0);
         // the first cell of the slab above: Gf - Vf X_me - Wf X_{me+1}
         xr[sys] = me + 1 < nranks ? W(me + 1, 14 + sys) - W(me + 1, m + 3) * xme - W(me + 1, m + 4) * xabove : R(0);
@@ -301,7 +292,7 @@ __global__ void __launch_bounds__(256) k_xreduce(const R *all, long long nl, int
 //   k_xreduce_a2a  per owned line: the R x R system once, then for EVERY rank the value below / above its slab -> [rank][8][line]
 //   all-to-all #2  the 8 boundary words per line back to the rank they belong to                 ((R-1)/R x 8 words per line)
 //   k_xunpack      blocks [owner][8][line] -> the carry layout of the slab solve
-// Same operations on the same values as k_xreduce: bit-identical to the all-gather form (tests/test_gpu_slabs.py).
+// The same xiface_solve as k_xreduce: bit-identical to the all-gather form (tests/test_gpu_slabs.py).
 template <typename R>
 __global__ void __launch_bounds__(256) k_xpack(const R *in, long long nl, long long lp, R *out)
 {
@@ -322,21 +313,8 @@ __global__ void __launch_bounds__(256) k_xreduce_a2a(const R *all, long long nl,
     auto W = [&](int r, int w) { return all[r * rs + w * lp + t]; };
     for (int sys = 0; sys < 4; sys++) {
         const int m = sys == 3 ? 5 : 0;
-        R cp[XREDUCE_MAXR], dq[XREDUCE_MAXR], X[XREDUCE_MAXR];
-        R c_ = R(0), d_ = R(0);
-        for (int r = 0; r < nranks; r++) {
-            const R lo = W(r, m + 0), cl = W(r, m + 2);
-            R di = W(r, m + 1), up = R(0), rhs = W(r, 10 + sys);
-            if (r + 1 < nranks) { di = di - cl * W(r + 1, m + 3); up = -cl * W(r + 1, m + 4); rhs = rhs - cl * W(r + 1, 14 + sys); }
-            const R den = di - lo * c_;
-            c_ = up / den; d_ = (rhs - lo * d_) / den;
-            cp[r] = c_; dq[r] = d_;
-        }
-        R x = dq[nranks - 1];
-        for (int r = nranks - 1; r >= 0; r--) {
-            if (r < nranks - 1) x = dq[r] - cp[r] * x;
-            X[r] = x;
-        }
+        R X[XREDUCE_MAXR];
+        xiface_solve<R>(W, nranks, sys, [&](int r, R x) { X[r] = x; });
         for (int r = 0; r < nranks; r++) {
             const R xl = r > 0 ? X[r - 1] : R(0);
             const R xr = r + 1 < nranks ? W(r + 1, 14 + sys) - W(r + 1, m + 3) * X[r] - W(r + 1, m + 4) * X[r + 1] : R(0);

@@ -193,6 +193,14 @@ __device__ __forceinline__ void part_step_vt(R lead_v, R diag_v, R trail_v, R le
 // X / Y sweeps
 // ------------------------------------------------------------------------------------------------------------
 #define PART_EXW 18               // interface words per (line, chunk): 5 per matrix, 2 per right-hand side
+// LDS of one workgroup of k_sweep_part in elements of R, for the kernel's pointers and part_launch_xy's byte count:
+//   [NCH*M][LT] dT of every cell | [EXW][NCH][LT] the interface words, and behind them the c' of the four interface systems
+//   where 32 chunks do not fit the registers
+template <int M, int NCH, int LT>
+struct PartLds {
+    static constexpr int EXW = PART_EXW + (NCH > 16 ? 4 : 0);
+    static constexpr size_t EX = (size_t)NCH * M * LT, ELEMS = EX + (size_t)EXW * NCH * LT;
+};
 
 // order: bit 0 = tile order (below); 0x40 = late start, delay in bits 8+ (part_launch_xy)
 // launch bound: fp32 four waves per SIMD (128 VGPRs), fp64 two (256 VGPRs: at 128 the double instances spill ~550 bytes per lane)
@@ -205,7 +213,7 @@ __global__ void __launch_bounds__(LT * NCH, sizeof(R) == 8 ? 2 : 4) k_sweep_part
     extern __shared__ __attribute__((aligned(16))) unsigned char part_smem[];
     static_assert(LT == 16 || LT == 32 || LT == 64, "lines per workgroup");
     R *const ldsD = (R *)part_smem;                      // [NCH*M][LT]  dT of every cell (P -> E)
-    R *const ex = ldsD + NCH * M * LT;                  // [PART_EXW][NCH][LT]
+    R *const ex = ldsD + PartLds<M, NCH, LT>::EX;       // [PART_EXW (+ 4)][NCH][LT]
     const int t = threadIdx.x, kk = t % LT, ch = t / LT;
     // measurement only (fs3d_profile_sweep): 8 s_memtime stamps per wave; wave 7 stamps the constant-rate, chip-wide
     // s_memrealtime (100 MHz) instead -- s_memtime counters are not aligned between CUs
@@ -650,17 +658,17 @@ __global__ void __launch_bounds__(LT * NCH, sizeof(R) == 8 ? 2 : 4) k_sweep_part
 }
 
 template <typename R, int DIR, int M, int NCH, int LT, int XB = 0>
-static bool part_launch_xy(fs3d_ctx *c, const SweepParams<R> &p)
+static Launch part_launch_xy(fs3d_ctx *c, const SweepParams<R> &p)
 {
     const int n_o = DIR == 0 ? p.dimy : (p.o_count ? p.o_count : p.dimx);
     const int n_tiles = (p.dimz + LT - 1) / LT;
-    const size_t lds = ((size_t)NCH * M * LT + (size_t)(PART_EXW + (NCH > 16 ? 4 : 0)) * NCH * LT) * sizeof(R);
+    const size_t lds = PartLds<M, NCH, LT>::ELEMS * sizeof(R);
     static std::atomic<unsigned long long> attr_set{0};
     const unsigned long long dev_bit = 1ull << (c->device & 63);
     if (!(attr_set.load() & dev_bit)) {
         if (hipFuncSetAttribute((const void *)k_sweep_part<R, DIR, M, NCH, LT, XB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-            c->err = std::string("partition kernel: hipFuncSetAttribute: ") + hipGetErrorString(hipGetLastError());
-            return false;
+            c->err = std::string("partition kernel: hipFuncSetAttribute failed: ") + hipGetErrorString(hipGetLastError());
+            return Launch::FAILED;
         }
         attr_set.fetch_or(dev_bit);
     }
@@ -674,46 +682,41 @@ static bool part_launch_xy(fs3d_ctx *c, const SweepParams<R> &p)
     const bool late = sizeof(R) == 4 && LT <= 32 && NCH == 16 && M == 16 && (long long)n_o * n_tiles >= 1024;
     const int order = LT <= 32 ? (((long long)n_o * n_tiles < 1024 || NCH == 32) ? 1 : 0) | (late ? 0x40 | (4 << 8) : 0) : 0;
     hipLaunchKernelGGL((k_sweep_part<R, DIR, M, NCH, LT, XB>), dim3((unsigned)(n_o * n_tiles)), dim3(LT * NCH), lds, c->stream, p, n_o, n_tiles, order);
-    return true;
+    return Launch::RAN;
+}
+
+// X sweep of an x-slab (fp32).  XB = 1: the values below / above the slab are given (reduced-interface form of the cross-slab
+// sweep).  XB = 2: its first pass, the slab's interface words -- whole chunks only.
+template <typename R, int XB>
+static Launch part_dispatch_xslab(fs3d_ctx *c, const SweepParams<R> &p)
+{
+    const int n = p.dimx;
+    if (n <= 32 && (XB == 1 || n % 8 == 0)) return part_launch_xy<R, 0, 8, 4, 64, XB>(c, p);   // thin slabs (a 32-plane slab of the 256^3 box): 8-cell chunks, every thread has cells
+    if (XB == 2 && n % 16 != 0) return Launch::NA;
+    const bool wide = (long long)p.dimy * ((p.dimz + 63) / 64) >= 512;      // enough 64-line tiles to fill the chip: 256-byte row pieces
+    if (n <= 64) return wide ? part_launch_xy<R, 0, 16, 4, 64, XB>(c, p) : part_launch_xy<R, 0, 16, 4, 32, XB>(c, p);
+    if (n <= 128) return wide ? part_launch_xy<R, 0, 16, 8, 64, XB>(c, p) : part_launch_xy<R, 0, 16, 8, 32, XB>(c, p);
+    if (n <= 256) return part_launch_xy<R, 0, 16, 16, 64, XB>(c, p);
+    return Launch::NA;
 }
 
 template <typename R, int DIR>
-static bool part_dispatch_xy(fs3d_ctx *c, const SweepParams<R> &p)
+static Launch part_dispatch_xy(fs3d_ctx *c, const SweepParams<R> &p)
 {
     const int n = DIR == 0 ? p.dimx : p.dimy;
-    if (n < 4) return false;
+    if (n < 4) return Launch::NA;
     if constexpr (std::is_same<R, double>::value) {
         // fp64 (FS3D_OPT_F64_PART; launch_sweep_part lets only the single-context form through): 68 KiB of LDS per workgroup at
         // 32 lines x 8 chunks and at 16 lines x 16 chunks, 256 threads, two workgroups per CU
         if (n <= 64) return part_launch_xy<R, DIR, 16, 4, 32>(c, p);
         if (n <= 128) return part_launch_xy<R, DIR, 16, 8, 32>(c, p);
         if (n <= 256) return part_launch_xy<R, DIR, 16, 16, 16>(c, p);
-        return false;
+        return Launch::NA;
     }
     if constexpr (std::is_same<R, float>::value) {
         static const int variant = getenv("FS3D_PART_VARIANT") ? atoi(getenv("FS3D_PART_VARIANT")) : 0;   // 16 / 32 / 64 lines per workgroup: same chunks, same arithmetic, same bits (tested)
-        if (DIR == 0 && p.xiface_pass) {
-            // first pass of the cross-slab sweep: the slab's interface words (whole chunks only)
-            constexpr int D0 = 0;
-            if (!p.carry_out) return false;
-            if (n <= 32 && n % 8 == 0) return part_launch_xy<R, D0, 8, 4, 64, 2>(c, p);   // thin slabs: 8-cell chunks, every thread has cells
-            if (n % 16 != 0) return false;
-            const bool wide = (long long)p.dimy * ((p.dimz + 63) / 64) >= 512;      // enough 64-line tiles to fill the chip: 256-byte row pieces
-            if (n <= 64) return wide ? part_launch_xy<R, D0, 16, 4, 64, 2>(c, p) : part_launch_xy<R, D0, 16, 4, 32, 2>(c, p);
-            if (n <= 128) return wide ? part_launch_xy<R, D0, 16, 8, 64, 2>(c, p) : part_launch_xy<R, D0, 16, 8, 32, 2>(c, p);
-            if (n <= 256) return part_launch_xy<R, D0, 16, 16, 64, 2>(c, p);
-            return false;
-        }
-        if (DIR == 0 && p.carry_in && p.xcarry_in) {
-            // x-slab with the values below / above it given (reduced-interface form of the cross-slab sweep)
-            constexpr int D0 = 0;
-            if (n <= 32) return part_launch_xy<R, D0, 8, 4, 64, 1>(c, p);      // thin slabs (a 32-plane slab of the 256^3 box)
-            const bool wide = (long long)p.dimy * ((p.dimz + 63) / 64) >= 512;      // enough 64-line tiles to fill the chip: 256-byte row pieces
-            if (n <= 64) return wide ? part_launch_xy<R, D0, 16, 4, 64, 1>(c, p) : part_launch_xy<R, D0, 16, 4, 32, 1>(c, p);
-            if (n <= 128) return wide ? part_launch_xy<R, D0, 16, 8, 64, 1>(c, p) : part_launch_xy<R, D0, 16, 8, 32, 1>(c, p);
-            if (n <= 256) return part_launch_xy<R, D0, 16, 16, 64, 1>(c, p);
-            return false;
-        }
+        if (DIR == 0 && p.xiface_pass) return p.carry_out ? part_dispatch_xslab<R, 2>(c, p) : Launch::NA;
+        if (DIR == 0 && p.carry_in && p.xcarry_in) return part_dispatch_xslab<R, 1>(c, p);
         if (n <= 64) return part_launch_xy<R, DIR, 16, 4, 32>(c, p);
         if (n <= 128) return part_launch_xy<R, DIR, 16, 8, 32>(c, p);
         if (n <= 256) {
@@ -730,7 +733,7 @@ static bool part_dispatch_xy(fs3d_ctx *c, const SweepParams<R> &p)
         }
         if (n <= 512) return part_launch_xy<R, DIR, 16, 32, 32>(c, p);
     }
-    return false;
+    return Launch::NA;
 }
 
 
@@ -1163,7 +1166,7 @@ __global__ void __launch_bounds__(256, 2) k_sweep_part_z(SweepParams<R> p, int n
 }
 
 template <typename R, int LPL, int NW = 1>
-static bool part_launch_z(fs3d_ctx *c, const SweepParams<R> &p)
+static Launch part_launch_z(fs3d_ctx *c, const SweepParams<R> &p)
 {
     constexpr int LI = 64 / LPL;
     const int rows = (p.dimy + LI - 1) / LI;              // rows of LI lines per plane
@@ -1177,36 +1180,36 @@ static bool part_launch_z(fs3d_ctx *c, const SweepParams<R> &p)
     const long long tasks = (long long)n_grp * npl;
     const int tpw = NW == 2 ? 2 : 4;                      // tasks per workgroup of four waves
     hipLaunchKernelGGL((k_sweep_part_z<R, LPL, NW>), dim3((unsigned)((tasks + tpw - 1) / tpw)), dim3(256), 0, c->stream, p, n_grp, LG);
-    return true;
+    return Launch::RAN;
 }
 
 template <typename R>
-static bool part_dispatch_z(fs3d_ctx *c, const SweepParams<R> &p)
+static Launch part_dispatch_z(fs3d_ctx *c, const SweepParams<R> &p)
 {
     constexpr int C = 16 / sizeof(R);
     const int n = p.dimz;
-    if (n % C != 0 || n < 8) return false;                // whole 16-byte pieces
-    if (p.dimy < 4) return false;
+    if (n % C != 0 || n < 8) return Launch::NA;                // whole 16-byte pieces
+    if (p.dimy < 4) return Launch::NA;
     if (n <= 16 * C) return part_launch_z<R, 16>(c, p);
     if (n <= 32 * C) return part_launch_z<R, 32>(c, p);
     if (n <= 64 * C) return part_launch_z<R, 64>(c, p);
     if (n <= 128 * C) return part_launch_z<R, 64, 2>(c, p);   // a pair of waves per line
-    return false;
+    return Launch::NA;
 }
 
-// false: dims / precision / slab configuration not covered -> the caller falls back to the exact kernels
+// NA: dims / precision / slab configuration not covered -> the caller falls back to the exact kernels
 template <typename R>
-bool launch_sweep_part(fs3d_ctx *c, int dir, const SweepParams<R> &p)
+Launch launch_sweep_part(fs3d_ctx *c, int dir, const SweepParams<R> &p)
 {
-    if ((unsigned long long)p.fstride * 4ull * sizeof(R) >= (1ull << 32)) return false;   // 32-bit buffer offsets span a layer
+    if ((unsigned long long)p.fstride * 4ull * sizeof(R) >= (1ull << 32)) return Launch::NA;   // 32-bit buffer offsets span a layer
     // fp64: only where the context asks for it (FS3D_OPT_F64_PART), and only the single-context form -- no sweep of a slab
     // (a group's rank, ghost planes, a range of planes beside the halo exchange, either pass of the cross-slab X sweep)
     if (std::is_same<R, double>::value &&
-        (!c->opt_f64_part || c->nranks > 1 || p.ghost_lo || p.ghost_hi || p.o_begin || p.o_count || p.xiface_pass || p.carry_in || p.xcarry_in)) return false;
-    if (dir == 0 && (p.ghost_lo || p.ghost_hi) && !(p.carry_in && p.xcarry_in) && !p.xiface_pass) return false;   // X sweep of an x-slab: only with the values below / above the slab given
+        (!c->opt_f64_part || c->nranks > 1 || p.ghost_lo || p.ghost_hi || p.o_begin || p.o_count || p.xiface_pass || p.carry_in || p.xcarry_in)) return Launch::NA;
+    if (dir == 0 && (p.ghost_lo || p.ghost_hi) && !(p.carry_in && p.xcarry_in) && !p.xiface_pass) return Launch::NA;   // X sweep of an x-slab: only with the values below / above the slab given
     if (dir == 0) return part_dispatch_xy<R, 0>(c, p);
     if (dir == 1) return part_dispatch_xy<R, 1>(c, p);
     return part_dispatch_z(c, p);
 }
-template bool launch_sweep_part<float>(fs3d_ctx *, int, const SweepParams<float> &);
-template bool launch_sweep_part<double>(fs3d_ctx *, int, const SweepParams<double> &);
+template Launch launch_sweep_part<float>(fs3d_ctx *, int, const SweepParams<float> &);
+template Launch launch_sweep_part<double>(fs3d_ctx *, int, const SweepParams<double> &);

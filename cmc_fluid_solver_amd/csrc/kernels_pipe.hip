@@ -363,6 +363,26 @@ struct Chunk {
     }
 };
 
+// LDS of one workgroup of k_sweep_pipe, in elements of R from the start of the dynamic segment (the flags: ints behind
+// FLAGS).  The kernel takes its pointers from here and the launcher its byte count:
+//   [NW*CH][64] d_T / d'_T | [NW*CH][64] c'_T | per-wave transposition tiles | relay | fflag | bflag | live
+// Transposition tiles (Z sweep, P and O phases): a tile must not overlap the c'_T rows of ANOTHER wave -- wave w starts
+// writing its own c'_T rows in its forward turn while later waves may still be building rows.  If a tile fits into the
+// wave's own c'_T row range it lives there, otherwise the tiles get a region of their own behind the c'_T rows.
+template <typename R, int DIR, int CH, int NW>
+struct PipeLds {
+    static constexpr int NPIECE = Chunk<R, DIR, CH, NW>::NPASS;
+    static constexpr size_t ROWS = (size_t)NW * CH * 64;
+    static constexpr size_t TILE = Chunk<R, DIR, CH, NW>::TILE_ELEMS;
+    static constexpr bool TILE_IN_ROWS = TILE <= (size_t)CH * 64;
+    static constexpr size_t D = 0, C = ROWS;
+    static constexpr size_t TILES = TILE_IN_ROWS ? C : C + ROWS, TILE_PITCH = TILE_IN_ROWS ? (size_t)CH * 64 : TILE;   // wave w: TILES + w * TILE_PITCH
+    static constexpr size_t RELAY = C + ROWS + (TILE_IN_ROWS ? 0 : (size_t)NW * TILE);
+    static constexpr size_t FLAGS = RELAY + 8 * 64;
+    static constexpr int N_FFLAG = 4 * NPIECE * NW, N_BFLAG = NPIECE * NW, N_LIVE = 2 * NW;
+    static constexpr size_t BYTES = FLAGS * sizeof(R) + (size_t)(N_FFLAG + N_BFLAG + N_LIVE) * sizeof(int);
+};
+
 // one workgroup = one bundle
 // FM (fp32 only): divide with the scaling-free core; a workgroup that met an operand outside the core's range
 // raises redo[bundle] and the FM = false instance, launched right behind with the same arguments, computes that
@@ -404,23 +424,16 @@ __global__ void __launch_bounds__(NW * 64, 2) k_sweep_pipe(SweepParams<R> p, int
     const bool hi_edge = lane == 63 || l + 1 >= la_len;     // right lane neighbour not in this wave
     const bool lo_edge = lane == 0;
 
-    // LDS: [NW*CH][64] d_T / d'_T | [NW*CH][64] c'_T (P and O phases: per-wave transposition tiles) | relay
-    constexpr size_t LDS_D = (size_t)NW * CH * 64;
-    // Per-wave transposition tiles (Z sweep, P and O phases).  A tile must not overlap the c'_T rows of
-    // ANOTHER wave: wave w starts writing its own c'_T rows in its forward turn while later waves may
-    // still be building rows.  If a tile fits into the wave's own c'_T row range it lives there,
-    // otherwise the tiles get a region of their own behind the c'_T rows.
-    constexpr size_t TILE = Chunk<R, DIR, CH, NW>::TILE_ELEMS;
-    constexpr bool TILE_IN_ROWS = TILE <= (size_t)CH * 64;
-    constexpr size_t LDS_C = (size_t)NW * CH * 64 + (TILE_IN_ROWS ? 0 : (size_t)NW * TILE);
-    R *ldsD = (R *)smem_raw;
-    R *ldsC = ldsD + LDS_D;
-    R *relay = ldsC + LDS_C;                                // 8 x 64 forward (c', d' per pass), reused 4 x 64 backward
-    constexpr int NPIECE = Chunk<R, DIR, CH, NW>::NPASS;        // pieces per wave; relay step (h, w) = piece h of wave w
-    volatile int *fflag = (volatile int *)(relay + 8 * 64); // [4 passes][NPIECE][NW]: forward pass k of step (h, w) is done
-    volatile int *bflag = fflag + 4 * NPIECE * NW;     // [NPIECE][NW]: backward step (h, w) is done
-    volatile int *live_lds = bflag + NPIECE * NW;      // [NW][2]: lanes whose line has a solved or merged cell among the wave's cells
-    if (threadIdx.x < 5 * NPIECE * NW) ((lds_flag_t *)fflag)[threadIdx.x] = 0;
+    typedef PipeLds<R, DIR, CH, NW> LDS;
+    R *const lds = (R *)smem_raw;
+    R *ldsD = lds + LDS::D;
+    R *ldsC = lds + LDS::C;
+    R *relay = lds + LDS::RELAY;                            // 8 x 64 forward (c', d' per pass), reused 4 x 64 backward
+    constexpr int NPIECE = LDS::NPIECE;                     // pieces per wave; relay step (h, w) = piece h of wave w
+    volatile int *fflag = (volatile int *)(lds + LDS::FLAGS);   // [4 passes][NPIECE][NW]: forward pass k of step (h, w) is done
+    volatile int *bflag = fflag + LDS::N_FFLAG;             // [NPIECE][NW]: backward step (h, w) is done
+    volatile int *live_lds = bflag + LDS::N_BFLAG;          // [NW][2]: lanes whose line has a solved or merged cell among the wave's cells
+    if (threadIdx.x < LDS::N_FFLAG + LDS::N_BFLAG) ((lds_flag_t *)fflag)[threadIdx.x] = 0;
     const FlagCtl fctl = {p.errw, p.test_drop ? (1 << 10) : (1 << 22)};
     __syncthreads();                                        // the only workgroup-wide barrier of the kernel
     // The relay visits the waves in order, so the low waves are needed first: give them the issue slots first.
@@ -450,7 +463,7 @@ __global__ void __launch_bounds__(NW * 64, 2) k_sweep_pipe(SweepParams<R> p, int
     }
     ck.dimz = p.dimz;
     ck.rows_valid = la_len - tile_id * 64 < 64 ? la_len - tile_id * 64 : 64;
-    ck.tile = TILE_IN_ROWS ? ldsC + (size_t)w * CH * 64 : ldsC + (size_t)NW * CH * 64 + (size_t)w * TILE;
+    ck.tile = lds + LDS::TILES + (size_t)w * LDS::TILE_PITCH;
     const int s0 = w * CH;                                      // first row of this wave in the LDS arrays (storage order, not line order)
     const bool lane_valid = ck.lane_valid;
     // this thread's column of the c'_T / d_T arrays: cell t of the chunk is at myX[t * 64] (immediate DS offsets)
@@ -987,76 +1000,29 @@ __global__ void __launch_bounds__(NW * 64, 2) k_sweep_pipe(SweepParams<R> p, int
     if (!FM && redo && threadIdx.x == 0) redo[blockIdx.x] = 0;   // handled: the flags are all zero again for the next sweep
 }
 
-template <typename R, int DIR, int CH>
-static bool launch_one(fs3d_ctx *c, const SweepParams<R> &p)
+// ---- host side ----------------------------------------------------------------------------------------------
+template <typename R> constexpr int PIPE_MAX_CH = std::is_same<R, float>::value ? 32 : 16;   // cells per wave that 128 VGPRs hold
+
+// 32-bit buffer offsets span a layer
+template <typename R> static bool pipe_addressable(const SweepParams<R> &p) { return (unsigned long long)p.fstride * 4ull * sizeof(R) < (1ull << 32); }
+
+static Launch pipe_failed(fs3d_ctx *c, const char *what)
 {
-    const int la_len = DIR == 2 ? p.dimy : p.dimz;
-    const int n_o = DIR == 0 ? p.dimy : p.dimx;
-    const int n_tiles = (la_len + 63) / 64;
-    if (DIR == 2 && p.dimz % Chunk<R, DIR, CH>::VW != 0) return false;   // Z moves whole 16-byte row pieces
-    const size_t tile = Chunk<R, DIR, CH>::TILE_ELEMS;
-    const size_t lds_c = (size_t)PIPE_NW * CH * 64 + (tile <= (size_t)CH * 64 ? 0 : (size_t)PIPE_NW * tile);
-    const size_t lds = ((size_t)PIPE_NW * CH * 64 + lds_c + 8 * 64) * sizeof(R) + (5 * Chunk<R, DIR, CH>::NPASS + 2) * PIPE_NW * sizeof(int);
-    const int grid = n_o * n_tiles;
-    constexpr bool HAS_FM = std::is_same<R, float>::value;
-    // the attribute is per device: one bit per device id (several devices can be driven from one process)
-    static std::atomic<unsigned long long> attr_set{0};
-    const unsigned long long dev_bit = 1ull << (c->device & 63);
-    if (!(attr_set.load() & dev_bit)) {
-        if (hipFuncSetAttribute((const void *)k_sweep_pipe<R, DIR, CH, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return false;
-        if (HAS_FM && hipFuncSetAttribute((const void *)k_sweep_pipe<R, DIR, CH, HAS_FM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return false;
-        attr_set.fetch_or(dev_bit);
-    }
-    if (HAS_FM && p.fast_div) {
-        // division core first; the full-division instance right behind it redoes the bundles that asked for it
-        if (c->redo_cap < grid) {
-            if (c->redo) { hipStreamSynchronize(c->stream); hipFree(c->redo); c->redo = nullptr; c->redo_cap = 0; }
-            if (hipMalloc(&c->redo, (size_t)grid * sizeof(int)) != hipSuccess) return false;
-            if (hipMemsetAsync(c->redo, 0, (size_t)grid * sizeof(int), c->stream) != hipSuccess) return false;
-            c->redo_cap = grid;
-        }
-        hipLaunchKernelGGL((k_sweep_pipe<R, DIR, CH, HAS_FM>), dim3((unsigned)grid), dim3(PIPE_NW * 64), lds, c->stream, p, n_o, n_tiles, c->redo);
-        hipLaunchKernelGGL((k_sweep_pipe<R, DIR, CH, false>), dim3((unsigned)grid), dim3(PIPE_NW * 64), lds, c->stream, p, n_o, n_tiles, c->redo);
-    } else {
-        hipLaunchKernelGGL((k_sweep_pipe<R, DIR, CH, false>), dim3((unsigned)grid), dim3(PIPE_NW * 64), lds, c->stream, p, n_o, n_tiles, (int *)nullptr);
-    }
+    c->err = std::string("pipe kernel: ") + what + " failed: " + hipGetErrorString(hipGetLastError());
+    return Launch::FAILED;
+}
+
+// per-bundle "compute again with full divisions" flags (fp32) for n bundles, all zero between sweeps; grows only
+static bool ensure_redo(fs3d_ctx *c, int n)
+{
+    if (c->redo_cap >= n) return true;
+    if (c->redo) { hipStreamSynchronize(c->stream); hipFree(c->redo); c->redo = nullptr; c->redo_cap = 0; }
+    if (hipMalloc(&c->redo, (size_t)n * sizeof(int)) != hipSuccess) return false;
+    if (hipMemsetAsync(c->redo, 0, (size_t)n * sizeof(int), c->stream) != hipSuccess) return false;
+    c->redo_cap = n;
     return true;
 }
 
-template <typename R, int CH>
-static bool launch_dir(fs3d_ctx *c, int dir, const SweepParams<R> &p)
-{
-    switch (dir) {
-    case 0: return launch_one<R, 0, CH>(c, p);
-    case 1: return launch_one<R, 1, CH>(c, p);
-    default: return launch_one<R, 2, CH>(c, p);
-    }
-}
-
-// false: the line is longer than NW*CH cells for every instantiated CH -> caller falls back to the LINE kernel
-template <>
-bool launch_sweep_pipe<float>(fs3d_ctx *c, int dir, const SweepParams<float> &p)
-{
-    const int n = dir == 0 ? p.dimx : (dir == 1 ? p.dimy : p.dimz);
-    if ((unsigned long long)p.fstride * 4ull * sizeof(float) >= (1ull << 32)) return false;   // 32-bit buffer offsets span a layer
-    if (n <= PIPE_NW * 16) return launch_dir<float, 16>(c, dir, p);
-    if (n <= PIPE_NW * 32) return launch_dir<float, 32>(c, dir, p);
-    return false;
-}
-
-template <>
-bool launch_sweep_pipe<double>(fs3d_ctx *c, int dir, const SweepParams<double> &p)
-{
-    const int n = dir == 0 ? p.dimx : (dir == 1 ? p.dimy : p.dimz);
-    if ((unsigned long long)p.fstride * 4ull * sizeof(double) >= (1ull << 32)) return false;
-    if (n <= PIPE_NW * 16) return launch_dir<double, 16>(c, dir, p);
-    return false;
-}
-
-// ---- sweep halves: X sweep of an x-slab (cross-slab pipeline, fs3d_hip.hip: xsweep_multi) and the segments of
-// ---- lines longer than one launch holds on chip (launch_sweep_pipe_segmented) ------------------------------
 // the context's scratch, at least `elems` elements of R (shared with the thread-per-line kernel, which needs 6 per cell)
 template <typename R>
 static bool pipe_scratch(fs3d_ctx *c, size_t elems)
@@ -1069,90 +1035,100 @@ static bool pipe_scratch(fs3d_ctx *c, size_t elems)
     return true;
 }
 
-template <typename R, int DIR, int CH, int NW = PIPE_NW>
-static bool launch_half(fs3d_ctx *c, SweepParams<R> p, int half, int b0, int b1)
+// MODE 0: the whole sweep, every bundle.  MODE 1 / 2: forward / backward half of the bundles [b0, b1) -- the X sweep of an
+// x-slab (cross-slab pipeline, fs3d_hip.hip: xsweep_multi) or one segment of lines longer than a launch holds on chip
+// (run_segments); the caller has put the scratch into p.
+template <typename R, int DIR, int CH, int MODE, int NW = PIPE_NW>
+static Launch launch_pipe(fs3d_ctx *c, SweepParams<R> p, int b0 = 0, int b1 = 0)
 {
-    constexpr bool HAS_FM = std::is_same<R, float>::value;
+    typedef PipeLds<R, DIR, CH, NW> LDS;
+    constexpr bool HAS_FM = std::is_same<R, float>::value && MODE != 2;      // the backward half has no division to speed up
     const int la_len = DIR == 2 ? p.dimy : p.dimz;
-    const int n_o = DIR == 0 ? p.dimy : p.dimx, n_tiles = (la_len + 63) / 64, grid = b1 - b0;
-    if (DIR == 2 && p.dimz % Chunk<R, DIR, CH, NW>::VW != 0) { c->err = "pipe halves: dimz is not a multiple of the 16-byte vector"; return false; }
-    const size_t tile = Chunk<R, DIR, CH, NW>::TILE_ELEMS;
-    const size_t lds_c = (size_t)NW * CH * 64 + (tile <= (size_t)CH * 64 ? 0 : (size_t)NW * tile);
-    const size_t lds = ((size_t)NW * CH * 64 + lds_c + 8 * 64) * sizeof(R) + (5 * Chunk<R, DIR, CH, NW>::NPASS + 2) * NW * sizeof(int);
+    const int n_o = DIR == 0 ? p.dimy : p.dimx, n_tiles = (la_len + 63) / 64;
+    const int grid = MODE == 0 ? n_o * n_tiles : b1 - b0;
+    if (DIR == 2 && p.dimz % Chunk<R, DIR, CH, NW>::VW != 0) { c->err = "pipe kernel: dimz is not a multiple of the 16-byte vector"; return Launch::NA; }   // Z moves whole 16-byte row pieces
     // the attribute is per device: one bit per device id (several devices can be driven from one process)
     static std::atomic<unsigned long long> attr_set{0};
     const unsigned long long dev_bit = 1ull << (c->device & 63);
     if (!(attr_set.load() & dev_bit)) {
-        if (hipFuncSetAttribute((const void *)k_sweep_pipe<R, DIR, CH, false, 1, NW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) { c->err = std::string("pipe halves: hipFuncSetAttribute: ") + hipGetErrorString(hipGetLastError()); return false; }
-        if (hipFuncSetAttribute((const void *)k_sweep_pipe<R, DIR, CH, false, 2, NW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return false;
-        if (HAS_FM && hipFuncSetAttribute((const void *)k_sweep_pipe<R, DIR, CH, HAS_FM, 1, NW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return false;
+        if (hipFuncSetAttribute((const void *)k_sweep_pipe<R, DIR, CH, false, MODE, NW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS::BYTES) != hipSuccess ||
+            (HAS_FM && hipFuncSetAttribute((const void *)k_sweep_pipe<R, DIR, CH, HAS_FM, MODE, NW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS::BYTES) != hipSuccess))
+            return pipe_failed(c, "hipFuncSetAttribute");
         attr_set.fetch_or(dev_bit);
     }
-    if (grid <= 0) return true;
-    p.bundle0 = b0;
-    if (!p.scr_ || p.scr_bundles < b1) { c->err = "pipe halves: scratch not prepared"; return false; }
-    if (half == 1) {
-        if (HAS_FM && p.fast_div) {
-            if (c->redo_cap < grid) {
-                if (c->redo) { hipStreamSynchronize(c->stream); hipFree(c->redo); c->redo = nullptr; c->redo_cap = 0; }
-                const int cap = std::max(grid, n_o * n_tiles);
-                if (hipMalloc(&c->redo, (size_t)cap * sizeof(int)) != hipSuccess) return false;
-                if (hipMemsetAsync(c->redo, 0, (size_t)cap * sizeof(int), c->stream) != hipSuccess) return false;
-                c->redo_cap = cap;
-            }
-            hipLaunchKernelGGL((k_sweep_pipe<R, DIR, CH, HAS_FM, 1, NW>), dim3((unsigned)grid), dim3(NW * 64), lds, c->stream, p, n_o, n_tiles, c->redo);
-            hipLaunchKernelGGL((k_sweep_pipe<R, DIR, CH, false, 1, NW>), dim3((unsigned)grid), dim3(NW * 64), lds, c->stream, p, n_o, n_tiles, c->redo);
-        } else {
-            hipLaunchKernelGGL((k_sweep_pipe<R, DIR, CH, false, 1, NW>), dim3((unsigned)grid), dim3(NW * 64), lds, c->stream, p, n_o, n_tiles, (int *)nullptr);
-        }
-    } else {
-        hipLaunchKernelGGL((k_sweep_pipe<R, DIR, CH, false, 2, NW>), dim3((unsigned)grid), dim3(NW * 64), lds, c->stream, p, n_o, n_tiles, (int *)nullptr);
+    if (grid <= 0) return Launch::RAN;
+    if (MODE != 0) {
+        p.bundle0 = b0;
+        if (!p.scr_ || p.scr_bundles < b1) { c->err = "pipe halves: scratch not prepared"; return Launch::FAILED; }
     }
-    return true;
+    int *redo = nullptr;
+    if (HAS_FM && p.fast_div) {
+        if (!ensure_redo(c, std::max(grid, n_o * n_tiles))) return pipe_failed(c, "hipMalloc of the redo flags");
+        redo = c->redo;
+    }
+    // division core first; the full-division instance right behind it redoes the bundles that asked for it
+    if (redo) hipLaunchKernelGGL((k_sweep_pipe<R, DIR, CH, HAS_FM, MODE, NW>), dim3((unsigned)grid), dim3(NW * 64), LDS::BYTES, c->stream, p, n_o, n_tiles, redo);
+    hipLaunchKernelGGL((k_sweep_pipe<R, DIR, CH, false, MODE, NW>), dim3((unsigned)grid), dim3(NW * 64), LDS::BYTES, c->stream, p, n_o, n_tiles, redo);
+    return Launch::RAN;
 }
 
-template <> bool xslab_pipe_supported<float>(const SweepParams<float> &p)
-{
-    return p.dimz % 64 == 0 && p.dimx <= PIPE_NW * 32 && (unsigned long long)p.fstride * 4ull * sizeof(float) < (1ull << 32);
-}
-template <> bool xslab_pipe_supported<double>(const SweepParams<double> &p)
-{
-    return p.dimz % 64 == 0 && p.dimx <= PIPE_NW * 16 && (unsigned long long)p.fstride * 4ull * sizeof(double) < (1ull << 32);
-}
-// a slab piece of n planes keeps ceil(n / CH) waves busy: workgroups of 1, 2, 4 or 8 waves (small workgroups leave
-// room for several bundles per CU, which is what a thin slab needs)
 template <typename R, int CH>
-static bool launch_xslab_nw(fs3d_ctx *c, SweepParams<R> p, int half, int b0, int b1)
+static Launch launch_dir(fs3d_ctx *c, int dir, const SweepParams<R> &p)
 {
-    const int nbt = p.dimy * (p.dimz / 64);
-    const int nw = p.dimx <= CH ? 1 : (p.dimx <= 2 * CH ? 2 : (p.dimx <= 4 * CH ? 4 : 8));
-    if (!pipe_scratch<R>(c, (size_t)nbt * 6 * nw * CH * 64)) return false;
-    p.scr_ = (R *)c->scr; p.scr_bundles = nbt; p.seg_index = 0;
-    switch (nw) {
-    case 1: return launch_half<R, 0, CH, 1>(c, p, half, b0, b1);
-    case 2: return launch_half<R, 0, CH, 2>(c, p, half, b0, b1);
-    case 4: return launch_half<R, 0, CH, 4>(c, p, half, b0, b1);
-    default: return launch_half<R, 0, CH, 8>(c, p, half, b0, b1);
+    switch (dir) {
+    case 0: return launch_pipe<R, 0, CH, 0>(c, p);
+    case 1: return launch_pipe<R, 1, CH, 0>(c, p);
+    default: return launch_pipe<R, 2, CH, 0>(c, p);
     }
 }
-template <> bool launch_xslab_pipe<float>(fs3d_ctx *c, SweepParams<float> p, int half, int b0, int b1)
+
+// NA: the line is longer than NW*CH cells for every instantiated CH
+template <typename R>
+Launch launch_sweep_pipe(fs3d_ctx *c, int dir, const SweepParams<R> &p)
 {
-    if (p.dimx <= PIPE_NW * 16) return launch_xslab_nw<float, 16>(c, p, half, b0, b1);
-    const int nbt = p.dimy * (p.dimz / 64);
-    if (!pipe_scratch<float>(c, (size_t)nbt * 6 * PIPE_NW * 32 * 64)) return false;
-    p.scr_ = (float *)c->scr; p.scr_bundles = nbt; p.seg_index = 0;
-    return launch_half<float, 0, 32>(c, p, half, b0, b1);
-}
-template <> bool launch_xslab_pipe<double>(fs3d_ctx *c, SweepParams<double> p, int half, int b0, int b1)
-{
-    return launch_xslab_nw<double, 16>(c, p, half, b0, b1);
+    const int n = dir == 0 ? p.dimx : (dir == 1 ? p.dimy : p.dimz);
+    if (!pipe_addressable(p)) return Launch::NA;
+    if (n <= PIPE_NW * 16) return launch_dir<R, 16>(c, dir, p);
+    if (n <= PIPE_NW * PIPE_MAX_CH<R>) return launch_dir<R, PIPE_MAX_CH<R>>(c, dir, p);      // fp64: the same instance, never reached
+    return Launch::NA;
 }
 
-// A line of n cells, n above what one launch holds on chip (8 waves x CH cells): forward halves of the segments in
-// line order, backward halves in reverse, the carries of a segment's last / first cell in two per-line arrays that
-// each bundle reads before it overwrites them.  Cell for cell the arithmetic of the unsegmented sweep.
+// ---- sweep halves: the X sweep of an x-slab ------------------------------------------------------------------
+template <typename R> bool xslab_pipe_supported(const SweepParams<R> &p)
+{
+    return p.dimz % 64 == 0 && p.dimx <= PIPE_NW * PIPE_MAX_CH<R> && pipe_addressable(p);
+}
+
+template <typename R, int CH, int NW>
+static Launch launch_xslab_half(fs3d_ctx *c, const SweepParams<R> &p, int half, int b0, int b1)
+{
+    return half == 1 ? launch_pipe<R, 0, CH, 1, NW>(c, p, b0, b1) : launch_pipe<R, 0, CH, 2, NW>(c, p, b0, b1);
+}
+
+// a slab piece of n planes keeps ceil(n / CH) waves busy: up to 8 x 16 planes workgroups of 1, 2, 4 or 8 waves of 16 cells
+// (small workgroups leave room for several bundles per CU, which is what a thin slab needs), above that 8 waves of PIPE_MAX_CH
+template <typename R>
+Launch launch_xslab_pipe(fs3d_ctx *c, SweepParams<R> p, int half, int b0, int b1)
+{
+    const int nbt = p.dimy * (p.dimz / 64);
+    const int ch = p.dimx <= PIPE_NW * 16 ? 16 : PIPE_MAX_CH<R>;
+    const int nw = p.dimx <= 16 ? 1 : (p.dimx <= 2 * 16 ? 2 : (p.dimx <= 4 * 16 ? 4 : 8));
+    if (!pipe_scratch<R>(c, (size_t)nbt * 6 * nw * ch * 64)) return pipe_failed(c, "hipMalloc of the scratch");
+    p.scr_ = (R *)c->scr; p.scr_bundles = nbt; p.seg_index = 0;
+    if (ch != 16) return launch_xslab_half<R, PIPE_MAX_CH<R>, 8>(c, p, half, b0, b1);
+    switch (nw) {
+    case 1: return launch_xslab_half<R, 16, 1>(c, p, half, b0, b1);
+    case 2: return launch_xslab_half<R, 16, 2>(c, p, half, b0, b1);
+    case 4: return launch_xslab_half<R, 16, 4>(c, p, half, b0, b1);
+    default: return launch_xslab_half<R, 16, 8>(c, p, half, b0, b1);
+    }
+}
+
+// ---- lines longer than one launch holds on chip (8 waves x CH cells): forward halves of the segments in line order,
+// backward halves in reverse, the carries of a segment's last / first cell in two per-line arrays that each bundle reads
+// before it overwrites them.  Cell for cell the arithmetic of the unsegmented sweep.
 template <typename R, int DIR, int CH>
-static bool run_segments(fs3d_ctx *c, SweepParams<R> p)
+static Launch run_segments(fs3d_ctx *c, SweepParams<R> p)
 {
     const int n = DIR == 0 ? p.dimx : (DIR == 1 ? p.dimy : p.dimz);
     const int la_len = DIR == 2 ? p.dimy : p.dimz, n_o = DIR == 0 ? p.dimy : p.dimx;
@@ -1162,38 +1138,44 @@ static bool run_segments(fs3d_ctx *c, SweepParams<R> p)
         for (int i = 0; i < 2; i++) if (c->seg_carry[i]) { hipStreamSynchronize(c->stream); hipFree(c->seg_carry[i]); c->seg_carry[i] = nullptr; }
         // two forward carry arrays, used alternately: a bundle that asks for the full-division instance reads its carry_in
         // a second time, after the first instance has stored the segment's own carries
-        if (hipMalloc(&c->seg_carry[0], 12 * (size_t)lines * sizeof(R)) != hipSuccess) { c->err = "pipe segments: hipMalloc of the carries failed"; return false; }
-        if (hipMalloc(&c->seg_carry[1], 4 * (size_t)lines * sizeof(R)) != hipSuccess) return false;
+        if (hipMalloc(&c->seg_carry[0], 12 * (size_t)lines * sizeof(R)) != hipSuccess || hipMalloc(&c->seg_carry[1], 4 * (size_t)lines * sizeof(R)) != hipSuccess)
+            return pipe_failed(c, "hipMalloc of the segment carries");
         c->seg_carry_lines = lines;
     }
     p.carry_pitch = lines;
-    if (!pipe_scratch<R>(c, (size_t)nseg * nb * 6 * PIPE_NW * CH * 64)) { c->err = "pipe segments: hipMalloc of the scratch failed"; return false; }
+    if (!pipe_scratch<R>(c, (size_t)nseg * nb * 6 * PIPE_NW * CH * 64)) return pipe_failed(c, "hipMalloc of the segment scratch");
     p.scr_ = (R *)c->scr; p.scr_bundles = nb;
-    for (int s = 0; s < nseg; s++) {
+    Launch r = Launch::RAN;
+    for (int s = 0; s < nseg && r == Launch::RAN; s++) {
         p.seg_index = s;
         p.seg_begin = s * seg; p.seg_len = std::min(seg, n - s * seg);
         R *const fc[2] = {(R *)c->seg_carry[0], (R *)c->seg_carry[0] + 6 * lines};
         p.carry_in = s > 0 ? (const R *)fc[(s - 1) & 1] : nullptr; p.carry_out = fc[s & 1];
-        if (!launch_half<R, DIR, CH>(c, p, 1, 0, nb)) return false;
+        r = launch_pipe<R, DIR, CH, 1>(c, p, 0, nb);
     }
-    for (int s = nseg - 1; s >= 0; s--) {
+    for (int s = nseg - 1; s >= 0 && r == Launch::RAN; s--) {
         p.seg_index = s;
         p.seg_begin = s * seg; p.seg_len = std::min(seg, n - s * seg);
         p.xcarry_in = s < nseg - 1 ? (const R *)c->seg_carry[1] : nullptr; p.xcarry_out = (R *)c->seg_carry[1];
-        if (!launch_half<R, DIR, CH>(c, p, 2, 0, nb)) return false;
+        r = launch_pipe<R, DIR, CH, 2>(c, p, 0, nb);
     }
-    return true;
+    return r;
 }
 
-template <> bool launch_sweep_pipe_segmented<float>(fs3d_ctx *c, int dir, SweepParams<float> p)
+template <typename R>
+Launch launch_sweep_pipe_segmented(fs3d_ctx *c, int dir, SweepParams<R> p)
 {
-    if ((unsigned long long)p.fstride * 4ull * sizeof(float) >= (1ull << 32)) return false;
-    if (dir == 0 && (p.ghost_lo || p.ghost_hi)) return false;          // a slab's X sweep has its own path
-    return dir == 0 ? run_segments<float, 0, 32>(c, p) : (dir == 1 ? run_segments<float, 1, 32>(c, p) : run_segments<float, 2, 32>(c, p));
+    if (!pipe_addressable(p)) return Launch::NA;
+    if (dir == 0 && (p.ghost_lo || p.ghost_hi)) return Launch::NA;          // a slab's X sweep has its own path
+    constexpr int CH = PIPE_MAX_CH<R>;
+    return dir == 0 ? run_segments<R, 0, CH>(c, p) : (dir == 1 ? run_segments<R, 1, CH>(c, p) : run_segments<R, 2, CH>(c, p));
 }
-template <> bool launch_sweep_pipe_segmented<double>(fs3d_ctx *c, int dir, SweepParams<double> p)
-{
-    if ((unsigned long long)p.fstride * 4ull * sizeof(double) >= (1ull << 32)) return false;
-    if (dir == 0 && (p.ghost_lo || p.ghost_hi)) return false;
-    return dir == 0 ? run_segments<double, 0, 16>(c, p) : (dir == 1 ? run_segments<double, 1, 16>(c, p) : run_segments<double, 2, 16>(c, p));
-}
+
+template Launch launch_sweep_pipe<float>(fs3d_ctx *, int, const SweepParams<float> &);
+template Launch launch_sweep_pipe<double>(fs3d_ctx *, int, const SweepParams<double> &);
+template bool xslab_pipe_supported<float>(const SweepParams<float> &);
+template bool xslab_pipe_supported<double>(const SweepParams<double> &);
+template Launch launch_xslab_pipe<float>(fs3d_ctx *, SweepParams<float>, int, int, int);
+template Launch launch_xslab_pipe<double>(fs3d_ctx *, SweepParams<double>, int, int, int);
+template Launch launch_sweep_pipe_segmented<float>(fs3d_ctx *, int, SweepParams<float>);
+template Launch launch_sweep_pipe_segmented<double>(fs3d_ctx *, int, SweepParams<double>);
