@@ -37,6 +37,10 @@ SYMBOLS = {
     "fs3d_update_nodes_dev": (_i, [_vp] + [_vp] * 7 + [C.POINTER(_i)]),
     "fs3d_extrude_shape2d_dev": (_i, [_vp] + [_vp] * 4 + [_d] * 4 + [_vp] * 7),
     "fs3d_update_nodes_shape2d": (_i, [_vp] + [_vp] * 4 + [_d] * 4 + [C.POINTER(_i)]),
+    "fs3d_update_nodes_shape3d": (_i, [_vp] + [_vp] * 3 + [_i, _vp, _i, _d, C.POINTER(_i)]),
+    "fs3d_voxelize_shape3d_dev": (_i, [_vp] + [_vp] * 3 + [_i, _vp, _i, _d] + [_vp] * 7),
+    "fs3d_flood_fill_dev": (_i, [_vp, _vp]),
+    "fs3d_mesh_fill_rounds": (_i, [_vp, C.POINTER(_i)]),
     "fs3d_shape2d_bottom": (_i, [_i, _i, _d, _d, _d, C.POINTER(_i)]),
     "fs3d_clear_outer_cells": (_i, [_vp, _i, _d]),
     "fs3d_geometry_info": (_i, [_vp, C.POINTER(C.c_longlong)]),
@@ -220,6 +224,52 @@ class Solver:
         self._chk(self.lib.fs3d_update_nodes_shape2d(self.h, *[_p(a) for a in arrs], float(dz), float(depth), float(depth_var), float(baseT), nseg))
         self.num_segments = list(nseg)
         return self.num_segments
+
+    @staticmethod
+    def _mesh_arrays(g, idx):
+        """x, y, z (float32) and the flat index list (int32) of vertices g [n, 3] in grid coordinates and triangles idx [m, 3]."""
+        g = np.asarray(g, np.float32).reshape(-1, 3)
+        xyz = [np.ascontiguousarray(g[:, a]) for a in range(3)]
+        tri = np.ascontiguousarray(np.asarray(idx).reshape(-1), np.int32)
+        if tri.size % 3 or not np.array_equal(tri, np.asarray(idx).reshape(-1)):
+            raise ValueError("triangles: [m, 3] indices that fit an int")
+        return xyz, tri
+
+    def _dev_ptrs(self, what, arrays):
+        def ptr(a, want):
+            if isinstance(a, int):
+                return C.c_void_p(a)
+            if not a.is_cuda or not a.is_contiguous() or a.element_size() != want or a.numel() != int(np.prod(self.gdims)):
+                raise ValueError(what + ": contiguous device tensors of the grid's size and the context's precision")
+            return C.c_void_p(a.data_ptr())
+        return [ptr(a, 1) for a in arrays[:3]] + [ptr(a, self.dtype.itemsize) for a in arrays[3:]]
+
+    def voxelize_shape3d_dev(self, g, idx, baseT, type, bc_vel, bc_temp, vx, vy, vz, T):
+        """Grid3D::Build + FloodFill + the Node array on the device: the mesh (g, idx) of shape3d.Shape3D.subframe(t) voxelised into
+        seven arrays on the context's device -- torch tensors or raw pointers, as update_nodes_dev takes them.  The context's
+        geometry is not touched."""
+        ptrs = self._dev_ptrs("voxelize_shape3d_dev", [type, bc_vel, bc_temp, vx, vy, vz, T])
+        xyz, tri = self._mesh_arrays(g, idx)
+        self._chk(self.lib.fs3d_voxelize_shape3d_dev(self.h, *[_p(a) for a in xyz], len(xyz[0]), _p(tri), tri.size // 3, float(baseT), *ptrs))
+
+    def update_nodes_shape3d(self, g, idx, baseT):
+        """update_nodes with the voxelisation of the mesh (g, idx) as the source: 12 bytes per vertex travel, the node arrays are
+        written by kernels.  Same contract as update_nodes."""
+        xyz, tri = self._mesh_arrays(g, idx)
+        nseg = (C.c_int * 3)()
+        self._chk(self.lib.fs3d_update_nodes_shape3d(self.h, *[_p(a) for a in xyz], len(xyz[0]), _p(tri), tri.size // 3, float(baseT), nseg))
+        self.num_segments = list(nseg)
+        return self.num_segments
+
+    def flood_fill_dev(self, type):
+        """FloodFill alone on a device array of node types (uint8 torch tensor or raw pointer) of the context's dims, in place."""
+        self._chk(self.lib.fs3d_flood_fill_dev(self.h, self._dev_ptrs("flood_fill_dev", [type])[0]))
+
+    def mesh_fill_rounds(self):
+        """Rounds of directional passes the last flood fill on this context ran (the closing one without a change included)."""
+        n = C.c_int(0)
+        self._chk(self.lib.fs3d_mesh_fill_rounds(self.h, C.byref(n)))
+        return n.value
 
     def clear_outer_cells(self, layer, baseT):
         """Solver3D::ClearOutterCells on one layer: U, V, W := 0 and T := baseT on the NODE_OUT cells."""

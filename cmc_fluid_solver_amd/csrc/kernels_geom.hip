@@ -4,6 +4,8 @@
 // definition of every table; the kernels here end with the same tables.
 // Also the extrusion of a Shape2D grid into the node arrays on the device (k_geom_extrude; fs3d_extrude_shape2d_dev,
 // fs3d_update_nodes_shape2d): a moving Shape2D geometry then ships its 2D grid per step, not the 3D node arrays.
+// And the voxelisation of a Shape3D mesh (k_geom_raster_mesh, the flood fill k_geom_fill_z / k_geom_fill_strided, k_geom_mesh_nodes;
+// fs3d_voxelize_shape3d_dev, fs3d_flood_fill_dev, fs3d_update_nodes_shape3d): a moving mesh ships its vertices per step.
 //
 // Row kinds without the serial walk of line_kinds (fs3d_hip.hip): that walk opens a run at `pos` when cell pos + 1 is
 // NODE_IN and closes it at the first cell after the run that is not NODE_IN; a run that reaches the end of the line is
@@ -384,6 +386,248 @@ __global__ void __launch_bounds__(256) k_geom_extrude(const float *__restrict__ 
     }
 }
 
+// ---- Shape3D meshes: Grid3D::Build (Grid3D.cpp:859-903) on the device ------------------------------------------------------------
+// k_geom_raster_mesh restates RasterPolygon + ProjectPointOnPolygon + the three RasterLines of every triangle as host/Shape3D.h and
+// its twin cmc_fluid_solver_amd/shape3d.py (_raster_polygon, _raster_line) state them: every fp32 operation is the twin's, in the
+// twin's order, rounded after each one (this file is compiled without contraction and with IEEE divide and sqrt).
+// The type array is preset to NODE_IN and the ONLY write is NODE_BOUND: the result is the union of the cells every triangle
+// touches, so the order of triangles and of cells is free -- that is what makes the rasteriser parallel.  One wave per triangle:
+// the scan point p += dp accumulates rounding and is advanced serially by the whole wave, the cells of one scan line
+// (i from (int)p.x to last_i) are spread across the lanes; lanes 0..2 then walk one edge line each.
+// Guards are the twin's, not the undefined behaviour of the C++ host: a projection whose quotient is not finite or exceeds 2e9 in
+// magnitude writes nothing, writes outside the grid are dropped, a degenerate triangle (len not > 0, or the three vertices equal
+// within COMP_EPS) draws its edge lines only.  Every loop is bounded: where the twin raises (a scan line of more than
+// 4 (dimx + dimy + dimz) + 16 cells, or one that runs away from its end cell) and where it would spin (a scan point that
+// p.y += dp.y no longer moves) the wave stops its triangle and sets the flag word; the host refuses the mesh.
+#define MESH_COMP_EPS 1e-8
+#define MESH_FLAG_SCANLINE 1u
+#define MESH_FLAG_STALLED 2u
+
+struct MV2 { float x, y; };
+
+// (int) of the twin for every value it can meet; defined for any float
+__device__ __forceinline__ int mesh_int(float v) { return (int)fminf(fmaxf(v, -2.0e9f), 2.0e9f); }
+
+__device__ __forceinline__ bool mesh_close(float a, float b) { return fabs((double)(a - b)) < MESH_COMP_EPS; }
+
+// GetIntersectHorizon (Grid3D.cpp:676-685), the x of the result
+__device__ __forceinline__ float mesh_horizon_x(MV2 p1, MV2 p2, MV2 p)
+{
+    if (mesh_close(p1.y, p2.y)) return p.x;
+    return p1.x + ((p2.x - p1.x) * (p.y - p1.y)) / (p2.y - p1.y);
+}
+
+__device__ __forceinline__ void mesh_set(uint8_t *type, int i, int j, int k, int dimx, int dimy, int dimz)
+{
+    if (i >= 0 && j >= 0 && k >= 0 && i < dimx && j < dimy && k < dimz) type[((long long)i * dimy + j) * dimz + k] = FS3D_NODE_BOUND;
+}
+
+// the plane of one triangle, seen along its dominant axis: the normal's components on the two scan axes and the dominant one,
+// the sizes and strides of the three axes in that order
+struct MeshPlane { float na, nb, nd, d; int lima, limb, limd; long long sa, sb, sd; };
+
+// ProjectPointOnPolygon (Grid3D.cpp:688-707): cell (i, j) of the scan plane back onto the polygon's plane
+__device__ __forceinline__ void mesh_project(uint8_t *type, const MeshPlane &pl, int i, int j, float ty)
+{
+    const float kf = (-pl.d - ((float)i * pl.na + ty * pl.nb)) / pl.nd;
+    if (!(fabsf(kf) <= 2.0e9f)) return;                      // not finite, or no int
+    const int k = (int)kf;
+    if (k >= 0 && k < pl.limd && i >= 0 && i < pl.lima && j >= 0 && j < pl.limb) type[i * pl.sa + j * pl.sb + k * pl.sd] = FS3D_NODE_BOUND;
+}
+
+// one half of RasterPolygon's scan (the twin's _scan_half); false: the triangle is given up and the flag word set
+__device__ __forceinline__ bool mesh_scan_half(uint8_t *type, const MeshPlane &pl, MV2 &p, float yend, MV2 dp, int steps, MV2 e1, MV2 e2,
+                                               int di, long long bound, int lane, unsigned *flag)
+{
+    // a scan point that moves gains at least 2/3 of dp.y per line (round to nearest), and steps * dp.y is the half's height
+    const int max_lines = 2 * steps + 16;
+    int lines = 0;
+    while (p.y < yend) {
+        const int j = mesh_int(p.y), last_i = mesh_int(mesh_horizon_x(e1, e2, p)), i0 = mesh_int(p.x);
+        const long long cnt = ((long long)last_i - i0) * di + 1;            // cells i0, i0 + di, .., last_i
+        if (cnt < 0 || cnt > bound) { if (lane == 0) atomicOr(flag, MESH_FLAG_SCANLINE); return false; }
+        for (long long q = lane; q < cnt; q += 64) mesh_project(type, pl, i0 + (int)q * di, j, p.y);
+        const float ny = p.y + dp.y;
+        if (!(ny > p.y) || ++lines > max_lines) { if (lane == 0) atomicOr(flag, MESH_FLAG_STALLED); return false; }
+        p.x = p.x + dp.x; p.y = ny;
+    }
+    return true;
+}
+
+__global__ void __launch_bounds__(64) k_geom_raster_mesh(const float *__restrict__ vx, const float *__restrict__ vy, const float *__restrict__ vz,
+                                                          const int *__restrict__ tri, int dimx, int dimy, int dimz, uint8_t *type, unsigned *flag)
+{
+    const int lane = threadIdx.x;
+    const int i1 = tri[3 * blockIdx.x], i2 = tri[3 * blockIdx.x + 1], i3 = tri[3 * blockIdx.x + 2];
+    const float p1x = vx[i1], p1y = vy[i1], p1z = vz[i1], p2x = vx[i2], p2y = vy[i2], p2z = vz[i2], p3x = vx[i3], p3y = vy[i3], p3z = vz[i3];
+    // RasterPolygon (Grid3D.cpp:709-789), wave-uniform up to the cells of a scan line
+    const bool same = mesh_close(p1x, p2x) && mesh_close(p1y, p2y) && mesh_close(p1z, p2z) && mesh_close(p1x, p3x) && mesh_close(p1y, p3y) && mesh_close(p1z, p3z);
+    const float ax = p2x - p1x, ay = p2y - p1y, az = p2z - p1z, bx = p3x - p1x, by = p3y - p1y, bz = p3z - p1z;
+    float nx = ay * bz - az * by, ny = az * bx - ax * bz, nz = ax * by - ay * bx;
+    const float len = sqrtf((nx * nx + ny * ny) + nz * nz);
+    if (!same && len > 0) {
+        const float t = 1.0f / len;
+        nx = nx * t; ny = ny * t; nz = nz * t;
+        const float d = -((p1x * nx + p1y * ny) + p1z * nz);
+        MeshPlane pl;
+        const float fx = fabsf(nx), fy = fabsf(ny), fz = fabsf(nz), maxv = fmaxf(fx, fmaxf(fy, fz));
+        int dir = 0;
+        if (mesh_close(maxv, fy)) dir = 1;
+        if (mesh_close(maxv, fz)) dir = 2;
+        const long long plane = (long long)dimy * dimz;
+        MV2 pp1, pp2, pp3, mid;
+        if (dir == 0) { pp1 = {p1y, p1z}; pp2 = {p2y, p2z}; pp3 = {p3y, p3z}; pl = {ny, nz, nx, d, dimy, dimz, dimx, dimz, 1, plane}; }
+        else if (dir == 1) { pp1 = {p1x, p1z}; pp2 = {p2x, p2z}; pp3 = {p3x, p3z}; pl = {nx, nz, ny, d, dimx, dimz, dimy, plane, 1, dimz}; }
+        else { pp1 = {p1x, p1y}; pp2 = {p2x, p2y}; pp3 = {p3x, p3y}; pl = {nx, ny, nz, d, dimx, dimy, dimz, plane, dimz, 1}; }
+        if (pp3.y < pp2.y) { mid = pp3; pp3 = pp2; pp2 = mid; }
+        if (pp1.y > pp2.y) { mid = pp1; pp1 = pp2; pp2 = mid; }
+        if (pp3.y < pp2.y) { mid = pp3; pp3 = pp2; pp2 = mid; }
+        mid.x = mesh_horizon_x(pp1, pp3, pp2); mid.y = pp2.y;
+        const MV2 dir1 = {mid.x - pp1.x, mid.y - pp1.y}, dir2 = {pp3.x - mid.x, pp3.y - mid.y};
+        const int steps1 = mesh_int(fmaxf(fabsf(dir1.x), fabsf(dir1.y))) + 1, steps2 = mesh_int(fmaxf(fabsf(dir2.x), fabsf(dir2.y))) + 1;
+        const MV2 dp1 = {dir1.x / (float)steps1, dir1.y / (float)steps1}, dp2 = {dir2.x / (float)steps2, dir2.y / (float)steps2};
+        const int di = mid.x < pp2.x ? 1 : -1;
+        const long long bound = 4LL * ((long long)dimx + dimy + dimz) + 16;
+        MV2 p = pp1;
+        if (!mesh_scan_half(type, pl, p, mid.y, dp1, steps1, pp1, pp2, di, bound, lane, flag)) return;
+        if (!mesh_scan_half(type, pl, p, pp3.y, dp2, steps2, pp2, pp3, di, bound, lane, flag)) return;
+    }
+    // RasterLine (Grid3D.cpp:791-811) of (p1, p2), (p1, p3), (p3, p2): one lane each
+    if (lane < 3) {
+        const float sx = lane == 2 ? p3x : p1x, sy = lane == 2 ? p3y : p1y, sz = lane == 2 ? p3z : p1z;
+        const float ex = lane == 1 ? p3x : p2x, ey = lane == 1 ? p3y : p2y, ez = lane == 1 ? p3z : p2z;
+        const float dx = ex - sx, dy = ey - sy, dz = ez - sz;
+        const int steps = mesh_int(fmaxf(fabsf(dx), fmaxf(fabsf(dy), fabsf(dz)))) + 1;        // coordinates are at most 65536: 131073 steps at most
+        const float qx = dx / (float)steps, qy = dy / (float)steps, qz = dz / (float)steps;
+        float x = sx, y = sy, z = sz;
+        for (int s = 0; s <= steps; s++) {
+            mesh_set(type, mesh_int(x), mesh_int(y), mesh_int(z), dimx, dimy, dimz);
+            x = x + qx; y = y + qy; z = z + qz;
+        }
+    }
+}
+
+// FloodFill (Grid3D.cpp:813-857): NODE_OUT spreads from cell (0,0,0) through NODE_IN cells over the 6-neighbourhood.  The result is
+// the connected component of that cell, so it does not depend on the order: here as directional passes over the byte array, each
+// of which carries NODE_OUT along every line of its direction as far as the line's NODE_IN cells reach (both ways), repeated by
+// the host until a whole round of three passes changes nothing.  *cnt counts the cells a pass turns.
+__device__ __forceinline__ void fill_block_count(unsigned n, unsigned *cnt)
+{
+    __shared__ unsigned s_n;
+    if (threadIdx.x == 0) s_n = 0;
+    __syncthreads();
+    if (n) atomicAdd(&s_n, n);
+    __syncthreads();
+    if (threadIdx.x == 0 && s_n) atomicAdd(cnt, s_n);
+}
+
+// X and Y lines: one thread per line, lanes along k (the access shape of k_geom_lines_strided).  One walk: `carry` = the run of
+// cells the walk is in has met NODE_OUT; the NODE_IN cells of the run before the first NODE_OUT (from rs on) are turned when it is met.
+__global__ void __launch_bounds__(256) k_geom_fill_strided(uint8_t *type, int n_o, int dimz, long long os, long long ss, int n, unsigned *cnt)
+{
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    unsigned turned = 0;
+    if (t < (long long)n_o * dimz) {
+        const int o = (int)(t / dimz), k = (int)(t - (long long)o * dimz);
+        uint8_t *p = type + (long long)o * os + k;
+        bool carry = false;
+        int rs = 0;
+        for (int s0 = 0; s0 < n; s0 += 8) {               // 8 loads in flight: a wave per 64 lines leaves the memory latency uncovered
+            int v[8];
+#pragma unroll
+            for (int u = 0; u < 8; u++) v[u] = s0 + u < n ? p[(long long)(s0 + u) * ss] : FS3D_NODE_BOUND;
+#pragma unroll
+            for (int u = 0; u < 8; u++) {
+                const int s = s0 + u, ty = v[u];              // (the walk writes no cell it has yet to look at)
+                if (s >= n) break;
+                if (ty == FS3D_NODE_OUT) {
+                    if (!carry) { for (int q = rs; q < s; q++) p[(long long)q * ss] = FS3D_NODE_OUT; turned += s - rs; carry = true; }
+                } else if (ty == FS3D_NODE_IN) {
+                    if (carry) { p[(long long)s * ss] = FS3D_NODE_OUT; turned++; }
+                } else { carry = false; rs = s + 1; }
+            }
+        }
+    }
+    fill_block_count(turned, cnt);
+}
+
+// 64 cells of a Z line, one per lane: a segmented scan with ballots.  A lane's run reaches from the cell after the last wall below
+// it to the cell before the first wall above it; it turns when the run holds a NODE_OUT cell or touches a neighbouring chunk
+// whose end cell is NODE_OUT (from_below / from_above).  Returns the turned lanes; *ends: bit 0 / 1 = the chunk's first / last cell is NODE_OUT now.
+__device__ __forceinline__ unsigned long long fill_chunk(uint8_t *p, int k0, int dimz, int lane, bool from_below, bool from_above, int *ends)
+{
+    const int k = k0 + lane;
+    const int ty = k < dimz ? p[k] : FS3D_NODE_BOUND;                  // past the line's end: a wall
+    const unsigned long long wall = __ballot(ty != FS3D_NODE_IN && ty != FS3D_NODE_OUT), out = __ballot(ty == FS3D_NODE_OUT);
+    const unsigned long long below = wall & ((1ull << lane) - 1), above = lane == 63 ? 0ull : wall >> (lane + 1);
+    const int lo = below ? 64 - __clzll((long long)below) : 0, hi = above ? lane + __ffsll((unsigned long long)above) - 1 : 63;
+    const unsigned long long run = (hi == 63 ? ~0ull : (1ull << (hi + 1)) - 1) & ~((1ull << lo) - 1);
+    const bool src = (out & run) != 0 || (from_below && lo == 0) || (from_above && hi == 63);
+    const bool turn = ty == FS3D_NODE_IN && src;
+    if (turn) p[k] = FS3D_NODE_OUT;
+    const unsigned long long turned = __ballot(turn), now = out | turned;
+    *ends = (int)(now & 1) | (int)((now >> 63) & 1) << 1;
+    return turned;
+}
+
+// Z lines are the contiguous axis: one wave per line (the access shape of k_geom_lines_z); a line of more than 64 cells goes chunk
+// by chunk upwards with the carry of the chunk below, then downwards with the carry of the chunk above
+__global__ void __launch_bounds__(256) k_geom_fill_z(uint8_t *type, long long nlines, int dimz, unsigned *cnt)
+{
+    const long long line = ((long long)blockIdx.x * 256 + threadIdx.x) >> 6;
+    const int lane = threadIdx.x & 63;
+    unsigned turned = 0;
+    if (line < nlines) {                                               // whole waves
+        uint8_t *p = type + line * dimz;
+        const int nch = (dimz + 63) / 64;
+        int ends = 0;
+        for (int c = 0; c < nch; c++) turned += __popcll(fill_chunk(p, 64 * c, dimz, lane, (ends & 2) != 0, false, &ends));
+        if (nch > 1) {
+            ends = 0;
+            for (int c = nch - 1; c >= 0; c--) turned += __popcll(fill_chunk(p, 64 * c, dimz, lane, false, (ends & 1) != 0, &ends));
+        }
+    }
+    fill_block_count(lane == 0 ? turned : 0, cnt);
+}
+
+// The other six node arrays of a Shape3D grid from its finished type array (nodes_of in shape3d.py; FillShape3DNodes in host/Shape3D.h):
+// bc_vel = bc_temp = NOSLIP, v = 0, T = 0 on NODE_BOUND and baseT elsewhere.  Store shapes of k_geom_extrude: V == 4 cells per
+// thread with one dword per byte array and 16-byte stores (dimz % 4 == 0 and the arrays aligned), V == 1 cell by cell.
+// Stateless by definition: the reference's repeated Prepare_CPU leaves T = 0 on cells that once were walls, a value nothing reads
+// after the layers have been initialised (the third stated deviation, host/Shape3D.h).
+template <typename R, int V>
+__global__ void __launch_bounds__(256) k_geom_mesh_nodes(const uint8_t *__restrict__ type, long long ncell, R baseT, uint8_t *__restrict__ bc_vel,
+                                                          uint8_t *__restrict__ bc_temp, R *__restrict__ vx, R *__restrict__ vy, R *__restrict__ vz,
+                                                          R *__restrict__ T)
+{
+    constexpr int P = 16 / sizeof(R);
+    typedef R RP __attribute__((ext_vector_type(P)));
+    const long long l = ((long long)blockIdx.x * 256 + threadIdx.x) * V;
+    if (l >= ncell) return;                                            // V == 4: ncell % 4 == 0
+    if constexpr (V == 4) {
+        const unsigned w = *(const unsigned *)(type + l);
+        __builtin_nontemporal_store(0u, (unsigned *)(bc_vel + l));
+        __builtin_nontemporal_store(0u, (unsigned *)(bc_temp + l));
+#pragma unroll
+        for (int h = 0; h < V; h += P) {
+            RP z, t;
+#pragma unroll
+            for (int q = 0; q < P; q++) { z[q] = R(0); t[q] = ((w >> (8 * (h + q))) & 0xFF) == FS3D_NODE_BOUND ? R(0) : baseT; }
+            __builtin_nontemporal_store(z, (RP *)(vx + l + h));
+            __builtin_nontemporal_store(z, (RP *)(vy + l + h));
+            __builtin_nontemporal_store(z, (RP *)(vz + l + h));
+            __builtin_nontemporal_store(t, (RP *)(T + l + h));
+        }
+    } else {
+        __builtin_nontemporal_store((uint8_t)FS3D_BC_NOSLIP, bc_vel + l);
+        __builtin_nontemporal_store((uint8_t)FS3D_BC_NOSLIP, bc_temp + l);
+        __builtin_nontemporal_store(R(0), vx + l);
+        __builtin_nontemporal_store(R(0), vy + l);
+        __builtin_nontemporal_store(R(0), vz + l);
+        __builtin_nontemporal_store(type[l] == FS3D_NODE_BOUND ? R(0) : baseT, T + l);
+    }
+}
+
 // ---------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------
@@ -401,10 +645,19 @@ static inline int geom_ng(const fs3d_ctx *c) { return (c->dimz + 31) / 32; }
 
 // Device time of an update, while fs3d_enable_timing is on: an event before the first launch of every batch and one before the
 // synchronisation that ends it (the host's work between two batches is not device time).
+static void gev_fold(fs3d_geom &g)
+{
+    for (int k = 0; k + 1 < g.ev_n; k += 2) {
+        float ms = 0;
+        if (hipEventSynchronize(g.ev[k + 1]) == hipSuccess && hipEventElapsedTime(&ms, g.ev[k], g.ev[k + 1]) == hipSuccess) g.ev_ms += ms;
+    }
+    g.ev_n = 0;
+}
 static void gev_begin(fs3d_ctx *c)
 {
     fs3d_geom &g = c->geom;
-    if (!c->timing_period || g.ev_open || g.ev_n + 2 > 16) return;
+    if (!c->timing_period || g.ev_open) return;
+    if (g.ev_n + 2 > 16) gev_fold(g);                  // (the flood fill of a mesh has one batch per look at its counters)
     for (int k = g.ev_n; k < g.ev_n + 2; k++) if (!g.ev[k] && hipEventCreate(&g.ev[k]) != hipSuccess) return;
     hipEventRecord(g.ev[g.ev_n], c->stream);
     g.ev_open = true;
@@ -416,16 +669,14 @@ static void gev_end(fs3d_ctx *c)
     hipEventRecord(g.ev[g.ev_n + 1], c->stream);
     g.ev_n += 2; g.ev_open = false;
 }
+static void gev_reset(fs3d_ctx *c) { c->geom.ev_n = 0; c->geom.ev_open = false; c->geom.ev_ms = 0; }
 static void gev_collect(fs3d_ctx *c)
 {
     fs3d_geom &g = c->geom;
     gev_end(c);
-    g.last_dev_ms = 0;
-    for (int k = 0; k + 1 < g.ev_n; k += 2) {
-        float ms = 0;
-        if (hipEventSynchronize(g.ev[k + 1]) == hipSuccess && hipEventElapsedTime(&ms, g.ev[k], g.ev[k + 1]) == hipSuccess) g.last_dev_ms += ms;
-    }
-    g.ev_n = 0;
+    gev_fold(g);
+    g.last_dev_ms = g.ev_ms;
+    g.ev_ms = 0;
 }
 
 void fs3d_geom_destroy(fs3d_ctx *c)
@@ -444,6 +695,10 @@ void fs3d_geom_destroy(fs3d_ctx *c)
     if (g.host) hipHostFree(g.host);
     if (g.ex_host) hipHostFree(g.ex_host);
     if (g.ex_dev) hipFree(g.ex_dev);
+    if (g.mesh_host) hipHostFree(g.mesh_host);
+    if (g.mesh_vert) hipFree(g.mesh_vert);
+    if (g.mesh_idx) hipFree(g.mesh_idx);
+    if (g.mesh_cnt) hipFree(g.mesh_cnt);
 }
 
 // the buffers an update keeps: allocated by the first one
@@ -671,16 +926,133 @@ static fs3d_status extrude_launch(fs3d_ctx *c, const ExtrudeIn &in, uint8_t *typ
     return FS3D_OK;
 }
 
+// ---- voxelisation of a Shape3D mesh ---------------------------------------------------------------------------------------------
+struct MeshIn { const float *x, *y, *z; int nvert; const int *tri; int ntri; double baseT; };
+
+#define MESH_FILL_BATCH 2                              // rounds of the flood fill between two looks at their counters
+enum { MC_FLAG = 0, MC_ROUND = 1, MC_WORDS = 1 + MESH_FILL_BATCH };
+
+static inline float *mesh_host_vert(const fs3d_geom &g) { return (float *)g.mesh_host; }
+static inline int *mesh_host_idx(const fs3d_geom &g) { return (int *)((float *)g.mesh_host + 3 * (size_t)g.mesh_vcap); }
+static inline unsigned *mesh_host_cnt(const fs3d_geom &g) { return (unsigned *)(mesh_host_idx(g) + 3 * (size_t)g.mesh_tcap); }
+
+// the buffers of the mesh paths, for at least nvert vertices and ntri triangles: allocated by the first call, grown by a larger mesh
+static fs3d_status mesh_prepare(fs3d_ctx *c, int nvert, int ntri)
+{
+    fs3d_geom &g = c->geom;
+    GHIP(c, hipSetDevice(c->device));
+    if (!g.mesh_cnt) GMALLOC(c, &g.mesh_cnt, MC_WORDS * sizeof(unsigned));
+    if (g.mesh_host && nvert <= g.mesh_vcap && ntri <= g.mesh_tcap) return FS3D_OK;
+    if (g.mesh_host) { hipHostFree(g.mesh_host); g.mesh_host = nullptr; }
+    gfree(c, g.mesh_vert); g.mesh_vert = nullptr;
+    gfree(c, g.mesh_idx); g.mesh_idx = nullptr;
+    g.mesh_vcap = std::max(std::max(nvert, g.mesh_vcap), 1); g.mesh_tcap = std::max(std::max(ntri, g.mesh_tcap), 1); g.mesh_ntri_dev = -1;
+    GHIP(c, hipHostMalloc(&g.mesh_host, (3 * (size_t)g.mesh_vcap + 3 * (size_t)g.mesh_tcap) * 4 + MC_WORDS * sizeof(unsigned), hipHostMallocDefault));
+    GMALLOC(c, &g.mesh_vert, 3 * (size_t)g.mesh_vcap * sizeof(float));
+    GMALLOC(c, &g.mesh_idx, 3 * (size_t)g.mesh_tcap * sizeof(int));
+    return FS3D_OK;
+}
+
+// Everything that refuses a mesh, before anything is launched; leaves the vertices (and new indices) in the pinned block.
+// *new_idx: the index list differs from the one on the device.
+static fs3d_status mesh_check(fs3d_ctx *c, const MeshIn &in, const char *name, bool *new_idx)
+{
+    fs3d_geom &g = c->geom;
+    if (in.nvert < 1 || in.ntri < 0) return gfail(c, FS3D_ERR_INVALID, std::string(name) + ": a mesh has at least one vertex and no negative number of triangles");
+    for (int q = 0; q < 3 * in.ntri; q++)
+        if (in.tri[q] < 0 || in.tri[q] >= in.nvert) return gfail(c, FS3D_ERR_INVALID, std::string(name) + ": triangle index outside the vertex list");
+    // keeps (int) defined and the line loops short
+    for (const float *a : {in.x, in.y, in.z})
+        for (int q = 0; q < in.nvert; q++)
+            if (!(std::fabs(a[q]) <= 65536.0f))
+                return gfail(c, FS3D_ERR_INVALID, std::string(name) + ": a vertex coordinate is not finite or exceeds 65536 grid cells in magnitude");
+    const fs3d_status st = mesh_prepare(c, in.nvert, in.ntri);
+    if (st) return st;
+    float *hv = mesh_host_vert(g);
+    memcpy(hv, in.x, 4 * (size_t)in.nvert); memcpy(hv + g.mesh_vcap, in.y, 4 * (size_t)in.nvert); memcpy(hv + 2 * (size_t)g.mesh_vcap, in.z, 4 * (size_t)in.nvert);
+    *new_idx = g.mesh_ntri_dev != in.ntri || memcmp(mesh_host_idx(g), in.tri, 12 * (size_t)in.ntri) != 0;
+    if (*new_idx) memcpy(mesh_host_idx(g), in.tri, 12 * (size_t)in.ntri);
+    return FS3D_OK;
+}
+
+// FloodFill on a device type array, on the context's stream; returns synchronised.  with_flag: the rasteriser ran before on the
+// same counters -- its flag word comes back with the first batch of rounds.  An event pair is open on entry and on (successful) return.
+static fs3d_status mesh_fill(fs3d_ctx *c, uint8_t *type, bool with_flag, const char *name)
+{
+    fs3d_geom &g = c->geom;
+    const int dx = c->dimx, dy = c->dimy, dz = c->dimz;
+    unsigned *hc = mesh_host_cnt(g);
+    GHIP(c, hipMemsetAsync(type, FS3D_NODE_OUT, 1, c->stream));      // cell (0,0,0), whatever it was
+    g.mesh_fill_rounds = 0;
+    // no cap on the rounds: one that changes nothing ends the fill, every other one turns at least one cell
+    for (bool first = true;; first = false) {
+        GHIP(c, hipMemsetAsync(g.mesh_cnt + MC_ROUND, 0, MESH_FILL_BATCH * sizeof(unsigned), c->stream));
+        for (int r = 0; r < MESH_FILL_BATCH; r++) {
+            unsigned *cnt = g.mesh_cnt + MC_ROUND + r;
+            hipLaunchKernelGGL(k_geom_fill_z, dim3(geom_grid((long long)dx * dy * 64, 1 << 30)), dim3(256), 0, c->stream, type, (long long)dx * dy, dz, cnt);
+            hipLaunchKernelGGL(k_geom_fill_strided, dim3(geom_grid((long long)dx * dz, 1 << 30)), dim3(256), 0, c->stream, type, dx, dz,
+                               c->plane, (long long)dz, dy, cnt);
+            hipLaunchKernelGGL(k_geom_fill_strided, dim3(geom_grid((long long)dy * dz, 1 << 30)), dim3(256), 0, c->stream, type, dy, dz,
+                               (long long)dz, c->plane, dx, cnt);
+        }
+        GHIP(c, hipGetLastError());
+        GHIP(c, hipMemcpyAsync(hc, g.mesh_cnt, MC_WORDS * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+        gev_end(c);
+        GHIP(c, hipStreamSynchronize(c->stream));
+        if (first && with_flag && hc[MC_FLAG])
+            return gfail(c, FS3D_ERR_INVALID, std::string(name) + (hc[MC_FLAG] & MESH_FLAG_SCANLINE
+                         ? ": Shape3D: a scan line of a polygon never reaches its end cell (the reference loops there)"
+                         : ": Shape3D: the scan of a polygon stops advancing (its triangle is too thin for fp32 at these coordinates; the reference loops there)"));
+        bool done = false;
+        for (int r = 0; r < MESH_FILL_BATCH && !done; r++) { g.mesh_fill_rounds++; done = hc[MC_ROUND + r] == 0; }
+        gev_begin(c);
+        if (done) return FS3D_OK;
+    }
+}
+
+// vertices (and new indices) to the device, raster, fill and node kernels into the seven arrays, on the context's stream; the
+// node kernel is not waited for
+template <typename R>
+static fs3d_status mesh_launch(fs3d_ctx *c, const MeshIn &in, bool new_idx, const char *name, uint8_t *type, uint8_t *bc_vel, uint8_t *bc_temp,
+                               void *vx, void *vy, void *vz, void *T)
+{
+    fs3d_geom &g = c->geom;
+    GHIP(c, hipMemcpyAsync(g.mesh_vert, g.mesh_host, 3 * (size_t)g.mesh_vcap * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if (new_idx) {
+        g.mesh_ntri_dev = -1;
+        GHIP(c, hipMemcpyAsync(g.mesh_idx, mesh_host_idx(g), 12 * (size_t)std::max(in.ntri, 1), hipMemcpyHostToDevice, c->stream));
+        g.mesh_ntri_dev = in.ntri;
+    }
+    GHIP(c, hipMemsetAsync(type, FS3D_NODE_IN, (size_t)c->ncell, c->stream));
+    GHIP(c, hipMemsetAsync(g.mesh_cnt, 0, sizeof(unsigned), c->stream));
+    if (in.ntri)
+        hipLaunchKernelGGL(k_geom_raster_mesh, dim3((unsigned)in.ntri), dim3(64), 0, c->stream, g.mesh_vert, g.mesh_vert + g.mesh_vcap,
+                           g.mesh_vert + 2 * (size_t)g.mesh_vcap, g.mesh_idx, c->dimx, c->dimy, c->dimz, type, g.mesh_cnt + MC_FLAG);
+    GHIP(c, hipGetLastError());
+    const fs3d_status st = mesh_fill(c, type, true, name);
+    if (st) return st;
+    uintptr_t mis = ((uintptr_t)type | (uintptr_t)bc_vel | (uintptr_t)bc_temp) & 3;
+    mis |= ((uintptr_t)vx | (uintptr_t)vy | (uintptr_t)vz | (uintptr_t)T) & 15;
+    const bool vec = c->dimz % 4 == 0 && !mis;
+    auto kern = vec ? k_geom_mesh_nodes<R, 4> : k_geom_mesh_nodes<R, 1>;
+    hipLaunchKernelGGL(kern, dim3(geom_grid(vec ? c->ncell / 4 : c->ncell, 1 << 30)), dim3(256), 0, c->stream, type, c->ncell, (R)(float)in.baseT,
+                       bc_vel, bc_temp, (R *)vx, (R *)vy, (R *)vz, (R *)T);
+    GHIP(c, hipGetLastError());
+    return FS3D_OK;
+}
+
 static bool geom_is_slab(const fs3d_ctx *c) { return c->dimx != c->dimx_global || c->x_offset != 0 || c->comm || c->local || c->nranks > 1; }
 
-// ex != nullptr: the seven arrays come from the extrusion kernel (fs3d_update_nodes_shape2d)
+// ex != nullptr: the seven arrays come from the extrusion kernel (fs3d_update_nodes_shape2d); mesh != nullptr: from the
+// voxelisation kernels (fs3d_update_nodes_shape3d)
 static fs3d_status update_nodes_common(fs3d_ctx *c, bool host_arrays, const uint8_t *type, const uint8_t *bc_vel, const uint8_t *bc_temp,
                                        const void *vx, const void *vy, const void *vz, const void *T, int n_seg_out[3],
-                                       const ExtrudeIn *ex = nullptr)
+                                       const ExtrudeIn *ex = nullptr, const MeshIn *mesh = nullptr)
 {
-    const char *name = ex ? "fs3d_update_nodes_shape2d" : host_arrays ? "fs3d_update_nodes" : "fs3d_update_nodes_dev";
+    const char *name = mesh ? "fs3d_update_nodes_shape3d" : ex ? "fs3d_update_nodes_shape2d" : host_arrays ? "fs3d_update_nodes" : "fs3d_update_nodes_dev";
     if (!c) return FS3D_ERR_INVALID;
-    if (ex ? (!ex->cell || !ex->velx || !ex->vely || !ex->T) : (!type || !bc_vel || !bc_temp || !vx || !vy || !vz || !T))
+    if (mesh ? (!mesh->x || !mesh->y || !mesh->z || !mesh->tri)
+             : ex ? (!ex->cell || !ex->velx || !ex->vely || !ex->T) : (!type || !bc_vel || !bc_temp || !vx || !vy || !vz || !T))
         return gfail(c, FS3D_ERR_INVALID, std::string(name) + ": NULL array");
     if (geom_is_slab(c))
         return gfail(c, FS3D_ERR_UNSUPPORTED, std::string(name) + ": moving geometry is implemented for a single context only, "
@@ -696,21 +1068,30 @@ static fs3d_status update_nodes_common(fs3d_ctx *c, bool host_arrays, const uint
         st = extrude_check(c, exin, name);
         if (st) return st;
     }
+    bool new_idx = false;
+    if (mesh) {
+        st = mesh_check(c, *mesh, name, &new_idx);
+        if (st) return st;
+    }
     // rebuilt in place: from here until the end the context has no geometry
     c->have_nodes = false;
-    st = geom_prepare(c, host_arrays || ex);
+    st = geom_prepare(c, host_arrays || ex || mesh);
     if (st) return st;
     const void *val[4] = {vx, vy, vz, T};
-    c->geom.ev_n = 0; c->geom.ev_open = false;
+    gev_reset(c);
     gev_begin(c);
-    if (ex) {
+    if (ex || mesh) {
         // the three byte arrays into the staging buffer, the four value fields straight into the node-value table
         uint8_t *sg = c->geom.stage;
         char *nv[4];
         for (int v = 0; v < 4; v++) { nv[v] = (char *)c->node + (size_t)v * c->nstride * c->esize; val[v] = nv[v]; }
-        st = c->prec == FS3D_F32 ? extrude_launch<float>(c, exin, sg, sg + c->ncell, sg + 2 * c->ncell, nv[0], nv[1], nv[2], nv[3])
-                                 : extrude_launch<double>(c, exin, sg, sg + c->ncell, sg + 2 * c->ncell, nv[0], nv[1], nv[2], nv[3]);
-        if (st) return st;
+        if (mesh)
+            st = c->prec == FS3D_F32 ? mesh_launch<float>(c, *mesh, new_idx, name, sg, sg + c->ncell, sg + 2 * c->ncell, nv[0], nv[1], nv[2], nv[3])
+                                     : mesh_launch<double>(c, *mesh, new_idx, name, sg, sg + c->ncell, sg + 2 * c->ncell, nv[0], nv[1], nv[2], nv[3]);
+        else
+            st = c->prec == FS3D_F32 ? extrude_launch<float>(c, exin, sg, sg + c->ncell, sg + 2 * c->ncell, nv[0], nv[1], nv[2], nv[3])
+                                     : extrude_launch<double>(c, exin, sg, sg + c->ncell, sg + 2 * c->ncell, nv[0], nv[1], nv[2], nv[3]);
+        if (st) { hipStreamSynchronize(c->stream); gev_collect(c); return st; }
         type = sg; bc_vel = sg + c->ncell; bc_temp = sg + 2 * c->ncell;
     } else if (host_arrays) {
         const uint8_t *src[3] = {type, bc_vel, bc_temp};
@@ -770,6 +1151,61 @@ extern "C" fs3d_status fs3d_extrude_shape2d_dev(fs3d_ctx *c, const uint8_t *cell
                              : extrude_launch<double>(c, in, type_out, bc_vel_out, bc_temp_out, vx_out, vy_out, vz_out, T_out);
     if (st) return st;
     GHIP(c, hipStreamSynchronize(c->stream));
+    return FS3D_OK;
+}
+
+extern "C" fs3d_status fs3d_update_nodes_shape3d(fs3d_ctx *c, const float *x, const float *y, const float *z, int nvert, const int *tri, int ntri,
+                                                 double baseT, int n_seg_out[3])
+{
+    const MeshIn in = {x, y, z, nvert, tri, ntri, baseT};
+    return update_nodes_common(c, false, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, n_seg_out, nullptr, &in);
+}
+
+extern "C" fs3d_status fs3d_voxelize_shape3d_dev(fs3d_ctx *c, const float *x, const float *y, const float *z, int nvert, const int *tri, int ntri,
+                                                 double baseT, uint8_t *type_out, uint8_t *bc_vel_out, uint8_t *bc_temp_out, void *vx_out,
+                                                 void *vy_out, void *vz_out, void *T_out)
+{
+    const char *name = "fs3d_voxelize_shape3d_dev";
+    if (!c) return FS3D_ERR_INVALID;
+    if (!x || !y || !z || !tri || !type_out || !bc_vel_out || !bc_temp_out || !vx_out || !vy_out || !vz_out || !T_out)
+        return gfail(c, FS3D_ERR_INVALID, std::string(name) + ": NULL array");
+    if (geom_is_slab(c))
+        return gfail(c, FS3D_ERR_UNSUPPORTED, std::string(name) + ": the voxelisation is implemented for a single context only, "
+                     "not for an x-slab of a larger grid or a member of a multi-GPU group");
+    const MeshIn in = {x, y, z, nvert, tri, ntri, baseT};
+    bool new_idx = false;
+    fs3d_status st = mesh_check(c, in, name, &new_idx);
+    if (st) return st;
+    gev_reset(c);                                        // (no update: its device time is not reported)
+    st = c->prec == FS3D_F32 ? mesh_launch<float>(c, in, new_idx, name, type_out, bc_vel_out, bc_temp_out, vx_out, vy_out, vz_out, T_out)
+                             : mesh_launch<double>(c, in, new_idx, name, type_out, bc_vel_out, bc_temp_out, vx_out, vy_out, vz_out, T_out);
+    const hipError_t e = hipStreamSynchronize(c->stream);
+    gev_reset(c);
+    if (st) return st;
+    GHIP(c, e);
+    return FS3D_OK;
+}
+
+extern "C" fs3d_status fs3d_flood_fill_dev(fs3d_ctx *c, uint8_t *type_inout)
+{
+    const char *name = "fs3d_flood_fill_dev";
+    if (!c) return FS3D_ERR_INVALID;
+    if (!type_inout) return gfail(c, FS3D_ERR_INVALID, std::string(name) + ": NULL array");
+    if (geom_is_slab(c))
+        return gfail(c, FS3D_ERR_UNSUPPORTED, std::string(name) + ": the flood fill is implemented for a single context only, "
+                     "not for an x-slab of a larger grid or a member of a multi-GPU group");
+    fs3d_status st = mesh_prepare(c, 0, 0);
+    if (st) return st;
+    gev_reset(c);
+    st = mesh_fill(c, type_inout, false, name);
+    gev_reset(c);
+    return st;
+}
+
+extern "C" fs3d_status fs3d_mesh_fill_rounds(fs3d_ctx *c, int *rounds_out)
+{
+    if (!c || !rounds_out) return FS3D_ERR_INVALID;
+    *rounds_out = c->geom.mesh_fill_rounds;
     return FS3D_OK;
 }
 

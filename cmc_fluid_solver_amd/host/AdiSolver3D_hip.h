@@ -107,6 +107,16 @@ public:
         if (g2.dimx != grid_->dimx || g2.dimy != grid_->dimy) throw std::runtime_error("UpdateGridExtruded: the 2D grid does not have the 3D grid's dims");
         chk(fs3d_update_nodes_shape2d(ctx_, g2.cell.data(), g2.velx.data(), g2.vely.data(), g2.T.data(), dz, depth, depth_var, grid_->baseT, numSegs));
     }
+    // The same for the grid of a Shape3D mesh (Grid3D::Prepare3D_Shape, Grid3D.cpp:905-946): the sub-frame's vertices in grid
+    // coordinates (Shape3D::SubFrame(t), host/Shape3D.h) and the triangle indices travel, the mesh is voxelised and flood-filled on
+    // the device.  As with UpdateGridExtruded the host Grid3D given to Init is NOT kept current: its dims and baseT are read.
+    void UpdateGridShape3D(const std::vector<float> &x, const std::vector<float> &y, const std::vector<float> &z, const std::vector<int> &idx)
+    {
+        if (x.size() != y.size() || x.size() != z.size()) throw std::runtime_error("UpdateGridShape3D: x, y, z differ in length");
+        static const int none = 0;
+        chk(fs3d_update_nodes_shape3d(ctx_, x.data(), y.data(), z.data(), (int)x.size(), idx.empty() ? &none : idx.data(), (int)(idx.size() / 3),
+                                      grid_->baseT, numSegs));
+    }
     // Solver3D::ClearOutterCells (Solver3D.cpp:41-44), on `next` as there and on `cur`: a cell that turns NODE_IN with the next
     // geometry starts from (0, 0, 0, baseT) in both
     void ClearOutterCells()

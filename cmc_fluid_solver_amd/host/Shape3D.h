@@ -6,7 +6,7 @@
 //                                               (Grid3D.cpp:676-946)
 // File: frames; per frame: vertices, per vertex "x y z  vx vy vz", triangles, 3 indices each.  Frame duration 1/75 s; the
 // cycle length of a Shape3D run is Config::frame_time and GetFrame is always 0 (Grid3D.cpp:303-336).
-// Deviations, on purpose:
+// Deviations, on purpose (a third one, of the moving loop, stands at FillShape3DNodes below):
 //   * NODE_BOUND cells: the reference sets only their type; bc_vel / bc_temp keep whatever `new Node[]` left there
 //     (Grid3D.cpp:351-371, 818-838: SetData runs for NODE_IN / NODE_OUT only).  Here they read as zero-filled memory:
 //     BC_NOSLIP for both, v = 0, T = 0 (Init's values).
@@ -111,8 +111,10 @@ struct Shape3D {
 
     int GetFramesNum() const { return (int)frames.size(); }
 
-    // Grid3D::Prepare3D_Shape(time): ComputeSubframeInfo(frame, substep) + Build
-    void Prepare(double time)
+    // ComputeSubframeInfo(frame, substep) and the interpolation of Grid3D::Prepare3D_Shape(time) (Grid3D.cpp:905-946): the vertices of
+    // the mesh at `time`, in grid coordinates; returns the frame whose triangles the sub-frame has.  This is what changes with time:
+    // fs3d_update_nodes_shape3d takes these vertices and frames[frame].idx
+    size_t SubFrame(double time, std::vector<float> &x, std::vector<float> &y, std::vector<float> &z) const
     {
         const size_t nf = frames.size();
         std::vector<double> a(nf + 1, 0.0);
@@ -122,13 +124,19 @@ struct Shape3D {
         for (size_t i = 1; i < nf; i++) if (a[i] < r) frame = i;
         const float s = (float)((r - a[frame]) / (a[frame + 1] - a[frame])), is = 1 - s;
         const Shape3DFrame &f0 = frames[frame], &f1 = frames[(frame + 1) % nf];
-        Shape3DFrame sub;
-        sub.idx = f0.idx;
         const size_t nv = f0.x.size();
-        sub.x.resize(nv); sub.y.resize(nv); sub.z.resize(nv);
+        x.resize(nv); y.resize(nv); z.resize(nv);
         for (size_t k = 0; k < nv; k++) {
-            sub.x[k] = mix(f0.x[k], is, f1.x[k], s); sub.y[k] = mix(f0.y[k], is, f1.y[k], s); sub.z[k] = mix(f0.z[k], is, f1.z[k], s);
+            x[k] = mix(f0.x[k], is, f1.x[k], s); y[k] = mix(f0.y[k], is, f1.y[k], s); z[k] = mix(f0.z[k], is, f1.z[k], s);
         }
+        return frame;
+    }
+
+    // Grid3D::Prepare3D_Shape(time): SubFrame + Build
+    void Prepare(double time)
+    {
+        Shape3DFrame sub;
+        sub.idx = frames[SubFrame(time, sub.x, sub.y, sub.z)].idx;
         Build(sub);
     }
 
@@ -238,6 +246,21 @@ private:
     }
 };
 
+// The Node array of the grid `sh` holds: Init's values, then Build's SetData(.., baseT) on NODE_IN / NODE_OUT cells only.
+// Third deviation, of a moving run: this is a function of the current grid alone.  The reference's repeated Prepare_CPU(t) keeps
+// T = 0 on every cell that once was a wall (Build never writes a NODE_BOUND cell's T and Init runs once); the Node T of a fluid
+// cell is read by nothing after the layers have been initialised, so no result differs.
+template <typename FTYPE>
+void FillShape3DNodes(Grid3D<FTYPE> &g, const Shape3D &sh, double baseT)
+{
+    for (size_t c = 0; c < sh.type.size(); c++) {
+        g.type[c] = sh.type[c];
+        g.bc_vel[c] = BC_NOSLIP; g.bc_temp[c] = BC_NOSLIP;
+        g.vx[c] = 0; g.vy[c] = 0; g.vz[c] = 0;
+        g.T[c] = sh.type[c] == NODE_BOUND ? (FTYPE)0 : (FTYPE)(float)baseT;     // Init: T = 0; Build: SetData(.., baseT) on NODE_IN / NODE_OUT only
+    }
+}
+
 // Grid3D(dx,dy,dz,baseT) + LoadFromFile + Prepare_CPU(0) for a Shape3D input (FluidSolver3D.cpp:121-145)
 template <typename FTYPE>
 void LoadShape3D(Grid3D<FTYPE> &g, Shape3D &sh, const std::string &path, double dx, double dy, double dz, double baseT, bool align)
@@ -245,12 +268,7 @@ void LoadShape3D(Grid3D<FTYPE> &g, Shape3D &sh, const std::string &path, double 
     sh.Load(path, dx, dy, dz, align);
     g.Resize(sh.dimx, sh.dimy, sh.dimz);
     g.dx = dx; g.dy = dy; g.dz = dz; g.baseT = baseT;
-    for (size_t c = 0; c < sh.type.size(); c++) {
-        g.type[c] = sh.type[c];
-        g.bc_vel[c] = BC_NOSLIP; g.bc_temp[c] = BC_NOSLIP;
-        g.vx[c] = 0; g.vy[c] = 0; g.vz[c] = 0;
-        g.T[c] = sh.type[c] == NODE_BOUND ? (FTYPE)0 : (FTYPE)(float)baseT;     // Init: T = 0; Build: SetData(.., baseT) on NODE_IN / NODE_OUT only
-    }
+    FillShape3DNodes(g, sh, baseT);
 }
 
 }  // namespace fs3d

@@ -1,5 +1,5 @@
 // Command-line driver: the reference's FluidSolver3D main (FluidSolver3D/FluidSolver3D.cpp:60-330) on top of
-// libfs3d_hip.so.   fs3d_run <input data> <output prefix> <config> [align] [GPU [n]] [double] [moving [--host-extrusion] [--time-geometry]] [--steps N] [--same-device] [--grid-only FILE [--grid-time T]]
+// libfs3d_hip.so.   fs3d_run <input data> <output prefix> <config> [align] [GPU [n]] [double] [moving [--host-extrusion] [--time-geometry]] [moving-mesh [--host-voxels] [--time-geometry] [--time-both]] [--steps N] [--same-device] [--grid-only FILE [--grid-time T]]
 //   * reads the config (host/Config.h) and a Shape2D, Shape3D or SeaNetCDF geometry (host/Shape2D.h, Shape3D.h, SeaNetCDF.h), prints the grid summary lines
 //     the reference prints ("Grid = X x Y x Z", "NODE_IN points = ..."),
 //   * runs the same loop: dt = cycle length / (frames * time_steps), UpdateBoundaries + TimeStep per step with the
@@ -14,10 +14,19 @@
 //   --host-extrusion: the extrusion on the host (ExtrudeShape2D into the Grid3D, then UpdateGrid with its seven arrays) -- the same
 //   results bit for bit; kept for A/B timing and as the checker of the device extrusion.
 //   --time-geometry: one more line after the timing table, the host clock per step around Prepare, the host extrusion and the update call.
+// `moving-mesh` (single GPU, in_fmt Shape3D): the same loop for a triangle mesh per frame -- per step Shape3D::SubFrame(t) (the
+//   interpolation of Grid3D::Prepare3D_Shape, Grid3D.cpp:905-946), then the voxelisation, the flood fill and CreateSegments on the
+//   device (UpdateGridShape3D: the vertices travel).  The frame counter of the progress line stays 0, as Grid3D::GetFrame gives it
+//   for a Shape3D input.  `moving` keeps its meaning: Shape2D inputs only.
+//   --host-voxels: Shape3D::Prepare(t) on the host (rasteriser and flood fill), then UpdateGrid with the seven arrays -- the same
+//   results bit for bit; kept for A/B timing and as the checker of the device voxeliser.
+//   --time-both: a measurement run -- every step makes the geometry through BOTH paths, the word's own last (same tables either way),
+//   and one more line gives, per call after 3 warm-up steps, median (min - max) of the host clock around each path, the device
+//   time of the device path (fs3d_last_update_device_ms), and the host clock around UpdateBoundaries + TimeStep, synchronised.
 // There is no CPU backend here: without a GPU the run stops with the library's error.
 // --grid-only FILE: build the grid, dump it (dims, type, bc_vel, bc_temp, vx, vy, vz, T as raw arrays) and exit
 //   without touching the GPU -- used by the CPU tests to compare the C++ loader with its Python twin.
-//   --grid-time T: the grid the moving loop uses at time T (load, Prepare(T), extrude again) instead of the one of time 0.
+//   --grid-time T: the grid the moving loop uses at time T (Shape2D: load, Prepare(T), extrude again; Shape3D: Prepare(T)) instead of the one of time 0.
 #include <algorithm>
 #include <chrono>
 #include <condition_variable>
@@ -54,13 +63,18 @@ static int run_slabs(const fs3d::Grid3D<FTYPE> &grid, const RunGeom &geo, const 
 
 template <typename FTYPE>
 static int run(const std::string &data, const std::string &prefix, const fs3d::Config &cfg, bool align, int device, long max_steps, const std::string &grid_only, bool csv,
-               int nslabs, bool same_device, bool grid_images, bool moving, double grid_time, bool host_extrusion, bool time_geometry)
+               int nslabs, bool same_device, bool grid_images, bool moving, double grid_time, bool host_extrusion, bool time_geometry, bool moving_mesh, bool host_voxels, bool time_both)
 {
     if (moving && cfg.in_fmt != "Shape2D") throw std::runtime_error("moving: only in_fmt Shape2D inputs move (this one is " + cfg.in_fmt + ")");
     if (moving && nslabs > 1) throw std::runtime_error("moving: single GPU only (moving geometry on x-slabs is not implemented)");
     if (host_extrusion && !moving) throw std::runtime_error("--host-extrusion: only with moving (it selects where a moving geometry is extruded)");
-    if (time_geometry && !moving) throw std::runtime_error("--time-geometry: only with moving (it times the per-step geometry work)");
-    if (grid_time >= 0 && cfg.in_fmt != "Shape2D") throw std::runtime_error("--grid-time: only in_fmt Shape2D inputs move");
+    if (moving_mesh && cfg.in_fmt != "Shape3D") throw std::runtime_error("moving-mesh: only in_fmt Shape3D inputs are meshes (this one is " + cfg.in_fmt + "; Shape2D inputs move with `moving`)");
+    if (moving_mesh && nslabs > 1) throw std::runtime_error("moving-mesh: single GPU only (moving geometry on x-slabs is not implemented)");
+    if (moving_mesh && moving) throw std::runtime_error("moving-mesh: not together with moving");
+    if (host_voxels && !moving_mesh) throw std::runtime_error("--host-voxels: only with moving-mesh (it selects where a moving mesh is voxelised)");
+    if (time_both && !moving_mesh) throw std::runtime_error("--time-both: only with moving-mesh (it times both ways of making a mesh's geometry)");
+    if (time_geometry && !moving && !moving_mesh) throw std::runtime_error("--time-geometry: only with moving or moving-mesh (it times the per-step geometry work)");
+    if (grid_time >= 0 && cfg.in_fmt != "Shape2D" && cfg.in_fmt != "Shape3D") throw std::runtime_error("--grid-time: only in_fmt Shape2D and Shape3D inputs move");
     using namespace fs3d;
     Grid3D<FTYPE> grid;
     Grid2D g2;
@@ -91,7 +105,8 @@ static int run(const std::string &data, const std::string &prefix, const fs3d::C
                 inside * grid.dx * grid.dy * grid.dz);                                          // :170
     if (grid_images) OutputGridImages(grid, prefix + "_grid_3d");                             // FluidSolver3D.cpp:152-153 (there: always)
     if (!grid_only.empty()) {
-        if (grid_time >= 0) { g2.Prepare(grid_time); ExtrudeShape2D(grid, g2, cfg.dz, cfg.depth, cfg.depth_var, cfg.baseT); }
+        if (grid_time >= 0 && cfg.in_fmt == "Shape3D") { sh3.Prepare(grid_time); FillShape3DNodes(grid, sh3, cfg.baseT); }
+        else if (grid_time >= 0) { g2.Prepare(grid_time); ExtrudeShape2D(grid, g2, cfg.dz, cfg.depth, cfg.depth_var, cfg.baseT); }
         FILE *f = std::fopen(grid_only.c_str(), "wb");
         if (!f) throw std::runtime_error("cannot create " + grid_only);
         const int hdr[4] = {grid.dimx, grid.dimy, grid.dimz, (int)sizeof(FTYPE)};
@@ -129,6 +144,10 @@ static int run(const std::string &data, const std::string &prefix, const fs3d::C
     long steps = 0;
     int lastframe = -1;
     double geom_ms[3] = {0, 0, 0};                     // moving: host clock around Prepare, the host extrusion, the update call
+    std::vector<float> mx, my, mz;                     // moving-mesh: the sub-frame's vertices
+    std::vector<double> ab_host, ab_dev, ab_dev_gpu, ab_step;   // --time-both: per step, ms
+    int fill_rounds = 0;
+    auto ms_since = [](std::chrono::steady_clock::time_point a) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - a).count(); };
     // the geometry is frame 0's for the whole run: the reference prepares the grid once, before the loop (grid->Prepare(0), :226;
     // the per-step grid->Prepare(t) is commented out, :237) -- the frame only restarts the substep counter
     for (int i = 0; t < finaltime && (max_steps < 0 || steps < max_steps); t += dt, i++, steps++) {
@@ -147,8 +166,36 @@ static int run(const std::string &data, const std::string &prefix, const fs3d::C
             geom_ms[1] += std::chrono::duration<double, std::milli>(g3 - g1).count();
             geom_ms[2] += std::chrono::duration<double, std::milli>(g4 - g3).count();
         }
+        if (moving_mesh) {                                                                               // grid->Prepare(t), :237
+            if (time_both) {                                                                             // the other path first
+                const auto b0 = std::chrono::steady_clock::now();
+                if (host_voxels) { solver.UpdateGridShape3D(mx, my, mz, sh3.frames[sh3.SubFrame(t, mx, my, mz)].idx); ab_dev.push_back(ms_since(b0)); }
+                else { sh3.Prepare(t); FillShape3DNodes(grid, sh3, cfg.baseT); solver.UpdateGrid(grid); ab_host.push_back(ms_since(b0)); }
+            }
+            const auto g0 = std::chrono::steady_clock::now();
+            const size_t frame = sh3.SubFrame(t, mx, my, mz);
+            const auto g1 = std::chrono::steady_clock::now();
+            if (host_voxels) { sh3.Prepare(t); FillShape3DNodes(grid, sh3, cfg.baseT); }
+            const auto g3 = std::chrono::steady_clock::now();
+            if (host_voxels) solver.UpdateGrid(grid);
+            else solver.UpdateGridShape3D(mx, my, mz, sh3.frames[frame].idx);   // `grid` keeps the nodes of time 0: only its dims and baseT are read from here on
+            const auto g4 = std::chrono::steady_clock::now();
+            geom_ms[0] += std::chrono::duration<double, std::milli>(g1 - g0).count();
+            geom_ms[1] += std::chrono::duration<double, std::milli>(g3 - g1).count();
+            geom_ms[2] += std::chrono::duration<double, std::milli>(g4 - g3).count();
+            if (time_both) (host_voxels ? ab_host : ab_dev).push_back(std::chrono::duration<double, std::milli>(g4 - g0).count());
+        }
+        if (time_both) {
+            // (with --host-voxels the device path ran first: its device time was overwritten by the host path's update)
+            float dms = 0;
+            if (!host_voxels && fs3d_last_update_device_ms(solver.ctx(), &dms) == FS3D_OK) ab_dev_gpu.push_back(dms);
+            fs3d_mesh_fill_rounds(solver.ctx(), &fill_rounds);
+            fs3d_synchronize(solver.ctx());
+        }
+        const auto s0 = std::chrono::steady_clock::now();
         solver.UpdateBoundaries();                                                                       // :244
         solver.TimeStep((FTYPE)dt, cfg.num_global, cfg.num_local, (i % 10 == 0) || (t + dt >= finaltime)); // :245
+        if (time_both) { fs3d_synchronize(solver.ctx()); ab_step.push_back(ms_since(s0)); }
         std::printf("\rerr = %.8f,", solver.diffError);                                                  // AdiSolver3D.cpp:376
         const float elapsed = std::chrono::duration<float>(std::chrono::steady_clock::now() - t0).count();
         const float perres = (float)t * 100 / (float)finaltime;                                          // PrintTimeStepInfo, IO.h:455-478
@@ -162,7 +209,7 @@ static int run(const std::string &data, const std::string &prefix, const fs3d::C
             solver.GetLayer(resVel.data(), resT.data(), cfg.outdimx, cfg.outdimy, cfg.outdimz);
             nc.AppendLayer(resVel.data(), resT.data());
         }
-        if (moving) solver.ClearOutterCells();                                                           // AdiSolver3D.cpp:382-385
+        if (moving || moving_mesh) solver.ClearOutterCells();                                                           // AdiSolver3D.cpp:382-385
     }
     const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     // the reference's Profiler table (Common/Profiler.h:90-131: sorted by total time, events that never ran are absent; event
@@ -188,6 +235,22 @@ static int run(const std::string &data, const std::string &prefix, const fs3d::C
         const char *kn[] = {"none", "line", "pipe", "part"};
         fs3d_last_sweep_kernel(solver.ctx(), 0, &kx, &sg); fs3d_last_sweep_kernel(solver.ctx(), 1, &ky, &sg); fs3d_last_sweep_kernel(solver.ctx(), 2, &kz, &sg);
         std::printf("Sweep kernels: X %s, Y %s, Z %s\n", kn[kx & 3], kn[ky & 3], kn[kz & 3]);
+    }
+    if (moving_mesh && time_geometry && steps > 0)
+        std::printf("Moving mesh per step (host clock, ms): SubFrame %.3f, voxels on the host %.3f, update call %.3f; step %.3f\n",
+                    geom_ms[0] / steps, geom_ms[1] / steps, geom_ms[2] / steps, sec * 1e3 / steps);
+    if (time_both) {
+        auto line = [](const char *what, std::vector<double> v) {
+            if (v.size() <= 3) { std::printf(" %s: too few steps;", what); return; }
+            v.erase(v.begin(), v.begin() + 3);
+            std::sort(v.begin(), v.end());
+            const size_t n = v.size();
+            std::printf(" %s median %.3f min %.3f max %.3f n %zu;", what, n % 2 ? v[n / 2] : 0.5 * (v[n / 2 - 1] + v[n / 2]), v.front(), v.back(), n);
+        };
+        std::printf("Moving mesh, both paths per call (ms):");
+        line("host voxels + fs3d_update_nodes", ab_host); line("fs3d_update_nodes_shape3d", ab_dev); line("its device time", ab_dev_gpu);
+        line("time step", ab_step);
+        std::printf(" fill rounds %d\n", fill_rounds);
     }
     if (moving && time_geometry && steps > 0)
         std::printf("Moving geometry per step (host clock, ms): Prepare %.3f, extrusion on the host %.3f, update call %.3f; step %.3f\n",
@@ -301,7 +364,7 @@ static int run_slabs(const fs3d::Grid3D<FTYPE> &grid, const RunGeom &geo, const 
 int main(int argc, char **argv)
 {
     if (argc < 4) {
-        std::printf("Usage: %s <input data> <output prefix> <config file> [align] [GPU [n]] [double] [--steps N] [moving [--host-extrusion] [--time-geometry]] [--grid-only FILE [--grid-time T]] [--grid-images]\n", argv[0]);
+        std::printf("Usage: %s <input data> <output prefix> <config file> [align] [GPU [n]] [double] [--steps N] [moving [--host-extrusion] [--time-geometry]] [moving-mesh [--host-voxels] [--time-geometry] [--time-both]] [--grid-only FILE [--grid-time T]] [--grid-images]\n", argv[0]);
         return 0;
     }
     try {
@@ -311,7 +374,7 @@ int main(int argc, char **argv)
         if (cfg.in_fmt != "Shape2D" && cfg.in_fmt != "Shape3D" && cfg.in_fmt != "SeaNetCDF") throw std::runtime_error("in_fmt " + cfg.in_fmt + ": unknown input format");
         if (cfg.in_fmt != "Shape2D" && !(cfg.frame_time > 0)) throw std::runtime_error("must specify frame time!");   // the cycle length of a Shape3D run (Grid3D.cpp:303-309)
         if (cfg.solver != "ADI") throw std::runtime_error("solver " + cfg.solver + " is not implemented (the reference implements ADI only)");
-        bool align = false, dbl = false, csv = false, same_device = false, grid_images = false, moving = false, host_extrusion = false, time_geometry = false;
+        bool align = false, dbl = false, csv = false, same_device = false, grid_images = false, moving = false, host_extrusion = false, time_geometry = false, moving_mesh = false, host_voxels = false, time_both = false;
         double grid_time = -1;
         int nslabs = 1;
         int device = 0;
@@ -328,6 +391,9 @@ int main(int argc, char **argv)
             else if (s == "--grid-only" && a + 1 < argc) grid_only = argv[++a];
             else if (s == "--grid-time" && a + 1 < argc) grid_time = std::atof(argv[++a]);
             else if (s == "moving") moving = true;
+            else if (s == "moving-mesh") moving_mesh = true;
+            else if (s == "--host-voxels") host_voxels = true;
+            else if (s == "--time-both") time_both = true;
             else if (s == "--host-extrusion") host_extrusion = true;
             else if (s == "--time-geometry") time_geometry = true;
             else if (s == "blocking") { if (a + 1 < argc) a++; }
@@ -335,8 +401,8 @@ int main(int argc, char **argv)
             else if (s == "--grid-images") grid_images = true;       // <prefix>_grid_3d/<k>.bmp: the node types, one image per z-slice
             // transpose, decompose: accepted, no effect
         }
-        return dbl ? run<double>(argv[1], argv[2], cfg, align, device, max_steps, grid_only, csv, nslabs, same_device, grid_images, moving, grid_time, host_extrusion, time_geometry)
-                   : run<float>(argv[1], argv[2], cfg, align, device, max_steps, grid_only, csv, nslabs, same_device, grid_images, moving, grid_time, host_extrusion, time_geometry);
+        return dbl ? run<double>(argv[1], argv[2], cfg, align, device, max_steps, grid_only, csv, nslabs, same_device, grid_images, moving, grid_time, host_extrusion, time_geometry, moving_mesh, host_voxels, time_both)
+                   : run<float>(argv[1], argv[2], cfg, align, device, max_steps, grid_only, csv, nslabs, same_device, grid_images, moving, grid_time, host_extrusion, time_geometry, moving_mesh, host_voxels, time_both);
     } catch (std::exception &e) {
         std::fprintf(stderr, "\n\nCaught exception:\n%s\n\nTerminating...\n", e.what());     // FluidSolver3D.cpp:313-318
         return -1;

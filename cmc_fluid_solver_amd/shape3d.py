@@ -2,7 +2,8 @@
 
 Python twin of cmc_fluid_solver_amd/host/Shape3D.h (same operations in np.float32 where the reference computes in FTYPE = float;
 the header lists the reference lines and the two deliberate deviations: NODE_BOUND cells read as zero-filled memory --
-BC_NOSLIP, v = 0, T = 0 -- and cells addressed outside the grid are ignored).  Restates
+BC_NOSLIP, v = 0, T = 0 -- and cells addressed outside the grid are ignored; a third one concerns a moving run: nodes_of() is a
+function of the current grid alone, where the reference's repeated Prepare_CPU keeps T = 0 on cells that once were walls).  Restates
   Grid3D::Load3DShape / Init / Prepare3D_Shape / ComputeSubframeInfo / Build / RasterPolygon / ProjectPointOnPolygon /
   RasterLine / FloodFill                         (FluidSolver3D/Grid3D.cpp:351-431, 676-946)
   BBox3D::Build                                  (Common/Geometry.h:510-529)
@@ -63,7 +64,9 @@ class Shape3D:
             fr["g"] = ((fr["v"] - mn).astype(np.float32) / h).astype(np.float32)
         self.prepare(time)
 
-    def prepare(self, time):
+    def subframe(self, time):
+        """ComputeSubframeInfo + the interpolation of Prepare3D_Shape (Grid3D.cpp:905-946): (vertices in grid coordinates
+        [n, 3] float32, triangles [m, 3]) of the mesh at `time` -- what build() and the device voxeliser take."""
         nf = len(self.frames)
         a = [0.0]
         for fr in self.frames:
@@ -76,7 +79,10 @@ class Shape3D:
         s = F((r - a[frame]) / (a[frame + 1] - a[frame])); i_s = F(F(1) - s)
         f0, f1 = self.frames[frame], self.frames[(frame + 1) % nf]
         g = ((f0["g"] * i_s).astype(np.float32) + (f1["g"] * s).astype(np.float32)).astype(np.float32)
-        self.build(g, f0["idx"])
+        return g, f0["idx"]
+
+    def prepare(self, time):
+        self.build(*self.subframe(time))
 
     # ---- rasteriser -----------------------------------------------------------------------------------------------
     def _set(self, i, j, k, c):

@@ -187,6 +187,47 @@ fs3d_status fs3d_extrude_shape2d_dev(fs3d_ctx *ctx, const uint8_t *cell2d, const
 fs3d_status fs3d_update_nodes_shape2d(fs3d_ctx *ctx, const uint8_t *cell2d, const float *velx2d, const float *vely2d,
                                       const float *T2d, double dz, double depth, double depth_var, double baseT,
                                       int n_seg_out[3]);
+/* ---- moving geometry from a Shape3D mesh: voxelisation and flood fill on the device ------
+ * Grid3D::Prepare3D_Shape (Grid3D.cpp:905-946) after ComputeSubframeInfo: Grid3D::Build (:859-903 -- RasterPolygon :709-789,
+ * ProjectPointOnPolygon :688-707, RasterLine :791-811 for every triangle) and FloodFill (:813-857) by kernels, then the Node array
+ * as Grid3D::Init / SetData leave it (:351-371, 818-838).  What changes with time is the sub-frame's vertex list: x, y, z (float,
+ * nvert each) in GRID coordinates -- what host/Shape3D.h SubFrame(t) and shape3d.Shape3D.subframe(t) return -- and tri, 3 * ntri
+ * indices into it; 12 bytes per vertex travel where fs3d_update_nodes ships 19 (fp32) or 35 (fp64) bytes per cell.  baseT is
+ * Grid3D's constructor argument.  The rasteriser repeats every fp32 operation of host/Shape3D.h and its twin shape3d.py in their
+ * order, so the nodes equal theirs cell for cell, byte for byte: type from the mesh, bc_vel = bc_temp = NOSLIP, v = 0, T = 0 on
+ * NODE_BOUND cells and (real)(float)baseT elsewhere.  The result is a function of this call's mesh alone (stateless): the
+ * reference's repeated Prepare_CPU leaves T = 0 on cells that once were walls, a value nothing reads after the layers have been
+ * initialised -- the third stated deviation beside the two of host/Shape3D.h.
+ * All three entries return FS3D_ERR_INVALID before anything is launched, the context unchanged, for a NULL array, nvert < 1,
+ * ntri < 0, an index outside 0 .. nvert - 1 and a coordinate that is not finite or exceeds 65536 in magnitude (which keeps every
+ * (int) defined and every line loop short); FS3D_ERR_UNSUPPORTED for an x-slab or group member.
+ * A mesh with a polygon scan line of more than 4 (dimx + dimy + dimz) + 16 cells (where shape3d.py raises and the reference
+ * loops), or with a triangle so thin that its scan stops advancing in fp32, is refused with FS3D_ERR_INVALID after the rasteriser
+ * has run: fs3d_update_nodes_shape3d then leaves NO geometry, the arrays of fs3d_voxelize_shape3d_dev hold no valid grid.
+ *
+ * fs3d_voxelize_shape3d_dev: the seven SoA node arrays (ncell elements each, on the context's device; real = the context's
+ * precision) are written on the context's stream; returns synchronised.  The context's geometry is not touched (it needs none).
+ * Fast store path of the six arrays beside type as in fs3d_extrude_shape2d_dev (dimz % 4 == 0 and the arrays aligned).
+ *
+ * fs3d_update_nodes_shape3d: fs3d_update_nodes* with the voxelisation as the source -- the vertices go through a pinned buffer
+ * the context keeps, the indices are uploaded again only when they differ from the last call's, the kernels write type / bc_vel /
+ * bc_temp into the staging buffer of fs3d_update_nodes and the four value fields into the node-value table, and the device path
+ * of fs3d_update_nodes_dev rebuilds every table.  Its contract is that of fs3d_update_nodes* above in every line: after a first
+ * fs3d_upload_nodes only, single context only, a refused geometry gets the upload's status and leaves NO geometry, nothing
+ * allocated after the first call (a mesh with more vertices or triangles than any before grows the buffers once), counted in
+ * CreateSegments, device time in fs3d_last_update_device_ms.
+ *
+ * fs3d_flood_fill_dev: FloodFill alone on a device array of the context's dimx*dimy*dimz node types: cell (0,0,0) becomes
+ * NODE_OUT whatever it was, NODE_OUT then spreads through NODE_IN cells over the 6-neighbourhood, every other value is a wall.
+ * Returns synchronised; test and measurement aid.  fs3d_mesh_fill_rounds: the rounds (three directional passes each) the last
+ * fill on this context ran, the closing one that changed nothing included. */
+fs3d_status fs3d_update_nodes_shape3d(fs3d_ctx *ctx, const float *x, const float *y, const float *z, int nvert,
+                                      const int *tri, int ntri, double baseT, int n_seg_out[3]);
+fs3d_status fs3d_voxelize_shape3d_dev(fs3d_ctx *ctx, const float *x, const float *y, const float *z, int nvert,
+                                      const int *tri, int ntri, double baseT, uint8_t *type_out, uint8_t *bc_vel_out,
+                                      uint8_t *bc_temp_out, void *vx_out, void *vy_out, void *vz_out, void *T_out);
+fs3d_status fs3d_flood_fill_dev(fs3d_ctx *ctx, uint8_t *type_inout);
+fs3d_status fs3d_mesh_fill_rounds(fs3d_ctx *ctx, int *rounds_out);
 /* The `bottom` table the two entries use, dimx*dimy ints (index i*dimy + j); host only, no context, no GPU.  Test aid: the
  * table must equal the host loader's, whose (int) truncates a double product. */
 fs3d_status fs3d_shape2d_bottom(int dimx, int dimy, double dz, double depth, double depth_var, int *bottom_out);

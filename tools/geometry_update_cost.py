@@ -27,6 +27,21 @@ in one process, after a warm-up:
            (--skip-driver: no child processes under the profiler; its own rows are printed, and written only where --out names a file)
         3. python tools/geometry_update_cost.py --extrude --kernel-trace DIR/ext_kernel_trace.csv
            adds the kernel rows to the file of step 1, which must exist; DIR/ext_kernel_stats.csv is kept as profiles/extrude_kernel_stats.csv
+
+    python tools/geometry_update_cost.py --mesh [--out profiles/mesh_update_cost.json] [--write-inputs DIR] [--kernel-stats CSV]
+
+A moving Shape3D mesh: the voxelisation and flood fill on the device (fs3d_update_nodes_shape3d) against today's path.  The mesh is an
+icosphere of 1280 faces (642 vertices; the reference's heart_us_3D has 1294 triangles) breathing between two radii (x 1.0 and x 0.9), stretched to fill a
+grid of heart_us_3D's size, 128 x 160 x 128, and one of 256^3.  Everything runs in the driver, fs3d_run ... moving-mesh:
+  (a) Shape3D::Prepare(t) on the host + fs3d_update_nodes   and   (b) fs3d_update_nodes_shape3d, both per step of ONE process
+      (--time-both: host clock around each, the device time of (b), the time step of the same steps), after 3 warm-up steps
+  (c) the whole step of `moving-mesh` and of `moving-mesh --host-voxels`, runs alternating (--time-geometry)
+  (d) the kernels of (b) by name, from a run of the driver under the profiler:
+        1. python tools/geometry_update_cost.py --mesh --write-inputs DIR       the mesh and config files, nothing else
+        2. rocprofv3 --kernel-trace --stats --output-format csv -d OUT -o mesh -- \
+               cmc_fluid_solver_amd/fs3d_run DIR/<grid>_data.txt OUT/run DIR/<grid>_config.txt align GPU moving-mesh --steps 12
+        3. python tools/geometry_update_cost.py --mesh --kernel-stats OUT/mesh_kernel_stats.csv --grid <grid>
+           adds the rows to the file of the --mesh run, which must exist
 """
 import argparse
 import ctypes as C
@@ -287,6 +302,118 @@ def main_extrude(a):
     print("wrote", out_path)
 
 
+# radii in mm (cells).  The reference's rasteriser leaves holes in some meshes (the flood fill then takes the inside as well): these
+# two stay closed at every time of the run, which the run checks through its NODE_IN count
+MESH_GRIDS = {"heart_size_128x160x128": ((52.0, 66.0, 52.0), (128, 160, 128)), "cube_256": ((118.0, 118.0, 118.0), (256, 256, 256))}
+MESH_CONFIG = """dimension 3D
+in_fmt Shape3D
+Re 200.0
+Pr 0.72
+lambda 1.4
+bc_type NoSlip
+grid_dx 0.001
+grid_dy 0.001
+grid_dz 0.001
+frame_time 0.4
+cycles 1
+time_steps 16
+out_time_steps 1000
+out_gridx 16
+out_gridy 16
+out_gridz 16
+out_fmt NetCDF
+out_vars 4 u v w T
+solver ADI
+num_global 4
+num_local 2
+"""
+
+
+def write_mesh_inputs(d):
+    """Per grid: an icosphere of 1280 faces stretched to the radii (mm), and the same at 0.9 of them as the second frame."""
+    from cmc_fluid_solver_amd import shape3d
+    from test_shape3d import icosphere
+    out = {}
+    os.makedirs(d, exist_ok=True)
+    for name, (radii, dims) in MESH_GRIDS.items():
+        v, f = icosphere(1.0, (0.0, 0.0, 0.0), subdiv=3)
+        assert len(f) == 1280
+        centre = np.array(radii) * 1.5 + 0.5
+        frames = [(v * np.array(radii) * k + centre, f) for k in (1.0, 0.9)]
+        data, cfg = os.path.join(d, name + "_data.txt"), os.path.join(d, name + "_config.txt")
+        shape3d.write_mesh(data, frames)
+        open(cfg, "w").write(MESH_CONFIG)
+        out[name] = (data, cfg, dims)
+    return out
+
+
+def main_mesh(a):
+    import re
+    import tempfile
+    from cmc_fluid_solver_amd import build as B
+    out_path = a.out if a.out != DEFAULT_OUT else os.path.join(ROOT, "profiles", "mesh_update_cost.json")
+    if a.write_inputs:
+        for name, (data, cfg, dims) in write_mesh_inputs(a.write_inputs).items():
+            print(name, data, cfg)
+        return
+    if a.kernel_stats:
+        import csv
+        res = json.load(open(out_path))
+        rows = {}
+        for row in csv.DictReader(open(a.kernel_stats)):
+            nm = row["Name"].split("(")[0]
+            if "k_geom_" in nm or "k_clear_outer" in nm:
+                rows[nm] = {"calls": int(row["Calls"]), "total_us": float(row["TotalDurationNs"]) / 1e3, "average_us": float(row["AverageNs"]) / 1e3}
+        part = lambda pred: sum(r["total_us"] for n, r in rows.items() if pred(n))
+        updates = rows[[n for n in rows if "k_geom_codes" in n][0]]["calls"]
+        res[a.grid]["kernels"] = {"rows": rows, "updates": updates,
+                                  "raster_us_per_update": part(lambda n: "raster_mesh" in n) / updates,
+                                  "fill_us_per_update": part(lambda n: "k_geom_fill" in n) / updates,
+                                  "node_arrays_us_per_update": part(lambda n: "mesh_nodes" in n) / updates,
+                                  "table_rebuild_us_per_update": part(lambda n: "k_geom_" in n and "raster" not in n and "fill" not in n and "mesh_nodes" not in n) / updates}
+        json.dump(res, open(out_path, "w"), indent=1)
+        print(json.dumps(res[a.grid]["kernels"], indent=1))
+        return
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("geometry_update_cost: no GPU (there is no CPU fallback)")
+    driver = B.build_driver()
+    res = {"device": torch.cuda.get_device_name(0), "commit": a.commit or tree_commit(), "precision": "fp32",
+           "mesh": "icosphere, 1280 faces, 642 vertices, two frames (radii x 1.0 and x 0.9)",
+           "note": "fs3d_run moving-mesh; (a)/(b): --time-both, both paths in every step of one process, 3 warm-up steps dropped, host clock around "
+                   "calls that end synchronised, device time from HIP events inside the library; (c): --time-geometry, runs alternating"}
+    num = r"median ([0-9.]+) min ([0-9.]+) max ([0-9.]+) n (\d+)"
+    with tempfile.TemporaryDirectory() as d:
+        for name, (data, cfg, dims) in write_mesh_inputs(d).items():
+            base = [driver, data, os.path.join(d, "run"), cfg, "align", "GPU", "moving-mesh"]
+            o = subprocess.run(base + ["--time-both", "--steps", str(a.repeats + 3)], check=True, capture_output=True, text=True, timeout=1200).stdout
+            got = tuple(int(x) for x in re.search(r"Grid = (\d+) x (\d+) x (\d+)", o).groups())
+            assert got == dims, (got, dims)
+            assert float(re.search(r"NODE_IN points = ([0-9.]+)", o).group(1)) > got[0] * got[1] * got[2] / 8, "the mesh is not closed"
+            r = {"dims": list(got), "cells": got[0] * got[1] * got[2], "fill_rounds": int(re.search(r"fill rounds (\d+)", o).group(1))}
+            for key, label in (("a_host_voxels_update_nodes", "host voxels \\+ fs3d_update_nodes"), ("b_update_nodes_shape3d", "fs3d_update_nodes_shape3d"),
+                               ("b_device_time", "its device time"), ("time_step", "time step")):
+                m = re.search(label + " " + num, o)
+                r[key] = {"median_ms": float(m.group(1)), "min_ms": float(m.group(2)), "max_ms": float(m.group(3)), "n": int(m.group(4))}
+            r["b_over_a"] = r["b_update_nodes_shape3d"]["median_ms"] / r["a_host_voxels_update_nodes"]["median_ms"]
+            r["condition_b_below_a_ranges_apart"] = r["b_update_nodes_shape3d"]["max_ms"] < r["a_host_voxels_update_nodes"]["min_ms"]
+            r["b_device_time_over_time_step"] = r["b_device_time"]["median_ms"] / r["time_step"]["median_ms"]
+            runs = {"moving-mesh": [], "moving-mesh --host-voxels": []}
+            for k in range(a.driver_runs + 1):
+                for word, acc in runs.items():
+                    o = subprocess.run(base + word.split()[1:] + ["--time-geometry", "--steps", "12"], check=True, capture_output=True, text=True, timeout=1200).stdout
+                    if k:                                    # the first pair is the warm-up
+                        acc.append(float(re.search(r"update call [0-9.]+; step ([0-9.]+)", o).group(1)))
+            r["driver_step"] = {w: stats(v) for w, v in runs.items()}
+            r["condition_driver_step_not_above_host_voxels"] = r["driver_step"]["moving-mesh"]["median_ms"] <= r["driver_step"]["moving-mesh --host-voxels"]["median_ms"]
+            res[name] = r
+            print(name, json.dumps(r), flush=True)
+    os.makedirs(os.path.dirname(out_path), exist_ok=True)
+    with open(out_path, "w") as f:
+        json.dump(res, f, indent=1)
+    print("wrote", out_path)
+
+
 def tree_commit():
     try:
         return subprocess.run(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], capture_output=True, text=True).stdout.strip() or None
@@ -303,11 +430,18 @@ def main():
     ap.add_argument("--extrude", action="store_true", help="the rows of the device extrusion (profiles/extrude_update_cost.json)")
     ap.add_argument("--skip-driver", action="store_true", help="--extrude: the library calls only (the run under the profiler)")
     ap.add_argument("--kernel-trace", default=None, help="--extrude: ..._kernel_trace.csv of a rocprofv3 run of this command; adds the kernel rows")
+    ap.add_argument("--mesh", action="store_true", help="the rows of the device voxeliser of Shape3D meshes (profiles/mesh_update_cost.json)")
+    ap.add_argument("--write-inputs", default=None, help="--mesh: write the mesh and config files of the two grids into this directory and stop")
+    ap.add_argument("--kernel-stats", default=None, help="--mesh: ..._kernel_stats.csv of a rocprofv3 run of the driver; adds the kernel rows of --grid")
+    ap.add_argument("--grid", default="heart_size_128x160x128", help="--mesh --kernel-stats: the grid the profiled run used")
+    ap.add_argument("--driver-runs", type=int, default=3, help="--mesh: runs per word of row (c), after one warm-up pair")
     ap.add_argument("--commit", default=None, help="what to record as the commit (default: git rev-parse of the tree)")
     ap.add_argument("--out", default=DEFAULT_OUT)
     a = ap.parse_args()
     if a.extrude:
         return main_extrude(a)
+    if a.mesh:
+        return main_mesh(a)
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("geometry_update_cost: no GPU (there is no CPU fallback)")
