@@ -123,12 +123,7 @@ class Solver:
         if st != OK:
             raise Fs3dError(st, (self.lib.fs3d_last_error(None) or b"").decode())
         self._chk(self.lib.fs3d_set_params(self.h, *[float(p) for p in params]))
-        arrs = [np.ascontiguousarray(nodes.type, np.uint8), np.ascontiguousarray(nodes.bc_vel, np.uint8),
-                np.ascontiguousarray(nodes.bc_temp, np.uint8)] + [
-            np.ascontiguousarray(v, self.dtype) for v in (nodes.vx, nodes.vy, nodes.vz, nodes.T)]
-        nseg = (C.c_int * 3)()
-        self._chk(self.lib.fs3d_upload_nodes(self.h, *[_p(a) for a in arrs], nseg))
-        self.num_segments = list(nseg)
+        self._update(self.lib.fs3d_upload_nodes, *[_p(a) for a in self._node_arrays(nodes)])
         self._chk(self.lib.fs3d_init_layers_from_nodes(self.h))
 
     # -- plumbing -----------------------------------------------------------------
@@ -166,33 +161,38 @@ class Solver:
         self._group = group        # keep the group alive as long as the context
 
     # -- moving geometry ------------------------------------------------------------
-    def update_nodes(self, nodes):
-        """AdiSolver3D::CreateSegments between time steps: the tables of a new geometry (same dims), rebuilt on the device.
-        Layers are kept.  After a refusal the context has no geometry until an update succeeds."""
-        assert tuple(nodes.shape) == tuple(self.gdims)
-        arrs = [np.ascontiguousarray(nodes.type, np.uint8), np.ascontiguousarray(nodes.bc_vel, np.uint8),
-                np.ascontiguousarray(nodes.bc_temp, np.uint8)] + [
+    def _node_arrays(self, nodes):
+        """The seven node arrays as the C ABI takes them from the host: uint8 x 3, the context's precision x 4."""
+        return [np.ascontiguousarray(a, np.uint8) for a in (nodes.type, nodes.bc_vel, nodes.bc_temp)] + [
             np.ascontiguousarray(v, self.dtype) for v in (nodes.vx, nodes.vy, nodes.vz, nodes.T)]
+
+    def _update(self, fn, *args):
+        """fn(ctx, *args, n_seg_out): an entry that leaves the context with new tables; sets and returns num_segments."""
         nseg = (C.c_int * 3)()
-        self._chk(self.lib.fs3d_update_nodes(self.h, *[_p(a) for a in arrs], nseg))
+        self._chk(fn(self.h, *args, nseg))
         self.num_segments = list(nseg)
         return self.num_segments
 
-    def update_nodes_dev(self, type, bc_vel, bc_temp, vx, vy, vz, T):
-        """The same from arrays on the context's device: torch tensors (contiguous; uint8 x 3, the context's precision x 4)
-        or raw device pointers (int)."""
+    def _dev_ptrs(self, what, arrays):
+        """Node arrays on the context's device (the byte arrays first) as pointers; `what` names the method in the refusal."""
         def ptr(a, want):
             if isinstance(a, int):
                 return C.c_void_p(a)
             if not a.is_cuda or not a.is_contiguous() or a.element_size() != want or a.numel() != int(np.prod(self.gdims)):
-                raise ValueError("update_nodes_dev: contiguous device tensors of the grid's size and the context's precision")
+                raise ValueError(what + ": contiguous device tensors of the grid's size and the context's precision")
             return C.c_void_p(a.data_ptr())
-        es = self.dtype.itemsize
-        ptrs = [ptr(a, 1) for a in (type, bc_vel, bc_temp)] + [ptr(a, es) for a in (vx, vy, vz, T)]
-        nseg = (C.c_int * 3)()
-        self._chk(self.lib.fs3d_update_nodes_dev(self.h, *ptrs, nseg))
-        self.num_segments = list(nseg)
-        return self.num_segments
+        return [ptr(a, 1) for a in arrays[:3]] + [ptr(a, self.dtype.itemsize) for a in arrays[3:]]
+
+    def update_nodes(self, nodes):
+        """AdiSolver3D::CreateSegments between time steps: the tables of a new geometry (same dims), rebuilt on the device.
+        Layers are kept.  After a refusal the context has no geometry until an update succeeds."""
+        assert tuple(nodes.shape) == tuple(self.gdims)
+        return self._update(self.lib.fs3d_update_nodes, *[_p(a) for a in self._node_arrays(nodes)])
+
+    def update_nodes_dev(self, type, bc_vel, bc_temp, vx, vy, vz, T):
+        """The same from arrays on the context's device: torch tensors (contiguous; uint8 x 3, the context's precision x 4)
+        or raw device pointers (int)."""
+        return self._update(self.lib.fs3d_update_nodes_dev, *self._dev_ptrs("update_nodes_dev", [type, bc_vel, bc_temp, vx, vy, vz, T]))
 
     def _grid2d_arrays(self, g2):
         """cell, velx, vely, T of a shape2d.Grid2D (or any object with these four [dimx, dimy] arrays) as the C ABI takes them."""
@@ -205,14 +205,7 @@ class Solver:
     def extrude_shape2d_dev(self, g2, dz, depth, depth_var, baseT, type, bc_vel, bc_temp, vx, vy, vz, T):
         """Grid3D::Prepare2D on the device: the 2D grid g2 as it stands (after g2.prepare(t)) extruded into seven arrays on the
         context's device -- torch tensors or raw pointers, as update_nodes_dev takes them.  The context's geometry is not touched."""
-        def ptr(a, want):
-            if isinstance(a, int):
-                return C.c_void_p(a)
-            if not a.is_cuda or not a.is_contiguous() or a.element_size() != want or a.numel() != int(np.prod(self.gdims)):
-                raise ValueError("extrude_shape2d_dev: contiguous device tensors of the grid's size and the context's precision")
-            return C.c_void_p(a.data_ptr())
-        es = self.dtype.itemsize
-        ptrs = [ptr(a, 1) for a in (type, bc_vel, bc_temp)] + [ptr(a, es) for a in (vx, vy, vz, T)]
+        ptrs = self._dev_ptrs("extrude_shape2d_dev", [type, bc_vel, bc_temp, vx, vy, vz, T])
         arrs = self._grid2d_arrays(g2)
         self._chk(self.lib.fs3d_extrude_shape2d_dev(self.h, *[_p(a) for a in arrs], float(dz), float(depth), float(depth_var), float(baseT), *ptrs))
 
@@ -220,10 +213,7 @@ class Solver:
         """update_nodes with the extrusion of the 2D grid g2 as the source: 13 bytes per column travel, the node arrays are written
         by a kernel.  Same contract as update_nodes."""
         arrs = self._grid2d_arrays(g2)
-        nseg = (C.c_int * 3)()
-        self._chk(self.lib.fs3d_update_nodes_shape2d(self.h, *[_p(a) for a in arrs], float(dz), float(depth), float(depth_var), float(baseT), nseg))
-        self.num_segments = list(nseg)
-        return self.num_segments
+        return self._update(self.lib.fs3d_update_nodes_shape2d, *[_p(a) for a in arrs], float(dz), float(depth), float(depth_var), float(baseT))
 
     @staticmethod
     def _mesh_arrays(g, idx):
@@ -234,15 +224,6 @@ class Solver:
         if tri.size % 3 or not np.array_equal(tri, np.asarray(idx).reshape(-1)):
             raise ValueError("triangles: [m, 3] indices that fit an int")
         return xyz, tri
-
-    def _dev_ptrs(self, what, arrays):
-        def ptr(a, want):
-            if isinstance(a, int):
-                return C.c_void_p(a)
-            if not a.is_cuda or not a.is_contiguous() or a.element_size() != want or a.numel() != int(np.prod(self.gdims)):
-                raise ValueError(what + ": contiguous device tensors of the grid's size and the context's precision")
-            return C.c_void_p(a.data_ptr())
-        return [ptr(a, 1) for a in arrays[:3]] + [ptr(a, self.dtype.itemsize) for a in arrays[3:]]
 
     def voxelize_shape3d_dev(self, g, idx, baseT, type, bc_vel, bc_temp, vx, vy, vz, T):
         """Grid3D::Build + FloodFill + the Node array on the device: the mesh (g, idx) of shape3d.Shape3D.subframe(t) voxelised into
@@ -256,10 +237,7 @@ class Solver:
         """update_nodes with the voxelisation of the mesh (g, idx) as the source: 12 bytes per vertex travel, the node arrays are
         written by kernels.  Same contract as update_nodes."""
         xyz, tri = self._mesh_arrays(g, idx)
-        nseg = (C.c_int * 3)()
-        self._chk(self.lib.fs3d_update_nodes_shape3d(self.h, *[_p(a) for a in xyz], len(xyz[0]), _p(tri), tri.size // 3, float(baseT), nseg))
-        self.num_segments = list(nseg)
-        return self.num_segments
+        return self._update(self.lib.fs3d_update_nodes_shape3d, *[_p(a) for a in xyz], len(xyz[0]), _p(tri), tri.size // 3, float(baseT))
 
     def flood_fill_dev(self, type):
         """FloodFill alone on a device array of node types (uint8 torch tensor or raw pointer) of the context's dims, in place."""

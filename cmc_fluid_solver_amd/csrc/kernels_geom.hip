@@ -42,6 +42,8 @@ static fs3d_status gfail(fs3d_ctx *c, fs3d_status st, const std::string &msg)
         }                                                                                            \
     } while (0)
 
+#define GTRY(call) do { const fs3d_status st_ = (call); if (st_) return st_; } while (0)
+
 // device allocations / frees of the geometry paths are counted (fs3d_geometry_info entry 13)
 #define GMALLOC(c, pp, bytes) do { GHIP(c, hipMalloc((void **)(pp), (bytes))); (c)->geom_allocs++; } while (0)
 static void gfree(fs3d_ctx *c, void *p) { if (p) { hipFree(p); c->geom_allocs++; } }
@@ -331,11 +333,47 @@ __device__ __forceinline__ ExNode extrude_node(int k, int c2, float velx, float 
     return n;
 }
 
-// Pure store kernel, 19 bytes per cell in fp32 and 35 in fp64.  One thread writes V consecutive k of one column: V == 4 (dimz % 4 == 0,
-// the byte arrays aligned to 4 bytes and the value arrays to 16) one dword per byte array and 16-byte stores for the value arrays
-// (one per array in fp32, two in fp64), V == 1 cell by cell.
-// Lanes run along k, so a wave writes 64 * V consecutive cells; the column record is read once per thread.  Stores are nontemporal:
-// the geometry kernels read these arrays next, but only after the whole grid has been written.
+// Store tail of the two node-writing kernels: the V consecutive cells from l.  wt / wv / wb hold type, bc_vel and bc_temp of cell q
+// in byte q (TYPE false: the type array is not written); vz is 0.  V == 4 (l % 4 == 0, the byte arrays aligned to 4 bytes and the
+// value arrays to 16): one dword per byte array and 16-byte stores for the value arrays (one per array in fp32, two in fp64);
+// V == 1: cell by cell.  Stores are nontemporal: the geometry kernels read these arrays next, but only after the whole grid has
+// been written.
+template <typename R, int V, bool TYPE>
+__device__ __forceinline__ void store_nodes(long long l, unsigned wt, unsigned wv, unsigned wb, const R (&ax)[V], const R (&ay)[V],
+                                            const R (&aT)[V], uint8_t *__restrict__ type, uint8_t *__restrict__ bc_vel,
+                                            uint8_t *__restrict__ bc_temp, R *__restrict__ vx, R *__restrict__ vy, R *__restrict__ vz,
+                                            R *__restrict__ T)
+{
+    constexpr int P = 16 / sizeof(R);                  // values per 16-byte store
+    typedef R RP __attribute__((ext_vector_type(P)));
+    if constexpr (V == 4) {
+        if constexpr (TYPE) __builtin_nontemporal_store(wt, (unsigned *)(type + l));
+        __builtin_nontemporal_store(wv, (unsigned *)(bc_vel + l));
+        __builtin_nontemporal_store(wb, (unsigned *)(bc_temp + l));
+#pragma unroll
+        for (int h = 0; h < V; h += P) {
+            RP x, y, z, w;
+#pragma unroll
+            for (int q = 0; q < P; q++) { x[q] = ax[h + q]; y[q] = ay[h + q]; z[q] = R(0); w[q] = aT[h + q]; }
+            __builtin_nontemporal_store(x, (RP *)(vx + l + h));
+            __builtin_nontemporal_store(y, (RP *)(vy + l + h));
+            __builtin_nontemporal_store(z, (RP *)(vz + l + h));
+            __builtin_nontemporal_store(w, (RP *)(T + l + h));
+        }
+    } else {
+        if constexpr (TYPE) __builtin_nontemporal_store((uint8_t)wt, type + l);
+        __builtin_nontemporal_store((uint8_t)wv, bc_vel + l);
+        __builtin_nontemporal_store((uint8_t)wb, bc_temp + l);
+        __builtin_nontemporal_store(ax[0], vx + l);
+        __builtin_nontemporal_store(ay[0], vy + l);
+        __builtin_nontemporal_store(R(0), vz + l);
+        __builtin_nontemporal_store(aT[0], T + l);
+    }
+}
+
+// Pure store kernel, 19 bytes per cell in fp32 and 35 in fp64.  One thread writes V consecutive k of one column (store_nodes;
+// V == 4 where dimz % 4 == 0 and the arrays are aligned).
+// Lanes run along k, so a wave writes 64 * V consecutive cells; the column record is read once per thread.
 template <typename R, int V>
 __global__ void __launch_bounds__(256) k_geom_extrude(const float *__restrict__ velx, const float *__restrict__ vely, const float *__restrict__ T2,
                                                        const int *__restrict__ bottom, const uint8_t *__restrict__ cell, long long ncol, int dimz,
@@ -343,8 +381,6 @@ __global__ void __launch_bounds__(256) k_geom_extrude(const float *__restrict__ 
                                                        uint8_t *__restrict__ bc_temp, R *__restrict__ vx, R *__restrict__ vy, R *__restrict__ vz,
                                                        R *__restrict__ T)
 {
-    constexpr int P = 16 / sizeof(R);                  // values per 16-byte store
-    typedef R RP __attribute__((ext_vector_type(P)));
     const int nq = dimz / V;                           // V == 4: dimz % 4 == 0
     const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
     if (t >= ncol * nq) return;
@@ -361,29 +397,7 @@ __global__ void __launch_bounds__(256) k_geom_extrude(const float *__restrict__ 
         wt |= (unsigned)n.type << (8 * q); wv |= (unsigned)n.bv << (8 * q); wb |= (unsigned)n.bt << (8 * q);
         ax[q] = (R)n.vx; ay[q] = (R)n.vy; aT[q] = (R)n.T;
     }
-    if constexpr (V == 4) {
-        __builtin_nontemporal_store(wt, (unsigned *)(type + l));
-        __builtin_nontemporal_store(wv, (unsigned *)(bc_vel + l));
-        __builtin_nontemporal_store(wb, (unsigned *)(bc_temp + l));
-#pragma unroll
-        for (int h = 0; h < V; h += P) {
-            RP x, y, z, w;
-#pragma unroll
-            for (int q = 0; q < P; q++) { x[q] = ax[h + q]; y[q] = ay[h + q]; z[q] = R(0); w[q] = aT[h + q]; }
-            __builtin_nontemporal_store(x, (RP *)(vx + l + h));
-            __builtin_nontemporal_store(y, (RP *)(vy + l + h));
-            __builtin_nontemporal_store(z, (RP *)(vz + l + h));
-            __builtin_nontemporal_store(w, (RP *)(T + l + h));
-        }
-    } else {
-        __builtin_nontemporal_store((uint8_t)wt, type + l);
-        __builtin_nontemporal_store((uint8_t)wv, bc_vel + l);
-        __builtin_nontemporal_store((uint8_t)wb, bc_temp + l);
-        __builtin_nontemporal_store(ax[0], vx + l);
-        __builtin_nontemporal_store(ay[0], vy + l);
-        __builtin_nontemporal_store(R(0), vz + l);
-        __builtin_nontemporal_store(aT[0], T + l);
-    }
+    store_nodes<R, V, true>(l, wt, wv, wb, ax, ay, aT, type, bc_vel, bc_temp, vx, vy, vz, T);
 }
 
 // ---- Shape3D meshes: Grid3D::Build (Grid3D.cpp:859-903) on the device ------------------------------------------------------------
@@ -591,8 +605,8 @@ __global__ void __launch_bounds__(256) k_geom_fill_z(uint8_t *type, long long nl
 }
 
 // The other six node arrays of a Shape3D grid from its finished type array (nodes_of in shape3d.py; FillShape3DNodes in host/Shape3D.h):
-// bc_vel = bc_temp = NOSLIP, v = 0, T = 0 on NODE_BOUND and baseT elsewhere.  Store shapes of k_geom_extrude: V == 4 cells per
-// thread with one dword per byte array and 16-byte stores (dimz % 4 == 0 and the arrays aligned), V == 1 cell by cell.
+// bc_vel = bc_temp = NOSLIP, v = 0, T = 0 on NODE_BOUND and baseT elsewhere.  Store shapes of k_geom_extrude (store_nodes): V == 4
+// cells per thread (dimz % 4 == 0 and the arrays aligned), V == 1 cell by cell.
 // Stateless by definition: the reference's repeated Prepare_CPU leaves T = 0 on cells that once were walls, a value nothing reads
 // after the layers have been initialised (the third stated deviation, host/Shape3D.h).
 template <typename R, int V>
@@ -600,32 +614,15 @@ __global__ void __launch_bounds__(256) k_geom_mesh_nodes(const uint8_t *__restri
                                                           uint8_t *__restrict__ bc_temp, R *__restrict__ vx, R *__restrict__ vy, R *__restrict__ vz,
                                                           R *__restrict__ T)
 {
-    constexpr int P = 16 / sizeof(R);
-    typedef R RP __attribute__((ext_vector_type(P)));
     const long long l = ((long long)blockIdx.x * 256 + threadIdx.x) * V;
     if (l >= ncell) return;                                            // V == 4: ncell % 4 == 0
-    if constexpr (V == 4) {
-        const unsigned w = *(const unsigned *)(type + l);
-        __builtin_nontemporal_store(0u, (unsigned *)(bc_vel + l));
-        __builtin_nontemporal_store(0u, (unsigned *)(bc_temp + l));
+    unsigned w;
+    if constexpr (V == 4) w = *(const unsigned *)(type + l); else w = type[l];
+    R a0[V], aT[V];
 #pragma unroll
-        for (int h = 0; h < V; h += P) {
-            RP z, t;
-#pragma unroll
-            for (int q = 0; q < P; q++) { z[q] = R(0); t[q] = ((w >> (8 * (h + q))) & 0xFF) == FS3D_NODE_BOUND ? R(0) : baseT; }
-            __builtin_nontemporal_store(z, (RP *)(vx + l + h));
-            __builtin_nontemporal_store(z, (RP *)(vy + l + h));
-            __builtin_nontemporal_store(z, (RP *)(vz + l + h));
-            __builtin_nontemporal_store(t, (RP *)(T + l + h));
-        }
-    } else {
-        __builtin_nontemporal_store((uint8_t)FS3D_BC_NOSLIP, bc_vel + l);
-        __builtin_nontemporal_store((uint8_t)FS3D_BC_NOSLIP, bc_temp + l);
-        __builtin_nontemporal_store(R(0), vx + l);
-        __builtin_nontemporal_store(R(0), vy + l);
-        __builtin_nontemporal_store(R(0), vz + l);
-        __builtin_nontemporal_store(type[l] == FS3D_NODE_BOUND ? R(0) : baseT, T + l);
-    }
+    for (int q = 0; q < V; q++) { a0[q] = R(0); aT[q] = ((w >> (8 * q)) & 0xFF) == FS3D_NODE_BOUND ? R(0) : baseT; }
+    constexpr unsigned noslip = 0x01010101u * FS3D_BC_NOSLIP;          // in every byte
+    store_nodes<R, V, false>(l, 0u, noslip, noslip, a0, a0, aT, nullptr, bc_vel, bc_temp, vx, vy, vz, T);
 }
 
 // ---------------------------------------------------------------------------------
@@ -638,9 +635,16 @@ static inline unsigned geom_grid(long long n, int cap = 4096)
     return (unsigned)(g < 1 ? 1 : (g > cap ? cap : g));
 }
 
-// lines / groups of the shared columns of direction d
-static inline int geom_n_o(const fs3d_ctx *c, int d) { return d == 0 ? c->dimy : c->dimx; }
-static inline int geom_n(const fs3d_ctx *c, int d) { return d == 0 ? c->dimx : c->dimy; }
+// The lines of direction d.  d = 0 (X) and 1 (Y): n_o * dimz lines -- `os` apart along the outer index, neighbours along k -- of n
+// cells `ss` apart; d = 2 (Z): dimx * dimy lines of dimz contiguous cells, one behind the other (n_o is not used).
+struct GeomLines { int n_o; long long os, ss; int n; long long nlines; };
+static inline GeomLines geom_lines(const fs3d_ctx *c, int d)
+{
+    if (d == 0) return {c->dimy, (long long)c->dimz, c->plane, c->dimx, (long long)c->dimy * c->dimz};
+    if (d == 1) return {c->dimx, c->plane, (long long)c->dimz, c->dimy, (long long)c->dimx * c->dimz};
+    return {0, (long long)c->dimz, 1, c->dimz, (long long)c->dimx * c->dimy};
+}
+// groups of 32 k: the shared columns of directions 0 and 1 are n_o * geom_ng of them
 static inline int geom_ng(const fs3d_ctx *c) { return (c->dimz + 31) / 32; }
 
 // Device time of an update, while fs3d_enable_timing is on: an event before the first launch of every batch and one before the
@@ -679,6 +683,14 @@ static void gev_collect(fs3d_ctx *c)
     g.ev_ms = 0;
 }
 
+// ends a batch: the event that closes it, then the wait for the stream
+static fs3d_status gev_sync(fs3d_ctx *c)
+{
+    gev_end(c);
+    GHIP(c, hipStreamSynchronize(c->stream));
+    return FS3D_OK;
+}
+
 void fs3d_geom_destroy(fs3d_ctx *c)
 {
     fs3d_geom &g = c->geom;
@@ -705,14 +717,14 @@ void fs3d_geom_destroy(fs3d_ctx *c)
 static fs3d_status geom_prepare(fs3d_ctx *c, bool need_stage)
 {
     fs3d_geom &g = c->geom;
-    const long long nl[3] = {(long long)c->dimy * c->dimz, (long long)c->dimx * c->dimz, (long long)c->dimx * c->dimy};
     if (need_stage && !g.stage) GMALLOC(c, &g.stage, (size_t)3 * c->ncell);
     if (g.cnt) return FS3D_OK;
-    for (int d = 0; d < 3; d++) GMALLOC(c, &g.lst[d], (size_t)nl[d] * sizeof(int));
+    for (int d = 0; d < 3; d++) GMALLOC(c, &g.lst[d], (size_t)geom_lines(c, d).nlines * sizeof(int));
     size_t host_bytes = GC_WORDS * sizeof(unsigned long long);
     for (int d = 0; d < 2; d++) {
-        if (geom_n(c, d) > UCOL_PITCH) continue;         // as upload_nodes_impl: no shared columns for longer lines
-        const size_t nq = (size_t)geom_n_o(c, d) * geom_ng(c);
+        const GeomLines L = geom_lines(c, d);
+        if (L.n > UCOL_PITCH) continue;                  // as upload_nodes_impl: no shared columns for longer lines
+        const size_t nq = (size_t)L.n_o * geom_ng(c);
         GMALLOC(c, &g.col[d], nq * UCOL_PITCH * sizeof(uint16_t));
         GHIP(c, hipMemsetAsync(g.col[d], 0, nq * UCOL_PITCH * sizeof(uint16_t), c->stream));
         GMALLOC(c, &g.cflag[d], nq);
@@ -729,19 +741,19 @@ static fs3d_status geom_prepare(fs3d_ctx *c, bool need_stage)
 static fs3d_status geom_columns(fs3d_ctx *c, int d)
 {
     fs3d_geom &g = c->geom;
-    const int n_o = geom_n_o(c, d), n = geom_n(c, d), ng = geom_ng(c);
-    if (n > UCOL_PITCH) { c->n_ucol[d] = 0; return FS3D_OK; }
-    const size_t nq = (size_t)n_o * ng;
+    const GeomLines L = geom_lines(c, d);
+    const int ng = geom_ng(c);
+    if (L.n > UCOL_PITCH) { c->n_ucol[d] = 0; return FS3D_OK; }
+    const size_t nq = (size_t)L.n_o * ng;
     if (c->ucol_cap[d] < (long long)nq) {                // the upload's table holds its own distinct columns only: once, room for any number
         gfree(c, c->ucol[d]); c->ucol[d] = nullptr; c->ucol_cap[d] = 0;
         GMALLOC(c, &c->ucol[d], nq * UCOL_PITCH * sizeof(uint16_t));
         c->ucol_cap[d] = (long long)nq;
     }
     const int keep = (0xF << (4 * d)) | (3 << CODE_TYPE_SHIFT);
-    const long long ss = d == 0 ? c->plane : c->dimz, os = d == 0 ? (long long)c->dimz : c->plane;
     gev_begin(c);
-    hipLaunchKernelGGL(k_geom_columns, dim3((unsigned)(n_o * ((ng + 1) / 2))), dim3(64), 0, c->stream, c->code, c->dead[d], ng, c->dimz,
-                       os, ss, n, keep, g.col[d], g.cflag[d], g.hash[d]);
+    hipLaunchKernelGGL(k_geom_columns, dim3((unsigned)(L.n_o * ((ng + 1) / 2))), dim3(64), 0, c->stream, c->code, c->dead[d], ng, c->dimz,
+                       L.os, L.ss, L.n, keep, g.col[d], g.cflag[d], g.hash[d]);
     GHIP(c, hipGetLastError());
     // identities on the host from the hashes (a few KB), numbered in the order of first appearance as upload_nodes_impl numbers them
     unsigned long long *hh = (unsigned long long *)g.host;
@@ -750,8 +762,7 @@ static fs3d_status geom_columns(fs3d_ctx *c, int d)
     uint8_t *cf = (uint8_t *)(rep + nq);
     GHIP(c, hipMemcpyAsync(hh, g.hash[d], nq * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
     GHIP(c, hipMemcpyAsync(cf, g.cflag[d], nq, hipMemcpyDeviceToHost, c->stream));
-    gev_end(c);
-    GHIP(c, hipStreamSynchronize(c->stream));
+    GTRY(gev_sync(c));
     std::unordered_map<unsigned long long, unsigned> ids;
     unsigned nid = 0;
     for (size_t q = 0; q < nq; q++) {
@@ -767,35 +778,34 @@ static fs3d_status geom_columns(fs3d_ctx *c, int d)
     if (nid) {
         GHIP(c, hipMemcpyAsync(g.rep[d], rep, nid * sizeof(int), hipMemcpyHostToDevice, c->stream));
         hipLaunchKernelGGL(k_geom_gather, dim3(nid), dim3(256), 0, c->stream, g.col[d], g.rep[d], c->ucol[d]);
-        hipLaunchKernelGGL(k_geom_verify, dim3((unsigned)nq), dim3(64), 0, c->stream, g.col[d], c->uflag[d], c->ucol[d], n, g.cnt);
+        hipLaunchKernelGGL(k_geom_verify, dim3((unsigned)nq), dim3(64), 0, c->stream, g.col[d], c->uflag[d], c->ucol[d], L.n, g.cnt);
         GHIP(c, hipGetLastError());
     }
     // the pinned block is reused by the next direction: its copies must have left
-    gev_end(c);
-    GHIP(c, hipStreamSynchronize(c->stream));
-    return FS3D_OK;
+    return gev_sync(c);
 }
 
 template <typename R>
 static fs3d_status update_nodes_impl(fs3d_ctx *c, const uint8_t *type, const uint8_t *bc_vel, const uint8_t *bc_temp, int n_seg_out[3])
 {
     fs3d_geom &g = c->geom;
-    const int dx = c->dimx, dy = c->dimy, dz = c->dimz;
-    const long long plane = c->plane, ncell = c->ncell;
+    const long long ncell = c->ncell;
     GHIP(c, hipMemsetAsync(g.cnt, 0, GC_WORDS * sizeof(unsigned long long), c->stream));
-    hipLaunchKernelGGL(k_geom_lines_strided, dim3(geom_grid((long long)dy * dz, 1 << 30)), dim3(256), 0, c->stream, type, dy, dz,
-                       (long long)dz, plane, dx, g.lst[0], c->dead[0]);
-    hipLaunchKernelGGL(k_geom_lines_strided, dim3(geom_grid((long long)dx * dz, 1 << 30)), dim3(256), 0, c->stream, type, dx, dz,
-                       plane, (long long)dz, dy, g.lst[1], c->dead[1]);
-    hipLaunchKernelGGL(k_geom_lines_z, dim3(geom_grid((long long)dx * dy * 64, 1 << 30)), dim3(256), 0, c->stream, type,
-                       (long long)dx * dy, dz, g.lst[2], c->dead[2]);
+    for (int d = 0; d < 3; d++) {
+        const GeomLines L = geom_lines(c, d);
+        if (d < 2)
+            hipLaunchKernelGGL(k_geom_lines_strided, dim3(geom_grid(L.nlines, 1 << 30)), dim3(256), 0, c->stream, type, L.n_o, c->dimz,
+                               L.os, L.ss, L.n, g.lst[d], c->dead[d]);
+        else
+            hipLaunchKernelGGL(k_geom_lines_z, dim3(geom_grid(L.nlines * 64, 1 << 30)), dim3(256), 0, c->stream, type, L.nlines, c->dimz,
+                               g.lst[d], c->dead[d]);
+    }
     hipLaunchKernelGGL(k_geom_codes, dim3(geom_grid(ncell)), dim3(256), 0, c->stream, type, bc_vel, bc_temp, g.lst[0], g.lst[1],
-                       g.lst[2], dx, dy, dz, c->code, g.cnt);
+                       g.lst[2], c->dimx, c->dimy, c->dimz, c->code, g.cnt);
     GHIP(c, hipGetLastError());
     unsigned long long *hc = (unsigned long long *)g.host;
     GHIP(c, hipMemcpyAsync(hc, g.cnt, GC_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-    gev_end(c);
-    GHIP(c, hipStreamSynchronize(c->stream));
+    GTRY(gev_sync(c));
     if (hc[GC_SHARED])
         return gfail(c, FS3D_ERR_UNSUPPORTED,
                      "fs3d_update_nodes: a cell with a FREE boundary condition closes one segment and opens the next "
@@ -820,11 +830,10 @@ static fs3d_status update_nodes_impl(fs3d_ctx *c, const uint8_t *type, const uin
                            (R *)c->bnd_val[3], g.cnt);
         GHIP(c, hipGetLastError());
     }
-    for (int d = 0; d < 2; d++) { const fs3d_status st = geom_columns(c, d); if (st) return st; }
+    for (int d = 0; d < 2; d++) GTRY(geom_columns(c, d));
     gev_begin(c);
     GHIP(c, hipMemcpyAsync(hc, g.cnt, GC_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-    gev_end(c);
-    GHIP(c, hipStreamSynchronize(c->stream));
+    GTRY(gev_sync(c));
     if ((long long)hc[GC_LIST] != nbnd)
         return gfail(c, FS3D_ERR_HIP, "fs3d_update_nodes: the BOUND / VALVE list does not hold the counted cells");
     if (hc[GC_MISMATCH])
@@ -832,6 +841,29 @@ static fs3d_status update_nodes_impl(fs3d_ctx *c, const uint8_t *type, const uin
     c->n_bnd = (int)nbnd;
     for (int d = 0; d < 3; d++) { c->nseg[d] = (int)nseg[d]; if (n_seg_out) n_seg_out[d] = (int)nseg[d]; }
     return FS3D_OK;
+}
+
+// ---- the seven node arrays on the device, as the extrusion and the voxelisation write them --------------------------------------
+struct NodeArrays {
+    uint8_t *type, *bc_vel, *bc_temp;
+    void *v[4];                                         // vx, vy, vz, T in the context's precision
+    bool any_null() const { return !type || !bc_vel || !bc_temp || !v[0] || !v[1] || !v[2] || !v[3]; }
+    // V == 4 of the two node-writing kernels: dimz % 4 == 0, the byte arrays aligned to 4 bytes and the value arrays to 16
+    bool vec4(int dimz) const
+    {
+        uintptr_t mis = ((uintptr_t)type | (uintptr_t)bc_vel | (uintptr_t)bc_temp) & 3;
+        mis |= ((uintptr_t)v[0] | (uintptr_t)v[1] | (uintptr_t)v[2] | (uintptr_t)v[3]) & 15;
+        return dimz % 4 == 0 && !mis;
+    }
+};
+
+// the context's own: the three byte arrays in the staging buffer, the four value fields in place in the node-value table
+static NodeArrays geom_own_arrays(const fs3d_ctx *c)
+{
+    uint8_t *sg = c->geom.stage;
+    NodeArrays a = {sg, sg + c->ncell, sg + 2 * c->ncell, {}};
+    for (int v = 0; v < 4; v++) a.v[v] = (char *)c->node + (size_t)v * c->nstride * c->esize;
+    return a;
 }
 
 // ---- extrusion of a Shape2D grid ----------------------------------------------------------------------------------------------
@@ -907,21 +939,20 @@ static fs3d_status extrude_check(fs3d_ctx *c, ExtrudeIn &in, const char *name)
 
 // the column records to the device and the kernel, on the context's stream; not synchronised
 template <typename R>
-static fs3d_status extrude_launch(fs3d_ctx *c, const ExtrudeIn &in, uint8_t *type, uint8_t *bc_vel, uint8_t *bc_temp, void *vx, void *vy, void *vz, void *T)
+static fs3d_status extrude_launch(fs3d_ctx *c, const ExtrudeIn &in, const NodeArrays &a)
 {
     fs3d_geom &g = c->geom;
     const size_t ncol = (size_t)c->dimx * c->dimy;
     const char *d = (const char *)g.ex_dev;
     GHIP(c, hipMemcpyAsync(g.ex_dev, g.ex_host, g.ex_bottom_valid ? ex_off_cell(ncol) + ncol : ex_bytes(ncol), hipMemcpyHostToDevice, c->stream));
     g.ex_bottom_valid = true;
-    uintptr_t mis = ((uintptr_t)type | (uintptr_t)bc_vel | (uintptr_t)bc_temp) & 3;
-    mis |= ((uintptr_t)vx | (uintptr_t)vy | (uintptr_t)vz | (uintptr_t)T) & 15;
-    const bool vec = c->dimz % 4 == 0 && !mis;
+    const bool vec = a.vec4(c->dimz);
     const long long nthr = (long long)ncol * (vec ? c->dimz / 4 : c->dimz);
     auto kern = vec ? k_geom_extrude<R, 4> : k_geom_extrude<R, 1>;
     hipLaunchKernelGGL(kern, dim3(geom_grid(nthr, 1 << 30)), dim3(256), 0, c->stream, (const float *)d, (const float *)(d + 4 * ncol),
                        (const float *)(d + 8 * ncol), (const int *)(d + ex_off_bottom(ncol)), (const uint8_t *)(d + ex_off_cell(ncol)),
-                       (long long)ncol, c->dimz, in.A, (float)in.baseT, type, bc_vel, bc_temp, (R *)vx, (R *)vy, (R *)vz, (R *)T);
+                       (long long)ncol, c->dimz, in.A, (float)in.baseT, a.type, a.bc_vel, a.bc_temp, (R *)a.v[0], (R *)a.v[1], (R *)a.v[2],
+                       (R *)a.v[3]);
     GHIP(c, hipGetLastError());
     return FS3D_OK;
 }
@@ -966,8 +997,7 @@ static fs3d_status mesh_check(fs3d_ctx *c, const MeshIn &in, const char *name, b
         for (int q = 0; q < in.nvert; q++)
             if (!(std::fabs(a[q]) <= 65536.0f))
                 return gfail(c, FS3D_ERR_INVALID, std::string(name) + ": a vertex coordinate is not finite or exceeds 65536 grid cells in magnitude");
-    const fs3d_status st = mesh_prepare(c, in.nvert, in.ntri);
-    if (st) return st;
+    GTRY(mesh_prepare(c, in.nvert, in.ntri));
     float *hv = mesh_host_vert(g);
     memcpy(hv, in.x, 4 * (size_t)in.nvert); memcpy(hv + g.mesh_vcap, in.y, 4 * (size_t)in.nvert); memcpy(hv + 2 * (size_t)g.mesh_vcap, in.z, 4 * (size_t)in.nvert);
     *new_idx = g.mesh_ntri_dev != in.ntri || memcmp(mesh_host_idx(g), in.tri, 12 * (size_t)in.ntri) != 0;
@@ -976,45 +1006,44 @@ static fs3d_status mesh_check(fs3d_ctx *c, const MeshIn &in, const char *name, b
 }
 
 // FloodFill on a device type array, on the context's stream; returns synchronised.  with_flag: the rasteriser ran before on the
-// same counters -- its flag word comes back with the first batch of rounds.  An event pair is open on entry and on (successful) return.
+// same counters -- its flag word comes back with the first batch of rounds.  Every batch of rounds is a batch of the device time
+// (the first one goes on with the caller's, where one is open) and ends closed: what the caller launches next begins its own.
 static fs3d_status mesh_fill(fs3d_ctx *c, uint8_t *type, bool with_flag, const char *name)
 {
     fs3d_geom &g = c->geom;
-    const int dx = c->dimx, dy = c->dimy, dz = c->dimz;
     unsigned *hc = mesh_host_cnt(g);
     GHIP(c, hipMemsetAsync(type, FS3D_NODE_OUT, 1, c->stream));      // cell (0,0,0), whatever it was
     g.mesh_fill_rounds = 0;
     // no cap on the rounds: one that changes nothing ends the fill, every other one turns at least one cell
-    for (bool first = true;; first = false) {
+    for (bool first = true, done = false; !done; first = false) {
+        gev_begin(c);
         GHIP(c, hipMemsetAsync(g.mesh_cnt + MC_ROUND, 0, MESH_FILL_BATCH * sizeof(unsigned), c->stream));
-        for (int r = 0; r < MESH_FILL_BATCH; r++) {
-            unsigned *cnt = g.mesh_cnt + MC_ROUND + r;
-            hipLaunchKernelGGL(k_geom_fill_z, dim3(geom_grid((long long)dx * dy * 64, 1 << 30)), dim3(256), 0, c->stream, type, (long long)dx * dy, dz, cnt);
-            hipLaunchKernelGGL(k_geom_fill_strided, dim3(geom_grid((long long)dx * dz, 1 << 30)), dim3(256), 0, c->stream, type, dx, dz,
-                               c->plane, (long long)dz, dy, cnt);
-            hipLaunchKernelGGL(k_geom_fill_strided, dim3(geom_grid((long long)dy * dz, 1 << 30)), dim3(256), 0, c->stream, type, dy, dz,
-                               (long long)dz, c->plane, dx, cnt);
-        }
+        for (int r = 0; r < MESH_FILL_BATCH; r++)
+            for (int d = 2; d >= 0; d--) {
+                const GeomLines L = geom_lines(c, d);
+                unsigned *cnt = g.mesh_cnt + MC_ROUND + r;
+                if (d == 2)
+                    hipLaunchKernelGGL(k_geom_fill_z, dim3(geom_grid(L.nlines * 64, 1 << 30)), dim3(256), 0, c->stream, type, L.nlines, c->dimz, cnt);
+                else
+                    hipLaunchKernelGGL(k_geom_fill_strided, dim3(geom_grid(L.nlines, 1 << 30)), dim3(256), 0, c->stream, type, L.n_o, c->dimz,
+                                       L.os, L.ss, L.n, cnt);
+            }
         GHIP(c, hipGetLastError());
         GHIP(c, hipMemcpyAsync(hc, g.mesh_cnt, MC_WORDS * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
-        gev_end(c);
-        GHIP(c, hipStreamSynchronize(c->stream));
+        GTRY(gev_sync(c));
         if (first && with_flag && hc[MC_FLAG])
             return gfail(c, FS3D_ERR_INVALID, std::string(name) + (hc[MC_FLAG] & MESH_FLAG_SCANLINE
                          ? ": Shape3D: a scan line of a polygon never reaches its end cell (the reference loops there)"
                          : ": Shape3D: the scan of a polygon stops advancing (its triangle is too thin for fp32 at these coordinates; the reference loops there)"));
-        bool done = false;
         for (int r = 0; r < MESH_FILL_BATCH && !done; r++) { g.mesh_fill_rounds++; done = hc[MC_ROUND + r] == 0; }
-        gev_begin(c);
-        if (done) return FS3D_OK;
     }
+    return FS3D_OK;
 }
 
 // vertices (and new indices) to the device, raster, fill and node kernels into the seven arrays, on the context's stream; the
 // node kernel is not waited for
 template <typename R>
-static fs3d_status mesh_launch(fs3d_ctx *c, const MeshIn &in, bool new_idx, const char *name, uint8_t *type, uint8_t *bc_vel, uint8_t *bc_temp,
-                               void *vx, void *vy, void *vz, void *T)
+static fs3d_status mesh_launch(fs3d_ctx *c, const MeshIn &in, bool new_idx, const char *name, const NodeArrays &a)
 {
     fs3d_geom &g = c->geom;
     GHIP(c, hipMemcpyAsync(g.mesh_vert, g.mesh_host, 3 * (size_t)g.mesh_vcap * sizeof(float), hipMemcpyHostToDevice, c->stream));
@@ -1023,92 +1052,71 @@ static fs3d_status mesh_launch(fs3d_ctx *c, const MeshIn &in, bool new_idx, cons
         GHIP(c, hipMemcpyAsync(g.mesh_idx, mesh_host_idx(g), 12 * (size_t)std::max(in.ntri, 1), hipMemcpyHostToDevice, c->stream));
         g.mesh_ntri_dev = in.ntri;
     }
-    GHIP(c, hipMemsetAsync(type, FS3D_NODE_IN, (size_t)c->ncell, c->stream));
+    GHIP(c, hipMemsetAsync(a.type, FS3D_NODE_IN, (size_t)c->ncell, c->stream));
     GHIP(c, hipMemsetAsync(g.mesh_cnt, 0, sizeof(unsigned), c->stream));
     if (in.ntri)
         hipLaunchKernelGGL(k_geom_raster_mesh, dim3((unsigned)in.ntri), dim3(64), 0, c->stream, g.mesh_vert, g.mesh_vert + g.mesh_vcap,
-                           g.mesh_vert + 2 * (size_t)g.mesh_vcap, g.mesh_idx, c->dimx, c->dimy, c->dimz, type, g.mesh_cnt + MC_FLAG);
+                           g.mesh_vert + 2 * (size_t)g.mesh_vcap, g.mesh_idx, c->dimx, c->dimy, c->dimz, a.type, g.mesh_cnt + MC_FLAG);
     GHIP(c, hipGetLastError());
-    const fs3d_status st = mesh_fill(c, type, true, name);
-    if (st) return st;
-    uintptr_t mis = ((uintptr_t)type | (uintptr_t)bc_vel | (uintptr_t)bc_temp) & 3;
-    mis |= ((uintptr_t)vx | (uintptr_t)vy | (uintptr_t)vz | (uintptr_t)T) & 15;
-    const bool vec = c->dimz % 4 == 0 && !mis;
+    GTRY(mesh_fill(c, a.type, true, name));
+    gev_begin(c);
+    const bool vec = a.vec4(c->dimz);
     auto kern = vec ? k_geom_mesh_nodes<R, 4> : k_geom_mesh_nodes<R, 1>;
-    hipLaunchKernelGGL(kern, dim3(geom_grid(vec ? c->ncell / 4 : c->ncell, 1 << 30)), dim3(256), 0, c->stream, type, c->ncell, (R)(float)in.baseT,
-                       bc_vel, bc_temp, (R *)vx, (R *)vy, (R *)vz, (R *)T);
+    hipLaunchKernelGGL(kern, dim3(geom_grid(vec ? c->ncell / 4 : c->ncell, 1 << 30)), dim3(256), 0, c->stream, a.type, c->ncell, (R)(float)in.baseT,
+                       a.bc_vel, a.bc_temp, (R *)a.v[0], (R *)a.v[1], (R *)a.v[2], (R *)a.v[3]);
     GHIP(c, hipGetLastError());
     return FS3D_OK;
 }
 
 static bool geom_is_slab(const fs3d_ctx *c) { return c->dimx != c->dimx_global || c->x_offset != 0 || c->comm || c->local || c->nranks > 1; }
 
-// ex != nullptr: the seven arrays come from the extrusion kernel (fs3d_update_nodes_shape2d); mesh != nullptr: from the
-// voxelisation kernels (fs3d_update_nodes_shape3d)
-static fs3d_status update_nodes_common(fs3d_ctx *c, bool host_arrays, const uint8_t *type, const uint8_t *bc_vel, const uint8_t *bc_temp,
-                                       const void *vx, const void *vy, const void *vz, const void *T, int n_seg_out[3],
-                                       const ExtrudeIn *ex = nullptr, const MeshIn *mesh = nullptr)
+// The refusals every geometry entry begins with, in this order; `what` is the entry's own wording ("moving geometry is", ...).
+static fs3d_status geom_refuse(fs3d_ctx *c, const char *name, bool any_null, const char *what)
 {
-    const char *name = mesh ? "fs3d_update_nodes_shape3d" : ex ? "fs3d_update_nodes_shape2d" : host_arrays ? "fs3d_update_nodes" : "fs3d_update_nodes_dev";
     if (!c) return FS3D_ERR_INVALID;
-    if (mesh ? (!mesh->x || !mesh->y || !mesh->z || !mesh->tri)
-             : ex ? (!ex->cell || !ex->velx || !ex->vely || !ex->T) : (!type || !bc_vel || !bc_temp || !vx || !vy || !vz || !T))
-        return gfail(c, FS3D_ERR_INVALID, std::string(name) + ": NULL array");
+    if (any_null) return gfail(c, FS3D_ERR_INVALID, std::string(name) + ": NULL array");
     if (geom_is_slab(c))
-        return gfail(c, FS3D_ERR_UNSUPPORTED, std::string(name) + ": moving geometry is implemented for a single context only, "
+        return gfail(c, FS3D_ERR_UNSUPPORTED, std::string(name) + ": " + what + " implemented for a single context only, "
                      "not for an x-slab of a larger grid or a member of a multi-GPU group");
+    return FS3D_OK;
+}
+
+// ---- fs3d_update_nodes*: one update, phase by phase ---------------------------------------------------------------------------
+// 1. update_refuse; 2. the entry starts the host clock of CreateSegments and selects the device; 3. the check of its source
+// (extrude_check, mesh_check) -- refused up to here, the context keeps the geometry it has and nothing is counted; 4. update_begin;
+// 5. the entry puts the three byte arrays and the four value fields on the device; 6. update_end.
+typedef std::chrono::steady_clock::time_point geom_clock;
+
+static fs3d_status update_refuse(fs3d_ctx *c, const char *name, bool any_null)
+{
+    GTRY(geom_refuse(c, name, any_null, "moving geometry is"));
     if (!c->uploaded_once)
         return gfail(c, FS3D_ERR_INVALID, std::string(name) + ": the first geometry comes through fs3d_upload_nodes; upload nodes first");
-    const auto t0 = std::chrono::steady_clock::now();
-    GHIP(c, hipSetDevice(c->device));
-    fs3d_status st;
-    ExtrudeIn exin;
-    if (ex) {                                             // refused here, the context keeps the geometry it has
-        exin = *ex;
-        st = extrude_check(c, exin, name);
-        if (st) return st;
-    }
-    bool new_idx = false;
-    if (mesh) {
-        st = mesh_check(c, *mesh, name, &new_idx);
-        if (st) return st;
-    }
-    // rebuilt in place: from here until the end the context has no geometry
+    return FS3D_OK;
+}
+
+// rebuilt in place: from here until the end of update_end the context has no geometry.  Opens the first batch of the device time.
+static fs3d_status update_begin(fs3d_ctx *c, bool need_stage)
+{
     c->have_nodes = false;
-    st = geom_prepare(c, host_arrays || ex || mesh);
-    if (st) return st;
-    const void *val[4] = {vx, vy, vz, T};
+    GTRY(geom_prepare(c, need_stage));
     gev_reset(c);
     gev_begin(c);
-    if (ex || mesh) {
-        // the three byte arrays into the staging buffer, the four value fields straight into the node-value table
-        uint8_t *sg = c->geom.stage;
-        char *nv[4];
-        for (int v = 0; v < 4; v++) { nv[v] = (char *)c->node + (size_t)v * c->nstride * c->esize; val[v] = nv[v]; }
-        if (mesh)
-            st = c->prec == FS3D_F32 ? mesh_launch<float>(c, *mesh, new_idx, name, sg, sg + c->ncell, sg + 2 * c->ncell, nv[0], nv[1], nv[2], nv[3])
-                                     : mesh_launch<double>(c, *mesh, new_idx, name, sg, sg + c->ncell, sg + 2 * c->ncell, nv[0], nv[1], nv[2], nv[3]);
-        else
-            st = c->prec == FS3D_F32 ? extrude_launch<float>(c, exin, sg, sg + c->ncell, sg + 2 * c->ncell, nv[0], nv[1], nv[2], nv[3])
-                                     : extrude_launch<double>(c, exin, sg, sg + c->ncell, sg + 2 * c->ncell, nv[0], nv[1], nv[2], nv[3]);
-        if (st) { hipStreamSynchronize(c->stream); gev_collect(c); return st; }
-        type = sg; bc_vel = sg + c->ncell; bc_temp = sg + 2 * c->ncell;
-    } else if (host_arrays) {
-        const uint8_t *src[3] = {type, bc_vel, bc_temp};
-        for (int a = 0; a < 3; a++)
-            GHIP(c, hipMemcpyAsync(c->geom.stage + (size_t)a * c->ncell, src[a], (size_t)c->ncell, hipMemcpyHostToDevice, c->stream));
-        type = c->geom.stage; bc_vel = type + c->ncell; bc_temp = bc_vel + c->ncell;
-    }
-    // the four node-value fields are one of the tables: copied straight into place
-    for (int v = 0; v < 4; v++) {
-        char *dst = (char *)c->node + (size_t)v * c->nstride * c->esize;
-        if (dst != (const char *)val[v])
-            GHIP(c, hipMemcpyAsync(dst, val[v], (size_t)c->ncell * c->esize, host_arrays ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, c->stream));
-    }
-    st = c->prec == FS3D_F32 ? update_nodes_impl<float>(c, type, bc_vel, bc_temp, n_seg_out)
-                             : update_nodes_impl<double>(c, type, bc_vel, bc_temp, n_seg_out);
+    return FS3D_OK;
+}
+
+// The tables from the byte arrays (the value fields are in the node-value table by now), the device time and the CreateSegments
+// event.  `produced`: what the kernels of phase 5 returned; their failure is waited for, and its time is not counted.
+static fs3d_status update_end(fs3d_ctx *c, geom_clock t0, fs3d_status produced, const uint8_t *type, const uint8_t *bc_vel, const uint8_t *bc_temp,
+                              int n_seg_out[3])
+{
+    fs3d_status st = produced;
+    if (st == FS3D_OK)
+        st = c->prec == FS3D_F32 ? update_nodes_impl<float>(c, type, bc_vel, bc_temp, n_seg_out)
+                                 : update_nodes_impl<double>(c, type, bc_vel, bc_temp, n_seg_out);
     hipStreamSynchronize(c->stream);                      // (a failure half way: the caller's arrays are not read after the call returns)
     gev_collect(c);
+    if (produced) return produced;
     if (st == FS3D_OK) { c->have_nodes = true; c->n_create_segments++; }
     c->t_create_segments_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return st;
@@ -1117,20 +1125,48 @@ static fs3d_status update_nodes_common(fs3d_ctx *c, bool host_arrays, const uint
 extern "C" fs3d_status fs3d_update_nodes(fs3d_ctx *c, const uint8_t *type, const uint8_t *bc_vel, const uint8_t *bc_temp,
                                          const void *vx, const void *vy, const void *vz, const void *T, int n_seg_out[3])
 {
-    return update_nodes_common(c, true, type, bc_vel, bc_temp, vx, vy, vz, T, n_seg_out);
+    GTRY(update_refuse(c, "fs3d_update_nodes", !type || !bc_vel || !bc_temp || !vx || !vy || !vz || !T));
+    const geom_clock t0 = std::chrono::steady_clock::now();
+    GHIP(c, hipSetDevice(c->device));
+    GTRY(update_begin(c, true));
+    const NodeArrays own = geom_own_arrays(c);
+    GHIP(c, hipMemcpyAsync(own.type, type, (size_t)c->ncell, hipMemcpyHostToDevice, c->stream));
+    GHIP(c, hipMemcpyAsync(own.bc_vel, bc_vel, (size_t)c->ncell, hipMemcpyHostToDevice, c->stream));
+    GHIP(c, hipMemcpyAsync(own.bc_temp, bc_temp, (size_t)c->ncell, hipMemcpyHostToDevice, c->stream));
+    // the four node-value fields are one of the tables: copied straight into place
+    const void *val[4] = {vx, vy, vz, T};
+    for (int v = 0; v < 4; v++) GHIP(c, hipMemcpyAsync(own.v[v], val[v], (size_t)c->ncell * c->esize, hipMemcpyHostToDevice, c->stream));
+    return update_end(c, t0, FS3D_OK, own.type, own.bc_vel, own.bc_temp, n_seg_out);
 }
 
 extern "C" fs3d_status fs3d_update_nodes_dev(fs3d_ctx *c, const uint8_t *type, const uint8_t *bc_vel, const uint8_t *bc_temp,
                                              const void *vx, const void *vy, const void *vz, const void *T, int n_seg_out[3])
 {
-    return update_nodes_common(c, false, type, bc_vel, bc_temp, vx, vy, vz, T, n_seg_out);
+    GTRY(update_refuse(c, "fs3d_update_nodes_dev", !type || !bc_vel || !bc_temp || !vx || !vy || !vz || !T));
+    const geom_clock t0 = std::chrono::steady_clock::now();
+    GHIP(c, hipSetDevice(c->device));
+    GTRY(update_begin(c, false));                         // the byte arrays are read where they are
+    const void *val[4] = {vx, vy, vz, T};
+    for (int v = 0; v < 4; v++) {
+        void *dst = (char *)c->node + (size_t)v * c->nstride * c->esize;
+        if (dst != val[v]) GHIP(c, hipMemcpyAsync(dst, val[v], (size_t)c->ncell * c->esize, hipMemcpyDeviceToDevice, c->stream));
+    }
+    return update_end(c, t0, FS3D_OK, type, bc_vel, bc_temp, n_seg_out);
 }
 
 extern "C" fs3d_status fs3d_update_nodes_shape2d(fs3d_ctx *c, const uint8_t *cell2d, const float *velx2d, const float *vely2d, const float *T2d,
                                                  double dz, double depth, double depth_var, double baseT, int n_seg_out[3])
 {
-    const ExtrudeIn in = {cell2d, velx2d, vely2d, T2d, dz, depth, depth_var, baseT, 0};
-    return update_nodes_common(c, false, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, n_seg_out, &in);
+    const char *name = "fs3d_update_nodes_shape2d";
+    GTRY(update_refuse(c, name, !cell2d || !velx2d || !vely2d || !T2d));
+    const geom_clock t0 = std::chrono::steady_clock::now();
+    GHIP(c, hipSetDevice(c->device));
+    ExtrudeIn in = {cell2d, velx2d, vely2d, T2d, dz, depth, depth_var, baseT, 0};
+    GTRY(extrude_check(c, in, name));
+    GTRY(update_begin(c, true));
+    const NodeArrays own = geom_own_arrays(c);
+    const fs3d_status st = c->prec == FS3D_F32 ? extrude_launch<float>(c, in, own) : extrude_launch<double>(c, in, own);
+    return update_end(c, t0, st, own.type, own.bc_vel, own.bc_temp, n_seg_out);
 }
 
 extern "C" fs3d_status fs3d_extrude_shape2d_dev(fs3d_ctx *c, const uint8_t *cell2d, const float *velx2d, const float *vely2d, const float *T2d,
@@ -1138,18 +1174,11 @@ extern "C" fs3d_status fs3d_extrude_shape2d_dev(fs3d_ctx *c, const uint8_t *cell
                                                 uint8_t *bc_vel_out, uint8_t *bc_temp_out, void *vx_out, void *vy_out, void *vz_out, void *T_out)
 {
     const char *name = "fs3d_extrude_shape2d_dev";
-    if (!c) return FS3D_ERR_INVALID;
-    if (!cell2d || !velx2d || !vely2d || !T2d || !type_out || !bc_vel_out || !bc_temp_out || !vx_out || !vy_out || !vz_out || !T_out)
-        return gfail(c, FS3D_ERR_INVALID, std::string(name) + ": NULL array");
-    if (geom_is_slab(c))
-        return gfail(c, FS3D_ERR_UNSUPPORTED, std::string(name) + ": the extrusion is implemented for a single context only, "
-                     "not for an x-slab of a larger grid or a member of a multi-GPU group");
+    const NodeArrays out = {type_out, bc_vel_out, bc_temp_out, {vx_out, vy_out, vz_out, T_out}};
+    GTRY(geom_refuse(c, name, !cell2d || !velx2d || !vely2d || !T2d || out.any_null(), "the extrusion is"));
     ExtrudeIn in = {cell2d, velx2d, vely2d, T2d, dz, depth, depth_var, baseT, 0};
-    fs3d_status st = extrude_check(c, in, name);
-    if (st) return st;
-    st = c->prec == FS3D_F32 ? extrude_launch<float>(c, in, type_out, bc_vel_out, bc_temp_out, vx_out, vy_out, vz_out, T_out)
-                             : extrude_launch<double>(c, in, type_out, bc_vel_out, bc_temp_out, vx_out, vy_out, vz_out, T_out);
-    if (st) return st;
+    GTRY(extrude_check(c, in, name));
+    GTRY(c->prec == FS3D_F32 ? extrude_launch<float>(c, in, out) : extrude_launch<double>(c, in, out));
     GHIP(c, hipStreamSynchronize(c->stream));
     return FS3D_OK;
 }
@@ -1157,8 +1186,17 @@ extern "C" fs3d_status fs3d_extrude_shape2d_dev(fs3d_ctx *c, const uint8_t *cell
 extern "C" fs3d_status fs3d_update_nodes_shape3d(fs3d_ctx *c, const float *x, const float *y, const float *z, int nvert, const int *tri, int ntri,
                                                  double baseT, int n_seg_out[3])
 {
+    const char *name = "fs3d_update_nodes_shape3d";
+    GTRY(update_refuse(c, name, !x || !y || !z || !tri));
+    const geom_clock t0 = std::chrono::steady_clock::now();
+    GHIP(c, hipSetDevice(c->device));
     const MeshIn in = {x, y, z, nvert, tri, ntri, baseT};
-    return update_nodes_common(c, false, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, n_seg_out, nullptr, &in);
+    bool new_idx = false;
+    GTRY(mesh_check(c, in, name, &new_idx));
+    GTRY(update_begin(c, true));
+    const NodeArrays own = geom_own_arrays(c);
+    const fs3d_status st = c->prec == FS3D_F32 ? mesh_launch<float>(c, in, new_idx, name, own) : mesh_launch<double>(c, in, new_idx, name, own);
+    return update_end(c, t0, st, own.type, own.bc_vel, own.bc_temp, n_seg_out);
 }
 
 extern "C" fs3d_status fs3d_voxelize_shape3d_dev(fs3d_ctx *c, const float *x, const float *y, const float *z, int nvert, const int *tri, int ntri,
@@ -1166,19 +1204,13 @@ extern "C" fs3d_status fs3d_voxelize_shape3d_dev(fs3d_ctx *c, const float *x, co
                                                  void *vy_out, void *vz_out, void *T_out)
 {
     const char *name = "fs3d_voxelize_shape3d_dev";
-    if (!c) return FS3D_ERR_INVALID;
-    if (!x || !y || !z || !tri || !type_out || !bc_vel_out || !bc_temp_out || !vx_out || !vy_out || !vz_out || !T_out)
-        return gfail(c, FS3D_ERR_INVALID, std::string(name) + ": NULL array");
-    if (geom_is_slab(c))
-        return gfail(c, FS3D_ERR_UNSUPPORTED, std::string(name) + ": the voxelisation is implemented for a single context only, "
-                     "not for an x-slab of a larger grid or a member of a multi-GPU group");
+    const NodeArrays out = {type_out, bc_vel_out, bc_temp_out, {vx_out, vy_out, vz_out, T_out}};
+    GTRY(geom_refuse(c, name, !x || !y || !z || !tri || out.any_null(), "the voxelisation is"));
     const MeshIn in = {x, y, z, nvert, tri, ntri, baseT};
     bool new_idx = false;
-    fs3d_status st = mesh_check(c, in, name, &new_idx);
-    if (st) return st;
+    GTRY(mesh_check(c, in, name, &new_idx));
     gev_reset(c);                                        // (no update: its device time is not reported)
-    st = c->prec == FS3D_F32 ? mesh_launch<float>(c, in, new_idx, name, type_out, bc_vel_out, bc_temp_out, vx_out, vy_out, vz_out, T_out)
-                             : mesh_launch<double>(c, in, new_idx, name, type_out, bc_vel_out, bc_temp_out, vx_out, vy_out, vz_out, T_out);
+    const fs3d_status st = c->prec == FS3D_F32 ? mesh_launch<float>(c, in, new_idx, name, out) : mesh_launch<double>(c, in, new_idx, name, out);
     const hipError_t e = hipStreamSynchronize(c->stream);
     gev_reset(c);
     if (st) return st;
@@ -1189,15 +1221,10 @@ extern "C" fs3d_status fs3d_voxelize_shape3d_dev(fs3d_ctx *c, const float *x, co
 extern "C" fs3d_status fs3d_flood_fill_dev(fs3d_ctx *c, uint8_t *type_inout)
 {
     const char *name = "fs3d_flood_fill_dev";
-    if (!c) return FS3D_ERR_INVALID;
-    if (!type_inout) return gfail(c, FS3D_ERR_INVALID, std::string(name) + ": NULL array");
-    if (geom_is_slab(c))
-        return gfail(c, FS3D_ERR_UNSUPPORTED, std::string(name) + ": the flood fill is implemented for a single context only, "
-                     "not for an x-slab of a larger grid or a member of a multi-GPU group");
-    fs3d_status st = mesh_prepare(c, 0, 0);
-    if (st) return st;
+    GTRY(geom_refuse(c, name, !type_inout, "the flood fill is"));
+    GTRY(mesh_prepare(c, 0, 0));
     gev_reset(c);
-    st = mesh_fill(c, type_inout, false, name);
+    const fs3d_status st = mesh_fill(c, type_inout, false, name);
     gev_reset(c);
     return st;
 }
@@ -1244,17 +1271,16 @@ extern "C" fs3d_status fs3d_geometry_info(fs3d_ctx *c, long long info[FS3D_N_GEO
     for (int d = 0; d < 3; d++) info[d] = c->nseg[d];
     info[3] = c->n_bnd;
     info[4] = c->stale_in_cells;
-    const long long nl[3] = {(long long)c->dimy * c->dimz, (long long)c->dimx * c->dimz, (long long)c->dimx * c->dimy};
     std::vector<uint8_t> hb;
     for (int d = 0; d < 3; d++) {
-        hb.resize((size_t)nl[d]);
-        GHIP(c, hipMemcpyAsync(hb.data(), c->dead[d], (size_t)nl[d], hipMemcpyDeviceToHost, c->stream));
+        hb.resize((size_t)geom_lines(c, d).nlines);
+        GHIP(c, hipMemcpyAsync(hb.data(), c->dead[d], hb.size(), hipMemcpyDeviceToHost, c->stream));
         GHIP(c, hipStreamSynchronize(c->stream));
         for (uint8_t b : hb) info[5 + d] += b != 0;
     }
     for (int d = 0; d < 2; d++) {
         if (!c->uflag[d]) continue;
-        std::vector<unsigned> fl((size_t)geom_n_o(c, d) * geom_ng(c));
+        std::vector<unsigned> fl((size_t)geom_lines(c, d).n_o * geom_ng(c));
         GHIP(c, hipMemcpyAsync(fl.data(), c->uflag[d], fl.size() * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
         GHIP(c, hipStreamSynchronize(c->stream));
         for (unsigned f : fl) info[8 + d] += f & 1;

@@ -57,24 +57,33 @@ struct RunGeom {
     int GetFrame(double t) const { return g2 ? g2->GetFrame(t) : 0; }
 };
 
+// the words after <config file>, as main's argument loop finds them
+struct RunOptions {
+    bool align = false, dbl = false, csv = false, same_device = false, grid_images = false;
+    bool moving = false, host_extrusion = false, moving_mesh = false, host_voxels = false, time_geometry = false, time_both = false;
+    double grid_time = -1;
+    int nslabs = 1, device = 0;
+    long max_steps = -1;
+    std::string grid_only;
+};
+
 template <typename FTYPE>
 static int run_slabs(const fs3d::Grid3D<FTYPE> &grid, const RunGeom &geo, const std::string &prefix, const fs3d::Config &cfg, int nslabs,
                      bool same_device, long max_steps, bool csv);
 
 template <typename FTYPE>
-static int run(const std::string &data, const std::string &prefix, const fs3d::Config &cfg, bool align, int device, long max_steps, const std::string &grid_only, bool csv,
-               int nslabs, bool same_device, bool grid_images, bool moving, double grid_time, bool host_extrusion, bool time_geometry, bool moving_mesh, bool host_voxels, bool time_both)
+static int run(const std::string &data, const std::string &prefix, const fs3d::Config &cfg, const RunOptions &o)
 {
-    if (moving && cfg.in_fmt != "Shape2D") throw std::runtime_error("moving: only in_fmt Shape2D inputs move (this one is " + cfg.in_fmt + ")");
-    if (moving && nslabs > 1) throw std::runtime_error("moving: single GPU only (moving geometry on x-slabs is not implemented)");
-    if (host_extrusion && !moving) throw std::runtime_error("--host-extrusion: only with moving (it selects where a moving geometry is extruded)");
-    if (moving_mesh && cfg.in_fmt != "Shape3D") throw std::runtime_error("moving-mesh: only in_fmt Shape3D inputs are meshes (this one is " + cfg.in_fmt + "; Shape2D inputs move with `moving`)");
-    if (moving_mesh && nslabs > 1) throw std::runtime_error("moving-mesh: single GPU only (moving geometry on x-slabs is not implemented)");
-    if (moving_mesh && moving) throw std::runtime_error("moving-mesh: not together with moving");
-    if (host_voxels && !moving_mesh) throw std::runtime_error("--host-voxels: only with moving-mesh (it selects where a moving mesh is voxelised)");
-    if (time_both && !moving_mesh) throw std::runtime_error("--time-both: only with moving-mesh (it times both ways of making a mesh's geometry)");
-    if (time_geometry && !moving && !moving_mesh) throw std::runtime_error("--time-geometry: only with moving or moving-mesh (it times the per-step geometry work)");
-    if (grid_time >= 0 && cfg.in_fmt != "Shape2D" && cfg.in_fmt != "Shape3D") throw std::runtime_error("--grid-time: only in_fmt Shape2D and Shape3D inputs move");
+    if (o.moving && cfg.in_fmt != "Shape2D") throw std::runtime_error("moving: only in_fmt Shape2D inputs move (this one is " + cfg.in_fmt + ")");
+    if (o.moving && o.nslabs > 1) throw std::runtime_error("moving: single GPU only (moving geometry on x-slabs is not implemented)");
+    if (o.host_extrusion && !o.moving) throw std::runtime_error("--host-extrusion: only with moving (it selects where a moving geometry is extruded)");
+    if (o.moving_mesh && cfg.in_fmt != "Shape3D") throw std::runtime_error("moving-mesh: only in_fmt Shape3D inputs are meshes (this one is " + cfg.in_fmt + "; Shape2D inputs move with `moving`)");
+    if (o.moving_mesh && o.nslabs > 1) throw std::runtime_error("moving-mesh: single GPU only (moving geometry on x-slabs is not implemented)");
+    if (o.moving_mesh && o.moving) throw std::runtime_error("moving-mesh: not together with moving");
+    if (o.host_voxels && !o.moving_mesh) throw std::runtime_error("--host-voxels: only with moving-mesh (it selects where a moving mesh is voxelised)");
+    if (o.time_both && !o.moving_mesh) throw std::runtime_error("--time-both: only with moving-mesh (it times both ways of making a mesh's geometry)");
+    if (o.time_geometry && !o.moving && !o.moving_mesh) throw std::runtime_error("--time-geometry: only with moving or moving-mesh (it times the per-step geometry work)");
+    if (o.grid_time >= 0 && cfg.in_fmt != "Shape2D" && cfg.in_fmt != "Shape3D") throw std::runtime_error("--grid-time: only in_fmt Shape2D and Shape3D inputs move");
     using namespace fs3d;
     Grid3D<FTYPE> grid;
     Grid2D g2;
@@ -83,17 +92,17 @@ static int run(const std::string &data, const std::string &prefix, const fs3d::C
     SeaNetCDF sea;
     if (cfg.in_fmt == "SeaNetCDF") {
         std::printf("Geometry: depths from NetCDF\n");                                           // FluidSolver3D.cpp:133-138
-        sea.Load(grid, data, cfg.dx, cfg.dy, cfg.dz, cfg.baseT, cfg.bc_inV, cfg.bc_inT, align);
+        sea.Load(grid, data, cfg.dx, cfg.dy, cfg.dz, cfg.baseT, cfg.bc_inV, cfg.bc_inT, o.align);
         geo.frames = 1; geo.length = cfg.frame_time; geo.depths = &sea.depths;                   // num_frames = 1, Grid3D.cpp:483
         for (int a = 0; a < 6; a++) geo.bbox[a] = sea.bbox[a];
     } else if (cfg.in_fmt == "Shape3D") {
         std::printf("Geometry: 3D polygons\n");                                                  // FluidSolver3D.cpp:121-126
-        LoadShape3D(grid, sh3, data, cfg.dx, cfg.dy, cfg.dz, cfg.baseT, align);
+        LoadShape3D(grid, sh3, data, cfg.dx, cfg.dy, cfg.dz, cfg.baseT, o.align);
         geo.frames = sh3.GetFramesNum(); geo.length = cfg.frame_time;                            // Grid3D.cpp:298-309
         for (int a = 0; a < 6; a++) geo.bbox[a] = sh3.bbox[a];
     } else {
         std::printf("Geometry: extruded 2D shape\n");                                            // :127-132
-        LoadShape2D(grid, g2, data, cfg.dx, cfg.dy, cfg.dz, cfg.depth, cfg.depth_var, cfg.baseT, align);
+        LoadShape2D(grid, g2, data, cfg.dx, cfg.dy, cfg.dz, cfg.depth, cfg.depth_var, cfg.baseT, o.align);
         geo.frames = g2.GetFramesNum(); geo.length = g2.GetCycleLenght(); geo.g2 = &g2;
         const float bb[6] = {g2.bbox[0], g2.bbox[1], 0.0f, g2.bbox[2], g2.bbox[3], (float)cfg.depth};   // BBox3D(bbox2D, depth), :203
         for (int a = 0; a < 6; a++) geo.bbox[a] = bb[a];
@@ -103,12 +112,12 @@ static int run(const std::string &data, const std::string &prefix, const fs3d::C
     for (uint8_t t : grid.type) inside += t == NODE_IN;
     std::printf("NODE_IN points = %f of total %f, volume = %f\n", inside, (double)grid.dimx * grid.dimy * grid.dimz,
                 inside * grid.dx * grid.dy * grid.dz);                                          // :170
-    if (grid_images) OutputGridImages(grid, prefix + "_grid_3d");                             // FluidSolver3D.cpp:152-153 (there: always)
-    if (!grid_only.empty()) {
-        if (grid_time >= 0 && cfg.in_fmt == "Shape3D") { sh3.Prepare(grid_time); FillShape3DNodes(grid, sh3, cfg.baseT); }
-        else if (grid_time >= 0) { g2.Prepare(grid_time); ExtrudeShape2D(grid, g2, cfg.dz, cfg.depth, cfg.depth_var, cfg.baseT); }
-        FILE *f = std::fopen(grid_only.c_str(), "wb");
-        if (!f) throw std::runtime_error("cannot create " + grid_only);
+    if (o.grid_images) OutputGridImages(grid, prefix + "_grid_3d");                             // FluidSolver3D.cpp:152-153 (there: always)
+    if (!o.grid_only.empty()) {
+        if (o.grid_time >= 0 && cfg.in_fmt == "Shape3D") { sh3.Prepare(o.grid_time); FillShape3DNodes(grid, sh3, cfg.baseT); }
+        else if (o.grid_time >= 0) { g2.Prepare(o.grid_time); ExtrudeShape2D(grid, g2, cfg.dz, cfg.depth, cfg.depth_var, cfg.baseT); }
+        FILE *f = std::fopen(o.grid_only.c_str(), "wb");
+        if (!f) throw std::runtime_error("cannot create " + o.grid_only);
         const int hdr[4] = {grid.dimx, grid.dimy, grid.dimz, (int)sizeof(FTYPE)};
         std::fwrite(hdr, sizeof hdr, 1, f);
         std::fwrite(grid.type.data(), 1, grid.type.size(), f); std::fwrite(grid.bc_vel.data(), 1, grid.bc_vel.size(), f);
@@ -117,11 +126,11 @@ static int run(const std::string &data, const std::string &prefix, const fs3d::C
         std::fclose(f);
         return 0;
     }
-    if (nslabs > 1) return run_slabs<FTYPE>(grid, geo, prefix, cfg, nslabs, same_device, max_steps, csv);
+    if (o.nslabs > 1) return run_slabs<FTYPE>(grid, geo, prefix, cfg, o.nslabs, o.same_device, o.max_steps, o.csv);
     FluidParams<FTYPE> params = cfg.useNormalizedParams ? FluidParams<FTYPE>(cfg.Re, cfg.Pr, cfg.lambda)
                                                         : FluidParams<FTYPE>(cfg.viscosity, cfg.density, cfg.R_specific, cfg.k, cfg.cv);
     AdiSolver3D<FTYPE> solver;
-    solver.Init(device, grid, params);
+    solver.Init(o.device, grid, params);
     std::printf("Segments: %i %i %i (x, y, z)\n", solver.numSegs[0], solver.numSegs[1], solver.numSegs[2]);
 
     const int frames = geo.frames;                                     // FluidSolver3D.cpp:194-195
@@ -143,59 +152,52 @@ static int run(const std::string &data, const std::string &prefix, const fs3d::C
     double t = dt;
     long steps = 0;
     int lastframe = -1;
-    double geom_ms[3] = {0, 0, 0};                     // moving: host clock around Prepare, the host extrusion, the update call
+    double geom_ms[3] = {0, 0, 0};                     // moving / moving-mesh: host clock around Prepare / SubFrame, the node arrays on the host, the update call
     std::vector<float> mx, my, mz;                     // moving-mesh: the sub-frame's vertices
     std::vector<double> ab_host, ab_dev, ab_dev_gpu, ab_step;   // --time-both: per step, ms
     int fill_rounds = 0;
     auto ms_since = [](std::chrono::steady_clock::time_point a) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - a).count(); };
     // the geometry is frame 0's for the whole run: the reference prepares the grid once, before the loop (grid->Prepare(0), :226;
     // the per-step grid->Prepare(t) is commented out, :237) -- the frame only restarts the substep counter
-    for (int i = 0; t < finaltime && (max_steps < 0 || steps < max_steps); t += dt, i++, steps++) {
+    for (int i = 0; t < finaltime && (o.max_steps < 0 || steps < o.max_steps); t += dt, i++, steps++) {
         const int currentframe = geo.GetFrame(t);                                                        // :229-236
         if (currentframe != lastframe) { lastframe = currentframe; i = 0; }
-        if (moving) {                                                                                    // grid->Prepare(t), :237
-            const auto g0 = std::chrono::steady_clock::now();
-            g2.Prepare(t);
-            const auto g1 = std::chrono::steady_clock::now();
-            if (host_extrusion) ExtrudeShape2D(grid, g2, cfg.dz, cfg.depth, cfg.depth_var, cfg.baseT);
-            const auto g3 = std::chrono::steady_clock::now();
-            if (host_extrusion) solver.UpdateGrid(grid);
-            else solver.UpdateGridExtruded(g2, cfg.dz, cfg.depth, cfg.depth_var);   // `grid` keeps the nodes of time 0: only its dims and baseT are read from here on
-            const auto g4 = std::chrono::steady_clock::now();
-            geom_ms[0] += std::chrono::duration<double, std::milli>(g1 - g0).count();
-            geom_ms[1] += std::chrono::duration<double, std::milli>(g3 - g1).count();
-            geom_ms[2] += std::chrono::duration<double, std::milli>(g4 - g3).count();
-        }
-        if (moving_mesh) {                                                                               // grid->Prepare(t), :237
-            if (time_both) {                                                                             // the other path first
+        if (o.moving || o.moving_mesh) {                                                                 // grid->Prepare(t), :237
+            const bool on_host = o.moving ? o.host_extrusion : o.host_voxels;     // the node arrays are made on the host and go through UpdateGrid
+            if (o.time_both) {                                                                           // the other path first (mesh only)
                 const auto b0 = std::chrono::steady_clock::now();
-                if (host_voxels) { solver.UpdateGridShape3D(mx, my, mz, sh3.frames[sh3.SubFrame(t, mx, my, mz)].idx); ab_dev.push_back(ms_since(b0)); }
+                if (o.host_voxels) { solver.UpdateGridShape3D(mx, my, mz, sh3.frames[sh3.SubFrame(t, mx, my, mz)].idx); ab_dev.push_back(ms_since(b0)); }
                 else { sh3.Prepare(t); FillShape3DNodes(grid, sh3, cfg.baseT); solver.UpdateGrid(grid); ab_host.push_back(ms_since(b0)); }
             }
             const auto g0 = std::chrono::steady_clock::now();
-            const size_t frame = sh3.SubFrame(t, mx, my, mz);
+            size_t frame = 0;
+            if (o.moving) g2.Prepare(t);
+            else frame = sh3.SubFrame(t, mx, my, mz);
             const auto g1 = std::chrono::steady_clock::now();
-            if (host_voxels) { sh3.Prepare(t); FillShape3DNodes(grid, sh3, cfg.baseT); }
+            if (on_host && o.moving) ExtrudeShape2D(grid, g2, cfg.dz, cfg.depth, cfg.depth_var, cfg.baseT);
+            else if (on_host) { sh3.Prepare(t); FillShape3DNodes(grid, sh3, cfg.baseT); }
             const auto g3 = std::chrono::steady_clock::now();
-            if (host_voxels) solver.UpdateGrid(grid);
-            else solver.UpdateGridShape3D(mx, my, mz, sh3.frames[frame].idx);   // `grid` keeps the nodes of time 0: only its dims and baseT are read from here on
+            // (on the device, `grid` keeps the nodes of time 0: only its dims and baseT are read from here on)
+            if (on_host) solver.UpdateGrid(grid);
+            else if (o.moving) solver.UpdateGridExtruded(g2, cfg.dz, cfg.depth, cfg.depth_var);
+            else solver.UpdateGridShape3D(mx, my, mz, sh3.frames[frame].idx);
             const auto g4 = std::chrono::steady_clock::now();
             geom_ms[0] += std::chrono::duration<double, std::milli>(g1 - g0).count();
             geom_ms[1] += std::chrono::duration<double, std::milli>(g3 - g1).count();
             geom_ms[2] += std::chrono::duration<double, std::milli>(g4 - g3).count();
-            if (time_both) (host_voxels ? ab_host : ab_dev).push_back(std::chrono::duration<double, std::milli>(g4 - g0).count());
+            if (o.time_both) (o.host_voxels ? ab_host : ab_dev).push_back(std::chrono::duration<double, std::milli>(g4 - g0).count());
         }
-        if (time_both) {
+        if (o.time_both) {
             // (with --host-voxels the device path ran first: its device time was overwritten by the host path's update)
             float dms = 0;
-            if (!host_voxels && fs3d_last_update_device_ms(solver.ctx(), &dms) == FS3D_OK) ab_dev_gpu.push_back(dms);
+            if (!o.host_voxels && fs3d_last_update_device_ms(solver.ctx(), &dms) == FS3D_OK) ab_dev_gpu.push_back(dms);
             fs3d_mesh_fill_rounds(solver.ctx(), &fill_rounds);
             fs3d_synchronize(solver.ctx());
         }
         const auto s0 = std::chrono::steady_clock::now();
         solver.UpdateBoundaries();                                                                       // :244
         solver.TimeStep((FTYPE)dt, cfg.num_global, cfg.num_local, (i % 10 == 0) || (t + dt >= finaltime)); // :245
-        if (time_both) { fs3d_synchronize(solver.ctx()); ab_step.push_back(ms_since(s0)); }
+        if (o.time_both) { fs3d_synchronize(solver.ctx()); ab_step.push_back(ms_since(s0)); }
         std::printf("\rerr = %.8f,", solver.diffError);                                                  // AdiSolver3D.cpp:376
         const float elapsed = std::chrono::duration<float>(std::chrono::steady_clock::now() - t0).count();
         const float perres = (float)t * 100 / (float)finaltime;                                          // PrintTimeStepInfo, IO.h:455-478
@@ -209,7 +211,7 @@ static int run(const std::string &data, const std::string &prefix, const fs3d::C
             solver.GetLayer(resVel.data(), resT.data(), cfg.outdimx, cfg.outdimy, cfg.outdimz);
             nc.AppendLayer(resVel.data(), resT.data());
         }
-        if (moving || moving_mesh) solver.ClearOutterCells();                                                           // AdiSolver3D.cpp:382-385
+        if (o.moving || o.moving_mesh) solver.ClearOutterCells();                                                           // AdiSolver3D.cpp:382-385
     }
     const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     // the reference's Profiler table (Common/Profiler.h:90-131: sorted by total time, events that never ran are absent; event
@@ -221,14 +223,14 @@ static int run(const std::string &data, const std::string &prefix, const fs3d::C
     for (int e = 0; e < FS3D_N_EVENTS; e++) if (cnt[e]) order.push_back(e);
     std::sort(order.begin(), order.end(), [&](int a, int b) { return ms[a] > ms[b]; });
     double total = 0;
-    if (csv) std::printf("\n%s,%s,%s,%s,\n", "Event Name", "Total (ms)", "Avg (ms)", "Count");
+    if (o.csv) std::printf("\n%s,%s,%s,%s,\n", "Event Name", "Total (ms)", "Avg (ms)", "Count");
     else std::printf("\nProfiling data node(0):\n%16s%16s%16s%16s\n", "Event Name", "Total (ms)", "Avg (ms)", "Count");
     for (int e : order) {
-        if (csv) std::printf("%s,%.2f,%.2f,%i,\n", names[e], ms[e], ms[e] / cnt[e], cnt[e]);
+        if (o.csv) std::printf("%s,%.2f,%.2f,%i,\n", names[e], ms[e], ms[e] / cnt[e], cnt[e]);
         else std::printf("%16s%16.2f%16.2f%16i\n", names[e], ms[e], ms[e] / cnt[e], cnt[e]);
         total += ms[e];
     }
-    if (csv) std::printf("%s,%.2f,sec\n", "Overall", total / 1000);
+    if (o.csv) std::printf("%s,%.2f,sec\n", "Overall", total / 1000);
     else std::printf("%16s%16.2f sec\n", "Overall", total / 1000);
     {
         int kx, ky, kz, sg;
@@ -236,10 +238,11 @@ static int run(const std::string &data, const std::string &prefix, const fs3d::C
         fs3d_last_sweep_kernel(solver.ctx(), 0, &kx, &sg); fs3d_last_sweep_kernel(solver.ctx(), 1, &ky, &sg); fs3d_last_sweep_kernel(solver.ctx(), 2, &kz, &sg);
         std::printf("Sweep kernels: X %s, Y %s, Z %s\n", kn[kx & 3], kn[ky & 3], kn[kz & 3]);
     }
-    if (moving_mesh && time_geometry && steps > 0)
-        std::printf("Moving mesh per step (host clock, ms): SubFrame %.3f, voxels on the host %.3f, update call %.3f; step %.3f\n",
+    if (o.time_geometry && steps > 0)                  // (before the line of --time-both, which only a mesh has)
+        std::printf(o.moving ? "Moving geometry per step (host clock, ms): Prepare %.3f, extrusion on the host %.3f, update call %.3f; step %.3f\n"
+                             : "Moving mesh per step (host clock, ms): SubFrame %.3f, voxels on the host %.3f, update call %.3f; step %.3f\n",
                     geom_ms[0] / steps, geom_ms[1] / steps, geom_ms[2] / steps, sec * 1e3 / steps);
-    if (time_both) {
+    if (o.time_both) {
         auto line = [](const char *what, std::vector<double> v) {
             if (v.size() <= 3) { std::printf(" %s: too few steps;", what); return; }
             v.erase(v.begin(), v.begin() + 3);
@@ -252,9 +255,6 @@ static int run(const std::string &data, const std::string &prefix, const fs3d::C
         line("time step", ab_step);
         std::printf(" fill rounds %d\n", fill_rounds);
     }
-    if (moving && time_geometry && steps > 0)
-        std::printf("Moving geometry per step (host clock, ms): Prepare %.3f, extrusion on the host %.3f, update call %.3f; step %.3f\n",
-                    geom_ms[0] / steps, geom_ms[1] / steps, geom_ms[2] / steps, sec * 1e3 / steps);
     std::printf("%ld steps in %.3f s: %.1f Mcells/s; %u layers in %s\n", steps, sec,
                 (double)grid.dimx * grid.dimy * grid.dimz * steps / sec / 1e6, nc.NumRecords(), out.c_str());
     return 0;
@@ -374,35 +374,29 @@ int main(int argc, char **argv)
         if (cfg.in_fmt != "Shape2D" && cfg.in_fmt != "Shape3D" && cfg.in_fmt != "SeaNetCDF") throw std::runtime_error("in_fmt " + cfg.in_fmt + ": unknown input format");
         if (cfg.in_fmt != "Shape2D" && !(cfg.frame_time > 0)) throw std::runtime_error("must specify frame time!");   // the cycle length of a Shape3D run (Grid3D.cpp:303-309)
         if (cfg.solver != "ADI") throw std::runtime_error("solver " + cfg.solver + " is not implemented (the reference implements ADI only)");
-        bool align = false, dbl = false, csv = false, same_device = false, grid_images = false, moving = false, host_extrusion = false, time_geometry = false, moving_mesh = false, host_voxels = false, time_both = false;
-        double grid_time = -1;
-        int nslabs = 1;
-        int device = 0;
-        long max_steps = -1;
-        std::string grid_only;
+        RunOptions o;
         for (int a = 4; a < argc; a++) {
             const std::string s = argv[a];
-            if (s == "align") align = true;
-            else if (s == "GPU") { if (a + 1 < argc && std::atoi(argv[a + 1]) > 0) nslabs = std::atoi(argv[++a]); }   // the reference's "GPU n": n devices of one process
-            else if (s == "--same-device") same_device = true;
-            else if (s == "double") dbl = true;
-            else if (s == "--device" && a + 1 < argc) device = std::atoi(argv[++a]);
-            else if (s == "--steps" && a + 1 < argc) max_steps = std::atol(argv[++a]);
-            else if (s == "--grid-only" && a + 1 < argc) grid_only = argv[++a];
-            else if (s == "--grid-time" && a + 1 < argc) grid_time = std::atof(argv[++a]);
-            else if (s == "moving") moving = true;
-            else if (s == "moving-mesh") moving_mesh = true;
-            else if (s == "--host-voxels") host_voxels = true;
-            else if (s == "--time-both") time_both = true;
-            else if (s == "--host-extrusion") host_extrusion = true;
-            else if (s == "--time-geometry") time_geometry = true;
+            if (s == "align") o.align = true;
+            else if (s == "GPU") { if (a + 1 < argc && std::atoi(argv[a + 1]) > 0) o.nslabs = std::atoi(argv[++a]); }   // the reference's "GPU n": n devices of one process
+            else if (s == "--same-device") o.same_device = true;
+            else if (s == "double") o.dbl = true;
+            else if (s == "--device" && a + 1 < argc) o.device = std::atoi(argv[++a]);
+            else if (s == "--steps" && a + 1 < argc) o.max_steps = std::atol(argv[++a]);
+            else if (s == "--grid-only" && a + 1 < argc) o.grid_only = argv[++a];
+            else if (s == "--grid-time" && a + 1 < argc) o.grid_time = std::atof(argv[++a]);
+            else if (s == "moving") o.moving = true;
+            else if (s == "moving-mesh") o.moving_mesh = true;
+            else if (s == "--host-voxels") o.host_voxels = true;
+            else if (s == "--time-both") o.time_both = true;
+            else if (s == "--host-extrusion") o.host_extrusion = true;
+            else if (s == "--time-geometry") o.time_geometry = true;
             else if (s == "blocking") { if (a + 1 < argc) a++; }
-            else if (s == "CSV") csv = true;
-            else if (s == "--grid-images") grid_images = true;       // <prefix>_grid_3d/<k>.bmp: the node types, one image per z-slice
+            else if (s == "CSV") o.csv = true;
+            else if (s == "--grid-images") o.grid_images = true;       // <prefix>_grid_3d/<k>.bmp: the node types, one image per z-slice
             // transpose, decompose: accepted, no effect
         }
-        return dbl ? run<double>(argv[1], argv[2], cfg, align, device, max_steps, grid_only, csv, nslabs, same_device, grid_images, moving, grid_time, host_extrusion, time_geometry, moving_mesh, host_voxels, time_both)
-                   : run<float>(argv[1], argv[2], cfg, align, device, max_steps, grid_only, csv, nslabs, same_device, grid_images, moving, grid_time, host_extrusion, time_geometry, moving_mesh, host_voxels, time_both);
+        return o.dbl ? run<double>(argv[1], argv[2], cfg, o) : run<float>(argv[1], argv[2], cfg, o);
     } catch (std::exception &e) {
         std::fprintf(stderr, "\n\nCaught exception:\n%s\n\nTerminating...\n", e.what());     // FluidSolver3D.cpp:313-318
         return -1;

@@ -309,11 +309,17 @@ def test_clear_outer_cells(built, dtype):
 
 # ---- refusals -------------------------------------------------------------------------------------------------------------
 
+def baffle_box(n):
+    """box(n) with a one-cell-thick baffle across x, temperature BC = FREE: the geometry fs3d_upload_nodes refuses."""
+    g = grids.box(n, n, n)
+    g.type[n // 2, n // 3:2 * n // 3, n // 3:2 * n // 3] = grids.NODE_BOUND
+    g.bc_temp[n // 2, n // 3:2 * n // 3, n // 3:2 * n // 3] = grids.BC_FREE
+    return g
+
+
 def test_refused_geometry_leaves_no_geometry_until_an_update_succeeds(built):
     good = grids.box(12, 12, 12)
-    baffle = grids.box(12, 12, 12)
-    baffle.type[6, 4:8, 4:8] = grids.NODE_BOUND     # one-cell-thick baffle, temperature BC = FREE: the geometry fs3d_upload_nodes refuses
-    baffle.bc_temp[6, 4:8, 4:8] = grids.BC_FREE
+    baffle = baffle_box(12)
     other = grids.box_with_obstacle(12, 12, 12)
     s = make(good, np.float32, capi.SWEEP_EXACT)
     with pytest.raises(capi.Fs3dError) as ei:
@@ -356,6 +362,85 @@ def test_update_on_a_slab_context_is_unsupported(built):
         s.update_nodes(g)
     assert ei.value.status == capi.ERR_UNSUPPORTED and "single context" in str(ei.value)
     s.UpdateBoundaries()                 # refused before anything was touched: the slab keeps its geometry
+    s.close()
+
+
+# The order of the refusals, entry by entry: NULL array, slab, (update entries) no upload yet, the source's own check -- all of
+# them before the context gives up its geometry -- and last the refusals of the tables, which leave it without one.
+ENTRIES = ["fs3d_update_nodes", "fs3d_update_nodes_dev", "fs3d_update_nodes_shape2d", "fs3d_update_nodes_shape3d",
+           "fs3d_extrude_shape2d_dev", "fs3d_voxelize_shape3d_dev", "fs3d_flood_fill_dev"]
+SOURCE_OF = {"fs3d_update_nodes_shape2d": "2d", "fs3d_extrude_shape2d_dev": "2d", "fs3d_update_nodes_shape3d": "3d",
+             "fs3d_voxelize_shape3d_dev": "3d"}
+
+
+def raw_entry_call(s, entry, g, null=False, bad_source=False):
+    """One call of `entry` on context s with raw ctypes arguments for the 8 x 8 x 8 grid g; null: the first array is NULL;
+    bad_source: the Shape2D depth gives active_dimz > dimz, the Shape3D index list names vertex nvert.  Arrays the entry takes
+    on the device are fields of the context's own TEMP and HALF layers, so that nothing is handed a pointer it could not use.
+    Returns (status, message)."""
+    n = g.dimx
+    host = [np.ascontiguousarray(a, np.uint8) for a in (g.type, g.bc_vel, g.bc_temp)] + [np.ascontiguousarray(a, np.float32) for a in (g.vx, g.vy, g.vz, g.T)]
+    dev = []
+    for layer, var in [(capi.LAYER_HALF, v) for v in range(3)] + [(capi.LAYER_TEMP, v) for v in range(4)]:
+        p = C.c_void_p()
+        s._chk(s.lib.fs3d_field_dev_ptr(s.h, layer, var, C.byref(p)))
+        dev.append(p)
+    g2 = [np.full((n, n), grids.NODE_IN, np.uint8)] + [np.zeros((n, n), np.float32) for _ in range(3)]
+    depth = g.dz * ((n + 1) if bad_source else (n - 2))            # active_dimz = ceil(depth / dz) + 1
+    xyz = [np.array(a, np.float32) for a in ([2, 5, 2], [2, 2, 5], [3, 3, 3])]
+    tri = np.array([0, 1, 3 if bad_source else 2], np.int32)
+    nseg = (C.c_int * 3)()
+    hole = lambda ptrs: [None] + ptrs[1:] if null else ptrs
+    if entry == "fs3d_update_nodes":
+        args = hole([capi._p(a) for a in host]) + [nseg]
+    elif entry == "fs3d_update_nodes_dev":
+        args = hole(dev) + [nseg]
+    elif entry == "fs3d_update_nodes_shape2d":
+        args = hole([capi._p(a) for a in g2]) + [g.dz, depth, 0.0, 1.0, nseg]
+    elif entry == "fs3d_extrude_shape2d_dev":
+        args = hole([capi._p(a) for a in g2]) + [g.dz, depth, 0.0, 1.0] + dev
+    elif entry == "fs3d_update_nodes_shape3d":
+        args = hole([capi._p(a) for a in xyz]) + [3, capi._p(tri), 1, 1.0, nseg]
+    elif entry == "fs3d_voxelize_shape3d_dev":
+        args = hole([capi._p(a) for a in xyz]) + [3, capi._p(tri), 1, 1.0] + dev
+    else:
+        args = hole(dev[:1])
+    st = getattr(s.lib, entry)(s.h, *args)
+    return st, (s.lib.fs3d_last_error(s.h) or b"").decode()
+
+
+@pytest.mark.parametrize("entry", ENTRIES)
+def test_refusal_precedence(built, entry):
+    g = grids.box_with_obstacle(8, 8, 8)
+    params = capi.fluid_params(np.float32, *PARAMS)
+    # a NULL array is named before the slab is
+    slab = capi.Solver(g, params, np.float32, x_range=(0, 4))
+    st, msg = raw_entry_call(slab, entry, g, null=True)
+    print(st, msg)
+    assert st == capi.ERR_INVALID and "NULL array" in msg and msg.startswith(entry + ":"), (st, msg)
+    st, msg = raw_entry_call(slab, entry, g)
+    print(st, msg)
+    assert st == capi.ERR_UNSUPPORTED and "single context" in msg and msg.startswith(entry + ":"), (st, msg)
+    slab.close()
+    # refused by the check of its source, the context keeps the geometry it has
+    s = make(g, np.float32, capi.SWEEP_EXACT)
+    before = s.geometry_info()
+    n_before = s.profiler_events()["CreateSegments"][1]
+    if entry in SOURCE_OF:
+        st, msg = raw_entry_call(s, entry, g, bad_source=True)
+        print(st, msg)
+        assert st == capi.ERR_INVALID and msg.startswith(entry + ":"), (st, msg)
+        assert ("active_dimz" if SOURCE_OF[entry] == "2d" else "index") in msg, msg
+    after = s.geometry_info()
+    assert [after[k] for k in TABLE_KEYS] == [before[k] for k in TABLE_KEYS] and s.profiler_events()["CreateSegments"][1] == n_before
+    s.UpdateBoundaries(); s.TimeStep(np.float32(DT), 1, 1, True)
+    # refused by the tables, it has none
+    st, msg = raw_entry_call(s, "fs3d_update_nodes", baffle_box(8))
+    print(st, msg)
+    assert st == capi.ERR_UNSUPPORTED and "FREE boundary condition" in msg, (st, msg)
+    with pytest.raises(capi.Fs3dError) as ei:
+        s.geometry_info()
+    assert ei.value.status == capi.ERR_INVALID and "upload nodes first" in str(ei.value)
     s.close()
 
 
