@@ -57,6 +57,9 @@ SYMBOLS = {
     "fs3d_merge": (_i, [_vp, _i, _i]),
     "fs3d_eval_div_error": (_i, [_vp, _i, C.POINTER(_d), C.POINTER(C.c_longlong)]),
     "fs3d_get_layer": (_i, [_vp, _vp, _vp, _i, _i, _i]),
+    "fs3d_get_layer_rows": (_i, [_vp, _vp, _vp, _i, _i, _i, C.POINTER(_i)]),
+    "fs3d_get_layer_dev": (_i, [_vp, _vp, _vp, _i, _i, _i, C.POINTER(_i)]),
+    "fs3d_get_layer_info": (_i, [_vp, C.POINTER(C.c_longlong)]),
     "fs3d_comm_unique_id": (_i, [_vp]),
     "fs3d_comm_init": (_i, [_vp, _vp, _i, _i]),
     "fs3d_local_group_create": (_i, [_i, C.POINTER(_vp)]),
@@ -291,6 +294,42 @@ class Solver:
         outT = np.empty(od, dtype=np.float64)
         self._chk(self.lib.fs3d_get_layer(self.h, _p(outV), _p(outT), *outdims))
         return outV, outT
+
+    def GetLayerRows(self, outV, outT, outdims=(0, 0, 0)):
+        """This slab's rows of the GLOBAL result: outV [odx, ody, odz, 3] (the context's precision) and outT [odx, ody, odz]
+        (float64) are the arrays of the whole output grid, shared by the slabs of a group (0 = the global dim); the rows i whose
+        source plane i*gx/odx this context owns are written.  Returns them as (i0, i1) -- slab.out_rows."""
+        od = tuple(o or d for o, d in zip(outdims, self.gdims))
+        for a, shape, dt in ((outV, od + (3,), self.dtype), (outT, od, np.float64)):
+            if not isinstance(a, np.ndarray) or a.shape != shape or a.dtype != dt or not a.flags.c_contiguous:
+                raise ValueError("GetLayerRows: C-contiguous arrays of the whole output grid, outV in the context's precision, outT float64")
+        rows = (C.c_int * 2)()
+        self._chk(self.lib.fs3d_get_layer_rows(self.h, _p(outV), _p(outT), *outdims, rows))
+        return rows[0], rows[1]
+
+    def GetLayerDev(self, outV, outT, outdims=(0, 0, 0)):
+        """The same with the two arrays on the context's device -- torch tensors (contiguous, of the whole output grid's size; the
+        context's precision and float64) or raw device pointers (int).  Returns (i0, i1) after the enqueue: read after synchronize()."""
+        n = int(np.prod([o or d for o, d in zip(outdims, self.gdims)]))
+
+        def ptr(a, size, numel):
+            if isinstance(a, int):
+                return C.c_void_p(a)
+            if not a.is_cuda or not a.is_contiguous() or a.element_size() != size or a.numel() != numel:
+                raise ValueError("GetLayerDev: contiguous device tensors of the whole output grid, outV in the context's precision, outT float64")
+            return C.c_void_p(a.data_ptr())
+        rows = (C.c_int * 2)()
+        self._chk(self.lib.fs3d_get_layer_dev(self.h, ptr(outV, self.dtype.itemsize, 3 * n), ptr(outT, 8, n), *outdims, rows))
+        return rows[0], rows[1]
+
+    GET_LAYER_INFO = ("samples", "bytes_to_host", "device_allocs")
+
+    def get_layer_info(self):
+        """fs3d_get_layer_info as a dict (keys: Solver.GET_LAYER_INFO): what the last GetLayer* call wrote and copied, and the
+        device allocations of all of them; measurement and test aid."""
+        info = (C.c_longlong * len(self.GET_LAYER_INFO))()
+        self._chk(self.lib.fs3d_get_layer_info(self.h, info))
+        return dict(zip(self.GET_LAYER_INFO, list(info)))
 
     # -- kernel-level access ------------------------------------------------------
     def sweep(self, d, dt, l_cur, l_temp, l_next, merge=False):

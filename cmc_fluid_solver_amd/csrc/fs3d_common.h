@@ -153,6 +153,11 @@ struct fs3d_ctx {
     double *red_host = nullptr;    // pinned
     int red_blocks = 0;
     double diffError = 0.0;
+    // result output (fs3d_get_layer*): device staging of the samples on their way to the host -- the V part, then the T part at
+    // a 256-byte boundary; grown when a call needs more, never shrunk
+    void *gl_stage = nullptr;
+    size_t gl_stage_bytes = 0;
+    long long gl_info[FS3D_N_GETLAYER_INFO] = {0, 0, 0};   // fs3d_get_layer_info
     int test_drop = 0;             // fault-injection hook of tests/test_gpu_failures.py: env FS3D_TEST_DROP_HANDOFF, read ONCE at fs3d_create
     hipStream_t stream = nullptr;
     hipStream_t comm_stream = nullptr;     // multi-GPU: halo planes travel here, beside the interior planes' sweep on `stream`

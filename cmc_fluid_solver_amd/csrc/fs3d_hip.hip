@@ -102,6 +102,32 @@ __global__ void __launch_bounds__(256) k_clear_type(const uint16_t *__restrict__
         if (((code[i] >> CODE_TYPE_SHIFT) & 3) == type) { d0[i] = val; d1[i] = val; d2[i] = val; d3[i] = val; }
 }
 
+// TimeLayer3D::FilterToArrays (TimeLayer3D.h:819-924): the nearest-neighbour samples of one layer, out[i,j,k] = layer[i*gx/odx,
+// j*dimy/ody, k*dimz/odz], into outV (interleaved x, y, z) and outT (double).  A pure gather: order-free, bit-exact.  One thread
+// per sample, k fastest: blockIdx.x = output row i - i0, the threads of a row walk its ody*odz samples (a wave stores 64 x 3
+// consecutive R and 64 consecutive doubles).  The slab holds the planes [x_offset, x_offset + dimx) of gx and writes the rows
+// [i0, i1) whose source plane it owns; outV / outT address the first sample of row i0.  Runs behind k_clear_type on the same
+// stream and reads the stamped values.
+template <typename R>
+__global__ void __launch_bounds__(256) k_get_layer(const R *__restrict__ U, const R *__restrict__ V, const R *__restrict__ W,
+                                                    const R *__restrict__ T, int x_offset, int dimx, long long plane, int dimy, int dimz,
+                                                    int gx, int odx, int ody, int odz, int i0, int i1,
+                                                    R *__restrict__ outV, double *__restrict__ outT)
+{
+    const int i = i0 + (int)blockIdx.x;
+    const int x = (int)((long long)i * gx / odx) - x_offset;
+    if (i >= i1 || x < 0 || x >= dimx) return;
+    const unsigned po = (unsigned)ody * (unsigned)odz;
+    for (unsigned p = blockIdx.y * 256u + threadIdx.x; p < po; p += gridDim.y * 256u) {
+        const unsigned j = p / (unsigned)odz, k = p - j * (unsigned)odz;
+        const int y = (int)((long long)j * dimy / ody), z = (int)((long long)k * dimz / odz);
+        const long long id = (long long)x * plane + (long long)y * dimz + z;
+        const long long ind = (long long)blockIdx.x * po + p;
+        outV[3 * ind] = U[id]; outV[3 * ind + 1] = V[id]; outV[3 * ind + 2] = W[id];
+        outT[ind] = (double)T[id];
+    }
+}
+
 // TimeLayer3D::EvalDivError (TimeLayer3D.h:595-641): per-cell FTYPE face sums, double
 // accumulation.  Wave64 shuffle reduction, one partial (sum,count) pair per block;
 // the partials are summed in a fixed order by k_div_final, so the result is
@@ -378,6 +404,7 @@ extern "C" void fs3d_destroy(fs3d_ctx *c)
     fs3d_geom_destroy(c);
     if (c->err_terms) hipFree(c->err_terms);
     if (c->red_buf) hipFree(c->red_buf);
+    if (c->gl_stage) hipFree(c->gl_stage);
     if (c->stamps) hipFree(c->stamps);
     if (c->red_host) hipHostFree(c->red_host);
     if (c->errw_host) hipHostFree(c->errw_host);
@@ -1325,42 +1352,86 @@ extern "C" fs3d_status fs3d_synchronize(fs3d_ctx *c)
     return check_device_errors(c);
 }
 
-// Solver3D::GetLayer, Solver3D.cpp:21-25
+// Solver3D::GetLayer, Solver3D.cpp:21-25: next->Clear(NODE_OUT, MISSING_VALUE), then FilterToArrays by k_get_layer.
+// `local`: the slab's own planes are the whole source (fs3d_get_layer: x = i*dimx/odx, rows [0, odx)); else the slab owns the rows
+// of the GLOBAL output whose source plane it holds.  `dev`: outV / outT are on the context's device, the kernel writes them and
+// the call returns after the enqueue; else the owned samples go through the staging buffer and the call returns synchronised.
 template <typename R>
-static fs3d_status get_layer_impl(fs3d_ctx *c, R *outV, double *outT, int odx, int ody, int odz)
+static fs3d_status get_layer_impl(fs3d_ctx *c, R *outV, double *outT, int odx, int ody, int odz, bool local, bool dev, int rows[2])
 {
     const int b = c->slot[FS3D_LAYER_NEXT];
+    const int gx = local ? c->dimx : c->dimx_global, x_offset = local ? 0 : c->x_offset;
+    if (odx == 0) odx = gx;
+    if (ody == 0) ody = c->dimy;
+    if (odz == 0) odz = c->dimz;
+    const long long po = (long long)ody * odz;
+    if (po >= (1LL << 31)) return fail(c, FS3D_ERR_UNSUPPORTED, "fs3d_get_layer: an output plane of 2^31 samples or more");
+    // the rows i with x_offset <= i*gx/odx < x_offset + dimx (slab.py out_rows)
+    const int i0 = (int)(((long long)x_offset * odx + gx - 1) / gx), i1 = (int)(((long long)(x_offset + c->dimx) * odx + gx - 1) / gx);
+    if (rows) { rows[0] = i0; rows[1] = i1; }
+    const long long n = (long long)(i1 - i0) * po;
+    const size_t vbytes = ((size_t)3 * n * sizeof(R) + 255) / 256 * 256;
+    c->gl_info[0] = n; c->gl_info[1] = 0;
+    R *dV = outV + 3 * (size_t)i0 * po;
+    double *dT = outT + (size_t)i0 * po;
+    if (!dev && vbytes + (size_t)n * 8 > c->gl_stage_bytes) {
+        if (c->gl_stage) HIPCHK(c, hipFree(c->gl_stage));
+        c->gl_stage = nullptr; c->gl_stage_bytes = 0;
+        HIPCHK(c, hipMalloc(&c->gl_stage, vbytes + (size_t)n * 8));
+        c->gl_stage_bytes = vbytes + (size_t)n * 8;
+        c->gl_info[2]++;
+    }
     hipLaunchKernelGGL((k_clear_type<R>), dim3(grid_for(c->ncell, 256)), dim3(256), 0, c->stream, c->code, c->ncell,
                        (int)FS3D_NODE_OUT, (R)99999.0f, fld<R>(c, b, 0), fld<R>(c, b, 1), fld<R>(c, b, 2), fld<R>(c, b, 3));
     HIPCHK(c, hipGetLastError());
-    std::vector<R> h[4];
-    for (int v = 0; v < 4; v++) {
-        h[v].resize((size_t)c->ncell);
-        HIPCHK(c, hipMemcpyAsync(h[v].data(), fld<R>(c, b, v), (size_t)c->ncell * sizeof(R), hipMemcpyDeviceToHost, c->stream));
+    if (n) {
+        R *kV = dev ? dV : (R *)c->gl_stage;
+        double *kT = dev ? dT : (double *)((char *)c->gl_stage + vbytes);
+        hipLaunchKernelGGL((k_get_layer<R>), dim3((unsigned)(i1 - i0), grid_for(po, 256, 1024)), dim3(256), 0, c->stream,
+                           (const R *)fld<R>(c, b, 0), (const R *)fld<R>(c, b, 1), (const R *)fld<R>(c, b, 2), (const R *)fld<R>(c, b, 3),
+                           x_offset, c->dimx, c->plane, c->dimy, c->dimz, gx, odx, ody, odz, i0, i1, kV, kT);
+        HIPCHK(c, hipGetLastError());
+        if (!dev) {
+            HIPCHK(c, hipMemcpyAsync(dV, kV, (size_t)3 * n * sizeof(R), hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipMemcpyAsync(dT, kT, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+            c->gl_info[1] = n * (long long)(3 * sizeof(R) + 8);
+        }
     }
+    if (dev) return FS3D_OK;
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (odx == 0) odx = c->dimx;
-    if (ody == 0) ody = c->dimy;
-    if (odz == 0) odz = c->dimz;
-    // FilterToArrays, TimeLayer3D.h:819-924 (single slab; a multi-GPU caller gathers the slabs)
-    for (int i = 0; i < odx; i++)
-        for (int j = 0; j < ody; j++)
-            for (int k = 0; k < odz; k++) {
-                const int x = i * c->dimx / odx, y = j * c->dimy / ody, z = k * c->dimz / odz;
-                const size_t ind = (size_t)i * ody * odz + (size_t)j * odz + k;
-                const size_t id = (size_t)x * c->plane + (size_t)y * c->dimz + z;
-                outV[3 * ind] = h[0][id]; outV[3 * ind + 1] = h[1][id]; outV[3 * ind + 2] = h[2][id];
-                outT[ind] = h[3][id];
-            }
-    return FS3D_OK;
+    if (c->ev_used) rec_collect(c);
+    return check_device_errors(c);
+}
+
+// the three output entries: refusals before any launch, then the precision's get_layer_impl
+static fs3d_status get_layer_entry(fs3d_ctx *c, const char *what, void *outV, double *outT, int odx, int ody, int odz, bool local, bool dev, int rows[2])
+{
+    if (!c || !outV || !outT || (!local && !rows)) return c ? fail(c, FS3D_ERR_INVALID, std::string(what) + ": NULL destination") : FS3D_ERR_INVALID;
+    if (!c->have_nodes) return fail(c, FS3D_ERR_INVALID, std::string(what) + ": upload nodes first");
+    if (odx < 0 || ody < 0 || odz < 0) return fail(c, FS3D_ERR_INVALID, std::string(what) + ": negative output dims");
+    HIPCHK(c, hipSetDevice(c->device));
+    return c->prec == FS3D_F32 ? get_layer_impl<float>(c, (float *)outV, outT, odx, ody, odz, local, dev, rows)
+                               : get_layer_impl<double>(c, (double *)outV, outT, odx, ody, odz, local, dev, rows);
 }
 
 extern "C" fs3d_status fs3d_get_layer(fs3d_ctx *c, void *outV, double *outT, int odx, int ody, int odz)
 {
-    if (!c || !outV || !outT) return FS3D_ERR_INVALID;
-    if (!c->have_nodes) return fail(c, FS3D_ERR_INVALID, "fs3d_get_layer: upload nodes first");
-    if (odx < 0 || ody < 0 || odz < 0) return fail(c, FS3D_ERR_INVALID, "fs3d_get_layer: negative output dims");
-    HIPCHK(c, hipSetDevice(c->device));
-    return c->prec == FS3D_F32 ? get_layer_impl<float>(c, (float *)outV, outT, odx, ody, odz)
-                               : get_layer_impl<double>(c, (double *)outV, outT, odx, ody, odz);
+    return get_layer_entry(c, "fs3d_get_layer", outV, outT, odx, ody, odz, true, false, nullptr);
+}
+
+extern "C" fs3d_status fs3d_get_layer_rows(fs3d_ctx *c, void *outV, double *outT, int odx, int ody, int odz, int rows[2])
+{
+    return get_layer_entry(c, "fs3d_get_layer_rows", outV, outT, odx, ody, odz, false, false, rows);
+}
+
+extern "C" fs3d_status fs3d_get_layer_dev(fs3d_ctx *c, void *outV, double *outT, int odx, int ody, int odz, int rows[2])
+{
+    return get_layer_entry(c, "fs3d_get_layer_dev", outV, outT, odx, ody, odz, false, true, rows);
+}
+
+extern "C" fs3d_status fs3d_get_layer_info(fs3d_ctx *c, long long info[FS3D_N_GETLAYER_INFO])
+{
+    if (!c || !info) return FS3D_ERR_INVALID;
+    for (int k = 0; k < FS3D_N_GETLAYER_INFO; k++) info[k] = c->gl_info[k];
+    return FS3D_OK;
 }

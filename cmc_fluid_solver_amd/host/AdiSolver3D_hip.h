@@ -133,6 +133,9 @@ public:
     }
     // Solver3D::GetLayer (Solver3D.cpp:21-25): v = interleaved x,y,z (Vec3D), T = double
     void GetLayer(FTYPE *v, double *T, int outdimx = 0, int outdimy = 0, int outdimz = 0) { chk(fs3d_get_layer(ctx_, v, T, outdimx, outdimy, outdimz)); }
+    // the same on an x-slab of a group: v / T are the arrays of the WHOLE output grid (0 = the grid's global dim), this slab writes
+    // the rows [rows[0], rows[1]) whose source plane it owns -- disjoint over the slabs, together [0, outdimx)
+    void GetLayerRows(FTYPE *v, double *T, int outdimx, int outdimy, int outdimz, int rows[2]) { chk(fs3d_get_layer_rows(ctx_, v, T, outdimx, outdimy, outdimz, rows)); }
     // cur layer on the host (ScalarField3D(CPU, field) copy constructor, TimeLayer3D.h:358-383)
     void DownloadCur(FTYPE *u, FTYPE *v, FTYPE *w, FTYPE *T) { chk(fs3d_download_layer(ctx_, FS3D_LAYER_CUR, u, v, w, T)); }
     // device time per event class since EnableTiming(true): 0 sweeps Z, 1 sweeps Y, 2 sweeps X, 3 everything else

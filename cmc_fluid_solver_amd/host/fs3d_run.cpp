@@ -1,5 +1,5 @@
 // Command-line driver: the reference's FluidSolver3D main (FluidSolver3D/FluidSolver3D.cpp:60-330) on top of
-// libfs3d_hip.so.   fs3d_run <input data> <output prefix> <config> [align] [GPU [n]] [double] [moving [--host-extrusion] [--time-geometry]] [moving-mesh [--host-voxels] [--time-geometry] [--time-both]] [--steps N] [--same-device] [--grid-only FILE [--grid-time T]]
+// libfs3d_hip.so.   fs3d_run <input data> <output prefix> <config> [align] [GPU [n]] [double] [moving [--host-extrusion] [--time-geometry]] [moving-mesh [--host-voxels] [--time-geometry] [--time-both]] [--time-output] [--steps N] [--same-device] [--grid-only FILE [--grid-time T]]
 //   * reads the config (host/Config.h) and a Shape2D, Shape3D or SeaNetCDF geometry (host/Shape2D.h, Shape3D.h, SeaNetCDF.h), prints the grid summary lines
 //     the reference prints ("Grid = X x Y x Z", "NODE_IN points = ..."),
 //   * runs the same loop: dt = cycle length / (frames * time_steps), UpdateBoundaries + TimeStep per step with the
@@ -23,6 +23,8 @@
 //   --time-both: a measurement run -- every step makes the geometry through BOTH paths, the word's own last (same tables either way),
 //   and one more line gives, per call after 3 warm-up steps, median (min - max) of the host clock around each path, the device
 //   time of the device path (fs3d_last_update_device_ms), and the host clock around UpdateBoundaries + TimeStep, synchronised.
+// --time-output: one closing line, the host clock per output record around the GetLayer call (GPU n: rank 0's call and the barrier that
+//   completes the record) and around AppendLayer, with the number of records.
 // There is no CPU backend here: without a GPU the run stops with the library's error.
 // --grid-only FILE: build the grid, dump it (dims, type, bc_vel, bc_temp, vx, vy, vz, T as raw arrays) and exit
 //   without touching the GPU -- used by the CPU tests to compare the C++ loader with its Python twin.
@@ -60,7 +62,7 @@ struct RunGeom {
 // the words after <config file>, as main's argument loop finds them
 struct RunOptions {
     bool align = false, dbl = false, csv = false, same_device = false, grid_images = false;
-    bool moving = false, host_extrusion = false, moving_mesh = false, host_voxels = false, time_geometry = false, time_both = false;
+    bool moving = false, host_extrusion = false, moving_mesh = false, host_voxels = false, time_geometry = false, time_both = false, time_output = false;
     double grid_time = -1;
     int nslabs = 1, device = 0;
     long max_steps = -1;
@@ -69,7 +71,7 @@ struct RunOptions {
 
 template <typename FTYPE>
 static int run_slabs(const fs3d::Grid3D<FTYPE> &grid, const RunGeom &geo, const std::string &prefix, const fs3d::Config &cfg, int nslabs,
-                     bool same_device, long max_steps, bool csv);
+                     bool same_device, long max_steps, bool csv, bool time_output);
 
 template <typename FTYPE>
 static int run(const std::string &data, const std::string &prefix, const fs3d::Config &cfg, const RunOptions &o)
@@ -126,7 +128,7 @@ static int run(const std::string &data, const std::string &prefix, const fs3d::C
         std::fclose(f);
         return 0;
     }
-    if (o.nslabs > 1) return run_slabs<FTYPE>(grid, geo, prefix, cfg, o.nslabs, o.same_device, o.max_steps, o.csv);
+    if (o.nslabs > 1) return run_slabs<FTYPE>(grid, geo, prefix, cfg, o.nslabs, o.same_device, o.max_steps, o.csv, o.time_output);
     FluidParams<FTYPE> params = cfg.useNormalizedParams ? FluidParams<FTYPE>(cfg.Re, cfg.Pr, cfg.lambda)
                                                         : FluidParams<FTYPE>(cfg.viscosity, cfg.density, cfg.R_specific, cfg.k, cfg.cv);
     AdiSolver3D<FTYPE> solver;
@@ -156,6 +158,7 @@ static int run(const std::string &data, const std::string &prefix, const fs3d::C
     std::vector<float> mx, my, mz;                     // moving-mesh: the sub-frame's vertices
     std::vector<double> ab_host, ab_dev, ab_dev_gpu, ab_step;   // --time-both: per step, ms
     int fill_rounds = 0;
+    double out_ms[2] = {0, 0};                         // --time-output: host clock around GetLayer, AppendLayer
     auto ms_since = [](std::chrono::steady_clock::time_point a) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - a).count(); };
     // the geometry is frame 0's for the whole run: the reference prepares the grid once, before the loop (grid->Prepare(0), :226;
     // the per-step grid->Prepare(t) is commented out, :237) -- the frame only restarts the substep counter
@@ -208,8 +211,11 @@ static int run(const std::string &data, const std::string &prefix, const fs3d::C
         }
         std::fflush(stdout);
         if ((i % cfg.out_time_steps) == 0) {                                                             // :254-264
+            const auto o0 = std::chrono::steady_clock::now();
             solver.GetLayer(resVel.data(), resT.data(), cfg.outdimx, cfg.outdimy, cfg.outdimz);
+            const auto o1 = std::chrono::steady_clock::now();
             nc.AppendLayer(resVel.data(), resT.data());
+            out_ms[0] += std::chrono::duration<double, std::milli>(o1 - o0).count(); out_ms[1] += ms_since(o1);
         }
         if (o.moving || o.moving_mesh) solver.ClearOutterCells();                                                           // AdiSolver3D.cpp:382-385
     }
@@ -255,6 +261,9 @@ static int run(const std::string &data, const std::string &prefix, const fs3d::C
         line("time step", ab_step);
         std::printf(" fill rounds %d\n", fill_rounds);
     }
+    if (o.time_output && nc.NumRecords() > 0)
+        std::printf("Result output per record (host clock, ms): GetLayer %.3f, AppendLayer %.3f; %u records\n", out_ms[0] / nc.NumRecords(),
+                    out_ms[1] / nc.NumRecords(), nc.NumRecords());
     std::printf("%ld steps in %.3f s: %.1f Mcells/s; %u layers in %s\n", steps, sec,
                 (double)grid.dimx * grid.dimy * grid.dimz * steps / sec / 1e6, nc.NumRecords(), out.c_str());
     return 0;
@@ -280,7 +289,7 @@ struct Barrier {
 
 template <typename FTYPE>
 static int run_slabs(const fs3d::Grid3D<FTYPE> &grid, const RunGeom &geo, const std::string &prefix, const fs3d::Config &cfg, int nslabs,
-                     bool same_device, long max_steps, bool csv)
+                     bool same_device, long max_steps, bool csv, bool time_output)
 {
     using namespace fs3d;
     FluidParams<FTYPE> params = cfg.useNormalizedParams ? FluidParams<FTYPE>(cfg.Re, cfg.Pr, cfg.lambda)
@@ -293,9 +302,9 @@ static int run_slabs(const fs3d::Grid3D<FTYPE> &grid, const RunGeom &geo, const 
     if (geo.depths) out_depths = DepthInfo3D(cfg.outdimx, cfg.outdimy, *geo.depths);
     nc.Create(out, bbox, dt * cfg.out_time_steps, finaltime, cfg.outdimx, cfg.outdimy, cfg.outdimz, cfg.out_vars, geo.depths != nullptr,
               geo.depths ? out_depths.depth.data() : nullptr);
-    const size_t ncell = (size_t)grid.dimx * grid.dimy * grid.dimz, plane = (size_t)grid.dimy * grid.dimz;
-    std::vector<FTYPE> fullV(ncell * 3), resVel((size_t)cfg.outdimx * cfg.outdimy * cfg.outdimz * 3);
-    std::vector<double> fullT(ncell), resT((size_t)cfg.outdimx * cfg.outdimy * cfg.outdimz);
+    std::vector<FTYPE> resVel((size_t)cfg.outdimx * cfg.outdimy * cfg.outdimz * 3);
+    std::vector<double> resT((size_t)cfg.outdimx * cfg.outdimy * cfg.outdimz);
+    double out_ms[2] = {0, 0};                         // --time-output (rank 0): host clock until the record is complete, AppendLayer
     void *group = AdiSolver3D<FTYPE>::CreateLocalGroup(nslabs);
     Barrier bar(nslabs);
     std::vector<std::exception_ptr> errs(nslabs);
@@ -321,22 +330,19 @@ static int run_slabs(const fs3d::Grid3D<FTYPE> &grid, const RunGeom &geo, const 
                     solver.TimeStep((FTYPE)dt, cfg.num_global, cfg.num_local, (i % 10 == 0) || (t + dt >= finaltime));
                     if (r == 0) { std::printf("\rerr = %.8f, frame %i\tsubstep %i\t%i%%", solver.diffError, currentframe, i, (int)((float)t * 100 / (float)finaltime)); std::fflush(stdout); }
                     if ((i % cfg.out_time_steps) == 0) {
-                        // each slab's part of `next` at full resolution (NODE_OUT stamped 99999), then FilterToArrays on the
-                        // assembled layer (TimeLayer3D.h:819-924: nearest-neighbour down-sample)
-                        solver.GetLayer(fullV.data() + 3 * (size_t)x0 * plane, fullT.data() + (size_t)x0 * plane, 0, 0, 0);
+                        // each slab samples the rows of the result whose source planes it owns (FilterToArrays, TimeLayer3D.h:819-924)
+                        // straight into the shared arrays: the rows are disjoint
+                        const auto o0 = std::chrono::steady_clock::now();
+                        int rows[2];
+                        solver.GetLayerRows(resVel.data(), resT.data(), cfg.outdimx, cfg.outdimy, cfg.outdimz, rows);
                         bar.wait();
                         if (r == 0) {
-                            for (int a = 0; a < cfg.outdimx; a++)
-                                for (int b = 0; b < cfg.outdimy; b++)
-                                    for (int c = 0; c < cfg.outdimz; c++) {
-                                        const size_t id = grid.Index(a * grid.dimx / cfg.outdimx, b * grid.dimy / cfg.outdimy, c * grid.dimz / cfg.outdimz);
-                                        const size_t ind = ((size_t)a * cfg.outdimy + b) * cfg.outdimz + c;
-                                        resVel[3 * ind] = fullV[3 * id]; resVel[3 * ind + 1] = fullV[3 * id + 1]; resVel[3 * ind + 2] = fullV[3 * id + 2];
-                                        resT[ind] = fullT[id];
-                                    }
+                            const auto o1 = std::chrono::steady_clock::now();
                             nc.AppendLayer(resVel.data(), resT.data());
+                            out_ms[0] += std::chrono::duration<double, std::milli>(o1 - o0).count();
+                            out_ms[1] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - o1).count();
                         }
-                        bar.wait();
+                        bar.wait();                    // nobody writes the next record's rows while rank 0 still reads this one
                     }
                 }
                 if (r == 0) steps_done = steps;
@@ -356,7 +362,11 @@ static int run_slabs(const fs3d::Grid3D<FTYPE> &grid, const RunGeom &geo, const 
     for (auto &e : errs) if (e) std::rethrow_exception(e);
     const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     (void)csv;
-    std::printf("\n%ld steps in %.3f s: %.1f Mcells/s; %u layers in %s\n", steps_done, sec,
+    std::printf("\n");
+    if (time_output && nc.NumRecords() > 0)
+        std::printf("Result output per record (host clock, ms): GetLayer %.3f, AppendLayer %.3f; %u records\n", out_ms[0] / nc.NumRecords(),
+                    out_ms[1] / nc.NumRecords(), nc.NumRecords());
+    std::printf("%ld steps in %.3f s: %.1f Mcells/s; %u layers in %s\n", steps_done, sec,
                 (double)grid.dimx * grid.dimy * grid.dimz * steps_done / sec / 1e6, nc.NumRecords(), out.c_str());
     return 0;
 }
@@ -364,7 +374,7 @@ static int run_slabs(const fs3d::Grid3D<FTYPE> &grid, const RunGeom &geo, const 
 int main(int argc, char **argv)
 {
     if (argc < 4) {
-        std::printf("Usage: %s <input data> <output prefix> <config file> [align] [GPU [n]] [double] [--steps N] [moving [--host-extrusion] [--time-geometry]] [moving-mesh [--host-voxels] [--time-geometry] [--time-both]] [--grid-only FILE [--grid-time T]] [--grid-images]\n", argv[0]);
+        std::printf("Usage: %s <input data> <output prefix> <config file> [align] [GPU [n]] [double] [--steps N] [moving [--host-extrusion] [--time-geometry]] [moving-mesh [--host-voxels] [--time-geometry] [--time-both]] [--time-output] [--grid-only FILE [--grid-time T]] [--grid-images]\n", argv[0]);
         return 0;
     }
     try {
@@ -391,6 +401,7 @@ int main(int argc, char **argv)
             else if (s == "--time-both") o.time_both = true;
             else if (s == "--host-extrusion") o.host_extrusion = true;
             else if (s == "--time-geometry") o.time_geometry = true;
+            else if (s == "--time-output") o.time_output = true;
             else if (s == "blocking") { if (a + 1 < argc) a++; }
             else if (s == "CSV") o.csv = true;
             else if (s == "--grid-images") o.grid_images = true;       // <prefix>_grid_3d/<k>.bmp: the node types, one image per z-slice

@@ -13,6 +13,12 @@ def slab_range(dimx, rank, nranks):
     return x0, x0 + q + (1 if rank < r else 0)
 
 
+def out_rows(x0, x1, gx, odx):
+    """Rows [i0, i1) of a result of odx rows that the slab of planes [x0, x1) of gx writes (fs3d_get_layer_rows): the i whose
+    source plane i*gx // odx (FilterToArrays, TimeLayer3D.h:819-924) it owns.  Slabs in rank order partition [0, odx)."""
+    return -(-x0 * odx // gx), -(-x1 * odx // gx)
+
+
 def thomas_forward_slab(a, b, c, d, carry):
     """Forward elimination (Algorithms.h:23-32) of the rows of ONE slab of a line batch.
 

@@ -303,6 +303,27 @@ fs3d_status fs3d_eval_div_error(fs3d_ctx *ctx, int layer, double *err_out, long 
  * step's layer -- the reference's one-step output lag is preserved. */
 fs3d_status fs3d_get_layer(fs3d_ctx *ctx, void *outV, double *outT,
                            int outdimx, int outdimy, int outdimz);
+/* The same output (Solver3D.cpp:21-25, TimeLayer3D.h:819-924) for an x-slab of a GLOBAL result: outV / outT are the arrays of
+ * the WHOLE output grid (outdimx*outdimy*outdimz samples, 0 = the GLOBAL dim), and the context writes the rows i whose source
+ * plane i*dimx_global/outdimx it owns -- rows[0] = ceil(x_offset*outdimx/dimx_global) up to
+ * rows[1] = ceil((x_offset+dimx)*outdimx/dimx_global), reported in `rows`.  Over the slabs of a group the ranges partition
+ * [0, outdimx) in rank order; a slab that owns no row writes nothing and returns FS3D_OK; a single context writes everything.
+ * (fs3d_get_layer on a slab samples the slab's OWN planes, x = i*dimx/outdimx, as it always did.)
+ * The samples are gathered by a kernel, one thread per sample, behind the 99999 stamp on the same stream: only the owned samples
+ * cross the bus, (rows[1]-rows[0])*outdimy*outdimz*(3*sizeof(real)+8) bytes, through a device staging buffer the context keeps
+ * and only grows.  Host destinations; returns synchronised.
+ * All three entries stamp `next` first and over all owned cells, refuse before any launch (NULL context, destination or rows,
+ * negative dims, no nodes yet: FS3D_ERR_INVALID, the context stays usable) and report pending device errors. */
+fs3d_status fs3d_get_layer_rows(fs3d_ctx *ctx, void *outV, double *outT, int outdimx, int outdimy, int outdimz, int rows[2]);
+/* fs3d_get_layer_rows (Solver3D.cpp:21-25, TimeLayer3D.h:819-924) with the two arrays on the context's DEVICE: the kernel
+ * writes them directly, nothing is copied.  Returns after the enqueue on the context's stream; read after fs3d_synchronize.
+ * The zero-copy partner of fs3d_field_dev_ptr and fs3d_update_nodes_dev. */
+fs3d_status fs3d_get_layer_dev(fs3d_ctx *ctx, void *outV_dev, double *outT_dev, int outdimx, int outdimy, int outdimz, int rows[2]);
+/* What the result output (Solver3D.cpp:21-25, TimeLayer3D.h:819-924) did: info[0] samples the last fs3d_get_layer* call wrote,
+ * [1] bytes it copied device-to-host, [2] device allocations the get-layer calls have made since fs3d_create.
+ * Measurement and test aid; no reference counterpart. */
+#define FS3D_N_GETLAYER_INFO 3
+fs3d_status fs3d_get_layer_info(fs3d_ctx *ctx, long long info[FS3D_N_GETLAYER_INFO]);
 
 /* ---- multi-GPU (one process per GPU, x-slabs) ---------------------------------
  * Replaces GPUplan peer copies / PARAplan MPI point-to-point (TimeLayer3D.h:47-247,
