@@ -7,7 +7,6 @@
 #include "fs3d_comm.h"
 #include <rccl/rccl.h>
 #include <condition_variable>
-#include <cstdio>
 #include <cstring>
 #include <cstdlib>
 #include <deque>
@@ -139,13 +138,7 @@ static fs3d_status local_allreduce_sum2(fs3d_ctx *c, double *dev2)
 
 // ---- RCCL transport -------------------------------------------------------------------------------------
 
-static fs3d_status cfail(fs3d_ctx *c, const char *what, ncclResult_t r)
-{
-    char b[256];
-    snprintf(b, sizeof b, "GPU %d: %s failed: %s", c ? c->device : -1, what, ncclGetErrorString(r));
-    if (c) c->err = b;
-    return FS3D_ERR_COMM;
-}
+static fs3d_status cfail(fs3d_ctx *c, const char *what, ncclResult_t r) { return fail(c, FS3D_ERR_COMM, call_failed(c, what, ncclGetErrorString(r))); }
 #define NCCLCHK(c, call) do { ncclResult_t r_ = (call); if (r_ != ncclSuccess) return cfail((c), #call, r_); } while (0)
 
 extern "C" fs3d_status fs3d_comm_unique_id(void *unique_id_128)

@@ -2,24 +2,12 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <algorithm>
 #include <string>
 #include <vector>
 
 #include "../../include/fs3d.h"
-
-// ---- per-cell code word (uint16) ------------------------------------------------
-// bits 0..3   row code of the X sweep
-// bits 4..7   row code of the Y sweep
-// bits 8..11  row code of the Z sweep
-// bits 12..13 NodeType (Geometry.h:31-36)
-// row code: bits 0..1 kind, bit 2 velocity BC is FREE, bit 3 temperature BC is FREE
-// (BC bits are only meaningful for START/END rows).
-// The kinds restate Grid3D::GenerateListSegments (Grid3D.cpp:47-127) per cell: a
-// segment is START, INTERIOR.., END along its line; everything else is SKIP.
-enum { ROW_SKIP = 0, ROW_INTERIOR = 1, ROW_START = 2, ROW_END = 3 };
-#define ROW_VELFREE 4
-#define ROW_TEMPFREE 8
-#define CODE_TYPE_SHIFT 12
+#include "fs3d_tables.h"      // the cell-code word, its row-code constants, UCOL_PITCH; the host definition of the geometry tables
 
 template <typename R>
 struct SweepParams {
@@ -74,7 +62,6 @@ struct SweepParams {
     int store_next;             // pipe kernel, fused time step: 0 when a later local iteration overwrites `next` unread (only the merge uses x)
 };
 
-#define UCOL_PITCH 512                 // codes per shared column (the partition kernels take lines of <= 512 cells)
 #define FS3D_XREDUCE_MAX_RANKS 64      // k_xreduce (kernels_line.hip) holds the R x R slab system of a line in per-thread arrays of this size
 
 // moving geometry (kernels_geom.hip): what fs3d_update_nodes* keeps between calls, allocated by the first one
@@ -207,6 +194,25 @@ struct fs3d_ctx {
     int xblocks = 4;               // line blocks of the cross-slab X sweep pipeline (env FS3D_XBLOCKS)
     std::string err;
 };
+
+// ---- host helpers shared by fs3d_hip.hip, kernels_geom.hip and fs3d_comm.hip ------------------------------------------------------
+// The error text of a call goes to its context; without one (fs3d_create, a NULL handle) to the thread's, for fs3d_last_error(NULL).
+inline thread_local std::string g_create_err;
+static inline fs3d_status fail(fs3d_ctx *c, fs3d_status st, const std::string &msg) { if (c) c->err = msg; else g_create_err = msg; return st; }
+// gpuSafeCall (GPUplan.cpp:173-193): message carries the device id (-1 without a context) and the runtime's error text
+static inline std::string call_failed(const fs3d_ctx *c, const char *call, const char *why)
+{
+    return "GPU " + std::to_string(c ? c->device : -1) + ": " + call + " failed: " + why;
+}
+#define HIPCHK(c, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return fail((c), FS3D_ERR_HIP, call_failed((c), #call, hipGetErrorString(e_))); } while (0)
+#define GTRY(call) do { const fs3d_status st_ = (call); if (st_) return st_; } while (0)
+
+// blocks of 256 threads for n items, at most `cap` (the kernels stride over what is left)
+static inline unsigned grid_for(long long n, int cap = 4096) { return (unsigned)std::max(1LL, std::min<long long>((n + 255) / 256, cap)); }
+
+// device allocations / frees of the geometry paths (fs3d_upload_nodes, fs3d_update_nodes*) are counted: fs3d_geometry_info entry 13
+#define GMALLOC(c, pp, bytes) do { HIPCHK(c, hipMalloc((void **)(pp), (bytes))); (c)->geom_allocs++; } while (0)
+static inline void gfree(fs3d_ctx *c, void *p) { if (p) { hipFree(p); c->geom_allocs++; } }
 
 // kernels_geom.hip
 void fs3d_geom_destroy(fs3d_ctx *c);

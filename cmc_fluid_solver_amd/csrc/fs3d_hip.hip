@@ -6,8 +6,6 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
-#include <cstring>
-#include <map>
 #include <string>
 #include <type_traits>
 
@@ -15,25 +13,6 @@
 #include "fs3d_comm.h"
 
 #define FS3D_VERSION "fs3d-hip 0.1 (gfx950)"
-static thread_local std::string g_create_err;
-
-static fs3d_status fail(fs3d_ctx *c, fs3d_status st, const std::string &msg)
-{
-    if (c) c->err = msg; else g_create_err = msg;
-    return st;
-}
-
-// gpuSafeCall (GPUplan.cpp:173-193): message carries the device id and the runtime's error text
-#define HIPCHK(c, call)                                                                              \
-    do {                                                                                             \
-        hipError_t e_ = (call);                                                                      \
-        if (e_ != hipSuccess) {                                                                      \
-            char b_[512];                                                                            \
-            snprintf(b_, sizeof b_, "GPU %d: %s failed: %s", (c) ? (c)->device : -1, #call,          \
-                     hipGetErrorString(e_));                                                         \
-            return fail((c), FS3D_ERR_HIP, b_);                                                      \
-        }                                                                                            \
-    } while (0)
 
 // ---------------------------------------------------------------------------------
 // auxiliary kernels
@@ -246,12 +225,6 @@ template <typename R> static R *fld(fs3d_ctx *c, int buf, int v) { return (R *)c
 // byte pointer to the first owned cell of field v of layer buffer buf
 static char *fptr(fs3d_ctx *c, int buf, int v) { return (char *)c->lay[buf] + ((size_t)v * c->fstride + c->plane) * c->esize; }
 
-static inline unsigned grid_for(long long n, int bs, int cap = 4096)
-{
-    long long g = (n + bs - 1) / bs;
-    return (unsigned)std::max(1LL, std::min<long long>(g, cap));
-}
-
 // per-launch HIP-event timing on the context's stream (events are pooled and reused): one event pair around what a scope
 // enqueues.  The end event is recorded on every way out of the scope, so rec_collect never meets a pair without one.
 struct RecScope {
@@ -344,7 +317,7 @@ extern "C" fs3d_status fs3d_create(fs3d_ctx **out, int device, fs3d_precision pr
         if (v >= FS3D_SWEEP_AUTO && v <= FS3D_SWEEP_EXACT) c->opt_kernel = v;
     }
     if (const char *e = getenv("FS3D_DEFAULT_F64_PART")) c->opt_f64_part = atoi(e) ? 1 : 0;   // initial FS3D_OPT_F64_PART of new contexts
-#define CK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { char b_[256]; snprintf(b_, sizeof b_, "GPU %d: %s failed: %s", device, #call, hipGetErrorString(e_)); g_create_err = b_; fs3d_destroy(c); return FS3D_ERR_HIP; } } while (0)
+#define CK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { g_create_err = call_failed(c, #call, hipGetErrorString(e_)); fs3d_destroy(c); return FS3D_ERR_HIP; } } while (0)
     CK(hipSetDevice(device));
     CK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     // every field = haloSize + dimx*dimy*dimz + haloSize elements, data at +haloSize
@@ -476,197 +449,61 @@ extern "C" fs3d_status fs3d_profiler_events(fs3d_ctx *c, const char *names[FS3D_
 }
 
 // ---------------------------------------------------------------------------------
-// geometry: row codes from the node-type array
+// geometry: the tables of fs3d_tables.h, built on the host and written to the device
 // ---------------------------------------------------------------------------------
 
-// Per-line restatement of Grid3D::GenerateListSegments (Grid3D.cpp:47-127, nblockZ = 1):
-// walk the line; a run of NODE_IN cells opened at pos+1 takes the cell at pos as its
-// first node and the first non-IN cell after it as its last node; a run that reaches the
-// end of the line without a closing cell is dropped.  kinds[] gets START/INTERIOR/END.
-// Returns the number of segments; *shared_free is set when a cell closes one segment and
-// opens the next while carrying a FREE boundary condition (two different rows on one cell).
-static int line_kinds(const uint8_t *type, long long base, long long stride, int n, uint8_t *kinds,
-                      const uint8_t *bc_vel, const uint8_t *bc_temp, bool *shared_free)
+// one table of the upload: the old buffer goes, one of the table's size comes and takes the table
+template <typename T>
+static fs3d_status put_table(fs3d_ctx *c, T *&dev, const void *src, size_t bytes)
 {
-    int nseg = 0, state = 0, start = 0;
-    for (int s = 0; s < n; s++) kinds[s] = ROW_SKIP;
-    for (int pos = 0; pos + 1 < n; pos++) {
-        if (type[base + (long long)(pos + 1) * stride] == FS3D_NODE_IN) {
-            if (state == 0) start = pos;
-            state = 1;
-        } else if (state == 1) {
-            const int end = pos + 1;
-            if (kinds[start] == ROW_END) {   // closes the previous segment and opens this one
-                const long long id = base + (long long)start * stride;
-                if (bc_vel[id] == FS3D_BC_FREE || bc_temp[id] == FS3D_BC_FREE) *shared_free = true;
-            }
-            kinds[start] = ROW_START;
-            for (int s = start + 1; s < end; s++) kinds[s] = ROW_INTERIOR;
-            kinds[end] = ROW_END;
-            nseg++;
-            state = 0;
-        }
-    }
-    return nseg;
+    gfree(c, dev); dev = nullptr;
+    GMALLOC(c, &dev, bytes);
+    HIPCHK(c, hipMemcpy(dev, src, bytes, hipMemcpyHostToDevice));
+    return FS3D_OK;
 }
 
+// build (build_geom_tables: the definition of every table), refuse, put
 template <typename R>
 static fs3d_status upload_nodes_impl(fs3d_ctx *c, const uint8_t *type, const uint8_t *bc_vel, const uint8_t *bc_temp,
                                      const R *vx, const R *vy, const R *vz, const R *T, int n_seg_out[3])
 {
-    const int gx = c->dimx_global, dy = c->dimy, dz = c->dimz, x0 = c->x_offset, nx = c->dimx;
-    const long long plane = c->plane;
-    std::vector<uint16_t> code((size_t)c->ncell, 0);
-    std::vector<uint8_t> kinds((size_t)std::max(gx, std::max(dy, dz)));
-    bool shared_free = false;
-    long long nseg[3] = {0, 0, 0};
-    auto put = [&](int dir, long long gid, int kind) {
-        const int gi = (int)(gid / plane);
-        if (gi < x0 || gi >= x0 + nx) return;
-        int rc = kind;
-        if (kind == ROW_START || kind == ROW_END) {
-            if (bc_vel[gid] == FS3D_BC_FREE) rc |= ROW_VELFREE;
-            if (bc_temp[gid] == FS3D_BC_FREE) rc |= ROW_TEMPFREE;
-        }
-        code[(size_t)(gid - (long long)x0 * plane)] |= (uint16_t)(rc << (4 * dir));
-    };
-    // X lines span all slabs: kinds come from the global line (as the reference builds
-    // global segments and clips them per device, AdiSolver3D.cpp:475-524)
-    for (int j = 0; j < dy; j++)
-        for (int k = 0; k < dz; k++) {
-            const long long base = (long long)j * dz + k;
-            nseg[0] += line_kinds(type, base, plane, gx, kinds.data(), bc_vel, bc_temp, &shared_free);
-            for (int s = x0; s < x0 + nx; s++) put(0, base + (long long)s * plane, kinds[s]);
-        }
-    for (int i = x0; i < x0 + nx; i++)
-        for (int k = 0; k < dz; k++) {
-            const long long base = (long long)i * plane + k;
-            nseg[1] += line_kinds(type, base, dz, dy, kinds.data(), bc_vel, bc_temp, &shared_free);
-            for (int s = 0; s < dy; s++) put(1, base + (long long)s * dz, kinds[s]);
-        }
-    for (int i = x0; i < x0 + nx; i++)
-        for (int j = 0; j < dy; j++) {
-            const long long base = (long long)i * plane + (long long)j * dz;
-            nseg[2] += line_kinds(type, base, 1, dz, kinds.data(), bc_vel, bc_temp, &shared_free);
-            for (int s = 0; s < dz; s++) put(2, base + s, kinds[s]);
-        }
-    if (shared_free)
+    const GeomTables t = build_geom_tables(c->dimx_global, c->dimy, c->dimz, c->x_offset, c->dimx, type, bc_vel, bc_temp);
+    if (t.shared_free)
         return fail(c, FS3D_ERR_UNSUPPORTED,
                     "fs3d_upload_nodes: a cell with a FREE boundary condition closes one segment and opens the next "
                     "on the same line (two rows on one cell; the reference's result there depends on thread timing)");
-    std::vector<int> bidx;
+    // node values of the local cells, and of the listed ones
+    const R *const val[4] = {vx, vy, vz, T};
+    const long long first = (long long)c->x_offset * c->plane;
     std::vector<R> bval[4];
-    std::vector<R> nv[4];
-    for (int v = 0; v < 4; v++) nv[v].resize((size_t)c->ncell);
-    for (long long l = 0; l < c->ncell; l++) {
-        const long long g = l + (long long)x0 * plane;
-        code[(size_t)l] |= (uint16_t)((type[g] & 3) << CODE_TYPE_SHIFT);
-        nv[0][l] = vx[g]; nv[1][l] = vy[g]; nv[2][l] = vz[g]; nv[3][l] = T[g];
-        if (type[g] == FS3D_NODE_BOUND || type[g] == FS3D_NODE_VALVE) {
-            bidx.push_back((int)l);
-            bval[0].push_back(vx[g]); bval[1].push_back(vy[g]); bval[2].push_back(vz[g]); bval[3].push_back(T[g]);
-        }
+    for (int v = 0; v < 4; v++) {
+        bval[v].resize(t.bnd_idx.size());
+        for (size_t q = 0; q < t.bnd_idx.size(); q++) bval[v][q] = val[v][first + t.bnd_idx[q]];
     }
     HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpy(c->code, code.data(), code.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-    {
-        // dead lines: no cell of the (local part of the) line is on a segment of that direction or NODE_IN -- nothing a
-        // sweep computes for such a line is ever stored; the partition kernels keep them off the row-kind paths
-        const long long nl[3] = {(long long)dy * dz, (long long)nx * dz, (long long)nx * dy};
-        // NODE_IN cells that lie on no segment of some direction (a run without a closing cell, Grid3D.cpp:87-117): the reference merges
-        // the STALE `next` value there -- whatever an earlier sweep left.  Only a geometry without such cells lets the time step drop
-        // stores of `next` that nothing but they could read (time_step_enqueue).
-        long long stale = 0;
-        for (long long l = 0; l < c->ncell; l++)
-            if (((code[(size_t)l] >> CODE_TYPE_SHIFT) & 3) == FS3D_NODE_IN)
-                for (int d = 0; d < 3; d++) stale += ((code[(size_t)l] >> (4 * d)) & 3) == ROW_SKIP;
-        c->stale_in_cells = stale;
-        for (int d = 0; d < 3; d++) {
-            std::vector<uint8_t> dead((size_t)nl[d], 1);
-            for (long long l = 0; l < c->ncell; l++) {
-                const int i = (int)(l / plane), rem = (int)(l - (long long)i * plane), j = rem / dz, k = rem - j * dz;
-                const bool live = ((code[(size_t)l] >> (4 * d)) & 3) != ROW_SKIP || ((code[(size_t)l] >> CODE_TYPE_SHIFT) & 3) == FS3D_NODE_IN;
-                if (live) dead[(size_t)(d == 0 ? (long long)j * dz + k : (d == 1 ? (long long)i * dz + k : (long long)i * dy + j))] = 0;
-            }
-            if (c->dead[d]) { hipFree(c->dead[d]); c->dead[d] = nullptr; c->geom_allocs++; }
-            HIPCHK(c, hipMalloc((void **)&c->dead[d], (size_t)nl[d])); c->geom_allocs++;
-            HIPCHK(c, hipMemcpy(c->dead[d], dead.data(), (size_t)nl[d], hipMemcpyHostToDevice));
-            if (d < 2) {
-                // shared code columns (X: o = j, line cells along i; Y: o = i, cells along j; lanes k in groups of 32): a group is
-                // uniform when all its live lines carry the same (row code of this direction, node type) on every cell
-                if (c->ucol[d]) { hipFree(c->ucol[d]); c->ucol[d] = nullptr; c->geom_allocs++; }
-                c->ucol_cap[d] = 0; c->n_ucol[d] = 0;
-                if (c->uflag[d]) { hipFree(c->uflag[d]); c->uflag[d] = nullptr; c->geom_allocs++; }
-                const int n_o = d == 0 ? dy : nx, n = d == 0 ? nx : dy, ng = (dz + 31) / 32;
-                if (n <= UCOL_PITCH) {
-                    const uint16_t keep = (uint16_t)((0xF << (4 * d)) | (3 << CODE_TYPE_SHIFT));
-                    const long long ss = d == 0 ? plane : dz, os = d == 0 ? (long long)dz : plane;
-                    std::vector<uint16_t> col((size_t)n_o * ng * UCOL_PITCH, 0);
-                    std::vector<uint8_t> flag((size_t)n_o * ng, 0);
-                    for (int o = 0; o < n_o; o++)
-                        for (int g = 0; g < ng; g++) {
-                            uint16_t *cc = &col[((size_t)o * ng + g) * UCOL_PITCH];
-                            int k0 = -1;
-                            bool uni = true;
-                            for (int k = 32 * g; k < std::min(32 * g + 32, dz) && uni; k++) {
-                                if (dead[(size_t)o * dz + k]) continue;
-                                const uint16_t *src = &code[(size_t)((long long)o * os + k)];
-                                if (k0 < 0) { k0 = k; for (int s2 = 0; s2 < n; s2++) cc[s2] = (uint16_t)(src[(size_t)s2 * ss] & keep); }
-                                else for (int s2 = 0; s2 < n; s2++) if ((uint16_t)(src[(size_t)s2 * ss] & keep) != cc[s2]) { uni = false; break; }
-                            }
-                            flag[(size_t)o * ng + g] = uni ? 1 : 0;
-                        }
-                    for (int o = 0; o < n_o; o++)
-                        for (int g = 0; g < ng; g += 2) {
-                            bool pair = flag[(size_t)o * ng + g] & 1;
-                            if (pair && g + 1 < ng) {
-                                pair = flag[(size_t)o * ng + g + 1] & 1;
-                                // an all-dead group holds zeros: it takes the other group's column
-                                const uint16_t *a = &col[((size_t)o * ng + g) * UCOL_PITCH], *b = a + UCOL_PITCH;
-                                bool da = true, db = true;
-                                for (int k = 32 * g; k < std::min(32 * g + 32, dz); k++) da = da && dead[(size_t)o * dz + k];
-                                for (int k = 32 * g + 32; k < std::min(32 * g + 64, dz); k++) db = db && dead[(size_t)o * dz + k];
-                                if (pair && da && !db) std::copy(b, b + UCOL_PITCH, &col[((size_t)o * ng + g) * UCOL_PITCH]);
-                                else if (pair && !da && !db) pair = std::equal(a, a + n, b);
-                            }
-                            if (pair) flag[(size_t)o * ng + g] |= 2;
-                        }
-                    // the distinct columns only (a box has three: interior lines, and the rows / planes at the faces): they stay in the caches
-                    std::map<std::string, unsigned> ids;
-                    std::vector<uint16_t> uniq;
-                    std::vector<unsigned> fl(flag.size(), 0);
-                    for (size_t q = 0; q < flag.size(); q++) {
-                        if (!flag[q]) continue;
-                        const uint16_t *cc = &col[q * UCOL_PITCH];
-                        const std::string key((const char *)cc, (size_t)n * sizeof(uint16_t));
-                        auto it = ids.find(key);
-                        if (it == ids.end()) { it = ids.emplace(key, (unsigned)(uniq.size() / UCOL_PITCH)).first; uniq.insert(uniq.end(), cc, cc + UCOL_PITCH); }
-                        fl[q] = (unsigned)flag[q] | (it->second << 2);
-                    }
-                    c->n_ucol[d] = (int)ids.size();
-                    if (uniq.empty()) uniq.resize(UCOL_PITCH, 0);
-                    HIPCHK(c, hipMalloc((void **)&c->ucol[d], uniq.size() * sizeof(uint16_t))); c->geom_allocs++;
-                    HIPCHK(c, hipMemcpy(c->ucol[d], uniq.data(), uniq.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-                    HIPCHK(c, hipMalloc((void **)&c->uflag[d], fl.size() * sizeof(unsigned))); c->geom_allocs++;
-                    HIPCHK(c, hipMemcpy(c->uflag[d], fl.data(), fl.size() * sizeof(unsigned), hipMemcpyHostToDevice));
-                }
-            }
-        }
+    HIPCHK(c, hipMemcpy(c->code, t.code.data(), t.code.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+    c->stale_in_cells = t.stale_in_cells;
+    for (int d = 0; d < 3; d++) {
+        GTRY(put_table(c, c->dead[d], t.dead[d].data(), t.dead[d].size()));
+        if (d == 2) break;
+        // exact-size tables (ucol_cap 0: fs3d_update_nodes allocates its own); none where the lines exceed UCOL_PITCH
+        gfree(c, c->ucol[d]); c->ucol[d] = nullptr;
+        gfree(c, c->uflag[d]); c->uflag[d] = nullptr;
+        c->ucol_cap[d] = 0; c->n_ucol[d] = t.n_ucol[d];
+        if (!t.has_columns[d]) continue;
+        GTRY(put_table(c, c->ucol[d], t.ucol[d].data(), t.ucol[d].size() * sizeof(uint16_t)));
+        GTRY(put_table(c, c->uflag[d], t.uflag[d].data(), t.uflag[d].size() * sizeof(unsigned)));
     }
     for (int v = 0; v < 4; v++)
-        HIPCHK(c, hipMemcpy((R *)c->node + (size_t)v * c->nstride, nv[v].data(), (size_t)c->ncell * sizeof(R), hipMemcpyHostToDevice));
-    if (c->bnd_idx) { hipFree(c->bnd_idx); c->bnd_idx = nullptr; c->geom_allocs++; }
-    for (int v = 0; v < 4; v++) if (c->bnd_val[v]) { hipFree(c->bnd_val[v]); c->bnd_val[v] = nullptr; c->geom_allocs++; }
-    c->n_bnd = (int)bidx.size(); c->bnd_cap = c->n_bnd;
+        HIPCHK(c, hipMemcpy((R *)c->node + (size_t)v * c->nstride, val[v] + first, (size_t)c->ncell * sizeof(R), hipMemcpyHostToDevice));
+    gfree(c, c->bnd_idx); c->bnd_idx = nullptr;
+    for (int v = 0; v < 4; v++) { gfree(c, c->bnd_val[v]); c->bnd_val[v] = nullptr; }
+    c->n_bnd = (int)t.bnd_idx.size(); c->bnd_cap = c->n_bnd;
     if (c->n_bnd) {
-        HIPCHK(c, hipMalloc((void **)&c->bnd_idx, sizeof(int) * bidx.size())); c->geom_allocs++;
-        HIPCHK(c, hipMemcpy(c->bnd_idx, bidx.data(), sizeof(int) * bidx.size(), hipMemcpyHostToDevice));
-        for (int v = 0; v < 4; v++) {
-            HIPCHK(c, hipMalloc(&c->bnd_val[v], sizeof(R) * bidx.size())); c->geom_allocs++;
-            HIPCHK(c, hipMemcpy(c->bnd_val[v], bval[v].data(), sizeof(R) * bidx.size(), hipMemcpyHostToDevice));
-        }
+        GTRY(put_table(c, c->bnd_idx, t.bnd_idx.data(), sizeof(int) * t.bnd_idx.size()));
+        for (int v = 0; v < 4; v++) GTRY(put_table(c, c->bnd_val[v], bval[v].data(), sizeof(R) * t.bnd_idx.size()));
     }
-    for (int d = 0; d < 3; d++) { c->nseg[d] = (int)nseg[d]; if (n_seg_out) n_seg_out[d] = (int)nseg[d]; }
+    for (int d = 0; d < 3; d++) { c->nseg[d] = (int)t.nseg[d]; if (n_seg_out) n_seg_out[d] = (int)t.nseg[d]; }
     c->have_nodes = true; c->uploaded_once = true; c->n_create_segments++;
     return FS3D_OK;
 }
@@ -1079,7 +916,7 @@ template <typename R>
 static fs3d_status merge_buffers(fs3d_ctx *c, int b_src, int b_dest)
 {
     RecScope rec(c, 4);
-    hipLaunchKernelGGL((k_merge<R>), dim3(grid_for(c->ncell, 256)), dim3(256), 0, c->stream, c->code, c->ncell,
+    hipLaunchKernelGGL((k_merge<R>), dim3(grid_for(c->ncell)), dim3(256), 0, c->stream, c->code, c->ncell,
                        fld<R>(c, b_src, 0), fld<R>(c, b_src, 1), fld<R>(c, b_src, 2), fld<R>(c, b_src, 3),
                        fld<R>(c, b_dest, 0), fld<R>(c, b_dest, 1), fld<R>(c, b_dest, 2), fld<R>(c, b_dest, 3));
     HIPCHK(c, hipGetLastError());
@@ -1134,7 +971,7 @@ static fs3d_status div_error_enqueue(fs3d_ctx *c, int layer)
                        (c->dimy + DIVE_JS - 1) / DIVE_JS);
     hipLaunchKernelGGL(k_div_final, dim3(1), dim3(256), 0, c->stream, c->red_buf + 2, c->red_blocks, c->red_buf);
     if (c->opt_err_order) {
-        hipLaunchKernelGGL((k_div_terms<R>), dim3(grid_for(c->ncell, 256)), dim3(256), 0, c->stream, c->code,
+        hipLaunchKernelGGL((k_div_terms<R>), dim3(grid_for(c->ncell)), dim3(256), 0, c->stream, c->code,
                            (const R *)fld<R>(c, b, 0), (const R *)fld<R>(c, b, 1), (const R *)fld<R>(c, b, 2),
                            c->dimx, c->dimy, c->dimz, (R)c->gdx, (R)c->gdy, (R)c->gdz, c->err_terms);
     }
@@ -1381,13 +1218,13 @@ static fs3d_status get_layer_impl(fs3d_ctx *c, R *outV, double *outT, int odx, i
         c->gl_stage_bytes = vbytes + (size_t)n * 8;
         c->gl_info[2]++;
     }
-    hipLaunchKernelGGL((k_clear_type<R>), dim3(grid_for(c->ncell, 256)), dim3(256), 0, c->stream, c->code, c->ncell,
+    hipLaunchKernelGGL((k_clear_type<R>), dim3(grid_for(c->ncell)), dim3(256), 0, c->stream, c->code, c->ncell,
                        (int)FS3D_NODE_OUT, (R)99999.0f, fld<R>(c, b, 0), fld<R>(c, b, 1), fld<R>(c, b, 2), fld<R>(c, b, 3));
     HIPCHK(c, hipGetLastError());
     if (n) {
         R *kV = dev ? dV : (R *)c->gl_stage;
         double *kT = dev ? dT : (double *)((char *)c->gl_stage + vbytes);
-        hipLaunchKernelGGL((k_get_layer<R>), dim3((unsigned)(i1 - i0), grid_for(po, 256, 1024)), dim3(256), 0, c->stream,
+        hipLaunchKernelGGL((k_get_layer<R>), dim3((unsigned)(i1 - i0), grid_for(po, 1024)), dim3(256), 0, c->stream,
                            (const R *)fld<R>(c, b, 0), (const R *)fld<R>(c, b, 1), (const R *)fld<R>(c, b, 2), (const R *)fld<R>(c, b, 3),
                            x_offset, c->dimx, c->plane, c->dimy, c->dimz, gx, odx, ody, odz, i0, i1, kV, kT);
         HIPCHK(c, hipGetLastError());

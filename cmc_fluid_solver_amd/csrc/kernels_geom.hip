@@ -1,13 +1,13 @@
 // Moving geometry: the tables the sweeps read, rebuilt on the device between time steps
 // (fs3d_update_nodes / fs3d_update_nodes_dev), Solver3D::ClearOutterCells (fs3d_clear_outer_cells) and the
-// table summary fs3d_geometry_info.  The host routine upload_nodes_impl (fs3d_hip.hip) stays the first upload and the
-// definition of every table; the kernels here end with the same tables.
+// table summary fs3d_geometry_info.  build_geom_tables (fs3d_tables.h, host only; fs3d_upload_nodes writes what it
+// returns) stays the first upload and the definition of every table; the kernels here end with the same tables.
 // Also the extrusion of a Shape2D grid into the node arrays on the device (k_geom_extrude; fs3d_extrude_shape2d_dev,
 // fs3d_update_nodes_shape2d): a moving Shape2D geometry then ships its 2D grid per step, not the 3D node arrays.
 // And the voxelisation of a Shape3D mesh (k_geom_raster_mesh, the flood fill k_geom_fill_z / k_geom_fill_strided, k_geom_mesh_nodes;
 // fs3d_voxelize_shape3d_dev, fs3d_flood_fill_dev, fs3d_update_nodes_shape3d): a moving mesh ships its vertices per step.
 //
-// Row kinds without the serial walk of line_kinds (fs3d_hip.hip): that walk opens a run at `pos` when cell pos + 1 is
+// Row kinds without the serial walk of line_kinds (fs3d_tables.h): that walk opens a run at `pos` when cell pos + 1 is
 // NODE_IN and closes it at the first cell after the run that is not NODE_IN; a run that reaches the end of the line is
 // dropped.  So, with Lst = the last index of the line whose type is not NODE_IN (-1: none),
 //   INTERIOR(s)  <=>  s >= 1, type[s] == NODE_IN and s < Lst        (cell 0 only ever opens a run; s < Lst: a closing cell exists)
@@ -19,34 +19,11 @@
 #include <chrono>
 #include <climits>
 #include <cmath>
-#include <cstdio>
 #include <cstring>
 #include <string>
 #include <unordered_map>
 
 #include "fs3d_common.h"
-
-static fs3d_status gfail(fs3d_ctx *c, fs3d_status st, const std::string &msg)
-{
-    if (c) c->err = msg;
-    return st;
-}
-
-#define GHIP(c, call)                                                                                \
-    do {                                                                                             \
-        hipError_t e_ = (call);                                                                      \
-        if (e_ != hipSuccess) {                                                                      \
-            char b_[512];                                                                            \
-            snprintf(b_, sizeof b_, "GPU %d: %s failed: %s", (c)->device, #call, hipGetErrorString(e_)); \
-            return gfail((c), FS3D_ERR_HIP, b_);                                                     \
-        }                                                                                            \
-    } while (0)
-
-#define GTRY(call) do { const fs3d_status st_ = (call); if (st_) return st_; } while (0)
-
-// device allocations / frees of the geometry paths are counted (fs3d_geometry_info entry 13)
-#define GMALLOC(c, pp, bytes) do { GHIP(c, hipMalloc((void **)(pp), (bytes))); (c)->geom_allocs++; } while (0)
-static void gfree(fs3d_ctx *c, void *p) { if (p) { hipFree(p); c->geom_allocs++; } }
 
 // counter words of one update (device, read back once)
 enum { GC_NSEG = 0 /* 0..2 */, GC_NBND = 3, GC_STALE = 4, GC_SHARED = 5, GC_LIST = 6, GC_MISMATCH = 7, GC_WORDS = 8 };
@@ -57,7 +34,7 @@ enum { GC_NSEG = 0 /* 0..2 */, GC_NBND = 3, GC_STALE = 4, GC_SHARED = 5, GC_LIST
 
 // X and Y lines: cells `ss` apart, neighbouring lines along k contiguous -- one thread per line, lanes along k read coalesced.
 // lst[line] = last index whose type is not NODE_IN (-1: none); dead[line] = 1 when the line has no NODE_IN cell (every cell on a
-// segment lies on a line with a NODE_IN cell, so this is upload_nodes_impl's "no segment cell and no NODE_IN cell").
+// segment lies on a line with a NODE_IN cell, so this is geom_dead_lines' "no segment cell and no NODE_IN cell").
 __global__ void __launch_bounds__(256) k_geom_lines_strided(const uint8_t *__restrict__ type, int n_o, int dimz, long long os,
                                                              long long ss, int n, int *__restrict__ lst, uint8_t *__restrict__ dead)
 {
@@ -204,7 +181,7 @@ __device__ __forceinline__ unsigned long long geom_mix(unsigned long long x)
     return x ^ (x >> 31);
 }
 
-// Shared code columns of direction d (X: o = j, cells along i; Y: o = i, cells along j), as upload_nodes_impl defines them: one
+// Shared code columns of direction d (X: o = j, cells along i; Y: o = i, cells along j), as geom_shared_columns defines them: one
 // wave per pair of groups (g, g + 1) of 32 neighbouring lines, lanes 0..31 the lines of g, lanes 32..63 those of g + 1.
 // col[o][g][s] = the (row code of d, node type) of the group's first live line; cflag bit 0 = every live line of the group equals
 // it on every cell, bit 1 (even g) = so does the pair; hash[o][g] = a hash of the column for the host's identity decision.
@@ -629,12 +606,6 @@ __global__ void __launch_bounds__(256) k_geom_mesh_nodes(const uint8_t *__restri
 // host side
 // ---------------------------------------------------------------------------------
 
-static inline unsigned geom_grid(long long n, int cap = 4096)
-{
-    const long long g = (n + 255) / 256;
-    return (unsigned)(g < 1 ? 1 : (g > cap ? cap : g));
-}
-
 // The lines of direction d.  d = 0 (X) and 1 (Y): n_o * dimz lines -- `os` apart along the outer index, neighbours along k -- of n
 // cells `ss` apart; d = 2 (Z): dimx * dimy lines of dimz contiguous cells, one behind the other (n_o is not used).
 struct GeomLines { int n_o; long long os, ss; int n; long long nlines; };
@@ -687,7 +658,7 @@ static void gev_collect(fs3d_ctx *c)
 static fs3d_status gev_sync(fs3d_ctx *c)
 {
     gev_end(c);
-    GHIP(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     return FS3D_OK;
 }
 
@@ -723,16 +694,16 @@ static fs3d_status geom_prepare(fs3d_ctx *c, bool need_stage)
     size_t host_bytes = GC_WORDS * sizeof(unsigned long long);
     for (int d = 0; d < 2; d++) {
         const GeomLines L = geom_lines(c, d);
-        if (L.n > UCOL_PITCH) continue;                  // as upload_nodes_impl: no shared columns for longer lines
+        if (L.n > UCOL_PITCH) continue;                  // as geom_shared_columns: no shared columns for longer lines
         const size_t nq = (size_t)L.n_o * geom_ng(c);
         GMALLOC(c, &g.col[d], nq * UCOL_PITCH * sizeof(uint16_t));
-        GHIP(c, hipMemsetAsync(g.col[d], 0, nq * UCOL_PITCH * sizeof(uint16_t), c->stream));
+        HIPCHK(c, hipMemsetAsync(g.col[d], 0, nq * UCOL_PITCH * sizeof(uint16_t), c->stream));
         GMALLOC(c, &g.cflag[d], nq);
         GMALLOC(c, &g.hash[d], nq * sizeof(unsigned long long));
         GMALLOC(c, &g.rep[d], nq * sizeof(int));
         host_bytes = std::max(host_bytes, nq * (sizeof(unsigned long long) + sizeof(unsigned) + sizeof(int) + 1) + 64);
     }
-    GHIP(c, hipHostMalloc((void **)&g.host, host_bytes, hipHostMallocDefault));
+    HIPCHK(c, hipHostMalloc((void **)&g.host, host_bytes, hipHostMallocDefault));
     GMALLOC(c, &g.cnt, GC_WORDS * sizeof(unsigned long long));
     return FS3D_OK;
 }
@@ -754,14 +725,14 @@ static fs3d_status geom_columns(fs3d_ctx *c, int d)
     gev_begin(c);
     hipLaunchKernelGGL(k_geom_columns, dim3((unsigned)(L.n_o * ((ng + 1) / 2))), dim3(64), 0, c->stream, c->code, c->dead[d], ng, c->dimz,
                        L.os, L.ss, L.n, keep, g.col[d], g.cflag[d], g.hash[d]);
-    GHIP(c, hipGetLastError());
-    // identities on the host from the hashes (a few KB), numbered in the order of first appearance as upload_nodes_impl numbers them
+    HIPCHK(c, hipGetLastError());
+    // identities on the host from the hashes (a few KB), numbered in the order of first appearance as geom_shared_columns numbers them
     unsigned long long *hh = (unsigned long long *)g.host;
     unsigned *fl = (unsigned *)(hh + nq);
     int *rep = (int *)(fl + nq);
     uint8_t *cf = (uint8_t *)(rep + nq);
-    GHIP(c, hipMemcpyAsync(hh, g.hash[d], nq * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-    GHIP(c, hipMemcpyAsync(cf, g.cflag[d], nq, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(hh, g.hash[d], nq * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(cf, g.cflag[d], nq, hipMemcpyDeviceToHost, c->stream));
     GTRY(gev_sync(c));
     std::unordered_map<unsigned long long, unsigned> ids;
     unsigned nid = 0;
@@ -774,12 +745,12 @@ static fs3d_status geom_columns(fs3d_ctx *c, int d)
     }
     c->n_ucol[d] = (int)nid;
     gev_begin(c);
-    GHIP(c, hipMemcpyAsync(c->uflag[d], fl, nq * sizeof(unsigned), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->uflag[d], fl, nq * sizeof(unsigned), hipMemcpyHostToDevice, c->stream));
     if (nid) {
-        GHIP(c, hipMemcpyAsync(g.rep[d], rep, nid * sizeof(int), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(g.rep[d], rep, nid * sizeof(int), hipMemcpyHostToDevice, c->stream));
         hipLaunchKernelGGL(k_geom_gather, dim3(nid), dim3(256), 0, c->stream, g.col[d], g.rep[d], c->ucol[d]);
         hipLaunchKernelGGL(k_geom_verify, dim3((unsigned)nq), dim3(64), 0, c->stream, g.col[d], c->uflag[d], c->ucol[d], L.n, g.cnt);
-        GHIP(c, hipGetLastError());
+        HIPCHK(c, hipGetLastError());
     }
     // the pinned block is reused by the next direction: its copies must have left
     return gev_sync(c);
@@ -790,24 +761,24 @@ static fs3d_status update_nodes_impl(fs3d_ctx *c, const uint8_t *type, const uin
 {
     fs3d_geom &g = c->geom;
     const long long ncell = c->ncell;
-    GHIP(c, hipMemsetAsync(g.cnt, 0, GC_WORDS * sizeof(unsigned long long), c->stream));
+    HIPCHK(c, hipMemsetAsync(g.cnt, 0, GC_WORDS * sizeof(unsigned long long), c->stream));
     for (int d = 0; d < 3; d++) {
         const GeomLines L = geom_lines(c, d);
         if (d < 2)
-            hipLaunchKernelGGL(k_geom_lines_strided, dim3(geom_grid(L.nlines, 1 << 30)), dim3(256), 0, c->stream, type, L.n_o, c->dimz,
+            hipLaunchKernelGGL(k_geom_lines_strided, dim3(grid_for(L.nlines, 1 << 30)), dim3(256), 0, c->stream, type, L.n_o, c->dimz,
                                L.os, L.ss, L.n, g.lst[d], c->dead[d]);
         else
-            hipLaunchKernelGGL(k_geom_lines_z, dim3(geom_grid(L.nlines * 64, 1 << 30)), dim3(256), 0, c->stream, type, L.nlines, c->dimz,
+            hipLaunchKernelGGL(k_geom_lines_z, dim3(grid_for(L.nlines * 64, 1 << 30)), dim3(256), 0, c->stream, type, L.nlines, c->dimz,
                                g.lst[d], c->dead[d]);
     }
-    hipLaunchKernelGGL(k_geom_codes, dim3(geom_grid(ncell)), dim3(256), 0, c->stream, type, bc_vel, bc_temp, g.lst[0], g.lst[1],
+    hipLaunchKernelGGL(k_geom_codes, dim3(grid_for(ncell)), dim3(256), 0, c->stream, type, bc_vel, bc_temp, g.lst[0], g.lst[1],
                        g.lst[2], c->dimx, c->dimy, c->dimz, c->code, g.cnt);
-    GHIP(c, hipGetLastError());
+    HIPCHK(c, hipGetLastError());
     unsigned long long *hc = (unsigned long long *)g.host;
-    GHIP(c, hipMemcpyAsync(hc, g.cnt, GC_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(hc, g.cnt, GC_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
     GTRY(gev_sync(c));
     if (hc[GC_SHARED])
-        return gfail(c, FS3D_ERR_UNSUPPORTED,
+        return fail(c, FS3D_ERR_UNSUPPORTED,
                      "fs3d_update_nodes: a cell with a FREE boundary condition closes one segment and opens the next "
                      "on the same line (two rows on one cell; the reference's result there depends on thread timing)");
     const long long nseg[3] = {(long long)hc[0], (long long)hc[1], (long long)hc[2]};
@@ -825,19 +796,19 @@ static fs3d_status update_nodes_impl(fs3d_ctx *c, const uint8_t *type, const uin
     }
     if (nbnd) {
         gev_begin(c);
-        hipLaunchKernelGGL((k_geom_bnd_list<R>), dim3(geom_grid((ncell + GEOM_LIST_CHUNKS - 1) / GEOM_LIST_CHUNKS)), dim3(256), 0, c->stream, type, ncell, (const R *)c->node,
+        hipLaunchKernelGGL((k_geom_bnd_list<R>), dim3(grid_for((ncell + GEOM_LIST_CHUNKS - 1) / GEOM_LIST_CHUNKS)), dim3(256), 0, c->stream, type, ncell, (const R *)c->node,
                            c->nstride, c->bnd_cap, c->bnd_idx, (R *)c->bnd_val[0], (R *)c->bnd_val[1], (R *)c->bnd_val[2],
                            (R *)c->bnd_val[3], g.cnt);
-        GHIP(c, hipGetLastError());
+        HIPCHK(c, hipGetLastError());
     }
     for (int d = 0; d < 2; d++) GTRY(geom_columns(c, d));
     gev_begin(c);
-    GHIP(c, hipMemcpyAsync(hc, g.cnt, GC_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(hc, g.cnt, GC_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
     GTRY(gev_sync(c));
     if ((long long)hc[GC_LIST] != nbnd)
-        return gfail(c, FS3D_ERR_HIP, "fs3d_update_nodes: the BOUND / VALVE list does not hold the counted cells");
+        return fail(c, FS3D_ERR_HIP, "fs3d_update_nodes: the BOUND / VALVE list does not hold the counted cells");
     if (hc[GC_MISMATCH])
-        return gfail(c, FS3D_ERR_HIP, "fs3d_update_nodes: two different shared code columns have the same hash; tables not usable");
+        return fail(c, FS3D_ERR_HIP, "fs3d_update_nodes: two different shared code columns have the same hash; tables not usable");
     c->n_bnd = (int)nbnd;
     for (int d = 0; d < 3; d++) { c->nseg[d] = (int)nseg[d]; if (n_seg_out) n_seg_out[d] = (int)nseg[d]; }
     return FS3D_OK;
@@ -911,10 +882,10 @@ static fs3d_status extrude_check(fs3d_ctx *c, ExtrudeIn &in, const char *name)
 {
     fs3d_geom &g = c->geom;
     if (!extrude_active_dimz(in.dz, in.depth, &in.A) || in.A < 2 || in.A > c->dimz)
-        return gfail(c, FS3D_ERR_INVALID, std::string(name) + ": active_dimz = ceil(depth / dz) + 1 must lie in 2 .. dimz");
+        return fail(c, FS3D_ERR_INVALID, std::string(name) + ": active_dimz = ceil(depth / dz) + 1 must lie in 2 .. dimz");
     const size_t ncol = (size_t)c->dimx * c->dimy;
-    GHIP(c, hipSetDevice(c->device));
-    if (!g.ex_host) GHIP(c, hipHostMalloc(&g.ex_host, ex_bytes(ncol), hipHostMallocDefault));
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!g.ex_host) HIPCHK(c, hipHostMalloc(&g.ex_host, ex_bytes(ncol), hipHostMallocDefault));
     if (!g.ex_dev) {                                      // (a failure leaves the pointer null: the next call allocates again)
         GMALLOC(c, &g.ex_dev, ex_bytes(ncol));
         g.ex_bottom_valid = false; g.ex_dz = -1;
@@ -927,10 +898,10 @@ static fs3d_status extrude_check(fs3d_ctx *c, ExtrudeIn &in, const char *name)
     }
     for (size_t q = 0; q < ncol; q++) {
         const uint8_t t = in.cell[q];
-        if (t > FS3D_NODE_VALVE) return gfail(c, FS3D_ERR_INVALID, std::string(name) + ": a cell2d value is not a node type");
+        if (t > FS3D_NODE_VALVE) return fail(c, FS3D_ERR_INVALID, std::string(name) + ": a cell2d value is not a node type");
         // where ExtrudeShape2D would write outside the column's dimz cells (it reads `bottom` of the columns that are not NODE_OUT)
         if (t != FS3D_NODE_OUT && (bottom[q] < -1 || bottom[q] >= c->dimz))
-            return gfail(c, FS3D_ERR_INVALID, std::string(name) + ": depth_var puts the bottom of a column outside the grid");
+            return fail(c, FS3D_ERR_INVALID, std::string(name) + ": depth_var puts the bottom of a column outside the grid");
     }
     memcpy(h, in.velx, 4 * ncol); memcpy(h + 4 * ncol, in.vely, 4 * ncol); memcpy(h + 8 * ncol, in.T, 4 * ncol);
     memcpy(h + ex_off_cell(ncol), in.cell, ncol);
@@ -944,16 +915,16 @@ static fs3d_status extrude_launch(fs3d_ctx *c, const ExtrudeIn &in, const NodeAr
     fs3d_geom &g = c->geom;
     const size_t ncol = (size_t)c->dimx * c->dimy;
     const char *d = (const char *)g.ex_dev;
-    GHIP(c, hipMemcpyAsync(g.ex_dev, g.ex_host, g.ex_bottom_valid ? ex_off_cell(ncol) + ncol : ex_bytes(ncol), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(g.ex_dev, g.ex_host, g.ex_bottom_valid ? ex_off_cell(ncol) + ncol : ex_bytes(ncol), hipMemcpyHostToDevice, c->stream));
     g.ex_bottom_valid = true;
     const bool vec = a.vec4(c->dimz);
     const long long nthr = (long long)ncol * (vec ? c->dimz / 4 : c->dimz);
     auto kern = vec ? k_geom_extrude<R, 4> : k_geom_extrude<R, 1>;
-    hipLaunchKernelGGL(kern, dim3(geom_grid(nthr, 1 << 30)), dim3(256), 0, c->stream, (const float *)d, (const float *)(d + 4 * ncol),
+    hipLaunchKernelGGL(kern, dim3(grid_for(nthr, 1 << 30)), dim3(256), 0, c->stream, (const float *)d, (const float *)(d + 4 * ncol),
                        (const float *)(d + 8 * ncol), (const int *)(d + ex_off_bottom(ncol)), (const uint8_t *)(d + ex_off_cell(ncol)),
                        (long long)ncol, c->dimz, in.A, (float)in.baseT, a.type, a.bc_vel, a.bc_temp, (R *)a.v[0], (R *)a.v[1], (R *)a.v[2],
                        (R *)a.v[3]);
-    GHIP(c, hipGetLastError());
+    HIPCHK(c, hipGetLastError());
     return FS3D_OK;
 }
 
@@ -971,14 +942,14 @@ static inline unsigned *mesh_host_cnt(const fs3d_geom &g) { return (unsigned *)(
 static fs3d_status mesh_prepare(fs3d_ctx *c, int nvert, int ntri)
 {
     fs3d_geom &g = c->geom;
-    GHIP(c, hipSetDevice(c->device));
+    HIPCHK(c, hipSetDevice(c->device));
     if (!g.mesh_cnt) GMALLOC(c, &g.mesh_cnt, MC_WORDS * sizeof(unsigned));
     if (g.mesh_host && nvert <= g.mesh_vcap && ntri <= g.mesh_tcap) return FS3D_OK;
     if (g.mesh_host) { hipHostFree(g.mesh_host); g.mesh_host = nullptr; }
     gfree(c, g.mesh_vert); g.mesh_vert = nullptr;
     gfree(c, g.mesh_idx); g.mesh_idx = nullptr;
     g.mesh_vcap = std::max(std::max(nvert, g.mesh_vcap), 1); g.mesh_tcap = std::max(std::max(ntri, g.mesh_tcap), 1); g.mesh_ntri_dev = -1;
-    GHIP(c, hipHostMalloc(&g.mesh_host, (3 * (size_t)g.mesh_vcap + 3 * (size_t)g.mesh_tcap) * 4 + MC_WORDS * sizeof(unsigned), hipHostMallocDefault));
+    HIPCHK(c, hipHostMalloc(&g.mesh_host, (3 * (size_t)g.mesh_vcap + 3 * (size_t)g.mesh_tcap) * 4 + MC_WORDS * sizeof(unsigned), hipHostMallocDefault));
     GMALLOC(c, &g.mesh_vert, 3 * (size_t)g.mesh_vcap * sizeof(float));
     GMALLOC(c, &g.mesh_idx, 3 * (size_t)g.mesh_tcap * sizeof(int));
     return FS3D_OK;
@@ -989,14 +960,14 @@ static fs3d_status mesh_prepare(fs3d_ctx *c, int nvert, int ntri)
 static fs3d_status mesh_check(fs3d_ctx *c, const MeshIn &in, const char *name, bool *new_idx)
 {
     fs3d_geom &g = c->geom;
-    if (in.nvert < 1 || in.ntri < 0) return gfail(c, FS3D_ERR_INVALID, std::string(name) + ": a mesh has at least one vertex and no negative number of triangles");
+    if (in.nvert < 1 || in.ntri < 0) return fail(c, FS3D_ERR_INVALID, std::string(name) + ": a mesh has at least one vertex and no negative number of triangles");
     for (int q = 0; q < 3 * in.ntri; q++)
-        if (in.tri[q] < 0 || in.tri[q] >= in.nvert) return gfail(c, FS3D_ERR_INVALID, std::string(name) + ": triangle index outside the vertex list");
+        if (in.tri[q] < 0 || in.tri[q] >= in.nvert) return fail(c, FS3D_ERR_INVALID, std::string(name) + ": triangle index outside the vertex list");
     // keeps (int) defined and the line loops short
     for (const float *a : {in.x, in.y, in.z})
         for (int q = 0; q < in.nvert; q++)
             if (!(std::fabs(a[q]) <= 65536.0f))
-                return gfail(c, FS3D_ERR_INVALID, std::string(name) + ": a vertex coordinate is not finite or exceeds 65536 grid cells in magnitude");
+                return fail(c, FS3D_ERR_INVALID, std::string(name) + ": a vertex coordinate is not finite or exceeds 65536 grid cells in magnitude");
     GTRY(mesh_prepare(c, in.nvert, in.ntri));
     float *hv = mesh_host_vert(g);
     memcpy(hv, in.x, 4 * (size_t)in.nvert); memcpy(hv + g.mesh_vcap, in.y, 4 * (size_t)in.nvert); memcpy(hv + 2 * (size_t)g.mesh_vcap, in.z, 4 * (size_t)in.nvert);
@@ -1012,27 +983,27 @@ static fs3d_status mesh_fill(fs3d_ctx *c, uint8_t *type, bool with_flag, const c
 {
     fs3d_geom &g = c->geom;
     unsigned *hc = mesh_host_cnt(g);
-    GHIP(c, hipMemsetAsync(type, FS3D_NODE_OUT, 1, c->stream));      // cell (0,0,0), whatever it was
+    HIPCHK(c, hipMemsetAsync(type, FS3D_NODE_OUT, 1, c->stream));      // cell (0,0,0), whatever it was
     g.mesh_fill_rounds = 0;
     // no cap on the rounds: one that changes nothing ends the fill, every other one turns at least one cell
     for (bool first = true, done = false; !done; first = false) {
         gev_begin(c);
-        GHIP(c, hipMemsetAsync(g.mesh_cnt + MC_ROUND, 0, MESH_FILL_BATCH * sizeof(unsigned), c->stream));
+        HIPCHK(c, hipMemsetAsync(g.mesh_cnt + MC_ROUND, 0, MESH_FILL_BATCH * sizeof(unsigned), c->stream));
         for (int r = 0; r < MESH_FILL_BATCH; r++)
             for (int d = 2; d >= 0; d--) {
                 const GeomLines L = geom_lines(c, d);
                 unsigned *cnt = g.mesh_cnt + MC_ROUND + r;
                 if (d == 2)
-                    hipLaunchKernelGGL(k_geom_fill_z, dim3(geom_grid(L.nlines * 64, 1 << 30)), dim3(256), 0, c->stream, type, L.nlines, c->dimz, cnt);
+                    hipLaunchKernelGGL(k_geom_fill_z, dim3(grid_for(L.nlines * 64, 1 << 30)), dim3(256), 0, c->stream, type, L.nlines, c->dimz, cnt);
                 else
-                    hipLaunchKernelGGL(k_geom_fill_strided, dim3(geom_grid(L.nlines, 1 << 30)), dim3(256), 0, c->stream, type, L.n_o, c->dimz,
+                    hipLaunchKernelGGL(k_geom_fill_strided, dim3(grid_for(L.nlines, 1 << 30)), dim3(256), 0, c->stream, type, L.n_o, c->dimz,
                                        L.os, L.ss, L.n, cnt);
             }
-        GHIP(c, hipGetLastError());
-        GHIP(c, hipMemcpyAsync(hc, g.mesh_cnt, MC_WORDS * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(hc, g.mesh_cnt, MC_WORDS * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
         GTRY(gev_sync(c));
         if (first && with_flag && hc[MC_FLAG])
-            return gfail(c, FS3D_ERR_INVALID, std::string(name) + (hc[MC_FLAG] & MESH_FLAG_SCANLINE
+            return fail(c, FS3D_ERR_INVALID, std::string(name) + (hc[MC_FLAG] & MESH_FLAG_SCANLINE
                          ? ": Shape3D: a scan line of a polygon never reaches its end cell (the reference loops there)"
                          : ": Shape3D: the scan of a polygon stops advancing (its triangle is too thin for fp32 at these coordinates; the reference loops there)"));
         for (int r = 0; r < MESH_FILL_BATCH && !done; r++) { g.mesh_fill_rounds++; done = hc[MC_ROUND + r] == 0; }
@@ -1046,25 +1017,25 @@ template <typename R>
 static fs3d_status mesh_launch(fs3d_ctx *c, const MeshIn &in, bool new_idx, const char *name, const NodeArrays &a)
 {
     fs3d_geom &g = c->geom;
-    GHIP(c, hipMemcpyAsync(g.mesh_vert, g.mesh_host, 3 * (size_t)g.mesh_vcap * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(g.mesh_vert, g.mesh_host, 3 * (size_t)g.mesh_vcap * sizeof(float), hipMemcpyHostToDevice, c->stream));
     if (new_idx) {
         g.mesh_ntri_dev = -1;
-        GHIP(c, hipMemcpyAsync(g.mesh_idx, mesh_host_idx(g), 12 * (size_t)std::max(in.ntri, 1), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(g.mesh_idx, mesh_host_idx(g), 12 * (size_t)std::max(in.ntri, 1), hipMemcpyHostToDevice, c->stream));
         g.mesh_ntri_dev = in.ntri;
     }
-    GHIP(c, hipMemsetAsync(a.type, FS3D_NODE_IN, (size_t)c->ncell, c->stream));
-    GHIP(c, hipMemsetAsync(g.mesh_cnt, 0, sizeof(unsigned), c->stream));
+    HIPCHK(c, hipMemsetAsync(a.type, FS3D_NODE_IN, (size_t)c->ncell, c->stream));
+    HIPCHK(c, hipMemsetAsync(g.mesh_cnt, 0, sizeof(unsigned), c->stream));
     if (in.ntri)
         hipLaunchKernelGGL(k_geom_raster_mesh, dim3((unsigned)in.ntri), dim3(64), 0, c->stream, g.mesh_vert, g.mesh_vert + g.mesh_vcap,
                            g.mesh_vert + 2 * (size_t)g.mesh_vcap, g.mesh_idx, c->dimx, c->dimy, c->dimz, a.type, g.mesh_cnt + MC_FLAG);
-    GHIP(c, hipGetLastError());
+    HIPCHK(c, hipGetLastError());
     GTRY(mesh_fill(c, a.type, true, name));
     gev_begin(c);
     const bool vec = a.vec4(c->dimz);
     auto kern = vec ? k_geom_mesh_nodes<R, 4> : k_geom_mesh_nodes<R, 1>;
-    hipLaunchKernelGGL(kern, dim3(geom_grid(vec ? c->ncell / 4 : c->ncell, 1 << 30)), dim3(256), 0, c->stream, a.type, c->ncell, (R)(float)in.baseT,
+    hipLaunchKernelGGL(kern, dim3(grid_for(vec ? c->ncell / 4 : c->ncell, 1 << 30)), dim3(256), 0, c->stream, a.type, c->ncell, (R)(float)in.baseT,
                        a.bc_vel, a.bc_temp, (R *)a.v[0], (R *)a.v[1], (R *)a.v[2], (R *)a.v[3]);
-    GHIP(c, hipGetLastError());
+    HIPCHK(c, hipGetLastError());
     return FS3D_OK;
 }
 
@@ -1074,9 +1045,9 @@ static bool geom_is_slab(const fs3d_ctx *c) { return c->dimx != c->dimx_global |
 static fs3d_status geom_refuse(fs3d_ctx *c, const char *name, bool any_null, const char *what)
 {
     if (!c) return FS3D_ERR_INVALID;
-    if (any_null) return gfail(c, FS3D_ERR_INVALID, std::string(name) + ": NULL array");
+    if (any_null) return fail(c, FS3D_ERR_INVALID, std::string(name) + ": NULL array");
     if (geom_is_slab(c))
-        return gfail(c, FS3D_ERR_UNSUPPORTED, std::string(name) + ": " + what + " implemented for a single context only, "
+        return fail(c, FS3D_ERR_UNSUPPORTED, std::string(name) + ": " + what + " implemented for a single context only, "
                      "not for an x-slab of a larger grid or a member of a multi-GPU group");
     return FS3D_OK;
 }
@@ -1091,7 +1062,7 @@ static fs3d_status update_refuse(fs3d_ctx *c, const char *name, bool any_null)
 {
     GTRY(geom_refuse(c, name, any_null, "moving geometry is"));
     if (!c->uploaded_once)
-        return gfail(c, FS3D_ERR_INVALID, std::string(name) + ": the first geometry comes through fs3d_upload_nodes; upload nodes first");
+        return fail(c, FS3D_ERR_INVALID, std::string(name) + ": the first geometry comes through fs3d_upload_nodes; upload nodes first");
     return FS3D_OK;
 }
 
@@ -1127,15 +1098,15 @@ extern "C" fs3d_status fs3d_update_nodes(fs3d_ctx *c, const uint8_t *type, const
 {
     GTRY(update_refuse(c, "fs3d_update_nodes", !type || !bc_vel || !bc_temp || !vx || !vy || !vz || !T));
     const geom_clock t0 = std::chrono::steady_clock::now();
-    GHIP(c, hipSetDevice(c->device));
+    HIPCHK(c, hipSetDevice(c->device));
     GTRY(update_begin(c, true));
     const NodeArrays own = geom_own_arrays(c);
-    GHIP(c, hipMemcpyAsync(own.type, type, (size_t)c->ncell, hipMemcpyHostToDevice, c->stream));
-    GHIP(c, hipMemcpyAsync(own.bc_vel, bc_vel, (size_t)c->ncell, hipMemcpyHostToDevice, c->stream));
-    GHIP(c, hipMemcpyAsync(own.bc_temp, bc_temp, (size_t)c->ncell, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(own.type, type, (size_t)c->ncell, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(own.bc_vel, bc_vel, (size_t)c->ncell, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(own.bc_temp, bc_temp, (size_t)c->ncell, hipMemcpyHostToDevice, c->stream));
     // the four node-value fields are one of the tables: copied straight into place
     const void *val[4] = {vx, vy, vz, T};
-    for (int v = 0; v < 4; v++) GHIP(c, hipMemcpyAsync(own.v[v], val[v], (size_t)c->ncell * c->esize, hipMemcpyHostToDevice, c->stream));
+    for (int v = 0; v < 4; v++) HIPCHK(c, hipMemcpyAsync(own.v[v], val[v], (size_t)c->ncell * c->esize, hipMemcpyHostToDevice, c->stream));
     return update_end(c, t0, FS3D_OK, own.type, own.bc_vel, own.bc_temp, n_seg_out);
 }
 
@@ -1144,12 +1115,12 @@ extern "C" fs3d_status fs3d_update_nodes_dev(fs3d_ctx *c, const uint8_t *type, c
 {
     GTRY(update_refuse(c, "fs3d_update_nodes_dev", !type || !bc_vel || !bc_temp || !vx || !vy || !vz || !T));
     const geom_clock t0 = std::chrono::steady_clock::now();
-    GHIP(c, hipSetDevice(c->device));
+    HIPCHK(c, hipSetDevice(c->device));
     GTRY(update_begin(c, false));                         // the byte arrays are read where they are
     const void *val[4] = {vx, vy, vz, T};
     for (int v = 0; v < 4; v++) {
         void *dst = (char *)c->node + (size_t)v * c->nstride * c->esize;
-        if (dst != val[v]) GHIP(c, hipMemcpyAsync(dst, val[v], (size_t)c->ncell * c->esize, hipMemcpyDeviceToDevice, c->stream));
+        if (dst != val[v]) HIPCHK(c, hipMemcpyAsync(dst, val[v], (size_t)c->ncell * c->esize, hipMemcpyDeviceToDevice, c->stream));
     }
     return update_end(c, t0, FS3D_OK, type, bc_vel, bc_temp, n_seg_out);
 }
@@ -1160,7 +1131,7 @@ extern "C" fs3d_status fs3d_update_nodes_shape2d(fs3d_ctx *c, const uint8_t *cel
     const char *name = "fs3d_update_nodes_shape2d";
     GTRY(update_refuse(c, name, !cell2d || !velx2d || !vely2d || !T2d));
     const geom_clock t0 = std::chrono::steady_clock::now();
-    GHIP(c, hipSetDevice(c->device));
+    HIPCHK(c, hipSetDevice(c->device));
     ExtrudeIn in = {cell2d, velx2d, vely2d, T2d, dz, depth, depth_var, baseT, 0};
     GTRY(extrude_check(c, in, name));
     GTRY(update_begin(c, true));
@@ -1179,7 +1150,7 @@ extern "C" fs3d_status fs3d_extrude_shape2d_dev(fs3d_ctx *c, const uint8_t *cell
     ExtrudeIn in = {cell2d, velx2d, vely2d, T2d, dz, depth, depth_var, baseT, 0};
     GTRY(extrude_check(c, in, name));
     GTRY(c->prec == FS3D_F32 ? extrude_launch<float>(c, in, out) : extrude_launch<double>(c, in, out));
-    GHIP(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     return FS3D_OK;
 }
 
@@ -1189,7 +1160,7 @@ extern "C" fs3d_status fs3d_update_nodes_shape3d(fs3d_ctx *c, const float *x, co
     const char *name = "fs3d_update_nodes_shape3d";
     GTRY(update_refuse(c, name, !x || !y || !z || !tri));
     const geom_clock t0 = std::chrono::steady_clock::now();
-    GHIP(c, hipSetDevice(c->device));
+    HIPCHK(c, hipSetDevice(c->device));
     const MeshIn in = {x, y, z, nvert, tri, ntri, baseT};
     bool new_idx = false;
     GTRY(mesh_check(c, in, name, &new_idx));
@@ -1214,7 +1185,7 @@ extern "C" fs3d_status fs3d_voxelize_shape3d_dev(fs3d_ctx *c, const float *x, co
     const hipError_t e = hipStreamSynchronize(c->stream);
     gev_reset(c);
     if (st) return st;
-    GHIP(c, e);
+    HIPCHK(c, e);
     return FS3D_OK;
 }
 
@@ -1246,27 +1217,27 @@ extern "C" fs3d_status fs3d_last_update_device_ms(fs3d_ctx *c, float *ms_out)
 extern "C" fs3d_status fs3d_clear_outer_cells(fs3d_ctx *c, int layer, double baseT)
 {
     if (!c) return FS3D_ERR_INVALID;
-    if (layer < 0 || layer > 3) return gfail(c, FS3D_ERR_INVALID, "fs3d_clear_outer_cells: bad layer id");
-    if (!c->have_nodes) return gfail(c, FS3D_ERR_INVALID, "fs3d_clear_outer_cells: upload nodes first");
-    GHIP(c, hipSetDevice(c->device));
+    if (layer < 0 || layer > 3) return fail(c, FS3D_ERR_INVALID, "fs3d_clear_outer_cells: bad layer id");
+    if (!c->have_nodes) return fail(c, FS3D_ERR_INVALID, "fs3d_clear_outer_cells: upload nodes first");
+    HIPCHK(c, hipSetDevice(c->device));
     char *f[4];
     for (int v = 0; v < 4; v++) f[v] = (char *)c->lay[c->slot[layer]] + ((size_t)v * c->fstride + c->plane) * c->esize;
     if (c->prec == FS3D_F32)
-        hipLaunchKernelGGL((k_clear_outer<float>), dim3(geom_grid(c->ncell)), dim3(256), 0, c->stream, c->code, c->ncell, (float)baseT,
+        hipLaunchKernelGGL((k_clear_outer<float>), dim3(grid_for(c->ncell)), dim3(256), 0, c->stream, c->code, c->ncell, (float)baseT,
                            (float *)f[0], (float *)f[1], (float *)f[2], (float *)f[3]);
     else
-        hipLaunchKernelGGL((k_clear_outer<double>), dim3(geom_grid(c->ncell)), dim3(256), 0, c->stream, c->code, c->ncell, baseT,
+        hipLaunchKernelGGL((k_clear_outer<double>), dim3(grid_for(c->ncell)), dim3(256), 0, c->stream, c->code, c->ncell, baseT,
                            (double *)f[0], (double *)f[1], (double *)f[2], (double *)f[3]);
-    GHIP(c, hipGetLastError());
-    GHIP(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     return FS3D_OK;
 }
 
 extern "C" fs3d_status fs3d_geometry_info(fs3d_ctx *c, long long info[FS3D_N_GEOM_INFO])
 {
     if (!c || !info) return FS3D_ERR_INVALID;
-    if (!c->have_nodes) return gfail(c, FS3D_ERR_INVALID, "fs3d_geometry_info: upload nodes first");
-    GHIP(c, hipSetDevice(c->device));
+    if (!c->have_nodes) return fail(c, FS3D_ERR_INVALID, "fs3d_geometry_info: upload nodes first");
+    HIPCHK(c, hipSetDevice(c->device));
     for (int k = 0; k < FS3D_N_GEOM_INFO; k++) info[k] = 0;
     for (int d = 0; d < 3; d++) info[d] = c->nseg[d];
     info[3] = c->n_bnd;
@@ -1274,25 +1245,25 @@ extern "C" fs3d_status fs3d_geometry_info(fs3d_ctx *c, long long info[FS3D_N_GEO
     std::vector<uint8_t> hb;
     for (int d = 0; d < 3; d++) {
         hb.resize((size_t)geom_lines(c, d).nlines);
-        GHIP(c, hipMemcpyAsync(hb.data(), c->dead[d], hb.size(), hipMemcpyDeviceToHost, c->stream));
-        GHIP(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, hipMemcpyAsync(hb.data(), c->dead[d], hb.size(), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
         for (uint8_t b : hb) info[5 + d] += b != 0;
     }
     for (int d = 0; d < 2; d++) {
         if (!c->uflag[d]) continue;
         std::vector<unsigned> fl((size_t)geom_lines(c, d).n_o * geom_ng(c));
-        GHIP(c, hipMemcpyAsync(fl.data(), c->uflag[d], fl.size() * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
-        GHIP(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, hipMemcpyAsync(fl.data(), c->uflag[d], fl.size() * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
         for (unsigned f : fl) info[8 + d] += f & 1;
         info[10 + d] = c->n_ucol[d];
     }
     // the digest comes from the table the sweeps read; its device word is borrowed from the EvalDivError partials (rewritten by every evaluation)
     unsigned long long *dw = (unsigned long long *)c->red_buf, hw = 0;
-    GHIP(c, hipMemsetAsync(dw, 0, sizeof(unsigned long long), c->stream));
-    hipLaunchKernelGGL(k_geom_digest, dim3(geom_grid(c->ncell, 1024)), dim3(256), 0, c->stream, c->code, c->ncell, dw);
-    GHIP(c, hipGetLastError());
-    GHIP(c, hipMemcpyAsync(&hw, dw, sizeof hw, hipMemcpyDeviceToHost, c->stream));
-    GHIP(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemsetAsync(dw, 0, sizeof(unsigned long long), c->stream));
+    hipLaunchKernelGGL(k_geom_digest, dim3(grid_for(c->ncell, 1024)), dim3(256), 0, c->stream, c->code, c->ncell, dw);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(&hw, dw, sizeof hw, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     info[12] = (long long)hw;
     info[13] = c->geom_allocs;
     return FS3D_OK;

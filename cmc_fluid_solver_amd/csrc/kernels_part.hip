@@ -41,16 +41,7 @@
 #include <type_traits>
 #include <utility>
 #include "fs3d_common.h"
-
-template <typename F, int... I>
-__device__ __forceinline__ void pstatic_for_impl(F &&f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
-template <int N, typename F>
-__device__ __forceinline__ void pstatic_for(F &&f) { pstatic_for_impl(f, std::make_integer_sequence<int, N>{}); }
-
-typedef __amdgpu_buffer_rsrc_t prsrc_t;
-typedef unsigned pu32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned pu32x4 __attribute__((ext_vector_type(4)));
-#define PART_OOB 0xFFFFFFFFu      // voffset >= num_records: the hardware drops the store / returns 0 for the load
+#include "fs3d_device.h"
 
 // Cache policy of the streams (the `aux` operand of the raw buffer intrinsics on gfx94x/gfx950: 1 = sc0, 2 = nt, 16 = sc1).
 // `cur` is read exactly once per sweep, `next` / `temp_out` are written once and read again only by the NEXT launch, a gigabyte
@@ -59,25 +50,10 @@ typedef unsigned pu32x4 __attribute__((ext_vector_type(4)));
 // Measured (profiles/r3_ab_nt.txt, one box, interleaved, per launch with all stores): X 0.300 -> 0.279, Y 0.272 -> 0.248,
 // Z 0.242 -> 0.219 ms; tools/ubench/stream2.hip: nt loads read at 7.0 instead of 6.0-6.2 TB/s.
 constexpr int PART_AUX_NT = 2;
-template <typename R> struct PBuf;
-template <> struct PBuf<float> {
-    template <int AUX = 0> static __device__ __forceinline__ float ld(prsrc_t r, unsigned vo, unsigned so) { return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, vo, so, AUX)); }
-    template <int AUX = 0> static __device__ __forceinline__ void st(prsrc_t r, unsigned vo, unsigned so, float v) { __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, vo, so, AUX); }
-};
-template <> struct PBuf<double> {
-    template <int AUX = 0> static __device__ __forceinline__ double ld(prsrc_t r, unsigned vo, unsigned so) { return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(r, vo, so, AUX)); }
-    template <int AUX = 0> static __device__ __forceinline__ void st(prsrc_t r, unsigned vo, unsigned so, double v) { __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(pu32x2, v), r, vo, so, AUX); }
-};
 
-// reciprocal: v_rcp_f32 (1 ulp) + one Newton step
-__device__ __forceinline__ float prcp(float y)
-{
-    const float r = __builtin_amdgcn_rcpf(y);
-    return __builtin_fmaf(__builtin_fmaf(-y, r, 1.0f), r, r);
-}
-// v_rcp_f64 + two Newton steps.  No scaling of the operand: the divisors of the elimination are diagonal entries
+// reciprocal in fp64 (fp32: recip_refined of fs3d_device.h): v_rcp_f64 + two Newton steps.  No scaling of the operand: the divisors of the elimination are diagonal entries
 // (3/dt + 2 vis, 1, 2 and what the recurrence makes of them) and 1 - (products below 1) of the cyclic reduction
-__device__ __forceinline__ double prcp(double y)
+__device__ __forceinline__ double recip_refined(double y)
 {
     double r = __builtin_amdgcn_rcp(y);
     r = __builtin_fma(__builtin_fma(-y, r, 1.0), r, r);
@@ -136,7 +112,7 @@ template <typename R, int NR>
 __device__ __forceinline__ void part_step(R lead, R diag, R trail, R &cp, R &sp, R (&dp)[NR], const R (&d)[NR])
 {
     const R den = pfma(-lead, cp, diag);
-    const R r = prcp(den);
+    const R r = recip_refined(den);
 #pragma unroll
     for (int k = 0; k < NR; k++) dp[k] = pquot(pfma(-lead, dp[k], d[k]), den, r);
     sp = pquot(-lead * sp, den, r);
@@ -259,12 +235,12 @@ __global__ void __launch_bounds__(LT * NCH, sizeof(R) == 8 ? 2 : 4) k_sweep_part
     const unsigned so0 = so0_p;
     const unsigned son = (unsigned)(((long long)o * os) * (long long)sizeof(R));              // node values / codes: no halo plane
     const unsigned lbytes = 4u * fsb;
-    const prsrc_t Lcur = __builtin_amdgcn_make_buffer_rsrc((void *)(p.cur_ - p.plane), 0, (int)lbytes, 0x00020000);
-    const prsrc_t Ltmp = __builtin_amdgcn_make_buffer_rsrc((void *)(p.temp_ - p.plane), 0, (int)lbytes, 0x00020000);
-    const prsrc_t Lnext = __builtin_amdgcn_make_buffer_rsrc((void *)(p.next_ - p.plane), 0, (int)lbytes, 0x00020000);
-    const prsrc_t Ltout = __builtin_amdgcn_make_buffer_rsrc((void *)(p.temp_out_ - p.plane), 0, (int)lbytes, 0x00020000);
-    const prsrc_t rNode = __builtin_amdgcn_make_buffer_rsrc((void *)p.node_, 0, (int)(4u * nsb), 0x00020000);
-    const prsrc_t rCode = __builtin_amdgcn_make_buffer_rsrc((void *)p.code, 0, (int)(nsb / (sizeof(R) / 2)), 0x00020000);
+    const rsrc_t Lcur = __builtin_amdgcn_make_buffer_rsrc((void *)(p.cur_ - p.plane), 0, (int)lbytes, 0x00020000);
+    const rsrc_t Ltmp = __builtin_amdgcn_make_buffer_rsrc((void *)(p.temp_ - p.plane), 0, (int)lbytes, 0x00020000);
+    const rsrc_t Lnext = __builtin_amdgcn_make_buffer_rsrc((void *)(p.next_ - p.plane), 0, (int)lbytes, 0x00020000);
+    const rsrc_t Ltout = __builtin_amdgcn_make_buffer_rsrc((void *)(p.temp_out_ - p.plane), 0, (int)lbytes, 0x00020000);
+    const rsrc_t rNode = __builtin_amdgcn_make_buffer_rsrc((void *)p.node_, 0, (int)(4u * nsb), 0x00020000);
+    const rsrc_t rCode = __builtin_amdgcn_make_buffer_rsrc((void *)p.code, 0, (int)(nsb / (sizeof(R) / 2)), 0x00020000);
 
     constexpr int M1 = DIR == 0 ? 1 : 0;                 // axis of the `o` neighbours
     constexpr int M2 = 2;                                // lane axis
@@ -288,10 +264,10 @@ __global__ void __launch_bounds__(LT * NCH, sizeof(R) == 8 ? 2 : 4) k_sweep_part
             ucol_id = f >> 2;
         }
         if (tile_uni) {
-            const pu32x4 *const col = (const pu32x4 *)(p.ucol + (long long)ucol_id * UCOL_PITCH + s0);
+            const u32x4 *const col = (const u32x4 *)(p.ucol + (long long)ucol_id * UCOL_PITCH + s0);
 #pragma unroll
             for (int q4 = 0; q4 < M / 8; q4++) {
-                const pu32x4 w = col[q4];
+                const u32x4 w = col[q4];
                 cwv[8 * q4 + 0] = (int)(w.x & 0xFFFFu); cwv[8 * q4 + 1] = (int)(w.x >> 16); cwv[8 * q4 + 2] = (int)(w.y & 0xFFFFu); cwv[8 * q4 + 3] = (int)(w.y >> 16);
                 cwv[8 * q4 + 4] = (int)(w.z & 0xFFFFu); cwv[8 * q4 + 5] = (int)(w.z >> 16); cwv[8 * q4 + 6] = (int)(w.w & 0xFFFFu); cwv[8 * q4 + 7] = (int)(w.w >> 16);
             }
@@ -308,23 +284,23 @@ __global__ void __launch_bounds__(LT * NCH, sizeof(R) == 8 ? 2 : 4) k_sweep_part
     // running scalar offsets, opaque from cell to cell: otherwise the offsets of all M cells are computed up front and
     // held in (spilled) SGPRs
     unsigned s_is = so0, s_nd = son;
-    const unsigned vo_edge = kk == 0 ? vo - (unsigned)sizeof(R) : (kk == LT - 1 ? vo + (unsigned)sizeof(R) : PART_OOB);
+    const unsigned vo_edge = kk == 0 ? vo - (unsigned)sizeof(R) : (kk == LT - 1 ? vo + (unsigned)sizeof(R) : BUF_OOB);
     auto issue = [&](CellLd &L) __attribute__((always_inline)) {
         const unsigned sc = s_is;
         s_is = opq_s(s_is + ssb);
 #pragma unroll
-        for (int f = 0; f < 4; f++) L.tp[f] = PBuf<R>::ld(Ltmp, vo, sc + ssb + (unsigned)f * fsb);
+        for (int f = 0; f < 4; f++) L.tp[f] = Buf<R>::ld(Ltmp, vo, sc + ssb + (unsigned)f * fsb);
 #pragma unroll
-        for (int f = 0; f < 4; f++) L.c[f] = PBuf<R>::template ld<PART_AUX_NT>(Lcur, vo, sc + (unsigned)f * fsb);
+        for (int f = 0; f < 4; f++) L.c[f] = Buf<R>::template ld<PART_AUX_NT>(Lcur, vo, sc + (unsigned)f * fsb);
         const unsigned sv = sc + (unsigned)DIR * fsb;
-        L.om = PBuf<R>::ld(Ltmp, vo, sv - osb); L.op = PBuf<R>::ld(Ltmp, vo, sv + osb);
+        L.om = Buf<R>::ld(Ltmp, vo, sv - osb); L.op = Buf<R>::ld(Ltmp, vo, sv + osb);
         // lane-axis neighbours: the lanes next door hold them (DPP shifts below); only the tile's first and last lane
         // fetch theirs from outside the tile -- every other lane of this load is out of range (no memory access)
-        L.le = PBuf<R>::ld(Ltmp, vo_edge, sv);
+        L.le = Buf<R>::ld(Ltmp, vo_edge, sv);
     };
     R Tm[4], Tc[4];
 #pragma unroll
-    for (int f = 0; f < 4; f++) { Tm[f] = PBuf<R>::ld(Ltmp, vo, so0 - ssb + (unsigned)f * fsb); Tc[f] = PBuf<R>::ld(Ltmp, vo, so0 + (unsigned)f * fsb); }
+    for (int f = 0; f < 4; f++) { Tm[f] = Buf<R>::ld(Ltmp, vo, so0 - ssb + (unsigned)f * fsb); Tc[f] = Buf<R>::ld(Ltmp, vo, so0 + (unsigned)f * fsb); }
     CellLd L[PF + 1];
 #pragma unroll
     for (int i = 0; i < PF && i < M; i++) issue(L[i]);
@@ -378,7 +354,7 @@ __global__ void __launch_bounds__(LT * NCH, sizeof(R) == 8 ? 2 : 4) k_sweep_part
     // ---- P: rows -------------------------------------------------------------------------------------------
     R q[M], dU[M], dV[M], dW[M];
     {
-        pstatic_for<M>([&](auto ic) __attribute__((always_inline)) {
+        static_for<M>([&](auto ic) __attribute__((always_inline)) {
             constexpr int i = decltype(ic)::value;
             if (i + PF < M) issue(L[(i + PF) % (PF + 1)]);
             __builtin_amdgcn_sched_barrier(0);
@@ -409,7 +385,7 @@ __global__ void __launch_bounds__(LT * NCH, sizeof(R) == 8 ? 2 : 4) k_sweep_part
                 const bool ns_v = kind != ROW_SKIP && !(code4 & ROW_VELFREE), ns_t = kind != ROW_SKIP && !(code4 & ROW_TEMPFREE);
                 R nv[4];
 #pragma unroll
-                for (int f = 0; f < 4; f++) nv[f] = PBuf<R>::ld(rNode, vo, s_nd + (unsigned)f * nsb);
+                for (int f = 0; f < 4; f++) nv[f] = Buf<R>::ld(rNode, vo, s_nd + (unsigned)f * nsb);
                 qq = is_int ? qq : R(0);
 #pragma unroll
                 for (int f = 0; f < 3; f++) dd[f] = is_int ? dd[f] : (ns_v ? nv[f] : R(0));
@@ -444,7 +420,7 @@ __global__ void __launch_bounds__(LT * NCH, sizeof(R) == 8 ? 2 : 4) k_sweep_part
         R apv = R(0), upv = R(-1), apt = R(0), upt = R(-1), ep3[3] = {R(0), R(0), R(0)}, ep1[1] = {R(0)};   // up:   x[0]   = ep - ap X_{p-1} - up X_p
         // the T right-hand sides stay in the LDS during this phase (register budget); read one step ahead of their use
         R tdn = myD[0], tup = myD[(M - 2) * LT];
-        pstatic_for<M - 1>([&](auto ic) __attribute__((always_inline)) {
+        static_for<M - 1>([&](auto ic) __attribute__((always_inline)) {
             constexpr int i = decltype(ic)::value, j = M - 2 - i;
             const R tdi = tdn, tdj = tup;
             if (i + 1 < M - 1) { tdn = myD[(i + 1) * LT]; tup = myD[(j - 1 < 0 ? 0 : j - 1) * LT]; }
@@ -491,7 +467,7 @@ __global__ void __launch_bounds__(LT * NCH, sizeof(R) == 8 ? 2 : 4) k_sweep_part
             for (int c = 0; c < cA; c++) {
                 R lo, di, up, rhs;
                 row(c, lo, di, up, rhs);
-                const R den = pfma(-lo, cq, di), r = prcp(den);
+                const R den = pfma(-lo, cq, di), r = recip_refined(den);
                 cq = pquot(up, den, r); dq = pquot(pfma(-lo, dq, rhs), den, r); lq = pquot(-lo * lq, den, r);
             }
             R eq = R(0), aq = R(0), uq = R(-1);
@@ -499,7 +475,7 @@ __global__ void __launch_bounds__(LT * NCH, sizeof(R) == 8 ? 2 : 4) k_sweep_part
             for (int c = cA - 1; c >= 0; c--) {
                 R lo, di, up, rhs;
                 row(c, lo, di, up, rhs);
-                const R den = pfma(-up, aq, di), r = prcp(den);
+                const R den = pfma(-up, aq, di), r = recip_refined(den);
                 eq = pquot(pfma(-up, eq, rhs), den, r); uq = pquot(-up * uq, den, r); aq = pquot(lo, den, r);
             }
             const R lo = em[0 * ES + cA * LT], bp = em[1 * ES + cA * LT], cl = em[2 * ES + cA * LT];
@@ -542,7 +518,7 @@ __global__ void __launch_bounds__(LT * NCH, sizeof(R) == 8 ? 2 : 4) k_sweep_part
             if (c + 1 < NCH) { vf = em[3 * ES + (c + 1) * LT]; wf = em[4 * ES + (c + 1) * LT]; gf = er[4 * ES + (c + 1) * LT]; }
             else gf = xr_last;
             const R di = pfma(-cl, vf, bp), up = -cl * wf, rhs = pfma(-cl, gf, er[c * LT]);
-            const R den = pfma(-lo, cp, di), r = prcp(den);
+            const R den = pfma(-lo, cp, di), r = recip_refined(den);
             cp = pquot(up, den, r); dp = pquot(pfma(-lo, dp, rhs), den, r);
         };
         if (RL) {
@@ -583,7 +559,7 @@ __global__ void __launch_bounds__(LT * NCH, sizeof(R) == 8 ? 2 : 4) k_sweep_part
         }
         R cpv = R(0), cpt = R(0), sp = R(0);
         R tdn = myD[0];
-        pstatic_for<M - 1>([&](auto ic) __attribute__((always_inline)) {
+        static_for<M - 1>([&](auto ic) __attribute__((always_inline)) {
             constexpr int i = decltype(ic)::value;
             const R tdi = tdn;
             if (i + 1 < M - 1) tdn = myD[(i + 1) * LT];
@@ -604,7 +580,7 @@ __global__ void __launch_bounds__(LT * NCH, sizeof(R) == 8 ? 2 : 4) k_sweep_part
     PSTAMP(6);
     // ---- O: scatter + merge -------------------------------------------------------------------------------------
     {
-        const unsigned vo_st = lane_valid ? vo : PART_OOB;
+        const unsigned vo_st = lane_valid ? vo : BUF_OOB;
         const unsigned so0 = opq_s(so0_p), ssb = opq_s(ssb_p), fsb = opq_s(fsb_p);   // not the P phase's address arithmetic kept alive
         R tv[OPF + 1][4];
         unsigned s_is = so0, s_o = so0;                 // running scalar offsets (issue side / store side), opaque per cell
@@ -612,14 +588,14 @@ __global__ void __launch_bounds__(LT * NCH, sizeof(R) == 8 ? 2 : 4) k_sweep_part
         const int nloc = opq_v(n - s0);                 // cells of this chunk inside the line
         auto issue = [&](R (&v)[4]) __attribute__((always_inline)) {
 #pragma unroll
-            for (int f = 0; f < 4; f++) v[f] = PBuf<R>::ld(Ltmp, vo, s_is + (unsigned)f * fsb);
+            for (int f = 0; f < 4; f++) v[f] = Buf<R>::ld(Ltmp, vo, s_is + (unsigned)f * fsb);
             s_is = opq_s(s_is + ssb);
         };
         if (p.merge) {
 #pragma unroll
             for (int i = 0; i < OPF && i < M; i++) issue(tv[i]);
         }
-        pstatic_for<M>([&](auto ic) __attribute__((always_inline)) {
+        static_for<M>([&](auto ic) __attribute__((always_inline)) {
             constexpr int i = decltype(ic)::value;
             const unsigned sc = s_o;
             s_o = opq_s(s_o + ssb);
@@ -630,9 +606,9 @@ __global__ void __launch_bounds__(LT * NCH, sizeof(R) == 8 ? 2 : 4) k_sweep_part
             const bool seg = !dead && (uni || ((segm >> i) & 1u)), isin = !dead && (uni || ((inm >> i) & 1u));
             const bool in_line = i < nloc;
             if (p.store_next) {
-                const unsigned v_ = seg ? vo_st : PART_OOB;            // UpdateSegment: every cell of a segment, nothing else
+                const unsigned v_ = seg ? vo_st : BUF_OOB;            // UpdateSegment: every cell of a segment, nothing else
 #pragma unroll
-                for (int f = 0; f < 4; f++) PBuf<R>::template st<PART_AUX_NT>(Lnext, v_, sc + (unsigned)f * fsb, xv[f]);
+                for (int f = 0; f < 4; f++) Buf<R>::template st<PART_AUX_NT>(Lnext, v_, sc + (unsigned)f * fsb, xv[f]);
             }
             if (p.merge) {
                 const R (&tq)[4] = tv[i % (OPF + 1)];
@@ -640,14 +616,14 @@ __global__ void __launch_bounds__(LT * NCH, sizeof(R) == 8 ? 2 : 4) k_sweep_part
                     // NODE_IN cell outside every segment (run without a closing cell, Grid3D.cpp:87-117): the reference
                     // merges the stale `next` value
 #pragma unroll
-                    for (int f = 0; f < 4; f++) { const R sv = PBuf<R>::ld(Lnext, vo, sc + (unsigned)f * fsb); xv[f] = (isin && !seg) ? sv : xv[f]; }
+                    for (int f = 0; f < 4; f++) { const R sv = Buf<R>::ld(Lnext, vo, sc + (unsigned)f * fsb); xv[f] = (isin && !seg) ? sv : xv[f]; }
                 }
-                const unsigned v_ = in_line ? vo_st : PART_OOB;
+                const unsigned v_ = in_line ? vo_st : BUF_OOB;
 #pragma unroll
                 for (int f = 0; f < 4; f++) {
                     R mv = (tq[f] + xv[f]) * R(0.5);                                   // MergeFieldTo (TimeLayer3D.h:415-436)
                     if (p.merge == 2) mv = (mv + xv[f]) * R(0.5);
-                    PBuf<R>::template st<PART_AUX_NT>(Ltout, v_, sc + (unsigned)f * fsb, isin ? mv : tq[f]);
+                    Buf<R>::template st<PART_AUX_NT>(Ltout, v_, sc + (unsigned)f * fsb, isin ? mv : tq[f]);
                 }
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -750,18 +726,18 @@ static Launch part_dispatch_xy(fs3d_ctx *c, const SweepParams<R> &p)
 // the merge are still in registers.
 template <typename R> struct PV { R v[16 / sizeof(R)]; };
 template <typename R, int AUX = 0>
-__device__ __forceinline__ PV<R> pld(prsrc_t r, unsigned vo, unsigned so)
+__device__ __forceinline__ PV<R> pld(rsrc_t r, unsigned vo, unsigned so)
 {
-    const pu32x4 q = __builtin_amdgcn_raw_buffer_load_b128(r, vo, so, AUX);
+    const u32x4 q = __builtin_amdgcn_raw_buffer_load_b128(r, vo, so, AUX);
     PV<R> o;
     __builtin_memcpy(o.v, &q, 16);
     return o;
 }
 template <int AUX = 0, typename R, int C>
-__device__ __forceinline__ void pst(prsrc_t r, unsigned vo, unsigned so, const R (&v)[C])
+__device__ __forceinline__ void pst(rsrc_t r, unsigned vo, unsigned so, const R (&v)[C])
 {
     static_assert(sizeof(R) * C == 16, "one 16-byte piece");
-    pu32x4 q;
+    u32x4 q;
     __builtin_memcpy(&q, v, 16);
     __builtin_amdgcn_raw_buffer_store_b128(q, r, vo, so, AUX);
     // A 16-byte store reads its data registers a few cycles after it issues.  hipcc pads a following VALU write of
@@ -812,12 +788,12 @@ __global__ void __launch_bounds__(256, 2) k_sweep_part_z(SweepParams<R> p, int n
     const unsigned fsb = (unsigned)(p.fstride * (long long)SZ), nsb = (unsigned)(p.nstride * (long long)SZ);
     const unsigned rowb = (unsigned)p.dimz * SZ, planeb = (unsigned)(p.plane * (long long)SZ);
     const unsigned lbytes = 4u * fsb;
-    const prsrc_t Lcur = __builtin_amdgcn_make_buffer_rsrc((void *)(p.cur_ - p.plane), 0, (int)lbytes, 0x00020000);
-    const prsrc_t Ltmp = __builtin_amdgcn_make_buffer_rsrc((void *)(p.temp_ - p.plane), 0, (int)lbytes, 0x00020000);
-    const prsrc_t Lnext = __builtin_amdgcn_make_buffer_rsrc((void *)(p.next_ - p.plane), 0, (int)lbytes, 0x00020000);
-    const prsrc_t Ltout = __builtin_amdgcn_make_buffer_rsrc((void *)(p.temp_out_ - p.plane), 0, (int)lbytes, 0x00020000);
-    const prsrc_t rNode = __builtin_amdgcn_make_buffer_rsrc((void *)p.node_, 0, (int)(4u * nsb), 0x00020000);
-    const prsrc_t rCode = __builtin_amdgcn_make_buffer_rsrc((void *)p.code, 0, (int)(nsb / (SZ / 2u)), 0x00020000);   // 2 bytes per cell
+    const rsrc_t Lcur = __builtin_amdgcn_make_buffer_rsrc((void *)(p.cur_ - p.plane), 0, (int)lbytes, 0x00020000);
+    const rsrc_t Ltmp = __builtin_amdgcn_make_buffer_rsrc((void *)(p.temp_ - p.plane), 0, (int)lbytes, 0x00020000);
+    const rsrc_t Lnext = __builtin_amdgcn_make_buffer_rsrc((void *)(p.next_ - p.plane), 0, (int)lbytes, 0x00020000);
+    const rsrc_t Ltout = __builtin_amdgcn_make_buffer_rsrc((void *)(p.temp_out_ - p.plane), 0, (int)lbytes, 0x00020000);
+    const rsrc_t rNode = __builtin_amdgcn_make_buffer_rsrc((void *)p.node_, 0, (int)(4u * nsb), 0x00020000);
+    const rsrc_t rCode = __builtin_amdgcn_make_buffer_rsrc((void *)p.code, 0, (int)(nsb / (SZ / 2u)), 0x00020000);   // 2 bytes per cell
 
     const R h2s = p.two_ds[2], h2o = p.two_ds[0], h2l = p.two_ds[1], dtv = p.dt;
     const R ir2s = R(1) / h2s, ir2o = R(1) / h2o, ir2l = R(1) / h2l, irdt = R(1) / dtv;
@@ -832,11 +808,11 @@ __global__ void __launch_bounds__(256, 2) k_sweep_part_z(SweepParams<R> p, int n
     // round trip of their own
     const bool is_end = l_ok && (gl == 0 || gl == n / C - 1);
     const int ec = gl == 0 ? 0 : C - 1;
-    const unsigned vo_e = is_end ? vo_l + SZ * (unsigned)ec : PART_OOB;
+    const unsigned vo_e = is_end ? vo_l + SZ * (unsigned)ec : BUF_OOB;
     // NW == 2: the cell across the cut between the two waves (cell 64 C - 1 for the upper wave's first lane, 64 C for the
     // lower wave's last lane; n >= 64 C + 2: both exist) comes with the line's other loads
     const bool at_cut = NW == 2 && (hi ? l == 0 : l == 63);
-    const unsigned vo_nb = at_cut ? (hi ? (64u * C - 1u) * SZ : 64u * C * SZ) : PART_OOB;
+    const unsigned vo_nb = at_cut ? (hi ? (64u * C - 1u) * SZ : 64u * C * SZ) : BUF_OOB;
 
     auto issue = [&](int jrow, ZLine<R> &L) __attribute__((always_inline)) {
         // jrow: first line of the row (wave-uniform); this lane's line is jrow + sub.  A row that starts past the plane (tail of
@@ -853,13 +829,13 @@ __global__ void __launch_bounds__(256, 2) k_sweep_part_z(SweepParams<R> p, int n
         if (LI > 1) { L.wjm = pld<R>(Ltmp, vo_l, so + 2u * fsb - rowb); L.wjp = pld<R>(Ltmp, vo_l, so + 2u * fsb + rowb); }
         const unsigned son = opq_s(line_son(jr));
         // the piece's C code words: 2 C bytes
-        if constexpr (C == 4) { const pu32x2 cw = __builtin_amdgcn_raw_buffer_load_b64(rCode, vo_l / 2u, son / 2u, 0); L.code[0] = cw.x; L.code[1] = cw.y; }
+        if constexpr (C == 4) { const u32x2 cw = __builtin_amdgcn_raw_buffer_load_b64(rCode, vo_l / 2u, son / 2u, 0); L.code[0] = cw.x; L.code[1] = cw.y; }
         else L.code[0] = __builtin_amdgcn_raw_buffer_load_b32(rCode, vo_l / 4u, son / 4u, 0);
 #pragma unroll
-        for (int f = 0; f < 4; f++) L.nve[f] = PBuf<R>::ld(rNode, vo_e, son + (unsigned)f * nsb);     // other lanes: out of range, no memory access
+        for (int f = 0; f < 4; f++) L.nve[f] = Buf<R>::ld(rNode, vo_e, son + (unsigned)f * nsb);     // other lanes: out of range, no memory access
         if (NW == 2) {
 #pragma unroll
-            for (int f = 0; f < 4; f++) L.nb[f] = PBuf<R>::ld(Ltmp, vo_nb, so + (unsigned)f * fsb);
+            for (int f = 0; f < 4; f++) L.nb[f] = Buf<R>::ld(Ltmp, vo_nb, so + (unsigned)f * fsb);
         }
     };
 
@@ -973,7 +949,7 @@ __global__ void __launch_bounds__(256, 2) k_sweep_part_z(SweepParams<R> p, int n
             const R clv = last ? R(0) : mv[ci].c, clt = last ? R(0) : mt[ci].c;
             const R lov = -mv[ci].a * lpv[cb], div = pfma(-clv, nvf, pfma(-mv[ci].a, cpv[cb], mv[ci].b)), upv_ = -clv * nwf;
             const R lot = -mt[ci].a * lpt[cb], dit = pfma(-clt, ntf, pfma(-mt[ci].a, cpt[cb], mt[ci].b)), upt_ = -clt * nuf;
-            const R rv = prcp(div), rt = prcp(dit);
+            const R rv = recip_refined(div), rt = recip_refined(dit);
             av = pquot(lov, div, rv); cv_ = pquot(upv_, div, rv); at = pquot(lot, dit, rt); ct_ = pquot(upt_, dit, rt);
             dd[0] = pquot(pfma(-clv, ng0, pfma(-mv[ci].a, dpd[cb][0], d[0][ci])), div, rv);
             dd[1] = pquot(pfma(-clv, ng1, pfma(-mv[ci].a, dpd[cb][1], d[1][ci])), div, rv);
@@ -1025,7 +1001,7 @@ __global__ void __launch_bounds__(256, 2) k_sweep_part_z(SweepParams<R> p, int n
                 const R a_v = has_m ? av : R(0), c_v = has_p ? cv_ : R(0), a_t = has_m ? at : R(0), c_t = has_p ? ct_ : R(0);
                 const R dnv = pfma(-a_v, __shfl_up(cv_, s, LPL), pfma(-c_v, __shfl_down(av, s, LPL), R(1)));
                 const R dnt = pfma(-a_t, __shfl_up(ct_, s, LPL), pfma(-c_t, __shfl_down(at, s, LPL), R(1)));
-                const R rv = prcp(dnv), rt = prcp(dnt);
+                const R rv = recip_refined(dnv), rt = recip_refined(dnt);
                 R nd[4];
 #pragma unroll
                 for (int k = 0; k < 4; k++) {
@@ -1054,7 +1030,7 @@ __global__ void __launch_bounds__(256, 2) k_sweep_part_z(SweepParams<R> p, int n
                 if (at_cut) { R *const b = hi ? bh : bl; b[0] = dd[0]; b[1] = dd[1]; b[2] = dd[2]; b[3] = dd[3]; b[4] = ev; b[5] = et; }
                 __syncthreads();
                 const R elv = bl[4], elt = bl[5], ehv = bh[4], eht = bh[5];
-                const R rdv = prcp(pfma(-elv, ehv, R(1))), rdt = prcp(pfma(-elt, eht, R(1)));
+                const R rdv = recip_refined(pfma(-elv, ehv, R(1))), rdt = recip_refined(pfma(-elt, eht, R(1)));
 #pragma unroll
                 for (int k = 0; k < 4; k++) {
                     const R el = k < 3 ? elv : elt, eh = k < 3 ? ehv : eht, den = pfma(-el, eh, R(1));
@@ -1075,7 +1051,7 @@ __global__ void __launch_bounds__(256, 2) k_sweep_part_z(SweepParams<R> p, int n
             }
         }
         // ---- scatter + merge
-        const unsigned vo_st = st_ok ? vo_l : PART_OOB;
+        const unsigned vo_st = st_ok ? vo_l : BUF_OOB;
         bool all_seg = true, stale = false;
 #pragma unroll
         for (int c = 0; c < C; c++) { all_seg = all_seg && seg[c]; stale = stale || (isin[c] && !seg[c]); }
@@ -1088,7 +1064,7 @@ __global__ void __launch_bounds__(256, 2) k_sweep_part_z(SweepParams<R> p, int n
                 for (int f = 0; f < 4; f++)
 #pragma unroll
                     for (int c = 0; c < C; c++)
-                        PBuf<R>::st(Lnext, seg[c] ? vo_st : PART_OOB, so + (unsigned)f * fsb + SZ * (unsigned)c, x[f][c]);
+                        Buf<R>::st(Lnext, seg[c] ? vo_st : BUF_OOB, so + (unsigned)f * fsb + SZ * (unsigned)c, x[f][c]);
             }
         }
         if (p.merge) {

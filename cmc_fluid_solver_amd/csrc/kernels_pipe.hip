@@ -29,17 +29,9 @@
 #include <type_traits>
 #include <utility>
 #include "fs3d_rows.h"
+#include "fs3d_device.h"
 
 #define PIPE_NW 8             // waves per workgroup of a whole sweep; the halves of short slab pieces use fewer (NW)
-
-
-// Compile-time loop: f(integral_constant<int, 0>) ... f(integral_constant<int, N-1>).  The sub-pass loops of the
-// P and O phases are too large for `#pragma unroll` (the unroller gives up past its size threshold, the cell
-// indices of the register arrays turn dynamic and the arrays land in scratch memory): instantiate them instead.
-template <typename F, int... I>
-__device__ __forceinline__ void static_for_impl(F &&f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
-template <int N, typename F>
-__device__ __forceinline__ void static_for(F &&f) { static_for_impl(f, std::make_integer_sequence<int, N>{}); }
 
 // Point-to-point hand-off between the waves of a workgroup through an LDS flag (the relay phases): the
 // producer publishes its data, then the flag; the consumer polls the flag, then reads.  DS operations of a wave
@@ -83,12 +75,6 @@ __device__ __forceinline__ void flag_set(volatile int *f_)
 // failed -- wave-uniform and rare (values between 0 and 8e-31).  Divisors are checked against [2^-30, 2^60) on
 // the host (constants) or per cell (den); finite fields below 2^60 are assumed (the reference aborts far earlier).
 template <typename R> struct DivC { R y, r; };          // divisor and its refined reciprocal
-__device__ __forceinline__ float recip_refined(float y)
-{
-    float r = __builtin_amdgcn_rcpf(y);
-    const float e = __builtin_fmaf(-y, r, 1.0f);
-    return __builtin_fmaf(e, r, r);
-}
 __device__ __forceinline__ float div_core(float x, float y, float r)
 {
     float q = x * r;
@@ -138,26 +124,9 @@ __device__ __forceinline__ void chain_core(float c, float num, float den, float 
 template <bool GUARD_DEN>
 __device__ __forceinline__ void chain_core(double c, double num, double den, double &cp, double &dp, DivGuard &) { cp = c / den; dp = num / den; }
 
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
-
-// Raw buffer access: address = descriptor base (4 SGPRs) + soffset (1 SGPR, wave-uniform row) +
-// voffset (1 VGPR, per-lane byte offset).  One SGPR per row instead of a 64-bit pointer, no 64-bit
-// VALU address arithmetic, and a store is masked by an out-of-range voffset instead of a branch.
-// Cache policy (aux operand: 2 = nt): `cur` is read once per sweep, `next` / `temp_out` are written once and read by the next launch
+// Cache policy of the raw buffer accesses (Buf<R>, fs3d_device.h; aux operand: 2 = nt): `cur` is read once per sweep, `next` / `temp_out` are written once and read by the next launch
 // only (see kernels_part.hip); the temp loads stay cached (neighbour rows, second read of the O phase).  Hints only: same bits.
 constexpr int PIPE_AUX_NT = 2;
-template <typename R> struct Buf;
-template <> struct Buf<float> {
-    template <int AUX = 0> static __device__ __forceinline__ float ld(rsrc_t r, unsigned vo, unsigned so) { return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, vo, so, AUX)); }
-    template <int AUX = 0> static __device__ __forceinline__ void st(rsrc_t r, unsigned vo, unsigned so, float v) { __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, vo, so, AUX); }
-};
-template <> struct Buf<double> {
-    template <int AUX = 0> static __device__ __forceinline__ double ld(rsrc_t r, unsigned vo, unsigned so) { return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(r, vo, so, AUX)); }
-    template <int AUX = 0> static __device__ __forceinline__ void st(rsrc_t r, unsigned vo, unsigned so, double v) { __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, v), r, vo, so, AUX); }
-};
-#define BUF_OOB 0xFFFFFFFFu      // voffset >= num_records: the hardware drops the store
 
 // Geometry of one wave's chunk and the accessors for "one field of PC consecutive cells of the chunk".
 // P and O phases walk the chunk in sub-passes of PC cells so that their transient register arrays stay small.

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import refgolden as RG
+from geom_rules import rule_segments
 from cmc_fluid_solver_amd import build as B
 from cmc_fluid_solver_amd import capi, grids, shape2d
 
@@ -38,25 +39,6 @@ def test_header_declares_and_library_exports_the_moving_entries(built):
         assert name in capi.SYMBOLS and hasattr(lib, name), name
     assert re.search(r"#define\s+FS3D_N_GEOM_INFO\s+14\b", hdr)
     assert len(capi.Solver.GEOMETRY_INFO) == 14
-
-
-def rule_segments(type3, d):
-    """The local rule: with Lst = the last index of a line whose type is not NODE_IN, cell s is INTERIOR iff s >= 1, its type is
-    NODE_IN and s < Lst; START iff s + 1 is INTERIOR and s is not; END iff s is not INTERIOR and s - 1 is.  Returns the set of
-    (start cell, end cell) index triples: the starts and the ends of a line pair up in order."""
-    ty = np.moveaxis(type3, d, 2)
-    n = ty.shape[2]
-    notin = ty != grids.NODE_IN
-    s = np.arange(n)
-    lst = np.where(notin, s, -1).max(axis=2)
-    interior = (~notin) & (s >= 1) & (s < lst[..., None])
-    nxt = np.zeros_like(interior); nxt[..., :-1] = interior[..., 1:]
-    prv = np.zeros_like(interior); prv[..., 1:] = interior[..., :-1]
-    start, end = ~interior & nxt, ~interior & prv
-    a, b = np.argwhere(start), np.argwhere(end)          # both sorted by (line, s)
-    assert len(a) == len(b) and np.array_equal(a[:, :2], b[:, :2]) and (a[:, 2] < b[:, 2]).all()
-    inv = {0: (2, 0, 1), 1: (0, 2, 1), 2: (0, 1, 2)}[d]   # moved axes back to (i, j, k)
-    return {(tuple(int(p[q]) for q in inv), tuple(int(e[q]) for q in inv)) for p, e in zip(a, b)}
 
 
 def check_rule_against_oracle(nodes):
