@@ -666,6 +666,7 @@ static fs3d_status xsweep_multi(fs3d_ctx *c, SweepParams<R> &p)
     // per-slab halves: the pipe kernel (rows on chip, 64 lines per bundle) where the slab allows it, else thread-per-line
     const bool pipe = c->opt_kernel != FS3D_SWEEP_LINE && xslab_pipe_supported<R>(p);
     c->ran_kernel[0] = pipe ? FS3D_SWEEP_PIPE : FS3D_SWEEP_LINE; c->ran_segmented[0] = 1;
+    c->ran_xsolve = 1; c->ran_xa2a = 0;
     if (c->opt_kernel == FS3D_SWEEP_PIPE && !pipe) return fail(c, FS3D_ERR_UNSUPPORTED, "pipe kernel: slab dims unsupported for the X sweep");
     auto range = [&](int b, long long &l0, long long &l1) {
         const long long per = ((long long)pl / 64 + nb - 1) / nb * 64;      // whole waves / bundles per block

@@ -15,6 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 if os.path.dirname(HERE) not in sys.path:          # run as a script (the child processes below)
     sys.path.insert(0, os.path.dirname(HERE))
 
+import bc_cases  # noqa: E402
 import refgolden as RG  # noqa: E402
 from cmc_fluid_solver_amd import build as B  # noqa: E402
 from cmc_fluid_solver_amd import capi, grids, shape2d  # noqa: E402
@@ -25,6 +26,7 @@ INPUTS = os.path.join(HERE, "golden", "inputs")
 PARAMS = (200.0, 0.72, 1.4)
 DT = 0.1
 TABLE_KEYS = capi.Solver.GEOMETRY_INFO[:13]        # entry 13 describes the path taken, not the tables
+BC_PAIRS = {"bcAB": ("F-A", "F-B"), "bcplates": ("F-C", "P-FN")}
 
 
 def _oracle():
@@ -53,6 +55,8 @@ def pair(name):
         return grids.box(16, 14, 18), grids.box_with_obstacle(16, 14, 18)
     if name == "box64":
         return grids.box(64), grids.box_with_obstacle(64)
+    if name in BC_PAIRS:                               # every FREE / NOSLIP bit of START and END rows in every direction (tests/bc_cases.py)
+        return tuple(bc_cases.grid(n) for n in BC_PAIRS[name])
     times = RG.Fixture("heart_us", "f32").meta["grid_times"]
     a, b = {"heart03": (0, 3), "heart45": (4, 5)}[name]
     return heart(times[a]), heart(times[b])
@@ -117,7 +121,7 @@ MODES = {"f32-exact": (np.float32, capi.SWEEP_EXACT, 0), "f32-auto": (np.float32
 
 
 @pytest.mark.parametrize("mode", list(MODES))
-@pytest.mark.parametrize("name", ["box16", "box64", "heart03", "heart45"])
+@pytest.mark.parametrize("name", ["box16", "box64", "heart03", "heart45", "bcAB", "bcplates"])
 def test_update_equals_upload(built, name, mode):
     g1, g2 = pair(name)
     check_update_equals_upload(g1, g2, *MODES[mode])
