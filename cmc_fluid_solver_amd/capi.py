@@ -22,6 +22,8 @@ KERNEL_NAMES = {0: "none", 1: "line", 2: "pipe", 3: "part"}
 OPT_SWEEP_KERNEL, OPT_FUSE_MERGE, OPT_DIV_CORE, OPT_XSOLVE, OPT_OVERLAP, OPT_KEEP_TEMP = 0, 1, 2, 3, 4, 5
 OPT_F64_PART = 6          # fp64 contexts: 1 opens the fp64 partition kernels to SWEEP_AUTO / SWEEP_PART (default 0: bit-exact kernels)
 OPT_ERR_ORDER = 7         # 1: EvalDivError sums its terms serially in cell order, as the CPU path (bit-equal reported error on the exact kernels)
+OPT_MESH_VOXELS = 8       # the two mesh entries: 0 the reference's rasteriser (default), 1 conservative voxelisation (watertight)
+MESH_VOXELS = {"reference": 0, "conservative": 1}
 XSOLVE_AUTO, XSOLVE_PIPELINED, XSOLVE_REDUCED, XSOLVE_REDUCED_A2A = 0, 1, 2, 3
 
 # every symbol include/fs3d.h declares: name -> (restype, argtypes)
@@ -228,17 +230,26 @@ class Solver:
             raise ValueError("triangles: [m, 3] indices that fit an int")
         return xyz, tri
 
-    def voxelize_shape3d_dev(self, g, idx, baseT, type, bc_vel, bc_temp, vx, vy, vz, T):
+    def _mesh_voxels(self, voxels):
+        """voxels= of the two mesh methods: None leaves FS3D_OPT_MESH_VOXELS as it is, "reference" / "conservative" set it (it stays set)."""
+        if voxels is not None:
+            if voxels not in MESH_VOXELS:
+                raise ValueError("voxels is 'reference' or 'conservative'")
+            self.set_option(OPT_MESH_VOXELS, MESH_VOXELS[voxels])
+
+    def voxelize_shape3d_dev(self, g, idx, baseT, type, bc_vel, bc_temp, vx, vy, vz, T, voxels=None):
         """Grid3D::Build + FloodFill + the Node array on the device: the mesh (g, idx) of shape3d.Shape3D.subframe(t) voxelised into
         seven arrays on the context's device -- torch tensors or raw pointers, as update_nodes_dev takes them.  The context's
         geometry is not touched."""
+        self._mesh_voxels(voxels)
         ptrs = self._dev_ptrs("voxelize_shape3d_dev", [type, bc_vel, bc_temp, vx, vy, vz, T])
         xyz, tri = self._mesh_arrays(g, idx)
         self._chk(self.lib.fs3d_voxelize_shape3d_dev(self.h, *[_p(a) for a in xyz], len(xyz[0]), _p(tri), tri.size // 3, float(baseT), *ptrs))
 
-    def update_nodes_shape3d(self, g, idx, baseT):
+    def update_nodes_shape3d(self, g, idx, baseT, voxels=None):
         """update_nodes with the voxelisation of the mesh (g, idx) as the source: 12 bytes per vertex travel, the node arrays are
         written by kernels.  Same contract as update_nodes."""
+        self._mesh_voxels(voxels)
         xyz, tri = self._mesh_arrays(g, idx)
         return self._update(self.lib.fs3d_update_nodes_shape3d, *[_p(a) for a in xyz], len(xyz[0]), _p(tri), tri.size // 3, float(baseT))
 

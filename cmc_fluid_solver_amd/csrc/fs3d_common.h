@@ -153,6 +153,7 @@ struct fs3d_ctx {
     int opt_overlap = 1;                   // FS3D_OPT_OVERLAP
     int opt_keep_temp = 0;                 // FS3D_OPT_KEEP_TEMP
     int opt_f64_part = 0;                  // FS3D_OPT_F64_PART
+    int opt_mesh_voxels = 0;               // FS3D_OPT_MESH_VOXELS: 0 = the reference's rasteriser, 1 = conservative voxelisation (k_geom_voxel_mesh)
     int opt_err_order = 0;                 // FS3D_OPT_ERR_ORDER: 1 = EvalDivError sums its per-cell terms serially in cell order (host), as the CPU path
     double *err_terms = nullptr;           // ... one term per cell (device, allocated on first use)
     std::vector<double> err_terms_host;

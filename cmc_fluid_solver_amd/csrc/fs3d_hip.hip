@@ -409,6 +409,9 @@ extern "C" fs3d_status fs3d_set_option(fs3d_ctx *c, int option, int value)
     case FS3D_OPT_KEEP_TEMP: c->opt_keep_temp = value ? 1 : 0; return FS3D_OK;
     case FS3D_OPT_F64_PART: c->opt_f64_part = value ? 1 : 0; return FS3D_OK;
     case FS3D_OPT_ERR_ORDER: c->opt_err_order = value ? 1 : 0; return FS3D_OK;
+    case FS3D_OPT_MESH_VOXELS:
+        if (value != 0 && value != 1) return fail(c, FS3D_ERR_INVALID, "bad mesh voxelisation id (0: the reference's rasteriser, 1: conservative)");
+        c->opt_mesh_voxels = value; return FS3D_OK;
     case FS3D_OPT_XSOLVE:
         if (value < 0 || value > 3) return fail(c, FS3D_ERR_INVALID, "bad cross-slab X solve id");
         c->opt_xsolve = value; return FS3D_OK;

@@ -498,6 +498,136 @@ __global__ void __launch_bounds__(64) k_geom_raster_mesh(const float *__restrict
     }
 }
 
+// ---- conservative voxelisation (FS3D_OPT_MESH_VOXELS = 1) -------------------------------------------------------------------------
+// k_geom_voxel_mesh: NODE_BOUND iff a triangle overlaps the cell's closed unit box -- Shape3D._voxel_setup / _voxel_triangle of
+// cmc_fluid_solver_amd/shape3d.py (where the rule, the slack and its derivation stand) and VoxelTriangle of host/Shape3D.h: fp32
+// vertices, every float64 operation theirs, in their order, rounded after each one.  One wave per triangle; the set-up (clipped bounding box, local
+// vertices, normal, the nine edge functions, the plane's two constants) is wave-uniform.  The three axes are renamed (a, b, d)
+// with d the depth axis -- the normal's dominant axis, so the columns of the (a, b) projection that pass its three edge functions
+// number about the triangle's area; the lanes stride over the columns of the clipped box.  A column takes its depth range from the
+// plane (one cell of margin each way: the range only bounds the loop, every cell in it runs all remaining tests as the twin's do);
+// a degenerate triangle has no plane and walks the box's depth, along its smallest extent.  The only write is a byte store of
+// NODE_BOUND into an array preset to NODE_IN: idempotent, so order is free and no atomics are needed.  Every index lies inside
+// the clipped box; there is no scan line, no guard and no flag word.
+#define VOXEL_SLACK 5.8207660913467407e-11              // 2^-34
+#define VOXEL_DEGENERATE 5.9604644775390625e-08        // 2^-24
+#define VOXEL_COORD_MAX 4096.0f
+
+struct VoxEdge { double wa, wb, c; };
+
+__device__ __forceinline__ bool vox_pass(const VoxEdge &e, double x, double y) { return (e.wa * x + e.wb * y) + e.c >= 0.0; }
+__device__ __forceinline__ double vox_sel(int c, double x, double y, double z) { return c == 0 ? x : (c == 1 ? y : z); }
+
+__global__ void __launch_bounds__(64) k_geom_voxel_mesh(const float *__restrict__ vx, const float *__restrict__ vy, const float *__restrict__ vz,
+                                                         const int *__restrict__ tri, int dimx, int dimy, int dimz, uint8_t *type)
+{
+    const int lane = threadIdx.x;
+    const int iv[3] = {tri[3 * blockIdx.x], tri[3 * blockIdx.x + 1], tri[3 * blockIdx.x + 2]};
+    float p[3][3];
+#pragma unroll
+    for (int i = 0; i < 3; i++) { p[i][0] = vx[iv[i]]; p[i][1] = vy[iv[i]]; p[i][2] = vz[iv[i]]; }
+    const int dims[3] = {dimx, dimy, dimz};
+    int o[3], n[3];
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        const float mn = fminf(p[0][c], fminf(p[1][c], p[2][c])), mx = fmaxf(p[0][c], fmaxf(p[1][c], p[2][c]));
+        const int lo = max((int)ceilf(mn) - 1, 0), hi = min((int)floorf(mx), dims[c] - 1);         // cells i with i + 1 >= mn and i <= mx
+        if (lo > hi) return;                                                                       // (wave-uniform)
+        o[c] = lo; n[c] = hi - lo + 1;
+    }
+    // float64 from here on: the local vertices and the edges are exact
+    double q[3][3], amax = 0.0;
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+        for (int c = 0; c < 3; c++) { q[i][c] = (double)p[i][c] - (double)o[c]; amax = fmax(amax, fabs(q[i][c])); }
+    const double S = (amax + 2.0) * VOXEL_SLACK;
+    const double e0x = q[1][0] - q[0][0], e0y = q[1][1] - q[0][1], e0z = q[1][2] - q[0][2];
+    const double e1x = -(q[0][0] - q[2][0]), e1y = -(q[0][1] - q[2][1]), e1z = -(q[0][2] - q[2][2]);
+    double nx = e0y * e1z - e0z * e1y, ny = e0z * e1x - e0x * e1z, nz = e0x * e1y - e0y * e1x;
+    const double nn = (nx * nx + ny * ny) + nz * nz;
+    const bool degenerate = !(nn >= VOXEL_DEGENERATE);
+    int d = 0;
+    if (degenerate) {
+        double ext[3];
+#pragma unroll
+        for (int c = 0; c < 3; c++) ext[c] = fmax(q[0][c], fmax(q[1][c], q[2][c])) - fmin(q[0][c], fmin(q[1][c], q[2][c]));
+        nx = 0.0; ny = 0.0; nz = 0.0;
+        double best = ext[0];
+        if (ext[1] < best) { d = 1; best = ext[1]; }
+        if (ext[2] < best) d = 2;
+    } else {
+        double best = fabs(nx);
+        if (fabs(ny) > best) { d = 1; best = fabs(ny); }
+        if (fabs(nz) > best) d = 2;
+    }
+    // the axes renamed: index 0, 1, 2 = a, b, d (cyclic, so orientation is kept)
+    const int a = d == 2 ? 0 : d + 1, b = d == 0 ? 2 : d - 1;
+    double t[3][3];
+#pragma unroll
+    for (int i = 0; i < 3; i++) { t[i][0] = vox_sel(a, q[i][0], q[i][1], q[i][2]); t[i][1] = vox_sel(b, q[i][0], q[i][1], q[i][2]); t[i][2] = vox_sel(d, q[i][0], q[i][1], q[i][2]); }
+    const double nr[3] = {vox_sel(a, nx, ny, nz), vox_sel(b, nx, ny, nz), vox_sel(d, nx, ny, nz)};
+    const int cnt_a = a == 0 ? n[0] : (a == 1 ? n[1] : n[2]), cnt_b = b == 0 ? n[0] : (b == 1 ? n[1] : n[2]), cnt_d = d == 0 ? n[0] : (d == 1 ? n[1] : n[2]);
+    const long long plane = (long long)dimy * dimz;
+    const long long sa = a == 0 ? plane : (a == 1 ? (long long)dimz : 1LL), sb = b == 0 ? plane : (b == 1 ? (long long)dimz : 1LL),
+                    sd = d == 0 ? plane : (d == 1 ? (long long)dimz : 1LL);
+    VoxEdge edge[3][3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) {                           // projections (a, b), (b, d), (d, a)
+        const int A = k, B = (k + 1) % 3, C = (k + 2) % 3;
+#pragma unroll
+        for (int j = 0; j < 3; j++) {
+            const int v0 = j, v1 = (j + 1) % 3;
+            const double eA = t[v1][A] - t[v0][A], eB = t[v1][B] - t[v0][B];
+            const double wa = nr[C] >= 0.0 ? -eB : eB, wb = nr[C] >= 0.0 ? eA : -eA;              // the inward normal of the edge
+            double tmin = wa * t[0][A] + wb * t[0][B];
+            tmin = fmin(tmin, wa * t[1][A] + wb * t[1][B]);
+            tmin = fmin(tmin, wa * t[2][A] + wb * t[2][B]);
+            const double cmax = fmax(wa, 0.0) + fmax(wb, 0.0);
+            const double sl = S * (fabs(wa) + fabs(wb));
+            edge[k][j].wa = wa; edge[k][j].wb = wb; edge[k][j].c = (cmax - tmin) + sl;
+        }
+    }
+    const double na = nr[0], nb = nr[1], nd = nr[2];
+    double c1 = 0.0, c2 = 0.0;
+    if (!degenerate) {
+        const double t0 = (na * t[0][0] + nb * t[0][1]) + nd * t[0][2], t1 = (na * t[1][0] + nb * t[1][1]) + nd * t[1][2],
+                     t2 = (na * t[2][0] + nb * t[2][1]) + nd * t[2][2];
+        const double tmin = fmin(t0, fmin(t1, t2)), tmax = fmax(t0, fmax(t1, t2));
+        const double cmax = (fmax(na, 0.0) + fmax(nb, 0.0)) + fmax(nd, 0.0), cmin = (fmin(na, 0.0) + fmin(nb, 0.0)) + fmin(nd, 0.0);
+        const double sl = S * ((fabs(na) + fabs(nb)) + fabs(nd));
+        c1 = (cmax - tmin) + sl; c2 = (cmin - tmax) - sl;
+    }
+    uint8_t *const base = type + (((long long)o[0] * dimy + o[1]) * dimz + o[2]);
+    const int ncol = cnt_a * cnt_b;                         // at most 8194^2
+#pragma unroll 1
+    for (int col = lane; col < ncol; col += 64) {
+        const int ia = col / cnt_b, ib = col - ia * cnt_b;
+        const double pa = (double)ia, pb = (double)ib;
+        if (!vox_pass(edge[0][0], pa, pb) || !vox_pass(edge[0][1], pa, pb) || !vox_pass(edge[0][2], pa, pb)) continue;
+        int k0 = 0, k1 = cnt_d - 1;
+        double g = 0.0;
+        if (!degenerate) {                                  // s + c1 >= 0 and s + c2 <= 0 for s = g + nd k
+            g = na * pa + nb * pb;
+            const double lo = (-c1 - g) / nd, hi = (-c2 - g) / nd, lim = 1048576.0;
+            k0 = max((int)floor(fmin(fmax(fmin(lo, hi), -lim), lim)) - 1, 0);
+            k1 = min((int)ceil(fmin(fmax(fmax(lo, hi), -lim), lim)) + 1, cnt_d - 1);
+        }
+        uint8_t *const colp = base + ia * sa + ib * sb;
+#pragma unroll 1
+        for (int k = k0; k <= k1; k++) {
+            const double pd = (double)k;
+            if (!vox_pass(edge[1][0], pb, pd) || !vox_pass(edge[1][1], pb, pd) || !vox_pass(edge[1][2], pb, pd)) continue;
+            if (!vox_pass(edge[2][0], pd, pa) || !vox_pass(edge[2][1], pd, pa) || !vox_pass(edge[2][2], pd, pa)) continue;
+            if (!degenerate) {
+                const double s = g + nd * pd;
+                if (!(s + c1 >= 0.0) || !(s + c2 <= 0.0)) continue;
+            }
+            colp[k * sd] = FS3D_NODE_BOUND;
+        }
+    }
+}
+
 // FloodFill (Grid3D.cpp:813-857): NODE_OUT spreads from cell (0,0,0) through NODE_IN cells over the 6-neighbourhood.  The result is
 // the connected component of that cell, so it does not depend on the order: here as directional passes over the byte array, each
 // of which carries NODE_OUT along every line of its direction as far as the line's NODE_IN cells reach (both ways), repeated by
@@ -960,14 +1090,17 @@ static fs3d_status mesh_prepare(fs3d_ctx *c, int nvert, int ntri)
 static fs3d_status mesh_check(fs3d_ctx *c, const MeshIn &in, const char *name, bool *new_idx)
 {
     fs3d_geom &g = c->geom;
+    const bool conservative = c->opt_mesh_voxels == 1;
     if (in.nvert < 1 || in.ntri < 0) return fail(c, FS3D_ERR_INVALID, std::string(name) + ": a mesh has at least one vertex and no negative number of triangles");
     for (int q = 0; q < 3 * in.ntri; q++)
         if (in.tri[q] < 0 || in.tri[q] >= in.nvert) return fail(c, FS3D_ERR_INVALID, std::string(name) + ": triangle index outside the vertex list");
     // keeps (int) defined and the line loops short
     for (const float *a : {in.x, in.y, in.z})
         for (int q = 0; q < in.nvert; q++)
-            if (!(std::fabs(a[q]) <= 65536.0f))
-                return fail(c, FS3D_ERR_INVALID, std::string(name) + ": a vertex coordinate is not finite or exceeds 65536 grid cells in magnitude");
+            if (!(std::fabs(a[q]) <= (conservative ? VOXEL_COORD_MAX : 65536.0f)))
+                return fail(c, FS3D_ERR_INVALID, std::string(name) + (conservative
+                             ? ": a vertex coordinate is not finite or exceeds 4096 grid cells in magnitude (the bound of the conservative voxelisation's slack)"
+                             : ": a vertex coordinate is not finite or exceeds 65536 grid cells in magnitude"));
     GTRY(mesh_prepare(c, in.nvert, in.ntri));
     float *hv = mesh_host_vert(g);
     memcpy(hv, in.x, 4 * (size_t)in.nvert); memcpy(hv + g.mesh_vcap, in.y, 4 * (size_t)in.nvert); memcpy(hv + 2 * (size_t)g.mesh_vcap, in.z, 4 * (size_t)in.nvert);
@@ -1025,11 +1158,15 @@ static fs3d_status mesh_launch(fs3d_ctx *c, const MeshIn &in, bool new_idx, cons
     }
     HIPCHK(c, hipMemsetAsync(a.type, FS3D_NODE_IN, (size_t)c->ncell, c->stream));
     HIPCHK(c, hipMemsetAsync(g.mesh_cnt, 0, sizeof(unsigned), c->stream));
-    if (in.ntri)
+    const bool conservative = c->opt_mesh_voxels == 1;      // (mesh_check admitted the coordinates for this mode)
+    if (in.ntri && conservative)
+        hipLaunchKernelGGL(k_geom_voxel_mesh, dim3((unsigned)in.ntri), dim3(64), 0, c->stream, g.mesh_vert, g.mesh_vert + g.mesh_vcap,
+                           g.mesh_vert + 2 * (size_t)g.mesh_vcap, g.mesh_idx, c->dimx, c->dimy, c->dimz, a.type);
+    else if (in.ntri)
         hipLaunchKernelGGL(k_geom_raster_mesh, dim3((unsigned)in.ntri), dim3(64), 0, c->stream, g.mesh_vert, g.mesh_vert + g.mesh_vcap,
                            g.mesh_vert + 2 * (size_t)g.mesh_vcap, g.mesh_idx, c->dimx, c->dimy, c->dimz, a.type, g.mesh_cnt + MC_FLAG);
     HIPCHK(c, hipGetLastError());
-    GTRY(mesh_fill(c, a.type, true, name));
+    GTRY(mesh_fill(c, a.type, !conservative, name));        // the conservative kernel has no flag word: it stays zero
     gev_begin(c);
     const bool vec = a.vec4(c->dimz);
     auto kern = vec ? k_geom_mesh_nodes<R, 4> : k_geom_mesh_nodes<R, 1>;

@@ -117,6 +117,9 @@ public:
         chk(fs3d_update_nodes_shape3d(ctx_, x.data(), y.data(), z.data(), (int)x.size(), idx.empty() ? &none : idx.data(), (int)(idx.size() / 3),
                                       grid_->baseT, numSegs));
     }
+    // FS3D_OPT_MESH_VOXELS for the UpdateGridShape3D calls that follow: 0 the reference's rasteriser, 1 the conservative
+    // voxelisation (Shape3D::voxels of host/Shape3D.h has the same values)
+    void SetMeshVoxels(int mode) { chk(fs3d_set_option(ctx_, FS3D_OPT_MESH_VOXELS, mode)); }
     // Solver3D::ClearOutterCells (Solver3D.cpp:41-44), on `next` as there and on `cur`: a cell that turns NODE_IN with the next
     // geometry starts from (0, 0, 0, baseT) in both
     void ClearOutterCells()

@@ -6,6 +6,8 @@
 //                                               (Grid3D.cpp:676-946)
 // File: frames; per frame: vertices, per vertex "x y z  vx vy vz", triangles, 3 indices each.  Frame duration 1/75 s; the
 // cycle length of a Shape3D run is Config::frame_time and GetFrame is always 0 (Grid3D.cpp:303-336).
+// Shape3D::voxels = 1 replaces the rasteriser (not the fill) by a conservative voxelisation, which the reference does not have: see
+// VoxelTriangle below and the derivation in cmc_fluid_solver_amd/shape3d.py.
 // Deviations, on purpose (a third one, of the moving loop, stands at FillShape3DNodes below):
 //   * NODE_BOUND cells: the reference sets only their type; bc_vel / bc_temp keep whatever `new Node[]` left there
 //     (Grid3D.cpp:351-371, 818-838: SetData runs for NODE_IN / NODE_OUT only).  Here they read as zero-filled memory:
@@ -44,6 +46,13 @@ struct Shape3D {
     int dimx = 0, dimy = 0, dimz = 0;
     double dx = 0, dy = 0, dz = 0;
     std::vector<uint8_t> type;
+    // 0: the reference's rasteriser (RasterPolygon + RasterLine; not watertight).  1: conservative voxelisation (VoxelTriangle below):
+    // NODE_BOUND iff a triangle overlaps the cell's closed unit box, so the shell of a closed mesh is closed for the flood fill.
+    // Set it before Load; Prepare(t) honours it.  Same value as FS3D_OPT_MESH_VOXELS.
+    int voxels = 0;
+    static constexpr double VOXEL_SLACK = 5.8207660913467407e-11;        // 2^-34: the derivation stands in cmc_fluid_solver_amd/shape3d.py
+    static constexpr double VOXEL_DEGENERATE = 5.9604644775390625e-08;   // 2^-24
+    static constexpr float VOXEL_COORD_MAX = 4096.0f;
 
     static float num(std::string tok) { std::replace(tok.begin(), tok.end(), ',', '.'); return (float)std::atof(tok.c_str()); }
 
@@ -140,6 +149,10 @@ struct Shape3D {
         Build(sub);
     }
 
+    // Build on a mesh given in grid coordinates (dimx, dimy, dimz set by the caller): what Prepare does with a sub-frame, for
+    // callers that bring their own vertices (tests/mesh_voxel_test.cpp)
+    void BuildMesh(const Shape3DFrame &fr) { Build(fr); }
+
 private:
     static float mix(float a, float wa, float b, float wb) { volatile float x = a * wa, y = b * wb; return x + y; }
     static float fl(float v) { volatile float x = v; return x; }                    // one rounding to float, no contraction
@@ -221,13 +234,114 @@ private:
             p[0] = fl(p[0] + dp[0]); p[1] = fl(p[1] + dp[1]); p[2] = fl(p[2] + dp[2]);
         }
     }
+    // ---- conservative voxelisation: Shape3D._voxel_setup / _voxel_triangle of the twin, operation for operation ----------------
+    // fp32 vertices, everything from them in float64 (the local vertices and edges are exact there), rounded after each operation
+    struct VoxelEdge { double wa, wb, c; };
+    static double fd(double v) { volatile double x = v; return x; }                 // one rounding to double, no contraction
+    static bool VoxelPass(const VoxelEdge &e, double x, double y) { return fd(fd(fd(e.wa * x) + fd(e.wb * y)) + e.c) >= 0; }
+    void VoxelTriangle(const float *const p[3])
+    {
+        const int dims[3] = {dimx, dimy, dimz};
+        int o[3], n[3];
+        for (int c = 0; c < 3; c++) {
+            const float mn = std::min(p[0][c], std::min(p[1][c], p[2][c])), mx = std::max(p[0][c], std::max(p[1][c], p[2][c]));
+            const int lo = std::max((int)std::ceil(mn) - 1, 0), hi = std::min((int)std::floor(mx), dims[c] - 1);   // cells i with i + 1 >= mn and i <= mx
+            if (lo > hi) return;
+            o[c] = lo; n[c] = hi - lo + 1;
+        }
+        double q[3][3], amax = 0;
+        for (int i = 0; i < 3; i++)
+            for (int c = 0; c < 3; c++) { q[i][c] = fd((double)p[i][c] - (double)o[c]); amax = std::max(amax, std::fabs(q[i][c])); }
+        const double S = fd(fd(amax + 2.0) * VOXEL_SLACK);
+        double e[3][3];                                   // edges v0 -> v1, v1 -> v2, v2 -> v0
+        for (int j = 0; j < 3; j++)
+            for (int c = 0; c < 3; c++) e[j][c] = fd(q[(j + 1) % 3][c] - q[j][c]);
+        const double *e0 = e[0];
+        const double e1[3] = {-e[2][0], -e[2][1], -e[2][2]};
+        double nrm[3] = {fd(fd(e0[1] * e1[2]) - fd(e0[2] * e1[1])), fd(fd(e0[2] * e1[0]) - fd(e0[0] * e1[2])), fd(fd(e0[0] * e1[1]) - fd(e0[1] * e1[0]))};
+        const double nn = fd(fd(fd(nrm[0] * nrm[0]) + fd(nrm[1] * nrm[1])) + fd(nrm[2] * nrm[2]));
+        const bool degenerate = !(nn >= VOXEL_DEGENERATE);
+        int d = 0;
+        if (degenerate) {                                 // depth along the axis of the smallest extent
+            double ext[3];
+            for (int c = 0; c < 3; c++)
+                ext[c] = fd(std::max(q[0][c], std::max(q[1][c], q[2][c])) - std::min(q[0][c], std::min(q[1][c], q[2][c])));
+            nrm[0] = nrm[1] = nrm[2] = 0;
+            if (ext[1] < ext[0]) d = 1;
+            if (ext[2] < ext[d]) d = 2;
+        } else {                                          // depth along the normal's dominant axis
+            if (std::fabs(nrm[1]) > std::fabs(nrm[0])) d = 1;
+            if (std::fabs(nrm[2]) > std::fabs(nrm[d])) d = 2;
+        }
+        const int axes[3] = {(d + 1) % 3, (d + 2) % 3, d};
+        const int a = axes[0], b = axes[1];
+        VoxelEdge edge[3][3];
+        for (int k = 0; k < 3; k++) {                     // projections (a, b), (b, d), (d, a)
+            const int A = axes[k], B = axes[(k + 1) % 3], C = axes[(k + 2) % 3];
+            for (int j = 0; j < 3; j++) {
+                const double eA = e[j][A], eB = e[j][B];
+                const double wa = nrm[C] >= 0 ? -eB : eB, wb = nrm[C] >= 0 ? eA : -eA;       // the inward normal of the edge
+                double tmin = fd(fd(wa * q[0][A]) + fd(wb * q[0][B]));
+                for (int v = 1; v < 3; v++) tmin = std::min(tmin, fd(fd(wa * q[v][A]) + fd(wb * q[v][B])));
+                const double cmax = fd(std::max(wa, 0.0) + std::max(wb, 0.0));
+                const double sl = fd(S * fd(std::fabs(wa) + std::fabs(wb)));
+                edge[k][j] = VoxelEdge{wa, wb, fd(fd(cmax - tmin) + sl)};
+            }
+        }
+        const double na = nrm[a], nb = nrm[b], nd = nrm[d];
+        double c1 = 0, c2 = 0;
+        if (!degenerate) {
+            double tmin = 0, tmax = 0;
+            for (int v = 0; v < 3; v++) {
+                const double t = fd(fd(fd(na * q[v][a]) + fd(nb * q[v][b])) + fd(nd * q[v][d]));
+                tmin = v ? std::min(tmin, t) : t; tmax = v ? std::max(tmax, t) : t;
+            }
+            const double cmax = fd(fd(std::max(na, 0.0) + std::max(nb, 0.0)) + std::max(nd, 0.0));
+            const double cmin = fd(fd(std::min(na, 0.0) + std::min(nb, 0.0)) + std::min(nd, 0.0));
+            const double sl = fd(S * fd(fd(std::fabs(na) + std::fabs(nb)) + std::fabs(nd)));
+            c1 = fd(fd(cmax - tmin) + sl); c2 = fd(fd(cmin - tmax) - sl);
+        }
+        const size_t stride[3] = {(size_t)dimy * dimz, (size_t)dimz, 1};
+        const size_t base = id(o[0], o[1], o[2]);
+        for (int ia = 0; ia < n[a]; ia++)
+            for (int ib = 0; ib < n[b]; ib++) {
+                const double pa = (double)ia, pb = (double)ib;
+                if (!VoxelPass(edge[0][0], pa, pb) || !VoxelPass(edge[0][1], pa, pb) || !VoxelPass(edge[0][2], pa, pb)) continue;
+                int k0 = 0, k1 = n[d] - 1;
+                double g = 0;
+                if (!degenerate) {                        // s + c1 >= 0 and s + c2 <= 0 for s = g + nd k; one cell of margin each way
+                    g = fd(fd(na * pa) + fd(nb * pb));
+                    const double lo = fd(fd(-c1 - g) / nd), hi = fd(fd(-c2 - g) / nd), lim = 1048576.0;
+                    k0 = std::max((int)std::floor(std::min(std::max(std::min(lo, hi), -lim), lim)) - 1, 0);
+                    k1 = std::min((int)std::ceil(std::min(std::max(std::max(lo, hi), -lim), lim)) + 1, n[d] - 1);
+                }
+                for (int k = k0; k <= k1; k++) {
+                    const double pd = (double)k;
+                    if (!VoxelPass(edge[1][0], pb, pd) || !VoxelPass(edge[1][1], pb, pd) || !VoxelPass(edge[1][2], pb, pd)) continue;
+                    if (!VoxelPass(edge[2][0], pd, pa) || !VoxelPass(edge[2][1], pd, pa) || !VoxelPass(edge[2][2], pd, pa)) continue;
+                    if (!degenerate) {
+                        const double s = fd(g + fd(nd * pd));
+                        if (!(fd(s + c1) >= 0) || !(fd(s + c2) <= 0)) continue;
+                    }
+                    type[base + ia * stride[a] + ib * stride[b] + k * stride[d]] = NODE_BOUND;
+                }
+            }
+    }
+
     // Grid3D::Build (Grid3D.cpp:859-903) + FloodFill (:813-857)
     void Build(const Shape3DFrame &fr)
     {
         type.assign((size_t)dimx * dimy * dimz, NODE_IN);
+        if (voxels != 0 && voxels != 1) throw std::runtime_error("Shape3D: voxels is 0 (the reference's rasteriser) or 1 (conservative)");
+        if (voxels == 1)
+            for (const std::vector<float> *a : {&fr.x, &fr.y, &fr.z})
+                for (float v : *a)
+                    if (!(std::fabs(v) <= VOXEL_COORD_MAX))
+                        throw std::runtime_error("Shape3D: a vertex coordinate is not finite or exceeds 4096 grid cells in magnitude (conservative voxelisation)");
         for (size_t q = 0; q + 2 < fr.idx.size(); q += 3) {
             const int i1 = fr.idx[q], i2 = fr.idx[q + 1], i3 = fr.idx[q + 2];
             const float p1[3] = {fr.x[i1], fr.y[i1], fr.z[i1]}, p2[3] = {fr.x[i2], fr.y[i2], fr.z[i2]}, p3[3] = {fr.x[i3], fr.y[i3], fr.z[i3]};
+            if (voxels == 1) { const float *const p[3] = {p1, p2, p3}; VoxelTriangle(p); continue; }
             RasterPolygon(p1, p2, p3);
             RasterLine(p1, p2); RasterLine(p1, p3); RasterLine(p3, p2);       // the edges as well, to cover holes
         }
@@ -263,8 +377,9 @@ void FillShape3DNodes(Grid3D<FTYPE> &g, const Shape3D &sh, double baseT)
 
 // Grid3D(dx,dy,dz,baseT) + LoadFromFile + Prepare_CPU(0) for a Shape3D input (FluidSolver3D.cpp:121-145)
 template <typename FTYPE>
-void LoadShape3D(Grid3D<FTYPE> &g, Shape3D &sh, const std::string &path, double dx, double dy, double dz, double baseT, bool align)
+void LoadShape3D(Grid3D<FTYPE> &g, Shape3D &sh, const std::string &path, double dx, double dy, double dz, double baseT, bool align, int voxels = 0)
 {
+    sh.voxels = voxels;
     sh.Load(path, dx, dy, dz, align);
     g.Resize(sh.dimx, sh.dimy, sh.dimz);
     g.dx = dx; g.dy = dy; g.dz = dz; g.baseT = baseT;

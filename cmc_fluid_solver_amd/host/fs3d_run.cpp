@@ -1,5 +1,5 @@
 // Command-line driver: the reference's FluidSolver3D main (FluidSolver3D/FluidSolver3D.cpp:60-330) on top of
-// libfs3d_hip.so.   fs3d_run <input data> <output prefix> <config> [align] [GPU [n]] [double] [moving [--host-extrusion] [--time-geometry]] [moving-mesh [--host-voxels] [--time-geometry] [--time-both]] [--time-output] [--steps N] [--same-device] [--grid-only FILE [--grid-time T]]
+// libfs3d_hip.so.   fs3d_run <input data> <output prefix> <config> [align] [GPU [n]] [double] [moving [--host-extrusion] [--time-geometry]] [moving-mesh [--host-voxels] [--time-geometry] [--time-both]] [--time-output] [--steps N] [--same-device] [--grid-only FILE [--grid-time T]] [--watertight]
 //   * reads the config (host/Config.h) and a Shape2D, Shape3D or SeaNetCDF geometry (host/Shape2D.h, Shape3D.h, SeaNetCDF.h), prints the grid summary lines
 //     the reference prints ("Grid = X x Y x Z", "NODE_IN points = ..."),
 //   * runs the same loop: dt = cycle length / (frames * time_steps), UpdateBoundaries + TimeStep per step with the
@@ -20,6 +20,9 @@
 //   for a Shape3D input.  `moving` keeps its meaning: Shape2D inputs only.
 //   --host-voxels: Shape3D::Prepare(t) on the host (rasteriser and flood fill), then UpdateGrid with the seven arrays -- the same
 //   results bit for bit; kept for A/B timing and as the checker of the device voxeliser.
+//   --watertight (in_fmt Shape3D, with or without moving-mesh): the conservative voxelisation instead of the reference's rasteriser
+//   (Shape3D::voxels = 1 on the host, FS3D_OPT_MESH_VOXELS = 1 on the device) for the first geometry and for every update alike: a
+//   closed mesh keeps its NODE_IN cells at every time; the shell is thicker, so the fluid volume is smaller.
 //   --time-both: a measurement run -- every step makes the geometry through BOTH paths, the word's own last (same tables either way),
 //   and one more line gives, per call after 3 warm-up steps, median (min - max) of the host clock around each path, the device
 //   time of the device path (fs3d_last_update_device_ms), and the host clock around UpdateBoundaries + TimeStep, synchronised.
@@ -61,7 +64,7 @@ struct RunGeom {
 
 // the words after <config file>, as main's argument loop finds them
 struct RunOptions {
-    bool align = false, dbl = false, csv = false, same_device = false, grid_images = false;
+    bool align = false, dbl = false, csv = false, same_device = false, grid_images = false, watertight = false;
     bool moving = false, host_extrusion = false, moving_mesh = false, host_voxels = false, time_geometry = false, time_both = false, time_output = false;
     double grid_time = -1;
     int nslabs = 1, device = 0;
@@ -85,6 +88,7 @@ static int run(const std::string &data, const std::string &prefix, const fs3d::C
     if (o.host_voxels && !o.moving_mesh) throw std::runtime_error("--host-voxels: only with moving-mesh (it selects where a moving mesh is voxelised)");
     if (o.time_both && !o.moving_mesh) throw std::runtime_error("--time-both: only with moving-mesh (it times both ways of making a mesh's geometry)");
     if (o.time_geometry && !o.moving && !o.moving_mesh) throw std::runtime_error("--time-geometry: only with moving or moving-mesh (it times the per-step geometry work)");
+    if (o.watertight && cfg.in_fmt != "Shape3D") throw std::runtime_error("--watertight: only in_fmt Shape3D inputs are meshes (this one is " + cfg.in_fmt + ")");
     if (o.grid_time >= 0 && cfg.in_fmt != "Shape2D" && cfg.in_fmt != "Shape3D") throw std::runtime_error("--grid-time: only in_fmt Shape2D and Shape3D inputs move");
     using namespace fs3d;
     Grid3D<FTYPE> grid;
@@ -99,7 +103,7 @@ static int run(const std::string &data, const std::string &prefix, const fs3d::C
         for (int a = 0; a < 6; a++) geo.bbox[a] = sea.bbox[a];
     } else if (cfg.in_fmt == "Shape3D") {
         std::printf("Geometry: 3D polygons\n");                                                  // FluidSolver3D.cpp:121-126
-        LoadShape3D(grid, sh3, data, cfg.dx, cfg.dy, cfg.dz, cfg.baseT, o.align);
+        LoadShape3D(grid, sh3, data, cfg.dx, cfg.dy, cfg.dz, cfg.baseT, o.align, o.watertight ? 1 : 0);
         geo.frames = sh3.GetFramesNum(); geo.length = cfg.frame_time;                            // Grid3D.cpp:298-309
         for (int a = 0; a < 6; a++) geo.bbox[a] = sh3.bbox[a];
     } else {
@@ -133,6 +137,7 @@ static int run(const std::string &data, const std::string &prefix, const fs3d::C
                                                         : FluidParams<FTYPE>(cfg.viscosity, cfg.density, cfg.R_specific, cfg.k, cfg.cv);
     AdiSolver3D<FTYPE> solver;
     solver.Init(o.device, grid, params);
+    if (o.watertight) solver.SetMeshVoxels(1);           // the updates voxelise as the host loader did
     std::printf("Segments: %i %i %i (x, y, z)\n", solver.numSegs[0], solver.numSegs[1], solver.numSegs[2]);
 
     const int frames = geo.frames;                                     // FluidSolver3D.cpp:194-195
@@ -374,7 +379,7 @@ static int run_slabs(const fs3d::Grid3D<FTYPE> &grid, const RunGeom &geo, const 
 int main(int argc, char **argv)
 {
     if (argc < 4) {
-        std::printf("Usage: %s <input data> <output prefix> <config file> [align] [GPU [n]] [double] [--steps N] [moving [--host-extrusion] [--time-geometry]] [moving-mesh [--host-voxels] [--time-geometry] [--time-both]] [--time-output] [--grid-only FILE [--grid-time T]] [--grid-images]\n", argv[0]);
+        std::printf("Usage: %s <input data> <output prefix> <config file> [align] [GPU [n]] [double] [--steps N] [moving [--host-extrusion] [--time-geometry]] [moving-mesh [--host-voxels] [--time-geometry] [--time-both]] [--time-output] [--grid-only FILE [--grid-time T]] [--grid-images] [--watertight]\n", argv[0]);
         return 0;
     }
     try {
@@ -398,6 +403,7 @@ int main(int argc, char **argv)
             else if (s == "moving") o.moving = true;
             else if (s == "moving-mesh") o.moving_mesh = true;
             else if (s == "--host-voxels") o.host_voxels = true;
+            else if (s == "--watertight") o.watertight = true;
             else if (s == "--time-both") o.time_both = true;
             else if (s == "--host-extrusion") o.host_extrusion = true;
             else if (s == "--time-geometry") o.time_geometry = true;

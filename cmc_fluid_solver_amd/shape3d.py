@@ -45,8 +45,47 @@ def parse_shape3d(text):
     return frames
 
 
+# ---- conservative voxelisation (voxels="conservative"): constants shared by host/Shape3D.h and csrc/kernels_geom.hip -------------
+# A cell becomes NODE_BOUND iff a triangle overlaps its closed unit box [i, i+1] x [j, j+1] x [k, k+1]: separating axes in the
+# Schwarz-Seidel form.  The bounding box is compared in grid coordinates, where nothing is rounded (floor / ceil of the fp32
+# vertices): its slack is zero.  Every other inequality is  f(p) = w.p + c >= 0  for an axis w (an edge normal of a projection, or
+# the plane's normal), c = (max of w over the unit box) - (min of w.q_i over the three vertices) + S |w|_1, on coordinates local to
+# the integer corner `o` of the triangle's clipped bounding box; S |w|_1 is the slack: the unit box grown by S.
+# Comparing the box's interval along w with the triangle's *interval* is a valid separating-axis test for any w whatever, so the
+# rounding of w (cancellation in the normal of a thin triangle) can never drop a cell: only the evaluation of f has to be guarded.
+# Arithmetic: the vertices are fp32, everything computed from them is float64, in a fixed order, uncontracted, so that numpy, g++
+# and the kernel produce the same bits.  In float64 the local vertices q = v - o (fp32 minus an integer below 2^13) and the edge
+# vectors are exact, so a vertex shared by two triangles is the same point seen from both origins; the cell coordinates p are
+# exact; the normal is the cross product of exact edges, good to 2^-52 of its terms.
+# Why not fp32: at coordinates near 100 one fp32 rounding is 6e-6 of a cell -- in the evaluation, and through the normal's
+# rounding in the width of the triangle's interval along it -- and a face that misses a cell corner by 1e-6 (the shipped tetra
+# mesh has 172 such corners) could not be told from one that touches it.
+# Where the slack comes from.  u = 2^-53, L = max |q| + 2 (a local cell corner p + 1 is at most max q + 1), every |w_c x_c| <= |w_c| L.
+# Roundings of one inequality in units of u L |w|_1: w.q_i -- products <= 1, sums <= 2; cmax - tmin <= 1; adding the slack <= 1;
+# w.p -- products exact, sums <= 2; the last sum <= 1: at most 8, second-order terms and the roundings of cmax and of S |w|_1 (a few
+# u |w|_1, without the factor L >= 2) fit into 4 more: the rounding bound is 12 u L |w|_1 = 1.3e-15 L |w|_1.  The slack is set far
+# above it, S = VOXEL_SLACK * L = 2^-34 L (6e-9 of a cell at L = 100, below 5e-7 whatever the mesh: coordinates are at most
+# VOXEL_COORD_MAX in magnitude, so L <= 2^13 + 3), so that a float64 restatement with a noise of its own (tests/watertight_cases.py)
+# can hold the result to it.  So: a cell whose box overlaps the triangle is always set, and a set cell's box grown by
+# VOXEL_TOL * L = (2^-34 + 12 u) L overlaps it.
+VOXEL_SLACK = 2.0 ** -34
+VOXEL_TOL = 2.0 ** -34 + 12 * 2.0 ** -53
+VOXEL_COORD_MAX = 4096.0
+# A triangle whose squared normal is below this is degenerate -- two or three equal vertices,
+# collinear ones, or an area below 2^-13 of a cell's face: it is within 2^-6 of a cell of its longest edge.  It has no plane to take
+# a depth range from; its three edges are tested as segments in the three projections (for collinear vertices the two shorter ones
+# lie on the longest: the cells of the longest edge, no more), never its bounding box.
+VOXEL_DEGENERATE = 2.0 ** -24
+_VOXEL_AXES = ((1, 2, 0), (2, 0, 1), (0, 1, 2))      # (a, b, d): the column plane and the depth axis, cyclic, by depth axis d
+_VOXEL_EDGES = ((0, 1), (1, 2), (2, 0))
+VOXEL_MODES = ("reference", "conservative")
+
+
 class Shape3D:
-    def __init__(self, frames, dx, dy, dz, align, time=0.0):
+    def __init__(self, frames, dx, dy, dz, align, time=0.0, voxels="reference"):
+        if voxels not in VOXEL_MODES:
+            raise ValueError("Shape3D: voxels is 'reference' or 'conservative'")
+        self.voxels = voxels
         self.frames = frames
         self.dx, self.dy, self.dz = dx, dy, dz
         allv = np.concatenate([fr["v"] for fr in frames], axis=0)
@@ -166,10 +205,98 @@ class Shape3D:
             self._set(int(p[0]), int(p[1]), int(p[2]), NODE_BOUND)
             p = [F(p[q] + dp[q]) for q in range(3)]
 
+    # ---- conservative voxeliser ---------------------------------------------------------------------------------------
+    def _voxel_setup(self, p):
+        """The wave-uniform part of k_geom_voxel_mesh for the triangle p[3][3] (fp32): None when its bounding box misses the grid,
+        else (o, n, axes, edge functions [projection][edge] = (wA, wB, c), plane (na, nb, nd, c1, c2) or None), all float64."""
+        dims = (self.dimx, self.dimy, self.dimz)
+        o, n = [], []
+        for c in range(3):
+            mn, mx = min(p[0][c], p[1][c], p[2][c]), max(p[0][c], p[1][c], p[2][c])
+            lo, hi = max(int(math.ceil(mn)) - 1, 0), min(int(math.floor(mx)), dims[c] - 1)      # cells i with i + 1 >= mn and i <= mx
+            if lo > hi:
+                return None
+            o.append(lo); n.append(hi - lo + 1)
+        # float64 from here on (Python floats), every operation rounded once: the local vertices and the edge vectors are exact
+        q = [[float(p[i][c]) - float(o[c]) for c in range(3)] for i in range(3)]
+        S = (max(abs(q[i][c]) for i in range(3) for c in range(3)) + 2.0) * VOXEL_SLACK
+        e = [[q[j][c] - q[i][c] for c in range(3)] for i, j in _VOXEL_EDGES]
+        e0, e1 = e[0], [-x for x in e[2]]                                                      # v1 - v0, v2 - v0
+        nrm = [e0[1] * e1[2] - e0[2] * e1[1], e0[2] * e1[0] - e0[0] * e1[2], e0[0] * e1[1] - e0[1] * e1[0]]
+        nn = (nrm[0] * nrm[0] + nrm[1] * nrm[1]) + nrm[2] * nrm[2]
+        degenerate = not nn >= VOXEL_DEGENERATE
+        if degenerate:                                   # depth along the axis of the smallest extent: few cells per column
+            ext = [max(q[0][c], q[1][c], q[2][c]) - min(q[0][c], q[1][c], q[2][c]) for c in range(3)]
+            nrm = [0.0, 0.0, 0.0]
+            d = 0
+            if ext[1] < ext[0]: d = 1
+            if ext[2] < ext[d]: d = 2
+        else:                                            # depth along the normal's dominant axis
+            d = 0
+            if abs(nrm[1]) > abs(nrm[0]): d = 1
+            if abs(nrm[2]) > abs(nrm[d]): d = 2
+        axes = _VOXEL_AXES[d]
+        edges = []
+        for k in range(3):                               # projections (a, b), (b, d), (d, a): (A, B) cyclic, C the third axis
+            A, B, C = axes[k], axes[(k + 1) % 3], axes[(k + 2) % 3]
+            fns = []
+            for j in range(3):
+                eA, eB = e[j][A], e[j][B]
+                wA, wB = (-eB, eA) if nrm[C] >= 0 else (eB, -eA)                               # the inward normal of the edge
+                tmin = min(wA * q[v][A] + wB * q[v][B] for v in range(3))
+                cmax = max(wA, 0.0) + max(wB, 0.0)
+                fns.append((wA, wB, (cmax - tmin) + S * (abs(wA) + abs(wB))))
+            edges.append(fns)
+        plane = None
+        if not degenerate:
+            a, b = axes[0], axes[1]
+            na, nb, nd = nrm[a], nrm[b], nrm[d]
+            t = [(na * q[v][a] + nb * q[v][b]) + nd * q[v][d] for v in range(3)]
+            cmax = (max(na, 0.0) + max(nb, 0.0)) + max(nd, 0.0); cmin = (min(na, 0.0) + min(nb, 0.0)) + min(nd, 0.0)
+            sl = S * ((abs(na) + abs(nb)) + abs(nd))
+            plane = (na, nb, nd, (cmax - min(t)) + sl, (cmin - max(t)) - sl)
+        return o, n, axes, edges, plane
+
+    def _voxel_triangle(self, p):
+        st = self._voxel_setup(p)
+        if st is None:
+            return
+        o, n, (a, b, d), edges, plane = st
+        pa = np.arange(n[a], dtype=np.float64)[:, None, None]; pb = np.arange(n[b], dtype=np.float64)[None, :, None]
+        pd = np.arange(n[d], dtype=np.float64)[None, None, :]
+        ev = lambda fn, x, y: ((fn[0] * x + fn[1] * y) + fn[2]) >= 0          # float64 arrays: rounded after every operation
+        col = ev(edges[0][0], pa, pb) & ev(edges[0][1], pa, pb) & ev(edges[0][2], pa, pb)
+        k0, k1 = np.zeros(col.shape, np.int64), np.full(col.shape, n[d] - 1, np.int64)
+        if plane is not None:
+            na, nb, nd, c1, c2 = plane
+            g = na * pa + nb * pb
+            lo, hi = (-c1 - g) / nd, (-c2 - g) / nd                             # s + c1 >= 0 and s + c2 <= 0 for s = g + nd k
+            lim = 2.0 ** 20
+            k0 = np.maximum(np.floor(np.clip(np.minimum(lo, hi), -lim, lim)).astype(np.int64) - 1, 0)      # one cell of margin each way:
+            k1 = np.minimum(np.ceil(np.clip(np.maximum(lo, hi), -lim, lim)).astype(np.int64) + 1, n[d] - 1)  # the range only bounds the loop
+        kk = np.arange(n[d])[None, None, :]
+        m = col & (kk >= k0) & (kk <= k1)
+        for fn in edges[1]:
+            m = m & ev(fn, pb, pd)
+        for fn in edges[2]:
+            m = m & ev(fn, pd, pa)
+        if plane is not None:
+            s = g + nd * pd
+            m = m & ((s + c1) >= 0) & ((s + c2) <= 0)
+        m = np.transpose(m, [(a, b, d).index(c) for c in range(3)])
+        self.type[o[0]:o[0] + n[0], o[1]:o[1] + n[1], o[2]:o[2] + n[2]][m] = NODE_BOUND
+
     def build(self, g, idx):
         self.type = np.full((self.dimx, self.dimy, self.dimz), NODE_IN, np.uint8)
+        if self.voxels == "conservative":
+            g = np.asarray(g, np.float32)
+            if len(g) and not (np.abs(g) <= VOXEL_COORD_MAX).all():
+                raise ValueError("Shape3D: a vertex coordinate is not finite or exceeds 4096 grid cells in magnitude (conservative voxelisation)")
         for i1, i2, i3 in idx:
             p1, p2, p3 = (tuple(F(c) for c in g[q]) for q in (i1, i2, i3))
+            if self.voxels == "conservative":
+                self._voxel_triangle((p1, p2, p3))
+                continue
             self._raster_polygon(p1, p2, p3)
             self._raster_line(p1, p2); self._raster_line(p1, p3); self._raster_line(p3, p2)
         # flood fill NODE_OUT from (0,0,0) through NODE_IN cells, 6-neighbourhood (scipy labels the same set)
@@ -180,10 +307,10 @@ class Shape3D:
         self.type[lab == lab[0, 0, 0]] = NODE_OUT
 
 
-def load_shape3d(path_or_text, dx, dy, dz, baseT=1.0, align=True, is_text=False):
+def load_shape3d(path_or_text, dx, dy, dz, baseT=1.0, align=True, is_text=False, voxels="reference"):
     """Grid3D(dx,dy,dz,baseT) + LoadFromFile + Prepare_CPU(0) for a Shape3D input -> (Nodes, Shape3D)."""
     text = path_or_text if is_text else open(path_or_text, "r").read()
-    sh = Shape3D(parse_shape3d(text), dx, dy, dz, align)
+    sh = Shape3D(parse_shape3d(text), dx, dy, dz, align, voxels=voxels)
     return nodes_of(sh, dx, dy, dz, baseT), sh
 
 

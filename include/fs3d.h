@@ -87,6 +87,9 @@ enum {
                                  No effect on slab contexts (a multi-GPU group, or a context with a neighbouring slab's ghost planes):
                                  fp64 slabs keep the bit-exact Y / Z kernels and their cross-slab X solve.
                                  Environment FS3D_DEFAULT_F64_PART=1 sets the initial value for new contexts */
+    FS3D_OPT_MESH_VOXELS = 8, /* how fs3d_update_nodes_shape3d and fs3d_voxelize_shape3d_dev turn a mesh into NODE_BOUND cells; no effect on
+                                 any other entry.  0 (default): the reference's rasteriser, which is not watertight.  1: conservative
+                                 voxelisation, closed for every closed mesh (the mesh section below).  Any other value: FS3D_ERR_INVALID */
     FS3D_OPT_ERR_ORDER = 7    /* summation order of EvalDivError (fs3d_eval_div_error, fs3d_time_step with compute_error).  0 (default): the
                                  per-cell terms are summed in parallel (per workgroup, then over the workgroups; deterministic, equal to the
                                  CPU path to ~1e-12 relative).  1: they are summed one after the other in cell order, as the loop of
@@ -204,6 +207,23 @@ fs3d_status fs3d_update_nodes_shape2d(fs3d_ctx *ctx, const uint8_t *cell2d, cons
  * A mesh with a polygon scan line of more than 4 (dimx + dimy + dimz) + 16 cells (where shape3d.py raises and the reference
  * loops), or with a triangle so thin that its scan stops advancing in fp32, is refused with FS3D_ERR_INVALID after the rasteriser
  * has run: fs3d_update_nodes_shape3d then leaves NO geometry, the arrays of fs3d_voxelize_shape3d_dev hold no valid grid.
+ *
+ * Conservative voxelisation (FS3D_OPT_MESH_VOXELS set to 1).  The reference's rasteriser projects one point per scan cell back onto the
+ * polygon and truncates: it can leave a gap in the NODE_BOUND shell of a closed mesh, the flood fill then runs through it and the
+ * whole interior becomes NODE_OUT (an icosphere of 20 faces at radii 15 x 19 x 15 cells has no NODE_IN cell).  With the option on,
+ * a cell is NODE_BOUND if and only if a triangle of the mesh overlaps the cell's CLOSED unit box [i, i+1] x [j, j+1] x [k, k+1] in
+ * grid coordinates (a point p lies in cell floor(p), the reference's (int)p) -- a separating-axis triangle-box test on the fp32
+ * vertices, evaluated in float64 (where the vertices local to the triangle's box and its edges are exact), whose every inequality
+ * accepts with a slack far above its rounding bound (2^-34 of the triangle's size in cells: below 5e-7 of a cell whatever the
+ * mesh, about 1e-9 for triangles a few cells wide; cmc_fluid_solver_amd/shape3d.py states rule and derivation), so rounding only
+ * ever adds a cell.
+ * Such a shell separates over the 26-neighbourhood: the 6-neighbour flood fill cannot cross the shell of a closed mesh.  It is up
+ * to about three cells thick where the reference's is one or two, so the fluid volume is smaller than with the default.  The
+ * nodes equal those of shape3d.Shape3D(voxels="conservative") and of host/Shape3D.h with voxels = 1 byte for byte, and are a
+ * function of this call's mesh alone.  This mode admits coordinates of at most 4096 grid cells in magnitude (FS3D_ERR_INVALID
+ * before anything is launched, the context unchanged; the default mode keeps its 65536).  It has no scan lines: nothing is
+ * refused after the kernels have run.  A triangle with two or three equal or collinear vertices sets the cells of its longest
+ * edge; triangles and parts of triangles outside the grid are dropped.
  *
  * fs3d_voxelize_shape3d_dev: the seven SoA node arrays (ncell elements each, on the context's device; real = the context's
  * precision) are written on the context's stream; returns synchronised.  The context's geometry is not touched (it needs none).

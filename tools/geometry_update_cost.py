@@ -30,6 +30,10 @@ in one process, after a warm-up:
 
     python tools/geometry_update_cost.py --mesh [--out profiles/mesh_update_cost.json] [--write-inputs DIR] [--kernel-stats CSV]
 
+    python tools/geometry_update_cost.py --mesh --voxels conservative [--out profiles/mesh_update_cost_conservative.json]
+        (the conservative voxelisation, FS3D_OPT_MESH_VOXELS = 1, beside the default one on the same two grids: main_mesh_voxels;
+        kernel rows: --kernel-stats CSV of a rocprofv3 --kernel-trace --stats run of `fs3d_run ... moving-mesh --watertight`)
+
 A moving Shape3D mesh: the voxelisation and flood fill on the device (fs3d_update_nodes_shape3d) against today's path.  The mesh is an
 icosphere of 1280 faces (642 vertices; the reference's heart_us_3D has 1294 triangles) breathing between two radii (x 1.0 and x 0.9), stretched to fill a
 grid of heart_us_3D's size, 128 x 160 x 128, and one of 256^3.  Everything runs in the driver, fs3d_run ... moving-mesh:
@@ -351,7 +355,7 @@ def main_mesh(a):
     import re
     import tempfile
     from cmc_fluid_solver_amd import build as B
-    out_path = a.out if a.out != DEFAULT_OUT else os.path.join(ROOT, "profiles", "mesh_update_cost.json")
+    out_path = a.out if a.out != DEFAULT_OUT else os.path.join(ROOT, "profiles", "mesh_update_cost_conservative.json" if a.voxels else "mesh_update_cost.json")
     if a.write_inputs:
         for name, (data, cfg, dims) in write_mesh_inputs(a.write_inputs).items():
             print(name, data, cfg)
@@ -368,9 +372,10 @@ def main_mesh(a):
         updates = rows[[n for n in rows if "k_geom_codes" in n][0]]["calls"]
         res[a.grid]["kernels"] = {"rows": rows, "updates": updates,
                                   "raster_us_per_update": part(lambda n: "raster_mesh" in n) / updates,
+                                  "voxel_us_per_update": part(lambda n: "voxel_mesh" in n) / updates,
                                   "fill_us_per_update": part(lambda n: "k_geom_fill" in n) / updates,
                                   "node_arrays_us_per_update": part(lambda n: "mesh_nodes" in n) / updates,
-                                  "table_rebuild_us_per_update": part(lambda n: "k_geom_" in n and "raster" not in n and "fill" not in n and "mesh_nodes" not in n) / updates}
+                                  "table_rebuild_us_per_update": part(lambda n: "k_geom_" in n and "raster" not in n and "voxel_mesh" not in n and "fill" not in n and "mesh_nodes" not in n) / updates}
         json.dump(res, open(out_path, "w"), indent=1)
         print(json.dumps(res[a.grid]["kernels"], indent=1))
         return
@@ -414,6 +419,60 @@ def main_mesh(a):
     print("wrote", out_path)
 
 
+def main_mesh_voxels(a):
+    """--mesh --voxels conservative: the two grids of --mesh, fs3d_update_nodes_shape3d with FS3D_OPT_MESH_VOXELS 0 and 1 alternating
+    in one process (the mesh breathes between its two frames, one update per mode and sample), then the time step of the same
+    geometry.  Condition: the conservative update's device time stays below the time step, on both grids."""
+    import tempfile
+    import torch
+    from cmc_fluid_solver_amd import shape3d
+    if not torch.cuda.is_available():
+        raise SystemExit("geometry_update_cost: no GPU (there is no CPU fallback)")
+    out_path = a.out if a.out != DEFAULT_OUT else os.path.join(ROOT, "profiles", "mesh_update_cost_conservative.json")
+    res = {"device": torch.cuda.get_device_name(0), "commit": a.commit or tree_commit(), "precision": "fp32", "repeats": a.repeats,
+           "mesh": "icosphere, 1280 faces, 642 vertices, two frames (radii x 1.0 and x 0.9)",
+           "note": "one process per grid; per sample one fs3d_update_nodes_shape3d per mode (default first), alternating, 3 warm-up samples "
+                   "dropped; host clock around calls that end synchronised, device time from HIP events inside the library; step = G 4, L 2, AUTO"}
+    h = float(np.float32(0.001))
+    with tempfile.TemporaryDirectory() as d:
+        for name, (data, cfg, dims) in write_mesh_inputs(d).items():
+            nodes, sh = shape3d.load_shape3d(data, h, h, h, align=True, voxels="conservative")
+            assert nodes.shape == dims, (nodes.shape, dims)
+            s = capi.Solver(nodes, capi.fluid_params(np.float32, 200.0, 0.72, 1.4), np.float32)
+            s.enable_timing(True)
+            acc = {m: {"host": [], "dev": [], "fluid": None} for m in ("reference", "conservative")}
+            step = []
+            for k in range(a.repeats + 3):
+                g, idx = sh.subframe(0.4 / 2 * ((k % 16) / 16.0))
+                for m in ("reference", "conservative"):
+                    t0 = time.perf_counter()
+                    s.update_nodes_shape3d(g, idx, 1.0, voxels=m)
+                    ms = (time.perf_counter() - t0) * 1e3
+                    if k >= 3:
+                        acc[m]["host"].append(ms); acc[m]["dev"].append(s.last_update_device_ms())
+                    info = s.geometry_info()
+                    acc[m]["fluid"] = int(np.prod(dims)) - info["bound_cells"]
+                    acc[m]["fill_rounds"] = s.mesh_fill_rounds()
+                t0 = time.perf_counter()
+                s.UpdateBoundaries(); s.TimeStep(np.float32(0.4 / 32), 4, 2, False)
+                s._chk(s.lib.fs3d_synchronize(s.h))
+                if k >= 3:
+                    step.append((time.perf_counter() - t0) * 1e3)
+            s.close()
+            r = {"dims": list(dims), "cells": int(np.prod(dims)), "time_step": stats(step)}
+            for m in acc:
+                r[m] = {"update_nodes_shape3d": stats(acc[m]["host"]), "device_time": stats(acc[m]["dev"]), "fill_rounds": acc[m]["fill_rounds"]}
+            r["conservative_device_time_over_time_step"] = r["conservative"]["device_time"]["median_ms"] / r["time_step"]["median_ms"]
+            r["conservative_over_reference_device_time"] = r["conservative"]["device_time"]["median_ms"] / r["reference"]["device_time"]["median_ms"]
+            r["condition_conservative_device_time_below_time_step"] = r["conservative"]["device_time"]["median_ms"] < r["time_step"]["median_ms"]
+            res[name] = r
+            print(name, json.dumps(r), flush=True)
+    os.makedirs(os.path.dirname(out_path), exist_ok=True)
+    with open(out_path, "w") as f:
+        json.dump(res, f, indent=1)
+    print("wrote", out_path)
+
+
 def tree_commit():
     try:
         return subprocess.run(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], capture_output=True, text=True).stdout.strip() or None
@@ -431,6 +490,8 @@ def main():
     ap.add_argument("--skip-driver", action="store_true", help="--extrude: the library calls only (the run under the profiler)")
     ap.add_argument("--kernel-trace", default=None, help="--extrude: ..._kernel_trace.csv of a rocprofv3 run of this command; adds the kernel rows")
     ap.add_argument("--mesh", action="store_true", help="the rows of the device voxeliser of Shape3D meshes (profiles/mesh_update_cost.json)")
+    ap.add_argument("--voxels", default=None, choices=["conservative"],
+                    help="--mesh: the conservative voxelisation beside the default one (profiles/mesh_update_cost_conservative.json)")
     ap.add_argument("--write-inputs", default=None, help="--mesh: write the mesh and config files of the two grids into this directory and stop")
     ap.add_argument("--kernel-stats", default=None, help="--mesh: ..._kernel_stats.csv of a rocprofv3 run of the driver; adds the kernel rows of --grid")
     ap.add_argument("--grid", default="heart_size_128x160x128", help="--mesh --kernel-stats: the grid the profiled run used")
@@ -440,6 +501,8 @@ def main():
     a = ap.parse_args()
     if a.extrude:
         return main_extrude(a)
+    if a.mesh and a.voxels and not a.kernel_stats and not a.write_inputs:
+        return main_mesh_voxels(a)
     if a.mesh:
         return main_mesh(a)
     import torch
