@@ -78,6 +78,12 @@ SYMBOLS = {
     "fs3d_version": (C.c_char_p, []),
 }
 
+# every symbol include/fs3d_mesh_walls.h declares (the extension header of the mesh entries with wall velocities)
+SYMBOLS_MESH_WALLS = {
+    "fs3d_update_nodes_shape3d_vel": (_i, [_vp] + [_vp] * 6 + [_i, _vp, _i, _d, _d, C.POINTER(_i)]),
+    "fs3d_voxelize_shape3d_vel_dev": (_i, [_vp] + [_vp] * 6 + [_i, _vp, _i, _d, _d] + [_vp] * 7),
+}
+
 _lib = None
 
 
@@ -95,7 +101,7 @@ def load():
             raise RuntimeError("libfs3d_hip.so is not built (%s); run `python -m cmc_fluid_solver_amd.build` "
                                "or __graft_entry__.build()" % LIB_PATH)
         lib = C.CDLL(LIB_PATH)
-        for name, (res, args) in SYMBOLS.items():
+        for name, (res, args) in list(SYMBOLS.items()) + list(SYMBOLS_MESH_WALLS.items()):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
@@ -252,6 +258,33 @@ class Solver:
         self._mesh_voxels(voxels)
         xyz, tri = self._mesh_arrays(g, idx)
         return self._update(self.lib.fs3d_update_nodes_shape3d, *[_p(a) for a in xyz], len(xyz[0]), _p(tri), tri.size // 3, float(baseT))
+
+    @staticmethod
+    def _mesh_velocities(w, nvert):
+        """wx, wy, wz (float32) of vertex velocities w [n, 3]"""
+        w = np.asarray(w, np.float32).reshape(-1, 3)
+        if len(w) != nvert:
+            raise ValueError("one velocity per vertex")
+        return [np.ascontiguousarray(w[:, a]) for a in range(3)]
+
+    def voxelize_shape3d_vel_dev(self, g, w, idx, baseT, wallT, type, bc_vel, bc_temp, vx, vy, vz, T, voxels=None):
+        """voxelize_shape3d_dev with walls that carry the velocity of the mesh -- w [n, 3], what shape3d.Shape3D.subframe_velocity(t)
+        returns -- and the temperature wallT (conservative voxelisation only)."""
+        self._mesh_voxels(voxels)
+        ptrs = self._dev_ptrs("voxelize_shape3d_vel_dev", [type, bc_vel, bc_temp, vx, vy, vz, T])
+        xyz, tri = self._mesh_arrays(g, idx)
+        wv = self._mesh_velocities(w, len(xyz[0]))
+        self._chk(self.lib.fs3d_voxelize_shape3d_vel_dev(self.h, *[_p(a) for a in xyz + wv], len(xyz[0]), _p(tri), tri.size // 3, float(baseT),
+                                                         float(wallT), *ptrs))
+
+    def update_nodes_shape3d_vel(self, g, w, idx, baseT, wallT, voxels=None):
+        """update_nodes_shape3d with walls that carry the velocity of the mesh (w [n, 3]) and the temperature wallT (conservative
+        voxelisation only).  Same contract as update_nodes."""
+        self._mesh_voxels(voxels)
+        xyz, tri = self._mesh_arrays(g, idx)
+        wv = self._mesh_velocities(w, len(xyz[0]))
+        return self._update(self.lib.fs3d_update_nodes_shape3d_vel, *[_p(a) for a in xyz + wv], len(xyz[0]), _p(tri), tri.size // 3, float(baseT),
+                            float(wallT))
 
     def flood_fill_dev(self, type):
         """FloodFill alone on a device array of node types (uint8 torch tensor or raw pointer) of the context's dims, in place."""

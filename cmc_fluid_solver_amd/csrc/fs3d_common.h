@@ -81,13 +81,14 @@ struct fs3d_geom {
     bool ex_bottom_valid = false;           // the bottom table on the device is the one of (ex_dz, ex_depth, ex_depth_var)
     double ex_dz = 0, ex_depth = 0, ex_depth_var = 0;
     // voxelisation of a Shape3D mesh (k_geom_raster_mesh, k_geom_fill_*): allocated by the first call, grown when a mesh has more
-    // vertices or triangles.  One pinned block -- x, y, z of mesh_vcap vertices (float), 3 * mesh_tcap indices (int), the counter
+    // vertices or triangles.  One pinned block -- x, y, z and the velocities wx, wy, wz of mesh_vcap vertices (float), 3 * mesh_tcap indices (int), the counter
     // words on their way back -- and the device copies of its three parts; the indices travel again only when they differ from
     // the ones the pinned block holds
     void *mesh_host = nullptr;
     float *mesh_vert = nullptr;
     int *mesh_idx = nullptr;
     unsigned *mesh_cnt = nullptr;
+    unsigned *mesh_owner = nullptr;         // the entries with wall velocities: per cell the smallest index of the triangles that set it (all ones: none)
     int mesh_vcap = 0, mesh_tcap = 0, mesh_ntri_dev = -1;   // mesh_ntri_dev: triangles of the index list on the device (-1: none)
     int mesh_fill_rounds = 0;               // rounds the last flood fill ran, the closing one without a change included
     // device time of one update (fs3d_last_update_device_ms): event pairs around every batch of launches between two synchronisations;

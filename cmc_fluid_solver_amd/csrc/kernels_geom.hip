@@ -24,6 +24,7 @@
 #include <unordered_map>
 
 #include "fs3d_common.h"
+#include "../../include/fs3d_mesh_walls.h"
 
 // counter words of one update (device, read back once)
 enum { GC_NSEG = 0 /* 0..2 */, GC_NBND = 3, GC_STALE = 4, GC_SHARED = 5, GC_LIST = 6, GC_MISMATCH = 7, GC_WORDS = 8 };
@@ -313,13 +314,13 @@ __device__ __forceinline__ ExNode extrude_node(int k, int c2, float velx, float 
 // Store tail of the two node-writing kernels: the V consecutive cells from l.  wt / wv / wb hold type, bc_vel and bc_temp of cell q
 // in byte q (TYPE false: the type array is not written); vz is 0.  V == 4 (l % 4 == 0, the byte arrays aligned to 4 bytes and the
 // value arrays to 16): one dword per byte array and 16-byte stores for the value arrays (one per array in fp32, two in fp64);
-// V == 1: cell by cell.  Stores are nontemporal: the geometry kernels read these arrays next, but only after the whole grid has
-// been written.
+// V == 1: cell by cell.  az: vz of the V cells where a kernel has one (else vz is 0).  Stores are nontemporal: the geometry kernels
+// read these arrays next, but only after the whole grid has been written.
 template <typename R, int V, bool TYPE>
 __device__ __forceinline__ void store_nodes(long long l, unsigned wt, unsigned wv, unsigned wb, const R (&ax)[V], const R (&ay)[V],
                                             const R (&aT)[V], uint8_t *__restrict__ type, uint8_t *__restrict__ bc_vel,
                                             uint8_t *__restrict__ bc_temp, R *__restrict__ vx, R *__restrict__ vy, R *__restrict__ vz,
-                                            R *__restrict__ T)
+                                            R *__restrict__ T, const R *az = nullptr)
 {
     constexpr int P = 16 / sizeof(R);                  // values per 16-byte store
     typedef R RP __attribute__((ext_vector_type(P)));
@@ -331,7 +332,7 @@ __device__ __forceinline__ void store_nodes(long long l, unsigned wt, unsigned w
         for (int h = 0; h < V; h += P) {
             RP x, y, z, w;
 #pragma unroll
-            for (int q = 0; q < P; q++) { x[q] = ax[h + q]; y[q] = ay[h + q]; z[q] = R(0); w[q] = aT[h + q]; }
+            for (int q = 0; q < P; q++) { x[q] = ax[h + q]; y[q] = ay[h + q]; z[q] = az ? az[h + q] : R(0); w[q] = aT[h + q]; }
             __builtin_nontemporal_store(x, (RP *)(vx + l + h));
             __builtin_nontemporal_store(y, (RP *)(vy + l + h));
             __builtin_nontemporal_store(z, (RP *)(vz + l + h));
@@ -343,7 +344,7 @@ __device__ __forceinline__ void store_nodes(long long l, unsigned wt, unsigned w
         __builtin_nontemporal_store((uint8_t)wb, bc_temp + l);
         __builtin_nontemporal_store(ax[0], vx + l);
         __builtin_nontemporal_store(ay[0], vy + l);
-        __builtin_nontemporal_store(R(0), vz + l);
+        __builtin_nontemporal_store(az ? az[0] : R(0), vz + l);
         __builtin_nontemporal_store(aT[0], T + l);
     }
 }
@@ -509,6 +510,9 @@ __global__ void __launch_bounds__(64) k_geom_raster_mesh(const float *__restrict
 // a degenerate triangle has no plane and walks the box's depth, along its smallest extent.  The only write is a byte store of
 // NODE_BOUND into an array preset to NODE_IN: idempotent, so order is free and no atomics are needed.  Every index lies inside
 // the clipped box; there is no scan line, no guard and no flag word.
+// OWNER (the entries with wall velocities): every store of NODE_BOUND comes with an integer atomicMin of the triangle's index into
+// the cell's word of `owner`, preset to all ones -- the owner of a wall cell is the smallest index of the triangles that set it
+// (shape3d.py), a minimum over a set: nothing depends on the order of arrival, and no float atomics take part.
 #define VOXEL_SLACK 5.8207660913467407e-11              // 2^-34
 #define VOXEL_DEGENERATE 5.9604644775390625e-08        // 2^-24
 #define VOXEL_COORD_MAX 4096.0f
@@ -518,8 +522,9 @@ struct VoxEdge { double wa, wb, c; };
 __device__ __forceinline__ bool vox_pass(const VoxEdge &e, double x, double y) { return (e.wa * x + e.wb * y) + e.c >= 0.0; }
 __device__ __forceinline__ double vox_sel(int c, double x, double y, double z) { return c == 0 ? x : (c == 1 ? y : z); }
 
+template <bool OWNER>
 __global__ void __launch_bounds__(64) k_geom_voxel_mesh(const float *__restrict__ vx, const float *__restrict__ vy, const float *__restrict__ vz,
-                                                         const int *__restrict__ tri, int dimx, int dimy, int dimz, uint8_t *type)
+                                                         const int *__restrict__ tri, int dimx, int dimy, int dimz, uint8_t *type, unsigned *owner)
 {
     const int lane = threadIdx.x;
     const int iv[3] = {tri[3 * blockIdx.x], tri[3 * blockIdx.x + 1], tri[3 * blockIdx.x + 2]};
@@ -624,6 +629,7 @@ __global__ void __launch_bounds__(64) k_geom_voxel_mesh(const float *__restrict_
                 if (!(s + c1 >= 0.0) || !(s + c2 <= 0.0)) continue;
             }
             colp[k * sd] = FS3D_NODE_BOUND;
+            if constexpr (OWNER) atomicMin(owner + ((colp - type) + k * sd), (unsigned)blockIdx.x);      // the same cell of the same grid
         }
     }
 }
@@ -732,6 +738,82 @@ __global__ void __launch_bounds__(256) k_geom_mesh_nodes(const uint8_t *__restri
     store_nodes<R, V, false>(l, 0u, noslip, noslip, a0, a0, aT, nullptr, bc_vel, bc_temp, vx, vy, vz, T);
 }
 
+// ---- walls that carry the mesh's velocity (fs3d_*_shape3d_vel) ---------------------------------------------------------------------
+// wall_weights / wall_velocity of cmc_fluid_solver_amd/shape3d.py (where the rule stands) and WallWeights / WallVelocity of
+// host/Shape3D.h: float64 from the fp32 vertices, every operation theirs, in their order, rounded after each one.
+struct D3 { double x, y, z; };
+__device__ __forceinline__ D3 d3_sub(D3 a, D3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
+__device__ __forceinline__ D3 d3_cross(D3 a, D3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
+__device__ __forceinline__ double d3_dot(D3 a, D3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
+
+// the velocity of the triangle (q0, q1, q2) -- local to the cell's corner -- with vertex velocities W0, W1, W2 at the cell's centre
+__device__ __forceinline__ D3 wall_velocity(D3 q0, D3 q1, D3 q2, D3 W0, D3 W1, D3 W2)
+{
+    const D3 c = {0.5, 0.5, 0.5};
+    const D3 e0 = d3_sub(q1, q0), e1 = d3_sub(q2, q0), r = d3_sub(c, q0);
+    const D3 n = d3_cross(e0, e1);
+    const double nn = d3_dot(n, n);
+    double w0, w1, w2;
+    if (nn >= VOXEL_DEGENERATE) {
+        const double b1 = d3_dot(d3_cross(r, e1), n) / nn, b2 = d3_dot(d3_cross(e0, r), n) / nn, b0 = (1.0 - b1) - b2;
+        const double m0 = fmax(b0, 0.0), m1 = fmax(b1, 0.0), m2 = fmax(b2, 0.0);
+        const double s = (m0 + m1) + m2;
+        w0 = m0 / s; w1 = m1 / s; w2 = m2 / s;
+    } else {                                               // the longest edge, the first of equals
+        const D3 d0 = e0, d1 = d3_sub(q2, q1), d2 = d3_sub(q0, q2);
+        const double l0 = d3_dot(d0, d0), l1 = d3_dot(d1, d1), l2 = d3_dot(d2, d2);
+        int best = 0;
+        double l = l0;
+        if (l1 > l) { best = 1; l = l1; }
+        if (l2 > l) { best = 2; l = l2; }
+        const D3 a = best == 0 ? q0 : (best == 1 ? q1 : q2), d = best == 0 ? d0 : (best == 1 ? d1 : d2);
+        double t = 0.0;
+        if (l > 0.0) t = fmin(fmax(d3_dot(d3_sub(c, a), d) / l, 0.0), 1.0);
+        const double u = 1.0 - t;                          // on the edge's first end, t on its second, 0 on the third vertex
+        w0 = best == 0 ? u : (best == 2 ? t : 0.0);
+        w1 = best == 1 ? u : (best == 0 ? t : 0.0);
+        w2 = best == 2 ? u : (best == 1 ? t : 0.0);
+    }
+    return {(w0 * W0.x + w1 * W1.x) + w2 * W2.x, (w0 * W0.y + w1 * W1.y) + w2 * W2.y, (w0 * W0.z + w1 * W1.z) + w2 * W2.z};
+}
+
+// k_geom_mesh_nodes with walls that move: a NODE_BOUND cell reads its owner (k_geom_voxel_mesh<true>), gathers that triangle's
+// three vertices and three velocities, evaluates the rule in float64 and stores v rounded once to R and T = wallT; every other
+// cell as there.  The same two store shapes.  Wall cells are a surface: the gather is a small part of the seven arrays' traffic.
+// A NODE_BOUND cell without an owner below ntri cannot come from the voxel kernel; it reads nothing and stays at rest.
+template <typename R, int V>
+__global__ void __launch_bounds__(256) k_geom_mesh_nodes_vel(const uint8_t *__restrict__ type, const unsigned *__restrict__ owner,
+                                                              const float *__restrict__ px, const float *__restrict__ py, const float *__restrict__ pz,
+                                                              const float *__restrict__ wx, const float *__restrict__ wy, const float *__restrict__ wz,
+                                                              const int *__restrict__ tri, unsigned ntri, long long ncell, int dimy, int dimz,
+                                                              R baseT, R wallT, uint8_t *__restrict__ bc_vel, uint8_t *__restrict__ bc_temp,
+                                                              R *__restrict__ vx, R *__restrict__ vy, R *__restrict__ vz, R *__restrict__ T)
+{
+    const long long l = ((long long)blockIdx.x * 256 + threadIdx.x) * V;
+    if (l >= ncell) return;                                            // V == 4: ncell % 4 == 0
+    unsigned w;
+    if constexpr (V == 4) w = *(const unsigned *)(type + l); else w = type[l];
+    R ax[V], ay[V], az[V], aT[V];
+#pragma unroll
+    for (int q = 0; q < V; q++) {
+        const bool wall = ((w >> (8 * q)) & 0xFF) == FS3D_NODE_BOUND;
+        ax[q] = R(0); ay[q] = R(0); az[q] = R(0); aT[q] = wall ? wallT : baseT;
+        if (!wall) continue;
+        const unsigned t = owner[l + q];
+        if (t >= ntri) continue;
+        const long long cell = l + q, col = cell / dimz;
+        const double ck = (double)(int)(cell - col * dimz), cj = (double)(int)(col % dimy), ci = (double)(int)(col / dimy);
+        const int i0 = tri[3 * (size_t)t], i1 = tri[3 * (size_t)t + 1], i2 = tri[3 * (size_t)t + 2];      // checked by mesh_check: inside the vertex list
+        const D3 q0 = {(double)px[i0] - ci, (double)py[i0] - cj, (double)pz[i0] - ck}, q1 = {(double)px[i1] - ci, (double)py[i1] - cj, (double)pz[i1] - ck},
+                 q2 = {(double)px[i2] - ci, (double)py[i2] - cj, (double)pz[i2] - ck};
+        const D3 u = wall_velocity(q0, q1, q2, {(double)wx[i0], (double)wy[i0], (double)wz[i0]}, {(double)wx[i1], (double)wy[i1], (double)wz[i1]},
+                                   {(double)wx[i2], (double)wy[i2], (double)wz[i2]});
+        ax[q] = (R)u.x; ay[q] = (R)u.y; az[q] = (R)u.z;
+    }
+    constexpr unsigned noslip = 0x01010101u * FS3D_BC_NOSLIP;          // in every byte
+    store_nodes<R, V, false>(l, 0u, noslip, noslip, ax, ay, aT, nullptr, bc_vel, bc_temp, vx, vy, vz, T, az);
+}
+
 // ---------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------
@@ -812,6 +894,7 @@ void fs3d_geom_destroy(fs3d_ctx *c)
     if (g.mesh_vert) hipFree(g.mesh_vert);
     if (g.mesh_idx) hipFree(g.mesh_idx);
     if (g.mesh_cnt) hipFree(g.mesh_cnt);
+    if (g.mesh_owner) hipFree(g.mesh_owner);
 }
 
 // the buffers an update keeps: allocated by the first one
@@ -1059,28 +1142,33 @@ static fs3d_status extrude_launch(fs3d_ctx *c, const ExtrudeIn &in, const NodeAr
 }
 
 // ---- voxelisation of a Shape3D mesh ---------------------------------------------------------------------------------------------
-struct MeshIn { const float *x, *y, *z; int nvert; const int *tri; int ntri; double baseT; };
+// vel: an entry with wall velocities -- wx, wy, wz per vertex and the walls' temperature (else null and 0)
+struct MeshIn { const float *x, *y, *z; int nvert; const int *tri; int ntri; double baseT; bool vel; const float *wx, *wy, *wz; double wallT; };
+#define MESH_COLS 6                                    // columns of mesh_vcap floats in the pinned and the device block: x, y, z, wx, wy, wz
 
 #define MESH_FILL_BATCH 2                              // rounds of the flood fill between two looks at their counters
 enum { MC_FLAG = 0, MC_ROUND = 1, MC_WORDS = 1 + MESH_FILL_BATCH };
 
 static inline float *mesh_host_vert(const fs3d_geom &g) { return (float *)g.mesh_host; }
-static inline int *mesh_host_idx(const fs3d_geom &g) { return (int *)((float *)g.mesh_host + 3 * (size_t)g.mesh_vcap); }
+static inline int *mesh_host_idx(const fs3d_geom &g) { return (int *)((float *)g.mesh_host + MESH_COLS * (size_t)g.mesh_vcap); }
 static inline unsigned *mesh_host_cnt(const fs3d_geom &g) { return (unsigned *)(mesh_host_idx(g) + 3 * (size_t)g.mesh_tcap); }
 
-// the buffers of the mesh paths, for at least nvert vertices and ntri triangles: allocated by the first call, grown by a larger mesh
-static fs3d_status mesh_prepare(fs3d_ctx *c, int nvert, int ntri)
+// the buffers of the mesh paths, for at least nvert vertices and ntri triangles: allocated by the first call, grown by a larger mesh.
+// The velocity columns have their room beside the vertex columns from the start (the number of allocations is the same with and
+// without them); the owner array, 4 bytes per cell, is allocated by the first call of an entry with wall velocities.
+static fs3d_status mesh_prepare(fs3d_ctx *c, int nvert, int ntri, bool vel = false)
 {
     fs3d_geom &g = c->geom;
     HIPCHK(c, hipSetDevice(c->device));
     if (!g.mesh_cnt) GMALLOC(c, &g.mesh_cnt, MC_WORDS * sizeof(unsigned));
+    if (vel && !g.mesh_owner) GMALLOC(c, &g.mesh_owner, (size_t)c->ncell * sizeof(unsigned));
     if (g.mesh_host && nvert <= g.mesh_vcap && ntri <= g.mesh_tcap) return FS3D_OK;
     if (g.mesh_host) { hipHostFree(g.mesh_host); g.mesh_host = nullptr; }
     gfree(c, g.mesh_vert); g.mesh_vert = nullptr;
     gfree(c, g.mesh_idx); g.mesh_idx = nullptr;
     g.mesh_vcap = std::max(std::max(nvert, g.mesh_vcap), 1); g.mesh_tcap = std::max(std::max(ntri, g.mesh_tcap), 1); g.mesh_ntri_dev = -1;
-    HIPCHK(c, hipHostMalloc(&g.mesh_host, (3 * (size_t)g.mesh_vcap + 3 * (size_t)g.mesh_tcap) * 4 + MC_WORDS * sizeof(unsigned), hipHostMallocDefault));
-    GMALLOC(c, &g.mesh_vert, 3 * (size_t)g.mesh_vcap * sizeof(float));
+    HIPCHK(c, hipHostMalloc(&g.mesh_host, (MESH_COLS * (size_t)g.mesh_vcap + 3 * (size_t)g.mesh_tcap) * 4 + MC_WORDS * sizeof(unsigned), hipHostMallocDefault));
+    GMALLOC(c, &g.mesh_vert, MESH_COLS * (size_t)g.mesh_vcap * sizeof(float));
     GMALLOC(c, &g.mesh_idx, 3 * (size_t)g.mesh_tcap * sizeof(int));
     return FS3D_OK;
 }
@@ -1101,9 +1189,19 @@ static fs3d_status mesh_check(fs3d_ctx *c, const MeshIn &in, const char *name, b
                 return fail(c, FS3D_ERR_INVALID, std::string(name) + (conservative
                              ? ": a vertex coordinate is not finite or exceeds 4096 grid cells in magnitude (the bound of the conservative voxelisation's slack)"
                              : ": a vertex coordinate is not finite or exceeds 65536 grid cells in magnitude"));
-    GTRY(mesh_prepare(c, in.nvert, in.ntri));
+    if (in.vel) {
+        if (!std::isfinite((float)in.wallT)) return fail(c, FS3D_ERR_INVALID, std::string(name) + ": the wall temperature is not finite (as a float, like baseT)");
+        for (const float *a : {in.wx, in.wy, in.wz})
+            for (int q = 0; q < in.nvert; q++)
+                if (!std::isfinite(a[q])) return fail(c, FS3D_ERR_INVALID, std::string(name) + ": a vertex velocity is not finite");
+    }
+    GTRY(mesh_prepare(c, in.nvert, in.ntri, in.vel));
     float *hv = mesh_host_vert(g);
     memcpy(hv, in.x, 4 * (size_t)in.nvert); memcpy(hv + g.mesh_vcap, in.y, 4 * (size_t)in.nvert); memcpy(hv + 2 * (size_t)g.mesh_vcap, in.z, 4 * (size_t)in.nvert);
+    if (in.vel) {
+        memcpy(hv + 3 * (size_t)g.mesh_vcap, in.wx, 4 * (size_t)in.nvert); memcpy(hv + 4 * (size_t)g.mesh_vcap, in.wy, 4 * (size_t)in.nvert);
+        memcpy(hv + 5 * (size_t)g.mesh_vcap, in.wz, 4 * (size_t)in.nvert);
+    }
     *new_idx = g.mesh_ntri_dev != in.ntri || memcmp(mesh_host_idx(g), in.tri, 12 * (size_t)in.ntri) != 0;
     if (*new_idx) memcpy(mesh_host_idx(g), in.tri, 12 * (size_t)in.ntri);
     return FS3D_OK;
@@ -1150,7 +1248,7 @@ template <typename R>
 static fs3d_status mesh_launch(fs3d_ctx *c, const MeshIn &in, bool new_idx, const char *name, const NodeArrays &a)
 {
     fs3d_geom &g = c->geom;
-    HIPCHK(c, hipMemcpyAsync(g.mesh_vert, g.mesh_host, 3 * (size_t)g.mesh_vcap * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(g.mesh_vert, g.mesh_host, (in.vel ? MESH_COLS : 3) * (size_t)g.mesh_vcap * sizeof(float), hipMemcpyHostToDevice, c->stream));
     if (new_idx) {
         g.mesh_ntri_dev = -1;
         HIPCHK(c, hipMemcpyAsync(g.mesh_idx, mesh_host_idx(g), 12 * (size_t)std::max(in.ntri, 1), hipMemcpyHostToDevice, c->stream));
@@ -1159,9 +1257,13 @@ static fs3d_status mesh_launch(fs3d_ctx *c, const MeshIn &in, bool new_idx, cons
     HIPCHK(c, hipMemsetAsync(a.type, FS3D_NODE_IN, (size_t)c->ncell, c->stream));
     HIPCHK(c, hipMemsetAsync(g.mesh_cnt, 0, sizeof(unsigned), c->stream));
     const bool conservative = c->opt_mesh_voxels == 1;      // (mesh_check admitted the coordinates for this mode)
-    if (in.ntri && conservative)
-        hipLaunchKernelGGL(k_geom_voxel_mesh, dim3((unsigned)in.ntri), dim3(64), 0, c->stream, g.mesh_vert, g.mesh_vert + g.mesh_vcap,
-                           g.mesh_vert + 2 * (size_t)g.mesh_vcap, g.mesh_idx, c->dimx, c->dimy, c->dimz, a.type);
+    if (in.vel) HIPCHK(c, hipMemsetAsync(g.mesh_owner, 0xFF, (size_t)c->ncell * sizeof(unsigned), c->stream));      // (the entries admit conservative only)
+    if (in.ntri && in.vel)
+        hipLaunchKernelGGL(k_geom_voxel_mesh<true>, dim3((unsigned)in.ntri), dim3(64), 0, c->stream, g.mesh_vert, g.mesh_vert + g.mesh_vcap,
+                           g.mesh_vert + 2 * (size_t)g.mesh_vcap, g.mesh_idx, c->dimx, c->dimy, c->dimz, a.type, g.mesh_owner);
+    else if (in.ntri && conservative)
+        hipLaunchKernelGGL(k_geom_voxel_mesh<false>, dim3((unsigned)in.ntri), dim3(64), 0, c->stream, g.mesh_vert, g.mesh_vert + g.mesh_vcap,
+                           g.mesh_vert + 2 * (size_t)g.mesh_vcap, g.mesh_idx, c->dimx, c->dimy, c->dimz, a.type, (unsigned *)nullptr);
     else if (in.ntri)
         hipLaunchKernelGGL(k_geom_raster_mesh, dim3((unsigned)in.ntri), dim3(64), 0, c->stream, g.mesh_vert, g.mesh_vert + g.mesh_vcap,
                            g.mesh_vert + 2 * (size_t)g.mesh_vcap, g.mesh_idx, c->dimx, c->dimy, c->dimz, a.type, g.mesh_cnt + MC_FLAG);
@@ -1169,6 +1271,16 @@ static fs3d_status mesh_launch(fs3d_ctx *c, const MeshIn &in, bool new_idx, cons
     GTRY(mesh_fill(c, a.type, !conservative, name));        // the conservative kernel has no flag word: it stays zero
     gev_begin(c);
     const bool vec = a.vec4(c->dimz);
+    if (in.vel) {
+        auto kv = vec ? k_geom_mesh_nodes_vel<R, 4> : k_geom_mesh_nodes_vel<R, 1>;
+        const float *v = g.mesh_vert;
+        const size_t cap = (size_t)g.mesh_vcap;
+        hipLaunchKernelGGL(kv, dim3(grid_for(vec ? c->ncell / 4 : c->ncell, 1 << 30)), dim3(256), 0, c->stream, a.type, g.mesh_owner, v, v + cap,
+                           v + 2 * cap, v + 3 * cap, v + 4 * cap, v + 5 * cap, g.mesh_idx, (unsigned)in.ntri, c->ncell, c->dimy, c->dimz,
+                           (R)(float)in.baseT, (R)(float)in.wallT, a.bc_vel, a.bc_temp, (R *)a.v[0], (R *)a.v[1], (R *)a.v[2], (R *)a.v[3]);
+        HIPCHK(c, hipGetLastError());
+        return FS3D_OK;
+    }
     auto kern = vec ? k_geom_mesh_nodes<R, 4> : k_geom_mesh_nodes<R, 1>;
     hipLaunchKernelGGL(kern, dim3(grid_for(vec ? c->ncell / 4 : c->ncell, 1 << 30)), dim3(256), 0, c->stream, a.type, c->ncell, (R)(float)in.baseT,
                        a.bc_vel, a.bc_temp, (R *)a.v[0], (R *)a.v[1], (R *)a.v[2], (R *)a.v[3]);
@@ -1298,7 +1410,7 @@ extern "C" fs3d_status fs3d_update_nodes_shape3d(fs3d_ctx *c, const float *x, co
     GTRY(update_refuse(c, name, !x || !y || !z || !tri));
     const geom_clock t0 = std::chrono::steady_clock::now();
     HIPCHK(c, hipSetDevice(c->device));
-    const MeshIn in = {x, y, z, nvert, tri, ntri, baseT};
+    const MeshIn in = {x, y, z, nvert, tri, ntri, baseT, false, nullptr, nullptr, nullptr, 0.0};
     bool new_idx = false;
     GTRY(mesh_check(c, in, name, &new_idx));
     GTRY(update_begin(c, true));
@@ -1314,7 +1426,53 @@ extern "C" fs3d_status fs3d_voxelize_shape3d_dev(fs3d_ctx *c, const float *x, co
     const char *name = "fs3d_voxelize_shape3d_dev";
     const NodeArrays out = {type_out, bc_vel_out, bc_temp_out, {vx_out, vy_out, vz_out, T_out}};
     GTRY(geom_refuse(c, name, !x || !y || !z || !tri || out.any_null(), "the voxelisation is"));
-    const MeshIn in = {x, y, z, nvert, tri, ntri, baseT};
+    const MeshIn in = {x, y, z, nvert, tri, ntri, baseT, false, nullptr, nullptr, nullptr, 0.0};
+    bool new_idx = false;
+    GTRY(mesh_check(c, in, name, &new_idx));
+    gev_reset(c);                                        // (no update: its device time is not reported)
+    const fs3d_status st = c->prec == FS3D_F32 ? mesh_launch<float>(c, in, new_idx, name, out) : mesh_launch<double>(c, in, new_idx, name, out);
+    const hipError_t e = hipStreamSynchronize(c->stream);
+    gev_reset(c);
+    if (st) return st;
+    HIPCHK(c, e);
+    return FS3D_OK;
+}
+
+// the refusal the two entries with wall velocities add: the owner of a wall cell is defined by the conservative overlap test
+static fs3d_status vel_refuse(fs3d_ctx *c, const char *name)
+{
+    if (c->opt_mesh_voxels != 1)
+        return fail(c, FS3D_ERR_INVALID, std::string(name) + ": wall velocities need the conservative voxelisation (FS3D_OPT_MESH_VOXELS = 1)");
+    return FS3D_OK;
+}
+
+extern "C" fs3d_status fs3d_update_nodes_shape3d_vel(fs3d_ctx *c, const float *x, const float *y, const float *z, const float *wx, const float *wy,
+                                                     const float *wz, int nvert, const int *tri, int ntri, double baseT, double wallT, int n_seg_out[3])
+{
+    const char *name = "fs3d_update_nodes_shape3d_vel";
+    GTRY(update_refuse(c, name, !x || !y || !z || !wx || !wy || !wz || !tri));
+    GTRY(vel_refuse(c, name));
+    const geom_clock t0 = std::chrono::steady_clock::now();
+    HIPCHK(c, hipSetDevice(c->device));
+    const MeshIn in = {x, y, z, nvert, tri, ntri, baseT, true, wx, wy, wz, wallT};
+    bool new_idx = false;
+    GTRY(mesh_check(c, in, name, &new_idx));
+    GTRY(update_begin(c, true));
+    const NodeArrays own = geom_own_arrays(c);
+    const fs3d_status st = c->prec == FS3D_F32 ? mesh_launch<float>(c, in, new_idx, name, own) : mesh_launch<double>(c, in, new_idx, name, own);
+    return update_end(c, t0, st, own.type, own.bc_vel, own.bc_temp, n_seg_out);
+}
+
+extern "C" fs3d_status fs3d_voxelize_shape3d_vel_dev(fs3d_ctx *c, const float *x, const float *y, const float *z, const float *wx, const float *wy,
+                                                     const float *wz, int nvert, const int *tri, int ntri, double baseT, double wallT,
+                                                     uint8_t *type_out, uint8_t *bc_vel_out, uint8_t *bc_temp_out, void *vx_out, void *vy_out,
+                                                     void *vz_out, void *T_out)
+{
+    const char *name = "fs3d_voxelize_shape3d_vel_dev";
+    const NodeArrays out = {type_out, bc_vel_out, bc_temp_out, {vx_out, vy_out, vz_out, T_out}};
+    GTRY(geom_refuse(c, name, !x || !y || !z || !wx || !wy || !wz || !tri || out.any_null(), "the voxelisation is"));
+    GTRY(vel_refuse(c, name));
+    const MeshIn in = {x, y, z, nvert, tri, ntri, baseT, true, wx, wy, wz, wallT};
     bool new_idx = false;
     GTRY(mesh_check(c, in, name, &new_idx));
     gev_reset(c);                                        // (no update: its device time is not reported)

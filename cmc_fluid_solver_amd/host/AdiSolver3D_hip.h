@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/fs3d.h"
+#include "../../include/fs3d_mesh_walls.h"
 
 namespace fs3d {
 
@@ -116,6 +117,18 @@ public:
         static const int none = 0;
         chk(fs3d_update_nodes_shape3d(ctx_, x.data(), y.data(), z.data(), (int)x.size(), idx.empty() ? &none : idx.data(), (int)(idx.size() / 3),
                                       grid_->baseT, numSegs));
+    }
+    // The same with walls that carry the mesh's velocity and a temperature (fs3d_update_nodes_shape3d_vel; conservative voxelisation
+    // only: SetMeshVoxels(1) first): wx, wy, wz the vertex velocities of the sub-frame (Shape3D::SubFrameVelocity), wallT the
+    // temperature of the NODE_BOUND cells.  Zero velocities and wallT = 0 give the grid of the overload above.
+    void UpdateGridShape3D(const std::vector<float> &x, const std::vector<float> &y, const std::vector<float> &z, const std::vector<float> &wx,
+                           const std::vector<float> &wy, const std::vector<float> &wz, const std::vector<int> &idx, double wallT)
+    {
+        if (x.size() != y.size() || x.size() != z.size()) throw std::runtime_error("UpdateGridShape3D: x, y, z differ in length");
+        if (x.size() != wx.size() || x.size() != wy.size() || x.size() != wz.size()) throw std::runtime_error("UpdateGridShape3D: one velocity per vertex");
+        static const int none = 0;
+        chk(fs3d_update_nodes_shape3d_vel(ctx_, x.data(), y.data(), z.data(), wx.data(), wy.data(), wz.data(), (int)x.size(),
+                                          idx.empty() ? &none : idx.data(), (int)(idx.size() / 3), grid_->baseT, wallT, numSegs));
     }
     // FS3D_OPT_MESH_VOXELS for the UpdateGridShape3D calls that follow: 0 the reference's rasteriser, 1 the conservative
     // voxelisation (Shape3D::voxels of host/Shape3D.h has the same values)

@@ -8,6 +8,8 @@
 // cycle length of a Shape3D run is Config::frame_time and GetFrame is always 0 (Grid3D.cpp:303-336).
 // Shape3D::voxels = 1 replaces the rasteriser (not the fill) by a conservative voxelisation, which the reference does not have: see
 // VoxelTriangle below and the derivation in cmc_fluid_solver_amd/shape3d.py.
+// Shape3D::wall_velocity (conservative voxelisation only) gives the NODE_BOUND cells the velocity of the mesh, which the reference
+// reads per vertex, interpolates (Grid3D.cpp:915) and then drops in RasterPolygon / RasterLine: see WallWeights below.
 // Deviations, on purpose (a third one, of the moving loop, stands at FillShape3DNodes below):
 //   * NODE_BOUND cells: the reference sets only their type; bc_vel / bc_temp keep whatever `new Node[]` left there
 //     (Grid3D.cpp:351-371, 818-838: SetData runs for NODE_IN / NODE_OUT only).  Here they read as zero-filled memory:
@@ -33,7 +35,8 @@
 namespace fs3d {
 
 struct Shape3DFrame {
-    std::vector<float> x, y, z, vx, vy, vz;   // vertices (physical, then grid coordinates) and their velocities (read, unused by the rasteriser)
+    std::vector<float> x, y, z, vx, vy, vz;   // vertices (physical, then grid coordinates) and their velocities (the file's columns; unused by the rasteriser)
+    std::vector<float> px, py, pz;            // the physical vertices, kept: the `motion` velocities are their differences
     std::vector<int> idx;                     // 3 per triangle
     double duration = 1.0 / 75;               // Grid3D.cpp:413
 };
@@ -50,6 +53,13 @@ struct Shape3D {
     // NODE_BOUND iff a triangle overlaps the cell's closed unit box, so the shell of a closed mesh is closed for the flood fill.
     // Set it before Load; Prepare(t) honours it.  Same value as FS3D_OPT_MESH_VOXELS.
     int voxels = 0;
+    // What the NODE_BOUND cells carry.  0: v = 0 (the reference's run).  1 (`motion`) / 2 (`file`): the velocity of the mesh at the
+    // projection of the cell's centre onto the cell's owner triangle (WallWeights below), from the vertex velocities
+    // SubFrameVelocity gives for that source.  Needs voxels = 1.  Set it before Load; Prepare(t) honours it and keeps `owner` and
+    // `cur`, which FillShape3DNodes reads.
+    int wall_velocity = 0;
+    std::vector<int> owner;                   // per cell: the smallest index of the triangles whose conservative test sets it, -1 off the walls
+    Shape3DFrame cur;                         // the sub-frame of the last Prepare: vertices in grid coordinates, velocities, triangles
     static constexpr double VOXEL_SLACK = 5.8207660913467407e-11;        // 2^-34: the derivation stands in cmc_fluid_solver_amd/shape3d.py
     static constexpr double VOXEL_DEGENERATE = 5.9604644775390625e-08;   // 2^-24
     static constexpr float VOXEL_COORD_MAX = 4096.0f;
@@ -73,6 +83,7 @@ struct Shape3D {
             for (int k = 0; k < nv; k++) {
                 const float px = num(next()), py = num(next()), pz = num(next());
                 fr.x.push_back(px * GRID_SCALE_FACTOR); fr.y.push_back(py * GRID_SCALE_FACTOR); fr.z.push_back(pz * GRID_SCALE_FACTOR);
+                fr.px.push_back(fr.x.back()); fr.py.push_back(fr.y.back()); fr.pz.push_back(fr.z.back());
                 fr.vx.push_back(num(next())); fr.vy.push_back(num(next())); fr.vz.push_back(num(next()));
             }
             const int nt = std::atoi(next().c_str());
@@ -125,14 +136,10 @@ struct Shape3D {
     // fs3d_update_nodes_shape3d takes these vertices and frames[frame].idx
     size_t SubFrame(double time, std::vector<float> &x, std::vector<float> &y, std::vector<float> &z) const
     {
-        const size_t nf = frames.size();
-        std::vector<double> a(nf + 1, 0.0);
-        for (size_t i = 1; i <= nf; i++) a[i] = a[i - 1] + frames[i - 1].duration;
-        const double r = std::fmod(time, a[nf]);
-        size_t frame = 0;
-        for (size_t i = 1; i < nf; i++) if (a[i] < r) frame = i;
-        const float s = (float)((r - a[frame]) / (a[frame + 1] - a[frame])), is = 1 - s;
-        const Shape3DFrame &f0 = frames[frame], &f1 = frames[(frame + 1) % nf];
+        float s;
+        const size_t frame = Locate(time, s);
+        const float is = 1 - s;
+        const Shape3DFrame &f0 = frames[frame], &f1 = frames[(frame + 1) % frames.size()];
         const size_t nv = f0.x.size();
         x.resize(nv); y.resize(nv); z.resize(nv);
         for (size_t k = 0; k < nv; k++) {
@@ -141,12 +148,92 @@ struct Shape3D {
         return frame;
     }
 
-    // Grid3D::Prepare3D_Shape(time): SubFrame + Build
+    // The vertex velocities of the mesh at `time`, in the solver's velocity units, beside SubFrame(time); source as wall_velocity.
+    // 1 (`motion`): (P[f+1] - P[f]) (1 / Duration[f]) on the physical vertices, fp32 in the order of Shape2D's border velocities;
+    //   f is SubFrame's frame and f + 1 wraps as there.  The vertices move linearly over a frame interval, so the velocity is
+    //   constant over it; a one-frame mesh is at rest.
+    // 2 (`file`): the file's velocity columns as the reference interpolates them (Grid3D.cpp:915), W[f] (1 - s) + W[f+1] s, taken as
+    //   they are (their unit is not documented).
+    void SubFrameVelocity(double time, int source, std::vector<float> &wx, std::vector<float> &wy, std::vector<float> &wz) const
+    {
+        if (source != 1 && source != 2) throw std::runtime_error("Shape3D: a velocity source is 1 (motion) or 2 (file)");
+        float s;
+        const size_t frame = Locate(time, s);
+        const float is = 1 - s;
+        const Shape3DFrame &f0 = frames[frame], &f1 = frames[(frame + 1) % frames.size()];
+        const size_t nv = f0.x.size();
+        wx.resize(nv); wy.resize(nv); wz.resize(nv);
+        const float m = (float)(1 / (double)f0.duration);
+        for (size_t k = 0; k < nv; k++) {
+            if (source == 1) { wx[k] = fl(fl(f1.px[k] - f0.px[k]) * m); wy[k] = fl(fl(f1.py[k] - f0.py[k]) * m); wz[k] = fl(fl(f1.pz[k] - f0.pz[k]) * m); }
+            else { wx[k] = mix(f0.vx[k], is, f1.vx[k], s); wy[k] = mix(f0.vy[k], is, f1.vy[k], s); wz[k] = mix(f0.vz[k], is, f1.vz[k], s); }
+        }
+    }
+
+    // Grid3D::Prepare3D_Shape(time): SubFrame + Build (and the velocities of `time` where the walls carry them)
     void Prepare(double time)
     {
-        Shape3DFrame sub;
-        sub.idx = frames[SubFrame(time, sub.x, sub.y, sub.z)].idx;
-        Build(sub);
+        cur.idx = frames[SubFrame(time, cur.x, cur.y, cur.z)].idx;
+        if (wall_velocity) SubFrameVelocity(time, wall_velocity, cur.vx, cur.vy, cur.vz);
+        Build(cur);
+    }
+
+    // ---- wall velocities: wall_weights / wall_velocity of the twin, operation for operation -----------------------------------
+    // The weights of the triangle p at the centre of cell (i, j, k).  float64 from the fp32 vertices, every operation rounded once.
+    // q_i = (double)v_i - (i, j, k), c = (1/2, 1/2, 1/2), e0 = q1 - q0, e1 = q2 - q0, r = c - q0, n = e0 x e1, nn = (nx nx + ny ny) + nz nz.
+    // nn >= VOXEL_DEGENERATE: b1 = ((r x e1) . n) / nn, b2 = ((e0 x r) . n) / nn, b0 = (1 - b1) - b2 (the barycentric coordinates of
+    // the centre's orthogonal projection onto the plane), m_i = max(b_i, 0), w_i = m_i / ((m0 + m1) + m2).  Else the longest of the
+    // edges (0,1), (1,2), (2,0) by squared length, the first of equals: t = the parameter of the centre's projection onto it
+    // clamped to [0, 1] (0 for a zero length), 1 - t and t on its ends, 0 on the third vertex.
+    // The owner of a cell -- the smallest index of the triangles whose conservative test sets it -- is arbitrary where several
+    // overlap the cell; the velocity field of a mesh is continuous across shared vertices, so another choice moves the value by
+    // the velocity gradient times a cell.
+    static void WallWeights(const float *const p[3], int i, int j, int k, double w[3])
+    {
+        const int ijk[3] = {i, j, k};
+        double q[3][3], e0[3], e1[3], r[3], n[3];
+        for (int v = 0; v < 3; v++)
+            for (int c = 0; c < 3; c++) q[v][c] = fd((double)p[v][c] - (double)ijk[c]);
+        for (int c = 0; c < 3; c++) { e0[c] = fd(q[1][c] - q[0][c]); e1[c] = fd(q[2][c] - q[0][c]); r[c] = fd(0.5 - q[0][c]); }
+        cross(e0, e1, n);
+        const double nn = dot(n, n);
+        if (nn >= VOXEL_DEGENERATE) {
+            double a[3], b[3];
+            cross(r, e1, a); cross(e0, r, b);
+            const double b1 = fd(dot(a, n) / nn), b2 = fd(dot(b, n) / nn), b0 = fd(fd(1.0 - b1) - b2);
+            const double m0 = std::max(b0, 0.0), m1 = std::max(b1, 0.0), m2 = std::max(b2, 0.0);
+            const double s = fd(fd(m0 + m1) + m2);
+            w[0] = fd(m0 / s); w[1] = fd(m1 / s); w[2] = fd(m2 / s);
+            return;
+        }
+        double d[3][3], l[3];
+        for (int e = 0; e < 3; e++) {
+            for (int c = 0; c < 3; c++) d[e][c] = fd(q[(e + 1) % 3][c] - q[e][c]);
+            l[e] = dot(d[e], d[e]);
+        }
+        int best = 0;
+        if (l[1] > l[0]) best = 1;
+        if (l[2] > l[best]) best = 2;
+        double t = 0.0;
+        if (l[best] > 0) {
+            const double rr[3] = {fd(0.5 - q[best][0]), fd(0.5 - q[best][1]), fd(0.5 - q[best][2])};
+            t = std::min(std::max(fd(dot(rr, d[best]) / l[best]), 0.0), 1.0);
+        }
+        w[0] = w[1] = w[2] = 0.0;
+        w[best] = fd(1.0 - t); w[(best + 1) % 3] = t;
+    }
+    // (w0 W0 + w1 W1) + w2 W2 per component at cell (i, j, k) of triangle t of the sub-frame `cur`: float64, to be rounded once
+    void WallVelocity(int t, int i, int j, int k, double u[3]) const
+    {
+        const int iv[3] = {cur.idx[3 * (size_t)t], cur.idx[3 * (size_t)t + 1], cur.idx[3 * (size_t)t + 2]};
+        float pv[3][3];
+        for (int v = 0; v < 3; v++) { pv[v][0] = cur.x[iv[v]]; pv[v][1] = cur.y[iv[v]]; pv[v][2] = cur.z[iv[v]]; }
+        const float *const p[3] = {pv[0], pv[1], pv[2]};
+        double w[3];
+        WallWeights(p, i, j, k, w);
+        const std::vector<float> *W[3] = {&cur.vx, &cur.vy, &cur.vz};
+        for (int c = 0; c < 3; c++)
+            u[c] = fd(fd(fd(w[0] * (double)(*W[c])[iv[0]]) + fd(w[1] * (double)(*W[c])[iv[1]])) + fd(w[2] * (double)(*W[c])[iv[2]]));
     }
 
     // Build on a mesh given in grid coordinates (dimx, dimy, dimz set by the caller): what Prepare does with a sub-frame, for
@@ -154,6 +241,18 @@ struct Shape3D {
     void BuildMesh(const Shape3DFrame &fr) { Build(fr); }
 
 private:
+    // ComputeSubframeInfo (Grid3D.cpp:905-946): the frame of `time` and the weight s of the one after it
+    size_t Locate(double time, float &s) const
+    {
+        const size_t nf = frames.size();
+        std::vector<double> a(nf + 1, 0.0);
+        for (size_t i = 1; i <= nf; i++) a[i] = a[i - 1] + frames[i - 1].duration;
+        const double r = std::fmod(time, a[nf]);
+        size_t frame = 0;
+        for (size_t i = 1; i < nf; i++) if (a[i] < r) frame = i;
+        s = (float)((r - a[frame]) / (a[frame + 1] - a[frame]));
+        return frame;
+    }
     static float mix(float a, float wa, float b, float wb) { volatile float x = a * wa, y = b * wb; return x + y; }
     static float fl(float v) { volatile float x = v; return x; }                    // one rounding to float, no contraction
     size_t id(int i, int j, int k) const { return ((size_t)i * dimy + j) * dimz + k; }
@@ -238,8 +337,13 @@ private:
     // fp32 vertices, everything from them in float64 (the local vertices and edges are exact there), rounded after each operation
     struct VoxelEdge { double wa, wb, c; };
     static double fd(double v) { volatile double x = v; return x; }                 // one rounding to double, no contraction
+    static void cross(const double a[3], const double b[3], double o[3])
+    {
+        o[0] = fd(fd(a[1] * b[2]) - fd(a[2] * b[1])); o[1] = fd(fd(a[2] * b[0]) - fd(a[0] * b[2])); o[2] = fd(fd(a[0] * b[1]) - fd(a[1] * b[0]));
+    }
+    static double dot(const double a[3], const double b[3]) { return fd(fd(fd(a[0] * b[0]) + fd(a[1] * b[1])) + fd(a[2] * b[2])); }
     static bool VoxelPass(const VoxelEdge &e, double x, double y) { return fd(fd(fd(e.wa * x) + fd(e.wb * y)) + e.c) >= 0; }
-    void VoxelTriangle(const float *const p[3])
+    void VoxelTriangle(const float *const p[3], int t)
     {
         const int dims[3] = {dimx, dimy, dimz};
         int o[3], n[3];
@@ -323,7 +427,9 @@ private:
                         const double s = fd(g + fd(nd * pd));
                         if (!(fd(s + c1) >= 0) || !(fd(s + c2) <= 0)) continue;
                     }
-                    type[base + ia * stride[a] + ib * stride[b] + k * stride[d]] = NODE_BOUND;
+                    const size_t cell = base + ia * stride[a] + ib * stride[b] + k * stride[d];
+                    type[cell] = NODE_BOUND;
+                    if (!owner.empty() && (owner[cell] < 0 || owner[cell] > t)) owner[cell] = t;
                 }
             }
     }
@@ -333,6 +439,16 @@ private:
     {
         type.assign((size_t)dimx * dimy * dimz, NODE_IN);
         if (voxels != 0 && voxels != 1) throw std::runtime_error("Shape3D: voxels is 0 (the reference's rasteriser) or 1 (conservative)");
+        if (wall_velocity < 0 || wall_velocity > 2) throw std::runtime_error("Shape3D: wall_velocity is 0 (walls at rest), 1 (motion) or 2 (file)");
+        if (wall_velocity && voxels != 1) throw std::runtime_error("Shape3D: wall velocities need the conservative voxelisation (the owner of a wall cell is defined by its overlap test)");
+        owner.clear();
+        if (wall_velocity) {
+            if (fr.vx.size() != fr.x.size() || fr.vy.size() != fr.x.size() || fr.vz.size() != fr.x.size()) throw std::runtime_error("Shape3D: one velocity per vertex");
+            for (const std::vector<float> *a : {&fr.vx, &fr.vy, &fr.vz})
+                for (float v : *a) if (!std::isfinite(v)) throw std::runtime_error("Shape3D: a vertex velocity is not finite");
+            owner.assign(type.size(), -1);
+            if (&fr != &cur) cur = fr;
+        }
         if (voxels == 1)
             for (const std::vector<float> *a : {&fr.x, &fr.y, &fr.z})
                 for (float v : *a)
@@ -341,7 +457,7 @@ private:
         for (size_t q = 0; q + 2 < fr.idx.size(); q += 3) {
             const int i1 = fr.idx[q], i2 = fr.idx[q + 1], i3 = fr.idx[q + 2];
             const float p1[3] = {fr.x[i1], fr.y[i1], fr.z[i1]}, p2[3] = {fr.x[i2], fr.y[i2], fr.z[i2]}, p3[3] = {fr.x[i3], fr.y[i3], fr.z[i3]};
-            if (voxels == 1) { const float *const p[3] = {p1, p2, p3}; VoxelTriangle(p); continue; }
+            if (voxels == 1) { const float *const p[3] = {p1, p2, p3}; VoxelTriangle(p, (int)(q / 3)); continue; }
             RasterPolygon(p1, p2, p3);
             RasterLine(p1, p2); RasterLine(p1, p3); RasterLine(p3, p2);       // the edges as well, to cover holes
         }
@@ -364,26 +480,36 @@ private:
 // Third deviation, of a moving run: this is a function of the current grid alone.  The reference's repeated Prepare_CPU(t) keeps
 // T = 0 on every cell that once was a wall (Build never writes a NODE_BOUND cell's T and Init runs once); the Node T of a fluid
 // cell is read by nothing after the layers have been initialised, so no result differs.
+// wallT: the temperature of the NODE_BOUND cells (0: the reference's run); where sh.wall_velocity is set they also carry the
+// velocity of the mesh (Shape3D::WallVelocity of the cell's owner, rounded once to FTYPE).
 template <typename FTYPE>
-void FillShape3DNodes(Grid3D<FTYPE> &g, const Shape3D &sh, double baseT)
+void FillShape3DNodes(Grid3D<FTYPE> &g, const Shape3D &sh, double baseT, double wallT = 0)
 {
     for (size_t c = 0; c < sh.type.size(); c++) {
         g.type[c] = sh.type[c];
         g.bc_vel[c] = BC_NOSLIP; g.bc_temp[c] = BC_NOSLIP;
         g.vx[c] = 0; g.vy[c] = 0; g.vz[c] = 0;
-        g.T[c] = sh.type[c] == NODE_BOUND ? (FTYPE)0 : (FTYPE)(float)baseT;     // Init: T = 0; Build: SetData(.., baseT) on NODE_IN / NODE_OUT only
+        g.T[c] = sh.type[c] == NODE_BOUND ? (FTYPE)(float)wallT : (FTYPE)(float)baseT;     // Init: T = 0; Build: SetData(.., baseT) on NODE_IN / NODE_OUT only
+        if (sh.type[c] == NODE_BOUND && !sh.owner.empty()) {
+            const int k = (int)(c % sh.dimz), j = (int)((c / sh.dimz) % sh.dimy), i = (int)(c / ((size_t)sh.dimz * sh.dimy));
+            double u[3];
+            sh.WallVelocity(sh.owner[c], i, j, k, u);
+            g.vx[c] = (FTYPE)u[0]; g.vy[c] = (FTYPE)u[1]; g.vz[c] = (FTYPE)u[2];
+        }
     }
 }
 
 // Grid3D(dx,dy,dz,baseT) + LoadFromFile + Prepare_CPU(0) for a Shape3D input (FluidSolver3D.cpp:121-145)
 template <typename FTYPE>
-void LoadShape3D(Grid3D<FTYPE> &g, Shape3D &sh, const std::string &path, double dx, double dy, double dz, double baseT, bool align, int voxels = 0)
+void LoadShape3D(Grid3D<FTYPE> &g, Shape3D &sh, const std::string &path, double dx, double dy, double dz, double baseT, bool align, int voxels = 0,
+                 int wall_velocity = 0, double wallT = 0)
 {
     sh.voxels = voxels;
+    sh.wall_velocity = wall_velocity;
     sh.Load(path, dx, dy, dz, align);
     g.Resize(sh.dimx, sh.dimy, sh.dimz);
     g.dx = dx; g.dy = dy; g.dz = dz; g.baseT = baseT;
-    FillShape3DNodes(g, sh, baseT);
+    FillShape3DNodes(g, sh, baseT, wallT);
 }
 
 }  // namespace fs3d

@@ -1,5 +1,5 @@
 // Command-line driver: the reference's FluidSolver3D main (FluidSolver3D/FluidSolver3D.cpp:60-330) on top of
-// libfs3d_hip.so.   fs3d_run <input data> <output prefix> <config> [align] [GPU [n]] [double] [moving [--host-extrusion] [--time-geometry]] [moving-mesh [--host-voxels] [--time-geometry] [--time-both]] [--time-output] [--steps N] [--same-device] [--grid-only FILE [--grid-time T]] [--watertight]
+// libfs3d_hip.so.   fs3d_run <input data> <output prefix> <config> [align] [GPU [n]] [double] [moving [--host-extrusion] [--time-geometry]] [moving-mesh [--host-voxels] [--time-geometry] [--time-both]] [--time-output] [--steps N] [--same-device] [--grid-only FILE [--grid-time T]] [--watertight [--wall-velocity motion|file]] [--wall-temperature T]
 //   * reads the config (host/Config.h) and a Shape2D, Shape3D or SeaNetCDF geometry (host/Shape2D.h, Shape3D.h, SeaNetCDF.h), prints the grid summary lines
 //     the reference prints ("Grid = X x Y x Z", "NODE_IN points = ..."),
 //   * runs the same loop: dt = cycle length / (frames * time_steps), UpdateBoundaries + TimeStep per step with the
@@ -23,6 +23,12 @@
 //   --watertight (in_fmt Shape3D, with or without moving-mesh): the conservative voxelisation instead of the reference's rasteriser
 //   (Shape3D::voxels = 1 on the host, FS3D_OPT_MESH_VOXELS = 1 on the device) for the first geometry and for every update alike: a
 //   closed mesh keeps its NODE_IN cells at every time; the shell is thicker, so the fluid volume is smaller.
+//   --wall-velocity motion|file (in_fmt Shape3D, needs --watertight): the NODE_BOUND cells carry the velocity of the mesh -- of the
+//   cell's owner triangle at the projection of the cell's centre (host/Shape3D.h WallWeights) -- in the first geometry and in every
+//   moving-mesh update (UpdateGridShape3D with velocities: fs3d_update_nodes_shape3d_vel), so a moving wall pushes the fluid.
+//   `motion`: the vertices' displacement per frame over the frame's duration; `file`: the velocity columns of the input,
+//   interpolated as the reference does and taken as they are.  With --host-voxels the host loader computes the same arrays, bit for bit.
+//   --wall-temperature T (in_fmt Shape3D): T of the NODE_BOUND cells instead of 0; a moving-mesh run on the device needs --watertight for it.
 //   --time-both: a measurement run -- every step makes the geometry through BOTH paths, the word's own last (same tables either way),
 //   and one more line gives, per call after 3 warm-up steps, median (min - max) of the host clock around each path, the device
 //   time of the device path (fs3d_last_update_device_ms), and the host clock around UpdateBoundaries + TimeStep, synchronised.
@@ -34,6 +40,7 @@
 //   --grid-time T: the grid the moving loop uses at time T (Shape2D: load, Prepare(T), extrude again; Shape3D: Prepare(T)) instead of the one of time 0.
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <condition_variable>
 #include <exception>
 #include <mutex>
@@ -66,7 +73,9 @@ struct RunGeom {
 struct RunOptions {
     bool align = false, dbl = false, csv = false, same_device = false, grid_images = false, watertight = false;
     bool moving = false, host_extrusion = false, moving_mesh = false, host_voxels = false, time_geometry = false, time_both = false, time_output = false;
-    double grid_time = -1;
+    double grid_time = -1, wall_T = 0;
+    int wall_velocity = 0;                             // 0: walls at rest; 1: motion; 2: file (Shape3D::wall_velocity)
+    bool has_wall_T = false;
     int nslabs = 1, device = 0;
     long max_steps = -1;
     std::string grid_only;
@@ -89,6 +98,13 @@ static int run(const std::string &data, const std::string &prefix, const fs3d::C
     if (o.time_both && !o.moving_mesh) throw std::runtime_error("--time-both: only with moving-mesh (it times both ways of making a mesh's geometry)");
     if (o.time_geometry && !o.moving && !o.moving_mesh) throw std::runtime_error("--time-geometry: only with moving or moving-mesh (it times the per-step geometry work)");
     if (o.watertight && cfg.in_fmt != "Shape3D") throw std::runtime_error("--watertight: only in_fmt Shape3D inputs are meshes (this one is " + cfg.in_fmt + ")");
+    if (o.wall_velocity && cfg.in_fmt != "Shape3D") throw std::runtime_error("--wall-velocity: only in_fmt Shape3D inputs are meshes (this one is " + cfg.in_fmt + ")");
+    if (o.wall_velocity && !o.watertight) throw std::runtime_error("--wall-velocity: needs --watertight (the owner triangle of a wall cell is defined by the conservative voxelisation's overlap test)");
+    if (o.has_wall_T && cfg.in_fmt != "Shape3D") throw std::runtime_error("--wall-temperature: only in_fmt Shape3D inputs are meshes (this one is " + cfg.in_fmt + ")");
+    if (o.has_wall_T && !std::isfinite(o.wall_T)) throw std::runtime_error("--wall-temperature: not a finite number");
+    if (o.has_wall_T && o.moving_mesh && !o.watertight) throw std::runtime_error("--wall-temperature: a moving-mesh run needs --watertight for it (the wall temperature travels with fs3d_update_nodes_shape3d_vel)");
+    const bool walls = o.wall_velocity || o.has_wall_T;    // the mesh updates go through the entries that take velocities and a wall temperature
+    if (walls && o.time_both) throw std::runtime_error("--time-both: not together with --wall-velocity or --wall-temperature");
     if (o.grid_time >= 0 && cfg.in_fmt != "Shape2D" && cfg.in_fmt != "Shape3D") throw std::runtime_error("--grid-time: only in_fmt Shape2D and Shape3D inputs move");
     using namespace fs3d;
     Grid3D<FTYPE> grid;
@@ -103,7 +119,7 @@ static int run(const std::string &data, const std::string &prefix, const fs3d::C
         for (int a = 0; a < 6; a++) geo.bbox[a] = sea.bbox[a];
     } else if (cfg.in_fmt == "Shape3D") {
         std::printf("Geometry: 3D polygons\n");                                                  // FluidSolver3D.cpp:121-126
-        LoadShape3D(grid, sh3, data, cfg.dx, cfg.dy, cfg.dz, cfg.baseT, o.align, o.watertight ? 1 : 0);
+        LoadShape3D(grid, sh3, data, cfg.dx, cfg.dy, cfg.dz, cfg.baseT, o.align, o.watertight ? 1 : 0, o.wall_velocity, o.wall_T);
         geo.frames = sh3.GetFramesNum(); geo.length = cfg.frame_time;                            // Grid3D.cpp:298-309
         for (int a = 0; a < 6; a++) geo.bbox[a] = sh3.bbox[a];
     } else {
@@ -120,7 +136,7 @@ static int run(const std::string &data, const std::string &prefix, const fs3d::C
                 inside * grid.dx * grid.dy * grid.dz);                                          // :170
     if (o.grid_images) OutputGridImages(grid, prefix + "_grid_3d");                             // FluidSolver3D.cpp:152-153 (there: always)
     if (!o.grid_only.empty()) {
-        if (o.grid_time >= 0 && cfg.in_fmt == "Shape3D") { sh3.Prepare(o.grid_time); FillShape3DNodes(grid, sh3, cfg.baseT); }
+        if (o.grid_time >= 0 && cfg.in_fmt == "Shape3D") { sh3.Prepare(o.grid_time); FillShape3DNodes(grid, sh3, cfg.baseT, o.wall_T); }
         else if (o.grid_time >= 0) { g2.Prepare(o.grid_time); ExtrudeShape2D(grid, g2, cfg.dz, cfg.depth, cfg.depth_var, cfg.baseT); }
         FILE *f = std::fopen(o.grid_only.c_str(), "wb");
         if (!f) throw std::runtime_error("cannot create " + o.grid_only);
@@ -161,6 +177,7 @@ static int run(const std::string &data, const std::string &prefix, const fs3d::C
     int lastframe = -1;
     double geom_ms[3] = {0, 0, 0};                     // moving / moving-mesh: host clock around Prepare / SubFrame, the node arrays on the host, the update call
     std::vector<float> mx, my, mz;                     // moving-mesh: the sub-frame's vertices
+    std::vector<float> mwx, mwy, mwz;                  // ... and their velocities (zeros without --wall-velocity)
     std::vector<double> ab_host, ab_dev, ab_dev_gpu, ab_step;   // --time-both: per step, ms
     int fill_rounds = 0;
     double out_ms[2] = {0, 0};                         // --time-output: host clock around GetLayer, AppendLayer
@@ -183,11 +200,16 @@ static int run(const std::string &data, const std::string &prefix, const fs3d::C
             else frame = sh3.SubFrame(t, mx, my, mz);
             const auto g1 = std::chrono::steady_clock::now();
             if (on_host && o.moving) ExtrudeShape2D(grid, g2, cfg.dz, cfg.depth, cfg.depth_var, cfg.baseT);
-            else if (on_host) { sh3.Prepare(t); FillShape3DNodes(grid, sh3, cfg.baseT); }
+            else if (on_host) { sh3.Prepare(t); FillShape3DNodes(grid, sh3, cfg.baseT, o.wall_T); }
+            else if (o.moving_mesh && walls) {
+                if (o.wall_velocity) sh3.SubFrameVelocity(t, o.wall_velocity, mwx, mwy, mwz);
+                else { mwx.assign(mx.size(), 0.0f); mwy = mwx; mwz = mwx; }
+            }
             const auto g3 = std::chrono::steady_clock::now();
             // (on the device, `grid` keeps the nodes of time 0: only its dims and baseT are read from here on)
             if (on_host) solver.UpdateGrid(grid);
             else if (o.moving) solver.UpdateGridExtruded(g2, cfg.dz, cfg.depth, cfg.depth_var);
+            else if (walls) solver.UpdateGridShape3D(mx, my, mz, mwx, mwy, mwz, sh3.frames[frame].idx, o.wall_T);
             else solver.UpdateGridShape3D(mx, my, mz, sh3.frames[frame].idx);
             const auto g4 = std::chrono::steady_clock::now();
             geom_ms[0] += std::chrono::duration<double, std::milli>(g1 - g0).count();
@@ -379,7 +401,7 @@ static int run_slabs(const fs3d::Grid3D<FTYPE> &grid, const RunGeom &geo, const 
 int main(int argc, char **argv)
 {
     if (argc < 4) {
-        std::printf("Usage: %s <input data> <output prefix> <config file> [align] [GPU [n]] [double] [--steps N] [moving [--host-extrusion] [--time-geometry]] [moving-mesh [--host-voxels] [--time-geometry] [--time-both]] [--time-output] [--grid-only FILE [--grid-time T]] [--grid-images] [--watertight]\n", argv[0]);
+        std::printf("Usage: %s <input data> <output prefix> <config file> [align] [GPU [n]] [double] [--steps N] [moving [--host-extrusion] [--time-geometry]] [moving-mesh [--host-voxels] [--time-geometry] [--time-both]] [--time-output] [--grid-only FILE [--grid-time T]] [--grid-images] [--watertight [--wall-velocity motion|file]] [--wall-temperature T]\n", argv[0]);
         return 0;
     }
     try {
@@ -404,6 +426,17 @@ int main(int argc, char **argv)
             else if (s == "moving-mesh") o.moving_mesh = true;
             else if (s == "--host-voxels") o.host_voxels = true;
             else if (s == "--watertight") o.watertight = true;
+            else if (s == "--wall-velocity") {
+                const std::string w = a + 1 < argc ? argv[++a] : "";
+                if (w != "motion" && w != "file") throw std::runtime_error("--wall-velocity: motion or file");
+                o.wall_velocity = w == "motion" ? 1 : 2;
+            }
+            else if (s == "--wall-temperature") {
+                if (a + 1 >= argc) throw std::runtime_error("--wall-temperature: a number follows");
+                char *end = nullptr;
+                o.wall_T = std::strtod(argv[++a], &end); o.has_wall_T = true;
+                if (end == argv[a] || *end) throw std::runtime_error("--wall-temperature: not a number");
+            }
             else if (s == "--time-both") o.time_both = true;
             else if (s == "--host-extrusion") o.host_extrusion = true;
             else if (s == "--time-geometry") o.time_geometry = true;

@@ -7,6 +7,8 @@ function of the current grid alone, where the reference's repeated Prepare_CPU k
   Grid3D::Load3DShape / Init / Prepare3D_Shape / ComputeSubframeInfo / Build / RasterPolygon / ProjectPointOnPolygon /
   RasterLine / FloodFill                         (FluidSolver3D/Grid3D.cpp:351-431, 676-946)
   BBox3D::Build                                  (Common/Geometry.h:510-529)
+Wall velocities (conservative voxelisation only; the reference reads a velocity per vertex and drops it in RasterPolygon): see
+wall_weights below -- every NODE_BOUND cell takes the velocity of its owner triangle at the projection of the cell's centre.
 Pinned to the reference (r3): tests/test_ref_golden.py holds this loader cell for cell to the node arrays of the reference's own
 Grid3D on the shipped box_pipe_3D and tetra meshes and on a two-frame icosphere at five times (tests/golden/ref_*_3D_*.npz,
 ref_tetra_f32.npz); tests/test_shape3d.py compares the C++ loader with this twin.
@@ -79,13 +81,82 @@ VOXEL_DEGENERATE = 2.0 ** -24
 _VOXEL_AXES = ((1, 2, 0), (2, 0, 1), (0, 1, 2))      # (a, b, d): the column plane and the depth axis, cyclic, by depth axis d
 _VOXEL_EDGES = ((0, 1), (1, 2), (2, 0))
 VOXEL_MODES = ("reference", "conservative")
+WALL_VELOCITY_SOURCES = ("motion", "file")
+NO_OWNER = -1
+
+
+# ---- wall velocities of a mesh (conservative voxelisation only): the specification host/Shape3D.h and k_geom_mesh_nodes_vel repeat ----
+# Owner.  The owner of a NODE_BOUND cell is the triangle of smallest index whose conservative test sets the cell (the mask of
+# _voxel_triangle): a minimum over a set, so it does not depend on the order in which triangles are visited.  Where several
+# triangles overlap a cell the choice is arbitrary; the velocity field of a mesh is continuous across shared vertices, so another
+# choice moves the value by the velocity gradient times a cell.
+# Weights.  float64 from the fp32 vertices, every operation rounded once, in the order written here, uncontracted.  Coordinates
+# are local to the cell's own corner, q_i = (double)v_i - (i, j, k) (exact for |v| <= VOXEL_COORD_MAX), the centre is c = (1/2, 1/2, 1/2).
+#   e0 = q1 - q0, e1 = q2 - q0, r = c - q0, n = e0 x e1, nn = (nx nx + ny ny) + nz nz
+#   nn >= VOXEL_DEGENERATE: b1 = ((r x e1) . n) / nn, b2 = ((e0 x r) . n) / nn, b0 = (1 - b1) - b2 -- the barycentric coordinates of
+#     the centre's orthogonal projection onto the plane; m_i = max(b_i, 0); w_i = m_i / ((m0 + m1) + m2)
+#   else: the longest of the edges (0,1), (1,2), (2,0) by squared length (the first wins ties), t = the parameter of the centre's
+#     projection onto it clamped to [0, 1] (0 for an edge of zero length): 1 - t and t on its two ends, 0 on the third vertex
+# a cross product is (ay bz - az by, az bx - ax bz, ax by - ay bx), a dot product (x x' + y y') + z z'.
+# Velocity.  Per component (w0 W0 + w1 W1) + w2 W2 from the fp32 vertex velocities W_i, rounded once to the solver's real type.
+
+def _cross(a, b):
+    return (a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0])
+
+
+def _dot(a, b):
+    return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]
+
+
+def wall_weights(p, cell):
+    """The three weights (float64) of the triangle p [3][3] (fp32 vertices in grid coordinates) at the cells `cell` = (i, j, k):
+    scalars or equal-shaped integer arrays.  Every operation is a float64 numpy operation, elementwise: rounded once, never fused."""
+    D = np.float64
+    ijk = [np.asarray(c, D) for c in cell]
+    q = [[np.asarray(p[i][c], D) - ijk[c] for c in range(3)] for i in range(3)]
+    e0 = [q[1][c] - q[0][c] for c in range(3)]; e1 = [q[2][c] - q[0][c] for c in range(3)]
+    r = [D(0.5) - q[0][c] for c in range(3)]
+    n = _cross(e0, e1)
+    nn = _dot(n, n)
+    with np.errstate(all="ignore"):
+        b1 = _dot(_cross(r, e1), n) / nn
+        b2 = _dot(_cross(e0, r), n) / nn
+        b0 = (D(1.0) - b1) - b2
+        m = [np.maximum(b, D(0.0)) for b in (b0, b1, b2)]
+        s = (m[0] + m[1]) + m[2]
+        plane = [x / s for x in m]
+        # degenerate: the longest edge, the first of equals
+        d = [[q[j][c] - q[i][c] for c in range(3)] for i, j in _VOXEL_EDGES]
+        l = [_dot(x, x) for x in d]
+        rr = [[D(0.5) - q[i][c] for c in range(3)] for i, _ in _VOXEL_EDGES]
+        t = [np.where(l[k] > 0, np.minimum(np.maximum(_dot(rr[k], d[k]) / l[k], D(0.0)), D(1.0)), D(0.0)) for k in range(3)]
+    best = np.where(l[1] > l[0], 1, 0)
+    best = np.where(l[2] > np.where(best == 1, l[1], l[0]), 2, best)
+    zero = np.zeros_like(nn)
+    edge = []
+    for v in range(3):                                   # vertex v: 1 - t as the first end of edge v, t as the second end of edge v - 1
+        prev = (v + 2) % 3
+        edge.append(np.where(best == v, D(1.0) - t[v], np.where(best == prev, t[prev], zero)))
+    deg = ~(nn >= VOXEL_DEGENERATE)
+    return [np.where(deg, edge[v], plane[v]) for v in range(3)]
+
+
+def wall_velocity(w, W):
+    """(w0 W0 + w1 W1) + w2 W2 per component, float64, from the weights of wall_weights and the fp32 vertex velocities W [3][3]."""
+    D = np.float64
+    return [(w[0] * np.asarray(W[0][c], D) + w[1] * np.asarray(W[1][c], D)) + w[2] * np.asarray(W[2][c], D) for c in range(3)]
 
 
 class Shape3D:
-    def __init__(self, frames, dx, dy, dz, align, time=0.0, voxels="reference"):
+    def __init__(self, frames, dx, dy, dz, align, time=0.0, voxels="reference", wall_velocity=None):
         if voxels not in VOXEL_MODES:
             raise ValueError("Shape3D: voxels is 'reference' or 'conservative'")
+        if wall_velocity is not None and wall_velocity not in WALL_VELOCITY_SOURCES:
+            raise ValueError("Shape3D: wall_velocity is None, 'motion' or 'file'")
+        if wall_velocity is not None and voxels != "conservative":
+            raise ValueError("Shape3D: wall velocities need voxels='conservative' (the owner of a wall cell is defined by its overlap test)")
         self.voxels = voxels
+        self.wall_velocity = wall_velocity                # prepare(t) then keeps owner and wall_v (build with the velocities of time t)
         self.frames = frames
         self.dx, self.dy, self.dz = dx, dy, dz
         allv = np.concatenate([fr["v"] for fr in frames], axis=0)
@@ -103,9 +174,8 @@ class Shape3D:
             fr["g"] = ((fr["v"] - mn).astype(np.float32) / h).astype(np.float32)
         self.prepare(time)
 
-    def subframe(self, time):
-        """ComputeSubframeInfo + the interpolation of Prepare3D_Shape (Grid3D.cpp:905-946): (vertices in grid coordinates
-        [n, 3] float32, triangles [m, 3]) of the mesh at `time` -- what build() and the device voxeliser take."""
+    def _locate(self, time):
+        """ComputeSubframeInfo (Grid3D.cpp:905-946): (frame, the next frame -- wrapped --, s as float32)"""
         nf = len(self.frames)
         a = [0.0]
         for fr in self.frames:
@@ -115,13 +185,37 @@ class Shape3D:
         for i in range(1, nf):
             if a[i] < r:
                 frame = i
-        s = F((r - a[frame]) / (a[frame + 1] - a[frame])); i_s = F(F(1) - s)
-        f0, f1 = self.frames[frame], self.frames[(frame + 1) % nf]
+        return frame, (frame + 1) % nf, F((r - a[frame]) / (a[frame + 1] - a[frame]))
+
+    def subframe(self, time):
+        """ComputeSubframeInfo + the interpolation of Prepare3D_Shape (Grid3D.cpp:905-946): (vertices in grid coordinates
+        [n, 3] float32, triangles [m, 3]) of the mesh at `time` -- what build() and the device voxeliser take."""
+        frame, nxt, s = self._locate(time)
+        i_s = F(F(1) - s)
+        f0, f1 = self.frames[frame], self.frames[nxt]
         g = ((f0["g"] * i_s).astype(np.float32) + (f1["g"] * s).astype(np.float32)).astype(np.float32)
         return g, f0["idx"]
 
+    def subframe_velocity(self, time, source="motion"):
+        """The vertex velocities [n, 3] float32 of the mesh at `time`, in the solver's velocity units, beside subframe(time).
+        "motion": (P[f+1] - P[f]) (1 / Duration[f]) on the physical vertices, fp32 in the order of shape2d.py's border velocities;
+        f is subframe's frame and f + 1 wraps as there.  The vertices move linearly over a frame interval, so the velocity is
+        constant over it; a one-frame mesh is at rest.
+        "file": the file's velocity columns as the reference interpolates them (Grid3D.cpp:915), W[f] (1 - s) + W[f+1] s, taken
+        as they are (their unit is not documented)."""
+        if source not in WALL_VELOCITY_SOURCES:
+            raise ValueError("Shape3D: a velocity source is 'motion' or 'file'")
+        frame, nxt, s = self._locate(time)
+        f0, f1 = self.frames[frame], self.frames[nxt]
+        if source == "motion":
+            m = F(1.0 / f0["duration"])
+            return ((f1["v"] - f0["v"]).astype(np.float32) * m).astype(np.float32)
+        i_s = F(F(1) - s)
+        return ((f0["vel"] * i_s).astype(np.float32) + (f1["vel"] * s).astype(np.float32)).astype(np.float32)
+
     def prepare(self, time):
-        self.build(*self.subframe(time))
+        g, idx = self.subframe(time)
+        self.build(g, idx, None if self.wall_velocity is None else self.subframe_velocity(time, self.wall_velocity))
 
     # ---- rasteriser -----------------------------------------------------------------------------------------------
     def _set(self, i, j, k, c):
@@ -257,7 +351,7 @@ class Shape3D:
             plane = (na, nb, nd, (cmax - min(t)) + sl, (cmin - max(t)) - sl)
         return o, n, axes, edges, plane
 
-    def _voxel_triangle(self, p):
+    def _voxel_triangle(self, p, t=0):
         st = self._voxel_setup(p)
         if st is None:
             return
@@ -284,18 +378,43 @@ class Shape3D:
             s = g + nd * pd
             m = m & ((s + c1) >= 0) & ((s + c2) <= 0)
         m = np.transpose(m, [(a, b, d).index(c) for c in range(3)])
-        self.type[o[0]:o[0] + n[0], o[1]:o[1] + n[1], o[2]:o[2] + n[2]][m] = NODE_BOUND
+        box = (slice(o[0], o[0] + n[0]), slice(o[1], o[1] + n[1]), slice(o[2], o[2] + n[2]))
+        self.type[box][m] = NODE_BOUND
+        own = self.owner[box]                             # the smallest index of the triangles that set the cell
+        own[m & ((own == NO_OWNER) | (own > t))] = t
 
-    def build(self, g, idx):
+    def _wall_velocities(self, g, idx, vel):
+        """wall_v = (vx, vy, vz) float64 [dimx, dimy, dimz]: wall_velocity(wall_weights(owner)) on NODE_BOUND cells, 0 elsewhere"""
+        out = [np.zeros(self.type.shape, np.float64) for _ in range(3)]
+        ci, cj, ck = np.nonzero(self.owner != NO_OWNER)
+        if len(ci):
+            tri = np.asarray(idx).reshape(-1, 3)[self.owner[ci, cj, ck]]          # [cells, 3]
+            p = [[np.asarray(g, np.float32)[tri[:, v], c] for c in range(3)] for v in range(3)]
+            W = [[np.asarray(vel, np.float32)[tri[:, v], c] for c in range(3)] for v in range(3)]
+            for c, u in enumerate(wall_velocity(wall_weights(p, (ci, cj, ck)), W)):
+                out[c][ci, cj, ck] = u
+        return tuple(out)
+
+    def build(self, g, idx, vel=None):
+        """The grid of the mesh (g, idx); with vertex velocities vel [n, 3] (conservative voxelisation only) also wall_v.
+        The conservative voxelisation always keeps `owner` (int, NO_OWNER off the walls)."""
         self.type = np.full((self.dimx, self.dimy, self.dimz), NODE_IN, np.uint8)
+        self.owner, self.wall_v = None, None
+        if vel is not None and self.voxels != "conservative":
+            raise ValueError("Shape3D: wall velocities need the conservative voxelisation")
         if self.voxels == "conservative":
             g = np.asarray(g, np.float32)
             if len(g) and not (np.abs(g) <= VOXEL_COORD_MAX).all():
                 raise ValueError("Shape3D: a vertex coordinate is not finite or exceeds 4096 grid cells in magnitude (conservative voxelisation)")
-        for i1, i2, i3 in idx:
+            self.owner = np.full(self.type.shape, NO_OWNER, np.int64)
+        if vel is not None:
+            vel = np.asarray(vel, np.float32)
+            if vel.shape != np.asarray(g).shape or not np.isfinite(vel).all():
+                raise ValueError("Shape3D: one finite velocity per vertex")
+        for t, (i1, i2, i3) in enumerate(idx):
             p1, p2, p3 = (tuple(F(c) for c in g[q]) for q in (i1, i2, i3))
             if self.voxels == "conservative":
-                self._voxel_triangle((p1, p2, p3))
+                self._voxel_triangle((p1, p2, p3), t)
                 continue
             self._raster_polygon(p1, p2, p3)
             self._raster_line(p1, p2); self._raster_line(p1, p3); self._raster_line(p3, p2)
@@ -305,23 +424,29 @@ class Shape3D:
         free[0, 0, 0] = True
         lab, _ = ndimage.label(free)
         self.type[lab == lab[0, 0, 0]] = NODE_OUT
+        if vel is not None:
+            self.wall_v = self._wall_velocities(g, idx, vel)
 
 
-def load_shape3d(path_or_text, dx, dy, dz, baseT=1.0, align=True, is_text=False, voxels="reference"):
-    """Grid3D(dx,dy,dz,baseT) + LoadFromFile + Prepare_CPU(0) for a Shape3D input -> (Nodes, Shape3D)."""
+def load_shape3d(path_or_text, dx, dy, dz, baseT=1.0, align=True, is_text=False, voxels="reference", wall_velocity=None, wall_T=0.0, time=0.0):
+    """Grid3D(dx,dy,dz,baseT) + LoadFromFile + Prepare_CPU(time) for a Shape3D input -> (Nodes, Shape3D).  wall_velocity ("motion" /
+    "file", conservative voxelisation only) and wall_T: what the walls carry, see nodes_of."""
     text = path_or_text if is_text else open(path_or_text, "r").read()
-    sh = Shape3D(parse_shape3d(text), dx, dy, dz, align, voxels=voxels)
-    return nodes_of(sh, dx, dy, dz, baseT), sh
+    sh = Shape3D(parse_shape3d(text), dx, dy, dz, align, time, voxels=voxels, wall_velocity=wall_velocity)
+    return nodes_of(sh, dx, dy, dz, baseT, sh.wall_v, wall_T), sh
 
 
-def nodes_of(sh, dx, dy, dz, baseT=1.0):
+def nodes_of(sh, dx, dy, dz, baseT=1.0, wall_v=None, wall_T=0.0):
     """The Node array of a prepared Shape3D grid: NODE_BOUND cells carry NOSLIP, v = 0, T = 0 (what the reference's run holds
-    there: tests/golden/ref_box_pipe_3D_f32.npz), every other cell T = baseT."""
+    there: tests/golden/ref_box_pipe_3D_f32.npz), every other cell T = baseT.  With wall_v = (vx, vy, vz) (sh.wall_v of a grid
+    built with vertex velocities) the NODE_BOUND cells carry those, float64 here and rounded once by whoever narrows them to the
+    solver's real type; wall_T is their temperature (through a float, like baseT)."""
     shape = sh.type.shape
     z8 = np.zeros(shape, np.uint8)
     zero = np.zeros(shape, np.float64)
-    T = np.where(sh.type == NODE_BOUND, 0.0, float(F(baseT)))
-    return Nodes(sh.dimx, sh.dimy, sh.dimz, dx, dy, dz, sh.type.copy(), z8 + BC_NOSLIP, z8 + BC_NOSLIP, zero, zero.copy(), zero.copy(), T)
+    T = np.where(sh.type == NODE_BOUND, float(F(wall_T)), float(F(baseT)))
+    v = [zero, zero.copy(), zero.copy()] if wall_v is None else [np.where(sh.type == NODE_BOUND, a, 0.0) for a in wall_v]
+    return Nodes(sh.dimx, sh.dimy, sh.dimz, dx, dy, dz, sh.type.copy(), z8 + BC_NOSLIP, z8 + BC_NOSLIP, v[0], v[1], v[2], T)
 
 
 def write_mesh(path, frames):

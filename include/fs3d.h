@@ -247,6 +247,8 @@ fs3d_status fs3d_voxelize_shape3d_dev(fs3d_ctx *ctx, const float *x, const float
                                       const int *tri, int ntri, double baseT, uint8_t *type_out, uint8_t *bc_vel_out,
                                       uint8_t *bc_temp_out, void *vx_out, void *vy_out, void *vz_out, void *T_out);
 fs3d_status fs3d_flood_fill_dev(fs3d_ctx *ctx, uint8_t *type_inout);
+
+/* The same two entries with walls that carry the mesh's velocity and a temperature: include/fs3d_mesh_walls.h. */
 fs3d_status fs3d_mesh_fill_rounds(fs3d_ctx *ctx, int *rounds_out);
 /* The `bottom` table the two entries use, dimx*dimy ints (index i*dimy + j); host only, no context, no GPU.  Test aid: the
  * table must equal the host loader's, whose (int) truncates a double product. */
