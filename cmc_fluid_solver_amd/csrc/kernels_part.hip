@@ -284,7 +284,15 @@ __global__ void __launch_bounds__(LT * NCH, sizeof(R) == 8 ? 2 : 4) k_sweep_part
     // running scalar offsets, opaque from cell to cell: otherwise the offsets of all M cells are computed up front and
     // held in (spilled) SGPRs
     unsigned s_is = so0, s_nd = son;
-    const unsigned vo_edge = kk == 0 ? vo - (unsigned)sizeof(R) : (kk == LT - 1 ? vo + (unsigned)sizeof(R) : BUF_OOB);
+    // The lane-axis neighbours k - 1 of the tile's first lane and k + 1 of its last lane by flat index, as the reference reads
+    // them: at k = 0 / k = dimz - 1 that is the last / first cell of the neighbouring row.  (Only a NODE_IN cell in a k face of
+    // the grid is a row there.)  Where the line ends inside the tile, the first lane past it (`ghost`; its own offset is clamped
+    // to the line's last cell) fetches cell dimz by flat index and hands it to the line's last lane in the DPP shift below.
+    // The halo plane's bytes ride in the per-lane offset, which alone is range-checked: k = 0 of chunk 0 would otherwise wrap
+    // below zero and load 0.
+    const bool ghost = k == la_len;
+    const unsigned edge_b = (unsigned)(p.plane * (long long)sizeof(R));
+    const unsigned vo_edge = kk == 0 ? vo + edge_b - (unsigned)sizeof(R) : ((kk == LT - 1 || ghost) ? vo + edge_b + (unsigned)sizeof(R) : BUF_OOB);
     auto issue = [&](CellLd &L) __attribute__((always_inline)) {
         const unsigned sc = s_is;
         s_is = opq_s(s_is + ssb);
@@ -296,7 +304,7 @@ __global__ void __launch_bounds__(LT * NCH, sizeof(R) == 8 ? 2 : 4) k_sweep_part
         L.om = Buf<R>::ld(Ltmp, vo, sv - osb); L.op = Buf<R>::ld(Ltmp, vo, sv + osb);
         // lane-axis neighbours: the lanes next door hold them (DPP shifts below); only the tile's first and last lane
         // fetch theirs from outside the tile -- every other lane of this load is out of range (no memory access)
-        L.le = Buf<R>::ld(Ltmp, vo_edge, sv);
+        L.le = Buf<R>::ld(Ltmp, vo_edge, sv - edge_b);
     };
     R Tm[4], Tc[4];
 #pragma unroll
@@ -364,11 +372,12 @@ __global__ void __launch_bounds__(LT * NCH, sizeof(R) == 8 ? 2 : 4) k_sweep_part
 #pragma unroll
             for (int f = 0; f < 4; f++) g[f] = pdivc(c.tp[f] - Tm[f], h2s, ir2s);          // d/ds of U, V, W, T (TimeLayer3D.h:338-340)
             R lm, lp;                                             // Vs of the lanes next door (wave_shr:1 / wave_shl:1)
+            const R vs = ghost ? c.le : Tc[DIR];
             if (sizeof(R) == 4) {
-                const int cv = __builtin_bit_cast(int, (float)Tc[DIR]);
+                const int cv = __builtin_bit_cast(int, (float)vs);
                 lm = (R)__builtin_bit_cast(float, __builtin_amdgcn_update_dpp(cv, cv, 0x138, 0xF, 0xF, false));
                 lp = (R)__builtin_bit_cast(float, __builtin_amdgcn_update_dpp(cv, cv, 0x130, 0xF, 0xF, false));
-            } else { lm = __shfl_up(Tc[DIR], 1, 64); lp = __shfl_down(Tc[DIR], 1, 64); }
+            } else { lm = __shfl_up(vs, 1, 64); lp = __shfl_down(vs, 1, 64); }
             lm = kk == 0 ? c.le : lm; lp = kk == LT - 1 ? c.le : lp;
             const R x1 = pdivc(c.op - c.om, h2o, ir2o), x2 = pdivc(lp - lm, h2l, ir2l);   // d(Vs)/d(o axis), d(Vs)/d(lane axis)
             const R t0 = (DIR == 0 ? R(2) : R(1)) * g[0] * g[0], t1 = (DIR == 1 ? R(2) : R(1)) * g[1] * g[1], t2 = g[2] * g[2];
@@ -820,7 +829,11 @@ __global__ void __launch_bounds__(256, 2) k_sweep_part_z(SweepParams<R> p, int n
         // one: valid addresses (out-of-range ones return 0), nothing stored
         const int jr = jrow < p.dimy ? jrow : p.dimy - 1;
         const unsigned so = opq_s(line_so(jr));
-        L.tc[2] = pld<R>(Ltmp, vo_l, so + 2u * fsb);     // W first: the row before needs it as its j+1 neighbour... and the stencils
+        // W first: the row before needs it as its j+1 neighbour... and the stencils.  LI == 1: the row just behind the plane is line
+        // dimy by flat index (line 0 of the next plane / of the halo plane behind the last one), as the reference reads j + 1 of
+        // the plane's last line (a NODE_IN cell in the high j face is a row there); nothing of that row is stored
+        const unsigned so_w = LI == 1 ? opq_s(line_so(jrow < p.dimy ? jrow : p.dimy)) : so;
+        L.tc[2] = pld<R>(Ltmp, vo_l, so_w + 2u * fsb);
         // (cached: the rows j+-1 and planes i+-1 read the W of this line again as their neighbour; the other temp fields nt)
         L.tc[0] = pld<R, PART_AUX_NT>(Ltmp, vo_l, so); L.tc[1] = pld<R, PART_AUX_NT>(Ltmp, vo_l, so + fsb); L.tc[3] = pld<R, PART_AUX_NT>(Ltmp, vo_l, so + 3u * fsb);
 #pragma unroll
@@ -1098,7 +1111,9 @@ __global__ void __launch_bounds__(256, 2) k_sweep_part_z(SweepParams<R> p, int n
     PV<R> wprev, wedge;
     if (LI == 1) {
         wprev = pld<R>(Ltmp, vo_l, opq_s(line_so(j0)) + 2u * fsb - rowb);
-        const int jl = j0 + LG < p.dimy ? j0 + LG : p.dimy - 1;
+        // the line behind the group by flat index, as the reference reads j + 1: behind the plane's last line that is line 0 of
+        // the next plane, or of the halo plane behind the last one (a NODE_IN cell in the high j face is a row there)
+        const int jl = j0 + LG < p.dimy ? j0 + LG : p.dimy;
         wedge = pld<R>(Ltmp, vo_l, opq_s(line_so(jl)) + 2u * fsb);
     }
     issue(j0, La);

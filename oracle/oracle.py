@@ -185,12 +185,17 @@ class Oracle:
         self.h = C.c_void_p(self._f("fs3d_oracle_create")(nodes.dimx, nodes.dimy, nodes.dimz,
                                                            nodes.dx, nodes.dy, nodes.dz))
         self._f("fs3d_oracle_set_params")(self.h, *[float(p) for p in params])
+        self.set_nodes(nodes)
+        self._f("fs3d_oracle_init_layers")(self.h)
+
+    def set_nodes(self, nodes):
+        """A new geometry of the same dims (AdiSolver3D::CreateSegments again); the layers are kept."""
+        assert (nodes.dimx, nodes.dimy, nodes.dimz) == self.dims
         arrs = [np.ascontiguousarray(nodes.type, np.uint8), np.ascontiguousarray(nodes.bc_vel, np.uint8),
                 np.ascontiguousarray(nodes.bc_temp, np.uint8)] + [
             np.ascontiguousarray(v, self.dtype) for v in (nodes.vx, nodes.vy, nodes.vz, nodes.T)]
         self._f("fs3d_oracle_set_nodes")(self.h, *[_ptr(a) for a in arrs])
         self._f("fs3d_oracle_create_segments")(self.h)
-        self._f("fs3d_oracle_init_layers")(self.h)
 
     def close(self):
         if self.h:
