@@ -84,6 +84,13 @@ SYMBOLS_MESH_WALLS = {
     "fs3d_voxelize_shape3d_vel_dev": (_i, [_vp] + [_vp] * 6 + [_i, _vp, _i, _d, _d] + [_vp] * 7),
 }
 
+# every symbol include/fs3d_slab_geometry.h declares (the extension header of moving geometry on x-slabs)
+SYMBOLS_SLAB_GEOMETRY = {
+    "fs3d_update_nodes_slab": (_i, [_vp] + [_vp] * 7 + [C.POINTER(_i)]),
+    "fs3d_update_nodes_shape2d_slab": (_i, [_vp] + [_vp] * 4 + [_d] * 4 + [C.POINTER(_i)]),
+    "fs3d_geometry_dead_lines": (_i, [_vp, _i, _vp, C.POINTER(C.c_longlong)]),
+}
+
 _lib = None
 
 
@@ -101,7 +108,7 @@ def load():
             raise RuntimeError("libfs3d_hip.so is not built (%s); run `python -m cmc_fluid_solver_amd.build` "
                                "or __graft_entry__.build()" % LIB_PATH)
         lib = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SYMBOLS.items()) + list(SYMBOLS_MESH_WALLS.items()):
+        for name, (res, args) in list(SYMBOLS.items()) + list(SYMBOLS_MESH_WALLS.items()) + list(SYMBOLS_SLAB_GEOMETRY.items()):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
@@ -200,6 +207,12 @@ class Solver:
         assert tuple(nodes.shape) == tuple(self.gdims)
         return self._update(self.lib.fs3d_update_nodes, *[_p(a) for a in self._node_arrays(nodes)])
 
+    def update_nodes_slab(self, nodes):
+        """update_nodes on an x-slab (or a whole-grid context): `nodes` is the GLOBAL grid, every rank of a group is given the
+        same one between the same two steps and rebuilds the tables of its own planes; no rank waits for another."""
+        assert tuple(nodes.shape) == tuple(self.gdims)
+        return self._update(self.lib.fs3d_update_nodes_slab, *[_p(a) for a in self._node_arrays(nodes)])
+
     def update_nodes_dev(self, type, bc_vel, bc_temp, vx, vy, vz, T):
         """The same from arrays on the context's device: torch tensors (contiguous; uint8 x 3, the context's precision x 4)
         or raw device pointers (int)."""
@@ -225,6 +238,12 @@ class Solver:
         by a kernel.  Same contract as update_nodes."""
         arrs = self._grid2d_arrays(g2)
         return self._update(self.lib.fs3d_update_nodes_shape2d, *[_p(a) for a in arrs], float(dz), float(depth), float(depth_var), float(baseT))
+
+    def update_nodes_shape2d_slab(self, g2, dz, depth, depth_var, baseT):
+        """update_nodes_shape2d on an x-slab (or a whole-grid context): g2 is the GLOBAL 2D grid, given to every rank."""
+        arrs = self._grid2d_arrays(g2)
+        return self._update(self.lib.fs3d_update_nodes_shape2d_slab, *[_p(a) for a in arrs], float(dz), float(depth), float(depth_var),
+                            float(baseT))
 
     @staticmethod
     def _mesh_arrays(g, idx):
@@ -309,6 +328,16 @@ class Solver:
     GEOMETRY_INFO = ("segments_x", "segments_y", "segments_z", "bound_cells", "stale_in_cells", "dead_lines_x", "dead_lines_y",
                      "dead_lines_z", "uniform_groups_x", "uniform_groups_y", "shared_columns_x", "shared_columns_y", "code_digest",
                      "device_allocs_and_frees")
+
+    def dead_lines(self, d):
+        """The dead-line bytes of direction d of the context's planes (uint8, X: [dimy, dimz], Y: [dimx, dimz], Z: [dimx, dimy]);
+        test and measurement aid."""
+        n = C.c_longlong(0)
+        self._chk(self.lib.fs3d_geometry_dead_lines(self.h, d, None, C.byref(n)))
+        out = np.empty(n.value, np.uint8)
+        self._chk(self.lib.fs3d_geometry_dead_lines(self.h, d, _p(out), None))
+        nx, ny, nz = self.dims
+        return out.reshape([(ny, nz), (nx, nz), (nx, ny)][d])
 
     def geometry_info(self):
         """fs3d_geometry_info as a dict (keys: Solver.GEOMETRY_INFO); measurement and test aid."""

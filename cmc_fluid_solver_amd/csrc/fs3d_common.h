@@ -66,7 +66,8 @@ struct SweepParams {
 
 // moving geometry (kernels_geom.hip): what fs3d_update_nodes* keeps between calls, allocated by the first one
 struct fs3d_geom {
-    uint8_t *stage = nullptr;               // 3 x ncell: type, bc_vel, bc_temp of the host entry point
+    uint8_t *stage = nullptr;               // type, bc_vel, bc_temp of the host entry points, dimx_global * plane cells each: a slab context
+                                            // (fs3d_update_nodes*_slab) keeps the byte arrays of the GLOBAL grid, its X lines are read from them
     int *lst[3] = {};                       // per line of X / Y / Z: last index whose type is not NODE_IN (-1: none)
     uint16_t *col[2] = {};                  // [o][group][UCOL_PITCH]: every group's candidate shared column (X, Y)
     uint8_t *cflag[2] = {};                 // [o][group]: bit 0 uniform, bit 1 the pair is

@@ -6,6 +6,9 @@
 // fs3d_update_nodes_shape2d): a moving Shape2D geometry then ships its 2D grid per step, not the 3D node arrays.
 // And the voxelisation of a Shape3D mesh (k_geom_raster_mesh, the flood fill k_geom_fill_z / k_geom_fill_strided, k_geom_mesh_nodes;
 // fs3d_voxelize_shape3d_dev, fs3d_flood_fill_dev, fs3d_update_nodes_shape3d): a moving mesh ships its vertices per step.
+// On an x-slab (fs3d_update_nodes_slab, fs3d_update_nodes_shape2d_slab; include/fs3d_slab_geometry.h) every rank is given the global
+// input and rebuilds the tables of its own planes, without communication: the X lines come from the global byte arrays
+// (k_geom_lines_x_slab, k_geom_codes<true>, k_geom_extrude_slab), everything else runs on the slab's planes.
 //
 // Row kinds without the serial walk of line_kinds (fs3d_tables.h): that walk opens a run at `pos` when cell pos + 1 is
 // NODE_IN and closes it at the first cell after the run that is not NODE_IN; a run that reaches the end of the line is
@@ -25,6 +28,7 @@
 
 #include "fs3d_common.h"
 #include "../../include/fs3d_mesh_walls.h"
+#include "../../include/fs3d_slab_geometry.h"
 
 // counter words of one update (device, read back once)
 enum { GC_NSEG = 0 /* 0..2 */, GC_NBND = 3, GC_STALE = 4, GC_SHARED = 5, GC_LIST = 6, GC_MISMATCH = 7, GC_WORDS = 8 };
@@ -32,6 +36,8 @@ enum { GC_NSEG = 0 /* 0..2 */, GC_NBND = 3, GC_STALE = 4, GC_SHARED = 5, GC_LIST
 // ---------------------------------------------------------------------------------
 // kernels
 // ---------------------------------------------------------------------------------
+
+__device__ __forceinline__ bool geom_interior(int s, int ty, int lst) { return s >= 1 && ty == FS3D_NODE_IN && s < lst; }
 
 // X and Y lines: cells `ss` apart, neighbouring lines along k contiguous -- one thread per line, lanes along k read coalesced.
 // lst[line] = last index whose type is not NODE_IN (-1: none); dead[line] = 1 when the line has no NODE_IN cell (every cell on a
@@ -49,6 +55,47 @@ __global__ void __launch_bounds__(256) k_geom_lines_strided(const uint8_t *__res
     }
     lst[t] = last;
     dead[t] = any_in ? 0 : 1;
+}
+
+// X lines of an x-slab -- the planes [x0, x0 + nx) of a line of n = dimx_global cells, `type` the GLOBAL array: one thread per line as
+// above (o = j, os = dimz, ss = plane).  The kinds of a line come from the whole line, so lst is the global one; a second walk,
+// with lst known, counts what only the whole line tells: its START cells (nseg[0] counts the global segments, GeomTables::nseg)
+// and its shared cells that carry a FREE condition, on whichever slab they lie.  dead[line] is LOCAL, as geom_dead_lines defines
+// it: 1 when no cell of the slab's piece is NODE_IN or on a segment -- a piece that holds only the line's END cell is live, so
+// "no NODE_IN cell" does not do here.  The second walk re-reads what the first one left in the caches.
+__global__ void __launch_bounds__(256) k_geom_lines_x_slab(const uint8_t *__restrict__ type, const uint8_t *__restrict__ bc_vel,
+                                                            const uint8_t *__restrict__ bc_temp, long long nlines, long long ss, int n,
+                                                            int x0, int nx, int *__restrict__ lst, uint8_t *__restrict__ dead,
+                                                            unsigned long long *cnt)
+{
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    unsigned starts = 0, shared = 0;
+    if (t < nlines) {
+        const uint8_t *p = type + t;
+        int last = -1;
+        for (int s = 0; s < n; s++)
+            if (p[(long long)s * ss] != FS3D_NODE_IN) last = s;
+        bool inm = false, in0 = false, live = false;      // INTERIOR(s - 1), INTERIOR(s): cell 0 never is
+        int t0 = p[0];
+        for (int s = 0; s < n; s++) {
+            const int tp = s + 1 < n ? p[(long long)(s + 1) * ss] : 0;
+            const bool inp = s + 1 < n && geom_interior(s + 1, tp, last);
+            if (!in0 && inp) {
+                starts++;
+                const long long id = t + (long long)s * ss;
+                if (inm && (bc_vel[id] == FS3D_BC_FREE || bc_temp[id] == FS3D_BC_FREE)) shared++;
+            }
+            if (s >= x0 && s < x0 + nx) live |= t0 == FS3D_NODE_IN || inp || inm;      // (INTERIOR cells are NODE_IN)
+            inm = in0; in0 = inp; t0 = tp;
+        }
+        lst[t] = last;
+        dead[t] = live ? 0 : 1;
+    }
+    for (int off = 32; off > 0; off >>= 1) { starts += __shfl_down(starts, off, 64); shared += __shfl_down(shared, off, 64); }
+    if ((threadIdx.x & 63) == 0) {
+        if (starts) atomicAdd(&cnt[GC_NSEG], (unsigned long long)starts);
+        if (shared) atomicAdd(&cnt[GC_SHARED], (unsigned long long)shared);
+    }
 }
 
 // Z lines are the contiguous axis: one wave per line, lanes along the line
@@ -70,8 +117,6 @@ __global__ void __launch_bounds__(256) k_geom_lines_z(const uint8_t *__restrict_
     if (lane == 0) { lst[line] = last; dead[line] = any_in ? 0 : 1; }
 }
 
-__device__ __forceinline__ bool geom_interior(int s, int ty, int lst) { return s >= 1 && ty == FS3D_NODE_IN && s < lst; }
-
 // row code of one direction for the cell at index s of its line (n cells); *shared: the cell closes one segment and opens the next
 __device__ __forceinline__ int geom_row_code(int s, int n, int t0, int tm, int tp, int lst, int bits, bool *shared)
 {
@@ -87,10 +132,14 @@ __device__ __forceinline__ int geom_row_code(int s, int n, int t0, int tm, int t
 
 // The cell codes of all three directions in one pass, with the counts the host needs: START cells per direction (= segments),
 // BOUND / VALVE cells, NODE_IN cells on no segment of a direction (stale_in_cells), shared cells that carry a FREE condition.
+// SLAB: the dimx planes from x0 of a grid of gx planes; `type` addresses the slab's first cell INSIDE the global array (the planes
+// x0 - 1 and x0 + dimx are read where they exist) and lstx is the global line's.  The X row code takes the global index; the START
+// cells and the shared cells of X are those of k_geom_lines_x_slab, which sees the whole line, and are not counted here.
+template <bool SLAB>
 __global__ void __launch_bounds__(256) k_geom_codes(const uint8_t *__restrict__ type, const uint8_t *__restrict__ bc_vel,
                                                      const uint8_t *__restrict__ bc_temp, const int *__restrict__ lstx,
                                                      const int *__restrict__ lsty, const int *__restrict__ lstz, int dimx, int dimy,
-                                                     int dimz, uint16_t *__restrict__ code, unsigned long long *cnt)
+                                                     int dimz, int x0, int gx, uint16_t *__restrict__ code, unsigned long long *cnt)
 {
     const long long plane = (long long)dimy * dimz, ncell = plane * dimx;
     unsigned acc[6] = {0, 0, 0, 0, 0, 0};
@@ -101,14 +150,17 @@ __global__ void __launch_bounds__(256) k_geom_codes(const uint8_t *__restrict__ 
         if (bc_vel[l] == FS3D_BC_FREE) bits |= ROW_VELFREE;
         if (bc_temp[l] == FS3D_BC_FREE) bits |= ROW_TEMPFREE;
         bool sh[3];
-        const int rx = geom_row_code(i, dimx, t0, i >= 1 ? type[l - plane] : 0, i + 1 < dimx ? type[l + plane] : 0,
+        const int sx = SLAB ? x0 + i : i, nx = SLAB ? gx : dimx;
+        const int rx = geom_row_code(sx, nx, t0, sx >= 1 ? type[l - plane] : 0, sx + 1 < nx ? type[l + plane] : 0,
                                      lstx[rem], bits, &sh[0]);
         const int ry = geom_row_code(j, dimy, t0, j >= 1 ? type[l - dimz] : 0, j + 1 < dimy ? type[l + dimz] : 0,
                                      lsty[(long long)i * dimz + k], bits, &sh[1]);
         const int rz = geom_row_code(k, dimz, t0, k >= 1 ? type[l - 1] : 0, k + 1 < dimz ? type[l + 1] : 0,
                                      lstz[(long long)i * dimy + j], bits, &sh[2]);
         code[l] = (uint16_t)(rx | (ry << 4) | (rz << 8) | ((t0 & 3) << CODE_TYPE_SHIFT));
-        acc[0] += (rx & 3) == ROW_START; acc[1] += (ry & 3) == ROW_START; acc[2] += (rz & 3) == ROW_START;
+        if constexpr (!SLAB) acc[0] += (rx & 3) == ROW_START;
+        else sh[0] = false;
+        acc[1] += (ry & 3) == ROW_START; acc[2] += (rz & 3) == ROW_START;
         acc[3] += t0 == FS3D_NODE_BOUND || t0 == FS3D_NODE_VALVE;
         if (t0 == FS3D_NODE_IN) acc[4] += ((rx & 3) == ROW_SKIP) + ((ry & 3) == ROW_SKIP) + ((rz & 3) == ROW_SKIP);
         acc[5] += (sh[0] || sh[1] || sh[2]) && bits != 0;
@@ -316,18 +368,28 @@ __device__ __forceinline__ ExNode extrude_node(int k, int c2, float velx, float 
 // value arrays to 16): one dword per byte array and 16-byte stores for the value arrays (one per array in fp32, two in fp64);
 // V == 1: cell by cell.  az: vz of the V cells where a kernel has one (else vz is 0).  Stores are nontemporal: the geometry kernels
 // read these arrays next, but only after the whole grid has been written.
-template <typename R, int V, bool TYPE>
-__device__ __forceinline__ void store_nodes(long long l, unsigned wt, unsigned wv, unsigned wb, const R (&ax)[V], const R (&ay)[V],
-                                            const R (&aT)[V], uint8_t *__restrict__ type, uint8_t *__restrict__ bc_vel,
-                                            uint8_t *__restrict__ bc_temp, R *__restrict__ vx, R *__restrict__ vy, R *__restrict__ vz,
-                                            R *__restrict__ T, const R *az = nullptr)
+template <int V, bool TYPE>
+__device__ __forceinline__ void store_node_bytes(long long l, unsigned wt, unsigned wv, unsigned wb, uint8_t *__restrict__ type,
+                                                 uint8_t *__restrict__ bc_vel, uint8_t *__restrict__ bc_temp)
 {
-    constexpr int P = 16 / sizeof(R);                  // values per 16-byte store
-    typedef R RP __attribute__((ext_vector_type(P)));
     if constexpr (V == 4) {
         if constexpr (TYPE) __builtin_nontemporal_store(wt, (unsigned *)(type + l));
         __builtin_nontemporal_store(wv, (unsigned *)(bc_vel + l));
         __builtin_nontemporal_store(wb, (unsigned *)(bc_temp + l));
+    } else {
+        if constexpr (TYPE) __builtin_nontemporal_store((uint8_t)wt, type + l);
+        __builtin_nontemporal_store((uint8_t)wv, bc_vel + l);
+        __builtin_nontemporal_store((uint8_t)wb, bc_temp + l);
+    }
+}
+
+template <typename R, int V>
+__device__ __forceinline__ void store_node_values(long long l, const R (&ax)[V], const R (&ay)[V], const R (&aT)[V], R *__restrict__ vx,
+                                                  R *__restrict__ vy, R *__restrict__ vz, R *__restrict__ T, const R *az = nullptr)
+{
+    constexpr int P = 16 / sizeof(R);                  // values per 16-byte store
+    typedef R RP __attribute__((ext_vector_type(P)));
+    if constexpr (V == 4) {
 #pragma unroll
         for (int h = 0; h < V; h += P) {
             RP x, y, z, w;
@@ -339,14 +401,21 @@ __device__ __forceinline__ void store_nodes(long long l, unsigned wt, unsigned w
             __builtin_nontemporal_store(w, (RP *)(T + l + h));
         }
     } else {
-        if constexpr (TYPE) __builtin_nontemporal_store((uint8_t)wt, type + l);
-        __builtin_nontemporal_store((uint8_t)wv, bc_vel + l);
-        __builtin_nontemporal_store((uint8_t)wb, bc_temp + l);
         __builtin_nontemporal_store(ax[0], vx + l);
         __builtin_nontemporal_store(ay[0], vy + l);
         __builtin_nontemporal_store(az ? az[0] : R(0), vz + l);
         __builtin_nontemporal_store(aT[0], T + l);
     }
+}
+
+template <typename R, int V, bool TYPE>
+__device__ __forceinline__ void store_nodes(long long l, unsigned wt, unsigned wv, unsigned wb, const R (&ax)[V], const R (&ay)[V],
+                                            const R (&aT)[V], uint8_t *__restrict__ type, uint8_t *__restrict__ bc_vel,
+                                            uint8_t *__restrict__ bc_temp, R *__restrict__ vx, R *__restrict__ vy, R *__restrict__ vz,
+                                            R *__restrict__ T, const R *az = nullptr)
+{
+    store_node_bytes<V, TYPE>(l, wt, wv, wb, type, bc_vel, bc_temp);
+    store_node_values<R, V>(l, ax, ay, aT, vx, vy, vz, T, az);
 }
 
 // Pure store kernel, 19 bytes per cell in fp32 and 35 in fp64.  One thread writes V consecutive k of one column (store_nodes;
@@ -376,6 +445,36 @@ __global__ void __launch_bounds__(256) k_geom_extrude(const float *__restrict__ 
         ax[q] = (R)n.vx; ay[q] = (R)n.vy; aT[q] = (R)n.T;
     }
     store_nodes<R, V, true>(l, wt, wv, wb, ax, ay, aT, type, bc_vel, bc_temp, vx, vy, vz, T);
+}
+
+// The extrusion on an x-slab: `ncol` counts the columns of the GLOBAL grid and the three byte arrays are global (the X lines of the
+// slab's tables are read from them), the four value arrays hold the slab's columns [col0, col0 + ncol_own) only -- a thread of
+// another slab's column stores its 3 bytes per cell and no values.  The same node per cell and the same two store shapes.
+template <typename R, int V>
+__global__ void __launch_bounds__(256) k_geom_extrude_slab(const float *__restrict__ velx, const float *__restrict__ vely, const float *__restrict__ T2,
+                                                            const int *__restrict__ bottom, const uint8_t *__restrict__ cell, long long ncol,
+                                                            long long col0, long long ncol_own, int dimz, int A, float baseT,
+                                                            uint8_t *__restrict__ type, uint8_t *__restrict__ bc_vel, uint8_t *__restrict__ bc_temp,
+                                                            R *__restrict__ vx, R *__restrict__ vy, R *__restrict__ vz, R *__restrict__ T)
+{
+    const int nq = dimz / V;                           // V == 4: dimz % 4 == 0
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= ncol * nq) return;
+    const long long col = t / nq;
+    const int k0 = (int)(t - col * nq) * V;
+    const int c2 = cell[col], bot = bottom[col];
+    const float ux = velx[col], uy = vely[col], t2 = T2[col];
+    unsigned wt = 0, wv = 0, wb = 0;
+    R ax[V], ay[V], aT[V];
+#pragma unroll
+    for (int q = 0; q < V; q++) {
+        const ExNode n = extrude_node(k0 + q, c2, ux, uy, t2, bot, A, baseT);
+        wt |= (unsigned)n.type << (8 * q); wv |= (unsigned)n.bv << (8 * q); wb |= (unsigned)n.bt << (8 * q);
+        ax[q] = (R)n.vx; ay[q] = (R)n.vy; aT[q] = (R)n.T;
+    }
+    store_node_bytes<V, true>(col * dimz + k0, wt, wv, wb, type, bc_vel, bc_temp);      // < ncol * dimz: the byte arrays' size
+    if (col >= col0 && col < col0 + ncol_own)                                            // (col - col0) * dimz + k0 < ncol_own * dimz: the value arrays'
+        store_node_values<R, V>((col - col0) * dimz + k0, ax, ay, aT, vx, vy, vz, T);
 }
 
 // ---- Shape3D meshes: Grid3D::Build (Grid3D.cpp:859-903) on the device ------------------------------------------------------------
@@ -897,11 +996,14 @@ void fs3d_geom_destroy(fs3d_ctx *c)
     if (g.mesh_owner) hipFree(g.mesh_owner);
 }
 
+// cells of the global grid: the byte arrays of an update cover them (a single context: its own cells)
+static inline long long geom_gcell(const fs3d_ctx *c) { return (long long)c->dimx_global * c->plane; }
+
 // the buffers an update keeps: allocated by the first one
 static fs3d_status geom_prepare(fs3d_ctx *c, bool need_stage)
 {
     fs3d_geom &g = c->geom;
-    if (need_stage && !g.stage) GMALLOC(c, &g.stage, (size_t)3 * c->ncell);
+    if (need_stage && !g.stage) GMALLOC(c, &g.stage, (size_t)3 * geom_gcell(c));      // (an x-slab: the byte arrays of the global grid)
     if (g.cnt) return FS3D_OK;
     for (int d = 0; d < 3; d++) GMALLOC(c, &g.lst[d], (size_t)geom_lines(c, d).nlines * sizeof(int));
     size_t host_bytes = GC_WORDS * sizeof(unsigned long long);
@@ -969,30 +1071,41 @@ static fs3d_status geom_columns(fs3d_ctx *c, int d)
     return gev_sync(c);
 }
 
+// The three byte arrays cover the global grid; the tables are those of the context's planes.  slab (fs3d_update_nodes*_slab): the
+// X lines are read from the global arrays (k_geom_lines_x_slab, k_geom_codes<true>); everything else runs on the local planes.
+// Without it the context is the whole grid (the other entries refuse a slab) and line and context coincide.
+// slab_entry: the name of the slab entry that was called (its refusals carry it), or null.
 template <typename R>
-static fs3d_status update_nodes_impl(fs3d_ctx *c, const uint8_t *type, const uint8_t *bc_vel, const uint8_t *bc_temp, int n_seg_out[3])
+static fs3d_status update_nodes_impl(fs3d_ctx *c, const uint8_t *gtype, const uint8_t *gbc_vel, const uint8_t *gbc_temp, const char *slab_entry,
+                                     int n_seg_out[3])
 {
+    const bool slab = slab_entry != nullptr;
     fs3d_geom &g = c->geom;
-    const long long ncell = c->ncell;
+    const long long ncell = c->ncell, first = (long long)c->x_offset * c->plane;
+    const uint8_t *type = gtype + first, *bc_vel = gbc_vel + first, *bc_temp = gbc_temp + first;
+    const std::string name = slab ? slab_entry : "fs3d_update_nodes";
     HIPCHK(c, hipMemsetAsync(g.cnt, 0, GC_WORDS * sizeof(unsigned long long), c->stream));
     for (int d = 0; d < 3; d++) {
         const GeomLines L = geom_lines(c, d);
-        if (d < 2)
+        if (d == 0 && slab)
+            hipLaunchKernelGGL(k_geom_lines_x_slab, dim3(grid_for(L.nlines, 1 << 30)), dim3(256), 0, c->stream, gtype, gbc_vel, gbc_temp,
+                               L.nlines, L.ss, c->dimx_global, c->x_offset, c->dimx, g.lst[d], c->dead[d], g.cnt);
+        else if (d < 2)
             hipLaunchKernelGGL(k_geom_lines_strided, dim3(grid_for(L.nlines, 1 << 30)), dim3(256), 0, c->stream, type, L.n_o, c->dimz,
                                L.os, L.ss, L.n, g.lst[d], c->dead[d]);
         else
             hipLaunchKernelGGL(k_geom_lines_z, dim3(grid_for(L.nlines * 64, 1 << 30)), dim3(256), 0, c->stream, type, L.nlines, c->dimz,
                                g.lst[d], c->dead[d]);
     }
-    hipLaunchKernelGGL(k_geom_codes, dim3(grid_for(ncell)), dim3(256), 0, c->stream, type, bc_vel, bc_temp, g.lst[0], g.lst[1],
-                       g.lst[2], c->dimx, c->dimy, c->dimz, c->code, g.cnt);
+    hipLaunchKernelGGL(slab ? k_geom_codes<true> : k_geom_codes<false>, dim3(grid_for(ncell)), dim3(256), 0, c->stream, type, bc_vel, bc_temp,
+                       g.lst[0], g.lst[1], g.lst[2], c->dimx, c->dimy, c->dimz, c->x_offset, c->dimx_global, c->code, g.cnt);
     HIPCHK(c, hipGetLastError());
     unsigned long long *hc = (unsigned long long *)g.host;
     HIPCHK(c, hipMemcpyAsync(hc, g.cnt, GC_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
     GTRY(gev_sync(c));
     if (hc[GC_SHARED])
         return fail(c, FS3D_ERR_UNSUPPORTED,
-                     "fs3d_update_nodes: a cell with a FREE boundary condition closes one segment and opens the next "
+                     name + ": a cell with a FREE boundary condition closes one segment and opens the next "
                      "on the same line (two rows on one cell; the reference's result there depends on thread timing)");
     const long long nseg[3] = {(long long)hc[0], (long long)hc[1], (long long)hc[2]};
     const long long nbnd = (long long)hc[GC_NBND];
@@ -1019,9 +1132,9 @@ static fs3d_status update_nodes_impl(fs3d_ctx *c, const uint8_t *type, const uin
     HIPCHK(c, hipMemcpyAsync(hc, g.cnt, GC_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
     GTRY(gev_sync(c));
     if ((long long)hc[GC_LIST] != nbnd)
-        return fail(c, FS3D_ERR_HIP, "fs3d_update_nodes: the BOUND / VALVE list does not hold the counted cells");
+        return fail(c, FS3D_ERR_HIP, name + ": the BOUND / VALVE list does not hold the counted cells");
     if (hc[GC_MISMATCH])
-        return fail(c, FS3D_ERR_HIP, "fs3d_update_nodes: two different shared code columns have the same hash; tables not usable");
+        return fail(c, FS3D_ERR_HIP, name + ": two different shared code columns have the same hash; tables not usable");
     c->n_bnd = (int)nbnd;
     for (int d = 0; d < 3; d++) { c->nseg[d] = (int)nseg[d]; if (n_seg_out) n_seg_out[d] = (int)nseg[d]; }
     return FS3D_OK;
@@ -1041,11 +1154,12 @@ struct NodeArrays {
     }
 };
 
-// the context's own: the three byte arrays in the staging buffer, the four value fields in place in the node-value table
+// the context's own: the three byte arrays (of the global grid) in the staging buffer, the four value fields (of its planes) in
+// place in the node-value table
 static NodeArrays geom_own_arrays(const fs3d_ctx *c)
 {
     uint8_t *sg = c->geom.stage;
-    NodeArrays a = {sg, sg + c->ncell, sg + 2 * c->ncell, {}};
+    NodeArrays a = {sg, sg + geom_gcell(c), sg + 2 * geom_gcell(c), {}};
     for (int v = 0; v < 4; v++) a.v[v] = (char *)c->node + (size_t)v * c->nstride * c->esize;
     return a;
 }
@@ -1096,7 +1210,7 @@ static fs3d_status extrude_check(fs3d_ctx *c, ExtrudeIn &in, const char *name)
     fs3d_geom &g = c->geom;
     if (!extrude_active_dimz(in.dz, in.depth, &in.A) || in.A < 2 || in.A > c->dimz)
         return fail(c, FS3D_ERR_INVALID, std::string(name) + ": active_dimz = ceil(depth / dz) + 1 must lie in 2 .. dimz");
-    const size_t ncol = (size_t)c->dimx * c->dimy;
+    const size_t ncol = (size_t)c->dimx_global * c->dimy;      // the 2D grid covers the global plane (a single context: its own)
     HIPCHK(c, hipSetDevice(c->device));
     if (!g.ex_host) HIPCHK(c, hipHostMalloc(&g.ex_host, ex_bytes(ncol), hipHostMallocDefault));
     if (!g.ex_dev) {                                      // (a failure leaves the pointer null: the next call allocates again)
@@ -1106,7 +1220,7 @@ static fs3d_status extrude_check(fs3d_ctx *c, ExtrudeIn &in, const char *name)
     char *h = (char *)g.ex_host;
     int *bottom = (int *)(h + ex_off_bottom(ncol));
     if (g.ex_dz != in.dz || g.ex_depth != in.depth || g.ex_depth_var != in.depth_var) {      // (a NaN depth_var: recomputed every call)
-        extrude_bottom_table(c->dimx, c->dimy, in.A, in.depth_var, bottom);
+        extrude_bottom_table(c->dimx_global, c->dimy, in.A, in.depth_var, bottom);
         g.ex_dz = in.dz; g.ex_depth = in.depth; g.ex_depth_var = in.depth_var; g.ex_bottom_valid = false;
     }
     for (size_t q = 0; q < ncol; q++) {
@@ -1121,17 +1235,27 @@ static fs3d_status extrude_check(fs3d_ctx *c, ExtrudeIn &in, const char *name)
     return FS3D_OK;
 }
 
-// the column records to the device and the kernel, on the context's stream; not synchronised
+// the column records to the device and the kernel, on the context's stream; not synchronised.  slab: the byte arrays of `a` cover
+// the global grid, its value arrays the context's planes (k_geom_extrude_slab); else all seven cover the same cells.
 template <typename R>
-static fs3d_status extrude_launch(fs3d_ctx *c, const ExtrudeIn &in, const NodeArrays &a)
+static fs3d_status extrude_launch(fs3d_ctx *c, const ExtrudeIn &in, const NodeArrays &a, bool slab = false)
 {
     fs3d_geom &g = c->geom;
-    const size_t ncol = (size_t)c->dimx * c->dimy;
+    const size_t ncol = (size_t)c->dimx_global * c->dimy;
     const char *d = (const char *)g.ex_dev;
     HIPCHK(c, hipMemcpyAsync(g.ex_dev, g.ex_host, g.ex_bottom_valid ? ex_off_cell(ncol) + ncol : ex_bytes(ncol), hipMemcpyHostToDevice, c->stream));
     g.ex_bottom_valid = true;
     const bool vec = a.vec4(c->dimz);
     const long long nthr = (long long)ncol * (vec ? c->dimz / 4 : c->dimz);
+    if (slab) {
+        auto ks = vec ? k_geom_extrude_slab<R, 4> : k_geom_extrude_slab<R, 1>;
+        hipLaunchKernelGGL(ks, dim3(grid_for(nthr, 1 << 30)), dim3(256), 0, c->stream, (const float *)d, (const float *)(d + 4 * ncol),
+                           (const float *)(d + 8 * ncol), (const int *)(d + ex_off_bottom(ncol)), (const uint8_t *)(d + ex_off_cell(ncol)),
+                           (long long)ncol, (long long)c->x_offset * c->dimy, (long long)c->dimx * c->dimy, c->dimz, in.A, (float)in.baseT,
+                           a.type, a.bc_vel, a.bc_temp, (R *)a.v[0], (R *)a.v[1], (R *)a.v[2], (R *)a.v[3]);
+        HIPCHK(c, hipGetLastError());
+        return FS3D_OK;
+    }
     auto kern = vec ? k_geom_extrude<R, 4> : k_geom_extrude<R, 1>;
     hipLaunchKernelGGL(kern, dim3(grid_for(nthr, 1 << 30)), dim3(256), 0, c->stream, (const float *)d, (const float *)(d + 4 * ncol),
                        (const float *)(d + 8 * ncol), (const int *)(d + ex_off_bottom(ncol)), (const uint8_t *)(d + ex_off_cell(ncol)),
@@ -1307,9 +1431,13 @@ static fs3d_status geom_refuse(fs3d_ctx *c, const char *name, bool any_null, con
 // 5. the entry puts the three byte arrays and the four value fields on the device; 6. update_end.
 typedef std::chrono::steady_clock::time_point geom_clock;
 
-static fs3d_status update_refuse(fs3d_ctx *c, const char *name, bool any_null)
+static fs3d_status update_refuse(fs3d_ctx *c, const char *name, bool any_null, bool slab = false)
 {
-    GTRY(geom_refuse(c, name, any_null, "moving geometry is"));
+    if (slab) {                                         // the slab entries: the same refusals but the one of a slab
+        if (!c) return FS3D_ERR_INVALID;
+        if (any_null) return fail(c, FS3D_ERR_INVALID, std::string(name) + ": NULL array");
+    } else
+        GTRY(geom_refuse(c, name, any_null, "moving geometry is"));
     if (!c->uploaded_once)
         return fail(c, FS3D_ERR_INVALID, std::string(name) + ": the first geometry comes through fs3d_upload_nodes; upload nodes first");
     return FS3D_OK;
@@ -1328,12 +1456,12 @@ static fs3d_status update_begin(fs3d_ctx *c, bool need_stage)
 // The tables from the byte arrays (the value fields are in the node-value table by now), the device time and the CreateSegments
 // event.  `produced`: what the kernels of phase 5 returned; their failure is waited for, and its time is not counted.
 static fs3d_status update_end(fs3d_ctx *c, geom_clock t0, fs3d_status produced, const uint8_t *type, const uint8_t *bc_vel, const uint8_t *bc_temp,
-                              int n_seg_out[3])
+                              int n_seg_out[3], const char *slab_entry = nullptr)
 {
     fs3d_status st = produced;
     if (st == FS3D_OK)
-        st = c->prec == FS3D_F32 ? update_nodes_impl<float>(c, type, bc_vel, bc_temp, n_seg_out)
-                                 : update_nodes_impl<double>(c, type, bc_vel, bc_temp, n_seg_out);
+        st = c->prec == FS3D_F32 ? update_nodes_impl<float>(c, type, bc_vel, bc_temp, slab_entry, n_seg_out)
+                                 : update_nodes_impl<double>(c, type, bc_vel, bc_temp, slab_entry, n_seg_out);
     hipStreamSynchronize(c->stream);                      // (a failure half way: the caller's arrays are not read after the call returns)
     gev_collect(c);
     if (produced) return produced;
@@ -1387,6 +1515,43 @@ extern "C" fs3d_status fs3d_update_nodes_shape2d(fs3d_ctx *c, const uint8_t *cel
     const NodeArrays own = geom_own_arrays(c);
     const fs3d_status st = c->prec == FS3D_F32 ? extrude_launch<float>(c, in, own) : extrude_launch<double>(c, in, own);
     return update_end(c, t0, st, own.type, own.bc_vel, own.bc_temp, n_seg_out);
+}
+
+// ---- the slab entries (include/fs3d_slab_geometry.h): every rank is given the global input and rebuilds the tables of its own
+// planes on its own stream; no rank talks to another one
+extern "C" fs3d_status fs3d_update_nodes_slab(fs3d_ctx *c, const uint8_t *type, const uint8_t *bc_vel, const uint8_t *bc_temp,
+                                              const void *vx, const void *vy, const void *vz, const void *T, int n_seg_out[3])
+{
+    const char *name = "fs3d_update_nodes_slab";
+    GTRY(update_refuse(c, name, !type || !bc_vel || !bc_temp || !vx || !vy || !vz || !T, true));
+    const geom_clock t0 = std::chrono::steady_clock::now();
+    HIPCHK(c, hipSetDevice(c->device));
+    GTRY(update_begin(c, true));
+    const NodeArrays own = geom_own_arrays(c);
+    const size_t gcell = (size_t)geom_gcell(c), first = (size_t)c->x_offset * c->plane;
+    HIPCHK(c, hipMemcpyAsync(own.type, type, gcell, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(own.bc_vel, bc_vel, gcell, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(own.bc_temp, bc_temp, gcell, hipMemcpyHostToDevice, c->stream));
+    // the value fields of the slab's planes only
+    const void *val[4] = {vx, vy, vz, T};
+    for (int v = 0; v < 4; v++)
+        HIPCHK(c, hipMemcpyAsync(own.v[v], (const char *)val[v] + first * c->esize, (size_t)c->ncell * c->esize, hipMemcpyHostToDevice, c->stream));
+    return update_end(c, t0, FS3D_OK, own.type, own.bc_vel, own.bc_temp, n_seg_out, name);
+}
+
+extern "C" fs3d_status fs3d_update_nodes_shape2d_slab(fs3d_ctx *c, const uint8_t *cell2d, const float *velx2d, const float *vely2d, const float *T2d,
+                                                      double dz, double depth, double depth_var, double baseT, int n_seg_out[3])
+{
+    const char *name = "fs3d_update_nodes_shape2d_slab";
+    GTRY(update_refuse(c, name, !cell2d || !velx2d || !vely2d || !T2d, true));
+    const geom_clock t0 = std::chrono::steady_clock::now();
+    HIPCHK(c, hipSetDevice(c->device));
+    ExtrudeIn in = {cell2d, velx2d, vely2d, T2d, dz, depth, depth_var, baseT, 0};
+    GTRY(extrude_check(c, in, name));
+    GTRY(update_begin(c, true));
+    const NodeArrays own = geom_own_arrays(c);
+    const fs3d_status st = c->prec == FS3D_F32 ? extrude_launch<float>(c, in, own, true) : extrude_launch<double>(c, in, own, true);
+    return update_end(c, t0, st, own.type, own.bc_vel, own.bc_temp, n_seg_out, name);
 }
 
 extern "C" fs3d_status fs3d_extrude_shape2d_dev(fs3d_ctx *c, const uint8_t *cell2d, const float *velx2d, const float *vely2d, const float *T2d,
@@ -1506,6 +1671,20 @@ extern "C" fs3d_status fs3d_last_update_device_ms(fs3d_ctx *c, float *ms_out)
 {
     if (!c || !ms_out) return FS3D_ERR_INVALID;
     *ms_out = c->geom.last_dev_ms;
+    return FS3D_OK;
+}
+
+extern "C" fs3d_status fs3d_geometry_dead_lines(fs3d_ctx *c, int dir, uint8_t *dead_out, long long *n_lines_out)
+{
+    if (!c) return FS3D_ERR_INVALID;
+    if (dir < 0 || dir > 2) return fail(c, FS3D_ERR_INVALID, "fs3d_geometry_dead_lines: bad direction");
+    if (!c->have_nodes) return fail(c, FS3D_ERR_INVALID, "fs3d_geometry_dead_lines: upload nodes first");
+    const long long n = geom_lines(c, dir).nlines;
+    if (n_lines_out) *n_lines_out = n;
+    if (!dead_out) return FS3D_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpyAsync(dead_out, c->dead[dir], (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     return FS3D_OK;
 }
 

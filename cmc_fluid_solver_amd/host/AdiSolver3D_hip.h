@@ -15,6 +15,7 @@
 
 #include "../../include/fs3d.h"
 #include "../../include/fs3d_mesh_walls.h"
+#include "../../include/fs3d_slab_geometry.h"
 
 namespace fs3d {
 
@@ -80,33 +81,36 @@ public:
                               grid.vz.data(), grid.T.data(), numSegs));
         chk(fs3d_init_layers_from_nodes(ctx_));
         dimx = x1 - x0; dimy = grid.dimy; dimz = grid.dimz;
+        slab_ = x0 != 0 || x1 != grid.dimx;
     }
     // multi-GPU: join the RCCL group (one process per GPU); id = 128-byte ncclUniqueId from UniqueId() on rank 0
     static void UniqueId(void *id128) { if (fs3d_comm_unique_id(id128) != FS3D_OK) throw std::runtime_error("fs3d_comm_unique_id failed"); }
-    void JoinGroup(const void *id128, int rank, int nranks) { chk(fs3d_comm_init(ctx_, id128, rank, nranks)); }
+    void JoinGroup(const void *id128, int rank, int nranks) { chk(fs3d_comm_init(ctx_, id128, rank, nranks)); slab_ = true; }
     // multi-GPU, one process (the reference's GPUplan mode, "GPU n"): one solver per slab, each driven by its own host thread,
     // joined by an in-process group; every collective call (TimeStep, ...) is then made by all the threads
     static void *CreateLocalGroup(int nranks) { void *g = nullptr; if (fs3d_local_group_create(nranks, &g) != FS3D_OK) throw std::runtime_error("fs3d_local_group_create failed"); return g; }
     static void DestroyLocalGroup(void *g) { fs3d_local_group_destroy(g); }
-    void JoinLocalGroup(void *group, int rank) { chk(fs3d_comm_init_local(ctx_, group, rank)); }
+    void JoinLocalGroup(void *group, int rank) { chk(fs3d_comm_init_local(ctx_, group, rank)); slab_ = true; }
 
-    // AdiSolver3D::CreateSegments again, for a grid whose walls have moved (same dims; single GPU): the device tables are rebuilt
-    // by kernels, the layers are kept
+    // AdiSolver3D::CreateSegments again, for a grid whose walls have moved (same dims): the device tables are rebuilt by kernels,
+    // the layers are kept.  A solver with a slab range or in a group (fs3d_update_nodes_slab): `grid` is the GLOBAL grid, every
+    // rank is given the same one between the same two steps and rebuilds the tables of its own planes; no rank waits for another.
     void UpdateGrid(const Grid3D<FTYPE> &grid)
     {
         grid_ = &grid;
-        chk(fs3d_update_nodes(ctx_, grid.type.data(), grid.bc_vel.data(), grid.bc_temp.data(), grid.vx.data(), grid.vy.data(),
+        chk((slab_ ? fs3d_update_nodes_slab : fs3d_update_nodes)(ctx_, grid.type.data(), grid.bc_vel.data(), grid.bc_temp.data(), grid.vx.data(), grid.vy.data(),
                               grid.vz.data(), grid.T.data(), numSegs));
     }
     // The same for a grid that is the extrusion of a 2D grid (Grid3D::Prepare2D, Grid3D.cpp:608-668): g2 as it stands after
     // g2.Prepare(t) is extruded on the device -- its cell types and three floats per column travel, no 3D node array is built or
     // copied on the host.  G2 = fs3d::Grid2D (host/Shape2D.h); dz, depth, depth_var as ExtrudeShape2D takes them, baseT the grid's
     // of Init.  The host Grid3D given to Init is NOT kept current by this call: only its dims and baseT are read afterwards.
+    // On a slab or in a group as UpdateGrid: g2 is the global 2D grid (fs3d_update_nodes_shape2d_slab).
     template <typename G2>
     void UpdateGridExtruded(const G2 &g2, double dz, double depth, double depth_var)
     {
         if (g2.dimx != grid_->dimx || g2.dimy != grid_->dimy) throw std::runtime_error("UpdateGridExtruded: the 2D grid does not have the 3D grid's dims");
-        chk(fs3d_update_nodes_shape2d(ctx_, g2.cell.data(), g2.velx.data(), g2.vely.data(), g2.T.data(), dz, depth, depth_var, grid_->baseT, numSegs));
+        chk((slab_ ? fs3d_update_nodes_shape2d_slab : fs3d_update_nodes_shape2d)(ctx_, g2.cell.data(), g2.velx.data(), g2.vely.data(), g2.T.data(), dz, depth, depth_var, grid_->baseT, numSegs));
     }
     // The same for the grid of a Shape3D mesh (Grid3D::Prepare3D_Shape, Grid3D.cpp:905-946): the sub-frame's vertices in grid
     // coordinates (Shape3D::SubFrame(t), host/Shape3D.h) and the triangle indices travel, the mesh is voxelised and flood-filled on
@@ -171,6 +175,7 @@ private:
     void chk(fs3d_status st) { if (st != FS3D_OK) throw std::runtime_error(fs3d_last_error(ctx_)); }
     fs3d_ctx *ctx_ = nullptr;
     const Grid3D<FTYPE> *grid_ = nullptr;
+    bool slab_ = false;                                 // Init with a slab range, or a member of a group: the geometry updates take the slab entries
 };
 
 }  // namespace fs3d

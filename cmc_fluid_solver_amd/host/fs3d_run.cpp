@@ -7,14 +7,14 @@
 //   * writes <output prefix>_res.nc through host/NetCDF3.h every out_time_steps steps (GetLayer).
 // `transpose`, `decompose`, `blocking n` of the reference are accepted and ignored (backend tuning switches); `CSV`
 // switches the closing timing table to the reference's comma-separated form.
-// `moving` (single GPU, in_fmt Shape2D): the walls follow the frames of the input -- per step grid2D->Prepare(t), the extrusion and
+// `moving` (in_fmt Shape2D; one GPU, or GPU n --same-device: run_slabs below): the walls follow the frames of the input -- per step grid2D->Prepare(t), the extrusion and
 //   CreateSegments on the device (UpdateGridExtruded: the 2D grid travels, the node arrays are written by a kernel), UpdateBoundaries,
 //   TimeStep, the output, ClearOutterCells: the loop of the reference's 2D driver (FluidSolver2D.cpp:130-133) with the 3D classes'
 //   mechanism (AdiSolver3D.cpp:382-385, Solver3D.cpp:41-44).
 //   --host-extrusion: the extrusion on the host (ExtrudeShape2D into the Grid3D, then UpdateGrid with its seven arrays) -- the same
 //   results bit for bit; kept for A/B timing and as the checker of the device extrusion.
 //   --time-geometry: one more line after the timing table, the host clock per step around Prepare, the host extrusion and the update call.
-// `moving-mesh` (single GPU, in_fmt Shape3D): the same loop for a triangle mesh per frame -- per step Shape3D::SubFrame(t) (the
+// `moving-mesh` (in_fmt Shape3D; one GPU, or GPU n with --host-voxels: run_slabs below): the same loop for a triangle mesh per frame -- per step Shape3D::SubFrame(t) (the
 //   interpolation of Grid3D::Prepare3D_Shape, Grid3D.cpp:905-946), then the voxelisation, the flood fill and CreateSegments on the
 //   device (UpdateGridShape3D: the vertices travel).  The frame counter of the progress line stays 0, as Grid3D::GetFrame gives it
 //   for a Shape3D input.  `moving` keeps its meaning: Shape2D inputs only.
@@ -82,17 +82,22 @@ struct RunOptions {
 };
 
 template <typename FTYPE>
-static int run_slabs(const fs3d::Grid3D<FTYPE> &grid, const RunGeom &geo, const std::string &prefix, const fs3d::Config &cfg, int nslabs,
-                     bool same_device, long max_steps, bool csv, bool time_output);
+static int run_slabs(fs3d::Grid3D<FTYPE> &grid, fs3d::Grid2D &g2, fs3d::Shape3D &sh3, const RunGeom &geo, const std::string &prefix,
+                     const fs3d::Config &cfg, const RunOptions &o);
 
 template <typename FTYPE>
 static int run(const std::string &data, const std::string &prefix, const fs3d::Config &cfg, const RunOptions &o)
 {
     if (o.moving && cfg.in_fmt != "Shape2D") throw std::runtime_error("moving: only in_fmt Shape2D inputs move (this one is " + cfg.in_fmt + ")");
-    if (o.moving && o.nslabs > 1) throw std::runtime_error("moving: single GPU only (moving geometry on x-slabs is not implemented)");
+    if (o.moving && o.nslabs > 1 && !o.same_device)
+        throw std::runtime_error("moving: single GPU only, or GPU n with --same-device (this driver runs a moving Shape2D geometry on x-slabs of one device only; "
+                                 "over several devices use fs3d_update_nodes_shape2d_slab through AdiSolver3D::UpdateGridExtruded)");
     if (o.host_extrusion && !o.moving) throw std::runtime_error("--host-extrusion: only with moving (it selects where a moving geometry is extruded)");
     if (o.moving_mesh && cfg.in_fmt != "Shape3D") throw std::runtime_error("moving-mesh: only in_fmt Shape3D inputs are meshes (this one is " + cfg.in_fmt + "; Shape2D inputs move with `moving`)");
-    if (o.moving_mesh && o.nslabs > 1) throw std::runtime_error("moving-mesh: single GPU only (moving geometry on x-slabs is not implemented)");
+    if (o.moving_mesh && o.nslabs > 1 && !o.host_voxels)
+        throw std::runtime_error("moving-mesh: the device voxelisation runs on a single GPU only (its flood fill is global); the host voxelisation "
+                                 "works on x-slabs: add --host-voxels to GPU n");
+    if ((o.time_both || o.time_geometry) && o.nslabs > 1) throw std::runtime_error("--time-both, --time-geometry: single GPU only");
     if (o.moving_mesh && o.moving) throw std::runtime_error("moving-mesh: not together with moving");
     if (o.host_voxels && !o.moving_mesh) throw std::runtime_error("--host-voxels: only with moving-mesh (it selects where a moving mesh is voxelised)");
     if (o.time_both && !o.moving_mesh) throw std::runtime_error("--time-both: only with moving-mesh (it times both ways of making a mesh's geometry)");
@@ -148,7 +153,7 @@ static int run(const std::string &data, const std::string &prefix, const fs3d::C
         std::fclose(f);
         return 0;
     }
-    if (o.nslabs > 1) return run_slabs<FTYPE>(grid, geo, prefix, cfg, o.nslabs, o.same_device, o.max_steps, o.csv, o.time_output);
+    if (o.nslabs > 1) return run_slabs<FTYPE>(grid, g2, sh3, geo, prefix, cfg, o);
     FluidParams<FTYPE> params = cfg.useNormalizedParams ? FluidParams<FTYPE>(cfg.Re, cfg.Pr, cfg.lambda)
                                                         : FluidParams<FTYPE>(cfg.viscosity, cfg.density, cfg.R_specific, cfg.k, cfg.cv);
     AdiSolver3D<FTYPE> solver;
@@ -299,6 +304,10 @@ static int run(const std::string &data, const std::string &prefix, const fs3d::C
 // "GPU n" with n > 1: the reference's single-process multi-GPU mode (GPUplan): n x-slabs (GPUplan::splitEven1D,
 // GPUplan.cpp:122-141), one solver and one host thread per slab, joined by the library's in-process group.
 // Results equal the single-GPU run's value for value.  Slab r runs on device r, or all on device 0 with --same-device.
+// moving / moving-mesh --host-voxels: rank 0 prepares the geometry of time t on the host (Prepare, and the host extrusion or
+// voxelisation into the shared Grid3D where asked), a barrier, then every rank rebuilds the tables of its own planes from that
+// global input (UpdateGrid / UpdateGridExtruded: the slab entries, no rank waits for another inside them); after the step
+// ClearOutterCells on every rank, and a barrier before rank 0 prepares the next geometry in the arrays the others have read.
 namespace {
 struct Barrier {
     std::mutex m; std::condition_variable cv; int n, waiting = 0; long gen = 0; bool broken = false;
@@ -315,10 +324,14 @@ struct Barrier {
 }
 
 template <typename FTYPE>
-static int run_slabs(const fs3d::Grid3D<FTYPE> &grid, const RunGeom &geo, const std::string &prefix, const fs3d::Config &cfg, int nslabs,
-                     bool same_device, long max_steps, bool csv, bool time_output)
+static int run_slabs(fs3d::Grid3D<FTYPE> &grid, fs3d::Grid2D &g2, fs3d::Shape3D &sh3, const RunGeom &geo, const std::string &prefix,
+                     const fs3d::Config &cfg, const RunOptions &o)
 {
     using namespace fs3d;
+    const int nslabs = o.nslabs;
+    const bool same_device = o.same_device, time_output = o.time_output, moves = o.moving || o.moving_mesh;
+    const bool on_host = o.moving ? o.host_extrusion : o.host_voxels;      // (a moving mesh on slabs: always)
+    const long max_steps = o.max_steps;
     FluidParams<FTYPE> params = cfg.useNormalizedParams ? FluidParams<FTYPE>(cfg.Re, cfg.Pr, cfg.lambda)
                                                         : FluidParams<FTYPE>(cfg.viscosity, cfg.density, cfg.R_specific, cfg.k, cfg.cv);
     const double length = geo.length, dt = length / (geo.frames * cfg.time_steps), finaltime = length * cfg.cycles;
@@ -346,6 +359,9 @@ static int run_slabs(const fs3d::Grid3D<FTYPE> &grid, const RunGeom &geo, const 
                 AdiSolver3D<FTYPE> solver;
                 solver.Init(same_device ? 0 : r, grid, params, x0, x1);
                 solver.JoinLocalGroup(group, r);
+                // every rank has uploaded the grid of time 0 before rank 0 writes the next geometry into the same arrays (Init
+                // reads them, and joining the group is no rendezvous)
+                if (moves) bar.wait();
                 if (r == 0) std::printf("Slabs: %d x-slabs of %d..%d planes\n", nslabs, q, q + (rem ? 1 : 0));
                 double t = dt;
                 long steps = 0;
@@ -353,6 +369,15 @@ static int run_slabs(const fs3d::Grid3D<FTYPE> &grid, const RunGeom &geo, const 
                 for (int i = 0; t < finaltime && (max_steps < 0 || steps < max_steps); t += dt, i++, steps++) {
                     const int currentframe = geo.GetFrame(t);
                     if (currentframe != lastframe) { lastframe = currentframe; i = 0; }
+                    if (moves) {
+                        if (r == 0) {
+                            if (o.moving) { g2.Prepare(t); if (on_host) ExtrudeShape2D(grid, g2, cfg.dz, cfg.depth, cfg.depth_var, cfg.baseT); }
+                            else { sh3.Prepare(t); FillShape3DNodes(grid, sh3, cfg.baseT, o.wall_T); }
+                        }
+                        bar.wait();
+                        if (on_host) solver.UpdateGrid(grid);
+                        else solver.UpdateGridExtruded(g2, cfg.dz, cfg.depth, cfg.depth_var);
+                    }
                     solver.UpdateBoundaries();
                     solver.TimeStep((FTYPE)dt, cfg.num_global, cfg.num_local, (i % 10 == 0) || (t + dt >= finaltime));
                     if (r == 0) { std::printf("\rerr = %.8f, frame %i\tsubstep %i\t%i%%", solver.diffError, currentframe, i, (int)((float)t * 100 / (float)finaltime)); std::fflush(stdout); }
@@ -371,6 +396,7 @@ static int run_slabs(const fs3d::Grid3D<FTYPE> &grid, const RunGeom &geo, const 
                         }
                         bar.wait();                    // nobody writes the next record's rows while rank 0 still reads this one
                     }
+                    if (moves) { solver.ClearOutterCells(); bar.wait(); }      // AdiSolver3D.cpp:382-385; every rank has read this step's geometry
                 }
                 if (r == 0) steps_done = steps;
             } catch (...) {
@@ -388,7 +414,6 @@ static int run_slabs(const fs3d::Grid3D<FTYPE> &grid, const RunGeom &geo, const 
     }
     for (auto &e : errs) if (e) std::rethrow_exception(e);
     const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    (void)csv;
     std::printf("\n");
     if (time_output && nc.NumRecords() > 0)
         std::printf("Result output per record (host clock, ms): GetLayer %.3f, AppendLayer %.3f; %u records\n", out_ms[0] / nc.NumRecords(),

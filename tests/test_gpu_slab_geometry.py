@@ -1,0 +1,325 @@
+"""Moving geometry on x-slabs (include/fs3d_slab_geometry.h): fs3d_update_nodes_slab / fs3d_update_nodes_shape2d_slab rebuild on
+the device, from the GLOBAL input and without talking to any other rank, the tables fs3d_upload_nodes builds for the slab's
+planes.  So everything is held bit for bit: the tables to a fresh slab context that uploaded the same arrays, the time steps of a
+group to a single context that took the same geometries through fs3d_update_nodes.  No tolerance is introduced; the reported
+error of a group is compared as tests/test_gpu_slabs.py::test_slabs_equal_single_context compares it (rtol 1e-12: the slabs add
+their partial sums in another order than one context adds its own, and only that).  Cases: tests/slab_geometry_cases.py."""
+import ctypes as C
+import functools
+import os
+import sys
+
+import numpy as np
+import pytest
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+if HERE not in sys.path:
+    sys.path.insert(0, HERE)
+
+import extrude_cases as EC  # noqa: E402
+import slab_geometry_cases as SC  # noqa: E402
+from cmc_fluid_solver_amd import capi, grids  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+PARAMS = (200.0, 0.72, 1.4)
+DT = 0.1
+TABLE_KEYS = capi.Solver.GEOMETRY_INFO[:13]        # entry 13, device_allocs_and_frees, describes the path taken, not the tables
+LAYERS = (capi.LAYER_CUR, capi.LAYER_TEMP, capi.LAYER_HALF, capi.LAYER_NEXT)
+
+
+@pytest.fixture(autouse=True)
+def _exact_kernels(monkeypatch):
+    """New contexts start on the bit-exact kernels (FS3D_SWEEP_EXACT); the test of the default kernels selects them itself."""
+    monkeypatch.setenv("FS3D_DEFAULT_KERNEL", "4")
+
+
+def bits(a):
+    return np.ascontiguousarray(a).view(np.uint32 if a.dtype == np.float32 else np.uint64)
+
+
+def params(dtype):
+    return capi.fluid_params(dtype, *PARAMS)
+
+
+def tables(s):
+    info = s.geometry_info()
+    return {k: info[k] for k in TABLE_KEYS}
+
+
+def node_values(s):
+    """The node-value table of the context, read through the layers fs3d_init_layers_from_nodes fills from it."""
+    s._chk(s.lib.fs3d_init_layers_from_nodes(s.h))
+    return [bits(f) for f in s.download_layer(capi.LAYER_CUR)]
+
+
+def assert_same_context(got, fresh, what):
+    assert tables(got) == tables(fresh), what
+    for d in range(3):                                     # which lines are dead, not only how many (the digest covers the codes)
+        a, b = got.dead_lines(d), fresh.dead_lines(d)
+        assert np.array_equal(a, b), "%s: %d dead-line bytes of direction %d differ" % (what, int((a != b).sum()), d)
+    assert got.num_segments == fresh.num_segments, what
+    for v, (a, b) in enumerate(zip(node_values(got), node_values(fresh))):
+        assert np.array_equal(a, b), "%s: node value field %d differs in %d cells" % (what, v, int((a != b).sum()))
+
+
+# ---- 1. the tables of an updated slab context equal those of a fresh upload --------------------------------------------------
+
+@pytest.mark.parametrize("nranks", [2, 3, 4])
+@pytest.mark.parametrize("name", SC.TABLE_PAIRS)
+def test_slab_update_equals_a_fresh_upload(built, name, nranks):
+    A, B = SC.pair(name, nranks)
+    for r, xr in enumerate(SC.ranges(A.dimx, nranks)):
+        s = capi.Solver(A, params(np.float32), np.float32, x_range=xr)
+        nseg = s.update_nodes_slab(B)
+        f = capi.Solver(B, params(np.float32), np.float32, x_range=xr)
+        print(name, nranks, xr, tables(s))
+        assert nseg == f.num_segments
+        if name == "solid_from" and r == 1:
+            # every X line through the fluid ends in this slab's first plane: the piece holds an END cell and no NODE_IN cell
+            assert not (B.type[xr[0]:xr[1]] == grids.NODE_IN).any()
+            interior = (B.dimy - 2) * (B.dimz - 2)
+            assert f.geometry_info()["dead_lines_x"] == B.dimy * B.dimz - interior
+            assert s.geometry_info()["dead_lines_x"] == f.geometry_info()["dead_lines_x"]
+        assert_same_context(s, f, "%s, planes %s of %d ranks" % (name, xr, nranks))
+        s.close(); f.close()
+
+
+@pytest.mark.parametrize("name", ["obstacle", "dimz18", "all_three"])
+def test_whole_grid_context_takes_the_slab_entry(built, name):
+    A, B = SC.pair(name)
+    a, b = capi.Solver(A, params(np.float32), np.float32), capi.Solver(A, params(np.float32), np.float32)
+    assert a.update_nodes_slab(B) == b.update_nodes(B)
+    assert_same_context(a, b, name)
+    a.close(); b.close()
+
+
+# ---- 2. refusals ---------------------------------------------------------------------------------------------------------------
+
+def raw_update(s, g, null=False):
+    arrs = [np.ascontiguousarray(a, np.uint8) for a in (g.type, g.bc_vel, g.bc_temp)] + [np.ascontiguousarray(a, s.dtype) for a in (g.vx, g.vy, g.vz, g.T)]
+    ptrs = [capi._p(a) for a in arrs]
+    if null:
+        ptrs[0] = None
+    nseg = (C.c_int * 3)()
+    st = s.lib.fs3d_update_nodes_slab(s.h, *ptrs, nseg)
+    return st, (s.lib.fs3d_last_error(s.h) or b"").decode()
+
+
+def raw_update_shape2d(s, dims, depth, null=False):
+    cell = np.zeros(dims[:2], np.uint8)
+    f = [np.zeros(dims[:2], np.float32) for _ in range(3)]
+    nseg = (C.c_int * 3)()
+    st = s.lib.fs3d_update_nodes_shape2d_slab(s.h, None if null else capi._p(cell), *[capi._p(a) for a in f], 1.0, float(depth), 0.0, 1.0, nseg)
+    return st, (s.lib.fs3d_last_error(s.h) or b"").decode()
+
+
+def test_refusals_before_the_geometry_is_given_up(built):
+    g, other = grids.box(*SC.REFUSAL_DIMS), grids.box_with_obstacle(*SC.REFUSAL_DIMS)
+    s = capi.Solver(g, params(np.float32), np.float32, x_range=(4, 8))
+    before, n_before = tables(s), s.profiler_events()["CreateSegments"][1]
+    for st, msg, entry, word in [raw_update(s, other, null=True) + ("fs3d_update_nodes_slab", "NULL array"),
+                                 raw_update_shape2d(s, g.shape, 1.0, null=True) + ("fs3d_update_nodes_shape2d_slab", "NULL array"),
+                                 # active_dimz = ceil(depth / dz) + 1 = 101 > dimz
+                                 raw_update_shape2d(s, g.shape, 100.0) + ("fs3d_update_nodes_shape2d_slab", "active_dimz")]:
+        print(st, msg)
+        assert st == capi.ERR_INVALID and msg.startswith(entry + ":") and word in msg, (st, msg)
+        assert tables(s) == before and s.profiler_events()["CreateSegments"][1] == n_before
+    s.UpdateBoundaries()                 # the slab keeps its geometry
+    assert s.update_nodes_slab(other) and s.profiler_events()["CreateSegments"][1] == n_before + 1
+    s.close()
+
+
+def test_no_slab_update_before_the_first_upload(built):
+    g = grids.box(*SC.REFUSAL_DIMS)
+    s = capi.Solver.__new__(capi.Solver)
+    s.lib, s.dtype, s.prec, s.h = capi.load(), np.dtype(np.float32), capi.F32, C.c_void_p()
+    assert s.lib.fs3d_create(C.byref(s.h), 0, s.prec, 4, g.dimy, g.dimz, g.dx, g.dy, g.dz, 4, g.dimx) == capi.OK
+    for st, msg in (raw_update(s, g), raw_update_shape2d(s, g.shape, 1.0)):
+        assert st == capi.ERR_INVALID and "upload nodes first" in msg, (st, msg)
+    assert s.profiler_events()["CreateSegments"][1] == 0
+    s.close()
+
+
+def test_a_refusal_by_the_tables_names_the_entry_that_was_called(built):
+    """A wall column one cell thick between fluid columns extrudes to BOUND cells with a FREE temperature condition that close
+    one X segment and open the next: refused by the tables, under the name of the Shape2D entry."""
+    g = grids.box(*SC.REFUSAL_DIMS)
+    cell = np.full(g.shape[:2], grids.NODE_BOUND, np.uint8)
+    cell[1:-1, 1:-1] = grids.NODE_IN
+    cell[2, 4:8] = grids.NODE_BOUND                        # in rank 0's planes: the X lines are global
+    f = [np.zeros(g.shape[:2], np.float32) for _ in range(3)]
+    s = capi.Solver(g, params(np.float32), np.float32, x_range=(4, 8))
+    nseg = (C.c_int * 3)()
+    st = s.lib.fs3d_update_nodes_shape2d_slab(s.h, capi._p(cell), *[capi._p(a) for a in f], 1.0, 8.0, 0.0, 1.0, nseg)     # active_dimz 9
+    msg = (s.lib.fs3d_last_error(s.h) or b"").decode()
+    print(st, msg)
+    assert st == capi.ERR_UNSUPPORTED and msg.startswith("fs3d_update_nodes_shape2d_slab:") and "FREE boundary condition" in msg
+    with pytest.raises(capi.Fs3dError):
+        s.geometry_info()
+    s.close()
+
+
+def upload_status(g, xr):
+    try:
+        capi.Solver(g, params(np.float32), np.float32, x_range=xr).close()
+        return capi.OK
+    except capi.Fs3dError as e:
+        return e.status
+
+
+@pytest.mark.parametrize("which,refusing", [("x", {0, 1, 2}), ("y", {1})])
+def test_a_shared_free_cell_is_refused_where_the_upload_refuses_it(built, which, refusing):
+    """A FREE baffle across an X line in rank 0's planes: the X lines are global, every rank refuses.  Across a Y line in rank 1's
+    planes: only rank 1 does."""
+    good = grids.box(*SC.REFUSAL_DIMS)
+    bad = SC.baffle_x() if which == "x" else SC.baffle_y()
+    for r, xr in enumerate(SC.ranges(good.dimx, 3)):
+        s = capi.Solver(good, params(np.float32), np.float32, x_range=xr)
+        n_before = s.profiler_events()["CreateSegments"][1]
+        st, msg = raw_update(s, bad)
+        print(r, xr, st, msg)
+        assert st == upload_status(bad, xr)
+        assert st == (capi.ERR_UNSUPPORTED if r in refusing else capi.OK)
+        if r in refusing:
+            assert "FREE boundary condition" in msg and msg.startswith("fs3d_update_nodes_slab:")
+            for call in (s.geometry_info, s.UpdateBoundaries):                 # refused by the tables: no geometry
+                with pytest.raises(capi.Fs3dError) as ei:
+                    call()
+                assert ei.value.status == capi.ERR_INVALID
+            assert s.profiler_events()["CreateSegments"][1] == n_before
+            assert s.update_nodes_slab(good)                                    # until an update succeeds
+            f = capi.Solver(good, params(np.float32), np.float32, x_range=xr)
+            assert tables(s) == tables(f)
+            f.close()
+        s.close()
+
+
+# ---- 3. time steps of a group, bit for bit -----------------------------------------------------------------------------------------
+
+def run_sequence(s, B, dtype, update):
+    """2 steps on the geometry the context has, the update to B with ClearOutterCells on cur and next, 2 more steps."""
+    errs = []
+    for part in range(2):
+        if part:
+            update(B)
+            s.clear_outer_cells(capi.LAYER_CUR, SC.BASE_T); s.clear_outer_cells(capi.LAYER_NEXT, SC.BASE_T)
+        for _ in range(2):
+            s.UpdateBoundaries()
+            errs.append(s.TimeStep(dtype(DT), 2, 2, True))
+    return s.download_layer(capi.LAYER_CUR), errs
+
+
+@functools.lru_cache(maxsize=None)
+def single_reference(name, dtype):
+    A, B = SC.pair(name)
+    s = capi.Solver(A, params(dtype), dtype)
+    out = run_sequence(s, B, dtype, s.update_nodes)
+    s.close()
+    return out
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+@pytest.mark.parametrize("nranks", [2, 3, 4])
+@pytest.mark.parametrize("name", SC.STEP_PAIRS)
+def test_group_steps_through_an_update_equal_the_single_context(built, name, nranks, dtype):
+    A, B = SC.pair(name)
+    ref, ref_err = single_reference(name, dtype)
+    grp = capi.LocalGroup(A, params(dtype), nranks, dtype)
+    res = grp.run(lambda rank, s: run_sequence(s, B, dtype, s.update_nodes_slab))
+    grp.close()
+    for v in range(4):
+        got = np.concatenate([res[r][0][v] for r in range(nranks)], axis=0)
+        assert np.array_equal(bits(ref[v]), bits(got)), "field %d differs in %d cells" % (v, int((bits(ref[v]) != bits(got)).sum()))
+    for r in range(nranks):                                   # every rank holds the global error
+        print(name, nranks, r, res[r][1], ref_err)
+        np.testing.assert_allclose(res[r][1], ref_err, rtol=1e-12)
+
+
+# ---- 4. the default kernels: same code, same tables, the shared columns the partition kernels read ---------------------------------
+
+@pytest.mark.parametrize("name", SC.AUTO_PAIRS)
+def test_default_kernels_after_an_update_equal_a_fresh_group(built, name, monkeypatch):
+    monkeypatch.setenv("FS3D_DEFAULT_KERNEL", str(capi.SWEEP_AUTO))
+    dtype, nranks = np.float32, 3
+    A, B = SC.pair(name, nranks)
+
+    def updated(rank, s):
+        for _ in range(2):
+            s.UpdateBoundaries(); s.TimeStep(dtype(DT), 2, 2, True)
+        s.update_nodes_slab(B)
+        s.clear_outer_cells(capi.LAYER_CUR, SC.BASE_T); s.clear_outer_cells(capi.LAYER_NEXT, SC.BASE_T)
+        return {l: s.download_layer(l) for l in LAYERS}, two_steps(s)
+
+    def two_steps(s):
+        errs = []
+        for _ in range(2):
+            s.UpdateBoundaries(); errs.append(s.TimeStep(dtype(DT), 2, 2, True))
+        return s.download_layer(capi.LAYER_CUR), errs, s.last_sweep_kernels()
+
+    ga = capi.LocalGroup(A, params(dtype), nranks, dtype)
+    got = ga.run(updated)
+    ga.close()
+
+    def fresh(rank, s):
+        for l in LAYERS:
+            s.upload_layer(l, got[rank][0][l])
+        return two_steps(s)
+    gb = capi.LocalGroup(B, params(dtype), nranks, dtype)
+    want = gb.run(fresh)
+    gb.close()
+    for r in range(nranks):
+        (cur_a, err_a, ran_a), (cur_b, err_b, ran_b) = got[r][1], want[r]
+        print(name, r, ran_a, err_a, err_b)
+        assert ran_a == ran_b and "part" in "".join(ran_a.values()), (ran_a, ran_b)
+        assert err_a == err_b
+        for v in range(4):
+            assert np.array_equal(bits(cur_a[v]), bits(cur_b[v])), "rank %d field %d differs in %d cells" % (r, v, int((bits(cur_a[v]) != bits(cur_b[v])).sum()))
+
+
+# ---- 5. Shape2D: the extrusion on the device, per slab -----------------------------------------------------------------------------
+
+def shape2d_case(name):
+    """(nodes the contexts start from, Grid2D at the case's time, params, the nodes of the extrusion)"""
+    nodes, g2, p = EC.load_case(name)
+    want = EC.twin(g2, p)                                  # shape2d.extrude_grid2d: shape2d.extrude_shape2d on the Grid2D's arrays
+    if name.startswith("heart_us"):
+        start = EC.load_case("heart_us-t0")[0]
+    else:                                                  # the degenerate outlines have no fluid to start from: a box of their dims
+        start = grids.box(*want.shape, h=p["dx"])
+        start.dx, start.dy, start.dz = want.dx, want.dy, want.dz
+    return start, g2, p, want
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+@pytest.mark.parametrize("nranks", [2, 3])
+@pytest.mark.parametrize("name", ["heart_us-t3", "adz5-var3-ragged", "adz5-var3-align"])
+def test_shape2d_slab_update_equals_a_fresh_upload_of_the_extruded_nodes(built, name, nranks, dtype):
+    start, g2, p, want = shape2d_case(name)
+    assert tuple(start.shape) == tuple(want.shape)
+    assert want.dimz >= 3 and want.dimx >= nranks
+    for xr in SC.ranges(want.dimx, nranks):
+        s = capi.Solver(start, params(dtype), dtype, x_range=xr)
+        s.update_nodes_shape2d_slab(g2, p["dz"], p["depth"], p["depth_var"], p["baseT"])
+        f = capi.Solver(want, params(dtype), dtype, x_range=xr)
+        print(name, xr, want.shape, tables(s))
+        assert_same_context(s, f, "%s, planes %s" % (name, xr))
+        s.close(); f.close()
+
+
+# ---- 6. steady state ---------------------------------------------------------------------------------------------------------------
+
+def test_no_allocation_after_the_second_slab_update(built):
+    A, B = SC.pair("obstacle")
+    start, g2, p, want = shape2d_case("heart_us-t3")
+    s = capi.Solver(A, params(np.float32), np.float32, x_range=(10, 20))
+    h = capi.Solver(start, params(np.float32), np.float32, x_range=SC.ranges(want.dimx, 2)[1])
+    counts, counts2 = [], []
+    for k in range(4):
+        s.update_nodes_slab(B if k % 2 == 0 else A)
+        counts.append(s.geometry_info()["device_allocs_and_frees"])
+        h.update_nodes_shape2d_slab(g2, p["dz"], p["depth"], p["depth_var"], p["baseT"])
+        counts2.append(h.geometry_info()["device_allocs_and_frees"])
+    print(counts, counts2)
+    assert counts[1] == counts[3] and counts2[1] == counts2[3]
+    s.close(); h.close()
