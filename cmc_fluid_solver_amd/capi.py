@@ -91,6 +91,13 @@ SYMBOLS_SLAB_GEOMETRY = {
     "fs3d_geometry_dead_lines": (_i, [_vp, _i, _vp, C.POINTER(C.c_longlong)]),
 }
 
+# every symbol include/fs3d_slab_mesh.h declares (the extension header of moving Shape3D meshes on x-slabs)
+SYMBOLS_SLAB_MESH = {
+    "fs3d_update_nodes_shape3d_slab": (_i, [_vp] + [_vp] * 3 + [_i, _vp, _i, _d, C.POINTER(_i)]),
+    "fs3d_update_nodes_shape3d_vel_slab": (_i, [_vp] + [_vp] * 6 + [_i, _vp, _i, _d, _d, C.POINTER(_i)]),
+    "fs3d_flood_fill_global_dev": (_i, [_vp, _vp]),
+}
+
 _lib = None
 
 
@@ -108,7 +115,8 @@ def load():
             raise RuntimeError("libfs3d_hip.so is not built (%s); run `python -m cmc_fluid_solver_amd.build` "
                                "or __graft_entry__.build()" % LIB_PATH)
         lib = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SYMBOLS.items()) + list(SYMBOLS_MESH_WALLS.items()) + list(SYMBOLS_SLAB_GEOMETRY.items()):
+        for name, (res, args) in list(SYMBOLS.items()) + list(SYMBOLS_MESH_WALLS.items()) + list(SYMBOLS_SLAB_GEOMETRY.items()) + \
+                list(SYMBOLS_SLAB_MESH.items()):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
@@ -304,6 +312,26 @@ class Solver:
         wv = self._mesh_velocities(w, len(xyz[0]))
         return self._update(self.lib.fs3d_update_nodes_shape3d_vel, *[_p(a) for a in xyz + wv], len(xyz[0]), _p(tri), tri.size // 3, float(baseT),
                             float(wallT))
+
+    def update_nodes_shape3d_slab(self, g, idx, baseT, voxels=None):
+        """update_nodes_shape3d on an x-slab (or a whole-grid context): the vertices g are in GLOBAL grid coordinates, every rank of a
+        group is given the same mesh and voxelises and fills the global grid on its own device; no rank waits for another."""
+        self._mesh_voxels(voxels)
+        xyz, tri = self._mesh_arrays(g, idx)
+        return self._update(self.lib.fs3d_update_nodes_shape3d_slab, *[_p(a) for a in xyz], len(xyz[0]), _p(tri), tri.size // 3, float(baseT))
+
+    def update_nodes_shape3d_vel_slab(self, g, w, idx, baseT, wallT, voxels=None):
+        """update_nodes_shape3d_vel on an x-slab (or a whole-grid context), as update_nodes_shape3d_slab."""
+        self._mesh_voxels(voxels)
+        xyz, tri = self._mesh_arrays(g, idx)
+        wv = self._mesh_velocities(w, len(xyz[0]))
+        return self._update(self.lib.fs3d_update_nodes_shape3d_vel_slab, *[_p(a) for a in xyz + wv], len(xyz[0]), _p(tri), tri.size // 3,
+                            float(baseT), float(wallT))
+
+    def flood_fill_global_dev(self, type):
+        """flood_fill_dev on a device array of the GLOBAL grid's node types, from any context (an x-slab too): the fill the two
+        mesh entries of a slab run."""
+        self._chk(self.lib.fs3d_flood_fill_global_dev(self.h, self._dev_ptrs("flood_fill_global_dev", [type])[0]))
 
     def flood_fill_dev(self, type):
         """FloodFill alone on a device array of node types (uint8 torch tensor or raw pointer) of the context's dims, in place."""

@@ -8,7 +8,9 @@
 // fs3d_voxelize_shape3d_dev, fs3d_flood_fill_dev, fs3d_update_nodes_shape3d): a moving mesh ships its vertices per step.
 // On an x-slab (fs3d_update_nodes_slab, fs3d_update_nodes_shape2d_slab; include/fs3d_slab_geometry.h) every rank is given the global
 // input and rebuilds the tables of its own planes, without communication: the X lines come from the global byte arrays
-// (k_geom_lines_x_slab, k_geom_codes<true>, k_geom_extrude_slab), everything else runs on the slab's planes.
+// (k_geom_lines_x_slab, k_geom_codes<true>, k_geom_extrude_slab), everything else runs on the slab's planes.  A mesh on an x-slab
+// (fs3d_update_nodes_shape3d_slab, fs3d_update_nodes_shape3d_vel_slab; include/fs3d_slab_mesh.h) is voxelised and flood-filled over
+// the GLOBAL grid by every rank, in the staging buffer that holds the global byte arrays anyway: the fill is global.
 //
 // Row kinds without the serial walk of line_kinds (fs3d_tables.h): that walk opens a run at `pos` when cell pos + 1 is
 // NODE_IN and closes it at the first cell after the run that is not NODE_IN; a run that reaches the end of the line is
@@ -611,7 +613,10 @@ __global__ void __launch_bounds__(64) k_geom_raster_mesh(const float *__restrict
 // the clipped box; there is no scan line, no guard and no flag word.
 // OWNER (the entries with wall velocities): every store of NODE_BOUND comes with an integer atomicMin of the triangle's index into
 // the cell's word of `owner`, preset to all ones -- the owner of a wall cell is the smallest index of the triangles that set it
-// (shape3d.py), a minimum over a set: nothing depends on the order of arrival, and no float atomics take part.
+// (shape3d.py), a minimum over a set: nothing depends on the order of arrival, and no float atomics take part.  `owner` holds the
+// planes [own_x0, own_x0 + own_nx) of the grid only (an x-slab: dimx is the GLOBAL grid's and the bytes go to the global type array,
+// the owners of the slab's own cells to its own array; a single context: 0 and dimx): the atomicMin is issued inside that window,
+// at the index relative to its first plane.
 #define VOXEL_SLACK 5.8207660913467407e-11              // 2^-34
 #define VOXEL_DEGENERATE 5.9604644775390625e-08        // 2^-24
 #define VOXEL_COORD_MAX 4096.0f
@@ -623,7 +628,8 @@ __device__ __forceinline__ double vox_sel(int c, double x, double y, double z) {
 
 template <bool OWNER>
 __global__ void __launch_bounds__(64) k_geom_voxel_mesh(const float *__restrict__ vx, const float *__restrict__ vy, const float *__restrict__ vz,
-                                                         const int *__restrict__ tri, int dimx, int dimy, int dimz, uint8_t *type, unsigned *owner)
+                                                         const int *__restrict__ tri, int dimx, int dimy, int dimz, uint8_t *type, unsigned *owner,
+                                                         int own_x0, int own_nx)
 {
     const int lane = threadIdx.x;
     const int iv[3] = {tri[3 * blockIdx.x], tri[3 * blockIdx.x + 1], tri[3 * blockIdx.x + 2]};
@@ -728,7 +734,10 @@ __global__ void __launch_bounds__(64) k_geom_voxel_mesh(const float *__restrict_
                 if (!(s + c1 >= 0.0) || !(s + c2 <= 0.0)) continue;
             }
             colp[k * sd] = FS3D_NODE_BOUND;
-            if constexpr (OWNER) atomicMin(owner + ((colp - type) + k * sd), (unsigned)blockIdx.x);      // the same cell of the same grid
+            if constexpr (OWNER) {
+                const int ix = o[0] + (a == 0 ? ia : (b == 0 ? ib : k)) - own_x0;                          // the cell's plane, in the window
+                if (ix >= 0 && ix < own_nx) atomicMin(owner + (((colp - type) + k * sd) - own_x0 * plane), (unsigned)blockIdx.x);      // < own_nx * plane
+            }
         }
     }
 }
@@ -880,11 +889,13 @@ __device__ __forceinline__ D3 wall_velocity(D3 q0, D3 q1, D3 q2, D3 W0, D3 W1, D
 // three vertices and three velocities, evaluates the rule in float64 and stores v rounded once to R and T = wallT; every other
 // cell as there.  The same two store shapes.  Wall cells are a surface: the gather is a small part of the seven arrays' traffic.
 // A NODE_BOUND cell without an owner below ntri cannot come from the voxel kernel; it reads nothing and stays at rest.
+// x0: the plane of the global grid that cell 0 of these arrays lies in (an x-slab; else 0) -- the vertices are in global grid
+// coordinates, every index is local to the arrays.
 template <typename R, int V>
 __global__ void __launch_bounds__(256) k_geom_mesh_nodes_vel(const uint8_t *__restrict__ type, const unsigned *__restrict__ owner,
                                                               const float *__restrict__ px, const float *__restrict__ py, const float *__restrict__ pz,
                                                               const float *__restrict__ wx, const float *__restrict__ wy, const float *__restrict__ wz,
-                                                              const int *__restrict__ tri, unsigned ntri, long long ncell, int dimy, int dimz,
+                                                              const int *__restrict__ tri, unsigned ntri, long long ncell, int x0, int dimy, int dimz,
                                                               R baseT, R wallT, uint8_t *__restrict__ bc_vel, uint8_t *__restrict__ bc_temp,
                                                               R *__restrict__ vx, R *__restrict__ vy, R *__restrict__ vz, R *__restrict__ T)
 {
@@ -901,7 +912,7 @@ __global__ void __launch_bounds__(256) k_geom_mesh_nodes_vel(const uint8_t *__re
         const unsigned t = owner[l + q];
         if (t >= ntri) continue;
         const long long cell = l + q, col = cell / dimz;
-        const double ck = (double)(int)(cell - col * dimz), cj = (double)(int)(col % dimy), ci = (double)(int)(col / dimy);
+        const double ck = (double)(int)(cell - col * dimz), cj = (double)(int)(col % dimy), ci = (double)(x0 + (int)(col / dimy));
         const int i0 = tri[3 * (size_t)t], i1 = tri[3 * (size_t)t + 1], i2 = tri[3 * (size_t)t + 2];      // checked by mesh_check: inside the vertex list
         const D3 q0 = {(double)px[i0] - ci, (double)py[i0] - cj, (double)pz[i0] - ck}, q1 = {(double)px[i1] - ci, (double)py[i1] - cj, (double)pz[i1] - ck},
                  q2 = {(double)px[i2] - ci, (double)py[i2] - cj, (double)pz[i2] - ck};
@@ -925,6 +936,14 @@ static inline GeomLines geom_lines(const fs3d_ctx *c, int d)
     if (d == 0) return {c->dimy, (long long)c->dimz, c->plane, c->dimx, (long long)c->dimy * c->dimz};
     if (d == 1) return {c->dimx, c->plane, (long long)c->dimz, c->dimy, (long long)c->dimx * c->dimz};
     return {0, (long long)c->dimz, 1, c->dimz, (long long)c->dimx * c->dimy};
+}
+// the same for the GLOBAL grid the context is a slab of (the flood fill of a mesh; a single context: geom_lines)
+static inline GeomLines geom_lines_global(const fs3d_ctx *c, int d)
+{
+    const int gx = c->dimx_global;
+    if (d == 0) return {c->dimy, (long long)c->dimz, c->plane, gx, (long long)c->dimy * c->dimz};
+    if (d == 1) return {gx, c->plane, (long long)c->dimz, c->dimy, (long long)gx * c->dimz};
+    return {0, (long long)c->dimz, 1, c->dimz, (long long)gx * c->dimy};
 }
 // groups of 32 k: the shared columns of directions 0 and 1 are n_o * geom_ng of them
 static inline int geom_ng(const fs3d_ctx *c) { return (c->dimz + 31) / 32; }
@@ -1331,7 +1350,7 @@ static fs3d_status mesh_check(fs3d_ctx *c, const MeshIn &in, const char *name, b
     return FS3D_OK;
 }
 
-// FloodFill on a device type array, on the context's stream; returns synchronised.  with_flag: the rasteriser ran before on the
+// FloodFill on a device type array of the GLOBAL grid (a single context: its own), on the context's stream; returns synchronised.  with_flag: the rasteriser ran before on the
 // same counters -- its flag word comes back with the first batch of rounds.  Every batch of rounds is a batch of the device time
 // (the first one goes on with the caller's, where one is open) and ends closed: what the caller launches next begins its own.
 static fs3d_status mesh_fill(fs3d_ctx *c, uint8_t *type, bool with_flag, const char *name)
@@ -1346,7 +1365,7 @@ static fs3d_status mesh_fill(fs3d_ctx *c, uint8_t *type, bool with_flag, const c
         HIPCHK(c, hipMemsetAsync(g.mesh_cnt + MC_ROUND, 0, MESH_FILL_BATCH * sizeof(unsigned), c->stream));
         for (int r = 0; r < MESH_FILL_BATCH; r++)
             for (int d = 2; d >= 0; d--) {
-                const GeomLines L = geom_lines(c, d);
+                const GeomLines L = geom_lines_global(c, d);   // the fill is global: a slab's own lines would stop at its cuts
                 unsigned *cnt = g.mesh_cnt + MC_ROUND + r;
                 if (d == 2)
                     hipLaunchKernelGGL(k_geom_fill_z, dim3(grid_for(L.nlines * 64, 1 << 30)), dim3(256), 0, c->stream, type, L.nlines, c->dimz, cnt);
@@ -1367,7 +1386,10 @@ static fs3d_status mesh_fill(fs3d_ctx *c, uint8_t *type, bool with_flag, const c
 }
 
 // vertices (and new indices) to the device, raster, fill and node kernels into the seven arrays, on the context's stream; the
-// node kernel is not waited for
+// node kernel is not waited for.  On an x-slab (the slab entries; every other caller has refused one) the three byte arrays of `a`
+// cover the GLOBAL grid and the value arrays the context's planes, as geom_own_arrays gives them: raster and fill run over the
+// global grid -- every rank repeats them and talks to nobody -- bc_vel / bc_temp are NOSLIP on all global cells, and the node
+// kernel works on the slab's planes.  A single context is the case x_offset == 0, dimx_global == dimx of the same lines.
 template <typename R>
 static fs3d_status mesh_launch(fs3d_ctx *c, const MeshIn &in, bool new_idx, const char *name, const NodeArrays &a)
 {
@@ -1378,36 +1400,44 @@ static fs3d_status mesh_launch(fs3d_ctx *c, const MeshIn &in, bool new_idx, cons
         HIPCHK(c, hipMemcpyAsync(g.mesh_idx, mesh_host_idx(g), 12 * (size_t)std::max(in.ntri, 1), hipMemcpyHostToDevice, c->stream));
         g.mesh_ntri_dev = in.ntri;
     }
-    HIPCHK(c, hipMemsetAsync(a.type, FS3D_NODE_IN, (size_t)c->ncell, c->stream));
+    const long long gcell = geom_gcell(c), first = (long long)c->x_offset * c->plane, tail = gcell - first - c->ncell;
+    const int gx = c->dimx_global;
+    HIPCHK(c, hipMemsetAsync(a.type, FS3D_NODE_IN, (size_t)gcell, c->stream));
     HIPCHK(c, hipMemsetAsync(g.mesh_cnt, 0, sizeof(unsigned), c->stream));
     const bool conservative = c->opt_mesh_voxels == 1;      // (mesh_check admitted the coordinates for this mode)
     if (in.vel) HIPCHK(c, hipMemsetAsync(g.mesh_owner, 0xFF, (size_t)c->ncell * sizeof(unsigned), c->stream));      // (the entries admit conservative only)
     if (in.ntri && in.vel)
         hipLaunchKernelGGL(k_geom_voxel_mesh<true>, dim3((unsigned)in.ntri), dim3(64), 0, c->stream, g.mesh_vert, g.mesh_vert + g.mesh_vcap,
-                           g.mesh_vert + 2 * (size_t)g.mesh_vcap, g.mesh_idx, c->dimx, c->dimy, c->dimz, a.type, g.mesh_owner);
+                           g.mesh_vert + 2 * (size_t)g.mesh_vcap, g.mesh_idx, gx, c->dimy, c->dimz, a.type, g.mesh_owner, c->x_offset, c->dimx);
     else if (in.ntri && conservative)
         hipLaunchKernelGGL(k_geom_voxel_mesh<false>, dim3((unsigned)in.ntri), dim3(64), 0, c->stream, g.mesh_vert, g.mesh_vert + g.mesh_vcap,
-                           g.mesh_vert + 2 * (size_t)g.mesh_vcap, g.mesh_idx, c->dimx, c->dimy, c->dimz, a.type, (unsigned *)nullptr);
+                           g.mesh_vert + 2 * (size_t)g.mesh_vcap, g.mesh_idx, gx, c->dimy, c->dimz, a.type, (unsigned *)nullptr, 0, 0);
     else if (in.ntri)
         hipLaunchKernelGGL(k_geom_raster_mesh, dim3((unsigned)in.ntri), dim3(64), 0, c->stream, g.mesh_vert, g.mesh_vert + g.mesh_vcap,
-                           g.mesh_vert + 2 * (size_t)g.mesh_vcap, g.mesh_idx, c->dimx, c->dimy, c->dimz, a.type, g.mesh_cnt + MC_FLAG);
+                           g.mesh_vert + 2 * (size_t)g.mesh_vcap, g.mesh_idx, gx, c->dimy, c->dimz, a.type, g.mesh_cnt + MC_FLAG);
     HIPCHK(c, hipGetLastError());
     GTRY(mesh_fill(c, a.type, !conservative, name));        // the conservative kernel has no flag word: it stays zero
     gev_begin(c);
-    const bool vec = a.vec4(c->dimz);
+    // the planes of the other slabs: bytes only (their cells are on this slab's X lines)
+    for (uint8_t *b : {a.bc_vel, a.bc_temp}) {
+        if (first) HIPCHK(c, hipMemsetAsync(b, FS3D_BC_NOSLIP, (size_t)first, c->stream));
+        if (tail) HIPCHK(c, hipMemsetAsync(b + first + c->ncell, FS3D_BC_NOSLIP, (size_t)tail, c->stream));
+    }
+    const NodeArrays s = {a.type + first, a.bc_vel + first, a.bc_temp + first, {a.v[0], a.v[1], a.v[2], a.v[3]}};      // the context's planes
+    const bool vec = s.vec4(c->dimz);                       // (first is a multiple of dimz)
     if (in.vel) {
         auto kv = vec ? k_geom_mesh_nodes_vel<R, 4> : k_geom_mesh_nodes_vel<R, 1>;
         const float *v = g.mesh_vert;
         const size_t cap = (size_t)g.mesh_vcap;
-        hipLaunchKernelGGL(kv, dim3(grid_for(vec ? c->ncell / 4 : c->ncell, 1 << 30)), dim3(256), 0, c->stream, a.type, g.mesh_owner, v, v + cap,
-                           v + 2 * cap, v + 3 * cap, v + 4 * cap, v + 5 * cap, g.mesh_idx, (unsigned)in.ntri, c->ncell, c->dimy, c->dimz,
-                           (R)(float)in.baseT, (R)(float)in.wallT, a.bc_vel, a.bc_temp, (R *)a.v[0], (R *)a.v[1], (R *)a.v[2], (R *)a.v[3]);
+        hipLaunchKernelGGL(kv, dim3(grid_for(vec ? c->ncell / 4 : c->ncell, 1 << 30)), dim3(256), 0, c->stream, s.type, g.mesh_owner, v, v + cap,
+                           v + 2 * cap, v + 3 * cap, v + 4 * cap, v + 5 * cap, g.mesh_idx, (unsigned)in.ntri, c->ncell, c->x_offset, c->dimy, c->dimz,
+                           (R)(float)in.baseT, (R)(float)in.wallT, s.bc_vel, s.bc_temp, (R *)s.v[0], (R *)s.v[1], (R *)s.v[2], (R *)s.v[3]);
         HIPCHK(c, hipGetLastError());
         return FS3D_OK;
     }
     auto kern = vec ? k_geom_mesh_nodes<R, 4> : k_geom_mesh_nodes<R, 1>;
-    hipLaunchKernelGGL(kern, dim3(grid_for(vec ? c->ncell / 4 : c->ncell, 1 << 30)), dim3(256), 0, c->stream, a.type, c->ncell, (R)(float)in.baseT,
-                       a.bc_vel, a.bc_temp, (R *)a.v[0], (R *)a.v[1], (R *)a.v[2], (R *)a.v[3]);
+    hipLaunchKernelGGL(kern, dim3(grid_for(vec ? c->ncell / 4 : c->ncell, 1 << 30)), dim3(256), 0, c->stream, s.type, c->ncell, (R)(float)in.baseT,
+                       s.bc_vel, s.bc_temp, (R *)s.v[0], (R *)s.v[1], (R *)s.v[2], (R *)s.v[3]);
     HIPCHK(c, hipGetLastError());
     return FS3D_OK;
 }
@@ -1628,6 +1658,35 @@ extern "C" fs3d_status fs3d_update_nodes_shape3d_vel(fs3d_ctx *c, const float *x
     return update_end(c, t0, st, own.type, own.bc_vel, own.bc_temp, n_seg_out);
 }
 
+// The mesh entries on a slab: every rank voxelises and fills the GLOBAL grid in its own staging buffer (mesh_launch), then builds
+// the tables of its own planes.  The refusals of the single-context entries, in their order, but the one of a slab.
+static fs3d_status update_shape3d_slab(fs3d_ctx *c, const char *name, const MeshIn &in, int n_seg_out[3])
+{
+    GTRY(update_refuse(c, name, !in.x || !in.y || !in.z || !in.tri || (in.vel && (!in.wx || !in.wy || !in.wz)), true));
+    if (in.vel) GTRY(vel_refuse(c, name));
+    const geom_clock t0 = std::chrono::steady_clock::now();
+    HIPCHK(c, hipSetDevice(c->device));
+    bool new_idx = false;
+    GTRY(mesh_check(c, in, name, &new_idx));
+    GTRY(update_begin(c, true));
+    const NodeArrays own = geom_own_arrays(c);
+    const fs3d_status st = c->prec == FS3D_F32 ? mesh_launch<float>(c, in, new_idx, name, own) : mesh_launch<double>(c, in, new_idx, name, own);
+    return update_end(c, t0, st, own.type, own.bc_vel, own.bc_temp, n_seg_out, name);
+}
+
+extern "C" fs3d_status fs3d_update_nodes_shape3d_slab(fs3d_ctx *c, const float *x, const float *y, const float *z, int nvert, const int *tri,
+                                                      int ntri, double baseT, int n_seg_out[3])
+{
+    return update_shape3d_slab(c, "fs3d_update_nodes_shape3d_slab", {x, y, z, nvert, tri, ntri, baseT, false, nullptr, nullptr, nullptr, 0.0}, n_seg_out);
+}
+
+extern "C" fs3d_status fs3d_update_nodes_shape3d_vel_slab(fs3d_ctx *c, const float *x, const float *y, const float *z, const float *wx,
+                                                          const float *wy, const float *wz, int nvert, const int *tri, int ntri, double baseT,
+                                                          double wallT, int n_seg_out[3])
+{
+    return update_shape3d_slab(c, "fs3d_update_nodes_shape3d_vel_slab", {x, y, z, nvert, tri, ntri, baseT, true, wx, wy, wz, wallT}, n_seg_out);
+}
+
 extern "C" fs3d_status fs3d_voxelize_shape3d_vel_dev(fs3d_ctx *c, const float *x, const float *y, const float *z, const float *wx, const float *wy,
                                                      const float *wz, int nvert, const int *tri, int ntri, double baseT, double wallT,
                                                      uint8_t *type_out, uint8_t *bc_vel_out, uint8_t *bc_temp_out, void *vx_out, void *vy_out,
@@ -1653,6 +1712,19 @@ extern "C" fs3d_status fs3d_flood_fill_dev(fs3d_ctx *c, uint8_t *type_inout)
 {
     const char *name = "fs3d_flood_fill_dev";
     GTRY(geom_refuse(c, name, !type_inout, "the flood fill is"));
+    GTRY(mesh_prepare(c, 0, 0));
+    gev_reset(c);
+    const fs3d_status st = mesh_fill(c, type_inout, false, name);
+    gev_reset(c);
+    return st;
+}
+
+// the same on the type array of the global grid, from any context (a slab: the fill does not stop at its cuts)
+extern "C" fs3d_status fs3d_flood_fill_global_dev(fs3d_ctx *c, uint8_t *type_inout)
+{
+    const char *name = "fs3d_flood_fill_global_dev";
+    if (!c) return FS3D_ERR_INVALID;
+    if (!type_inout) return fail(c, FS3D_ERR_INVALID, std::string(name) + ": NULL array");
     GTRY(mesh_prepare(c, 0, 0));
     gev_reset(c);
     const fs3d_status st = mesh_fill(c, type_inout, false, name);

@@ -115,11 +115,13 @@ public:
     // The same for the grid of a Shape3D mesh (Grid3D::Prepare3D_Shape, Grid3D.cpp:905-946): the sub-frame's vertices in grid
     // coordinates (Shape3D::SubFrame(t), host/Shape3D.h) and the triangle indices travel, the mesh is voxelised and flood-filled on
     // the device.  As with UpdateGridExtruded the host Grid3D given to Init is NOT kept current: its dims and baseT are read.
+    // On a slab or in a group as UpdateGrid: the vertices are in GLOBAL grid coordinates and every rank is given the same mesh
+    // (fs3d_update_nodes_shape3d_slab, fs3d_update_nodes_shape3d_vel_slab); each voxelises and fills the global grid for itself.
     void UpdateGridShape3D(const std::vector<float> &x, const std::vector<float> &y, const std::vector<float> &z, const std::vector<int> &idx)
     {
         if (x.size() != y.size() || x.size() != z.size()) throw std::runtime_error("UpdateGridShape3D: x, y, z differ in length");
         static const int none = 0;
-        chk(fs3d_update_nodes_shape3d(ctx_, x.data(), y.data(), z.data(), (int)x.size(), idx.empty() ? &none : idx.data(), (int)(idx.size() / 3),
+        chk((slab_ ? fs3d_update_nodes_shape3d_slab : fs3d_update_nodes_shape3d)(ctx_, x.data(), y.data(), z.data(), (int)x.size(), idx.empty() ? &none : idx.data(), (int)(idx.size() / 3),
                                       grid_->baseT, numSegs));
     }
     // The same with walls that carry the mesh's velocity and a temperature (fs3d_update_nodes_shape3d_vel; conservative voxelisation
@@ -131,7 +133,7 @@ public:
         if (x.size() != y.size() || x.size() != z.size()) throw std::runtime_error("UpdateGridShape3D: x, y, z differ in length");
         if (x.size() != wx.size() || x.size() != wy.size() || x.size() != wz.size()) throw std::runtime_error("UpdateGridShape3D: one velocity per vertex");
         static const int none = 0;
-        chk(fs3d_update_nodes_shape3d_vel(ctx_, x.data(), y.data(), z.data(), wx.data(), wy.data(), wz.data(), (int)x.size(),
+        chk((slab_ ? fs3d_update_nodes_shape3d_vel_slab : fs3d_update_nodes_shape3d_vel)(ctx_, x.data(), y.data(), z.data(), wx.data(), wy.data(), wz.data(), (int)x.size(),
                                           idx.empty() ? &none : idx.data(), (int)(idx.size() / 3), grid_->baseT, wallT, numSegs));
     }
     // FS3D_OPT_MESH_VOXELS for the UpdateGridShape3D calls that follow: 0 the reference's rasteriser, 1 the conservative

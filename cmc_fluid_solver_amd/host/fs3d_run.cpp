@@ -1,5 +1,5 @@
 // Command-line driver: the reference's FluidSolver3D main (FluidSolver3D/FluidSolver3D.cpp:60-330) on top of
-// libfs3d_hip.so.   fs3d_run <input data> <output prefix> <config> [align] [GPU [n]] [double] [moving [--host-extrusion] [--time-geometry]] [moving-mesh [--host-voxels] [--time-geometry] [--time-both]] [--time-output] [--steps N] [--same-device] [--grid-only FILE [--grid-time T]] [--watertight [--wall-velocity motion|file]] [--wall-temperature T]
+// libfs3d_hip.so.   fs3d_run <input data> <output prefix> <config> [align] [GPU [n]] [double] [moving [--host-extrusion] [--time-geometry]] [moving-mesh [--host-voxels | --slab-voxels] [--time-geometry] [--time-both]] [--time-output] [--steps N] [--same-device] [--grid-only FILE [--grid-time T]] [--watertight [--wall-velocity motion|file]] [--wall-temperature T]
 //   * reads the config (host/Config.h) and a Shape2D, Shape3D or SeaNetCDF geometry (host/Shape2D.h, Shape3D.h, SeaNetCDF.h), prints the grid summary lines
 //     the reference prints ("Grid = X x Y x Z", "NODE_IN points = ..."),
 //   * runs the same loop: dt = cycle length / (frames * time_steps), UpdateBoundaries + TimeStep per step with the
@@ -14,12 +14,15 @@
 //   --host-extrusion: the extrusion on the host (ExtrudeShape2D into the Grid3D, then UpdateGrid with its seven arrays) -- the same
 //   results bit for bit; kept for A/B timing and as the checker of the device extrusion.
 //   --time-geometry: one more line after the timing table, the host clock per step around Prepare, the host extrusion and the update call.
-// `moving-mesh` (in_fmt Shape3D; one GPU, or GPU n with --host-voxels: run_slabs below): the same loop for a triangle mesh per frame -- per step Shape3D::SubFrame(t) (the
+// `moving-mesh` (in_fmt Shape3D; one GPU, or GPU n with --host-voxels or --slab-voxels: run_slabs below): the same loop for a triangle mesh per frame -- per step Shape3D::SubFrame(t) (the
 //   interpolation of Grid3D::Prepare3D_Shape, Grid3D.cpp:905-946), then the voxelisation, the flood fill and CreateSegments on the
 //   device (UpdateGridShape3D: the vertices travel).  The frame counter of the progress line stays 0, as Grid3D::GetFrame gives it
 //   for a Shape3D input.  `moving` keeps its meaning: Shape2D inputs only.
 //   --host-voxels: Shape3D::Prepare(t) on the host (rasteriser and flood fill), then UpdateGrid with the seven arrays -- the same
 //   results bit for bit; kept for A/B timing and as the checker of the device voxeliser.
+//   --slab-voxels (GPU n, n > 1): the device path on x-slabs -- rank 0 computes SubFrame(t) (and the vertex velocities) once, every
+//   rank voxelises and fills the GLOBAL grid on its own device and builds the tables of its planes (UpdateGridShape3D: the slab
+//   entries fs3d_update_nodes_shape3d_slab / _vel_slab).  --watertight, --wall-velocity and --wall-temperature as on one GPU.
 //   --watertight (in_fmt Shape3D, with or without moving-mesh): the conservative voxelisation instead of the reference's rasteriser
 //   (Shape3D::voxels = 1 on the host, FS3D_OPT_MESH_VOXELS = 1 on the device) for the first geometry and for every update alike: a
 //   closed mesh keeps its NODE_IN cells at every time; the shell is thicker, so the fluid volume is smaller.
@@ -72,7 +75,7 @@ struct RunGeom {
 // the words after <config file>, as main's argument loop finds them
 struct RunOptions {
     bool align = false, dbl = false, csv = false, same_device = false, grid_images = false, watertight = false;
-    bool moving = false, host_extrusion = false, moving_mesh = false, host_voxels = false, time_geometry = false, time_both = false, time_output = false;
+    bool moving = false, host_extrusion = false, moving_mesh = false, host_voxels = false, slab_voxels = false, time_geometry = false, time_both = false, time_output = false;
     double grid_time = -1, wall_T = 0;
     int wall_velocity = 0;                             // 0: walls at rest; 1: motion; 2: file (Shape3D::wall_velocity)
     bool has_wall_T = false;
@@ -94,9 +97,12 @@ static int run(const std::string &data, const std::string &prefix, const fs3d::C
                                  "over several devices use fs3d_update_nodes_shape2d_slab through AdiSolver3D::UpdateGridExtruded)");
     if (o.host_extrusion && !o.moving) throw std::runtime_error("--host-extrusion: only with moving (it selects where a moving geometry is extruded)");
     if (o.moving_mesh && cfg.in_fmt != "Shape3D") throw std::runtime_error("moving-mesh: only in_fmt Shape3D inputs are meshes (this one is " + cfg.in_fmt + "; Shape2D inputs move with `moving`)");
-    if (o.moving_mesh && o.nslabs > 1 && !o.host_voxels)
+    if (o.slab_voxels && !o.moving_mesh) throw std::runtime_error("--slab-voxels: only with moving-mesh (it selects where a moving mesh is voxelised on x-slabs)");
+    if (o.slab_voxels && o.nslabs < 2) throw std::runtime_error("--slab-voxels: only with GPU n for n > 1 (one GPU voxelises on the device without it)");
+    if (o.slab_voxels && o.host_voxels) throw std::runtime_error("--slab-voxels: not together with --host-voxels");
+    if (o.moving_mesh && o.nslabs > 1 && !o.host_voxels && !o.slab_voxels)
         throw std::runtime_error("moving-mesh: the device voxelisation runs on a single GPU only (its flood fill is global); the host voxelisation "
-                                 "works on x-slabs: add --host-voxels to GPU n");
+                                 "works on x-slabs: add --host-voxels to GPU n, or --slab-voxels (every slab voxelises and fills the whole grid on its device)");
     if ((o.time_both || o.time_geometry) && o.nslabs > 1) throw std::runtime_error("--time-both, --time-geometry: single GPU only");
     if (o.moving_mesh && o.moving) throw std::runtime_error("moving-mesh: not together with moving");
     if (o.host_voxels && !o.moving_mesh) throw std::runtime_error("--host-voxels: only with moving-mesh (it selects where a moving mesh is voxelised)");
@@ -306,7 +312,9 @@ static int run(const std::string &data, const std::string &prefix, const fs3d::C
 // Results equal the single-GPU run's value for value.  Slab r runs on device r, or all on device 0 with --same-device.
 // moving / moving-mesh --host-voxels: rank 0 prepares the geometry of time t on the host (Prepare, and the host extrusion or
 // voxelisation into the shared Grid3D where asked), a barrier, then every rank rebuilds the tables of its own planes from that
-// global input (UpdateGrid / UpdateGridExtruded: the slab entries, no rank waits for another inside them); after the step
+// global input (UpdateGrid / UpdateGridExtruded: the slab entries, no rank waits for another inside them).
+// moving-mesh --slab-voxels: rank 0 computes the sub-frame's vertices (and their velocities) into shared vectors, a barrier, then
+// every rank voxelises the mesh for itself (UpdateGridShape3D: the slab entries).  Either way, after the step
 // ClearOutterCells on every rank, and a barrier before rank 0 prepares the next geometry in the arrays the others have read.
 namespace {
 struct Barrier {
@@ -330,7 +338,10 @@ static int run_slabs(fs3d::Grid3D<FTYPE> &grid, fs3d::Grid2D &g2, fs3d::Shape3D 
     using namespace fs3d;
     const int nslabs = o.nslabs;
     const bool same_device = o.same_device, time_output = o.time_output, moves = o.moving || o.moving_mesh;
-    const bool on_host = o.moving ? o.host_extrusion : o.host_voxels;      // (a moving mesh on slabs: always)
+    const bool on_host = o.moving ? o.host_extrusion : o.host_voxels;
+    const bool walls = o.wall_velocity || o.has_wall_T;    // --slab-voxels: the entry that takes velocities and a wall temperature
+    std::vector<float> mx, my, mz, mwx, mwy, mwz;          // --slab-voxels: the sub-frame of the step, written by rank 0 and read by all
+    size_t mframe = 0;
     const long max_steps = o.max_steps;
     FluidParams<FTYPE> params = cfg.useNormalizedParams ? FluidParams<FTYPE>(cfg.Re, cfg.Pr, cfg.lambda)
                                                         : FluidParams<FTYPE>(cfg.viscosity, cfg.density, cfg.R_specific, cfg.k, cfg.cv);
@@ -359,6 +370,7 @@ static int run_slabs(fs3d::Grid3D<FTYPE> &grid, fs3d::Grid2D &g2, fs3d::Shape3D 
                 AdiSolver3D<FTYPE> solver;
                 solver.Init(same_device ? 0 : r, grid, params, x0, x1);
                 solver.JoinLocalGroup(group, r);
+                if (o.watertight) solver.SetMeshVoxels(1);           // the updates voxelise as the host loader did
                 // every rank has uploaded the grid of time 0 before rank 0 writes the next geometry into the same arrays (Init
                 // reads them, and joining the group is no rendezvous)
                 if (moves) bar.wait();
@@ -372,11 +384,18 @@ static int run_slabs(fs3d::Grid3D<FTYPE> &grid, fs3d::Grid2D &g2, fs3d::Shape3D 
                     if (moves) {
                         if (r == 0) {
                             if (o.moving) { g2.Prepare(t); if (on_host) ExtrudeShape2D(grid, g2, cfg.dz, cfg.depth, cfg.depth_var, cfg.baseT); }
-                            else { sh3.Prepare(t); FillShape3DNodes(grid, sh3, cfg.baseT, o.wall_T); }
+                            else if (on_host) { sh3.Prepare(t); FillShape3DNodes(grid, sh3, cfg.baseT, o.wall_T); }
+                            else {
+                                mframe = sh3.SubFrame(t, mx, my, mz);
+                                if (o.wall_velocity) sh3.SubFrameVelocity(t, o.wall_velocity, mwx, mwy, mwz);
+                                else if (walls) { mwx.assign(mx.size(), 0.0f); mwy = mwx; mwz = mwx; }
+                            }
                         }
                         bar.wait();
                         if (on_host) solver.UpdateGrid(grid);
-                        else solver.UpdateGridExtruded(g2, cfg.dz, cfg.depth, cfg.depth_var);
+                        else if (o.moving) solver.UpdateGridExtruded(g2, cfg.dz, cfg.depth, cfg.depth_var);
+                        else if (walls) solver.UpdateGridShape3D(mx, my, mz, mwx, mwy, mwz, sh3.frames[mframe].idx, o.wall_T);
+                        else solver.UpdateGridShape3D(mx, my, mz, sh3.frames[mframe].idx);
                     }
                     solver.UpdateBoundaries();
                     solver.TimeStep((FTYPE)dt, cfg.num_global, cfg.num_local, (i % 10 == 0) || (t + dt >= finaltime));
@@ -426,7 +445,7 @@ static int run_slabs(fs3d::Grid3D<FTYPE> &grid, fs3d::Grid2D &g2, fs3d::Shape3D 
 int main(int argc, char **argv)
 {
     if (argc < 4) {
-        std::printf("Usage: %s <input data> <output prefix> <config file> [align] [GPU [n]] [double] [--steps N] [moving [--host-extrusion] [--time-geometry]] [moving-mesh [--host-voxels] [--time-geometry] [--time-both]] [--time-output] [--grid-only FILE [--grid-time T]] [--grid-images] [--watertight [--wall-velocity motion|file]] [--wall-temperature T]\n", argv[0]);
+        std::printf("Usage: %s <input data> <output prefix> <config file> [align] [GPU [n]] [double] [--steps N] [moving [--host-extrusion] [--time-geometry]] [moving-mesh [--host-voxels | --slab-voxels] [--time-geometry] [--time-both]] [--time-output] [--grid-only FILE [--grid-time T]] [--grid-images] [--watertight [--wall-velocity motion|file]] [--wall-temperature T]\n", argv[0]);
         return 0;
     }
     try {
@@ -450,6 +469,7 @@ int main(int argc, char **argv)
             else if (s == "moving") o.moving = true;
             else if (s == "moving-mesh") o.moving_mesh = true;
             else if (s == "--host-voxels") o.host_voxels = true;
+            else if (s == "--slab-voxels") o.slab_voxels = true;
             else if (s == "--watertight") o.watertight = true;
             else if (s == "--wall-velocity") {
                 const std::string w = a + 1 < argc ? argv[++a] : "";

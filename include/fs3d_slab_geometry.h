@@ -1,4 +1,6 @@
 /* Moving geometry on x-slabs: two entries beside fs3d_update_nodes and fs3d_update_nodes_shape2d of fs3d.h (and one test aid), in libfs3d_hip.so.
+ * The entries for a Shape3D mesh, beside fs3d_update_nodes_shape3d[_vel], are declared in fs3d_slab_mesh.h, which this header
+ * includes: whoever includes this one has every slab entry.
  * An extension header: fs3d.h keeps the set of functions it declared before these existed, and its update entries keep refusing
  * an x-slab (FS3D_ERR_UNSUPPORTED, "single context only"). */
 #ifndef FS3D_SLAB_GEOMETRY_H
@@ -39,9 +41,9 @@ extern "C" {
  * allocated by the first slab update, never shrunk -- and every rank reads them for the X lines, so that pass does not shrink
  * with the number of ranks; everything else works on the slab's planes.
  *
- * Not provided: a _dev form of these entries; shipping less than the global byte arrays; the voxelisation of a mesh on a slab
- * (its flood fill is global; fs3d_update_nodes_shape3d* keep refusing a slab -- voxelise on the host and call
- * fs3d_update_nodes_slab). */
+ * Not provided: a _dev form of these entries; shipping less than the global byte arrays.  (A mesh on a slab is voxelised on the
+ * device by the entries of fs3d_slab_mesh.h: the flood fill is global, so every rank runs it over the global grid in the staging
+ * buffer described above.  fs3d_update_nodes_shape3d[_vel] themselves keep refusing a slab.) */
 fs3d_status fs3d_update_nodes_slab(fs3d_ctx *ctx, const uint8_t *type, const uint8_t *bc_vel, const uint8_t *bc_temp,
                                    const void *vx, const void *vy, const void *vz, const void *T, int n_seg_out[3]);
 fs3d_status fs3d_update_nodes_shape2d_slab(fs3d_ctx *ctx, const uint8_t *cell2d, const float *velx2d, const float *vely2d,
@@ -57,4 +59,7 @@ fs3d_status fs3d_geometry_dead_lines(fs3d_ctx *ctx, int dir, uint8_t *dead_out, 
 #ifdef __cplusplus
 }
 #endif
+
+#include "fs3d_slab_mesh.h"
+
 #endif /* FS3D_SLAB_GEOMETRY_H */
