@@ -209,17 +209,19 @@ class Solver:
             return C.c_void_p(a.data_ptr())
         return [ptr(a, 1) for a in arrays[:3]] + [ptr(a, self.dtype.itemsize) for a in arrays[3:]]
 
+    def _update_arrays(self, fn, nodes):
+        assert tuple(nodes.shape) == tuple(self.gdims)
+        return self._update(fn, *[_p(a) for a in self._node_arrays(nodes)])
+
     def update_nodes(self, nodes):
         """AdiSolver3D::CreateSegments between time steps: the tables of a new geometry (same dims), rebuilt on the device.
         Layers are kept.  After a refusal the context has no geometry until an update succeeds."""
-        assert tuple(nodes.shape) == tuple(self.gdims)
-        return self._update(self.lib.fs3d_update_nodes, *[_p(a) for a in self._node_arrays(nodes)])
+        return self._update_arrays(self.lib.fs3d_update_nodes, nodes)
 
     def update_nodes_slab(self, nodes):
         """update_nodes on an x-slab (or a whole-grid context): `nodes` is the GLOBAL grid, every rank of a group is given the
         same one between the same two steps and rebuilds the tables of its own planes; no rank waits for another."""
-        assert tuple(nodes.shape) == tuple(self.gdims)
-        return self._update(self.lib.fs3d_update_nodes_slab, *[_p(a) for a in self._node_arrays(nodes)])
+        return self._update_arrays(self.lib.fs3d_update_nodes_slab, nodes)
 
     def update_nodes_dev(self, type, bc_vel, bc_temp, vx, vy, vz, T):
         """The same from arrays on the context's device: torch tensors (contiguous; uint8 x 3, the context's precision x 4)
@@ -241,17 +243,18 @@ class Solver:
         arrs = self._grid2d_arrays(g2)
         self._chk(self.lib.fs3d_extrude_shape2d_dev(self.h, *[_p(a) for a in arrs], float(dz), float(depth), float(depth_var), float(baseT), *ptrs))
 
+    def _update_shape2d(self, fn, g2, dz, depth, depth_var, baseT):
+        arrs = self._grid2d_arrays(g2)
+        return self._update(fn, *[_p(a) for a in arrs], float(dz), float(depth), float(depth_var), float(baseT))
+
     def update_nodes_shape2d(self, g2, dz, depth, depth_var, baseT):
         """update_nodes with the extrusion of the 2D grid g2 as the source: 13 bytes per column travel, the node arrays are written
         by a kernel.  Same contract as update_nodes."""
-        arrs = self._grid2d_arrays(g2)
-        return self._update(self.lib.fs3d_update_nodes_shape2d, *[_p(a) for a in arrs], float(dz), float(depth), float(depth_var), float(baseT))
+        return self._update_shape2d(self.lib.fs3d_update_nodes_shape2d, g2, dz, depth, depth_var, baseT)
 
     def update_nodes_shape2d_slab(self, g2, dz, depth, depth_var, baseT):
         """update_nodes_shape2d on an x-slab (or a whole-grid context): g2 is the GLOBAL 2D grid, given to every rank."""
-        arrs = self._grid2d_arrays(g2)
-        return self._update(self.lib.fs3d_update_nodes_shape2d_slab, *[_p(a) for a in arrs], float(dz), float(depth), float(depth_var),
-                            float(baseT))
+        return self._update_shape2d(self.lib.fs3d_update_nodes_shape2d_slab, g2, dz, depth, depth_var, baseT)
 
     @staticmethod
     def _mesh_arrays(g, idx):
@@ -270,22 +273,6 @@ class Solver:
                 raise ValueError("voxels is 'reference' or 'conservative'")
             self.set_option(OPT_MESH_VOXELS, MESH_VOXELS[voxels])
 
-    def voxelize_shape3d_dev(self, g, idx, baseT, type, bc_vel, bc_temp, vx, vy, vz, T, voxels=None):
-        """Grid3D::Build + FloodFill + the Node array on the device: the mesh (g, idx) of shape3d.Shape3D.subframe(t) voxelised into
-        seven arrays on the context's device -- torch tensors or raw pointers, as update_nodes_dev takes them.  The context's
-        geometry is not touched."""
-        self._mesh_voxels(voxels)
-        ptrs = self._dev_ptrs("voxelize_shape3d_dev", [type, bc_vel, bc_temp, vx, vy, vz, T])
-        xyz, tri = self._mesh_arrays(g, idx)
-        self._chk(self.lib.fs3d_voxelize_shape3d_dev(self.h, *[_p(a) for a in xyz], len(xyz[0]), _p(tri), tri.size // 3, float(baseT), *ptrs))
-
-    def update_nodes_shape3d(self, g, idx, baseT, voxels=None):
-        """update_nodes with the voxelisation of the mesh (g, idx) as the source: 12 bytes per vertex travel, the node arrays are
-        written by kernels.  Same contract as update_nodes."""
-        self._mesh_voxels(voxels)
-        xyz, tri = self._mesh_arrays(g, idx)
-        return self._update(self.lib.fs3d_update_nodes_shape3d, *[_p(a) for a in xyz], len(xyz[0]), _p(tri), tri.size // 3, float(baseT))
-
     @staticmethod
     def _mesh_velocities(w, nvert):
         """wx, wy, wz (float32) of vertex velocities w [n, 3]"""
@@ -294,39 +281,51 @@ class Solver:
             raise ValueError("one velocity per vertex")
         return [np.ascontiguousarray(w[:, a]) for a in range(3)]
 
+    def _mesh_args(self, g, w, idx, baseT, wallT):
+        """The mesh (g, idx) as the C ABI takes it; unless w is None, with its vertex velocities and wallT (the _vel entries)."""
+        xyz, tri = self._mesh_arrays(g, idx)
+        wv, wt = ([], []) if w is None else (self._mesh_velocities(w, len(xyz[0])), [float(wallT)])
+        return [_p(a) for a in xyz + wv] + [len(xyz[0]), _p(tri), tri.size // 3, float(baseT)] + wt
+
+    def _voxelize_dev(self, fn, what, g, w, idx, baseT, wallT, arrays, voxels):
+        self._mesh_voxels(voxels)
+        ptrs = self._dev_ptrs(what, arrays)
+        self._chk(fn(self.h, *self._mesh_args(g, w, idx, baseT, wallT), *ptrs))
+
+    def _update_shape3d(self, fn, g, w, idx, baseT, wallT, voxels):
+        self._mesh_voxels(voxels)
+        return self._update(fn, *self._mesh_args(g, w, idx, baseT, wallT))
+
+    def voxelize_shape3d_dev(self, g, idx, baseT, type, bc_vel, bc_temp, vx, vy, vz, T, voxels=None):
+        """Grid3D::Build + FloodFill + the Node array on the device: the mesh (g, idx) of shape3d.Shape3D.subframe(t) voxelised into
+        seven arrays on the context's device -- torch tensors or raw pointers, as update_nodes_dev takes them.  The context's
+        geometry is not touched."""
+        self._voxelize_dev(self.lib.fs3d_voxelize_shape3d_dev, "voxelize_shape3d_dev", g, None, idx, baseT, None, [type, bc_vel, bc_temp, vx, vy, vz, T], voxels)
+
+    def update_nodes_shape3d(self, g, idx, baseT, voxels=None):
+        """update_nodes with the voxelisation of the mesh (g, idx) as the source: 12 bytes per vertex travel, the node arrays are
+        written by kernels.  Same contract as update_nodes."""
+        return self._update_shape3d(self.lib.fs3d_update_nodes_shape3d, g, None, idx, baseT, None, voxels)
+
     def voxelize_shape3d_vel_dev(self, g, w, idx, baseT, wallT, type, bc_vel, bc_temp, vx, vy, vz, T, voxels=None):
         """voxelize_shape3d_dev with walls that carry the velocity of the mesh -- w [n, 3], what shape3d.Shape3D.subframe_velocity(t)
         returns -- and the temperature wallT (conservative voxelisation only)."""
-        self._mesh_voxels(voxels)
-        ptrs = self._dev_ptrs("voxelize_shape3d_vel_dev", [type, bc_vel, bc_temp, vx, vy, vz, T])
-        xyz, tri = self._mesh_arrays(g, idx)
-        wv = self._mesh_velocities(w, len(xyz[0]))
-        self._chk(self.lib.fs3d_voxelize_shape3d_vel_dev(self.h, *[_p(a) for a in xyz + wv], len(xyz[0]), _p(tri), tri.size // 3, float(baseT),
-                                                         float(wallT), *ptrs))
+        self._voxelize_dev(self.lib.fs3d_voxelize_shape3d_vel_dev, "voxelize_shape3d_vel_dev", g, w, idx, baseT, wallT,
+                           [type, bc_vel, bc_temp, vx, vy, vz, T], voxels)
 
     def update_nodes_shape3d_vel(self, g, w, idx, baseT, wallT, voxels=None):
         """update_nodes_shape3d with walls that carry the velocity of the mesh (w [n, 3]) and the temperature wallT (conservative
         voxelisation only).  Same contract as update_nodes."""
-        self._mesh_voxels(voxels)
-        xyz, tri = self._mesh_arrays(g, idx)
-        wv = self._mesh_velocities(w, len(xyz[0]))
-        return self._update(self.lib.fs3d_update_nodes_shape3d_vel, *[_p(a) for a in xyz + wv], len(xyz[0]), _p(tri), tri.size // 3, float(baseT),
-                            float(wallT))
+        return self._update_shape3d(self.lib.fs3d_update_nodes_shape3d_vel, g, w, idx, baseT, wallT, voxels)
 
     def update_nodes_shape3d_slab(self, g, idx, baseT, voxels=None):
         """update_nodes_shape3d on an x-slab (or a whole-grid context): the vertices g are in GLOBAL grid coordinates, every rank of a
         group is given the same mesh and voxelises and fills the global grid on its own device; no rank waits for another."""
-        self._mesh_voxels(voxels)
-        xyz, tri = self._mesh_arrays(g, idx)
-        return self._update(self.lib.fs3d_update_nodes_shape3d_slab, *[_p(a) for a in xyz], len(xyz[0]), _p(tri), tri.size // 3, float(baseT))
+        return self._update_shape3d(self.lib.fs3d_update_nodes_shape3d_slab, g, None, idx, baseT, None, voxels)
 
     def update_nodes_shape3d_vel_slab(self, g, w, idx, baseT, wallT, voxels=None):
         """update_nodes_shape3d_vel on an x-slab (or a whole-grid context), as update_nodes_shape3d_slab."""
-        self._mesh_voxels(voxels)
-        xyz, tri = self._mesh_arrays(g, idx)
-        wv = self._mesh_velocities(w, len(xyz[0]))
-        return self._update(self.lib.fs3d_update_nodes_shape3d_vel_slab, *[_p(a) for a in xyz + wv], len(xyz[0]), _p(tri), tri.size // 3,
-                            float(baseT), float(wallT))
+        return self._update_shape3d(self.lib.fs3d_update_nodes_shape3d_vel_slab, g, w, idx, baseT, wallT, voxels)
 
     def flood_fill_global_dev(self, type):
         """flood_fill_dev on a device array of the GLOBAL grid's node types, from any context (an x-slab too): the fill the two

@@ -209,6 +209,8 @@ static inline std::string call_failed(const fs3d_ctx *c, const char *call, const
 }
 #define HIPCHK(c, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return fail((c), FS3D_ERR_HIP, call_failed((c), #call, hipGetErrorString(e_))); } while (0)
 #define GTRY(call) do { const fs3d_status st_ = (call); if (st_) return st_; } while (0)
+// f<float>(args) or f<double>(args), by the precision of context c
+#define BY_PREC(c, f, ...) ((c)->prec == FS3D_F32 ? f<float>(__VA_ARGS__) : f<double>(__VA_ARGS__))
 
 // blocks of 256 threads for n items, at most `cap` (the kernels stride over what is left)
 static inline unsigned grid_for(long long n, int cap = 4096) { return (unsigned)std::max(1LL, std::min<long long>((n + 255) / 256, cap)); }

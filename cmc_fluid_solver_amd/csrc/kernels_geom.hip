@@ -8,9 +8,11 @@
 // fs3d_voxelize_shape3d_dev, fs3d_flood_fill_dev, fs3d_update_nodes_shape3d): a moving mesh ships its vertices per step.
 // On an x-slab (fs3d_update_nodes_slab, fs3d_update_nodes_shape2d_slab; include/fs3d_slab_geometry.h) every rank is given the global
 // input and rebuilds the tables of its own planes, without communication: the X lines come from the global byte arrays
-// (k_geom_lines_x_slab, k_geom_codes<true>, k_geom_extrude_slab), everything else runs on the slab's planes.  A mesh on an x-slab
+// (k_geom_lines_x_slab, k_geom_codes<true>, k_geom_extrude<.., true>), everything else runs on the slab's planes.  A mesh on an x-slab
 // (fs3d_update_nodes_shape3d_slab, fs3d_update_nodes_shape3d_vel_slab; include/fs3d_slab_mesh.h) is voxelised and flood-filled over
 // the GLOBAL grid by every rank, in the staging buffer that holds the global byte arrays anyway: the fill is global.
+// Every fs3d_update_nodes* entry is one statement above update_run, the one body of an update: a source (node arrays, a Shape2D
+// grid, a mesh) gives its NULL test, its check and its producer, and a whole-grid context is the slab x_offset = 0, dimx_global = dimx.
 //
 // Row kinds without the serial walk of line_kinds (fs3d_tables.h): that walk opens a run at `pos` when cell pos + 1 is
 // NODE_IN and closes it at the first cell after the run that is not NODE_IN; a run that reaches the end of the line is
@@ -423,41 +425,16 @@ __device__ __forceinline__ void store_nodes(long long l, unsigned wt, unsigned w
 // Pure store kernel, 19 bytes per cell in fp32 and 35 in fp64.  One thread writes V consecutive k of one column (store_nodes;
 // V == 4 where dimz % 4 == 0 and the arrays are aligned).
 // Lanes run along k, so a wave writes 64 * V consecutive cells; the column record is read once per thread.
-template <typename R, int V>
+// SLAB, the extrusion on an x-slab: `ncol` counts the columns of the GLOBAL grid and the three byte arrays are global (the X lines of
+// the slab's tables are read from them), the four value arrays hold the slab's columns [col0, col0 + ncol_own) only -- a thread of
+// another slab's column stores its 3 bytes per cell and no values.  Without it all seven arrays cover the ncol columns (col0 and
+// ncol_own are not read).  The same node per cell and the same two store shapes.
+template <typename R, int V, bool SLAB>
 __global__ void __launch_bounds__(256) k_geom_extrude(const float *__restrict__ velx, const float *__restrict__ vely, const float *__restrict__ T2,
-                                                       const int *__restrict__ bottom, const uint8_t *__restrict__ cell, long long ncol, int dimz,
-                                                       int A, float baseT, uint8_t *__restrict__ type, uint8_t *__restrict__ bc_vel,
-                                                       uint8_t *__restrict__ bc_temp, R *__restrict__ vx, R *__restrict__ vy, R *__restrict__ vz,
-                                                       R *__restrict__ T)
-{
-    const int nq = dimz / V;                           // V == 4: dimz % 4 == 0
-    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (t >= ncol * nq) return;
-    const long long col = t / nq;
-    const int k0 = (int)(t - col * nq) * V;
-    const int c2 = cell[col], bot = bottom[col];
-    const float ux = velx[col], uy = vely[col], t2 = T2[col];
-    const long long l = col * dimz + k0;               // < ncol * dimz: the arrays' size
-    unsigned wt = 0, wv = 0, wb = 0;
-    R ax[V], ay[V], aT[V];
-#pragma unroll
-    for (int q = 0; q < V; q++) {
-        const ExNode n = extrude_node(k0 + q, c2, ux, uy, t2, bot, A, baseT);
-        wt |= (unsigned)n.type << (8 * q); wv |= (unsigned)n.bv << (8 * q); wb |= (unsigned)n.bt << (8 * q);
-        ax[q] = (R)n.vx; ay[q] = (R)n.vy; aT[q] = (R)n.T;
-    }
-    store_nodes<R, V, true>(l, wt, wv, wb, ax, ay, aT, type, bc_vel, bc_temp, vx, vy, vz, T);
-}
-
-// The extrusion on an x-slab: `ncol` counts the columns of the GLOBAL grid and the three byte arrays are global (the X lines of the
-// slab's tables are read from them), the four value arrays hold the slab's columns [col0, col0 + ncol_own) only -- a thread of
-// another slab's column stores its 3 bytes per cell and no values.  The same node per cell and the same two store shapes.
-template <typename R, int V>
-__global__ void __launch_bounds__(256) k_geom_extrude_slab(const float *__restrict__ velx, const float *__restrict__ vely, const float *__restrict__ T2,
-                                                            const int *__restrict__ bottom, const uint8_t *__restrict__ cell, long long ncol,
-                                                            long long col0, long long ncol_own, int dimz, int A, float baseT,
-                                                            uint8_t *__restrict__ type, uint8_t *__restrict__ bc_vel, uint8_t *__restrict__ bc_temp,
-                                                            R *__restrict__ vx, R *__restrict__ vy, R *__restrict__ vz, R *__restrict__ T)
+                                                       const int *__restrict__ bottom, const uint8_t *__restrict__ cell, long long ncol,
+                                                       long long col0, long long ncol_own, int dimz, int A, float baseT,
+                                                       uint8_t *__restrict__ type, uint8_t *__restrict__ bc_vel, uint8_t *__restrict__ bc_temp,
+                                                       R *__restrict__ vx, R *__restrict__ vy, R *__restrict__ vz, R *__restrict__ T)
 {
     const int nq = dimz / V;                           // V == 4: dimz % 4 == 0
     const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -474,9 +451,13 @@ __global__ void __launch_bounds__(256) k_geom_extrude_slab(const float *__restri
         wt |= (unsigned)n.type << (8 * q); wv |= (unsigned)n.bv << (8 * q); wb |= (unsigned)n.bt << (8 * q);
         ax[q] = (R)n.vx; ay[q] = (R)n.vy; aT[q] = (R)n.T;
     }
-    store_node_bytes<V, true>(col * dimz + k0, wt, wv, wb, type, bc_vel, bc_temp);      // < ncol * dimz: the byte arrays' size
-    if (col >= col0 && col < col0 + ncol_own)                                            // (col - col0) * dimz + k0 < ncol_own * dimz: the value arrays'
-        store_node_values<R, V>((col - col0) * dimz + k0, ax, ay, aT, vx, vy, vz, T);
+    // col * dimz + k0 < ncol * dimz: the byte arrays' size
+    if constexpr (!SLAB) store_nodes<R, V, true>(col * dimz + k0, wt, wv, wb, ax, ay, aT, type, bc_vel, bc_temp, vx, vy, vz, T);
+    else {
+        store_node_bytes<V, true>(col * dimz + k0, wt, wv, wb, type, bc_vel, bc_temp);
+        if (col >= col0 && col < col0 + ncol_own)      // (col - col0) * dimz + k0 < ncol_own * dimz: the value arrays'
+            store_node_values<R, V>((col - col0) * dimz + k0, ax, ay, aT, vx, vy, vz, T);
+    }
 }
 
 // ---- Shape3D meshes: Grid3D::Build (Grid3D.cpp:859-903) on the device ------------------------------------------------------------
@@ -1093,16 +1074,15 @@ static fs3d_status geom_columns(fs3d_ctx *c, int d)
 // The three byte arrays cover the global grid; the tables are those of the context's planes.  slab (fs3d_update_nodes*_slab): the
 // X lines are read from the global arrays (k_geom_lines_x_slab, k_geom_codes<true>); everything else runs on the local planes.
 // Without it the context is the whole grid (the other entries refuse a slab) and line and context coincide.
-// slab_entry: the name of the slab entry that was called (its refusals carry it), or null.
+// name: the entry that was called; the refusals of a slab entry carry it, those of a whole-grid entry say fs3d_update_nodes.
 template <typename R>
-static fs3d_status update_nodes_impl(fs3d_ctx *c, const uint8_t *gtype, const uint8_t *gbc_vel, const uint8_t *gbc_temp, const char *slab_entry,
-                                     int n_seg_out[3])
+static fs3d_status update_nodes_impl(fs3d_ctx *c, const uint8_t *gtype, const uint8_t *gbc_vel, const uint8_t *gbc_temp, const char *entry,
+                                     bool slab, int n_seg_out[3])
 {
-    const bool slab = slab_entry != nullptr;
     fs3d_geom &g = c->geom;
     const long long ncell = c->ncell, first = (long long)c->x_offset * c->plane;
     const uint8_t *type = gtype + first, *bc_vel = gbc_vel + first, *bc_temp = gbc_temp + first;
-    const std::string name = slab ? slab_entry : "fs3d_update_nodes";
+    const std::string name = slab ? entry : "fs3d_update_nodes";
     HIPCHK(c, hipMemsetAsync(g.cnt, 0, GC_WORDS * sizeof(unsigned long long), c->stream));
     for (int d = 0; d < 3; d++) {
         const GeomLines L = geom_lines(c, d);
@@ -1178,13 +1158,17 @@ struct NodeArrays {
 static NodeArrays geom_own_arrays(const fs3d_ctx *c)
 {
     uint8_t *sg = c->geom.stage;
-    NodeArrays a = {sg, sg + geom_gcell(c), sg + 2 * geom_gcell(c), {}};
+    const long long gcell = sg ? geom_gcell(c) : 0;      // (no staging buffer: fs3d_update_nodes_dev, which reads its own byte arrays)
+    NodeArrays a = {sg, sg + gcell, sg + 2 * gcell, {}};
     for (int v = 0; v < 4; v++) a.v[v] = (char *)c->node + (size_t)v * c->nstride * c->esize;
     return a;
 }
 
 // ---- extrusion of a Shape2D grid ----------------------------------------------------------------------------------------------
-struct ExtrudeIn { const uint8_t *cell; const float *velx, *vely, *T; double dz, depth, depth_var, baseT; int A; };
+struct ExtrudeIn {
+    const uint8_t *cell; const float *velx, *vely, *T; double dz, depth, depth_var, baseT; int A = 0;      // A: extrude_check's
+    bool any_null() const { return !cell || !velx || !vely || !T; }
+};
 
 #define EX_BOTTOM_BAD INT_MIN
 
@@ -1255,9 +1239,9 @@ static fs3d_status extrude_check(fs3d_ctx *c, ExtrudeIn &in, const char *name)
 }
 
 // the column records to the device and the kernel, on the context's stream; not synchronised.  slab: the byte arrays of `a` cover
-// the global grid, its value arrays the context's planes (k_geom_extrude_slab); else all seven cover the same cells.
+// the global grid, its value arrays the context's planes (k_geom_extrude<.., true>); else all seven cover the same cells.
 template <typename R>
-static fs3d_status extrude_launch(fs3d_ctx *c, const ExtrudeIn &in, const NodeArrays &a, bool slab = false)
+static fs3d_status extrude_launch(fs3d_ctx *c, const ExtrudeIn &in, const NodeArrays &a, bool slab)
 {
     fs3d_geom &g = c->geom;
     const size_t ncol = (size_t)c->dimx_global * c->dimy;
@@ -1266,27 +1250,22 @@ static fs3d_status extrude_launch(fs3d_ctx *c, const ExtrudeIn &in, const NodeAr
     g.ex_bottom_valid = true;
     const bool vec = a.vec4(c->dimz);
     const long long nthr = (long long)ncol * (vec ? c->dimz / 4 : c->dimz);
-    if (slab) {
-        auto ks = vec ? k_geom_extrude_slab<R, 4> : k_geom_extrude_slab<R, 1>;
-        hipLaunchKernelGGL(ks, dim3(grid_for(nthr, 1 << 30)), dim3(256), 0, c->stream, (const float *)d, (const float *)(d + 4 * ncol),
-                           (const float *)(d + 8 * ncol), (const int *)(d + ex_off_bottom(ncol)), (const uint8_t *)(d + ex_off_cell(ncol)),
-                           (long long)ncol, (long long)c->x_offset * c->dimy, (long long)c->dimx * c->dimy, c->dimz, in.A, (float)in.baseT,
-                           a.type, a.bc_vel, a.bc_temp, (R *)a.v[0], (R *)a.v[1], (R *)a.v[2], (R *)a.v[3]);
-        HIPCHK(c, hipGetLastError());
-        return FS3D_OK;
-    }
-    auto kern = vec ? k_geom_extrude<R, 4> : k_geom_extrude<R, 1>;
+    auto kern = slab ? (vec ? k_geom_extrude<R, 4, true> : k_geom_extrude<R, 1, true>) : (vec ? k_geom_extrude<R, 4, false> : k_geom_extrude<R, 1, false>);
     hipLaunchKernelGGL(kern, dim3(grid_for(nthr, 1 << 30)), dim3(256), 0, c->stream, (const float *)d, (const float *)(d + 4 * ncol),
                        (const float *)(d + 8 * ncol), (const int *)(d + ex_off_bottom(ncol)), (const uint8_t *)(d + ex_off_cell(ncol)),
-                       (long long)ncol, c->dimz, in.A, (float)in.baseT, a.type, a.bc_vel, a.bc_temp, (R *)a.v[0], (R *)a.v[1], (R *)a.v[2],
-                       (R *)a.v[3]);
+                       (long long)ncol, (long long)c->x_offset * c->dimy, (long long)c->dimx * c->dimy, c->dimz, in.A, (float)in.baseT,
+                       a.type, a.bc_vel, a.bc_temp, (R *)a.v[0], (R *)a.v[1], (R *)a.v[2], (R *)a.v[3]);
     HIPCHK(c, hipGetLastError());
     return FS3D_OK;
 }
 
 // ---- voxelisation of a Shape3D mesh ---------------------------------------------------------------------------------------------
 // vel: an entry with wall velocities -- wx, wy, wz per vertex and the walls' temperature (else null and 0)
-struct MeshIn { const float *x, *y, *z; int nvert; const int *tri; int ntri; double baseT; bool vel; const float *wx, *wy, *wz; double wallT; };
+struct MeshIn {
+    const float *x, *y, *z; int nvert; const int *tri; int ntri; double baseT;
+    bool vel = false; const float *wx = nullptr, *wy = nullptr, *wz = nullptr; double wallT = 0.0;
+    bool any_null() const { return !x || !y || !z || !tri || (vel && (!wx || !wy || !wz)); }
+};
 #define MESH_COLS 6                                    // columns of mesh_vcap floats in the pinned and the device block: x, y, z, wx, wy, wz
 
 #define MESH_FILL_BATCH 2                              // rounds of the flood fill between two looks at their counters
@@ -1322,6 +1301,8 @@ static fs3d_status mesh_check(fs3d_ctx *c, const MeshIn &in, const char *name, b
 {
     fs3d_geom &g = c->geom;
     const bool conservative = c->opt_mesh_voxels == 1;
+    if (in.vel && !conservative)                         // the owner of a wall cell is defined by the conservative overlap test
+        return fail(c, FS3D_ERR_INVALID, std::string(name) + ": wall velocities need the conservative voxelisation (FS3D_OPT_MESH_VOXELS = 1)");
     if (in.nvert < 1 || in.ntri < 0) return fail(c, FS3D_ERR_INVALID, std::string(name) + ": a mesh has at least one vertex and no negative number of triangles");
     for (int q = 0; q < 3 * in.ntri; q++)
         if (in.tri[q] < 0 || in.tri[q] >= in.nvert) return fail(c, FS3D_ERR_INVALID, std::string(name) + ": triangle index outside the vertex list");
@@ -1444,34 +1425,20 @@ static fs3d_status mesh_launch(fs3d_ctx *c, const MeshIn &in, bool new_idx, cons
 
 static bool geom_is_slab(const fs3d_ctx *c) { return c->dimx != c->dimx_global || c->x_offset != 0 || c->comm || c->local || c->nranks > 1; }
 
-// The refusals every geometry entry begins with, in this order; `what` is the entry's own wording ("moving geometry is", ...).
-static fs3d_status geom_refuse(fs3d_ctx *c, const char *name, bool any_null, const char *what)
+// The refusals every geometry entry begins with, in this order.  slab_what: the entry's own wording of its refusal of a slab
+// ("moving geometry is", ...); null: the entry takes a slab.
+static fs3d_status geom_refuse(fs3d_ctx *c, const char *name, bool any_null, const char *slab_what)
 {
     if (!c) return FS3D_ERR_INVALID;
     if (any_null) return fail(c, FS3D_ERR_INVALID, std::string(name) + ": NULL array");
-    if (geom_is_slab(c))
-        return fail(c, FS3D_ERR_UNSUPPORTED, std::string(name) + ": " + what + " implemented for a single context only, "
+    if (slab_what && geom_is_slab(c))
+        return fail(c, FS3D_ERR_UNSUPPORTED, std::string(name) + ": " + slab_what + " implemented for a single context only, "
                      "not for an x-slab of a larger grid or a member of a multi-GPU group");
     return FS3D_OK;
 }
 
-// ---- fs3d_update_nodes*: one update, phase by phase ---------------------------------------------------------------------------
-// 1. update_refuse; 2. the entry starts the host clock of CreateSegments and selects the device; 3. the check of its source
-// (extrude_check, mesh_check) -- refused up to here, the context keeps the geometry it has and nothing is counted; 4. update_begin;
-// 5. the entry puts the three byte arrays and the four value fields on the device; 6. update_end.
+// ---- fs3d_update_nodes*: one update ---------------------------------------------------------------------------------------------
 typedef std::chrono::steady_clock::time_point geom_clock;
-
-static fs3d_status update_refuse(fs3d_ctx *c, const char *name, bool any_null, bool slab = false)
-{
-    if (slab) {                                         // the slab entries: the same refusals but the one of a slab
-        if (!c) return FS3D_ERR_INVALID;
-        if (any_null) return fail(c, FS3D_ERR_INVALID, std::string(name) + ": NULL array");
-    } else
-        GTRY(geom_refuse(c, name, any_null, "moving geometry is"));
-    if (!c->uploaded_once)
-        return fail(c, FS3D_ERR_INVALID, std::string(name) + ": the first geometry comes through fs3d_upload_nodes; upload nodes first");
-    return FS3D_OK;
-}
 
 // rebuilt in place: from here until the end of update_end the context has no geometry.  Opens the first batch of the device time.
 static fs3d_status update_begin(fs3d_ctx *c, bool need_stage)
@@ -1486,12 +1453,10 @@ static fs3d_status update_begin(fs3d_ctx *c, bool need_stage)
 // The tables from the byte arrays (the value fields are in the node-value table by now), the device time and the CreateSegments
 // event.  `produced`: what the kernels of phase 5 returned; their failure is waited for, and its time is not counted.
 static fs3d_status update_end(fs3d_ctx *c, geom_clock t0, fs3d_status produced, const uint8_t *type, const uint8_t *bc_vel, const uint8_t *bc_temp,
-                              int n_seg_out[3], const char *slab_entry = nullptr)
+                              int n_seg_out[3], const char *name, bool slab)
 {
     fs3d_status st = produced;
-    if (st == FS3D_OK)
-        st = c->prec == FS3D_F32 ? update_nodes_impl<float>(c, type, bc_vel, bc_temp, slab_entry, n_seg_out)
-                                 : update_nodes_impl<double>(c, type, bc_vel, bc_temp, slab_entry, n_seg_out);
+    if (st == FS3D_OK) st = BY_PREC(c, update_nodes_impl, c, type, bc_vel, bc_temp, name, slab, n_seg_out);
     hipStreamSynchronize(c->stream);                      // (a failure half way: the caller's arrays are not read after the call returns)
     gev_collect(c);
     if (produced) return produced;
@@ -1500,132 +1465,144 @@ static fs3d_status update_end(fs3d_ctx *c, geom_clock t0, fs3d_status produced, 
     return st;
 }
 
+// Every fs3d_update_nodes* entry, phase by phase.  `name` is the entry's, `slab` whether it takes an x-slab (a whole-grid context
+// is the slab x_offset = 0, dimx = dimx_global); the source supplies its NULL test, its check and its producer.
+// 1. the refusals; 2. the host clock of CreateSegments starts and the device is selected; 3. check(): everything that refuses
+// the source (extrude_check, mesh_check) -- refused up to here, the context keeps the geometry it has and nothing is counted;
+// 4. update_begin; 5. produce(a): the three byte arrays and the four value fields onto the device, a = geom_own_arrays (a source
+// whose byte arrays are on the device already points a's at them); 6. update_end.
+template <typename Check, typename Produce>
+static fs3d_status update_run(fs3d_ctx *c, const char *name, bool slab, bool any_null, bool need_stage, Check check, Produce produce, int n_seg_out[3])
+{
+    GTRY(geom_refuse(c, name, any_null, slab ? nullptr : "moving geometry is"));
+    if (!c->uploaded_once)
+        return fail(c, FS3D_ERR_INVALID, std::string(name) + ": the first geometry comes through fs3d_upload_nodes; upload nodes first");
+    const geom_clock t0 = std::chrono::steady_clock::now();
+    HIPCHK(c, hipSetDevice(c->device));
+    GTRY(check());
+    GTRY(update_begin(c, need_stage));
+    NodeArrays a = geom_own_arrays(c);
+    const fs3d_status st = produce(a);
+    return update_end(c, t0, st, a.type, a.bc_vel, a.bc_temp, n_seg_out, name, slab);
+}
+
+// Source 1, the node arrays of the global grid (a single context: its own), on the host or (dev) on the context's device.
+struct ArraysIn { const uint8_t *b[3]; const void *v[4]; bool dev; };
+
+static fs3d_status update_arrays(fs3d_ctx *c, const char *name, bool slab, const ArraysIn &in, int n_seg_out[3])
+{
+    const bool any_null = !in.b[0] || !in.b[1] || !in.b[2] || !in.v[0] || !in.v[1] || !in.v[2] || !in.v[3];
+    return update_run(c, name, slab, any_null, !in.dev, [] { return FS3D_OK; }, [&](NodeArrays &a) -> fs3d_status {
+        const size_t first = (size_t)c->x_offset * c->plane;
+        uint8_t **own[3] = {&a.type, &a.bc_vel, &a.bc_temp};
+        for (int q = 0; q < 3; q++) {
+            if (in.dev) *own[q] = const_cast<uint8_t *>(in.b[q]);      // read where they are, never written
+            else HIPCHK(c, hipMemcpyAsync(*own[q], in.b[q], (size_t)geom_gcell(c), hipMemcpyHostToDevice, c->stream));
+        }
+        // the four node-value fields are one of the tables: the context's planes, copied straight into place
+        for (int v = 0; v < 4; v++) {
+            const void *src = (const char *)in.v[v] + first * c->esize;
+            if (a.v[v] != src) HIPCHK(c, hipMemcpyAsync(a.v[v], src, (size_t)c->ncell * c->esize, in.dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
+        }
+        return FS3D_OK;
+    }, n_seg_out);
+}
+
+// Source 2, a Shape2D grid: on a slab the global one, given to every rank
+static fs3d_status update_shape2d(fs3d_ctx *c, const char *name, bool slab, ExtrudeIn in, int n_seg_out[3])
+{
+    return update_run(c, name, slab, in.any_null(), true, [&] { return extrude_check(c, in, name); },
+                      [&](NodeArrays &a) { return BY_PREC(c, extrude_launch, c, in, a, slab); }, n_seg_out);
+}
+
+// Source 3, a Shape3D mesh, with or without velocities.  On a slab every rank voxelises and fills the GLOBAL grid in its own staging
+// buffer (mesh_launch), then builds the tables of its own planes.
+static fs3d_status update_mesh(fs3d_ctx *c, const char *name, bool slab, const MeshIn &in, int n_seg_out[3])
+{
+    bool new_idx = false;
+    return update_run(c, name, slab, in.any_null(), true, [&] { return mesh_check(c, in, name, &new_idx); },
+                      [&](NodeArrays &a) { return BY_PREC(c, mesh_launch, c, in, new_idx, name, a); }, n_seg_out);
+}
+
+// The entries.  The slab ones (include/fs3d_slab_geometry.h, include/fs3d_slab_mesh.h): every rank is given the global input and
+// rebuilds the tables of its own planes on its own stream; no rank talks to another one.
 extern "C" fs3d_status fs3d_update_nodes(fs3d_ctx *c, const uint8_t *type, const uint8_t *bc_vel, const uint8_t *bc_temp,
                                          const void *vx, const void *vy, const void *vz, const void *T, int n_seg_out[3])
 {
-    GTRY(update_refuse(c, "fs3d_update_nodes", !type || !bc_vel || !bc_temp || !vx || !vy || !vz || !T));
-    const geom_clock t0 = std::chrono::steady_clock::now();
-    HIPCHK(c, hipSetDevice(c->device));
-    GTRY(update_begin(c, true));
-    const NodeArrays own = geom_own_arrays(c);
-    HIPCHK(c, hipMemcpyAsync(own.type, type, (size_t)c->ncell, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(own.bc_vel, bc_vel, (size_t)c->ncell, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(own.bc_temp, bc_temp, (size_t)c->ncell, hipMemcpyHostToDevice, c->stream));
-    // the four node-value fields are one of the tables: copied straight into place
-    const void *val[4] = {vx, vy, vz, T};
-    for (int v = 0; v < 4; v++) HIPCHK(c, hipMemcpyAsync(own.v[v], val[v], (size_t)c->ncell * c->esize, hipMemcpyHostToDevice, c->stream));
-    return update_end(c, t0, FS3D_OK, own.type, own.bc_vel, own.bc_temp, n_seg_out);
+    return update_arrays(c, "fs3d_update_nodes", false, {{type, bc_vel, bc_temp}, {vx, vy, vz, T}, false}, n_seg_out);
+}
+
+extern "C" fs3d_status fs3d_update_nodes_slab(fs3d_ctx *c, const uint8_t *type, const uint8_t *bc_vel, const uint8_t *bc_temp,
+                                              const void *vx, const void *vy, const void *vz, const void *T, int n_seg_out[3])
+{
+    return update_arrays(c, "fs3d_update_nodes_slab", true, {{type, bc_vel, bc_temp}, {vx, vy, vz, T}, false}, n_seg_out);
 }
 
 extern "C" fs3d_status fs3d_update_nodes_dev(fs3d_ctx *c, const uint8_t *type, const uint8_t *bc_vel, const uint8_t *bc_temp,
                                              const void *vx, const void *vy, const void *vz, const void *T, int n_seg_out[3])
 {
-    GTRY(update_refuse(c, "fs3d_update_nodes_dev", !type || !bc_vel || !bc_temp || !vx || !vy || !vz || !T));
-    const geom_clock t0 = std::chrono::steady_clock::now();
-    HIPCHK(c, hipSetDevice(c->device));
-    GTRY(update_begin(c, false));                         // the byte arrays are read where they are
-    const void *val[4] = {vx, vy, vz, T};
-    for (int v = 0; v < 4; v++) {
-        void *dst = (char *)c->node + (size_t)v * c->nstride * c->esize;
-        if (dst != val[v]) HIPCHK(c, hipMemcpyAsync(dst, val[v], (size_t)c->ncell * c->esize, hipMemcpyDeviceToDevice, c->stream));
-    }
-    return update_end(c, t0, FS3D_OK, type, bc_vel, bc_temp, n_seg_out);
+    return update_arrays(c, "fs3d_update_nodes_dev", false, {{type, bc_vel, bc_temp}, {vx, vy, vz, T}, true}, n_seg_out);
 }
 
 extern "C" fs3d_status fs3d_update_nodes_shape2d(fs3d_ctx *c, const uint8_t *cell2d, const float *velx2d, const float *vely2d, const float *T2d,
                                                  double dz, double depth, double depth_var, double baseT, int n_seg_out[3])
 {
-    const char *name = "fs3d_update_nodes_shape2d";
-    GTRY(update_refuse(c, name, !cell2d || !velx2d || !vely2d || !T2d));
-    const geom_clock t0 = std::chrono::steady_clock::now();
-    HIPCHK(c, hipSetDevice(c->device));
-    ExtrudeIn in = {cell2d, velx2d, vely2d, T2d, dz, depth, depth_var, baseT, 0};
-    GTRY(extrude_check(c, in, name));
-    GTRY(update_begin(c, true));
-    const NodeArrays own = geom_own_arrays(c);
-    const fs3d_status st = c->prec == FS3D_F32 ? extrude_launch<float>(c, in, own) : extrude_launch<double>(c, in, own);
-    return update_end(c, t0, st, own.type, own.bc_vel, own.bc_temp, n_seg_out);
-}
-
-// ---- the slab entries (include/fs3d_slab_geometry.h): every rank is given the global input and rebuilds the tables of its own
-// planes on its own stream; no rank talks to another one
-extern "C" fs3d_status fs3d_update_nodes_slab(fs3d_ctx *c, const uint8_t *type, const uint8_t *bc_vel, const uint8_t *bc_temp,
-                                              const void *vx, const void *vy, const void *vz, const void *T, int n_seg_out[3])
-{
-    const char *name = "fs3d_update_nodes_slab";
-    GTRY(update_refuse(c, name, !type || !bc_vel || !bc_temp || !vx || !vy || !vz || !T, true));
-    const geom_clock t0 = std::chrono::steady_clock::now();
-    HIPCHK(c, hipSetDevice(c->device));
-    GTRY(update_begin(c, true));
-    const NodeArrays own = geom_own_arrays(c);
-    const size_t gcell = (size_t)geom_gcell(c), first = (size_t)c->x_offset * c->plane;
-    HIPCHK(c, hipMemcpyAsync(own.type, type, gcell, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(own.bc_vel, bc_vel, gcell, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(own.bc_temp, bc_temp, gcell, hipMemcpyHostToDevice, c->stream));
-    // the value fields of the slab's planes only
-    const void *val[4] = {vx, vy, vz, T};
-    for (int v = 0; v < 4; v++)
-        HIPCHK(c, hipMemcpyAsync(own.v[v], (const char *)val[v] + first * c->esize, (size_t)c->ncell * c->esize, hipMemcpyHostToDevice, c->stream));
-    return update_end(c, t0, FS3D_OK, own.type, own.bc_vel, own.bc_temp, n_seg_out, name);
+    return update_shape2d(c, "fs3d_update_nodes_shape2d", false, {cell2d, velx2d, vely2d, T2d, dz, depth, depth_var, baseT}, n_seg_out);
 }
 
 extern "C" fs3d_status fs3d_update_nodes_shape2d_slab(fs3d_ctx *c, const uint8_t *cell2d, const float *velx2d, const float *vely2d, const float *T2d,
                                                       double dz, double depth, double depth_var, double baseT, int n_seg_out[3])
 {
-    const char *name = "fs3d_update_nodes_shape2d_slab";
-    GTRY(update_refuse(c, name, !cell2d || !velx2d || !vely2d || !T2d, true));
-    const geom_clock t0 = std::chrono::steady_clock::now();
-    HIPCHK(c, hipSetDevice(c->device));
-    ExtrudeIn in = {cell2d, velx2d, vely2d, T2d, dz, depth, depth_var, baseT, 0};
-    GTRY(extrude_check(c, in, name));
-    GTRY(update_begin(c, true));
-    const NodeArrays own = geom_own_arrays(c);
-    const fs3d_status st = c->prec == FS3D_F32 ? extrude_launch<float>(c, in, own, true) : extrude_launch<double>(c, in, own, true);
-    return update_end(c, t0, st, own.type, own.bc_vel, own.bc_temp, n_seg_out, name);
+    return update_shape2d(c, "fs3d_update_nodes_shape2d_slab", true, {cell2d, velx2d, vely2d, T2d, dz, depth, depth_var, baseT}, n_seg_out);
 }
 
+extern "C" fs3d_status fs3d_update_nodes_shape3d(fs3d_ctx *c, const float *x, const float *y, const float *z, int nvert, const int *tri, int ntri,
+                                                 double baseT, int n_seg_out[3])
+{
+    return update_mesh(c, "fs3d_update_nodes_shape3d", false, {x, y, z, nvert, tri, ntri, baseT}, n_seg_out);
+}
+
+extern "C" fs3d_status fs3d_update_nodes_shape3d_slab(fs3d_ctx *c, const float *x, const float *y, const float *z, int nvert, const int *tri,
+                                                      int ntri, double baseT, int n_seg_out[3])
+{
+    return update_mesh(c, "fs3d_update_nodes_shape3d_slab", true, {x, y, z, nvert, tri, ntri, baseT}, n_seg_out);
+}
+
+extern "C" fs3d_status fs3d_update_nodes_shape3d_vel(fs3d_ctx *c, const float *x, const float *y, const float *z, const float *wx, const float *wy,
+                                                     const float *wz, int nvert, const int *tri, int ntri, double baseT, double wallT, int n_seg_out[3])
+{
+    return update_mesh(c, "fs3d_update_nodes_shape3d_vel", false, {x, y, z, nvert, tri, ntri, baseT, true, wx, wy, wz, wallT}, n_seg_out);
+}
+
+extern "C" fs3d_status fs3d_update_nodes_shape3d_vel_slab(fs3d_ctx *c, const float *x, const float *y, const float *z, const float *wx,
+                                                          const float *wy, const float *wz, int nvert, const int *tri, int ntri, double baseT,
+                                                          double wallT, int n_seg_out[3])
+{
+    return update_mesh(c, "fs3d_update_nodes_shape3d_vel_slab", true, {x, y, z, nvert, tri, ntri, baseT, true, wx, wy, wz, wallT}, n_seg_out);
+}
+
+// ---- the test aids: one stage of an update into the caller's device arrays; the context's geometry is not touched ----------------
 extern "C" fs3d_status fs3d_extrude_shape2d_dev(fs3d_ctx *c, const uint8_t *cell2d, const float *velx2d, const float *vely2d, const float *T2d,
                                                 double dz, double depth, double depth_var, double baseT, uint8_t *type_out,
                                                 uint8_t *bc_vel_out, uint8_t *bc_temp_out, void *vx_out, void *vy_out, void *vz_out, void *T_out)
 {
     const char *name = "fs3d_extrude_shape2d_dev";
     const NodeArrays out = {type_out, bc_vel_out, bc_temp_out, {vx_out, vy_out, vz_out, T_out}};
-    GTRY(geom_refuse(c, name, !cell2d || !velx2d || !vely2d || !T2d || out.any_null(), "the extrusion is"));
-    ExtrudeIn in = {cell2d, velx2d, vely2d, T2d, dz, depth, depth_var, baseT, 0};
+    ExtrudeIn in = {cell2d, velx2d, vely2d, T2d, dz, depth, depth_var, baseT};
+    GTRY(geom_refuse(c, name, in.any_null() || out.any_null(), "the extrusion is"));
     GTRY(extrude_check(c, in, name));
-    GTRY(c->prec == FS3D_F32 ? extrude_launch<float>(c, in, out) : extrude_launch<double>(c, in, out));
+    GTRY(BY_PREC(c, extrude_launch, c, in, out, false));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return FS3D_OK;
 }
 
-extern "C" fs3d_status fs3d_update_nodes_shape3d(fs3d_ctx *c, const float *x, const float *y, const float *z, int nvert, const int *tri, int ntri,
-                                                 double baseT, int n_seg_out[3])
+static fs3d_status voxelize_dev(fs3d_ctx *c, const char *name, const MeshIn &in, const NodeArrays &out)
 {
-    const char *name = "fs3d_update_nodes_shape3d";
-    GTRY(update_refuse(c, name, !x || !y || !z || !tri));
-    const geom_clock t0 = std::chrono::steady_clock::now();
-    HIPCHK(c, hipSetDevice(c->device));
-    const MeshIn in = {x, y, z, nvert, tri, ntri, baseT, false, nullptr, nullptr, nullptr, 0.0};
-    bool new_idx = false;
-    GTRY(mesh_check(c, in, name, &new_idx));
-    GTRY(update_begin(c, true));
-    const NodeArrays own = geom_own_arrays(c);
-    const fs3d_status st = c->prec == FS3D_F32 ? mesh_launch<float>(c, in, new_idx, name, own) : mesh_launch<double>(c, in, new_idx, name, own);
-    return update_end(c, t0, st, own.type, own.bc_vel, own.bc_temp, n_seg_out);
-}
-
-extern "C" fs3d_status fs3d_voxelize_shape3d_dev(fs3d_ctx *c, const float *x, const float *y, const float *z, int nvert, const int *tri, int ntri,
-                                                 double baseT, uint8_t *type_out, uint8_t *bc_vel_out, uint8_t *bc_temp_out, void *vx_out,
-                                                 void *vy_out, void *vz_out, void *T_out)
-{
-    const char *name = "fs3d_voxelize_shape3d_dev";
-    const NodeArrays out = {type_out, bc_vel_out, bc_temp_out, {vx_out, vy_out, vz_out, T_out}};
-    GTRY(geom_refuse(c, name, !x || !y || !z || !tri || out.any_null(), "the voxelisation is"));
-    const MeshIn in = {x, y, z, nvert, tri, ntri, baseT, false, nullptr, nullptr, nullptr, 0.0};
+    GTRY(geom_refuse(c, name, in.any_null() || out.any_null(), "the voxelisation is"));
     bool new_idx = false;
     GTRY(mesh_check(c, in, name, &new_idx));
     gev_reset(c);                                        // (no update: its device time is not reported)
-    const fs3d_status st = c->prec == FS3D_F32 ? mesh_launch<float>(c, in, new_idx, name, out) : mesh_launch<double>(c, in, new_idx, name, out);
+    const fs3d_status st = BY_PREC(c, mesh_launch, c, in, new_idx, name, out);
     const hipError_t e = hipStreamSynchronize(c->stream);
     gev_reset(c);
     if (st) return st;
@@ -1633,58 +1610,12 @@ extern "C" fs3d_status fs3d_voxelize_shape3d_dev(fs3d_ctx *c, const float *x, co
     return FS3D_OK;
 }
 
-// the refusal the two entries with wall velocities add: the owner of a wall cell is defined by the conservative overlap test
-static fs3d_status vel_refuse(fs3d_ctx *c, const char *name)
+extern "C" fs3d_status fs3d_voxelize_shape3d_dev(fs3d_ctx *c, const float *x, const float *y, const float *z, int nvert, const int *tri, int ntri,
+                                                 double baseT, uint8_t *type_out, uint8_t *bc_vel_out, uint8_t *bc_temp_out, void *vx_out,
+                                                 void *vy_out, void *vz_out, void *T_out)
 {
-    if (c->opt_mesh_voxels != 1)
-        return fail(c, FS3D_ERR_INVALID, std::string(name) + ": wall velocities need the conservative voxelisation (FS3D_OPT_MESH_VOXELS = 1)");
-    return FS3D_OK;
-}
-
-extern "C" fs3d_status fs3d_update_nodes_shape3d_vel(fs3d_ctx *c, const float *x, const float *y, const float *z, const float *wx, const float *wy,
-                                                     const float *wz, int nvert, const int *tri, int ntri, double baseT, double wallT, int n_seg_out[3])
-{
-    const char *name = "fs3d_update_nodes_shape3d_vel";
-    GTRY(update_refuse(c, name, !x || !y || !z || !wx || !wy || !wz || !tri));
-    GTRY(vel_refuse(c, name));
-    const geom_clock t0 = std::chrono::steady_clock::now();
-    HIPCHK(c, hipSetDevice(c->device));
-    const MeshIn in = {x, y, z, nvert, tri, ntri, baseT, true, wx, wy, wz, wallT};
-    bool new_idx = false;
-    GTRY(mesh_check(c, in, name, &new_idx));
-    GTRY(update_begin(c, true));
-    const NodeArrays own = geom_own_arrays(c);
-    const fs3d_status st = c->prec == FS3D_F32 ? mesh_launch<float>(c, in, new_idx, name, own) : mesh_launch<double>(c, in, new_idx, name, own);
-    return update_end(c, t0, st, own.type, own.bc_vel, own.bc_temp, n_seg_out);
-}
-
-// The mesh entries on a slab: every rank voxelises and fills the GLOBAL grid in its own staging buffer (mesh_launch), then builds
-// the tables of its own planes.  The refusals of the single-context entries, in their order, but the one of a slab.
-static fs3d_status update_shape3d_slab(fs3d_ctx *c, const char *name, const MeshIn &in, int n_seg_out[3])
-{
-    GTRY(update_refuse(c, name, !in.x || !in.y || !in.z || !in.tri || (in.vel && (!in.wx || !in.wy || !in.wz)), true));
-    if (in.vel) GTRY(vel_refuse(c, name));
-    const geom_clock t0 = std::chrono::steady_clock::now();
-    HIPCHK(c, hipSetDevice(c->device));
-    bool new_idx = false;
-    GTRY(mesh_check(c, in, name, &new_idx));
-    GTRY(update_begin(c, true));
-    const NodeArrays own = geom_own_arrays(c);
-    const fs3d_status st = c->prec == FS3D_F32 ? mesh_launch<float>(c, in, new_idx, name, own) : mesh_launch<double>(c, in, new_idx, name, own);
-    return update_end(c, t0, st, own.type, own.bc_vel, own.bc_temp, n_seg_out, name);
-}
-
-extern "C" fs3d_status fs3d_update_nodes_shape3d_slab(fs3d_ctx *c, const float *x, const float *y, const float *z, int nvert, const int *tri,
-                                                      int ntri, double baseT, int n_seg_out[3])
-{
-    return update_shape3d_slab(c, "fs3d_update_nodes_shape3d_slab", {x, y, z, nvert, tri, ntri, baseT, false, nullptr, nullptr, nullptr, 0.0}, n_seg_out);
-}
-
-extern "C" fs3d_status fs3d_update_nodes_shape3d_vel_slab(fs3d_ctx *c, const float *x, const float *y, const float *z, const float *wx,
-                                                          const float *wy, const float *wz, int nvert, const int *tri, int ntri, double baseT,
-                                                          double wallT, int n_seg_out[3])
-{
-    return update_shape3d_slab(c, "fs3d_update_nodes_shape3d_vel_slab", {x, y, z, nvert, tri, ntri, baseT, true, wx, wy, wz, wallT}, n_seg_out);
+    return voxelize_dev(c, "fs3d_voxelize_shape3d_dev", {x, y, z, nvert, tri, ntri, baseT},
+                        {type_out, bc_vel_out, bc_temp_out, {vx_out, vy_out, vz_out, T_out}});
 }
 
 extern "C" fs3d_status fs3d_voxelize_shape3d_vel_dev(fs3d_ctx *c, const float *x, const float *y, const float *z, const float *wx, const float *wy,
@@ -1692,45 +1623,25 @@ extern "C" fs3d_status fs3d_voxelize_shape3d_vel_dev(fs3d_ctx *c, const float *x
                                                      uint8_t *type_out, uint8_t *bc_vel_out, uint8_t *bc_temp_out, void *vx_out, void *vy_out,
                                                      void *vz_out, void *T_out)
 {
-    const char *name = "fs3d_voxelize_shape3d_vel_dev";
-    const NodeArrays out = {type_out, bc_vel_out, bc_temp_out, {vx_out, vy_out, vz_out, T_out}};
-    GTRY(geom_refuse(c, name, !x || !y || !z || !wx || !wy || !wz || !tri || out.any_null(), "the voxelisation is"));
-    GTRY(vel_refuse(c, name));
-    const MeshIn in = {x, y, z, nvert, tri, ntri, baseT, true, wx, wy, wz, wallT};
-    bool new_idx = false;
-    GTRY(mesh_check(c, in, name, &new_idx));
-    gev_reset(c);                                        // (no update: its device time is not reported)
-    const fs3d_status st = c->prec == FS3D_F32 ? mesh_launch<float>(c, in, new_idx, name, out) : mesh_launch<double>(c, in, new_idx, name, out);
-    const hipError_t e = hipStreamSynchronize(c->stream);
-    gev_reset(c);
-    if (st) return st;
-    HIPCHK(c, e);
-    return FS3D_OK;
+    return voxelize_dev(c, "fs3d_voxelize_shape3d_vel_dev", {x, y, z, nvert, tri, ntri, baseT, true, wx, wy, wz, wallT},
+                        {type_out, bc_vel_out, bc_temp_out, {vx_out, vy_out, vz_out, T_out}});
 }
 
-extern "C" fs3d_status fs3d_flood_fill_dev(fs3d_ctx *c, uint8_t *type_inout)
+// slab_what: as geom_refuse takes it
+static fs3d_status flood_fill_dev(fs3d_ctx *c, const char *name, uint8_t *type_inout, const char *slab_what)
 {
-    const char *name = "fs3d_flood_fill_dev";
-    GTRY(geom_refuse(c, name, !type_inout, "the flood fill is"));
+    GTRY(geom_refuse(c, name, !type_inout, slab_what));
     GTRY(mesh_prepare(c, 0, 0));
     gev_reset(c);
     const fs3d_status st = mesh_fill(c, type_inout, false, name);
     gev_reset(c);
     return st;
 }
+
+extern "C" fs3d_status fs3d_flood_fill_dev(fs3d_ctx *c, uint8_t *type_inout) { return flood_fill_dev(c, "fs3d_flood_fill_dev", type_inout, "the flood fill is"); }
 
 // the same on the type array of the global grid, from any context (a slab: the fill does not stop at its cuts)
-extern "C" fs3d_status fs3d_flood_fill_global_dev(fs3d_ctx *c, uint8_t *type_inout)
-{
-    const char *name = "fs3d_flood_fill_global_dev";
-    if (!c) return FS3D_ERR_INVALID;
-    if (!type_inout) return fail(c, FS3D_ERR_INVALID, std::string(name) + ": NULL array");
-    GTRY(mesh_prepare(c, 0, 0));
-    gev_reset(c);
-    const fs3d_status st = mesh_fill(c, type_inout, false, name);
-    gev_reset(c);
-    return st;
-}
+extern "C" fs3d_status fs3d_flood_fill_global_dev(fs3d_ctx *c, uint8_t *type_inout) { return flood_fill_dev(c, "fs3d_flood_fill_global_dev", type_inout, nullptr); }
 
 extern "C" fs3d_status fs3d_mesh_fill_rounds(fs3d_ctx *c, int *rounds_out)
 {

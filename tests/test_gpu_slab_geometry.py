@@ -94,6 +94,21 @@ def test_whole_grid_context_takes_the_slab_entry(built, name):
     a.close(); b.close()
 
 
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+@pytest.mark.parametrize("name", ["adz5-var3-ragged", "adz5-var3-align"])       # dimz = 17: one cell per thread; dimz % 4 == 0: four
+def test_whole_grid_context_takes_the_shape2d_slab_entry(built, name, dtype):
+    """The two Shape2D entries are the two instantiations of one extrusion kernel (k_geom_extrude<.., SLAB>): on a whole-grid context
+    they leave the same tables and the same node values."""
+    start, g2, p, want = shape2d_case(name)
+    assert tuple(start.shape) == tuple(want.shape)
+    a, b = capi.Solver(start, params(dtype), dtype), capi.Solver(start, params(dtype), dtype)
+    args = (g2, p["dz"], p["depth"], p["depth_var"], p["baseT"])
+    assert a.update_nodes_shape2d_slab(*args) == b.update_nodes_shape2d(*args)
+    print(name, want.shape, tables(a))
+    assert_same_context(a, b, name)
+    a.close(); b.close()
+
+
 # ---- 2. refusals ---------------------------------------------------------------------------------------------------------------
 
 def raw_update(s, g, null=False):
