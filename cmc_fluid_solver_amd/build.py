@@ -13,7 +13,7 @@ LIB = os.path.join(HERE, "libfs3d_hip.so")
 SOURCES = ["fs3d_hip.hip", "fs3d_comm.hip", "kernels_line.hip", "kernels_pipe.hip", "kernels_part.hip", "kernels_geom.hip"]
 HEADERS = ["fs3d_common.h", "fs3d_tables.h", "fs3d_device.h", "fs3d_rows.h", "fs3d_comm.h", os.path.join("..", "..", "include", "fs3d.h"),
            os.path.join("..", "..", "include", "fs3d_mesh_walls.h"), os.path.join("..", "..", "include", "fs3d_slab_geometry.h"),
-           os.path.join("..", "..", "include", "fs3d_slab_mesh.h")]
+           os.path.join("..", "..", "include", "fs3d_slab_mesh.h"), os.path.join("..", "..", "include", "fs3d_fresh_cells.h")]
 
 # -ffp-contract=off: no FMA contraction, the reference's CPU path rounds after every operation.
 # -fhip-fp32-correctly-rounded-divide-sqrt: IEEE fp32 division (the hipcc default, stated explicitly).

@@ -24,6 +24,7 @@ OPT_F64_PART = 6          # fp64 contexts: 1 opens the fp64 partition kernels to
 OPT_ERR_ORDER = 7         # 1: EvalDivError sums its terms serially in cell order, as the CPU path (bit-equal reported error on the exact kernels)
 OPT_MESH_VOXELS = 8       # the two mesh entries: 0 the reference's rasteriser (default), 1 conservative voxelisation (watertight)
 MESH_VOXELS = {"reference": 0, "conservative": 1}
+OPT_FRESH_CELLS = 9       # 1: every single-context update_nodes* keeps the node types of the geometry it replaces, for fill_fresh_cells (default 0)
 XSOLVE_AUTO, XSOLVE_PIPELINED, XSOLVE_REDUCED, XSOLVE_REDUCED_A2A = 0, 1, 2, 3
 
 # every symbol include/fs3d.h declares: name -> (restype, argtypes)
@@ -98,6 +99,13 @@ SYMBOLS_SLAB_MESH = {
     "fs3d_flood_fill_global_dev": (_i, [_vp, _vp]),
 }
 
+# every symbol include/fs3d_fresh_cells.h declares (the extension header of the fresh-cell fill)
+SYMBOLS_FRESH_CELLS = {
+    "fs3d_fill_fresh_cells_dev": (_i, [_vp, _vp, _i, _i, C.POINTER(C.c_longlong)]),
+    "fs3d_fill_fresh_cells": (_i, [_vp, _i, _i, C.POINTER(C.c_longlong)]),
+    "fs3d_last_fill_device_ms": (_i, [_vp, C.POINTER(C.c_float)]),
+}
+
 _lib = None
 
 
@@ -116,7 +124,7 @@ def load():
                                "or __graft_entry__.build()" % LIB_PATH)
         lib = C.CDLL(LIB_PATH)
         for name, (res, args) in list(SYMBOLS.items()) + list(SYMBOLS_MESH_WALLS.items()) + list(SYMBOLS_SLAB_GEOMETRY.items()) + \
-                list(SYMBOLS_SLAB_MESH.items()):
+                list(SYMBOLS_SLAB_MESH.items()) + list(SYMBOLS_FRESH_CELLS.items()):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
@@ -345,6 +353,27 @@ class Solver:
     def clear_outer_cells(self, layer, baseT):
         """Solver3D::ClearOutterCells on one layer: U, V, W := 0 and T := baseT on the NODE_OUT cells."""
         self._chk(self.lib.fs3d_clear_outer_cells(self.h, layer, float(baseT)))
+
+    def fill_fresh_cells(self, layer, max_rounds=0):
+        """fs3d_fill_fresh_cells: the cells of `layer` that the last update_nodes* turned NODE_IN take the mean of their fluid
+        neighbours (fresh_cells.fill_fresh_cells is the rule), from the snapshot OPT_FRESH_CELLS keeps.
+        Returns (fresh, filled, rounds, left)."""
+        info = (C.c_longlong * 4)()
+        self._chk(self.lib.fs3d_fill_fresh_cells(self.h, layer, max_rounds, info))
+        return tuple(info)
+
+    def fill_fresh_cells_dev(self, prev_type, layer, max_rounds=0):
+        """The stateless form: prev_type is the node types before the update, on the context's device -- a uint8 torch tensor
+        (contiguous, of the grid's size) or a raw device pointer (int), as update_nodes_dev takes its arrays."""
+        info = (C.c_longlong * 4)()
+        self._chk(self.lib.fs3d_fill_fresh_cells_dev(self.h, self._dev_ptrs("fill_fresh_cells_dev", [prev_type])[0], layer, max_rounds, info))
+        return tuple(info)
+
+    def last_fill_device_ms(self):
+        """Device time of the last fill_fresh_cells* call (measured while enable_timing is on, else 0)."""
+        ms = C.c_float(0)
+        self._chk(self.lib.fs3d_last_fill_device_ms(self.h, C.byref(ms)))
+        return ms.value
 
     def last_update_device_ms(self):
         """Device time of the last update_nodes* call (measured while enable_timing is on, else 0)."""

@@ -99,6 +99,18 @@ struct fs3d_geom {
     bool ev_open = false;
     float ev_ms = 0;
     float last_dev_ms = 0;
+    // fresh cells (k_fresh_classify, k_fresh_round; fs3d_fill_fresh_cells*).  The snapshot belongs to FS3D_OPT_FRESH_CELLS: one byte per
+    // cell, the node types of the geometry the last update replaced, allocated by the first update made with the option on.  The
+    // fill's own buffers are allocated by the first fill, kept and only grown: the round tag of every cell, the compact list of the
+    // fresh cells, the counter words (device, and pinned on their way back)
+    uint8_t *prev_type = nullptr;
+    bool prev_valid = false;                // prev_type holds the types of the geometry before the one the tables describe now
+    float snap_ms = 0;                      // device time of the copy that made it (counted with the fill that reads it)
+    uint8_t *fill_tag = nullptr;
+    int *fill_list = nullptr;
+    long long fill_cap = 0;                 // entries fill_list holds
+    unsigned *fill_cnt = nullptr, *fill_host = nullptr;
+    float last_fill_ms = 0;
 };
 
 struct fs3d_ctx {
@@ -156,6 +168,7 @@ struct fs3d_ctx {
     int opt_keep_temp = 0;                 // FS3D_OPT_KEEP_TEMP
     int opt_f64_part = 0;                  // FS3D_OPT_F64_PART
     int opt_mesh_voxels = 0;               // FS3D_OPT_MESH_VOXELS: 0 = the reference's rasteriser, 1 = conservative voxelisation (k_geom_voxel_mesh)
+    int opt_fresh_cells = 0;               // FS3D_OPT_FRESH_CELLS: 1 = every single-context update keeps the node types of the geometry it replaces
     int opt_err_order = 0;                 // FS3D_OPT_ERR_ORDER: 1 = EvalDivError sums its per-cell terms serially in cell order (host), as the CPU path
     double *err_terms = nullptr;           // ... one term per cell (device, allocated on first use)
     std::vector<double> err_terms_host;

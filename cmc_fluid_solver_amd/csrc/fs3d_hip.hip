@@ -412,6 +412,9 @@ extern "C" fs3d_status fs3d_set_option(fs3d_ctx *c, int option, int value)
     case FS3D_OPT_MESH_VOXELS:
         if (value != 0 && value != 1) return fail(c, FS3D_ERR_INVALID, "bad mesh voxelisation id (0: the reference's rasteriser, 1: conservative)");
         c->opt_mesh_voxels = value; return FS3D_OK;
+    case FS3D_OPT_FRESH_CELLS:
+        if (value != 0 && value != 1) return fail(c, FS3D_ERR_INVALID, "bad fresh-cells value (0: off, 1: the updates keep the node types of the geometry they replace)");
+        c->opt_fresh_cells = value; return FS3D_OK;
     case FS3D_OPT_XSOLVE:
         if (value < 0 || value > 3) return fail(c, FS3D_ERR_INVALID, "bad cross-slab X solve id");
         c->opt_xsolve = value; return FS3D_OK;
@@ -517,6 +520,7 @@ extern "C" fs3d_status fs3d_upload_nodes(fs3d_ctx *c, const uint8_t *type, const
     if (!c) return FS3D_ERR_INVALID;
     if (!type || !bc_vel || !bc_temp || !vx || !vy || !vz || !T) return fail(c, FS3D_ERR_INVALID, "fs3d_upload_nodes: NULL array");
     const auto t0 = std::chrono::steady_clock::now();
+    c->geom.prev_valid = false;                           // an upload is a new first geometry: no update stands behind it
     const fs3d_status st = c->prec == FS3D_F32
         ? upload_nodes_impl<float>(c, type, bc_vel, bc_temp, (const float *)vx, (const float *)vy, (const float *)vz, (const float *)T, n_seg_out)
         : upload_nodes_impl<double>(c, type, bc_vel, bc_temp, (const double *)vx, (const double *)vy, (const double *)vz, (const double *)T, n_seg_out);

@@ -11,6 +11,8 @@
 // (k_geom_lines_x_slab, k_geom_codes<true>, k_geom_extrude<.., true>), everything else runs on the slab's planes.  A mesh on an x-slab
 // (fs3d_update_nodes_shape3d_slab, fs3d_update_nodes_shape3d_vel_slab; include/fs3d_slab_mesh.h) is voxelised and flood-filled over
 // the GLOBAL grid by every rank, in the staging buffer that holds the global byte arrays anyway: the fill is global.
+// And the fresh cells (k_fresh_classify, k_fresh_round; fs3d_fill_fresh_cells*, include/fs3d_fresh_cells.h): a cell that an update
+// turned NODE_IN takes the mean of its fluid neighbours, from the previous node types the caller gives or FS3D_OPT_FRESH_CELLS keeps.
 // Every fs3d_update_nodes* entry is one statement above update_run, the one body of an update: a source (node arrays, a Shape2D
 // grid, a mesh) gives its NULL test, its check and its producer, and a whole-grid context is the slab x_offset = 0, dimx_global = dimx.
 //
@@ -31,6 +33,7 @@
 #include <unordered_map>
 
 #include "fs3d_common.h"
+#include "../../include/fs3d_fresh_cells.h"
 #include "../../include/fs3d_mesh_walls.h"
 #include "../../include/fs3d_slab_geometry.h"
 
@@ -905,6 +908,145 @@ __global__ void __launch_bounds__(256) k_geom_mesh_nodes_vel(const uint8_t *__re
     store_nodes<R, V, false>(l, 0u, noslip, noslip, ax, ay, aT, nullptr, bc_vel, bc_temp, vx, vy, vz, T, az);
 }
 
+// ---- fresh cells: a cell that turns NODE_IN takes the mean of its fluid neighbours (fs3d_fill_fresh_cells*) ------------------------
+// cmc_fluid_solver_amd/fresh_cells.py fill_fresh_cells is the definition; the kernels end with its bits.  Every cell carries one
+// byte, its round tag: 0 a donor (NODE_IN before and now), 1 .. 250 the round that filled it, FRESH_UNFILLED a fresh cell (NODE_IN
+// now, something else before) still waiting, FRESH_OTHER everything else.  In round r a neighbour counts iff its tag is below r, and
+// a cell filled in round r gets tag r: a round reads only cells that no thread of the round writes (their tags are below r, the
+// written ones hold FRESH_UNFILLED or r), tags are single bytes read and written as single bytes, the fields are filled in place --
+// so a round is free of races and the order of the list is free.  The neighbours are summed in the order i-1, i+1, j-1, j+1, k-1,
+// k+1, the first one starting the sum, then ONE division by (R)n: this file is compiled without contraction and with IEEE division.
+#define FRESH_UNFILLED 254
+#define FRESH_OTHER 255
+#define FRESH_MAX_ROUNDS 250
+#define FRESH_BATCH 2                                   // rounds between two looks at their counters
+// counter words of one fill (unsigned): [0] the fresh cells (the list's length), [r] the cells round r filled, r = 1 .. 250
+enum { FC_FRESH = 0, FC_WORDS = FRESH_MAX_ROUNDS + 2 };
+
+typedef unsigned FreshU4 __attribute__((ext_vector_type(4)));
+typedef unsigned FreshU2 __attribute__((ext_vector_type(2)));
+
+// node types of the V == 8 cells from l (l % 8 == 0: the table is aligned to 16 bytes), one per byte of the two result words
+__device__ __forceinline__ FreshU2 fresh_types8(const uint16_t *__restrict__ code, long long l)
+{
+    const FreshU4 cw = *(const FreshU4 *)(code + l);
+    FreshU2 t = {0u, 0u};
+#pragma unroll
+    for (int q = 0; q < 8; q++) t[q >> 2] |= ((cw[q >> 1] >> (16 * (q & 1) + CODE_TYPE_SHIFT)) & 3u) << (8 * (q & 3));
+    return t;
+}
+
+// The snapshot of FS3D_OPT_FRESH_CELLS: the node types of the code table, one byte per cell, before an update rewrites the table.
+__global__ void __launch_bounds__(256) k_fresh_snapshot(const uint16_t *__restrict__ code, long long ncell, uint8_t *__restrict__ prev)
+{
+    const long long l = ((long long)blockIdx.x * 256 + threadIdx.x) * 8;
+    if (l + 8 <= ncell) *(FreshU2 *)(prev + l) = fresh_types8(code, l);        // (prev is the context's own allocation: aligned)
+    else for (long long q = l; q < ncell; q++) prev[q] = (uint8_t)((code[q] >> CODE_TYPE_SHIFT) & 3);
+}
+
+// One streaming pass: the round tag of every cell from its code word and its previous type, and the compact list of the fresh
+// cells.  One thread takes V consecutive cells -- V == 8 (prev aligned to 8 bytes): 16 bytes of codes, 8 of previous types and 8 of
+// tags per access, the last cells of a grid that is no multiple of 8 one by one; V == 1: cell by cell.  The list is appended by a
+// wave scan and ONE atomic per workgroup and tile (as k_geom_bnd_list); entries beyond `cap` are dropped and the host, which reads
+// the count, grows the list and runs the pass again.
+template <int V>
+__global__ void __launch_bounds__(256) k_fresh_classify(const uint16_t *__restrict__ code, const uint8_t *__restrict__ prev, long long ncell,
+                                                         uint8_t *__restrict__ tag, int *__restrict__ list, long long cap, unsigned *cnt)
+{
+    __shared__ unsigned s_cnt[4];
+    __shared__ unsigned s_first;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const long long ngroup = (ncell + V - 1) / V;
+    for (long long g0 = (long long)blockIdx.x * 256; g0 < ngroup; g0 += (long long)gridDim.x * 256) {      // workgroup-uniform
+        const long long l0 = (g0 + threadIdx.x) * V;
+        unsigned fresh = 0;                                 // bit q: cell l0 + q is fresh
+        if (V == 8 && l0 + 8 <= ncell) {
+            const FreshU2 t = fresh_types8(code, l0), p = *(const FreshU2 *)(prev + l0);
+            FreshU2 tg = {0u, 0u};
+#pragma unroll
+            for (int q = 0; q < 8; q++) {
+                const unsigned t0 = (t[q >> 2] >> (8 * (q & 3))) & 0xFFu, p0 = (p[q >> 2] >> (8 * (q & 3))) & 0xFFu;
+                const unsigned v = t0 != FS3D_NODE_IN ? FRESH_OTHER : (p0 == FS3D_NODE_IN ? 0u : FRESH_UNFILLED);
+                tg[q >> 2] |= v << (8 * (q & 3));
+                fresh |= (unsigned)(v == FRESH_UNFILLED) << q;
+            }
+            *(FreshU2 *)(tag + l0) = tg;
+        } else {
+            for (int q = 0; q < V && l0 + q < ncell; q++) {
+                const int t0 = (code[l0 + q] >> CODE_TYPE_SHIFT) & 3, p0 = prev[l0 + q];
+                const unsigned v = t0 != FS3D_NODE_IN ? FRESH_OTHER : (p0 == FS3D_NODE_IN ? 0u : FRESH_UNFILLED);
+                tag[l0 + q] = (uint8_t)v;
+                fresh |= (unsigned)(v == FRESH_UNFILLED) << q;
+            }
+        }
+        const unsigned mine = __popc(fresh);
+        unsigned incl = mine;                               // inclusive scan over the wave
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const unsigned up = __shfl_up(incl, off, 64);
+            if (lane >= off) incl += up;
+        }
+        if (lane == 63) s_cnt[w] = incl;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            const unsigned all = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+            s_first = all ? atomicAdd(&cnt[FC_FRESH], all) : 0u;
+        }
+        __syncthreads();
+        long long pos = (long long)s_first + (incl - mine);
+        for (int ww = 0; ww < w; ww++) pos += s_cnt[ww];
+#pragma unroll
+        for (int q = 0; q < V; q++)
+            if ((fresh >> q) & 1u) {
+                if (pos < cap) list[pos] = (int)(l0 + q);
+                pos++;
+            }
+        __syncthreads();                                    // s_cnt / s_first are rewritten by the next tile
+    }
+}
+
+// one neighbour of a fresh cell in round `round`: counted iff it lies inside the grid and its tag is below the round
+#define FRESH_TAKE(inside, off)                                                                    \
+    if ((inside) && tag[l + (off)] < round) {                                                      \
+        const long long m = l + (off);                                                             \
+        s0 = n ? s0 + f0[m] : f0[m]; s1 = n ? s1 + f1[m] : f1[m];                                  \
+        s2 = n ? s2 + f2[m] : f2[m]; s3 = n ? s3 + f3[m] : f3[m];                                  \
+        n++;                                                                                       \
+    }
+
+// Round `round` over the list of fresh cells, one thread per entry.  f0 .. f3 address the first OWNED cell of the layer's fields:
+// the halo plane in front of it is never read, a neighbour outside the grid is skipped.  cnt: the cells this round filled.
+template <typename R>
+__global__ void __launch_bounds__(256) k_fresh_round(const int *__restrict__ list, long long nlist, uint8_t *tag, int round, int dimx,
+                                                      int dimy, int dimz, R *f0, R *f1, R *f2, R *f3, unsigned *cnt)
+{
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    bool did = false;
+    if (t < nlist) {
+        const long long l = list[t];
+        if (tag[l] == FRESH_UNFILLED) {
+            const long long plane = (long long)dimy * dimz;
+            const int i = (int)(l / plane), rem = (int)(l - (long long)i * plane), j = rem / dimz, k = rem - j * dimz;
+            int n = 0;
+            R s0 = R(0), s1 = R(0), s2 = R(0), s3 = R(0);
+            FRESH_TAKE(i >= 1, -plane)
+            FRESH_TAKE(i + 1 < dimx, plane)
+            FRESH_TAKE(j >= 1, -(long long)dimz)
+            FRESH_TAKE(j + 1 < dimy, (long long)dimz)
+            FRESH_TAKE(k >= 1, -1LL)
+            FRESH_TAKE(k + 1 < dimz, 1LL)
+            if (n) {
+                const R d = (R)n;
+                f0[l] = s0 / d; f1[l] = s1 / d; f2[l] = s2 / d; f3[l] = s3 / d;
+                tag[l] = (uint8_t)round;
+                did = true;
+            }
+        }
+    }
+    const unsigned long long m = __ballot(did);
+    if ((threadIdx.x & 63) == 0 && m) atomicAdd(cnt, (unsigned)__popcll(m));
+}
+
 // ---------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------
@@ -972,6 +1114,16 @@ static fs3d_status gev_sync(fs3d_ctx *c)
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return FS3D_OK;
 }
+// the device time gathered since gev_reset, for a caller that is no update (fs3d_last_update_device_ms keeps its value)
+static float gev_take(fs3d_ctx *c)
+{
+    fs3d_geom &g = c->geom;
+    gev_end(c);
+    gev_fold(g);
+    const float ms = g.ev_ms;
+    g.ev_ms = 0;
+    return ms;
+}
 
 void fs3d_geom_destroy(fs3d_ctx *c)
 {
@@ -994,6 +1146,11 @@ void fs3d_geom_destroy(fs3d_ctx *c)
     if (g.mesh_idx) hipFree(g.mesh_idx);
     if (g.mesh_cnt) hipFree(g.mesh_cnt);
     if (g.mesh_owner) hipFree(g.mesh_owner);
+    if (g.prev_type) hipFree(g.prev_type);
+    if (g.fill_tag) hipFree(g.fill_tag);
+    if (g.fill_list) hipFree(g.fill_list);
+    if (g.fill_cnt) hipFree(g.fill_cnt);
+    if (g.fill_host) hipHostFree(g.fill_host);
 }
 
 // cells of the global grid: the byte arrays of an update cover them (a single context: its own cells)
@@ -1437,6 +1594,25 @@ static fs3d_status geom_refuse(fs3d_ctx *c, const char *name, bool any_null, con
     return FS3D_OK;
 }
 
+// FS3D_OPT_FRESH_CELLS: the node types of the code table into the snapshot, before the update that called rewrites the table.
+// *taken: the context had a geometry to take them from (after a failed update it has none).  Its device time is kept apart from
+// the update's and counted with the fill that reads the snapshot (fs3d_last_fill_device_ms).
+static fs3d_status fresh_snapshot(fs3d_ctx *c, bool *taken)
+{
+    fs3d_geom &g = c->geom;
+    *taken = false;
+    g.prev_valid = false; g.snap_ms = 0;
+    if (!g.prev_type) GMALLOC(c, &g.prev_type, (size_t)c->ncell);
+    if (!c->have_nodes) return FS3D_OK;
+    gev_reset(c);
+    gev_begin(c);
+    hipLaunchKernelGGL(k_fresh_snapshot, dim3(grid_for((c->ncell + 7) / 8, 1 << 30)), dim3(256), 0, c->stream, c->code, c->ncell, g.prev_type);
+    HIPCHK(c, hipGetLastError());
+    g.snap_ms = gev_take(c);
+    *taken = true;
+    return FS3D_OK;
+}
+
 // ---- fs3d_update_nodes*: one update ---------------------------------------------------------------------------------------------
 typedef std::chrono::steady_clock::time_point geom_clock;
 
@@ -1480,10 +1656,15 @@ static fs3d_status update_run(fs3d_ctx *c, const char *name, bool slab, bool any
     const geom_clock t0 = std::chrono::steady_clock::now();
     HIPCHK(c, hipSetDevice(c->device));
     GTRY(check());
+    // FS3D_OPT_FRESH_CELLS, single context: the types of the geometry about to be replaced (from here on the tables are rewritten)
+    bool snapshot = false;
+    if (c->opt_fresh_cells && !geom_is_slab(c)) GTRY(fresh_snapshot(c, &snapshot));
     GTRY(update_begin(c, need_stage));
     NodeArrays a = geom_own_arrays(c);
     const fs3d_status st = produce(a);
-    return update_end(c, t0, st, a.type, a.bc_vel, a.bc_temp, n_seg_out, name, slab);
+    const fs3d_status done = update_end(c, t0, st, a.type, a.bc_vel, a.bc_temp, n_seg_out, name, slab);
+    c->geom.prev_valid = snapshot && done == FS3D_OK;
+    return done;
 }
 
 // Source 1, the node arrays of the global grid (a single context: its own), on the host or (dev) on the context's device.
@@ -1654,6 +1835,104 @@ extern "C" fs3d_status fs3d_last_update_device_ms(fs3d_ctx *c, float *ms_out)
 {
     if (!c || !ms_out) return FS3D_ERR_INVALID;
     *ms_out = c->geom.last_dev_ms;
+    return FS3D_OK;
+}
+
+// ---- fresh cells --------------------------------------------------------------------------------------------------------------
+// The fill of one layer from the previous types `prev` (device), on the context's stream; returns synchronised.  Batches of the
+// device time as in mesh_fill: the classify pass up to the look at its count, then FRESH_BATCH rounds per look at their counters.
+template <typename R>
+static fs3d_status fresh_fill_impl(fs3d_ctx *c, const uint8_t *prev, int layer, int max_rounds, long long info[4])
+{
+    fs3d_geom &g = c->geom;
+    const long long ncell = c->ncell;
+    if (!g.fill_tag) GMALLOC(c, &g.fill_tag, (size_t)ncell);
+    if (!g.fill_cnt) GMALLOC(c, &g.fill_cnt, FC_WORDS * sizeof(unsigned));
+    if (!g.fill_host) HIPCHK(c, hipHostMalloc((void **)&g.fill_host, FC_WORDS * sizeof(unsigned), hipHostMallocDefault));
+    if (!g.fill_list) {                                     // the fresh cells are a thin shell: an eighth of the grid to begin with
+        const long long cap = std::min<long long>(ncell, ncell / 8 + 1024);
+        GMALLOC(c, &g.fill_list, sizeof(int) * (size_t)cap);
+        g.fill_cap = cap;
+    }
+    R *f[4];
+    for (int v = 0; v < 4; v++) f[v] = (R *)((char *)c->lay[c->slot[layer]] + ((size_t)v * c->fstride + c->plane) * c->esize);
+    const bool vec = ((uintptr_t)prev & 7) == 0;
+    long long fresh = 0;
+    for (;;) {
+        gev_begin(c);
+        HIPCHK(c, hipMemsetAsync(g.fill_cnt, 0, FC_WORDS * sizeof(unsigned), c->stream));
+        hipLaunchKernelGGL(vec ? k_fresh_classify<8> : k_fresh_classify<1>, dim3(grid_for(vec ? (ncell + 7) / 8 : ncell)), dim3(256), 0, c->stream,
+                           c->code, prev, ncell, g.fill_tag, g.fill_list, g.fill_cap, g.fill_cnt);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(g.fill_host, g.fill_cnt, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+        GTRY(gev_sync(c));
+        fresh = (long long)g.fill_host[FC_FRESH];
+        if (fresh <= g.fill_cap) break;
+        gfree(c, g.fill_list); g.fill_list = nullptr; g.fill_cap = 0;      // grow-only, with headroom: the shell of a moving wall breathes
+        const long long cap = std::min<long long>(ncell, fresh + fresh / 4 + 1024);
+        GMALLOC(c, &g.fill_list, sizeof(int) * (size_t)cap);
+        g.fill_cap = cap;
+    }
+    const int limit = max_rounds ? max_rounds : FRESH_MAX_ROUNDS;
+    long long filled = 0;
+    int rounds = 0;
+    bool done = fresh == 0;
+    for (int r = 1; !done && r <= limit; r += FRESH_BATCH) {
+        const int nb = std::min(FRESH_BATCH, limit - r + 1);
+        gev_begin(c);
+        for (int q = 0; q < nb; q++)
+            hipLaunchKernelGGL((k_fresh_round<R>), dim3(grid_for(fresh, 1 << 30)), dim3(256), 0, c->stream, g.fill_list, fresh, g.fill_tag, r + q,
+                               c->dimx, c->dimy, c->dimz, f[0], f[1], f[2], f[3], g.fill_cnt + r + q);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(g.fill_host + r, g.fill_cnt + r, nb * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+        GTRY(gev_sync(c));
+        for (int q = 0; q < nb && !done; q++) {             // a round that fills nothing ends the fill; so does the last fresh cell
+            const long long n = (long long)g.fill_host[r + q];
+            if (!n) { done = true; break; }
+            rounds++; filled += n;
+            done = filled == fresh;
+        }
+    }
+    info[0] = fresh; info[1] = filled; info[2] = rounds; info[3] = fresh - filled;
+    return FS3D_OK;
+}
+
+// own: the plain entry, which reads the snapshot the context keeps; else `prev` is the caller's
+static fs3d_status fresh_fill(fs3d_ctx *c, const char *name, bool own, const uint8_t *prev, int layer, int max_rounds, long long info[4])
+{
+    GTRY(geom_refuse(c, name, (!own && !prev) || !info, "the fresh-cell fill is"));
+    if (layer < 0 || layer > 3) return fail(c, FS3D_ERR_INVALID, std::string(name) + ": bad layer id");
+    if (max_rounds < 0 || max_rounds > FRESH_MAX_ROUNDS) return fail(c, FS3D_ERR_INVALID, std::string(name) + ": max_rounds is 0 .. 250 (0: 250)");
+    if (!c->have_nodes) return fail(c, FS3D_ERR_INVALID, std::string(name) + ": upload nodes first");
+    if (own) {
+        if (!c->opt_fresh_cells) return fail(c, FS3D_ERR_INVALID, std::string(name) + ": FS3D_OPT_FRESH_CELLS is off: no update keeps the previous node types");
+        if (!c->geom.prev_valid || !c->geom.prev_type)
+            return fail(c, FS3D_ERR_INVALID, std::string(name) + ": no previous geometry: no fs3d_update_nodes* has succeeded (with FS3D_OPT_FRESH_CELLS on, "
+                         "on a context that had a geometry) since the last fs3d_upload_nodes");
+        prev = c->geom.prev_type;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    gev_reset(c);
+    const fs3d_status st = BY_PREC(c, fresh_fill_impl, c, prev, layer, max_rounds, info);
+    if (st) { hipStreamSynchronize(c->stream); gev_reset(c); return st; }
+    c->geom.last_fill_ms = gev_take(c) + (own ? c->geom.snap_ms : 0.0f);
+    return FS3D_OK;
+}
+
+extern "C" fs3d_status fs3d_fill_fresh_cells_dev(fs3d_ctx *c, const uint8_t *prev_type_dev, int layer, int max_rounds, long long info[4])
+{
+    return fresh_fill(c, "fs3d_fill_fresh_cells_dev", false, prev_type_dev, layer, max_rounds, info);
+}
+
+extern "C" fs3d_status fs3d_fill_fresh_cells(fs3d_ctx *c, int layer, int max_rounds, long long info[4])
+{
+    return fresh_fill(c, "fs3d_fill_fresh_cells", true, nullptr, layer, max_rounds, info);
+}
+
+extern "C" fs3d_status fs3d_last_fill_device_ms(fs3d_ctx *c, float *ms_out)
+{
+    if (!c || !ms_out) return FS3D_ERR_INVALID;
+    *ms_out = c->geom.last_fill_ms;
     return FS3D_OK;
 }
 

@@ -1,5 +1,5 @@
 // Command-line driver: the reference's FluidSolver3D main (FluidSolver3D/FluidSolver3D.cpp:60-330) on top of
-// libfs3d_hip.so.   fs3d_run <input data> <output prefix> <config> [align] [GPU [n]] [double] [moving [--host-extrusion] [--time-geometry]] [moving-mesh [--host-voxels | --slab-voxels] [--time-geometry] [--time-both]] [--time-output] [--steps N] [--same-device] [--grid-only FILE [--grid-time T]] [--watertight [--wall-velocity motion|file]] [--wall-temperature T]
+// libfs3d_hip.so.   fs3d_run <input data> <output prefix> <config> [align] [GPU [n]] [double] [moving [--host-extrusion] [--time-geometry]] [moving-mesh [--host-voxels | --slab-voxels] [--time-geometry] [--time-both]] [--time-output] [--steps N] [--same-device] [--grid-only FILE [--grid-time T]] [--watertight [--wall-velocity motion|file]] [--wall-temperature T] [--fresh-cells]
 //   * reads the config (host/Config.h) and a Shape2D, Shape3D or SeaNetCDF geometry (host/Shape2D.h, Shape3D.h, SeaNetCDF.h), prints the grid summary lines
 //     the reference prints ("Grid = X x Y x Z", "NODE_IN points = ..."),
 //   * runs the same loop: dt = cycle length / (frames * time_steps), UpdateBoundaries + TimeStep per step with the
@@ -35,6 +35,12 @@
 //   --time-both: a measurement run -- every step makes the geometry through BOTH paths, the word's own last (same tables either way),
 //   and one more line gives, per call after 3 warm-up steps, median (min - max) of the host clock around each path, the device
 //   time of the device path (fs3d_last_update_device_ms), and the host clock around UpdateBoundaries + TimeStep, synchronised.
+// --fresh-cells (with moving or moving-mesh, one GPU): directly after every geometry update and before UpdateBoundaries, the cells of
+//   `cur` that the update turned NODE_IN take the mean of their fluid neighbours (FS3D_OPT_FRESH_CELLS, FillFreshCells;
+//   include/fs3d_fresh_cells.h) instead of starting from the values of the wall or the outside they were.  Either way of making the
+//   geometry (device, --host-extrusion / --host-voxels) goes through an update entry, so both work, with the same results.  One
+//   more line after the timing table: "Fresh cells: <fresh> in <updates> updates, <filled> filled, at most <rounds> rounds".
+//   Refused with GPU n (a slab would need its neighbour's plane), with --time-both (two updates per step) and without a moving word.
 // --time-output: one closing line, the host clock per output record around the GetLayer call (GPU n: rank 0's call and the barrier that
 //   completes the record) and around AppendLayer, with the number of records.
 // There is no CPU backend here: without a GPU the run stops with the library's error.
@@ -78,7 +84,7 @@ struct RunOptions {
     bool moving = false, host_extrusion = false, moving_mesh = false, host_voxels = false, slab_voxels = false, time_geometry = false, time_both = false, time_output = false;
     double grid_time = -1, wall_T = 0;
     int wall_velocity = 0;                             // 0: walls at rest; 1: motion; 2: file (Shape3D::wall_velocity)
-    bool has_wall_T = false;
+    bool has_wall_T = false, fresh_cells = false;
     int nslabs = 1, device = 0;
     long max_steps = -1;
     std::string grid_only;
@@ -116,6 +122,9 @@ static int run(const std::string &data, const std::string &prefix, const fs3d::C
     if (o.has_wall_T && o.moving_mesh && !o.watertight) throw std::runtime_error("--wall-temperature: a moving-mesh run needs --watertight for it (the wall temperature travels with fs3d_update_nodes_shape3d_vel)");
     const bool walls = o.wall_velocity || o.has_wall_T;    // the mesh updates go through the entries that take velocities and a wall temperature
     if (walls && o.time_both) throw std::runtime_error("--time-both: not together with --wall-velocity or --wall-temperature");
+    if (o.fresh_cells && !o.moving && !o.moving_mesh) throw std::runtime_error("--fresh-cells: only with moving or moving-mesh (cells turn fluid only where the geometry moves)");
+    if (o.fresh_cells && o.nslabs > 1) throw std::runtime_error("--fresh-cells: single GPU only (fs3d_fill_fresh_cells refuses an x-slab: it would need the neighbouring slab's plane)");
+    if (o.fresh_cells && o.time_both) throw std::runtime_error("--fresh-cells: not together with --time-both (it updates the geometry twice per step)");
     if (o.grid_time >= 0 && cfg.in_fmt != "Shape2D" && cfg.in_fmt != "Shape3D") throw std::runtime_error("--grid-time: only in_fmt Shape2D and Shape3D inputs move");
     using namespace fs3d;
     Grid3D<FTYPE> grid;
@@ -165,6 +174,7 @@ static int run(const std::string &data, const std::string &prefix, const fs3d::C
     AdiSolver3D<FTYPE> solver;
     solver.Init(o.device, grid, params);
     if (o.watertight) solver.SetMeshVoxels(1);           // the updates voxelise as the host loader did
+    if (o.fresh_cells) solver.SetFreshCells(true);
     std::printf("Segments: %i %i %i (x, y, z)\n", solver.numSegs[0], solver.numSegs[1], solver.numSegs[2]);
 
     const int frames = geo.frames;                                     // FluidSolver3D.cpp:194-195
@@ -191,6 +201,7 @@ static int run(const std::string &data, const std::string &prefix, const fs3d::C
     std::vector<float> mwx, mwy, mwz;                  // ... and their velocities (zeros without --wall-velocity)
     std::vector<double> ab_host, ab_dev, ab_dev_gpu, ab_step;   // --time-both: per step, ms
     int fill_rounds = 0;
+    long long fresh_sum[2] = {0, 0}, fresh_updates = 0, fresh_rounds = 0;   // --fresh-cells: fresh and filled cells over the run, updates, most rounds of one fill
     double out_ms[2] = {0, 0};                         // --time-output: host clock around GetLayer, AppendLayer
     auto ms_since = [](std::chrono::steady_clock::time_point a) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - a).count(); };
     // the geometry is frame 0's for the whole run: the reference prepares the grid once, before the loop (grid->Prepare(0), :226;
@@ -223,6 +234,11 @@ static int run(const std::string &data, const std::string &prefix, const fs3d::C
             else if (walls) solver.UpdateGridShape3D(mx, my, mz, mwx, mwy, mwz, sh3.frames[frame].idx, o.wall_T);
             else solver.UpdateGridShape3D(mx, my, mz, sh3.frames[frame].idx);
             const auto g4 = std::chrono::steady_clock::now();
+            if (o.fresh_cells) {                       // the cells this update turned fluid, before UpdateBoundaries
+                long long info[4];
+                solver.FillFreshCells(info);
+                fresh_sum[0] += info[0]; fresh_sum[1] += info[1]; fresh_updates++; fresh_rounds = std::max(fresh_rounds, info[2]);
+            }
             geom_ms[0] += std::chrono::duration<double, std::milli>(g1 - g0).count();
             geom_ms[1] += std::chrono::duration<double, std::milli>(g3 - g1).count();
             geom_ms[2] += std::chrono::duration<double, std::milli>(g4 - g3).count();
@@ -282,6 +298,7 @@ static int run(const std::string &data, const std::string &prefix, const fs3d::C
         fs3d_last_sweep_kernel(solver.ctx(), 0, &kx, &sg); fs3d_last_sweep_kernel(solver.ctx(), 1, &ky, &sg); fs3d_last_sweep_kernel(solver.ctx(), 2, &kz, &sg);
         std::printf("Sweep kernels: X %s, Y %s, Z %s\n", kn[kx & 3], kn[ky & 3], kn[kz & 3]);
     }
+    if (o.fresh_cells) std::printf("Fresh cells: %lld in %lld updates, %lld filled, at most %lld rounds\n", fresh_sum[0], fresh_updates, fresh_sum[1], fresh_rounds);
     if (o.time_geometry && steps > 0)                  // (before the line of --time-both, which only a mesh has)
         std::printf(o.moving ? "Moving geometry per step (host clock, ms): Prepare %.3f, extrusion on the host %.3f, update call %.3f; step %.3f\n"
                              : "Moving mesh per step (host clock, ms): SubFrame %.3f, voxels on the host %.3f, update call %.3f; step %.3f\n",
@@ -445,7 +462,7 @@ static int run_slabs(fs3d::Grid3D<FTYPE> &grid, fs3d::Grid2D &g2, fs3d::Shape3D 
 int main(int argc, char **argv)
 {
     if (argc < 4) {
-        std::printf("Usage: %s <input data> <output prefix> <config file> [align] [GPU [n]] [double] [--steps N] [moving [--host-extrusion] [--time-geometry]] [moving-mesh [--host-voxels | --slab-voxels] [--time-geometry] [--time-both]] [--time-output] [--grid-only FILE [--grid-time T]] [--grid-images] [--watertight [--wall-velocity motion|file]] [--wall-temperature T]\n", argv[0]);
+        std::printf("Usage: %s <input data> <output prefix> <config file> [align] [GPU [n]] [double] [--steps N] [moving [--host-extrusion] [--time-geometry]] [moving-mesh [--host-voxels | --slab-voxels] [--time-geometry] [--time-both]] [--time-output] [--grid-only FILE [--grid-time T]] [--grid-images] [--watertight [--wall-velocity motion|file]] [--wall-temperature T] [--fresh-cells]\n", argv[0]);
         return 0;
     }
     try {
@@ -482,6 +499,7 @@ int main(int argc, char **argv)
                 o.wall_T = std::strtod(argv[++a], &end); o.has_wall_T = true;
                 if (end == argv[a] || *end) throw std::runtime_error("--wall-temperature: not a number");
             }
+            else if (s == "--fresh-cells") o.fresh_cells = true;
             else if (s == "--time-both") o.time_both = true;
             else if (s == "--host-extrusion") o.host_extrusion = true;
             else if (s == "--time-geometry") o.time_geometry = true;

@@ -90,6 +90,10 @@ enum {
     FS3D_OPT_MESH_VOXELS = 8, /* how fs3d_update_nodes_shape3d and fs3d_voxelize_shape3d_dev turn a mesh into NODE_BOUND cells; no effect on
                                  any other entry.  0 (default): the reference's rasteriser, which is not watertight.  1: conservative
                                  voxelisation, closed for every closed mesh (the mesh section below).  Any other value: FS3D_ERR_INVALID */
+    FS3D_OPT_FRESH_CELLS = 9, /* 0 (default): nothing changes anywhere.  1: every successful fs3d_update_nodes* call on a single context first
+                                 copies the node types of the geometry it replaces into a one-byte-per-cell buffer the context keeps (allocated
+                                 by the first such update, counted in fs3d_geometry_info entry 13), which fs3d_fill_fresh_cells reads
+                                 (include/fs3d_fresh_cells.h).  Any other value: FS3D_ERR_INVALID */
     FS3D_OPT_ERR_ORDER = 7    /* summation order of EvalDivError (fs3d_eval_div_error, fs3d_time_step with compute_error).  0 (default): the
                                  per-cell terms are summed in parallel (per workgroup, then over the workgroups; deterministic, equal to the
                                  CPU path to ~1e-12 relative).  1: they are summed one after the other in cell order, as the loop of
@@ -256,13 +260,15 @@ fs3d_status fs3d_shape2d_bottom(int dimx, int dimy, double dz, double depth, dou
 /* Solver3D::ClearOutterCells (Solver3D.cpp:41-44) = TimeLayer3D::Clear(grid, NODE_OUT, 0, 0, 0, (FTYPE)baseT) on one layer:
  * U, V, W := 0 and T := baseT on the NODE_OUT cells of the current geometry, every other cell untouched.  Needed once cells
  * change type: fs3d_get_layer stamps 99999 into the NODE_OUT cells of `next`, and a cell that becomes NODE_IN starts from
- * what its layer holds. */
+ * what its layer holds (unless fs3d_fill_fresh_cells, include/fs3d_fresh_cells.h, gives it the mean of its fluid neighbours). */
 fs3d_status fs3d_clear_outer_cells(fs3d_ctx *ctx, int layer, double baseT);
+/* Fresh cells -- what a cell holds when a wall moves off it and it becomes NODE_IN: FS3D_OPT_FRESH_CELLS above, and the entries that
+ * fill such cells from their fluid neighbours, in include/fs3d_fresh_cells.h (an extension header, as fs3d_mesh_walls.h). */
 /* Summary of the geometry tables, the same after an upload and after an update of the same geometry.  info[0..2] segment
  * counts X, Y, Z; [3] BOUND / VALVE cells; [4] NODE_IN cells on no segment of some direction; [5..7] dead lines X, Y, Z;
  * [8..9] shared-column groups flagged uniform in X, Y; [10..11] distinct shared columns in X, Y; [12] an order-independent
  * 64-bit digest of the cell-code table (sum over cells of a mix of cell index and code), computed on the device from the
- * table the sweeps read; [13] the number of device allocations and frees fs3d_upload_nodes / fs3d_update_nodes* have made
+ * table the sweeps read; [13] the number of device allocations and frees fs3d_upload_nodes / fs3d_update_nodes* / fs3d_fill_fresh_cells* have made
  * since the context was created (the one entry that describes the path taken, not the tables).
  * Measurement and test aid; no reference counterpart. */
 /* Device time of the last fs3d_update_nodes* call: its kernels and copies on the context's stream, summed over HIP event pairs
