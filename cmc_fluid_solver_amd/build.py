@@ -11,9 +11,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libfs3d_hip.so")
 SOURCES = ["fs3d_hip.hip", "fs3d_comm.hip", "kernels_line.hip", "kernels_pipe.hip", "kernels_part.hip", "kernels_geom.hip"]
-HEADERS = ["fs3d_common.h", "fs3d_tables.h", "fs3d_device.h", "fs3d_rows.h", "fs3d_comm.h", os.path.join("..", "..", "include", "fs3d.h"),
-           os.path.join("..", "..", "include", "fs3d_mesh_walls.h"), os.path.join("..", "..", "include", "fs3d_slab_geometry.h"),
-           os.path.join("..", "..", "include", "fs3d_slab_mesh.h"), os.path.join("..", "..", "include", "fs3d_fresh_cells.h")]
+PUBLIC_HEADER = os.path.join(HERE, "..", "include", "fs3d.h")
+HEADERS = ["fs3d_common.h", "fs3d_tables.h", "fs3d_device.h", "fs3d_rows.h", "fs3d_comm.h", PUBLIC_HEADER]
 
 # -ffp-contract=off: no FMA contraction, the reference's CPU path rounds after every operation.
 # -fhip-fp32-correctly-rounded-divide-sqrt: IEEE fp32 division (the hipcc default, stated explicitly).
@@ -60,7 +59,7 @@ DRIVER2D = os.path.join(HERE, "fs2d_run")
 def build_driver2d(force=False):
     """The CPU-only 2D command line (host/fs2d_run.cpp: Stable solver over a Grid2D); g++, no GPU library."""
     host = os.path.join(HERE, "host")
-    deps = [os.path.join(host, f) for f in ("fs2d_run.cpp", "Stable2D.h", "Shape2D.h", "Config.h", "AdiSolver3D_hip.h")]
+    deps = [os.path.join(host, f) for f in ("fs2d_run.cpp", "Stable2D.h", "Shape2D.h", "Config.h", "AdiSolver3D_hip.h")] + [PUBLIC_HEADER]
     if force or _stale(DRIVER2D, deps):
         subprocess.check_call([os.environ.get("CXX", "g++"), "-std=c++17", "-O2", "-Wall", "-ffp-contract=off", "-I" + os.path.join(HERE, "..", "include"),
                                os.path.join(host, "fs2d_run.cpp"), "-o", DRIVER2D])
@@ -71,7 +70,7 @@ def build_driver(force=False, verbose=False):
     """The C++ command-line driver (host/fs3d_run.cpp) above the C ABI; g++, links libfs3d_hip.so."""
     build(force=False, verbose=verbose)
     host = os.path.join(HERE, "host")
-    deps = [os.path.join(host, f) for f in ("fs3d_run.cpp", "AdiSolver3D_hip.h", "Config.h", "Shape2D.h", "Shape3D.h", "SeaNetCDF.h", "Hdf5Min.h", "NetCDF3.h", "GridImage.h")] + [LIB]
+    deps = [os.path.join(host, f) for f in ("fs3d_run.cpp", "AdiSolver3D_hip.h", "Config.h", "Shape2D.h", "Shape3D.h", "SeaNetCDF.h", "Hdf5Min.h", "NetCDF3.h", "GridImage.h")] + [PUBLIC_HEADER, LIB]
     if force or _stale(DRIVER, deps):
         cmd = [os.environ.get("CXX", "g++"), "-std=c++17", "-O2", "-Wall", "-I" + os.path.join(HERE, "..", "include"),
                os.path.join(host, "fs3d_run.cpp"), "-o", DRIVER, "-L" + HERE, "-lfs3d_hip", "-lz", "-Wl,-rpath,$ORIGIN", "-Wl,-rpath,/opt/rocm/lib"]

@@ -27,27 +27,42 @@ MESH_VOXELS = {"reference": 0, "conservative": 1}
 OPT_FRESH_CELLS = 9       # 1: every single-context update_nodes* keeps the node types of the geometry it replaces, for fill_fresh_cells (default 0)
 XSOLVE_AUTO, XSOLVE_PIPELINED, XSOLVE_REDUCED, XSOLVE_REDUCED_A2A = 0, 1, 2, 3
 
-# every symbol include/fs3d.h declares: name -> (restype, argtypes)
+# every function include/fs3d.h declares, in the header's order: name -> (restype, argtypes)
 _vp, _i, _d = C.c_void_p, C.c_int, C.c_double
+_pi, _pll, _pf = C.POINTER(_i), C.POINTER(C.c_longlong), C.POINTER(C.c_float)
+_nodes, _grid2d = [_vp] * 7, [_vp] * 4 + [_d] * 4        # the seven SoA node arrays; cell2d, velx2d, vely2d, T2d, dz, depth, depth_var, baseT
+_mesh, _mesh_vel = [_vp] * 3 + [_i, _vp, _i, _d], [_vp] * 6 + [_i, _vp, _i, _d, _d]     # x, y, z[, wx, wy, wz], nvert, tri, ntri, baseT[, wallT]
+N_EVENTS = 9              # FS3D_N_EVENTS: the length of the three arrays of fs3d_profiler_events
 SYMBOLS = {
     "fs3d_create": (_i, [C.POINTER(_vp), _i, _i, _i, _i, _i, _d, _d, _d, _i, _i]),
     "fs3d_destroy": (None, [_vp]),
     "fs3d_last_error": (C.c_char_p, [_vp]),
     "fs3d_set_params": (_i, [_vp, _d, _d, _d, _d]),
     "fs3d_set_option": (_i, [_vp, _i, _i]),
-    "fs3d_upload_nodes": (_i, [_vp] + [_vp] * 7 + [C.POINTER(_i)]),
-    "fs3d_update_nodes": (_i, [_vp] + [_vp] * 7 + [C.POINTER(_i)]),
-    "fs3d_update_nodes_dev": (_i, [_vp] + [_vp] * 7 + [C.POINTER(_i)]),
-    "fs3d_extrude_shape2d_dev": (_i, [_vp] + [_vp] * 4 + [_d] * 4 + [_vp] * 7),
-    "fs3d_update_nodes_shape2d": (_i, [_vp] + [_vp] * 4 + [_d] * 4 + [C.POINTER(_i)]),
-    "fs3d_update_nodes_shape3d": (_i, [_vp] + [_vp] * 3 + [_i, _vp, _i, _d, C.POINTER(_i)]),
-    "fs3d_voxelize_shape3d_dev": (_i, [_vp] + [_vp] * 3 + [_i, _vp, _i, _d] + [_vp] * 7),
+    "fs3d_upload_nodes": (_i, [_vp] + _nodes + [_pi]),
+    "fs3d_update_nodes": (_i, [_vp] + _nodes + [_pi]),
+    "fs3d_update_nodes_dev": (_i, [_vp] + _nodes + [_pi]),
+    "fs3d_update_nodes_slab": (_i, [_vp] + _nodes + [_pi]),
+    "fs3d_extrude_shape2d_dev": (_i, [_vp] + _grid2d + _nodes),
+    "fs3d_update_nodes_shape2d": (_i, [_vp] + _grid2d + [_pi]),
+    "fs3d_update_nodes_shape2d_slab": (_i, [_vp] + _grid2d + [_pi]),
+    "fs3d_shape2d_bottom": (_i, [_i, _i, _d, _d, _d, _pi]),
+    "fs3d_update_nodes_shape3d": (_i, [_vp] + _mesh + [_pi]),
+    "fs3d_update_nodes_shape3d_vel": (_i, [_vp] + _mesh_vel + [_pi]),
+    "fs3d_update_nodes_shape3d_slab": (_i, [_vp] + _mesh + [_pi]),
+    "fs3d_update_nodes_shape3d_vel_slab": (_i, [_vp] + _mesh_vel + [_pi]),
+    "fs3d_voxelize_shape3d_dev": (_i, [_vp] + _mesh + _nodes),
+    "fs3d_voxelize_shape3d_vel_dev": (_i, [_vp] + _mesh_vel + _nodes),
     "fs3d_flood_fill_dev": (_i, [_vp, _vp]),
-    "fs3d_mesh_fill_rounds": (_i, [_vp, C.POINTER(_i)]),
-    "fs3d_shape2d_bottom": (_i, [_i, _i, _d, _d, _d, C.POINTER(_i)]),
+    "fs3d_flood_fill_global_dev": (_i, [_vp, _vp]),
+    "fs3d_mesh_fill_rounds": (_i, [_vp, _pi]),
+    "fs3d_fill_fresh_cells_dev": (_i, [_vp, _vp, _i, _i, _pll]),
+    "fs3d_fill_fresh_cells": (_i, [_vp, _i, _i, _pll]),
+    "fs3d_last_fill_device_ms": (_i, [_vp, _pf]),
     "fs3d_clear_outer_cells": (_i, [_vp, _i, _d]),
-    "fs3d_geometry_info": (_i, [_vp, C.POINTER(C.c_longlong)]),
-    "fs3d_last_update_device_ms": (_i, [_vp, C.POINTER(C.c_float)]),
+    "fs3d_last_update_device_ms": (_i, [_vp, _pf]),
+    "fs3d_geometry_info": (_i, [_vp, _pll]),
+    "fs3d_geometry_dead_lines": (_i, [_vp, _i, _vp, _pll]),
     "fs3d_init_layers_from_nodes": (_i, [_vp]),
     "fs3d_upload_layer": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
     "fs3d_download_layer": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
@@ -58,11 +73,11 @@ SYMBOLS = {
     "fs3d_synchronize": (_i, [_vp]),
     "fs3d_sweep": (_i, [_vp, _i, _d, _i, _i, _i, _i]),
     "fs3d_merge": (_i, [_vp, _i, _i]),
-    "fs3d_eval_div_error": (_i, [_vp, _i, C.POINTER(_d), C.POINTER(C.c_longlong)]),
+    "fs3d_eval_div_error": (_i, [_vp, _i, C.POINTER(_d), _pll]),
     "fs3d_get_layer": (_i, [_vp, _vp, _vp, _i, _i, _i]),
-    "fs3d_get_layer_rows": (_i, [_vp, _vp, _vp, _i, _i, _i, C.POINTER(_i)]),
-    "fs3d_get_layer_dev": (_i, [_vp, _vp, _vp, _i, _i, _i, C.POINTER(_i)]),
-    "fs3d_get_layer_info": (_i, [_vp, C.POINTER(C.c_longlong)]),
+    "fs3d_get_layer_rows": (_i, [_vp, _vp, _vp, _i, _i, _i, _pi]),
+    "fs3d_get_layer_dev": (_i, [_vp, _vp, _vp, _i, _i, _i, _pi]),
+    "fs3d_get_layer_info": (_i, [_vp, _pll]),
     "fs3d_comm_unique_id": (_i, [_vp]),
     "fs3d_comm_init": (_i, [_vp, _vp, _i, _i]),
     "fs3d_local_group_create": (_i, [_i, C.POINTER(_vp)]),
@@ -71,39 +86,12 @@ SYMBOLS = {
     "fs3d_comm_init_local": (_i, [_vp, _vp, _i]),
     "fs3d_comm_abort": (_i, [_vp]),
     "fs3d_comm_selftest": (_i, [_vp, C.c_size_t]),
-    "fs3d_last_step_timing": (_i, [_vp, C.POINTER(C.c_float), C.POINTER(_i)]),
+    "fs3d_last_step_timing": (_i, [_vp, _pf, _pi]),
+    "fs3d_profiler_events": (_i, [_vp, C.POINTER(C.c_char_p), _pf, _pi]),
     "fs3d_enable_timing": (_i, [_vp, _i]),
-    "fs3d_profiler_events": (_i, [_vp, C.POINTER(C.c_char_p), C.POINTER(C.c_float), C.POINTER(_i)]),
-    "fs3d_profile_sweep": (_i, [_vp, _i, _d, _i, _i, _i, C.POINTER(C.c_ulonglong), _i, C.POINTER(_i)]),
-    "fs3d_last_sweep_kernel": (_i, [_vp, _i, C.POINTER(_i), C.POINTER(_i)]),
+    "fs3d_profile_sweep": (_i, [_vp, _i, _d, _i, _i, _i, C.POINTER(C.c_ulonglong), _i, _pi]),
+    "fs3d_last_sweep_kernel": (_i, [_vp, _i, _pi, _pi]),
     "fs3d_version": (C.c_char_p, []),
-}
-
-# every symbol include/fs3d_mesh_walls.h declares (the extension header of the mesh entries with wall velocities)
-SYMBOLS_MESH_WALLS = {
-    "fs3d_update_nodes_shape3d_vel": (_i, [_vp] + [_vp] * 6 + [_i, _vp, _i, _d, _d, C.POINTER(_i)]),
-    "fs3d_voxelize_shape3d_vel_dev": (_i, [_vp] + [_vp] * 6 + [_i, _vp, _i, _d, _d] + [_vp] * 7),
-}
-
-# every symbol include/fs3d_slab_geometry.h declares (the extension header of moving geometry on x-slabs)
-SYMBOLS_SLAB_GEOMETRY = {
-    "fs3d_update_nodes_slab": (_i, [_vp] + [_vp] * 7 + [C.POINTER(_i)]),
-    "fs3d_update_nodes_shape2d_slab": (_i, [_vp] + [_vp] * 4 + [_d] * 4 + [C.POINTER(_i)]),
-    "fs3d_geometry_dead_lines": (_i, [_vp, _i, _vp, C.POINTER(C.c_longlong)]),
-}
-
-# every symbol include/fs3d_slab_mesh.h declares (the extension header of moving Shape3D meshes on x-slabs)
-SYMBOLS_SLAB_MESH = {
-    "fs3d_update_nodes_shape3d_slab": (_i, [_vp] + [_vp] * 3 + [_i, _vp, _i, _d, C.POINTER(_i)]),
-    "fs3d_update_nodes_shape3d_vel_slab": (_i, [_vp] + [_vp] * 6 + [_i, _vp, _i, _d, _d, C.POINTER(_i)]),
-    "fs3d_flood_fill_global_dev": (_i, [_vp, _vp]),
-}
-
-# every symbol include/fs3d_fresh_cells.h declares (the extension header of the fresh-cell fill)
-SYMBOLS_FRESH_CELLS = {
-    "fs3d_fill_fresh_cells_dev": (_i, [_vp, _vp, _i, _i, C.POINTER(C.c_longlong)]),
-    "fs3d_fill_fresh_cells": (_i, [_vp, _i, _i, C.POINTER(C.c_longlong)]),
-    "fs3d_last_fill_device_ms": (_i, [_vp, C.POINTER(C.c_float)]),
 }
 
 _lib = None
@@ -123,8 +111,7 @@ def load():
             raise RuntimeError("libfs3d_hip.so is not built (%s); run `python -m cmc_fluid_solver_amd.build` "
                                "or __graft_entry__.build()" % LIB_PATH)
         lib = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SYMBOLS.items()) + list(SYMBOLS_MESH_WALLS.items()) + list(SYMBOLS_SLAB_GEOMETRY.items()) + \
-                list(SYMBOLS_SLAB_MESH.items()) + list(SYMBOLS_FRESH_CELLS.items()):
+        for name, (res, args) in SYMBOLS.items():
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
@@ -504,9 +491,9 @@ class Solver:
 
     def profiler_events(self):
         """{event name of the reference's Profiler: (total ms, count)} since enable_timing(True)"""
-        names, ms, n = (C.c_char_p * 9)(), (C.c_float * 9)(), (C.c_int * 9)()
+        names, ms, n = (C.c_char_p * N_EVENTS)(), (C.c_float * N_EVENTS)(), (C.c_int * N_EVENTS)()
         self._chk(self.lib.fs3d_profiler_events(self.h, names, ms, n))
-        return {names[k].decode(): (ms[k], n[k]) for k in range(9)}
+        return {names[k].decode(): (ms[k], n[k]) for k in range(N_EVENTS)}
 
     def enable_timing(self, on=True):
         self._chk(self.lib.fs3d_enable_timing(self.h, int(on)))

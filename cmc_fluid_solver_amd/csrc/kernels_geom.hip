@@ -6,12 +6,12 @@
 // fs3d_update_nodes_shape2d): a moving Shape2D geometry then ships its 2D grid per step, not the 3D node arrays.
 // And the voxelisation of a Shape3D mesh (k_geom_raster_mesh, the flood fill k_geom_fill_z / k_geom_fill_strided, k_geom_mesh_nodes;
 // fs3d_voxelize_shape3d_dev, fs3d_flood_fill_dev, fs3d_update_nodes_shape3d): a moving mesh ships its vertices per step.
-// On an x-slab (fs3d_update_nodes_slab, fs3d_update_nodes_shape2d_slab; include/fs3d_slab_geometry.h) every rank is given the global
+// On an x-slab (fs3d_update_nodes_slab, fs3d_update_nodes_shape2d_slab) every rank is given the global
 // input and rebuilds the tables of its own planes, without communication: the X lines come from the global byte arrays
 // (k_geom_lines_x_slab, k_geom_codes<true>, k_geom_extrude<.., true>), everything else runs on the slab's planes.  A mesh on an x-slab
-// (fs3d_update_nodes_shape3d_slab, fs3d_update_nodes_shape3d_vel_slab; include/fs3d_slab_mesh.h) is voxelised and flood-filled over
+// (fs3d_update_nodes_shape3d_slab, fs3d_update_nodes_shape3d_vel_slab) is voxelised and flood-filled over
 // the GLOBAL grid by every rank, in the staging buffer that holds the global byte arrays anyway: the fill is global.
-// And the fresh cells (k_fresh_classify, k_fresh_round; fs3d_fill_fresh_cells*, include/fs3d_fresh_cells.h): a cell that an update
+// And the fresh cells (k_fresh_classify, k_fresh_round; fs3d_fill_fresh_cells*): a cell that an update
 // turned NODE_IN takes the mean of its fluid neighbours, from the previous node types the caller gives or FS3D_OPT_FRESH_CELLS keeps.
 // Every fs3d_update_nodes* entry is one statement above update_run, the one body of an update: a source (node arrays, a Shape2D
 // grid, a mesh) gives its NULL test, its check and its producer, and a whole-grid context is the slab x_offset = 0, dimx_global = dimx.
@@ -33,9 +33,6 @@
 #include <unordered_map>
 
 #include "fs3d_common.h"
-#include "../../include/fs3d_fresh_cells.h"
-#include "../../include/fs3d_mesh_walls.h"
-#include "../../include/fs3d_slab_geometry.h"
 
 // counter words of one update (device, read back once)
 enum { GC_NSEG = 0 /* 0..2 */, GC_NBND = 3, GC_STALE = 4, GC_SHARED = 5, GC_LIST = 6, GC_MISMATCH = 7, GC_WORDS = 8 };
@@ -1705,7 +1702,7 @@ static fs3d_status update_mesh(fs3d_ctx *c, const char *name, bool slab, const M
                       [&](NodeArrays &a) { return BY_PREC(c, mesh_launch, c, in, new_idx, name, a); }, n_seg_out);
 }
 
-// The entries.  The slab ones (include/fs3d_slab_geometry.h, include/fs3d_slab_mesh.h): every rank is given the global input and
+// The entries.  The slab ones: every rank is given the global input and
 // rebuilds the tables of its own planes on its own stream; no rank talks to another one.
 extern "C" fs3d_status fs3d_update_nodes(fs3d_ctx *c, const uint8_t *type, const uint8_t *bc_vel, const uint8_t *bc_temp,
                                          const void *vx, const void *vy, const void *vz, const void *T, int n_seg_out[3])

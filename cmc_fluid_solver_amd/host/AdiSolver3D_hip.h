@@ -14,9 +14,6 @@
 #include <vector>
 
 #include "../../include/fs3d.h"
-#include "../../include/fs3d_fresh_cells.h"
-#include "../../include/fs3d_mesh_walls.h"
-#include "../../include/fs3d_slab_geometry.h"
 
 namespace fs3d {
 
@@ -142,7 +139,7 @@ public:
     void SetMeshVoxels(int mode) { chk(fs3d_set_option(ctx_, FS3D_OPT_MESH_VOXELS, mode)); }
     // FS3D_OPT_FRESH_CELLS: with it on, every UpdateGrid* call of a single-GPU solver keeps the node types of the geometry it
     // replaces, and FillFreshCells, called directly after the update and before UpdateBoundaries, gives every cell of `cur` that
-    // the update turned NODE_IN the mean of its fluid neighbours (include/fs3d_fresh_cells.h; no reference
+    // the update turned NODE_IN the mean of its fluid neighbours (fs3d_fill_fresh_cells; no reference
     // counterpart).  info: fresh cells, filled, rounds, left unfilled.  Single GPU only: a slab or group member throws.
     void SetFreshCells(bool on) { chk(fs3d_set_option(ctx_, FS3D_OPT_FRESH_CELLS, on ? 1 : 0)); }
     void FillFreshCells(long long info[4]) { chk(fs3d_fill_fresh_cells(ctx_, FS3D_LAYER_CUR, 0, info)); }

@@ -36,8 +36,8 @@
 //   and one more line gives, per call after 3 warm-up steps, median (min - max) of the host clock around each path, the device
 //   time of the device path (fs3d_last_update_device_ms), and the host clock around UpdateBoundaries + TimeStep, synchronised.
 // --fresh-cells (with moving or moving-mesh, one GPU): directly after every geometry update and before UpdateBoundaries, the cells of
-//   `cur` that the update turned NODE_IN take the mean of their fluid neighbours (FS3D_OPT_FRESH_CELLS, FillFreshCells;
-//   include/fs3d_fresh_cells.h) instead of starting from the values of the wall or the outside they were.  Either way of making the
+//   `cur` that the update turned NODE_IN take the mean of their fluid neighbours (FS3D_OPT_FRESH_CELLS, FillFreshCells)
+//   instead of starting from the values of the wall or the outside they were.  Either way of making the
 //   geometry (device, --host-extrusion / --host-voxels) goes through an update entry, so both work, with the same results.  One
 //   more line after the timing table: "Fresh cells: <fresh> in <updates> updates, <filled> filled, at most <rounds> rounds".
 //   Refused with GPU n (a slab would need its neighbour's plane), with --time-both (two updates per step) and without a moving word.

@@ -1,13 +1,11 @@
 """Result output by rows, the parts that need no GPU: slab.out_rows -- the twin of the row range fs3d_get_layer_rows reports --
 against a brute-force count, and the three C-ABI entries exist."""
 import ctypes as C
-import os
-import re
 
+import abi_decls
 from cmc_fluid_solver_amd import capi
 from cmc_fluid_solver_amd.slab import out_rows, slab_range
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("fs3d_get_layer_rows", "fs3d_get_layer_dev", "fs3d_get_layer_info")
 
 
@@ -38,10 +36,9 @@ def test_out_rows_of_the_whole_grid_is_everything():
 
 
 def test_header_declares_and_library_exports_the_get_layer_entries(built):
-    hdr = open(os.path.join(ROOT, "include", "fs3d.h")).read()
     lib = C.CDLL(capi.LIB_PATH)
     for name in NEW:
-        assert re.search(r"fs3d_status\s+%s\s*\(" % name, hdr), name
+        assert abi_decls.declares_status(name), name
         assert name in capi.SYMBOLS and hasattr(lib, name), name
-    assert re.search(r"#define\s+FS3D_N_GETLAYER_INFO\s+3\b", hdr)
+    assert abi_decls.defines()["FS3D_N_GETLAYER_INFO"] == 3
     assert len(capi.Solver.GET_LAYER_INFO) == 3

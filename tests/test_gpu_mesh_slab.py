@@ -1,4 +1,4 @@
-"""Moving Shape3D meshes on x-slabs (include/fs3d_slab_mesh.h): fs3d_update_nodes_shape3d_slab / fs3d_update_nodes_shape3d_vel_slab
+"""Moving Shape3D meshes on x-slabs (include/fs3d.h): fs3d_update_nodes_shape3d_slab / fs3d_update_nodes_shape3d_vel_slab
 voxelise and flood-fill the GLOBAL grid on every rank's own device, without talking to any other rank, and build the tables
 fs3d_upload_nodes builds for the slab's planes from the twin's global nodes.  Everything is held bit for bit: the tables to a fresh
 slab context that uploaded the twin's nodes, the time steps of a group to a single context that took the same meshes through
@@ -330,7 +330,7 @@ def test_scan_line_guard_names_the_slab_entry_and_leaves_no_geometry(built):
     fresh = capi.Solver(nodes, params(np.float32), np.float32, x_range=xr)
     assert_same_context(s, fresh, "restored")
     assert s.profiler_events()["CreateSegments"][1] == n_before + 1
-    # the entries of fs3d.h and fs3d_mesh_walls.h still refuse a slab
+    # the entries without _slab still refuse a slab
     xyz, tri = s._mesh_arrays(g, idx)
     w = s._mesh_velocities(np.zeros_like(g), len(xyz[0]))
     nseg = (C.c_int * 3)()

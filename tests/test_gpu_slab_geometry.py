@@ -1,4 +1,4 @@
-"""Moving geometry on x-slabs (include/fs3d_slab_geometry.h): fs3d_update_nodes_slab / fs3d_update_nodes_shape2d_slab rebuild on
+"""Moving geometry on x-slabs (include/fs3d.h): fs3d_update_nodes_slab / fs3d_update_nodes_shape2d_slab rebuild on
 the device, from the GLOBAL input and without talking to any other rank, the tables fs3d_upload_nodes builds for the slab's
 planes.  So everything is held bit for bit: the tables to a fresh slab context that uploaded the same arrays, the time steps of a
 group to a single context that took the same geometries through fs3d_update_nodes.  No tolerance is introduced; the reported

@@ -1,9 +1,8 @@
-"""Moving Shape3D meshes on x-slabs, the parts that need no GPU: include/fs3d_slab_mesh.h declares exactly what
-capi.SYMBOLS_SLAB_MESH binds and the library exports it, the headers before it keep their function sets, the driver refuses
---slab-voxels where it means nothing, and the cases of tests/mesh_slab_cases.py can show what the GPU tests use them for."""
+"""Moving Shape3D meshes on x-slabs, the parts that need no GPU: include/fs3d.h declares the entries, capi.SYMBOLS binds them
+with their twins' arguments and the library exports them, the driver refuses --slab-voxels where it means nothing, and the cases
+of tests/mesh_slab_cases.py can show what the GPU tests use them for."""
 import ctypes
 import os
-import re
 import subprocess
 import sys
 
@@ -14,46 +13,35 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 if HERE not in sys.path:
     sys.path.insert(0, HERE)
 
+import abi_decls  # noqa: E402
 import mesh_slab_cases as MS  # noqa: E402
 import wall_velocity_cases as WV  # noqa: E402
 from cmc_fluid_solver_amd import build as B  # noqa: E402
 from cmc_fluid_solver_amd import capi, grids  # noqa: E402
 
-ROOT = os.path.dirname(HERE)
 INPUTS = os.path.join(HERE, "golden", "inputs")
 SPHERE = ("sphere_3D_data.txt", "sphere_3D_config.txt")
 ENTRIES = {"fs3d_update_nodes_shape3d_slab", "fs3d_update_nodes_shape3d_vel_slab", "fs3d_flood_fill_global_dev"}
 
 
-def declared(header):
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", header)).read(), flags=re.S)
-    return set(re.findall(r"\b(fs3d_[a-z0-9_]+)\s*\(", text))
-
-
 # ---- the symbols ----------------------------------------------------------------------------------------------------------------------
 
-def test_the_extension_header_declares_what_the_binding_binds():
-    assert declared("fs3d_slab_mesh.h") == set(capi.SYMBOLS_SLAB_MESH) == ENTRIES
-    # whoever includes the header of the slab entries has these too
-    assert re.search(r'^#include "fs3d_slab_mesh.h"', open(os.path.join(ROOT, "include", "fs3d_slab_geometry.h")).read(), flags=re.M)
-
-
-def test_the_headers_before_it_keep_their_function_sets():
-    assert declared("fs3d.h") == set(capi.SYMBOLS)
-    assert declared("fs3d_mesh_walls.h") == set(capi.SYMBOLS_MESH_WALLS)
-    assert declared("fs3d_slab_geometry.h") == set(capi.SYMBOLS_SLAB_GEOMETRY)
-    for other in (capi.SYMBOLS, capi.SYMBOLS_MESH_WALLS, capi.SYMBOLS_SLAB_GEOMETRY):
-        assert not ENTRIES & set(other)
+def test_the_header_declares_and_the_binding_binds_the_entries():
+    for name in sorted(ENTRIES):
+        assert abi_decls.declares_status(name), name
+        assert name in capi.SYMBOLS, name
 
 
 def test_the_library_exports_the_entries_with_their_twins_arguments(built):
     lib = ctypes.CDLL(capi.LIB_PATH)
     for name in sorted(ENTRIES):
         assert hasattr(lib, name), "libfs3d_hip.so does not export %s" % name
-        assert getattr(capi.load(), name).argtypes == capi.SYMBOLS_SLAB_MESH[name][1]
-    assert capi.SYMBOLS_SLAB_MESH["fs3d_update_nodes_shape3d_slab"] == capi.SYMBOLS["fs3d_update_nodes_shape3d"]
-    assert capi.SYMBOLS_SLAB_MESH["fs3d_update_nodes_shape3d_vel_slab"] == capi.SYMBOLS_MESH_WALLS["fs3d_update_nodes_shape3d_vel"]
-    assert capi.SYMBOLS_SLAB_MESH["fs3d_flood_fill_global_dev"] == capi.SYMBOLS["fs3d_flood_fill_dev"]
+        assert getattr(capi.load(), name).argtypes == capi.SYMBOLS[name][1]
+    declared = abi_decls.functions()
+    for entry, twin in (("fs3d_update_nodes_shape3d_slab", "fs3d_update_nodes_shape3d"),
+                        ("fs3d_update_nodes_shape3d_vel_slab", "fs3d_update_nodes_shape3d_vel"),
+                        ("fs3d_flood_fill_global_dev", "fs3d_flood_fill_dev")):
+        assert capi.SYMBOLS[entry] == capi.SYMBOLS[twin] and declared[entry] == declared[twin], entry
 
 
 def test_the_solver_class_has_the_methods():

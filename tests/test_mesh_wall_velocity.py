@@ -3,7 +3,6 @@ painting, its weights against a least-squares projection, the two velocity sourc
 byte for byte (fs3d_run --grid-only) and the physics of a translating sphere on the CPU oracle alone."""
 import ctypes
 import os
-import re
 import subprocess
 import sys
 
@@ -14,6 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 if HERE not in sys.path:
     sys.path.insert(0, HERE)
 
+import abi_decls  # noqa: E402
 import mesh_cases as MC  # noqa: E402
 import wall_velocity_cases as WV  # noqa: E402
 import watertight_cases as W  # noqa: E402
@@ -316,17 +316,13 @@ def test_sphere_3D_with_moving_walls_stays_below_the_error_threshold(built):
     o.close()
 
 
-# ---- the extension header ----------------------------------------------------------------------------------------------------------
+# ---- the declarations --------------------------------------------------------------------------------------------------------------
 
-def test_the_extension_header_the_binding_and_the_library_agree(built):
-    """include/fs3d_mesh_walls.h declares the two entries, capi.SYMBOLS_MESH_WALLS binds exactly those, the library exports them;
-    include/fs3d.h and capi.SYMBOLS do not name them."""
-    root = os.path.dirname(HERE)
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(root, "include", "fs3d_mesh_walls.h")).read(), flags=re.S)
-    declared = set(re.findall(r"\b(fs3d_[a-z0-9_]+)\s*\(", text))
-    assert declared == set(capi.SYMBOLS_MESH_WALLS) == {"fs3d_update_nodes_shape3d_vel", "fs3d_voxelize_shape3d_vel_dev"}
-    assert not declared & set(capi.SYMBOLS)
+def test_the_header_the_binding_and_the_library_agree(built):
+    """include/fs3d.h declares the two entries, capi.SYMBOLS binds them, the library exports them."""
     lib = ctypes.CDLL(capi.LIB_PATH)
-    for name in declared:
+    for name in ("fs3d_update_nodes_shape3d_vel", "fs3d_voxelize_shape3d_vel_dev"):
+        assert abi_decls.declares_status(name), name
         assert hasattr(lib, name), "libfs3d_hip.so does not export %s" % name
-        assert getattr(capi.load(), name).argtypes == capi.SYMBOLS_MESH_WALLS[name][1]
+        assert getattr(capi.load(), name).argtypes == capi.SYMBOLS[name][1]
+        assert callable(getattr(capi.Solver, name[len("fs3d_"):]))

