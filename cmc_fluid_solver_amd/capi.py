@@ -25,6 +25,7 @@ OPT_ERR_ORDER = 7         # 1: EvalDivError sums its terms serially in cell orde
 OPT_MESH_VOXELS = 8       # the two mesh entries: 0 the reference's rasteriser (default), 1 conservative voxelisation (watertight)
 MESH_VOXELS = {"reference": 0, "conservative": 1}
 OPT_FRESH_CELLS = 9       # 1: every single-context update_nodes* keeps the node types of the geometry it replaces, for fill_fresh_cells (default 0)
+OPT_FRESH_CELLS_SLABS = 10  # 1: a slab of a group keeps that snapshot too (the update_nodes*_slab entries) and fill_fresh_cells* run collectively (default 0)
 XSOLVE_AUTO, XSOLVE_PIPELINED, XSOLVE_REDUCED, XSOLVE_REDUCED_A2A = 0, 1, 2, 3
 
 # every function include/fs3d.h declares, in the header's order: name -> (restype, argtypes)
@@ -344,14 +345,16 @@ class Solver:
     def fill_fresh_cells(self, layer, max_rounds=0):
         """fs3d_fill_fresh_cells: the cells of `layer` that the last update_nodes* turned NODE_IN take the mean of their fluid
         neighbours (fresh_cells.fill_fresh_cells is the rule), from the snapshot OPT_FRESH_CELLS keeps.
-        Returns (fresh, filled, rounds, left)."""
+        Returns (fresh, filled, rounds, left).  On a slab of a group with OPT_FRESH_CELLS_SLABS: a collective call, every rank makes
+        it with the same arguments; fresh, filled and left count the slab's own cells, rounds is the group's."""
         info = (C.c_longlong * 4)()
         self._chk(self.lib.fs3d_fill_fresh_cells(self.h, layer, max_rounds, info))
         return tuple(info)
 
     def fill_fresh_cells_dev(self, prev_type, layer, max_rounds=0):
         """The stateless form: prev_type is the node types before the update, on the context's device -- a uint8 torch tensor
-        (contiguous, of the grid's size) or a raw device pointer (int), as update_nodes_dev takes its arrays."""
+        (contiguous, of the grid's size) or a raw device pointer (int), as update_nodes_dev takes its arrays.  On a slab of a group
+        (the collective form): the types of the slab's own planes, as a raw device pointer."""
         info = (C.c_longlong * 4)()
         self._chk(self.lib.fs3d_fill_fresh_cells_dev(self.h, self._dev_ptrs("fill_fresh_cells_dev", [prev_type])[0], layer, max_rounds, info))
         return tuple(info)

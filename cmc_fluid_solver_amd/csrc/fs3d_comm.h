@@ -7,8 +7,16 @@ void fs3d_comm_destroy(fs3d_ctx *c);
 // exchange the boundary x-planes of the first nfields fields of layer buffer `buf`
 // with the slab neighbours (ScalarField3D::syncHalos, TimeLayer3D.h:272-335). No-op for one rank.
 fs3d_status fs3d_comm_halo_exchange(fs3d_ctx *c, int buf, int nfields);
+// The whole halo of one round of the fresh-cell fill (kernels_geom.hip) in ONE grouped exchange: per neighbour the boundary plane of
+// the four fields of layer buffer `buf`, as fs3d_comm_halo_exchange moves them, and one plane of round tags (bytes) each way.  `tag`
+// addresses the first owned plane of a byte array laid out as a field: a ghost plane in front of it and one behind the last.
+// No-op for one rank.
+fs3d_status fs3d_comm_fill_exchange(fs3d_ctx *c, int buf, uint8_t *tag);
 // in-place sum of two doubles on the device over all ranks (TimeLayer3D.h:630-637). No-op for one rank.
 fs3d_status fs3d_comm_allreduce_sum2(fs3d_ctx *c, double *dev2);
+// the same for n doubles.  EvalDivError of a group: every rank holds zeros but for its own planes' partial sums, so each sum has one
+// non-zero term and is exact -- the result is the array a single context of the global grid computes
+fs3d_status fs3d_comm_allreduce_sum(fs3d_ctx *c, double *dev, size_t n);
 // one grouped transfer of elements [l0,l1) of each of `nrows` rows (row pitch `pitch` elements) to/from `peer`
 fs3d_status fs3d_comm_xfer_rows(fs3d_ctx *c, void *dev, int nrows, size_t pitch, long long l0, long long l1, int peer, bool send);
 // all-gather of `count` elements per rank: recv = [rank][count] (send may not alias recv); one grouped exchange

@@ -13,7 +13,9 @@
 #include <mutex>
 #include <vector>
 
-struct XOp { void *ptr; size_t count; int peer; bool send; };
+// count: elements of the context's precision, or (bytes) single bytes -- the round tags of the fresh-cell fill
+struct XOp { void *ptr; size_t count; int peer; bool send; bool bytes = false; };
+static size_t op_bytes(const fs3d_ctx *c, const XOp &o) { return o.bytes ? o.count : o.count * c->esize; }
 
 // ---- in-process transport -------------------------------------------------------------------------------
 struct LocalMsg { const void *ptr; size_t bytes; };
@@ -23,12 +25,12 @@ struct fs3d_local_group {
     std::condition_variable cv;
     std::vector<std::deque<LocalMsg>> box;      // [src * n + dst]
     std::vector<long long> posted, done;        // [src * n + dst]
-    std::vector<double> red;                    // [rank][2]
-    double sum[2][2];
+    std::vector<double> red;                    // [rank][n]: the all-reduce in flight (every rank gives the same n)
+    std::vector<double> sum[2];                 // its result, by the parity of the generation
     int arrived = 0;
     long long gen = 0;
     bool broken = false;
-    explicit fs3d_local_group(int n_) : n(n_), box((size_t)n_ * n_), posted((size_t)n_ * n_, 0), done((size_t)n_ * n_, 0), red((size_t)n_ * 2, 0.0) {}
+    explicit fs3d_local_group(int n_) : n(n_), box((size_t)n_ * n_), posted((size_t)n_ * n_, 0), done((size_t)n_ * n_, 0) {}
 };
 
 extern "C" fs3d_status fs3d_local_group_create(int nranks, void **group_out)
@@ -75,7 +77,7 @@ static fs3d_status local_exec(fs3d_ctx *c, const std::vector<XOp> &ops)
     if (hipSetDevice(c->device) != hipSuccess || hipStreamSynchronize(xs(c)) != hipSuccess) return local_fail(c, "stream sync before send");
     {
         std::lock_guard<std::mutex> lk(g->m);
-        for (const XOp &o : ops) if (o.send) { g->box[(size_t)me * n + o.peer].push_back({o.ptr, o.count * c->esize}); g->posted[(size_t)me * n + o.peer]++; }
+        for (const XOp &o : ops) if (o.send) { g->box[(size_t)me * n + o.peer].push_back({o.ptr, op_bytes(c, o)}); g->posted[(size_t)me * n + o.peer]++; }
     }
     g->cv.notify_all();
     std::vector<int> took(n, 0);
@@ -89,7 +91,7 @@ static fs3d_status local_exec(fs3d_ctx *c, const std::vector<XOp> &ops)
             if (g->broken) { c->err = "in-process transport: a peer failed"; return FS3D_ERR_COMM; }
             msg = q.front(); q.pop_front();
         }
-        if (msg.bytes != o.count * c->esize) return local_fail(c, "send/recv size mismatch");
+        if (msg.bytes != op_bytes(c, o)) return local_fail(c, "send/recv size mismatch");
         if (hipMemcpyAsync(o.ptr, msg.ptr, msg.bytes, hipMemcpyDefault, xs(c)) != hipSuccess) return local_fail(c, "device copy");
         took[o.peer]++;
     }
@@ -109,29 +111,32 @@ static fs3d_status local_exec(fs3d_ctx *c, const std::vector<XOp> &ops)
     return FS3D_OK;
 }
 
-static fs3d_status local_allreduce_sum2(fs3d_ctx *c, double *dev2)
+// in-place sum of n doubles on the device over the ranks, added in rank order from 0.0
+static fs3d_status local_allreduce_sum(fs3d_ctx *c, double *dev, size_t n)
 {
     fs3d_local_group *g = (fs3d_local_group *)c->local;
-    double v[2];
-    if (hipSetDevice(c->device) != hipSuccess || hipMemcpyAsync(v, dev2, sizeof v, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+    std::vector<double> v(n);
+    if (hipSetDevice(c->device) != hipSuccess || hipMemcpyAsync(v.data(), dev, n * sizeof(double), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
         hipStreamSynchronize(c->stream) != hipSuccess) return local_fail(c, "all-reduce read");
     {
         std::unique_lock<std::mutex> lk(g->m);
-        g->red[2 * c->rank] = v[0]; g->red[2 * c->rank + 1] = v[1];
+        if (g->red.size() < (size_t)g->n * n) g->red.resize((size_t)g->n * n);
+        std::copy(v.begin(), v.end(), g->red.begin() + (size_t)c->rank * n);
         const long long my_gen = g->gen;
         if (++g->arrived == g->n) {
-            double s0 = 0, s1 = 0;
-            for (int r = 0; r < g->n; r++) { s0 += g->red[2 * r]; s1 += g->red[2 * r + 1]; }   // rank order
-            g->sum[my_gen & 1][0] = s0; g->sum[my_gen & 1][1] = s1;
+            std::vector<double> &s = g->sum[my_gen & 1];
+            s.assign(n, 0.0);
+            for (int r = 0; r < g->n; r++) for (size_t k = 0; k < n; k++) s[k] += g->red[(size_t)r * n + k];   // rank order
             g->arrived = 0; g->gen++;
             g->cv.notify_all();
         } else {
             g->cv.wait(lk, [&] { return g->gen != my_gen || g->broken; });
             if (g->broken) { c->err = "in-process transport: a peer failed"; return FS3D_ERR_COMM; }
         }
-        v[0] = g->sum[my_gen & 1][0]; v[1] = g->sum[my_gen & 1][1];
+        v = g->sum[my_gen & 1];
     }
-    if (hipMemcpyAsync(dev2, v, sizeof v, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+    if (v.size() != n) return local_fail(c, "all-reduce size mismatch");
+    if (hipMemcpyAsync(dev, v.data(), n * sizeof(double), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
         hipStreamSynchronize(c->stream) != hipSuccess) return local_fail(c, "all-reduce write");
     return FS3D_OK;
 }
@@ -249,20 +254,20 @@ static fs3d_status exec_group(fs3d_ctx *c, const std::vector<XOp> &ops)
     const ncclDataType_t dt = c->prec == FS3D_F32 ? ncclFloat : ncclDouble;
     NCCLCHK(c, ncclGroupStart());
     for (const XOp &o : ops) {
-        const ncclResult_t r = o.send ? ncclSend(o.ptr, o.count, dt, o.peer, (ncclComm_t)c->comm, xs(c))
-                                      : ncclRecv(o.ptr, o.count, dt, o.peer, (ncclComm_t)c->comm, xs(c));
+        const ncclDataType_t t = o.bytes ? ncclUint8 : dt;
+        const ncclResult_t r = o.send ? ncclSend(o.ptr, o.count, t, o.peer, (ncclComm_t)c->comm, xs(c))
+                                      : ncclRecv(o.ptr, o.count, t, o.peer, (ncclComm_t)c->comm, xs(c));
         if (r != ncclSuccess) { ncclGroupEnd(); return cfail(c, o.send ? "ncclSend" : "ncclRecv", r); }     // never leave the group open
     }
     NCCLCHK(c, ncclGroupEnd());
     return FS3D_OK;
 }
 
-fs3d_status fs3d_comm_halo_exchange(fs3d_ctx *c, int buf, int nfields)
+// the boundary planes of the first nfields fields of layer buffer `buf`, to and from either neighbour
+static void halo_ops(fs3d_ctx *c, int buf, int nfields, std::vector<XOp> &ops)
 {
-    if (c->nranks == 1) return FS3D_OK;
     const size_t pl = (size_t)c->plane;
     // layout per field: [ghost lo][dimx owned planes][ghost hi]; one grouped send/recv per neighbour
-    std::vector<XOp> ops;
     for (int v = 0; v < nfields; v++) {
         char *base = (char *)c->lay[buf] + (size_t)v * c->fstride * c->esize;
         char *first = base + pl * c->esize;                       // first owned plane
@@ -272,17 +277,39 @@ fs3d_status fs3d_comm_halo_exchange(fs3d_ctx *c, int buf, int nfields)
         if (c->rank > 0) { ops.push_back({first, pl, c->rank - 1, true}); ops.push_back({glo, pl, c->rank - 1, false}); }
         if (c->rank < c->nranks - 1) { ops.push_back({last, pl, c->rank + 1, true}); ops.push_back({ghi, pl, c->rank + 1, false}); }
     }
+}
+
+fs3d_status fs3d_comm_halo_exchange(fs3d_ctx *c, int buf, int nfields)
+{
+    if (c->nranks == 1) return FS3D_OK;
+    std::vector<XOp> ops;
+    halo_ops(c, buf, nfields, ops);
     return exec_group(c, ops);
 }
 
-fs3d_status fs3d_comm_allreduce_sum2(fs3d_ctx *c, double *dev2)
+fs3d_status fs3d_comm_fill_exchange(fs3d_ctx *c, int buf, uint8_t *tag)
 {
     if (c->nranks == 1) return FS3D_OK;
-    if (c->local) return local_allreduce_sum2(c, dev2);
+    const size_t pl = (size_t)c->plane;
+    std::vector<XOp> ops;
+    halo_ops(c, buf, 4, ops);
+    // the tag array has the fields' layout, one byte per cell: `tag` is its first owned plane
+    uint8_t *last = tag + (size_t)(c->dimx - 1) * pl, *glo = tag - pl, *ghi = tag + (size_t)c->dimx * pl;
+    if (c->rank > 0) { ops.push_back({tag, pl, c->rank - 1, true, true}); ops.push_back({glo, pl, c->rank - 1, false, true}); }
+    if (c->rank < c->nranks - 1) { ops.push_back({last, pl, c->rank + 1, true, true}); ops.push_back({ghi, pl, c->rank + 1, false, true}); }
+    return exec_group(c, ops);
+}
+
+fs3d_status fs3d_comm_allreduce_sum(fs3d_ctx *c, double *dev, size_t n)
+{
+    if (c->nranks == 1) return FS3D_OK;
+    if (c->local) return local_allreduce_sum(c, dev, n);
     if (!c->comm) { c->err = "slab context has no communicator"; return FS3D_ERR_COMM; }
-    NCCLCHK(c, ncclAllReduce(dev2, dev2, 2, ncclDouble, ncclSum, (ncclComm_t)c->comm, c->stream));
+    NCCLCHK(c, ncclAllReduce(dev, dev, n, ncclDouble, ncclSum, (ncclComm_t)c->comm, c->stream));
     return FS3D_OK;
 }
+
+fs3d_status fs3d_comm_allreduce_sum2(fs3d_ctx *c, double *dev2) { return fs3d_comm_allreduce_sum(c, dev2, 2); }
 
 fs3d_status fs3d_comm_xfer_rows(fs3d_ctx *c, void *dev, int nrows, size_t pitch, long long l0, long long l1, int peer, bool send)
 {

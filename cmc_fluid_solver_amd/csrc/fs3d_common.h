@@ -107,9 +107,12 @@ struct fs3d_geom {
     bool prev_valid = false;                // prev_type holds the types of the geometry before the one the tables describe now
     float snap_ms = 0;                      // device time of the copy that made it (counted with the fill that reads it)
     uint8_t *fill_tag = nullptr;
+    long long fill_tag_off = 0;             // bytes from fill_tag to the first owned cell's tag: 0, or on a slab of a group (FS3D_OPT_FRESH_CELLS_SLABS)
+                                            // the ghost plane in front of the owned planes, rounded up to 8
     int *fill_list = nullptr;
     long long fill_cap = 0;                 // entries fill_list holds
     unsigned *fill_cnt = nullptr, *fill_host = nullptr;
+    double *fill_red = nullptr, *fill_red_host = nullptr;   // the collective fill: two counts on their way through fs3d_comm_allreduce_sum2 (device, pinned)
     float last_fill_ms = 0;
 };
 
@@ -169,9 +172,11 @@ struct fs3d_ctx {
     int opt_f64_part = 0;                  // FS3D_OPT_F64_PART
     int opt_mesh_voxels = 0;               // FS3D_OPT_MESH_VOXELS: 0 = the reference's rasteriser, 1 = conservative voxelisation (k_geom_voxel_mesh)
     int opt_fresh_cells = 0;               // FS3D_OPT_FRESH_CELLS: 1 = every single-context update keeps the node types of the geometry it replaces
+    int opt_fresh_slabs = 0;               // FS3D_OPT_FRESH_CELLS_SLABS: 1 = a slab of a group keeps that snapshot too and fills collectively
     int opt_err_order = 0;                 // FS3D_OPT_ERR_ORDER: 1 = EvalDivError sums its per-cell terms serially in cell order (host), as the CPU path
     double *err_terms = nullptr;           // ... one term per cell (device, allocated on first use)
     std::vector<double> err_terms_host;
+    double *err_parts = nullptr;           // a member of a group: EvalDivError's per-workgroup (sum, count) pairs of ALL global planes (device, allocated on first use)
     // options
     int opt_kernel = FS3D_SWEEP_AUTO;
     int ran_kernel[3] = {0, 0, 0};   // per direction: the kernel the last sweep really ran (fs3d_last_sweep_kernel)

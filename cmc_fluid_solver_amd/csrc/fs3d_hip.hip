@@ -111,7 +111,8 @@ __global__ void __launch_bounds__(256) k_get_layer(const R *__restrict__ U, cons
 // accumulation.  Wave64 shuffle reduction, one partial (sum,count) pair per block;
 // the partials are summed in a fixed order by k_div_final, so the result is
 // run-to-run deterministic (it is NOT the reference's serial summation order: compare
-// with a relative tolerance of ~1e-12).
+// with a relative tolerance of ~1e-12).  A group of x-slabs gathers the partials of all global planes and sums them in
+// that same order (div_error_enqueue): its error equals the single context's bit for bit where the fields do.
 // (r3) One block = one plane i x DIVE_JS rows j x all k: a thread walks its k column down the rows, keeping row j-1 in
 // registers and taking the k-1 values from the lane next door, so every U/V/W value is fetched once per plane pair (6 loads
 // per cell instead of 24 through the caches; no integer divisions).  The per-cell expression is the reference's, term for term.
@@ -376,6 +377,7 @@ extern "C" void fs3d_destroy(fs3d_ctx *c)
     if (c->bnd_idx) hipFree(c->bnd_idx);
     fs3d_geom_destroy(c);
     if (c->err_terms) hipFree(c->err_terms);
+    if (c->err_parts) hipFree(c->err_parts);
     if (c->red_buf) hipFree(c->red_buf);
     if (c->gl_stage) hipFree(c->gl_stage);
     if (c->stamps) hipFree(c->stamps);
@@ -415,6 +417,9 @@ extern "C" fs3d_status fs3d_set_option(fs3d_ctx *c, int option, int value)
     case FS3D_OPT_FRESH_CELLS:
         if (value != 0 && value != 1) return fail(c, FS3D_ERR_INVALID, "bad fresh-cells value (0: off, 1: the updates keep the node types of the geometry they replace)");
         c->opt_fresh_cells = value; return FS3D_OK;
+    case FS3D_OPT_FRESH_CELLS_SLABS:
+        if (value != 0 && value != 1) return fail(c, FS3D_ERR_INVALID, "bad fresh-cells-on-slabs value (0: off, 1: a slab of a group keeps the snapshot and fills with its neighbours)");
+        c->opt_fresh_slabs = value; return FS3D_OK;
     case FS3D_OPT_XSOLVE:
         if (value < 0 || value > 3) return fail(c, FS3D_ERR_INVALID, "bad cross-slab X solve id");
         c->opt_xsolve = value; return FS3D_OK;
@@ -972,12 +977,20 @@ static fs3d_status div_error_enqueue(fs3d_ctx *c, int layer)
             return fail(c, FS3D_ERR_UNSUPPORTED, "FS3D_OPT_ERR_ORDER = 1 (the CPU path's summation order) is implemented for a single context only");
         if (!c->err_terms) HIPCHK(c, hipMalloc((void **)&c->err_terms, (size_t)c->ncell * sizeof(double)));
     }
+    // A group sums what a single context of the global grid sums, in its order: every rank writes the partial sums of its own
+    // planes into their place in an array over the GLOBAL planes that is zero elsewhere, the arrays are added over the ranks
+    // (div_error_finish: one non-zero term per sum, so exact), and k_div_final runs over the global array on every rank.
+    const int nj = (c->dimy + DIVE_JS - 1) / DIVE_JS;
+    const bool group = c->nranks > 1;
+    const size_t gwords = (size_t)2 * c->dimx_global * nj;
+    if (group && !c->err_parts) HIPCHK(c, hipMalloc((void **)&c->err_parts, gwords * sizeof(double)));
     RecScope rec(c, 5);
+    if (group) HIPCHK(c, hipMemsetAsync(c->err_parts, 0, gwords * sizeof(double), c->stream));
     hipLaunchKernelGGL((k_div_error<R>), dim3(c->red_blocks), dim3(256), 0, c->stream, c->code,
                        (const R *)fld<R>(c, b, 0), (const R *)fld<R>(c, b, 1), (const R *)fld<R>(c, b, 2),
-                       c->dimx, c->dimy, c->dimz, i_end, c->x_offset == 0 ? 1 : 0, (R)c->gdx, (R)c->gdy, (R)c->gdz, c->red_buf + 2,
-                       (c->dimy + DIVE_JS - 1) / DIVE_JS);
-    hipLaunchKernelGGL(k_div_final, dim3(1), dim3(256), 0, c->stream, c->red_buf + 2, c->red_blocks, c->red_buf);
+                       c->dimx, c->dimy, c->dimz, i_end, c->x_offset == 0 ? 1 : 0, (R)c->gdx, (R)c->gdy, (R)c->gdz,
+                       group ? c->err_parts + (size_t)2 * c->x_offset * nj : c->red_buf + 2, nj);
+    if (!group) hipLaunchKernelGGL(k_div_final, dim3(1), dim3(256), 0, c->stream, c->red_buf + 2, c->red_blocks, c->red_buf);
     if (c->opt_err_order) {
         hipLaunchKernelGGL((k_div_terms<R>), dim3(grid_for(c->ncell)), dim3(256), 0, c->stream, c->code,
                            (const R *)fld<R>(c, b, 0), (const R *)fld<R>(c, b, 1), (const R *)fld<R>(c, b, 2),
@@ -989,8 +1002,13 @@ static fs3d_status div_error_enqueue(fs3d_ctx *c, int layer)
 
 static fs3d_status div_error_finish(fs3d_ctx *c, double *err, long long *count)
 {
-    fs3d_status st = fs3d_comm_allreduce_sum2(c, c->red_buf);   // no-op for a single rank
-    if (st) return st;
+    if (c->nranks > 1) {                                        // the partial sums of all global planes, then the single context's final sum
+        const int gblocks = c->dimx_global * ((c->dimy + DIVE_JS - 1) / DIVE_JS);
+        fs3d_status st = fs3d_comm_allreduce_sum(c, c->err_parts, (size_t)2 * gblocks);
+        if (st) return st;
+        hipLaunchKernelGGL(k_div_final, dim3(1), dim3(256), 0, c->stream, c->err_parts, gblocks, c->red_buf);
+        HIPCHK(c, hipGetLastError());
+    }
     HIPCHK(c, hipMemcpyAsync(c->red_host, c->red_buf, 2 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     if (c->opt_err_order) {
         // TimeLayer3D.h:604-628: err += fabs(...) cell after cell; adding the 0.0 of a cell the loop skips changes nothing

@@ -13,6 +13,8 @@
 // the GLOBAL grid by every rank, in the staging buffer that holds the global byte arrays anyway: the fill is global.
 // And the fresh cells (k_fresh_classify, k_fresh_round; fs3d_fill_fresh_cells*): a cell that an update
 // turned NODE_IN takes the mean of its fluid neighbours, from the previous node types the caller gives or FS3D_OPT_FRESH_CELLS keeps.
+// On the slabs of a group (FS3D_OPT_FRESH_CELLS_SLABS) that fill is the one place here where ranks talk: a plane of fields and of
+// round tags per neighbour and round, and the counts summed over the ranks (fresh_fill_impl).
 // Every fs3d_update_nodes* entry is one statement above update_run, the one body of an update: a source (node arrays, a Shape2D
 // grid, a mesh) gives its NULL test, its check and its producer, and a whole-grid context is the slab x_offset = 0, dimx_global = dimx.
 //
@@ -33,6 +35,7 @@
 #include <unordered_map>
 
 #include "fs3d_common.h"
+#include "fs3d_comm.h"
 
 // counter words of one update (device, read back once)
 enum { GC_NSEG = 0 /* 0..2 */, GC_NBND = 3, GC_STALE = 4, GC_SHARED = 5, GC_LIST = 6, GC_MISMATCH = 7, GC_WORDS = 8 };
@@ -1011,11 +1014,14 @@ __global__ void __launch_bounds__(256) k_fresh_classify(const uint16_t *__restri
         n++;                                                                                       \
     }
 
-// Round `round` over the list of fresh cells, one thread per entry.  f0 .. f3 address the first OWNED cell of the layer's fields:
-// the halo plane in front of it is never read, a neighbour outside the grid is skipped.  cnt: the cells this round filled.
-template <typename R>
+// Round `round` over the list of fresh cells, one thread per entry.  f0 .. f3 address the first OWNED cell of the layer's fields,
+// tag the first owned cell's tag.  SLAB false, a whole grid: the halo plane in front of the fields is never read, a neighbour
+// outside the grid is skipped.  SLAB true, an x-slab of a group: lo / hi say that a neighbouring slab stands before / behind the
+// owned planes; its boundary plane of the fields is in the layer's ghost plane and its tags in the ghost plane of the tag array
+// (fs3d_comm_fill_exchange brought both), and that neighbour counts exactly as an owned one.  cnt: the cells this round filled.
+template <typename R, bool SLAB>
 __global__ void __launch_bounds__(256) k_fresh_round(const int *__restrict__ list, long long nlist, uint8_t *tag, int round, int dimx,
-                                                      int dimy, int dimz, R *f0, R *f1, R *f2, R *f3, unsigned *cnt)
+                                                      int dimy, int dimz, R *f0, R *f1, R *f2, R *f3, unsigned *cnt, int lo, int hi)
 {
     const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
     bool did = false;
@@ -1026,8 +1032,8 @@ __global__ void __launch_bounds__(256) k_fresh_round(const int *__restrict__ lis
             const int i = (int)(l / plane), rem = (int)(l - (long long)i * plane), j = rem / dimz, k = rem - j * dimz;
             int n = 0;
             R s0 = R(0), s1 = R(0), s2 = R(0), s3 = R(0);
-            FRESH_TAKE(i >= 1, -plane)
-            FRESH_TAKE(i + 1 < dimx, plane)
+            FRESH_TAKE(i >= 1 || (SLAB && lo), -plane)
+            FRESH_TAKE(i + 1 < dimx || (SLAB && hi), plane)
             FRESH_TAKE(j >= 1, -(long long)dimz)
             FRESH_TAKE(j + 1 < dimy, (long long)dimz)
             FRESH_TAKE(k >= 1, -1LL)
@@ -1042,6 +1048,12 @@ __global__ void __launch_bounds__(256) k_fresh_round(const int *__restrict__ lis
     }
     const unsigned long long m = __ballot(did);
     if ((threadIdx.x & 63) == 0 && m) atomicAdd(cnt, (unsigned)__popcll(m));
+}
+
+// The collective fill: the counts of n (1 or 2) consecutive counter words as the two doubles fs3d_comm_allreduce_sum2 sums
+__global__ void k_fresh_counts(const unsigned *__restrict__ cnt, int n, double *__restrict__ red)
+{
+    if (threadIdx.x < 2) red[threadIdx.x] = (int)threadIdx.x < n ? (double)cnt[threadIdx.x] : 0.0;
 }
 
 // ---------------------------------------------------------------------------------
@@ -1148,6 +1160,8 @@ void fs3d_geom_destroy(fs3d_ctx *c)
     if (g.fill_list) hipFree(g.fill_list);
     if (g.fill_cnt) hipFree(g.fill_cnt);
     if (g.fill_host) hipHostFree(g.fill_host);
+    if (g.fill_red) hipFree(g.fill_red);
+    if (g.fill_red_host) hipHostFree(g.fill_red_host);
 }
 
 // cells of the global grid: the byte arrays of an update cover them (a single context: its own cells)
@@ -1578,6 +1592,8 @@ static fs3d_status mesh_launch(fs3d_ctx *c, const MeshIn &in, bool new_idx, cons
 }
 
 static bool geom_is_slab(const fs3d_ctx *c) { return c->dimx != c->dimx_global || c->x_offset != 0 || c->comm || c->local || c->nranks > 1; }
+// FS3D_OPT_FRESH_CELLS_SLABS on a member of a group: the slab keeps the snapshot and the fill is the collective one
+static bool fresh_collective(const fs3d_ctx *c) { return c->opt_fresh_slabs && (c->local || c->comm); }
 
 // The refusals every geometry entry begins with, in this order.  slab_what: the entry's own wording of its refusal of a slab
 // ("moving geometry is", ...); null: the entry takes a slab.
@@ -1653,9 +1669,10 @@ static fs3d_status update_run(fs3d_ctx *c, const char *name, bool slab, bool any
     const geom_clock t0 = std::chrono::steady_clock::now();
     HIPCHK(c, hipSetDevice(c->device));
     GTRY(check());
-    // FS3D_OPT_FRESH_CELLS, single context: the types of the geometry about to be replaced (from here on the tables are rewritten)
+    // FS3D_OPT_FRESH_CELLS, a single context or (FS3D_OPT_FRESH_CELLS_SLABS) a slab of a group: the types of the geometry about to be
+    // replaced, of the context's own planes (from here on the tables are rewritten)
     bool snapshot = false;
-    if (c->opt_fresh_cells && !geom_is_slab(c)) GTRY(fresh_snapshot(c, &snapshot));
+    if (c->opt_fresh_cells && (!geom_is_slab(c) || fresh_collective(c))) GTRY(fresh_snapshot(c, &snapshot));
     GTRY(update_begin(c, need_stage));
     NodeArrays a = geom_own_arrays(c);
     const fs3d_status st = produce(a);
@@ -1838,28 +1855,42 @@ extern "C" fs3d_status fs3d_last_update_device_ms(fs3d_ctx *c, float *ms_out)
 // ---- fresh cells --------------------------------------------------------------------------------------------------------------
 // The fill of one layer from the previous types `prev` (device), on the context's stream; returns synchronised.  Batches of the
 // device time as in mesh_fill: the classify pass up to the look at its count, then FRESH_BATCH rounds per look at their counters.
+// One body: a single context is the group of one rank that exchanges nothing and sums nothing.  `coll`, a slab of a group
+// (fresh_collective): the tag array has a ghost plane on either side, as the fields have; before every round one grouped exchange
+// (fs3d_comm_fill_exchange) brings the neighbours' boundary planes of the four fields and of the tags as the round before left them;
+// the count of fresh cells and, per batch, the counts of its rounds are summed over the ranks (fs3d_comm_allreduce_sum2), so every
+// rank sees the same numbers, ends in the same round and makes the same exchanges and sums whatever it holds.  Every wait is the
+// transport's.  The device time is that of the rank's own kernels and copies; the transport's copies and waits are not in it.
 template <typename R>
-static fs3d_status fresh_fill_impl(fs3d_ctx *c, const uint8_t *prev, int layer, int max_rounds, long long info[4])
+static fs3d_status fresh_fill_impl(fs3d_ctx *c, const uint8_t *prev, int layer, int max_rounds, bool coll, long long info[4])
 {
     fs3d_geom &g = c->geom;
     const long long ncell = c->ncell;
-    if (!g.fill_tag) GMALLOC(c, &g.fill_tag, (size_t)ncell);
+    if (!g.fill_tag) {
+        // a slab of a group: [pad][ghost plane][owned planes][ghost plane], the first owned cell aligned to 8 bytes (k_fresh_classify<8>)
+        g.fill_tag_off = coll ? (c->plane + 7) / 8 * 8 : 0;
+        GMALLOC(c, &g.fill_tag, (size_t)(g.fill_tag_off + ncell + (coll ? c->plane : 0)));
+    }
     if (!g.fill_cnt) GMALLOC(c, &g.fill_cnt, FC_WORDS * sizeof(unsigned));
     if (!g.fill_host) HIPCHK(c, hipHostMalloc((void **)&g.fill_host, FC_WORDS * sizeof(unsigned), hipHostMallocDefault));
+    if (coll && !g.fill_red) GMALLOC(c, &g.fill_red, 2 * sizeof(double));
+    if (coll && !g.fill_red_host) HIPCHK(c, hipHostMalloc((void **)&g.fill_red_host, 2 * sizeof(double), hipHostMallocDefault));
     if (!g.fill_list) {                                     // the fresh cells are a thin shell: an eighth of the grid to begin with
         const long long cap = std::min<long long>(ncell, ncell / 8 + 1024);
         GMALLOC(c, &g.fill_list, sizeof(int) * (size_t)cap);
         g.fill_cap = cap;
     }
+    uint8_t *tag = g.fill_tag + g.fill_tag_off;            // the first owned cell's
+    const int buf = c->slot[layer];
     R *f[4];
-    for (int v = 0; v < 4; v++) f[v] = (R *)((char *)c->lay[c->slot[layer]] + ((size_t)v * c->fstride + c->plane) * c->esize);
+    for (int v = 0; v < 4; v++) f[v] = (R *)((char *)c->lay[buf] + ((size_t)v * c->fstride + c->plane) * c->esize);
     const bool vec = ((uintptr_t)prev & 7) == 0;
     long long fresh = 0;
     for (;;) {
         gev_begin(c);
         HIPCHK(c, hipMemsetAsync(g.fill_cnt, 0, FC_WORDS * sizeof(unsigned), c->stream));
         hipLaunchKernelGGL(vec ? k_fresh_classify<8> : k_fresh_classify<1>, dim3(grid_for(vec ? (ncell + 7) / 8 : ncell)), dim3(256), 0, c->stream,
-                           c->code, prev, ncell, g.fill_tag, g.fill_list, g.fill_cap, g.fill_cnt);
+                           c->code, prev, ncell, tag, g.fill_list, g.fill_cap, g.fill_cnt);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipMemcpyAsync(g.fill_host, g.fill_cnt, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
         GTRY(gev_sync(c));
@@ -1870,24 +1901,41 @@ static fs3d_status fresh_fill_impl(fs3d_ctx *c, const uint8_t *prev, int layer, 
         GMALLOC(c, &g.fill_list, sizeof(int) * (size_t)cap);
         g.fill_cap = cap;
     }
+    // the collective fill: the counter words [at, at + n), n <= 2, summed over the ranks into fill_red_host; returns synchronised
+    auto sum_counts = [&](int at, int n) -> fs3d_status {
+        gev_begin(c);
+        hipLaunchKernelGGL(k_fresh_counts, dim3(1), dim3(64), 0, c->stream, g.fill_cnt + at, n, g.fill_red);
+        HIPCHK(c, hipGetLastError());
+        gev_end(c);
+        GTRY(fs3d_comm_allreduce_sum2(c, g.fill_red));
+        HIPCHK(c, hipMemcpyAsync(g.fill_red_host, g.fill_red, 2 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return FS3D_OK;
+    };
+    long long all_fresh = fresh;                            // over the ranks
+    if (coll) { GTRY(sum_counts(FC_FRESH, 1)); all_fresh = (long long)g.fill_red_host[0]; }
+    const auto round_kernel = coll ? k_fresh_round<R, true> : k_fresh_round<R, false>;
+    const int lo = coll && c->rank > 0, hi = coll && c->rank + 1 < c->nranks;
     const int limit = max_rounds ? max_rounds : FRESH_MAX_ROUNDS;
-    long long filled = 0;
+    long long filled = 0, all_filled = 0;
     int rounds = 0;
-    bool done = fresh == 0;
+    bool done = all_fresh == 0;
     for (int r = 1; !done && r <= limit; r += FRESH_BATCH) {
         const int nb = std::min(FRESH_BATCH, limit - r + 1);
-        gev_begin(c);
-        for (int q = 0; q < nb; q++)
-            hipLaunchKernelGGL((k_fresh_round<R>), dim3(grid_for(fresh, 1 << 30)), dim3(256), 0, c->stream, g.fill_list, fresh, g.fill_tag, r + q,
-                               c->dimx, c->dimy, c->dimz, f[0], f[1], f[2], f[3], g.fill_cnt + r + q);
+        for (int q = 0; q < nb; q++) {
+            if (coll) { gev_end(c); GTRY(fs3d_comm_fill_exchange(c, buf, tag)); }      // the state after round r + q - 1
+            gev_begin(c);
+            hipLaunchKernelGGL(round_kernel, dim3(grid_for(fresh, 1 << 30)), dim3(256), 0, c->stream,
+                               g.fill_list, fresh, tag, r + q, c->dimx, c->dimy, c->dimz, f[0], f[1], f[2], f[3], g.fill_cnt + r + q, lo, hi);
+        }
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipMemcpyAsync(g.fill_host + r, g.fill_cnt + r, nb * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
-        GTRY(gev_sync(c));
+        if (coll) { gev_end(c); GTRY(sum_counts(r, nb)); } else GTRY(gev_sync(c));
         for (int q = 0; q < nb && !done; q++) {             // a round that fills nothing ends the fill; so does the last fresh cell
-            const long long n = (long long)g.fill_host[r + q];
-            if (!n) { done = true; break; }
-            rounds++; filled += n;
-            done = filled == fresh;
+            const long long n = (long long)g.fill_host[r + q], all_n = coll ? (long long)g.fill_red_host[q] : n;
+            if (!all_n) { done = true; break; }
+            rounds++; filled += n; all_filled += all_n;
+            done = all_filled == all_fresh;
         }
     }
     info[0] = fresh; info[1] = filled; info[2] = rounds; info[3] = fresh - filled;
@@ -1897,7 +1945,14 @@ static fs3d_status fresh_fill_impl(fs3d_ctx *c, const uint8_t *prev, int layer, 
 // own: the plain entry, which reads the snapshot the context keeps; else `prev` is the caller's
 static fs3d_status fresh_fill(fs3d_ctx *c, const char *name, bool own, const uint8_t *prev, int layer, int max_rounds, long long info[4])
 {
-    GTRY(geom_refuse(c, name, (!own && !prev) || !info, "the fresh-cell fill is"));
+    GTRY(geom_refuse(c, name, (!own && !prev) || !info, nullptr));
+    const bool coll = fresh_collective(c);
+    if (geom_is_slab(c) && !coll) {
+        if (c->opt_fresh_slabs)
+            return fail(c, FS3D_ERR_UNSUPPORTED, std::string(name) + ": FS3D_OPT_FRESH_CELLS_SLABS: a lone x-slab of a larger grid needs its neighbours' "
+                         "planes: make it a member of a group (fs3d_comm_init_local, fs3d_comm_init) first");
+        return geom_refuse(c, name, false, "the fresh-cell fill is");
+    }
     if (layer < 0 || layer > 3) return fail(c, FS3D_ERR_INVALID, std::string(name) + ": bad layer id");
     if (max_rounds < 0 || max_rounds > FRESH_MAX_ROUNDS) return fail(c, FS3D_ERR_INVALID, std::string(name) + ": max_rounds is 0 .. 250 (0: 250)");
     if (!c->have_nodes) return fail(c, FS3D_ERR_INVALID, std::string(name) + ": upload nodes first");
@@ -1908,10 +1963,17 @@ static fs3d_status fresh_fill(fs3d_ctx *c, const char *name, bool own, const uin
                          "on a context that had a geometry) since the last fs3d_upload_nodes");
         prev = c->geom.prev_type;
     }
+    // the tag array of a slab has ghost planes, a single context's has none: one that was allocated in the other form is refused
+    if (c->geom.fill_tag && (c->geom.fill_tag_off != 0) != coll)
+        return fail(c, FS3D_ERR_INVALID, std::string(name) + ": the context has filled fresh cells before it joined its group; join the group before the first fill");
     HIPCHK(c, hipSetDevice(c->device));
     gev_reset(c);
-    const fs3d_status st = BY_PREC(c, fresh_fill_impl, c, prev, layer, max_rounds, info);
-    if (st) { hipStreamSynchronize(c->stream); gev_reset(c); return st; }
+    const fs3d_status st = BY_PREC(c, fresh_fill_impl, c, prev, layer, max_rounds, coll, info);
+    if (st) {                                               // a rank that fails takes the group down: its peers return FS3D_ERR_COMM
+        if (coll) fs3d_comm_abort(c);
+        hipStreamSynchronize(c->stream); gev_reset(c);
+        return st;
+    }
     c->geom.last_fill_ms = gev_take(c) + (own ? c->geom.snap_ms : 0.0f);
     return FS3D_OK;
 }

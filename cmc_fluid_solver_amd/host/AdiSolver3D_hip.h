@@ -140,8 +140,15 @@ public:
     // FS3D_OPT_FRESH_CELLS: with it on, every UpdateGrid* call of a single-GPU solver keeps the node types of the geometry it
     // replaces, and FillFreshCells, called directly after the update and before UpdateBoundaries, gives every cell of `cur` that
     // the update turned NODE_IN the mean of its fluid neighbours (fs3d_fill_fresh_cells; no reference
-    // counterpart).  info: fresh cells, filled, rounds, left unfilled.  Single GPU only: a slab or group member throws.
+    // counterpart).  info: fresh cells, filled, rounds, left unfilled.  A slab of a group throws unless SetFreshCellsSlabs(true) was
+    // called on every slab; a lone slab of a larger grid, in no group, always throws.
     void SetFreshCells(bool on) { chk(fs3d_set_option(ctx_, FS3D_OPT_FRESH_CELLS, on ? 1 : 0)); }
+    // FS3D_OPT_FRESH_CELLS_SLABS, for a solver that has joined a group (JoinLocalGroup, JoinGroup): with SetFreshCells(true) the
+    // UpdateGrid* calls of the slab keep the node types of its own planes, and FillFreshCells becomes a collective call -- every slab
+    // of the group makes it between the same two steps, the slabs exchange a plane of fields and tags per round, and the planes of
+    // every slab end with the bits the single-GPU fill leaves in them.  info then counts the slab's own fresh, filled and unfilled
+    // cells (their sums over the slabs are the single-GPU numbers); the rounds are the group's, the same on every slab.
+    void SetFreshCellsSlabs(bool on) { chk(fs3d_set_option(ctx_, FS3D_OPT_FRESH_CELLS_SLABS, on ? 1 : 0)); }
     void FillFreshCells(long long info[4]) { chk(fs3d_fill_fresh_cells(ctx_, FS3D_LAYER_CUR, 0, info)); }
     // Solver3D::ClearOutterCells (Solver3D.cpp:41-44), on `next` as there and on `cur`: a cell that turns NODE_IN with the next
     // geometry starts from (0, 0, 0, baseT) in both

@@ -1,5 +1,5 @@
 // Command-line driver: the reference's FluidSolver3D main (FluidSolver3D/FluidSolver3D.cpp:60-330) on top of
-// libfs3d_hip.so.   fs3d_run <input data> <output prefix> <config> [align] [GPU [n]] [double] [moving [--host-extrusion] [--time-geometry]] [moving-mesh [--host-voxels | --slab-voxels] [--time-geometry] [--time-both]] [--time-output] [--steps N] [--same-device] [--grid-only FILE [--grid-time T]] [--watertight [--wall-velocity motion|file]] [--wall-temperature T] [--fresh-cells]
+// libfs3d_hip.so.   fs3d_run <input data> <output prefix> <config> [align] [GPU [n]] [double] [moving [--host-extrusion] [--time-geometry]] [moving-mesh [--host-voxels | --slab-voxels] [--time-geometry] [--time-both]] [--time-output] [--steps N] [--same-device] [--grid-only FILE [--grid-time T]] [--watertight [--wall-velocity motion|file]] [--wall-temperature T] [--fresh-cells | --slab-fresh-cells]
 //   * reads the config (host/Config.h) and a Shape2D, Shape3D or SeaNetCDF geometry (host/Shape2D.h, Shape3D.h, SeaNetCDF.h), prints the grid summary lines
 //     the reference prints ("Grid = X x Y x Z", "NODE_IN points = ..."),
 //   * runs the same loop: dt = cycle length / (frames * time_steps), UpdateBoundaries + TimeStep per step with the
@@ -40,7 +40,12 @@
 //   instead of starting from the values of the wall or the outside they were.  Either way of making the
 //   geometry (device, --host-extrusion / --host-voxels) goes through an update entry, so both work, with the same results.  One
 //   more line after the timing table: "Fresh cells: <fresh> in <updates> updates, <filled> filled, at most <rounds> rounds".
-//   Refused with GPU n (a slab would need its neighbour's plane), with --time-both (two updates per step) and without a moving word.
+//   Refused with GPU n (use --slab-fresh-cells), with --time-both (two updates per step) and without a moving word.
+// --slab-fresh-cells: --fresh-cells that also runs with GPU n, wherever this driver moves a geometry on x-slabs (moving --same-device,
+//   moving-mesh --host-voxels, moving-mesh --slab-voxels): every rank sets FS3D_OPT_FRESH_CELLS and FS3D_OPT_FRESH_CELLS_SLABS and
+//   fills directly after its update and before UpdateBoundaries -- a collective call, the slabs exchange a plane of fields and round
+//   tags per round.  The results and the `Fresh cells:` line (sums over the ranks, the group's rounds) equal the single-GPU run's.
+//   With one GPU it is --fresh-cells.
 // --time-output: one closing line, the host clock per output record around the GetLayer call (GPU n: rank 0's call and the barrier that
 //   completes the record) and around AppendLayer, with the number of records.
 // There is no CPU backend here: without a GPU the run stops with the library's error.
@@ -84,7 +89,7 @@ struct RunOptions {
     bool moving = false, host_extrusion = false, moving_mesh = false, host_voxels = false, slab_voxels = false, time_geometry = false, time_both = false, time_output = false;
     double grid_time = -1, wall_T = 0;
     int wall_velocity = 0;                             // 0: walls at rest; 1: motion; 2: file (Shape3D::wall_velocity)
-    bool has_wall_T = false, fresh_cells = false;
+    bool has_wall_T = false, fresh_cells = false, slab_fresh_cells = false;
     int nslabs = 1, device = 0;
     long max_steps = -1;
     std::string grid_only;
@@ -123,7 +128,8 @@ static int run(const std::string &data, const std::string &prefix, const fs3d::C
     const bool walls = o.wall_velocity || o.has_wall_T;    // the mesh updates go through the entries that take velocities and a wall temperature
     if (walls && o.time_both) throw std::runtime_error("--time-both: not together with --wall-velocity or --wall-temperature");
     if (o.fresh_cells && !o.moving && !o.moving_mesh) throw std::runtime_error("--fresh-cells: only with moving or moving-mesh (cells turn fluid only where the geometry moves)");
-    if (o.fresh_cells && o.nslabs > 1) throw std::runtime_error("--fresh-cells: single GPU only (fs3d_fill_fresh_cells refuses an x-slab: it would need the neighbouring slab's plane)");
+    if (o.fresh_cells && o.nslabs > 1 && !o.slab_fresh_cells)
+        throw std::runtime_error("--fresh-cells: single GPU only (with GPU n the fill is a collective call of all slabs: --slab-fresh-cells)");
     if (o.fresh_cells && o.time_both) throw std::runtime_error("--fresh-cells: not together with --time-both (it updates the geometry twice per step)");
     if (o.grid_time >= 0 && cfg.in_fmt != "Shape2D" && cfg.in_fmt != "Shape3D") throw std::runtime_error("--grid-time: only in_fmt Shape2D and Shape3D inputs move");
     using namespace fs3d;
@@ -360,6 +366,9 @@ static int run_slabs(fs3d::Grid3D<FTYPE> &grid, fs3d::Grid2D &g2, fs3d::Shape3D 
     std::vector<float> mx, my, mz, mwx, mwy, mwz;          // --slab-voxels: the sub-frame of the step, written by rank 0 and read by all
     size_t mframe = 0;
     const long max_steps = o.max_steps;
+    // --slab-fresh-cells: every rank's own fresh and filled cells over the run; the updates and the most rounds of one fill (the group's: rank 0 writes them)
+    std::vector<long long> fresh_own(nslabs, 0), filled_own(nslabs, 0);
+    long long fresh_updates = 0, fresh_rounds = 0;
     FluidParams<FTYPE> params = cfg.useNormalizedParams ? FluidParams<FTYPE>(cfg.Re, cfg.Pr, cfg.lambda)
                                                         : FluidParams<FTYPE>(cfg.viscosity, cfg.density, cfg.R_specific, cfg.k, cfg.cv);
     const double length = geo.length, dt = length / (geo.frames * cfg.time_steps), finaltime = length * cfg.cycles;
@@ -388,6 +397,7 @@ static int run_slabs(fs3d::Grid3D<FTYPE> &grid, fs3d::Grid2D &g2, fs3d::Shape3D 
                 solver.Init(same_device ? 0 : r, grid, params, x0, x1);
                 solver.JoinLocalGroup(group, r);
                 if (o.watertight) solver.SetMeshVoxels(1);           // the updates voxelise as the host loader did
+                if (o.fresh_cells) { solver.SetFreshCells(true); solver.SetFreshCellsSlabs(true); }
                 // every rank has uploaded the grid of time 0 before rank 0 writes the next geometry into the same arrays (Init
                 // reads them, and joining the group is no rendezvous)
                 if (moves) bar.wait();
@@ -413,6 +423,12 @@ static int run_slabs(fs3d::Grid3D<FTYPE> &grid, fs3d::Grid2D &g2, fs3d::Shape3D 
                         else if (o.moving) solver.UpdateGridExtruded(g2, cfg.dz, cfg.depth, cfg.depth_var);
                         else if (walls) solver.UpdateGridShape3D(mx, my, mz, mwx, mwy, mwz, sh3.frames[mframe].idx, o.wall_T);
                         else solver.UpdateGridShape3D(mx, my, mz, sh3.frames[mframe].idx);
+                        if (o.fresh_cells) {               // the cells this update turned fluid, all slabs together, before UpdateBoundaries
+                            long long info[4];
+                            solver.FillFreshCells(info);
+                            fresh_own[r] += info[0]; filled_own[r] += info[1];
+                            if (r == 0) { fresh_updates++; fresh_rounds = std::max(fresh_rounds, info[2]); }
+                        }
                     }
                     solver.UpdateBoundaries();
                     solver.TimeStep((FTYPE)dt, cfg.num_global, cfg.num_local, (i % 10 == 0) || (t + dt >= finaltime));
@@ -451,6 +467,11 @@ static int run_slabs(fs3d::Grid3D<FTYPE> &grid, fs3d::Grid2D &g2, fs3d::Shape3D 
     for (auto &e : errs) if (e) std::rethrow_exception(e);
     const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     std::printf("\n");
+    if (o.fresh_cells) {
+        long long fresh = 0, filled = 0;
+        for (int r = 0; r < nslabs; r++) { fresh += fresh_own[r]; filled += filled_own[r]; }
+        std::printf("Fresh cells: %lld in %lld updates, %lld filled, at most %lld rounds\n", fresh, fresh_updates, filled, fresh_rounds);
+    }
     if (time_output && nc.NumRecords() > 0)
         std::printf("Result output per record (host clock, ms): GetLayer %.3f, AppendLayer %.3f; %u records\n", out_ms[0] / nc.NumRecords(),
                     out_ms[1] / nc.NumRecords(), nc.NumRecords());
@@ -462,7 +483,7 @@ static int run_slabs(fs3d::Grid3D<FTYPE> &grid, fs3d::Grid2D &g2, fs3d::Shape3D 
 int main(int argc, char **argv)
 {
     if (argc < 4) {
-        std::printf("Usage: %s <input data> <output prefix> <config file> [align] [GPU [n]] [double] [--steps N] [moving [--host-extrusion] [--time-geometry]] [moving-mesh [--host-voxels | --slab-voxels] [--time-geometry] [--time-both]] [--time-output] [--grid-only FILE [--grid-time T]] [--grid-images] [--watertight [--wall-velocity motion|file]] [--wall-temperature T] [--fresh-cells]\n", argv[0]);
+        std::printf("Usage: %s <input data> <output prefix> <config file> [align] [GPU [n]] [double] [--steps N] [moving [--host-extrusion] [--time-geometry]] [moving-mesh [--host-voxels | --slab-voxels] [--time-geometry] [--time-both]] [--time-output] [--grid-only FILE [--grid-time T]] [--grid-images] [--watertight [--wall-velocity motion|file]] [--wall-temperature T] [--fresh-cells | --slab-fresh-cells]\n", argv[0]);
         return 0;
     }
     try {
@@ -500,6 +521,7 @@ int main(int argc, char **argv)
                 if (end == argv[a] || *end) throw std::runtime_error("--wall-temperature: not a number");
             }
             else if (s == "--fresh-cells") o.fresh_cells = true;
+            else if (s == "--slab-fresh-cells") o.fresh_cells = o.slab_fresh_cells = true;
             else if (s == "--time-both") o.time_both = true;
             else if (s == "--host-extrusion") o.host_extrusion = true;
             else if (s == "--time-geometry") o.time_geometry = true;

@@ -90,11 +90,17 @@ enum {
     FS3D_OPT_MESH_VOXELS = 8, /* how fs3d_update_nodes_shape3d and fs3d_voxelize_shape3d_dev turn a mesh into NODE_BOUND cells; no effect on
                                  any other entry.  0 (default): the reference's rasteriser, which is not watertight.  1: conservative
                                  voxelisation, closed for every closed mesh (the mesh section below).  Any other value: FS3D_ERR_INVALID */
-    FS3D_OPT_FRESH_CELLS = 9, /* 0 (default): nothing changes anywhere.  1: every successful fs3d_update_nodes* call on a single context first
-                                 copies the node types of the geometry it replaces into a one-byte-per-cell buffer the context keeps (allocated
-                                 by the first such update, counted in fs3d_geometry_info entry 13), which fs3d_fill_fresh_cells reads
+    FS3D_OPT_FRESH_CELLS = 9, /* 0 (default): nothing changes anywhere.  1: every successful fs3d_update_nodes* call on a single context
+                                 (on a slab of a group: together with FS3D_OPT_FRESH_CELLS_SLABS) first copies the node types of the
+                                 geometry it replaces into a one-byte-per-cell buffer the context keeps (allocated by the first such update, counted in fs3d_geometry_info entry 13), which fs3d_fill_fresh_cells reads
                                  (the fresh-cell section below).  Any other value: FS3D_ERR_INVALID */
-    FS3D_OPT_ERR_ORDER = 7    /* summation order of EvalDivError (fs3d_eval_div_error, fs3d_time_step with compute_error).  0 (default): the
+    FS3D_OPT_FRESH_CELLS_SLABS = 10, /* 0 (default): nothing changes anywhere -- an x-slab keeps no snapshot and fs3d_fill_fresh_cells* refuses
+                                 it.  1, on an x-slab context that is a member of a group (fs3d_comm_init_local, or fs3d_comm_init with more
+                                 than one rank): while FS3D_OPT_FRESH_CELLS is 1 the four fs3d_update_nodes*_slab entries keep the snapshot
+                                 of the node types of the slab's own planes, under the single context's rules, and fs3d_fill_fresh_cells*
+                                 run their collective form (the fresh-cell section below).  No effect on a single context; a lone slab
+                                 of a larger grid, in no group, is still refused.  Any other value: FS3D_ERR_INVALID */
+    FS3D_OPT_ERR_ORDER = 7   /* summation order of EvalDivError (fs3d_eval_div_error, fs3d_time_step with compute_error).  0 (default): the
                                  per-cell terms are summed in parallel (per workgroup, then over the workgroups; deterministic, equal to the
                                  CPU path to ~1e-12 relative).  1: they are summed one after the other in cell order, as the loop of
                                  TimeLayer3D::EvalDivError (TimeLayer3D.h:604-628) does -- on the bit-exact kernels the reported error then
@@ -369,14 +375,40 @@ fs3d_status fs3d_mesh_fill_rounds(fs3d_ctx *ctx, int *rounds_out);
  * fs3d_fill_fresh_cells reads the snapshot of FS3D_OPT_FRESH_CELLS and returns FS3D_ERR_INVALID without a valid one: the option is
  * off (or was when the last update ran), no update has succeeded since the last fs3d_upload_nodes, or the update before the last
  * one failed and left no geometry to take the types from.
- * Both refuse before any launch, the context unchanged: a NULL argument, a bad layer, a bad max_rounds, no nodes yet --
- * FS3D_ERR_INVALID; an x-slab or group member -- FS3D_ERR_UNSUPPORTED (single context only: a slab would need its neighbour's
- * plane).  Both work on the context's stream and return synchronised.  The round tag of every cell (one byte), the compact list
- * of the fresh cells and the counter words are allocated by the first fill, kept, and only the list grows: counted in
- * fs3d_geometry_info entry 13.  In a time loop the fill of FS3D_LAYER_CUR goes between the update and fs3d_update_boundaries.
+ * Both refuse before any launch and before any word to a peer, the context unchanged: a NULL argument, a bad layer, a bad
+ * max_rounds, no nodes yet -- FS3D_ERR_INVALID; an x-slab or group member while FS3D_OPT_FRESH_CELLS_SLABS is 0 --
+ * FS3D_ERR_UNSUPPORTED (single context only); with that option on, a lone x-slab of a larger grid that is in no group --
+ * FS3D_ERR_UNSUPPORTED (it needs its neighbours).  Both work on the context's stream and return synchronised.  The round tag of
+ * every cell (one byte), the compact list of the fresh cells and the counter words are allocated by the first fill, kept, and
+ * only the list grows: counted in fs3d_geometry_info entry 13.  In a time loop the fill of FS3D_LAYER_CUR goes between the update
+ * and fs3d_update_boundaries.
  * fs3d_last_fill_device_ms: device time of the last fill (as fs3d_last_update_device_ms: while fs3d_enable_timing is on, else 0);
  * for fs3d_fill_fresh_cells it includes the snapshot's copy kernel, which runs inside the update call but is not part of the
- * update's device time. */
+ * update's device time.
+ *
+ * On x-slabs (FS3D_OPT_FRESH_CELLS_SLABS set to 1 on every member of a group): the same two entries, as one COLLECTIVE call.  The
+ * result is that of the rule above on the GLOBAL grid: after the call the planes of `layer` that each slab owns hold, bit for bit,
+ * what the fill of a single context of the global grid leaves in those planes.  A neighbour on the plane before a slab's first
+ * plane, or behind its last, counts exactly as an owned one; only the first slab's i-1 and the last slab's i+1 lie outside the grid.
+ *  - contract: every rank of the group makes the call between the same two time steps, with the same `layer` and the same
+ *    max_rounds (as it makes every fs3d_update_nodes*_slab call).  Every rank then makes the same exchanges and the same sums,
+ *    whatever it holds: a slab without a single fresh cell takes part until the last round.
+ *  - fs3d_fill_fresh_cells reads the slab's own snapshot, kept by the _slab update entries under the rules above;
+ *    prev_type_dev of fs3d_fill_fresh_cells_dev holds the node types of the slab's dimx*dimy*dimz cells.
+ *  - what travels: before every round, in one grouped exchange per rank, the boundary plane of the four fields of `layer` and one
+ *    plane of round tags (a byte per cell) to and from either neighbour; once after the classifying pass and once per two rounds,
+ *    two numbers summed over the ranks.  The ghost planes of `layer` are overwritten (every time step exchanges them again).
+ *  - info[0], [1] and [3] count the rank's OWN cells, and their sums over the ranks are the numbers of the single context; info[2]
+ *    is the number of rounds that filled a cell on ANY rank, the same on every rank and equal to the single context's.
+ *  - a rank that fails inside the call (a HIP error, a transport error) aborts the group's transport as the other collective
+ *    calls do (fs3d_comm_abort): its peers return FS3D_ERR_COMM from the exchange they wait in instead of waiting for ever.  The
+ *    refusals listed above come before the first exchange; a caller that gives the ranks different arguments breaks the contract.
+ *  - allocations: the first fill of a slab brings the tag array with a ghost plane on either side and two doubles for the sums,
+ *    beside the single context's buffers; kept, counted in fs3d_geometry_info entry 13, nothing in steady state.  Set the option
+ *    and join the group before the context's first fill.
+ *  - fs3d_last_fill_device_ms is the device time of the rank's own kernels and copies; the transport's copies and the waits for
+ *    the peers are not in it.
+ *  - not provided: a lone slab; a fill that overlaps its exchange with the cells that have no neighbour across a cut. */
 fs3d_status fs3d_fill_fresh_cells_dev(fs3d_ctx *ctx, const uint8_t *prev_type_dev, int layer, int max_rounds, long long info[4]);
 fs3d_status fs3d_fill_fresh_cells(fs3d_ctx *ctx, int layer, int max_rounds, long long info[4]);
 fs3d_status fs3d_last_fill_device_ms(fs3d_ctx *ctx, float *ms_out);
@@ -448,7 +480,9 @@ fs3d_status fs3d_sweep(fs3d_ctx *ctx, int dir, double dt, int l_cur, int l_temp,
 fs3d_status fs3d_merge(fs3d_ctx *ctx, int l_src, int l_dest);
 /* TimeLayer3D::EvalDivError (TimeLayer3D.h:595-641): mean |div| over NODE_IN cells.
  * count_out (optional) receives the number of cells summed.  In a multi-GPU group the
- * sum and count are all-reduced (the reference's MPI_Reduce+Bcast, :630-637). */
+ * sum and count are all-reduced (the reference's MPI_Reduce+Bcast, :630-637): the per-workgroup sums of all
+ * global planes are gathered and added in the order a single context of the global grid adds them, so every
+ * rank reports what that context would report from the same fields, bit for bit. */
 fs3d_status fs3d_eval_div_error(fs3d_ctx *ctx, int layer, double *err_out, long long *count_out);
 
 /* Solver3D::GetLayer (Solver3D.cpp:21-25): next->Clear(NODE_OUT -> MISSING_VALUE 99999)
