@@ -12,7 +12,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libfs3d_hip.so")
 SOURCES = ["fs3d_hip.hip", "fs3d_comm.hip", "kernels_line.hip", "kernels_pipe.hip", "kernels_part.hip", "kernels_geom.hip"]
 PUBLIC_HEADER = os.path.join(HERE, "..", "include", "fs3d.h")
-HEADERS = ["fs3d_common.h", "fs3d_tables.h", "fs3d_device.h", "fs3d_rows.h", "fs3d_comm.h", PUBLIC_HEADER]
+HEADERS = ["fs3d_common.h", "fs3d_buf.h", "fs3d_tables.h", "fs3d_device.h", "fs3d_rows.h", "fs3d_comm.h", PUBLIC_HEADER]
 
 # -ffp-contract=off: no FMA contraction, the reference's CPU path rounds after every operation.
 # -fhip-fp32-correctly-rounded-divide-sqrt: IEEE fp32 division (the hipcc default, stated explicitly).

@@ -196,7 +196,8 @@ extern "C" fs3d_status fs3d_comm_selftest(fs3d_ctx *c, size_t elems)
     ncclComm_t comm;
     NCCLCHK(c, ncclCommInitRank(&comm, 1, id, 0));
     const size_t bytes = elems * c->esize;
-    char *src = nullptr, *dst = nullptr; double *red = nullptr;
+    DevBuf<char> src, dst;
+    DevBuf<double> red;
     std::vector<unsigned char> pat(bytes), back(bytes);
     for (size_t i = 0; i < bytes; i++) pat[i] = (unsigned char)((i * 2654435761u) >> 13);
     for (size_t i = c->esize - 1; i < bytes; i += c->esize) pat[i] &= 0x3f;          // finite values of either precision
@@ -207,7 +208,7 @@ extern "C" fs3d_status fs3d_comm_selftest(fs3d_ctx *c, size_t elems)
     hipStream_t s2 = nullptr;                      // a second, non-blocking stream like the one the halo planes travel on
     do {
         if (hipStreamCreateWithFlags(&s2, hipStreamNonBlocking) != hipSuccess) { s2 = nullptr; hipfail("stream"); break; }
-        if (hipMalloc((void **)&src, bytes) != hipSuccess || hipMalloc((void **)&dst, bytes) != hipSuccess || hipMalloc((void **)&red, 2 * sizeof(double)) != hipSuccess) { hipfail("hipMalloc"); break; }
+        if (!reserve_all<DevMem>({{&src, bytes}, {&dst, bytes}, {&red, 2 * sizeof(double)}})) { hipfail("hipMalloc"); break; }
         if (hipMemcpy(src, pat.data(), bytes, hipMemcpyHostToDevice) != hipSuccess || hipMemset(dst, 0, bytes) != hipSuccess) { hipfail("upload"); break; }
         // 1. grouped send/recv (the halo-plane shape), own rank as the peer, on the exchange stream
         ncclResult_t r;
@@ -230,9 +231,6 @@ extern "C" fs3d_status fs3d_comm_selftest(fs3d_ctx *c, size_t elems)
         if (hipStreamSynchronize(c->stream) != hipSuccess || hipMemcpy(w, red, sizeof w, hipMemcpyDeviceToHost) != hipSuccess) { hipfail("all-reduce readback"); break; }
         if (w[0] != v[0] || w[1] != v[1]) { c->err = "comm selftest: all-reduce over one rank changed the values"; st = FS3D_ERR_COMM; break; }
     } while (0);
-    if (src) hipFree(src);
-    if (dst) hipFree(dst);
-    if (red) hipFree(red);
     if (s2) hipStreamDestroy(s2);
     if (st == FS3D_OK) ncclCommDestroy(comm); else ncclCommAbort(comm);
     return st;
@@ -242,8 +240,10 @@ void fs3d_comm_destroy(fs3d_ctx *c)
 {
     if (c && c->comm) { ncclCommDestroy((ncclComm_t)c->comm); c->comm = nullptr; }
     if (c) c->local = nullptr;
-    if (c) for (int i = 0; i < 4; i++) if (c->carry[i]) { hipFree(c->carry[i]); c->carry[i] = nullptr; }
-    if (c) for (int i = 0; i < 4; i++) if (c->xa2a[i]) { hipFree(c->xa2a[i]); c->xa2a[i] = nullptr; }
+    if (!c) return;
+    // the buffers whose size depends on the group: the next group makes its own
+    for (int i = 0; i < 4; i++) { c->carry[i].reset(); c->xa2a[i].reset(); }
+    c->xif_send.reset(); c->xif_all.reset();
 }
 
 // one grouped exchange: every send and receive of `ops` is in flight together (no ordering deadlock)

@@ -7,7 +7,20 @@
 #include <vector>
 
 #include "../../include/fs3d.h"
+#include "fs3d_buf.h"         // OwnedBuf: the one owner of a device or pinned allocation
 #include "fs3d_tables.h"      // the cell-code word, its row-code constants, UCOL_PITCH; the host definition of the geometry tables
+
+// the two kinds of memory a context owns (fs3d_buf.h); a failed allocation leaves the runtime's error for the caller's text
+struct DevMem {
+    static void *alloc(size_t bytes) { void *p = nullptr; return hipMalloc(&p, bytes) == hipSuccess ? p : nullptr; }
+    static void free(void *p) { (void)hipFree(p); }
+};
+struct PinnedMem {
+    static void *alloc(size_t bytes) { void *p = nullptr; return hipHostMalloc(&p, bytes, hipHostMallocDefault) == hipSuccess ? p : nullptr; }
+    static void free(void *p) { (void)hipHostFree(p); }
+};
+template <class T = void> using DevBuf = OwnedBuf<DevMem, T>;
+template <class T = void> using PinnedBuf = OwnedBuf<PinnedMem, T>;
 
 template <typename R>
 struct SweepParams {
@@ -66,30 +79,30 @@ struct SweepParams {
 
 // moving geometry (kernels_geom.hip): what fs3d_update_nodes* keeps between calls, allocated by the first one
 struct fs3d_geom {
-    uint8_t *stage = nullptr;               // type, bc_vel, bc_temp of the host entry points, dimx_global * plane cells each: a slab context
+    DevBuf<uint8_t> stage;                  // type, bc_vel, bc_temp of the host entry points, dimx_global * plane cells each: a slab context
                                             // (fs3d_update_nodes*_slab) keeps the byte arrays of the GLOBAL grid, its X lines are read from them
-    int *lst[3] = {};                       // per line of X / Y / Z: last index whose type is not NODE_IN (-1: none)
-    uint16_t *col[2] = {};                  // [o][group][UCOL_PITCH]: every group's candidate shared column (X, Y)
-    uint8_t *cflag[2] = {};                 // [o][group]: bit 0 uniform, bit 1 the pair is
-    unsigned long long *hash[2] = {};       // [o][group]: hash of the column, for the identity decision on the host
-    int *rep[2] = {};                       // [column id]: the group whose column it is
-    unsigned long long *cnt = nullptr;      // counter words of one update
-    void *host = nullptr;                   // pinned: counters, hashes, flags on their way to / from the host
+    DevBuf<int> lst[3];                     // per line of X / Y / Z: last index whose type is not NODE_IN (-1: none)
+    DevBuf<uint16_t> col[2];                // [o][group][UCOL_PITCH]: every group's candidate shared column (X, Y)
+    DevBuf<uint8_t> cflag[2];               // [o][group]: bit 0 uniform, bit 1 the pair is
+    DevBuf<unsigned long long> hash[2];     // [o][group]: hash of the column, for the identity decision on the host
+    DevBuf<int> rep[2];                     // [column id]: the group whose column it is
+    DevBuf<unsigned long long> cnt;         // counter words of one update
+    PinnedBuf<> host;                       // pinned: counters, hashes, flags on their way to / from the host
     // extrusion of a Shape2D grid (k_geom_extrude): the per-column records, allocated by the first call.  One pinned block and its
     // device copy, dimx*dimy columns each: velx, vely, T (float), cell (uint8) -- the 13 bytes per column that change with time --
     // then bottom (int), which changes with (dz, depth, depth_var) only
-    void *ex_host = nullptr, *ex_dev = nullptr;
+    PinnedBuf<> ex_host; DevBuf<> ex_dev;
     bool ex_bottom_valid = false;           // the bottom table on the device is the one of (ex_dz, ex_depth, ex_depth_var)
     double ex_dz = 0, ex_depth = 0, ex_depth_var = 0;
     // voxelisation of a Shape3D mesh (k_geom_raster_mesh, k_geom_fill_*): allocated by the first call, grown when a mesh has more
     // vertices or triangles.  One pinned block -- x, y, z and the velocities wx, wy, wz of mesh_vcap vertices (float), 3 * mesh_tcap indices (int), the counter
     // words on their way back -- and the device copies of its three parts; the indices travel again only when they differ from
     // the ones the pinned block holds
-    void *mesh_host = nullptr;
-    float *mesh_vert = nullptr;
-    int *mesh_idx = nullptr;
-    unsigned *mesh_cnt = nullptr;
-    unsigned *mesh_owner = nullptr;         // the entries with wall velocities: per cell the smallest index of the triangles that set it (all ones: none)
+    PinnedBuf<> mesh_host;
+    DevBuf<float> mesh_vert;
+    DevBuf<int> mesh_idx;
+    DevBuf<unsigned> mesh_cnt;
+    DevBuf<unsigned> mesh_owner;            // the entries with wall velocities: per cell the smallest index of the triangles that set it (all ones: none)
     int mesh_vcap = 0, mesh_tcap = 0, mesh_ntri_dev = -1;   // mesh_ntri_dev: triangles of the index list on the device (-1: none)
     int mesh_fill_rounds = 0;               // rounds the last flood fill ran, the closing one without a change included
     // device time of one update (fs3d_last_update_device_ms): event pairs around every batch of launches between two synchronisations;
@@ -103,16 +116,16 @@ struct fs3d_geom {
     // cell, the node types of the geometry the last update replaced, allocated by the first update made with the option on.  The
     // fill's own buffers are allocated by the first fill, kept and only grown: the round tag of every cell, the compact list of the
     // fresh cells, the counter words (device, and pinned on their way back)
-    uint8_t *prev_type = nullptr;
+    DevBuf<uint8_t> prev_type;
     bool prev_valid = false;                // prev_type holds the types of the geometry before the one the tables describe now
     float snap_ms = 0;                      // device time of the copy that made it (counted with the fill that reads it)
-    uint8_t *fill_tag = nullptr;
+    DevBuf<uint8_t> fill_tag;
     long long fill_tag_off = 0;             // bytes from fill_tag to the first owned cell's tag: 0, or on a slab of a group (FS3D_OPT_FRESH_CELLS_SLABS)
                                             // the ghost plane in front of the owned planes, rounded up to 8
-    int *fill_list = nullptr;
+    DevBuf<int> fill_list;
     long long fill_cap = 0;                 // entries fill_list holds
-    unsigned *fill_cnt = nullptr, *fill_host = nullptr;
-    double *fill_red = nullptr, *fill_red_host = nullptr;   // the collective fill: two counts on their way through fs3d_comm_allreduce_sum2 (device, pinned)
+    DevBuf<unsigned> fill_cnt; PinnedBuf<unsigned> fill_host;
+    DevBuf<double> fill_red; PinnedBuf<double> fill_red_host;   // the collective fill: two counts on their way through fs3d_comm_allreduce_sum2 (device, pinned)
     float last_fill_ms = 0;
 };
 
@@ -128,20 +141,19 @@ struct fs3d_ctx {
     long long nstride = 0;      // elements between the fields of the node-value / scratch arrays: ncell + padding
     // 5 layer buffers (cur,temp,half,next + spare temp for double-buffering)
     void *lay[5] = {};          // one allocation per layer buffer: 4 fields of fstride elements (lay_raw + a per-layer skew)
-    void *lay_raw[5] = {};      // what hipMalloc returned
+    DevBuf<> lay_raw[5];        // the allocations
     long long fstride = 0;      // ncell + 2*plane + padding (the fields / layers of one cell must not share their low address bits)
     int slot[4] = {0, 1, 2, 3}; // layer id -> buffer
     int spare = 4;
-    uint16_t *code = nullptr;
-    uint16_t *ucol[2] = {};     // shared code columns of the X / Y partition kernels (SweepParams::ucol)
-    unsigned *uflag[2] = {};
-    uint8_t *dead[3] = {};      // per direction, one byte per line: the line has no segment cell and no NODE_IN cell (X: [j][k], Y: [i][k], Z: [i][j])
-    void *node = nullptr;       // 4 x ncell
-    void *scr = nullptr;        // >= 6 x ncell: rows of the thread-per-line kernel / of the pipe kernel's halves (allocated on demand)
-    size_t scr_bytes = 0;
+    DevBuf<uint16_t> code;
+    DevBuf<uint16_t> ucol[2];   // shared code columns of the X / Y partition kernels (SweepParams::ucol)
+    DevBuf<unsigned> uflag[2];
+    DevBuf<uint8_t> dead[3];    // per direction, one byte per line: the line has no segment cell and no NODE_IN cell (X: [j][k], Y: [i][k], Z: [i][j])
+    DevBuf<> node;              // 4 x ncell
+    DevBuf<> scr;               // >= 6 x ncell: rows of the thread-per-line kernel / of the pipe kernel's halves (allocated on demand)
     // compact list of NODE_BOUND / NODE_VALVE cells (AdiSolver3D.cpp:286-311)
-    int *bnd_idx = nullptr;
-    void *bnd_val[4] = {};
+    DevBuf<int> bnd_idx;
+    DevBuf<> bnd_val[4];
     int n_bnd = 0;
     int bnd_cap = 0;            // entries the list buffers hold (fs3d_update_nodes grows them, never shrinks)
     long long ucol_cap[2] = {0, 0};   // columns ucol[d] holds when fs3d_update_nodes allocated it (0: the upload's exact-size table)
@@ -153,14 +165,13 @@ struct fs3d_ctx {
     int nseg[3] = {0, 0, 0};
     long long stale_in_cells = 0;  // NODE_IN cells on no segment of some direction (they merge stale `next` values): 0 for closed geometries
     // div error partials
-    double *red_buf = nullptr;     // device
-    double *red_host = nullptr;    // pinned
+    DevBuf<double> red_buf;
+    PinnedBuf<double> red_host;
     int red_blocks = 0;
     double diffError = 0.0;
     // result output (fs3d_get_layer*): device staging of the samples on their way to the host -- the V part, then the T part at
     // a 256-byte boundary; grown when a call needs more, never shrunk
-    void *gl_stage = nullptr;
-    size_t gl_stage_bytes = 0;
+    DevBuf<> gl_stage;
     long long gl_info[FS3D_N_GETLAYER_INFO] = {0, 0, 0};   // fs3d_get_layer_info
     int test_drop = 0;             // fault-injection hook of tests/test_gpu_failures.py: env FS3D_TEST_DROP_HANDOFF, read ONCE at fs3d_create
     hipStream_t stream = nullptr;
@@ -174,9 +185,9 @@ struct fs3d_ctx {
     int opt_fresh_cells = 0;               // FS3D_OPT_FRESH_CELLS: 1 = every single-context update keeps the node types of the geometry it replaces
     int opt_fresh_slabs = 0;               // FS3D_OPT_FRESH_CELLS_SLABS: 1 = a slab of a group keeps that snapshot too and fills collectively
     int opt_err_order = 0;                 // FS3D_OPT_ERR_ORDER: 1 = EvalDivError sums its per-cell terms serially in cell order (host), as the CPU path
-    double *err_terms = nullptr;           // ... one term per cell (device, allocated on first use)
+    DevBuf<double> err_terms;              // ... one term per cell (device, allocated on first use)
     std::vector<double> err_terms_host;
-    double *err_parts = nullptr;           // a member of a group: EvalDivError's per-workgroup (sum, count) pairs of ALL global planes (device, allocated on first use)
+    DevBuf<double> err_parts;              // a member of a group: EvalDivError's per-workgroup (sum, count) pairs of ALL global planes (device, allocated on first use)
     // options
     int opt_kernel = FS3D_SWEEP_AUTO;
     int ran_kernel[3] = {0, 0, 0};   // per direction: the kernel the last sweep really ran (fs3d_last_sweep_kernel)
@@ -194,21 +205,20 @@ struct fs3d_ctx {
     float t_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     int t_n[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     double t_create_segments_ms = 0;       // host time of fs3d_upload_nodes (CreateSegments + Init_GPU)
-    unsigned long long *stamps = nullptr;   // device buffer for fs3d_profile_sweep
-    int stamps_cap = 0;
+    DevBuf<unsigned long long> stamps;      // device buffer for fs3d_profile_sweep
     // comm
     void *comm = nullptr;          // ncclComm_t
     void *local = nullptr;         // fs3d_local_group* (in-process transport)
-    void *carry[4] = {};           // cross-slab X sweep: fwd in/out (6 x plane), bwd in/out (4 x plane)
+    DevBuf<> carry[4];             // cross-slab X sweep: fwd in/out (6 x plane), bwd in/out (4 x plane)
     int opt_div_core = 1;          // FS3D_OPT_DIV_CORE
-    void *seg_carry[2] = {};       // segmented long-line sweeps: forward (6 x lines) and backward (4 x lines) carries
-    long long seg_carry_lines = 0;
-    int *redo = nullptr;           // pipe kernel, fp32: per-bundle "compute again with full divisions" flags (all zero between sweeps)
-    int redo_cap = 0;
-    int *errw_host = nullptr, *errw_dev = nullptr;   // pinned + mapped error word of the kernels (checked at every synchronisation)
+    DevBuf<> seg_carry[2];         // segmented long-line sweeps: forward (2 x 6 x lines) and backward (4 x lines) carries
+    DevBuf<int> redo;              // pipe kernel, fp32: per-bundle "compute again with full divisions" flags (all zero between sweeps)
+    // pinned + mapped error word of the kernels (checked at every synchronisation).  The one allocation that is no OwnedBuf: mapped
+    // memory with a device alias, made once by fs3d_create and freed by fs3d_destroy
+    int *errw_host = nullptr, *errw_dev = nullptr;
     int rank = 0, nranks = 1;
-    void *xif_send = nullptr, *xif_all = nullptr;   // reduced-interface X sweep: this slab's 18 words per line / all ranks'
-    void *xa2a[4] = {};            // distributed interface solve: packed words out / in, boundary values out / in ([rank][words][lines per rank])
+    DevBuf<> xif_send, xif_all;    // reduced-interface X sweep: this slab's 18 words per line / all ranks'
+    DevBuf<> xa2a[4];              // distributed interface solve: packed words out / in, boundary values out / in ([rank][words][lines per rank])
     int opt_xsolve = 0;            // FS3D_OPT_XSOLVE: 0 auto, 1 pipelined (bit-exact), 2 reduced interface
     int ran_xsolve = 0;            // what the last cross-slab X sweep ran: 1 pipelined, 2 reduced interface, 3 reduced interface with the interface words from the partition kernel
     int ran_xa2a = 0;              // ... and whether the interface solve was distributed over the ranks (two all-to-alls instead of one all-gather)
@@ -233,9 +243,15 @@ static inline std::string call_failed(const fs3d_ctx *c, const char *call, const
 // blocks of 256 threads for n items, at most `cap` (the kernels stride over what is left)
 static inline unsigned grid_for(long long n, int cap = 4096) { return (unsigned)std::max(1LL, std::min<long long>((n + 255) / 256, cap)); }
 
-// device allocations / frees of the geometry paths (fs3d_upload_nodes, fs3d_update_nodes*) are counted: fs3d_geometry_info entry 13
-#define GMALLOC(c, pp, bytes) do { HIPCHK(c, hipMalloc((void **)(pp), (bytes))); (c)->geom_allocs++; } while (0)
-static inline void gfree(fs3d_ctx *c, void *p) { if (p) { hipFree(p); c->geom_allocs++; } }
+// a reserve / replace / reserve_all of the context's buffers that failed, as the status of the call.  The geometry paths
+// (fs3d_upload_nodes, fs3d_update_nodes*, the fill) pass &c->geom_allocs to their device buffers: fs3d_geometry_info entry 13
+#define BUFCHK(c, ok) do { if (!(ok)) return fail((c), FS3D_ERR_HIP, call_failed((c), #ok, hipGetErrorString(hipGetLastError()))); } while (0)
+// reserve_all for the buffers the sweeps use: before one of them is freed to grow, what the stream still does with it finishes
+static inline bool stream_reserve(fs3d_ctx *c, std::initializer_list<BufWant<DevMem>> set, bool *fresh = nullptr)
+{
+    for (const BufWant<DevMem> &w : set) if (w.buf->raw() && !w.buf->holds(w.bytes)) { hipStreamSynchronize(c->stream); break; }
+    return reserve_all(set, nullptr, fresh);
+}
 
 // kernels_geom.hip
 void fs3d_geom_destroy(fs3d_ctx *c);

@@ -318,7 +318,9 @@ extern "C" fs3d_status fs3d_create(fs3d_ctx **out, int device, fs3d_precision pr
         if (v >= FS3D_SWEEP_AUTO && v <= FS3D_SWEEP_EXACT) c->opt_kernel = v;
     }
     if (const char *e = getenv("FS3D_DEFAULT_F64_PART")) c->opt_f64_part = atoi(e) ? 1 : 0;   // initial FS3D_OPT_F64_PART of new contexts
-#define CK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { g_create_err = call_failed(c, #call, hipGetErrorString(e_)); fs3d_destroy(c); return FS3D_ERR_HIP; } } while (0)
+#define CK_FAILED(what, e) { g_create_err = call_failed(c, what, hipGetErrorString(e)); fs3d_destroy(c); return FS3D_ERR_HIP; }
+#define CK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) CK_FAILED(#call, e_) } while (0)
+#define CKBUF(ok) do { if (!(ok)) CK_FAILED(#ok, hipGetLastError()) } while (0)
     CK(hipSetDevice(device));
     CK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     // every field = haloSize + dimx*dimy*dimz + haloSize elements, data at +haloSize
@@ -335,24 +337,26 @@ extern "C" fs3d_status fs3d_create(fs3d_ctx **out, int device, fs3d_precision pr
     c->fstride = c->ncell + 2 * c->plane + fpad;
     const size_t lbytes = (size_t)4 * c->fstride * c->esize;
     for (int l = 0; l < 5; l++) {
-        CK(hipMalloc(&c->lay_raw[l], lbytes + 5 * skew));
+        CKBUF(c->lay_raw[l].replace(lbytes + 5 * skew));
         c->lay[l] = (char *)c->lay_raw[l] + (size_t)l * skew;
         CK(hipMemsetAsync(c->lay[l], 0, lbytes, c->stream));
     }
     // the 4 node-value fields and the 6 row fields of the exact kernels' scratch: padded the same way
     c->nstride = c->ncell + (getenv("FS3D_FIELD_PAD") ? fpad : 832);
-    CK(hipMalloc((void **)&c->code, (size_t)c->nstride * sizeof(uint16_t)));
+    CKBUF(c->code.replace((size_t)c->nstride * sizeof(uint16_t)));
     CK(hipMemsetAsync(c->code, 0, (size_t)c->nstride * sizeof(uint16_t), c->stream));
-    CK(hipMalloc(&c->node, (size_t)4 * c->nstride * c->esize));
+    CKBUF(c->node.replace((size_t)4 * c->nstride * c->esize));
     CK(hipMemsetAsync(c->node, 0, (size_t)4 * c->nstride * c->esize, c->stream));
     c->red_blocks = dimx * ((dimy + DIVE_JS - 1) / DIVE_JS);      // k_div_error: one block per plane and DIVE_JS rows
-    CK(hipMalloc((void **)&c->red_buf, sizeof(double) * 2 * (c->red_blocks + 1)));
-    CK(hipHostMalloc((void **)&c->red_host, sizeof(double) * 2, hipHostMallocDefault));
+    CKBUF(c->red_buf.replace(sizeof(double) * 2 * (c->red_blocks + 1)));
+    CKBUF(c->red_host.replace(sizeof(double) * 2));
     CK(hipHostMalloc((void **)&c->errw_host, sizeof(int), hipHostMallocMapped));
     *c->errw_host = 0;
     CK(hipHostGetDevicePointer((void **)&c->errw_dev, c->errw_host, 0));
     CK(hipStreamSynchronize(c->stream));
+#undef CKBUF
 #undef CK
+#undef CK_FAILED
     *out = c;
     return FS3D_OK;
 }
@@ -363,32 +367,14 @@ extern "C" void fs3d_destroy(fs3d_ctx *c)
     hipSetDevice(c->device);
     if (c->stream) hipStreamSynchronize(c->stream);
     fs3d_comm_destroy(c);
-    for (int l = 0; l < 5; l++) if (c->lay_raw[l]) hipFree(c->lay_raw[l]);
-    if (c->redo) hipFree(c->redo);
-    for (int i = 0; i < 2; i++) if (c->seg_carry[i]) hipFree(c->seg_carry[i]);
-    if (c->code) hipFree(c->code);
-    for (int d = 0; d < 3; d++) if (c->dead[d]) hipFree(c->dead[d]);
-    for (int d = 0; d < 2; d++) { if (c->ucol[d]) hipFree(c->ucol[d]); if (c->uflag[d]) hipFree(c->uflag[d]); }
-    if (c->node) hipFree(c->node);
-    if (c->scr) hipFree(c->scr);
-    if (c->xif_send) hipFree(c->xif_send);
-    if (c->xif_all) hipFree(c->xif_all);
-    for (int v = 0; v < 4; v++) if (c->bnd_val[v]) hipFree(c->bnd_val[v]);
-    if (c->bnd_idx) hipFree(c->bnd_idx);
     fs3d_geom_destroy(c);
-    if (c->err_terms) hipFree(c->err_terms);
-    if (c->err_parts) hipFree(c->err_parts);
-    if (c->red_buf) hipFree(c->red_buf);
-    if (c->gl_stage) hipFree(c->gl_stage);
-    if (c->stamps) hipFree(c->stamps);
-    if (c->red_host) hipHostFree(c->red_host);
     if (c->errw_host) hipHostFree(c->errw_host);
     for (auto e : c->ev) hipEventDestroy(e);
     if (c->ev_src) hipEventDestroy(c->ev_src);
     if (c->ev_halo) hipEventDestroy(c->ev_halo);
     if (c->comm_stream) hipStreamDestroy(c->comm_stream);
     if (c->stream) hipStreamDestroy(c->stream);
-    delete c;
+    delete c;                                      // every buffer goes with its member (the device is still current)
 }
 
 extern "C" fs3d_status fs3d_set_params(fs3d_ctx *c, double v_T, double v_vis, double t_vis, double t_phi)
@@ -464,12 +450,10 @@ extern "C" fs3d_status fs3d_profiler_events(fs3d_ctx *c, const char *names[FS3D_
 // ---------------------------------------------------------------------------------
 
 // one table of the upload: the old buffer goes, one of the table's size comes and takes the table
-template <typename T>
-static fs3d_status put_table(fs3d_ctx *c, T *&dev, const void *src, size_t bytes)
+static fs3d_status put_table(fs3d_ctx *c, RawBuf<DevMem> &dev, const void *src, size_t bytes)
 {
-    gfree(c, dev); dev = nullptr;
-    GMALLOC(c, &dev, bytes);
-    HIPCHK(c, hipMemcpy(dev, src, bytes, hipMemcpyHostToDevice));
+    BUFCHK(c, dev.replace(bytes, &c->geom_allocs));
+    HIPCHK(c, hipMemcpy(dev.raw(), src, bytes, hipMemcpyHostToDevice));
     return FS3D_OK;
 }
 
@@ -498,8 +482,7 @@ static fs3d_status upload_nodes_impl(fs3d_ctx *c, const uint8_t *type, const uin
         GTRY(put_table(c, c->dead[d], t.dead[d].data(), t.dead[d].size()));
         if (d == 2) break;
         // exact-size tables (ucol_cap 0: fs3d_update_nodes allocates its own); none where the lines exceed UCOL_PITCH
-        gfree(c, c->ucol[d]); c->ucol[d] = nullptr;
-        gfree(c, c->uflag[d]); c->uflag[d] = nullptr;
+        c->ucol[d].reset(&c->geom_allocs); c->uflag[d].reset(&c->geom_allocs);
         c->ucol_cap[d] = 0; c->n_ucol[d] = t.n_ucol[d];
         if (!t.has_columns[d]) continue;
         GTRY(put_table(c, c->ucol[d], t.ucol[d].data(), t.ucol[d].size() * sizeof(uint16_t)));
@@ -507,8 +490,8 @@ static fs3d_status upload_nodes_impl(fs3d_ctx *c, const uint8_t *type, const uin
     }
     for (int v = 0; v < 4; v++)
         HIPCHK(c, hipMemcpy((R *)c->node + (size_t)v * c->nstride, val[v] + first, (size_t)c->ncell * sizeof(R), hipMemcpyHostToDevice));
-    gfree(c, c->bnd_idx); c->bnd_idx = nullptr;
-    for (int v = 0; v < 4; v++) { gfree(c, c->bnd_val[v]); c->bnd_val[v] = nullptr; }
+    c->bnd_idx.reset(&c->geom_allocs);
+    for (int v = 0; v < 4; v++) c->bnd_val[v].reset(&c->geom_allocs);
     c->n_bnd = (int)t.bnd_idx.size(); c->bnd_cap = c->n_bnd;
     if (c->n_bnd) {
         GTRY(put_table(c, c->bnd_idx, t.bnd_idx.data(), sizeof(int) * t.bnd_idx.size()));
@@ -637,27 +620,17 @@ static void fill_params(fs3d_ctx *c, SweepParams<R> &p, int dir, double dt_, int
     p.fast_div = c->opt_div_core && plain((double)p.two_ds[0]) && plain((double)p.two_ds[1]) && plain((double)p.two_ds[2]) && plain((double)p.dt);
 }
 
-static fs3d_status ensure_scratch(fs3d_ctx *c)
-{
-    if (c->scr) return FS3D_OK;
-    HIPCHK(c, hipMalloc(&c->scr, (size_t)6 * c->nstride * c->esize));
-    c->scr_bytes = (size_t)6 * c->nstride * c->esize;
-    return FS3D_OK;
-}
+// the rows of the thread-per-line kernels, 6 per cell: allocated by the first sweep that needs them
+static fs3d_status ensure_scratch(fs3d_ctx *c) { BUFCHK(c, c->scr.reserve((size_t)6 * c->nstride * c->esize)); return FS3D_OK; }
 
 // carry buffers of the cross-slab X sweeps ([value][line]: 6 forward, 4 backward words per line); failure is a status, not an
 // early return past the callers' abort guard
 static fs3d_status ensure_carries(fs3d_ctx *c)
 {
-    if (c->carry[0] && c->carry[1] && c->carry[2] && c->carry[3]) return FS3D_OK;
-    const size_t pl = (size_t)c->plane;
-    const size_t words[4] = {6, 6, 4, 4};
-    for (int k = 0; k < 4; k++)
-        if (!c->carry[k] && hipMalloc(&c->carry[k], words[k] * pl * c->esize) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(c, FS3D_ERR_HIP, "cross-slab X sweep: hipMalloc of the carry buffers failed");
-        }
-    return FS3D_OK;
+    const size_t w = (size_t)c->plane * c->esize;
+    if (reserve_all<DevMem>({{&c->carry[0], 6 * w}, {&c->carry[1], 6 * w}, {&c->carry[2], 4 * w}, {&c->carry[3], 4 * w}})) return FS3D_OK;
+    (void)hipGetLastError();
+    return fail(c, FS3D_ERR_HIP, "cross-slab X sweep: hipMalloc of the carry buffers failed");
 }
 
 // Cross-slab X sweep (nranks > 1): forward over the slabs 0 -> R-1, backward R-1 -> 0, carries over RCCL.
@@ -718,11 +691,10 @@ static fs3d_status xsweep_reduced(fs3d_ctx *c, SweepParams<R> &p)
     p.scr_ = (R *)c->scr;
     const size_t pl = (size_t)c->plane;
     if ((st = ensure_carries(c))) return st;
-    if (!c->xif_send) {
-        if (hipMalloc(&c->xif_send, 18 * pl * c->esize) != hipSuccess || hipMalloc(&c->xif_all, (size_t)c->nranks * 18 * pl * c->esize) != hipSuccess) {
-            (void)hipGetLastError();
-            return st = fail(c, FS3D_ERR_HIP, "reduced-interface X solve: hipMalloc of the interface buffers failed");
-        }
+    const size_t xif = 18 * pl * c->esize;
+    if (!stream_reserve(c, {{&c->xif_send, xif}, {&c->xif_all, c->nranks * xif}})) {
+        (void)hipGetLastError();
+        return st = fail(c, FS3D_ERR_HIP, "reduced-interface X solve: hipMalloc of the interface buffers failed");
     }
     // the slab's interface words: a first pass of the X partition kernel (rows and chunk elimination on chip, 8 words per cell
     // read, 18 words per line written) where it applies, else the thread-per-line walk over the planes
@@ -743,13 +715,12 @@ static fs3d_status xsweep_reduced(fs3d_ctx *c, SweepParams<R> &p)
     if (a2a) {
         const long long lp = (((long long)pl + c->nranks - 1) / c->nranks + 63) / 64 * 64;       // lines per owner
         const size_t w1 = (size_t)c->nranks * 18 * lp * c->esize, w2 = (size_t)c->nranks * 8 * lp * c->esize;
-        if (!c->xa2a[0]) {
-            const size_t sz[4] = {w1, w1, w2, w2};
-            for (int k = 0; k < 4; k++)
-                if (hipMalloc(&c->xa2a[k], sz[k]) != hipSuccess || hipMemsetAsync(c->xa2a[k], 0, sz[k], c->stream) != hipSuccess) {
-                    (void)hipGetLastError();
-                    return st = fail(c, FS3D_ERR_HIP, "distributed interface solve: hipMalloc of the exchange buffers failed");
-                }
+        bool fresh = false;                        // new buffers start as zeros (the all-to-alls move the padding lines too)
+        bool ok = stream_reserve(c, {{&c->xa2a[0], w1}, {&c->xa2a[1], w1}, {&c->xa2a[2], w2}, {&c->xa2a[3], w2}}, &fresh);
+        for (int k = 0; k < 4 && ok && fresh; k++) ok = hipMemsetAsync(c->xa2a[k], 0, c->xa2a[k].bytes(), c->stream) == hipSuccess;
+        if (!ok) {
+            (void)hipGetLastError();
+            return st = fail(c, FS3D_ERR_HIP, "distributed interface solve: hipMalloc of the exchange buffers failed");
         }
         launch_xpack<R>(c, c->xif_send, (long long)pl, lp, c->xa2a[0]);
         if ((st = fs3d_comm_alltoall(c, c->xa2a[0], c->xa2a[1], (size_t)18 * lp))) return st;
@@ -899,11 +870,7 @@ extern "C" fs3d_status fs3d_profile_sweep(fs3d_ctx *c, int dir, double dt, int l
     HIPCHK(c, hipSetDevice(c->device));
     const int la = dir == 2 ? c->dimy : c->dimz, n_o = dir == 0 ? c->dimy : c->dimx;
     const int nb = n_o * ((la + 31) / 32);      // enough for the partition kernel's 32-line workgroups too
-    if (c->stamps_cap < nb) {
-        if (c->stamps) hipFree(c->stamps);
-        HIPCHK(c, hipMalloc((void **)&c->stamps, sizeof(unsigned long long) * 64 * (size_t)nb));
-        c->stamps_cap = nb;
-    }
+    BUFCHK(c, c->stamps.reserve(sizeof(unsigned long long) * 64 * (size_t)nb));
     HIPCHK(c, hipMemsetAsync(c->stamps, 0, sizeof(unsigned long long) * 64 * (size_t)nb, c->stream));
     Launch r = Launch::NA;
     if (c->prec == FS3D_F32) {
@@ -975,7 +942,7 @@ static fs3d_status div_error_enqueue(fs3d_ctx *c, int layer)
     if (c->opt_err_order) {
         if (c->dimx != c->dimx_global || c->comm || c->local || c->nranks > 1)
             return fail(c, FS3D_ERR_UNSUPPORTED, "FS3D_OPT_ERR_ORDER = 1 (the CPU path's summation order) is implemented for a single context only");
-        if (!c->err_terms) HIPCHK(c, hipMalloc((void **)&c->err_terms, (size_t)c->ncell * sizeof(double)));
+        BUFCHK(c, c->err_terms.reserve((size_t)c->ncell * sizeof(double)));
     }
     // A group sums what a single context of the global grid sums, in its order: every rank writes the partial sums of its own
     // planes into their place in an array over the GLOBAL planes that is zero elsewhere, the arrays are added over the ranks
@@ -983,7 +950,7 @@ static fs3d_status div_error_enqueue(fs3d_ctx *c, int layer)
     const int nj = (c->dimy + DIVE_JS - 1) / DIVE_JS;
     const bool group = c->nranks > 1;
     const size_t gwords = (size_t)2 * c->dimx_global * nj;
-    if (group && !c->err_parts) HIPCHK(c, hipMalloc((void **)&c->err_parts, gwords * sizeof(double)));
+    if (group) BUFCHK(c, c->err_parts.reserve(gwords * sizeof(double)));
     RecScope rec(c, 5);
     if (group) HIPCHK(c, hipMemsetAsync(c->err_parts, 0, gwords * sizeof(double), c->stream));
     hipLaunchKernelGGL((k_div_error<R>), dim3(c->red_blocks), dim3(256), 0, c->stream, c->code,
@@ -1237,12 +1204,10 @@ static fs3d_status get_layer_impl(fs3d_ctx *c, R *outV, double *outT, int odx, i
     c->gl_info[0] = n; c->gl_info[1] = 0;
     R *dV = outV + 3 * (size_t)i0 * po;
     double *dT = outT + (size_t)i0 * po;
-    if (!dev && vbytes + (size_t)n * 8 > c->gl_stage_bytes) {
-        if (c->gl_stage) HIPCHK(c, hipFree(c->gl_stage));
-        c->gl_stage = nullptr; c->gl_stage_bytes = 0;
-        HIPCHK(c, hipMalloc(&c->gl_stage, vbytes + (size_t)n * 8));
-        c->gl_stage_bytes = vbytes + (size_t)n * 8;
-        c->gl_info[2]++;
+    if (!dev && n) {
+        bool grown = false;
+        BUFCHK(c, c->gl_stage.reserve(vbytes + (size_t)n * 8, nullptr, &grown));
+        c->gl_info[2] += grown;
     }
     hipLaunchKernelGGL((k_clear_type<R>), dim3(grid_for(c->ncell)), dim3(256), 0, c->stream, c->code, c->ncell,
                        (int)FS3D_NODE_OUT, (R)99999.0f, fld<R>(c, b, 0), fld<R>(c, b, 1), fld<R>(c, b, 2), fld<R>(c, b, 3));

@@ -1134,35 +1134,8 @@ static float gev_take(fs3d_ctx *c)
     return ms;
 }
 
-void fs3d_geom_destroy(fs3d_ctx *c)
-{
-    fs3d_geom &g = c->geom;
-    for (hipEvent_t e : g.ev) if (e) hipEventDestroy(e);
-    if (g.stage) hipFree(g.stage);
-    for (int d = 0; d < 3; d++) if (g.lst[d]) hipFree(g.lst[d]);
-    for (int d = 0; d < 2; d++) {
-        if (g.col[d]) hipFree(g.col[d]);
-        if (g.cflag[d]) hipFree(g.cflag[d]);
-        if (g.hash[d]) hipFree(g.hash[d]);
-        if (g.rep[d]) hipFree(g.rep[d]);
-    }
-    if (g.cnt) hipFree(g.cnt);
-    if (g.host) hipHostFree(g.host);
-    if (g.ex_host) hipHostFree(g.ex_host);
-    if (g.ex_dev) hipFree(g.ex_dev);
-    if (g.mesh_host) hipHostFree(g.mesh_host);
-    if (g.mesh_vert) hipFree(g.mesh_vert);
-    if (g.mesh_idx) hipFree(g.mesh_idx);
-    if (g.mesh_cnt) hipFree(g.mesh_cnt);
-    if (g.mesh_owner) hipFree(g.mesh_owner);
-    if (g.prev_type) hipFree(g.prev_type);
-    if (g.fill_tag) hipFree(g.fill_tag);
-    if (g.fill_list) hipFree(g.fill_list);
-    if (g.fill_cnt) hipFree(g.fill_cnt);
-    if (g.fill_host) hipHostFree(g.fill_host);
-    if (g.fill_red) hipFree(g.fill_red);
-    if (g.fill_red_host) hipHostFree(g.fill_red_host);
-}
+// (the buffers of fs3d_geom go with the context)
+void fs3d_geom_destroy(fs3d_ctx *c) { for (hipEvent_t e : c->geom.ev) if (e) hipEventDestroy(e); }
 
 // cells of the global grid: the byte arrays of an update cover them (a single context: its own cells)
 static inline long long geom_gcell(const fs3d_ctx *c) { return (long long)c->dimx_global * c->plane; }
@@ -1171,23 +1144,24 @@ static inline long long geom_gcell(const fs3d_ctx *c) { return (long long)c->dim
 static fs3d_status geom_prepare(fs3d_ctx *c, bool need_stage)
 {
     fs3d_geom &g = c->geom;
-    if (need_stage && !g.stage) GMALLOC(c, &g.stage, (size_t)3 * geom_gcell(c));      // (an x-slab: the byte arrays of the global grid)
-    if (g.cnt) return FS3D_OK;
-    for (int d = 0; d < 3; d++) GMALLOC(c, &g.lst[d], (size_t)geom_lines(c, d).nlines * sizeof(int));
+    long long *const na = &c->geom_allocs;
+    if (need_stage) BUFCHK(c, g.stage.reserve((size_t)3 * geom_gcell(c), na));      // (an x-slab: the byte arrays of the global grid)
+    for (int d = 0; d < 3; d++) BUFCHK(c, g.lst[d].reserve((size_t)geom_lines(c, d).nlines * sizeof(int), na));
     size_t host_bytes = GC_WORDS * sizeof(unsigned long long);
     for (int d = 0; d < 2; d++) {
         const GeomLines L = geom_lines(c, d);
         if (L.n > UCOL_PITCH) continue;                  // as geom_shared_columns: no shared columns for longer lines
         const size_t nq = (size_t)L.n_o * geom_ng(c);
-        GMALLOC(c, &g.col[d], nq * UCOL_PITCH * sizeof(uint16_t));
-        HIPCHK(c, hipMemsetAsync(g.col[d], 0, nq * UCOL_PITCH * sizeof(uint16_t), c->stream));
-        GMALLOC(c, &g.cflag[d], nq);
-        GMALLOC(c, &g.hash[d], nq * sizeof(unsigned long long));
-        GMALLOC(c, &g.rep[d], nq * sizeof(int));
+        bool fresh = false;
+        BUFCHK(c, g.col[d].reserve(nq * UCOL_PITCH * sizeof(uint16_t), na, &fresh));
+        if (fresh) HIPCHK(c, hipMemsetAsync(g.col[d], 0, nq * UCOL_PITCH * sizeof(uint16_t), c->stream));
+        BUFCHK(c, g.cflag[d].reserve(nq, na));
+        BUFCHK(c, g.hash[d].reserve(nq * sizeof(unsigned long long), na));
+        BUFCHK(c, g.rep[d].reserve(nq * sizeof(int), na));
         host_bytes = std::max(host_bytes, nq * (sizeof(unsigned long long) + sizeof(unsigned) + sizeof(int) + 1) + 64);
     }
-    HIPCHK(c, hipHostMalloc((void **)&g.host, host_bytes, hipHostMallocDefault));
-    GMALLOC(c, &g.cnt, GC_WORDS * sizeof(unsigned long long));
+    BUFCHK(c, g.host.reserve(host_bytes));
+    BUFCHK(c, g.cnt.reserve(GC_WORDS * sizeof(unsigned long long), na));
     return FS3D_OK;
 }
 
@@ -1200,8 +1174,8 @@ static fs3d_status geom_columns(fs3d_ctx *c, int d)
     if (L.n > UCOL_PITCH) { c->n_ucol[d] = 0; return FS3D_OK; }
     const size_t nq = (size_t)L.n_o * ng;
     if (c->ucol_cap[d] < (long long)nq) {                // the upload's table holds its own distinct columns only: once, room for any number
-        gfree(c, c->ucol[d]); c->ucol[d] = nullptr; c->ucol_cap[d] = 0;
-        GMALLOC(c, &c->ucol[d], nq * UCOL_PITCH * sizeof(uint16_t));
+        c->ucol_cap[d] = 0;
+        BUFCHK(c, c->ucol[d].replace(nq * UCOL_PITCH * sizeof(uint16_t), &c->geom_allocs));
         c->ucol_cap[d] = (long long)nq;
     }
     const int keep = (0xF << (4 * d)) | (3 << CODE_TYPE_SHIFT);
@@ -1279,12 +1253,10 @@ static fs3d_status update_nodes_impl(fs3d_ctx *c, const uint8_t *gtype, const ui
     c->stale_in_cells = (long long)hc[GC_STALE];
     // BOUND / VALVE list: grow-only
     if (nbnd > c->bnd_cap) {
-        gfree(c, c->bnd_idx); c->bnd_idx = nullptr;
-        for (int v = 0; v < 4; v++) { gfree(c, c->bnd_val[v]); c->bnd_val[v] = nullptr; }
         c->bnd_cap = 0; c->n_bnd = 0;
         const long long cap = std::min<long long>(ncell, nbnd + nbnd / 4 + 1024);      // headroom: the list of a moving wall breathes
-        GMALLOC(c, &c->bnd_idx, sizeof(int) * (size_t)cap);
-        for (int v = 0; v < 4; v++) GMALLOC(c, &c->bnd_val[v], sizeof(R) * (size_t)cap);
+        BUFCHK(c, c->bnd_idx.replace(sizeof(int) * (size_t)cap, &c->geom_allocs));
+        for (int v = 0; v < 4; v++) BUFCHK(c, c->bnd_val[v].replace(sizeof(R) * (size_t)cap, &c->geom_allocs));
         c->bnd_cap = (int)cap;
     }
     if (nbnd) {
@@ -1383,11 +1355,10 @@ static fs3d_status extrude_check(fs3d_ctx *c, ExtrudeIn &in, const char *name)
         return fail(c, FS3D_ERR_INVALID, std::string(name) + ": active_dimz = ceil(depth / dz) + 1 must lie in 2 .. dimz");
     const size_t ncol = (size_t)c->dimx_global * c->dimy;      // the 2D grid covers the global plane (a single context: its own)
     HIPCHK(c, hipSetDevice(c->device));
-    if (!g.ex_host) HIPCHK(c, hipHostMalloc(&g.ex_host, ex_bytes(ncol), hipHostMallocDefault));
-    if (!g.ex_dev) {                                      // (a failure leaves the pointer null: the next call allocates again)
-        GMALLOC(c, &g.ex_dev, ex_bytes(ncol));
-        g.ex_bottom_valid = false; g.ex_dz = -1;
-    }
+    BUFCHK(c, g.ex_host.reserve(ex_bytes(ncol)));
+    bool fresh = false;                                   // (a failure leaves the buffer empty: the next call allocates again)
+    BUFCHK(c, g.ex_dev.reserve(ex_bytes(ncol), &c->geom_allocs, &fresh));
+    if (fresh) { g.ex_bottom_valid = false; g.ex_dz = -1; }
     char *h = (char *)g.ex_host;
     int *bottom = (int *)(h + ex_off_bottom(ncol));
     if (g.ex_dz != in.dz || g.ex_depth != in.depth || g.ex_depth_var != in.depth_var) {      // (a NaN depth_var: recomputed every call)
@@ -1450,16 +1421,14 @@ static fs3d_status mesh_prepare(fs3d_ctx *c, int nvert, int ntri, bool vel = fal
 {
     fs3d_geom &g = c->geom;
     HIPCHK(c, hipSetDevice(c->device));
-    if (!g.mesh_cnt) GMALLOC(c, &g.mesh_cnt, MC_WORDS * sizeof(unsigned));
-    if (vel && !g.mesh_owner) GMALLOC(c, &g.mesh_owner, (size_t)c->ncell * sizeof(unsigned));
-    if (g.mesh_host && nvert <= g.mesh_vcap && ntri <= g.mesh_tcap) return FS3D_OK;
-    if (g.mesh_host) { hipHostFree(g.mesh_host); g.mesh_host = nullptr; }
-    gfree(c, g.mesh_vert); g.mesh_vert = nullptr;
-    gfree(c, g.mesh_idx); g.mesh_idx = nullptr;
+    BUFCHK(c, g.mesh_cnt.reserve(MC_WORDS * sizeof(unsigned), &c->geom_allocs));
+    if (vel) BUFCHK(c, g.mesh_owner.reserve((size_t)c->ncell * sizeof(unsigned), &c->geom_allocs));
+    if (g.mesh_host && g.mesh_vert && g.mesh_idx && nvert <= g.mesh_vcap && ntri <= g.mesh_tcap) return FS3D_OK;
+    // either capacity exceeded: the pinned block and both device copies are made again together
     g.mesh_vcap = std::max(std::max(nvert, g.mesh_vcap), 1); g.mesh_tcap = std::max(std::max(ntri, g.mesh_tcap), 1); g.mesh_ntri_dev = -1;
-    HIPCHK(c, hipHostMalloc(&g.mesh_host, (MESH_COLS * (size_t)g.mesh_vcap + 3 * (size_t)g.mesh_tcap) * 4 + MC_WORDS * sizeof(unsigned), hipHostMallocDefault));
-    GMALLOC(c, &g.mesh_vert, MESH_COLS * (size_t)g.mesh_vcap * sizeof(float));
-    GMALLOC(c, &g.mesh_idx, 3 * (size_t)g.mesh_tcap * sizeof(int));
+    BUFCHK(c, g.mesh_host.replace((MESH_COLS * (size_t)g.mesh_vcap + 3 * (size_t)g.mesh_tcap) * 4 + MC_WORDS * sizeof(unsigned)));
+    BUFCHK(c, g.mesh_vert.replace(MESH_COLS * (size_t)g.mesh_vcap * sizeof(float), &c->geom_allocs));
+    BUFCHK(c, g.mesh_idx.replace(3 * (size_t)g.mesh_tcap * sizeof(int), &c->geom_allocs));
     return FS3D_OK;
 }
 
@@ -1615,7 +1584,7 @@ static fs3d_status fresh_snapshot(fs3d_ctx *c, bool *taken)
     fs3d_geom &g = c->geom;
     *taken = false;
     g.prev_valid = false; g.snap_ms = 0;
-    if (!g.prev_type) GMALLOC(c, &g.prev_type, (size_t)c->ncell);
+    BUFCHK(c, g.prev_type.reserve((size_t)c->ncell, &c->geom_allocs));
     if (!c->have_nodes) return FS3D_OK;
     gev_reset(c);
     gev_begin(c);
@@ -1866,18 +1835,17 @@ static fs3d_status fresh_fill_impl(fs3d_ctx *c, const uint8_t *prev, int layer, 
 {
     fs3d_geom &g = c->geom;
     const long long ncell = c->ncell;
-    if (!g.fill_tag) {
-        // a slab of a group: [pad][ghost plane][owned planes][ghost plane], the first owned cell aligned to 8 bytes (k_fresh_classify<8>)
-        g.fill_tag_off = coll ? (c->plane + 7) / 8 * 8 : 0;
-        GMALLOC(c, &g.fill_tag, (size_t)(g.fill_tag_off + ncell + (coll ? c->plane : 0)));
-    }
-    if (!g.fill_cnt) GMALLOC(c, &g.fill_cnt, FC_WORDS * sizeof(unsigned));
-    if (!g.fill_host) HIPCHK(c, hipHostMalloc((void **)&g.fill_host, FC_WORDS * sizeof(unsigned), hipHostMallocDefault));
-    if (coll && !g.fill_red) GMALLOC(c, &g.fill_red, 2 * sizeof(double));
-    if (coll && !g.fill_red_host) HIPCHK(c, hipHostMalloc((void **)&g.fill_red_host, 2 * sizeof(double), hipHostMallocDefault));
+    long long *const na = &c->geom_allocs;
+    // a slab of a group: [pad][ghost plane][owned planes][ghost plane], the first owned cell aligned to 8 bytes (k_fresh_classify<8>)
+    g.fill_tag_off = coll ? (c->plane + 7) / 8 * 8 : 0;
+    BUFCHK(c, g.fill_tag.reserve((size_t)(g.fill_tag_off + ncell + (coll ? c->plane : 0)), na));
+    BUFCHK(c, g.fill_cnt.reserve(FC_WORDS * sizeof(unsigned), na));
+    BUFCHK(c, g.fill_host.reserve(FC_WORDS * sizeof(unsigned)));
+    if (coll) BUFCHK(c, g.fill_red.reserve(2 * sizeof(double), na));
+    if (coll) BUFCHK(c, g.fill_red_host.reserve(2 * sizeof(double)));
     if (!g.fill_list) {                                     // the fresh cells are a thin shell: an eighth of the grid to begin with
         const long long cap = std::min<long long>(ncell, ncell / 8 + 1024);
-        GMALLOC(c, &g.fill_list, sizeof(int) * (size_t)cap);
+        BUFCHK(c, g.fill_list.replace(sizeof(int) * (size_t)cap, na));
         g.fill_cap = cap;
     }
     uint8_t *tag = g.fill_tag + g.fill_tag_off;            // the first owned cell's
@@ -1896,9 +1864,9 @@ static fs3d_status fresh_fill_impl(fs3d_ctx *c, const uint8_t *prev, int layer, 
         GTRY(gev_sync(c));
         fresh = (long long)g.fill_host[FC_FRESH];
         if (fresh <= g.fill_cap) break;
-        gfree(c, g.fill_list); g.fill_list = nullptr; g.fill_cap = 0;      // grow-only, with headroom: the shell of a moving wall breathes
+        g.fill_cap = 0;                                     // grow-only, with headroom: the shell of a moving wall breathes
         const long long cap = std::min<long long>(ncell, fresh + fresh / 4 + 1024);
-        GMALLOC(c, &g.fill_list, sizeof(int) * (size_t)cap);
+        BUFCHK(c, g.fill_list.replace(sizeof(int) * (size_t)cap, na));
         g.fill_cap = cap;
     }
     // the collective fill: the counter words [at, at + n), n <= 2, summed over the ranks into fill_red_host; returns synchronised

@@ -981,28 +981,9 @@ static Launch pipe_failed(fs3d_ctx *c, const char *what)
     return Launch::FAILED;
 }
 
-// per-bundle "compute again with full divisions" flags (fp32) for n bundles, all zero between sweeps; grows only
-static bool ensure_redo(fs3d_ctx *c, int n)
-{
-    if (c->redo_cap >= n) return true;
-    if (c->redo) { hipStreamSynchronize(c->stream); hipFree(c->redo); c->redo = nullptr; c->redo_cap = 0; }
-    if (hipMalloc(&c->redo, (size_t)n * sizeof(int)) != hipSuccess) return false;
-    if (hipMemsetAsync(c->redo, 0, (size_t)n * sizeof(int), c->stream) != hipSuccess) return false;
-    c->redo_cap = n;
-    return true;
-}
-
 // the context's scratch, at least `elems` elements of R (shared with the thread-per-line kernel, which needs 6 per cell)
 template <typename R>
-static bool pipe_scratch(fs3d_ctx *c, size_t elems)
-{
-    const size_t bytes = std::max(elems, (size_t)6 * (size_t)c->nstride) * sizeof(R);
-    if (c->scr && c->scr_bytes >= bytes) return true;
-    if (c->scr) { hipStreamSynchronize(c->stream); hipFree(c->scr); c->scr = nullptr; c->scr_bytes = 0; }
-    if (hipMalloc(&c->scr, bytes) != hipSuccess) return false;
-    c->scr_bytes = bytes;
-    return true;
-}
+static bool pipe_scratch(fs3d_ctx *c, size_t elems) { return stream_reserve(c, {{&c->scr, std::max(elems, (size_t)6 * (size_t)c->nstride) * sizeof(R)}}); }
 
 // MODE 0: the whole sweep, every bundle.  MODE 1 / 2: forward / backward half of the bundles [b0, b1) -- the X sweep of an
 // x-slab (cross-slab pipeline, fs3d_hip.hip: xsweep_multi) or one segment of lines longer than a launch holds on chip
@@ -1031,8 +1012,11 @@ static Launch launch_pipe(fs3d_ctx *c, SweepParams<R> p, int b0 = 0, int b1 = 0)
         if (!p.scr_ || p.scr_bundles < b1) { c->err = "pipe halves: scratch not prepared"; return Launch::FAILED; }
     }
     int *redo = nullptr;
-    if (HAS_FM && p.fast_div) {
-        if (!ensure_redo(c, std::max(grid, n_o * n_tiles))) return pipe_failed(c, "hipMalloc of the redo flags");
+    if (HAS_FM && p.fast_div) {      // per-bundle "compute again with full divisions" flags: grow-only, all zero between sweeps
+        const size_t bytes = (size_t)std::max(grid, n_o * n_tiles) * sizeof(int);
+        bool fresh = false;
+        if (!stream_reserve(c, {{&c->redo, bytes}}, &fresh)) return pipe_failed(c, "hipMalloc of the redo flags");
+        if (fresh && hipMemsetAsync(c->redo, 0, bytes, c->stream) != hipSuccess) { c->redo.reset(); return pipe_failed(c, "hipMemsetAsync of the redo flags"); }
         redo = c->redo;
     }
     // division core first; the full-division instance right behind it redoes the bundles that asked for it
@@ -1103,14 +1087,10 @@ static Launch run_segments(fs3d_ctx *c, SweepParams<R> p)
     const int la_len = DIR == 2 ? p.dimy : p.dimz, n_o = DIR == 0 ? p.dimy : p.dimx;
     const int seg = PIPE_NW * CH, nseg = (n + seg - 1) / seg, nb = n_o * ((la_len + 63) / 64);
     const long long lines = (long long)n_o * la_len;
-    if (c->seg_carry_lines < lines) {
-        for (int i = 0; i < 2; i++) if (c->seg_carry[i]) { hipStreamSynchronize(c->stream); hipFree(c->seg_carry[i]); c->seg_carry[i] = nullptr; }
-        // two forward carry arrays, used alternately: a bundle that asks for the full-division instance reads its carry_in
-        // a second time, after the first instance has stored the segment's own carries
-        if (hipMalloc(&c->seg_carry[0], 12 * (size_t)lines * sizeof(R)) != hipSuccess || hipMalloc(&c->seg_carry[1], 4 * (size_t)lines * sizeof(R)) != hipSuccess)
-            return pipe_failed(c, "hipMalloc of the segment carries");
-        c->seg_carry_lines = lines;
-    }
+    // two forward carry arrays, used alternately: a bundle that asks for the full-division instance reads its carry_in
+    // a second time, after the first instance has stored the segment's own carries
+    if (!stream_reserve(c, {{&c->seg_carry[0], 12 * (size_t)lines * sizeof(R)}, {&c->seg_carry[1], 4 * (size_t)lines * sizeof(R)}}))
+        return pipe_failed(c, "hipMalloc of the segment carries");
     p.carry_pitch = lines;
     if (!pipe_scratch<R>(c, (size_t)nseg * nb * 6 * PIPE_NW * CH * 64)) return pipe_failed(c, "hipMalloc of the segment scratch");
     p.scr_ = (R *)c->scr; p.scr_bundles = nb;
