@@ -25,6 +25,8 @@ OPT_ERR_ORDER = 7         # 1: EvalDivError sums its terms serially in cell orde
 OPT_MESH_VOXELS = 8       # the two mesh entries: 0 the reference's rasteriser (default), 1 conservative voxelisation (watertight)
 MESH_VOXELS = {"reference": 0, "conservative": 1}
 OPT_FRESH_CELLS = 9       # 1: every single-context update_nodes* keeps the node types of the geometry it replaces, for fill_fresh_cells (default 0)
+OPT_MESH_SHELL = 11       # the mesh entries, with the conservative voxelisation: 0 every cell whose box a triangle touches (default), 1 the thin shell
+MESH_SHELL = {"box": 0, "cross": 1}
 OPT_FRESH_CELLS_SLABS = 10  # 1: a slab of a group keeps that snapshot too (the update_nodes*_slab entries) and fill_fresh_cells* run collectively (default 0)
 XSOLVE_AUTO, XSOLVE_PIPELINED, XSOLVE_REDUCED, XSOLVE_REDUCED_A2A = 0, 1, 2, 3
 
@@ -262,12 +264,17 @@ class Solver:
             raise ValueError("triangles: [m, 3] indices that fit an int")
         return xyz, tri
 
-    def _mesh_voxels(self, voxels):
-        """voxels= of the two mesh methods: None leaves FS3D_OPT_MESH_VOXELS as it is, "reference" / "conservative" set it (it stays set)."""
+    def _mesh_voxels(self, voxels, shell=None):
+        """voxels= of the two mesh methods: None leaves FS3D_OPT_MESH_VOXELS as it is, "reference" / "conservative" set it (it stays set).
+        shell= likewise for FS3D_OPT_MESH_SHELL: "box" / "cross"."""
         if voxels is not None:
             if voxels not in MESH_VOXELS:
                 raise ValueError("voxels is 'reference' or 'conservative'")
             self.set_option(OPT_MESH_VOXELS, MESH_VOXELS[voxels])
+        if shell is not None:
+            if shell not in MESH_SHELL:
+                raise ValueError("shell is 'box' or 'cross'")
+            self.set_option(OPT_MESH_SHELL, MESH_SHELL[shell])
 
     @staticmethod
     def _mesh_velocities(w, nvert):
@@ -283,45 +290,46 @@ class Solver:
         wv, wt = ([], []) if w is None else (self._mesh_velocities(w, len(xyz[0])), [float(wallT)])
         return [_p(a) for a in xyz + wv] + [len(xyz[0]), _p(tri), tri.size // 3, float(baseT)] + wt
 
-    def _voxelize_dev(self, fn, what, g, w, idx, baseT, wallT, arrays, voxels):
-        self._mesh_voxels(voxels)
+    def _voxelize_dev(self, fn, what, g, w, idx, baseT, wallT, arrays, voxels, shell=None):
+        self._mesh_voxels(voxels, shell)
         ptrs = self._dev_ptrs(what, arrays)
         self._chk(fn(self.h, *self._mesh_args(g, w, idx, baseT, wallT), *ptrs))
 
-    def _update_shape3d(self, fn, g, w, idx, baseT, wallT, voxels):
-        self._mesh_voxels(voxels)
+    def _update_shape3d(self, fn, g, w, idx, baseT, wallT, voxels, shell=None):
+        self._mesh_voxels(voxels, shell)
         return self._update(fn, *self._mesh_args(g, w, idx, baseT, wallT))
 
-    def voxelize_shape3d_dev(self, g, idx, baseT, type, bc_vel, bc_temp, vx, vy, vz, T, voxels=None):
+    def voxelize_shape3d_dev(self, g, idx, baseT, type, bc_vel, bc_temp, vx, vy, vz, T, voxels=None, shell=None):
         """Grid3D::Build + FloodFill + the Node array on the device: the mesh (g, idx) of shape3d.Shape3D.subframe(t) voxelised into
         seven arrays on the context's device -- torch tensors or raw pointers, as update_nodes_dev takes them.  The context's
-        geometry is not touched."""
-        self._voxelize_dev(self.lib.fs3d_voxelize_shape3d_dev, "voxelize_shape3d_dev", g, None, idx, baseT, None, [type, bc_vel, bc_temp, vx, vy, vz, T], voxels)
+        geometry is not touched.  voxels= / shell= of every mesh method: None leaves FS3D_OPT_MESH_VOXELS / FS3D_OPT_MESH_SHELL as
+        they are, a word of MESH_VOXELS / MESH_SHELL sets the option, and it stays set ("cross", the thin shell, needs "conservative")."""
+        self._voxelize_dev(self.lib.fs3d_voxelize_shape3d_dev, "voxelize_shape3d_dev", g, None, idx, baseT, None, [type, bc_vel, bc_temp, vx, vy, vz, T], voxels, shell)
 
-    def update_nodes_shape3d(self, g, idx, baseT, voxels=None):
+    def update_nodes_shape3d(self, g, idx, baseT, voxels=None, shell=None):
         """update_nodes with the voxelisation of the mesh (g, idx) as the source: 12 bytes per vertex travel, the node arrays are
         written by kernels.  Same contract as update_nodes."""
-        return self._update_shape3d(self.lib.fs3d_update_nodes_shape3d, g, None, idx, baseT, None, voxels)
+        return self._update_shape3d(self.lib.fs3d_update_nodes_shape3d, g, None, idx, baseT, None, voxels, shell)
 
-    def voxelize_shape3d_vel_dev(self, g, w, idx, baseT, wallT, type, bc_vel, bc_temp, vx, vy, vz, T, voxels=None):
+    def voxelize_shape3d_vel_dev(self, g, w, idx, baseT, wallT, type, bc_vel, bc_temp, vx, vy, vz, T, voxels=None, shell=None):
         """voxelize_shape3d_dev with walls that carry the velocity of the mesh -- w [n, 3], what shape3d.Shape3D.subframe_velocity(t)
         returns -- and the temperature wallT (conservative voxelisation only)."""
         self._voxelize_dev(self.lib.fs3d_voxelize_shape3d_vel_dev, "voxelize_shape3d_vel_dev", g, w, idx, baseT, wallT,
-                           [type, bc_vel, bc_temp, vx, vy, vz, T], voxels)
+                           [type, bc_vel, bc_temp, vx, vy, vz, T], voxels, shell)
 
-    def update_nodes_shape3d_vel(self, g, w, idx, baseT, wallT, voxels=None):
+    def update_nodes_shape3d_vel(self, g, w, idx, baseT, wallT, voxels=None, shell=None):
         """update_nodes_shape3d with walls that carry the velocity of the mesh (w [n, 3]) and the temperature wallT (conservative
         voxelisation only).  Same contract as update_nodes."""
-        return self._update_shape3d(self.lib.fs3d_update_nodes_shape3d_vel, g, w, idx, baseT, wallT, voxels)
+        return self._update_shape3d(self.lib.fs3d_update_nodes_shape3d_vel, g, w, idx, baseT, wallT, voxels, shell)
 
-    def update_nodes_shape3d_slab(self, g, idx, baseT, voxels=None):
+    def update_nodes_shape3d_slab(self, g, idx, baseT, voxels=None, shell=None):
         """update_nodes_shape3d on an x-slab (or a whole-grid context): the vertices g are in GLOBAL grid coordinates, every rank of a
         group is given the same mesh and voxelises and fills the global grid on its own device; no rank waits for another."""
-        return self._update_shape3d(self.lib.fs3d_update_nodes_shape3d_slab, g, None, idx, baseT, None, voxels)
+        return self._update_shape3d(self.lib.fs3d_update_nodes_shape3d_slab, g, None, idx, baseT, None, voxels, shell)
 
-    def update_nodes_shape3d_vel_slab(self, g, w, idx, baseT, wallT, voxels=None):
+    def update_nodes_shape3d_vel_slab(self, g, w, idx, baseT, wallT, voxels=None, shell=None):
         """update_nodes_shape3d_vel on an x-slab (or a whole-grid context), as update_nodes_shape3d_slab."""
-        return self._update_shape3d(self.lib.fs3d_update_nodes_shape3d_vel_slab, g, w, idx, baseT, wallT, voxels)
+        return self._update_shape3d(self.lib.fs3d_update_nodes_shape3d_vel_slab, g, w, idx, baseT, wallT, voxels, shell)
 
     def flood_fill_global_dev(self, type):
         """flood_fill_dev on a device array of the GLOBAL grid's node types, from any context (an x-slab too): the fill the two

@@ -182,6 +182,7 @@ struct fs3d_ctx {
     int opt_keep_temp = 0;                 // FS3D_OPT_KEEP_TEMP
     int opt_f64_part = 0;                  // FS3D_OPT_F64_PART
     int opt_mesh_voxels = 0;               // FS3D_OPT_MESH_VOXELS: 0 = the reference's rasteriser, 1 = conservative voxelisation (k_geom_voxel_mesh)
+    int opt_mesh_shell = 0;                // FS3D_OPT_MESH_SHELL: 0 = the conservative shell as it is, 1 = its thin (6-separating) subset (k_geom_voxel_mesh<.., true>)
     int opt_fresh_cells = 0;               // FS3D_OPT_FRESH_CELLS: 1 = every single-context update keeps the node types of the geometry it replaces
     int opt_fresh_slabs = 0;               // FS3D_OPT_FRESH_CELLS_SLABS: 1 = a slab of a group keeps that snapshot too and fills collectively
     int opt_err_order = 0;                 // FS3D_OPT_ERR_ORDER: 1 = EvalDivError sums its per-cell terms serially in cell order (host), as the CPU path

@@ -400,6 +400,9 @@ extern "C" fs3d_status fs3d_set_option(fs3d_ctx *c, int option, int value)
     case FS3D_OPT_MESH_VOXELS:
         if (value != 0 && value != 1) return fail(c, FS3D_ERR_INVALID, "bad mesh voxelisation id (0: the reference's rasteriser, 1: conservative)");
         c->opt_mesh_voxels = value; return FS3D_OK;
+    case FS3D_OPT_MESH_SHELL:
+        if (value != 0 && value != 1) return fail(c, FS3D_ERR_INVALID, "bad mesh shell id (0: every cell whose box a triangle touches, 1: the thin shell of centre crosses)");
+        c->opt_mesh_shell = value; return FS3D_OK;
     case FS3D_OPT_FRESH_CELLS:
         if (value != 0 && value != 1) return fail(c, FS3D_ERR_INVALID, "bad fresh-cells value (0: off, 1: the updates keep the node types of the geometry they replace)");
         c->opt_fresh_cells = value; return FS3D_OK;

@@ -595,6 +595,8 @@ __global__ void __launch_bounds__(64) k_geom_raster_mesh(const float *__restrict
 // a degenerate triangle has no plane and walks the box's depth, along its smallest extent.  The only write is a byte store of
 // NODE_BOUND into an array preset to NODE_IN: idempotent, so order is free and no atomics are needed.  Every index lies inside
 // the clipped box; there is no scan line, no guard and no flag word.
+// THIN (FS3D_OPT_MESH_SHELL = 1): of the cells that pass, a non-degenerate triangle sets those whose centre cross it meets -- the
+// filter of shape3d.py (SHELL_MODES), on the values the conservative test has just computed; its half-widths are wave-uniform.
 // OWNER (the entries with wall velocities): every store of NODE_BOUND comes with an integer atomicMin of the triangle's index into
 // the cell's word of `owner`, preset to all ones -- the owner of a wall cell is the smallest index of the triangles that set it
 // (shape3d.py), a minimum over a set: nothing depends on the order of arrival, and no float atomics take part.  `owner` holds the
@@ -607,10 +609,16 @@ __global__ void __launch_bounds__(64) k_geom_raster_mesh(const float *__restrict
 
 struct VoxEdge { double wa, wb, c; };
 
-__device__ __forceinline__ bool vox_pass(const VoxEdge &e, double x, double y) { return (e.wa * x + e.wb * y) + e.c >= 0.0; }
+__device__ __forceinline__ double vox_val(const VoxEdge &e, double x, double y) { return (e.wa * x + e.wb * y) + e.c; }
+__device__ __forceinline__ bool vox_pass(const VoxEdge &e, double x, double y) { return vox_val(e, x, y) >= 0.0; }
+// the thin shell: the centre of the unit square of a projection lies inside all three edges -- each value reaches its half-width
+__device__ __forceinline__ bool vox_centre(const VoxEdge (&e)[3], const double (&hw)[3], double x, double y)
+{
+    return vox_val(e[0], x, y) >= hw[0] && vox_val(e[1], x, y) >= hw[1] && vox_val(e[2], x, y) >= hw[2];
+}
 __device__ __forceinline__ double vox_sel(int c, double x, double y, double z) { return c == 0 ? x : (c == 1 ? y : z); }
 
-template <bool OWNER>
+template <bool OWNER, bool THIN>
 __global__ void __launch_bounds__(64) k_geom_voxel_mesh(const float *__restrict__ vx, const float *__restrict__ vy, const float *__restrict__ vz,
                                                          const int *__restrict__ tri, int dimx, int dimy, int dimz, uint8_t *type, unsigned *owner,
                                                          int own_x0, int own_nx)
@@ -692,6 +700,18 @@ __global__ void __launch_bounds__(64) k_geom_voxel_mesh(const float *__restrict_
         const double sl = S * ((fabs(na) + fabs(nb)) + fabs(nd));
         c1 = (cmax - tmin) + sl; c2 = (cmin - tmax) - sl;
     }
+    // THIN: per projection k of third axis C, the half-widths of its three edge values and of the plane value, and n_C != 0
+    [[maybe_unused]] double hw[3][3], hn[3];
+    [[maybe_unused]] bool along[3];
+    if constexpr (THIN) {
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+#pragma unroll
+            for (int j = 0; j < 3; j++) hw[k][j] = 0.5 * (fabs(edge[k][j].wa) + fabs(edge[k][j].wb));
+            hn[k] = 0.5 * (fabs(nr[k]) + fabs(nr[(k + 1) % 3]));
+            along[k] = nr[(k + 2) % 3] != 0.0;
+        }
+    }
     uint8_t *const base = type + (((long long)o[0] * dimy + o[1]) * dimz + o[2]);
     const int ncol = cnt_a * cnt_b;                         // at most 8194^2
 #pragma unroll 1
@@ -707,6 +727,8 @@ __global__ void __launch_bounds__(64) k_geom_voxel_mesh(const float *__restrict_
             k0 = max((int)floor(fmin(fmax(fmin(lo, hi), -lim), lim)) - 1, 0);
             k1 = min((int)ceil(fmin(fmax(fmax(lo, hi), -lim), lim)) + 1, cnt_d - 1);
         }
+        [[maybe_unused]] bool centre_d = false;             // THIN: the column's centre line (along d) passes inside the three edges
+        if constexpr (THIN) centre_d = along[0] && vox_centre(edge[0], hw[0], pa, pb);
         uint8_t *const colp = base + ia * sa + ib * sb;
 #pragma unroll 1
         for (int k = k0; k <= k1; k++) {
@@ -716,6 +738,12 @@ __global__ void __launch_bounds__(64) k_geom_voxel_mesh(const float *__restrict_
             if (!degenerate) {
                 const double s = g + nd * pd;
                 if (!(s + c1 >= 0.0) || !(s + c2 <= 0.0)) continue;
+                if constexpr (THIN) {                       // one of the three centre segments meets the triangle: inside the edges, and in depth
+                    const double u1 = s + c1, u2 = s + c2;
+                    if (!(centre_d && u1 >= hn[0] && u2 <= -hn[0]) &&
+                        !(along[1] && u1 >= hn[1] && u2 <= -hn[1] && vox_centre(edge[1], hw[1], pb, pd)) &&
+                        !(along[2] && u1 >= hn[2] && u2 <= -hn[2] && vox_centre(edge[2], hw[2], pd, pa))) continue;
+                }
             }
             colp[k * sd] = FS3D_NODE_BOUND;
             if constexpr (OWNER) {
@@ -1440,6 +1468,8 @@ static fs3d_status mesh_check(fs3d_ctx *c, const MeshIn &in, const char *name, b
     const bool conservative = c->opt_mesh_voxels == 1;
     if (in.vel && !conservative)                         // the owner of a wall cell is defined by the conservative overlap test
         return fail(c, FS3D_ERR_INVALID, std::string(name) + ": wall velocities need the conservative voxelisation (FS3D_OPT_MESH_VOXELS = 1)");
+    if (c->opt_mesh_shell && !conservative)              // the thin shell is a filter inside the conservative overlap test
+        return fail(c, FS3D_ERR_INVALID, std::string(name) + ": the thin shell (FS3D_OPT_MESH_SHELL = 1) needs the conservative voxelisation (FS3D_OPT_MESH_VOXELS = 1)");
     if (in.nvert < 1 || in.ntri < 0) return fail(c, FS3D_ERR_INVALID, std::string(name) + ": a mesh has at least one vertex and no negative number of triangles");
     for (int q = 0; q < 3 * in.ntri; q++)
         if (in.tri[q] < 0 || in.tri[q] >= in.nvert) return fail(c, FS3D_ERR_INVALID, std::string(name) + ": triangle index outside the vertex list");
@@ -1524,11 +1554,14 @@ static fs3d_status mesh_launch(fs3d_ctx *c, const MeshIn &in, bool new_idx, cons
     HIPCHK(c, hipMemsetAsync(g.mesh_cnt, 0, sizeof(unsigned), c->stream));
     const bool conservative = c->opt_mesh_voxels == 1;      // (mesh_check admitted the coordinates for this mode)
     if (in.vel) HIPCHK(c, hipMemsetAsync(g.mesh_owner, 0xFF, (size_t)c->ncell * sizeof(unsigned), c->stream));      // (the entries admit conservative only)
+    const bool thin = c->opt_mesh_shell == 1;               // (mesh_check admitted it with the conservative mode only)
+    auto vox_own = thin ? k_geom_voxel_mesh<true, true> : k_geom_voxel_mesh<true, false>;
+    auto vox = thin ? k_geom_voxel_mesh<false, true> : k_geom_voxel_mesh<false, false>;
     if (in.ntri && in.vel)
-        hipLaunchKernelGGL(k_geom_voxel_mesh<true>, dim3((unsigned)in.ntri), dim3(64), 0, c->stream, g.mesh_vert, g.mesh_vert + g.mesh_vcap,
+        hipLaunchKernelGGL(vox_own, dim3((unsigned)in.ntri), dim3(64), 0, c->stream, g.mesh_vert, g.mesh_vert + g.mesh_vcap,
                            g.mesh_vert + 2 * (size_t)g.mesh_vcap, g.mesh_idx, gx, c->dimy, c->dimz, a.type, g.mesh_owner, c->x_offset, c->dimx);
     else if (in.ntri && conservative)
-        hipLaunchKernelGGL(k_geom_voxel_mesh<false>, dim3((unsigned)in.ntri), dim3(64), 0, c->stream, g.mesh_vert, g.mesh_vert + g.mesh_vcap,
+        hipLaunchKernelGGL(vox, dim3((unsigned)in.ntri), dim3(64), 0, c->stream, g.mesh_vert, g.mesh_vert + g.mesh_vcap,
                            g.mesh_vert + 2 * (size_t)g.mesh_vcap, g.mesh_idx, gx, c->dimy, c->dimz, a.type, (unsigned *)nullptr, 0, 0);
     else if (in.ntri)
         hipLaunchKernelGGL(k_geom_raster_mesh, dim3((unsigned)in.ntri), dim3(64), 0, c->stream, g.mesh_vert, g.mesh_vert + g.mesh_vcap,

@@ -137,6 +137,8 @@ public:
     // FS3D_OPT_MESH_VOXELS for the UpdateGridShape3D calls that follow: 0 the reference's rasteriser, 1 the conservative
     // voxelisation (Shape3D::voxels of host/Shape3D.h has the same values)
     void SetMeshVoxels(int mode) { chk(fs3d_set_option(ctx_, FS3D_OPT_MESH_VOXELS, mode)); }
+    // FS3D_OPT_MESH_SHELL for the same calls: 0 the conservative shell as it is, 1 its thin subset (needs SetMeshVoxels(1))
+    void SetMeshShell(int mode) { chk(fs3d_set_option(ctx_, FS3D_OPT_MESH_SHELL, mode)); }
     // FS3D_OPT_FRESH_CELLS: with it on, every UpdateGrid* call of a single-GPU solver keeps the node types of the geometry it
     // replaces, and FillFreshCells, called directly after the update and before UpdateBoundaries, gives every cell of `cur` that
     // the update turned NODE_IN the mean of its fluid neighbours (fs3d_fill_fresh_cells; no reference

@@ -7,7 +7,8 @@
 // File: frames; per frame: vertices, per vertex "x y z  vx vy vz", triangles, 3 indices each.  Frame duration 1/75 s; the
 // cycle length of a Shape3D run is Config::frame_time and GetFrame is always 0 (Grid3D.cpp:303-336).
 // Shape3D::voxels = 1 replaces the rasteriser (not the fill) by a conservative voxelisation, which the reference does not have: see
-// VoxelTriangle below and the derivation in cmc_fluid_solver_amd/shape3d.py.
+// VoxelTriangle below and the derivation in cmc_fluid_solver_amd/shape3d.py.  Shape3D::shell = 1 keeps of that shell the cells whose centre
+// cross a triangle meets (the thin, 6-separating shell: the same file).
 // Shape3D::wall_velocity (conservative voxelisation only) gives the NODE_BOUND cells the velocity of the mesh, which the reference
 // reads per vertex, interpolates (Grid3D.cpp:915) and then drops in RasterPolygon / RasterLine: see WallWeights below.
 // Deviations, on purpose (a third one, of the moving loop, stands at FillShape3DNodes below):
@@ -53,12 +54,17 @@ struct Shape3D {
     // NODE_BOUND iff a triangle overlaps the cell's closed unit box, so the shell of a closed mesh is closed for the flood fill.
     // Set it before Load; Prepare(t) honours it.  Same value as FS3D_OPT_MESH_VOXELS.
     int voxels = 0;
+    // 0: the conservative shell as it is.  1 (needs voxels = 1): the thin shell -- of the cells a non-degenerate triangle's conservative
+    // test sets, those whose centre cross (the three unit segments through the centre, one along each axis) the triangle meets:
+    // closed for the fill's 6-neighbourhood, about 0.55 of the cells.  The rule and why it separates stand in
+    // cmc_fluid_solver_amd/shape3d.py (SHELL_MODES).  Set it before Load; Prepare(t) honours it.  Same value as FS3D_OPT_MESH_SHELL.
+    int shell = 0;
     // What the NODE_BOUND cells carry.  0: v = 0 (the reference's run).  1 (`motion`) / 2 (`file`): the velocity of the mesh at the
     // projection of the cell's centre onto the cell's owner triangle (WallWeights below), from the vertex velocities
     // SubFrameVelocity gives for that source.  Needs voxels = 1.  Set it before Load; Prepare(t) honours it and keeps `owner` and
     // `cur`, which FillShape3DNodes reads.
     int wall_velocity = 0;
-    std::vector<int> owner;                   // per cell: the smallest index of the triangles whose conservative test sets it, -1 off the walls
+    std::vector<int> owner;                   // per cell: the smallest index of the triangles whose test (with shell = 1: the thin one) sets it, -1 off the walls
     Shape3DFrame cur;                         // the sub-frame of the last Prepare: vertices in grid coordinates, velocities, triangles
     static constexpr double VOXEL_SLACK = 5.8207660913467407e-11;        // 2^-34: the derivation stands in cmc_fluid_solver_amd/shape3d.py
     static constexpr double VOXEL_DEGENERATE = 5.9604644775390625e-08;   // 2^-24
@@ -342,7 +348,13 @@ private:
         o[0] = fd(fd(a[1] * b[2]) - fd(a[2] * b[1])); o[1] = fd(fd(a[2] * b[0]) - fd(a[0] * b[2])); o[2] = fd(fd(a[0] * b[1]) - fd(a[1] * b[0]));
     }
     static double dot(const double a[3], const double b[3]) { return fd(fd(fd(a[0] * b[0]) + fd(a[1] * b[1])) + fd(a[2] * b[2])); }
-    static bool VoxelPass(const VoxelEdge &e, double x, double y) { return fd(fd(fd(e.wa * x) + fd(e.wb * y)) + e.c) >= 0; }
+    static double VoxelValue(const VoxelEdge &e, double x, double y) { return fd(fd(fd(e.wa * x) + fd(e.wb * y)) + e.c); }
+    static bool VoxelPass(const VoxelEdge &e, double x, double y) { return VoxelValue(e, x, y) >= 0; }
+    // the thin shell: the centre of the unit square of a projection lies inside all three edges -- each value reaches its half-width
+    static bool VoxelCentre(const VoxelEdge e[3], const double hw[3], double x, double y)
+    {
+        return VoxelValue(e[0], x, y) >= hw[0] && VoxelValue(e[1], x, y) >= hw[1] && VoxelValue(e[2], x, y) >= hw[2];
+    }
     void VoxelTriangle(const float *const p[3], int t)
     {
         const int dims[3] = {dimx, dimy, dimz};
@@ -405,6 +417,16 @@ private:
             const double sl = fd(S * fd(fd(std::fabs(na) + std::fabs(nb)) + std::fabs(nd)));
             c1 = fd(fd(cmax - tmin) + sl); c2 = fd(fd(cmin - tmax) - sl);
         }
+        // shell = 1: per projection k of third axis C, the half-widths of its three edge values and of the plane value, and n_C != 0
+        const bool thin = shell == 1 && !degenerate;
+        const double nr[3] = {na, nb, nd};
+        double hw[3][3], hn[3];
+        bool along[3];
+        for (int k = 0; k < 3; k++) {
+            for (int j = 0; j < 3; j++) hw[k][j] = fd(0.5 * fd(std::fabs(edge[k][j].wa) + std::fabs(edge[k][j].wb)));
+            hn[k] = fd(0.5 * fd(std::fabs(nr[k]) + std::fabs(nr[(k + 1) % 3])));
+            along[k] = nr[(k + 2) % 3] != 0;
+        }
         const size_t stride[3] = {(size_t)dimy * dimz, (size_t)dimz, 1};
         const size_t base = id(o[0], o[1], o[2]);
         for (int ia = 0; ia < n[a]; ia++)
@@ -426,6 +448,12 @@ private:
                     if (!degenerate) {
                         const double s = fd(g + fd(nd * pd));
                         if (!(fd(s + c1) >= 0) || !(fd(s + c2) <= 0)) continue;
+                        if (thin) {                       // one of the three centre segments meets the triangle: inside the edges, and in depth
+                            const double u1 = fd(s + c1), u2 = fd(s + c2);
+                            if (!(along[0] && u1 >= hn[0] && u2 <= -hn[0] && VoxelCentre(edge[0], hw[0], pa, pb)) &&
+                                !(along[1] && u1 >= hn[1] && u2 <= -hn[1] && VoxelCentre(edge[1], hw[1], pb, pd)) &&
+                                !(along[2] && u1 >= hn[2] && u2 <= -hn[2] && VoxelCentre(edge[2], hw[2], pd, pa))) continue;
+                        }
                     }
                     const size_t cell = base + ia * stride[a] + ib * stride[b] + k * stride[d];
                     type[cell] = NODE_BOUND;
@@ -439,6 +467,8 @@ private:
     {
         type.assign((size_t)dimx * dimy * dimz, NODE_IN);
         if (voxels != 0 && voxels != 1) throw std::runtime_error("Shape3D: voxels is 0 (the reference's rasteriser) or 1 (conservative)");
+        if (shell != 0 && shell != 1) throw std::runtime_error("Shape3D: shell is 0 (every cell whose box a triangle touches) or 1 (the thin shell of centre crosses)");
+        if (shell && voxels != 1) throw std::runtime_error("Shape3D: the thin shell needs the conservative voxelisation (it is a filter inside its overlap test)");
         if (wall_velocity < 0 || wall_velocity > 2) throw std::runtime_error("Shape3D: wall_velocity is 0 (walls at rest), 1 (motion) or 2 (file)");
         if (wall_velocity && voxels != 1) throw std::runtime_error("Shape3D: wall velocities need the conservative voxelisation (the owner of a wall cell is defined by its overlap test)");
         owner.clear();
@@ -502,9 +532,10 @@ void FillShape3DNodes(Grid3D<FTYPE> &g, const Shape3D &sh, double baseT, double 
 // Grid3D(dx,dy,dz,baseT) + LoadFromFile + Prepare_CPU(0) for a Shape3D input (FluidSolver3D.cpp:121-145)
 template <typename FTYPE>
 void LoadShape3D(Grid3D<FTYPE> &g, Shape3D &sh, const std::string &path, double dx, double dy, double dz, double baseT, bool align, int voxels = 0,
-                 int wall_velocity = 0, double wallT = 0)
+                 int wall_velocity = 0, double wallT = 0, int shell = 0)
 {
     sh.voxels = voxels;
+    sh.shell = shell;
     sh.wall_velocity = wall_velocity;
     sh.Load(path, dx, dy, dz, align);
     g.Resize(sh.dimx, sh.dimy, sh.dimz);

@@ -81,14 +81,34 @@ VOXEL_DEGENERATE = 2.0 ** -24
 _VOXEL_AXES = ((1, 2, 0), (2, 0, 1), (0, 1, 2))      # (a, b, d): the column plane and the depth axis, cyclic, by depth axis d
 _VOXEL_EDGES = ((0, 1), (1, 2), (2, 0))
 VOXEL_MODES = ("reference", "conservative")
+# ---- thin shell (voxels="conservative", shell="cross"): a filter inside the conservative test -------------------------------------
+# The flood fill spreads over the 6-neighbourhood, so a shell only has to be 6-separating: where a triangle cuts the straight
+# line between two neighbouring cell centres, one of the two cells has to be a wall.  That line is one half of the centre cross of
+# each of the two cells -- the three unit segments through a cell's centre, one parallel to each axis -- so it is enough to set the
+# cells whose centre cross the triangle meets, not every cell whose box it touches.
+# Rule.  A non-degenerate triangle sets a cell of its clipped box iff the conservative test holds (every v[k][j] >= 0, s + c1 >= 0,
+# s + c2 <= 0, with v[k][j] = (wA x + wB y) + c the nine edge values and s = (na pa + nb pb) + nd pd the plane value of
+# _voxel_triangle) and some projection k = 0, 1, 2 = (a, b), (b, d), (d, a), of third axis C = d, a, b, has all of
+#   n_C != 0,   v[k][j] >= (|wA| + |wB|) / 2 for j = 0, 1, 2,   s + c1 >= H_k,   s + c2 <= -H_k,   H_k = (|n_A| + |n_B|) / 2.
+# Why this is the centre segment along C.  In projection k that segment is a point, the centre of the unit square: c holds the
+# maximum of w over the square, which exceeds w at the centre by (|wA| + |wB|) / 2, so comparing v with that half-width instead of
+# 0 tests the point where the conservative test tests the square.  Along the normal the box's interval is wider than the
+# segment's by (|n|_1 - |n_C|) / 2 = H_k on each side.  n_C = 0 is a triangle parallel to the segment: an edge-on contact, which the
+# other two projections see.  The slack S and the rounding bound are the conservative test's own (the half-widths are exact
+# halves of sums it already forms), so a centre segment that truly meets the triangle always sets its cell, and the thin shell is
+# a subset of the conservative one by construction.
+# Degenerate triangles (nn < VOXEL_DEGENERATE) keep the conservative treatment: a needle below the area threshold can still be cut
+# by a centre line, and a superset there is harmless.  The owner of a wall cell is the smallest index of the triangles whose
+# *thin* test sets it.
+SHELL_MODES = ("box", "cross")
 WALL_VELOCITY_SOURCES = ("motion", "file")
 NO_OWNER = -1
 
 
 # ---- wall velocities of a mesh (conservative voxelisation only): the specification host/Shape3D.h and k_geom_mesh_nodes_vel repeat ----
-# Owner.  The owner of a NODE_BOUND cell is the triangle of smallest index whose conservative test sets the cell (the mask of
-# _voxel_triangle): a minimum over a set, so it does not depend on the order in which triangles are visited.  Where several
-# triangles overlap a cell the choice is arbitrary; the velocity field of a mesh is continuous across shared vertices, so another
+# Owner.  The owner of a NODE_BOUND cell is the triangle of smallest index whose test sets the cell (the mask of
+# _voxel_triangle: the conservative test, with shell="cross" the thin one): a minimum over a set, so it does not depend on the
+# order in which triangles are visited.  Where several triangles overlap a cell the choice is arbitrary; the velocity field of a mesh is continuous across shared vertices, so another
 # choice moves the value by the velocity gradient times a cell.
 # Weights.  float64 from the fp32 vertices, every operation rounded once, in the order written here, uncontracted.  Coordinates
 # are local to the cell's own corner, q_i = (double)v_i - (i, j, k) (exact for |v| <= VOXEL_COORD_MAX), the centre is c = (1/2, 1/2, 1/2).
@@ -148,9 +168,16 @@ def wall_velocity(w, W):
 
 
 class Shape3D:
-    def __init__(self, frames, dx, dy, dz, align, time=0.0, voxels="reference", wall_velocity=None):
+    shell = "box"                                         # (a class default: twins made without __init__ keep the conservative shell)
+
+    def __init__(self, frames, dx, dy, dz, align, time=0.0, voxels="reference", wall_velocity=None, shell="box"):
         if voxels not in VOXEL_MODES:
             raise ValueError("Shape3D: voxels is 'reference' or 'conservative'")
+        if shell not in SHELL_MODES:
+            raise ValueError("Shape3D: shell is 'box' or 'cross'")
+        if shell == "cross" and voxels != "conservative":
+            raise ValueError("Shape3D: shell='cross' needs voxels='conservative' (the thin shell is a filter inside its overlap test)")
+        self.shell = shell
         if wall_velocity is not None and wall_velocity not in WALL_VELOCITY_SOURCES:
             raise ValueError("Shape3D: wall_velocity is None, 'motion' or 'file'")
         if wall_velocity is not None and voxels != "conservative":
@@ -377,6 +404,20 @@ class Shape3D:
         if plane is not None:
             s = g + nd * pd
             m = m & ((s + c1) >= 0) & ((s + c2) <= 0)
+            if self.shell == "cross":                     # the centre cross: some projection sees the cell's centre inside, in depth too
+                val = lambda fn, x, y: (fn[0] * x + fn[1] * y) + fn[2]
+                xy = ((pa, pb), (pb, pd), (pd, pa))
+                nr = (na, nb, nd)
+                thin = np.zeros(m.shape, bool)
+                for k in range(3):
+                    if nr[(k + 2) % 3] == 0:
+                        continue
+                    H = 0.5 * (abs(nr[k]) + abs(nr[(k + 1) % 3]))
+                    hit = ((s + c1) >= H) & ((s + c2) <= -H)
+                    for fn in edges[k]:
+                        hit = hit & (val(fn, *xy[k]) >= 0.5 * (abs(fn[0]) + abs(fn[1])))
+                    thin = thin | hit
+                m = m & thin
         m = np.transpose(m, [(a, b, d).index(c) for c in range(3)])
         box = (slice(o[0], o[0] + n[0]), slice(o[1], o[1] + n[1]), slice(o[2], o[2] + n[2]))
         self.type[box][m] = NODE_BOUND
@@ -428,11 +469,13 @@ class Shape3D:
             self.wall_v = self._wall_velocities(g, idx, vel)
 
 
-def load_shape3d(path_or_text, dx, dy, dz, baseT=1.0, align=True, is_text=False, voxels="reference", wall_velocity=None, wall_T=0.0, time=0.0):
+def load_shape3d(path_or_text, dx, dy, dz, baseT=1.0, align=True, is_text=False, voxels="reference", wall_velocity=None, wall_T=0.0, time=0.0,
+                 shell="box"):
     """Grid3D(dx,dy,dz,baseT) + LoadFromFile + Prepare_CPU(time) for a Shape3D input -> (Nodes, Shape3D).  wall_velocity ("motion" /
-    "file", conservative voxelisation only) and wall_T: what the walls carry, see nodes_of."""
+    "file", conservative voxelisation only) and wall_T: what the walls carry, see nodes_of; shell ("box" / "cross", the latter with the
+    conservative voxelisation only): the thin shell."""
     text = path_or_text if is_text else open(path_or_text, "r").read()
-    sh = Shape3D(parse_shape3d(text), dx, dy, dz, align, time, voxels=voxels, wall_velocity=wall_velocity)
+    sh = Shape3D(parse_shape3d(text), dx, dy, dz, align, time, voxels=voxels, wall_velocity=wall_velocity, shell=shell)
     return nodes_of(sh, dx, dy, dz, baseT, sh.wall_v, wall_T), sh
 
 

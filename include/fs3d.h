@@ -100,6 +100,13 @@ enum {
                                  of the node types of the slab's own planes, under the single context's rules, and fs3d_fill_fresh_cells*
                                  run their collective form (the fresh-cell section below).  No effect on a single context; a lone slab
                                  of a larger grid, in no group, is still refused.  Any other value: FS3D_ERR_INVALID */
+    FS3D_OPT_MESH_SHELL = 11, /* which cells of the conservative voxelisation (FS3D_OPT_MESH_VOXELS set to 1) become NODE_BOUND, for every mesh entry
+                                 that voxelises (fs3d_update_nodes_shape3d, _vel, _slab, _vel_slab, fs3d_voxelize_shape3d_dev, _vel_dev).
+                                 0 (default): nothing changes anywhere -- every cell whose closed unit box a triangle touches.  1: the thin
+                                 shell -- of those, the cells whose centre cross (the three unit segments through the centre, one along each
+                                 axis) a triangle meets: closed for the 6-neighbourhood of the fill, about 0.55 of the cells (the mesh section
+                                 below).  A mesh entry called with 1 while FS3D_OPT_MESH_VOXELS is 0 fails with FS3D_ERR_INVALID before
+                                 anything is touched.  Any other value: FS3D_ERR_INVALID */
     FS3D_OPT_ERR_ORDER = 7   /* summation order of EvalDivError (fs3d_eval_div_error, fs3d_time_step with compute_error).  0 (default): the
                                  per-cell terms are summed in parallel (per workgroup, then over the workgroups; deterministic, equal to the
                                  CPU path to ~1e-12 relative).  1: they are summed one after the other in cell order, as the loop of
@@ -272,6 +279,18 @@ fs3d_status fs3d_shape2d_bottom(int dimx, int dimy, double dz, double depth, dou
  * before anything is launched, the context unchanged; the default mode keeps its 65536).  It has no scan lines: nothing is
  * refused after the kernels have run.  A triangle with two or three equal or collinear vertices sets the cells of its longest
  * edge; triangles and parts of triangles outside the grid are dropped.
+ *
+ * Thin shell (FS3D_OPT_MESH_SHELL set to 1, with FS3D_OPT_MESH_VOXELS set to 1).  The fill spreads over the 6-neighbourhood, so a
+ * shell only has to keep apart two neighbouring cell centres whose connecting line a triangle cuts.  With the option on, a
+ * triangle sets, of the cells its box test sets, those whose CENTRE CROSS it meets -- the three unit segments through the cell's
+ * centre, one parallel to each axis (the same float64 values and slack, compared with the half-widths of the segment instead of
+ * the box; cmc_fluid_solver_amd/shape3d.py states the rule and why it separates).  The shell of a closed mesh stays closed for
+ * the fill, is a subset of the conservative one with about 0.55 of its cells, and every cell that was fluid stays fluid.
+ * Degenerate triangles are treated as without the option.  In the _vel entries the owner of a wall cell is the triangle of
+ * smallest index whose thin test sets it.  The nodes equal those of shape3d.Shape3D(voxels="conservative", shell="cross") and of
+ * host/Shape3D.h with voxels = 1, shell = 1 byte for byte.  Every mesh entry that voxelises honours the option
+ * (fs3d_update_nodes_shape3d, _vel, _slab, _vel_slab, fs3d_voxelize_shape3d_dev, _vel_dev); with it set while
+ * FS3D_OPT_MESH_VOXELS is 0 they fail with FS3D_ERR_INVALID before anything is launched, the context unchanged.
  *
  * fs3d_voxelize_shape3d_dev: the seven SoA node arrays (ncell elements each, on the context's device; real = the context's
  * precision) are written on the context's stream; returns synchronised.  The context's geometry is not touched (it needs none).

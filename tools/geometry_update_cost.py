@@ -34,6 +34,13 @@ in one process, after a warm-up:
         (the conservative voxelisation, FS3D_OPT_MESH_VOXELS = 1, beside the default one on the same two grids: main_mesh_voxels;
         kernel rows: --kernel-stats CSV of a rocprofv3 --kernel-trace --stats run of `fs3d_run ... moving-mesh --watertight`)
 
+    python tools/geometry_update_cost.py --mesh --voxels conservative --shell box|cross [--repeats 24] [--out FILE]
+        (the thin shell, FS3D_OPT_MESH_SHELL = 1, against the conservative shell: main_mesh_shell -- ONE configuration per process, the
+        1280-face sphere watertight_cases.SINGLE[2] on its 120 x 151 x 120 grid breathing between x 1.0 and x 0.95, device time of
+        fs3d_update_nodes_shape3d after 4 warm-up calls; one line of JSON, appended to FILE where --out names one.  `box` never touches
+        the option, so FS3D_LIB_PATH may name the library of a commit that does not have it: run fresh processes alternating,
+        profiles/mesh_thin_shell_cost.txt)
+
 A moving Shape3D mesh: the voxelisation and flood fill on the device (fs3d_update_nodes_shape3d) against today's path.  The mesh is an
 icosphere of 1280 faces (642 vertices; the reference's heart_us_3D has 1294 triangles) breathing between two radii (x 1.0 and x 0.9), stretched to fill a
 grid of heart_us_3D's size, 128 x 160 x 128, and one of 256^3.  Everything runs in the driver, fs3d_run ... moving-mesh:
@@ -48,6 +55,7 @@ grid of heart_us_3D's size, 128 x 160 x 128, and one of 256^3.  Everything runs 
            adds the rows to the file of the --mesh run, which must exist
 """
 import argparse
+import copy
 import ctypes as C
 import json
 import os
@@ -473,6 +481,54 @@ def main_mesh_voxels(a):
     print("wrote", out_path)
 
 
+def main_mesh_shell(a):
+    """--mesh --voxels conservative --shell box|cross: one configuration, one process, one line of JSON."""
+    import torch
+    import watertight_cases as W
+    if not torch.cuda.is_available():
+        raise SystemExit("geometry_update_cost: no GPU (there is no CPU fallback)")
+    faces, r, dims = W.SINGLE[2]
+    sh, _ = W.sphere(faces, r)
+    g0, idx = sh.subframe(0.0)
+    centre = g0.mean(axis=0, dtype=np.float64)
+    meshes = [((g0 - centre) * k + centre).astype(np.float32) for k in (1.0, 0.95)]
+    nodes = shape3d_nodes(sh)
+    assert nodes.shape == dims, (nodes.shape, dims)
+    s = capi.Solver(nodes, capi.fluid_params(np.float32, 200.0, 0.72, 1.4), np.float32)
+    s.enable_timing(True)
+    s.set_option(capi.OPT_MESH_VOXELS, 1)
+    if a.shell == "cross":
+        s.set_option(capi.OPT_MESH_SHELL, 1)
+    dev, host = [], []
+    for k in range(a.repeats + 4):
+        t0 = time.perf_counter()
+        s.update_nodes_shape3d(meshes[k % 2], idx, 1.0)
+        ms = (time.perf_counter() - t0) * 1e3
+        if k >= 4:
+            dev.append(s.last_update_device_ms()); host.append(ms)
+    info = s.geometry_info()
+    tw = copy.copy(sh)                                       # the twin's grid of the last mesh: the fluid cells, and a check of the shell
+    tw.voxels, tw.shell = "conservative", a.shell
+    tw.build(meshes[(a.repeats + 3) % 2], idx)
+    assert info["bound_cells"] == int((tw.type == grids.NODE_BOUND).sum()), "the device's shell is not the twin's"
+    r = {"device": torch.cuda.get_device_name(0), "commit": a.commit or tree_commit(), "library": capi.LIB_PATH, "shell": a.shell,
+         "dims": list(dims), "faces": faces, "device_time": stats(dev), "update_nodes_shape3d": stats(host),
+         "bound_cells": info["bound_cells"], "fluid_cells": int((tw.type == grids.NODE_IN).sum()),
+         "fill_rounds": s.mesh_fill_rounds()}
+    s.close()
+    line = json.dumps(r)
+    print(line, flush=True)
+    if a.out != DEFAULT_OUT:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "a") as f:
+            f.write(line + "\n")
+
+
+def shape3d_nodes(sh):
+    from cmc_fluid_solver_amd import shape3d
+    return shape3d.nodes_of(sh, sh.dx, sh.dy, sh.dz, 1.0)
+
+
 def tree_commit():
     try:
         return subprocess.run(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], capture_output=True, text=True).stdout.strip() or None
@@ -492,6 +548,8 @@ def main():
     ap.add_argument("--mesh", action="store_true", help="the rows of the device voxeliser of Shape3D meshes (profiles/mesh_update_cost.json)")
     ap.add_argument("--voxels", default=None, choices=["conservative"],
                     help="--mesh: the conservative voxelisation beside the default one (profiles/mesh_update_cost_conservative.json)")
+    ap.add_argument("--shell", default=None, choices=["box", "cross"],
+                    help="--mesh --voxels conservative: one configuration of the thin-shell comparison (profiles/mesh_thin_shell_cost.txt)")
     ap.add_argument("--write-inputs", default=None, help="--mesh: write the mesh and config files of the two grids into this directory and stop")
     ap.add_argument("--kernel-stats", default=None, help="--mesh: ..._kernel_stats.csv of a rocprofv3 run of the driver; adds the kernel rows of --grid")
     ap.add_argument("--grid", default="heart_size_128x160x128", help="--mesh --kernel-stats: the grid the profiled run used")
@@ -501,6 +559,8 @@ def main():
     a = ap.parse_args()
     if a.extrude:
         return main_extrude(a)
+    if a.mesh and a.voxels and a.shell:
+        return main_mesh_shell(a)
     if a.mesh and a.voxels and not a.kernel_stats and not a.write_inputs:
         return main_mesh_voxels(a)
     if a.mesh:
