@@ -12,7 +12,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libfs3d_hip.so")
 SOURCES = ["fs3d_hip.hip", "fs3d_comm.hip", "kernels_line.hip", "kernels_pipe.hip", "kernels_part.hip", "kernels_geom.hip"]
 PUBLIC_HEADER = os.path.join(HERE, "..", "include", "fs3d.h")
-HEADERS = ["fs3d_common.h", "fs3d_buf.h", "fs3d_tables.h", "fs3d_device.h", "fs3d_rows.h", "fs3d_comm.h", PUBLIC_HEADER]
+HEADERS = ["fs3d_common.h", "fs3d_buf.h", "fs3d_tables.h", "fs3d_voxel.h", "fs3d_device.h", "fs3d_rows.h", "fs3d_comm.h", PUBLIC_HEADER]
 
 # -ffp-contract=off: no FMA contraction, the reference's CPU path rounds after every operation.
 # -fhip-fp32-correctly-rounded-divide-sqrt: IEEE fp32 division (the hipcc default, stated explicitly).
@@ -70,9 +70,11 @@ def build_driver(force=False, verbose=False):
     """The C++ command-line driver (host/fs3d_run.cpp) above the C ABI; g++, links libfs3d_hip.so."""
     build(force=False, verbose=verbose)
     host = os.path.join(HERE, "host")
-    deps = [os.path.join(host, f) for f in ("fs3d_run.cpp", "AdiSolver3D_hip.h", "Config.h", "Shape2D.h", "Shape3D.h", "SeaNetCDF.h", "Hdf5Min.h", "NetCDF3.h", "GridImage.h")] + [PUBLIC_HEADER, LIB]
+    deps = [os.path.join(host, f) for f in ("fs3d_run.cpp", "AdiSolver3D_hip.h", "Config.h", "Shape2D.h", "Shape3D.h", "SeaNetCDF.h", "Hdf5Min.h", "NetCDF3.h", "GridImage.h")] + \
+           [os.path.join(CSRC, "fs3d_voxel.h"), PUBLIC_HEADER, LIB]
     if force or _stale(DRIVER, deps):
-        cmd = [os.environ.get("CXX", "g++"), "-std=c++17", "-O2", "-Wall", "-I" + os.path.join(HERE, "..", "include"),
+        # -ffp-contract=off: host/Shape3D.h runs the voxel rule of csrc/fs3d_voxel.h, which rounds after every operation
+        cmd = [os.environ.get("CXX", "g++"), "-std=c++17", "-O2", "-Wall", "-ffp-contract=off", "-I" + os.path.join(HERE, "..", "include"),
                os.path.join(host, "fs3d_run.cpp"), "-o", DRIVER, "-L" + HERE, "-lfs3d_hip", "-lz", "-Wl,-rpath,$ORIGIN", "-Wl,-rpath,/opt/rocm/lib"]
         if verbose:
             print(" ".join(cmd))

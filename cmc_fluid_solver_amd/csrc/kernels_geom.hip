@@ -36,6 +36,7 @@
 
 #include "fs3d_common.h"
 #include "fs3d_comm.h"
+#include "fs3d_voxel.h"
 
 // counter words of one update (device, read back once)
 enum { GC_NSEG = 0 /* 0..2 */, GC_NBND = 3, GC_STALE = 4, GC_SHARED = 5, GC_LIST = 6, GC_MISMATCH = 7, GC_WORDS = 8 };
@@ -585,9 +586,10 @@ __global__ void __launch_bounds__(64) k_geom_raster_mesh(const float *__restrict
 }
 
 // ---- conservative voxelisation (FS3D_OPT_MESH_VOXELS = 1) -------------------------------------------------------------------------
-// k_geom_voxel_mesh: NODE_BOUND iff a triangle overlaps the cell's closed unit box -- Shape3D._voxel_setup / _voxel_triangle of
-// cmc_fluid_solver_amd/shape3d.py (where the rule, the slack and its derivation stand) and VoxelTriangle of host/Shape3D.h: fp32
-// vertices, every float64 operation theirs, in their order, rounded after each one.  One wave per triangle; the set-up (clipped bounding box, local
+// k_geom_voxel_mesh: NODE_BOUND iff a triangle overlaps the cell's closed unit box.  The rule -- set-up, column, cell test -- is
+// fs3d_voxel.h, which the host loader (host/Shape3D.h) runs as well: one C++ text, specified by Shape3D._voxel_setup /
+// _voxel_triangle of cmc_fluid_solver_amd/shape3d.py (where the slack and its derivation stand).  What is here belongs to the device:
+// the vertex loads, the strides, the loops, the stores.  One wave per triangle; the set-up (clipped bounding box, local
 // vertices, normal, the nine edge functions, the plane's two constants) is wave-uniform.  The three axes are renamed (a, b, d)
 // with d the depth axis -- the normal's dominant axis, so the columns of the (a, b) projection that pass its three edge functions
 // number about the triangle's area; the lanes stride over the columns of the clipped box.  A column takes its depth range from the
@@ -595,6 +597,9 @@ __global__ void __launch_bounds__(64) k_geom_raster_mesh(const float *__restrict
 // a degenerate triangle has no plane and walks the box's depth, along its smallest extent.  The only write is a byte store of
 // NODE_BOUND into an array preset to NODE_IN: idempotent, so order is free and no atomics are needed.  Every index lies inside
 // the clipped box; there is no scan line, no guard and no flag word.
+// The per-cell loop is neither vectorised nor interleaved: the cell test is one boolean and the store a plain predicated one, which
+// the loop vectoriser would take four cells of a column at a time -- four times the live float64 values (242 VGPRs with THIN, two
+// waves per SIMD) for columns that are a few cells deep.
 // THIN (FS3D_OPT_MESH_SHELL = 1): of the cells that pass, a non-degenerate triangle sets those whose centre cross it meets -- the
 // filter of shape3d.py (SHELL_MODES), on the values the conservative test has just computed; its half-widths are wave-uniform.
 // OWNER (the entries with wall velocities): every store of NODE_BOUND comes with an integer atomicMin of the triangle's index into
@@ -603,21 +608,6 @@ __global__ void __launch_bounds__(64) k_geom_raster_mesh(const float *__restrict
 // planes [own_x0, own_x0 + own_nx) of the grid only (an x-slab: dimx is the GLOBAL grid's and the bytes go to the global type array,
 // the owners of the slab's own cells to its own array; a single context: 0 and dimx): the atomicMin is issued inside that window,
 // at the index relative to its first plane.
-#define VOXEL_SLACK 5.8207660913467407e-11              // 2^-34
-#define VOXEL_DEGENERATE 5.9604644775390625e-08        // 2^-24
-#define VOXEL_COORD_MAX 4096.0f
-
-struct VoxEdge { double wa, wb, c; };
-
-__device__ __forceinline__ double vox_val(const VoxEdge &e, double x, double y) { return (e.wa * x + e.wb * y) + e.c; }
-__device__ __forceinline__ bool vox_pass(const VoxEdge &e, double x, double y) { return vox_val(e, x, y) >= 0.0; }
-// the thin shell: the centre of the unit square of a projection lies inside all three edges -- each value reaches its half-width
-__device__ __forceinline__ bool vox_centre(const VoxEdge (&e)[3], const double (&hw)[3], double x, double y)
-{
-    return vox_val(e[0], x, y) >= hw[0] && vox_val(e[1], x, y) >= hw[1] && vox_val(e[2], x, y) >= hw[2];
-}
-__device__ __forceinline__ double vox_sel(int c, double x, double y, double z) { return c == 0 ? x : (c == 1 ? y : z); }
-
 template <bool OWNER, bool THIN>
 __global__ void __launch_bounds__(64) k_geom_voxel_mesh(const float *__restrict__ vx, const float *__restrict__ vy, const float *__restrict__ vz,
                                                          const int *__restrict__ tri, int dimx, int dimy, int dimz, uint8_t *type, unsigned *owner,
@@ -628,126 +618,26 @@ __global__ void __launch_bounds__(64) k_geom_voxel_mesh(const float *__restrict_
     float p[3][3];
 #pragma unroll
     for (int i = 0; i < 3; i++) { p[i][0] = vx[iv[i]]; p[i][1] = vy[iv[i]]; p[i][2] = vz[iv[i]]; }
-    const int dims[3] = {dimx, dimy, dimz};
-    int o[3], n[3];
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-        const float mn = fminf(p[0][c], fminf(p[1][c], p[2][c])), mx = fmaxf(p[0][c], fmaxf(p[1][c], p[2][c]));
-        const int lo = max((int)ceilf(mn) - 1, 0), hi = min((int)floorf(mx), dims[c] - 1);         // cells i with i + 1 >= mn and i <= mx
-        if (lo > hi) return;                                                                       // (wave-uniform)
-        o[c] = lo; n[c] = hi - lo + 1;
-    }
-    // float64 from here on: the local vertices and the edges are exact
-    double q[3][3], amax = 0.0;
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-#pragma unroll
-        for (int c = 0; c < 3; c++) { q[i][c] = (double)p[i][c] - (double)o[c]; amax = fmax(amax, fabs(q[i][c])); }
-    const double S = (amax + 2.0) * VOXEL_SLACK;
-    const double e0x = q[1][0] - q[0][0], e0y = q[1][1] - q[0][1], e0z = q[1][2] - q[0][2];
-    const double e1x = -(q[0][0] - q[2][0]), e1y = -(q[0][1] - q[2][1]), e1z = -(q[0][2] - q[2][2]);
-    double nx = e0y * e1z - e0z * e1y, ny = e0z * e1x - e0x * e1z, nz = e0x * e1y - e0y * e1x;
-    const double nn = (nx * nx + ny * ny) + nz * nz;
-    const bool degenerate = !(nn >= VOXEL_DEGENERATE);
-    int d = 0;
-    if (degenerate) {
-        double ext[3];
-#pragma unroll
-        for (int c = 0; c < 3; c++) ext[c] = fmax(q[0][c], fmax(q[1][c], q[2][c])) - fmin(q[0][c], fmin(q[1][c], q[2][c]));
-        nx = 0.0; ny = 0.0; nz = 0.0;
-        double best = ext[0];
-        if (ext[1] < best) { d = 1; best = ext[1]; }
-        if (ext[2] < best) d = 2;
-    } else {
-        double best = fabs(nx);
-        if (fabs(ny) > best) { d = 1; best = fabs(ny); }
-        if (fabs(nz) > best) d = 2;
-    }
-    // the axes renamed: index 0, 1, 2 = a, b, d (cyclic, so orientation is kept)
-    const int a = d == 2 ? 0 : d + 1, b = d == 0 ? 2 : d - 1;
-    double t[3][3];
-#pragma unroll
-    for (int i = 0; i < 3; i++) { t[i][0] = vox_sel(a, q[i][0], q[i][1], q[i][2]); t[i][1] = vox_sel(b, q[i][0], q[i][1], q[i][2]); t[i][2] = vox_sel(d, q[i][0], q[i][1], q[i][2]); }
-    const double nr[3] = {vox_sel(a, nx, ny, nz), vox_sel(b, nx, ny, nz), vox_sel(d, nx, ny, nz)};
-    const int cnt_a = a == 0 ? n[0] : (a == 1 ? n[1] : n[2]), cnt_b = b == 0 ? n[0] : (b == 1 ? n[1] : n[2]), cnt_d = d == 0 ? n[0] : (d == 1 ? n[1] : n[2]);
+    VoxelSetup s;
+    if (!voxel_setup<THIN>(p, dimx, dimy, dimz, s)) return;                                        // (wave-uniform)
     const long long plane = (long long)dimy * dimz;
-    const long long sa = a == 0 ? plane : (a == 1 ? (long long)dimz : 1LL), sb = b == 0 ? plane : (b == 1 ? (long long)dimz : 1LL),
-                    sd = d == 0 ? plane : (d == 1 ? (long long)dimz : 1LL);
-    VoxEdge edge[3][3];
-#pragma unroll
-    for (int k = 0; k < 3; k++) {                           // projections (a, b), (b, d), (d, a)
-        const int A = k, B = (k + 1) % 3, C = (k + 2) % 3;
-#pragma unroll
-        for (int j = 0; j < 3; j++) {
-            const int v0 = j, v1 = (j + 1) % 3;
-            const double eA = t[v1][A] - t[v0][A], eB = t[v1][B] - t[v0][B];
-            const double wa = nr[C] >= 0.0 ? -eB : eB, wb = nr[C] >= 0.0 ? eA : -eA;              // the inward normal of the edge
-            double tmin = wa * t[0][A] + wb * t[0][B];
-            tmin = fmin(tmin, wa * t[1][A] + wb * t[1][B]);
-            tmin = fmin(tmin, wa * t[2][A] + wb * t[2][B]);
-            const double cmax = fmax(wa, 0.0) + fmax(wb, 0.0);
-            const double sl = S * (fabs(wa) + fabs(wb));
-            edge[k][j].wa = wa; edge[k][j].wb = wb; edge[k][j].c = (cmax - tmin) + sl;
-        }
-    }
-    const double na = nr[0], nb = nr[1], nd = nr[2];
-    double c1 = 0.0, c2 = 0.0;
-    if (!degenerate) {
-        const double t0 = (na * t[0][0] + nb * t[0][1]) + nd * t[0][2], t1 = (na * t[1][0] + nb * t[1][1]) + nd * t[1][2],
-                     t2 = (na * t[2][0] + nb * t[2][1]) + nd * t[2][2];
-        const double tmin = fmin(t0, fmin(t1, t2)), tmax = fmax(t0, fmax(t1, t2));
-        const double cmax = (fmax(na, 0.0) + fmax(nb, 0.0)) + fmax(nd, 0.0), cmin = (fmin(na, 0.0) + fmin(nb, 0.0)) + fmin(nd, 0.0);
-        const double sl = S * ((fabs(na) + fabs(nb)) + fabs(nd));
-        c1 = (cmax - tmin) + sl; c2 = (cmin - tmax) - sl;
-    }
-    // THIN: per projection k of third axis C, the half-widths of its three edge values and of the plane value, and n_C != 0
-    [[maybe_unused]] double hw[3][3], hn[3];
-    [[maybe_unused]] bool along[3];
-    if constexpr (THIN) {
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-#pragma unroll
-            for (int j = 0; j < 3; j++) hw[k][j] = 0.5 * (fabs(edge[k][j].wa) + fabs(edge[k][j].wb));
-            hn[k] = 0.5 * (fabs(nr[k]) + fabs(nr[(k + 1) % 3]));
-            along[k] = nr[(k + 2) % 3] != 0.0;
-        }
-    }
-    uint8_t *const base = type + (((long long)o[0] * dimy + o[1]) * dimz + o[2]);
-    const int ncol = cnt_a * cnt_b;                         // at most 8194^2
+    const long long sa = voxel_sel(s.a, plane, (long long)dimz, 1LL), sb = voxel_sel(s.b, plane, (long long)dimz, 1LL),
+                    sd = voxel_sel(s.d, plane, (long long)dimz, 1LL);
+    uint8_t *const base = type + (((long long)s.o[0] * dimy + s.o[1]) * dimz + s.o[2]);
+    const int cnt_b = s.cnt[1], ncol = s.cnt[0] * cnt_b;   // at most 8194^2
 #pragma unroll 1
     for (int col = lane; col < ncol; col += 64) {
         const int ia = col / cnt_b, ib = col - ia * cnt_b;
-        const double pa = (double)ia, pb = (double)ib;
-        if (!vox_pass(edge[0][0], pa, pb) || !vox_pass(edge[0][1], pa, pb) || !vox_pass(edge[0][2], pa, pb)) continue;
-        int k0 = 0, k1 = cnt_d - 1;
-        double g = 0.0;
-        if (!degenerate) {                                  // s + c1 >= 0 and s + c2 <= 0 for s = g + nd k
-            g = na * pa + nb * pb;
-            const double lo = (-c1 - g) / nd, hi = (-c2 - g) / nd, lim = 1048576.0;
-            k0 = max((int)floor(fmin(fmax(fmin(lo, hi), -lim), lim)) - 1, 0);
-            k1 = min((int)ceil(fmin(fmax(fmax(lo, hi), -lim), lim)) + 1, cnt_d - 1);
-        }
-        [[maybe_unused]] bool centre_d = false;             // THIN: the column's centre line (along d) passes inside the three edges
-        if constexpr (THIN) centre_d = along[0] && vox_centre(edge[0], hw[0], pa, pb);
+        VoxelColumn c;
+        if (!voxel_column<THIN>(s, ia, ib, c)) continue;
         uint8_t *const colp = base + ia * sa + ib * sb;
+#pragma clang loop vectorize(disable) interleave(disable)
 #pragma unroll 1
-        for (int k = k0; k <= k1; k++) {
-            const double pd = (double)k;
-            if (!vox_pass(edge[1][0], pb, pd) || !vox_pass(edge[1][1], pb, pd) || !vox_pass(edge[1][2], pb, pd)) continue;
-            if (!vox_pass(edge[2][0], pd, pa) || !vox_pass(edge[2][1], pd, pa) || !vox_pass(edge[2][2], pd, pa)) continue;
-            if (!degenerate) {
-                const double s = g + nd * pd;
-                if (!(s + c1 >= 0.0) || !(s + c2 <= 0.0)) continue;
-                if constexpr (THIN) {                       // one of the three centre segments meets the triangle: inside the edges, and in depth
-                    const double u1 = s + c1, u2 = s + c2;
-                    if (!(centre_d && u1 >= hn[0] && u2 <= -hn[0]) &&
-                        !(along[1] && u1 >= hn[1] && u2 <= -hn[1] && vox_centre(edge[1], hw[1], pb, pd)) &&
-                        !(along[2] && u1 >= hn[2] && u2 <= -hn[2] && vox_centre(edge[2], hw[2], pd, pa))) continue;
-                }
-            }
+        for (int k = c.k0; k <= c.k1; k++) {
+            if (!voxel_cell<THIN>(s, c, k)) continue;
             colp[k * sd] = FS3D_NODE_BOUND;
             if constexpr (OWNER) {
-                const int ix = o[0] + (a == 0 ? ia : (b == 0 ? ib : k)) - own_x0;                          // the cell's plane, in the window
+                const int ix = s.o[0] + (s.a == 0 ? ia : (s.b == 0 ? ib : k)) - own_x0;                    // the cell's plane, in the window
                 if (ix >= 0 && ix < own_nx) atomicMin(owner + (((colp - type) + k * sd) - own_x0 * plane), (unsigned)blockIdx.x);      // < own_nx * plane
             }
         }
@@ -859,43 +749,8 @@ __global__ void __launch_bounds__(256) k_geom_mesh_nodes(const uint8_t *__restri
 }
 
 // ---- walls that carry the mesh's velocity (fs3d_*_shape3d_vel) ---------------------------------------------------------------------
-// wall_weights / wall_velocity of cmc_fluid_solver_amd/shape3d.py (where the rule stands) and WallWeights / WallVelocity of
-// host/Shape3D.h: float64 from the fp32 vertices, every operation theirs, in their order, rounded after each one.
-struct D3 { double x, y, z; };
-__device__ __forceinline__ D3 d3_sub(D3 a, D3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ D3 d3_cross(D3 a, D3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-__device__ __forceinline__ double d3_dot(D3 a, D3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
-
-// the velocity of the triangle (q0, q1, q2) -- local to the cell's corner -- with vertex velocities W0, W1, W2 at the cell's centre
-__device__ __forceinline__ D3 wall_velocity(D3 q0, D3 q1, D3 q2, D3 W0, D3 W1, D3 W2)
-{
-    const D3 c = {0.5, 0.5, 0.5};
-    const D3 e0 = d3_sub(q1, q0), e1 = d3_sub(q2, q0), r = d3_sub(c, q0);
-    const D3 n = d3_cross(e0, e1);
-    const double nn = d3_dot(n, n);
-    double w0, w1, w2;
-    if (nn >= VOXEL_DEGENERATE) {
-        const double b1 = d3_dot(d3_cross(r, e1), n) / nn, b2 = d3_dot(d3_cross(e0, r), n) / nn, b0 = (1.0 - b1) - b2;
-        const double m0 = fmax(b0, 0.0), m1 = fmax(b1, 0.0), m2 = fmax(b2, 0.0);
-        const double s = (m0 + m1) + m2;
-        w0 = m0 / s; w1 = m1 / s; w2 = m2 / s;
-    } else {                                               // the longest edge, the first of equals
-        const D3 d0 = e0, d1 = d3_sub(q2, q1), d2 = d3_sub(q0, q2);
-        const double l0 = d3_dot(d0, d0), l1 = d3_dot(d1, d1), l2 = d3_dot(d2, d2);
-        int best = 0;
-        double l = l0;
-        if (l1 > l) { best = 1; l = l1; }
-        if (l2 > l) { best = 2; l = l2; }
-        const D3 a = best == 0 ? q0 : (best == 1 ? q1 : q2), d = best == 0 ? d0 : (best == 1 ? d1 : d2);
-        double t = 0.0;
-        if (l > 0.0) t = fmin(fmax(d3_dot(d3_sub(c, a), d) / l, 0.0), 1.0);
-        const double u = 1.0 - t;                          // on the edge's first end, t on its second, 0 on the third vertex
-        w0 = best == 0 ? u : (best == 2 ? t : 0.0);
-        w1 = best == 1 ? u : (best == 0 ? t : 0.0);
-        w2 = best == 2 ? u : (best == 1 ? t : 0.0);
-    }
-    return {(w0 * W0.x + w1 * W1.x) + w2 * W2.x, (w0 * W0.y + w1 * W1.y) + w2 * W2.y, (w0 * W0.z + w1 * W1.z) + w2 * W2.z};
-}
+// The rule is wall_velocity of fs3d_voxel.h, shared with host/Shape3D.h (WallVelocity) and specified by wall_weights / wall_velocity
+// of cmc_fluid_solver_amd/shape3d.py: float64 from the fp32 vertices, rounded after each operation.
 
 // k_geom_mesh_nodes with walls that move: a NODE_BOUND cell reads its owner (k_geom_voxel_mesh<true>), gathers that triangle's
 // three vertices and three velocities, evaluates the rule in float64 and stores v rounded once to R and T = wallT; every other

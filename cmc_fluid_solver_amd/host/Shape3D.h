@@ -7,10 +7,10 @@
 // File: frames; per frame: vertices, per vertex "x y z  vx vy vz", triangles, 3 indices each.  Frame duration 1/75 s; the
 // cycle length of a Shape3D run is Config::frame_time and GetFrame is always 0 (Grid3D.cpp:303-336).
 // Shape3D::voxels = 1 replaces the rasteriser (not the fill) by a conservative voxelisation, which the reference does not have: see
-// VoxelTriangle below and the derivation in cmc_fluid_solver_amd/shape3d.py.  Shape3D::shell = 1 keeps of that shell the cells whose centre
+// VoxelTriangle below, the rule in csrc/fs3d_voxel.h (shared with the kernels) and its derivation in cmc_fluid_solver_amd/shape3d.py.  Shape3D::shell = 1 keeps of that shell the cells whose centre
 // cross a triangle meets (the thin, 6-separating shell: the same file).
 // Shape3D::wall_velocity (conservative voxelisation only) gives the NODE_BOUND cells the velocity of the mesh, which the reference
-// reads per vertex, interpolates (Grid3D.cpp:915) and then drops in RasterPolygon / RasterLine: see WallWeights below.
+// reads per vertex, interpolates (Grid3D.cpp:915) and then drops in RasterPolygon / RasterLine: see WallVelocity below.
 // Deviations, on purpose (a third one, of the moving loop, stands at FillShape3DNodes below):
 //   * NODE_BOUND cells: the reference sets only their type; bc_vel / bc_temp keep whatever `new Node[]` left there
 //     (Grid3D.cpp:351-371, 818-838: SetData runs for NODE_IN / NODE_OUT only).  Here they read as zero-filled memory:
@@ -30,6 +30,7 @@
 #include <string>
 #include <vector>
 
+#include "../csrc/fs3d_voxel.h"
 #include "AdiSolver3D_hip.h"
 #include "Shape2D.h"
 
@@ -60,15 +61,12 @@ struct Shape3D {
     // cmc_fluid_solver_amd/shape3d.py (SHELL_MODES).  Set it before Load; Prepare(t) honours it.  Same value as FS3D_OPT_MESH_SHELL.
     int shell = 0;
     // What the NODE_BOUND cells carry.  0: v = 0 (the reference's run).  1 (`motion`) / 2 (`file`): the velocity of the mesh at the
-    // projection of the cell's centre onto the cell's owner triangle (WallWeights below), from the vertex velocities
+    // projection of the cell's centre onto the cell's owner triangle (WallVelocity below), from the vertex velocities
     // SubFrameVelocity gives for that source.  Needs voxels = 1.  Set it before Load; Prepare(t) honours it and keeps `owner` and
     // `cur`, which FillShape3DNodes reads.
     int wall_velocity = 0;
     std::vector<int> owner;                   // per cell: the smallest index of the triangles whose test (with shell = 1: the thin one) sets it, -1 off the walls
     Shape3DFrame cur;                         // the sub-frame of the last Prepare: vertices in grid coordinates, velocities, triangles
-    static constexpr double VOXEL_SLACK = 5.8207660913467407e-11;        // 2^-34: the derivation stands in cmc_fluid_solver_amd/shape3d.py
-    static constexpr double VOXEL_DEGENERATE = 5.9604644775390625e-08;   // 2^-24
-    static constexpr float VOXEL_COORD_MAX = 4096.0f;
 
     static float num(std::string tok) { std::replace(tok.begin(), tok.end(), ',', '.'); return (float)std::atof(tok.c_str()); }
 
@@ -184,62 +182,21 @@ struct Shape3D {
         Build(cur);
     }
 
-    // ---- wall velocities: wall_weights / wall_velocity of the twin, operation for operation -----------------------------------
-    // The weights of the triangle p at the centre of cell (i, j, k).  float64 from the fp32 vertices, every operation rounded once.
-    // q_i = (double)v_i - (i, j, k), c = (1/2, 1/2, 1/2), e0 = q1 - q0, e1 = q2 - q0, r = c - q0, n = e0 x e1, nn = (nx nx + ny ny) + nz nz.
-    // nn >= VOXEL_DEGENERATE: b1 = ((r x e1) . n) / nn, b2 = ((e0 x r) . n) / nn, b0 = (1 - b1) - b2 (the barycentric coordinates of
-    // the centre's orthogonal projection onto the plane), m_i = max(b_i, 0), w_i = m_i / ((m0 + m1) + m2).  Else the longest of the
-    // edges (0,1), (1,2), (2,0) by squared length, the first of equals: t = the parameter of the centre's projection onto it
-    // clamped to [0, 1] (0 for a zero length), 1 - t and t on its ends, 0 on the third vertex.
+    // ---- wall velocities: wall_velocity of csrc/fs3d_voxel.h (where the rule is stated; the twin: wall_weights / wall_velocity) ----
+    // The velocity of triangle t of the sub-frame `cur` at the centre of cell (i, j, k): float64, to be rounded once.
     // The owner of a cell -- the smallest index of the triangles whose conservative test sets it -- is arbitrary where several
     // overlap the cell; the velocity field of a mesh is continuous across shared vertices, so another choice moves the value by
     // the velocity gradient times a cell.
-    static void WallWeights(const float *const p[3], int i, int j, int k, double w[3])
-    {
-        const int ijk[3] = {i, j, k};
-        double q[3][3], e0[3], e1[3], r[3], n[3];
-        for (int v = 0; v < 3; v++)
-            for (int c = 0; c < 3; c++) q[v][c] = fd((double)p[v][c] - (double)ijk[c]);
-        for (int c = 0; c < 3; c++) { e0[c] = fd(q[1][c] - q[0][c]); e1[c] = fd(q[2][c] - q[0][c]); r[c] = fd(0.5 - q[0][c]); }
-        cross(e0, e1, n);
-        const double nn = dot(n, n);
-        if (nn >= VOXEL_DEGENERATE) {
-            double a[3], b[3];
-            cross(r, e1, a); cross(e0, r, b);
-            const double b1 = fd(dot(a, n) / nn), b2 = fd(dot(b, n) / nn), b0 = fd(fd(1.0 - b1) - b2);
-            const double m0 = std::max(b0, 0.0), m1 = std::max(b1, 0.0), m2 = std::max(b2, 0.0);
-            const double s = fd(fd(m0 + m1) + m2);
-            w[0] = fd(m0 / s); w[1] = fd(m1 / s); w[2] = fd(m2 / s);
-            return;
-        }
-        double d[3][3], l[3];
-        for (int e = 0; e < 3; e++) {
-            for (int c = 0; c < 3; c++) d[e][c] = fd(q[(e + 1) % 3][c] - q[e][c]);
-            l[e] = dot(d[e], d[e]);
-        }
-        int best = 0;
-        if (l[1] > l[0]) best = 1;
-        if (l[2] > l[best]) best = 2;
-        double t = 0.0;
-        if (l[best] > 0) {
-            const double rr[3] = {fd(0.5 - q[best][0]), fd(0.5 - q[best][1]), fd(0.5 - q[best][2])};
-            t = std::min(std::max(fd(dot(rr, d[best]) / l[best]), 0.0), 1.0);
-        }
-        w[0] = w[1] = w[2] = 0.0;
-        w[best] = fd(1.0 - t); w[(best + 1) % 3] = t;
-    }
-    // (w0 W0 + w1 W1) + w2 W2 per component at cell (i, j, k) of triangle t of the sub-frame `cur`: float64, to be rounded once
     void WallVelocity(int t, int i, int j, int k, double u[3]) const
     {
-        const int iv[3] = {cur.idx[3 * (size_t)t], cur.idx[3 * (size_t)t + 1], cur.idx[3 * (size_t)t + 2]};
-        float pv[3][3];
-        for (int v = 0; v < 3; v++) { pv[v][0] = cur.x[iv[v]]; pv[v][1] = cur.y[iv[v]]; pv[v][2] = cur.z[iv[v]]; }
-        const float *const p[3] = {pv[0], pv[1], pv[2]};
-        double w[3];
-        WallWeights(p, i, j, k, w);
-        const std::vector<float> *W[3] = {&cur.vx, &cur.vy, &cur.vz};
-        for (int c = 0; c < 3; c++)
-            u[c] = fd(fd(fd(w[0] * (double)(*W[c])[iv[0]]) + fd(w[1] * (double)(*W[c])[iv[1]])) + fd(w[2] * (double)(*W[c])[iv[2]]));
+        D3 q[3], W[3];
+        for (int v = 0; v < 3; v++) {
+            const int iv = cur.idx[3 * (size_t)t + v];
+            q[v] = {(double)cur.x[iv] - (double)i, (double)cur.y[iv] - (double)j, (double)cur.z[iv] - (double)k};
+            W[v] = {(double)cur.vx[iv], (double)cur.vy[iv], (double)cur.vz[iv]};
+        }
+        const D3 r = ::wall_velocity(q[0], q[1], q[2], W[0], W[1], W[2]);
+        u[0] = r.x; u[1] = r.y; u[2] = r.z;
     }
 
     // Build on a mesh given in grid coordinates (dimx, dimy, dimz set by the caller): what Prepare does with a sub-frame, for
@@ -339,123 +296,24 @@ private:
             p[0] = fl(p[0] + dp[0]); p[1] = fl(p[1] + dp[1]); p[2] = fl(p[2] + dp[2]);
         }
     }
-    // ---- conservative voxelisation: Shape3D._voxel_setup / _voxel_triangle of the twin, operation for operation ----------------
-    // fp32 vertices, everything from them in float64 (the local vertices and edges are exact there), rounded after each operation
-    struct VoxelEdge { double wa, wb, c; };
-    static double fd(double v) { volatile double x = v; return x; }                 // one rounding to double, no contraction
-    static void cross(const double a[3], const double b[3], double o[3])
+    // ---- conservative voxelisation: set-up, column and cell test of csrc/fs3d_voxel.h (where the rule is stated), serially -------
+    // THIN: the thin shell (shell = 1); a degenerate triangle keeps the conservative treatment inside the shared cell test
+    template <bool THIN>
+    void VoxelTriangle(const float (&p)[3][3], int t)
     {
-        o[0] = fd(fd(a[1] * b[2]) - fd(a[2] * b[1])); o[1] = fd(fd(a[2] * b[0]) - fd(a[0] * b[2])); o[2] = fd(fd(a[0] * b[1]) - fd(a[1] * b[0]));
-    }
-    static double dot(const double a[3], const double b[3]) { return fd(fd(fd(a[0] * b[0]) + fd(a[1] * b[1])) + fd(a[2] * b[2])); }
-    static double VoxelValue(const VoxelEdge &e, double x, double y) { return fd(fd(fd(e.wa * x) + fd(e.wb * y)) + e.c); }
-    static bool VoxelPass(const VoxelEdge &e, double x, double y) { return VoxelValue(e, x, y) >= 0; }
-    // the thin shell: the centre of the unit square of a projection lies inside all three edges -- each value reaches its half-width
-    static bool VoxelCentre(const VoxelEdge e[3], const double hw[3], double x, double y)
-    {
-        return VoxelValue(e[0], x, y) >= hw[0] && VoxelValue(e[1], x, y) >= hw[1] && VoxelValue(e[2], x, y) >= hw[2];
-    }
-    void VoxelTriangle(const float *const p[3], int t)
-    {
-        const int dims[3] = {dimx, dimy, dimz};
-        int o[3], n[3];
-        for (int c = 0; c < 3; c++) {
-            const float mn = std::min(p[0][c], std::min(p[1][c], p[2][c])), mx = std::max(p[0][c], std::max(p[1][c], p[2][c]));
-            const int lo = std::max((int)std::ceil(mn) - 1, 0), hi = std::min((int)std::floor(mx), dims[c] - 1);   // cells i with i + 1 >= mn and i <= mx
-            if (lo > hi) return;
-            o[c] = lo; n[c] = hi - lo + 1;
-        }
-        double q[3][3], amax = 0;
-        for (int i = 0; i < 3; i++)
-            for (int c = 0; c < 3; c++) { q[i][c] = fd((double)p[i][c] - (double)o[c]); amax = std::max(amax, std::fabs(q[i][c])); }
-        const double S = fd(fd(amax + 2.0) * VOXEL_SLACK);
-        double e[3][3];                                   // edges v0 -> v1, v1 -> v2, v2 -> v0
-        for (int j = 0; j < 3; j++)
-            for (int c = 0; c < 3; c++) e[j][c] = fd(q[(j + 1) % 3][c] - q[j][c]);
-        const double *e0 = e[0];
-        const double e1[3] = {-e[2][0], -e[2][1], -e[2][2]};
-        double nrm[3] = {fd(fd(e0[1] * e1[2]) - fd(e0[2] * e1[1])), fd(fd(e0[2] * e1[0]) - fd(e0[0] * e1[2])), fd(fd(e0[0] * e1[1]) - fd(e0[1] * e1[0]))};
-        const double nn = fd(fd(fd(nrm[0] * nrm[0]) + fd(nrm[1] * nrm[1])) + fd(nrm[2] * nrm[2]));
-        const bool degenerate = !(nn >= VOXEL_DEGENERATE);
-        int d = 0;
-        if (degenerate) {                                 // depth along the axis of the smallest extent
-            double ext[3];
-            for (int c = 0; c < 3; c++)
-                ext[c] = fd(std::max(q[0][c], std::max(q[1][c], q[2][c])) - std::min(q[0][c], std::min(q[1][c], q[2][c])));
-            nrm[0] = nrm[1] = nrm[2] = 0;
-            if (ext[1] < ext[0]) d = 1;
-            if (ext[2] < ext[d]) d = 2;
-        } else {                                          // depth along the normal's dominant axis
-            if (std::fabs(nrm[1]) > std::fabs(nrm[0])) d = 1;
-            if (std::fabs(nrm[2]) > std::fabs(nrm[d])) d = 2;
-        }
-        const int axes[3] = {(d + 1) % 3, (d + 2) % 3, d};
-        const int a = axes[0], b = axes[1];
-        VoxelEdge edge[3][3];
-        for (int k = 0; k < 3; k++) {                     // projections (a, b), (b, d), (d, a)
-            const int A = axes[k], B = axes[(k + 1) % 3], C = axes[(k + 2) % 3];
-            for (int j = 0; j < 3; j++) {
-                const double eA = e[j][A], eB = e[j][B];
-                const double wa = nrm[C] >= 0 ? -eB : eB, wb = nrm[C] >= 0 ? eA : -eA;       // the inward normal of the edge
-                double tmin = fd(fd(wa * q[0][A]) + fd(wb * q[0][B]));
-                for (int v = 1; v < 3; v++) tmin = std::min(tmin, fd(fd(wa * q[v][A]) + fd(wb * q[v][B])));
-                const double cmax = fd(std::max(wa, 0.0) + std::max(wb, 0.0));
-                const double sl = fd(S * fd(std::fabs(wa) + std::fabs(wb)));
-                edge[k][j] = VoxelEdge{wa, wb, fd(fd(cmax - tmin) + sl)};
-            }
-        }
-        const double na = nrm[a], nb = nrm[b], nd = nrm[d];
-        double c1 = 0, c2 = 0;
-        if (!degenerate) {
-            double tmin = 0, tmax = 0;
-            for (int v = 0; v < 3; v++) {
-                const double t = fd(fd(fd(na * q[v][a]) + fd(nb * q[v][b])) + fd(nd * q[v][d]));
-                tmin = v ? std::min(tmin, t) : t; tmax = v ? std::max(tmax, t) : t;
-            }
-            const double cmax = fd(fd(std::max(na, 0.0) + std::max(nb, 0.0)) + std::max(nd, 0.0));
-            const double cmin = fd(fd(std::min(na, 0.0) + std::min(nb, 0.0)) + std::min(nd, 0.0));
-            const double sl = fd(S * fd(fd(std::fabs(na) + std::fabs(nb)) + std::fabs(nd)));
-            c1 = fd(fd(cmax - tmin) + sl); c2 = fd(fd(cmin - tmax) - sl);
-        }
-        // shell = 1: per projection k of third axis C, the half-widths of its three edge values and of the plane value, and n_C != 0
-        const bool thin = shell == 1 && !degenerate;
-        const double nr[3] = {na, nb, nd};
-        double hw[3][3], hn[3];
-        bool along[3];
-        for (int k = 0; k < 3; k++) {
-            for (int j = 0; j < 3; j++) hw[k][j] = fd(0.5 * fd(std::fabs(edge[k][j].wa) + std::fabs(edge[k][j].wb)));
-            hn[k] = fd(0.5 * fd(std::fabs(nr[k]) + std::fabs(nr[(k + 1) % 3])));
-            along[k] = nr[(k + 2) % 3] != 0;
-        }
-        const size_t stride[3] = {(size_t)dimy * dimz, (size_t)dimz, 1};
-        const size_t base = id(o[0], o[1], o[2]);
-        for (int ia = 0; ia < n[a]; ia++)
-            for (int ib = 0; ib < n[b]; ib++) {
-                const double pa = (double)ia, pb = (double)ib;
-                if (!VoxelPass(edge[0][0], pa, pb) || !VoxelPass(edge[0][1], pa, pb) || !VoxelPass(edge[0][2], pa, pb)) continue;
-                int k0 = 0, k1 = n[d] - 1;
-                double g = 0;
-                if (!degenerate) {                        // s + c1 >= 0 and s + c2 <= 0 for s = g + nd k; one cell of margin each way
-                    g = fd(fd(na * pa) + fd(nb * pb));
-                    const double lo = fd(fd(-c1 - g) / nd), hi = fd(fd(-c2 - g) / nd), lim = 1048576.0;
-                    k0 = std::max((int)std::floor(std::min(std::max(std::min(lo, hi), -lim), lim)) - 1, 0);
-                    k1 = std::min((int)std::ceil(std::min(std::max(std::max(lo, hi), -lim), lim)) + 1, n[d] - 1);
-                }
-                for (int k = k0; k <= k1; k++) {
-                    const double pd = (double)k;
-                    if (!VoxelPass(edge[1][0], pb, pd) || !VoxelPass(edge[1][1], pb, pd) || !VoxelPass(edge[1][2], pb, pd)) continue;
-                    if (!VoxelPass(edge[2][0], pd, pa) || !VoxelPass(edge[2][1], pd, pa) || !VoxelPass(edge[2][2], pd, pa)) continue;
-                    if (!degenerate) {
-                        const double s = fd(g + fd(nd * pd));
-                        if (!(fd(s + c1) >= 0) || !(fd(s + c2) <= 0)) continue;
-                        if (thin) {                       // one of the three centre segments meets the triangle: inside the edges, and in depth
-                            const double u1 = fd(s + c1), u2 = fd(s + c2);
-                            if (!(along[0] && u1 >= hn[0] && u2 <= -hn[0] && VoxelCentre(edge[0], hw[0], pa, pb)) &&
-                                !(along[1] && u1 >= hn[1] && u2 <= -hn[1] && VoxelCentre(edge[1], hw[1], pb, pd)) &&
-                                !(along[2] && u1 >= hn[2] && u2 <= -hn[2] && VoxelCentre(edge[2], hw[2], pd, pa))) continue;
-                        }
-                    }
-                    const size_t cell = base + ia * stride[a] + ib * stride[b] + k * stride[d];
+        VoxelSetup s;
+        if (!voxel_setup<THIN>(p, dimx, dimy, dimz, s)) return;
+        const size_t plane = (size_t)dimy * dimz;
+        const size_t sa = voxel_sel(s.a, plane, (size_t)dimz, (size_t)1), sb = voxel_sel(s.b, plane, (size_t)dimz, (size_t)1),
+                     sd = voxel_sel(s.d, plane, (size_t)dimz, (size_t)1);
+        const size_t base = id(s.o[0], s.o[1], s.o[2]);
+        for (int ia = 0; ia < s.cnt[0]; ia++)
+            for (int ib = 0; ib < s.cnt[1]; ib++) {
+                VoxelColumn c;
+                if (!voxel_column<THIN>(s, ia, ib, c)) continue;
+                for (int k = c.k0; k <= c.k1; k++) {
+                    if (!voxel_cell<THIN>(s, c, k)) continue;
+                    const size_t cell = base + ia * sa + ib * sb + k * sd;
                     type[cell] = NODE_BOUND;
                     if (!owner.empty() && (owner[cell] < 0 || owner[cell] > t)) owner[cell] = t;
                 }
@@ -486,8 +344,12 @@ private:
                         throw std::runtime_error("Shape3D: a vertex coordinate is not finite or exceeds 4096 grid cells in magnitude (conservative voxelisation)");
         for (size_t q = 0; q + 2 < fr.idx.size(); q += 3) {
             const int i1 = fr.idx[q], i2 = fr.idx[q + 1], i3 = fr.idx[q + 2];
+            if (voxels == 1) {
+                const float p[3][3] = {{fr.x[i1], fr.y[i1], fr.z[i1]}, {fr.x[i2], fr.y[i2], fr.z[i2]}, {fr.x[i3], fr.y[i3], fr.z[i3]}};
+                if (shell == 1) VoxelTriangle<true>(p, (int)(q / 3)); else VoxelTriangle<false>(p, (int)(q / 3));
+                continue;
+            }
             const float p1[3] = {fr.x[i1], fr.y[i1], fr.z[i1]}, p2[3] = {fr.x[i2], fr.y[i2], fr.z[i2]}, p3[3] = {fr.x[i3], fr.y[i3], fr.z[i3]};
-            if (voxels == 1) { const float *const p[3] = {p1, p2, p3}; VoxelTriangle(p, (int)(q / 3)); continue; }
             RasterPolygon(p1, p2, p3);
             RasterLine(p1, p2); RasterLine(p1, p3); RasterLine(p3, p2);       // the edges as well, to cover holes
         }

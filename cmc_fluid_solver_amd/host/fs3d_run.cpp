@@ -30,7 +30,7 @@
 //   on the host, FS3D_OPT_MESH_SHELL = 1 on the device) -- still closed for the fill, about 0.55 of the wall cells, so more fluid; for the
 //   first geometry, every moving-mesh update (device, --host-voxels, --slab-voxels) and --grid-only alike.
 //   --wall-velocity motion|file (in_fmt Shape3D, needs --watertight): the NODE_BOUND cells carry the velocity of the mesh -- of the
-//   cell's owner triangle at the projection of the cell's centre (host/Shape3D.h WallWeights) -- in the first geometry and in every
+//   cell's owner triangle at the projection of the cell's centre (host/Shape3D.h WallVelocity) -- in the first geometry and in every
 //   moving-mesh update (UpdateGridShape3D with velocities: fs3d_update_nodes_shape3d_vel), so a moving wall pushes the fluid.
 //   `motion`: the vertices' displacement per frame over the frame's duration; `file`: the velocity columns of the input,
 //   interpolated as the reference does and taken as they are.  With --host-voxels the host loader computes the same arrays, bit for bit.

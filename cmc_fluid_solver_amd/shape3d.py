@@ -47,7 +47,8 @@ def parse_shape3d(text):
     return frames
 
 
-# ---- conservative voxelisation (voxels="conservative"): constants shared by host/Shape3D.h and csrc/kernels_geom.hip -------------
+# ---- conservative voxelisation (voxels="conservative"): the specification; its one C++ statement, constants included, is -----------
+# csrc/fs3d_voxel.h, which host/Shape3D.h and csrc/kernels_geom.hip both run
 # A cell becomes NODE_BOUND iff a triangle overlaps its closed unit box [i, i+1] x [j, j+1] x [k, k+1]: separating axes in the
 # Schwarz-Seidel form.  The bounding box is compared in grid coordinates, where nothing is rounded (floor / ceil of the fp32
 # vertices): its slack is zero.  Every other inequality is  f(p) = w.p + c >= 0  for an axis w (an edge normal of a projection, or
@@ -105,7 +106,8 @@ WALL_VELOCITY_SOURCES = ("motion", "file")
 NO_OWNER = -1
 
 
-# ---- wall velocities of a mesh (conservative voxelisation only): the specification host/Shape3D.h and k_geom_mesh_nodes_vel repeat ----
+# ---- wall velocities of a mesh (conservative voxelisation only): the specification of wall_velocity in csrc/fs3d_voxel.h, ----
+# which host/Shape3D.h and k_geom_mesh_nodes_vel share
 # Owner.  The owner of a NODE_BOUND cell is the triangle of smallest index whose test sets the cell (the mask of
 # _voxel_triangle: the conservative test, with shell="cross" the thin one): a minimum over a set, so it does not depend on the
 # order in which triangles are visited.  Where several triangles overlap a cell the choice is arbitrary; the velocity field of a mesh is continuous across shared vertices, so another
@@ -328,7 +330,7 @@ class Shape3D:
 
     # ---- conservative voxeliser ---------------------------------------------------------------------------------------
     def _voxel_setup(self, p):
-        """The wave-uniform part of k_geom_voxel_mesh for the triangle p[3][3] (fp32): None when its bounding box misses the grid,
+        """The set-up (voxel_setup of csrc/fs3d_voxel.h: wave-uniform in k_geom_voxel_mesh) for the triangle p[3][3] (fp32): None when its bounding box misses the grid,
         else (o, n, axes, edge functions [projection][edge] = (wA, wB, c), plane (na, nb, nd, c1, c2) or None), all float64."""
         dims = (self.dimx, self.dimy, self.dimz)
         o, n = [], []

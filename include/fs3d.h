@@ -274,7 +274,8 @@ fs3d_status fs3d_shape2d_bottom(int dimx, int dimy, double dz, double depth, dou
  * ever adds a cell.
  * Such a shell separates over the 26-neighbourhood: the 6-neighbour flood fill cannot cross the shell of a closed mesh.  It is up
  * to about three cells thick where the reference's is one or two, so the fluid volume is smaller than with the default.  The
- * nodes equal those of shape3d.Shape3D(voxels="conservative") and of host/Shape3D.h with voxels = 1 byte for byte, and are a
+ * nodes equal those of shape3d.Shape3D(voxels="conservative") and of host/Shape3D.h with voxels = 1 byte for byte (the host loader
+ * and the kernels share one C++ text of the rule, csrc/fs3d_voxel.h; the numpy twin is its specification), and are a
  * function of this call's mesh alone.  This mode admits coordinates of at most 4096 grid cells in magnitude (FS3D_ERR_INVALID
  * before anything is launched, the context unchanged; the default mode keeps its 65536).  It has no scan lines: nothing is
  * refused after the kernels have run.  A triangle with two or three equal or collinear vertices sets the cells of its longest

@@ -23,6 +23,8 @@ PINS = {
     "outside": ((646, 367), (1361, 1490)),
     "box_pipe_3D": ((120016, 118808), (941192, 941192)),
     "degenerate": ((114, 114), None),
+    "degenerate-yzx": ((114, 114), None),
+    "degenerate-zxy": ((114, 114), None),
 }
 RESTATED = ["sphere-20", "tetra", "outside", "sphere-320-small", "box_pipe_3D"]
 

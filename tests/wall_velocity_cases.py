@@ -11,7 +11,7 @@ import watertight_cases as W
 from cmc_fluid_solver_amd import grids, shape3d
 
 WALL_T = 0.625                     # not 0, not baseT: a wall temperature that went astray shows
-GPU_CASES = ["sphere-20", "sphere-320-small", "tetra", "box_pipe_3D", "ragged", "outside", "degenerate"]
+GPU_CASES = ["sphere-20", "sphere-320-small", "tetra", "box_pipe_3D", "ragged", "outside", "degenerate"] + list(W.DEGENERATE_ROTATED)
 CPU_OWNER_CASES = ["sphere-20", "tetra", "box_pipe_3D", "degenerate"]
 
 

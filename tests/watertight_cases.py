@@ -136,6 +136,11 @@ def degenerate_mesh():
     return g, np.arange(len(g)).reshape(-1, 3)
 
 
+# The degenerate mesh with its coordinates and its grid rotated: (x, y, z) -> (y, z, x) and (z, x, y).  Every triangle of DEGENERATE,
+# and the needle, has its smallest extent along z, or ties and takes x; rotated, the depth axis of a degenerate triangle is y as well.
+DEGENERATE_ROTATED = {"degenerate-yzx": (1, 2, 0), "degenerate-zxy": (2, 0, 1)}
+
+
 @functools.lru_cache(maxsize=None)
 def gpu_case(case):
     """(conservative twin, vertices in grid coordinates, triangles, centre cell or None) of a case of tests/test_gpu_mesh_watertight.py"""
@@ -149,8 +154,15 @@ def gpu_case(case):
         g, idx = degenerate_mesh()
         sh.build(g, idx)
         return sh, g, idx, None
+    if case in DEGENERATE_ROTATED:
+        perm = list(DEGENERATE_ROTATED[case])
+        sh = blank(tuple(DEGENERATE_DIMS[c] for c in perm))
+        g, idx = degenerate_mesh()
+        g = np.ascontiguousarray(g[:, perm])
+        sh.build(g, idx)
+        return sh, g, idx, None
     sh, g, idx, _ = MC.load_case({"ragged": "sphere-ragged", "outside": "sphere-outside"}.get(case, case))
     return conservative(sh, g, idx), g, idx, None
 
 
-GPU_CASES = ["sphere-20", "sphere-80", "sphere-320-small", "box_pipe_3D", "tetra", "ragged", "outside", "degenerate"]
+GPU_CASES = ["sphere-20", "sphere-80", "sphere-320-small", "box_pipe_3D", "tetra", "ragged", "outside", "degenerate"] + list(DEGENERATE_ROTATED)

@@ -37,9 +37,10 @@ BASE_T = 1.0
 
 
 def build_helper():
-    deps = [HELPER_SRC, os.path.join(ROOT, "cmc_fluid_solver_amd", "host", "Shape3D.h")]
+    deps = [HELPER_SRC, os.path.join(ROOT, "cmc_fluid_solver_amd", "host", "Shape3D.h"), os.path.join(ROOT, "cmc_fluid_solver_amd", "csrc", "fs3d_voxel.h")]
     if not os.path.exists(HELPER) or any(os.path.getmtime(d) > os.path.getmtime(HELPER) for d in deps):
-        subprocess.check_call([os.environ.get("CXX", "g++"), "-std=c++17", "-O2", "-Wall", "-I" + os.path.join(ROOT, "include"), HELPER_SRC, "-o", HELPER])
+        # -ffp-contract=off: the voxel rule of csrc/fs3d_voxel.h rounds after every operation
+        subprocess.check_call([os.environ.get("CXX", "g++"), "-std=c++17", "-O2", "-Wall", "-ffp-contract=off", "-I" + os.path.join(ROOT, "include"), HELPER_SRC, "-o", HELPER])
     return HELPER
 
 
