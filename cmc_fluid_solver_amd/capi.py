@@ -28,6 +28,10 @@ OPT_FRESH_CELLS = 9       # 1: every single-context update_nodes* keeps the node
 OPT_MESH_SHELL = 11       # the mesh entries, with the conservative voxelisation: 0 every cell whose box a triangle touches (default), 1 the thin shell
 MESH_SHELL = {"box": 0, "cross": 1}
 OPT_FRESH_CELLS_SLABS = 10  # 1: a slab of a group keeps that snapshot too (the update_nodes*_slab entries) and fill_fresh_cells* run collectively (default 0)
+OPT_OUTPUT_FILTER = 12    # the three GetLayer entries: 0 the reference's point sample (default), 1 the mean over the NODE_IN cells of the sample's box
+OUTPUT_FILTER = {"point": 0, "box": 1}
+OPT_OUTPUT_VECTOR = 13    # outV of the same entries: 0 the velocity (default), 1 the vorticity (layer_output.py is the rule of both options)
+OUTPUT_VECTOR = {"velocity": 0, "vorticity": 1}
 XSOLVE_AUTO, XSOLVE_PIPELINED, XSOLVE_REDUCED, XSOLVE_REDUCED_A2A = 0, 1, 2, 3
 
 # every function include/fs3d.h declares, in the header's order: name -> (restype, argtypes)

@@ -185,6 +185,8 @@ struct fs3d_ctx {
     int opt_mesh_shell = 0;                // FS3D_OPT_MESH_SHELL: 0 = the conservative shell as it is, 1 = its thin (6-separating) subset (k_geom_voxel_mesh<.., true>)
     int opt_fresh_cells = 0;               // FS3D_OPT_FRESH_CELLS: 1 = every single-context update keeps the node types of the geometry it replaces
     int opt_fresh_slabs = 0;               // FS3D_OPT_FRESH_CELLS_SLABS: 1 = a slab of a group keeps that snapshot too and fills collectively
+    int opt_out_filter = 0;                // FS3D_OPT_OUTPUT_FILTER: 1 = the GetLayer entries average the NODE_IN cells of every sample's box (k_get_layer_box)
+    int opt_out_vector = 0;                // FS3D_OPT_OUTPUT_VECTOR: 1 = their outV holds the vorticity (k_get_layer_box<R, true>)
     int opt_err_order = 0;                 // FS3D_OPT_ERR_ORDER: 1 = EvalDivError sums its per-cell terms serially in cell order (host), as the CPU path
     DevBuf<double> err_terms;              // ... one term per cell (device, allocated on first use)
     std::vector<double> err_terms_host;

@@ -107,6 +107,101 @@ __global__ void __launch_bounds__(256) k_get_layer(const R *__restrict__ U, cons
     }
 }
 
+// FS3D_OPT_OUTPUT_FILTER / FS3D_OPT_OUTPUT_VECTOR (no reference counterpart; the rule: layer_output.py): the sample (i, j, k) is the
+// mean over the NODE_IN cells of its box [x0, x1) x [y0, y1) x [z0, z1) of source cells -- lo = i*g/o, hi = max(lo + 1, (i+1)*g/o) per
+// axis -- and the cell (x0, y0, z0) itself where the box holds none.  `point` (filter 0 of the vorticity): every sample is that cell,
+// one lane per output k as in k_get_layer, no box is walked.
+// VORT: the three velocity quantities are the curl, central differences in R, on the NODE_IN cells whose six neighbours are in the
+// grid and not NODE_OUT; 0 on the other NODE_IN cells and the walls, 99999 on NODE_OUT cells.
+// One block = one output row i and the output rows j = blockIdx.y, + gridDim.y, ...; per j the output k go in groups of 256, one
+// lane per output k.  The source cells [zb, ze) under a group are walked in chunks of 256, lanes along the source k (unit stride):
+// a thread runs down the planes and rows of the box for its k with four double sums and a count in registers, the per-k partials
+// go through LDS and the lane of every output k adds the ones of its box.  For o <= g the boxes partition the axis, so every source
+// cell is read once (2 bytes of code and four reals); no atomics, plain cached loads (the next step reads `next` again).  The curl
+// reads its six neighbours through the cache (the k +- 1 ones are the neighbouring lanes' lines).  Double sums of at most 2^31
+// terms; the order is the kernel's own, the rule leaves it free.  Whole-grid contexts only (get_layer_entry refuses slabs).
+template <typename R, bool VORT>
+__global__ void __launch_bounds__(256) k_get_layer_box(const uint16_t *__restrict__ code, const R *__restrict__ U, const R *__restrict__ V,
+                                                        const R *__restrict__ W, const R *__restrict__ T, int dimx, int dimy, int dimz,
+                                                        int odx, int ody, int odz, int point, R two_dx, R two_dy, R two_dz,
+                                                        R *__restrict__ outV, double *__restrict__ outT)
+{
+    __shared__ double sq[4][256];
+    __shared__ int sn[256];
+    const long long plane = (long long)dimy * dimz;
+    const int t = (int)threadIdx.x;
+    auto box_lo = [](int i, int g, int o) { return (int)((long long)i * g / o); };
+    auto box_hi = [&](int i, int lo, int g, int o) { const int h = (int)((long long)(i + 1) * g / o); return h < lo + 1 ? lo + 1 : h; };
+    auto type_of = [&](long long l) { return (code[l] >> CODE_TYPE_SHIFT) & 3; };
+    // (a, b, c) of cell l = (x, y, z), whose type is ty
+    auto vec_of = [&](long long l, int x, int y, int z, int ty, R &a, R &b, R &c) __attribute__((always_inline)) {
+        if (!VORT) { a = U[l]; b = V[l]; c = W[l]; return; }
+        a = b = c = ty == FS3D_NODE_OUT ? R(99999.0f) : R(0);
+        if (ty != FS3D_NODE_IN || x < 1 || x > dimx - 2 || y < 1 || y > dimy - 2 || z < 1 || z > dimz - 2) return;
+        if (type_of(l - plane) == FS3D_NODE_OUT || type_of(l + plane) == FS3D_NODE_OUT || type_of(l - dimz) == FS3D_NODE_OUT ||
+            type_of(l + dimz) == FS3D_NODE_OUT || type_of(l - 1) == FS3D_NODE_OUT || type_of(l + 1) == FS3D_NODE_OUT) return;
+        a = (W[l + dimz] - W[l - dimz]) / two_dy - (V[l + 1] - V[l - 1]) / two_dz;
+        b = (U[l + 1] - U[l - 1]) / two_dz - (W[l + plane] - W[l - plane]) / two_dx;
+        c = (V[l + plane] - V[l - plane]) / two_dx - (U[l + dimz] - U[l - dimz]) / two_dy;
+    };
+    const int i = (int)blockIdx.x;
+    const int x0 = box_lo(i, dimx, odx), x1 = box_hi(i, x0, dimx, odx);
+    for (int j = (int)blockIdx.y; j < ody; j += (int)gridDim.y) {
+        const int y0 = box_lo(j, dimy, ody), y1 = box_hi(j, y0, dimy, ody);
+        for (long long kg = 0; kg < odz; kg += 256) {          // (64-bit: odz may lie within 256 of 2^31)
+            const int klast = (int)(kg + 256 < odz ? kg + 256 : odz) - 1;
+            const bool kout = kg + t < odz;
+            const int ko = kout ? (int)kg + t : klast;
+            const int z0 = box_lo(ko, dimz, odz), z1 = box_hi(ko, z0, dimz, odz);
+            // the group's source cells, block-uniform; `point`: none are walked, every lane takes the one cell of its own output k below
+            const int zb = box_lo((int)kg, dimz, odz), zl = box_lo(klast, dimz, odz), ze = point ? zb : box_hi(klast, zl, dimz, odz);
+            double acc[4] = {0.0, 0.0, 0.0, 0.0};
+            int n = 0;
+            for (int cb = zb; cb < ze; cb += 256) {
+                const int z = cb + t;
+                double s[4] = {0.0, 0.0, 0.0, 0.0};
+                int m = 0;
+                if (z < ze)
+                    for (int x = x0; x < x1; x++)
+                        for (int y = y0; y < y1; y++) {
+                            const long long l = (long long)x * plane + (long long)y * dimz + z;
+                            if (type_of(l) != FS3D_NODE_IN) continue;
+                            R a, b, c;
+                            vec_of(l, x, y, z, FS3D_NODE_IN, a, b, c);
+                            s[0] += (double)a; s[1] += (double)b; s[2] += (double)c; s[3] += (double)T[l];
+                            m++;
+                        }
+#pragma unroll
+                for (int q = 0; q < 4; q++) sq[q][t] = s[q];
+                sn[t] = m;
+                __syncthreads();
+                if (kout) {
+                    const int e = z1 < cb + 256 ? z1 : cb + 256;
+                    for (int zz = z0 > cb ? z0 : cb; zz < e; zz++) {
+#pragma unroll
+                        for (int q = 0; q < 4; q++) acc[q] += sq[q][zz - cb];
+                        n += sn[zz - cb];
+                    }
+                }
+                __syncthreads();
+            }
+            if (!kout) continue;
+            const long long ind = ((long long)i * ody + j) * odz + ko;
+            if (n) {
+                const double d = (double)n;
+                outV[3 * ind] = (R)(acc[0] / d); outV[3 * ind + 1] = (R)(acc[1] / d); outV[3 * ind + 2] = (R)(acc[2] / d);
+                outT[ind] = acc[3] / d;
+            } else {                                       // no fluid in the box, or `point`: the point sample (on a wall, or the stamp)
+                const long long l = (long long)x0 * plane + (long long)y0 * dimz + z0;
+                R a, b, c;
+                vec_of(l, x0, y0, z0, type_of(l), a, b, c);
+                outV[3 * ind] = a; outV[3 * ind + 1] = b; outV[3 * ind + 2] = c;
+                outT[ind] = (double)T[l];
+            }
+        }
+    }
+}
+
 // TimeLayer3D::EvalDivError (TimeLayer3D.h:595-641): per-cell FTYPE face sums, double
 // accumulation.  Wave64 shuffle reduction, one partial (sum,count) pair per block;
 // the partials are summed in a fixed order by k_div_final, so the result is
@@ -409,6 +504,12 @@ extern "C" fs3d_status fs3d_set_option(fs3d_ctx *c, int option, int value)
     case FS3D_OPT_FRESH_CELLS_SLABS:
         if (value != 0 && value != 1) return fail(c, FS3D_ERR_INVALID, "bad fresh-cells-on-slabs value (0: off, 1: a slab of a group keeps the snapshot and fills with its neighbours)");
         c->opt_fresh_slabs = value; return FS3D_OK;
+    case FS3D_OPT_OUTPUT_FILTER:
+        if (value != 0 && value != 1) return fail(c, FS3D_ERR_INVALID, "bad output filter id (0: the reference's point sample, 1: the mean over the fluid cells of the sample's box)");
+        c->opt_out_filter = value; return FS3D_OK;
+    case FS3D_OPT_OUTPUT_VECTOR:
+        if (value != 0 && value != 1) return fail(c, FS3D_ERR_INVALID, "bad output vector id (0: the velocity, 1: the vorticity)");
+        c->opt_out_vector = value; return FS3D_OK;
     case FS3D_OPT_XSOLVE:
         if (value < 0 || value > 3) return fail(c, FS3D_ERR_INVALID, "bad cross-slab X solve id");
         c->opt_xsolve = value; return FS3D_OK;
@@ -1189,6 +1290,7 @@ extern "C" fs3d_status fs3d_synchronize(fs3d_ctx *c)
 // `local`: the slab's own planes are the whole source (fs3d_get_layer: x = i*dimx/odx, rows [0, odx)); else the slab owns the rows
 // of the GLOBAL output whose source plane it holds.  `dev`: outV / outT are on the context's device, the kernel writes them and
 // the call returns after the enqueue; else the owned samples go through the staging buffer and the call returns synchronised.
+// FS3D_OPT_OUTPUT_FILTER / FS3D_OPT_OUTPUT_VECTOR: k_get_layer_box in place of k_get_layer, everything around it as it is.
 template <typename R>
 static fs3d_status get_layer_impl(fs3d_ctx *c, R *outV, double *outT, int odx, int ody, int odz, bool local, bool dev, int rows[2])
 {
@@ -1218,9 +1320,20 @@ static fs3d_status get_layer_impl(fs3d_ctx *c, R *outV, double *outT, int odx, i
     if (n) {
         R *kV = dev ? dV : (R *)c->gl_stage;
         double *kT = dev ? dT : (double *)((char *)c->gl_stage + vbytes);
-        hipLaunchKernelGGL((k_get_layer<R>), dim3((unsigned)(i1 - i0), grid_for(po, 1024)), dim3(256), 0, c->stream,
-                           (const R *)fld<R>(c, b, 0), (const R *)fld<R>(c, b, 1), (const R *)fld<R>(c, b, 2), (const R *)fld<R>(c, b, 3),
-                           x_offset, c->dimx, c->plane, c->dimy, c->dimz, gx, odx, ody, odz, i0, i1, kV, kT);
+        const R *const F[4] = {fld<R>(c, b, 0), fld<R>(c, b, 1), fld<R>(c, b, 2), fld<R>(c, b, 3)};
+        if (c->opt_out_filter || c->opt_out_vector) {          // a whole-grid context (get_layer_entry): i0 = 0, i1 = odx
+            const dim3 grid((unsigned)odx, (unsigned)std::min(ody, 65535));
+            const R two_dx = R(2) * (R)c->gdx, two_dy = R(2) * (R)c->gdy, two_dz = R(2) * (R)c->gdz;
+            const int point = c->opt_out_filter ? 0 : 1;
+            if (c->opt_out_vector)
+                hipLaunchKernelGGL((k_get_layer_box<R, true>), grid, dim3(256), 0, c->stream, (const uint16_t *)c->code, F[0], F[1], F[2], F[3],
+                                   c->dimx, c->dimy, c->dimz, odx, ody, odz, point, two_dx, two_dy, two_dz, kV, kT);
+            else
+                hipLaunchKernelGGL((k_get_layer_box<R, false>), grid, dim3(256), 0, c->stream, (const uint16_t *)c->code, F[0], F[1], F[2], F[3],
+                                   c->dimx, c->dimy, c->dimz, odx, ody, odz, point, two_dx, two_dy, two_dz, kV, kT);
+        } else
+            hipLaunchKernelGGL((k_get_layer<R>), dim3((unsigned)(i1 - i0), grid_for(po, 1024)), dim3(256), 0, c->stream, F[0], F[1], F[2], F[3],
+                               x_offset, c->dimx, c->plane, c->dimy, c->dimz, gx, odx, ody, odz, i0, i1, kV, kT);
         HIPCHK(c, hipGetLastError());
         if (!dev) {
             HIPCHK(c, hipMemcpyAsync(dV, kV, (size_t)3 * n * sizeof(R), hipMemcpyDeviceToHost, c->stream));
@@ -1240,6 +1353,9 @@ static fs3d_status get_layer_entry(fs3d_ctx *c, const char *what, void *outV, do
     if (!c || !outV || !outT || (!local && !rows)) return c ? fail(c, FS3D_ERR_INVALID, std::string(what) + ": NULL destination") : FS3D_ERR_INVALID;
     if (!c->have_nodes) return fail(c, FS3D_ERR_INVALID, std::string(what) + ": upload nodes first");
     if (odx < 0 || ody < 0 || odz < 0) return fail(c, FS3D_ERR_INVALID, std::string(what) + ": negative output dims");
+    if ((c->opt_out_filter || c->opt_out_vector) && (c->x_offset != 0 || c->dimx != c->dimx_global || c->comm || c->local || c->nranks > 1))
+        return fail(c, FS3D_ERR_UNSUPPORTED, std::string(what) + ": FS3D_OPT_OUTPUT_FILTER / FS3D_OPT_OUTPUT_VECTOR on an x-slab or a member of a group "
+                                             "(a box can straddle a cut and the curl needs the neighbour's planes)");
     HIPCHK(c, hipSetDevice(c->device));
     return c->prec == FS3D_F32 ? get_layer_impl<float>(c, (float *)outV, outT, odx, ody, odz, local, dev, rows)
                                : get_layer_impl<double>(c, (double *)outV, outT, odx, ody, odz, local, dev, rows);

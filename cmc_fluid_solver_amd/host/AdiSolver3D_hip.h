@@ -139,6 +139,13 @@ public:
     void SetMeshVoxels(int mode) { chk(fs3d_set_option(ctx_, FS3D_OPT_MESH_VOXELS, mode)); }
     // FS3D_OPT_MESH_SHELL for the same calls: 0 the conservative shell as it is, 1 its thin subset (needs SetMeshVoxels(1))
     void SetMeshShell(int mode) { chk(fs3d_set_option(ctx_, FS3D_OPT_MESH_SHELL, mode)); }
+    // FS3D_OPT_OUTPUT_FILTER for the GetLayer / GetLayerRows calls that follow: 0 the reference's point sample, 1 the mean over the
+    // NODE_IN cells of every sample's box of source cells (the point sample where a box holds none).  While it is not 0 the calls
+    // of a slab solver throw (FS3D_ERR_UNSUPPORTED)
+    void SetOutputFilter(int mode) { chk(fs3d_set_option(ctx_, FS3D_OPT_OUTPUT_FILTER, mode)); }
+    // FS3D_OPT_OUTPUT_VECTOR for the same calls: 0 resVel holds the velocity, 1 the vorticity (central differences on the NODE_IN
+    // cells whose six neighbours are no NODE_OUT cells, 99999 on NODE_OUT cells, 0 elsewhere); slab solvers throw as above
+    void SetOutputVector(int mode) { chk(fs3d_set_option(ctx_, FS3D_OPT_OUTPUT_VECTOR, mode)); }
     // FS3D_OPT_FRESH_CELLS: with it on, every UpdateGrid* call of a single-GPU solver keeps the node types of the geometry it
     // replaces, and FillFreshCells, called directly after the update and before UpdateBoundaries, gives every cell of `cur` that
     // the update turned NODE_IN the mean of its fluid neighbours (fs3d_fill_fresh_cells; no reference

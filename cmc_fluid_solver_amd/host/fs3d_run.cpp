@@ -1,5 +1,5 @@
 // Command-line driver: the reference's FluidSolver3D main (FluidSolver3D/FluidSolver3D.cpp:60-330) on top of
-// libfs3d_hip.so.   fs3d_run <input data> <output prefix> <config> [align] [GPU [n]] [double] [moving [--host-extrusion] [--time-geometry]] [moving-mesh [--host-voxels | --slab-voxels] [--time-geometry] [--time-both]] [--time-output] [--steps N] [--same-device] [--grid-only FILE [--grid-time T]] [--watertight [--thin-shell] [--wall-velocity motion|file]] [--wall-temperature T] [--fresh-cells | --slab-fresh-cells]
+// libfs3d_hip.so.   fs3d_run <input data> <output prefix> <config> [align] [GPU [n]] [double] [moving [--host-extrusion] [--time-geometry]] [moving-mesh [--host-voxels | --slab-voxels] [--time-geometry] [--time-both]] [--time-output] [--steps N] [--same-device] [--grid-only FILE [--grid-time T]] [--watertight [--thin-shell] [--wall-velocity motion|file]] [--wall-temperature T] [--fresh-cells | --slab-fresh-cells] [--output-filter point|box]
 //   * reads the config (host/Config.h) and a Shape2D, Shape3D or SeaNetCDF geometry (host/Shape2D.h, Shape3D.h, SeaNetCDF.h), prints the grid summary lines
 //     the reference prints ("Grid = X x Y x Z", "NODE_IN points = ..."),
 //   * runs the same loop: dt = cycle length / (frames * time_steps), UpdateBoundaries + TimeStep per step with the
@@ -49,6 +49,11 @@
 //   fills directly after its update and before UpdateBoundaries -- a collective call, the slabs exchange a plane of fields and round
 //   tags per round.  The results and the `Fresh cells:` line (sums over the ranks, the group's rounds) equal the single-GPU run's.
 //   With one GPU it is --fresh-cells.
+// --output-filter point|box: `box` calls SetOutputFilter(1) before the loop -- every sample of a record is the mean over the NODE_IN cells of
+//   its box of source cells instead of one cell of it (FS3D_OPT_OUTPUT_FILTER; walls and the outside show only where a box holds no
+//   fluid); `point`, the default, is the reference's sample.  With an output grid at least as fine as the grid the two are the same
+//   bytes.  `box` is refused with GPU n, n > 1, when the arguments are read: a box can straddle the cut between two x-slabs.
+//   (The vorticity, FS3D_OPT_OUTPUT_VECTOR, has no word: the result file's variables are the reference's u, v, w, T.)
 // --time-output: one closing line, the host clock per output record around the GetLayer call (GPU n: rank 0's call and the barrier that
 //   completes the record) and around AppendLayer, with the number of records.
 // There is no CPU backend here: without a GPU the run stops with the library's error.
@@ -92,7 +97,7 @@ struct RunOptions {
     bool moving = false, host_extrusion = false, moving_mesh = false, host_voxels = false, slab_voxels = false, time_geometry = false, time_both = false, time_output = false;
     double grid_time = -1, wall_T = 0;
     int wall_velocity = 0;                             // 0: walls at rest; 1: motion; 2: file (Shape3D::wall_velocity)
-    bool has_wall_T = false, fresh_cells = false, slab_fresh_cells = false;
+    bool has_wall_T = false, fresh_cells = false, slab_fresh_cells = false, output_box = false;
     int nslabs = 1, device = 0;
     long max_steps = -1;
     std::string grid_only;
@@ -186,6 +191,7 @@ static int run(const std::string &data, const std::string &prefix, const fs3d::C
     if (o.watertight) solver.SetMeshVoxels(1);           // the updates voxelise as the host loader did
     if (o.thin_shell) solver.SetMeshShell(1);
     if (o.fresh_cells) solver.SetFreshCells(true);
+    if (o.output_box) solver.SetOutputFilter(1);
     std::printf("Segments: %i %i %i (x, y, z)\n", solver.numSegs[0], solver.numSegs[1], solver.numSegs[2]);
 
     const int frames = geo.frames;                                     // FluidSolver3D.cpp:194-195
@@ -489,7 +495,7 @@ static int run_slabs(fs3d::Grid3D<FTYPE> &grid, fs3d::Grid2D &g2, fs3d::Shape3D 
 int main(int argc, char **argv)
 {
     if (argc < 4) {
-        std::printf("Usage: %s <input data> <output prefix> <config file> [align] [GPU [n]] [double] [--steps N] [moving [--host-extrusion] [--time-geometry]] [moving-mesh [--host-voxels | --slab-voxels] [--time-geometry] [--time-both]] [--time-output] [--grid-only FILE [--grid-time T]] [--grid-images] [--watertight [--thin-shell] [--wall-velocity motion|file]] [--wall-temperature T] [--fresh-cells | --slab-fresh-cells]\n", argv[0]);
+        std::printf("Usage: %s <input data> <output prefix> <config file> [align] [GPU [n]] [double] [--steps N] [moving [--host-extrusion] [--time-geometry]] [moving-mesh [--host-voxels | --slab-voxels] [--time-geometry] [--time-both]] [--time-output] [--grid-only FILE [--grid-time T]] [--grid-images] [--watertight [--thin-shell] [--wall-velocity motion|file]] [--wall-temperature T] [--fresh-cells | --slab-fresh-cells] [--output-filter point|box]\n", argv[0]);
         return 0;
     }
     try {
@@ -529,6 +535,11 @@ int main(int argc, char **argv)
             }
             else if (s == "--fresh-cells") o.fresh_cells = true;
             else if (s == "--slab-fresh-cells") o.fresh_cells = o.slab_fresh_cells = true;
+            else if (s == "--output-filter") {
+                const std::string w = a + 1 < argc ? argv[++a] : "";
+                if (w != "point" && w != "box") throw std::runtime_error("--output-filter: point or box");
+                o.output_box = w == "box";
+            }
             else if (s == "--time-both") o.time_both = true;
             else if (s == "--host-extrusion") o.host_extrusion = true;
             else if (s == "--time-geometry") o.time_geometry = true;
@@ -538,6 +549,9 @@ int main(int argc, char **argv)
             else if (s == "--grid-images") o.grid_images = true;       // <prefix>_grid_3d/<k>.bmp: the node types, one image per z-slice
             // transpose, decompose: accepted, no effect
         }
+        if (o.output_box && o.nslabs > 1)
+            throw std::runtime_error("--output-filter box: single GPU only (with GPU n the grid is cut into x-slabs, a sample's box of source cells can "
+                                     "straddle a cut, and the library refuses filtered records on a slab)");
         return o.dbl ? run<double>(argv[1], argv[2], cfg, o) : run<float>(argv[1], argv[2], cfg, o);
     } catch (std::exception &e) {
         std::fprintf(stderr, "\n\nCaught exception:\n%s\n\nTerminating...\n", e.what());     // FluidSolver3D.cpp:313-318

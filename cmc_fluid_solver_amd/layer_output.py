@@ -1,0 +1,152 @@
+"""Filtered and derived result records: what fs3d_get_layer, fs3d_get_layer_rows and fs3d_get_layer_dev return while
+FS3D_OPT_OUTPUT_FILTER or FS3D_OPT_OUTPUT_VECTOR is set.
+
+layer_output is the definition of the rule; k_get_layer_box (csrc/fs3d_hip.hip) is held to it -- bit for bit wherever the double
+sums are exact, to the rounding of one sum elsewhere.  The reference has no counterpart: its FilterToArrays (TimeLayer3D.h:819-924)
+is the point sample, which is filter 0 with vector 0 here.
+
+The source is `next` after the 99999 stamp on the NODE_OUT cells (Solver3D.cpp:21-25); the types are the context's current ones.
+
+Box of output index i on an axis of g source cells and o samples (o = 0: o = g): lo = i*g // o, hi = max(lo + 1, (i+1)*g // o).
+For o <= g the boxes partition the axis and each starts at the reference's sample cell; for o >= g every box is that one cell.
+
+Per cell q = (a, b, c, T).  vector 0: (a, b, c) = (U, V, W).  vector 1: the vorticity in the fields' type R, central differences,
+every operation rounded in R, two_dx = R(2) * R(dx):
+  wx = (W[j+1] - W[j-1]) / two_dy - (V[k+1] - V[k-1]) / two_dz
+  wy = (U[k+1] - U[k-1]) / two_dz - (W[i+1] - W[i-1]) / two_dx
+  wz = (V[i+1] - V[i-1]) / two_dx - (U[j+1] - U[j-1]) / two_dy
+on a NODE_IN cell whose six neighbours are inside the grid and not NODE_OUT (an OUT neighbour holds the stamp, not a velocity);
+(99999, 99999, 99999) on a NODE_OUT cell, so the missing-value marker survives; (0, 0, 0) on every other cell.
+
+filter 0: the sample is q of the cell (lo_x, lo_y, lo_z).
+filter 1: with C the NODE_IN cells of the sample's box -- C empty: filter 0's sample (a wall value or 99999); else per quantity
+m = (sum over C of (double)q) / (double)|C|, the sum in double in any order, one double division; outT = m and each outV component
+is m rounded once to R.  With every o >= g filter 1 equals filter 0 bit for bit.  A field that is constant on NODE_IN comes out as
+that constant wherever |C| times the constant is exact in double: in fp32 for every box of up to 2^29 cells (24 + 29 bits), in fp64 for constants of few
+significant bits (else to the rounding of the sum).
+"""
+import math
+
+import numpy as np
+
+from .grids import NODE_IN, NODE_OUT
+
+MISSING_VALUE = 99999.0
+POINT, BOX = 0, 1
+VELOCITY, VORTICITY = 0, 1
+
+
+def boxes(g, o):
+    """(lo, hi) of every output index of one axis: int64 arrays of o (or g, for o = 0) entries"""
+    o = o or g
+    i = np.arange(o, dtype=np.int64)
+    lo = i * g // o
+    return lo, np.maximum(lo + 1, (i + 1) * g // o)
+
+
+def stamp(type, fields):
+    """Copies of the four fields with 99999 on the NODE_OUT cells: what the entries leave in `next`"""
+    out_cells = np.asarray(type) == NODE_OUT
+    out = [np.array(f, copy=True) for f in fields]
+    for f in out:
+        f[out_cells] = MISSING_VALUE
+    return out
+
+
+def curl_defined(type):
+    """The cells that carry a vorticity: NODE_IN, the six neighbours inside the grid and not NODE_OUT"""
+    t = np.asarray(type)
+    ok = np.zeros(t.shape, bool)
+    not_out = t != NODE_OUT
+    ok[1:-1, 1:-1, 1:-1] = (t[1:-1, 1:-1, 1:-1] == NODE_IN) & \
+        not_out[:-2, 1:-1, 1:-1] & not_out[2:, 1:-1, 1:-1] & not_out[1:-1, :-2, 1:-1] & not_out[1:-1, 2:, 1:-1] & \
+        not_out[1:-1, 1:-1, :-2] & not_out[1:-1, 1:-1, 2:]
+    return ok
+
+
+def vorticity(type, fields, spacing):
+    """(wx, wy, wz) per cell as the rule gives them, in the fields' dtype; fields are the stamped U, V, W(, T)."""
+    U, V, W = fields[:3]
+    R = U.dtype.type
+    two = [R(2) * R(d) for d in spacing]
+    c = (slice(1, -1),) * 3
+
+    def d(f, axis):                                       # f[+1] - f[-1] along axis, on the interior
+        hi = [slice(1, -1)] * 3
+        lo = [slice(1, -1)] * 3
+        hi[axis], lo[axis] = slice(2, None), slice(None, -2)
+        return f[tuple(hi)] - f[tuple(lo)]
+    with np.errstate(all="ignore"):                       # differences against the stamp are computed and thrown away
+        w = [d(W, 1) / two[1] - d(V, 2) / two[2], d(U, 2) / two[2] - d(W, 0) / two[0], d(V, 0) / two[0] - d(U, 1) / two[1]]
+    ok = curl_defined(type)
+    out_cells = np.asarray(type) == NODE_OUT
+    res = []
+    for comp in w:
+        assert comp.dtype == U.dtype
+        full = np.zeros(U.shape, U.dtype)
+        full[c] = np.where(ok[c], comp, R(0))
+        full[out_cells] = R(MISSING_VALUE)
+        res.append(full)
+    return res
+
+
+def cell_quantities(type, fields, vector=VELOCITY, spacing=None):
+    """q = (a, b, c, T) per cell from the fields as they are before the call (the stamp is applied here)."""
+    st = stamp(type, fields)
+    if vector == VELOCITY:
+        return st
+    if vector != VORTICITY:
+        raise ValueError("vector is 0 (velocity) or 1 (vorticity)")
+    if spacing is None:
+        raise ValueError("the vorticity needs the grid's spacing (dx, dy, dz)")
+    return vorticity(type, st, spacing) + [st[3]]
+
+
+def layer_output(type, fields, outdims=(0, 0, 0), filter=POINT, vector=VELOCITY, spacing=None, exact_sum=False):
+    """The record of one call: (outV [odx, ody, odz, 3] in the fields' dtype, outT [odx, ody, odz] float64).
+    fields: U, V, W, T of `next` before the call, four arrays [dimx, dimy, dimz] of one float dtype (not modified).
+    exact_sum: the box sums by math.fsum, so that a mean carries the rounding of its division alone (the yardstick of a bound);
+    otherwise numpy's double sum."""
+    if filter not in (POINT, BOX):
+        raise ValueError("filter is 0 (point) or 1 (box)")
+    type = np.asarray(type)
+    q = cell_quantities(type, fields, vector, spacing)
+    R = q[0].dtype
+    dims = type.shape
+    ax = [boxes(g, o) for g, o in zip(dims, outdims)]
+    sel = np.ix_(*[lo for lo, _ in ax])
+    outV = np.stack([f[sel] for f in q[:3]], axis=-1)
+    outT = q[3][sel].astype(np.float64)
+    if filter == POINT or all((hi - lo == 1).all() for lo, hi in ax):      # (the mean of one value: (R)((double)q / 1.0) = q)
+        return outV, outT
+    fluid = type == NODE_IN
+    for i, (x0, x1) in enumerate(zip(*ax[0])):
+        for j, (y0, y1) in enumerate(zip(*ax[1])):
+            for k, (z0, z1) in enumerate(zip(*ax[2])):
+                box = (slice(x0, x1), slice(y0, y1), slice(z0, z1))
+                m = fluid[box]
+                n = int(m.sum())
+                if n == 0:
+                    continue
+                mean = []
+                for f in q:
+                    vals = f[box][m].astype(np.float64)
+                    mean.append((math.fsum(vals) if exact_sum else float(vals.sum())) / float(n))
+                outV[i, j, k] = np.array(mean[:3], np.float64).astype(R)
+                outT[i, j, k] = mean[3]
+    return outV, outT
+
+
+def box_kinds(type, outdims):
+    """Per sample: 0 every cell of the box NODE_IN, 1 mixed, 2 no NODE_IN and the sample cell a wall (NODE_BOUND / NODE_VALVE),
+    3 no NODE_IN and the sample cell NODE_OUT.  int8 [odx, ody, odz]; test aid."""
+    type = np.asarray(type)
+    ax = [boxes(g, o) for g, o in zip(type.shape, outdims)]
+    kinds = np.empty([len(lo) for lo, _ in ax], np.int8)
+    for i, (x0, x1) in enumerate(zip(*ax[0])):
+        for j, (y0, y1) in enumerate(zip(*ax[1])):
+            for k, (z0, z1) in enumerate(zip(*ax[2])):
+                t = type[x0:x1, y0:y1, z0:z1]
+                n = int((t == NODE_IN).sum())
+                kinds[i, j, k] = 0 if n == t.size else 1 if n else 3 if type[x0, y0, z0] == NODE_OUT else 2
+    return kinds

@@ -107,6 +107,16 @@ enum {
                                  axis) a triangle meets: closed for the 6-neighbourhood of the fill, about 0.55 of the cells (the mesh section
                                  below).  A mesh entry called with 1 while FS3D_OPT_MESH_VOXELS is 0 fails with FS3D_ERR_INVALID before
                                  anything is touched.  Any other value: FS3D_ERR_INVALID */
+    FS3D_OPT_OUTPUT_FILTER = 12, /* how fs3d_get_layer, fs3d_get_layer_rows and fs3d_get_layer_dev turn `next` into samples; no effect on any
+                                 other entry.  0 (default): nothing changes anywhere -- the reference's point sample (FilterToArrays).
+                                 1: the box mean -- every sample is the mean over the NODE_IN cells of its box of source cells, and the
+                                 point sample where the box holds none (the GetLayer section below).  While it is 1 an x-slab or a member
+                                 of a group is refused by the three entries (FS3D_ERR_UNSUPPORTED).  Any other value: FS3D_ERR_INVALID */
+    FS3D_OPT_OUTPUT_VECTOR = 13, /* what outV of the same three entries holds; outT is the temperature either way.  0 (default): nothing
+                                 changes anywhere -- the velocity.  1: the vorticity, central differences on the NODE_IN cells whose six
+                                 neighbours are inside the grid and not NODE_OUT, 99999 on NODE_OUT cells, 0 elsewhere (the GetLayer
+                                 section below); combines with either filter.  Slabs are refused as above.  Any other value:
+                                 FS3D_ERR_INVALID */
     FS3D_OPT_ERR_ORDER = 7   /* summation order of EvalDivError (fs3d_eval_div_error, fs3d_time_step with compute_error).  0 (default): the
                                  per-cell terms are summed in parallel (per workgroup, then over the workgroups; deterministic, equal to the
                                  CPU path to ~1e-12 relative).  1: they are summed one after the other in cell order, as the loop of
@@ -522,7 +532,28 @@ fs3d_status fs3d_get_layer(fs3d_ctx *ctx, void *outV, double *outT,
  * cross the bus, (rows[1]-rows[0])*outdimy*outdimz*(3*sizeof(real)+8) bytes, through a device staging buffer the context keeps
  * and only grows.  Host destinations; returns synchronised.
  * All three entries stamp `next` first and over all owned cells, refuse before any launch (NULL context, destination or rows,
- * negative dims, no nodes yet: FS3D_ERR_INVALID, the context stays usable) and report pending device errors. */
+ * negative dims, no nodes yet: FS3D_ERR_INVALID, the context stays usable) and report pending device errors.
+ *
+ * Filtered and derived records (FS3D_OPT_OUTPUT_FILTER, FS3D_OPT_OUTPUT_VECTOR; no reference counterpart; the rule and its numpy
+ * twin: cmc_fluid_solver_amd/layer_output.py).  With either option non-zero the three entries run k_get_layer_box in place of the
+ * gather, behind the same stamp, through the same staging buffer and copies: `next` is left as a default call leaves it.
+ * The box of output index i on an axis of g source cells and o samples is [lo, hi), lo = i*g/o, hi = max(lo + 1, (i+1)*g/o) in
+ * 64-bit integers: for o <= g the boxes partition the axis and start at the reference's sample cell, for o >= g each is that cell.
+ * Per cell q = (a, b, c, T): (a, b, c) is the velocity, or with FS3D_OPT_OUTPUT_VECTOR set to 1 the vorticity in the context's real
+ * type R, each operation rounded, two_dx = R(2) * R(dx):
+ *   wx = (W[j+1] - W[j-1]) / two_dy - (V[k+1] - V[k-1]) / two_dz
+ *   wy = (U[k+1] - U[k-1]) / two_dz - (W[i+1] - W[i-1]) / two_dx
+ *   wz = (V[i+1] - V[i-1]) / two_dx - (U[j+1] - U[j-1]) / two_dy
+ * on a NODE_IN cell whose six neighbours are inside the grid and not NODE_OUT (their fields hold the stamp); (99999, 99999, 99999)
+ * on a NODE_OUT cell; (0, 0, 0) on every other cell.  Filter 0: the sample is q of the cell (lo_x, lo_y, lo_z).  Filter 1: with C
+ * the NODE_IN cells of the sample's box, the sample is filter 0's where C is empty (a wall value or 99999: walls and the outside
+ * show only where a box holds no fluid); else each quantity is m = (sum over C of (double)q) / (double)|C|, summed in double in an
+ * unspecified order, one double division; outT = m, each outV component is m rounded once to R.  With every o >= g filter 1 equals
+ * filter 0 bit for bit; a field that is constant on NODE_IN comes out as that constant wherever |C| times it is exact in double
+ * (in fp32: every box of up to 2^29 cells).
+ * While either option is non-zero, an x-slab (x_offset != 0 or dimx != dimx_global) or a member of a group is refused by all three
+ * entries with FS3D_ERR_UNSUPPORTED before any launch, destinations and `next` untouched: a box can straddle a cut and the curl
+ * needs the neighbour's planes.  fs3d_get_layer_rows / _dev on a whole-grid context work and report rows = [0, outdimx). */
 fs3d_status fs3d_get_layer_rows(fs3d_ctx *ctx, void *outV, double *outT, int outdimx, int outdimy, int outdimz, int rows[2]);
 /* fs3d_get_layer_rows (Solver3D.cpp:21-25, TimeLayer3D.h:819-924) with the two arrays on the context's DEVICE: the kernel
  * writes them directly, nothing is copied.  Returns after the enqueue on the context's stream; read after fs3d_synchronize.
