@@ -98,6 +98,7 @@ SYMBOLS = {
     "fs3d_enable_timing": (_i, [_vp, _i]),
     "fs3d_profile_sweep": (_i, [_vp, _i, _d, _i, _i, _i, C.POINTER(C.c_ulonglong), _i, _pi]),
     "fs3d_last_sweep_kernel": (_i, [_vp, _i, _pi, _pi]),
+    "fs3d_last_sweep_launch": (_i, [_vp, _i, _i, _pi]),
     "fs3d_version": (C.c_char_p, []),
 }
 
@@ -503,6 +504,17 @@ class Solver:
                 {0: "", 1: "+pipelined-ranks", 2: "+reduced-interface", 3: "+reduced-interface(on-chip)"}[(sg.value >> 1) & 3] + \
                 ("+all-to-all" if sg.value & 8 else "")
         return out
+
+    LAUNCH_FIELDS = {0: ("family",), 1: ("family", "M", "NCH", "LT", "XB", "order", "workgroups"),
+                     2: ("family", "LPL", "NW", "LG", "n_grp", "workgroups")}
+
+    def last_sweep_launch(self, d, pass_=0):
+        """The partition kernel instance and launch of the last sweep of direction d: {"family": 1, "M": 16, "NCH": 16, "LT": 32,
+        "XB": 0, "order": 0x440, "workgroups": 2048}, {"family": 2, "LPL": 64, "NW": 1, "LG": 16, "n_grp": 16, "workgroups": 1024},
+        or {"family": 0} where that pass (1: the interface pass of a reduced-interface X sweep) launched no partition kernel."""
+        out = (C.c_int * 8)()
+        self._chk(self.lib.fs3d_last_sweep_launch(self.h, d, pass_, out))
+        return dict(zip(self.LAUNCH_FIELDS[out[0]], out))
 
     def profiler_events(self):
         """{event name of the reference's Profiler: (total ms, count)} since enable_timing(True)"""

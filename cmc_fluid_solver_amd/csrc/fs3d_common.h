@@ -195,6 +195,7 @@ struct fs3d_ctx {
     int opt_kernel = FS3D_SWEEP_AUTO;
     int ran_kernel[3] = {0, 0, 0};   // per direction: the kernel the last sweep really ran (fs3d_last_sweep_kernel)
     int ran_segmented[3] = {0, 0, 0};
+    int ran_launch[3][2][8] = {};    // per direction and pass: the partition kernel instance and launch of the last sweep (fs3d_last_sweep_launch)
     int opt_fuse = 1;
     // timing
     bool timing = false;           // events around the launches being enqueued now

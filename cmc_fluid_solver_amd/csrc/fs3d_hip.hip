@@ -907,6 +907,7 @@ static fs3d_status sweep_buffers(fs3d_ctx *c, int dir, double dt, int b_cur, int
 {
     SweepParams<R> p;
     fill_params<R>(c, p, dir, dt, b_cur, b_temp, b_next, b_tout, merge);
+    std::fill(&c->ran_launch[dir][0][0], &c->ran_launch[dir][0][0] + 16, 0);
     const int cls = dir == 2 ? 0 : (dir == 1 ? 1 : 2);
     fs3d_status st;
     if (halo && c->nranks > 1) {
@@ -1274,6 +1275,13 @@ extern "C" fs3d_status fs3d_last_sweep_kernel(fs3d_ctx *c, int dir, int *kernel_
     if (!c || dir < 0 || dir > 2 || !kernel_out) return FS3D_ERR_INVALID;
     *kernel_out = c->ran_kernel[dir];
     if (segmented_out) *segmented_out = c->ran_segmented[dir] | (dir == 0 ? (c->ran_xsolve << 1) | (c->ran_xa2a << 3) : 0);
+    return FS3D_OK;
+}
+
+extern "C" fs3d_status fs3d_last_sweep_launch(fs3d_ctx *c, int dir, int pass, int out[8])
+{
+    if (!c || dir < 0 || dir > 2 || pass < 0 || pass > 1 || !out) return FS3D_ERR_INVALID;
+    std::copy(c->ran_launch[dir][pass], c->ran_launch[dir][pass] + 8, out);
     return FS3D_OK;
 }
 

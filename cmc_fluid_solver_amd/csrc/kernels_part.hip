@@ -667,6 +667,8 @@ static Launch part_launch_xy(fs3d_ctx *c, const SweepParams<R> &p)
     const bool late = sizeof(R) == 4 && LT <= 32 && NCH == 16 && M == 16 && (long long)n_o * n_tiles >= 1024;
     const int order = LT <= 32 ? (((long long)n_o * n_tiles < 1024 || NCH == 32) ? 1 : 0) | (late ? 0x40 | (4 << 8) : 0) : 0;
     hipLaunchKernelGGL((k_sweep_part<R, DIR, M, NCH, LT, XB>), dim3((unsigned)(n_o * n_tiles)), dim3(LT * NCH), lds, c->stream, p, n_o, n_tiles, order);
+    const int rec[8] = {1, M, NCH, LT, XB, order, n_o * n_tiles, 0};
+    std::copy(rec, rec + 8, c->ran_launch[DIR][p.xiface_pass ? 1 : 0]);
     return Launch::RAN;
 }
 
@@ -1171,6 +1173,8 @@ static Launch part_launch_z(fs3d_ctx *c, const SweepParams<R> &p)
     const long long tasks = (long long)n_grp * npl;
     const int tpw = NW == 2 ? 2 : 4;                      // tasks per workgroup of four waves
     hipLaunchKernelGGL((k_sweep_part_z<R, LPL, NW>), dim3((unsigned)((tasks + tpw - 1) / tpw)), dim3(256), 0, c->stream, p, n_grp, LG);
+    const int rec[8] = {2, LPL, NW, LG, n_grp, (int)((tasks + tpw - 1) / tpw), 0, 0};
+    std::copy(rec, rec + 8, c->ran_launch[2][0]);
     return Launch::RAN;
 }
 

@@ -626,6 +626,13 @@ fs3d_status fs3d_profile_sweep(fs3d_ctx *ctx, int dir, double dt, int l_cur, int
  * FS3D_SWEEP_AUTO never falls back silently: callers (bench.py, fs3d_run) print this. */
 fs3d_status fs3d_last_sweep_kernel(fs3d_ctx *ctx, int dir, int *kernel_out, int *segmented_out);
 
+/* Which partition kernel instance the last sweep of direction dir launched, and how.  pass 0: the sweep itself; pass 1: the
+ * interface pass of a reduced-interface cross-slab X sweep.  out[0] is the family: 0 = that pass launched no partition kernel
+ * (exact kernels, or the thread-per-line interface walk); 1 = k_sweep_part: {1, M, NCH, LT, XB, order, workgroups, 0};
+ * 2 = k_sweep_part_z: {2, LPL, NW, LG, n_grp, workgroups, 0, 0}.  Cleared to family 0 when a sweep of that direction begins; a
+ * sweep cut into plane ranges (halo overlap) leaves its last launch.  For tests that must prove which instance they ran. */
+fs3d_status fs3d_last_sweep_launch(fs3d_ctx *ctx, int dir, int pass, int out[8]);
+
 /* library / device identification */
 const char *fs3d_version(void);
 

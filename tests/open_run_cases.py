@@ -37,6 +37,7 @@ WIDE = functools.partial(grids.box, 70, 40, 68, h=0.02)                        #
 LONG_Z = functools.partial(grids.box, 12, 14, 70, h=0.02)                      # 70-cell Z lines: the thread-per-line kernel
 ODD_Z = functools.partial(grids.box, 20, 16, 33, h=0.04)                       # dimz % 32 == 1 (and % 16): one lane in the last X/Y tile
 TALL = functools.partial(grids.box, 90, 93, 68, h=0.015)                       # fp64 Z kernel: one line per wave, 2 rows per group, 93 odd
+LONG_Z_PART = functools.partial(grids.box, 12, 10, 132, h=0.01)                # 132-cell Z lines: fp32 one line per wave (33 of 64 lanes), fp64 a pair of waves
 
 # stale: stale_in_cells > 0; in_starts: NODE_IN cells that carry a START row, over the three directions; sensitive: see above;
 # part: the sweep directions whose open runs the partition kernels are tested on ("" = none: dims they refuse, or exact-only)
@@ -83,11 +84,14 @@ CASES = {
                          "and an X / Y row that reads k + 1 (the Z kernels refuse 33-cell lines)", part="XY"),
     "part_y_row_behind": _c(TALL, [(S(10, 14), -1, S(32, 64))], True, 0, True, "fp64 Z kernel, one line per wave-wide access and two rows per "
                             "group: line dimy - 1 opens its group, its j + 1 is the row behind the plane", part="YZ"),
+    "part_z_row_behind_132": _c(LONG_Z_PART, [(S(4, 8), -1, S(100, 131))], True, 0, True, "the fp32 twin of part_y_row_behind: Z lines of 132 cells, one per "
+                                "wave-wide access; line dimy - 1 is a row of its own, its j + 1 is the row behind the plane", part="Z"),
     "line_fallback": _c(LONG_Z, [(S(4, 8), S(5, 9), -1)], True, 0, True, "Z lines the pipelined kernel refuses: the thread-per-line walk", part=""),
 }
 EVERY = list(CASES)
-ALL = [n for n in EVERY if CASES[n].base is not TALL]           # the exact-kernel matrices leave out the 90x93x68 grid: it is there for
-                                                                # one path of the fp64 Z partition kernel and costs as much as the rest together
+ALL = [n for n in EVERY if CASES[n].base not in (TALL, LONG_Z_PART)]   # the exact-kernel matrices leave out the 90x93x68 grid: it is there for
+                                                                # one path of the fp64 Z partition kernel and costs as much as the rest together;
+                                                                # and its fp32 twin on 132-cell lines, there for the Z partition kernels alone
 SENSITIVE = [n for n in EVERY if CASES[n].sensitive]
 PART = [n for n in EVERY if CASES[n].part]
 

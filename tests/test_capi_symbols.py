@@ -1,5 +1,5 @@
 """CPU-side checks of the drop-in boundary, the one place that pins the whole C ABI: include/fs3d.h, capi.SYMBOLS and the
-exports of the library built for gfx950 name the same 58 functions, every ctypes signature agrees with its prototype, and the
+exports of the library built for gfx950 name the same 59 functions, every ctypes signature agrees with its prototype, and the
 constants of capi.py are the header's (no compute, no GPU).  A new entry is declared, bound and counted here."""
 import ctypes
 import os
@@ -9,7 +9,7 @@ import abi_decls
 from cmc_fluid_solver_amd import capi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-N_FUNCTIONS = 58
+N_FUNCTIONS = 59
 INT_TYPES = ("int", "fs3d_precision", "fs3d_status")            # an enum is an int in the C ABI of every target the library builds for
 SCALARS = {"double": ctypes.c_double, "size_t": ctypes.c_size_t}
 RETURNS = {"fs3d_status": ctypes.c_int, "void": None, "const char *": ctypes.c_char_p}

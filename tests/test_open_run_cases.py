@@ -94,6 +94,12 @@ def test_partition_shapes(built):
         LG //= 2
     assert 64 < g.dimz <= 128 and LG == 2 and (g.dimy - 1) % LG == 0
     assert (OC.kinds("part_y_row_behind")[2][10:14, -1, 32:64] == ROW_INTERIOR).all()
+    # part_z_row_behind_132: in fp32 the Z kernel holds a 132-cell line in one wave-wide access (4 cells per lane: 129 .. 256 cells, 33
+    # lanes in use), one row per group on so small a grid; in fp64 a pair of waves holds it.  The window reaches into lane 32.
+    g = OC.grid("part_z_row_behind_132")
+    assert 128 < g.dimz <= 256 and g.dimz % 4 == 0 and g.dimy * g.dimx < 4096
+    assert (OC.kinds("part_z_row_behind_132")[2][4:8, -1, 100:131] == ROW_INTERIOR).all()
+    assert OC.stale_mask("part_z_row_behind_132", 1)[4:8, -1, 100:131].all() and not OC.stale_mask("part_z_row_behind_132", 2).any()
 
 
 @pytest.mark.parametrize("name", OC.EVERY)

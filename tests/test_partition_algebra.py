@@ -73,8 +73,12 @@ def test_identity_rows_decouple_segments():
 # e(K) = max over lines of max |K - x64| / S, and e(partition fp32) <= F e(sequential fp32) + 2^-23 with F = 2.  The model uses
 # plain reciprocals, coarser than the kernels' corrected quotients, so F rests on it and not on the kernels.
 F_LINE, FLOOR = 2.0, 2.0 ** -23
-COEFS = [(5.6, 41.1, 6.0), (312.0, 655.0, 44.0)]        # (vis, b, max |q|): the solver's rows at h = 0.03 and at h = 0.004
+COEFS = [(5.6, 41.1, 6.0), (312.0, 655.0, 44.0), (1250.0, 2530.0, 90.0)]   # (vis, b, max |q|): the solver's rows at h = 0.03, 0.004 and 0.002
 CHUNKINGS = [(16, "thomas"), (4, "pcr")]                # X / Y sweeps; Z sweep
+# the line lengths of tests/launch_shape_cases.py too: 260, 388, 512 are 32 chunks of 16 cells (the sequential interface solve over 64
+# unknowns) and 128 lanes of 4 (cyclic reduction over 128 unknowns); 72 / 130 and 68 / 132 leave the last chunk and the last lanes
+# partly empty; 8-cell chunks with the sequential interface solve are the thin-slab instance (24 and 32 planes)
+MORE_LINES = [(72, 16, "thomas"), (130, 16, "thomas"), (68, 4, "pcr"), (132, 4, "pcr"), (24, 8, "thomas"), (32, 8, "thomas")]
 
 
 def _two_segment_system(n, chunk, coef, dtype, seed, nrhs=4):
@@ -128,9 +132,19 @@ def _line_error(K, x64):
 
 
 @pytest.mark.parametrize("chunk,reduced", CHUNKINGS)
-@pytest.mark.parametrize("coef", COEFS, ids=["h0.03", "h0.004"])
-@pytest.mark.parametrize("n", [44, 48, 64, 128, 256])
+@pytest.mark.parametrize("coef", COEFS, ids=["h0.03", "h0.004", "h0.002"])
+@pytest.mark.parametrize("n", [44, 48, 64, 128, 256, 260, 388, 512])
 def test_two_segments_every_end_row_kind_per_line(n, coef, chunk, reduced):
+    two_segments_per_line(n, coef, chunk, reduced)
+
+
+@pytest.mark.parametrize("coef", COEFS, ids=["h0.03", "h0.004", "h0.002"])
+@pytest.mark.parametrize("n,chunk,reduced", MORE_LINES)
+def test_two_segments_partly_filled_and_thin_slab_chunkings_per_line(n, chunk, reduced, coef):
+    two_segments_per_line(n, coef, chunk, reduced)
+
+
+def two_segments_per_line(n, coef, chunk, reduced):
     a, b, c, d = _two_segment_system(n, chunk, coef, np.float32, seed=n + chunk)
     a64, b64, c64, d64 = (v.astype(np.float64) for v in (a, b, c, d))
     bounds = list(range(0, n, chunk)) + [n]
