@@ -32,6 +32,10 @@ OPT_OUTPUT_FILTER = 12    # the three GetLayer entries: 0 the reference's point 
 OUTPUT_FILTER = {"point": 0, "box": 1}
 OPT_OUTPUT_VECTOR = 13    # outV of the same entries: 0 the velocity (default), 1 the vorticity (layer_output.py is the rule of both options)
 OUTPUT_VECTOR = {"velocity": 0, "vorticity": 1}
+OPT_TIME_STATS = 14       # 1: every successful time step adds the new `cur` to per-cell sums on the device, 2: and its squares; every set opens a new window (default 0)
+TIME_STATS = {"off": 0, "mean": 1, "variance": 2}
+OPT_OUTPUT_SOURCE = 15    # what the three GetLayer entries sample: 0 `next` (default), 1 the time mean, 2 the time variance, 3 the fluid fraction (time_stats.py is the rule)
+OUTPUT_SOURCE = {"next": 0, "mean": 1, "variance": 2, "fraction": 3}
 XSOLVE_AUTO, XSOLVE_PIPELINED, XSOLVE_REDUCED, XSOLVE_REDUCED_A2A = 0, 1, 2, 3
 
 # every function include/fs3d.h declares, in the header's order: name -> (restype, argtypes)

@@ -187,6 +187,18 @@ struct fs3d_ctx {
     int opt_fresh_slabs = 0;               // FS3D_OPT_FRESH_CELLS_SLABS: 1 = a slab of a group keeps that snapshot too and fills collectively
     int opt_out_filter = 0;                // FS3D_OPT_OUTPUT_FILTER: 1 = the GetLayer entries average the NODE_IN cells of every sample's box (k_get_layer_box)
     int opt_out_vector = 0;                // FS3D_OPT_OUTPUT_VECTOR: 1 = their outV holds the vorticity (k_get_layer_box<R, true>)
+    // time statistics (kernels_stats.hip): per own cell, no ghost planes -- the steps it was NODE_IN (ts_n), the double sums of U, V, W, T
+    // over those steps (ts_s1, field v at + v * ts_stride) and, in mode 2, of their squares (ts_s2).  Allocated by the first
+    // accumulation, counted in geom_allocs, freed when the option is set to 0; ts_q is the statistic layer of the read-out (4 fields of
+    // ts_stride reals), allocated by the first fs3d_get_layer* call with a source other than 0 and kept
+    int opt_time_stats = 0;                // FS3D_OPT_TIME_STATS: 0 off, 1 first moments, 2 first and second moments
+    int opt_out_source = 0;                // FS3D_OPT_OUTPUT_SOURCE: 0 `next`, 1 time mean, 2 time variance, 3 fluid fraction
+    long long ts_steps = 0;                // N: accumulated steps of the open window
+    bool ts_clear = false;                 // the window is new: the next accumulation zeroes the accumulators first
+    long long ts_stride = 0;               // ncell rounded up to 4 (every field of the accumulators starts on 16 bytes)
+    DevBuf<unsigned> ts_n;
+    DevBuf<double> ts_s1, ts_s2;
+    DevBuf<> ts_q;
     int opt_err_order = 0;                 // FS3D_OPT_ERR_ORDER: 1 = EvalDivError sums its per-cell terms serially in cell order (host), as the CPU path
     DevBuf<double> err_terms;              // ... one term per cell (device, allocated on first use)
     std::vector<double> err_terms_host;
@@ -259,6 +271,13 @@ static inline bool stream_reserve(fs3d_ctx *c, std::initializer_list<BufWant<Dev
 
 // kernels_geom.hip
 void fs3d_geom_destroy(fs3d_ctx *c);
+
+// kernels_stats.hip: FS3D_OPT_TIME_STATS / FS3D_OPT_OUTPUT_SOURCE
+// one accumulation of FS3D_LAYER_CUR into the window, enqueued on the context's stream (the first one allocates and clears)
+fs3d_status fs3d_time_stats_accumulate(fs3d_ctx *c);
+// the statistic layer of `source` (1 mean, 2 variance, 3 fluid fraction) into ts_q, enqueued; q_out: its four fields
+fs3d_status fs3d_time_stats_layer(fs3d_ctx *c, int source, void *q_out[4], bool *grown);
+void fs3d_time_stats_free(fs3d_ctx *c);
 
 // kernels_*.hip
 // What a sweep launcher did.  NA: it does not cover these dims / this precision / this slab form -- the caller may try the

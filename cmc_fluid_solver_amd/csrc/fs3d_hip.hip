@@ -407,6 +407,7 @@ extern "C" fs3d_status fs3d_create(fs3d_ctx **out, int device, fs3d_precision pr
     c->gdx = dx; c->gdy = dy; c->gdz = dz;
     c->esize = prec == FS3D_F32 ? 4 : 8;
     c->plane = (long long)dimy * dimz; c->ncell = c->plane * dimx;
+    c->ts_stride = (c->ncell + 3) / 4 * 4;
     if (const char *e = getenv("FS3D_TEST_DROP_HANDOFF")) c->test_drop = atoi(e) ? 1 : 0;
     if (const char *e = getenv("FS3D_DEFAULT_KERNEL")) {       // initial FS3D_OPT_SWEEP_KERNEL of new contexts (tests: 4 = bit-exact kernels only)
         const int v = atoi(e);
@@ -510,6 +511,19 @@ extern "C" fs3d_status fs3d_set_option(fs3d_ctx *c, int option, int value)
     case FS3D_OPT_OUTPUT_VECTOR:
         if (value != 0 && value != 1) return fail(c, FS3D_ERR_INVALID, "bad output vector id (0: the velocity, 1: the vorticity)");
         c->opt_out_vector = value; return FS3D_OK;
+    case FS3D_OPT_TIME_STATS:
+        // every call opens a new window; 0 gives the accumulators back (what the stream still does with them finishes first)
+        if (value < 0 || value > 2) return fail(c, FS3D_ERR_INVALID, "bad time-statistics mode (0: off, 1: first moments, 2: first and second moments)");
+        c->opt_time_stats = value; c->ts_steps = 0; c->ts_clear = true;
+        if (value == 0 && c->ts_n.raw()) {
+            HIPCHK(c, hipSetDevice(c->device));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            fs3d_time_stats_free(c);
+        }
+        return FS3D_OK;
+    case FS3D_OPT_OUTPUT_SOURCE:
+        if (value < 0 || value > 3) return fail(c, FS3D_ERR_INVALID, "bad output source id (0: `next`, 1: time mean, 2: time variance, 3: fluid fraction)");
+        c->opt_out_source = value; return FS3D_OK;
     case FS3D_OPT_XSOLVE:
         if (value < 0 || value > 3) return fail(c, FS3D_ERR_INVALID, "bad cross-slab X solve id");
         c->opt_xsolve = value; return FS3D_OK;
@@ -1251,6 +1265,7 @@ extern "C" fs3d_status fs3d_time_step(fs3d_ctx *c, double dt, int G, int L, int 
         return fail(c, FS3D_ERR_DIVERGED, b);
     }
     std::swap(c->slot[FS3D_LAYER_CUR], c->slot[FS3D_LAYER_NEXT]);            // :388-390
+    if (c->opt_time_stats) return fs3d_time_stats_accumulate(c);             // the new `cur` joins the window (enqueued)
     return FS3D_OK;
 }
 
@@ -1267,6 +1282,7 @@ extern "C" fs3d_status fs3d_time_step_async(fs3d_ctx *c, double dt, int G, int L
     st = c->prec == FS3D_F32 ? time_step_enqueue<float>(c, dt, G, L, false, true) : time_step_enqueue<double>(c, dt, G, L, false, true);
     if (st) return st;
     std::swap(c->slot[FS3D_LAYER_CUR], c->slot[FS3D_LAYER_NEXT]);
+    if (c->opt_time_stats) return fs3d_time_stats_accumulate(c);
     return FS3D_OK;
 }
 
@@ -1299,6 +1315,8 @@ extern "C" fs3d_status fs3d_synchronize(fs3d_ctx *c)
 // of the GLOBAL output whose source plane it holds.  `dev`: outV / outT are on the context's device, the kernel writes them and
 // the call returns after the enqueue; else the owned samples go through the staging buffer and the call returns synchronised.
 // FS3D_OPT_OUTPUT_FILTER / FS3D_OPT_OUTPUT_VECTOR: k_get_layer_box in place of k_get_layer, everything around it as it is.
+// FS3D_OPT_OUTPUT_SOURCE 1..3: the statistic layer of kernels_stats.hip, in a buffer of its own, takes the place of `next` -- stamp,
+// gather or box kernel, staging and copies run on it unchanged; `next` and `cur` are not written.
 template <typename R>
 static fs3d_status get_layer_impl(fs3d_ctx *c, R *outV, double *outT, int odx, int ody, int odz, bool local, bool dev, int rows[2])
 {
@@ -1322,13 +1340,18 @@ static fs3d_status get_layer_impl(fs3d_ctx *c, R *outV, double *outT, int odx, i
         BUFCHK(c, c->gl_stage.reserve(vbytes + (size_t)n * 8, nullptr, &grown));
         c->gl_info[2] += grown;
     }
+    R *F[4] = {fld<R>(c, b, 0), fld<R>(c, b, 1), fld<R>(c, b, 2), fld<R>(c, b, 3)};
+    if (c->opt_out_source) {
+        bool grown = false;
+        GTRY(fs3d_time_stats_layer(c, c->opt_out_source, (void **)F, &grown));
+        c->gl_info[2] += grown;
+    }
     hipLaunchKernelGGL((k_clear_type<R>), dim3(grid_for(c->ncell)), dim3(256), 0, c->stream, c->code, c->ncell,
-                       (int)FS3D_NODE_OUT, (R)99999.0f, fld<R>(c, b, 0), fld<R>(c, b, 1), fld<R>(c, b, 2), fld<R>(c, b, 3));
+                       (int)FS3D_NODE_OUT, (R)99999.0f, F[0], F[1], F[2], F[3]);
     HIPCHK(c, hipGetLastError());
     if (n) {
         R *kV = dev ? dV : (R *)c->gl_stage;
         double *kT = dev ? dT : (double *)((char *)c->gl_stage + vbytes);
-        const R *const F[4] = {fld<R>(c, b, 0), fld<R>(c, b, 1), fld<R>(c, b, 2), fld<R>(c, b, 3)};
         if (c->opt_out_filter || c->opt_out_vector) {          // a whole-grid context (get_layer_entry): i0 = 0, i1 = odx
             const dim3 grid((unsigned)odx, (unsigned)std::min(ody, 65535));
             const R two_dx = R(2) * (R)c->gdx, two_dy = R(2) * (R)c->gdy, two_dz = R(2) * (R)c->gdz;
@@ -1364,6 +1387,13 @@ static fs3d_status get_layer_entry(fs3d_ctx *c, const char *what, void *outV, do
     if ((c->opt_out_filter || c->opt_out_vector) && (c->x_offset != 0 || c->dimx != c->dimx_global || c->comm || c->local || c->nranks > 1))
         return fail(c, FS3D_ERR_UNSUPPORTED, std::string(what) + ": FS3D_OPT_OUTPUT_FILTER / FS3D_OPT_OUTPUT_VECTOR on an x-slab or a member of a group "
                                              "(a box can straddle a cut and the curl needs the neighbour's planes)");
+    if (c->opt_out_source) {
+        const char *const names[4] = {"", "the time mean", "the time variance", "the fluid fraction"};
+        if (c->opt_time_stats == 0 || (c->opt_out_source == 2 && c->opt_time_stats < 2))
+            return fail(c, FS3D_ERR_INVALID, std::string(what) + ": FS3D_OPT_OUTPUT_SOURCE asks for " + names[c->opt_out_source] +
+                                             ", which the FS3D_OPT_TIME_STATS mode " + std::to_string(c->opt_time_stats) + " does not hold");
+        if (c->ts_steps == 0) return fail(c, FS3D_ERR_INVALID, std::string(what) + ": the window of FS3D_OPT_TIME_STATS holds no time step yet");
+    }
     HIPCHK(c, hipSetDevice(c->device));
     return c->prec == FS3D_F32 ? get_layer_impl<float>(c, (float *)outV, outT, odx, ody, odz, local, dev, rows)
                                : get_layer_impl<double>(c, (double *)outV, outT, odx, ody, odz, local, dev, rows);

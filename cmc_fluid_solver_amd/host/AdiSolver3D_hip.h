@@ -146,6 +146,14 @@ public:
     // FS3D_OPT_OUTPUT_VECTOR for the same calls: 0 resVel holds the velocity, 1 the vorticity (central differences on the NODE_IN
     // cells whose six neighbours are no NODE_OUT cells, 99999 on NODE_OUT cells, 0 elsewhere); slab solvers throw as above
     void SetOutputVector(int mode) { chk(fs3d_set_option(ctx_, FS3D_OPT_OUTPUT_VECTOR, mode)); }
+    // FS3D_OPT_TIME_STATS: 1 -- from now on every TimeStep that succeeds adds its result to per-cell sums on the device (the cells
+    // that are NODE_IN at that step), 2 -- and its squares, 0 -- off, the sums are freed.  EVERY call opens a new window.  Works on
+    // a slab solver as on a single one (a cell asks nothing of a neighbour)
+    void SetTimeStats(int mode) { chk(fs3d_set_option(ctx_, FS3D_OPT_TIME_STATS, mode)); }
+    // FS3D_OPT_OUTPUT_SOURCE for the GetLayer / GetLayerRows calls that follow: 0 `next` as always, 1 the time mean of the window,
+    // 2 its variance (needs SetTimeStats(2)), 3 the fluid fraction (in T; the velocity is 0).  The calls throw (FS3D_ERR_INVALID)
+    // for a source the mode does not hold and for a window without a step; filter and vector apply to the statistic layer
+    void SetOutputSource(int source) { chk(fs3d_set_option(ctx_, FS3D_OPT_OUTPUT_SOURCE, source)); }
     // FS3D_OPT_FRESH_CELLS: with it on, every UpdateGrid* call of a single-GPU solver keeps the node types of the geometry it
     // replaces, and FillFreshCells, called directly after the update and before UpdateBoundaries, gives every cell of `cur` that
     // the update turned NODE_IN the mean of its fluid neighbours (fs3d_fill_fresh_cells; no reference

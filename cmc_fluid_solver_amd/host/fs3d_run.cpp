@@ -1,5 +1,5 @@
 // Command-line driver: the reference's FluidSolver3D main (FluidSolver3D/FluidSolver3D.cpp:60-330) on top of
-// libfs3d_hip.so.   fs3d_run <input data> <output prefix> <config> [align] [GPU [n]] [double] [moving [--host-extrusion] [--time-geometry]] [moving-mesh [--host-voxels | --slab-voxels] [--time-geometry] [--time-both]] [--time-output] [--steps N] [--same-device] [--grid-only FILE [--grid-time T]] [--watertight [--thin-shell] [--wall-velocity motion|file]] [--wall-temperature T] [--fresh-cells | --slab-fresh-cells] [--output-filter point|box]
+// libfs3d_hip.so.   fs3d_run <input data> <output prefix> <config> [align] [GPU [n]] [double] [moving [--host-extrusion] [--time-geometry]] [moving-mesh [--host-voxels | --slab-voxels] [--time-geometry] [--time-both]] [--time-output] [--steps N] [--same-device] [--grid-only FILE [--grid-time T]] [--watertight [--thin-shell] [--wall-velocity motion|file]] [--wall-temperature T] [--fresh-cells | --slab-fresh-cells] [--output-filter point|box] [--time-stats mean|variance]
 //   * reads the config (host/Config.h) and a Shape2D, Shape3D or SeaNetCDF geometry (host/Shape2D.h, Shape3D.h, SeaNetCDF.h), prints the grid summary lines
 //     the reference prints ("Grid = X x Y x Z", "NODE_IN points = ..."),
 //   * runs the same loop: dt = cycle length / (frames * time_steps), UpdateBoundaries + TimeStep per step with the
@@ -54,6 +54,14 @@
 //   fluid); `point`, the default, is the reference's sample.  With an output grid at least as fine as the grid the two are the same
 //   bytes.  `box` is refused with GPU n, n > 1, when the arguments are read: a box can straddle the cut between two x-slabs.
 //   (The vorticity, FS3D_OPT_OUTPUT_VECTOR, has no word: the result file's variables are the reference's u, v, w, T.)
+// --time-stats mean|variance: SetTimeStats(1 | 2) before the loop -- every time step adds its result to per-cell sums on the device
+//   (FS3D_OPT_TIME_STATS) -- and after the loop one more file, <prefix>_stats.nc, with the header of _res.nc: record 0 is the time mean of
+//   u, v, w, T over the steps of the run, with `variance` record 1 is their variance, the last record is the fluid fraction (the share of the
+//   steps a cell was NODE_IN, in T; u = v = w = 0).  Each record is taken by GetLayer (GPU n: GetLayerRows, as the normal records are) at
+//   the config's output dims with SetOutputSource(1 | 2 | 3), cells that are NODE_OUT at the end carry 99999, --output-filter box applies
+//   to them as to every record; the record axis of that file counts statistics, not time.  _res.nc and every other line are those of
+//   the run without the word.  The last line: "Time statistics: <N> steps, mean[, variance] in <file>".  A run of no step (--steps 0)
+//   has no window to read: no file is written and the line is "Time statistics: 0 steps, no file".
 // --time-output: one closing line, the host clock per output record around the GetLayer call (GPU n: rank 0's call and the barrier that
 //   completes the record) and around AppendLayer, with the number of records.
 // There is no CPU backend here: without a GPU the run stops with the library's error.
@@ -98,6 +106,7 @@ struct RunOptions {
     double grid_time = -1, wall_T = 0;
     int wall_velocity = 0;                             // 0: walls at rest; 1: motion; 2: file (Shape3D::wall_velocity)
     bool has_wall_T = false, fresh_cells = false, slab_fresh_cells = false, output_box = false;
+    int time_stats = 0;                                // --time-stats: 0 none, 1 mean, 2 mean and variance (FS3D_OPT_TIME_STATS)
     int nslabs = 1, device = 0;
     long max_steps = -1;
     std::string grid_only;
@@ -106,6 +115,14 @@ struct RunOptions {
 template <typename FTYPE>
 static int run_slabs(fs3d::Grid3D<FTYPE> &grid, fs3d::Grid2D &g2, fs3d::Shape3D &sh3, const RunGeom &geo, const std::string &prefix,
                      const fs3d::Config &cfg, const RunOptions &o);
+
+// --time-stats: the sources of the records of <prefix>_stats.nc, in order (FS3D_OPT_OUTPUT_SOURCE: 1 mean, 2 variance, 3 fluid fraction)
+static std::vector<int> stats_sources(int time_stats) { return time_stats == 2 ? std::vector<int>{1, 2, 3} : std::vector<int>{1, 3}; }
+static void print_stats_line(long steps, int time_stats, const std::string &file)
+{
+    if (steps > 0) std::printf("Time statistics: %ld steps, mean%s in %s\n", steps, time_stats == 2 ? ", variance" : "", file.c_str());
+    else std::printf("Time statistics: 0 steps, no file\n");
+}
 
 template <typename FTYPE>
 static int run(const std::string &data, const std::string &prefix, const fs3d::Config &cfg, const RunOptions &o)
@@ -192,6 +209,7 @@ static int run(const std::string &data, const std::string &prefix, const fs3d::C
     if (o.thin_shell) solver.SetMeshShell(1);
     if (o.fresh_cells) solver.SetFreshCells(true);
     if (o.output_box) solver.SetOutputFilter(1);
+    if (o.time_stats) solver.SetTimeStats(o.time_stats);
     std::printf("Segments: %i %i %i (x, y, z)\n", solver.numSegs[0], solver.numSegs[1], solver.numSegs[2]);
 
     const int frames = geo.frames;                                     // FluidSolver3D.cpp:194-195
@@ -338,6 +356,21 @@ static int run(const std::string &data, const std::string &prefix, const fs3d::C
                     out_ms[1] / nc.NumRecords(), nc.NumRecords());
     std::printf("%ld steps in %.3f s: %.1f Mcells/s; %u layers in %s\n", steps, sec,
                 (double)grid.dimx * grid.dimy * grid.dimz * steps / sec / 1e6, nc.NumRecords(), out.c_str());
+    if (o.time_stats) {
+        const std::string stats = prefix + "_stats.nc";
+        if (steps > 0) {
+            NetCDF3Writer ns;
+            ns.Create(stats, bbox, dt * cfg.out_time_steps, finaltime, cfg.outdimx, cfg.outdimy, cfg.outdimz, cfg.out_vars, geo.depths != nullptr,
+                      geo.depths ? out_depths.depth.data() : nullptr);
+            for (int source : stats_sources(o.time_stats)) {
+                solver.SetOutputSource(source);
+                solver.GetLayer(resVel.data(), resT.data(), cfg.outdimx, cfg.outdimy, cfg.outdimz);
+                ns.AppendLayer(resVel.data(), resT.data());
+            }
+            solver.SetOutputSource(0);
+        }
+        print_stats_line(steps, o.time_stats, stats);
+    }
     return 0;
 }
 
@@ -384,7 +417,8 @@ static int run_slabs(fs3d::Grid3D<FTYPE> &grid, fs3d::Grid2D &g2, fs3d::Shape3D 
                                                         : FluidParams<FTYPE>(cfg.viscosity, cfg.density, cfg.R_specific, cfg.k, cfg.cv);
     const double length = geo.length, dt = length / (geo.frames * cfg.time_steps), finaltime = length * cfg.cycles;
     const std::string out = prefix + "_res.nc";
-    NetCDF3Writer nc;
+    NetCDF3Writer nc, ns;                              // ns: --time-stats, <prefix>_stats.nc (rank 0 creates and appends)
+    const std::string stats = prefix + "_stats.nc";
     const float *bbox = geo.bbox;
     DepthInfo3D out_depths;                                                                  // IO.h:270-273
     if (geo.depths) out_depths = DepthInfo3D(cfg.outdimx, cfg.outdimy, *geo.depths);
@@ -410,6 +444,7 @@ static int run_slabs(fs3d::Grid3D<FTYPE> &grid, fs3d::Grid2D &g2, fs3d::Shape3D 
                 if (o.watertight) solver.SetMeshVoxels(1);           // the updates voxelise as the host loader did
                 if (o.thin_shell) solver.SetMeshShell(1);
                 if (o.fresh_cells) { solver.SetFreshCells(true); solver.SetFreshCellsSlabs(true); }
+                if (o.time_stats) solver.SetTimeStats(o.time_stats);
                 // every rank has uploaded the grid of time 0 before rank 0 writes the next geometry into the same arrays (Init
                 // reads them, and joining the group is no rendezvous)
                 if (moves) bar.wait();
@@ -463,6 +498,20 @@ static int run_slabs(fs3d::Grid3D<FTYPE> &grid, fs3d::Grid2D &g2, fs3d::Shape3D 
                     if (moves) { solver.ClearOutterCells(); bar.wait(); }      // AdiSolver3D.cpp:382-385; every rank has read this step's geometry
                 }
                 if (r == 0) steps_done = steps;
+                if (o.time_stats && steps > 0) {
+                    // the statistics records as the normal ones: every slab writes its rows of the shared arrays, rank 0 appends
+                    if (r == 0) ns.Create(stats, bbox, dt * cfg.out_time_steps, finaltime, cfg.outdimx, cfg.outdimy, cfg.outdimz, cfg.out_vars,
+                                          geo.depths != nullptr, geo.depths ? out_depths.depth.data() : nullptr);
+                    for (int source : stats_sources(o.time_stats)) {
+                        int rows[2];
+                        solver.SetOutputSource(source);
+                        solver.GetLayerRows(resVel.data(), resT.data(), cfg.outdimx, cfg.outdimy, cfg.outdimz, rows);
+                        bar.wait();
+                        if (r == 0) ns.AppendLayer(resVel.data(), resT.data());
+                        bar.wait();
+                    }
+                    solver.SetOutputSource(0);
+                }
             } catch (...) {
                 // release the other slab threads: they wait for this one in the transport (halo planes, carries) or at the
                 // output barrier and would never return
@@ -489,13 +538,14 @@ static int run_slabs(fs3d::Grid3D<FTYPE> &grid, fs3d::Grid2D &g2, fs3d::Shape3D 
                     out_ms[1] / nc.NumRecords(), nc.NumRecords());
     std::printf("%ld steps in %.3f s: %.1f Mcells/s; %u layers in %s\n", steps_done, sec,
                 (double)grid.dimx * grid.dimy * grid.dimz * steps_done / sec / 1e6, nc.NumRecords(), out.c_str());
+    if (o.time_stats) print_stats_line(steps_done, o.time_stats, stats);
     return 0;
 }
 
 int main(int argc, char **argv)
 {
     if (argc < 4) {
-        std::printf("Usage: %s <input data> <output prefix> <config file> [align] [GPU [n]] [double] [--steps N] [moving [--host-extrusion] [--time-geometry]] [moving-mesh [--host-voxels | --slab-voxels] [--time-geometry] [--time-both]] [--time-output] [--grid-only FILE [--grid-time T]] [--grid-images] [--watertight [--thin-shell] [--wall-velocity motion|file]] [--wall-temperature T] [--fresh-cells | --slab-fresh-cells] [--output-filter point|box]\n", argv[0]);
+        std::printf("Usage: %s <input data> <output prefix> <config file> [align] [GPU [n]] [double] [--steps N] [moving [--host-extrusion] [--time-geometry]] [moving-mesh [--host-voxels | --slab-voxels] [--time-geometry] [--time-both]] [--time-output] [--grid-only FILE [--grid-time T]] [--grid-images] [--watertight [--thin-shell] [--wall-velocity motion|file]] [--wall-temperature T] [--fresh-cells | --slab-fresh-cells] [--output-filter point|box] [--time-stats mean|variance]\n", argv[0]);
         return 0;
     }
     try {
@@ -539,6 +589,11 @@ int main(int argc, char **argv)
                 const std::string w = a + 1 < argc ? argv[++a] : "";
                 if (w != "point" && w != "box") throw std::runtime_error("--output-filter: point or box");
                 o.output_box = w == "box";
+            }
+            else if (s == "--time-stats") {
+                const std::string w = a + 1 < argc ? argv[++a] : "";
+                if (w != "mean" && w != "variance") throw std::runtime_error("--time-stats: mean or variance");
+                o.time_stats = w == "mean" ? 1 : 2;
             }
             else if (s == "--time-both") o.time_both = true;
             else if (s == "--host-extrusion") o.host_extrusion = true;
