@@ -36,6 +36,9 @@ OPT_TIME_STATS = 14       # 1: every successful time step adds the new `cur` to 
 TIME_STATS = {"off": 0, "mean": 1, "variance": 2}
 OPT_OUTPUT_SOURCE = 15    # what the three GetLayer entries sample: 0 `next` (default), 1 the time mean, 2 the time variance, 3 the fluid fraction (time_stats.py is the rule)
 OUTPUT_SOURCE = {"next": 0, "mean": 1, "variance": 2, "fraction": 3}
+OPT_TIME_STATS_CROSS = 16  # 1: mode 2 also sums the six products uv, uw, vw, uT, vT, wT per cell; every set opens a new window, 0 frees them (default 0)
+OPT_OUTPUT_MOMENT = 17    # what source 2 builds: 0 the variances (default), 1 the Reynolds stresses and k, 2 the heat fluxes and var_T (time_stats.MOMENTS)
+OPT_TIME_STATS_EVERY = 18  # the stride k of the accumulated steps, 1 (default) .. 2^20: candidate s of a window counts where (s - 1) % k == 0; every set opens a new window
 XSOLVE_AUTO, XSOLVE_PIPELINED, XSOLVE_REDUCED, XSOLVE_REDUCED_A2A = 0, 1, 2, 3
 
 # every function include/fs3d.h declares, in the header's order: name -> (restype, argtypes)

@@ -188,16 +188,25 @@ struct fs3d_ctx {
     int opt_out_filter = 0;                // FS3D_OPT_OUTPUT_FILTER: 1 = the GetLayer entries average the NODE_IN cells of every sample's box (k_get_layer_box)
     int opt_out_vector = 0;                // FS3D_OPT_OUTPUT_VECTOR: 1 = their outV holds the vorticity (k_get_layer_box<R, true>)
     // time statistics (kernels_stats.hip): per own cell, no ghost planes -- the steps it was NODE_IN (ts_n), the double sums of U, V, W, T
-    // over those steps (ts_s1, field v at + v * ts_stride) and, in mode 2, of their squares (ts_s2).  Allocated by the first
-    // accumulation, counted in geom_allocs, freed when the option is set to 0; ts_q is the statistic layer of the read-out (4 fields of
-    // ts_stride reals), allocated by the first fs3d_get_layer* call with a source other than 0 and kept
+    // over those steps (ts_s1, field v at + v * ts_stride), in mode 2 of their squares (ts_s2) and, in mode 2 with
+    // FS3D_OPT_TIME_STATS_CROSS, of the six products uv, uw, vw, uT, vT, wT (ts_sx, pair p at + p * ts_stride).  Each is allocated by
+    // the first accumulation that needs it, counted in geom_allocs and kept over later windows; all are freed when FS3D_OPT_TIME_STATS is
+    // set to 0, ts_sx also when the CROSS option is.  Every set of FS3D_OPT_TIME_STATS, _CROSS or _EVERY opens a new window: ts_steps and
+    // ts_candidates 0, ts_clear.  A candidate is a step that reached fs3d_time_stats_accumulate (a successful fs3d_time_step, every
+    // fs3d_time_step_async); candidate s = 1, 2, .. is accumulated where (s - 1) % opt_ts_every == 0, nothing runs on the others.
+    // ts_q is the statistic layer of the read-out (4 fields of ts_stride reals), allocated by the first fs3d_get_layer* call with a
+    // source other than 0 and kept; with source 2, opt_out_moment chooses the variances, the Reynolds stresses or the heat fluxes
     int opt_time_stats = 0;                // FS3D_OPT_TIME_STATS: 0 off, 1 first moments, 2 first and second moments
+    int opt_ts_cross = 0;                  // FS3D_OPT_TIME_STATS_CROSS: 1 = mode 2 also accumulates the six cross sums
+    int opt_ts_every = 1;                  // FS3D_OPT_TIME_STATS_EVERY: the stride k of the accumulated steps, 1 .. 2^20
     int opt_out_source = 0;                // FS3D_OPT_OUTPUT_SOURCE: 0 `next`, 1 time mean, 2 time variance, 3 fluid fraction
+    int opt_out_moment = 0;                // FS3D_OPT_OUTPUT_MOMENT: what source 2 builds -- 0 variances, 1 Reynolds stresses and k, 2 heat fluxes and var_T
     long long ts_steps = 0;                // N: accumulated steps of the open window
+    long long ts_candidates = 0;           // candidate steps of the open window, accumulated or not
     bool ts_clear = false;                 // the window is new: the next accumulation zeroes the accumulators first
     long long ts_stride = 0;               // ncell rounded up to 4 (every field of the accumulators starts on 16 bytes)
     DevBuf<unsigned> ts_n;
-    DevBuf<double> ts_s1, ts_s2;
+    DevBuf<double> ts_s1, ts_s2, ts_sx;
     DevBuf<> ts_q;
     int opt_err_order = 0;                 // FS3D_OPT_ERR_ORDER: 1 = EvalDivError sums its per-cell terms serially in cell order (host), as the CPU path
     DevBuf<double> err_terms;              // ... one term per cell (device, allocated on first use)
@@ -272,12 +281,16 @@ static inline bool stream_reserve(fs3d_ctx *c, std::initializer_list<BufWant<Dev
 // kernels_geom.hip
 void fs3d_geom_destroy(fs3d_ctx *c);
 
-// kernels_stats.hip: FS3D_OPT_TIME_STATS / FS3D_OPT_OUTPUT_SOURCE
-// one accumulation of FS3D_LAYER_CUR into the window, enqueued on the context's stream (the first one allocates and clears)
+// kernels_stats.hip: FS3D_OPT_TIME_STATS / _CROSS / _EVERY, FS3D_OPT_OUTPUT_SOURCE / _MOMENT
+// one candidate step of the window: where the stride takes it, one accumulation of FS3D_LAYER_CUR, enqueued on the context's stream
+// (the first one allocates and clears); else nothing
 fs3d_status fs3d_time_stats_accumulate(fs3d_ctx *c);
-// the statistic layer of `source` (1 mean, 2 variance, 3 fluid fraction) into ts_q, enqueued; q_out: its four fields
-fs3d_status fs3d_time_stats_layer(fs3d_ctx *c, int source, void *q_out[4], bool *grown);
+// the statistic layer of `source` (1 mean, 2 second moments -- `moment` 0 variance, 1 stresses, 2 heat fluxes --, 3 fluid fraction)
+// into ts_q, enqueued; q_out: its four fields
+fs3d_status fs3d_time_stats_layer(fs3d_ctx *c, int source, int moment, void *q_out[4], bool *grown);
+// all accumulators / the cross sums alone; the caller has synchronised the stream
 void fs3d_time_stats_free(fs3d_ctx *c);
+void fs3d_time_stats_free_cross(fs3d_ctx *c);
 
 // kernels_*.hip
 // What a sweep launcher did.  NA: it does not cover these dims / this precision / this slab form -- the caller may try the

@@ -514,16 +514,33 @@ extern "C" fs3d_status fs3d_set_option(fs3d_ctx *c, int option, int value)
     case FS3D_OPT_TIME_STATS:
         // every call opens a new window; 0 gives the accumulators back (what the stream still does with them finishes first)
         if (value < 0 || value > 2) return fail(c, FS3D_ERR_INVALID, "bad time-statistics mode (0: off, 1: first moments, 2: first and second moments)");
-        c->opt_time_stats = value; c->ts_steps = 0; c->ts_clear = true;
+        c->opt_time_stats = value; c->ts_steps = 0; c->ts_candidates = 0; c->ts_clear = true;
         if (value == 0 && c->ts_n.raw()) {
             HIPCHK(c, hipSetDevice(c->device));
             HIPCHK(c, hipStreamSynchronize(c->stream));
             fs3d_time_stats_free(c);
         }
         return FS3D_OK;
+    case FS3D_OPT_TIME_STATS_CROSS:
+        // a new window as above; 0 gives the cross sums back
+        if (value != 0 && value != 1) return fail(c, FS3D_ERR_INVALID, "bad time-statistics cross value (0: off, 1: mode 2 also sums the six products uv, uw, vw, uT, vT, wT)");
+        c->opt_ts_cross = value; c->ts_steps = 0; c->ts_candidates = 0; c->ts_clear = true;
+        if (value == 0 && c->ts_sx.raw()) {
+            HIPCHK(c, hipSetDevice(c->device));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            fs3d_time_stats_free_cross(c);
+        }
+        return FS3D_OK;
+    case FS3D_OPT_TIME_STATS_EVERY:
+        if (value < 1 || value > (1 << 20)) return fail(c, FS3D_ERR_INVALID, "bad time-statistics stride (1 .. 2^20: every k-th step of a window is accumulated, the first one always)");
+        c->opt_ts_every = value; c->ts_steps = 0; c->ts_candidates = 0; c->ts_clear = true;
+        return FS3D_OK;
     case FS3D_OPT_OUTPUT_SOURCE:
         if (value < 0 || value > 3) return fail(c, FS3D_ERR_INVALID, "bad output source id (0: `next`, 1: time mean, 2: time variance, 3: fluid fraction)");
         c->opt_out_source = value; return FS3D_OK;
+    case FS3D_OPT_OUTPUT_MOMENT:
+        if (value < 0 || value > 2) return fail(c, FS3D_ERR_INVALID, "bad output moment id (0: variances, 1: Reynolds stresses and k, 2: turbulent heat fluxes and var_T)");
+        c->opt_out_moment = value; return FS3D_OK;
     case FS3D_OPT_XSOLVE:
         if (value < 0 || value > 3) return fail(c, FS3D_ERR_INVALID, "bad cross-slab X solve id");
         c->opt_xsolve = value; return FS3D_OK;
@@ -1315,7 +1332,7 @@ extern "C" fs3d_status fs3d_synchronize(fs3d_ctx *c)
 // of the GLOBAL output whose source plane it holds.  `dev`: outV / outT are on the context's device, the kernel writes them and
 // the call returns after the enqueue; else the owned samples go through the staging buffer and the call returns synchronised.
 // FS3D_OPT_OUTPUT_FILTER / FS3D_OPT_OUTPUT_VECTOR: k_get_layer_box in place of k_get_layer, everything around it as it is.
-// FS3D_OPT_OUTPUT_SOURCE 1..3: the statistic layer of kernels_stats.hip, in a buffer of its own, takes the place of `next` -- stamp,
+// FS3D_OPT_OUTPUT_SOURCE 1..3 (source 2: the layer FS3D_OPT_OUTPUT_MOMENT chooses): the statistic layer of kernels_stats.hip, in a buffer of its own, takes the place of `next` -- stamp,
 // gather or box kernel, staging and copies run on it unchanged; `next` and `cur` are not written.
 template <typename R>
 static fs3d_status get_layer_impl(fs3d_ctx *c, R *outV, double *outT, int odx, int ody, int odz, bool local, bool dev, int rows[2])
@@ -1343,7 +1360,7 @@ static fs3d_status get_layer_impl(fs3d_ctx *c, R *outV, double *outT, int odx, i
     R *F[4] = {fld<R>(c, b, 0), fld<R>(c, b, 1), fld<R>(c, b, 2), fld<R>(c, b, 3)};
     if (c->opt_out_source) {
         bool grown = false;
-        GTRY(fs3d_time_stats_layer(c, c->opt_out_source, (void **)F, &grown));
+        GTRY(fs3d_time_stats_layer(c, c->opt_out_source, c->opt_out_source == 2 ? c->opt_out_moment : 0, (void **)F, &grown));
         c->gl_info[2] += grown;
     }
     hipLaunchKernelGGL((k_clear_type<R>), dim3(grid_for(c->ncell)), dim3(256), 0, c->stream, c->code, c->ncell,
@@ -1392,6 +1409,14 @@ static fs3d_status get_layer_entry(fs3d_ctx *c, const char *what, void *outV, do
         if (c->opt_time_stats == 0 || (c->opt_out_source == 2 && c->opt_time_stats < 2))
             return fail(c, FS3D_ERR_INVALID, std::string(what) + ": FS3D_OPT_OUTPUT_SOURCE asks for " + names[c->opt_out_source] +
                                              ", which the FS3D_OPT_TIME_STATS mode " + std::to_string(c->opt_time_stats) + " does not hold");
+        if (c->opt_out_source == 2 && c->opt_out_moment) {         // the moment is read for source 2 only
+            if (c->opt_time_stats < 2 || !c->opt_ts_cross)
+                return fail(c, FS3D_ERR_INVALID, std::string(what) + ": FS3D_OPT_OUTPUT_MOMENT " + std::to_string(c->opt_out_moment) +
+                                                 " asks for covariances, and the open window holds no cross sums (FS3D_OPT_TIME_STATS 2 with FS3D_OPT_TIME_STATS_CROSS 1)");
+            if (c->opt_out_vector)
+                return fail(c, FS3D_ERR_INVALID, std::string(what) + ": FS3D_OPT_OUTPUT_MOMENT " + std::to_string(c->opt_out_moment) +
+                                                 " with FS3D_OPT_OUTPUT_VECTOR 1 (the curl of a stress layer means nothing)");
+        }
         if (c->ts_steps == 0) return fail(c, FS3D_ERR_INVALID, std::string(what) + ": the window of FS3D_OPT_TIME_STATS holds no time step yet");
     }
     HIPCHK(c, hipSetDevice(c->device));

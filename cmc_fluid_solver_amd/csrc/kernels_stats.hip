@@ -1,5 +1,6 @@
-// Time statistics (FS3D_OPT_TIME_STATS, FS3D_OPT_OUTPUT_SOURCE; no reference counterpart): running sums of the fields over the
-// time steps of a window, and the statistic layers the result output reads in place of `next`.  The rule and its numpy twin:
+// Time statistics (FS3D_OPT_TIME_STATS, FS3D_OPT_TIME_STATS_CROSS, FS3D_OPT_TIME_STATS_EVERY, FS3D_OPT_OUTPUT_SOURCE,
+// FS3D_OPT_OUTPUT_MOMENT; no reference counterpart): running sums of the fields and of their products over the accumulated time steps
+// of a window, and the statistic layers the result output reads in place of `next`.  The rule and its numpy twin:
 // cmc_fluid_solver_amd/time_stats.py.  Per cell, nothing from a neighbour: a slab accumulates and reads out its own planes.
 // Built with -ffp-contract=off like everything outside kernels_part.hip: every operation below is rounded once in double.
 #include "fs3d_common.h"
@@ -8,6 +9,10 @@ typedef float ts_f4 __attribute__((ext_vector_type(4)));
 typedef double ts_d2 __attribute__((ext_vector_type(2)));
 typedef unsigned ts_u4 __attribute__((ext_vector_type(4)));
 typedef unsigned ts_u2 __attribute__((ext_vector_type(2)));
+
+// the six cross sums of FS3D_OPT_TIME_STATS_CROSS: pair p is the fields (ts_pair_a(p), ts_pair_b(p)) of U, V, W, T -- uv, uw, vw, uT, vT, wT
+static __device__ __forceinline__ constexpr int ts_pair_a(int p) { return p < 2 ? 0 : p == 2 ? 1 : p - 3; }
+static __device__ __forceinline__ constexpr int ts_pair_b(int p) { return p == 0 ? 1 : p < 3 ? 2 : 3; }
 
 // four consecutive values of a field, widened to double
 static __device__ __forceinline__ void ts_load4(const float *p, double (&x)[4])
@@ -23,16 +28,20 @@ static __device__ __forceinline__ void ts_load4(const double *p, double (&x)[4])
 
 // One accumulation, vector form: a thread owns the four consecutive cells [4q, 4q + 4) -- 8 bytes of codes, 16 bytes of counts, per
 // field 16 (fp32) or 2 x 16 (fp64) bytes of `cur` and 2 x 16 bytes of every sum.  On the NODE_IN cells n += 1, S1 += (double)x and,
-// MODE 2, S2 += (double)x * (double)x; the other cells of a quad are written back as they were read, a quad without a NODE_IN cell
-// is not touched.  Needs ncell % 4 == 0 and every base pointer on 16 bytes (codes: 8); fs3d_time_stats_accumulate decides.
+// MODE 2 and 3, S2 += (double)x * (double)x; MODE 3 (FS3D_OPT_TIME_STATS_CROSS) keeps the four fields of the four cells, 16 doubles,
+// and then streams the six cross sums the same way, S_ab += (double)x_a * (double)x_b for the pairs uv, uw, vw, uT, vT, wT (pair p
+// at sx + p * sstride): 12 more 16-byte loads and stores, 34 against 22 per thread.  The other cells of a quad are written back as
+// they were read, a quad without a NODE_IN cell is not touched.  Needs ncell % 4 == 0 and every base pointer on 16 bytes (codes: 8);
+// fs3d_time_stats_accumulate decides.
 // A pure stream: no LDS, no atomics, one quad per thread and no loop -- 14 (MODE 1) or 22 independent 16-byte loads in flight.
 // Every access is a plain one.  The accumulators are not touched again for a whole step, so nontemporal loads and stores of them
 // were the candidate: measured at 256^3 fp32 in one session they lose, 278.6 against 239.6 us in mode 1 and 503.5 against 447.1 us
 // in mode 2 (profiles/time_stats_cost.txt, which says how the variant was built).
+// MODE 1 and 2 are the instantiations they were: what MODE 3 adds stands under `if constexpr`, and sx is their last, unread argument.
 template <typename R, int MODE>
 __global__ void __launch_bounds__(256) k_time_stats_v4(const uint16_t *__restrict__ code, long long nquad, const R *__restrict__ cur,
                                                         long long fstride, unsigned *__restrict__ cnt, double *__restrict__ s1,
-                                                        double *__restrict__ s2, long long sstride)
+                                                        double *__restrict__ s2, long long sstride, double *__restrict__ sx)
 {
     const long long q = (long long)blockIdx.x * 256 + threadIdx.x;
     if (q >= nquad) return;
@@ -44,9 +53,10 @@ __global__ void __launch_bounds__(256) k_time_stats_v4(const uint16_t *__restric
     ts_u4 n = *(const ts_u4 *)(cnt + l);
     n.x += in[0]; n.y += in[1]; n.z += in[2]; n.w += in[3];
     *(ts_u4 *)(cnt + l) = n;
+    double xs[MODE == 3 ? 4 : 1][4];                          // MODE 3: the fields stay for the cross products
 #pragma unroll
     for (int v = 0; v < 4; v++) {
-        double x[4];
+        double (&x)[4] = xs[MODE == 3 ? v : 0];
         ts_load4(cur + v * fstride + l, x);
 #pragma unroll
         for (int h = 0; h < 2; h++) {
@@ -55,12 +65,26 @@ __global__ void __launch_bounds__(256) k_time_stats_v4(const uint16_t *__restric
             if (in[2 * h]) a.x = a.x + x[2 * h];
             if (in[2 * h + 1]) a.y = a.y + x[2 * h + 1];
             *p1 = a;
-            if constexpr (MODE == 2) {
+            if constexpr (MODE >= 2) {
                 ts_d2 *const p2 = (ts_d2 *)(s2 + v * sstride + l + 2 * h);
                 ts_d2 b = *p2;
                 if (in[2 * h]) b.x = b.x + x[2 * h] * x[2 * h];
                 if (in[2 * h + 1]) b.y = b.y + x[2 * h + 1] * x[2 * h + 1];
                 *p2 = b;
+            }
+        }
+    }
+    if constexpr (MODE == 3) {
+#pragma unroll
+        for (int p = 0; p < 6; p++) {
+            const int a = ts_pair_a(p), b = ts_pair_b(p);
+#pragma unroll
+            for (int h = 0; h < 2; h++) {
+                ts_d2 *const px = (ts_d2 *)(sx + p * sstride + l + 2 * h);
+                ts_d2 c = *px;
+                if (in[2 * h]) c.x = c.x + xs[a][2 * h] * xs[b][2 * h];
+                if (in[2 * h + 1]) c.y = c.y + xs[a][2 * h + 1] * xs[b][2 * h + 1];
+                *px = c;
             }
         }
     }
@@ -70,37 +94,74 @@ __global__ void __launch_bounds__(256) k_time_stats_v4(const uint16_t *__restric
 template <typename R, int MODE>
 __global__ void __launch_bounds__(256) k_time_stats_v1(const uint16_t *__restrict__ code, long long ncell, const R *__restrict__ cur,
                                                         long long fstride, unsigned *__restrict__ cnt, double *__restrict__ s1,
-                                                        double *__restrict__ s2, long long sstride)
+                                                        double *__restrict__ s2, long long sstride, double *__restrict__ sx)
 {
     const long long l = (long long)blockIdx.x * 256 + threadIdx.x;
     if (l >= ncell || ((code[l] >> CODE_TYPE_SHIFT) & 3) != FS3D_NODE_IN) return;
     cnt[l] += 1u;
+    double xs[MODE == 3 ? 4 : 1];
 #pragma unroll
     for (int v = 0; v < 4; v++) {
         const double x = (double)cur[v * fstride + l];
+        if constexpr (MODE == 3) xs[v] = x;
         double *const p1 = s1 + v * sstride + l;
         *p1 = *p1 + x;
-        if constexpr (MODE == 2) {
+        if constexpr (MODE >= 2) {
             double *const p2 = s2 + v * sstride + l;
             *p2 = *p2 + x * x;
+        }
+    }
+    if constexpr (MODE == 3) {
+#pragma unroll
+        for (int p = 0; p < 6; p++) {
+            double *const px = sx + p * sstride + l;
+            *px = *px + xs[ts_pair_a(p)] * xs[ts_pair_b(p)];
         }
     }
 }
 
 // The statistic layer Q of one source, four fields of the context's real type, one cell per thread.  With n the steps the cell was
-// NODE_IN and N the steps of the window: n >= 1 -- m = S1 / (double)n; source 1 (mean): Q = (R)m; source 2 (variance):
-// v = S2 / (double)n - m * m, 0 where negative, Q = (R)v; source 3 (fluid fraction): Q_T = (R)((double)n / (double)N), Q_U = Q_V =
-// Q_W = 0.  n = 0 -- source 1: what the cell holds in `cur` (a wall shows its node values as in every record); sources 2, 3: 0.
+// NODE_IN and N the steps of the window: n >= 1 -- dn = (double)n, m_a = S1_a / dn; source 1 (mean): Q = (R)m; source 2, moment 0
+// (variance): var_a = S2_a / dn - m_a * m_a, 0 where negative, Q = (R)var; source 2, moment 1 (Reynolds stresses):
+// cov(a, b) = S_ab / dn - m_a * m_b, not clamped, Q_U, Q_V, Q_W = (R)cov of uv, uw, vw and Q_T = (R)(0.5 * ((var_u + var_v) + var_w));
+// source 2, moment 2 (turbulent heat flux): Q_U, Q_V, Q_W = (R)cov of uT, vT, wT and Q_T = (R)var_T; source 3 (fluid fraction):
+// Q_T = (R)((double)n / (double)N), Q_U = Q_V = Q_W = 0.  n = 0 -- source 1: what the cell holds in `cur` (a wall shows its node
+// values as in every record); sources 2, 3: 0.  `moment` is read for source 2 only; sx only with a moment other than 0.
 template <typename R>
-__global__ void __launch_bounds__(256) k_time_stats_layer(int source, long long ncell, double steps, const R *__restrict__ cur,
+__global__ void __launch_bounds__(256) k_time_stats_layer(int source, int moment, long long ncell, double steps, const R *__restrict__ cur,
                                                            long long fstride, const unsigned *__restrict__ cnt,
                                                            const double *__restrict__ s1, const double *__restrict__ s2,
-                                                           long long sstride, R *__restrict__ q)
+                                                           const double *__restrict__ sx, long long sstride, R *__restrict__ q)
 {
     const long long l = (long long)blockIdx.x * 256 + threadIdx.x;
     if (l >= ncell) return;
     const unsigned n = cnt[l];
     const double dn = (double)n;
+    if (source == 2 && moment != 0) {
+        R r[4] = {R(0), R(0), R(0), R(0)};
+        if (n) {
+            double m[4], var[4];
+#pragma unroll
+            for (int v = 0; v < 4; v++) {
+                m[v] = s1[v * sstride + l] / dn;
+                const double mm = m[v] * m[v];
+                const double d = s2[v * sstride + l] / dn - mm;
+                var[v] = d < 0.0 ? 0.0 : d;
+            }
+            double cov[6];                                    // every index below is a constant once unrolled: registers
+#pragma unroll
+            for (int p = 0; p < 6; p++) {
+                const double mab = m[ts_pair_a(p)] * m[ts_pair_b(p)];
+                cov[p] = (p < 3) == (moment == 1) ? sx[p * sstride + l] / dn - mab : 0.0;
+            }
+#pragma unroll
+            for (int v = 0; v < 3; v++) r[v] = (R)(moment == 1 ? cov[v] : cov[3 + v]);
+            r[3] = moment == 1 ? (R)(0.5 * ((var[0] + var[1]) + var[2])) : (R)var[3];
+        }
+#pragma unroll
+        for (int v = 0; v < 4; v++) q[v * sstride + l] = r[v];
+        return;
+    }
 #pragma unroll
     for (int v = 0; v < 4; v++) {
         R r = R(0);
@@ -128,53 +189,60 @@ static void launch_accumulate(fs3d_ctx *c)
     const R *const cur = (const R *)c->lay[c->slot[FS3D_LAYER_CUR]] + c->plane;      // first owned cell of field 0
     const uint16_t *const code = c->code;
     bool vec = c->ncell % 4 == 0 && aligned(code, 8) && aligned(c->ts_n.raw(), 16) && aligned(c->ts_s1.raw(), 16) &&
-               (MODE < 2 || aligned(c->ts_s2.raw(), 16));
+               (MODE < 2 || aligned(c->ts_s2.raw(), 16)) && (MODE < 3 || aligned(c->ts_sx.raw(), 16));
     for (int v = 0; v < 4; v++) vec = vec && aligned(cur + v * c->fstride, 16);
     if (vec) {
         const long long nquad = c->ncell / 4;
         hipLaunchKernelGGL((k_time_stats_v4<R, MODE>), dim3((unsigned)((nquad + 255) / 256)), dim3(256), 0, c->stream, code, nquad, cur,
-                           c->fstride, (unsigned *)c->ts_n, (double *)c->ts_s1, (double *)c->ts_s2, c->ts_stride);
+                           c->fstride, (unsigned *)c->ts_n, (double *)c->ts_s1, (double *)c->ts_s2, c->ts_stride,
+                           (double *)c->ts_sx);
     } else {
         hipLaunchKernelGGL((k_time_stats_v1<R, MODE>), dim3((unsigned)((c->ncell + 255) / 256)), dim3(256), 0, c->stream, code, c->ncell, cur,
-                           c->fstride, (unsigned *)c->ts_n, (double *)c->ts_s1, (double *)c->ts_s2, c->ts_stride);
+                           c->fstride, (unsigned *)c->ts_n, (double *)c->ts_s1, (double *)c->ts_s2, c->ts_stride,
+                           (double *)c->ts_sx);
     }
 }
 
 fs3d_status fs3d_time_stats_accumulate(fs3d_ctx *c)
 {
+    // FS3D_OPT_TIME_STATS_EVERY: candidate s = 1, 2, .. of the window is taken where (s - 1) % k == 0; on the others nothing runs
+    if (c->ts_candidates++ % c->opt_ts_every) return FS3D_OK;
     const int mode = c->opt_time_stats;
-    const size_t sbytes = (size_t)4 * c->ts_stride * sizeof(double);
+    const bool cross = mode == 2 && c->opt_ts_cross;
+    const size_t sbytes = (size_t)4 * c->ts_stride * sizeof(double), xbytes = (size_t)6 * c->ts_stride * sizeof(double);
     if (c->ts_clear) {
         // a new window: the buffers of the mode (kept from the window before where they exist), zeroed
         long long *const na = &c->geom_allocs;
         BUFCHK(c, c->ts_n.reserve((size_t)c->ts_stride * sizeof(unsigned), na));
         BUFCHK(c, c->ts_s1.reserve(sbytes, na));
         if (mode == 2) BUFCHK(c, c->ts_s2.reserve(sbytes, na));
+        if (cross) BUFCHK(c, c->ts_sx.reserve(xbytes, na));
         HIPCHK(c, hipMemsetAsync(c->ts_n, 0, (size_t)c->ts_stride * sizeof(unsigned), c->stream));
         HIPCHK(c, hipMemsetAsync(c->ts_s1, 0, sbytes, c->stream));
         if (mode == 2) HIPCHK(c, hipMemsetAsync(c->ts_s2, 0, sbytes, c->stream));
+        if (cross) HIPCHK(c, hipMemsetAsync(c->ts_sx, 0, xbytes, c->stream));
         c->ts_clear = false;
     }
-    if (c->prec == FS3D_F32) { if (mode == 2) launch_accumulate<float, 2>(c); else launch_accumulate<float, 1>(c); }
-    else { if (mode == 2) launch_accumulate<double, 2>(c); else launch_accumulate<double, 1>(c); }
+    if (c->prec == FS3D_F32) { if (cross) launch_accumulate<float, 3>(c); else if (mode == 2) launch_accumulate<float, 2>(c); else launch_accumulate<float, 1>(c); }
+    else { if (cross) launch_accumulate<double, 3>(c); else if (mode == 2) launch_accumulate<double, 2>(c); else launch_accumulate<double, 1>(c); }
     HIPCHK(c, hipGetLastError());
     c->ts_steps++;
     return FS3D_OK;
 }
 
 template <typename R>
-static void launch_layer(fs3d_ctx *c, int source)
+static void launch_layer(fs3d_ctx *c, int source, int moment)
 {
     const R *const cur = (const R *)c->lay[c->slot[FS3D_LAYER_CUR]] + c->plane;
-    hipLaunchKernelGGL((k_time_stats_layer<R>), dim3((unsigned)((c->ncell + 255) / 256)), dim3(256), 0, c->stream, source, c->ncell,
-                       (double)c->ts_steps, cur, c->fstride, (const unsigned *)c->ts_n, (const double *)c->ts_s1, (const double *)c->ts_s2,
-                       c->ts_stride, (R *)c->ts_q);
+    hipLaunchKernelGGL((k_time_stats_layer<R>), dim3((unsigned)((c->ncell + 255) / 256)), dim3(256), 0, c->stream, source, moment,
+                       c->ncell, (double)c->ts_steps, cur, c->fstride, (const unsigned *)c->ts_n, (const double *)c->ts_s1,
+                       (const double *)c->ts_s2, (const double *)c->ts_sx, c->ts_stride, (R *)c->ts_q);
 }
 
-fs3d_status fs3d_time_stats_layer(fs3d_ctx *c, int source, void *q_out[4], bool *grown)
+fs3d_status fs3d_time_stats_layer(fs3d_ctx *c, int source, int moment, void *q_out[4], bool *grown)
 {
     BUFCHK(c, c->ts_q.reserve((size_t)4 * c->ts_stride * c->esize, nullptr, grown));
-    if (c->prec == FS3D_F32) launch_layer<float>(c, source); else launch_layer<double>(c, source);
+    if (c->prec == FS3D_F32) launch_layer<float>(c, source, moment); else launch_layer<double>(c, source, moment);
     HIPCHK(c, hipGetLastError());
     for (int v = 0; v < 4; v++) q_out[v] = (char *)c->ts_q.raw() + (size_t)v * c->ts_stride * c->esize;
     return FS3D_OK;
@@ -183,4 +251,7 @@ fs3d_status fs3d_time_stats_layer(fs3d_ctx *c, int source, void *q_out[4], bool 
 void fs3d_time_stats_free(fs3d_ctx *c)
 {
     c->ts_n.reset(&c->geom_allocs); c->ts_s1.reset(&c->geom_allocs); c->ts_s2.reset(&c->geom_allocs);
+    fs3d_time_stats_free_cross(c);
 }
+
+void fs3d_time_stats_free_cross(fs3d_ctx *c) { c->ts_sx.reset(&c->geom_allocs); }

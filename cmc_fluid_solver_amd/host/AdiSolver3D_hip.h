@@ -150,6 +150,17 @@ public:
     // that are NODE_IN at that step), 2 -- and its squares, 0 -- off, the sums are freed.  EVERY call opens a new window.  Works on
     // a slab solver as on a single one (a cell asks nothing of a neighbour)
     void SetTimeStats(int mode) { chk(fs3d_set_option(ctx_, FS3D_OPT_TIME_STATS, mode)); }
+    // FS3D_OPT_TIME_STATS_CROSS: 1 -- with SetTimeStats(2) every accumulated step also adds the six products uv, uw, vw, uT, vT, wT to
+    // per-cell sums (the Reynolds stresses and the turbulent heat fluxes of SetOutputMoment), 0 -- off, those sums are freed.  EVERY
+    // call opens a new window
+    void SetTimeStatsCross(int on) { chk(fs3d_set_option(ctx_, FS3D_OPT_TIME_STATS_CROSS, on)); }
+    // FS3D_OPT_TIME_STATS_EVERY: of the successful TimeSteps of a window the 1st, (k + 1)th, (2k + 1)th, .. are accumulated, on the
+    // others nothing runs; k from 1 (the default) to 2^20.  EVERY call opens a new window
+    void SetTimeStatsEvery(int k) { chk(fs3d_set_option(ctx_, FS3D_OPT_TIME_STATS_EVERY, k)); }
+    // FS3D_OPT_OUTPUT_MOMENT, read while SetOutputSource(2): 0 the four variances, 1 the Reynolds stresses u'v', u'w', v'w' in resVel
+    // and the turbulent kinetic energy in resT, 2 the heat fluxes u'T', v'T', w'T' in resVel and the variance of T in resT.  With 1 or
+    // 2 the calls throw (FS3D_ERR_INVALID) without SetTimeStats(2) and SetTimeStatsCross(1), and with SetOutputVector(1)
+    void SetOutputMoment(int moment) { chk(fs3d_set_option(ctx_, FS3D_OPT_OUTPUT_MOMENT, moment)); }
     // FS3D_OPT_OUTPUT_SOURCE for the GetLayer / GetLayerRows calls that follow: 0 `next` as always, 1 the time mean of the window,
     // 2 its variance (needs SetTimeStats(2)), 3 the fluid fraction (in T; the velocity is 0).  The calls throw (FS3D_ERR_INVALID)
     // for a source the mode does not hold and for a window without a step; filter and vector apply to the statistic layer

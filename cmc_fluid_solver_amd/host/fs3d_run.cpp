@@ -1,5 +1,5 @@
 // Command-line driver: the reference's FluidSolver3D main (FluidSolver3D/FluidSolver3D.cpp:60-330) on top of
-// libfs3d_hip.so.   fs3d_run <input data> <output prefix> <config> [align] [GPU [n]] [double] [moving [--host-extrusion] [--time-geometry]] [moving-mesh [--host-voxels | --slab-voxels] [--time-geometry] [--time-both]] [--time-output] [--steps N] [--same-device] [--grid-only FILE [--grid-time T]] [--watertight [--thin-shell] [--wall-velocity motion|file]] [--wall-temperature T] [--fresh-cells | --slab-fresh-cells] [--output-filter point|box] [--time-stats mean|variance]
+// libfs3d_hip.so.   fs3d_run <input data> <output prefix> <config> [align] [GPU [n]] [double] [moving [--host-extrusion] [--time-geometry]] [moving-mesh [--host-voxels | --slab-voxels] [--time-geometry] [--time-both]] [--time-output] [--steps N] [--same-device] [--grid-only FILE [--grid-time T]] [--watertight [--thin-shell] [--wall-velocity motion|file]] [--wall-temperature T] [--fresh-cells | --slab-fresh-cells] [--output-filter point|box] [--time-stats mean|variance] [--time-covariances] [--time-stats-every K]
 //   * reads the config (host/Config.h) and a Shape2D, Shape3D or SeaNetCDF geometry (host/Shape2D.h, Shape3D.h, SeaNetCDF.h), prints the grid summary lines
 //     the reference prints ("Grid = X x Y x Z", "NODE_IN points = ..."),
 //   * runs the same loop: dt = cycle length / (frames * time_steps), UpdateBoundaries + TimeStep per step with the
@@ -62,6 +62,16 @@
 //   to them as to every record; the record axis of that file counts statistics, not time.  _res.nc and every other line are those of
 //   the run without the word.  The last line: "Time statistics: <N> steps, mean[, variance] in <file>".  A run of no step (--steps 0)
 //   has no window to read: no file is written and the line is "Time statistics: 0 steps, no file".
+// --time-covariances, with --time-stats variance (else refused when the arguments are read: "--time-covariances: needs --time-stats
+//   variance"): SetTimeStatsCross(1) before the loop -- every accumulated step also adds the six products uv, uw, vw, uT, vT, wT to
+//   per-cell sums (FS3D_OPT_TIME_STATS_CROSS) -- and <prefix>_stats.nc holds five records, in this order: mean, variance, Reynolds
+//   stresses (u'v' in u, u'w' in v, v'w' in w, the turbulent kinetic energy in T), turbulent heat flux (u'T' in u, v'T' in v, w'T'
+//   in w, the variance of T in T), fluid fraction; the two new ones are source 2 with SetOutputMoment(1 | 2), taken as the others.
+//   The last line then reads "Time statistics: <N> steps, mean, variance, covariances in <file>".
+// --time-stats-every K, K an integer from 1 to 1048576 (else refused when the arguments are read): SetTimeStatsEvery(K) before the
+//   loop -- of the time steps of the run the 1st, (K + 1)th, (2K + 1)th, .. are accumulated and nothing runs on the others
+//   (FS3D_OPT_TIME_STATS_EVERY); <N> of the last line counts the accumulated steps.  Without --time-stats it has no effect.
+//   Without the two words every file and every print is that of --time-stats alone.
 // --time-output: one closing line, the host clock per output record around the GetLayer call (GPU n: rank 0's call and the barrier that
 //   completes the record) and around AppendLayer, with the number of records.
 // There is no CPU backend here: without a GPU the run stops with the library's error.
@@ -107,6 +117,8 @@ struct RunOptions {
     int wall_velocity = 0;                             // 0: walls at rest; 1: motion; 2: file (Shape3D::wall_velocity)
     bool has_wall_T = false, fresh_cells = false, slab_fresh_cells = false, output_box = false;
     int time_stats = 0;                                // --time-stats: 0 none, 1 mean, 2 mean and variance (FS3D_OPT_TIME_STATS)
+    bool time_cov = false;                             // --time-covariances (FS3D_OPT_TIME_STATS_CROSS; needs time_stats 2)
+    long time_every = 1;                               // --time-stats-every K (FS3D_OPT_TIME_STATS_EVERY)
     int nslabs = 1, device = 0;
     long max_steps = -1;
     std::string grid_only;
@@ -116,11 +128,28 @@ template <typename FTYPE>
 static int run_slabs(fs3d::Grid3D<FTYPE> &grid, fs3d::Grid2D &g2, fs3d::Shape3D &sh3, const RunGeom &geo, const std::string &prefix,
                      const fs3d::Config &cfg, const RunOptions &o);
 
-// --time-stats: the sources of the records of <prefix>_stats.nc, in order (FS3D_OPT_OUTPUT_SOURCE: 1 mean, 2 variance, 3 fluid fraction)
-static std::vector<int> stats_sources(int time_stats) { return time_stats == 2 ? std::vector<int>{1, 2, 3} : std::vector<int>{1, 3}; }
-static void print_stats_line(long steps, int time_stats, const std::string &file)
+// --time-stats: the records of <prefix>_stats.nc, in order, each a source and a moment (FS3D_OPT_OUTPUT_SOURCE: 1 mean, 2 second
+// moments, 3 fluid fraction; FS3D_OPT_OUTPUT_MOMENT: 0 variance, 1 stresses, 2 heat flux)
+struct StatsRecord { int source, moment; };
+static std::vector<StatsRecord> stats_records(const RunOptions &o)
 {
-    if (steps > 0) std::printf("Time statistics: %ld steps, mean%s in %s\n", steps, time_stats == 2 ? ", variance" : "", file.c_str());
+    if (o.time_stats != 2) return {{1, 0}, {3, 0}};
+    if (!o.time_cov) return {{1, 0}, {2, 0}, {3, 0}};
+    return {{1, 0}, {2, 0}, {2, 1}, {2, 2}, {3, 0}};
+}
+// the window's options, before the loop
+template <class Solver>
+static void set_time_stats(Solver &solver, const RunOptions &o)
+{
+    solver.SetTimeStats(o.time_stats);
+    if (o.time_cov) solver.SetTimeStatsCross(1);
+    if (o.time_every > 1) solver.SetTimeStatsEvery((int)o.time_every);
+}
+// steps: the time steps of the run; the line names the accumulated ones, the 1st, (K + 1)th, .. of them
+static void print_stats_line(long steps, const RunOptions &o, const std::string &file)
+{
+    if (steps > 0) std::printf("Time statistics: %ld steps, mean%s%s in %s\n", (steps + o.time_every - 1) / o.time_every,
+                               o.time_stats == 2 ? ", variance" : "", o.time_cov ? ", covariances" : "", file.c_str());
     else std::printf("Time statistics: 0 steps, no file\n");
 }
 
@@ -209,7 +238,7 @@ static int run(const std::string &data, const std::string &prefix, const fs3d::C
     if (o.thin_shell) solver.SetMeshShell(1);
     if (o.fresh_cells) solver.SetFreshCells(true);
     if (o.output_box) solver.SetOutputFilter(1);
-    if (o.time_stats) solver.SetTimeStats(o.time_stats);
+    if (o.time_stats) set_time_stats(solver, o);
     std::printf("Segments: %i %i %i (x, y, z)\n", solver.numSegs[0], solver.numSegs[1], solver.numSegs[2]);
 
     const int frames = geo.frames;                                     // FluidSolver3D.cpp:194-195
@@ -362,14 +391,15 @@ static int run(const std::string &data, const std::string &prefix, const fs3d::C
             NetCDF3Writer ns;
             ns.Create(stats, bbox, dt * cfg.out_time_steps, finaltime, cfg.outdimx, cfg.outdimy, cfg.outdimz, cfg.out_vars, geo.depths != nullptr,
                       geo.depths ? out_depths.depth.data() : nullptr);
-            for (int source : stats_sources(o.time_stats)) {
-                solver.SetOutputSource(source);
+            for (const StatsRecord &rec : stats_records(o)) {
+                solver.SetOutputSource(rec.source);
+                if (o.time_cov) solver.SetOutputMoment(rec.moment);
                 solver.GetLayer(resVel.data(), resT.data(), cfg.outdimx, cfg.outdimy, cfg.outdimz);
                 ns.AppendLayer(resVel.data(), resT.data());
             }
             solver.SetOutputSource(0);
         }
-        print_stats_line(steps, o.time_stats, stats);
+        print_stats_line(steps, o, stats);
     }
     return 0;
 }
@@ -444,7 +474,7 @@ static int run_slabs(fs3d::Grid3D<FTYPE> &grid, fs3d::Grid2D &g2, fs3d::Shape3D 
                 if (o.watertight) solver.SetMeshVoxels(1);           // the updates voxelise as the host loader did
                 if (o.thin_shell) solver.SetMeshShell(1);
                 if (o.fresh_cells) { solver.SetFreshCells(true); solver.SetFreshCellsSlabs(true); }
-                if (o.time_stats) solver.SetTimeStats(o.time_stats);
+                if (o.time_stats) set_time_stats(solver, o);
                 // every rank has uploaded the grid of time 0 before rank 0 writes the next geometry into the same arrays (Init
                 // reads them, and joining the group is no rendezvous)
                 if (moves) bar.wait();
@@ -502,9 +532,10 @@ static int run_slabs(fs3d::Grid3D<FTYPE> &grid, fs3d::Grid2D &g2, fs3d::Shape3D 
                     // the statistics records as the normal ones: every slab writes its rows of the shared arrays, rank 0 appends
                     if (r == 0) ns.Create(stats, bbox, dt * cfg.out_time_steps, finaltime, cfg.outdimx, cfg.outdimy, cfg.outdimz, cfg.out_vars,
                                           geo.depths != nullptr, geo.depths ? out_depths.depth.data() : nullptr);
-                    for (int source : stats_sources(o.time_stats)) {
+                    for (const StatsRecord &rec : stats_records(o)) {
                         int rows[2];
-                        solver.SetOutputSource(source);
+                        solver.SetOutputSource(rec.source);
+                        if (o.time_cov) solver.SetOutputMoment(rec.moment);
                         solver.GetLayerRows(resVel.data(), resT.data(), cfg.outdimx, cfg.outdimy, cfg.outdimz, rows);
                         bar.wait();
                         if (r == 0) ns.AppendLayer(resVel.data(), resT.data());
@@ -538,14 +569,14 @@ static int run_slabs(fs3d::Grid3D<FTYPE> &grid, fs3d::Grid2D &g2, fs3d::Shape3D 
                     out_ms[1] / nc.NumRecords(), nc.NumRecords());
     std::printf("%ld steps in %.3f s: %.1f Mcells/s; %u layers in %s\n", steps_done, sec,
                 (double)grid.dimx * grid.dimy * grid.dimz * steps_done / sec / 1e6, nc.NumRecords(), out.c_str());
-    if (o.time_stats) print_stats_line(steps_done, o.time_stats, stats);
+    if (o.time_stats) print_stats_line(steps_done, o, stats);
     return 0;
 }
 
 int main(int argc, char **argv)
 {
     if (argc < 4) {
-        std::printf("Usage: %s <input data> <output prefix> <config file> [align] [GPU [n]] [double] [--steps N] [moving [--host-extrusion] [--time-geometry]] [moving-mesh [--host-voxels | --slab-voxels] [--time-geometry] [--time-both]] [--time-output] [--grid-only FILE [--grid-time T]] [--grid-images] [--watertight [--thin-shell] [--wall-velocity motion|file]] [--wall-temperature T] [--fresh-cells | --slab-fresh-cells] [--output-filter point|box] [--time-stats mean|variance]\n", argv[0]);
+        std::printf("Usage: %s <input data> <output prefix> <config file> [align] [GPU [n]] [double] [--steps N] [moving [--host-extrusion] [--time-geometry]] [moving-mesh [--host-voxels | --slab-voxels] [--time-geometry] [--time-both]] [--time-output] [--grid-only FILE [--grid-time T]] [--grid-images] [--watertight [--thin-shell] [--wall-velocity motion|file]] [--wall-temperature T] [--fresh-cells | --slab-fresh-cells] [--output-filter point|box] [--time-stats mean|variance] [--time-covariances] [--time-stats-every K]\n", argv[0]);
         return 0;
     }
     try {
@@ -595,6 +626,14 @@ int main(int argc, char **argv)
                 if (w != "mean" && w != "variance") throw std::runtime_error("--time-stats: mean or variance");
                 o.time_stats = w == "mean" ? 1 : 2;
             }
+            else if (s == "--time-covariances") o.time_cov = true;
+            else if (s == "--time-stats-every") {
+                const char *const w = a + 1 < argc ? argv[++a] : "";
+                char *end = nullptr;
+                o.time_every = std::strtol(w, &end, 10);
+                if (end == w || *end || o.time_every < 1 || o.time_every > (1L << 20))
+                    throw std::runtime_error("--time-stats-every: an integer from 1 to 1048576 follows");
+            }
             else if (s == "--time-both") o.time_both = true;
             else if (s == "--host-extrusion") o.host_extrusion = true;
             else if (s == "--time-geometry") o.time_geometry = true;
@@ -604,6 +643,7 @@ int main(int argc, char **argv)
             else if (s == "--grid-images") o.grid_images = true;       // <prefix>_grid_3d/<k>.bmp: the node types, one image per z-slice
             // transpose, decompose: accepted, no effect
         }
+        if (o.time_cov && o.time_stats != 2) throw std::runtime_error("--time-covariances: needs --time-stats variance");
         if (o.output_box && o.nslabs > 1)
             throw std::runtime_error("--output-filter box: single GPU only (with GPU n the grid is cut into x-slabs, a sample's box of source cells can "
                                      "straddle a cut, and the library refuses filtered records on a slab)");

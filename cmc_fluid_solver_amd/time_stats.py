@@ -1,34 +1,50 @@
-"""Time statistics of the fields: what FS3D_OPT_TIME_STATS accumulates and what fs3d_get_layer, fs3d_get_layer_rows and
-fs3d_get_layer_dev sample while FS3D_OPT_OUTPUT_SOURCE is 1, 2 or 3.
+"""Time statistics of the fields: what FS3D_OPT_TIME_STATS (with FS3D_OPT_TIME_STATS_CROSS and FS3D_OPT_TIME_STATS_EVERY)
+accumulates and what fs3d_get_layer, fs3d_get_layer_rows and fs3d_get_layer_dev sample while FS3D_OPT_OUTPUT_SOURCE is 1, 2 or 3
+(source 2: the second-moment layer FS3D_OPT_OUTPUT_MOMENT chooses).
 
 TimeStats is the definition of the rule; the kernels of csrc/kernels_stats.hip equal it bit for bit (every operation below is one
 IEEE double operation, none is fused, and a cell asks nothing of a neighbour, so no order is left free).  The reference has no
 counterpart: every record it writes is one instant.
 
-Accumulation, once per time step, with x each of U, V, W, T of FS3D_LAYER_CUR after the step and `types` the node types of that
+The stride.  A window counts its candidate steps s = 1, 2, ..: every time step that succeeds (a diverged one is no candidate).
+Candidate s is accumulated if and only if (s - 1) % every == 0, so the first step of a window always counts; on the other steps
+nothing happens.  N and the per-cell n count accumulated steps only.
+
+Accumulation, once per accumulated step, with x each of U, V, W, T of FS3D_LAYER_CUR after the step and `types` the node types of that
 moment -- on the NODE_IN cells only:
     n += 1          (uint32)
     S1 += double(x)
     S2 += double(x) * double(x)          (mode 2)
-and the window's step count N += 1.  Cells are counted by the type they have at each step: a geometry may move inside a window.
+    S_ab += double(x_a) * double(x_b)    (mode 2 with cross; the pairs 0..5: uv, uw, vw, uT, vT, wT)
+and the window's step count N += 1.  The product is rounded once, the addition once.  Cells are counted by the type they have at
+each step: a geometry may move inside a window.
 
 Read-out, per cell, all in double, each operation rounded once; R is the fields' type:
-    n >= 1:  m = S1 / double(n)
+    n >= 1:  dn = double(n), m_a = S1_a / dn
         source 1, mean            Q = R(m)
-        source 2, variance        v = S2 / double(n) - m * m, 0 where v < 0, Q = R(v)      (population variance over the n steps)
+        source 2, moment 0, variance   var_a = S2_a / dn - m_a * m_a, 0 where that is negative, Q = R(var)   (population variance
+                                       over the n steps)
+        source 2, moment 1, Reynolds stresses   cov(a, b) = S_ab / dn - m_a * m_b, NOT clamped (a covariance may be negative):
+                                       Q_U = R(cov(u, v)), Q_V = R(cov(u, w)), Q_W = R(cov(v, w)),
+                                       Q_T = R(0.5 * ((var_u + var_v) + var_w)), the turbulent kinetic energy
+        source 2, moment 2, turbulent heat flux   Q_U = R(cov(u, T)), Q_V = R(cov(v, T)), Q_W = R(cov(w, T)), Q_T = R(var_T)
         source 3, fluid fraction  Q_T = R(double(n) / double(N)), Q_U = Q_V = Q_W = 0
     n == 0:  source 1: the value the cell holds in FS3D_LAYER_CUR now (walls show their node values as in every record);
-             sources 2 and 3: 0.
+             sources 2 (every moment) and 3: 0.
 The record rule of the three entries then runs on Q in place of `next`: the 99999 stamp on the cells that are NODE_OUT now, the
-gather, and layer_output.py's filter and vector where those options are set.
+gather, and layer_output.py's filter where that option is set (the vector option: moment 0 only, the curl of a stress layer means
+nothing).
 
 Rounding of the mean: S1 is a recursive double sum of n terms, so |S1 - sum x| <= (n - 1) u sum |x| / (1 - (n - 1) u) with
 u = 2^-53 (Higham, Accuracy and Stability of Numerical Algorithms, eq. 4.4), the division adds one relative u, and the rounding to
 R one relative half-ulp of R.  mean_bound returns that bound.  The variance is the textbook one-pass formula: it cancels where
 the mean is large against the spread (relative error about 2 u (m^2 / v)), is clamped at 0, and is exactly 0 for a constant field whose
-square is exact in double (every fp32 value; S2 / n = x^2 and m * m = x^2 as long as n * x and n * x^2 are exact).
+square is exact in double (every fp32 value; S2 / n = x^2 and m * m = x^2 as long as n * x and n * x^2 are exact).  The one-pass
+covariance carries the same caveat: S_ab / n and m_a * m_b cancel where the means are large against the co-fluctuation (absolute
+error about 2 u |m_a m_b|), it is not clamped, and it is exactly 0 for two constant fields whose product is exact in double (every
+pair of fp32 values) as long as n * x_a, n * x_b and n * x_a * x_b are exact.
 
-Not provided: covariances (Reynolds stresses), a stride (every k-th step), a history of cells that are NODE_OUT now, the 2D solver.
+Not provided: third moments, covariances with the vorticity, a history of cells that are NODE_OUT now, the 2D solver.
 """
 import numpy as np
 
@@ -36,43 +52,65 @@ from .grids import NODE_IN
 
 MEAN, VARIANCE, FRACTION = 1, 2, 3
 SOURCES = {"next": 0, "mean": MEAN, "variance": VARIANCE, "fraction": FRACTION}
+MOMENTS = {"variance": 0, "stress": 1, "heatflux": 2}
+PAIRS = ((0, 1), (0, 2), (1, 2), (0, 3), (1, 3), (2, 3))       # uv, uw, vw, uT, vT, wT
+MAX_EVERY = 2 ** 20
 
 
 class TimeStats:
-    """One window.  mode 1: first moments; mode 2: first and second moments."""
+    """One window.  mode 1: first moments; mode 2: first and second moments; cross (mode 2 only, without effect in mode 1): the six
+    cross sums as well; every: the stride of the accumulated steps."""
 
-    def __init__(self, shape, mode=2):
+    def __init__(self, shape, mode=2, cross=False, every=1):
         if mode not in (1, 2):
             raise ValueError("mode is 1 (first moments) or 2 (first and second moments)")
-        self.shape, self.mode = tuple(shape), mode
+        if int(every) != every or not 1 <= every <= MAX_EVERY:
+            raise ValueError("every is an integer from 1 to 2^20")
+        self.shape, self.mode, self.cross, self.every = tuple(shape), mode, bool(cross) and mode == 2, int(every)
         self.reset()
 
     def reset(self):
-        """A new window: N = 0, every sum zero (what every fs3d_set_option(FS3D_OPT_TIME_STATS, ..) does)"""
+        """A new window: N = 0, no candidate step yet, every sum zero (what every fs3d_set_option of FS3D_OPT_TIME_STATS,
+        FS3D_OPT_TIME_STATS_CROSS and FS3D_OPT_TIME_STATS_EVERY does)"""
         self.N = 0
+        self.candidates = 0
         self.n = np.zeros(self.shape, np.uint32)
         self.S1 = [np.zeros(self.shape, np.float64) for _ in range(4)]
         self.S2 = [np.zeros(self.shape, np.float64) for _ in range(4)] if self.mode == 2 else None
+        self.SX = [np.zeros(self.shape, np.float64) for _ in PAIRS] if self.cross else None
 
     def add(self, fields, types):
-        """One accumulated step: fields = U, V, W, T of `cur` after the step, types = the node types of that moment"""
+        """One candidate step: fields = U, V, W, T of `cur` after the step, types = the node types of that moment.  Returns whether
+        the stride let it be accumulated."""
+        self.candidates += 1
+        if (self.candidates - 1) % self.every:
+            return False
         fluid = np.asarray(types) == NODE_IN
         assert fluid.shape == self.shape
         self.n[fluid] += np.uint32(1)
         with np.errstate(all="ignore"):
+            x = [np.asarray(fields[v])[fluid].astype(np.float64) for v in range(4)]
             for v in range(4):
-                x = np.asarray(fields[v])[fluid].astype(np.float64)
-                self.S1[v][fluid] = self.S1[v][fluid] + x
+                self.S1[v][fluid] = self.S1[v][fluid] + x[v]
                 if self.mode == 2:
-                    self.S2[v][fluid] = self.S2[v][fluid] + x * x
+                    self.S2[v][fluid] = self.S2[v][fluid] + x[v] * x[v]
+            if self.cross:
+                for p, (a, b) in enumerate(PAIRS):
+                    self.SX[p][fluid] = self.SX[p][fluid] + x[a] * x[b]
         self.N += 1
+        return True
 
-    def layer(self, source, cur_fields):
-        """Q of `source` (1 mean, 2 variance, 3 fluid fraction): four arrays of cur_fields' dtype, before the 99999 stamp"""
+    def layer(self, source, cur_fields, moment=0):
+        """Q of `source` (1 mean, 2 second moments, 3 fluid fraction): four arrays of cur_fields' dtype, before the 99999 stamp.
+        moment, read for source 2 only: 0 the variances, 1 the Reynolds stresses and k, 2 the heat fluxes and var_T"""
         if source not in (MEAN, VARIANCE, FRACTION):
             raise ValueError("source is 1 (mean), 2 (variance) or 3 (fluid fraction)")
         if source == VARIANCE and self.mode < 2:
             raise ValueError("the variance needs mode 2")
+        if source == VARIANCE and moment not in (0, 1, 2):
+            raise ValueError("moment is 0 (variance), 1 (stress) or 2 (heatflux)")
+        if source == VARIANCE and moment and not self.cross:
+            raise ValueError("the covariances need mode 2 with cross")
         if self.N == 0:
             raise ValueError("the window holds no step")
         R = np.asarray(cur_fields[0]).dtype
@@ -80,6 +118,27 @@ class TimeStats:
         dn = self.n[seen].astype(np.float64)
         out = []
         with np.errstate(all="ignore"):
+            if source == VARIANCE and moment:
+                m = [self.S1[v][seen] / dn for v in range(4)]
+
+                def var(v):
+                    mm = m[v] * m[v]
+                    d = self.S2[v][seen] / dn - mm
+                    return np.where(d < 0.0, 0.0, d)
+
+                def cov(p):
+                    a, b = PAIRS[p]
+                    mab = m[a] * m[b]
+                    return self.SX[p][seen] / dn - mab
+                if moment == 1:
+                    vals = [cov(0), cov(1), cov(2), 0.5 * ((var(0) + var(1)) + var(2))]
+                else:
+                    vals = [cov(3), cov(4), cov(5), var(3)]
+                for v in range(4):
+                    q = np.zeros(self.shape, R)
+                    q[seen] = vals[v].astype(R)
+                    out.append(q)
+                return out
             for v in range(4):
                 q = np.zeros(self.shape, R)
                 if source == MEAN:

@@ -126,6 +126,19 @@ enum {
     FS3D_OPT_OUTPUT_SOURCE = 15, /* the layer fs3d_get_layer, fs3d_get_layer_rows and fs3d_get_layer_dev turn into samples.  0 (default):
                                  `next`, nothing changes anywhere.  1: the time mean, 2: the time variance, 3: the fluid fraction of the
                                  open window of FS3D_OPT_TIME_STATS (the time-statistics section below).  Any other value: FS3D_ERR_INVALID */
+    FS3D_OPT_TIME_STATS_CROSS = 16, /* 0 (default): nothing changes anywhere and nothing is allocated.  1: while FS3D_OPT_TIME_STATS is 2,
+                                 every accumulation also adds the six products uv, uw, vw, uT, vT, wT to six more per-cell double sums, in
+                                 the same kernel (48 bytes per own cell); while the mode is 0 or 1 it has no effect and allocates nothing.
+                                 EVERY call with this option opens a new window; setting 0 also frees the cross sums.  Any other value:
+                                 FS3D_ERR_INVALID */
+    FS3D_OPT_OUTPUT_MOMENT = 17, /* which second-moment layer FS3D_OPT_OUTPUT_SOURCE 2 builds; read only when the source is 2.  0 (default):
+                                 the four variances, nothing changes.  1: the Reynolds stresses cov(u,v), cov(u,w), cov(v,w) in outV and the
+                                 turbulent kinetic energy in outT.  2: the turbulent heat fluxes cov(u,T), cov(v,T), cov(w,T) in outV and
+                                 the variance of T in outT.  1 and 2 need the cross sums of the open window and exclude
+                                 FS3D_OPT_OUTPUT_VECTOR 1 (the time-statistics section below).  Any other value: FS3D_ERR_INVALID */
+    FS3D_OPT_TIME_STATS_EVERY = 18, /* the stride k of the accumulated steps, 1 (default) .. 2^20: of the candidate steps s = 1, 2, .. of a
+                                 window those with (s - 1) % k == 0 are accumulated, on the others no kernel runs.  EVERY call with this
+                                 option opens a new window.  Needs no memory.  A value below 1 or above 2^20: FS3D_ERR_INVALID */
     FS3D_OPT_ERR_ORDER = 7   /* summation order of EvalDivError (fs3d_eval_div_error, fs3d_time_step with compute_error).  0 (default): the
                                  per-cell terms are summed in parallel (per workgroup, then over the workgroups; deterministic, equal to the
                                  CPU path to ~1e-12 relative).  1: they are summed one after the other in cell order, as the loop of
@@ -465,7 +478,7 @@ fs3d_status fs3d_last_update_device_ms(fs3d_ctx *ctx, float *ms_out);
  * counts X, Y, Z; [3] BOUND / VALVE cells; [4] NODE_IN cells on no segment of some direction; [5..7] dead lines X, Y, Z;
  * [8..9] shared-column groups flagged uniform in X, Y; [10..11] distinct shared columns in X, Y; [12] an order-independent
  * 64-bit digest of the cell-code table (sum over cells of a mix of cell index and code), computed on the device from the
- * table the sweeps read; [13] the number of device allocations and frees fs3d_upload_nodes / fs3d_update_nodes* / fs3d_fill_fresh_cells* and the accumulators of FS3D_OPT_TIME_STATS have made
+ * table the sweeps read; [13] the number of device allocations and frees fs3d_upload_nodes / fs3d_update_nodes* / fs3d_fill_fresh_cells* and the accumulators of FS3D_OPT_TIME_STATS (the cross sums of FS3D_OPT_TIME_STATS_CROSS among them) have made
  * since the context was created (the one entry that describes the path taken, not the tables).
  * Measurement and test aid; no reference counterpart. */
 #define FS3D_N_GEOM_INFO 14
@@ -564,36 +577,56 @@ fs3d_status fs3d_get_layer(fs3d_ctx *ctx, void *outV, double *outT,
  * entries with FS3D_ERR_UNSUPPORTED before any launch, destinations and `next` untouched: a box can straddle a cut and the curl
  * needs the neighbour's planes.  fs3d_get_layer_rows / _dev on a whole-grid context work and report rows = [0, outdimx).
  *
- * Time statistics (FS3D_OPT_TIME_STATS, FS3D_OPT_OUTPUT_SOURCE; no reference counterpart; the rule and its numpy twin:
- * cmc_fluid_solver_amd/time_stats.py).  While FS3D_OPT_TIME_STATS is 1 or 2, every fs3d_time_step that returns FS3D_OK and every
- * fs3d_time_step_async enqueues one kernel behind the step, after the cur / next swap, over the context's own cells: for each cell that
- * is NODE_IN in the geometry of that moment, with x each of U, V, W, T of FS3D_LAYER_CUR,
- *   n += 1 (uint32 per cell),  S1 += (double)x,  and in mode 2  S2 += (double)x * (double)x
- * -- every operation rounded once in double, no fused multiply-add -- and the window's step count N grows by one.  A step that returns
- * FS3D_ERR_DIVERGED does not swap and accumulates nothing.  The geometry may change inside a window (fs3d_update_nodes*,
- * fs3d_upload_nodes): a cell is counted by the type it has at each step, which is what the per-cell n is for.
- *  - the window: every fs3d_set_option(FS3D_OPT_TIME_STATS, ..) opens a new one, N = 0 and all sums zero, whatever the value was.
- *  - memory: 4 + 32 (mode 2: 64) bytes per own cell, no ghost planes, allocated by the first accumulation after the option was set
- *    (a failed allocation is that step's status: the step itself stands, nothing was accumulated), kept over later windows, freed
- *    by setting the option to 0 and by fs3d_destroy; counted in fs3d_geometry_info entry 13.  With the option at 0 nothing is
- *    allocated and no kernel runs.
+ * Time statistics (FS3D_OPT_TIME_STATS, FS3D_OPT_TIME_STATS_CROSS, FS3D_OPT_TIME_STATS_EVERY, FS3D_OPT_OUTPUT_SOURCE,
+ * FS3D_OPT_OUTPUT_MOMENT; no reference counterpart; the rule and its numpy twin: cmc_fluid_solver_amd/time_stats.py).  While
+ * FS3D_OPT_TIME_STATS is 1 or 2, every fs3d_time_step that returns FS3D_OK and every fs3d_time_step_async is a CANDIDATE step of the
+ * open window, counted s = 1, 2, ..; a step that returns FS3D_ERR_DIVERGED does not swap and is no candidate.  With k the value of
+ * FS3D_OPT_TIME_STATS_EVERY (default 1), candidate s is ACCUMULATED if and only if (s - 1) % k is 0: the first step of a window always
+ * counts, so a window of at least one step is never empty, and on the other steps no kernel runs.  An accumulated step enqueues one
+ * kernel behind the step, after the cur / next swap, over the context's own cells: for each cell that is NODE_IN in the geometry of
+ * that moment, with x each of U, V, W, T of FS3D_LAYER_CUR,
+ *   n += 1 (uint32 per cell),  S1 += (double)x,  in mode 2  S2 += (double)x * (double)x,
+ *   and in mode 2 with FS3D_OPT_TIME_STATS_CROSS set to 1  S_ab += (double)x_a * (double)x_b  for the six pairs
+ *   0 uv, 1 uw, 2 vw, 3 uT, 4 vT, 5 wT
+ * -- the product rounded once, the addition rounded once, in double, no fused multiply-add -- and the window's step count N grows by
+ * one: N and the per-cell n count accumulated steps only, and the fluid fraction stays n / N.  The geometry may change inside a
+ * window (fs3d_update_nodes*, fs3d_upload_nodes): a cell is counted by the type it has at each accumulated step, which is what the
+ * per-cell n is for.  While the mode is 0 or 1 the CROSS option has no effect.
+ *  - the window: every fs3d_set_option of FS3D_OPT_TIME_STATS, FS3D_OPT_TIME_STATS_CROSS or FS3D_OPT_TIME_STATS_EVERY opens a new
+ *    one, N = 0, no candidate yet and all sums zero, whatever the value was.
+ *  - memory: 4 + 32 (mode 2: 64; with the cross sums: 112) bytes per own cell, no ghost planes.  Each buffer is allocated by the first
+ *    accumulation that needs it (a failed allocation is that step's status: the step itself stands, nothing was accumulated), kept
+ *    over later windows, and counted in fs3d_geometry_info entry 13: mode 2 makes 3 allocations, with the cross sums 4.  Setting
+ *    FS3D_OPT_TIME_STATS to 0 frees all of them, setting FS3D_OPT_TIME_STATS_CROSS to 0 the cross sums, either after a stream
+ *    synchronise; fs3d_destroy frees what is left.  With FS3D_OPT_TIME_STATS at 0 nothing is allocated and no kernel runs; the stride
+ *    needs no memory.
  *  - read-out: with FS3D_OPT_OUTPUT_SOURCE 1..3 the three GetLayer entries first build a statistic layer Q -- four fields of the
  *    context's real type R in a buffer of the context's own (4 fields of the own cells, allocated by the first such call, counted
- *    in fs3d_get_layer_info entry 2, kept) -- and then run on Q what they run on `next`.  Per cell with n >= 1, m = S1 / (double)n:
+ *    in fs3d_get_layer_info entry 2, kept) -- and then run on Q what they run on `next`.  Per cell with n >= 1, dn = (double)n and
+ *    m_a = S1_a / dn:
  *      1 time mean       Q = (R)m
- *      2 time variance   v = S2 / (double)n - m * m, 0 where that is negative, Q = (R)v   (the population variance over the n steps)
+ *      2 second moments, chosen by FS3D_OPT_OUTPUT_MOMENT (read for this source only):
+ *        moment 0  the variances: var_a = S2_a / dn - m_a * m_a, 0 where that is negative, Q = (R)var   (the population variance
+ *                  over the n steps)
+ *        moment 1  the Reynolds stresses: cov(a,b) = S_ab / dn - m_a * m_b, NOT clamped (a covariance may be negative);
+ *                  Q_U = (R)cov(u,v), Q_V = (R)cov(u,w), Q_W = (R)cov(v,w), Q_T = (R)(0.5 * ((var_u + var_v) + var_w)), the
+ *                  turbulent kinetic energy, from the clamped variances of moment 0
+ *        moment 2  the turbulent heat flux: Q_U = (R)cov(u,T), Q_V = (R)cov(v,T), Q_W = (R)cov(w,T), Q_T = (R)var_T
  *      3 fluid fraction  Q_T = (R)((double)n / (double)N), Q_U = Q_V = Q_W = 0
  *    all in double, each operation rounded once; with n = 0: source 1 the value the cell holds in FS3D_LAYER_CUR (walls show their
- *    node values as in every record), sources 2 and 3 zero.  Then, unchanged: the 99999 stamp on the cells that are NODE_OUT in
- *    the CURRENT geometry (written into Q), the gather -- or with FS3D_OPT_OUTPUT_FILTER / FS3D_OPT_OUTPUT_VECTOR the box mean of
- *    the mean and the vorticity of the mean flow --, staging, copies, rows and the fs3d_get_layer_info counts.  outT is the
- *    widening of Q_T.  `next` and `cur` are not written.
- *  - refusals, FS3D_ERR_INVALID before any launch with the destinations untouched: a source the current FS3D_OPT_TIME_STATS mode
- *    does not hold (any source at 0, source 2 at 1), and a window without a step (N = 0).  The slab refusal of the filter and
- *    vector options stands; without them an x-slab or group member accumulates and reads out its own planes, and the rows the
- *    slabs write are those of the global record a single context gives.
- *  - not provided: covariances (Reynolds stresses); a stride (every k-th step); a history of the cells that are NODE_OUT now (they
- *    are stamped as in every record); the 2D solver. */
+ *    node values as in every record), sources 2 (every moment) and 3 zero.  Then, unchanged: the 99999 stamp on the cells that are
+ *    NODE_OUT in the CURRENT geometry (written into Q), the gather -- or with FS3D_OPT_OUTPUT_FILTER / FS3D_OPT_OUTPUT_VECTOR the box
+ *    mean of the layer and, for the mean and the variances, the curl --, staging, copies, rows and the fs3d_get_layer_info counts.
+ *    outT is the widening of Q_T.  `next` and `cur` are not written.  The one-pass variance and covariance cancel where the means
+ *    are large against the fluctuation (absolute error about 2 * 2^-53 * |m_a * m_b|).
+ *  - refusals, FS3D_ERR_INVALID before any launch with the destinations, rows and layers untouched: a source the current
+ *    FS3D_OPT_TIME_STATS mode does not hold (any source at 0, source 2 at 1); source 2 with moment 1 or 2 while the open window holds
+ *    no cross sums (FS3D_OPT_TIME_STATS_CROSS is 0, or the mode is below 2); moment 1 or 2 with source 2 and FS3D_OPT_OUTPUT_VECTOR 1
+ *    (the curl of a stress layer means nothing); and a window without an accumulated step (N = 0).  The slab refusal of the filter
+ *    and vector options stands; without them an x-slab or group member accumulates and reads out its own planes -- every layer is
+ *    per cell --, and the rows the slabs write are those of the global record a single context gives.
+ *  - not provided: third moments; covariances with the vorticity; a history of the cells that are NODE_OUT now (they are stamped
+ *    as in every record); the 2D solver. */
 fs3d_status fs3d_get_layer_rows(fs3d_ctx *ctx, void *outV, double *outT, int outdimx, int outdimy, int outdimz, int rows[2]);
 /* fs3d_get_layer_rows (Solver3D.cpp:21-25, TimeLayer3D.h:819-924) with the two arrays on the context's DEVICE: the kernel
  * writes them directly, nothing is copied.  Returns after the enqueue on the context's stream; read after fs3d_synchronize.
