@@ -1,20 +1,21 @@
 // Command-line driver: the reference's FluidSolver3D main (FluidSolver3D/FluidSolver3D.cpp:60-330) on top of
-// libfs3d_hip.so.   fs3d_run <input data> <output prefix> <config> [align] [GPU [n]] [double] [moving [--host-extrusion] [--time-geometry]] [moving-mesh [--host-voxels | --slab-voxels] [--time-geometry] [--time-both]] [--time-output] [--steps N] [--same-device] [--grid-only FILE [--grid-time T]] [--watertight [--thin-shell] [--wall-velocity motion|file]] [--wall-temperature T] [--fresh-cells | --slab-fresh-cells] [--output-filter point|box] [--time-stats mean|variance] [--time-covariances] [--time-stats-every K]
+// libfs3d_hip.so.   fs3d_run <input data> <output prefix> <config file> [words]: the words are those of USAGE below, which main prints.
 //   * reads the config (host/Config.h) and a Shape2D, Shape3D or SeaNetCDF geometry (host/Shape2D.h, Shape3D.h, SeaNetCDF.h), prints the grid summary lines
 //     the reference prints ("Grid = X x Y x Z", "NODE_IN points = ..."),
-//   * runs the same loop: dt = cycle length / (frames * time_steps), UpdateBoundaries + TimeStep per step with the
+//   * runs the same loop, ONE loop for a single GPU and for `GPU n` (run_loop below: the single GPU is its one-rank case): dt = cycle length /
+//     (frames * time_steps), UpdateBoundaries + TimeStep per step with the
 //     divergence error every 10th step and on the last one, "err = ..." and the progress line per step,
 //   * writes <output prefix>_res.nc through host/NetCDF3.h every out_time_steps steps (GetLayer).
 // `transpose`, `decompose`, `blocking n` of the reference are accepted and ignored (backend tuning switches); `CSV`
 // switches the closing timing table to the reference's comma-separated form.
-// `moving` (in_fmt Shape2D; one GPU, or GPU n --same-device: run_slabs below): the walls follow the frames of the input -- per step grid2D->Prepare(t), the extrusion and
+// `moving` (in_fmt Shape2D; one GPU, or GPU n --same-device): the walls follow the frames of the input -- per step grid2D->Prepare(t), the extrusion and
 //   CreateSegments on the device (UpdateGridExtruded: the 2D grid travels, the node arrays are written by a kernel), UpdateBoundaries,
 //   TimeStep, the output, ClearOutterCells: the loop of the reference's 2D driver (FluidSolver2D.cpp:130-133) with the 3D classes'
 //   mechanism (AdiSolver3D.cpp:382-385, Solver3D.cpp:41-44).
 //   --host-extrusion: the extrusion on the host (ExtrudeShape2D into the Grid3D, then UpdateGrid with its seven arrays) -- the same
 //   results bit for bit; kept for A/B timing and as the checker of the device extrusion.
 //   --time-geometry: one more line after the timing table, the host clock per step around Prepare, the host extrusion and the update call.
-// `moving-mesh` (in_fmt Shape3D; one GPU, or GPU n with --host-voxels or --slab-voxels: run_slabs below): the same loop for a triangle mesh per frame -- per step Shape3D::SubFrame(t) (the
+// `moving-mesh` (in_fmt Shape3D; one GPU, or GPU n with --host-voxels or --slab-voxels): the same loop for a triangle mesh per frame -- per step Shape3D::SubFrame(t) (the
 //   interpolation of Grid3D::Prepare3D_Shape, Grid3D.cpp:905-946), then the voxelisation, the flood fill and CreateSegments on the
 //   device (UpdateGridShape3D: the vertices travel).  The frame counter of the progress line stays 0, as Grid3D::GetFrame gives it
 //   for a Shape3D input.  `moving` keeps its meaning: Shape2D inputs only.
@@ -122,39 +123,15 @@ struct RunOptions {
     int nslabs = 1, device = 0;
     long max_steps = -1;
     std::string grid_only;
+    bool moves() const { return moving || moving_mesh; }
+    bool on_host() const { return moving ? host_extrusion : host_voxels; }   // the node arrays are made on the host and go through UpdateGrid
+    bool walls() const { return wall_velocity || has_wall_T; }               // the mesh updates go through the entries that take velocities and a wall temperature
 };
 
-template <typename FTYPE>
-static int run_slabs(fs3d::Grid3D<FTYPE> &grid, fs3d::Grid2D &g2, fs3d::Shape3D &sh3, const RunGeom &geo, const std::string &prefix,
-                     const fs3d::Config &cfg, const RunOptions &o);
+static const char USAGE[] = "<input data> <output prefix> <config file> [align] [GPU [n]] [double] [--steps N] [moving [--host-extrusion] [--time-geometry]] [moving-mesh [--host-voxels | --slab-voxels] [--time-geometry] [--time-both]] [--time-output] [--grid-only FILE [--grid-time T]] [--grid-images] [--watertight [--thin-shell] [--wall-velocity motion|file]] [--wall-temperature T] [--fresh-cells | --slab-fresh-cells] [--output-filter point|box] [--time-stats mean|variance] [--time-covariances] [--time-stats-every K]";
 
-// --time-stats: the records of <prefix>_stats.nc, in order, each a source and a moment (FS3D_OPT_OUTPUT_SOURCE: 1 mean, 2 second
-// moments, 3 fluid fraction; FS3D_OPT_OUTPUT_MOMENT: 0 variance, 1 stresses, 2 heat flux)
-struct StatsRecord { int source, moment; };
-static std::vector<StatsRecord> stats_records(const RunOptions &o)
-{
-    if (o.time_stats != 2) return {{1, 0}, {3, 0}};
-    if (!o.time_cov) return {{1, 0}, {2, 0}, {3, 0}};
-    return {{1, 0}, {2, 0}, {2, 1}, {2, 2}, {3, 0}};
-}
-// the window's options, before the loop
-template <class Solver>
-static void set_time_stats(Solver &solver, const RunOptions &o)
-{
-    solver.SetTimeStats(o.time_stats);
-    if (o.time_cov) solver.SetTimeStatsCross(1);
-    if (o.time_every > 1) solver.SetTimeStatsEvery((int)o.time_every);
-}
-// steps: the time steps of the run; the line names the accumulated ones, the 1st, (K + 1)th, .. of them
-static void print_stats_line(long steps, const RunOptions &o, const std::string &file)
-{
-    if (steps > 0) std::printf("Time statistics: %ld steps, mean%s%s in %s\n", (steps + o.time_every - 1) / o.time_every,
-                               o.time_stats == 2 ? ", variance" : "", o.time_cov ? ", covariances" : "", file.c_str());
-    else std::printf("Time statistics: 0 steps, no file\n");
-}
-
-template <typename FTYPE>
-static int run(const std::string &data, const std::string &prefix, const fs3d::Config &cfg, const RunOptions &o)
+// the refusals that need no geometry, in the order a user meets them
+static void check_words(const RunOptions &o, const fs3d::Config &cfg)
 {
     if (o.moving && cfg.in_fmt != "Shape2D") throw std::runtime_error("moving: only in_fmt Shape2D inputs move (this one is " + cfg.in_fmt + ")");
     if (o.moving && o.nslabs > 1 && !o.same_device)
@@ -180,13 +157,362 @@ static int run(const std::string &data, const std::string &prefix, const fs3d::C
     if (o.has_wall_T && cfg.in_fmt != "Shape3D") throw std::runtime_error("--wall-temperature: only in_fmt Shape3D inputs are meshes (this one is " + cfg.in_fmt + ")");
     if (o.has_wall_T && !std::isfinite(o.wall_T)) throw std::runtime_error("--wall-temperature: not a finite number");
     if (o.has_wall_T && o.moving_mesh && !o.watertight) throw std::runtime_error("--wall-temperature: a moving-mesh run needs --watertight for it (the wall temperature travels with fs3d_update_nodes_shape3d_vel)");
-    const bool walls = o.wall_velocity || o.has_wall_T;    // the mesh updates go through the entries that take velocities and a wall temperature
-    if (walls && o.time_both) throw std::runtime_error("--time-both: not together with --wall-velocity or --wall-temperature");
+    if (o.walls() && o.time_both) throw std::runtime_error("--time-both: not together with --wall-velocity or --wall-temperature");
     if (o.fresh_cells && !o.moving && !o.moving_mesh) throw std::runtime_error("--fresh-cells: only with moving or moving-mesh (cells turn fluid only where the geometry moves)");
     if (o.fresh_cells && o.nslabs > 1 && !o.slab_fresh_cells)
         throw std::runtime_error("--fresh-cells: single GPU only (with GPU n the fill is a collective call of all slabs: --slab-fresh-cells)");
     if (o.fresh_cells && o.time_both) throw std::runtime_error("--fresh-cells: not together with --time-both (it updates the geometry twice per step)");
     if (o.grid_time >= 0 && cfg.in_fmt != "Shape2D" && cfg.in_fmt != "Shape3D") throw std::runtime_error("--grid-time: only in_fmt Shape2D and Shape3D inputs move");
+}
+
+using Clock = std::chrono::steady_clock;
+static double ms_between(Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); }
+
+// --time-stats: the records of <prefix>_stats.nc, in order, each a source and a moment (FS3D_OPT_OUTPUT_SOURCE: 1 mean, 2 second
+// moments, 3 fluid fraction; FS3D_OPT_OUTPUT_MOMENT: 0 variance, 1 stresses, 2 heat flux)
+struct StatsRecord { int source, moment; };
+static std::vector<StatsRecord> stats_records(const RunOptions &o)
+{
+    if (o.time_stats != 2) return {{1, 0}, {3, 0}};
+    if (!o.time_cov) return {{1, 0}, {2, 0}, {3, 0}};
+    return {{1, 0}, {2, 0}, {2, 1}, {2, 2}, {3, 0}};
+}
+
+// what a solver is told before the loop; nslabs > 1: it is a slab of a group
+template <class Solver>
+static void apply_options(Solver &solver, const RunOptions &o, int nslabs)
+{
+    if (o.watertight) solver.SetMeshVoxels(1);           // the updates voxelise as the host loader did
+    if (o.thin_shell) solver.SetMeshShell(1);
+    if (o.fresh_cells) solver.SetFreshCells(true);
+    if (o.fresh_cells && nslabs > 1) solver.SetFreshCellsSlabs(true);
+    if (o.output_box) solver.SetOutputFilter(1);
+    if (o.time_stats) solver.SetTimeStats(o.time_stats);
+    if (o.time_stats && o.time_cov) solver.SetTimeStatsCross(1);
+    if (o.time_stats && o.time_every > 1) solver.SetTimeStatsEvery((int)o.time_every);
+}
+
+// The ranks wait for one another here.  One rank: every wait returns at once.
+namespace {
+struct Barrier {
+    std::mutex m; std::condition_variable cv; int n, waiting = 0; long gen = 0; bool broken = false;
+    explicit Barrier(int n_) : n(n_) {}
+    void wait()
+    {
+        std::unique_lock<std::mutex> lk(m);
+        const long g = gen;
+        if (++waiting == n) { waiting = 0; gen++; cv.notify_all(); return; }
+        cv.wait(lk, [&] { return gen != g || broken; });
+        // a rank that every other rank has joined here goes on, whatever has failed since: how far the ranks get beside a failing one
+        // does not depend on which of them wakes first
+        if (gen == g) throw std::runtime_error("another slab thread failed");
+    }
+    void abort() { { std::lock_guard<std::mutex> lk(m); broken = true; } cv.notify_all(); }
+};
+}
+
+// What the ranks of a run share.  A single GPU is the run of one rank; "GPU n" with n > 1 is the reference's single-process
+// multi-GPU mode (GPUplan): n x-slabs (GPUplan::splitEven1D, GPUplan.cpp:122-141), one solver and one host thread per slab,
+// joined by the library's in-process group; its results equal the single-GPU run's value for value.  Slab r runs on device r, or
+// all on device 0 with --same-device.  Rank 0 alone writes the grid, the 2D grid, the sub-frame vectors, both files and the
+// counters that are no per-rank vector; the barrier says when the others may read them.
+template <typename FTYPE>
+struct Run {
+    fs3d::Grid3D<FTYPE> &grid; fs3d::Grid2D &g2; fs3d::Shape3D &sh3;
+    const RunGeom &geo; const fs3d::Config &cfg; const RunOptions &o;
+    const int nslabs;
+    const fs3d::FluidParams<FTYPE> params;
+    const double dt, finaltime;                        // FluidSolver3D.cpp:194-196
+    const std::string out, stats;
+    fs3d::NetCDF3Writer nc, ns;                        // <prefix>_res.nc; --time-stats: <prefix>_stats.nc
+    fs3d::DepthInfo3D out_depths;                      // IO.h:270-273
+    std::vector<FTYPE> resVel;                         // one record: every rank writes the rows it owns, rank 0 appends
+    std::vector<double> resT;
+    Barrier bar;
+    void *group = nullptr;
+    std::vector<float> mx, my, mz, mwx, mwy, mwz;      // moving-mesh on the device: the sub-frame's vertices and their velocities (zeros without --wall-velocity)
+    size_t mframe = 0;
+    std::vector<long long> fresh_own, filled_own;      // --fresh-cells: every rank's own fresh and filled cells over the run
+    long long fresh_updates = 0, fresh_rounds = 0;     // ... the updates and the most rounds of one fill (the group's)
+    double out_ms[2] = {0, 0};                         // --time-output: host clock until the record is complete, AppendLayer
+    Clock::time_point t0;
+    long steps = 0;
+    double sec = 0;
+    // the single-GPU measurement words
+    double geom_ms[3] = {0, 0, 0};                     // --time-geometry: host clock around Prepare / SubFrame, the node arrays on the host, the update call
+    std::vector<double> ab_host, ab_dev, ab_dev_gpu, ab_step;   // --time-both: per step, ms
+    int fill_rounds = 0;
+
+    Run(fs3d::Grid3D<FTYPE> &grid_, fs3d::Grid2D &g2_, fs3d::Shape3D &sh3_, const RunGeom &geo_, const std::string &prefix,
+        const fs3d::Config &cfg_, const RunOptions &o_)
+        : grid(grid_), g2(g2_), sh3(sh3_), geo(geo_), cfg(cfg_), o(o_), nslabs(o_.nslabs),
+          params(cfg_.useNormalizedParams ? fs3d::FluidParams<FTYPE>(cfg_.Re, cfg_.Pr, cfg_.lambda)
+                                          : fs3d::FluidParams<FTYPE>(cfg_.viscosity, cfg_.density, cfg_.R_specific, cfg_.k, cfg_.cv)),
+          dt(geo_.length / (geo_.frames * cfg_.time_steps)), finaltime(geo_.length * cfg_.cycles),
+          out(prefix + "_res.nc"), stats(prefix + "_stats.nc"),
+          resVel((size_t)cfg_.outdimx * cfg_.outdimy * cfg_.outdimz * 3), resT((size_t)cfg_.outdimx * cfg_.outdimy * cfg_.outdimz),
+          bar(o_.nslabs), fresh_own(o_.nslabs, 0), filled_own(o_.nslabs, 0)
+    {
+        if (geo.depths) out_depths = fs3d::DepthInfo3D(cfg.outdimx, cfg.outdimy, *geo.depths);
+    }
+    void create_result_file(fs3d::NetCDF3Writer &file, const std::string &name)
+    {
+        file.Create(name, geo.bbox, dt * cfg.out_time_steps, finaltime, cfg.outdimx, cfg.outdimy, cfg.outdimz, cfg.out_vars, geo.depths != nullptr,
+                    geo.depths ? out_depths.depth.data() : nullptr);
+    }
+};
+
+// The geometry of time t, first half: what rank 0 does on the host.  on_host: the node arrays are made here, in the shared grid
+// (--host-extrusion, --host-voxels); else the 2D grid of time t, or the sub-frame's vertices and their velocities, are what travels.
+// *mid: the clock between Prepare / SubFrame and the rest (--time-geometry).
+// (on the device, `grid` keeps the nodes of time 0: only its dims and baseT are read from here on)
+template <typename FTYPE>
+static void prepare_geometry(Run<FTYPE> &s, double t, bool on_host, Clock::time_point *mid = nullptr)
+{
+    const RunOptions &o = s.o;
+    const fs3d::Config &cfg = s.cfg;
+    if (o.moving) s.g2.Prepare(t);                                                                   // grid->Prepare(t), FluidSolver3D.cpp:237
+    else if (!on_host) s.mframe = s.sh3.SubFrame(t, s.mx, s.my, s.mz);
+    if (mid) *mid = Clock::now();
+    if (on_host && o.moving) ExtrudeShape2D(s.grid, s.g2, cfg.dz, cfg.depth, cfg.depth_var, cfg.baseT);
+    else if (on_host) { s.sh3.Prepare(t); FillShape3DNodes(s.grid, s.sh3, cfg.baseT, o.wall_T); }
+    else if (o.wall_velocity) s.sh3.SubFrameVelocity(t, o.wall_velocity, s.mwx, s.mwy, s.mwz);
+    else if (o.walls()) { s.mwx.assign(s.mx.size(), 0.0f); s.mwy = s.mwx; s.mwz = s.mwx; }
+}
+// ... second half: what every rank then asks of its solver, which rebuilds the tables of its own planes from that global input
+// (the slab entries on a slab: no rank waits for another inside them)
+template <typename FTYPE>
+static void update_geometry(Run<FTYPE> &s, fs3d::AdiSolver3D<FTYPE> &solver, bool on_host)
+{
+    const RunOptions &o = s.o;
+    if (on_host) solver.UpdateGrid(s.grid);
+    else if (o.moving) solver.UpdateGridExtruded(s.g2, s.cfg.dz, s.cfg.depth, s.cfg.depth_var);
+    else if (o.walls()) solver.UpdateGridShape3D(s.mx, s.my, s.mz, s.mwx, s.mwy, s.mwz, s.sh3.frames[s.mframe].idx, o.wall_T);
+    else solver.UpdateGridShape3D(s.mx, s.my, s.mz, s.sh3.frames[s.mframe].idx);
+}
+
+// One record into `file`.  One rank: GetLayer.  Several: each slab samples the rows of the result whose source planes it owns
+// (FilterToArrays, TimeLayer3D.h:819-924) straight into the shared arrays -- the rows are disjoint -- and rank 0 appends once every
+// rank has written its rows.  ms (--time-output, may be NULL): rank 0's host clock until the record is complete, and around AppendLayer.
+template <typename FTYPE>
+static void record(Run<FTYPE> &s, fs3d::AdiSolver3D<FTYPE> &solver, int r, fs3d::NetCDF3Writer &file, double *ms)
+{
+    const auto o0 = Clock::now();
+    int rows[2];
+    if (s.nslabs == 1) solver.GetLayer(s.resVel.data(), s.resT.data(), s.cfg.outdimx, s.cfg.outdimy, s.cfg.outdimz);
+    else solver.GetLayerRows(s.resVel.data(), s.resT.data(), s.cfg.outdimx, s.cfg.outdimy, s.cfg.outdimz, rows);
+    s.bar.wait();
+    if (r == 0) {
+        const auto o1 = Clock::now();
+        file.AppendLayer(s.resVel.data(), s.resT.data());
+        if (ms) { ms[0] += ms_between(o0, o1); ms[1] += ms_between(o1, Clock::now()); }
+    }
+    s.bar.wait();                                      // nobody writes the next record's rows while rank 0 still reads this one
+}
+
+// the reference's Profiler table (Common/Profiler.h:90-131: sorted by total time, events that never ran are absent; event
+// names of AdiSolver3D.cpp:297-367, 555-680).  Device times from HIP events; MergeLayer has no launches of its own while
+// the merge is fused into the sweep kernels; CreateSegments is the host time of the geometry upload.  Then the sweep kernels that ran.
+template <typename FTYPE>
+static void print_profiler_table(fs3d::AdiSolver3D<FTYPE> &solver, const RunOptions &o)
+{
+    const char *names[FS3D_N_EVENTS]; float ms[FS3D_N_EVENTS]; int cnt[FS3D_N_EVENTS];
+    solver.ProfilerEvents(names, ms, cnt);
+    std::vector<int> order;
+    for (int e = 0; e < FS3D_N_EVENTS; e++) if (cnt[e]) order.push_back(e);
+    std::sort(order.begin(), order.end(), [&](int a, int b) { return ms[a] > ms[b]; });
+    double total = 0;
+    if (o.csv) std::printf("\n%s,%s,%s,%s,\n", "Event Name", "Total (ms)", "Avg (ms)", "Count");
+    else std::printf("\nProfiling data node(0):\n%16s%16s%16s%16s\n", "Event Name", "Total (ms)", "Avg (ms)", "Count");
+    for (int e : order) {
+        if (o.csv) std::printf("%s,%.2f,%.2f,%i,\n", names[e], ms[e], ms[e] / cnt[e], cnt[e]);
+        else std::printf("%16s%16.2f%16.2f%16i\n", names[e], ms[e], ms[e] / cnt[e], cnt[e]);
+        total += ms[e];
+    }
+    if (o.csv) std::printf("%s,%.2f,sec\n", "Overall", total / 1000);
+    else std::printf("%16s%16.2f sec\n", "Overall", total / 1000);
+    int kx, ky, kz, sg;
+    const char *kn[] = {"none", "line", "pipe", "part"};
+    fs3d_last_sweep_kernel(solver.ctx(), 0, &kx, &sg); fs3d_last_sweep_kernel(solver.ctx(), 1, &ky, &sg); fs3d_last_sweep_kernel(solver.ctx(), 2, &kz, &sg);
+    std::printf("Sweep kernels: X %s, Y %s, Z %s\n", kn[kx & 3], kn[ky & 3], kn[kz & 3]);
+}
+
+// the lines that close a run, up to the `steps in` line
+template <typename FTYPE>
+static void print_closing_lines(const Run<FTYPE> &s)
+{
+    const RunOptions &o = s.o;
+    if (o.fresh_cells) {
+        long long fresh = 0, filled = 0;
+        for (int r = 0; r < s.nslabs; r++) { fresh += s.fresh_own[r]; filled += s.filled_own[r]; }
+        std::printf("Fresh cells: %lld in %lld updates, %lld filled, at most %lld rounds\n", fresh, s.fresh_updates, filled, s.fresh_rounds);
+    }
+    if (o.time_geometry && s.steps > 0)                // (before the line of --time-both, which only a mesh has)
+        std::printf(o.moving ? "Moving geometry per step (host clock, ms): Prepare %.3f, extrusion on the host %.3f, update call %.3f; step %.3f\n"
+                             : "Moving mesh per step (host clock, ms): SubFrame %.3f, voxels on the host %.3f, update call %.3f; step %.3f\n",
+                    s.geom_ms[0] / s.steps, s.geom_ms[1] / s.steps, s.geom_ms[2] / s.steps, s.sec * 1e3 / s.steps);
+    if (o.time_both) {
+        auto line = [](const char *what, std::vector<double> v) {
+            if (v.size() <= 3) { std::printf(" %s: too few steps;", what); return; }
+            v.erase(v.begin(), v.begin() + 3);
+            std::sort(v.begin(), v.end());
+            const size_t n = v.size();
+            std::printf(" %s median %.3f min %.3f max %.3f n %zu;", what, n % 2 ? v[n / 2] : 0.5 * (v[n / 2 - 1] + v[n / 2]), v.front(), v.back(), n);
+        };
+        std::printf("Moving mesh, both paths per call (ms):");
+        line("host voxels + fs3d_update_nodes", s.ab_host); line("fs3d_update_nodes_shape3d", s.ab_dev); line("its device time", s.ab_dev_gpu);
+        line("time step", s.ab_step);
+        std::printf(" fill rounds %d\n", s.fill_rounds);
+    }
+    if (o.time_output && s.nc.NumRecords() > 0)
+        std::printf("Result output per record (host clock, ms): GetLayer %.3f, AppendLayer %.3f; %u records\n", s.out_ms[0] / s.nc.NumRecords(),
+                    s.out_ms[1] / s.nc.NumRecords(), s.nc.NumRecords());
+    std::printf("%ld steps in %.3f s: %.1f Mcells/s; %u layers in %s\n", s.steps, s.sec,
+                (double)s.grid.dimx * s.grid.dimy * s.grid.dimz * s.steps / s.sec / 1e6, s.nc.NumRecords(), s.out.c_str());
+}
+
+// What rank r of the run does: its solver over its planes, the time loop, the statistics records.  On one rank every `r == 0` holds
+// and every barrier is a barrier of one.  On several, rank 0 prepares the geometry of time t on the host, a barrier, then every rank
+// updates its solver from it; after the step ClearOutterCells on every rank, and a barrier before rank 0 prepares the next geometry
+// in the arrays the others have read.
+template <typename FTYPE>
+static void run_rank(Run<FTYPE> &s, const int r)
+{
+    using namespace fs3d;
+    const RunOptions &o = s.o;
+    const Config &cfg = s.cfg;
+    const int nslabs = s.nslabs;
+    const int q = s.grid.dimx / nslabs, rem = s.grid.dimx % nslabs;
+    const int x0 = r * q + std::min(r, rem), x1 = x0 + q + (r < rem ? 1 : 0);
+    AdiSolver3D<FTYPE> solver;
+    solver.Init(nslabs == 1 ? o.device : o.same_device ? 0 : r, s.grid, s.params, x0, x1);
+    if (nslabs > 1) solver.JoinLocalGroup(s.group, r);
+    apply_options(solver, o, nslabs);
+    // every rank has uploaded the grid of time 0 before rank 0 writes the next geometry into the same arrays (Init
+    // reads them, and joining the group is no rendezvous)
+    if (o.moves()) s.bar.wait();
+    if (nslabs == 1) {
+        std::printf("Segments: %i %i %i (x, y, z)\n", solver.numSegs[0], solver.numSegs[1], solver.numSegs[2]);
+        s.create_result_file(s.nc, s.out);             // (after Init: a run that finds no GPU leaves no file)
+        solver.EnableTiming(true);
+        s.t0 = Clock::now();
+    } else if (r == 0) std::printf("Slabs: %d x-slabs of %d..%d planes\n", nslabs, q, q + (rem ? 1 : 0));
+
+    double t = s.dt;
+    long steps = 0;
+    int lastframe = -1;
+    // without a moving word the geometry is frame 0's for the whole run: the reference prepares the grid once, before the loop
+    // (grid->Prepare(0), :226; the per-step grid->Prepare(t) is commented out, :237) -- the frame only restarts the substep counter
+    for (int i = 0; t < s.finaltime && (o.max_steps < 0 || steps < o.max_steps); t += s.dt, i++, steps++) {
+        const int currentframe = s.geo.GetFrame(t);                                                      // :229-236
+        if (currentframe != lastframe) { lastframe = currentframe; i = 0; }
+        if (o.moves()) {
+            if (o.time_both) {                         // a measurement run: the other path first, the word's own last (same tables either way)
+                const auto b0 = Clock::now();
+                prepare_geometry(s, t, !o.on_host());
+                update_geometry(s, solver, !o.on_host());
+                (o.host_voxels ? s.ab_dev : s.ab_host).push_back(ms_between(b0, Clock::now()));
+            }
+            const auto g0 = Clock::now();
+            auto g1 = g0;
+            if (r == 0) prepare_geometry(s, t, o.on_host(), &g1);
+            s.bar.wait();
+            const auto g3 = Clock::now();
+            update_geometry(s, solver, o.on_host());
+            const auto g4 = Clock::now();
+            if (o.fresh_cells) {                       // the cells this update turned fluid, all ranks together, before UpdateBoundaries
+                long long info[4];
+                solver.FillFreshCells(info);
+                s.fresh_own[r] += info[0]; s.filled_own[r] += info[1];
+                if (r == 0) { s.fresh_updates++; s.fresh_rounds = std::max(s.fresh_rounds, info[2]); }
+            }
+            if (o.time_geometry) { s.geom_ms[0] += ms_between(g0, g1); s.geom_ms[1] += ms_between(g1, g3); s.geom_ms[2] += ms_between(g3, g4); }
+            if (o.time_both) (o.host_voxels ? s.ab_host : s.ab_dev).push_back(ms_between(g0, g4));
+        }
+        if (o.time_both) {
+            // (with --host-voxels the device path ran first: its device time was overwritten by the host path's update)
+            float dms = 0;
+            if (!o.host_voxels && fs3d_last_update_device_ms(solver.ctx(), &dms) == FS3D_OK) s.ab_dev_gpu.push_back(dms);
+            fs3d_mesh_fill_rounds(solver.ctx(), &s.fill_rounds);
+            fs3d_synchronize(solver.ctx());
+        }
+        const auto s0 = Clock::now();
+        solver.UpdateBoundaries();                                                                       // :244
+        solver.TimeStep((FTYPE)s.dt, cfg.num_global, cfg.num_local, (i % 10 == 0) || (t + s.dt >= s.finaltime)); // :245
+        if (o.time_both) { fs3d_synchronize(solver.ctx()); s.ab_step.push_back(ms_between(s0, Clock::now())); }
+        if (r == 0) {
+            const float perres = (float)t * 100 / (float)s.finaltime;                                    // PrintTimeStepInfo, IO.h:455-478
+            std::printf("\rerr = %.8f, frame %i\tsubstep %i\t%i%%", solver.diffError, currentframe, i, (int)perres);   // AdiSolver3D.cpp:376
+            if (nslabs == 1 && perres < 2) std::printf("\t(----- left)");
+            else if (nslabs == 1) {
+                const float left = std::chrono::duration<float>(Clock::now() - s.t0).count() * (100 - perres) / perres;
+                std::printf("\t(%i h %i m %i s left)", ((int)left) / 3600, (((int)left) / 60) % 60, ((int)left) % 60);
+            }
+            std::fflush(stdout);
+        }
+        if ((i % cfg.out_time_steps) == 0) record(s, solver, r, s.nc, s.out_ms);                          // :254-264
+        if (o.moves()) { solver.ClearOutterCells(); s.bar.wait(); }      // AdiSolver3D.cpp:382-385; every rank has read this step's geometry
+    }
+    s.bar.wait();                                      // every rank is through its steps: the clock of the `steps in` line stops here
+    if (r == 0) { s.steps = steps; s.sec = std::chrono::duration<double>(Clock::now() - s.t0).count(); }
+    if (nslabs == 1) { print_profiler_table(solver, o); print_closing_lines(s); }    // (one GPU: before the statistics records)
+    if (o.time_stats && steps > 0) {
+        if (r == 0) s.create_result_file(s.ns, s.stats);
+        for (const StatsRecord &rec : stats_records(o)) {
+            solver.SetOutputSource(rec.source);
+            if (o.time_cov) solver.SetOutputMoment(rec.moment);
+            record(s, solver, r, s.ns, nullptr);
+        }
+        solver.SetOutputSource(0);
+    }
+}
+
+template <typename FTYPE>
+static int run_loop(fs3d::Grid3D<FTYPE> &grid, fs3d::Grid2D &g2, fs3d::Shape3D &sh3, const RunGeom &geo, const std::string &prefix,
+                    const fs3d::Config &cfg, const RunOptions &o)
+{
+    Run<FTYPE> s(grid, g2, sh3, geo, prefix, cfg, o);
+    const int nslabs = s.nslabs;
+    if (nslabs == 1) run_rank(s, 0);                   // on the calling thread: no group, no thread
+    else {
+        s.create_result_file(s.nc, s.out);
+        s.group = fs3d::AdiSolver3D<FTYPE>::CreateLocalGroup(nslabs);
+        std::vector<std::exception_ptr> errs(nslabs);
+        std::vector<std::thread> th;
+        s.t0 = Clock::now();
+        for (int r = 0; r < nslabs; r++)
+            th.emplace_back([&, r] {
+                try { run_rank(s, r); }
+                catch (...) {
+                    // release the other slab threads: they wait for this one in the transport (halo planes, carries) or at a
+                    // barrier and would never return
+                    errs[r] = std::current_exception();
+                    fs3d_local_group_abort(s.group);
+                    s.bar.abort();
+                }
+            });
+        for (auto &t : th) t.join();
+        fs3d::AdiSolver3D<FTYPE>::DestroyLocalGroup(s.group);
+        for (auto &e : errs) if (e) {          // the first failure, not the "another slab thread failed" it caused
+            try { std::rethrow_exception(e); } catch (std::exception &x) { if (std::string(x.what()).find("another slab thread") == std::string::npos && std::string(x.what()).find("a peer failed") == std::string::npos) throw; } catch (...) { throw; }
+        }
+        for (auto &e : errs) if (e) std::rethrow_exception(e);
+        std::printf("\n");
+        print_closing_lines(s);
+    }
+    if (o.time_stats) {
+        // steps: the time steps of the run; the line names the accumulated ones, the 1st, (K + 1)th, .. of them
+        if (s.steps > 0) std::printf("Time statistics: %ld steps, mean%s%s in %s\n", (s.steps + o.time_every - 1) / o.time_every,
+                                     o.time_stats == 2 ? ", variance" : "", o.time_cov ? ", covariances" : "", s.stats.c_str());
+        else std::printf("Time statistics: 0 steps, no file\n");
+    }
+    return 0;
+}
+
+template <typename FTYPE>
+static int run(const std::string &data, const std::string &prefix, const fs3d::Config &cfg, const RunOptions &o)
+{
+    check_words(o, cfg);
     using namespace fs3d;
     Grid3D<FTYPE> grid;
     Grid2D g2;
@@ -229,354 +555,13 @@ static int run(const std::string &data, const std::string &prefix, const fs3d::C
         std::fclose(f);
         return 0;
     }
-    if (o.nslabs > 1) return run_slabs<FTYPE>(grid, g2, sh3, geo, prefix, cfg, o);
-    FluidParams<FTYPE> params = cfg.useNormalizedParams ? FluidParams<FTYPE>(cfg.Re, cfg.Pr, cfg.lambda)
-                                                        : FluidParams<FTYPE>(cfg.viscosity, cfg.density, cfg.R_specific, cfg.k, cfg.cv);
-    AdiSolver3D<FTYPE> solver;
-    solver.Init(o.device, grid, params);
-    if (o.watertight) solver.SetMeshVoxels(1);           // the updates voxelise as the host loader did
-    if (o.thin_shell) solver.SetMeshShell(1);
-    if (o.fresh_cells) solver.SetFreshCells(true);
-    if (o.output_box) solver.SetOutputFilter(1);
-    if (o.time_stats) set_time_stats(solver, o);
-    std::printf("Segments: %i %i %i (x, y, z)\n", solver.numSegs[0], solver.numSegs[1], solver.numSegs[2]);
-
-    const int frames = geo.frames;                                     // FluidSolver3D.cpp:194-195
-    const double length = geo.length;
-    const double dt = length / (frames * cfg.time_steps);              // :196
-    const double finaltime = length * cfg.cycles;
-    const std::string out = prefix + "_res.nc";
-    NetCDF3Writer nc;
-    const float *bbox = geo.bbox;
-    DepthInfo3D out_depths;                                                                  // IO.h:270-273
-    if (geo.depths) out_depths = DepthInfo3D(cfg.outdimx, cfg.outdimy, *geo.depths);
-    nc.Create(out, bbox, dt * cfg.out_time_steps, finaltime, cfg.outdimx, cfg.outdimy, cfg.outdimz, cfg.out_vars, geo.depths != nullptr,
-              geo.depths ? out_depths.depth.data() : nullptr);
-    std::vector<FTYPE> resVel((size_t)cfg.outdimx * cfg.outdimy * cfg.outdimz * 3);
-    std::vector<double> resT((size_t)cfg.outdimx * cfg.outdimy * cfg.outdimz);
-
-    solver.EnableTiming(true);
-    const auto t0 = std::chrono::steady_clock::now();
-    double t = dt;
-    long steps = 0;
-    int lastframe = -1;
-    double geom_ms[3] = {0, 0, 0};                     // moving / moving-mesh: host clock around Prepare / SubFrame, the node arrays on the host, the update call
-    std::vector<float> mx, my, mz;                     // moving-mesh: the sub-frame's vertices
-    std::vector<float> mwx, mwy, mwz;                  // ... and their velocities (zeros without --wall-velocity)
-    std::vector<double> ab_host, ab_dev, ab_dev_gpu, ab_step;   // --time-both: per step, ms
-    int fill_rounds = 0;
-    long long fresh_sum[2] = {0, 0}, fresh_updates = 0, fresh_rounds = 0;   // --fresh-cells: fresh and filled cells over the run, updates, most rounds of one fill
-    double out_ms[2] = {0, 0};                         // --time-output: host clock around GetLayer, AppendLayer
-    auto ms_since = [](std::chrono::steady_clock::time_point a) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - a).count(); };
-    // the geometry is frame 0's for the whole run: the reference prepares the grid once, before the loop (grid->Prepare(0), :226;
-    // the per-step grid->Prepare(t) is commented out, :237) -- the frame only restarts the substep counter
-    for (int i = 0; t < finaltime && (o.max_steps < 0 || steps < o.max_steps); t += dt, i++, steps++) {
-        const int currentframe = geo.GetFrame(t);                                                        // :229-236
-        if (currentframe != lastframe) { lastframe = currentframe; i = 0; }
-        if (o.moving || o.moving_mesh) {                                                                 // grid->Prepare(t), :237
-            const bool on_host = o.moving ? o.host_extrusion : o.host_voxels;     // the node arrays are made on the host and go through UpdateGrid
-            if (o.time_both) {                                                                           // the other path first (mesh only)
-                const auto b0 = std::chrono::steady_clock::now();
-                if (o.host_voxels) { solver.UpdateGridShape3D(mx, my, mz, sh3.frames[sh3.SubFrame(t, mx, my, mz)].idx); ab_dev.push_back(ms_since(b0)); }
-                else { sh3.Prepare(t); FillShape3DNodes(grid, sh3, cfg.baseT); solver.UpdateGrid(grid); ab_host.push_back(ms_since(b0)); }
-            }
-            const auto g0 = std::chrono::steady_clock::now();
-            size_t frame = 0;
-            if (o.moving) g2.Prepare(t);
-            else frame = sh3.SubFrame(t, mx, my, mz);
-            const auto g1 = std::chrono::steady_clock::now();
-            if (on_host && o.moving) ExtrudeShape2D(grid, g2, cfg.dz, cfg.depth, cfg.depth_var, cfg.baseT);
-            else if (on_host) { sh3.Prepare(t); FillShape3DNodes(grid, sh3, cfg.baseT, o.wall_T); }
-            else if (o.moving_mesh && walls) {
-                if (o.wall_velocity) sh3.SubFrameVelocity(t, o.wall_velocity, mwx, mwy, mwz);
-                else { mwx.assign(mx.size(), 0.0f); mwy = mwx; mwz = mwx; }
-            }
-            const auto g3 = std::chrono::steady_clock::now();
-            // (on the device, `grid` keeps the nodes of time 0: only its dims and baseT are read from here on)
-            if (on_host) solver.UpdateGrid(grid);
-            else if (o.moving) solver.UpdateGridExtruded(g2, cfg.dz, cfg.depth, cfg.depth_var);
-            else if (walls) solver.UpdateGridShape3D(mx, my, mz, mwx, mwy, mwz, sh3.frames[frame].idx, o.wall_T);
-            else solver.UpdateGridShape3D(mx, my, mz, sh3.frames[frame].idx);
-            const auto g4 = std::chrono::steady_clock::now();
-            if (o.fresh_cells) {                       // the cells this update turned fluid, before UpdateBoundaries
-                long long info[4];
-                solver.FillFreshCells(info);
-                fresh_sum[0] += info[0]; fresh_sum[1] += info[1]; fresh_updates++; fresh_rounds = std::max(fresh_rounds, info[2]);
-            }
-            geom_ms[0] += std::chrono::duration<double, std::milli>(g1 - g0).count();
-            geom_ms[1] += std::chrono::duration<double, std::milli>(g3 - g1).count();
-            geom_ms[2] += std::chrono::duration<double, std::milli>(g4 - g3).count();
-            if (o.time_both) (o.host_voxels ? ab_host : ab_dev).push_back(std::chrono::duration<double, std::milli>(g4 - g0).count());
-        }
-        if (o.time_both) {
-            // (with --host-voxels the device path ran first: its device time was overwritten by the host path's update)
-            float dms = 0;
-            if (!o.host_voxels && fs3d_last_update_device_ms(solver.ctx(), &dms) == FS3D_OK) ab_dev_gpu.push_back(dms);
-            fs3d_mesh_fill_rounds(solver.ctx(), &fill_rounds);
-            fs3d_synchronize(solver.ctx());
-        }
-        const auto s0 = std::chrono::steady_clock::now();
-        solver.UpdateBoundaries();                                                                       // :244
-        solver.TimeStep((FTYPE)dt, cfg.num_global, cfg.num_local, (i % 10 == 0) || (t + dt >= finaltime)); // :245
-        if (o.time_both) { fs3d_synchronize(solver.ctx()); ab_step.push_back(ms_since(s0)); }
-        std::printf("\rerr = %.8f,", solver.diffError);                                                  // AdiSolver3D.cpp:376
-        const float elapsed = std::chrono::duration<float>(std::chrono::steady_clock::now() - t0).count();
-        const float perres = (float)t * 100 / (float)finaltime;                                          // PrintTimeStepInfo, IO.h:455-478
-        if (perres < 2) std::printf(" frame %i\tsubstep %i\t%i%%\t(----- left)", currentframe, i, (int)perres);
-        else {
-            const float left = elapsed * (100 - perres) / perres;
-            std::printf(" frame %i\tsubstep %i\t%i%%\t(%i h %i m %i s left)", currentframe, i, (int)perres, ((int)left) / 3600, (((int)left) / 60) % 60, ((int)left) % 60);
-        }
-        std::fflush(stdout);
-        if ((i % cfg.out_time_steps) == 0) {                                                             // :254-264
-            const auto o0 = std::chrono::steady_clock::now();
-            solver.GetLayer(resVel.data(), resT.data(), cfg.outdimx, cfg.outdimy, cfg.outdimz);
-            const auto o1 = std::chrono::steady_clock::now();
-            nc.AppendLayer(resVel.data(), resT.data());
-            out_ms[0] += std::chrono::duration<double, std::milli>(o1 - o0).count(); out_ms[1] += ms_since(o1);
-        }
-        if (o.moving || o.moving_mesh) solver.ClearOutterCells();                                                           // AdiSolver3D.cpp:382-385
-    }
-    const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    // the reference's Profiler table (Common/Profiler.h:90-131: sorted by total time, events that never ran are absent; event
-    // names of AdiSolver3D.cpp:297-367, 555-680).  Device times from HIP events; MergeLayer has no launches of its own while
-    // the merge is fused into the sweep kernels; CreateSegments is the host time of the geometry upload.
-    const char *names[FS3D_N_EVENTS]; float ms[FS3D_N_EVENTS]; int cnt[FS3D_N_EVENTS];
-    solver.ProfilerEvents(names, ms, cnt);
-    std::vector<int> order;
-    for (int e = 0; e < FS3D_N_EVENTS; e++) if (cnt[e]) order.push_back(e);
-    std::sort(order.begin(), order.end(), [&](int a, int b) { return ms[a] > ms[b]; });
-    double total = 0;
-    if (o.csv) std::printf("\n%s,%s,%s,%s,\n", "Event Name", "Total (ms)", "Avg (ms)", "Count");
-    else std::printf("\nProfiling data node(0):\n%16s%16s%16s%16s\n", "Event Name", "Total (ms)", "Avg (ms)", "Count");
-    for (int e : order) {
-        if (o.csv) std::printf("%s,%.2f,%.2f,%i,\n", names[e], ms[e], ms[e] / cnt[e], cnt[e]);
-        else std::printf("%16s%16.2f%16.2f%16i\n", names[e], ms[e], ms[e] / cnt[e], cnt[e]);
-        total += ms[e];
-    }
-    if (o.csv) std::printf("%s,%.2f,sec\n", "Overall", total / 1000);
-    else std::printf("%16s%16.2f sec\n", "Overall", total / 1000);
-    {
-        int kx, ky, kz, sg;
-        const char *kn[] = {"none", "line", "pipe", "part"};
-        fs3d_last_sweep_kernel(solver.ctx(), 0, &kx, &sg); fs3d_last_sweep_kernel(solver.ctx(), 1, &ky, &sg); fs3d_last_sweep_kernel(solver.ctx(), 2, &kz, &sg);
-        std::printf("Sweep kernels: X %s, Y %s, Z %s\n", kn[kx & 3], kn[ky & 3], kn[kz & 3]);
-    }
-    if (o.fresh_cells) std::printf("Fresh cells: %lld in %lld updates, %lld filled, at most %lld rounds\n", fresh_sum[0], fresh_updates, fresh_sum[1], fresh_rounds);
-    if (o.time_geometry && steps > 0)                  // (before the line of --time-both, which only a mesh has)
-        std::printf(o.moving ? "Moving geometry per step (host clock, ms): Prepare %.3f, extrusion on the host %.3f, update call %.3f; step %.3f\n"
-                             : "Moving mesh per step (host clock, ms): SubFrame %.3f, voxels on the host %.3f, update call %.3f; step %.3f\n",
-                    geom_ms[0] / steps, geom_ms[1] / steps, geom_ms[2] / steps, sec * 1e3 / steps);
-    if (o.time_both) {
-        auto line = [](const char *what, std::vector<double> v) {
-            if (v.size() <= 3) { std::printf(" %s: too few steps;", what); return; }
-            v.erase(v.begin(), v.begin() + 3);
-            std::sort(v.begin(), v.end());
-            const size_t n = v.size();
-            std::printf(" %s median %.3f min %.3f max %.3f n %zu;", what, n % 2 ? v[n / 2] : 0.5 * (v[n / 2 - 1] + v[n / 2]), v.front(), v.back(), n);
-        };
-        std::printf("Moving mesh, both paths per call (ms):");
-        line("host voxels + fs3d_update_nodes", ab_host); line("fs3d_update_nodes_shape3d", ab_dev); line("its device time", ab_dev_gpu);
-        line("time step", ab_step);
-        std::printf(" fill rounds %d\n", fill_rounds);
-    }
-    if (o.time_output && nc.NumRecords() > 0)
-        std::printf("Result output per record (host clock, ms): GetLayer %.3f, AppendLayer %.3f; %u records\n", out_ms[0] / nc.NumRecords(),
-                    out_ms[1] / nc.NumRecords(), nc.NumRecords());
-    std::printf("%ld steps in %.3f s: %.1f Mcells/s; %u layers in %s\n", steps, sec,
-                (double)grid.dimx * grid.dimy * grid.dimz * steps / sec / 1e6, nc.NumRecords(), out.c_str());
-    if (o.time_stats) {
-        const std::string stats = prefix + "_stats.nc";
-        if (steps > 0) {
-            NetCDF3Writer ns;
-            ns.Create(stats, bbox, dt * cfg.out_time_steps, finaltime, cfg.outdimx, cfg.outdimy, cfg.outdimz, cfg.out_vars, geo.depths != nullptr,
-                      geo.depths ? out_depths.depth.data() : nullptr);
-            for (const StatsRecord &rec : stats_records(o)) {
-                solver.SetOutputSource(rec.source);
-                if (o.time_cov) solver.SetOutputMoment(rec.moment);
-                solver.GetLayer(resVel.data(), resT.data(), cfg.outdimx, cfg.outdimy, cfg.outdimz);
-                ns.AppendLayer(resVel.data(), resT.data());
-            }
-            solver.SetOutputSource(0);
-        }
-        print_stats_line(steps, o, stats);
-    }
-    return 0;
-}
-
-// "GPU n" with n > 1: the reference's single-process multi-GPU mode (GPUplan): n x-slabs (GPUplan::splitEven1D,
-// GPUplan.cpp:122-141), one solver and one host thread per slab, joined by the library's in-process group.
-// Results equal the single-GPU run's value for value.  Slab r runs on device r, or all on device 0 with --same-device.
-// moving / moving-mesh --host-voxels: rank 0 prepares the geometry of time t on the host (Prepare, and the host extrusion or
-// voxelisation into the shared Grid3D where asked), a barrier, then every rank rebuilds the tables of its own planes from that
-// global input (UpdateGrid / UpdateGridExtruded: the slab entries, no rank waits for another inside them).
-// moving-mesh --slab-voxels: rank 0 computes the sub-frame's vertices (and their velocities) into shared vectors, a barrier, then
-// every rank voxelises the mesh for itself (UpdateGridShape3D: the slab entries).  Either way, after the step
-// ClearOutterCells on every rank, and a barrier before rank 0 prepares the next geometry in the arrays the others have read.
-namespace {
-struct Barrier {
-    std::mutex m; std::condition_variable cv; int n, waiting = 0; long gen = 0; bool broken = false;
-    explicit Barrier(int n_) : n(n_) {}
-    void wait()
-    {
-        std::unique_lock<std::mutex> lk(m);
-        const long g = gen;
-        if (++waiting == n) { waiting = 0; gen++; cv.notify_all(); } else cv.wait(lk, [&] { return gen != g || broken; });
-        if (broken) throw std::runtime_error("another slab thread failed");
-    }
-    void abort() { { std::lock_guard<std::mutex> lk(m); broken = true; } cv.notify_all(); }
-};
-}
-
-template <typename FTYPE>
-static int run_slabs(fs3d::Grid3D<FTYPE> &grid, fs3d::Grid2D &g2, fs3d::Shape3D &sh3, const RunGeom &geo, const std::string &prefix,
-                     const fs3d::Config &cfg, const RunOptions &o)
-{
-    using namespace fs3d;
-    const int nslabs = o.nslabs;
-    const bool same_device = o.same_device, time_output = o.time_output, moves = o.moving || o.moving_mesh;
-    const bool on_host = o.moving ? o.host_extrusion : o.host_voxels;
-    const bool walls = o.wall_velocity || o.has_wall_T;    // --slab-voxels: the entry that takes velocities and a wall temperature
-    std::vector<float> mx, my, mz, mwx, mwy, mwz;          // --slab-voxels: the sub-frame of the step, written by rank 0 and read by all
-    size_t mframe = 0;
-    const long max_steps = o.max_steps;
-    // --slab-fresh-cells: every rank's own fresh and filled cells over the run; the updates and the most rounds of one fill (the group's: rank 0 writes them)
-    std::vector<long long> fresh_own(nslabs, 0), filled_own(nslabs, 0);
-    long long fresh_updates = 0, fresh_rounds = 0;
-    FluidParams<FTYPE> params = cfg.useNormalizedParams ? FluidParams<FTYPE>(cfg.Re, cfg.Pr, cfg.lambda)
-                                                        : FluidParams<FTYPE>(cfg.viscosity, cfg.density, cfg.R_specific, cfg.k, cfg.cv);
-    const double length = geo.length, dt = length / (geo.frames * cfg.time_steps), finaltime = length * cfg.cycles;
-    const std::string out = prefix + "_res.nc";
-    NetCDF3Writer nc, ns;                              // ns: --time-stats, <prefix>_stats.nc (rank 0 creates and appends)
-    const std::string stats = prefix + "_stats.nc";
-    const float *bbox = geo.bbox;
-    DepthInfo3D out_depths;                                                                  // IO.h:270-273
-    if (geo.depths) out_depths = DepthInfo3D(cfg.outdimx, cfg.outdimy, *geo.depths);
-    nc.Create(out, bbox, dt * cfg.out_time_steps, finaltime, cfg.outdimx, cfg.outdimy, cfg.outdimz, cfg.out_vars, geo.depths != nullptr,
-              geo.depths ? out_depths.depth.data() : nullptr);
-    std::vector<FTYPE> resVel((size_t)cfg.outdimx * cfg.outdimy * cfg.outdimz * 3);
-    std::vector<double> resT((size_t)cfg.outdimx * cfg.outdimy * cfg.outdimz);
-    double out_ms[2] = {0, 0};                         // --time-output (rank 0): host clock until the record is complete, AppendLayer
-    void *group = AdiSolver3D<FTYPE>::CreateLocalGroup(nslabs);
-    Barrier bar(nslabs);
-    std::vector<std::exception_ptr> errs(nslabs);
-    std::vector<std::thread> th;
-    long steps_done = 0;
-    const auto t0 = std::chrono::steady_clock::now();
-    for (int r = 0; r < nslabs; r++)
-        th.emplace_back([&, r] {
-            try {
-                const int q = grid.dimx / nslabs, rem = grid.dimx % nslabs;
-                const int x0 = r * q + std::min(r, rem), x1 = x0 + q + (r < rem ? 1 : 0);
-                AdiSolver3D<FTYPE> solver;
-                solver.Init(same_device ? 0 : r, grid, params, x0, x1);
-                solver.JoinLocalGroup(group, r);
-                if (o.watertight) solver.SetMeshVoxels(1);           // the updates voxelise as the host loader did
-                if (o.thin_shell) solver.SetMeshShell(1);
-                if (o.fresh_cells) { solver.SetFreshCells(true); solver.SetFreshCellsSlabs(true); }
-                if (o.time_stats) set_time_stats(solver, o);
-                // every rank has uploaded the grid of time 0 before rank 0 writes the next geometry into the same arrays (Init
-                // reads them, and joining the group is no rendezvous)
-                if (moves) bar.wait();
-                if (r == 0) std::printf("Slabs: %d x-slabs of %d..%d planes\n", nslabs, q, q + (rem ? 1 : 0));
-                double t = dt;
-                long steps = 0;
-                int lastframe = -1;
-                for (int i = 0; t < finaltime && (max_steps < 0 || steps < max_steps); t += dt, i++, steps++) {
-                    const int currentframe = geo.GetFrame(t);
-                    if (currentframe != lastframe) { lastframe = currentframe; i = 0; }
-                    if (moves) {
-                        if (r == 0) {
-                            if (o.moving) { g2.Prepare(t); if (on_host) ExtrudeShape2D(grid, g2, cfg.dz, cfg.depth, cfg.depth_var, cfg.baseT); }
-                            else if (on_host) { sh3.Prepare(t); FillShape3DNodes(grid, sh3, cfg.baseT, o.wall_T); }
-                            else {
-                                mframe = sh3.SubFrame(t, mx, my, mz);
-                                if (o.wall_velocity) sh3.SubFrameVelocity(t, o.wall_velocity, mwx, mwy, mwz);
-                                else if (walls) { mwx.assign(mx.size(), 0.0f); mwy = mwx; mwz = mwx; }
-                            }
-                        }
-                        bar.wait();
-                        if (on_host) solver.UpdateGrid(grid);
-                        else if (o.moving) solver.UpdateGridExtruded(g2, cfg.dz, cfg.depth, cfg.depth_var);
-                        else if (walls) solver.UpdateGridShape3D(mx, my, mz, mwx, mwy, mwz, sh3.frames[mframe].idx, o.wall_T);
-                        else solver.UpdateGridShape3D(mx, my, mz, sh3.frames[mframe].idx);
-                        if (o.fresh_cells) {               // the cells this update turned fluid, all slabs together, before UpdateBoundaries
-                            long long info[4];
-                            solver.FillFreshCells(info);
-                            fresh_own[r] += info[0]; filled_own[r] += info[1];
-                            if (r == 0) { fresh_updates++; fresh_rounds = std::max(fresh_rounds, info[2]); }
-                        }
-                    }
-                    solver.UpdateBoundaries();
-                    solver.TimeStep((FTYPE)dt, cfg.num_global, cfg.num_local, (i % 10 == 0) || (t + dt >= finaltime));
-                    if (r == 0) { std::printf("\rerr = %.8f, frame %i\tsubstep %i\t%i%%", solver.diffError, currentframe, i, (int)((float)t * 100 / (float)finaltime)); std::fflush(stdout); }
-                    if ((i % cfg.out_time_steps) == 0) {
-                        // each slab samples the rows of the result whose source planes it owns (FilterToArrays, TimeLayer3D.h:819-924)
-                        // straight into the shared arrays: the rows are disjoint
-                        const auto o0 = std::chrono::steady_clock::now();
-                        int rows[2];
-                        solver.GetLayerRows(resVel.data(), resT.data(), cfg.outdimx, cfg.outdimy, cfg.outdimz, rows);
-                        bar.wait();
-                        if (r == 0) {
-                            const auto o1 = std::chrono::steady_clock::now();
-                            nc.AppendLayer(resVel.data(), resT.data());
-                            out_ms[0] += std::chrono::duration<double, std::milli>(o1 - o0).count();
-                            out_ms[1] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - o1).count();
-                        }
-                        bar.wait();                    // nobody writes the next record's rows while rank 0 still reads this one
-                    }
-                    if (moves) { solver.ClearOutterCells(); bar.wait(); }      // AdiSolver3D.cpp:382-385; every rank has read this step's geometry
-                }
-                if (r == 0) steps_done = steps;
-                if (o.time_stats && steps > 0) {
-                    // the statistics records as the normal ones: every slab writes its rows of the shared arrays, rank 0 appends
-                    if (r == 0) ns.Create(stats, bbox, dt * cfg.out_time_steps, finaltime, cfg.outdimx, cfg.outdimy, cfg.outdimz, cfg.out_vars,
-                                          geo.depths != nullptr, geo.depths ? out_depths.depth.data() : nullptr);
-                    for (const StatsRecord &rec : stats_records(o)) {
-                        int rows[2];
-                        solver.SetOutputSource(rec.source);
-                        if (o.time_cov) solver.SetOutputMoment(rec.moment);
-                        solver.GetLayerRows(resVel.data(), resT.data(), cfg.outdimx, cfg.outdimy, cfg.outdimz, rows);
-                        bar.wait();
-                        if (r == 0) ns.AppendLayer(resVel.data(), resT.data());
-                        bar.wait();
-                    }
-                    solver.SetOutputSource(0);
-                }
-            } catch (...) {
-                // release the other slab threads: they wait for this one in the transport (halo planes, carries) or at the
-                // output barrier and would never return
-                errs[r] = std::current_exception();
-                fs3d_local_group_abort(group);
-                bar.abort();
-            }
-        });
-    for (auto &t : th) t.join();
-    AdiSolver3D<FTYPE>::DestroyLocalGroup(group);
-    for (auto &e : errs) if (e) {          // the first failure, not the "another slab thread failed" it caused
-        try { std::rethrow_exception(e); } catch (std::exception &x) { if (std::string(x.what()).find("another slab thread") == std::string::npos && std::string(x.what()).find("a peer failed") == std::string::npos) throw; } catch (...) { throw; }
-    }
-    for (auto &e : errs) if (e) std::rethrow_exception(e);
-    const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    std::printf("\n");
-    if (o.fresh_cells) {
-        long long fresh = 0, filled = 0;
-        for (int r = 0; r < nslabs; r++) { fresh += fresh_own[r]; filled += filled_own[r]; }
-        std::printf("Fresh cells: %lld in %lld updates, %lld filled, at most %lld rounds\n", fresh, fresh_updates, filled, fresh_rounds);
-    }
-    if (time_output && nc.NumRecords() > 0)
-        std::printf("Result output per record (host clock, ms): GetLayer %.3f, AppendLayer %.3f; %u records\n", out_ms[0] / nc.NumRecords(),
-                    out_ms[1] / nc.NumRecords(), nc.NumRecords());
-    std::printf("%ld steps in %.3f s: %.1f Mcells/s; %u layers in %s\n", steps_done, sec,
-                (double)grid.dimx * grid.dimy * grid.dimz * steps_done / sec / 1e6, nc.NumRecords(), out.c_str());
-    if (o.time_stats) print_stats_line(steps_done, o, stats);
-    return 0;
+    return run_loop<FTYPE>(grid, g2, sh3, geo, prefix, cfg, o);
 }
 
 int main(int argc, char **argv)
 {
     if (argc < 4) {
-        std::printf("Usage: %s <input data> <output prefix> <config file> [align] [GPU [n]] [double] [--steps N] [moving [--host-extrusion] [--time-geometry]] [moving-mesh [--host-voxels | --slab-voxels] [--time-geometry] [--time-both]] [--time-output] [--grid-only FILE [--grid-time T]] [--grid-images] [--watertight [--thin-shell] [--wall-velocity motion|file]] [--wall-temperature T] [--fresh-cells | --slab-fresh-cells] [--output-filter point|box] [--time-stats mean|variance] [--time-covariances] [--time-stats-every K]\n", argv[0]);
+        std::printf("Usage: %s %s\n", argv[0], USAGE);
         return 0;
     }
     try {
