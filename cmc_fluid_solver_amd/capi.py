@@ -39,6 +39,7 @@ OUTPUT_SOURCE = {"next": 0, "mean": 1, "variance": 2, "fraction": 3}
 OPT_TIME_STATS_CROSS = 16  # 1: mode 2 also sums the six products uv, uw, vw, uT, vT, wT per cell; every set opens a new window, 0 frees them (default 0)
 OPT_OUTPUT_MOMENT = 17    # what source 2 builds: 0 the variances (default), 1 the Reynolds stresses and k, 2 the heat fluxes and var_T (time_stats.MOMENTS)
 OPT_TIME_STATS_EVERY = 18  # the stride k of the accumulated steps, 1 (default) .. 2^20: candidate s of a window counts where (s - 1) % k == 0; every set opens a new window
+OPT_OUTPUT_SLABS = 19     # 1: on a member of a group GetLayerRows / GetLayerDev take the filter and vector options, as one collective call (default 0)
 XSOLVE_AUTO, XSOLVE_PIPELINED, XSOLVE_REDUCED, XSOLVE_REDUCED_A2A = 0, 1, 2, 3
 
 # every function include/fs3d.h declares, in the header's order: name -> (restype, argtypes)

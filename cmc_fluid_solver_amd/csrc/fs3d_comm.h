@@ -12,6 +12,12 @@ fs3d_status fs3d_comm_halo_exchange(fs3d_ctx *c, int buf, int nfields);
 // addresses the first owned plane of a byte array laid out as a field: a ghost plane in front of it and one behind the last.
 // No-op for one rank.
 fs3d_status fs3d_comm_fill_exchange(fs3d_ctx *c, int buf, uint8_t *tag);
+// The same grouped exchange for any four fields laid out as a layer buffer's (`base`: the ghost plane below field 0, `fstride`
+// elements from field to field) and any four planes of bytes: the own first and last plane go out, the neighbours' come in.  The
+// collective result records (FS3D_OPT_OUTPUT_SLABS) move the sampled layer -- `next` or the statistic layer -- and the node types
+// of the planes at the cuts with it.  No-op for one rank.
+struct fs3d_byte_planes { uint8_t *send_lo, *send_hi, *recv_lo, *recv_hi; };
+fs3d_status fs3d_comm_layer_exchange(fs3d_ctx *c, void *base, long long fstride, const fs3d_byte_planes &b);
 // in-place sum of two doubles on the device over all ranks (TimeLayer3D.h:630-637). No-op for one rank.
 fs3d_status fs3d_comm_allreduce_sum2(fs3d_ctx *c, double *dev2);
 // the same for n doubles.  EvalDivError of a group: every rank holds zeros but for its own planes' partial sums, so each sum has one

@@ -244,6 +244,7 @@ void fs3d_comm_destroy(fs3d_ctx *c)
     // the buffers whose size depends on the group: the next group makes its own
     for (int i = 0; i < 4; i++) { c->carry[i].reset(); c->xa2a[i].reset(); }
     c->xif_send.reset(); c->xif_all.reset();
+    c->os_cut_dev.reset(); c->os_cuts.clear();
 }
 
 // one grouped exchange: every send and receive of `ops` is in flight together (no ordering deadlock)
@@ -263,13 +264,14 @@ static fs3d_status exec_group(fs3d_ctx *c, const std::vector<XOp> &ops)
     return FS3D_OK;
 }
 
-// the boundary planes of the first nfields fields of layer buffer `buf`, to and from either neighbour
-static void halo_ops(fs3d_ctx *c, int buf, int nfields, std::vector<XOp> &ops)
+// the boundary planes of nfields fields laid out as a layer buffer's -- `base` the ghost plane below field 0, `fstride` elements from
+// field to field -- to and from either neighbour
+static void halo_ops(fs3d_ctx *c, void *base0, long long fstride, int nfields, std::vector<XOp> &ops)
 {
     const size_t pl = (size_t)c->plane;
     // layout per field: [ghost lo][dimx owned planes][ghost hi]; one grouped send/recv per neighbour
     for (int v = 0; v < nfields; v++) {
-        char *base = (char *)c->lay[buf] + (size_t)v * c->fstride * c->esize;
+        char *base = (char *)base0 + (size_t)v * fstride * c->esize;
         char *first = base + pl * c->esize;                       // first owned plane
         char *last = base + (size_t)c->dimx * pl * c->esize;      // last owned plane
         char *glo = base;                                         // ghost below
@@ -283,21 +285,26 @@ fs3d_status fs3d_comm_halo_exchange(fs3d_ctx *c, int buf, int nfields)
 {
     if (c->nranks == 1) return FS3D_OK;
     std::vector<XOp> ops;
-    halo_ops(c, buf, nfields, ops);
+    halo_ops(c, c->lay[buf], c->fstride, nfields, ops);
+    return exec_group(c, ops);
+}
+
+fs3d_status fs3d_comm_layer_exchange(fs3d_ctx *c, void *base, long long fstride, const fs3d_byte_planes &b)
+{
+    if (c->nranks == 1) return FS3D_OK;
+    const size_t pl = (size_t)c->plane;
+    std::vector<XOp> ops;
+    halo_ops(c, base, fstride, 4, ops);
+    if (c->rank > 0) { ops.push_back({b.send_lo, pl, c->rank - 1, true, true}); ops.push_back({b.recv_lo, pl, c->rank - 1, false, true}); }
+    if (c->rank < c->nranks - 1) { ops.push_back({b.send_hi, pl, c->rank + 1, true, true}); ops.push_back({b.recv_hi, pl, c->rank + 1, false, true}); }
     return exec_group(c, ops);
 }
 
 fs3d_status fs3d_comm_fill_exchange(fs3d_ctx *c, int buf, uint8_t *tag)
 {
-    if (c->nranks == 1) return FS3D_OK;
-    const size_t pl = (size_t)c->plane;
-    std::vector<XOp> ops;
-    halo_ops(c, buf, 4, ops);
     // the tag array has the fields' layout, one byte per cell: `tag` is its first owned plane
-    uint8_t *last = tag + (size_t)(c->dimx - 1) * pl, *glo = tag - pl, *ghi = tag + (size_t)c->dimx * pl;
-    if (c->rank > 0) { ops.push_back({tag, pl, c->rank - 1, true, true}); ops.push_back({glo, pl, c->rank - 1, false, true}); }
-    if (c->rank < c->nranks - 1) { ops.push_back({last, pl, c->rank + 1, true, true}); ops.push_back({ghi, pl, c->rank + 1, false, true}); }
-    return exec_group(c, ops);
+    const size_t pl = (size_t)c->plane;
+    return fs3d_comm_layer_exchange(c, c->lay[buf], c->fstride, {tag, tag + (size_t)(c->dimx - 1) * pl, tag - pl, tag + (size_t)c->dimx * pl});
 }
 
 fs3d_status fs3d_comm_allreduce_sum(fs3d_ctx *c, double *dev, size_t n)

@@ -187,6 +187,16 @@ struct fs3d_ctx {
     int opt_fresh_slabs = 0;               // FS3D_OPT_FRESH_CELLS_SLABS: 1 = a slab of a group keeps that snapshot too and fills collectively
     int opt_out_filter = 0;                // FS3D_OPT_OUTPUT_FILTER: 1 = the GetLayer entries average the NODE_IN cells of every sample's box (k_get_layer_box)
     int opt_out_vector = 0;                // FS3D_OPT_OUTPUT_VECTOR: 1 = their outV holds the vorticity (k_get_layer_box<R, true>)
+    // FS3D_OPT_OUTPUT_SLABS: 1 = on a member of a group fs3d_get_layer_rows / _dev take the two options above as one collective call
+    // (get_layer_slabs_impl).  Its buffers are allocated by the first call that needs them, kept and only grown, counted in gl_info[2]:
+    // os_type -- four planes of node types, a byte per cell: the own first and last plane (derived from `code` per call), the lower
+    // and the upper neighbour's; os_part -- the five partial sums per sample of the straddling rows, [row][4 sums, count][ody*odz];
+    // os_cuts -- (x_offset, dimx) of every rank, gathered once through os_cut_dev (the cuts of a group never move)
+    int opt_out_slabs = 0;
+    DevBuf<uint8_t> os_type;
+    DevBuf<double> os_part;
+    DevBuf<> os_cut_dev;
+    std::vector<int> os_cuts;
     // time statistics (kernels_stats.hip): per own cell, no ghost planes -- the steps it was NODE_IN (ts_n), the double sums of U, V, W, T
     // over those steps (ts_s1, field v at + v * ts_stride), in mode 2 of their squares (ts_s2) and, in mode 2 with
     // FS3D_OPT_TIME_STATS_CROSS, of the six products uv, uw, vw, uT, vT, wT (ts_sx, pair p at + p * ts_stride).  Each is allocated by
@@ -286,8 +296,10 @@ void fs3d_geom_destroy(fs3d_ctx *c);
 // (the first one allocates and clears); else nothing
 fs3d_status fs3d_time_stats_accumulate(fs3d_ctx *c);
 // the statistic layer of `source` (1 mean, 2 second moments -- `moment` 0 variance, 1 stresses, 2 heat fluxes --, 3 fluid fraction)
-// into ts_q, enqueued; q_out: its four fields
-fs3d_status fs3d_time_stats_layer(fs3d_ctx *c, int source, int moment, void *q_out[4], bool *grown);
+// into ts_q, enqueued; q_out: its four fields.  `ghost`: ts_q in the layout of a layer buffer, a ghost plane on either side of every
+// field (the collective records of FS3D_OPT_OUTPUT_SLABS exchange them); *qstride_out: elements from field to field
+fs3d_status fs3d_time_stats_layer(fs3d_ctx *c, int source, int moment, void *q_out[4], bool *grown, bool ghost = false,
+                                  long long *qstride_out = nullptr);
 // all accumulators / the cross sums alone; the caller has synchronised the stream
 void fs3d_time_stats_free(fs3d_ctx *c);
 void fs3d_time_stats_free_cross(fs3d_ctx *c);

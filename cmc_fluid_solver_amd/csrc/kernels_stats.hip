@@ -131,7 +131,7 @@ template <typename R>
 __global__ void __launch_bounds__(256) k_time_stats_layer(int source, int moment, long long ncell, double steps, const R *__restrict__ cur,
                                                            long long fstride, const unsigned *__restrict__ cnt,
                                                            const double *__restrict__ s1, const double *__restrict__ s2,
-                                                           const double *__restrict__ sx, long long sstride, R *__restrict__ q)
+                                                           const double *__restrict__ sx, long long sstride, R *__restrict__ q, long long qstride)
 {
     const long long l = (long long)blockIdx.x * 256 + threadIdx.x;
     if (l >= ncell) return;
@@ -159,7 +159,7 @@ __global__ void __launch_bounds__(256) k_time_stats_layer(int source, int moment
             r[3] = moment == 1 ? (R)(0.5 * ((var[0] + var[1]) + var[2])) : (R)var[3];
         }
 #pragma unroll
-        for (int v = 0; v < 4; v++) q[v * sstride + l] = r[v];
+        for (int v = 0; v < 4; v++) q[v * qstride + l] = r[v];
         return;
     }
 #pragma unroll
@@ -177,7 +177,7 @@ __global__ void __launch_bounds__(256) k_time_stats_layer(int source, int moment
         } else if (v == 3 && n) {
             r = (R)(dn / steps);
         }
-        q[v * sstride + l] = r;
+        q[v * qstride + l] = r;
     }
 }
 
@@ -231,20 +231,24 @@ fs3d_status fs3d_time_stats_accumulate(fs3d_ctx *c)
 }
 
 template <typename R>
-static void launch_layer(fs3d_ctx *c, int source, int moment)
+static void launch_layer(fs3d_ctx *c, int source, int moment, R *q, long long qstride)
 {
     const R *const cur = (const R *)c->lay[c->slot[FS3D_LAYER_CUR]] + c->plane;
     hipLaunchKernelGGL((k_time_stats_layer<R>), dim3((unsigned)((c->ncell + 255) / 256)), dim3(256), 0, c->stream, source, moment,
                        c->ncell, (double)c->ts_steps, cur, c->fstride, (const unsigned *)c->ts_n, (const double *)c->ts_s1,
-                       (const double *)c->ts_s2, (const double *)c->ts_sx, c->ts_stride, (R *)c->ts_q);
+                       (const double *)c->ts_s2, (const double *)c->ts_sx, c->ts_stride, q, qstride);
 }
 
-fs3d_status fs3d_time_stats_layer(fs3d_ctx *c, int source, int moment, void *q_out[4], bool *grown)
+fs3d_status fs3d_time_stats_layer(fs3d_ctx *c, int source, int moment, void *q_out[4], bool *grown, bool ghost, long long *qstride_out)
 {
-    BUFCHK(c, c->ts_q.reserve((size_t)4 * c->ts_stride * c->esize, nullptr, grown));
-    if (c->prec == FS3D_F32) launch_layer<float>(c, source, moment); else launch_layer<double>(c, source, moment);
+    // `ghost`: [ghost plane][own cells][ghost plane] per field, as a layer buffer; the kernel writes the own cells either way
+    const long long qstride = c->ts_stride + (ghost ? 2 * c->plane : 0), first = ghost ? c->plane : 0;
+    BUFCHK(c, c->ts_q.reserve((size_t)4 * qstride * c->esize, nullptr, grown));
+    char *const q = (char *)c->ts_q.raw() + (size_t)first * c->esize;
+    if (c->prec == FS3D_F32) launch_layer<float>(c, source, moment, (float *)q, qstride); else launch_layer<double>(c, source, moment, (double *)q, qstride);
     HIPCHK(c, hipGetLastError());
-    for (int v = 0; v < 4; v++) q_out[v] = (char *)c->ts_q.raw() + (size_t)v * c->ts_stride * c->esize;
+    for (int v = 0; v < 4; v++) q_out[v] = q + (size_t)v * qstride * c->esize;
+    if (qstride_out) *qstride_out = qstride;
     return FS3D_OK;
 }
 

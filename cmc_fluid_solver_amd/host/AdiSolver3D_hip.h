@@ -143,6 +143,9 @@ public:
     // NODE_IN cells of every sample's box of source cells (the point sample where a box holds none).  While it is not 0 the calls
     // of a slab solver throw (FS3D_ERR_UNSUPPORTED)
     void SetOutputFilter(int mode) { chk(fs3d_set_option(ctx_, FS3D_OPT_OUTPUT_FILTER, mode)); }
+    // FS3D_OPT_OUTPUT_SLABS: 1 = on a slab of a group GetLayerRows / GetLayerDev take the filter and vector options, as one collective call of
+    // all slabs (every rank between the same two steps, with the same output dims and options); 0 (default): they refuse them on a slab
+    void SetOutputSlabs(int on) { chk(fs3d_set_option(ctx_, FS3D_OPT_OUTPUT_SLABS, on)); }
     // FS3D_OPT_OUTPUT_VECTOR for the same calls: 0 resVel holds the velocity, 1 the vorticity (central differences on the NODE_IN
     // cells whose six neighbours are no NODE_OUT cells, 99999 on NODE_OUT cells, 0 elsewhere); slab solvers throw as above
     void SetOutputVector(int mode) { chk(fs3d_set_option(ctx_, FS3D_OPT_OUTPUT_VECTOR, mode)); }

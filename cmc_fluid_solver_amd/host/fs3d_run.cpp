@@ -55,6 +55,10 @@
 //   fluid); `point`, the default, is the reference's sample.  With an output grid at least as fine as the grid the two are the same
 //   bytes.  `box` is refused with GPU n, n > 1, when the arguments are read: a box can straddle the cut between two x-slabs.
 //   (The vorticity, FS3D_OPT_OUTPUT_VECTOR, has no word: the result file's variables are the reference's u, v, w, T.)
+// --slab-output-filter point|box: --output-filter that also runs with GPU n -- `box` calls SetOutputSlabs(1) and SetOutputFilter(1) on every
+//   slab before the loop (FS3D_OPT_OUTPUT_SLABS): every record, the ones of <prefix>_stats.nc among them, is then a collective call of
+//   the slabs, which add the partial sums of the rows whose box straddles a cut, and holds the global grid's box means.  With an
+//   output grid at least as fine as the grid the file is the single-GPU run's, byte for byte.  With one GPU it is --output-filter.
 // --time-stats mean|variance: SetTimeStats(1 | 2) before the loop -- every time step adds its result to per-cell sums on the device
 //   (FS3D_OPT_TIME_STATS) -- and after the loop one more file, <prefix>_stats.nc, with the header of _res.nc: record 0 is the time mean of
 //   u, v, w, T over the steps of the run, with `variance` record 1 is their variance, the last record is the fluid fraction (the share of the
@@ -116,7 +120,7 @@ struct RunOptions {
     bool moving = false, host_extrusion = false, moving_mesh = false, host_voxels = false, slab_voxels = false, time_geometry = false, time_both = false, time_output = false;
     double grid_time = -1, wall_T = 0;
     int wall_velocity = 0;                             // 0: walls at rest; 1: motion; 2: file (Shape3D::wall_velocity)
-    bool has_wall_T = false, fresh_cells = false, slab_fresh_cells = false, output_box = false;
+    bool has_wall_T = false, fresh_cells = false, slab_fresh_cells = false, output_box = false, slab_output_box = false;
     int time_stats = 0;                                // --time-stats: 0 none, 1 mean, 2 mean and variance (FS3D_OPT_TIME_STATS)
     bool time_cov = false;                             // --time-covariances (FS3D_OPT_TIME_STATS_CROSS; needs time_stats 2)
     long time_every = 1;                               // --time-stats-every K (FS3D_OPT_TIME_STATS_EVERY)
@@ -128,7 +132,7 @@ struct RunOptions {
     bool walls() const { return wall_velocity || has_wall_T; }               // the mesh updates go through the entries that take velocities and a wall temperature
 };
 
-static const char USAGE[] = "<input data> <output prefix> <config file> [align] [GPU [n]] [double] [--steps N] [moving [--host-extrusion] [--time-geometry]] [moving-mesh [--host-voxels | --slab-voxels] [--time-geometry] [--time-both]] [--time-output] [--grid-only FILE [--grid-time T]] [--grid-images] [--watertight [--thin-shell] [--wall-velocity motion|file]] [--wall-temperature T] [--fresh-cells | --slab-fresh-cells] [--output-filter point|box] [--time-stats mean|variance] [--time-covariances] [--time-stats-every K]";
+static const char USAGE[] = "<input data> <output prefix> <config file> [align] [GPU [n]] [double] [--steps N] [moving [--host-extrusion] [--time-geometry]] [moving-mesh [--host-voxels | --slab-voxels] [--time-geometry] [--time-both]] [--time-output] [--grid-only FILE [--grid-time T]] [--grid-images] [--watertight [--thin-shell] [--wall-velocity motion|file]] [--wall-temperature T] [--fresh-cells | --slab-fresh-cells] [--output-filter point|box] [--slab-output-filter point|box] [--time-stats mean|variance] [--time-covariances] [--time-stats-every K]";
 
 // the refusals that need no geometry, in the order a user meets them
 static void check_words(const RunOptions &o, const fs3d::Config &cfg)
@@ -186,6 +190,7 @@ static void apply_options(Solver &solver, const RunOptions &o, int nslabs)
     if (o.thin_shell) solver.SetMeshShell(1);
     if (o.fresh_cells) solver.SetFreshCells(true);
     if (o.fresh_cells && nslabs > 1) solver.SetFreshCellsSlabs(true);
+    if (o.output_box && nslabs > 1) solver.SetOutputSlabs(1);   // --slab-output-filter box (check in main: the plain word never gets here with slabs)
     if (o.output_box) solver.SetOutputFilter(1);
     if (o.time_stats) solver.SetTimeStats(o.time_stats);
     if (o.time_stats && o.time_cov) solver.SetTimeStatsCross(1);
@@ -601,10 +606,11 @@ int main(int argc, char **argv)
             }
             else if (s == "--fresh-cells") o.fresh_cells = true;
             else if (s == "--slab-fresh-cells") o.fresh_cells = o.slab_fresh_cells = true;
-            else if (s == "--output-filter") {
+            else if (s == "--output-filter" || s == "--slab-output-filter") {       // one check for the argument of both words
                 const std::string w = a + 1 < argc ? argv[++a] : "";
                 if (w != "point" && w != "box") throw std::runtime_error("--output-filter: point or box");
                 o.output_box = w == "box";
+                o.slab_output_box = o.output_box && s == "--slab-output-filter";
             }
             else if (s == "--time-stats") {
                 const std::string w = a + 1 < argc ? argv[++a] : "";
@@ -629,7 +635,7 @@ int main(int argc, char **argv)
             // transpose, decompose: accepted, no effect
         }
         if (o.time_cov && o.time_stats != 2) throw std::runtime_error("--time-covariances: needs --time-stats variance");
-        if (o.output_box && o.nslabs > 1)
+        if (o.output_box && !o.slab_output_box && o.nslabs > 1)
             throw std::runtime_error("--output-filter box: single GPU only (with GPU n the grid is cut into x-slabs, a sample's box of source cells can "
                                      "straddle a cut, and the library refuses filtered records on a slab)");
         return o.dbl ? run<double>(argv[1], argv[2], cfg, o) : run<float>(argv[1], argv[2], cfg, o);

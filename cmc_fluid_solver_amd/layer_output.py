@@ -137,6 +137,98 @@ def layer_output(type, fields, outdims=(0, 0, 0), filter=POINT, vector=VELOCITY,
     return outV, outT
 
 
+# ---- the record on x-slabs (FS3D_OPT_OUTPUT_SLABS): every slab reduces its own planes, the partial sums of the rows at the cuts travel ----
+# `cuts`: the planes [x0, x1) of every rank, in rank order, a partition of [0, gx).  The statement works from the GLOBAL arrays: q of
+# a cell is the global rule's (the library gets the same bits from its own planes, the neighbours' boundary planes and their types).
+
+def owned_rows(cuts, rank, gx, odx):
+    """Rows [i0, i1) of the record that rank writes: those whose box begins in its planes (slab.out_rows)"""
+    odx = odx or gx
+    x0, x1 = cuts[rank]
+    return -(-x0 * odx // gx), -(-x1 * odx // gx)
+
+
+def straddling_rows(cuts, gx, odx):
+    """The rows whose box holds planes of more than one slab, ascending: at most len(cuts) - 1, whatever the width of a box"""
+    lo, hi = boxes(gx, odx)
+    rows = []
+    for x0, _ in cuts[1:]:
+        for i in np.nonzero((lo < x0) & (hi > x0))[0]:
+            if int(i) not in rows:
+                rows.append(int(i))
+    return sorted(rows)
+
+
+def slab_partials(type, fields, cuts, rank, outdims=(0, 0, 0), filter=POINT, vector=VELOCITY, spacing=None):
+    """What one rank computes before anything travels: ((i0, i1), outV [i1 - i0, ody, odz, 3], outT [i1 - i0, ody, odz], partials).
+    The owned rows that straddle no cut are finished (the others are NaN); partials: {straddling row: float64 [5, ody, odz]} for
+    EVERY straddling row of the group -- the four double sums and the count over the NODE_IN cells of the box that lie in the rank's
+    own planes, zeros where its planes miss the box.  filter 0 has no straddling row: a sample is one cell, and its owner holds it."""
+    type = np.asarray(type)
+    q = cell_quantities(type, fields, vector, spacing)
+    R = q[0].dtype
+    gx = type.shape[0]
+    ax = [boxes(g, o) for g, o in zip(type.shape, outdims)]
+    od = [len(lo) for lo, _ in ax]
+    x0s, x1s = cuts[rank]
+    i0, i1 = owned_rows(cuts, rank, gx, od[0])
+    strad = straddling_rows(cuts, gx, od[0]) if filter == BOX else []
+    outV = np.full((i1 - i0, od[1], od[2], 3), np.nan, R)
+    outT = np.full((i1 - i0, od[1], od[2]), np.nan, np.float64)
+    partials = {i: np.zeros((5, od[1], od[2]), np.float64) for i in strad}
+    fluid = type == NODE_IN
+    for i in sorted(set(range(i0, i1)) | set(strad)):
+        x0, x1 = max(int(ax[0][0][i]), x0s), min(int(ax[0][1][i]), x1s)       # the box, clipped to the slab's planes
+        if x0 >= x1:
+            continue
+        for j, (y0, y1) in enumerate(zip(*ax[1])):
+            for k, (z0, z1) in enumerate(zip(*ax[2])):
+                box = (slice(x0, x1), slice(y0, y1), slice(z0, z1))
+                m = fluid[box] if filter == BOX else np.zeros((x1 - x0, y1 - y0, z1 - z0), bool)
+                n = int(m.sum())
+                sums = [float(f[box][m].astype(np.float64).sum()) for f in q]
+                if i in partials:
+                    partials[i][:, j, k] = sums + [float(n)]
+                elif n:
+                    outV[i - i0, j, k] = np.array([s / float(n) for s in sums[:3]], np.float64).astype(R)
+                    outT[i - i0, j, k] = sums[3] / float(n)
+                else:
+                    outV[i - i0, j, k] = [f[x0, y0, z0] for f in q[:3]]
+                    outT[i - i0, j, k] = np.float64(q[3][x0, y0, z0])
+    return (i0, i1), outV, outT, partials
+
+
+def finish_slabs(type, fields, cuts, per_rank, outdims=(0, 0, 0), vector=VELOCITY, spacing=None):
+    """The global record from every rank's slab_partials: the partials of a straddling row are added in rank order, then one division
+    and one rounding, or the point sample of the cell (lo_x, lo_y, lo_z) where no rank counted a NODE_IN cell -- written, as in the
+    library, by the row's owner, whose planes hold that cell."""
+    type = np.asarray(type)
+    q = cell_quantities(type, fields, vector, spacing)
+    R = q[0].dtype
+    ax = [boxes(g, o) for g, o in zip(type.shape, outdims)]
+    od = [len(lo) for lo, _ in ax]
+    outV, outT = np.full(od + [3], np.nan, R), np.full(od, np.nan, np.float64)
+    for (i0, i1), V, T, _ in per_rank:
+        outV[i0:i1], outT[i0:i1] = V, T
+    for i in per_rank[0][3]:
+        owner = [r for r, ((i0, i1), _, _, _) in enumerate(per_rank) if i0 <= i < i1]
+        x0 = int(ax[0][0][i])
+        assert len(owner) == 1 and cuts[owner[0]][0] <= x0 < cuts[owner[0]][1]
+        total = np.zeros_like(per_rank[0][3][i])
+        for p in per_rank:
+            total = total + p[3][i]
+        for j, y0 in enumerate(ax[1][0]):
+            for k, z0 in enumerate(ax[2][0]):
+                n = total[4, j, k]
+                if n:
+                    outV[i, j, k] = (total[:3, j, k] / n).astype(R)
+                    outT[i, j, k] = total[3, j, k] / n
+                else:
+                    outV[i, j, k] = [f[x0, y0, z0] for f in q[:3]]
+                    outT[i, j, k] = np.float64(q[3][x0, y0, z0])
+    return outV, outT
+
+
 def box_kinds(type, outdims):
     """Per sample: 0 every cell of the box NODE_IN, 1 mixed, 2 no NODE_IN and the sample cell a wall (NODE_BOUND / NODE_VALVE),
     3 no NODE_IN and the sample cell NODE_OUT.  int8 [odx, ody, odz]; test aid."""

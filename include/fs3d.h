@@ -111,7 +111,8 @@ enum {
                                  other entry.  0 (default): nothing changes anywhere -- the reference's point sample (FilterToArrays).
                                  1: the box mean -- every sample is the mean over the NODE_IN cells of its box of source cells, and the
                                  point sample where the box holds none (the GetLayer section below).  While it is 1 an x-slab or a member
-                                 of a group is refused by the three entries (FS3D_ERR_UNSUPPORTED).  Any other value: FS3D_ERR_INVALID */
+                                 of a group is refused by the three entries (FS3D_ERR_UNSUPPORTED) unless FS3D_OPT_OUTPUT_SLABS is 1.
+                                 Any other value: FS3D_ERR_INVALID */
     FS3D_OPT_OUTPUT_VECTOR = 13, /* what outV of the same three entries holds; outT is the temperature either way.  0 (default): nothing
                                  changes anywhere -- the velocity.  1: the vorticity, central differences on the NODE_IN cells whose six
                                  neighbours are inside the grid and not NODE_OUT, 99999 on NODE_OUT cells, 0 elsewhere (the GetLayer
@@ -139,6 +140,14 @@ enum {
     FS3D_OPT_TIME_STATS_EVERY = 18, /* the stride k of the accumulated steps, 1 (default) .. 2^20: of the candidate steps s = 1, 2, .. of a
                                  window those with (s - 1) % k == 0 are accumulated, on the others no kernel runs.  EVERY call with this
                                  option opens a new window.  Needs no memory.  A value below 1 or above 2^20: FS3D_ERR_INVALID */
+    FS3D_OPT_OUTPUT_SLABS = 19, /* 0 (default): nothing changes anywhere -- the slab refusal of FS3D_OPT_OUTPUT_FILTER / FS3D_OPT_OUTPUT_VECTOR
+                                 stands.  1: on an x-slab context that is a member of a group (fs3d_comm_init_local, or fs3d_comm_init with
+                                 more than one rank) fs3d_get_layer_rows and fs3d_get_layer_dev take a non-zero filter or vector option and
+                                 run as one COLLECTIVE call: the slab writes its rows of the record a single context of the GLOBAL grid
+                                 writes (the GetLayer section below).  No effect on a whole-grid context and none while both options are 0.
+                                 Still refused with FS3D_ERR_UNSUPPORTED before any launch and any word to a peer: a lone slab of a larger
+                                 grid in no group, and fs3d_get_layer on any slab (it samples the slab's own planes and stays
+                                 non-collective).  Any other value: FS3D_ERR_INVALID */
     FS3D_OPT_ERR_ORDER = 7   /* summation order of EvalDivError (fs3d_eval_div_error, fs3d_time_step with compute_error).  0 (default): the
                                  per-cell terms are summed in parallel (per workgroup, then over the workgroups; deterministic, equal to the
                                  CPU path to ~1e-12 relative).  1: they are summed one after the other in cell order, as the loop of
@@ -577,6 +586,36 @@ fs3d_status fs3d_get_layer(fs3d_ctx *ctx, void *outV, double *outT,
  * entries with FS3D_ERR_UNSUPPORTED before any launch, destinations and `next` untouched: a box can straddle a cut and the curl
  * needs the neighbour's planes.  fs3d_get_layer_rows / _dev on a whole-grid context work and report rows = [0, outdimx).
  *
+ * On x-slabs (FS3D_OPT_OUTPUT_SLABS set to 1 on every member of a group): fs3d_get_layer_rows and fs3d_get_layer_dev, with either
+ * option non-zero, as one COLLECTIVE call.  The rows a slab writes are the rows [ceil(x_offset*odx/gx), ceil((x_offset+dimx)*odx/gx))
+ * of the record a single context of the GLOBAL grid writes -- the rule above applied to the global types and fields; over the ranks
+ * they partition [0, odx) as ever.  The vorticity of an own cell tests the GLOBAL x against the grid's faces and takes the x
+ * neighbours across a cut from the neighbour's stamped boundary plane and node types: its bits are the single context's, so with
+ * filter 0 the rows equal the global record bit for bit.  Box mean: every slab sums (double)q and counts over the NODE_IN cells of
+ * the box that lie in its own planes; for a row whose box holds planes of more than one slab (at most nranks - 1 rows, whatever the
+ * width of a box) the slabs' sums and counts are added over the group (the counts exactly, as doubles below 2^53), then one division
+ * and one rounding as above, by the slab that holds the first plane of the box; a box without a NODE_IN cell on any slab gives the
+ * point sample of (lo_x, lo_y, lo_z), which that slab holds.  The rule leaves the order of the double sum free: the bound of a
+ * single context's record holds, and wherever the sums are exact the rows equal it bit for bit.  FS3D_OPT_OUTPUT_SOURCE and
+ * FS3D_OPT_OUTPUT_MOMENT combine as on one GPU; the statistic layer Q then has a ghost plane on either side.
+ * What runs, on every rank alike whatever it owns (a rank without a row takes part to the end): all refusals; the statistic layer
+ * and the stamp on the own cells; with the vector option ONE grouped exchange per neighbour -- the boundary plane of the four fields
+ * of the sampled layer and one plane of node types, a byte per cell, derived from the current geometry per call; the slab kernel,
+ * which finishes the rows inside the slab and leaves five doubles per sample of a straddling row; ONE all-reduce of those partial
+ * sums, at most (nranks - 1) * ody * odz * 40 bytes, skipped when no row straddles a cut (every rank finds the same list from the
+ * cuts of the group, which are gathered once per context); the finishing kernel on the row's owner; staging, copies, rows and
+ * fs3d_get_layer_info as ever.  No source plane beyond that one ghost plane travels.
+ * The contract, as for the collective fresh-cell fill: every rank makes the call between the same two steps, with the same output
+ * dims, the same filter, vector, source and moment options, and FS3D_OPT_OUTPUT_SLABS at 1.  A rank that fails inside the call
+ * aborts the group's transport (fs3d_comm_abort): its peers return FS3D_ERR_COMM instead of waiting.  fs3d_get_layer_dev may
+ * synchronise inside the call in this mode (the in-process transport does).  `next` and `cur` are left as a default call leaves
+ * them, but with the vector option the ghost planes of the sampled layer are overwritten (every time step exchanges them again).
+ * The type planes, the partial sums, the cuts and a Q with ghost planes are allocated by the first call that needs them, kept and
+ * only grown, and counted in fs3d_get_layer_info entry 2: nothing is allocated in steady state.
+ * Still refused with FS3D_ERR_UNSUPPORTED, before any launch and any word to a peer, destinations, rows and layers untouched: a lone
+ * slab of a larger grid in no group, and fs3d_get_layer on any slab.  The FS3D_ERR_INVALID refusals of the time statistics come
+ * before any exchange too.  Between devices and over RCCL the path is compiled and has not been run.
+ *
  * Time statistics (FS3D_OPT_TIME_STATS, FS3D_OPT_TIME_STATS_CROSS, FS3D_OPT_TIME_STATS_EVERY, FS3D_OPT_OUTPUT_SOURCE,
  * FS3D_OPT_OUTPUT_MOMENT; no reference counterpart; the rule and its numpy twin: cmc_fluid_solver_amd/time_stats.py).  While
  * FS3D_OPT_TIME_STATS is 1 or 2, every fs3d_time_step that returns FS3D_OK and every fs3d_time_step_async is a CANDIDATE step of the
@@ -623,13 +662,17 @@ fs3d_status fs3d_get_layer(fs3d_ctx *ctx, void *outV, double *outT,
  *    FS3D_OPT_TIME_STATS mode does not hold (any source at 0, source 2 at 1); source 2 with moment 1 or 2 while the open window holds
  *    no cross sums (FS3D_OPT_TIME_STATS_CROSS is 0, or the mode is below 2); moment 1 or 2 with source 2 and FS3D_OPT_OUTPUT_VECTOR 1
  *    (the curl of a stress layer means nothing); and a window without an accumulated step (N = 0).  The slab refusal of the filter
- *    and vector options stands; without them an x-slab or group member accumulates and reads out its own planes -- every layer is
- *    per cell --, and the rows the slabs write are those of the global record a single context gives.
+ *    and vector options stands while FS3D_OPT_OUTPUT_SLABS is 0; without them an x-slab or group member accumulates and reads out
+ *    its own planes -- every layer is per cell --, and the rows the slabs write are those of the global record a single context
+ *    gives.  With FS3D_OPT_OUTPUT_SLABS at 1 on a group every source combines with the filter and the curl as on one GPU, as the
+ *    collective call described above; Q then carries a ghost plane on either side (two more planes per field), and the refusals of
+ *    this list come before any exchange.
  *  - not provided: third moments; covariances with the vorticity; a history of the cells that are NODE_OUT now (they are stamped
  *    as in every record); the 2D solver. */
 fs3d_status fs3d_get_layer_rows(fs3d_ctx *ctx, void *outV, double *outT, int outdimx, int outdimy, int outdimz, int rows[2]);
 /* fs3d_get_layer_rows (Solver3D.cpp:21-25, TimeLayer3D.h:819-924) with the two arrays on the context's DEVICE: the kernel
  * writes them directly, nothing is copied.  Returns after the enqueue on the context's stream; read after fs3d_synchronize.
+ * (As the collective call of FS3D_OPT_OUTPUT_SLABS it may synchronise inside the call; read after fs3d_synchronize all the same.)
  * The zero-copy partner of fs3d_field_dev_ptr and fs3d_update_nodes_dev. */
 fs3d_status fs3d_get_layer_dev(fs3d_ctx *ctx, void *outV_dev, double *outT_dev, int outdimx, int outdimy, int outdimz, int rows[2]);
 /* What the result output (Solver3D.cpp:21-25, TimeLayer3D.h:819-924) did: info[0] samples the last fs3d_get_layer* call wrote,
