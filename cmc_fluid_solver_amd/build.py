@@ -10,7 +10,8 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libfs3d_hip.so")
-SOURCES = ["fs3d_hip.hip", "fs3d_comm.hip", "kernels_line.hip", "kernels_pipe.hip", "kernels_part.hip", "kernels_geom.hip", "kernels_stats.hip"]
+SOURCES = ["fs3d_hip.hip", "fs3d_comm.hip", "kernels_line.hip", "kernels_pipe.hip", "kernels_part.hip", "kernels_geom.hip", "kernels_stats.hip",
+           "kernels_output.hip"]
 PUBLIC_HEADER = os.path.join(HERE, "..", "include", "fs3d.h")
 HEADERS = ["fs3d_common.h", "fs3d_buf.h", "fs3d_tables.h", "fs3d_voxel.h", "fs3d_device.h", "fs3d_rows.h", "fs3d_comm.h", PUBLIC_HEADER]
 

@@ -186,9 +186,9 @@ struct fs3d_ctx {
     int opt_fresh_cells = 0;               // FS3D_OPT_FRESH_CELLS: 1 = every single-context update keeps the node types of the geometry it replaces
     int opt_fresh_slabs = 0;               // FS3D_OPT_FRESH_CELLS_SLABS: 1 = a slab of a group keeps that snapshot too and fills collectively
     int opt_out_filter = 0;                // FS3D_OPT_OUTPUT_FILTER: 1 = the GetLayer entries average the NODE_IN cells of every sample's box (k_get_layer_box)
-    int opt_out_vector = 0;                // FS3D_OPT_OUTPUT_VECTOR: 1 = their outV holds the vorticity (k_get_layer_box<R, true>)
+    int opt_out_vector = 0;                // FS3D_OPT_OUTPUT_VECTOR: 1 = their outV holds the vorticity (k_get_layer_box with VORT)
     // FS3D_OPT_OUTPUT_SLABS: 1 = on a member of a group fs3d_get_layer_rows / _dev take the two options above as one collective call
-    // (get_layer_slabs_impl).  Its buffers are allocated by the first call that needs them, kept and only grown, counted in gl_info[2]:
+    // (get_layer_impl with `collective`, kernels_output.hip).  Its buffers are allocated by the first call that needs them, kept and only grown, counted in gl_info[2]:
     // os_type -- four planes of node types, a byte per cell: the own first and last plane (derived from `code` per call), the lower
     // and the upper neighbour's; os_part -- the five partial sums per sample of the straddling rows, [row][4 sums, count][ody*odz];
     // os_cuts -- (x_offset, dimx) of every rank, gathered once through os_cut_dev (the cuts of a group never move)
@@ -261,7 +261,7 @@ struct fs3d_ctx {
     std::string err;
 };
 
-// ---- host helpers shared by fs3d_hip.hip, kernels_geom.hip and fs3d_comm.hip ------------------------------------------------------
+// ---- host helpers shared by fs3d_hip.hip, kernels_geom.hip, kernels_output.hip and fs3d_comm.hip ---------------------------------
 // The error text of a call goes to its context; without one (fs3d_create, a NULL handle) to the thread's, for fs3d_last_error(NULL).
 inline thread_local std::string g_create_err;
 static inline fs3d_status fail(fs3d_ctx *c, fs3d_status st, const std::string &msg) { if (c) c->err = msg; else g_create_err = msg; return st; }
@@ -287,6 +287,17 @@ static inline bool stream_reserve(fs3d_ctx *c, std::initializer_list<BufWant<Dev
     for (const BufWant<DevMem> &w : set) if (w.buf->raw() && !w.buf->holds(w.bytes)) { hipStreamSynchronize(c->stream); break; }
     return reserve_all(set, nullptr, fresh);
 }
+
+// the first owned cell of field v of layer buffer buf
+template <typename R> static inline R *fld(fs3d_ctx *c, int buf, int v) { return (R *)c->lay[buf] + (long long)v * c->fstride + c->plane; }
+// A rank that fails anywhere in a collective sequence -- allocations included -- must not leave its neighbours blocked in their
+// receives: it aborts the group (fs3d_comm_abort), the peers' pending and later exchanges return FS3D_ERR_COMM
+struct AbortOnError { fs3d_ctx *c; fs3d_status *st; ~AbortOnError() { if (*st != FS3D_OK) fs3d_comm_abort(c); } };
+
+// fs3d_hip.hip: what every entry that returns synchronised does after the wait -- the event pairs of the timed launches into
+// t_ms / t_n, then the kernels' error word
+void rec_collect(fs3d_ctx *c);
+fs3d_status check_device_errors(fs3d_ctx *c);
 
 // kernels_geom.hip
 void fs3d_geom_destroy(fs3d_ctx *c);

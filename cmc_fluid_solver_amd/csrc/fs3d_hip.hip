@@ -1,6 +1,6 @@
 // libfs3d_hip.so -- C ABI (include/fs3d.h) of the MI355X-native FluidSolver3D hot path:
 // context, geometry tables, auxiliary kernels and the time-step orchestration.
-// The line-sweep kernels live in kernels_line.hip / kernels_pipe.hip.
+// The line-sweep kernels live in kernels_line.hip / kernels_pipe.hip, the result records in kernels_output.hip.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -69,289 +69,6 @@ __global__ void __launch_bounds__(256) k_impose_list2(const int *__restrict__ id
         int i = idx[t];
         const R a = v0[t], b = v1[t], c = v2[t], d = v3[t];
         d0[i] = a; d1[i] = b; d2[i] = c; d3[i] = d; e0[i] = a; e1[i] = b; e2[i] = c; e3[i] = d;
-    }
-}
-
-// TimeLayer3D::Clear(grid, NODE_OUT, MISSING_VALUE x4) (TimeLayer3D.h:974-999; `clear`, TimeLayer3D.cu:98-116)
-template <typename R>
-__global__ void __launch_bounds__(256) k_clear_type(const uint16_t *__restrict__ code, long long n, int type, R val,
-                                                     R *d0, R *d1, R *d2, R *d3)
-{
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
-        if (((code[i] >> CODE_TYPE_SHIFT) & 3) == type) { d0[i] = val; d1[i] = val; d2[i] = val; d3[i] = val; }
-}
-
-// TimeLayer3D::FilterToArrays (TimeLayer3D.h:819-924): the nearest-neighbour samples of one layer, out[i,j,k] = layer[i*gx/odx,
-// j*dimy/ody, k*dimz/odz], into outV (interleaved x, y, z) and outT (double).  A pure gather: order-free, bit-exact.  One thread
-// per sample, k fastest: blockIdx.x = output row i - i0, the threads of a row walk its ody*odz samples (a wave stores 64 x 3
-// consecutive R and 64 consecutive doubles).  The slab holds the planes [x_offset, x_offset + dimx) of gx and writes the rows
-// [i0, i1) whose source plane it owns; outV / outT address the first sample of row i0.  Runs behind k_clear_type on the same
-// stream and reads the stamped values.
-template <typename R>
-__global__ void __launch_bounds__(256) k_get_layer(const R *__restrict__ U, const R *__restrict__ V, const R *__restrict__ W,
-                                                    const R *__restrict__ T, int x_offset, int dimx, long long plane, int dimy, int dimz,
-                                                    int gx, int odx, int ody, int odz, int i0, int i1,
-                                                    R *__restrict__ outV, double *__restrict__ outT)
-{
-    const int i = i0 + (int)blockIdx.x;
-    const int x = (int)((long long)i * gx / odx) - x_offset;
-    if (i >= i1 || x < 0 || x >= dimx) return;
-    const unsigned po = (unsigned)ody * (unsigned)odz;
-    for (unsigned p = blockIdx.y * 256u + threadIdx.x; p < po; p += gridDim.y * 256u) {
-        const unsigned j = p / (unsigned)odz, k = p - j * (unsigned)odz;
-        const int y = (int)((long long)j * dimy / ody), z = (int)((long long)k * dimz / odz);
-        const long long id = (long long)x * plane + (long long)y * dimz + z;
-        const long long ind = (long long)blockIdx.x * po + p;
-        outV[3 * ind] = U[id]; outV[3 * ind + 1] = V[id]; outV[3 * ind + 2] = W[id];
-        outT[ind] = (double)T[id];
-    }
-}
-
-// FS3D_OPT_OUTPUT_FILTER / FS3D_OPT_OUTPUT_VECTOR (no reference counterpart; the rule: layer_output.py): the sample (i, j, k) is the
-// mean over the NODE_IN cells of its box [x0, x1) x [y0, y1) x [z0, z1) of source cells -- lo = i*g/o, hi = max(lo + 1, (i+1)*g/o) per
-// axis -- and the cell (x0, y0, z0) itself where the box holds none.  `point` (filter 0 of the vorticity): every sample is that cell,
-// one lane per output k as in k_get_layer, no box is walked.
-// VORT: the three velocity quantities are the curl, central differences in R, on the NODE_IN cells whose six neighbours are in the
-// grid and not NODE_OUT; 0 on the other NODE_IN cells and the walls, 99999 on NODE_OUT cells.
-// One block = one output row i and the output rows j = blockIdx.y, + gridDim.y, ...; per j the output k go in groups of 256, one
-// lane per output k.  The source cells [zb, ze) under a group are walked in chunks of 256, lanes along the source k (unit stride):
-// a thread runs down the planes and rows of the box for its k with four double sums and a count in registers, the per-k partials
-// go through LDS and the lane of every output k adds the ones of its box.  For o <= g the boxes partition the axis, so every source
-// cell is read once (2 bytes of code and four reals); no atomics, plain cached loads (the next step reads `next` again).  The curl
-// reads its six neighbours through the cache (the k +- 1 ones are the neighbouring lanes' lines).  Double sums of at most 2^31
-// terms; the order is the kernel's own, the rule leaves it free.  Whole-grid contexts only (get_layer_entry refuses slabs).
-template <typename R, bool VORT>
-__global__ void __launch_bounds__(256) k_get_layer_box(const uint16_t *__restrict__ code, const R *__restrict__ U, const R *__restrict__ V,
-                                                        const R *__restrict__ W, const R *__restrict__ T, int dimx, int dimy, int dimz,
-                                                        int odx, int ody, int odz, int point, R two_dx, R two_dy, R two_dz,
-                                                        R *__restrict__ outV, double *__restrict__ outT)
-{
-    __shared__ double sq[4][256];
-    __shared__ int sn[256];
-    const long long plane = (long long)dimy * dimz;
-    const int t = (int)threadIdx.x;
-    auto box_lo = [](int i, int g, int o) { return (int)((long long)i * g / o); };
-    auto box_hi = [&](int i, int lo, int g, int o) { const int h = (int)((long long)(i + 1) * g / o); return h < lo + 1 ? lo + 1 : h; };
-    auto type_of = [&](long long l) { return (code[l] >> CODE_TYPE_SHIFT) & 3; };
-    // (a, b, c) of cell l = (x, y, z), whose type is ty
-    auto vec_of = [&](long long l, int x, int y, int z, int ty, R &a, R &b, R &c) __attribute__((always_inline)) {
-        if (!VORT) { a = U[l]; b = V[l]; c = W[l]; return; }
-        a = b = c = ty == FS3D_NODE_OUT ? R(99999.0f) : R(0);
-        if (ty != FS3D_NODE_IN || x < 1 || x > dimx - 2 || y < 1 || y > dimy - 2 || z < 1 || z > dimz - 2) return;
-        if (type_of(l - plane) == FS3D_NODE_OUT || type_of(l + plane) == FS3D_NODE_OUT || type_of(l - dimz) == FS3D_NODE_OUT ||
-            type_of(l + dimz) == FS3D_NODE_OUT || type_of(l - 1) == FS3D_NODE_OUT || type_of(l + 1) == FS3D_NODE_OUT) return;
-        a = (W[l + dimz] - W[l - dimz]) / two_dy - (V[l + 1] - V[l - 1]) / two_dz;
-        b = (U[l + 1] - U[l - 1]) / two_dz - (W[l + plane] - W[l - plane]) / two_dx;
-        c = (V[l + plane] - V[l - plane]) / two_dx - (U[l + dimz] - U[l - dimz]) / two_dy;
-    };
-    const int i = (int)blockIdx.x;
-    const int x0 = box_lo(i, dimx, odx), x1 = box_hi(i, x0, dimx, odx);
-    for (int j = (int)blockIdx.y; j < ody; j += (int)gridDim.y) {
-        const int y0 = box_lo(j, dimy, ody), y1 = box_hi(j, y0, dimy, ody);
-        for (long long kg = 0; kg < odz; kg += 256) {          // (64-bit: odz may lie within 256 of 2^31)
-            const int klast = (int)(kg + 256 < odz ? kg + 256 : odz) - 1;
-            const bool kout = kg + t < odz;
-            const int ko = kout ? (int)kg + t : klast;
-            const int z0 = box_lo(ko, dimz, odz), z1 = box_hi(ko, z0, dimz, odz);
-            // the group's source cells, block-uniform; `point`: none are walked, every lane takes the one cell of its own output k below
-            const int zb = box_lo((int)kg, dimz, odz), zl = box_lo(klast, dimz, odz), ze = point ? zb : box_hi(klast, zl, dimz, odz);
-            double acc[4] = {0.0, 0.0, 0.0, 0.0};
-            int n = 0;
-            for (int cb = zb; cb < ze; cb += 256) {
-                const int z = cb + t;
-                double s[4] = {0.0, 0.0, 0.0, 0.0};
-                int m = 0;
-                if (z < ze)
-                    for (int x = x0; x < x1; x++)
-                        for (int y = y0; y < y1; y++) {
-                            const long long l = (long long)x * plane + (long long)y * dimz + z;
-                            if (type_of(l) != FS3D_NODE_IN) continue;
-                            R a, b, c;
-                            vec_of(l, x, y, z, FS3D_NODE_IN, a, b, c);
-                            s[0] += (double)a; s[1] += (double)b; s[2] += (double)c; s[3] += (double)T[l];
-                            m++;
-                        }
-#pragma unroll
-                for (int q = 0; q < 4; q++) sq[q][t] = s[q];
-                sn[t] = m;
-                __syncthreads();
-                if (kout) {
-                    const int e = z1 < cb + 256 ? z1 : cb + 256;
-                    for (int zz = z0 > cb ? z0 : cb; zz < e; zz++) {
-#pragma unroll
-                        for (int q = 0; q < 4; q++) acc[q] += sq[q][zz - cb];
-                        n += sn[zz - cb];
-                    }
-                }
-                __syncthreads();
-            }
-            if (!kout) continue;
-            const long long ind = ((long long)i * ody + j) * odz + ko;
-            if (n) {
-                const double d = (double)n;
-                outV[3 * ind] = (R)(acc[0] / d); outV[3 * ind + 1] = (R)(acc[1] / d); outV[3 * ind + 2] = (R)(acc[2] / d);
-                outT[ind] = acc[3] / d;
-            } else {                                       // no fluid in the box, or `point`: the point sample (on a wall, or the stamp)
-                const long long l = (long long)x0 * plane + (long long)y0 * dimz + z0;
-                R a, b, c;
-                vec_of(l, x0, y0, z0, type_of(l), a, b, c);
-                outV[3 * ind] = a; outV[3 * ind + 1] = b; outV[3 * ind + 2] = c;
-                outT[ind] = (double)T[l];
-            }
-        }
-    }
-}
-
-// FS3D_OPT_OUTPUT_SLABS: the same rule on an x-slab of a group, every slab reducing its own planes (get_layer_slabs_impl).
-// What a slab knows of the grid: its planes [x_offset, x_offset + dimx) of gx, the fields with the neighbours' stamped boundary
-// planes in their ghost planes (U .. T address the first owned cell), and the node types of those two planes (tlo below the first
-// owned plane, thi above the last; read only where the neighbour exists).  q of an own cell is then the single context's, bit for
-// bit: the curl tests the GLOBAL x against the grid's faces and takes the x neighbours across a cut from the ghost and type planes.
-template <typename R, bool VORT>
-struct SlabCells {
-    const uint16_t *code;
-    const R *U, *V, *W, *T;
-    const uint8_t *tlo, *thi;
-    int x_offset, dimx, gx, dimy, dimz;
-    R two_dx, two_dy, two_dz;
-    __device__ int type_of(long long l) const { return (code[l] >> CODE_TYPE_SHIFT) & 3; }
-    // (a, b, c) of the own cell l = (x, y, z), x counted from the slab's first plane, whose type is ty
-    __device__ __attribute__((always_inline)) void vec_of(long long l, int x, int y, int z, int ty, R &a, R &b, R &c) const
-    {
-        if (!VORT) { a = U[l]; b = V[l]; c = W[l]; return; }
-        const long long plane = (long long)dimy * dimz;
-        const int xg = x + x_offset;
-        a = b = c = ty == FS3D_NODE_OUT ? R(99999.0f) : R(0);
-        if (ty != FS3D_NODE_IN || xg < 1 || xg > gx - 2 || y < 1 || y > dimy - 2 || z < 1 || z > dimz - 2) return;
-        const long long r = (long long)y * dimz + z;
-        const int tm = x > 0 ? type_of(l - plane) : (int)tlo[r], tp = x < dimx - 1 ? type_of(l + plane) : (int)thi[r];
-        if (tm == FS3D_NODE_OUT || tp == FS3D_NODE_OUT || type_of(l - dimz) == FS3D_NODE_OUT ||
-            type_of(l + dimz) == FS3D_NODE_OUT || type_of(l - 1) == FS3D_NODE_OUT || type_of(l + 1) == FS3D_NODE_OUT) return;
-        a = (W[l + dimz] - W[l - dimz]) / two_dy - (V[l + 1] - V[l - 1]) / two_dz;
-        b = (U[l + 1] - U[l - 1]) / two_dz - (W[l + plane] - W[l - plane]) / two_dx;
-        c = (V[l + plane] - V[l - plane]) / two_dx - (U[l + dimz] - U[l - dimz]) / two_dy;
-    }
-};
-
-// the node types of the slab's first and last plane, a byte per cell: what the neighbours' curl reads across the cuts
-__global__ void __launch_bounds__(256) k_type_planes(const uint16_t *__restrict__ code, long long plane, long long last,
-                                                      uint8_t *__restrict__ first_out, uint8_t *__restrict__ last_out)
-{
-    for (long long r = (long long)blockIdx.x * 256 + threadIdx.x; r < plane; r += (long long)gridDim.x * 256) {
-        first_out[r] = (uint8_t)((code[r] >> CODE_TYPE_SHIFT) & 3);
-        last_out[r] = (uint8_t)((code[last + r] >> CODE_TYPE_SHIFT) & 3);
-    }
-}
-
-// The slab form of k_get_layer_box: the same walk -- lanes along the source k, per-k partials through LDS, no atomics, plain cached
-// loads -- over the output rows ia + blockIdx.x whose box holds a plane of this slab, the x range of every box clipped to the
-// slab's planes.  A row whose box lies inside the slab is finished here as k_get_layer_box finishes it; outV / outT address the
-// first sample of the first OWNED row i0.  A straddling row (its box holds planes of more than one slab; at most the first and the
-// last row of a slab, their places in the group's list s_first / s_last, -1: not straddling) leaves its four double sums and its
-// count, planar, in part[s][q][ody * odz]: the sums of the slabs are added over the group and k_get_layer_finish divides.
-// `point`: as in k_get_layer_box; no row straddles then and the rows are the owned ones.
-template <typename R, bool VORT>
-__global__ void __launch_bounds__(256) k_get_layer_box_slab(const SlabCells<R, VORT> s, int odx, int ody, int odz, int point, int ia, int i0,
-                                                             int s_first, int s_last, R *__restrict__ outV, double *__restrict__ outT,
-                                                             double *__restrict__ part)
-{
-    __shared__ double sq[4][256];
-    __shared__ int sn[256];
-    const int dimy = s.dimy, dimz = s.dimz;
-    const long long plane = (long long)dimy * dimz;
-    const int t = (int)threadIdx.x;
-    auto box_lo = [](int i, int g, int o) { return (int)((long long)i * g / o); };
-    auto box_hi = [&](int i, int lo, int g, int o) { const int h = (int)((long long)(i + 1) * g / o); return h < lo + 1 ? lo + 1 : h; };
-    const int i = ia + (int)blockIdx.x;
-    const int sidx = blockIdx.x == 0 ? s_first : blockIdx.x == gridDim.x - 1 ? s_last : -1;
-    const int g0 = box_lo(i, s.gx, odx), g1 = box_hi(i, g0, s.gx, odx);
-    const int x0 = g0 > s.x_offset ? g0 - s.x_offset : 0, x1 = g1 - s.x_offset < s.dimx ? g1 - s.x_offset : s.dimx;
-    const long long po = (long long)ody * odz;
-    for (int j = (int)blockIdx.y; j < ody; j += (int)gridDim.y) {
-        const int y0 = box_lo(j, dimy, ody), y1 = box_hi(j, y0, dimy, ody);
-        for (long long kg = 0; kg < odz; kg += 256) {
-            const int klast = (int)(kg + 256 < odz ? kg + 256 : odz) - 1;
-            const bool kout = kg + t < odz;
-            const int ko = kout ? (int)kg + t : klast;
-            const int z0 = box_lo(ko, dimz, odz), z1 = box_hi(ko, z0, dimz, odz);
-            const int zb = box_lo((int)kg, dimz, odz), zl = box_lo(klast, dimz, odz), ze = point ? zb : box_hi(klast, zl, dimz, odz);
-            double acc[4] = {0.0, 0.0, 0.0, 0.0};
-            int n = 0;
-            for (int cb = zb; cb < ze; cb += 256) {
-                const int z = cb + t;
-                double q[4] = {0.0, 0.0, 0.0, 0.0};
-                int m = 0;
-                if (z < ze)
-                    for (int x = x0; x < x1; x++)
-                        for (int y = y0; y < y1; y++) {
-                            const long long l = (long long)x * plane + (long long)y * dimz + z;
-                            if (s.type_of(l) != FS3D_NODE_IN) continue;
-                            R a, b, c;
-                            s.vec_of(l, x, y, z, FS3D_NODE_IN, a, b, c);
-                            q[0] += (double)a; q[1] += (double)b; q[2] += (double)c; q[3] += (double)s.T[l];
-                            m++;
-                        }
-#pragma unroll
-                for (int v = 0; v < 4; v++) sq[v][t] = q[v];
-                sn[t] = m;
-                __syncthreads();
-                if (kout) {
-                    const int e = z1 < cb + 256 ? z1 : cb + 256;
-                    for (int zz = z0 > cb ? z0 : cb; zz < e; zz++) {
-#pragma unroll
-                        for (int v = 0; v < 4; v++) acc[v] += sq[v][zz - cb];
-                        n += sn[zz - cb];
-                    }
-                }
-                __syncthreads();
-            }
-            if (!kout) continue;
-            if (sidx >= 0) {                                   // the group adds the slabs' sums; the row's owner finishes
-                double *const p = part + (long long)sidx * 5 * po + (long long)j * odz + ko;
-#pragma unroll
-                for (int v = 0; v < 4; v++) p[v * po] = acc[v];
-                p[4 * po] = (double)n;
-                continue;
-            }
-            const long long ind = ((long long)(i - i0) * ody + j) * odz + ko;
-            if (n) {
-                const double d = (double)n;
-                outV[3 * ind] = (R)(acc[0] / d); outV[3 * ind + 1] = (R)(acc[1] / d); outV[3 * ind + 2] = (R)(acc[2] / d);
-                outT[ind] = acc[3] / d;
-            } else {                                           // the box is inside the slab: so is its first cell
-                const long long l = (long long)x0 * plane + (long long)y0 * dimz + z0;
-                R a, b, c;
-                s.vec_of(l, x0, y0, z0, s.type_of(l), a, b, c);
-                outV[3 * ind] = a; outV[3 * ind + 1] = b; outV[3 * ind + 2] = c;
-                outT[ind] = (double)s.T[l];
-            }
-        }
-    }
-}
-
-// The owner of the straddling row i (the slab that holds the first plane of its box) finishes it from the group's sums: one
-// division and one rounding per quantity, or the point sample of the cell (lo_x, lo_y, lo_z) where no slab counted a NODE_IN cell.
-// One thread per sample, k fastest; `part` addresses the row's five planes, outV / outT the row's first sample.
-template <typename R, bool VORT>
-__global__ void __launch_bounds__(256) k_get_layer_finish(const SlabCells<R, VORT> s, int i, int odx, int ody, int odz,
-                                                           const double *__restrict__ part, R *__restrict__ outV, double *__restrict__ outT)
-{
-    const long long po = (long long)ody * odz;
-    const long long plane = (long long)s.dimy * s.dimz;
-    for (long long p = (long long)blockIdx.x * 256 + threadIdx.x; p < po; p += (long long)gridDim.x * 256) {
-        const double d = part[4 * po + p];
-        if (d > 0.0) {
-            outV[3 * p] = (R)(part[p] / d); outV[3 * p + 1] = (R)(part[po + p] / d); outV[3 * p + 2] = (R)(part[2 * po + p] / d);
-            outT[p] = part[3 * po + p] / d;
-        } else {
-            const int j = (int)(p / odz), k = (int)(p - (long long)j * odz);
-            const int x = (int)((long long)i * s.gx / odx) - s.x_offset, y = (int)((long long)j * s.dimy / ody), z = (int)((long long)k * s.dimz / odz);
-            const long long l = (long long)x * plane + (long long)y * s.dimz + z;
-            R a, b, c;
-            s.vec_of(l, x, y, z, s.type_of(l), a, b, c);
-            outV[3 * p] = a; outV[3 * p + 1] = b; outV[3 * p + 2] = c;
-            outT[p] = (double)s.T[l];
-        }
     }
 }
 
@@ -470,7 +187,6 @@ __global__ void __launch_bounds__(256) k_div_final(const double *partial, int nb
 // context helpers
 // ---------------------------------------------------------------------------------
 
-template <typename R> static R *fld(fs3d_ctx *c, int buf, int v) { return (R *)c->lay[buf] + (long long)v * c->fstride + c->plane; }
 // byte pointer to the first owned cell of field v of layer buffer buf
 static char *fptr(fs3d_ctx *c, int buf, int v) { return (char *)c->lay[buf] + ((size_t)v * c->fstride + c->plane) * c->esize; }
 
@@ -498,7 +214,7 @@ struct RecScope {
     void cancel() { if (end) { c->ev_used -= 2; c->ev_class.pop_back(); end = 0; } }
 };
 // accumulates into t_ms/t_n (reset with fs3d_enable_timing)
-static void rec_collect(fs3d_ctx *c)
+void rec_collect(fs3d_ctx *c)
 {
     for (size_t i = 0; i < c->ev_class.size(); i++) {
         float ms = 0;
@@ -512,7 +228,7 @@ static void rec_collect(fs3d_ctx *c)
 // Device-side failures that cannot raise a HIP error (a relay hand-over of the pipe kernel that never arrived): the
 // kernels set a bit in the context's pinned error word; every entry point that synchronises the stream checks it, so
 // that wrong numbers are never returned with FS3D_OK (GPUplan.cpp:173-193: the reference throws on every device error).
-static fs3d_status check_device_errors(fs3d_ctx *c)
+fs3d_status check_device_errors(fs3d_ctx *c)
 {
     if (!c->errw_host || *c->errw_host == 0) return FS3D_OK;
     *c->errw_host = 0;
@@ -527,10 +243,6 @@ static fs3d_status launch_failed(fs3d_ctx *c, const char *what)
 {
     return fail(c, FS3D_ERR_HIP, "GPU " + std::to_string(c->device) + ": " + what + ": " + c->err);
 }
-
-// A rank that fails anywhere in a cross-slab sweep -- allocations included -- must not leave its neighbours blocked in their
-// receives: it aborts the group (fs3d_comm_abort), the peers' pending and later exchanges return FS3D_ERR_COMM
-struct AbortOnError { fs3d_ctx *c; fs3d_status *st; ~AbortOnError() { if (*st != FS3D_OK) fs3d_comm_abort(c); } };
 
 // ---------------------------------------------------------------------------------
 // lifetime
@@ -1481,255 +1193,4 @@ extern "C" fs3d_status fs3d_synchronize(fs3d_ctx *c)
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (c->ev_used) rec_collect(c);
     return check_device_errors(c);
-}
-
-// Solver3D::GetLayer, Solver3D.cpp:21-25: next->Clear(NODE_OUT, MISSING_VALUE), then FilterToArrays by k_get_layer.
-// `local`: the slab's own planes are the whole source (fs3d_get_layer: x = i*dimx/odx, rows [0, odx)); else the slab owns the rows
-// of the GLOBAL output whose source plane it holds.  `dev`: outV / outT are on the context's device, the kernel writes them and
-// the call returns after the enqueue; else the owned samples go through the staging buffer and the call returns synchronised.
-// FS3D_OPT_OUTPUT_FILTER / FS3D_OPT_OUTPUT_VECTOR: k_get_layer_box in place of k_get_layer, everything around it as it is.
-// FS3D_OPT_OUTPUT_SOURCE 1..3 (source 2: the layer FS3D_OPT_OUTPUT_MOMENT chooses): the statistic layer of kernels_stats.hip, in a buffer of its own, takes the place of `next` -- stamp,
-// gather or box kernel, staging and copies run on it unchanged; `next` and `cur` are not written.
-template <typename R>
-static fs3d_status get_layer_impl(fs3d_ctx *c, R *outV, double *outT, int odx, int ody, int odz, bool local, bool dev, int rows[2])
-{
-    const int b = c->slot[FS3D_LAYER_NEXT];
-    const int gx = local ? c->dimx : c->dimx_global, x_offset = local ? 0 : c->x_offset;
-    if (odx == 0) odx = gx;
-    if (ody == 0) ody = c->dimy;
-    if (odz == 0) odz = c->dimz;
-    const long long po = (long long)ody * odz;
-    if (po >= (1LL << 31)) return fail(c, FS3D_ERR_UNSUPPORTED, "fs3d_get_layer: an output plane of 2^31 samples or more");
-    // the rows i with x_offset <= i*gx/odx < x_offset + dimx (slab.py out_rows)
-    const int i0 = (int)(((long long)x_offset * odx + gx - 1) / gx), i1 = (int)(((long long)(x_offset + c->dimx) * odx + gx - 1) / gx);
-    if (rows) { rows[0] = i0; rows[1] = i1; }
-    const long long n = (long long)(i1 - i0) * po;
-    const size_t vbytes = ((size_t)3 * n * sizeof(R) + 255) / 256 * 256;
-    c->gl_info[0] = n; c->gl_info[1] = 0;
-    R *dV = outV + 3 * (size_t)i0 * po;
-    double *dT = outT + (size_t)i0 * po;
-    if (!dev && n) {
-        bool grown = false;
-        BUFCHK(c, c->gl_stage.reserve(vbytes + (size_t)n * 8, nullptr, &grown));
-        c->gl_info[2] += grown;
-    }
-    R *F[4] = {fld<R>(c, b, 0), fld<R>(c, b, 1), fld<R>(c, b, 2), fld<R>(c, b, 3)};
-    if (c->opt_out_source) {
-        bool grown = false;
-        GTRY(fs3d_time_stats_layer(c, c->opt_out_source, c->opt_out_source == 2 ? c->opt_out_moment : 0, (void **)F, &grown));
-        c->gl_info[2] += grown;
-    }
-    hipLaunchKernelGGL((k_clear_type<R>), dim3(grid_for(c->ncell)), dim3(256), 0, c->stream, c->code, c->ncell,
-                       (int)FS3D_NODE_OUT, (R)99999.0f, F[0], F[1], F[2], F[3]);
-    HIPCHK(c, hipGetLastError());
-    if (n) {
-        R *kV = dev ? dV : (R *)c->gl_stage;
-        double *kT = dev ? dT : (double *)((char *)c->gl_stage + vbytes);
-        if (c->opt_out_filter || c->opt_out_vector) {          // a whole-grid context (get_layer_entry): i0 = 0, i1 = odx
-            const dim3 grid((unsigned)odx, (unsigned)std::min(ody, 65535));
-            const R two_dx = R(2) * (R)c->gdx, two_dy = R(2) * (R)c->gdy, two_dz = R(2) * (R)c->gdz;
-            const int point = c->opt_out_filter ? 0 : 1;
-            if (c->opt_out_vector)
-                hipLaunchKernelGGL((k_get_layer_box<R, true>), grid, dim3(256), 0, c->stream, (const uint16_t *)c->code, F[0], F[1], F[2], F[3],
-                                   c->dimx, c->dimy, c->dimz, odx, ody, odz, point, two_dx, two_dy, two_dz, kV, kT);
-            else
-                hipLaunchKernelGGL((k_get_layer_box<R, false>), grid, dim3(256), 0, c->stream, (const uint16_t *)c->code, F[0], F[1], F[2], F[3],
-                                   c->dimx, c->dimy, c->dimz, odx, ody, odz, point, two_dx, two_dy, two_dz, kV, kT);
-        } else
-            hipLaunchKernelGGL((k_get_layer<R>), dim3((unsigned)(i1 - i0), grid_for(po, 1024)), dim3(256), 0, c->stream, F[0], F[1], F[2], F[3],
-                               x_offset, c->dimx, c->plane, c->dimy, c->dimz, gx, odx, ody, odz, i0, i1, kV, kT);
-        HIPCHK(c, hipGetLastError());
-        if (!dev) {
-            HIPCHK(c, hipMemcpyAsync(dV, kV, (size_t)3 * n * sizeof(R), hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipMemcpyAsync(dT, kT, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
-            c->gl_info[1] = n * (long long)(3 * sizeof(R) + 8);
-        }
-    }
-    if (dev) return FS3D_OK;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->ev_used) rec_collect(c);
-    return check_device_errors(c);
-}
-
-// FS3D_OPT_OUTPUT_SLABS: (x_offset, dimx) of every rank into os_cuts, one all-gather per context (8 bytes per rank: two ints, moved
-// as elements of the context's precision).  The slabs must be the group's partition of [0, dimx_global) in rank order.
-static fs3d_status gather_cuts(fs3d_ctx *c)
-{
-    const int nr = c->nranks;
-    BUFCHK(c, c->os_cut_dev.reserve((size_t)(nr + 1) * 8));
-    int *const dev = (int *)c->os_cut_dev.raw();
-    const int mine[2] = {c->x_offset, c->dimx};
-    HIPCHK(c, hipMemcpyAsync(dev + 2 * nr, mine, sizeof mine, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));                // `mine` is pageable: the copy has left it
-    GTRY(fs3d_comm_allgather(c, dev + 2 * nr, dev, 8 / c->esize));
-    std::vector<int> cuts((size_t)2 * nr);
-    HIPCHK(c, hipMemcpyAsync(cuts.data(), dev, (size_t)nr * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    int at = 0;
-    for (int r = 0; r < nr; r++) {
-        if (cuts[2 * r] != at || cuts[2 * r + 1] < 1) return fail(c, FS3D_ERR_INVALID, "FS3D_OPT_OUTPUT_SLABS: the slabs of the group do not partition the grid's planes in rank order");
-        at += cuts[2 * r + 1];
-    }
-    if (at != c->dimx_global) return fail(c, FS3D_ERR_INVALID, "FS3D_OPT_OUTPUT_SLABS: the slabs of the group do not partition the grid's planes in rank order");
-    c->os_cuts = cuts;
-    return FS3D_OK;
-}
-
-// FS3D_OPT_OUTPUT_SLABS on a member of a group, with the filter or the vector option set: the record as ONE COLLECTIVE call.
-// Every rank runs the same sequence whatever it owns -- (the cuts, once) -- layer and stamp -- with the vector option one grouped
-// exchange of the sampled layer's boundary planes and the type planes -- k_get_layer_box_slab over the rows its planes take part
-// in -- with at least one straddling row, which every rank finds alike from the cuts, one all-reduce of their partial sums --
-// k_get_layer_finish on the straddling row it owns -- staging, copies, rows and gl_info as get_layer_impl.  Returns synchronised
-// but for the `dev` form, which may synchronise in the transport.  The caller aborts the group when this fails.
-template <typename R>
-static fs3d_status get_layer_slabs_impl(fs3d_ctx *c, R *outV, double *outT, int odx, int ody, int odz, bool dev, int rows[2])
-{
-    const int b = c->slot[FS3D_LAYER_NEXT];
-    const int gx = c->dimx_global, x_offset = c->x_offset;
-    if (odx == 0) odx = gx;
-    if (ody == 0) ody = c->dimy;
-    if (odz == 0) odz = c->dimz;
-    const long long po = (long long)ody * odz;
-    if (po >= (1LL << 31)) return fail(c, FS3D_ERR_UNSUPPORTED, "fs3d_get_layer: an output plane of 2^31 samples or more");
-    const int i0 = (int)(((long long)x_offset * odx + gx - 1) / gx), i1 = (int)(((long long)(x_offset + c->dimx) * odx + gx - 1) / gx);
-    if (rows) { rows[0] = i0; rows[1] = i1; }
-    const long long n = (long long)(i1 - i0) * po;
-    const size_t vbytes = ((size_t)3 * n * sizeof(R) + 255) / 256 * 256;
-    c->gl_info[0] = n; c->gl_info[1] = 0;
-    R *dV = outV + 3 * (size_t)i0 * po;
-    double *dT = outT + (size_t)i0 * po;
-    bool grown = false;
-    if (c->os_cuts.empty()) GTRY(gather_cuts(c));
-    // the straddling rows: per cut the row whose box begins below it, where that box reaches beyond it (the box mean only: a point
-    // sample is one cell).  Ascending, a row over several cuts once; the same list on every rank
-    auto box_lo = [](int i, int g, int o) { return (int)((long long)i * g / o); };
-    auto box_hi = [&](int i, int g, int o) { return std::max(box_lo(i, g, o) + 1, (int)((long long)(i + 1) * g / o)); };
-    std::vector<int> list;
-    if (c->opt_out_filter)
-        for (int r = 1; r < c->nranks; r++) {
-            const int cut = c->os_cuts[2 * r], i = (int)(((long long)cut * odx + gx - 1) / gx) - 1;
-            if (i >= 0 && box_lo(i, gx, odx) < cut && box_hi(i, gx, odx) > cut && (list.empty() || list.back() != i)) list.push_back(i);
-        }
-    auto place = [&](int i) { const auto it = std::find(list.begin(), list.end(), i); return it == list.end() ? -1 : (int)(it - list.begin()); };
-    // the rows this slab's planes take part in: the owned ones, and in front of them the row that begins in a slab below
-    const int ia = i0 > 0 && place(i0 - 1) >= 0 && box_hi(i0 - 1, gx, odx) > x_offset ? i0 - 1 : i0;
-    const int s_first = i1 > ia ? place(ia) : -1, s_last = i1 > ia ? place(i1 - 1) : -1;
-    const bool finish = i1 > i0 && s_last >= 0;              // the last owned row reaches into the next slab
-    const size_t nsum = list.size() * (size_t)5 * po;
-    if (!dev && n) { BUFCHK(c, c->gl_stage.reserve(vbytes + (size_t)n * 8, nullptr, &grown)); c->gl_info[2] += grown; }
-    if (c->opt_out_vector) { BUFCHK(c, c->os_type.reserve((size_t)4 * c->plane, nullptr, &grown)); c->gl_info[2] += grown; }
-    if (nsum) { BUFCHK(c, c->os_part.reserve(nsum * sizeof(double), nullptr, &grown)); c->gl_info[2] += grown; }
-    R *F[4] = {fld<R>(c, b, 0), fld<R>(c, b, 1), fld<R>(c, b, 2), fld<R>(c, b, 3)};
-    long long fstride = c->fstride;
-    if (c->opt_out_source) {
-        GTRY(fs3d_time_stats_layer(c, c->opt_out_source, c->opt_out_source == 2 ? c->opt_out_moment : 0, (void **)F, &grown, true, &fstride));
-        c->gl_info[2] += grown;
-    }
-    hipLaunchKernelGGL((k_clear_type<R>), dim3(grid_for(c->ncell)), dim3(256), 0, c->stream, c->code, c->ncell,
-                       (int)FS3D_NODE_OUT, (R)99999.0f, F[0], F[1], F[2], F[3]);
-    HIPCHK(c, hipGetLastError());
-    uint8_t *const ty = c->os_type;
-    if (c->opt_out_vector) {
-        hipLaunchKernelGGL(k_type_planes, dim3(grid_for(c->plane)), dim3(256), 0, c->stream, (const uint16_t *)c->code, c->plane,
-                           (long long)(c->dimx - 1) * c->plane, ty, ty + c->plane);
-        HIPCHK(c, hipGetLastError());
-        GTRY(fs3d_comm_layer_exchange(c, F[0] - c->plane, fstride, {ty, ty + c->plane, ty + 2 * c->plane, ty + 3 * c->plane}));
-    }
-    if (nsum) HIPCHK(c, hipMemsetAsync(c->os_part, 0, nsum * sizeof(double), c->stream));
-    R *kV = dev ? dV : (R *)c->gl_stage;
-    double *kT = dev ? dT : (double *)((char *)c->gl_stage + vbytes);
-    const R two_dx = R(2) * (R)c->gdx, two_dy = R(2) * (R)c->gdy, two_dz = R(2) * (R)c->gdz;
-    auto run = [&](auto vort) {
-        constexpr bool VORT = decltype(vort)::value;
-        const SlabCells<R, VORT> s{c->code, F[0], F[1], F[2], F[3], VORT ? ty + 2 * c->plane : nullptr, VORT ? ty + 3 * c->plane : nullptr, x_offset, c->dimx, gx, c->dimy, c->dimz,
-                                   two_dx, two_dy, two_dz};
-        if (i1 > ia)
-            hipLaunchKernelGGL((k_get_layer_box_slab<R, VORT>), dim3((unsigned)(i1 - ia), (unsigned)std::min(ody, 65535)), dim3(256), 0, c->stream, s,
-                               odx, ody, odz, c->opt_out_filter ? 0 : 1, ia, i0, s_first, s_last, kV, kT, (double *)c->os_part);
-        if (hipGetLastError() != hipSuccess) return fail(c, FS3D_ERR_HIP, call_failed(c, "k_get_layer_box_slab", "launch"));
-        if (nsum) GTRY(fs3d_comm_allreduce_sum(c, c->os_part, nsum));
-        if (finish) {
-            const long long at = (long long)(i1 - 1 - i0) * po;
-            hipLaunchKernelGGL((k_get_layer_finish<R, VORT>), dim3(grid_for(po, 1024)), dim3(256), 0, c->stream, s, i1 - 1, odx, ody, odz,
-                               (const double *)c->os_part + (size_t)s_last * 5 * po, kV + 3 * at, kT + at);
-            if (hipGetLastError() != hipSuccess) return fail(c, FS3D_ERR_HIP, call_failed(c, "k_get_layer_finish", "launch"));
-        }
-        return FS3D_OK;
-    };
-    GTRY(c->opt_out_vector ? run(std::true_type{}) : run(std::false_type{}));
-    if (!dev && n) {
-        HIPCHK(c, hipMemcpyAsync(dV, kV, (size_t)3 * n * sizeof(R), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(dT, kT, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
-        c->gl_info[1] = n * (long long)(3 * sizeof(R) + 8);
-    }
-    if (dev) return FS3D_OK;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->ev_used) rec_collect(c);
-    return check_device_errors(c);
-}
-
-// the three output entries: refusals before any launch, then the precision's get_layer_impl
-static fs3d_status get_layer_entry(fs3d_ctx *c, const char *what, void *outV, double *outT, int odx, int ody, int odz, bool local, bool dev, int rows[2])
-{
-    if (!c || !outV || !outT || (!local && !rows)) return c ? fail(c, FS3D_ERR_INVALID, std::string(what) + ": NULL destination") : FS3D_ERR_INVALID;
-    if (!c->have_nodes) return fail(c, FS3D_ERR_INVALID, std::string(what) + ": upload nodes first");
-    if (odx < 0 || ody < 0 || odz < 0) return fail(c, FS3D_ERR_INVALID, std::string(what) + ": negative output dims");
-    const bool slab_record = (c->opt_out_filter || c->opt_out_vector) &&
-                             (c->x_offset != 0 || c->dimx != c->dimx_global || c->comm || c->local || c->nranks > 1);
-    if (slab_record && !c->opt_out_slabs)
-        return fail(c, FS3D_ERR_UNSUPPORTED, std::string(what) + ": FS3D_OPT_OUTPUT_FILTER / FS3D_OPT_OUTPUT_VECTOR on an x-slab or a member of a group "
-                                             "(a box can straddle a cut and the curl needs the neighbour's planes)");
-    if (slab_record && local)
-        return fail(c, FS3D_ERR_UNSUPPORTED, std::string(what) + ": FS3D_OPT_OUTPUT_FILTER / FS3D_OPT_OUTPUT_VECTOR on an x-slab: this entry samples the slab's own "
-                                             "planes and is not collective; FS3D_OPT_OUTPUT_SLABS serves fs3d_get_layer_rows and fs3d_get_layer_dev");
-    if (slab_record && !c->comm && !c->local)
-        return fail(c, FS3D_ERR_UNSUPPORTED, std::string(what) + ": FS3D_OPT_OUTPUT_SLABS: a lone x-slab of a larger grid needs its neighbours' planes and sums: "
-                                             "make it a member of a group (fs3d_comm_init_local, fs3d_comm_init) first");
-    if (c->opt_out_source) {
-        const char *const names[4] = {"", "the time mean", "the time variance", "the fluid fraction"};
-        if (c->opt_time_stats == 0 || (c->opt_out_source == 2 && c->opt_time_stats < 2))
-            return fail(c, FS3D_ERR_INVALID, std::string(what) + ": FS3D_OPT_OUTPUT_SOURCE asks for " + names[c->opt_out_source] +
-                                             ", which the FS3D_OPT_TIME_STATS mode " + std::to_string(c->opt_time_stats) + " does not hold");
-        if (c->opt_out_source == 2 && c->opt_out_moment) {         // the moment is read for source 2 only
-            if (c->opt_time_stats < 2 || !c->opt_ts_cross)
-                return fail(c, FS3D_ERR_INVALID, std::string(what) + ": FS3D_OPT_OUTPUT_MOMENT " + std::to_string(c->opt_out_moment) +
-                                                 " asks for covariances, and the open window holds no cross sums (FS3D_OPT_TIME_STATS 2 with FS3D_OPT_TIME_STATS_CROSS 1)");
-            if (c->opt_out_vector)
-                return fail(c, FS3D_ERR_INVALID, std::string(what) + ": FS3D_OPT_OUTPUT_MOMENT " + std::to_string(c->opt_out_moment) +
-                                                 " with FS3D_OPT_OUTPUT_VECTOR 1 (the curl of a stress layer means nothing)");
-        }
-        if (c->ts_steps == 0) return fail(c, FS3D_ERR_INVALID, std::string(what) + ": the window of FS3D_OPT_TIME_STATS holds no time step yet");
-    }
-    HIPCHK(c, hipSetDevice(c->device));
-    if (slab_record) {                                         // collective from here on: a rank that fails takes the group down
-        fs3d_status st = FS3D_ERR_HIP;
-        AbortOnError guard{c, &st};
-        st = c->prec == FS3D_F32 ? get_layer_slabs_impl<float>(c, (float *)outV, outT, odx, ody, odz, dev, rows)
-                                 : get_layer_slabs_impl<double>(c, (double *)outV, outT, odx, ody, odz, dev, rows);
-        return st;
-    }
-    return c->prec == FS3D_F32 ? get_layer_impl<float>(c, (float *)outV, outT, odx, ody, odz, local, dev, rows)
-                               : get_layer_impl<double>(c, (double *)outV, outT, odx, ody, odz, local, dev, rows);
-}
-
-extern "C" fs3d_status fs3d_get_layer(fs3d_ctx *c, void *outV, double *outT, int odx, int ody, int odz)
-{
-    return get_layer_entry(c, "fs3d_get_layer", outV, outT, odx, ody, odz, true, false, nullptr);
-}
-
-extern "C" fs3d_status fs3d_get_layer_rows(fs3d_ctx *c, void *outV, double *outT, int odx, int ody, int odz, int rows[2])
-{
-    return get_layer_entry(c, "fs3d_get_layer_rows", outV, outT, odx, ody, odz, false, false, rows);
-}
-
-extern "C" fs3d_status fs3d_get_layer_dev(fs3d_ctx *c, void *outV, double *outT, int odx, int ody, int odz, int rows[2])
-{
-    return get_layer_entry(c, "fs3d_get_layer_dev", outV, outT, odx, ody, odz, false, true, rows);
-}
-
-extern "C" fs3d_status fs3d_get_layer_info(fs3d_ctx *c, long long info[FS3D_N_GETLAYER_INFO])
-{
-    if (!c || !info) return FS3D_ERR_INVALID;
-    for (int k = 0; k < FS3D_N_GETLAYER_INFO; k++) info[k] = c->gl_info[k];
-    return FS3D_OK;
 }

@@ -1,7 +1,7 @@
 """Filtered and derived result records: what fs3d_get_layer, fs3d_get_layer_rows and fs3d_get_layer_dev return while
 FS3D_OPT_OUTPUT_FILTER or FS3D_OPT_OUTPUT_VECTOR is set.
 
-layer_output is the definition of the rule; k_get_layer_box (csrc/fs3d_hip.hip) is held to it -- bit for bit wherever the double
+layer_output is the definition of the rule; k_get_layer_box (csrc/kernels_output.hip) is held to it -- bit for bit wherever the double
 sums are exact, to the rounding of one sum elsewhere.  The reference has no counterpart: its FilterToArrays (TimeLayer3D.h:819-924)
 is the point sample, which is filter 0 with vector 0 here.
 

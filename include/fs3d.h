@@ -566,8 +566,8 @@ fs3d_status fs3d_get_layer(fs3d_ctx *ctx, void *outV, double *outT,
  * negative dims, no nodes yet: FS3D_ERR_INVALID, the context stays usable) and report pending device errors.
  *
  * Filtered and derived records (FS3D_OPT_OUTPUT_FILTER, FS3D_OPT_OUTPUT_VECTOR; no reference counterpart; the rule and its numpy
- * twin: cmc_fluid_solver_amd/layer_output.py).  With either option non-zero the three entries run k_get_layer_box in place of the
- * gather, behind the same stamp, through the same staging buffer and copies: `next` is left as a default call leaves it.
+ * twin: cmc_fluid_solver_amd/layer_output.py).  With either option non-zero the three entries run k_get_layer_box
+ * (csrc/kernels_output.hip) in place of the gather, behind the same stamp, through the same staging buffer and copies: `next` is left as a default call leaves it.
  * The box of output index i on an axis of g source cells and o samples is [lo, hi), lo = i*g/o, hi = max(lo + 1, (i+1)*g/o) in
  * 64-bit integers: for o <= g the boxes partition the axis and start at the reference's sample cell, for o >= g each is that cell.
  * Per cell q = (a, b, c, T): (a, b, c) is the velocity, or with FS3D_OPT_OUTPUT_VECTOR set to 1 the vorticity in the context's real

@@ -1,4 +1,4 @@
-"""Result output on the device (k_get_layer; fs3d_get_layer_rows / _dev / _info; fs3d_get_layer through the same kernel).
+"""Result output on the device (k_get_layer, csrc/kernels_output.hip; fs3d_get_layer_rows / _dev / _info; fs3d_get_layer through the same kernel).
 
 FilterToArrays is a gather, so every comparison is array_equal.  `next` is filled through upload_layer with distinct values in a
 random order (no time step is needed), the expectation is the numpy gather of download_layer(LAYER_NEXT) taken AFTER the call --
@@ -205,6 +205,25 @@ def test_get_layer_info_counts_samples_bytes_and_allocations(built, dtype, nbyte
     s.GetLayer()
     s.GetLayerRows(V, T, (7, 6, 5))
     assert s.get_layer_info() == {"samples": 210, "bytes_to_host": nbytes, "device_allocs": 2}
+    s.close()
+
+
+@pytest.mark.parametrize("filter", [0, 1])
+def test_a_larger_record_of_a_time_statistic_counts_its_one_allocation(built, filter):
+    """Two buffers serve a record of a statistic layer, the staging buffer and the layer: a larger record grows the first and finds
+    the second as it is -- one allocation more, through the gather and through the box kernel."""
+    nodes = grids.box_with_obstacle(23, 13, 11)
+    s = capi.Solver(nodes, capi.fluid_params(np.float32, 200.0, 0.72, 1.4), np.float32)
+    s.set_option(capi.OPT_TIME_STATS, 1)
+    s.UpdateBoundaries()
+    s.TimeStep(0.05, 1, 1, True)
+    s.set_option(capi.OPT_OUTPUT_SOURCE, 1)
+    s.set_option(capi.OPT_OUTPUT_FILTER, filter)
+    allocs = []
+    for od in ((5, 4, 7), (5, 4, 7), (0, 0, 0), (0, 0, 0), (5, 4, 7)):
+        s.GetLayer(od)
+        allocs.append(s.get_layer_info()["device_allocs"])
+    assert allocs == [2, 2, 3, 3, 3]
     s.close()
 
 

@@ -1,4 +1,4 @@
-"""Filtered and derived result records on the device (k_get_layer_box behind FS3D_OPT_OUTPUT_FILTER / FS3D_OPT_OUTPUT_VECTOR)
+"""Filtered and derived result records on the device (k_get_layer_box, csrc/kernels_output.hip, behind FS3D_OPT_OUTPUT_FILTER / FS3D_OPT_OUTPUT_VECTOR)
 against the rule's numpy twin, cmc_fluid_solver_amd/layer_output.py.
 
 Exact fields (integers + 0.5 below 2^23, all different): every double sum is exact whatever order the kernel adds in, so the

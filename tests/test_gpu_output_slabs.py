@@ -1,4 +1,4 @@
-"""GPU: filtered and derived result records on x-slabs (FS3D_OPT_OUTPUT_SLABS; k_get_layer_box_slab, k_get_layer_finish, the grouped
+"""GPU: filtered and derived result records on x-slabs (FS3D_OPT_OUTPUT_SLABS; k_get_layer_box<.., SLAB>, k_get_layer_finish, the grouped
 exchange of the sampled layer's boundary planes and type planes, one all-reduce of the straddling rows' partial sums) -- in-process
 groups of 2, 3 and 4 slabs on device 0, both precisions.  The rows of all ranks together must be the record of the numpy twin on the
 GLOBAL grid (cmc_fluid_solver_amd/layer_output.py): bit for bit on exact fields and for the point vorticity, within the derived bound
@@ -333,6 +333,32 @@ def test_nothing_is_allocated_from_the_second_identical_call_on(built):
     for rank, a in enumerate(grp.run(work)):
         print("rank", rank, "device allocations after each call", a)
         assert a[0] >= 1 and a[1] == a[2] == a[0] and a[3] > a[2] and a[4] == a[5] == a[3], (rank, a)
+    grp.close()
+
+
+def test_a_larger_record_counts_only_the_buffers_that_grow(built):
+    """23 -> 5 on 3 slabs, rows 1 and 3 straddle, every rank owns rows.  The first filtered curl record of the time mean allocates
+    four buffers per rank: staging, type planes, partial sums, statistic layer.  A record of four times the samples per row grows
+    the staging buffer and the partial sums; the type planes and the statistic layer hold: two more, not four."""
+    dims, od, nranks = OC.CASES[1]
+    large = (od[0], 2 * od[1], 2 * od[2])
+    nodes = grids.box_with_obstacle(*dims)
+    grp = group(nodes, nranks, np.float32)
+
+    def work(rank, s):
+        s.set_option(capi.OPT_TIME_STATS, 1)
+        s.UpdateBoundaries()
+        s.TimeStep(DT, 1, 1, True)
+        s.set_option(capi.OPT_OUTPUT_SOURCE, 1)
+        set_mode(s, 1, 1)
+        allocs = []
+        for o in (od, od, large, large, od):
+            V, T = nan_arrays(o, np.float32)
+            s.GetLayerRows(V, T, o)
+            allocs.append(s.get_layer_info()["device_allocs"])
+        return allocs
+    for rank, a in enumerate(grp.run(work)):
+        assert a == [4, 4, 6, 6, 6], (rank, a)
     grp.close()
 
 

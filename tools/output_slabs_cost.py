@@ -1,10 +1,12 @@
-"""What a filtered or derived result record costs on x-slabs (FS3D_OPT_OUTPUT_SLABS; k_get_layer_box_slab, k_get_layer_finish,
+"""What a filtered or derived result record costs on x-slabs (FS3D_OPT_OUTPUT_SLABS; k_get_layer_box, k_get_layer_finish,
 k_type_planes), fp32, in-process slabs of ONE device, beside the whole-grid record of the same library in the same session.
 
   python tools/output_slabs_cost.py [--repeats N] [--out FILE]        -> profiles/output_slabs_cost.txt
 
-A 256^3 box with an obstacle -> 54 x 54 x 52 samples.  One child per layout -- the whole grid (k_get_layer_box), 2 slabs, 4 slabs --
-makes, for the box mean and for the box-mean vorticity, 3 warm-up records and `--repeats` timed ones: the host clock around the
+A 256^3 box with an obstacle -> 54 x 54 x 52 samples.  One child per layout -- the whole grid, 2 slabs, 4 slabs: the same box
+kernel, told apart by the child's layout (a library from before the two box kernels became one gives the slabs' kernel a longer
+name that begins alike; it is counted as the box kernel too, so FS3D_LIB_PATH may select such a library) -- makes, for the box
+mean and for the box-mean vorticity, 3 warm-up records and `--repeats` timed ones: the host clock around the
 call on rank 0 (the call returns synchronised; on slabs it holds the exchange, the all-reduce and the waits for the peers).  A second
 child of the same layout runs under `rocprofv3 --kernel-trace` (alone): per kernel name the median device duration and the
 launches per record; a record's device time is the sum over the names of median x launches per record, over all ranks.  The slabs
@@ -35,7 +37,7 @@ DIMS, OUTDIMS = (256, 256, 256), (54, 54, 52)
 MODES = (("box mean", 1, 0), ("box-mean vorticity", 1, 1))
 LAYOUTS = (1, 2, 4)
 WARMUP = 3
-KERNELS = ("k_clear_type", "k_type_planes", "k_get_layer_box_slab", "k_get_layer_box", "k_get_layer_finish")
+KERNELS = ("k_clear_type", "k_type_planes", "k_get_layer_box", "k_get_layer_finish")
 
 
 def run_child(cmd, seconds):
@@ -85,7 +87,7 @@ def kernel_times(path, calls_per_mode):
     rows.sort(key=lambda r: int(r["Start_Timestamp"]))
 
     def name_of(r):
-        return [k for k in KERNELS if k in r["Kernel_Name"]][0] if "k_get_layer_box_slab" not in r["Kernel_Name"] else "k_get_layer_box_slab"
+        return [k for k in KERNELS if k in r["Kernel_Name"]][0]
     # the stamp opens every rank's record: split the trace into the modes by the share of stamps seen
     stamps = [k for k, r in enumerate(rows) if name_of(r) == "k_clear_type"]
     per_mode = len(stamps) // len(MODES)
