@@ -40,6 +40,9 @@ OPT_TIME_STATS_CROSS = 16  # 1: mode 2 also sums the six products uv, uw, vw, uT
 OPT_OUTPUT_MOMENT = 17    # what source 2 builds: 0 the variances (default), 1 the Reynolds stresses and k, 2 the heat fluxes and var_T (time_stats.MOMENTS)
 OPT_TIME_STATS_EVERY = 18  # the stride k of the accumulated steps, 1 (default) .. 2^20: candidate s of a window counts where (s - 1) % k == 0; every set opens a new window
 OPT_OUTPUT_SLABS = 19     # 1: on a member of a group GetLayerRows / GetLayerDev take the filter and vector options, as one collective call (default 0)
+OPT_OUTPUT_GRADIENT = 20  # outV of the three GetLayer entries: 0 as FS3D_OPT_OUTPUT_VECTOR has it (default), 1 the invariants (div, Q, S:S) of the velocity gradient of the
+                          # sampled layer, 2 their time mean from the gradient sums (layer_output.invariants, time_stats.TimeStats.gradient_layer are the rule)
+OPT_TIME_STATS_GRAD = 21  # 1: every accumulated step also sums div, Q and S:S of the new `cur` per cell; whole grids only; every set opens a new window, 0 frees them (default 0)
 XSOLVE_AUTO, XSOLVE_PIPELINED, XSOLVE_REDUCED, XSOLVE_REDUCED_A2A = 0, 1, 2, 3
 
 # every function include/fs3d.h declares, in the header's order: name -> (restype, argtypes)

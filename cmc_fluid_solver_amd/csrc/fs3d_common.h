@@ -186,7 +186,7 @@ struct fs3d_ctx {
     int opt_fresh_cells = 0;               // FS3D_OPT_FRESH_CELLS: 1 = every single-context update keeps the node types of the geometry it replaces
     int opt_fresh_slabs = 0;               // FS3D_OPT_FRESH_CELLS_SLABS: 1 = a slab of a group keeps that snapshot too and fills collectively
     int opt_out_filter = 0;                // FS3D_OPT_OUTPUT_FILTER: 1 = the GetLayer entries average the NODE_IN cells of every sample's box (k_get_layer_box)
-    int opt_out_vector = 0;                // FS3D_OPT_OUTPUT_VECTOR: 1 = their outV holds the vorticity (k_get_layer_box with VORT)
+    int opt_out_vector = 0;                // FS3D_OPT_OUTPUT_VECTOR: 1 = their outV holds the vorticity (k_get_layer_box with VEC 1)
     // FS3D_OPT_OUTPUT_SLABS: 1 = on a member of a group fs3d_get_layer_rows / _dev take the two options above as one collective call
     // (get_layer_impl with `collective`, kernels_output.hip).  Its buffers are allocated by the first call that needs them, kept and only grown, counted in gl_info[2]:
     // os_type -- four planes of node types, a byte per cell: the own first and last plane (derived from `code` per call), the lower
@@ -218,6 +218,15 @@ struct fs3d_ctx {
     DevBuf<unsigned> ts_n;
     DevBuf<double> ts_s1, ts_s2, ts_sx;
     DevBuf<> ts_q;
+    // gradient sums (FS3D_OPT_TIME_STATS_GRAD; k_time_grad, kernels_stats.hip): per own cell the accumulated steps on which it carried
+    // invariants (tg_n) and the double sums of div, Q and S:S over them (tg_g, quantity v at + v * ts_stride) -- 28 bytes per cell in
+    // two buffers, allocated by the first accumulation that needs them, counted in geom_allocs, kept over windows, freed when this
+    // option or FS3D_OPT_TIME_STATS is set to 0.  They share the window of the sums above (every set of the option opens a new one)
+    // and are zeroed by the accumulation that zeroes those
+    int opt_ts_grad = 0;                   // FS3D_OPT_TIME_STATS_GRAD: 1 = every accumulated step also sums the invariants of the velocity gradient
+    int opt_out_gradient = 0;              // FS3D_OPT_OUTPUT_GRADIENT: outV of the GetLayer entries -- 1 the invariants of the sampled layer, 2 their time mean
+    DevBuf<unsigned> tg_n;
+    DevBuf<double> tg_g;
     int opt_err_order = 0;                 // FS3D_OPT_ERR_ORDER: 1 = EvalDivError sums its per-cell terms serially in cell order (host), as the CPU path
     DevBuf<double> err_terms;              // ... one term per cell (device, allocated on first use)
     std::vector<double> err_terms_host;
@@ -302,7 +311,22 @@ fs3d_status check_device_errors(fs3d_ctx *c);
 // kernels_geom.hip
 void fs3d_geom_destroy(fs3d_ctx *c);
 
-// kernels_stats.hip: FS3D_OPT_TIME_STATS / _CROSS / _EVERY, FS3D_OPT_OUTPUT_SOURCE / _MOMENT
+// The invariants of the velocity gradient (FS3D_OPT_OUTPUT_GRADIENT, FS3D_OPT_TIME_STATS_GRAD; the rule: layer_output.py) from the
+// nine central-difference quotients g[a][b] = d u_a / d x_b: (div, Q, S:S), every operation rounded once in R, in the rule's order.
+// Shared by the record kernel (kernels_output.hip) and the accumulation (kernels_stats.hip), both built with -ffp-contract=off.
+template <typename R>
+static __device__ __forceinline__ void fs3d_invariants(const R (&g)[3][3], R &div, R &q, R &ss)
+{
+    const R h = R(0.5f);
+    div = (g[0][0] + g[1][1]) + g[2][2];
+    const R sxy = h * (g[0][1] + g[1][0]), sxz = h * (g[0][2] + g[2][0]), syz = h * (g[1][2] + g[2][1]);
+    const R oxy = h * (g[0][1] - g[1][0]), oxz = h * (g[0][2] - g[2][0]), oyz = h * (g[1][2] - g[2][1]);
+    ss = ((g[0][0] * g[0][0] + g[1][1] * g[1][1]) + g[2][2] * g[2][2]) + R(2) * ((sxy * sxy + sxz * sxz) + syz * syz);
+    const R oo = R(2) * ((oxy * oxy + oxz * oxz) + oyz * oyz);
+    q = h * (oo - ss);
+}
+
+// kernels_stats.hip: FS3D_OPT_TIME_STATS / _CROSS / _EVERY / _GRAD, FS3D_OPT_OUTPUT_SOURCE / _MOMENT
 // one candidate step of the window: where the stride takes it, one accumulation of FS3D_LAYER_CUR, enqueued on the context's stream
 // (the first one allocates and clears); else nothing
 fs3d_status fs3d_time_stats_accumulate(fs3d_ctx *c);
@@ -311,9 +335,13 @@ fs3d_status fs3d_time_stats_accumulate(fs3d_ctx *c);
 // field (the collective records of FS3D_OPT_OUTPUT_SLABS exchange them); *qstride_out: elements from field to field
 fs3d_status fs3d_time_stats_layer(fs3d_ctx *c, int source, int moment, void *q_out[4], bool *grown, bool ghost = false,
                                   long long *qstride_out = nullptr);
-// all accumulators / the cross sums alone; the caller has synchronised the stream
+// FS3D_OPT_OUTPUT_GRADIENT 2: the fields U, V, W of the statistic layer a source-1 call has just built (q: their first own cells,
+// qstride apart) become the time means of div, Q and S:S from the gradient sums, enqueued behind it; T stays the mean of T
+fs3d_status fs3d_time_stats_grad_layer(fs3d_ctx *c, void *q, long long qstride);
+// all accumulators / the cross sums alone / the gradient sums alone; the caller has synchronised the stream
 void fs3d_time_stats_free(fs3d_ctx *c);
 void fs3d_time_stats_free_cross(fs3d_ctx *c);
+void fs3d_time_stats_free_grad(fs3d_ctx *c);
 
 // kernels_*.hip
 // What a sweep launcher did.  NA: it does not cover these dims / this precision / this slab form -- the caller may try the

@@ -403,6 +403,22 @@ extern "C" fs3d_status fs3d_set_option(fs3d_ctx *c, int option, int value)
         if (value < 1 || value > (1 << 20)) return fail(c, FS3D_ERR_INVALID, "bad time-statistics stride (1 .. 2^20: every k-th step of a window is accumulated, the first one always)");
         c->opt_ts_every = value; c->ts_steps = 0; c->ts_candidates = 0; c->ts_clear = true;
         return FS3D_OK;
+    case FS3D_OPT_TIME_STATS_GRAD:
+        // a new window as above; 0 gives the gradient sums back.  Whole grids only: the stencil would read ghost planes of `cur`,
+        // which are not current after a step, and the accumulation is no collective call
+        if (value != 0 && value != 1) return fail(c, FS3D_ERR_INVALID, "bad time-statistics gradient value (0: off, 1: every accumulated step also sums div, Q and S:S of the velocity gradient)");
+        if (value == 1 && (c->x_offset != 0 || c->dimx != c->dimx_global))
+            return fail(c, FS3D_ERR_UNSUPPORTED, "FS3D_OPT_TIME_STATS_GRAD on an x-slab (the stencil needs the neighbours' planes of `cur` at every accumulated step)");
+        c->opt_ts_grad = value; c->ts_steps = 0; c->ts_candidates = 0; c->ts_clear = true;
+        if (value == 0 && (c->tg_n.raw() || c->tg_g.raw())) {
+            HIPCHK(c, hipSetDevice(c->device));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            fs3d_time_stats_free_grad(c);
+        }
+        return FS3D_OK;
+    case FS3D_OPT_OUTPUT_GRADIENT:
+        if (value < 0 || value > 2) return fail(c, FS3D_ERR_INVALID, "bad output gradient id (0: off, 1: the invariants div, Q, S:S of the sampled layer, 2: their time mean)");
+        c->opt_out_gradient = value; return FS3D_OK;
     case FS3D_OPT_OUTPUT_SOURCE:
         if (value < 0 || value > 3) return fail(c, FS3D_ERR_INVALID, "bad output source id (0: `next`, 1: time mean, 2: time variance, 3: fluid fraction)");
         c->opt_out_source = value; return FS3D_OK;
@@ -1130,6 +1146,8 @@ extern "C" fs3d_status fs3d_time_step(fs3d_ctx *c, double dt, int G, int L, int 
     if (!c) return FS3D_ERR_INVALID;
     if (!c->have_nodes || !c->have_params) return fail(c, FS3D_ERR_INVALID, "fs3d_time_step: upload nodes and set params first");
     if (G < 0 || L < 0 || !(dt > 0)) return fail(c, FS3D_ERR_INVALID, "fs3d_time_step: bad dt / iteration counts");
+    if (c->opt_ts_grad && c->opt_time_stats && c->nranks > 1)
+        return fail(c, FS3D_ERR_UNSUPPORTED, "fs3d_time_step: FS3D_OPT_TIME_STATS_GRAD on a member of a group (the gradient sums are not collective)");
     HIPCHK(c, hipSetDevice(c->device));
     if (c->timing_period > 1) c->timing = (c->timing_steps++ % c->timing_period) == 0;      // sampled timing: every N-th time step carries the events
     fs3d_status st = c->prec == FS3D_F32 ? time_step_enqueue<float>(c, dt, G, L, compute_error != 0)
@@ -1159,6 +1177,8 @@ extern "C" fs3d_status fs3d_time_step_async(fs3d_ctx *c, double dt, int G, int L
     if (!c) return FS3D_ERR_INVALID;
     if (!c->have_nodes || !c->have_params) return fail(c, FS3D_ERR_INVALID, "fs3d_time_step_async: upload nodes and set params first");
     if (G < 0 || L < 0 || !(dt > 0)) return fail(c, FS3D_ERR_INVALID, "fs3d_time_step_async: bad dt / iteration counts");
+    if (c->opt_ts_grad && c->opt_time_stats && c->nranks > 1)
+        return fail(c, FS3D_ERR_UNSUPPORTED, "fs3d_time_step_async: FS3D_OPT_TIME_STATS_GRAD on a member of a group (the gradient sums are not collective)");
     HIPCHK(c, hipSetDevice(c->device));
     if (c->timing_period > 1) c->timing = (c->timing_steps++ % c->timing_period) == 0;
     // UpdateBoundaries and the cur -> next copy of the boundary cells that opens TimeStep: one pass over the list

@@ -1,5 +1,5 @@
-// Result records (fs3d_get_layer, _rows, _dev, _info of include/fs3d.h): the stamp, the gather behind GetLayer, the box-mean filter and
-// the vorticity, on a whole grid and -- as one collective call, FS3D_OPT_OUTPUT_SLABS -- on the x-slabs of a group.  One kernel per
+// Result records (fs3d_get_layer, _rows, _dev, _info of include/fs3d.h): the stamp, the gather behind GetLayer, the box-mean filter,
+// the vorticity and the invariants of the velocity gradient, on a whole grid and -- as one collective call, FS3D_OPT_OUTPUT_SLABS -- on the x-slabs of a group.  One kernel per
 // stage and one host body: a whole grid is the slab x_offset = 0, dimx = dimx_global of a group of one, with no straddling row.
 #include <algorithm>
 #include <string>
@@ -50,7 +50,8 @@ __global__ void __launch_bounds__(256) k_get_layer(const R *__restrict__ U, cons
 // then the single context's, bit for bit: the curl tests the GLOBAL x against the grid's faces and takes the x neighbours across a
 // cut from the ghost and type planes.  A whole grid is the slab x_offset = 0, dimx = gx: both faces are the grid's, no neighbour
 // exists, and tlo / thi are never read.
-template <typename R, bool VORT>
+// VEC: what (a, b, c) is -- 0 the velocity, 1 the vorticity, 2 the invariants of the velocity gradient (div, Q, S:S; fs3d_invariants).
+template <typename R, int VEC>
 struct SlabCells {
     const uint16_t *code;
     const R *U, *V, *W, *T;
@@ -63,7 +64,7 @@ struct SlabCells {
     template <bool SLAB = true>
     __device__ __attribute__((always_inline)) void vec_of(long long l, int x, int y, int z, int ty, R &a, R &b, R &c) const
     {
-        if (!VORT) { a = U[l]; b = V[l]; c = W[l]; return; }
+        if (VEC == 0) { a = U[l]; b = V[l]; c = W[l]; return; }
         const long long plane = (long long)dimy * dimz;
         const int xg = x + x_offset;
         a = b = c = ty == FS3D_NODE_OUT ? R(99999.0f) : R(0);
@@ -72,9 +73,21 @@ struct SlabCells {
         const int tm = !SLAB || x > 0 ? type_of(l - plane) : (int)tlo[r], tp = !SLAB || x < dimx - 1 ? type_of(l + plane) : (int)thi[r];
         if (tm == FS3D_NODE_OUT || tp == FS3D_NODE_OUT || type_of(l - dimz) == FS3D_NODE_OUT ||
             type_of(l + dimz) == FS3D_NODE_OUT || type_of(l - 1) == FS3D_NODE_OUT || type_of(l + 1) == FS3D_NODE_OUT) return;
-        a = (W[l + dimz] - W[l - dimz]) / two_dy - (V[l + 1] - V[l - 1]) / two_dz;
-        b = (U[l + 1] - U[l - 1]) / two_dz - (W[l + plane] - W[l - plane]) / two_dx;
-        c = (V[l + plane] - V[l - plane]) / two_dx - (U[l + dimz] - U[l - dimz]) / two_dy;
+        if constexpr (VEC == 1) {
+            a = (W[l + dimz] - W[l - dimz]) / two_dy - (V[l + 1] - V[l - 1]) / two_dz;
+            b = (U[l + 1] - U[l - 1]) / two_dz - (W[l + plane] - W[l - plane]) / two_dx;
+            c = (V[l + plane] - V[l - plane]) / two_dx - (U[l + dimz] - U[l - dimz]) / two_dy;
+        } else {
+            const R *const F[3] = {U, V, W};
+            R g[3][3];
+#pragma unroll
+            for (int f = 0; f < 3; f++) {
+                g[f][0] = (F[f][l + plane] - F[f][l - plane]) / two_dx;
+                g[f][1] = (F[f][l + dimz] - F[f][l - dimz]) / two_dy;
+                g[f][2] = (F[f][l + 1] - F[f][l - 1]) / two_dz;
+            }
+            fs3d_invariants(g, a, b, c);
+        }
     }
 };
 
@@ -92,8 +105,10 @@ __global__ void __launch_bounds__(256) k_type_planes(const uint16_t *__restrict_
 // mean over the NODE_IN cells of its box [x0, x1) x [y0, y1) x [z0, z1) of source cells -- lo = i*g/o, hi = max(lo + 1, (i+1)*g/o) per
 // axis -- and the cell (x0, y0, z0) itself where the box holds none.  `point` (filter 0 of the vorticity): every sample is that cell,
 // one lane per output k as in k_get_layer, no box is walked.
-// VORT: the three velocity quantities are the curl, central differences in R, on the NODE_IN cells whose six neighbours are in the
-// grid and not NODE_OUT; 0 on the other NODE_IN cells and the walls, 99999 on NODE_OUT cells.
+// VEC 1: the three velocity quantities are the curl, central differences in R, on the NODE_IN cells whose six neighbours are in the
+// grid and not NODE_OUT; 0 on the other NODE_IN cells and the walls, 99999 on NODE_OUT cells.  VEC 2 (FS3D_OPT_OUTPUT_GRADIENT 1):
+// the invariants div, Q, S:S of the velocity gradient on the same cells, with the same values elsewhere: 18 neighbour values
+// where the curl reads 12, behind the same seven codes.
 // One block = one output row i and the output rows j = blockIdx.y, + gridDim.y, ...; per j the output k go in groups of 256, one
 // lane per output k.  The source cells [zb, ze) under a group are walked in chunks of 256, lanes along the source k (unit stride):
 // a thread runs down the planes and rows of the box for its k with four double sums and a count in registers, the per-k partials
@@ -112,8 +127,8 @@ __global__ void __launch_bounds__(256) k_type_planes(const uint16_t *__restrict_
 // the values the same body would run with, here known to the compiler, as k_geom_codes<SLAB> has it: the instantiation drops the
 // clipping, the row offsets, the straddling store and the fetch of the type planes, and with them the 11 SGPRs that cost the
 // box mean a wave per SIMD.
-template <typename R, bool VORT, bool SLAB>
-__global__ void __launch_bounds__(256) k_get_layer_box(const SlabCells<R, VORT> s, int odx, int ody, int odz, int point, int ia, int i0,
+template <typename R, int VEC, bool SLAB>
+__global__ void __launch_bounds__(256) k_get_layer_box(const SlabCells<R, VEC> s, int odx, int ody, int odz, int point, int ia, int i0,
                                                         int s_first, int s_last, R *__restrict__ outV, double *__restrict__ outT,
                                                         double *__restrict__ part)
 {
@@ -197,8 +212,8 @@ __global__ void __launch_bounds__(256) k_get_layer_box(const SlabCells<R, VORT> 
 // The owner of the straddling row i (the slab that holds the first plane of its box) finishes it from the group's sums: one
 // division and one rounding per quantity, or the point sample of the cell (lo_x, lo_y, lo_z) where no slab counted a NODE_IN cell.
 // One thread per sample, k fastest; `part` addresses the row's five planes, outV / outT the row's first sample.
-template <typename R, bool VORT>
-__global__ void __launch_bounds__(256) k_get_layer_finish(const SlabCells<R, VORT> s, int i, int odx, int ody, int odz,
+template <typename R, int VEC>
+__global__ void __launch_bounds__(256) k_get_layer_finish(const SlabCells<R, VEC> s, int i, int odx, int ody, int odz,
                                                            const double *__restrict__ part, R *__restrict__ outV, double *__restrict__ outT)
 {
     const long long po = (long long)ody * odz;
@@ -250,6 +265,9 @@ static fs3d_status gather_cuts(fs3d_ctx *c)
 // the call returns after the enqueue; else the owned samples go through the staging buffer and the call returns synchronised.
 // One sequence for every record: the rows -- the source layer -- the stamp -- the record stage -- the copies.
 // FS3D_OPT_OUTPUT_FILTER / FS3D_OPT_OUTPUT_VECTOR: the record stage is k_get_layer_box in place of k_get_layer.
+// FS3D_OPT_OUTPUT_GRADIENT 1: the same stage with VEC = 2, the invariants where the vector option has the curl -- "the vector option"
+// below stands for either.  FS3D_OPT_OUTPUT_GRADIENT 2 (with source 1): k_time_grad_layer of kernels_stats.hip writes the mean
+// invariants over U, V, W of the statistic layer, which is then sampled as a velocity layer (VEC = 0).
 // FS3D_OPT_OUTPUT_SOURCE 1..3 (source 2: the layer FS3D_OPT_OUTPUT_MOMENT chooses): the statistic layer of kernels_stats.hip, in a
 // buffer of its own, takes the place of `next` -- stamp, record stage, staging and copies run on it unchanged; `next` and `cur` are
 // not written.
@@ -270,6 +288,7 @@ static fs3d_status get_layer_impl(fs3d_ctx *c, R *outV, double *outT, int odx, i
     if (odz == 0) odz = c->dimz;
     const long long po = (long long)ody * odz;
     if (po >= (1LL << 31)) return fail(c, FS3D_ERR_UNSUPPORTED, "fs3d_get_layer: an output plane of 2^31 samples or more");
+    const int vec = c->opt_out_gradient == 1 ? 2 : c->opt_out_vector;      // SlabCells' VEC (the two options exclude each other)
     // the rows i with x_offset <= i*gx/odx < x_offset + dimx (slab.py out_rows)
     const int i0 = (int)(((long long)x_offset * odx + gx - 1) / gx), i1 = (int)(((long long)(x_offset + c->dimx) * odx + gx - 1) / gx);
     if (rows) { rows[0] = i0; rows[1] = i1; }
@@ -299,7 +318,7 @@ static fs3d_status get_layer_impl(fs3d_ctx *c, R *outV, double *outT, int odx, i
     const size_t nsum = list.size() * (size_t)5 * po;
     // gl_info[2] counts every allocation once: a reserve only ever sets its flag, so each gets a flag of its own
     if (!dev && n) { bool grown = false; BUFCHK(c, c->gl_stage.reserve(vbytes + (size_t)n * 8, nullptr, &grown)); c->gl_info[2] += grown; }
-    if (collective && c->opt_out_vector) { bool grown = false; BUFCHK(c, c->os_type.reserve((size_t)4 * c->plane, nullptr, &grown)); c->gl_info[2] += grown; }
+    if (collective && vec) { bool grown = false; BUFCHK(c, c->os_type.reserve((size_t)4 * c->plane, nullptr, &grown)); c->gl_info[2] += grown; }
     if (nsum) { bool grown = false; BUFCHK(c, c->os_part.reserve(nsum * sizeof(double), nullptr, &grown)); c->gl_info[2] += grown; }
     R *F[4] = {fld<R>(c, b, 0), fld<R>(c, b, 1), fld<R>(c, b, 2), fld<R>(c, b, 3)};
     long long fstride = c->fstride;
@@ -307,12 +326,13 @@ static fs3d_status get_layer_impl(fs3d_ctx *c, R *outV, double *outT, int odx, i
         bool grown = false;
         GTRY(fs3d_time_stats_layer(c, c->opt_out_source, c->opt_out_source == 2 ? c->opt_out_moment : 0, (void **)F, &grown, collective, &fstride));
         c->gl_info[2] += grown;
+        if (c->opt_out_gradient == 2) GTRY(fs3d_time_stats_grad_layer(c, F[0], fstride));      // U, V, W of the mean layer: the mean invariants
     }
     hipLaunchKernelGGL((k_clear_type<R>), dim3(grid_for(c->ncell)), dim3(256), 0, c->stream, c->code, c->ncell,
                        (int)FS3D_NODE_OUT, (R)99999.0f, F[0], F[1], F[2], F[3]);
     HIPCHK(c, hipGetLastError());
     uint8_t *const ty = c->os_type;
-    if (collective && c->opt_out_vector) {
+    if (collective && vec) {
         hipLaunchKernelGGL(k_type_planes, dim3(grid_for(c->plane)), dim3(256), 0, c->stream, (const uint16_t *)c->code, c->plane,
                            (long long)(c->dimx - 1) * c->plane, ty, ty + c->plane);
         HIPCHK(c, hipGetLastError());
@@ -321,17 +341,17 @@ static fs3d_status get_layer_impl(fs3d_ctx *c, R *outV, double *outT, int odx, i
     if (nsum) HIPCHK(c, hipMemsetAsync(c->os_part, 0, nsum * sizeof(double), c->stream));
     R *kV = dev ? dV : (R *)c->gl_stage;
     double *kT = dev ? dT : (double *)((char *)c->gl_stage + vbytes);
-    auto box_stage = [&](auto vort) {
-        constexpr bool VORT = decltype(vort)::value;
+    auto box_stage = [&](auto vec_c) {
+        constexpr int VEC = decltype(vec_c)::value;
         // not collective: the whole grid.  No neighbour exists and the two type planes are null; they would never be read -- a cell on
         // the grid's first or last plane returns from SlabCells::vec_of before the neighbour types are fetched -- and SLAB = false
         // compiles the fetch out
-        const bool cut_types = collective && VORT;
-        const SlabCells<R, VORT> s{c->code, F[0], F[1], F[2], F[3], cut_types ? ty + 2 * c->plane : nullptr, cut_types ? ty + 3 * c->plane : nullptr,
+        const bool cut_types = collective && VEC != 0;
+        const SlabCells<R, VEC> s{c->code, F[0], F[1], F[2], F[3], cut_types ? ty + 2 * c->plane : nullptr, cut_types ? ty + 3 * c->plane : nullptr,
                                    x_offset, c->dimx, gx, c->dimy, c->dimz, R(2) * (R)c->gdx, R(2) * (R)c->gdy, R(2) * (R)c->gdz};
         if (i1 > ia) {
             auto launch = [&](auto slab) {
-                hipLaunchKernelGGL((k_get_layer_box<R, VORT, decltype(slab)::value>), dim3((unsigned)(i1 - ia), (unsigned)std::min(ody, 65535)), dim3(256), 0, c->stream, s,
+                hipLaunchKernelGGL((k_get_layer_box<R, VEC, decltype(slab)::value>), dim3((unsigned)(i1 - ia), (unsigned)std::min(ody, 65535)), dim3(256), 0, c->stream, s,
                                    odx, ody, odz, c->opt_out_filter ? 0 : 1, ia, i0, s_first, s_last, kV, kT, (double *)c->os_part);
             };
             if (collective) launch(std::true_type{}); else launch(std::false_type{});
@@ -341,14 +361,14 @@ static fs3d_status get_layer_impl(fs3d_ctx *c, R *outV, double *outT, int odx, i
         if (nsum) GTRY(fs3d_comm_allreduce_sum(c, c->os_part, nsum));
         if (finish) {
             const long long at = (long long)(i1 - 1 - i0) * po;
-            hipLaunchKernelGGL((k_get_layer_finish<R, VORT>), dim3(grid_for(po, 1024)), dim3(256), 0, c->stream, s, i1 - 1, odx, ody, odz,
+            hipLaunchKernelGGL((k_get_layer_finish<R, VEC>), dim3(grid_for(po, 1024)), dim3(256), 0, c->stream, s, i1 - 1, odx, ody, odz,
                                (const double *)c->os_part + (size_t)s_last * 5 * po, kV + 3 * at, kT + at);
             if (hipGetLastError() != hipSuccess) return fail(c, FS3D_ERR_HIP, call_failed(c, "k_get_layer_finish", "launch"));
         }
         return FS3D_OK;
     };
-    if (c->opt_out_filter || c->opt_out_vector)
-        GTRY(c->opt_out_vector ? box_stage(std::true_type{}) : box_stage(std::false_type{}));
+    if (c->opt_out_filter || vec)
+        GTRY(vec == 2 ? box_stage(std::integral_constant<int, 2>{}) : vec ? box_stage(std::integral_constant<int, 1>{}) : box_stage(std::integral_constant<int, 0>{}));
     else if (n) {
         hipLaunchKernelGGL((k_get_layer<R>), dim3((unsigned)(i1 - i0), grid_for(po, 1024)), dim3(256), 0, c->stream, F[0], F[1], F[2], F[3],
                            x_offset, c->dimx, c->plane, c->dimy, c->dimz, gx, odx, ody, odz, i0, i1, kV, kT);
@@ -371,13 +391,19 @@ static fs3d_status get_layer_entry(fs3d_ctx *c, const char *what, void *outV, do
     if (!c || !outV || !outT || (!local && !rows)) return c ? fail(c, FS3D_ERR_INVALID, std::string(what) + ": NULL destination") : FS3D_ERR_INVALID;
     if (!c->have_nodes) return fail(c, FS3D_ERR_INVALID, std::string(what) + ": upload nodes first");
     if (odx < 0 || ody < 0 || odz < 0) return fail(c, FS3D_ERR_INVALID, std::string(what) + ": negative output dims");
-    const bool slab_record = (c->opt_out_filter || c->opt_out_vector) &&
+    if (c->opt_out_gradient && c->opt_out_vector)
+        return fail(c, FS3D_ERR_INVALID, std::string(what) + ": FS3D_OPT_OUTPUT_GRADIENT " + std::to_string(c->opt_out_gradient) +
+                                         " with FS3D_OPT_OUTPUT_VECTOR 1 (two options claim outV)");
+    if (c->opt_out_gradient == 2 && (c->opt_out_source != 1 || c->opt_time_stats == 0 || !c->opt_ts_grad || c->ts_steps == 0 || !c->tg_n.raw() || !c->tg_g.raw()))
+        return fail(c, FS3D_ERR_INVALID, std::string(what) + ": FS3D_OPT_OUTPUT_GRADIENT 2 asks for the time mean of the invariants: it needs FS3D_OPT_OUTPUT_SOURCE 1 and an "
+                                         "open window of FS3D_OPT_TIME_STATS with FS3D_OPT_TIME_STATS_GRAD 1 that holds a time step");
+    const bool slab_record = (c->opt_out_filter || c->opt_out_vector || c->opt_out_gradient == 1) &&
                              (c->x_offset != 0 || c->dimx != c->dimx_global || c->comm || c->local || c->nranks > 1);
     if (slab_record && !c->opt_out_slabs)
-        return fail(c, FS3D_ERR_UNSUPPORTED, std::string(what) + ": FS3D_OPT_OUTPUT_FILTER / FS3D_OPT_OUTPUT_VECTOR on an x-slab or a member of a group "
-                                             "(a box can straddle a cut and the curl needs the neighbour's planes)");
+        return fail(c, FS3D_ERR_UNSUPPORTED, std::string(what) + ": FS3D_OPT_OUTPUT_FILTER / FS3D_OPT_OUTPUT_VECTOR / FS3D_OPT_OUTPUT_GRADIENT on an x-slab or a member of a group "
+                                             "(a box can straddle a cut, the curl and the gradient need the neighbour's planes)");
     if (slab_record && local)
-        return fail(c, FS3D_ERR_UNSUPPORTED, std::string(what) + ": FS3D_OPT_OUTPUT_FILTER / FS3D_OPT_OUTPUT_VECTOR on an x-slab: this entry samples the slab's own "
+        return fail(c, FS3D_ERR_UNSUPPORTED, std::string(what) + ": FS3D_OPT_OUTPUT_FILTER / FS3D_OPT_OUTPUT_VECTOR / FS3D_OPT_OUTPUT_GRADIENT on an x-slab: this entry samples the slab's own "
                                              "planes and is not collective; FS3D_OPT_OUTPUT_SLABS serves fs3d_get_layer_rows and fs3d_get_layer_dev");
     if (slab_record && !c->comm && !c->local)
         return fail(c, FS3D_ERR_UNSUPPORTED, std::string(what) + ": FS3D_OPT_OUTPUT_SLABS: a lone x-slab of a larger grid needs its neighbours' planes and sums: "
@@ -391,9 +417,10 @@ static fs3d_status get_layer_entry(fs3d_ctx *c, const char *what, void *outV, do
             if (c->opt_time_stats < 2 || !c->opt_ts_cross)
                 return fail(c, FS3D_ERR_INVALID, std::string(what) + ": FS3D_OPT_OUTPUT_MOMENT " + std::to_string(c->opt_out_moment) +
                                                  " asks for covariances, and the open window holds no cross sums (FS3D_OPT_TIME_STATS 2 with FS3D_OPT_TIME_STATS_CROSS 1)");
-            if (c->opt_out_vector)
+            if (c->opt_out_vector || c->opt_out_gradient == 1)
                 return fail(c, FS3D_ERR_INVALID, std::string(what) + ": FS3D_OPT_OUTPUT_MOMENT " + std::to_string(c->opt_out_moment) +
-                                                 " with FS3D_OPT_OUTPUT_VECTOR 1 (the curl of a stress layer means nothing)");
+                                                 (c->opt_out_vector ? " with FS3D_OPT_OUTPUT_VECTOR 1 (the curl of a stress layer means nothing)"
+                                                                    : " with FS3D_OPT_OUTPUT_GRADIENT 1 (the gradient of a stress layer means nothing)"));
         }
         if (c->ts_steps == 0) return fail(c, FS3D_ERR_INVALID, std::string(what) + ": the window of FS3D_OPT_TIME_STATS holds no time step yet");
     }

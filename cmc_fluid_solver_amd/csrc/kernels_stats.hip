@@ -1,7 +1,8 @@
-// Time statistics (FS3D_OPT_TIME_STATS, FS3D_OPT_TIME_STATS_CROSS, FS3D_OPT_TIME_STATS_EVERY, FS3D_OPT_OUTPUT_SOURCE,
-// FS3D_OPT_OUTPUT_MOMENT; no reference counterpart): running sums of the fields and of their products over the accumulated time steps
+// Time statistics (FS3D_OPT_TIME_STATS, FS3D_OPT_TIME_STATS_CROSS, FS3D_OPT_TIME_STATS_EVERY, FS3D_OPT_TIME_STATS_GRAD,
+// FS3D_OPT_OUTPUT_SOURCE, FS3D_OPT_OUTPUT_MOMENT; no reference counterpart): running sums of the fields and of their products over the accumulated time steps
 // of a window, and the statistic layers the result output reads in place of `next`.  The rule and its numpy twin:
-// cmc_fluid_solver_amd/time_stats.py.  Per cell, nothing from a neighbour: a slab accumulates and reads out its own planes.
+// cmc_fluid_solver_amd/time_stats.py.  Per cell, nothing from a neighbour: a slab accumulates and reads out its own planes -- but for
+// the gradient sums of FS3D_OPT_TIME_STATS_GRAD (k_time_grad), a stencil over `cur`, which whole grids alone accumulate.
 // Built with -ffp-contract=off like everything outside kernels_part.hip: every operation below is rounded once in double.
 #include "fs3d_common.h"
 
@@ -181,6 +182,94 @@ __global__ void __launch_bounds__(256) k_time_stats_layer(int source, int moment
     }
 }
 
+// FS3D_OPT_TIME_STATS_GRAD: one accumulation of the invariants of the velocity gradient (fs3d_invariants: div, Q, S:S in R) of `cur`,
+// on the cells that carry them -- NODE_IN, the six neighbours inside the grid and not NODE_OUT: ng += 1, G_v += (double)value.
+// Whole grids only (`cur` and `code` address the cell (0, 0, 0); no ghost plane is read).
+// The form is k_div_error's: one block = the plane i = 1 .. dimx - 2 and TG_JS of the rows 1 .. dimy - 2, lanes along k in chunks of
+// 256.  A thread walks down its rows with the rows j - 1, j, j + 1 of plane i in registers (three fields and the node type), takes
+// the k - 1 and k + 1 values of row j from the lanes next door (the first and last lane of a wave load theirs) and loads the two
+// values of the planes i - 1 and i + 1: per cell and field one new row value and two plane values, 3 loads where the plain form has
+// 6, and every value of plane i comes in once per tile (plus the two rows around the tile).  The planes i +- 1 are the neighbouring
+// blocks' own planes: they come through the caches.  Every address is inside the grid: i, j stay off the faces and k is clamped
+// to dimz - 1 (the lanes past the line compute nothing).  The accumulators are a plain read-modify-write stream on the defined
+// cells, as in k_time_stats_v4 (nontemporal accesses of them lose there).  No LDS, no atomics, no scratch.
+#define TG_JS 16
+template <typename R>
+__global__ void __launch_bounds__(256) k_time_grad(const uint16_t *__restrict__ code, const R *__restrict__ cur, long long fstride,
+                                                    int dimy, int dimz, int nj, R two_dx, R two_dy, R two_dz,
+                                                    unsigned *__restrict__ cnt, double *__restrict__ gs, long long sstride)
+{
+    const long long plane = (long long)dimy * dimz;
+    const int i = (int)(blockIdx.x / nj) + 1, j0 = (int)(blockIdx.x % nj) * TG_JS + 1;
+    const int jend = j0 + TG_JS < dimy - 1 ? j0 + TG_JS : dimy - 1;
+    const int lane = (int)threadIdx.x & 63;
+    const R *const F[3] = {cur, cur + fstride, cur + 2 * fstride};
+    auto type_at = [&](long long l) { return (int)((code[l] >> CODE_TYPE_SHIFT) & 3); };
+    for (int kb = 0; kb < dimz; kb += 256) {
+        const int k = kb + (int)threadIdx.x;
+        const int kc = k < dimz ? k : dimz - 1;
+        const bool kin = k >= 1 && k < dimz - 1;
+        long long a = (long long)i * plane + (long long)(j0 - 1) * dimz + kc;
+        R lo[3], mid[3], hi[3];
+        int tlo = type_at(a), tmid = type_at(a + dimz);
+#pragma unroll
+        for (int f = 0; f < 3; f++) { lo[f] = F[f][a]; mid[f] = F[f][a + dimz]; }
+        a += dimz;
+        for (int j = j0; j < jend; j++, a += dimz) {          // a: the cell (i, j, kc)
+            const int thi = type_at(a + dimz), txm = type_at(a - plane), txp = type_at(a + plane);
+            int tkm = __shfl_up(tmid, 1, 64), tkp = __shfl_down(tmid, 1, 64);
+            R xm[3], xp[3], km[3], kp[3];
+#pragma unroll
+            for (int f = 0; f < 3; f++) {
+                hi[f] = F[f][a + dimz]; xm[f] = F[f][a - plane]; xp[f] = F[f][a + plane];
+                km[f] = __shfl_up(mid[f], 1, 64); kp[f] = __shfl_down(mid[f], 1, 64);
+            }
+            if (lane == 0 && kc > 0) {
+                tkm = type_at(a - 1);
+#pragma unroll
+                for (int f = 0; f < 3; f++) km[f] = F[f][a - 1];
+            }
+            if (lane == 63 && kc < dimz - 1) {
+                tkp = type_at(a + 1);
+#pragma unroll
+                for (int f = 0; f < 3; f++) kp[f] = F[f][a + 1];
+            }
+            if (kin && tmid == FS3D_NODE_IN && tlo != FS3D_NODE_OUT && thi != FS3D_NODE_OUT && txm != FS3D_NODE_OUT &&
+                txp != FS3D_NODE_OUT && tkm != FS3D_NODE_OUT && tkp != FS3D_NODE_OUT) {
+                R g[3][3];
+#pragma unroll
+                for (int f = 0; f < 3; f++) {
+                    g[f][0] = (xp[f] - xm[f]) / two_dx; g[f][1] = (hi[f] - lo[f]) / two_dy; g[f][2] = (kp[f] - km[f]) / two_dz;
+                }
+                R div, q, ss;
+                fs3d_invariants(g, div, q, ss);
+                cnt[a] += 1u;
+                double *const p = gs + a;
+                p[0] = p[0] + (double)div;
+                p[sstride] = p[sstride] + (double)q;
+                p[2 * sstride] = p[2 * sstride] + (double)ss;
+            }
+            tlo = tmid; tmid = thi;
+#pragma unroll
+            for (int f = 0; f < 3; f++) { lo[f] = mid[f]; mid[f] = hi[f]; }
+        }
+    }
+}
+
+// FS3D_OPT_OUTPUT_GRADIENT 2: the time means of div, Q and S:S into the fields U, V, W of a statistic layer, (R)(G / (double)ng)
+// where ng >= 1 and 0 elsewhere; one cell per thread
+template <typename R>
+__global__ void __launch_bounds__(256) k_time_grad_layer(long long ncell, const unsigned *__restrict__ cnt, const double *__restrict__ gs,
+                                                          long long sstride, R *__restrict__ q, long long qstride)
+{
+    const long long l = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (l >= ncell) return;
+    const unsigned n = cnt[l];
+    const double dn = (double)n;
+#pragma unroll
+    for (int v = 0; v < 3; v++) q[v * qstride + l] = n ? (R)(gs[v * sstride + l] / dn) : R(0);
+}
+
 static bool aligned(const void *p, size_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
 
 template <typename R, int MODE>
@@ -203,10 +292,38 @@ static void launch_accumulate(fs3d_ctx *c)
     }
 }
 
+// FS3D_OPT_TIME_STATS_GRAD: the gradient sums of one accumulated step.  `fresh`: the step opens the window.  The two buffers are
+// allocated by the first accumulation that needs them and kept; a grid without an interior cell launches nothing
+static fs3d_status accumulate_gradients(fs3d_ctx *c, bool fresh)
+{
+    const size_t nbytes = (size_t)c->ts_stride * sizeof(unsigned), gbytes = (size_t)3 * c->ts_stride * sizeof(double);
+    const bool held = c->tg_n.raw() && c->tg_g.raw();
+    BUFCHK(c, c->tg_n.reserve(nbytes, &c->geom_allocs));
+    BUFCHK(c, c->tg_g.reserve(gbytes, &c->geom_allocs));
+    if (fresh || !held) {
+        HIPCHK(c, hipMemsetAsync(c->tg_n, 0, nbytes, c->stream));
+        HIPCHK(c, hipMemsetAsync(c->tg_g, 0, gbytes, c->stream));
+    }
+    if (c->dimx < 3 || c->dimy < 3 || c->dimz < 3) return FS3D_OK;
+    const int nj = (c->dimy - 2 + TG_JS - 1) / TG_JS;
+    const long long blocks = (long long)(c->dimx - 2) * nj;
+    if (blocks >= (1LL << 31)) return fail(c, FS3D_ERR_UNSUPPORTED, "FS3D_OPT_TIME_STATS_GRAD: 2^31 row tiles or more");
+    auto launch = [&](auto r) {
+        using R = decltype(r);
+        hipLaunchKernelGGL((k_time_grad<R>), dim3((unsigned)blocks), dim3(256), 0, c->stream, (const uint16_t *)c->code,
+                           (const R *)c->lay[c->slot[FS3D_LAYER_CUR]] + c->plane, c->fstride, c->dimy, c->dimz, nj,
+                           R(2) * (R)c->gdx, R(2) * (R)c->gdy, R(2) * (R)c->gdz, (unsigned *)c->tg_n, (double *)c->tg_g, c->ts_stride);
+    };
+    if (c->prec == FS3D_F32) launch(0.0f); else launch(0.0);
+    HIPCHK(c, hipGetLastError());
+    return FS3D_OK;
+}
+
 fs3d_status fs3d_time_stats_accumulate(fs3d_ctx *c)
 {
     // FS3D_OPT_TIME_STATS_EVERY: candidate s = 1, 2, .. of the window is taken where (s - 1) % k == 0; on the others nothing runs
     if (c->ts_candidates++ % c->opt_ts_every) return FS3D_OK;
+    const bool fresh = c->ts_clear;
     const int mode = c->opt_time_stats;
     const bool cross = mode == 2 && c->opt_ts_cross;
     const size_t sbytes = (size_t)4 * c->ts_stride * sizeof(double), xbytes = (size_t)6 * c->ts_stride * sizeof(double);
@@ -227,6 +344,7 @@ fs3d_status fs3d_time_stats_accumulate(fs3d_ctx *c)
     else { if (cross) launch_accumulate<double, 3>(c); else if (mode == 2) launch_accumulate<double, 2>(c); else launch_accumulate<double, 1>(c); }
     HIPCHK(c, hipGetLastError());
     c->ts_steps++;
+    if (c->opt_ts_grad) return accumulate_gradients(c, fresh);      // behind the step and the sums above; a failure is the step's status, the step stands
     return FS3D_OK;
 }
 
@@ -252,10 +370,26 @@ fs3d_status fs3d_time_stats_layer(fs3d_ctx *c, int source, int moment, void *q_o
     return FS3D_OK;
 }
 
+fs3d_status fs3d_time_stats_grad_layer(fs3d_ctx *c, void *q, long long qstride)
+{
+    const unsigned blocks = (unsigned)((c->ncell + 255) / 256);
+    if (c->prec == FS3D_F32)
+        hipLaunchKernelGGL((k_time_grad_layer<float>), dim3(blocks), dim3(256), 0, c->stream, c->ncell, (const unsigned *)c->tg_n,
+                           (const double *)c->tg_g, c->ts_stride, (float *)q, qstride);
+    else
+        hipLaunchKernelGGL((k_time_grad_layer<double>), dim3(blocks), dim3(256), 0, c->stream, c->ncell, (const unsigned *)c->tg_n,
+                           (const double *)c->tg_g, c->ts_stride, (double *)q, qstride);
+    HIPCHK(c, hipGetLastError());
+    return FS3D_OK;
+}
+
 void fs3d_time_stats_free(fs3d_ctx *c)
 {
     c->ts_n.reset(&c->geom_allocs); c->ts_s1.reset(&c->geom_allocs); c->ts_s2.reset(&c->geom_allocs);
     fs3d_time_stats_free_cross(c);
+    fs3d_time_stats_free_grad(c);
 }
+
+void fs3d_time_stats_free_grad(fs3d_ctx *c) { c->tg_n.reset(&c->geom_allocs); c->tg_g.reset(&c->geom_allocs); }
 
 void fs3d_time_stats_free_cross(fs3d_ctx *c) { c->ts_sx.reset(&c->geom_allocs); }

@@ -149,6 +149,15 @@ public:
     // FS3D_OPT_OUTPUT_VECTOR for the same calls: 0 resVel holds the velocity, 1 the vorticity (central differences on the NODE_IN
     // cells whose six neighbours are no NODE_OUT cells, 99999 on NODE_OUT cells, 0 elsewhere); slab solvers throw as above
     void SetOutputVector(int mode) { chk(fs3d_set_option(ctx_, FS3D_OPT_OUTPUT_VECTOR, mode)); }
+    // FS3D_OPT_OUTPUT_GRADIENT for the same calls: 1 resVel holds the invariants of the velocity gradient of the sampled layer --
+    // div u, the Q criterion and the strain rate S:S, on the cells that carry a vorticity, 99999 on NODE_OUT cells, 0 elsewhere --,
+    // accepted and refused where SetOutputVector(1) is; 2 their time mean (needs SetOutputSource(1) and a window accumulated with
+    // SetTimeStatsGradients(1)); 0 off.  With SetOutputVector(1) as well the calls throw (FS3D_ERR_INVALID)
+    void SetOutputGradient(int mode) { chk(fs3d_set_option(ctx_, FS3D_OPT_OUTPUT_GRADIENT, mode)); }
+    // FS3D_OPT_TIME_STATS_GRAD: 1 -- with SetTimeStats(1 or 2) every accumulated step also adds div u, Q and S:S of its result to
+    // per-cell sums (the cells that carry them at that step), 0 -- off, those sums are freed.  EVERY call opens a new window.  A
+    // single-GPU solver only: a slab solver throws (FS3D_ERR_UNSUPPORTED)
+    void SetTimeStatsGradients(int on) { chk(fs3d_set_option(ctx_, FS3D_OPT_TIME_STATS_GRAD, on)); }
     // FS3D_OPT_TIME_STATS: 1 -- from now on every TimeStep that succeeds adds its result to per-cell sums on the device (the cells
     // that are NODE_IN at that step), 2 -- and its squares, 0 -- off, the sums are freed.  EVERY call opens a new window.  Works on
     // a slab solver as on a single one (a cell asks nothing of a neighbour)

@@ -1,5 +1,5 @@
 """Filtered and derived result records: what fs3d_get_layer, fs3d_get_layer_rows and fs3d_get_layer_dev return while
-FS3D_OPT_OUTPUT_FILTER or FS3D_OPT_OUTPUT_VECTOR is set.
+FS3D_OPT_OUTPUT_FILTER, FS3D_OPT_OUTPUT_VECTOR or FS3D_OPT_OUTPUT_GRADIENT is set.
 
 layer_output is the definition of the rule; k_get_layer_box (csrc/kernels_output.hip) is held to it -- bit for bit wherever the double
 sums are exact, to the rounding of one sum elsewhere.  The reference has no counterpart: its FilterToArrays (TimeLayer3D.h:819-924)
@@ -18,6 +18,21 @@ every operation rounded in R, two_dx = R(2) * R(dx):
 on a NODE_IN cell whose six neighbours are inside the grid and not NODE_OUT (an OUT neighbour holds the stamp, not a velocity);
 (99999, 99999, 99999) on a NODE_OUT cell, so the missing-value marker survives; (0, 0, 0) on every other cell.
 
+vector INVARIANTS (FS3D_OPT_OUTPUT_GRADIENT 1; the constant is that option's id, 20: `vector` 2 stays refused here as
+FS3D_OPT_OUTPUT_VECTOR 2 is by the library): the invariants of the velocity gradient, (a, b, c) = (div, Q, S:S), on the cells that carry a
+vorticity (curl_defined, unchanged); 99999 and 0 elsewhere as above.  With a over the fields U, V, W (indices x, y, z), b over the
+axes and h = R(0.5), every operation rounded once in R, in this order, nothing fused:
+  g_ab = (u_a[b+1] - u_a[b-1]) / two_db                                  nine quotients
+  div  = (g_xx + g_yy) + g_zz
+  s_xy = h*(g_xy + g_yx)   s_xz = h*(g_xz + g_zx)   s_yz = h*(g_yz + g_zy)
+  o_xy = h*(g_xy - g_yx)   o_xz = h*(g_xz - g_zx)   o_yz = h*(g_yz - g_zy)
+  SS   = ((g_xx*g_xx + g_yy*g_yy) + g_zz*g_zz) + R(2)*((s_xy*s_xy + s_xz*s_xz) + s_yz*s_yz)       S:S, the strain rate (2 nu S:S is the dissipation)
+  OO   = R(2)*((o_xy*o_xy + o_xz*o_xz) + o_yz*o_yz)                                                the rotation rate
+  Q    = h*(OO - SS)                                                                               positive inside a vortex
+A rigid rotation of rate w gives (0, w^2, 0), a plane shear of rate w (0, 0, w^2 / 2), a plane stretch (0, -w^2, 2 w^2), a uniform
+dilatation of rate w (3 w, -3 w^2 / 2, 3 w^2).  On integer fields of magnitude up to 63 with power-of-two spacings every operation
+is exact in fp32, so fp32 and fp64 agree value for value.
+
 filter 0: the sample is q of the cell (lo_x, lo_y, lo_z).
 filter 1: with C the NODE_IN cells of the sample's box -- C empty: filter 0's sample (a wall value or 99999); else per quantity
 m = (sum over C of (double)q) / (double)|C|, the sum in double in any order, one double division; outT = m and each outV component
@@ -33,7 +48,8 @@ from .grids import NODE_IN, NODE_OUT
 
 MISSING_VALUE = 99999.0
 POINT, BOX = 0, 1
-VELOCITY, VORTICITY = 0, 1
+VELOCITY, VORTICITY = 0, 1                                # the values of FS3D_OPT_OUTPUT_VECTOR
+INVARIANTS = 20                                           # FS3D_OPT_OUTPUT_GRADIENT 1, which claims outV in the vector option's place
 
 
 def boxes(g, o):
@@ -90,16 +106,49 @@ def vorticity(type, fields, spacing):
     return res
 
 
+def invariants(type, fields, spacing):
+    """(div, Q, S:S) per cell as the rule gives them, in the fields' dtype; fields are the stamped U, V, W(, T)."""
+    F = fields[:3]
+    R = F[0].dtype.type
+    two = [R(2) * R(d) for d in spacing]
+    c = (slice(1, -1),) * 3
+    h = R(0.5)
+
+    def g(a, b):                                          # (u_a[b+1] - u_a[b-1]) / two_db, on the interior
+        hi = [slice(1, -1)] * 3
+        lo = [slice(1, -1)] * 3
+        hi[b], lo[b] = slice(2, None), slice(None, -2)
+        return (F[a][tuple(hi)] - F[a][tuple(lo)]) / two[b]
+    with np.errstate(all="ignore"):                       # differences against the stamp are computed and thrown away
+        gxx, gxy, gxz, gyx, gyy, gyz, gzx, gzy, gzz = [g(a, b) for a in range(3) for b in range(3)]
+        div = (gxx + gyy) + gzz
+        sxy, sxz, syz = h * (gxy + gyx), h * (gxz + gzx), h * (gyz + gzy)
+        oxy, oxz, oyz = h * (gxy - gyx), h * (gxz - gzx), h * (gyz - gzy)
+        SS = ((gxx * gxx + gyy * gyy) + gzz * gzz) + R(2) * ((sxy * sxy + sxz * sxz) + syz * syz)
+        OO = R(2) * ((oxy * oxy + oxz * oxz) + oyz * oyz)
+        Q = h * (OO - SS)
+    ok = curl_defined(type)
+    out_cells = np.asarray(type) == NODE_OUT
+    res = []
+    for comp in (div, Q, SS):
+        assert comp.dtype == F[0].dtype
+        full = np.zeros(F[0].shape, F[0].dtype)
+        full[c] = np.where(ok[c], comp, R(0))
+        full[out_cells] = R(MISSING_VALUE)
+        res.append(full)
+    return res
+
+
 def cell_quantities(type, fields, vector=VELOCITY, spacing=None):
     """q = (a, b, c, T) per cell from the fields as they are before the call (the stamp is applied here)."""
     st = stamp(type, fields)
     if vector == VELOCITY:
         return st
-    if vector != VORTICITY:
-        raise ValueError("vector is 0 (velocity) or 1 (vorticity)")
+    if vector not in (VORTICITY, INVARIANTS):
+        raise ValueError("vector is 0 (velocity), 1 (vorticity) or INVARIANTS (the velocity-gradient invariants)")
     if spacing is None:
-        raise ValueError("the vorticity needs the grid's spacing (dx, dy, dz)")
-    return vorticity(type, st, spacing) + [st[3]]
+        raise ValueError("the vorticity and the invariants need the grid's spacing (dx, dy, dz)")
+    return (vorticity if vector == VORTICITY else invariants)(type, st, spacing) + [st[3]]
 
 
 def layer_output(type, fields, outdims=(0, 0, 0), filter=POINT, vector=VELOCITY, spacing=None, exact_sum=False):

@@ -19,6 +19,16 @@ moment -- on the NODE_IN cells only:
 and the window's step count N += 1.  The product is rounded once, the addition once.  Cells are counted by the type they have at
 each step: a geometry may move inside a window.
 
+Gradient sums (FS3D_OPT_TIME_STATS_GRAD 1; TimeStats(gradients=True, spacing=...)): every accumulated step also evaluates the
+invariants of the velocity gradient, layer_output.invariants, on FS3D_LAYER_CUR -- (div, Q, S:S) in R, from a cell's six neighbours
+-- and on the cells that carry them in the geometry of that moment (layer_output.curl_defined):
+    ng += 1         (uint32)
+    G_div += double(div),  G_Q += double(Q),  G_SS += double(SS)      each addition rounded once
+They are quadratic in the gradient, so the time mean of S:S is not S:S of the mean field: it has to be summed step by step.
+Whole-grid contexts only.  Every set of the option opens a new window.
+Read-out (FS3D_OPT_OUTPUT_GRADIENT 2 with source 1; gradient_layer): Q_U, Q_V, Q_W = R(G_div / double(ng)), R(G_Q / double(ng)),
+R(G_SS / double(ng)) where ng >= 1 and R(0) where ng = 0; Q_T is source 1's.  The record rule then runs on Q as a velocity layer.
+
 Read-out, per cell, all in double, each operation rounded once; R is the fields' type:
     n >= 1:  dn = double(n), m_a = S1_a / dn
         source 1, mean            Q = R(m)
@@ -44,11 +54,12 @@ covariance carries the same caveat: S_ab / n and m_a * m_b cancel where the mean
 error about 2 u |m_a m_b|), it is not clamped, and it is exactly 0 for two constant fields whose product is exact in double (every
 pair of fp32 values) as long as n * x_a, n * x_b and n * x_a * x_b are exact.
 
-Not provided: third moments, covariances with the vorticity, a history of cells that are NODE_OUT now, the 2D solver.
+Not provided: third moments, covariances with the vorticity, second moments of the invariants, gradient sums on x-slabs, a history of cells that are NODE_OUT now, the 2D solver.
 """
 import numpy as np
 
 from .grids import NODE_IN
+from .layer_output import curl_defined, invariants
 
 MEAN, VARIANCE, FRACTION = 1, 2, 3
 SOURCES = {"next": 0, "mean": MEAN, "variance": VARIANCE, "fraction": FRACTION}
@@ -61,12 +72,15 @@ class TimeStats:
     """One window.  mode 1: first moments; mode 2: first and second moments; cross (mode 2 only, without effect in mode 1): the six
     cross sums as well; every: the stride of the accumulated steps."""
 
-    def __init__(self, shape, mode=2, cross=False, every=1):
+    def __init__(self, shape, mode=2, cross=False, every=1, gradients=False, spacing=None):
         if mode not in (1, 2):
             raise ValueError("mode is 1 (first moments) or 2 (first and second moments)")
         if int(every) != every or not 1 <= every <= MAX_EVERY:
             raise ValueError("every is an integer from 1 to 2^20")
+        if gradients and spacing is None:
+            raise ValueError("the gradient sums need the grid's spacing (dx, dy, dz)")
         self.shape, self.mode, self.cross, self.every = tuple(shape), mode, bool(cross) and mode == 2, int(every)
+        self.gradients, self.spacing = bool(gradients), None if spacing is None else tuple(spacing)
         self.reset()
 
     def reset(self):
@@ -78,6 +92,8 @@ class TimeStats:
         self.S1 = [np.zeros(self.shape, np.float64) for _ in range(4)]
         self.S2 = [np.zeros(self.shape, np.float64) for _ in range(4)] if self.mode == 2 else None
         self.SX = [np.zeros(self.shape, np.float64) for _ in PAIRS] if self.cross else None
+        self.ng = np.zeros(self.shape, np.uint32) if self.gradients else None
+        self.G = [np.zeros(self.shape, np.float64) for _ in range(3)] if self.gradients else None      # div, Q, S:S
 
     def add(self, fields, types):
         """One candidate step: fields = U, V, W, T of `cur` after the step, types = the node types of that moment.  Returns whether
@@ -97,8 +113,32 @@ class TimeStats:
             if self.cross:
                 for p, (a, b) in enumerate(PAIRS):
                     self.SX[p][fluid] = self.SX[p][fluid] + x[a] * x[b]
+            if self.gradients:
+                ok = curl_defined(types)
+                inv = invariants(types, [np.asarray(f) for f in fields[:3]], self.spacing)
+                self.ng[ok] += np.uint32(1)
+                for v in range(3):
+                    self.G[v][ok] = self.G[v][ok] + inv[v][ok].astype(np.float64)
         self.N += 1
         return True
+
+    def gradient_layer(self, cur_fields):
+        """Q of FS3D_OPT_OUTPUT_GRADIENT 2: the time means of div, Q and S:S in place of U, V, W (0 where ng = 0) and source 1's T,
+        four arrays of cur_fields' dtype, before the 99999 stamp"""
+        if not self.gradients:
+            raise ValueError("the window holds no gradient sums")
+        if self.N == 0:
+            raise ValueError("the window holds no step")
+        R = np.asarray(cur_fields[0]).dtype
+        seen = self.ng >= 1
+        dn = self.ng[seen].astype(np.float64)
+        out = []
+        with np.errstate(all="ignore"):
+            for v in range(3):
+                q = np.zeros(self.shape, R)
+                q[seen] = (self.G[v][seen] / dn).astype(R)
+                out.append(q)
+        return out + [self.layer(MEAN, cur_fields)[3]]
 
     def layer(self, source, cur_fields, moment=0):
         """Q of `source` (1 mean, 2 second moments, 3 fluid fraction): four arrays of cur_fields' dtype, before the 99999 stamp.

@@ -148,6 +148,30 @@ enum {
                                  Still refused with FS3D_ERR_UNSUPPORTED before any launch and any word to a peer: a lone slab of a larger
                                  grid in no group, and fs3d_get_layer on any slab (it samples the slab's own planes and stays
                                  non-collective).  Any other value: FS3D_ERR_INVALID */
+    FS3D_OPT_OUTPUT_GRADIENT = 20, /* what outV of fs3d_get_layer, fs3d_get_layer_rows and fs3d_get_layer_dev holds, beside
+                                 FS3D_OPT_OUTPUT_VECTOR; outT is the temperature either way.  0 (default): nothing changes anywhere, no
+                                 launch differs.  1: the invariants of the velocity gradient of the sampled layer (`next`, or the statistic
+                                 layer FS3D_OPT_OUTPUT_SOURCE names) in place of the velocity -- (div u, Q, S:S), central differences on the
+                                 cells that carry a vorticity, 99999 on NODE_OUT cells, 0 elsewhere (the GetLayer section below).  Accepted
+                                 and refused exactly where FS3D_OPT_OUTPUT_VECTOR 1 is, with the same statuses: it combines with either
+                                 filter, is refused on an x-slab or group member unless FS3D_OPT_OUTPUT_SLABS is 1 (then the same
+                                 collective call as the curl), by fs3d_get_layer on any slab, on a lone slab in no group, and with
+                                 FS3D_OPT_OUTPUT_MOMENT 1 or 2 under source 2.  2: the time mean of the invariants from the gradient sums
+                                 of FS3D_OPT_TIME_STATS_GRAD (the time-statistics section below); needs FS3D_OPT_OUTPUT_SOURCE 1 and an open
+                                 window with those sums and an accumulated step, else the three entries return FS3D_ERR_INVALID before any
+                                 launch.  1 or 2 while FS3D_OPT_OUTPUT_VECTOR is 1: the three entries return FS3D_ERR_INVALID (two options
+                                 claim outV); fs3d_set_option accepts the two in either order.  Any other value: FS3D_ERR_INVALID, the
+                                 option stays as it was */
+    FS3D_OPT_TIME_STATS_GRAD = 21, /* 0 (default): nothing changes anywhere and nothing is allocated.  1: while FS3D_OPT_TIME_STATS is 1 or
+                                 2, every accumulated step also enqueues one kernel, behind the step and the accumulation of the fields,
+                                 that evaluates the invariants (div u, Q, S:S) of the velocity gradient of the new FS3D_LAYER_CUR on the
+                                 cells that carry them and adds them to three per-cell double sums, with a per-cell count (28 bytes per
+                                 own cell in two buffers; the time-statistics section below).  EVERY call with this option opens a new
+                                 window; setting 0 also frees the gradient sums.  Whole-grid contexts only: on an x-slab (x_offset != 0 or
+                                 dimx != dimx_global) the value 1 returns FS3D_ERR_UNSUPPORTED, and on a member of a group of more than one
+                                 rank fs3d_time_step / fs3d_time_step_async return FS3D_ERR_UNSUPPORTED before any launch, without a swap
+                                 and without counting a candidate, while this option and the mode are on.  Any other value:
+                                 FS3D_ERR_INVALID */
     FS3D_OPT_ERR_ORDER = 7   /* summation order of EvalDivError (fs3d_eval_div_error, fs3d_time_step with compute_error).  0 (default): the
                                  per-cell terms are summed in parallel (per workgroup, then over the workgroups; deterministic, equal to the
                                  CPU path to ~1e-12 relative).  1: they are summed one after the other in cell order, as the loop of
@@ -487,7 +511,7 @@ fs3d_status fs3d_last_update_device_ms(fs3d_ctx *ctx, float *ms_out);
  * counts X, Y, Z; [3] BOUND / VALVE cells; [4] NODE_IN cells on no segment of some direction; [5..7] dead lines X, Y, Z;
  * [8..9] shared-column groups flagged uniform in X, Y; [10..11] distinct shared columns in X, Y; [12] an order-independent
  * 64-bit digest of the cell-code table (sum over cells of a mix of cell index and code), computed on the device from the
- * table the sweeps read; [13] the number of device allocations and frees fs3d_upload_nodes / fs3d_update_nodes* / fs3d_fill_fresh_cells* and the accumulators of FS3D_OPT_TIME_STATS (the cross sums of FS3D_OPT_TIME_STATS_CROSS among them) have made
+ * table the sweeps read; [13] the number of device allocations and frees fs3d_upload_nodes / fs3d_update_nodes* / fs3d_fill_fresh_cells* and the accumulators of FS3D_OPT_TIME_STATS (the cross sums of FS3D_OPT_TIME_STATS_CROSS and the gradient sums of FS3D_OPT_TIME_STATS_GRAD among them) have made
  * since the context was created (the one entry that describes the path taken, not the tables).
  * Measurement and test aid; no reference counterpart. */
 #define FS3D_N_GEOM_INFO 14
@@ -565,7 +589,7 @@ fs3d_status fs3d_get_layer(fs3d_ctx *ctx, void *outV, double *outT,
  * All three entries stamp `next` first and over all owned cells, refuse before any launch (NULL context, destination or rows,
  * negative dims, no nodes yet: FS3D_ERR_INVALID, the context stays usable) and report pending device errors.
  *
- * Filtered and derived records (FS3D_OPT_OUTPUT_FILTER, FS3D_OPT_OUTPUT_VECTOR; no reference counterpart; the rule and its numpy
+ * Filtered and derived records (FS3D_OPT_OUTPUT_FILTER, FS3D_OPT_OUTPUT_VECTOR, FS3D_OPT_OUTPUT_GRADIENT; no reference counterpart; the rule and its numpy
  * twin: cmc_fluid_solver_amd/layer_output.py).  With either option non-zero the three entries run k_get_layer_box
  * (csrc/kernels_output.hip) in place of the gather, behind the same stamp, through the same staging buffer and copies: `next` is left as a default call leaves it.
  * The box of output index i on an axis of g source cells and o samples is [lo, hi), lo = i*g/o, hi = max(lo + 1, (i+1)*g/o) in
@@ -576,7 +600,20 @@ fs3d_status fs3d_get_layer(fs3d_ctx *ctx, void *outV, double *outT,
  *   wy = (U[k+1] - U[k-1]) / two_dz - (W[i+1] - W[i-1]) / two_dx
  *   wz = (V[i+1] - V[i-1]) / two_dx - (U[j+1] - U[j-1]) / two_dy
  * on a NODE_IN cell whose six neighbours are inside the grid and not NODE_OUT (their fields hold the stamp); (99999, 99999, 99999)
- * on a NODE_OUT cell; (0, 0, 0) on every other cell.  Filter 0: the sample is q of the cell (lo_x, lo_y, lo_z).  Filter 1: with C
+ * on a NODE_OUT cell; (0, 0, 0) on every other cell.  With FS3D_OPT_OUTPUT_GRADIENT set to 1 (a, b, c) is (div, Q, SS), the
+ * invariants of the velocity gradient, on the same cells and with the same values elsewhere.  With a over the fields U, V, W
+ * (indices x, y, z), b over the axes and h = R(0.5), every operation rounded once in R, in this order, nothing fused:
+ *   g_ab = (u_a[b+1] - u_a[b-1]) / two_db                                   nine quotients
+ *   div  = (g_xx + g_yy) + g_zz
+ *   s_xy = h*(g_xy + g_yx)   s_xz = h*(g_xz + g_zx)   s_yz = h*(g_yz + g_zy)
+ *   o_xy = h*(g_xy - g_yx)   o_xz = h*(g_xz - g_zx)   o_yz = h*(g_yz - g_zy)
+ *   SS   = ((g_xx*g_xx + g_yy*g_yy) + g_zz*g_zz) + R(2)*((s_xy*s_xy + s_xz*s_xz) + s_yz*s_yz)      S:S (2 nu S:S is the dissipation)
+ *   OO   = R(2)*((o_xy*o_xy + o_xz*o_xz) + o_yz*o_yz)
+ *   Q    = h*(OO - SS)                                                                              positive inside a vortex
+ * Everything said of the vector option below holds for FS3D_OPT_OUTPUT_GRADIENT 1 as well: the slab refusals, and with
+ * FS3D_OPT_OUTPUT_SLABS the same collective call with the same one ghost plane and type plane per neighbour.  The two options
+ * exclude each other: with both non-zero the three entries return FS3D_ERR_INVALID before any launch.
+ * Filter 0: the sample is q of the cell (lo_x, lo_y, lo_z).  Filter 1: with C
  * the NODE_IN cells of the sample's box, the sample is filter 0's where C is empty (a wall value or 99999: walls and the outside
  * show only where a box holds no fluid); else each quantity is m = (sum over C of (double)q) / (double)|C|, summed in double in an
  * unspecified order, one double division; outT = m, each outV component is m rounded once to R.  With every o >= g filter 1 equals
@@ -616,8 +653,8 @@ fs3d_status fs3d_get_layer(fs3d_ctx *ctx, void *outV, double *outT,
  * slab of a larger grid in no group, and fs3d_get_layer on any slab.  The FS3D_ERR_INVALID refusals of the time statistics come
  * before any exchange too.  Between devices and over RCCL the path is compiled and has not been run.
  *
- * Time statistics (FS3D_OPT_TIME_STATS, FS3D_OPT_TIME_STATS_CROSS, FS3D_OPT_TIME_STATS_EVERY, FS3D_OPT_OUTPUT_SOURCE,
- * FS3D_OPT_OUTPUT_MOMENT; no reference counterpart; the rule and its numpy twin: cmc_fluid_solver_amd/time_stats.py).  While
+ * Time statistics (FS3D_OPT_TIME_STATS, FS3D_OPT_TIME_STATS_CROSS, FS3D_OPT_TIME_STATS_EVERY, FS3D_OPT_TIME_STATS_GRAD,
+ * FS3D_OPT_OUTPUT_SOURCE, FS3D_OPT_OUTPUT_MOMENT, FS3D_OPT_OUTPUT_GRADIENT 2; no reference counterpart; the rule and its numpy twin: cmc_fluid_solver_amd/time_stats.py).  While
  * FS3D_OPT_TIME_STATS is 1 or 2, every fs3d_time_step that returns FS3D_OK and every fs3d_time_step_async is a CANDIDATE step of the
  * open window, counted s = 1, 2, ..; a step that returns FS3D_ERR_DIVERGED does not swap and is no candidate.  With k the value of
  * FS3D_OPT_TIME_STATS_EVERY (default 1), candidate s is ACCUMULATED if and only if (s - 1) % k is 0: the first step of a window always
@@ -631,7 +668,23 @@ fs3d_status fs3d_get_layer(fs3d_ctx *ctx, void *outV, double *outT,
  * one: N and the per-cell n count accumulated steps only, and the fluid fraction stays n / N.  The geometry may change inside a
  * window (fs3d_update_nodes*, fs3d_upload_nodes): a cell is counted by the type it has at each accumulated step, which is what the
  * per-cell n is for.  While the mode is 0 or 1 the CROSS option has no effect.
- *  - the window: every fs3d_set_option of FS3D_OPT_TIME_STATS, FS3D_OPT_TIME_STATS_CROSS or FS3D_OPT_TIME_STATS_EVERY opens a new
+ *  - gradient sums (FS3D_OPT_TIME_STATS_GRAD set to 1, whole-grid contexts only): every accumulated step enqueues one more kernel
+ *    behind the one above, over the context's own cells.  On each cell that carries invariants in the geometry of that moment
+ *    (NODE_IN, the six neighbours inside the grid and not NODE_OUT), with (div, Q, SS) the R values of the GetLayer section's rule
+ *    on FS3D_LAYER_CUR after the swap:  ng += 1 (uint32),  G_div += (double)div,  G_Q += (double)Q,  G_SS += (double)SS,  each
+ *    addition rounded once in double.  The invariants are quadratic in the gradient, so their time mean cannot be had from the
+ *    mean field.  28 bytes per own cell in two buffers (the counts; the three sums), allocated by the first accumulation that
+ *    needs them, kept over windows, counted in fs3d_geometry_info entry 13, freed by setting this option or FS3D_OPT_TIME_STATS
+ *    to 0 (after a stream synchronise) and by fs3d_destroy.  The refusals on slabs and group members: the option's entry above.
+ *    Read-out, FS3D_OPT_OUTPUT_GRADIENT 2 with FS3D_OPT_OUTPUT_SOURCE 1: the statistic layer is
+ *      Q_U, Q_V, Q_W = (R)(G_div / (double)ng), (R)(G_Q / (double)ng), (R)(G_SS / (double)ng)  where ng >= 1, R(0) where ng = 0,
+ *      Q_T = source 1's (the mean of T, or `cur` where n = 0),
+ *    and the call then runs unchanged on Q as a velocity layer: the stamp on the cells that are NODE_OUT now, the gather or the
+ *    box mean, staging, copies, rows, fs3d_get_layer_info.  Refused with FS3D_ERR_INVALID before any launch, destinations, rows
+ *    and layers untouched: a source other than 1, FS3D_OPT_TIME_STATS at 0, FS3D_OPT_TIME_STATS_GRAD at 0 in the open window, a
+ *    window without an accumulated step, and FS3D_OPT_OUTPUT_VECTOR 1.
+ *  - the window: every fs3d_set_option of FS3D_OPT_TIME_STATS, FS3D_OPT_TIME_STATS_CROSS, FS3D_OPT_TIME_STATS_EVERY or
+ *    FS3D_OPT_TIME_STATS_GRAD opens a new
  *    one, N = 0, no candidate yet and all sums zero, whatever the value was.
  *  - memory: 4 + 32 (mode 2: 64; with the cross sums: 112) bytes per own cell, no ghost planes.  Each buffer is allocated by the first
  *    accumulation that needs it (a failed allocation is that step's status: the step itself stands, nothing was accumulated), kept
@@ -661,13 +714,15 @@ fs3d_status fs3d_get_layer(fs3d_ctx *ctx, void *outV, double *outT,
  *  - refusals, FS3D_ERR_INVALID before any launch with the destinations, rows and layers untouched: a source the current
  *    FS3D_OPT_TIME_STATS mode does not hold (any source at 0, source 2 at 1); source 2 with moment 1 or 2 while the open window holds
  *    no cross sums (FS3D_OPT_TIME_STATS_CROSS is 0, or the mode is below 2); moment 1 or 2 with source 2 and FS3D_OPT_OUTPUT_VECTOR 1
- *    (the curl of a stress layer means nothing); and a window without an accumulated step (N = 0).  The slab refusal of the filter
+ *    (the curl of a stress layer means nothing) or FS3D_OPT_OUTPUT_GRADIENT 1; and a window without an accumulated step (N = 0).  The slab refusal of the filter
  *    and vector options stands while FS3D_OPT_OUTPUT_SLABS is 0; without them an x-slab or group member accumulates and reads out
  *    its own planes -- every layer is per cell --, and the rows the slabs write are those of the global record a single context
  *    gives.  With FS3D_OPT_OUTPUT_SLABS at 1 on a group every source combines with the filter and the curl as on one GPU, as the
  *    collective call described above; Q then carries a ghost plane on either side (two more planes per field), and the refusals of
  *    this list come before any exchange.
- *  - not provided: third moments; covariances with the vorticity; a history of the cells that are NODE_OUT now (they are stamped
+ *  - not provided: third moments; covariances with the vorticity; second moments of the invariants; gradient sums on x-slabs (they
+ *    need an exchange of the ghost planes of `cur` per accumulated step, a collective of their own); lambda_2, the eigenvalues
+ *    and the nine components of the gradient; a history of the cells that are NODE_OUT now (they are stamped
  *    as in every record); the 2D solver. */
 fs3d_status fs3d_get_layer_rows(fs3d_ctx *ctx, void *outV, double *outT, int outdimx, int outdimy, int outdimz, int rows[2]);
 /* fs3d_get_layer_rows (Solver3D.cpp:21-25, TimeLayer3D.h:819-924) with the two arrays on the context's DEVICE: the kernel

@@ -1,4 +1,4 @@
-"""What the filtered and derived result records cost (FS3D_OPT_OUTPUT_FILTER, FS3D_OPT_OUTPUT_VECTOR; k_get_layer_box), fp32, one GPU.
+"""What the filtered and derived result records cost (FS3D_OPT_OUTPUT_FILTER, FS3D_OPT_OUTPUT_VECTOR, FS3D_OPT_OUTPUT_GRADIENT; k_get_layer_box), fp32, one GPU.
 
   python tools/output_filter_cost.py --parent-lib DIR/libfs3d_hip.so [--out FILE]        -> profiles/output_filter_cost.json
 
@@ -8,12 +8,15 @@
     this tree's first.  Verdict per shape, the rule of profiles/voxel_rule_shared_cost.txt, set before the run: the median of this
     tree's process medians is no larger than the largest of the parent's process medians.  The records of the two must be the same bytes.
 (b) what a filtered record costs.  One child of this tree's library per grid makes, mode after mode -- default, box mean, point
-    vorticity, box-mean vorticity -- 3 warm-up calls and `--repeats` timed ones (host clock).  A second child does the same under
+    vorticity, box-mean vorticity, point invariants, box-mean invariants (FS3D_OPT_OUTPUT_GRADIENT 1) -- 3 warm-up calls and `--repeats` timed ones (host clock).  A second child does the same under
     `rocprofv3 --kernel-trace` (alone: no counters, no other tracing): the device duration of every k_clear_type and of the kernel
     behind it on the stream, call by call, from the trace's timestamps.  Each kernel is set beside the bytes its shape says it
     moves -- k_get_layer_box: 18 B per source cell (2 B of code and four reals) plus 20 B per sample; k_clear_type: the 2 B of code
     per cell (the same table) plus 16 B per NODE_OUT cell -- as a rate and as a share of the 8 TB/s peak and of the 5.3 - 5.8 TB/s a
-    copy reaches.
+    copy reaches.  The invariants read 18 neighbour values where the curl reads 12, behind the same seven codes:
+    the expectation, stated before the run, is that the box-mean invariants' kernel stays within 1.5 x the box-mean vorticity's of
+    the same session (reported as invariants_over_vorticity; no threshold beyond that: a record is taken per output record).
+    `--skip-default --cases box256` runs (b) alone on the 256^3 box.
 Every GPU child runs under its own `timeout`; the tool stops at the first child that fails.
 """
 import argparse
@@ -35,7 +38,10 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 DEFAULT_OUT = os.path.join(ROOT, "profiles", "output_filter_cost.json")
 GET_LAYER_COST = os.path.join(ROOT, "tools", "get_layer_cost.py")
-MODES = (("default", 0, 0), ("box mean", 1, 0), ("point vorticity", 0, 1), ("box-mean vorticity", 1, 1))
+# (name, FS3D_OPT_OUTPUT_FILTER, FS3D_OPT_OUTPUT_VECTOR, FS3D_OPT_OUTPUT_GRADIENT)
+MODES = (("default", 0, 0, 0), ("box mean", 1, 0, 0), ("point vorticity", 0, 1, 0), ("box-mean vorticity", 1, 1, 0), ("point invariants", 0, 0, 1),
+         ("box-mean invariants", 1, 0, 1))
+INVARIANTS_EXPECTED = 1.5
 CASES = ("box256", "heart_us")
 WARMUP = 3
 PEAK_TBS, COPY_TBS = 8.0, (5.3, 5.8)
@@ -67,9 +73,10 @@ def child(case, repeats):
     pV, pT = V.ctypes.data_as(C.c_void_p), T.ctypes.data_as(C.c_void_p)
     out = {"case": case, "dims": list(nodes.shape), "outdims": list(od), "cells": int(nodes.ncells), "out_cells": nodes.count(grids.NODE_OUT),
            "fluid_cells": nodes.count(grids.NODE_IN), "samples": int(np.prod(od)), "modes": {}}
-    for name, filter, vector in MODES:
+    for name, filter, vector, gradient in MODES:
         s.set_option(capi.OPT_OUTPUT_FILTER, filter)
         s.set_option(capi.OPT_OUTPUT_VECTOR, vector)
+        s.set_option(capi.OPT_OUTPUT_GRADIENT, gradient)
         ms = []
         for k in range(WARMUP + repeats):
             t0 = time.perf_counter()
@@ -132,7 +139,7 @@ def filtered_record(a):
     env = dict(os.environ)
     env.pop("FS3D_LIB_PATH", None)
     me = [sys.executable, os.path.abspath(__file__)]
-    for case in CASES:
+    for case in a.cases:
         o = json.loads(run_child(me + ["--child", case, "--repeats", str(a.repeats)], env, 300).strip().splitlines()[-1])
         tmp = tempfile.mkdtemp(prefix="output_filter_cost_")
         run_child(["rocprofv3", "--kernel-trace", "--output-format", "csv", "-d", tmp, "-o", "t", "--"] + me + ["--child", case, "--repeats", str(a.repeats)], env, 600)
@@ -144,11 +151,11 @@ def filtered_record(a):
         if len(pairs) != calls:
             raise SystemExit("output_filter_cost: %d calls, %d kernel pairs in the trace" % (calls, len(pairs)))
         at = 0
-        for name, filter, vector in MODES:
+        for name, filter, vector, gradient in MODES:
             m = o["modes"][name]
             mine = pairs[at + WARMUP:at + m["calls"]]
             at += m["calls"]
-            kernel = "k_get_layer_box" if filter or vector else "k_get_layer"
+            kernel = "k_get_layer_box" if filter or vector or gradient else "k_get_layer"
             assert all(p[2] == kernel for p in mine), (name, kernel)
             clear, layer = stats([p[0] for p in mine], "us"), stats([p[1] for p in mine], "us")
             row = {"host_clock_per_call": stats(m.pop("host_ms"), "ms"), "kernel": kernel, "kernel_device": layer, "k_clear_type_device": clear,
@@ -160,6 +167,9 @@ def filtered_record(a):
             print("(b) %-9s %-19s host %.3f ms; %s %.1f (%.1f - %.1f) us; k_clear_type %.1f (%.1f - %.1f) us" % (
                 case, name, m["host_clock_per_call"]["median_ms"], kernel, layer["median_us"], layer["min_us"], layer["max_us"],
                 clear["median_us"], clear["min_us"], clear["max_us"]), flush=True)
+        ratio = o["modes"]["box-mean invariants"]["kernel_device"]["median_us"] / o["modes"]["box-mean vorticity"]["kernel_device"]["median_us"]
+        o["invariants_over_vorticity"] = {"box_mean_kernels": ratio, "expected_at_most": INVARIANTS_EXPECTED, "as_expected": bool(ratio <= INVARIANTS_EXPECTED)}
+        print("(b) %-9s box-mean invariants / box-mean vorticity = %.2f (expected: at most %.1f)" % (case, ratio, INVARIANTS_EXPECTED), flush=True)
         res[case] = o
     return res
 
@@ -173,15 +183,18 @@ def main():
     ap.add_argument("--commit", default=None)
     ap.add_argument("--parent-commit", default=None)
     ap.add_argument("--out", default=DEFAULT_OUT)
+    ap.add_argument("--skip-default", action="store_true", help="leave out (a)")
+    ap.add_argument("--cases", nargs="+", default=list(CASES), choices=CASES, help="(b): the grids")
     a = ap.parse_args()
     if a.child:
         return child(a.child, a.repeats)
-    if not a.parent_lib or not os.path.isfile(a.parent_lib):
-        raise SystemExit("output_filter_cost: --parent-lib: the library of the build to compare with")
+    if not a.skip_default and (not a.parent_lib or not os.path.isfile(a.parent_lib)):
+        raise SystemExit("output_filter_cost: --parent-lib: the library of the build to compare with (or --skip-default)")
     res = {"commit": a.commit, "parent_commit": a.parent_commit, "precision": "fp32", "repeats": a.repeats, "rounds": a.rounds,
            "note": "(a) host clock around fs3d_get_layer with both options 0, fresh processes alternating, parent first then this tree first; "
                    "(b) host clock per call, and device durations of the two kernels of a call from a rocprofv3 --kernel-trace run of the same child"}
-    res["default_record"] = default_record(a, {"this_tree": None, "parent": os.path.abspath(a.parent_lib)})
+    if not a.skip_default:
+        res["default_record"] = default_record(a, {"this_tree": None, "parent": os.path.abspath(a.parent_lib)})
     res["filtered_record"] = filtered_record(a)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:

@@ -24,6 +24,13 @@ The cases: mode 0, 1, 2, `2x` (mode 2 with the cross sums) and `2x/4` (the same 
     spread of the README).  (The trace, as in tools/output_filter_cost.py: the accumulation is enqueued inside the time step, where
     the tool cannot put events of its own around it, and the nine event classes of fs3d_enable_timing are the reference Profiler's
     names.)
+(e) the gradient sums (FS3D_OPT_TIME_STATS_GRAD; k_time_grad).  `--gradients --out profiles/time_grad_cost.txt` runs (a), then (b) on the
+    cases 0, 1, 1g, 2, 2g (g: with the gradient sums), then ONE child of case 1g under `rocprofv3 --kernel-trace` (alone): the median
+    device time of k_time_grad<float> and of k_time_stats_v4<float, 1> over the same 20 steps.  The rule's bytes: the mode-1 kernel
+    moves 54 B/cell counting every accumulator once (90 with reads and writes apart), the gradient kernel 42 when every field
+    value is fetched once -- 2 of code, 4 of count, 12 of fields, 24 of sums -- (70 apart), so equal time leaves about 29 % for the
+    neighbours' planes coming through the caches and for the arithmetic.  Verdict, set before the run: the median of k_time_grad is
+    no larger than the median of the mode-1 kernel in that same trace.
 (d) a kernel variant.  `--tree-lib FILE --skip-bench --note TEXT` runs (b) and (c) on another build of this tree's sources.
 Every GPU child runs under its own `timeout`; the tool stops at the first child that fails.
 """
@@ -47,6 +54,9 @@ N, STEPS, WARMUP = 256, 20, 3
 COPY_TBS = (5.3, 5.8)
 # case: (FS3D_OPT_TIME_STATS, FS3D_OPT_TIME_STATS_CROSS, FS3D_OPT_TIME_STATS_EVERY)
 CASES = {"0": (0, 0, 1), "1": (1, 0, 1), "2": (2, 0, 1), "2x": (2, 1, 1), "2x/4": (2, 1, 4)}
+# --gradients: the cases of (e); a trailing g sets FS3D_OPT_TIME_STATS_GRAD
+GRAD_CASES = {"0": (0, 0, 1), "1": (1, 0, 1), "1g": (1, 0, 1), "2": (2, 0, 1), "2g": (2, 0, 1)}
+GRAD_BYTES = 2 + 12 + 2 * (4 + 24)                           # code and fields read once, counts and sums read and written
 # bytes per cell of one accumulation, fp32: code and `cur` read, counts and sums read and written
 BYTES = {"1": 18 + 2 * 36, "2": 18 + 2 * 68, "2x": 18 + 2 * 116}
 CROSS_RATE_SHARE = 0.9
@@ -65,7 +75,7 @@ def child(case, repeats, layers):
     import bench
     from cmc_fluid_solver_amd import capi, grids
     dtype = np.float32
-    mode, cross, every = CASES[case]
+    mode, cross, every = {**CASES, **GRAD_CASES}[case]
     g = grids.box(N, h=1.0 / (N - 1))
     s = capi.Solver(g, capi.fluid_params(dtype, bench.RE, bench.PR, bench.LAMBDA), dtype)
     s.set_option(capi.OPT_TIME_STATS, mode)
@@ -73,6 +83,8 @@ def child(case, repeats, layers):
         s.set_option(capi.OPT_TIME_STATS_CROSS, cross)
     if every != 1:
         s.set_option(capi.OPT_TIME_STATS_EVERY, every)
+    if case.endswith("g"):
+        s.set_option(capi.OPT_TIME_STATS_GRAD, 1)
 
     def step(i):
         if i % 10 == 0:
@@ -91,7 +103,7 @@ def child(case, repeats, layers):
         s.synchronize()
         ms.append((time.perf_counter() - t0) * 1e3 / STEPS)
     out = {"case": case, "ms_per_step": ms, "cells": N ** 3, "kernels": s.last_sweep_kernels()}
-    if layers and mode:
+    if layers and mode and not case.endswith("g"):
         od = (54, 54, 52)
         rec = {}
         sources = [(0, 0), (1, 0), (3, 0)] + ([(2, 0)] if mode == 2 else []) + ([(2, 1), (2, 2)] if cross else [])
@@ -148,6 +160,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--tree-lib", default=None, help="a build of this tree's sources to measure in place of the tree's own library (a kernel variant)")
     ap.add_argument("--skip-bench", action="store_true", help="leave out (a) and the parent's side of (c)")
+    ap.add_argument("--gradients", action="store_true", help="(e): the cost of FS3D_OPT_TIME_STATS_GRAD in place of (b) and (c)")
     ap.add_argument("--note", default="", help="a line for the head of the file (which build this is)")
     ap.add_argument("--out", default=DEFAULT_OUT)
     a = ap.parse_args()
@@ -188,10 +201,11 @@ def main():
         say("    parent:    " + ", ".join("%.1f" % v for v in val["parent"]))
         say("    this tree: " + ", ".join("%.1f" % v for v in val["this_tree"]))
         say("    median of this tree %.1f, smallest of the parent %.1f: %s" % (tree, low, "PASS" if tree >= low else "FAIL"))
-    med = {case: [] for case in CASES}
+    cases = GRAD_CASES if a.gradients else CASES
+    med = {case: [] for case in cases}
     rec = {}
     for rnd in range(a.rounds):
-        for case in CASES:
+        for case in cases:
             o = json.loads(run_child(me + ["--child", case, "--repeats", str(a.repeats)] + (["--layers"] if rnd == 0 else []), env0, 300).strip().splitlines()[-1])
             med[case].append(statistics.median(o["ms_per_step"]))
             print("    case %s: %.4f ms per step" % (case, med[case][-1]), file=sys.stderr, flush=True)
@@ -199,11 +213,29 @@ def main():
                 rec[case] = o["record_ms"]
     say("(b) ms per step (host clock, %d-step blocks, process medians of %d blocks; %d processes per case; 2x: mode 2 with the cross sums, 2x/4: and a stride of 4)"
         % (STEPS, a.repeats, a.rounds))
-    for case in CASES:
+    for case in cases:
         say("    mode %s: %s; median %.4f (+%.4f over mode 0)" % (case, ", ".join("%.4f" % v for v in med[case]), statistics.median(med[case]),
                                                                 statistics.median(med[case]) - statistics.median(med["0"])))
-    say("(c) device time of the kernels (rocprofv3 --kernel-trace), median (min - max) us")
     cells = N ** 3
+    if a.gradients:
+        tmp = tempfile.mkdtemp(prefix="time_grad_cost_")
+        run_child(["rocprofv3", "--kernel-trace", "--output-format", "csv", "-d", tmp, "-o", "t", "--"] + me + ["--child", "1g", "--repeats", "1"], env0, 600)
+        found = [os.path.join(dp, f) for dp, _, fs in os.walk(tmp) for f in fs if f.endswith("kernel_trace.csv")]
+        if len(found) != 1:
+            raise SystemExit("time_stats_cost: no kernel trace under " + tmp)
+        grad, acc = durations(found[0], "k_time_grad<")[WARMUP:], durations(found[0], "k_time_stats_v4<float, 1>")[WARMUP:]
+        if len(grad) != STEPS or len(acc) != STEPS:
+            raise SystemExit("time_stats_cost: %d gradient and %d mode-1 launches in the trace, %d steps" % (len(grad), len(acc), STEPS))
+        say("(e) device time over the same %d steps of one trace (rocprofv3 --kernel-trace, case 1g), median (min - max) us" % STEPS)
+        for name, d, nb in (("k_time_stats_v4<float, 1>", acc, BYTES["1"]), ("k_time_grad<float>", grad, GRAD_BYTES)):
+            say("    %s: %.1f (%.1f - %.1f); %d B/cell with reads and writes apart: %s"
+                % (name, statistics.median(d), min(d), max(d), nb, rate_text(nb * cells, statistics.median(d))))
+        say("    the gradient kernel's median %.1f against the mode-1 kernel's %.1f: %s"
+            % (statistics.median(grad), statistics.median(acc), "PASS" if statistics.median(grad) <= statistics.median(acc) else "FAIL"))
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+        return
+    say("(c) device time of the kernels (rocprofv3 --kernel-trace), median (min - max) us")
     rate = {}
     for case in ("1", "2", "2x"):
         # fresh processes, `--rounds` per side, the sides alternating and taking turns to go first; the launches of a side are pooled
