@@ -43,6 +43,10 @@ OPT_OUTPUT_SLABS = 19     # 1: on a member of a group GetLayerRows / GetLayerDev
 OPT_OUTPUT_GRADIENT = 20  # outV of the three GetLayer entries: 0 as FS3D_OPT_OUTPUT_VECTOR has it (default), 1 the invariants (div, Q, S:S) of the velocity gradient of the
                           # sampled layer, 2 their time mean from the gradient sums (layer_output.invariants, time_stats.TimeStats.gradient_layer are the rule)
 OPT_TIME_STATS_GRAD = 21  # 1: every accumulated step also sums div, Q and S:S of the new `cur` per cell; whole grids only; every set opens a new window, 0 frees them (default 0)
+OPT_OUTPUT_WALL = 22      # outV of the three GetLayer entries: 0 as the options above have it (default), 1 the wall shear stress tau of the sampled layer on the wall cells that
+                          # carry one, 2 (|tau|, the wall heat flux q, the exposed area), 3 the time mean of tau, 4 (tawss, mean q, osi) from the wall sums
+                          # (layer_output.wall_loads, time_stats.TimeStats.wall_layer are the rule); whole grids only
+OPT_TIME_STATS_WALL = 23  # 1: every accumulated step also sums tau, |tau| and q of the new `cur` per carrier; whole grids only; every set opens a new window, 0 frees them (default 0)
 XSOLVE_AUTO, XSOLVE_PIPELINED, XSOLVE_REDUCED, XSOLVE_REDUCED_A2A = 0, 1, 2, 3
 
 # every function include/fs3d.h declares, in the header's order: name -> (restype, argtypes)

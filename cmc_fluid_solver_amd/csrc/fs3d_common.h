@@ -227,6 +227,15 @@ struct fs3d_ctx {
     int opt_out_gradient = 0;              // FS3D_OPT_OUTPUT_GRADIENT: outV of the GetLayer entries -- 1 the invariants of the sampled layer, 2 their time mean
     DevBuf<unsigned> tg_n;
     DevBuf<double> tg_g;
+    // wall sums (FS3D_OPT_TIME_STATS_WALL; k_time_wall, kernels_stats.hip): per own cell the accumulated steps on which it was a
+    // carrier of wall loads (tw_n) and the double sums of tau_x, tau_y, tau_z, |tau| and q over them (tw_w, quantity v at
+    // + v * ts_stride) -- 44 bytes per cell in two buffers, with the life of the gradient sums above: allocated by the first
+    // accumulation that needs them, counted in geom_allocs, kept over windows, freed when this option or FS3D_OPT_TIME_STATS is
+    // set to 0, zeroed by the accumulation that opens a window
+    int opt_ts_wall = 0;                   // FS3D_OPT_TIME_STATS_WALL: 1 = every accumulated step also sums the wall loads
+    int opt_out_wall = 0;                  // FS3D_OPT_OUTPUT_WALL: outV of the GetLayer entries -- 1 tau, 2 (|tau|, q, area), 3 mean tau, 4 (tawss, mean q, osi)
+    DevBuf<unsigned> tw_n;
+    DevBuf<double> tw_w;
     int opt_err_order = 0;                 // FS3D_OPT_ERR_ORDER: 1 = EvalDivError sums its per-cell terms serially in cell order (host), as the CPU path
     DevBuf<double> err_terms;              // ... one term per cell (device, allocated on first use)
     std::vector<double> err_terms_host;
@@ -326,7 +335,69 @@ static __device__ __forceinline__ void fs3d_invariants(const R (&g)[3][3], R &di
     q = h * (oo - ss);
 }
 
-// kernels_stats.hip: FS3D_OPT_TIME_STATS / _CROSS / _EVERY / _GRAD, FS3D_OPT_OUTPUT_SOURCE / _MOMENT
+// The wall loads (FS3D_OPT_OUTPUT_WALL, FS3D_OPT_TIME_STATS_WALL; the rule: layer_output.py wall_loads) of the cell l = (x, y, z) of a
+// whole grid whose code word is cw: false where it is no carrier.  Else area, the sums divided by it -- tau, q -- from the exposed
+// faces in the order x-, x+, y-, y+, z-, z+, every operation rounded once in R in the rule's order.  The face (d, -1) is exposed
+// iff the cell below is NODE_IN and not the first of its line (the wall cell itself closes its run); the face (d, +1) iff the wall
+// cell's row kind of direction d is ROW_START (the next cell is then an INTERIOR row).  Either way the cell's nibble of direction d
+// is that of a START or END row and carries the FREE bits.  Every address is inside the grid.  Shared by the record kernel
+// (kernels_output.hip) and the accumulation (kernels_stats.hip), both built with -ffp-contract=off and IEEE divide and sqrt.
+template <typename R>
+struct WallRule {
+    R h[3], A[3], nu, kappa;               // R(dx), R(dy), R(dz); the face areas R(dy)*R(dz), R(dx)*R(dz), R(dx)*R(dy); R(v_vis), R(t_vis)
+};
+
+template <typename R>
+static WallRule<R> fs3d_wall_rule(double dx, double dy, double dz, double v_vis, double t_vis)
+{
+    const R hx = (R)dx, hy = (R)dy, hz = (R)dz;
+    return WallRule<R>{{hx, hy, hz}, {hy * hz, hx * hz, hx * hy}, (R)v_vis, (R)t_vis};
+}
+
+template <typename R>
+static __device__ __forceinline__ bool fs3d_wall_loads(const WallRule<R> &w, const uint16_t *__restrict__ code, const R *U, const R *V,
+                                                       const R *W, const R *T, long long l, int x, int y, int z, long long plane,
+                                                       int dimz, int cw, R (&tau)[3], R &q, R &area)
+{
+    const int ty = (cw >> CODE_TYPE_SHIFT) & 3;
+    if (ty != FS3D_NODE_BOUND && ty != FS3D_NODE_VALVE) return false;
+    const R *const F[4] = {U, V, W, T};
+    const int idx[3] = {x, y, z};
+    const long long stride[3] = {plane, (long long)dimz, 1};
+    R sum[4] = {R(0), R(0), R(0), R(0)};
+    area = R(0);
+    bool carrier = false;
+#pragma unroll
+    for (int d = 0; d < 3; d++) {
+        const int nib = (cw >> (4 * d)) & 0xF;
+        const bool vel = !(nib & ROW_VELFREE), temp = !(nib & ROW_TEMPFREE);
+#pragma unroll
+        for (int s = -1; s <= 1; s += 2) {
+            const long long p = l + s * stride[d];
+            const bool face = s < 0 ? idx[d] >= 2 && ((code[p] >> CODE_TYPE_SHIFT) & 3) == FS3D_NODE_IN : (nib & 3) == ROW_START;
+            if (!face) continue;
+            carrier = true;
+            area = area + w.A[d];
+#pragma unroll
+            for (int c = 0; c < 4; c++) {
+                if (c == d || !(c == 3 ? temp : vel)) continue;
+                const R g = (F[c][p] - F[c][l]) / w.h[d];
+                const R t = (c == 3 ? w.kappa : w.nu) * g;
+                sum[c] = sum[c] + w.A[d] * t;
+            }
+        }
+    }
+    if (!carrier) return false;
+    tau[0] = sum[0] / area; tau[1] = sum[1] / area; tau[2] = sum[2] / area;
+    q = sum[3] / area;
+    return true;
+}
+
+// mag of the rule: sqrt((tau_x*tau_x + tau_y*tau_y) + tau_z*tau_z), correctly rounded
+static __device__ __forceinline__ float fs3d_wall_mag(const float (&t)[3]) { return sqrtf((t[0] * t[0] + t[1] * t[1]) + t[2] * t[2]); }
+static __device__ __forceinline__ double fs3d_wall_mag(const double (&t)[3]) { return sqrt((t[0] * t[0] + t[1] * t[1]) + t[2] * t[2]); }
+
+// kernels_stats.hip: FS3D_OPT_TIME_STATS / _CROSS / _EVERY / _GRAD / _WALL, FS3D_OPT_OUTPUT_SOURCE / _MOMENT
 // one candidate step of the window: where the stride takes it, one accumulation of FS3D_LAYER_CUR, enqueued on the context's stream
 // (the first one allocates and clears); else nothing
 fs3d_status fs3d_time_stats_accumulate(fs3d_ctx *c);
@@ -338,10 +409,14 @@ fs3d_status fs3d_time_stats_layer(fs3d_ctx *c, int source, int moment, void *q_o
 // FS3D_OPT_OUTPUT_GRADIENT 2: the fields U, V, W of the statistic layer a source-1 call has just built (q: their first own cells,
 // qstride apart) become the time means of div, Q and S:S from the gradient sums, enqueued behind it; T stays the mean of T
 fs3d_status fs3d_time_stats_grad_layer(fs3d_ctx *c, void *q, long long qstride);
-// all accumulators / the cross sums alone / the gradient sums alone; the caller has synchronised the stream
+// FS3D_OPT_OUTPUT_WALL 3 / 4: the same for the time means of the wall loads from the wall sums -- `which` 3: the mean traction,
+// 4: (tawss, the mean heat flux, osi)
+fs3d_status fs3d_time_stats_wall_layer(fs3d_ctx *c, int which, void *q, long long qstride);
+// all accumulators / the cross sums alone / the gradient sums alone / the wall sums alone; the caller has synchronised the stream
 void fs3d_time_stats_free(fs3d_ctx *c);
 void fs3d_time_stats_free_cross(fs3d_ctx *c);
 void fs3d_time_stats_free_grad(fs3d_ctx *c);
+void fs3d_time_stats_free_wall(fs3d_ctx *c);
 
 // kernels_*.hip
 // What a sweep launcher did.  NA: it does not cover these dims / this precision / this slab form -- the caller may try the

@@ -416,6 +416,21 @@ extern "C" fs3d_status fs3d_set_option(fs3d_ctx *c, int option, int value)
             fs3d_time_stats_free_grad(c);
         }
         return FS3D_OK;
+    case FS3D_OPT_TIME_STATS_WALL:
+        // the contract of FS3D_OPT_TIME_STATS_GRAD: a new window; 0 gives the wall sums back; whole grids only
+        if (value != 0 && value != 1) return fail(c, FS3D_ERR_INVALID, "bad time-statistics wall value (0: off, 1: every accumulated step also sums the wall shear stress and the wall heat flux)");
+        if (value == 1 && (c->x_offset != 0 || c->dimx != c->dimx_global))
+            return fail(c, FS3D_ERR_UNSUPPORTED, "FS3D_OPT_TIME_STATS_WALL on an x-slab (the faces across a cut need the neighbours' planes of `cur` at every accumulated step)");
+        c->opt_ts_wall = value; c->ts_steps = 0; c->ts_candidates = 0; c->ts_clear = true;
+        if (value == 0 && (c->tw_n.raw() || c->tw_w.raw())) {
+            HIPCHK(c, hipSetDevice(c->device));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            fs3d_time_stats_free_wall(c);
+        }
+        return FS3D_OK;
+    case FS3D_OPT_OUTPUT_WALL:
+        if (value < 0 || value > 4) return fail(c, FS3D_ERR_INVALID, "bad output wall id (0: off, 1: the wall shear stress, 2: its magnitude, the wall heat flux and the area, 3 and 4: their time means)");
+        c->opt_out_wall = value; return FS3D_OK;
     case FS3D_OPT_OUTPUT_GRADIENT:
         if (value < 0 || value > 2) return fail(c, FS3D_ERR_INVALID, "bad output gradient id (0: off, 1: the invariants div, Q, S:S of the sampled layer, 2: their time mean)");
         c->opt_out_gradient = value; return FS3D_OK;
@@ -1148,6 +1163,8 @@ extern "C" fs3d_status fs3d_time_step(fs3d_ctx *c, double dt, int G, int L, int 
     if (G < 0 || L < 0 || !(dt > 0)) return fail(c, FS3D_ERR_INVALID, "fs3d_time_step: bad dt / iteration counts");
     if (c->opt_ts_grad && c->opt_time_stats && c->nranks > 1)
         return fail(c, FS3D_ERR_UNSUPPORTED, "fs3d_time_step: FS3D_OPT_TIME_STATS_GRAD on a member of a group (the gradient sums are not collective)");
+    if (c->opt_ts_wall && c->opt_time_stats && c->nranks > 1)
+        return fail(c, FS3D_ERR_UNSUPPORTED, "fs3d_time_step: FS3D_OPT_TIME_STATS_WALL on a member of a group (the wall sums are not collective)");
     HIPCHK(c, hipSetDevice(c->device));
     if (c->timing_period > 1) c->timing = (c->timing_steps++ % c->timing_period) == 0;      // sampled timing: every N-th time step carries the events
     fs3d_status st = c->prec == FS3D_F32 ? time_step_enqueue<float>(c, dt, G, L, compute_error != 0)
@@ -1179,6 +1196,8 @@ extern "C" fs3d_status fs3d_time_step_async(fs3d_ctx *c, double dt, int G, int L
     if (G < 0 || L < 0 || !(dt > 0)) return fail(c, FS3D_ERR_INVALID, "fs3d_time_step_async: bad dt / iteration counts");
     if (c->opt_ts_grad && c->opt_time_stats && c->nranks > 1)
         return fail(c, FS3D_ERR_UNSUPPORTED, "fs3d_time_step_async: FS3D_OPT_TIME_STATS_GRAD on a member of a group (the gradient sums are not collective)");
+    if (c->opt_ts_wall && c->opt_time_stats && c->nranks > 1)
+        return fail(c, FS3D_ERR_UNSUPPORTED, "fs3d_time_step_async: FS3D_OPT_TIME_STATS_WALL on a member of a group (the wall sums are not collective)");
     HIPCHK(c, hipSetDevice(c->device));
     if (c->timing_period > 1) c->timing = (c->timing_steps++ % c->timing_period) == 0;
     // UpdateBoundaries and the cur -> next copy of the boundary cells that opens TimeStep: one pass over the list

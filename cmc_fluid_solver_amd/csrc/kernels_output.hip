@@ -1,5 +1,5 @@
 // Result records (fs3d_get_layer, _rows, _dev, _info of include/fs3d.h): the stamp, the gather behind GetLayer, the box-mean filter,
-// the vorticity and the invariants of the velocity gradient, on a whole grid and -- as one collective call, FS3D_OPT_OUTPUT_SLABS -- on the x-slabs of a group.  One kernel per
+// the vorticity, the invariants of the velocity gradient and (whole grids only) the wall loads, on a whole grid and -- as one collective call, FS3D_OPT_OUTPUT_SLABS -- on the x-slabs of a group.  One kernel per
 // stage and one host body: a whole grid is the slab x_offset = 0, dimx = dimx_global of a group of one, with no straddling row.
 #include <algorithm>
 #include <string>
@@ -51,8 +51,20 @@ __global__ void __launch_bounds__(256) k_get_layer(const R *__restrict__ U, cons
 // cut from the ghost and type planes.  A whole grid is the slab x_offset = 0, dimx = gx: both faces are the grid's, no neighbour
 // exists, and tlo / thi are never read.
 // VEC: what (a, b, c) is -- 0 the velocity, 1 the vorticity, 2 the invariants of the velocity gradient (div, Q, S:S; fs3d_invariants).
+// Whole grids only (FS3D_OPT_OUTPUT_WALL; fs3d_wall_loads): 3 the wall shear stress tau, 4 (|tau|, q, area), on the carriers, and the
+// members of a box are its carriers; 5 the velocity fields of a statistic layer of the wall sums, whose members are the cells with
+// nw >= 1 that are not NODE_OUT.  What these three need rides in a base that is empty for the others: their struct is unchanged.
 template <typename R, int VEC>
-struct SlabCells {
+struct WallPart {};
+template <typename R>
+struct WallPart<R, 3> { WallRule<R> wall; const unsigned *nw; };
+template <typename R>
+struct WallPart<R, 4> : WallPart<R, 3> {};
+template <typename R>
+struct WallPart<R, 5> : WallPart<R, 3> {};
+
+template <typename R, int VEC>
+struct SlabCells : WallPart<R, VEC> {
     const uint16_t *code;
     const R *U, *V, *W, *T;
     const uint8_t *tlo, *thi;
@@ -64,7 +76,12 @@ struct SlabCells {
     template <bool SLAB = true>
     __device__ __attribute__((always_inline)) void vec_of(long long l, int x, int y, int z, int ty, R &a, R &b, R &c) const
     {
-        if (VEC == 0) { a = U[l]; b = V[l]; c = W[l]; return; }
+        if (VEC == 0 || VEC == 5) { a = U[l]; b = V[l]; c = W[l]; return; }
+        if constexpr (VEC == 3 || VEC == 4) {
+            a = b = c = ty == FS3D_NODE_OUT ? R(99999.0f) : R(0);
+            member(l, x, y, z, a, b, c);
+            return;
+        }
         const long long plane = (long long)dimy * dimz;
         const int xg = x + x_offset;
         a = b = c = ty == FS3D_NODE_OUT ? R(99999.0f) : R(0);
@@ -89,6 +106,22 @@ struct SlabCells {
             fs3d_invariants(g, a, b, c);
         }
     }
+    // VEC >= 3: whether the own cell l = (x, y, z) is a member of its box, and then its (a, b, c); else they are left alone
+    __device__ __attribute__((always_inline)) bool member(long long l, int x, int y, int z, R &a, R &b, R &c) const
+    {
+        if constexpr (VEC == 5) {
+            if (this->nw[l] == 0u || type_of(l) == FS3D_NODE_OUT) return false;
+            a = U[l]; b = V[l]; c = W[l];
+            return true;
+        } else if constexpr (VEC == 3 || VEC == 4) {
+            R tau[3], q, area;
+            if (!fs3d_wall_loads(this->wall, code, U, V, W, T, l, x, y, z, (long long)dimy * dimz, dimz, (int)code[l], tau, q, area)) return false;
+            if (VEC == 3) { a = tau[0]; b = tau[1]; c = tau[2]; }
+            else { a = fs3d_wall_mag(tau); b = q; c = area; }
+            return true;
+        } else
+            return false;
+    }
 };
 
 // the node types of the slab's first and last plane, a byte per cell: what the neighbours' curl reads across the cuts
@@ -105,6 +138,8 @@ __global__ void __launch_bounds__(256) k_type_planes(const uint16_t *__restrict_
 // mean over the NODE_IN cells of its box [x0, x1) x [y0, y1) x [z0, z1) of source cells -- lo = i*g/o, hi = max(lo + 1, (i+1)*g/o) per
 // axis -- and the cell (x0, y0, z0) itself where the box holds none.  `point` (filter 0 of the vorticity): every sample is that cell,
 // one lane per output k as in k_get_layer, no box is walked.
+// VEC 3, 4 (FS3D_OPT_OUTPUT_WALL 1, 2; whole grids): the wall loads on the carriers, and the box is averaged over its carriers in place
+// of its NODE_IN cells; VEC 5 (FS3D_OPT_OUTPUT_WALL 3, 4 with the filter): the layer's values over the cells with nw >= 1.
 // VEC 1: the three velocity quantities are the curl, central differences in R, on the NODE_IN cells whose six neighbours are in the
 // grid and not NODE_OUT; 0 on the other NODE_IN cells and the walls, 99999 on NODE_OUT cells.  VEC 2 (FS3D_OPT_OUTPUT_GRADIENT 1):
 // the invariants div, Q, S:S of the velocity gradient on the same cells, with the same values elsewhere: 18 neighbour values
@@ -164,9 +199,13 @@ __global__ void __launch_bounds__(256) k_get_layer_box(const SlabCells<R, VEC> s
                     for (int x = x0; x < x1; x++)
                         for (int y = y0; y < y1; y++) {
                             const long long l = (long long)x * plane + (long long)y * dimz + z;
-                            if (s.type_of(l) != FS3D_NODE_IN) continue;
                             R a, b, c;
-                            s.template vec_of<SLAB>(l, x, y, z, FS3D_NODE_IN, a, b, c);
+                            if constexpr (VEC >= 3) {                  // the wall records: the members are not the fluid cells
+                                if (!s.member(l, x, y, z, a, b, c)) continue;
+                            } else {
+                                if (s.type_of(l) != FS3D_NODE_IN) continue;
+                                s.template vec_of<SLAB>(l, x, y, z, FS3D_NODE_IN, a, b, c);
+                            }
                             q[0] += (double)a; q[1] += (double)b; q[2] += (double)c; q[3] += (double)s.T[l];
                             m++;
                         }
@@ -288,7 +327,9 @@ static fs3d_status get_layer_impl(fs3d_ctx *c, R *outV, double *outT, int odx, i
     if (odz == 0) odz = c->dimz;
     const long long po = (long long)ody * odz;
     if (po >= (1LL << 31)) return fail(c, FS3D_ERR_UNSUPPORTED, "fs3d_get_layer: an output plane of 2^31 samples or more");
-    const int vec = c->opt_out_gradient == 1 ? 2 : c->opt_out_vector;      // SlabCells' VEC (the two options exclude each other)
+    // SlabCells' VEC (the three options exclude each other); the time means of the wall loads are a velocity layer, with members
+    // of their own under the filter
+    const int vec = c->opt_out_wall == 1 ? 3 : c->opt_out_wall == 2 ? 4 : c->opt_out_wall && c->opt_out_filter ? 5 : c->opt_out_gradient == 1 ? 2 : c->opt_out_vector;
     // the rows i with x_offset <= i*gx/odx < x_offset + dimx (slab.py out_rows)
     const int i0 = (int)(((long long)x_offset * odx + gx - 1) / gx), i1 = (int)(((long long)(x_offset + c->dimx) * odx + gx - 1) / gx);
     if (rows) { rows[0] = i0; rows[1] = i1; }
@@ -327,6 +368,7 @@ static fs3d_status get_layer_impl(fs3d_ctx *c, R *outV, double *outT, int odx, i
         GTRY(fs3d_time_stats_layer(c, c->opt_out_source, c->opt_out_source == 2 ? c->opt_out_moment : 0, (void **)F, &grown, collective, &fstride));
         c->gl_info[2] += grown;
         if (c->opt_out_gradient == 2) GTRY(fs3d_time_stats_grad_layer(c, F[0], fstride));      // U, V, W of the mean layer: the mean invariants
+        if (c->opt_out_wall >= 3) GTRY(fs3d_time_stats_wall_layer(c, c->opt_out_wall, F[0], fstride));      // ... the mean wall loads
     }
     hipLaunchKernelGGL((k_clear_type<R>), dim3(grid_for(c->ncell)), dim3(256), 0, c->stream, c->code, c->ncell,
                        (int)FS3D_NODE_OUT, (R)99999.0f, F[0], F[1], F[2], F[3]);
@@ -347,19 +389,21 @@ static fs3d_status get_layer_impl(fs3d_ctx *c, R *outV, double *outT, int odx, i
         // the grid's first or last plane returns from SlabCells::vec_of before the neighbour types are fetched -- and SLAB = false
         // compiles the fetch out
         const bool cut_types = collective && VEC != 0;
-        const SlabCells<R, VEC> s{c->code, F[0], F[1], F[2], F[3], cut_types ? ty + 2 * c->plane : nullptr, cut_types ? ty + 3 * c->plane : nullptr,
-                                   x_offset, c->dimx, gx, c->dimy, c->dimz, R(2) * (R)c->gdx, R(2) * (R)c->gdy, R(2) * (R)c->gdz};
+        SlabCells<R, VEC> s{{}, c->code, F[0], F[1], F[2], F[3], cut_types ? ty + 2 * c->plane : nullptr, cut_types ? ty + 3 * c->plane : nullptr,
+                             x_offset, c->dimx, gx, c->dimy, c->dimz, R(2) * (R)c->gdx, R(2) * (R)c->gdy, R(2) * (R)c->gdz};
+        if constexpr (VEC >= 3) { s.wall = fs3d_wall_rule<R>(c->gdx, c->gdy, c->gdz, c->v_vis, c->t_vis); s.nw = c->tw_n; }
         if (i1 > ia) {
             auto launch = [&](auto slab) {
                 hipLaunchKernelGGL((k_get_layer_box<R, VEC, decltype(slab)::value>), dim3((unsigned)(i1 - ia), (unsigned)std::min(ody, 65535)), dim3(256), 0, c->stream, s,
                                    odx, ody, odz, c->opt_out_filter ? 0 : 1, ia, i0, s_first, s_last, kV, kT, (double *)c->os_part);
             };
-            if (collective) launch(std::true_type{}); else launch(std::false_type{});
+            if constexpr (VEC >= 3) launch(std::false_type{});          // the wall records: whole grids only, the entries refuse a slab
+            else if (collective) launch(std::true_type{}); else launch(std::false_type{});
         }
         if (const hipError_t e = hipGetLastError(); e != hipSuccess)       // (checked where no row is launched too, as ever)
             return fail(c, FS3D_ERR_HIP, collective ? call_failed(c, "k_get_layer_box", "launch") : call_failed(c, "hipGetLastError()", hipGetErrorString(e)));
         if (nsum) GTRY(fs3d_comm_allreduce_sum(c, c->os_part, nsum));
-        if (finish) {
+        if constexpr (VEC < 3) if (finish) {
             const long long at = (long long)(i1 - 1 - i0) * po;
             hipLaunchKernelGGL((k_get_layer_finish<R, VEC>), dim3(grid_for(po, 1024)), dim3(256), 0, c->stream, s, i1 - 1, odx, ody, odz,
                                (const double *)c->os_part + (size_t)s_last * 5 * po, kV + 3 * at, kT + at);
@@ -368,7 +412,8 @@ static fs3d_status get_layer_impl(fs3d_ctx *c, R *outV, double *outT, int odx, i
         return FS3D_OK;
     };
     if (c->opt_out_filter || vec)
-        GTRY(vec == 2 ? box_stage(std::integral_constant<int, 2>{}) : vec ? box_stage(std::integral_constant<int, 1>{}) : box_stage(std::integral_constant<int, 0>{}));
+        GTRY(vec == 5 ? box_stage(std::integral_constant<int, 5>{}) : vec == 4 ? box_stage(std::integral_constant<int, 4>{}) : vec == 3 ? box_stage(std::integral_constant<int, 3>{})
+             : vec == 2 ? box_stage(std::integral_constant<int, 2>{}) : vec ? box_stage(std::integral_constant<int, 1>{}) : box_stage(std::integral_constant<int, 0>{}));
     else if (n) {
         hipLaunchKernelGGL((k_get_layer<R>), dim3((unsigned)(i1 - i0), grid_for(po, 1024)), dim3(256), 0, c->stream, F[0], F[1], F[2], F[3],
                            x_offset, c->dimx, c->plane, c->dimy, c->dimz, gx, odx, ody, odz, i0, i1, kV, kT);
@@ -391,6 +436,18 @@ static fs3d_status get_layer_entry(fs3d_ctx *c, const char *what, void *outV, do
     if (!c || !outV || !outT || (!local && !rows)) return c ? fail(c, FS3D_ERR_INVALID, std::string(what) + ": NULL destination") : FS3D_ERR_INVALID;
     if (!c->have_nodes) return fail(c, FS3D_ERR_INVALID, std::string(what) + ": upload nodes first");
     if (odx < 0 || ody < 0 || odz < 0) return fail(c, FS3D_ERR_INVALID, std::string(what) + ": negative output dims");
+    if (c->opt_out_wall) {                                     // FS3D_OPT_OUTPUT_WALL: whole grids only, and outV is its own
+        const std::string w = std::string(what) + ": FS3D_OPT_OUTPUT_WALL " + std::to_string(c->opt_out_wall);
+        if (c->opt_out_vector || c->opt_out_gradient)
+            return fail(c, FS3D_ERR_INVALID, w + (c->opt_out_vector ? " with FS3D_OPT_OUTPUT_VECTOR 1" : " with FS3D_OPT_OUTPUT_GRADIENT set") + " (two options claim outV)");
+        if (c->opt_out_source >= 2)
+            return fail(c, FS3D_ERR_INVALID, w + " with FS3D_OPT_OUTPUT_SOURCE " + std::to_string(c->opt_out_source) + " (the wall loads of a variance or a fraction layer mean nothing)");
+        if (c->x_offset != 0 || c->dimx != c->dimx_global || c->comm || c->local || c->nranks > 1)
+            return fail(c, FS3D_ERR_UNSUPPORTED, w + " on an x-slab or a member of a group (the faces across a cut need the neighbour's planes; FS3D_OPT_OUTPUT_SLABS does not serve it)");
+        if (c->opt_out_wall >= 3 && (c->opt_out_source != 1 || c->opt_time_stats == 0 || !c->opt_ts_wall || c->ts_steps == 0 || !c->tw_n.raw() || !c->tw_w.raw()))
+            return fail(c, FS3D_ERR_INVALID, w + " asks for a time mean of the wall loads: it needs FS3D_OPT_OUTPUT_SOURCE 1 and an open window of "
+                                             "FS3D_OPT_TIME_STATS with FS3D_OPT_TIME_STATS_WALL 1 that holds a time step");
+    }
     if (c->opt_out_gradient && c->opt_out_vector)
         return fail(c, FS3D_ERR_INVALID, std::string(what) + ": FS3D_OPT_OUTPUT_GRADIENT " + std::to_string(c->opt_out_gradient) +
                                          " with FS3D_OPT_OUTPUT_VECTOR 1 (two options claim outV)");

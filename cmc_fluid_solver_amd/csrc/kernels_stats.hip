@@ -1,8 +1,9 @@
-// Time statistics (FS3D_OPT_TIME_STATS, FS3D_OPT_TIME_STATS_CROSS, FS3D_OPT_TIME_STATS_EVERY, FS3D_OPT_TIME_STATS_GRAD,
+// Time statistics (FS3D_OPT_TIME_STATS, FS3D_OPT_TIME_STATS_CROSS, FS3D_OPT_TIME_STATS_EVERY, FS3D_OPT_TIME_STATS_GRAD, FS3D_OPT_TIME_STATS_WALL,
 // FS3D_OPT_OUTPUT_SOURCE, FS3D_OPT_OUTPUT_MOMENT; no reference counterpart): running sums of the fields and of their products over the accumulated time steps
 // of a window, and the statistic layers the result output reads in place of `next`.  The rule and its numpy twin:
 // cmc_fluid_solver_amd/time_stats.py.  Per cell, nothing from a neighbour: a slab accumulates and reads out its own planes -- but for
-// the gradient sums of FS3D_OPT_TIME_STATS_GRAD (k_time_grad), a stencil over `cur`, which whole grids alone accumulate.
+// the gradient sums of FS3D_OPT_TIME_STATS_GRAD (k_time_grad), a stencil over `cur`, and the wall sums of FS3D_OPT_TIME_STATS_WALL
+// (k_time_wall), one-sided differences at the wall cells, which whole grids alone accumulate.
 // Built with -ffp-contract=off like everything outside kernels_part.hip: every operation below is rounded once in double.
 #include "fs3d_common.h"
 
@@ -270,6 +271,77 @@ __global__ void __launch_bounds__(256) k_time_grad_layer(long long ncell, const 
     for (int v = 0; v < 3; v++) q[v * qstride + l] = n ? (R)(gs[v * sstride + l] / dn) : R(0);
 }
 
+// FS3D_OPT_TIME_STATS_WALL: one accumulation of the wall loads (fs3d_wall_loads: tau, |tau|, q in R) of `cur` on the carriers of the
+// current geometry: nw += 1, W_v += (double)value.  Whole grids only (`cur` and `code` address the cell (0, 0, 0)).
+// Most cells are no walls, so this is a stream over the 2-byte code words with work on the wall cells alone: a thread takes the 8
+// consecutive codes l0 .. l0 + 7 in one 16-byte load (lanes along k, a wave reads 1 KiB of the table per instruction; l0 is a
+// multiple of 8 and the table is allocated on 256 bytes; the last thread of a grid whose cell count is no multiple of 8 reads its
+// codes one by one) and keeps a bit per NODE_BOUND / NODE_VALVE cell.  The lanes that hold wall cells then take them one per turn,
+// so a wave runs the rule as often as its busiest lane holds walls, not once per position: the cell's (x, y, z) by two divisions,
+// up to three more codes and, per exposed face, the fields of the cell and of its fluid neighbour.  The sums of a cell that is no
+// carrier are never read.  Plain loads and stores (the accumulators are a read-modify-write on few cells); no LDS, no atomics.
+template <typename R>
+__global__ void __launch_bounds__(256) k_time_wall(const uint16_t *__restrict__ code, const R *__restrict__ cur, long long fstride,
+                                                    long long ncell, int dimy, int dimz, const WallRule<R> w,
+                                                    unsigned *__restrict__ cnt, double *__restrict__ ws, long long sstride)
+{
+    const long long l0 = ((long long)blockIdx.x * 256 + threadIdx.x) * 8;
+    if (l0 >= ncell) return;
+    unsigned mask = 0;                                         // bit q: the cell l0 + q is a wall (types 2 and 3: bit 1 of the type)
+    if (l0 + 8 <= ncell) {
+        const uint4 v = *reinterpret_cast<const uint4 *>(code + l0);
+        const unsigned wd[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int q = 0; q < 8; q++) mask |= ((wd[q >> 1] >> (16 * (q & 1) + CODE_TYPE_SHIFT + 1)) & 1u) << q;
+    } else
+        for (int q = 0; l0 + q < ncell; q++) mask |= (((unsigned)code[l0 + q] >> (CODE_TYPE_SHIFT + 1)) & 1u) << q;
+    const long long plane = (long long)dimy * dimz;
+    while (mask) {
+        const long long l = l0 + (__ffs((int)mask) - 1);
+        mask &= mask - 1;
+        const int x = (int)(l / plane);
+        const long long r = l - (long long)x * plane;
+        const int y = (int)(r / dimz), z = (int)(r - (long long)y * dimz);
+        R tau[3], q, area;
+        if (!fs3d_wall_loads(w, code, cur, cur + fstride, cur + 2 * fstride, cur + 3 * fstride, l, x, y, z, plane, dimz, (int)code[l], tau, q, area))
+            continue;
+        const R mag = fs3d_wall_mag(tau);
+        cnt[l] += 1u;
+        double *const p = ws + l;
+        p[0] = p[0] + (double)tau[0];
+        p[sstride] = p[sstride] + (double)tau[1];
+        p[2 * sstride] = p[2 * sstride] + (double)tau[2];
+        p[3 * sstride] = p[3 * sstride] + (double)mag;
+        p[4 * sstride] = p[4 * sstride] + (double)q;
+    }
+}
+
+// FS3D_OPT_OUTPUT_WALL 3 / 4: the time means of the wall loads into the fields U, V, W of a statistic layer, in double with
+// dn = (double)nw where nw >= 1 and 0 elsewhere -- 3: (R)(W_x / dn), (R)(W_y / dn), (R)(W_z / dn); 4: (R)tawss, (R)(W_q / dn),
+// (R)osi with tawss = W_mag / dn, mm the magnitude of the mean traction, osi = 0.5 * (1 - mm / tawss) where tawss > 0, else 0, and
+// 0 where that is negative.  One cell per thread.
+template <typename R>
+__global__ void __launch_bounds__(256) k_time_wall_layer(int which, long long ncell, const unsigned *__restrict__ cnt, const double *__restrict__ ws,
+                                                          long long sstride, R *__restrict__ q, long long qstride)
+{
+    const long long l = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (l >= ncell) return;
+    const unsigned n = cnt[l];
+    double a = 0.0, b = 0.0, c = 0.0;
+    if (n) {
+        const double dn = (double)n;
+        const double m[3] = {ws[l] / dn, ws[sstride + l] / dn, ws[2 * sstride + l] / dn};
+        if (which == 3) { a = m[0]; b = m[1]; c = m[2]; }
+        else {
+            const double mm = fs3d_wall_mag(m), tawss = ws[3 * sstride + l] / dn;
+            double osi = tawss > 0.0 ? 0.5 * (1.0 - mm / tawss) : 0.0;
+            if (osi < 0.0) osi = 0.0;
+            a = tawss; b = ws[4 * sstride + l] / dn; c = osi;
+        }
+    }
+    q[l] = (R)a; q[qstride + l] = (R)b; q[2 * qstride + l] = (R)c;
+}
+
 static bool aligned(const void *p, size_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
 
 template <typename R, int MODE>
@@ -319,6 +391,30 @@ static fs3d_status accumulate_gradients(fs3d_ctx *c, bool fresh)
     return FS3D_OK;
 }
 
+// FS3D_OPT_TIME_STATS_WALL: the wall sums of one accumulated step, with the life of the gradient sums' buffers above
+static fs3d_status accumulate_wall(fs3d_ctx *c, bool fresh)
+{
+    const size_t nbytes = (size_t)c->ts_stride * sizeof(unsigned), wbytes = (size_t)5 * c->ts_stride * sizeof(double);
+    const bool held = c->tw_n.raw() && c->tw_w.raw();
+    BUFCHK(c, c->tw_n.reserve(nbytes, &c->geom_allocs));
+    BUFCHK(c, c->tw_w.reserve(wbytes, &c->geom_allocs));
+    if (fresh || !held) {
+        HIPCHK(c, hipMemsetAsync(c->tw_n, 0, nbytes, c->stream));
+        HIPCHK(c, hipMemsetAsync(c->tw_w, 0, wbytes, c->stream));
+    }
+    const long long blocks = (c->ncell + 2047) / 2048;
+    if (blocks >= (1LL << 31)) return fail(c, FS3D_ERR_UNSUPPORTED, "FS3D_OPT_TIME_STATS_WALL: 2^42 cells or more");
+    auto launch = [&](auto r) {
+        using R = decltype(r);
+        hipLaunchKernelGGL((k_time_wall<R>), dim3((unsigned)blocks), dim3(256), 0, c->stream, (const uint16_t *)c->code,
+                           (const R *)c->lay[c->slot[FS3D_LAYER_CUR]] + c->plane, c->fstride, c->ncell, c->dimy, c->dimz,
+                           fs3d_wall_rule<R>(c->gdx, c->gdy, c->gdz, c->v_vis, c->t_vis), (unsigned *)c->tw_n, (double *)c->tw_w, c->ts_stride);
+    };
+    if (c->prec == FS3D_F32) launch(0.0f); else launch(0.0);
+    HIPCHK(c, hipGetLastError());
+    return FS3D_OK;
+}
+
 fs3d_status fs3d_time_stats_accumulate(fs3d_ctx *c)
 {
     // FS3D_OPT_TIME_STATS_EVERY: candidate s = 1, 2, .. of the window is taken where (s - 1) % k == 0; on the others nothing runs
@@ -344,7 +440,9 @@ fs3d_status fs3d_time_stats_accumulate(fs3d_ctx *c)
     else { if (cross) launch_accumulate<double, 3>(c); else if (mode == 2) launch_accumulate<double, 2>(c); else launch_accumulate<double, 1>(c); }
     HIPCHK(c, hipGetLastError());
     c->ts_steps++;
-    if (c->opt_ts_grad) return accumulate_gradients(c, fresh);      // behind the step and the sums above; a failure is the step's status, the step stands
+    // behind the step and the sums above; a failure is the step's status, the step stands
+    if (c->opt_ts_grad) { const fs3d_status st = accumulate_gradients(c, fresh); if (st != FS3D_OK) return st; }
+    if (c->opt_ts_wall) return accumulate_wall(c, fresh);
     return FS3D_OK;
 }
 
@@ -383,12 +481,28 @@ fs3d_status fs3d_time_stats_grad_layer(fs3d_ctx *c, void *q, long long qstride)
     return FS3D_OK;
 }
 
+fs3d_status fs3d_time_stats_wall_layer(fs3d_ctx *c, int which, void *q, long long qstride)
+{
+    const unsigned blocks = (unsigned)((c->ncell + 255) / 256);
+    if (c->prec == FS3D_F32)
+        hipLaunchKernelGGL((k_time_wall_layer<float>), dim3(blocks), dim3(256), 0, c->stream, which, c->ncell, (const unsigned *)c->tw_n,
+                           (const double *)c->tw_w, c->ts_stride, (float *)q, qstride);
+    else
+        hipLaunchKernelGGL((k_time_wall_layer<double>), dim3(blocks), dim3(256), 0, c->stream, which, c->ncell, (const unsigned *)c->tw_n,
+                           (const double *)c->tw_w, c->ts_stride, (double *)q, qstride);
+    HIPCHK(c, hipGetLastError());
+    return FS3D_OK;
+}
+
 void fs3d_time_stats_free(fs3d_ctx *c)
 {
     c->ts_n.reset(&c->geom_allocs); c->ts_s1.reset(&c->geom_allocs); c->ts_s2.reset(&c->geom_allocs);
     fs3d_time_stats_free_cross(c);
     fs3d_time_stats_free_grad(c);
+    fs3d_time_stats_free_wall(c);
 }
+
+void fs3d_time_stats_free_wall(fs3d_ctx *c) { c->tw_n.reset(&c->geom_allocs); c->tw_w.reset(&c->geom_allocs); }
 
 void fs3d_time_stats_free_grad(fs3d_ctx *c) { c->tg_n.reset(&c->geom_allocs); c->tg_g.reset(&c->geom_allocs); }
 

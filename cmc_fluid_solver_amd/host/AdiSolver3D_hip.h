@@ -158,6 +158,17 @@ public:
     // per-cell sums (the cells that carry them at that step), 0 -- off, those sums are freed.  EVERY call opens a new window.  A
     // single-GPU solver only: a slab solver throws (FS3D_ERR_UNSUPPORTED)
     void SetTimeStatsGradients(int on) { chk(fs3d_set_option(ctx_, FS3D_OPT_TIME_STATS_GRAD, on)); }
+    // FS3D_OPT_OUTPUT_WALL for the same calls: 1 resVel holds the wall shear stress vector of the sampled layer on the wall cells
+    // that carry one (a wall cell with a fluid neighbour on a line the solver closes there), 2 its magnitude, the wall heat flux and
+    // the exposed area, 99999 on NODE_OUT cells, 0 elsewhere; with SetOutputFilter(1) the mean over the carriers of a box; 3 the
+    // time mean of the vector, 4 the time-averaged magnitude (TAWSS), the mean heat flux and the oscillatory shear index (both
+    // need SetOutputSource(1) and a window accumulated with SetTimeStatsWall(1)); 0 off.  With SetOutputVector(1) or a non-zero
+    // SetOutputGradient the calls throw (FS3D_ERR_INVALID); a slab solver throws (FS3D_ERR_UNSUPPORTED)
+    void SetOutputWall(int mode) { chk(fs3d_set_option(ctx_, FS3D_OPT_OUTPUT_WALL, mode)); }
+    // FS3D_OPT_TIME_STATS_WALL: 1 -- with SetTimeStats(1 or 2) every accumulated step also adds the wall shear stress, its
+    // magnitude and the wall heat flux of its result to per-cell sums (the carriers of that step), 0 -- off, those sums are freed.
+    // EVERY call opens a new window.  A single-GPU solver only: a slab solver throws (FS3D_ERR_UNSUPPORTED)
+    void SetTimeStatsWall(int on) { chk(fs3d_set_option(ctx_, FS3D_OPT_TIME_STATS_WALL, on)); }
     // FS3D_OPT_TIME_STATS: 1 -- from now on every TimeStep that succeeds adds its result to per-cell sums on the device (the cells
     // that are NODE_IN at that step), 2 -- and its squares, 0 -- off, the sums are freed.  EVERY call opens a new window.  Works on
     // a slab solver as on a single one (a cell asks nothing of a neighbour)

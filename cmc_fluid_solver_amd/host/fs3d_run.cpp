@@ -82,6 +82,13 @@
 //   (FS3D_OPT_TIME_STATS_GRAD) -- and <prefix>_stats.nc holds one more record, directly before the fluid fraction, which stays last: the
 //   time mean of div u in u, of Q in v, of S:S in w and of T in T (source 1 with SetOutputGradient(2)).  The closing line gains
 //   `, gradients`.  Without the word every file and every print is unchanged.
+// --time-wall, with --time-stats (else refused when the arguments are read; refused with GPU n, n > 1, too): SetTimeStatsWall(1) before
+//   the loop -- every accumulated step also adds the wall shear stress, its magnitude and the wall heat flux to per-cell sums on the
+//   wall cells that carry them (FS3D_OPT_TIME_STATS_WALL) -- and <prefix>_stats.nc holds two more records, directly before the fluid
+//   fraction, which stays last, and after the record of --time-gradients: the time mean of the wall shear stress vector in u, v, w
+//   (source 1 with SetOutputWall(3)), then the time-averaged magnitude (TAWSS) in u, the mean wall heat flux in v and the oscillatory
+//   shear index in w (SetOutputWall(4)); T is the mean of T in both.  --output-filter box applies to them (the mean over the wall
+//   cells under a sample).  The closing line gains `, wall`.  Without the word every file and every print is unchanged.
 // --time-output: one closing line, the host clock per output record around the GetLayer call (GPU n: rank 0's call and the barrier that
 //   completes the record) and around AppendLayer, with the number of records.
 // There is no CPU backend here: without a GPU the run stops with the library's error.
@@ -130,6 +137,7 @@ struct RunOptions {
     bool time_cov = false;                             // --time-covariances (FS3D_OPT_TIME_STATS_CROSS; needs time_stats 2)
     long time_every = 1;                               // --time-stats-every K (FS3D_OPT_TIME_STATS_EVERY)
     bool time_grad = false;                            // --time-gradients (FS3D_OPT_TIME_STATS_GRAD; needs time_stats, one GPU)
+    bool time_wall = false;                            // --time-wall (FS3D_OPT_TIME_STATS_WALL; needs time_stats, one GPU)
     int nslabs = 1, device = 0;
     long max_steps = -1;
     std::string grid_only;
@@ -138,7 +146,7 @@ struct RunOptions {
     bool walls() const { return wall_velocity || has_wall_T; }               // the mesh updates go through the entries that take velocities and a wall temperature
 };
 
-static const char USAGE[] = "<input data> <output prefix> <config file> [align] [GPU [n]] [double] [--steps N] [moving [--host-extrusion] [--time-geometry]] [moving-mesh [--host-voxels | --slab-voxels] [--time-geometry] [--time-both]] [--time-output] [--grid-only FILE [--grid-time T]] [--grid-images] [--watertight [--thin-shell] [--wall-velocity motion|file]] [--wall-temperature T] [--fresh-cells | --slab-fresh-cells] [--output-filter point|box] [--slab-output-filter point|box] [--time-stats mean|variance] [--time-covariances] [--time-stats-every K] [--time-gradients]";
+static const char USAGE[] = "<input data> <output prefix> <config file> [align] [GPU [n]] [double] [--steps N] [moving [--host-extrusion] [--time-geometry]] [moving-mesh [--host-voxels | --slab-voxels] [--time-geometry] [--time-both]] [--time-output] [--grid-only FILE [--grid-time T]] [--grid-images] [--watertight [--thin-shell] [--wall-velocity motion|file]] [--wall-temperature T] [--fresh-cells | --slab-fresh-cells] [--output-filter point|box] [--slab-output-filter point|box] [--time-stats mean|variance] [--time-covariances] [--time-stats-every K] [--time-gradients] [--time-wall]";
 
 // the refusals that need no geometry, in the order a user meets them
 static void check_words(const RunOptions &o, const fs3d::Config &cfg)
@@ -181,14 +189,16 @@ static double ms_between(Clock::time_point a, Clock::time_point b) { return std:
 // --time-stats: the records of <prefix>_stats.nc, in order, each a source and a moment (FS3D_OPT_OUTPUT_SOURCE: 1 mean, 2 second
 // moments, 3 fluid fraction; FS3D_OPT_OUTPUT_MOMENT: 0 variance, 1 stresses, 2 heat flux)
 // --time-gradients: one more record directly before the fluid fraction, source 1 with FS3D_OPT_OUTPUT_GRADIENT 2
-struct StatsRecord { int source, moment, gradient; };
+// --time-wall: two more behind it, source 1 with FS3D_OPT_OUTPUT_WALL 3 and 4
+struct StatsRecord { int source, moment, gradient, wall; };
 static std::vector<StatsRecord> stats_records(const RunOptions &o)
 {
-    std::vector<StatsRecord> recs = {{1, 0, 0}};
-    if (o.time_stats == 2) recs.push_back({2, 0, 0});
-    if (o.time_stats == 2 && o.time_cov) { recs.push_back({2, 1, 0}); recs.push_back({2, 2, 0}); }
-    if (o.time_grad) recs.push_back({1, 0, 2});
-    recs.push_back({3, 0, 0});
+    std::vector<StatsRecord> recs = {{1, 0, 0, 0}};
+    if (o.time_stats == 2) recs.push_back({2, 0, 0, 0});
+    if (o.time_stats == 2 && o.time_cov) { recs.push_back({2, 1, 0, 0}); recs.push_back({2, 2, 0, 0}); }
+    if (o.time_grad) recs.push_back({1, 0, 2, 0});
+    if (o.time_wall) { recs.push_back({1, 0, 0, 3}); recs.push_back({1, 0, 0, 4}); }
+    recs.push_back({3, 0, 0, 0});
     return recs;
 }
 
@@ -206,6 +216,7 @@ static void apply_options(Solver &solver, const RunOptions &o, int nslabs)
     if (o.time_stats && o.time_cov) solver.SetTimeStatsCross(1);
     if (o.time_stats && o.time_every > 1) solver.SetTimeStatsEvery((int)o.time_every);
     if (o.time_stats && o.time_grad) solver.SetTimeStatsGradients(1);
+    if (o.time_stats && o.time_wall) solver.SetTimeStatsWall(1);
 }
 
 // The ranks wait for one another here.  One rank: every wait returns at once.
@@ -478,6 +489,7 @@ static void run_rank(Run<FTYPE> &s, const int r)
             solver.SetOutputSource(rec.source);
             if (o.time_cov) solver.SetOutputMoment(rec.moment);
             if (o.time_grad) solver.SetOutputGradient(rec.gradient);
+            if (o.time_wall) solver.SetOutputWall(rec.wall);
             record(s, solver, r, s.ns, nullptr);
         }
         solver.SetOutputSource(0);
@@ -519,9 +531,9 @@ static int run_loop(fs3d::Grid3D<FTYPE> &grid, fs3d::Grid2D &g2, fs3d::Shape3D &
     }
     if (o.time_stats) {
         // steps: the time steps of the run; the line names the accumulated ones, the 1st, (K + 1)th, .. of them
-        if (s.steps > 0) std::printf("Time statistics: %ld steps, mean%s%s%s in %s\n", (s.steps + o.time_every - 1) / o.time_every,
+        if (s.steps > 0) std::printf("Time statistics: %ld steps, mean%s%s%s%s in %s\n", (s.steps + o.time_every - 1) / o.time_every,
                                      o.time_stats == 2 ? ", variance" : "", o.time_cov ? ", covariances" : "", o.time_grad ? ", gradients" : "",
-                                     s.stats.c_str());
+                                     o.time_wall ? ", wall" : "", s.stats.c_str());
         else std::printf("Time statistics: 0 steps, no file\n");
     }
     return 0;
@@ -632,6 +644,7 @@ int main(int argc, char **argv)
             }
             else if (s == "--time-covariances") o.time_cov = true;
             else if (s == "--time-gradients") o.time_grad = true;
+            else if (s == "--time-wall") o.time_wall = true;
             else if (s == "--time-stats-every") {
                 const char *const w = a + 1 < argc ? argv[++a] : "";
                 char *end = nullptr;
@@ -655,6 +668,11 @@ int main(int argc, char **argv)
         if (o.time_grad && o.nslabs > 1)
             throw std::invalid_argument("--time-gradients: single GPU only (the gradient sums read a cell's neighbours in `cur`, whose ghost planes are not "
                                      "current after a step, and the library refuses them on an x-slab)");
+        // (std::invalid_argument as the two above; their cases are in tests/test_wall_loads_twin.py)
+        if (o.time_wall && !o.time_stats) throw std::invalid_argument("--time-wall: needs --time-stats mean or --time-stats variance");
+        if (o.time_wall && o.nslabs > 1)
+            throw std::invalid_argument("--time-wall: single GPU only (the wall sums read a wall cell's fluid neighbours in `cur`, whose ghost planes are not "
+                                        "current after a step, and the library refuses them on an x-slab)");
         if (o.output_box && !o.slab_output_box && o.nslabs > 1)
             throw std::runtime_error("--output-filter box: single GPU only (with GPU n the grid is cut into x-slabs, a sample's box of source cells can "
                                      "straddle a cut, and the library refuses filtered records on a slab)");

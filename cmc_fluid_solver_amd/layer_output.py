@@ -1,5 +1,5 @@
 """Filtered and derived result records: what fs3d_get_layer, fs3d_get_layer_rows and fs3d_get_layer_dev return while
-FS3D_OPT_OUTPUT_FILTER, FS3D_OPT_OUTPUT_VECTOR or FS3D_OPT_OUTPUT_GRADIENT is set.
+FS3D_OPT_OUTPUT_FILTER, FS3D_OPT_OUTPUT_VECTOR, FS3D_OPT_OUTPUT_GRADIENT or FS3D_OPT_OUTPUT_WALL is set.
 
 layer_output is the definition of the rule; k_get_layer_box (csrc/kernels_output.hip) is held to it -- bit for bit wherever the double
 sums are exact, to the rounding of one sum elsewhere.  The reference has no counterpart: its FilterToArrays (TimeLayer3D.h:819-924)
@@ -33,6 +33,25 @@ A rigid rotation of rate w gives (0, w^2, 0), a plane shear of rate w (0, 0, w^2
 dilatation of rate w (3 w, -3 w^2 / 2, 3 w^2).  On integer fields of magnitude up to 63 with power-of-two spacings every operation
 is exact in fp32, so fp32 and fp64 agree value for value.
 
+vector WALL_VECTOR / WALL_SCALARS (FS3D_OPT_OUTPUT_WALL 1 / 2; wall_loads is the rule): what the flow does to the wall, on the wall
+cells.  A wall cell B (NODE_BOUND or NODE_VALVE) has the exposed face (d, s), axis d and s = -1 or +1, iff P = B + s*e_d is inside the
+grid, NODE_IN and an INTERIOR row of direction d of the geometry tables (fs3d_tables.h line_kinds: its index along the line is >= 1
+and a cell that is not NODE_IN lies beyond it) -- the faces where the solver imposes B's node value on the line through P.  A
+carrier is a wall cell with at least one exposed face.  With A_x = R(dy)*R(dz), A_y = R(dx)*R(dz), A_z = R(dx)*R(dy), h_d = R(d_d),
+nu = R(v_vis), kappa = R(t_vis), all sums from R(0), the exposed faces in the order x-, x+, y-, y+, z-, z+, every operation
+rounded once in R, nothing fused:
+  area = area + A_d
+  velocity BC of B NOSLIP, each component c != d:   g = (F_c[P] - F_c[B]) / h_d ;  t = nu * g ;     sum_c = sum_c + A_d * t
+  temperature BC of B NOSLIP:                       g = (T[P] - T[B]) / h_d ;      t = kappa * g ;  sum_q = sum_q + A_d * t
+  tau_c = sum_c / area     q = sum_q / area     mag = sqrt((tau_x*tau_x + tau_y*tau_y) + tau_z*tau_z)
+tau is the shear traction the fluid exerts on the wall (fluid moving +x over a wall at rest: tau_x > 0 on either side of the wall),
+q > 0 is heat flowing into the wall; a FREE face adds its area and nothing else (an outflow face is a carrier with zero loads); the
+wall's own value F[B] is read from the sampled layer, so a wall that carries a velocity gives the relative shear.  (a, b, c) is
+tau (WALL_VECTOR) or (mag, q, area) (WALL_SCALARS) on the carriers, 99999 on NODE_OUT cells and 0 on every other cell.  For these
+two modes the C of filter 1 below is the carriers of the box, not its NODE_IN cells: a coarse record shows the mean load of the
+wall cells under each sample.  Not provided: second-order one-sided differences, the wall-normal viscous stress, a pressure-like
+force, x-slabs.
+
 filter 0: the sample is q of the cell (lo_x, lo_y, lo_z).
 filter 1: with C the NODE_IN cells of the sample's box -- C empty: filter 0's sample (a wall value or 99999); else per quantity
 m = (sum over C of (double)q) / (double)|C|, the sum in double in any order, one double division; outT = m and each outV component
@@ -44,12 +63,13 @@ import math
 
 import numpy as np
 
-from .grids import NODE_IN, NODE_OUT
+from .grids import BC_FREE, NODE_BOUND, NODE_IN, NODE_OUT, NODE_VALVE
 
 MISSING_VALUE = 99999.0
 POINT, BOX = 0, 1
 VELOCITY, VORTICITY = 0, 1                                # the values of FS3D_OPT_OUTPUT_VECTOR
 INVARIANTS = 20                                           # FS3D_OPT_OUTPUT_GRADIENT 1, which claims outV in the vector option's place
+WALL_VECTOR, WALL_SCALARS = 221, 222                      # FS3D_OPT_OUTPUT_WALL (id 22) 1 and 2, which claim outV too
 
 
 def boxes(g, o):
@@ -139,8 +159,105 @@ def invariants(type, fields, spacing):
     return res
 
 
-def cell_quantities(type, fields, vector=VELOCITY, spacing=None):
-    """q = (a, b, c, T) per cell from the fields as they are before the call (the stamp is applied here)."""
+def node_arrays(nodes_or_arrays):
+    """(type, bc_vel, bc_temp) of a grids.Nodes object or of a triple of arrays"""
+    n = nodes_or_arrays
+    if hasattr(n, "bc_vel"):
+        return np.asarray(n.type), np.asarray(n.bc_vel), np.asarray(n.bc_temp)
+    if isinstance(n, (tuple, list)) and len(n) == 3:
+        return tuple(np.asarray(a) for a in n)
+    raise ValueError("the wall loads need the node types and both boundary-condition arrays: a Nodes object or (type, bc_vel, bc_temp)")
+
+
+def interior_rows(type, d):
+    """The INTERIOR rows of direction d, indexed (i, j, k): NODE_IN, index along the line >= 1, a cell that is not NODE_IN beyond it"""
+    ty = np.moveaxis(np.asarray(type), d, 2)
+    s = np.arange(ty.shape[2])
+    notin = ty != NODE_IN
+    lst = np.where(notin, s, -1).max(axis=2)
+    return np.moveaxis(~notin & (s >= 1) & (s < lst[..., None]), 2, d)
+
+
+def exposed_faces(type):
+    """Six bool arrays, in the order x-, x+, y-, y+, z-, z+: the wall cells B whose face towards B + s*e_d is exposed"""
+    t = np.asarray(type)
+    wall = (t == NODE_BOUND) | (t == NODE_VALVE)
+    faces = []
+    for d in range(3):
+        inter = np.moveaxis(interior_rows(t, d), d, 0)
+        for s in (-1, 1):
+            f = np.zeros_like(inter)
+            if s < 0:
+                f[1:] = inter[:-1]
+            else:
+                f[:-1] = inter[1:]
+            faces.append(np.moveaxis(f, 0, d) & wall)
+    return faces
+
+
+class WallLoads:
+    """What wall_loads returns: carrier (bool) and tau (three arrays), mag, q, area in the fields' dtype, 0 off the carriers"""
+
+    def __init__(self, carrier, tau, mag, q, area):
+        self.carrier, self.tau, self.mag, self.q, self.area = carrier, tau, mag, q, area
+
+
+def wall_loads(nodes_or_arrays, fields, spacing, nu, kappa):
+    """The wall shear stress and the wall heat flux per wall cell as the rule gives them (module docstring), from the fields U, V, W, T
+    of the sampled layer."""
+    type, bc_vel, bc_temp = node_arrays(nodes_or_arrays)
+    F = [np.asarray(f) for f in fields[:4]]
+    R = F[0].dtype.type
+    h = [R(d) for d in spacing]
+    A = [h[1] * h[2], h[0] * h[2], h[0] * h[1]]
+    nu, kappa = R(nu), R(kappa)
+    vel_ns, temp_ns = bc_vel != BC_FREE, bc_temp != BC_FREE
+    area = np.zeros(type.shape, F[0].dtype)
+    sums = [np.zeros(type.shape, F[0].dtype) for _ in range(4)]
+    faces = exposed_faces(type)
+    with np.errstate(all="ignore"):
+        for n, face in enumerate(faces):
+            d, s = n // 2, (-1, 1)[n % 2]
+            area = np.where(face, area + A[d], area)
+            for c in range(4):
+                if c == d:
+                    continue
+                fp = np.roll(F[c], -s, axis=d)             # F_c[P] at B (the wrapped entries are never on a face)
+                g = (fp - F[c]) / h[d]
+                t = (kappa if c == 3 else nu) * g
+                on = face & (temp_ns if c == 3 else vel_ns)
+                sums[c] = np.where(on, sums[c] + A[d] * t, sums[c])
+        carrier = faces[0] | faces[1] | faces[2] | faces[3] | faces[4] | faces[5]
+        one = np.where(carrier, area, R(1))
+        tau = [np.where(carrier, sums[c] / one, R(0)) for c in range(3)]
+        q = np.where(carrier, sums[3] / one, R(0))
+        mag = np.sqrt((tau[0] * tau[0] + tau[1] * tau[1]) + tau[2] * tau[2])
+    for a in tau + [q, mag, area]:
+        assert a.dtype == F[0].dtype
+    return WallLoads(carrier, tau, mag, q, area)
+
+
+def wall_quantities(nodes_or_arrays, fields, vector, spacing, nu, kappa):
+    """(a, b, c) of the modes WALL_VECTOR and WALL_SCALARS per cell, and the carriers"""
+    type = node_arrays(nodes_or_arrays)[0]
+    w = wall_loads(nodes_or_arrays, fields, spacing, nu, kappa)
+    R = w.mag.dtype.type
+    res = []
+    for comp in (w.tau if vector == WALL_VECTOR else [w.mag, w.q, w.area]):
+        full = np.where(w.carrier, comp, R(0))
+        full[type == NODE_OUT] = R(MISSING_VALUE)
+        res.append(full)
+    return res, w.carrier
+
+
+def cell_quantities(type, fields, vector=VELOCITY, spacing=None, nu=None, kappa=None):
+    """q = (a, b, c, T) per cell from the fields as they are before the call (the stamp is applied here).  The wall modes take a
+    Nodes object or (type, bc_vel, bc_temp) as `type`, and nu and kappa."""
+    if vector in (WALL_VECTOR, WALL_SCALARS):
+        if spacing is None or nu is None or kappa is None:
+            raise ValueError("the wall loads need the grid's spacing (dx, dy, dz), nu and kappa")
+        st = stamp(node_arrays(type)[0], fields)
+        return wall_quantities(type, st, vector, spacing, nu, kappa)[0] + [st[3]]
     st = stamp(type, fields)
     if vector == VELOCITY:
         return st
@@ -151,15 +268,19 @@ def cell_quantities(type, fields, vector=VELOCITY, spacing=None):
     return (vorticity if vector == VORTICITY else invariants)(type, st, spacing) + [st[3]]
 
 
-def layer_output(type, fields, outdims=(0, 0, 0), filter=POINT, vector=VELOCITY, spacing=None, exact_sum=False):
+def layer_output(type, fields, outdims=(0, 0, 0), filter=POINT, vector=VELOCITY, spacing=None, exact_sum=False, nu=None, kappa=None,
+                 members=None):
     """The record of one call: (outV [odx, ody, odz, 3] in the fields' dtype, outT [odx, ody, odz] float64).
     fields: U, V, W, T of `next` before the call, four arrays [dimx, dimy, dimz] of one float dtype (not modified).
     exact_sum: the box sums by math.fsum, so that a mean carries the rounding of its division alone (the yardstick of a bound);
-    otherwise numpy's double sum."""
+    otherwise numpy's double sum.
+    The wall modes take a Nodes object or (type, bc_vel, bc_temp) as `type`, and nu and kappa; the C of their filter 1 is the carriers.
+    members: the C of filter 1 as a bool array, in place of the mode's own (the statistic layers of FS3D_OPT_OUTPUT_WALL 3 and 4)."""
     if filter not in (POINT, BOX):
         raise ValueError("filter is 0 (point) or 1 (box)")
-    type = np.asarray(type)
-    q = cell_quantities(type, fields, vector, spacing)
+    q = cell_quantities(type, fields, vector, spacing, nu, kappa)
+    wall_mode = vector in (WALL_VECTOR, WALL_SCALARS)
+    type = node_arrays(type)[0] if wall_mode else np.asarray(type)
     R = q[0].dtype
     dims = type.shape
     ax = [boxes(g, o) for g, o in zip(dims, outdims)]
@@ -168,7 +289,15 @@ def layer_output(type, fields, outdims=(0, 0, 0), filter=POINT, vector=VELOCITY,
     outT = q[3][sel].astype(np.float64)
     if filter == POINT or all((hi - lo == 1).all() for lo, hi in ax):      # (the mean of one value: (R)((double)q / 1.0) = q)
         return outV, outT
-    fluid = type == NODE_IN
+    if members is not None:
+        fluid = np.asarray(members, bool)
+    elif wall_mode:
+        t3 = type
+        fluid = np.zeros(t3.shape, bool)
+        for f in exposed_faces(t3):
+            fluid |= f
+    else:
+        fluid = type == NODE_IN
     for i, (x0, x1) in enumerate(zip(*ax[0])):
         for j, (y0, y1) in enumerate(zip(*ax[1])):
             for k, (z0, z1) in enumerate(zip(*ax[2])):

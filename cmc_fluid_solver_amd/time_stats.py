@@ -29,6 +29,20 @@ Whole-grid contexts only.  Every set of the option opens a new window.
 Read-out (FS3D_OPT_OUTPUT_GRADIENT 2 with source 1; gradient_layer): Q_U, Q_V, Q_W = R(G_div / double(ng)), R(G_Q / double(ng)),
 R(G_SS / double(ng)) where ng >= 1 and R(0) where ng = 0; Q_T is source 1's.  The record rule then runs on Q as a velocity layer.
 
+Wall sums (FS3D_OPT_TIME_STATS_WALL 1; TimeStats(wall=True, spacing=..., nu=..., kappa=...)): every accumulated step also evaluates
+the wall loads, layer_output.wall_loads, on FS3D_LAYER_CUR in the geometry of that moment, and on each carrier:
+    nw += 1         (uint32)
+    W_x += double(tau_x),  W_y += double(tau_y),  W_z += double(tau_z),  W_mag += double(mag),  W_q += double(q)      each addition rounded once
+The traction is linear in the fields, its magnitude is not: the time-averaged wall shear stress (TAWSS, the mean of |tau|) and the
+oscillatory shear index (OSI) have to be summed step by step.  Whole-grid contexts only.  Every set of the option opens a new window.
+Read-out (FS3D_OPT_OUTPUT_WALL 3 and 4 with source 1; wall_layer), in double with dn = double(nw), nw >= 1:
+    3:  Q_U, Q_V, Q_W = R(W_x / dn), R(W_y / dn), R(W_z / dn)
+    4:  m_c = W_c / dn ;  mm = sqrt((m_x*m_x + m_y*m_y) + m_z*m_z) ;  tawss = W_mag / dn
+        osi = 0.5 * (1 - mm / tawss) where tawss > 0, else 0; 0 where that is negative
+        Q_U, Q_V, Q_W = R(tawss), R(W_q / dn), R(osi)
+and R(0) where nw = 0; Q_T is source 1's.  The record rule then runs on Q as a velocity layer; the C of its filter 1 is the cells with
+nw >= 1 that are not NODE_OUT now.
+
 Read-out, per cell, all in double, each operation rounded once; R is the fields' type:
     n >= 1:  dn = double(n), m_a = S1_a / dn
         source 1, mean            Q = R(m)
@@ -54,12 +68,12 @@ covariance carries the same caveat: S_ab / n and m_a * m_b cancel where the mean
 error about 2 u |m_a m_b|), it is not clamped, and it is exactly 0 for two constant fields whose product is exact in double (every
 pair of fp32 values) as long as n * x_a, n * x_b and n * x_a * x_b are exact.
 
-Not provided: third moments, covariances with the vorticity, second moments of the invariants, gradient sums on x-slabs, a history of cells that are NODE_OUT now, the 2D solver.
+Not provided: third moments, covariances with the vorticity, second moments of the invariants, gradient sums and wall sums on x-slabs, wall sums on a compact list of wall cells, a history of cells that are NODE_OUT now, the 2D solver.
 """
 import numpy as np
 
 from .grids import NODE_IN
-from .layer_output import curl_defined, invariants
+from .layer_output import curl_defined, invariants, node_arrays, wall_loads
 
 MEAN, VARIANCE, FRACTION = 1, 2, 3
 SOURCES = {"next": 0, "mean": MEAN, "variance": VARIANCE, "fraction": FRACTION}
@@ -72,7 +86,7 @@ class TimeStats:
     """One window.  mode 1: first moments; mode 2: first and second moments; cross (mode 2 only, without effect in mode 1): the six
     cross sums as well; every: the stride of the accumulated steps."""
 
-    def __init__(self, shape, mode=2, cross=False, every=1, gradients=False, spacing=None):
+    def __init__(self, shape, mode=2, cross=False, every=1, gradients=False, spacing=None, wall=False, nu=None, kappa=None):
         if mode not in (1, 2):
             raise ValueError("mode is 1 (first moments) or 2 (first and second moments)")
         if int(every) != every or not 1 <= every <= MAX_EVERY:
@@ -80,7 +94,10 @@ class TimeStats:
         if gradients and spacing is None:
             raise ValueError("the gradient sums need the grid's spacing (dx, dy, dz)")
         self.shape, self.mode, self.cross, self.every = tuple(shape), mode, bool(cross) and mode == 2, int(every)
+        if wall and (spacing is None or nu is None or kappa is None):
+            raise ValueError("the wall sums need the grid's spacing (dx, dy, dz), nu and kappa")
         self.gradients, self.spacing = bool(gradients), None if spacing is None else tuple(spacing)
+        self.wall, self.nu, self.kappa = bool(wall), nu, kappa
         self.reset()
 
     def reset(self):
@@ -94,13 +111,18 @@ class TimeStats:
         self.SX = [np.zeros(self.shape, np.float64) for _ in PAIRS] if self.cross else None
         self.ng = np.zeros(self.shape, np.uint32) if self.gradients else None
         self.G = [np.zeros(self.shape, np.float64) for _ in range(3)] if self.gradients else None      # div, Q, S:S
+        self.nw = np.zeros(self.shape, np.uint32) if self.wall else None
+        self.W = [np.zeros(self.shape, np.float64) for _ in range(5)] if self.wall else None           # tau_x, tau_y, tau_z, mag, q
 
     def add(self, fields, types):
-        """One candidate step: fields = U, V, W, T of `cur` after the step, types = the node types of that moment.  Returns whether
-        the stride let it be accumulated."""
+        """One candidate step: fields = U, V, W, T of `cur` after the step, types = the node types of that moment (with wall sums: a
+        Nodes object or (type, bc_vel, bc_temp) of that moment).  Returns whether the stride let it be accumulated."""
         self.candidates += 1
         if (self.candidates - 1) % self.every:
             return False
+        nodes = types
+        if self.wall or hasattr(types, "bc_vel"):
+            types = node_arrays(types)[0]
         fluid = np.asarray(types) == NODE_IN
         assert fluid.shape == self.shape
         self.n[fluid] += np.uint32(1)
@@ -119,8 +141,42 @@ class TimeStats:
                 self.ng[ok] += np.uint32(1)
                 for v in range(3):
                     self.G[v][ok] = self.G[v][ok] + inv[v][ok].astype(np.float64)
+            if self.wall:
+                w = wall_loads(nodes, [np.asarray(f) for f in fields[:4]], self.spacing, self.nu, self.kappa)
+                on = w.carrier
+                self.nw[on] += np.uint32(1)
+                for v, a in enumerate(w.tau + [w.mag, w.q]):
+                    self.W[v][on] = self.W[v][on] + a[on].astype(np.float64)
         self.N += 1
         return True
+
+    def wall_layer(self, cur_fields, which):
+        """Q of FS3D_OPT_OUTPUT_WALL `which`: 3 the time mean of tau, 4 (tawss, mean q, osi), in place of U, V, W (0 where nw = 0)
+        and source 1's T, four arrays of cur_fields' dtype, before the 99999 stamp"""
+        if not self.wall:
+            raise ValueError("the window holds no wall sums")
+        if which not in (3, 4):
+            raise ValueError("which is 3 (the mean traction) or 4 (tawss, the mean heat flux, osi)")
+        if self.N == 0:
+            raise ValueError("the window holds no step")
+        R = np.asarray(cur_fields[0]).dtype
+        seen = self.nw >= 1
+        dn = self.nw[seen].astype(np.float64)
+        with np.errstate(all="ignore"):
+            m = [self.W[v][seen] / dn for v in range(5)]
+            if which == 3:
+                vals = m[:3]
+            else:
+                mm = np.sqrt((m[0] * m[0] + m[1] * m[1]) + m[2] * m[2])
+                tawss = m[3]
+                osi = np.where(tawss > 0.0, 0.5 * (1.0 - mm / np.where(tawss > 0.0, tawss, 1.0)), 0.0)
+                vals = [tawss, m[4], np.where(osi < 0.0, 0.0, osi)]
+            out = []
+            for v in range(3):
+                q = np.zeros(self.shape, R)
+                q[seen] = vals[v].astype(R)
+                out.append(q)
+        return out + [self.layer(MEAN, cur_fields)[3]]
 
     def gradient_layer(self, cur_fields):
         """Q of FS3D_OPT_OUTPUT_GRADIENT 2: the time means of div, Q and S:S in place of U, V, W (0 where ng = 0) and source 1's T,

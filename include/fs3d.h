@@ -172,7 +172,31 @@ enum {
                                  rank fs3d_time_step / fs3d_time_step_async return FS3D_ERR_UNSUPPORTED before any launch, without a swap
                                  and without counting a candidate, while this option and the mode are on.  Any other value:
                                  FS3D_ERR_INVALID */
-    FS3D_OPT_ERR_ORDER = 7   /* summation order of EvalDivError (fs3d_eval_div_error, fs3d_time_step with compute_error).  0 (default): the
+    FS3D_OPT_OUTPUT_WALL = 22, /* what the flow does to the wall, in outV of fs3d_get_layer, fs3d_get_layer_rows and fs3d_get_layer_dev;
+                                 outT is the temperature as ever.  0 (default): nothing changes anywhere, no launch differs.  1: the
+                                 wall shear stress vector tau of the sampled layer (`next`, or the mean layer with
+                                 FS3D_OPT_OUTPUT_SOURCE 1) on the wall cells that carry one; 2: (|tau|, the wall heat flux q, the exposed
+                                 area) on the same cells; 99999 on NODE_OUT cells and 0 on every other cell (the GetLayer section below).
+                                 With FS3D_OPT_OUTPUT_FILTER 1 the mean runs over the carriers of a box, not over its NODE_IN cells.
+                                 3: the time mean of tau, 4: (the time-averaged |tau|, the time mean of q, the oscillatory shear index)
+                                 from the wall sums of FS3D_OPT_TIME_STATS_WALL (the time-statistics section below); both need
+                                 FS3D_OPT_OUTPUT_SOURCE 1 and an open window with those sums and an accumulated step, else the three
+                                 entries return FS3D_ERR_INVALID before any launch.  Non-zero while FS3D_OPT_OUTPUT_VECTOR is 1 or
+                                 FS3D_OPT_OUTPUT_GRADIENT is non-zero: the three entries return FS3D_ERR_INVALID (two options claim
+                                 outV); fs3d_set_option accepts them in any order.  1 or 2 with FS3D_OPT_OUTPUT_SOURCE 2 or 3:
+                                 FS3D_ERR_INVALID.  Non-zero on an x-slab or a member of a group: FS3D_ERR_UNSUPPORTED from the three
+                                 entries, also with FS3D_OPT_OUTPUT_SLABS at 1.  Every refusal comes before any launch and leaves
+                                 destinations, rows and layers untouched.  Any other value: FS3D_ERR_INVALID, the option stays as it was */
+    FS3D_OPT_TIME_STATS_WALL = 23, /* 0 (default): nothing changes anywhere and nothing is allocated.  1: while FS3D_OPT_TIME_STATS is 1 or
+                                 2, every accumulated step also enqueues one kernel, behind the step and the accumulation of the fields,
+                                 that evaluates the wall loads of the new FS3D_LAYER_CUR on the wall cells that carry them and adds tau,
+                                 |tau| and q to five per-cell double sums, with a per-cell count (44 bytes per own cell in two buffers;
+                                 the time-statistics section below).  EVERY call with this option opens a new window; setting 0 also frees
+                                 the wall sums.  Whole-grid contexts only, with the statuses of FS3D_OPT_TIME_STATS_GRAD: on an x-slab the
+                                 value 1 returns FS3D_ERR_UNSUPPORTED, and on a member of a group of more than one rank fs3d_time_step /
+                                 fs3d_time_step_async return FS3D_ERR_UNSUPPORTED before any launch, without a swap and without counting a
+                                 candidate, while this option and the mode are on.  Any other value: FS3D_ERR_INVALID */
+    FS3D_OPT_ERR_ORDER = 7  /* summation order of EvalDivError (fs3d_eval_div_error, fs3d_time_step with compute_error).  0 (default): the
                                  per-cell terms are summed in parallel (per workgroup, then over the workgroups; deterministic, equal to the
                                  CPU path to ~1e-12 relative).  1: they are summed one after the other in cell order, as the loop of
                                  TimeLayer3D::EvalDivError (TimeLayer3D.h:604-628) does -- on the bit-exact kernels the reported error then
@@ -511,7 +535,7 @@ fs3d_status fs3d_last_update_device_ms(fs3d_ctx *ctx, float *ms_out);
  * counts X, Y, Z; [3] BOUND / VALVE cells; [4] NODE_IN cells on no segment of some direction; [5..7] dead lines X, Y, Z;
  * [8..9] shared-column groups flagged uniform in X, Y; [10..11] distinct shared columns in X, Y; [12] an order-independent
  * 64-bit digest of the cell-code table (sum over cells of a mix of cell index and code), computed on the device from the
- * table the sweeps read; [13] the number of device allocations and frees fs3d_upload_nodes / fs3d_update_nodes* / fs3d_fill_fresh_cells* and the accumulators of FS3D_OPT_TIME_STATS (the cross sums of FS3D_OPT_TIME_STATS_CROSS and the gradient sums of FS3D_OPT_TIME_STATS_GRAD among them) have made
+ * table the sweeps read; [13] the number of device allocations and frees fs3d_upload_nodes / fs3d_update_nodes* / fs3d_fill_fresh_cells* and the accumulators of FS3D_OPT_TIME_STATS (the cross sums of FS3D_OPT_TIME_STATS_CROSS the gradient sums of FS3D_OPT_TIME_STATS_GRAD and the wall sums of FS3D_OPT_TIME_STATS_WALL among them) have made
  * since the context was created (the one entry that describes the path taken, not the tables).
  * Measurement and test aid; no reference counterpart. */
 #define FS3D_N_GEOM_INFO 14
@@ -589,7 +613,7 @@ fs3d_status fs3d_get_layer(fs3d_ctx *ctx, void *outV, double *outT,
  * All three entries stamp `next` first and over all owned cells, refuse before any launch (NULL context, destination or rows,
  * negative dims, no nodes yet: FS3D_ERR_INVALID, the context stays usable) and report pending device errors.
  *
- * Filtered and derived records (FS3D_OPT_OUTPUT_FILTER, FS3D_OPT_OUTPUT_VECTOR, FS3D_OPT_OUTPUT_GRADIENT; no reference counterpart; the rule and its numpy
+ * Filtered and derived records (FS3D_OPT_OUTPUT_FILTER, FS3D_OPT_OUTPUT_VECTOR, FS3D_OPT_OUTPUT_GRADIENT, FS3D_OPT_OUTPUT_WALL; no reference counterpart; the rule and its numpy
  * twin: cmc_fluid_solver_amd/layer_output.py).  With either option non-zero the three entries run k_get_layer_box
  * (csrc/kernels_output.hip) in place of the gather, behind the same stamp, through the same staging buffer and copies: `next` is left as a default call leaves it.
  * The box of output index i on an axis of g source cells and o samples is [lo, hi), lo = i*g/o, hi = max(lo + 1, (i+1)*g/o) in
@@ -613,6 +637,22 @@ fs3d_status fs3d_get_layer(fs3d_ctx *ctx, void *outV, double *outT,
  * Everything said of the vector option below holds for FS3D_OPT_OUTPUT_GRADIENT 1 as well: the slab refusals, and with
  * FS3D_OPT_OUTPUT_SLABS the same collective call with the same one ghost plane and type plane per neighbour.  The two options
  * exclude each other: with both non-zero the three entries return FS3D_ERR_INVALID before any launch.
+ * Wall loads (FS3D_OPT_OUTPUT_WALL 1 and 2; whole-grid contexts only; the rule: layer_output.wall_loads).  A wall cell B (NODE_BOUND
+ * or NODE_VALVE) has the exposed face (d, s), axis d and s = -1 or +1, iff P = B + s*e_d is inside the grid, NODE_IN and an INTERIOR
+ * row of direction d of the geometry tables (its index along the line is >= 1 and a cell that is not NODE_IN lies beyond it): the
+ * faces where the solver imposes B's node value on the line through P.  A carrier is a wall cell with at least one exposed face.
+ * With A_x = R(dy)*R(dz), A_y = R(dx)*R(dz), A_z = R(dx)*R(dy), h_d = R(d_d), nu = R(v_vis), kappa = R(t_vis) of fs3d_set_params,
+ * all sums from R(0), the exposed faces in the order x-, x+, y-, y+, z-, z+, every operation rounded once in R, nothing fused:
+ *   area = area + A_d
+ *   velocity BC of B NOSLIP, each component c != d:   g = (F_c[P] - F_c[B]) / h_d ;  t = nu * g ;     sum_c = sum_c + A_d * t
+ *   temperature BC of B NOSLIP:                       g = (T[P] - T[B]) / h_d ;      t = kappa * g ;  sum_q = sum_q + A_d * t
+ *   tau_c = sum_c / area     q = sum_q / area     mag = sqrt((tau_x*tau_x + tau_y*tau_y) + tau_z*tau_z)     (correctly rounded)
+ * tau is the shear traction the fluid exerts on the wall (fluid moving +x over a wall at rest gives tau_x > 0 on either side of the
+ * wall; the wall-normal component of a face's own axis is left out), q > 0 is heat flowing into the wall.  A FREE face adds its
+ * area and nothing else: an outflow face is a carrier with zero loads.  F[B] is read from the sampled layer, so a wall that carries
+ * a velocity gives the relative shear.  (a, b, c) is tau (value 1) or (mag, q, area) (value 2) on the carriers, 99999 on NODE_OUT
+ * cells, 0 on every other cell.  For these two values the C of filter 1 below is the carriers of the box, not its NODE_IN cells.
+ * Not provided: x-slabs; second-order one-sided differences; the wall-normal viscous stress and any pressure-like force.
  * Filter 0: the sample is q of the cell (lo_x, lo_y, lo_z).  Filter 1: with C
  * the NODE_IN cells of the sample's box, the sample is filter 0's where C is empty (a wall value or 99999: walls and the outside
  * show only where a box holds no fluid); else each quantity is m = (sum over C of (double)q) / (double)|C|, summed in double in an
@@ -653,8 +693,8 @@ fs3d_status fs3d_get_layer(fs3d_ctx *ctx, void *outV, double *outT,
  * slab of a larger grid in no group, and fs3d_get_layer on any slab.  The FS3D_ERR_INVALID refusals of the time statistics come
  * before any exchange too.  Between devices and over RCCL the path is compiled and has not been run.
  *
- * Time statistics (FS3D_OPT_TIME_STATS, FS3D_OPT_TIME_STATS_CROSS, FS3D_OPT_TIME_STATS_EVERY, FS3D_OPT_TIME_STATS_GRAD,
- * FS3D_OPT_OUTPUT_SOURCE, FS3D_OPT_OUTPUT_MOMENT, FS3D_OPT_OUTPUT_GRADIENT 2; no reference counterpart; the rule and its numpy twin: cmc_fluid_solver_amd/time_stats.py).  While
+ * Time statistics (FS3D_OPT_TIME_STATS, FS3D_OPT_TIME_STATS_CROSS, FS3D_OPT_TIME_STATS_EVERY, FS3D_OPT_TIME_STATS_GRAD, FS3D_OPT_TIME_STATS_WALL,
+ * FS3D_OPT_OUTPUT_SOURCE, FS3D_OPT_OUTPUT_MOMENT, FS3D_OPT_OUTPUT_GRADIENT 2, FS3D_OPT_OUTPUT_WALL 3 and 4; no reference counterpart; the rule and its numpy twin: cmc_fluid_solver_amd/time_stats.py).  While
  * FS3D_OPT_TIME_STATS is 1 or 2, every fs3d_time_step that returns FS3D_OK and every fs3d_time_step_async is a CANDIDATE step of the
  * open window, counted s = 1, 2, ..; a step that returns FS3D_ERR_DIVERGED does not swap and is no candidate.  With k the value of
  * FS3D_OPT_TIME_STATS_EVERY (default 1), candidate s is ACCUMULATED if and only if (s - 1) % k is 0: the first step of a window always
@@ -683,8 +723,23 @@ fs3d_status fs3d_get_layer(fs3d_ctx *ctx, void *outV, double *outT,
  *    box mean, staging, copies, rows, fs3d_get_layer_info.  Refused with FS3D_ERR_INVALID before any launch, destinations, rows
  *    and layers untouched: a source other than 1, FS3D_OPT_TIME_STATS at 0, FS3D_OPT_TIME_STATS_GRAD at 0 in the open window, a
  *    window without an accumulated step, and FS3D_OPT_OUTPUT_VECTOR 1.
- *  - the window: every fs3d_set_option of FS3D_OPT_TIME_STATS, FS3D_OPT_TIME_STATS_CROSS, FS3D_OPT_TIME_STATS_EVERY or
- *    FS3D_OPT_TIME_STATS_GRAD opens a new
+ *  - wall sums (FS3D_OPT_TIME_STATS_WALL set to 1, whole-grid contexts only): every accumulated step enqueues one more kernel,
+ *    k_time_wall, behind the ones above.  On each carrier of the geometry of that moment, with tau, mag and q the R values of the
+ *    GetLayer section's wall rule on FS3D_LAYER_CUR after the swap:  nw += 1 (uint32),  W_x, W_y, W_z += (double)tau_c,
+ *    W_mag += (double)mag,  W_q += (double)q,  each addition rounded once in double.  The mean of |tau| (TAWSS) and the oscillatory
+ *    shear index cannot be had from the mean field.  44 bytes per own cell in two buffers (the counts; the five sums), allocated by
+ *    the first accumulation that needs them, kept over windows, counted in fs3d_geometry_info entry 13, freed by setting this
+ *    option or FS3D_OPT_TIME_STATS to 0 (after a stream synchronise) and by fs3d_destroy.  Read-out, FS3D_OPT_OUTPUT_WALL 3 or 4
+ *    with FS3D_OPT_OUTPUT_SOURCE 1: the statistic layer is, in double with dn = (double)nw where nw >= 1,
+ *      3:  Q_U, Q_V, Q_W = (R)(W_x / dn), (R)(W_y / dn), (R)(W_z / dn)
+ *      4:  m_c = W_c / dn ;  mm = sqrt((m_x*m_x + m_y*m_y) + m_z*m_z) ;  tawss = W_mag / dn
+ *          osi = tawss > 0 ? 0.5 * (1 - mm / tawss) : 0, 0 where that is negative
+ *          Q_U, Q_V, Q_W = (R)tawss, (R)(W_q / dn), (R)osi
+ *    and R(0) where nw = 0; Q_T is source 1's.  The call then runs unchanged on Q as a velocity layer; with filter 1 C is the cells
+ *    of the box with nw >= 1 that are not NODE_OUT now.  Refused with FS3D_ERR_INVALID before any launch: a source other than 1,
+ *    FS3D_OPT_TIME_STATS at 0, FS3D_OPT_TIME_STATS_WALL at 0 in the open window, a window without an accumulated step.
+ *  - the window: every fs3d_set_option of FS3D_OPT_TIME_STATS, FS3D_OPT_TIME_STATS_CROSS, FS3D_OPT_TIME_STATS_EVERY,
+ *    FS3D_OPT_TIME_STATS_GRAD or FS3D_OPT_TIME_STATS_WALL opens a new
  *    one, N = 0, no candidate yet and all sums zero, whatever the value was.
  *  - memory: 4 + 32 (mode 2: 64; with the cross sums: 112) bytes per own cell, no ghost planes.  Each buffer is allocated by the first
  *    accumulation that needs it (a failed allocation is that step's status: the step itself stands, nothing was accumulated), kept
@@ -721,7 +776,8 @@ fs3d_status fs3d_get_layer(fs3d_ctx *ctx, void *outV, double *outT,
  *    collective call described above; Q then carries a ghost plane on either side (two more planes per field), and the refusals of
  *    this list come before any exchange.
  *  - not provided: third moments; covariances with the vorticity; second moments of the invariants; gradient sums on x-slabs (they
- *    need an exchange of the ghost planes of `cur` per accumulated step, a collective of their own); lambda_2, the eigenvalues
+ *    need an exchange of the ghost planes of `cur` per accumulated step, a collective of their own); wall sums on x-slabs and on a
+ *    compact list of wall cells; lambda_2, the eigenvalues
  *    and the nine components of the gradient; a history of the cells that are NODE_OUT now (they are stamped
  *    as in every record); the 2D solver. */
 fs3d_status fs3d_get_layer_rows(fs3d_ctx *ctx, void *outV, double *outT, int outdimx, int outdimy, int outdimz, int rows[2]);

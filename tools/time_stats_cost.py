@@ -31,6 +31,13 @@ The cases: mode 0, 1, 2, `2x` (mode 2 with the cross sums) and `2x/4` (the same 
     value is fetched once -- 2 of code, 4 of count, 12 of fields, 24 of sums -- (70 apart), so equal time leaves about 29 % for the
     neighbours' planes coming through the caches and for the arithmetic.  Verdict, set before the run: the median of k_time_grad is
     no larger than the median of the mode-1 kernel in that same trace.
+(f) the wall sums (FS3D_OPT_TIME_STATS_WALL; k_time_wall).  `--wall --out profiles/wall_loads_cost.txt` runs, on the box and on the box
+    with an obstacle, ONE child of case 1gw (mode 1 with the gradient sums and the wall sums) under `rocprofv3 --kernel-trace` (alone):
+    the median device time of k_time_wall<float>, k_time_grad<float> and k_time_stats_v4<float, 1> over the same 20 steps, so the
+    three kernels alternate step by step in one process; the fraction of carriers among the cells (from the numpy twin); and, in a
+    child of its own, the time a plain read of a table of the code table's size takes (2 B per cell: torch's int16 sum under
+    device events, back to back -- the table stays in the Infinity Cache -- and with a 1 GiB fill between the reads).  No verdict:
+    nobody has measured this before.
 (d) a kernel variant.  `--tree-lib FILE --skip-bench --note TEXT` runs (b) and (c) on another build of this tree's sources.
 Every GPU child runs under its own `timeout`; the tool stops at the first child that fails.
 """
@@ -56,6 +63,9 @@ COPY_TBS = (5.3, 5.8)
 CASES = {"0": (0, 0, 1), "1": (1, 0, 1), "2": (2, 0, 1), "2x": (2, 1, 1), "2x/4": (2, 1, 4)}
 # --gradients: the cases of (e); a trailing g sets FS3D_OPT_TIME_STATS_GRAD
 GRAD_CASES = {"0": (0, 0, 1), "1": (1, 0, 1), "1g": (1, 0, 1), "2": (2, 0, 1), "2g": (2, 0, 1)}
+# --wall: the case of (f), on both geometries
+WALL_CASES = {"1gw": (1, 0, 1)}
+GEOMETRIES = ("box", "obstacle")
 GRAD_BYTES = 2 + 12 + 2 * (4 + 24)                           # code and fields read once, counts and sums read and written
 # bytes per cell of one accumulation, fp32: code and `cur` read, counts and sums read and written
 BYTES = {"1": 18 + 2 * 36, "2": 18 + 2 * 68, "2x": 18 + 2 * 116}
@@ -70,21 +80,49 @@ def run_child(cmd, env, seconds):
     return r.stdout
 
 
-def child(case, repeats, layers):
+def geometry(name):
+    from cmc_fluid_solver_amd import grids
+    return grids.box(N, h=1.0 / (N - 1)) if name == "box" else grids.box_with_obstacle(N, h=1.0 / (N - 1))
+
+
+def read_child(repeats):
+    """(f): a plain read of 2 B per cell, us per read under device events; prints one JSON line"""
+    import torch
+    t = torch.ones(N ** 3, dtype=torch.int16, device="cuda")
+    fill = torch.empty(1 << 28, dtype=torch.int32, device="cuda")
+    out = {}
+    for name in ("back to back", "after a 1 GiB fill"):
+        us = []
+        for i in range(WARMUP + repeats):
+            if name != "back to back":
+                fill.fill_(i)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            t.sum(dtype=torch.int32)
+            e1.record()
+            torch.cuda.synchronize()
+            us.append(e0.elapsed_time(e1) * 1e3)
+        out[name] = us[WARMUP:]
+    print(json.dumps(out))
+
+
+def child(case, repeats, layers, geom="box"):
     """bench.py's case and loop with the options of `case`; prints one JSON line"""
     import bench
-    from cmc_fluid_solver_amd import capi, grids
+    from cmc_fluid_solver_amd import capi
     dtype = np.float32
-    mode, cross, every = {**CASES, **GRAD_CASES}[case]
-    g = grids.box(N, h=1.0 / (N - 1))
+    mode, cross, every = {**CASES, **GRAD_CASES, **WALL_CASES}[case]
+    g = geometry(geom)
     s = capi.Solver(g, capi.fluid_params(dtype, bench.RE, bench.PR, bench.LAMBDA), dtype)
     s.set_option(capi.OPT_TIME_STATS, mode)
     if cross:                                                  # (a library of the parent commit knows neither option: cases 0, 1, 2 only)
         s.set_option(capi.OPT_TIME_STATS_CROSS, cross)
     if every != 1:
         s.set_option(capi.OPT_TIME_STATS_EVERY, every)
-    if case.endswith("g"):
+    if "g" in case:
         s.set_option(capi.OPT_TIME_STATS_GRAD, 1)
+    if "w" in case:
+        s.set_option(capi.OPT_TIME_STATS_WALL, 1)
 
     def step(i):
         if i % 10 == 0:
@@ -103,7 +141,7 @@ def child(case, repeats, layers):
         s.synchronize()
         ms.append((time.perf_counter() - t0) * 1e3 / STEPS)
     out = {"case": case, "ms_per_step": ms, "cells": N ** 3, "kernels": s.last_sweep_kernels()}
-    if layers and mode and not case.endswith("g"):
+    if layers and mode and "g" not in case:
         od = (54, 54, 52)
         rec = {}
         sources = [(0, 0), (1, 0), (3, 0)] + ([(2, 0)] if mode == 2 else []) + ([(2, 1), (2, 2)] if cross else [])
@@ -151,6 +189,45 @@ def traced(me, case, env):
     return acc, lay
 
 
+def wall_cost(a):
+    """(f) of the module docstring"""
+    from cmc_fluid_solver_amd import layer_output as LO
+    lines = ["wall sums (FS3D_OPT_TIME_STATS_WALL), %d^3 fp32, one MI355X; tools/time_stats_cost.py --wall" % N]
+    if a.note:
+        lines.append(a.note)
+
+    def say(text):
+        print(text, flush=True)
+        lines.append(text)
+    env0 = dict(os.environ)
+    env0.pop("FS3D_LIB_PATH", None)
+    me = [sys.executable, os.path.abspath(__file__)]
+    cells = N ** 3
+    say("device time over the same %d steps of one trace per geometry (rocprofv3 --kernel-trace, case 1gw: the three kernels run in every step), median (min - max) us" % STEPS)
+    for geom in GEOMETRIES:
+        ty = np.asarray(geometry(geom).type)
+        ncar = int(np.logical_or.reduce(LO.exposed_faces(ty)).sum())
+        nwall = int(((ty == 2) | (ty == 3)).sum())
+        tmp = tempfile.mkdtemp(prefix="time_wall_cost_")
+        run_child(["rocprofv3", "--kernel-trace", "--output-format", "csv", "-d", tmp, "-o", "t", "--"] + me +
+                  ["--child", "1gw", "--repeats", "1", "--geometry", geom], env0, 600)
+        found = [os.path.join(dp, f) for dp, _, fs in os.walk(tmp) for f in fs if f.endswith("kernel_trace.csv")]
+        if len(found) != 1:
+            raise SystemExit("time_stats_cost: no kernel trace under " + tmp)
+        say("  %s: %d carriers among %d cells, a fraction of %.5f (%d wall cells)" % (geom, ncar, cells, ncar / cells, nwall))
+        for name in ("k_time_wall<", "k_time_grad<", "k_time_stats_v4<float, 1>"):
+            d = durations(found[0], name)[WARMUP:]
+            if len(d) != STEPS:
+                raise SystemExit("time_stats_cost: %d launches of %s in the trace, %d steps" % (len(d), name, STEPS))
+            say("    %-28s %.1f (%.1f - %.1f) us per accumulated step" % (name.rstrip("<") + ":", statistics.median(d), min(d), max(d)))
+    o = json.loads(run_child(me + ["--child", "read", "--repeats", str(max(a.repeats, 10))], env0, 300).strip().splitlines()[-1])
+    say("a plain read of %d x 2 B (the size of the code table; torch int16 sum, device events), median (min - max) us" % cells)
+    for name, us in o.items():
+        say("    %-20s %.1f (%.1f - %.1f): %s" % (name + ":", statistics.median(us), min(us), max(us), rate_text(2 * cells, statistics.median(us))))
+    with open(a.out, "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--child", default=None, help="internal: run one case in this process")
@@ -161,11 +238,17 @@ def main():
     ap.add_argument("--tree-lib", default=None, help="a build of this tree's sources to measure in place of the tree's own library (a kernel variant)")
     ap.add_argument("--skip-bench", action="store_true", help="leave out (a) and the parent's side of (c)")
     ap.add_argument("--gradients", action="store_true", help="(e): the cost of FS3D_OPT_TIME_STATS_GRAD in place of (b) and (c)")
+    ap.add_argument("--wall", action="store_true", help="(f): the cost of FS3D_OPT_TIME_STATS_WALL, alone: no (a), (b), (c)")
+    ap.add_argument("--geometry", default="box", choices=GEOMETRIES, help="internal: the child's grid")
     ap.add_argument("--note", default="", help="a line for the head of the file (which build this is)")
     ap.add_argument("--out", default=DEFAULT_OUT)
     a = ap.parse_args()
+    if a.child == "read":
+        return read_child(a.repeats)
     if a.child is not None:
-        return child(a.child, a.repeats, a.layers)
+        return child(a.child, a.repeats, a.layers, a.geometry)
+    if a.wall:
+        return wall_cost(a)
     lines = ["time statistics, %d^3 fp32 box (the bench.py case), one MI355X; tools/time_stats_cost.py" % N,
              "bytes per cell count what an accumulation reads and what it writes separately: mode 1 %d, mode 2 %d, with the cross sums %d"
              % (BYTES["1"], BYTES["2"], BYTES["2x"]),
